@@ -5,7 +5,7 @@ A "step" = one pass of the integrator over one batch of synthetic input: ONE fra
 (scenes/cornell-box, the reference's own asset) at 1920x1080, 256 spp, 8 bounces, entirely through the C ABI (ptx_render).
 The scene is resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scene cornell|mesh|atrium|atrium4k|jack]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scene cornell|mesh|atrium|atrium4k|jack] [--dump-outputs DIR] [--full]
 
 N = 1: one process, one GPU. N > 1: one process per GPU over RCCL (torch.distributed "nccl"); when this script is started from a
 plain shell (no WORLD_SIZE) with --gpus N > 1 it starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
@@ -19,12 +19,20 @@ accumulation buffer onto rank 0 inside the timed region. --weak: every rank trac
 mesh (config 3), the 262 k-triangle 24-surface atrium at 1080p / 8 bounces (config 4) and at 4K / 16 bounces (config 5), stand-ins for
 the bunny and Sponza the reference does not ship — shard over N ranks the same way (interleaved tiles + one RCCL reduce).
 
-Prints ONE JSON line on rank 0 (bench contract): value = whole-job Msamples/s; plus
+Prints ONE JSON line on rank 0 (bench contract): value = whole-job Msamples/s, ms_per_step = wall time of one timed step; plus
   roofline     — dominant kernel (k_render_pass), bound by the resource that limits it (VALU issue), with the HBM view beside it
-  psnr_db      — GPU vs CPU oracle on a fixed 1080p tile at equal spp and RNG keys (outside the timed region)
-  cpu_baseline — the UNMODIFIED reference renderer (oracle/_ref/ref_harness) timed on this box's host cores: median of 5 runs at 2 spp
-  configs      — (N = 1, default scene) configs 3 / 4 / 5 and jack-of-blades rendered after the timed loop, outside it: Msamples/s, Mrays/s,
+                 (replayed from the committed PMC profile and the timed steps' own kernel times: no run of its own)
+and, with --full only (each after the timed loop, outside it; --no-psnr / --no-cpu-baseline / --no-configs leave one out):
+  psnr_db      — GPU vs CPU oracle on a fixed 1080p tile at equal spp and RNG keys
+  cpu_baseline — the UNMODIFIED reference renderer (oracle/_ref/ref_harness) timed on the host cores: median of 5 runs at 2 spp
+  configs      — (N = 1, default scene) configs 3 / 4 / 5 and jack-of-blades: Msamples/s, Mrays/s,
                  dominant kernel, its launch time and roofline view (tools/bench_configs.py)
+A plain run (no --full) sets up, warms up, times the steps and prints the line.
+
+--dump-outputs DIR: after the timed loop, rank 0 writes what the last timed step computed: DIR/accum.npy, the float32 [H, W, 4]
+radiance sums of the frame (above 64 MB, as at 4K: DIR/accum_sample.npy, the [k, 4] sums of a fixed seeded sample of pixels, and
+DIR/accum_sample_pixels.npy, their row-major pixel indices as float64), and DIR/rays.npy, float64 [1], the rays that step traced over
+all ranks. The scene, camera and RNG keys are fixed, so the same arguments give the same inputs in every run.
 """
 import argparse
 import glob
@@ -128,6 +136,26 @@ def psnr_vs_oracle(ptx, scene, ctx):
                            f"8-bit RGB after tonemap, GPU vs oracle/pt_oracle.cpp"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21     # 32 MB of sums + 16 MB of indices
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, accum, rays):
+    """--dump-outputs: the accumulation buffer of the last timed step (a seeded pixel sample when it exceeds 64 MB) and its ray count."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = accum.detach().cpu().numpy().astype(np.float32, copy=False)
+    if a.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "accum.npy"), a)
+    else:
+        flat = a.reshape(-1, a.shape[-1])
+        pix = np.sort(np.random.default_rng(DUMP_SEED).choice(len(flat), DUMP_SAMPLE_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "accum_sample.npy"), np.ascontiguousarray(flat[pix]))
+        np.save(os.path.join(out_dir, "accum_sample_pixels.npy"), pix.astype(np.float64))
+    np.save(os.path.join(out_dir, "rays.npy"), np.array([rays], np.float64))
+
+
 def spawn_ranks(args):
     """--gpus N > 1 from a plain shell: run the N ranks as a fresh child job; this process never touches a GPU."""
     import socket
@@ -157,9 +185,12 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--spp", type=int, default=0, help="samples per pixel of the frame (default: 256 for the Cornell frame of the BASELINE config, 16-64 for the others)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-psnr", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs 3 / 4 / 5 block after the timed loop")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed loop, also the PSNR check against the CPU oracle, the CPU baseline and the configs 3 / 4 / 5 block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-psnr", action="store_true", help="with --full: skip the PSNR check")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the configs 3 / 4 / 5 block after the timed loop")
     ap.add_argument("--scene", choices=sorted(SCENES), default="cornell", help="the frame that is timed (default: BASELINE configs[1])")
     ap.add_argument("--shard", choices=("tiles", "samples"), default="tiles",
                     help="how ONE frame is split over N ranks: interleaved 64x64 image tiles (default; BASELINE.json: \"image tiles shard naturally "
@@ -167,6 +198,8 @@ def main():
     ap.add_argument("--spp-per-pass", type=int, default=0, help="samples of every pixel per kernel launch (0 = the library's default)")
     ap.add_argument("--weak", action="store_true", help="weak scaling instead: every rank traces --spp samples of its own")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -235,6 +268,7 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     my_rays = float(sum(s["rays"] for s in stats))
+    last_rays = float(stats[-1]["rays"])                   # this rank's rays in the last timed step (--dump-outputs)
     my_kernel_ms = float(sum(s["kernel_ms"] for s in stats)) / max(args.steps, 1)     # this rank's integrator time per frame: the tile load balance
     rank_kernel_ms = [my_kernel_ms]
     if world > 1:
@@ -246,13 +280,15 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        r = torch.tensor([my_rays], dtype=torch.float64, device=f"cuda:{local_rank}")
+        r = torch.tensor([my_rays, last_rays], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(r, op=dist.ReduceOp.SUM)
-        total_rays = float(r.item())
+        total_rays, last_rays = (float(v) for v in r.tolist())
     else:
         total_rays = my_rays
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, accum, last_rays)
         spp_total = spp * world if mode == "weak" else spp
         samples = float(W) * H * spp_total * args.steps
         launches = sum(s["passes"] for s in stats)
@@ -264,7 +300,7 @@ def main():
         # --- binding resource: VALU issue. Peak = one wave64 VALU instruction per SIMD every 2 cycles (measured: v_add_f32 2.00 cycles per
         # instruction per SIMD at >= 2 waves per SIMD, profiles/round2_valu_issue.txt) at the clock the kernel held; achieved = the kernel's
         # wave64 VALU instructions per second (count per ray from the PMC profile x this run's rays / this run's kernel time).
-        roof = {"bound": "valu", "kernel": "k_render_pass<LDS>" if headline else "see the configs block of the default run (tools/bench_configs.py)",
+        roof = {"bound": "valu", "kernel": "k_render_pass<LDS>" if headline else "see the configs block of a --full run (tools/bench_configs.py)",
                 "avg_launch_ms": round(kernel_ms, 4), "launches": launches,
                 "rays_per_launch": round(rays_per_launch)}
         hbm_alg = rays_per_launch * (B_STREAM + hit_frac * B_ATTR)
@@ -314,16 +350,16 @@ def main():
         if world > 1:
             out["rank_kernel_ms_per_frame"] = rank_kernel_ms      # integrator time per rank (HIP events): how evenly the tiles / samples were dealt
             out["rank_kernel_ms_spread"] = round(max(rank_kernel_ms) / max(min(rank_kernel_ms), 1e-9), 4)
-        if world == 1 and headline and not args.no_configs:
+        if args.full and world == 1 and headline and not args.no_configs:
             # configs 3 / 4 / 5 + the textured asset: same process, after the timed loop and outside it (<= 60 s with the scene builds)
             t_cfg = time.time()
             del accum
             torch.cuda.empty_cache()
             out["configs"] = bench_configs.run_all(ptx, ctx)
             out["configs_seconds"] = round(time.time() - t_cfg, 1)
-        if not args.no_psnr and headline:
+        if args.full and not args.no_psnr and headline:
             out.update(psnr_vs_oracle(ptx, scene, ctx))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if use_dist:

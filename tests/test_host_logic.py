@@ -593,16 +593,19 @@ def test_jpeg_decode_matches_reference_texel_for_texel(ptx, ora, tmp_path, gold_
         np.testing.assert_array_equal(out[:, 3:6].view(np.uint32), np.ascontiguousarray(exp, np.float32).view(np.uint32))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/path-tracer-core/scenes/sponza-new/textures"), reason="the reference tree (38 MB of textures) is not on this machine")
 def test_all_63_sponza_jpegs_decode_like_the_reference(ptx, tmp_path, gold_jpeg):
-    """Every JPEG of scenes/sponza-new/textures (63 baseline 4:4:4 files of 1024 x 1024): SHA-256 of the decoded pixels equals the
-    digest of the compiled reference's decode (fixture). Runs only where the reference tree exists; the fixture travels."""
+    """JPEGs of the reference's scenes/sponza-new/textures (63 baseline 4:4:4 files of 1024 x 1024; the fixture holds the digest of the
+    compiled reference's decode of every one): 16 of them are stored under tests/golden/jpeg_sponza (the 16 smallest apart from the two
+    in tests/golden/jpeg, 4.5 MB), and the SHA-256 of the product's decoded pixels equals the reference's digest for each."""
     from conftest import sha_u8
-    d = "/root/reference/path-tracer-core/scenes/sponza-new/textures"
+    d = os.path.join(ROOT, "tests", "golden", "jpeg_sponza")
     names = [str(n) for n in gold_jpeg["sponza_names"]]
     assert len(names) == 63
-    for n, ref in zip(names[::4], gold_jpeg["sponza_sha"][::4]):          # every fourth file: 16 MB of pixels, ~2 s
-        np.testing.assert_array_equal(sha_u8(_texture_scene(ptx, tmp_path, os.path.join(d, n))), ref, err_msg=n)
+    ref = dict(zip(names, gold_jpeg["sponza_sha"]))
+    files = sorted(os.listdir(d))
+    assert len(files) == 16 and set(files) <= set(names), files
+    for n in files:                                                       # 16 MB of pixels, ~2 s
+        np.testing.assert_array_equal(sha_u8(_texture_scene(ptx, tmp_path, os.path.join(d, n))), ref[n], err_msg=n)
 
 
 def test_jpeg_refusals_and_malformed_files(ptx, tmp_path):

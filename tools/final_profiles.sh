@@ -2,8 +2,8 @@
 # End-of-round measurement set (GPU box, repo root): tools/final_profiles.sh <outdir (relative)>
 set -u
 R=$PWD; REL=${1:-gpurun_out/final}; OUT=$R/$REL; mkdir -p $OUT
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; cat $OUT/bench.json
-(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --no-cpu-baseline --no-psnr > $OUT/bench_under_rocprof.json 2> $OUT/stats.err)
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; cat $OUT/bench.json
+(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --no-cpu-baseline --no-psnr > $OUT/bench_under_rocprof.json 2> $OUT/stats.err)
 find $OUT/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats.csv; head -5 $OUT/kernel_stats.csv
 python tools/bench_scenes.py --spp 64 --level7 > $OUT/scenes.txt 2>&1; grep scene\" $OUT/scenes.txt
 # the many-surface scene on the fused kernel, same box (the queue-based pipeline is its default)

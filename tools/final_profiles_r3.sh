@@ -3,8 +3,8 @@
 # Copy what it writes into profiles/round3_* afterwards (the list is printed at the end).
 set -u
 R=$PWD; OUT=$R/${1:-gpurun_out/final}; mkdir -p $OUT
-timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-(cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --no-cpu-baseline --no-psnr > $OUT/bench_under_rocprof.json 2> $OUT/stats.err); echo "rocprof stats rc=$?"
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+(cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --no-cpu-baseline --no-psnr > $OUT/bench_under_rocprof.json 2> $OUT/stats.err); echo "rocprof stats rc=$?"
 cp $(ls $OUT/stats/*/*_kernel_stats.csv | head -1) $OUT/kernel_stats.csv 2>/dev/null
 tools/pmc_passes.sh ${1:-gpurun_out/final}/pmc_headline 64 > $OUT/pmc_headline.txt 2>&1; echo "pmc headline rc=$?"
 tools/pmc_configs.sh ${1:-gpurun_out/final}/pmc_configs > $OUT/pmc_configs.txt 2>&1; echo "pmc configs rc=$?"

@@ -12,8 +12,8 @@ run() { name=$1; shift; ctr=$1; shift
   echo "$name rc=$?"; }
 run cal_a "$A" $R/tools/bin/valu_issue_bench
 run cal_b "$B" $R/tools/bin/valu_issue_bench
-run k_a "$A" python3 $R/bench.py --steps 1 --warmup 0 --spp $SPP --no-cpu-baseline
-run k_b "$B" python3 $R/bench.py --steps 1 --warmup 0 --spp $SPP --no-cpu-baseline
+run k_a "$A" python3 $R/bench.py --full --steps 1 --warmup 0 --spp $SPP --no-cpu-baseline
+run k_b "$B" python3 $R/bench.py --full --steps 1 --warmup 0 --spp $SPP --no-cpu-baseline
 python3 - <<PY
 import csv,glob,collections
 for d in sorted(glob.glob("$OUT/*/")):
