@@ -772,6 +772,9 @@ __global__ void __launch_bounds__(kWfBlock) k_wf_merge_batch(DevScene S0, Inters
                                                             const uint32_t* __restrict__ t_model_space) {
 	DevScene S = S0;
 	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;
+	// this slice's pairs did not fit the pool: the traverse kernels wrote no result, and the host repeats the slice smaller. The tiles
+	// that did fit still hold result slots and masks; their pair_hit entries are stale (another slice's, another scene's triangle words)
+	if (W.ctl[1]) return;
 	const uint32_t i = blockIdx.x * kWfBlock + threadIdx.x;
 	if (i >= n) return;
 	const size_t gi = first_ray + i;

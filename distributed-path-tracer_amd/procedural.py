@@ -207,3 +207,108 @@ def atrium_scene(detail: int = 5, seed: int = 11):
     ident = [1, 0, 0, 0, 1, 0, 0, 0, 1]
     return dict(model_xform=np.array([[0, 0, 0] + ident], np.float32), model_surf=np.array([[0, 24]], np.int32),
                 surf_range=np.array(sr, np.int32), vertices=verts, triangles=tris, materials=mats, camera=cam, sun=sun13)
+
+
+def _rotation(rng):
+    """Uniformly random rotation matrix (QR of a Gaussian matrix, signs fixed so that det = +1)."""
+    q, r = np.linalg.qr(rng.standard_normal((3, 3)))
+    q = q * np.sign(np.diag(r))
+    if np.linalg.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    return q
+
+
+def _corners(half):
+    return np.array([[sx, sy, sz] for sx in (-half, half) for sy in (-half, half) for sz in (-half, half)], np.float64)
+
+
+def cloud_scene(n_models: int = 1, surfaces_per_model: int = 64, tris_per_surface: int = 16, seed: int = 5,
+                layout: str = "overlap", spaces=None, tri_size: float = 0.08):
+    """Many surfaces of small random triangles, for the per-surface / per-model limits of the kernels (surface masks and
+    deferral lists are 64 lanes or bits wide). n_models models of surfaces_per_model surfaces each (surface u = m *
+    surfaces_per_model + k), tris_per_surface triangles per surface, one directional light.
+    Every model has its own transform (rotation, non-uniform scale, translation); with `spaces` = k, model m takes transform
+    m % k (A, B, A, B, ...: several models share a ray space, not next to each other). The geometry is laid out in WORLD space
+    and stored in the model's local space (inverse transform), so the layout does not depend on the transforms:
+      "overlap":   every surface spreads its triangles over the same cube [-1, 1]^3, with a vertex on each of the cube's corners
+                   (the convex hull of every surface's vertices is the whole cube, so every surface box, in any ray space, contains
+                   every point of it). The camera sits near the centre: every camera ray enters every surface box.
+      "scattered": each surface is a small cluster on a grid in front of the camera: a ray enters a few boxes at most.
+    At 16 triangles per surface, 64-65 surfaces fit one CU's LDS (the fused kernel's LDS route); at 24 the scene is hybrid.
+    -> dict of arrays as plaza_scene (vertices [n, 11]: position, uv, normal, tangent)."""
+    if layout not in ("overlap", "scattered"):
+        raise ValueError(f"layout must be 'overlap' or 'scattered', not {layout!r}")
+    n_surf = n_models * surfaces_per_model
+    if layout == "overlap" and tris_per_surface < 8:
+        raise ValueError("'overlap' needs at least 8 triangles per surface (one at each corner of the cube)")
+    rng = np.random.default_rng(seed)
+    n_xf = n_models if spaces is None else int(spaces)
+    xforms = []
+    for _ in range(n_xf):
+        rot = _rotation(rng)
+        scale = rng.uniform(0.6, 1.6, 3)
+        basis = rot * scale[None, :]                      # world = basis @ local + origin
+        origin = rng.uniform(-0.5, 0.5, 3)
+        xforms.append((basis.astype(np.float32).astype(np.float64), origin.astype(np.float32).astype(np.float64)))
+    if layout == "scattered":
+        cols = int(np.ceil(np.sqrt(n_surf)))
+        rows = (n_surf + cols - 1) // cols
+    verts, tris, sr = [], [], []
+    v0 = t0 = 0
+    for m in range(n_models):
+        basis, origin = xforms[m % n_xf]
+        inv = np.linalg.inv(basis)
+        for k in range(surfaces_per_model):
+            u = m * surfaces_per_model + k
+            if layout == "overlap":
+                centres = rng.uniform(-0.95, 0.95, (tris_per_surface, 3))
+                centres[:8] = _corners(0.95)
+                size = tri_size
+            else:
+                r, c = divmod(u, cols)
+                cell = np.array([(c - (cols - 1) / 2) * 0.5, (r - (rows - 1) / 2) * 0.5, rng.uniform(-0.2, 0.2)])
+                centres = cell + rng.uniform(-0.12, 0.12, (tris_per_surface, 3))
+                size = tri_size
+            p = centres[:, None, :] + rng.uniform(-size, size, (tris_per_surface, 3, 3))
+            if layout == "overlap":                       # corner triangles: one vertex ON the corner, two inside the cube
+                c8 = _corners(1.0)
+                p[:8] = c8[:, None, :] - np.sign(c8)[:, None, :] * rng.uniform(0.0, 2.0 * size, (8, 3, 3))
+                p[:8, 0] = c8
+            p = p.reshape(-1, 3)
+            fn = np.cross(p[1::3] - p[0::3], p[2::3] - p[0::3])
+            fn /= np.maximum(np.linalg.norm(fn, axis=1, keepdims=True), 1e-20)
+            tw = p[1::3] - p[0::3]
+            tw /= np.maximum(np.linalg.norm(tw, axis=1, keepdims=True), 1e-20)
+            v = np.zeros((3 * tris_per_surface, 11), np.float64)
+            v[:, 0:3] = (p - origin) @ inv.T                 # local = inv(basis) (world - origin)
+            v[:, 3:5] = rng.random((3 * tris_per_surface, 2))
+            nl = np.repeat(fn, 3, axis=0) @ basis            # normals by the transpose: inv(basis)^T (basis^T n) = n
+            v[:, 5:8] = nl / np.linalg.norm(nl, axis=1, keepdims=True)
+            tl = np.repeat(tw, 3, axis=0) @ inv.T            # tangents as positions
+            v[:, 8:11] = tl / np.linalg.norm(tl, axis=1, keepdims=True)
+            verts.append(v)
+            tris.append(np.arange(3 * tris_per_surface).reshape(-1, 3))
+            sr.append([v0, len(v), t0, tris_per_surface])
+            v0 += len(v)
+            t0 += tris_per_surface
+    model_xform = np.array([np.concatenate([xforms[m % n_xf][1], xforms[m % n_xf][0].T.ravel()]) for m in range(n_models)], np.float32)
+    model_surf = np.array([[m * surfaces_per_model, surfaces_per_model] for m in range(n_models)], np.int32)
+    mats = np.zeros((n_surf, 11), np.float32)
+    mats[:, 0:3] = 0.3 + 0.6 * rng.random((n_surf, 3))
+    mats[:, 3] = 1.0
+    mats[:, 4] = 0.2 + 0.7 * rng.random(n_surf)
+    mats[:, 5] = rng.random(n_surf) < 0.25
+    mats[:, 9] = 1.45
+    d = np.array([0.3, 0.8, 0.5])                    # towards the sun
+    d /= np.linalg.norm(d)
+    x = np.cross([0, 1, 0], d); x /= np.linalg.norm(x)
+    y = np.cross(d, x)
+    sun13 = np.concatenate([x, y, d, [3.0, 2.8, 2.5], [0.004732]]).astype(np.float32)
+    if layout == "overlap":
+        cam = _look_at([0.02, 0.01, 0.03], [0.3, -0.1, -1.0])
+    else:
+        cam = _look_at([0.1, 0.05, 4.5], [0.0, 0.0, 0.0])
+    cam = np.concatenate([cam, [np.float32(1.0 if layout == "overlap" else 0.8)]]).astype(np.float32)
+    return dict(model_xform=model_xform, model_surf=model_surf, surf_range=np.array(sr, np.int32),
+                vertices=np.concatenate(verts).astype(np.float32), triangles=np.concatenate(tris).astype(np.uint32),
+                materials=mats, camera=cam, sun=sun13)
