@@ -50,9 +50,7 @@ struct DevScene {
 	const float4* hot_lds;
 	uint32_t n_hot, tri_id_mask;
 	const float4* tri_isect; // global-memory traversal: one TriIsect per leaf reference, in leaf order, triangle id in word 10; same allocation as `nodes`, behind them
-	uint64_t geom_bytes;     // bytes of that allocation (nodes + records [+ nodes2])
-	const uint2* nodes2;     // nullptr, or the KD nodes in 2-level blocks (wavefront.hip: BLOCK2; built when PTX_WF_BLOCK2 is set at scene creation), same allocation
-	const uint2* roots2;     // [n_surfaces] root node contents for nodes2
+	uint64_t geom_bytes;     // bytes of that allocation (nodes + records)
 	// resident copy (staged into LDS by MODE_LDS / MODE_HYBRID kernels): nodes, refs and one TriIsect per triangle of the
 	// surfaces that fit, indices rewritten to be local to these arrays (SurfaceRec::lds_root)
 	const uint2* res_nodes;
@@ -154,12 +152,8 @@ struct WfStream {
 constexpr uint32_t kWfIdMask = 0x0FFFFFFFu, kWfZombie = 1u << 31, kWfPending = 1u << 30, kWfRequest = 1u << 29;
 constexpr uint32_t kWfMaxSlab = 1u << 27;   // paths of a slab at most: the whole 128 Mi-path pass (the stream buffers of a slab take 224 bytes per path; ids have 28 bits)
 constexpr int kWfMaxSurfaces = 64;   // surface masks are one 64-bit word
-// persistent 256-thread workgroups of the traverse kernel: as many as can be resident (59 VGPRs and 24 KB of LDS allow 6 per CU; 8 are launched).
-// PTX_WF_GRID=<workgroups per CU> (measurement): fewer leave room for another stream's kernels
-inline int wf_traverse_grid(int n_cu) {
-	static const int per_cu = [] { const char* e = getenv("PTX_WF_GRID"); const int v = e ? atoi(e) : 8; return v >= 1 && v <= 8 ? v : 8; }();
-	return n_cu * per_cu;
-}
+// persistent 256-thread workgroups of the traverse kernel: as many as can be resident (59 VGPRs and 24 KB of LDS allow 6 per CU; 8 are launched)
+inline int wf_traverse_grid(int n_cu) { return n_cu * 8; }
 // a slab's steps run back to back on the device: step s reads its entry count from flow[s] and adds what it emits to flow[s + 1]
 hipError_t launch_wf_generate(const DevScene& S, const RenderParams& P, const WfStream& out, uint32_t cap, uint32_t first, uint32_t n, float4* sample_rad, hipStream_t stream);
 hipError_t launch_wf_step(const DevScene& S, const RenderParams& P, const WfBuffers& W, const WfStream& in, const WfStream& out, uint32_t cap, uint32_t max_in,

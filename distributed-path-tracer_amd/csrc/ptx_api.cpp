@@ -82,16 +82,11 @@ struct ptx_ctx {
 	int n_cu = 0;
 	std::mutex mu;
 	DevBuf queues, sample_rad, counters, spill, stage_a, stage_b, pixel_list, srgb_thr;
-	// workspace of the queue-based pipeline (wavefront.hip). A render advances two slabs of paths side by side, each on its own stream with
-	// its own set: the end of one slab's traverse kernel (a few waves finishing walks of hundreds of dependent fetches) and the host's
-	// wait for its entry count then run under the other slab's kernels. ptx_intersect_batch uses set 0 on the context's stream.
+	// workspace of the queue-based pipeline (wavefront.hip): ptx_render and ptx_intersect_batch run it on the context's stream
 	struct WfSet {
 		DevBuf qent, pair_hit, seg, first, mask, ctl, spill, stream_buf, flow;
 		uint32_t* flow_host = nullptr;   // pinned copy of the flow words (kWfFlowWords)
-		hipStream_t stream = nullptr;
-		hipEvent_t done = nullptr;
-	} wf[2];
-	hipEvent_t wf_main_ev = nullptr;
+	} wf;
 	std::vector<hipEvent_t> events;
 	// per-kernel timing of the last ptx_render that was given a stats pointer (ptx_ctx_set_timing / ptx_ctx_get_timing)
 	bool timing_on = false;
@@ -230,50 +225,10 @@ int upload_scene(ptx_scene* sc) {
 			isect_bytes = h.tri_isect.size() * 48;
 		}
 	}
-	// measurement (PTX_WF_BLOCK2 at scene creation): a second copy of the nodes in 2-level blocks (wavefront.hip: BLOCK2) — a branch at even
-	// depth owns three 16-byte pairs: its children, then the children of each child
-	std::vector<uint2> nodes2, roots2;
-	if (getenv("PTX_WF_BLOCK2") && sc->mode != MODE_LDS && sc->leaf_ordered) {
-		auto W1 = [](uint32_t old_w1, bool blockroot, uint32_t pair) { return (old_w1 & 15u) | (blockroot ? 16u : 0u) | (pair << 5); };
-		auto alloc_block = [&]() { const uint32_t pair = (uint32_t)(nodes2.size() / 2); nodes2.resize(nodes2.size() + 6, make_uint2(0, 0)); return pair; };
-		std::vector<std::pair<uint32_t, uint32_t>> work;   // (old index of an even-depth branch, first pair of its block)
-		for (const SurfaceRec& sr : h.surfaces) {
-			const KdNode r = h.kd_nodes[sr.kd_root];
-			if ((r.w1 & 3u) == KD_LEAF) { roots2.push_back(make_uint2(r.w0, r.w1)); continue; }
-			const uint32_t b = alloc_block();
-			roots2.push_back(make_uint2(r.w0, W1(r.w1, true, b)));
-			work.push_back({sr.kd_root, b});
-			while (!work.empty()) {
-				const auto [old, blk] = work.back();
-				work.pop_back();
-				const KdNode P = h.kd_nodes[old];
-				const uint32_t nk = ((P.w1 >> 2) & 1u) + ((P.w1 >> 3) & 1u), li = P.w1 >> 4;
-				for (uint32_t i = 0; i < nk; i++) {
-					const KdNode K = h.kd_nodes[li + i];
-					if ((K.w1 & 3u) == KD_LEAF) { nodes2[2 * (size_t)blk + i] = make_uint2(K.w0, K.w1); continue; }
-					const uint32_t kp = blk + 1 + i;   // the pair of K's children inside P's block
-					nodes2[2 * (size_t)blk + i] = make_uint2(K.w0, W1(K.w1, false, kp));
-					const uint32_t ng = ((K.w1 >> 2) & 1u) + ((K.w1 >> 3) & 1u), gi = K.w1 >> 4;
-					for (uint32_t j = 0; j < ng; j++) {
-						const KdNode G = h.kd_nodes[gi + j];
-						if ((G.w1 & 3u) == KD_LEAF) { nodes2[2 * (size_t)kp + j] = make_uint2(G.w0, G.w1); continue; }
-						const uint32_t b2 = alloc_block();
-						nodes2[2 * (size_t)kp + j] = make_uint2(G.w0, W1(G.w1, true, b2));
-						work.push_back({gi + j, b2});
-					}
-				}
-			}
-		}
-	}
 	const size_t isect_pad = (std::max<size_t>(isect_bytes, 16) + 255) & ~(size_t)255;
-	const size_t n2_bytes = nodes2.size() * 8 + (nodes2.empty() ? 0 : 64), r2_bytes = (roots2.size() * 8 + 255) & ~(size_t)255;
-	const size_t geom_total = nodes_bytes + isect_pad + (nodes2.empty() ? 0 : n2_bytes + r2_bytes);
+	const size_t geom_total = nodes_bytes + isect_pad;
 	HIP_TRY(sc->d_nodes.ensure(geom_total));
 	HIP_TRY(hipMemsetAsync(sc->d_nodes.p, 0, geom_total, c->stream));
-	if (!nodes2.empty()) {
-		HIP_TRY(hipMemcpyAsync((char*)sc->d_nodes.p + nodes_bytes + isect_pad, nodes2.data(), nodes2.size() * 8, hipMemcpyHostToDevice, c->stream));
-		HIP_TRY(hipMemcpyAsync((char*)sc->d_nodes.p + nodes_bytes + isect_pad + n2_bytes, roots2.data(), roots2.size() * 8, hipMemcpyHostToDevice, c->stream));
-	}
 	if (!h.kd_nodes.empty()) HIP_TRY(hipMemcpyAsync(sc->d_nodes.p, h.kd_nodes.data(), h.kd_nodes.size() * 8, hipMemcpyHostToDevice, c->stream));
 	if (isect_bytes)
 		HIP_TRY(hipMemcpyAsync((char*)sc->d_nodes.p + nodes_bytes, sc->leaf_ordered ? (const void*)leaf.data() : (const void*)h.tri_isect.data(), isect_bytes, hipMemcpyHostToDevice, c->stream));
@@ -327,8 +282,6 @@ int upload_scene(ptx_scene* sc) {
 	d.tris = (const float4*)sc->d_tris.p;
 	d.tri_isect = isect_bytes ? (const float4*)((const char*)sc->d_nodes.p + nodes_bytes) : nullptr;
 	d.geom_bytes = (uint64_t)geom_total;
-	d.nodes2 = nodes2.empty() ? nullptr : (const uint2*)((const char*)sc->d_nodes.p + nodes_bytes + isect_pad);
-	d.roots2 = nodes2.empty() ? nullptr : (const uint2*)((const char*)sc->d_nodes.p + nodes_bytes + isect_pad + n2_bytes);
 	d.res_nodes = (const uint2*)sc->d_res_nodes.p;
 	d.res_refs = (const uint32_t*)sc->d_res_refs.p;
 	d.res_tris = (const float4*)sc->d_res_tris.p;
@@ -416,13 +369,9 @@ static void ctx_release(ptx_ctx* c) {
 	for (hipEvent_t ev : c->events) (void)hipEventDestroy(ev);
 	for (hipEvent_t ev : c->step_events) (void)hipEventDestroy(ev);
 	c->queues.release(); c->spill.release(); c->sample_rad.release(); c->counters.release(); c->stage_a.release(); c->stage_b.release(); c->pixel_list.release(); c->srgb_thr.release();
-	for (auto& w : c->wf) {
-		for (DevBuf* b : {&w.qent, &w.pair_hit, &w.seg, &w.first, &w.mask, &w.ctl, &w.spill, &w.stream_buf, &w.flow}) b->release();
-		if (w.flow_host) { (void)hipHostFree(w.flow_host); w.flow_host = nullptr; }
-		if (w.done) { (void)hipEventDestroy(w.done); w.done = nullptr; }
-		if (w.stream) { (void)hipStreamDestroy(w.stream); w.stream = nullptr; }
-	}
-	if (c->wf_main_ev) { (void)hipEventDestroy(c->wf_main_ev); c->wf_main_ev = nullptr; }
+	ptx_ctx::WfSet& w = c->wf;
+	for (DevBuf* b : {&w.qent, &w.pair_hit, &w.seg, &w.first, &w.mask, &w.ctl, &w.spill, &w.stream_buf, &w.flow}) b->release();
+	if (w.flow_host) { (void)hipHostFree(w.flow_host); w.flow_host = nullptr; }
 	(void)hipStreamDestroy(c->stream);
 	delete c;
 }
@@ -666,6 +615,12 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 
 namespace {
 
+int32_t max_surfaces_per_model(const ptx_scene* sc) {
+	int32_t m = 0;
+	for (const ModelRec& mr : sc->host.models) m = std::max(m, mr.n_surfaces);
+	return m;
+}
+
 // Scenes the queue-based pipeline (wavefront.hip) takes: trees in global memory, a model of many surfaces (where the fused kernel's
 // waves run nearly empty), at most 64 surfaces (one mask word per ray). PTX_WAVEFRONT=0/1 overrides the choice (measurement).
 // Pair space is a pool sized from DEMAND: `wf_pairs_per_ray` of the scene (what its rays were seen to need; before the first
@@ -677,14 +632,18 @@ namespace {
 // pass as ONE slab — 490-495 (profiles/round3_surface_order.txt): every step of a slab ends with a few waves finishing walks of
 // hundreds of dependent fetches, and a larger slab has fewer such ends per path (jack-of-blades, whose steps after the first are small:
 // 2300 -> 2850 Msamples/s from 66 M- to 133 M-path slabs). The default takes 1 Gi pairs (48 GB of a 288 GB device) unless that is more
-// than a sixth of the free memory; what is ALLOCATED follows the scene's demand (ptx_render: alloc_pairs).
+// than a sixth of the free memory; what is ALLOCATED follows the scene's demand (wf_allocate).
 constexpr uint64_t kWfPoolPairs = 1024ull << 20;
 constexpr uint64_t kWfBatchPairs = 256ull << 20;   // ... of a batch-intersect slice at most (12 GB); sized by the batch
 constexpr uint32_t kWfFlowWords = 64, kWfFlowRays = 58 /* 64-bit */, kWfFlowPeak = 60, kWfFlowOverflow = 63, kWfMaxRound = 56;   // flow words: [s] entries of step s of the round, then the pool's peak demand and the overflow word
+// The traverse kernel reads leaf-ordered records at 32-bit offsets from the nodes (k_wf_traverse2), so a scene whose global-memory copy
+// holds one record per triangle (PTX_LEAF_ORDER=0, measurement) or takes more than 4 GB goes to the fused kernel: both pipelines give
+// bitwise equal results, and no test or benchmark scene reaches either case.
 bool wf_eligible(const ptx_scene* sc) {
 	const size_t n_surf = sc->host.surfaces.size();
 	if (n_surf == 0 || n_surf > (size_t)kWfMaxSurfaces) return false;
-	return sc->mode != MODE_LDS && sc->dev.tri_isect;   // LDS-resident scenes keep no global-memory copy of the traversal records
+	if (sc->mode == MODE_LDS || !sc->dev.tri_isect) return false;   // LDS-resident scenes keep no global-memory copy of the traversal records
+	return sc->leaf_ordered && sc->dev.geom_bytes <= 0xFFFFFFFFull;
 }
 // Which pipeline renders a scene. The fused kernel is at its best when the geometry rays meet is in LDS; the queues, when it is in
 // global memory: lanes are compacted per (ray, surface) pair and more waves cover the fetch latency. Two static signs of the latter:
@@ -696,9 +655,7 @@ int pipeline_choice(const ptx_scene* sc) {
 	if (!wf_eligible(sc)) return 0;
 	if (const char* e = getenv("PTX_WAVEFRONT")) return e[0] == '1' ? 1 : 0;
 	if (getenv("PTX_FORCE_GLOBAL") || getenv("PTX_NO_HYBRID")) return 0;
-	int32_t max_per_model = 0;
-	for (const ModelRec& mr : sc->host.models) max_per_model = std::max(max_per_model, mr.n_surfaces);
-	return (max_per_model >= 8 || sc->lds_area_share < 0.35) ? 1 : 0;
+	return (max_surfaces_per_model(sc) >= 8 || sc->lds_area_share < 0.35) ? 1 : 0;
 }
 bool use_wavefront(const ptx_scene* sc) { return pipeline_choice(sc) == 1; }
 double wf_ratio_guess(const ptx_scene* sc) {
@@ -707,9 +664,9 @@ double wf_ratio_guess(const ptx_scene* sc) {
 	if (const char* e = getenv("PTX_WF_RATIO_GUESS")) return std::max(0.01, atof(e));   // tests: a guess that is too low exercises the overflow path
 	return std::min(n_surf, 4.0);
 }
-// buffers of one workspace set for `rays` rays per step, a pool of `pool` pairs and `steps` control blocks
-hipError_t wf_workspace(ptx_ctx* c, int set, size_t rays, size_t pool, size_t n_surf, size_t steps, WfBuffers& W) {
-	ptx_ctx::WfSet& w = c->wf[set];
+// buffers of the workspace for `rays` rays per step, a pool of `pool` pairs and `steps` control blocks
+hipError_t wf_workspace(ptx_ctx* c, size_t rays, size_t pool, size_t n_surf, size_t steps, WfBuffers& W) {
+	ptx_ctx::WfSet& w = c->wf;
 	const size_t tiles = (rays + kWfTile - 1) / kWfTile;
 	hipError_t e;
 	if ((e = w.qent.ensure(pool * 32)) != hipSuccess) return e;
@@ -734,9 +691,289 @@ hipError_t wf_workspace(ptx_ctx* c, int set, size_t rays, size_t pool, size_t n_
 }
 size_t wf_workspace_bytes(const ptx_ctx* c) {
 	size_t b = 0;
-	for (const auto& w : c->wf)
-		for (const DevBuf* d : {&w.qent, &w.pair_hit, &w.seg, &w.first, &w.mask, &w.ctl, &w.spill, &w.stream_buf, &w.flow}) b += d->cap;
+	const ptx_ctx::WfSet& w = c->wf;
+	for (const DevBuf* d : {&w.qent, &w.pair_hit, &w.seg, &w.first, &w.mask, &w.ctl, &w.spill, &w.stream_buf, &w.flow}) b += d->cap;
 	return b;
+}
+
+// The order in which a pass enumerates its pixels (path id -> pixel). Per-sample radiance is keyed by (pixel, sample), so the order
+// changes no result — only which rays sit next to each other in a wave and in a classify tile. "tiled": 8 x 8 pixel blocks (one
+// wave of camera rays) inside 32 x 32 blocks (one classify tile) — coherent rays enter the same surfaces and walk the same nodes;
+// PTX_PIXEL_ORDER=linear|tiled overrides (measurement). Interleaved tile sharding: only the pixels of this shard's image tiles.
+// The list lives on the device, cached on the context by its key. Without sharding or tiling there is none: `d_pixels` stays nullptr
+// and `n_pixels` the rectangle's pixels.
+int pixel_list(ptx_ctx* c, const ptx_scene* sc, const ptx_render_cfg* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint64_t& n_pixels,
+               const uint32_t*& d_pixels) {
+	const bool sharded = cfg->shard_count > 1;
+	bool tiled = use_wavefront(sc);   // measured: profiles/round3_pixel_order.txt
+	if (const char* e = getenv("PTX_PIXEL_ORDER")) tiled = e[0] == 't';
+	n_pixels = (uint64_t)w * h;
+	d_pixels = nullptr;
+	if (!sharded && !tiled) return PTX_OK;
+	const uint32_t ts = sharded ? (cfg->shard_tile ? cfg->shard_tile : 64u) : 0u;
+	const uint32_t key[9] = {cfg->W, cfg->H, x0, y0, w, h, sharded ? cfg->shard_index : 0u, (sharded ? cfg->shard_count : 1u) | (tiled ? 0x80000000u : 0u), ts};
+	if (memcmp(key, c->list_key, sizeof key) != 0 || !c->pixel_list.p) {
+		std::vector<uint32_t> list;
+		// the pixels of the image rectangle [xa, xb) x [ya, yb): rows, or 8 x 8 blocks inside 32 x 32 blocks anchored at the image origin
+		auto add_rect = [&](uint32_t xa, uint32_t ya, uint32_t xb, uint32_t yb) {
+			if (!tiled) {
+				for (uint32_t y = ya; y < yb; y++)
+					for (uint32_t x = xa; x < xb; x++) list.push_back((y - y0) * w + (x - x0));
+				return;
+			}
+			for (uint32_t by = ya / 32; by <= (yb - 1) / 32; by++)
+				for (uint32_t bx = xa / 32; bx <= (xb - 1) / 32; bx++)
+					for (uint32_t sy = 0; sy < 4; sy++)
+						for (uint32_t sx = 0; sx < 4; sx++)
+							for (uint32_t y = by * 32 + sy * 8; y < by * 32 + sy * 8 + 8; y++)
+								for (uint32_t x = bx * 32 + sx * 8; x < bx * 32 + sx * 8 + 8; x++)
+									if (x >= xa && x < xb && y >= ya && y < yb) list.push_back((y - y0) * w + (x - x0));
+		};
+		if (!sharded) add_rect(x0, y0, x0 + w, y0 + h);
+		else {
+			const uint32_t tiles_x = (cfg->W + ts - 1) / ts;
+			for (uint32_t ty = y0 / ts; ty <= (y0 + h - 1) / ts; ty++)
+				for (uint32_t tx = x0 / ts; tx <= (x0 + w - 1) / ts; tx++) {
+					if ((uint64_t)(ty * (uint64_t)tiles_x + tx) % cfg->shard_count != cfg->shard_index) continue;
+					add_rect(std::max(tx * ts, x0), std::max(ty * ts, y0), std::min((tx + 1) * ts, x0 + w), std::min((ty + 1) * ts, y0 + h));
+				}
+		}
+		// a previous render with stats == NULL and a device buffer returns without a sync (ptx.h): its generate / resolve kernels may
+		// still be reading the list this call is about to replace, and the context's stream is non-blocking (not ordered with the
+		// NULL stream a plain hipMemcpy would use) — drain it first, then upload on the same stream
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		HIP_TRY(c->pixel_list.ensure(std::max<size_t>(list.size() * 4, 16)));
+		if (!list.empty()) {
+			HIP_TRY(hipMemcpyAsync(c->pixel_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, c->stream));
+			HIP_TRY(hipStreamSynchronize(c->stream));   // `list` is a local
+		}
+		memcpy(c->list_key, key, sizeof key);
+		c->list_len = (uint32_t)list.size();
+	}
+	n_pixels = c->list_len;
+	d_pixels = (const uint32_t*)c->pixel_list.p;
+	return PTX_OK;
+}
+
+// samples of every pixel per launch: enough paths to fill the chip many times over, bounded workspace; 0: one sample of every pixel
+// is already too many paths for one pass
+uint32_t pass_size(const ptx_render_cfg* cfg, uint64_t n_pixels) {
+	uint32_t pass_spp = cfg->spp_per_pass;
+	if (pass_spp == 0) {
+		const uint64_t target_paths = 128ull << 20;   // 64 spp of a 1080p frame: 2 GB of per-sample radiance; fewer, longer launches (measured: 8 -> 64 spp per launch = +11 %)
+		pass_spp = (uint32_t)std::max<uint64_t>(1, target_paths / n_pixels);
+	}
+	pass_spp = std::min(pass_spp, cfg->spp);
+	while ((uint64_t)pass_spp * n_pixels > 0xFFFFFFFFull) pass_spp--;  // path ids are 32-bit
+	return pass_spp;
+}
+
+// The queue-based pipeline of one render: the pair pool, the slab size and the workspace sized for them
+struct WfPlan {
+	uint64_t pool_pairs = kWfPoolPairs;   // pair budget
+	uint64_t pass_paths = 0;              // paths of a full pass
+	uint32_t round = 0;                   // steps enqueued before the host reads the flow words again
+	uint32_t slab = 0;                    // paths of a slab: never above what the buffers were sized for
+	WfBuffers W{};
+};
+// ptx_ctx_set_timing on: the step events used so far, and the traverse waves' run times against waves x longest run
+struct WfClock {
+	size_t n_step_ev = 0;
+	double busy = 0, all = 0;
+};
+
+// paths of a slab: the pool must hold the pairs of its busiest step — a step classifies two rays per path (extend + shadow)
+uint32_t wf_slab_cap(const ptx_scene* sc, const WfPlan& plan) {
+	const double per_path = 2.0 * wf_ratio_guess(sc);
+	const uint64_t by_pool = (uint64_t)std::max(65536.0, (double)plan.pool_pairs / per_path);
+	static const uint64_t max_slab = [] { const char* e = getenv("PTX_WF_MAX_SLAB_M"); return e ? std::min<uint64_t>((uint64_t)kWfIdMask, strtoull(e, nullptr, 10) << 20) : (uint64_t)kWfMaxSlab - 1; }();   // measurement
+	const uint64_t cap = std::min<uint64_t>({plan.pass_paths, max_slab, by_pool});
+	const uint64_t n_slabs = (plan.pass_paths + cap - 1) / cap;   // slabs of equal size rather than full ones and a remainder
+	return (uint32_t)((plan.pass_paths + n_slabs - 1) / n_slabs);
+}
+
+// The workspace for slabs of `plan.slab` paths. The pool that is allocated: what the slab needs at the pairs per path this scene is
+// expected to ask for (+ 10 %), not the whole budget — a scene whose rays enter few boxes (jack-of-blades: 0.3 pairs per ray) holds
+// 2 GB of pairs, not 18 (in steps of 64 Mi pairs: the ratio learnt from one frame must not move the allocation by a few per cent in the next)
+hipError_t wf_allocate(ptx_ctx* c, const ptx_scene* sc, WfPlan& plan) {
+	const uint64_t want_pairs = (uint64_t)((double)plan.slab * 2.0 * wf_ratio_guess(sc) * 1.1), step = want_pairs > (128ull << 20) ? (64ull << 20) : (16ull << 20);
+	const uint64_t alloc_pairs = std::min<uint64_t>(plan.pool_pairs, std::max<uint64_t>(16ull << 20, (want_pairs + step - 1) / step * step));
+	ptx_ctx::WfSet& w = c->wf;
+	if (w.qent.cap > 4 * alloc_pairs * 32) { w.qent.release(); w.pair_hit.release(); }   // held from a much hungrier scene: give it back
+	hipError_t e = wf_workspace(c, 2 * (size_t)plan.slab, alloc_pairs, sc->host.surfaces.size(), plan.round, plan.W);
+	if (e != hipSuccess) return e;
+	plan.W.ray_counter = (unsigned long long*)((uint32_t*)w.flow.p + kWfFlowRays);   // rays of the slab: added to the total once the slab is through (an overflowing attempt is not counted)
+	return w.stream_buf.ensure((size_t)plan.slab * 14 * sizeof(float4));
+}
+
+// The plan of a render of passes of `pass_paths` paths. `fits` = false: the device cannot spare even a small pool, the fused kernel renders.
+int wf_plan(ptx_ctx* c, const ptx_scene* sc, uint64_t pass_paths, uint32_t bounces, WfPlan& plan, bool& fits) {
+	plan.pass_paths = pass_paths;
+	// steps enqueued back to back before the host looks at the flow words again. The grids of a round are sized for the entries the
+	// slab had when the round began (entries only ever get fewer): short rounds keep the later steps' grids close to what is alive —
+	// the shade kernel's workgroups beyond the entry count only read it and leave, but a 66 M-path slab has 259 K of them per launch —
+	// at the price of one host round trip (tens of microseconds) per round. PTX_WF_ROUND overrides (measurement).
+	uint32_t round = 3;
+	if (const char* e = getenv("PTX_WF_ROUND")) round = (uint32_t)std::max(1, atoi(e));
+	plan.round = (uint32_t)std::min<uint64_t>({(uint64_t)round, (uint64_t)bounces + 1u, (uint64_t)kWfMaxRound});
+	size_t free_b = 0, total_b = 0;
+	if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+		const uint64_t held = wf_workspace_bytes(c);   // what the context already holds counts as available: the same answer frame after frame
+		plan.pool_pairs = std::min<uint64_t>(plan.pool_pairs, std::max<uint64_t>(16ull << 20, (free_b + held) / 4 / 48));
+	} else (void)hipGetLastError();
+	if (const char* e = getenv("PTX_WF_PAIRS_M")) plan.pool_pairs = std::max<uint64_t>(1, strtoull(e, nullptr, 10)) << 20;   // measurement: pool size in Mi pairs
+	plan.pool_pairs = std::min<uint64_t>(plan.pool_pairs, 0xFFFFFFFFull);
+	// when the device cannot spare the pool: a smaller one (smaller slabs), and below 8 Mi pairs the fused kernel
+	for (;;) {
+		plan.slab = wf_slab_cap(sc, plan);
+		const hipError_t e = wf_allocate(c, sc, plan);
+		if (e == hipSuccess) { fits = true; return PTX_OK; }
+		if (e != hipErrorOutOfMemory) return set_err(PTX_ERR_HIP, std::string("queue-based pipeline workspace: ") + hipGetErrorString(e));
+		(void)hipGetLastError();
+		ptx_ctx::WfSet& w = c->wf;
+		for (DevBuf* b : {&w.qent, &w.pair_hit, &w.seg, &w.first, &w.mask, &w.stream_buf}) b->release();
+		plan.pool_pairs /= 2;
+		if (plan.pool_pairs < (8ull << 20)) { fits = false; return PTX_OK; }
+	}
+}
+
+// The scene's first frame has just told what its rays need: bring the workspace to the size the NEXT frame of this kind will ask
+// for now (a larger slab, a smaller or larger pool), inside the frame that pays for allocations anyway
+int wf_resize(ptx_ctx* c, const ptx_scene* sc, WfPlan& plan) {
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	plan.slab = wf_slab_cap(sc, plan);
+	if (wf_allocate(c, sc, plan) != hipSuccess) (void)hipGetLastError();   // not fatal: the next frame sizes its workspace itself
+	return PTX_OK;
+}
+
+// four events per step (before classify / traverse / shade, after), or nullptr when timing is off
+hipEvent_t* step_events(ptx_ctx* c, WfClock* clk) {
+	if (!clk) return nullptr;
+	while (c->step_events.size() < clk->n_step_ev + 4) {
+		hipEvent_t ev;
+		if (hipEventCreate(&ev) != hipSuccess) return nullptr;
+		c->step_events.push_back(ev);
+	}
+	clk->n_step_ev += 4;
+	return &c->step_events[clk->n_step_ev - 4];
+}
+
+// One pass through the queue-based pipeline (wavefront.hip), in slabs of at most `plan.slab` paths. The steps of a slab are enqueued back
+// to back, `plan.round` at a time: every kernel takes its entry count from the device (flow words), and the host reads them back once
+// per round — whether paths are left (pass-through materials can outlive bounces + 1 steps), whether some step's pairs overflowed the
+// pool, and the peak demand that sizes the next slab. Adds the rays traced (slabs that went through) to `rays`.
+int wf_pass(ptx_ctx* c, ptx_scene* sc, const RenderParams& P, float4* sample_rad, bool stats, WfClock* clk, WfPlan& plan, unsigned long long& rays) {
+	ptx_ctx::WfSet& ws = c->wf;
+	uint32_t* const flow = (uint32_t*)ws.flow.p;
+	uint64_t first = 0;
+	while (first < P.n_paths) {
+		plan.slab = std::min(plan.slab, wf_slab_cap(sc, plan));
+		const uint32_t cap = plan.slab;
+		float4* const base = (float4*)ws.stream_buf.p;   // the slab's two stream buffers, `cap` entries per array
+		const WfStream st[2] = {WfStream{base, base + 8 * (size_t)cap}, WfStream{base + 4 * (size_t)cap, base + 11 * (size_t)cap}};
+		const uint32_t slab_first = (uint32_t)first, n_slab = (uint32_t)std::min<uint64_t>(cap, P.n_paths - first);
+		HIP_TRY(launch_wf_generate(sc->dev, P, st[0], cap, slab_first, n_slab, sample_rad, c->stream));
+		HIP_TRY(hipMemsetAsync(ws.flow.p, 0, kWfFlowWords * 4, c->stream));
+		HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ws.flow.p, (int)n_slab, 1, c->stream));   // flow[0] = entries of step 0
+		bool live = P.bounces > 0, overflow = false;
+		uint32_t n_round = n_slab;   // entries when the current round began
+		int cur = 0;
+		uint64_t peak = 0;
+		while (live) {
+			HIP_TRY(hipMemsetAsync(ws.ctl.p, 0, (size_t)plan.round * kWfCtlWords * 4, c->stream));
+			HIP_TRY(hipMemsetAsync(flow + 1, 0, (size_t)plan.round * 4, c->stream));
+			for (uint32_t s = 0; s < plan.round; s++) {
+				WfBuffers W = plan.W;
+				W.ctl = (uint32_t*)ws.ctl.p + (size_t)s * kWfCtlWords;
+				W.n_in = flow + s;
+				W.wave_clock = clk ? 1u : 0u;
+				HIP_TRY(launch_wf_step(sc->dev, P, W, st[cur], st[cur ^ 1], cap, n_round, slab_first, flow + s + 1, sample_rad, c->n_cu, c->stream, step_events(c, clk)));
+				cur ^= 1;
+			}
+			HIP_TRY(hipMemcpyAsync(ws.flow_host, flow, kWfFlowWords * 4, hipMemcpyDeviceToHost, c->stream));
+			HIP_TRY(hipStreamSynchronize(c->stream));
+			peak = std::max<uint64_t>(peak, ws.flow_host[kWfFlowPeak]);
+			if (clk) {   // the traverse waves' own clocks of this round's steps (wavefront.hip: kWfCtlClock)
+				for (uint32_t s = 0; s < plan.round; s++) {
+					uint32_t ck[4];
+					HIP_TRY(hipMemcpy(ck, (uint32_t*)ws.ctl.p + (size_t)s * kWfCtlWords + kWfCtlClock, sizeof ck, hipMemcpyDeviceToHost));
+					clk->busy += (double)(((uint64_t)ck[1] << 32) | ck[0]);
+					clk->all += (double)ck[2] * (double)ck[3];
+				}
+			}
+			if (ws.flow_host[kWfFlowOverflow]) { overflow = true; break; }
+			n_round = ws.flow_host[plan.round];
+			live = n_round != 0;
+			if (live) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ws.flow.p, (int)n_round, 1, c->stream));   // next round: flow[0] = what this one left
+		}
+		// what a ray of this scene needs, from the busiest step of the slab (two rays per path and step)
+		if (peak && n_slab) sc->wf_pairs_per_ray = std::max(sc->wf_pairs_per_ray, (double)peak / (2.0 * n_slab));
+		if (stats) { c->timing.peak_pairs = std::max<uint64_t>(c->timing.peak_pairs, peak); c->timing.slab_paths = std::max<uint64_t>(c->timing.slab_paths, n_slab); }
+		if (overflow) {
+			if (stats) c->timing.pool_overflows++;
+			// some step needed more pairs than the pool holds: the same slab again, smaller (the ratio just learnt says how much). The
+			// samples the aborted attempt already stored are stored again with the same values.
+			HIP_TRY(hipStreamSynchronize(c->stream));
+			const uint32_t smaller = std::min<uint32_t>(wf_slab_cap(sc, plan), cap - cap / 4);
+			if (cap <= 4096) return set_err(PTX_ERR_HIP, "queue-based pipeline: the pair pool cannot hold one step of a 4096-path slab");
+			plan.slab = std::max<uint32_t>(4096, smaller);
+			continue;
+		}
+		if (n_slab && P.bounces > 0) { unsigned long long r; memcpy(&r, ws.flow_host + kWfFlowRays, 8); rays += r; }
+		first += cap;
+	}
+	return PTX_OK;
+}
+
+// ptx_render_stats of a finished render, and the context's ptx_kernel_timing (PTX_CLK / PTX_PROF builds: region clocks and counters
+// of the fused kernel on stderr)
+int render_stats(ptx_ctx* c, uint64_t samples, uint32_t n_pass, bool wavefront, const WfPlan& plan, const WfClock& clk, unsigned long long wf_rays,
+                 ptx_render_stats* stats) {
+	unsigned long long rays = 0;
+	HIP_TRY(hipMemcpy(&rays, (char*)c->counters.p + 16, 8, hipMemcpyDeviceToHost));
+	stats->rays = rays + wf_rays;
+	stats->samples = samples;
+	stats->passes = n_pass;
+	double ms = 0;
+	for (uint32_t p = 0; p < n_pass; p++) {
+		float t = 0;
+		HIP_TRY(hipEventElapsedTime(&t, c->events[2 * p], c->events[2 * p + 1]));
+		ms += t;
+	}
+	stats->kernel_ms = ms;
+	ptx_kernel_timing& tm = c->timing;
+	tm.pipeline = wavefront ? 1u : 0u;
+	tm.pool_pairs = wavefront ? plan.W.pool_cap : 0;
+	tm.workspace_bytes = wavefront ? wf_workspace_bytes(c) : c->queues.cap + c->spill.cap;
+	if (!wavefront) { tm.fused_ms = ms; tm.fused_launches = n_pass; }
+	for (size_t k = 0; k + 4 <= clk.n_step_ev; k += 4) {
+		float t0 = 0, t1 = 0, t2 = 0;
+		HIP_TRY(hipEventElapsedTime(&t0, c->step_events[k], c->step_events[k + 1]));
+		HIP_TRY(hipEventElapsedTime(&t1, c->step_events[k + 1], c->step_events[k + 2]));
+		HIP_TRY(hipEventElapsedTime(&t2, c->step_events[k + 2], c->step_events[k + 3]));
+		tm.classify_ms += t0; tm.traverse_ms += t1; tm.shade_ms += t2;
+		tm.steps++;
+	}
+	tm.traverse_drain_frac = clk.all > 0 ? 1.0 - clk.busy / clk.all : 0.0;
+#ifdef PTX_CLK
+	if (!wavefront) {
+		unsigned long long clks[8];
+		HIP_TRY(hipMemcpy(clks, (char*)c->counters.p + 64, sizeof clks, hipMemcpyDeviceToHost));
+		static const char* names[8] = {"kernel", "chunk_fetch", "extend_entry_loads", "extend_sweep_rest", "set_aside_lists", "shade_entry_hit_loads", "shade_hitrec_gathers", "shade_rest"};
+		for (int k = 0; k < 8; k++) fprintf(stderr, "CLK %-22s %12llu kcycles summed over waves (%.2f %% of the waves' time)\n", names[k], clks[k], 100.0 * clks[k] / (double)clks[0]);
+	}
+#endif
+#ifdef PTX_PROF
+	unsigned long long prof[2 * kProfRegions];
+	HIP_TRY(hipMemcpy(prof, (char*)c->counters.p + 64, sizeof prof, hipMemcpyDeviceToHost));
+	static const char* names[kProfRegions] = {"extend_iter", "model_iter", "space_xform", "inline_model", "mesh_call", "mesh_pop", "node_step",
+	                                           "tri_test", "defer_iter", "shade_iter", "defer_mesh_call", "defer_mesh_pop", "defer_node_step", "defer_tri_test",
+	                                           "list_append", "shade_hit"};
+	for (int k = 0; k < kProfRegions; k++)
+		fprintf(stderr, "PROF %-16s trips %12llu lanes %14llu  util %.3f  trips/64rays %.3f\n", names[k], prof[2 * k], prof[2 * k + 1],
+		        prof[2 * k] ? (double)prof[2 * k + 1] / (64.0 * prof[2 * k]) : 0.0, (double)prof[2 * k] / ((double)rays / 64.0));
+#endif
+	return PTX_OK;
 }
 
 }  // namespace
@@ -750,8 +987,7 @@ int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_rende
 	if (!w || !h || (uint64_t)x0 + w > cfg->W || (uint64_t)y0 + h > cfg->H) return set_err(PTX_ERR_INVALID, "ptx_render: tile outside the image");
 	if (cfg->bounces > 0xFFFFu) return set_err(PTX_ERR_INVALID, "ptx_render: bounces > 65535");
 	if (cfg->integrator > PTX_INTEGRATOR_WORKER) return set_err(PTX_ERR_INVALID, "ptx_render: unknown integrator");
-	const bool sharded = cfg->shard_count > 1;
-	if (sharded && cfg->shard_index >= cfg->shard_count) return set_err(PTX_ERR_INVALID, "ptx_render: shard_index >= shard_count");
+	if (cfg->shard_count > 1 && cfg->shard_index >= cfg->shard_count) return set_err(PTX_ERR_INVALID, "ptx_render: shard_index >= shard_count");
 	ptx_ctx* c = sc->ctx;
 	std::lock_guard<std::mutex> lk(c->mu);
 	HIP_TRY(hipSetDevice(c->device));
@@ -759,79 +995,19 @@ int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_rende
 	if (rect_pixels > 0x7FFFFFFFull) return set_err(PTX_ERR_INVALID, "ptx_render: tile too large");
 	if (stats) *stats = ptx_render_stats{};
 	if (cfg->spp == 0) return PTX_OK;
-
-	// The order in which a pass enumerates its pixels (path id -> pixel). Per-sample radiance is keyed by (pixel, sample), so the order
-	// changes no result — only which rays sit next to each other in a wave and in a classify tile. "tiled": 8 x 8 pixel blocks (one
-	// wave of camera rays) inside 32 x 32 blocks (one classify tile) — coherent rays enter the same surfaces and walk the same nodes;
-	// PTX_PIXEL_ORDER=linear|tiled overrides (measurement). Interleaved tile sharding: only the pixels of this shard's image tiles.
-	uint64_t n_pixels = rect_pixels;
+	uint64_t n_pixels = 0;
 	const uint32_t* d_pixels = nullptr;
-	bool tiled = use_wavefront(sc);   // measured: profiles/round3_pixel_order.txt
-	if (const char* e = getenv("PTX_PIXEL_ORDER")) tiled = e[0] == 't';
-	if (sharded || tiled) {
-		const uint32_t ts = sharded ? (cfg->shard_tile ? cfg->shard_tile : 64u) : 0u;
-		const uint32_t key[9] = {cfg->W, cfg->H, x0, y0, w, h, sharded ? cfg->shard_index : 0u, (sharded ? cfg->shard_count : 1u) | (tiled ? 0x80000000u : 0u), ts};
-		if (memcmp(key, c->list_key, sizeof key) != 0 || !c->pixel_list.p) {
-			std::vector<uint32_t> list;
-			// the pixels of the image rectangle [xa, xb) x [ya, yb): rows, or 8 x 8 blocks inside 32 x 32 blocks anchored at the image origin
-			auto add_rect = [&](uint32_t xa, uint32_t ya, uint32_t xb, uint32_t yb) {
-				if (!tiled) {
-					for (uint32_t y = ya; y < yb; y++)
-						for (uint32_t x = xa; x < xb; x++) list.push_back((y - y0) * w + (x - x0));
-					return;
-				}
-				for (uint32_t by = ya / 32; by <= (yb - 1) / 32; by++)
-					for (uint32_t bx = xa / 32; bx <= (xb - 1) / 32; bx++)
-						for (uint32_t sy = 0; sy < 4; sy++)
-							for (uint32_t sx = 0; sx < 4; sx++)
-								for (uint32_t y = by * 32 + sy * 8; y < by * 32 + sy * 8 + 8; y++)
-									for (uint32_t x = bx * 32 + sx * 8; x < bx * 32 + sx * 8 + 8; x++)
-										if (x >= xa && x < xb && y >= ya && y < yb) list.push_back((y - y0) * w + (x - x0));
-			};
-			if (!sharded) add_rect(x0, y0, x0 + w, y0 + h);
-			else {
-				const uint32_t tiles_x = (cfg->W + ts - 1) / ts;
-				for (uint32_t ty = y0 / ts; ty <= (y0 + h - 1) / ts; ty++)
-					for (uint32_t tx = x0 / ts; tx <= (x0 + w - 1) / ts; tx++) {
-						if ((uint64_t)(ty * (uint64_t)tiles_x + tx) % cfg->shard_count != cfg->shard_index) continue;
-						add_rect(std::max(tx * ts, x0), std::max(ty * ts, y0), std::min((tx + 1) * ts, x0 + w), std::min((ty + 1) * ts, y0 + h));
-					}
-			}
-			// a previous render with stats == NULL and a device buffer returns without a sync (ptx.h): its generate / resolve kernels may
-			// still be reading the list this call is about to replace, and the context's stream is non-blocking (not ordered with the
-			// NULL stream a plain hipMemcpy would use) — drain it first, then upload on the same stream
-			HIP_TRY(hipStreamSynchronize(c->stream));
-			HIP_TRY(c->pixel_list.ensure(std::max<size_t>(list.size() * 4, 16)));
-			if (!list.empty()) {
-				HIP_TRY(hipMemcpyAsync(c->pixel_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, c->stream));
-				HIP_TRY(hipStreamSynchronize(c->stream));   // `list` is a local
-			}
-			memcpy(c->list_key, key, sizeof key);
-			c->list_len = (uint32_t)list.size();
-		}
-		n_pixels = c->list_len;
-		d_pixels = (const uint32_t*)c->pixel_list.p;
-		if (n_pixels == 0) return PTX_OK;   // no tile of this shard meets the rectangle
-	}
-
-	// samples of every pixel per launch: enough paths to fill the chip many times over, bounded workspace
-	uint32_t pass_spp = cfg->spp_per_pass;
-	if (pass_spp == 0) {
-		const uint64_t target_paths = 128ull << 20;   // 64 spp of a 1080p frame: 2 GB of per-sample radiance; fewer, longer launches (measured: 8 -> 64 spp per launch = +11 %)
-		pass_spp = (uint32_t)std::max<uint64_t>(1, target_paths / n_pixels);
-	}
-	pass_spp = std::min(pass_spp, cfg->spp);
-	while ((uint64_t)pass_spp * n_pixels > 0xFFFFFFFFull) pass_spp--;  // path ids are 32-bit
+	if (const int rc = pixel_list(c, sc, cfg, x0, y0, w, h, n_pixels, d_pixels); rc != PTX_OK) return rc;
+	if (n_pixels == 0) return PTX_OK;   // no tile of this shard meets the rectangle
+	const uint32_t pass_spp = pass_size(cfg, n_pixels);
 	if (pass_spp == 0) return set_err(PTX_ERR_INVALID, "ptx_render: tile too large for one pass");
 
 	const int grid = c->n_cu;
 	const size_t n_slots = (size_t)grid * (kBlock / 64);
-	// Units the kernels may set aside: whole models, or — when some model has many surfaces (a Sponza-class mesh) — single
+	// Units the fused kernel may set aside: whole models, or — when some model has many surfaces (a Sponza-class mesh) — single
 	// surfaces. PTX_SURFACE_UNITS=0/1 overrides the choice (measurement).
 	const uint32_t n_surf = (uint32_t)sc->host.surfaces.size(), n_mod = (uint32_t)sc->host.models.size();
-	int32_t max_per_model = 0;
-	for (const ModelRec& mr : sc->host.models) max_per_model = std::max(max_per_model, mr.n_surfaces);
-	bool surface_units = max_per_model >= 8 && n_surf <= (uint32_t)kMaxDeferModels;   // measured: +49 % on a 24-surface model, -2..-7 % on scenes of 1-3 surfaces per model
+	bool surface_units = max_surfaces_per_model(sc) >= 8 && n_surf <= (uint32_t)kMaxDeferModels;   // measured: +49 % on a 24-surface model, -2..-7 % on scenes of 1-3 surfaces per model
 	if (const char* e = getenv("PTX_SURFACE_UNITS")) surface_units = e[0] == '1' && n_surf <= (uint32_t)kMaxDeferModels;
 	const uint32_t queue_stride = queue_float4_per_wave(surface_units ? n_surf : n_mod);
 	bool wavefront = use_wavefront(sc);
@@ -858,99 +1034,18 @@ int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_rende
 			c->events.push_back(ev);
 		}
 	PassBuffers B{nullptr /* the fused kernel's streams: set below, once it is known which pipeline runs */, queue_stride, surface_units ? 1u : 0u, (float4*)c->sample_rad.p, (uint2*)c->spill.p, chunk_counter, ray_counter};
-	// queue-based pipeline (wavefront.hip): a pass runs in slabs; slab size from the pair pool and the pairs a path of this scene was
-	// seen to need — a step classifies two rays per path (extend + shadow)
-	WfBuffers WF[2]{};
-	WfStream wf_st[2][2]{};
-	uint32_t wf_cap = 0;
-	int wf_sets = 1;
-	uint64_t pool_pairs = kWfPoolPairs;
-	const uint64_t pass_paths = (uint64_t)pass_spp * n_pixels;
+	WfPlan plan;
+	WfClock clk;
+	unsigned long long wf_rays = 0;   // rays the queue-based pipeline traced (slabs that went through)
 	const double ratio_at_entry = sc->wf_pairs_per_ray;
-	// steps enqueued back to back before the host looks at the flow words again. The grids of a round are sized for the entries the
-	// slab had when the round began (entries only ever get fewer): short rounds keep the later steps' grids close to what is alive —
-	// the shade kernel's workgroups beyond the entry count only read it and leave, but a 66 M-path slab has 259 K of them per launch —
-	// at the price of one host round trip (tens of microseconds) per round. PTX_WF_ROUND overrides (measurement).
-	uint32_t wf_round = 3;
-	if (const char* e = getenv("PTX_WF_ROUND")) wf_round = (uint32_t)std::max(1, atoi(e));
-	wf_round = (uint32_t)std::min<uint64_t>({(uint64_t)wf_round, (uint64_t)cfg->bounces + 1u, (uint64_t)kWfMaxRound});
 	const bool timing = stats && c->timing_on;
-	double clock_busy = 0, clock_all = 0;   // queue-based pipeline with timing on: traverse waves' run times against waves x longest run, summed over launches
 	if (stats) c->timing = ptx_kernel_timing{};
-	auto slab_cap = [&]() -> uint32_t {   // paths of a slab: the pool must hold the pairs of its busiest step
-		const double per_path = 2.0 * wf_ratio_guess(sc);
-		const uint64_t by_pool = (uint64_t)std::max(65536.0, (double)pool_pairs / per_path);
-		static const uint64_t max_slab = [] { const char* e = getenv("PTX_WF_MAX_SLAB_M"); return e ? std::min<uint64_t>((uint64_t)kWfIdMask, strtoull(e, nullptr, 10) << 20) : (uint64_t)kWfMaxSlab - 1; }();   // measurement
-		const uint64_t cap = std::min<uint64_t>({(pass_paths + wf_sets - 1) / wf_sets, max_slab, by_pool});
-		const uint64_t n_slabs = (pass_paths + cap - 1) / cap;   // slabs of equal size rather than full ones and a remainder
-		return (uint32_t)((pass_paths + n_slabs - 1) / n_slabs);
-	};
-	auto allocate = [&]() -> hipError_t {
-		hipError_t e;
-		// the pool that is allocated: what the slab needs at the pairs per path this scene is expected to ask for (+ 10 %), not the
-		// whole budget — a scene whose rays enter few boxes (jack-of-blades: 0.3 pairs per ray) holds 2 GB of pairs, not 18
-		// (in steps of 64 Mi pairs: the ratio learnt from one frame must not move the allocation by a few per cent in the next)
-		const uint64_t want_pairs = (uint64_t)((double)wf_cap * 2.0 * wf_ratio_guess(sc) * 1.1), step = want_pairs > (128ull << 20) ? (64ull << 20) : (16ull << 20);
-		const uint64_t alloc_pairs = std::min<uint64_t>(pool_pairs, std::max<uint64_t>(16ull << 20, (want_pairs + step - 1) / step * step));
-		for (int k = 0; k < wf_sets; k++) {
-			ptx_ctx::WfSet& w = c->wf[k];
-			if (w.qent.cap > 4 * alloc_pairs * 32) { w.qent.release(); w.pair_hit.release(); }   // held from a much hungrier scene: give it back
-			if ((e = wf_workspace(c, k, 2 * (size_t)wf_cap, alloc_pairs, n_surf, wf_round, WF[k])) != hipSuccess) return e;
-			WF[k].ray_counter = (unsigned long long*)((uint32_t*)w.flow.p + kWfFlowRays);   // rays of the slab: added to the total once the slab is through (an overflowing attempt is not counted)
-			if ((e = w.stream_buf.ensure((size_t)wf_cap * 14 * sizeof(float4))) != hipSuccess) return e;
-			if (!w.stream && (e = hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking)) != hipSuccess) return e;
-			if (!w.done && (e = hipEventCreateWithFlags(&w.done, hipEventDisableTiming)) != hipSuccess) return e;
-		}
-		return hipSuccess;
-	};
-	if (wavefront) {
-		{
-			size_t free_b = 0, total_b = 0;
-			if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-				const uint64_t held = wf_workspace_bytes(c);   // what the context already holds counts as available: the same answer frame after frame
-				pool_pairs = std::min<uint64_t>(pool_pairs, std::max<uint64_t>(16ull << 20, (free_b + held) / 4 / 48));
-			} else (void)hipGetLastError();
-		}
-		if (const char* e = getenv("PTX_WF_PAIRS_M")) pool_pairs = std::max<uint64_t>(1, strtoull(e, nullptr, 10)) << 20;   // measurement: pool size in Mi pairs
-		pool_pairs = std::min<uint64_t>(pool_pairs, 0xFFFFFFFFull);
-		wf_sets = getenv("PTX_WF_TWO_STREAMS") ? 2 : 1;   // measurement: two slabs side by side on two streams
-		if (!c->wf_main_ev) HIP_TRY(hipEventCreateWithFlags(&c->wf_main_ev, hipEventDisableTiming));
-		// when the device cannot spare the pool: a smaller one (smaller slabs), and below 8 Mi pairs the fused kernel
-		for (;;) {
-			wf_cap = slab_cap();
-			const hipError_t e = allocate();
-			if (e == hipSuccess) break;
-			if (e != hipErrorOutOfMemory) return set_err(PTX_ERR_HIP, std::string("queue-based pipeline workspace: ") + hipGetErrorString(e));
-			(void)hipGetLastError();
-			for (auto& w : c->wf)
-				for (DevBuf* b : {&w.qent, &w.pair_hit, &w.seg, &w.first, &w.mask, &w.stream_buf}) b->release();
-			pool_pairs /= 2;
-			if (pool_pairs < (8ull << 20)) { wavefront = false; break; }
-		}
-	}
-	auto set_streams = [&](uint32_t cap) {   // the two stream buffers of each set, `cap` entries per array
-		for (int k = 0; k < wf_sets; k++) {
-			float4* base = (float4*)c->wf[k].stream_buf.p;
-			wf_st[k][0] = WfStream{base, base + 8 * (size_t)cap};
-			wf_st[k][1] = WfStream{base + 4 * (size_t)cap, base + 11 * (size_t)cap};
-		}
-	};
+	if (wavefront)   // a device that cannot spare a pool sets `wavefront` to false: the fused kernel renders
+		if (const int rc = wf_plan(c, sc, (uint64_t)pass_spp * n_pixels, cfg->bounces, plan, wavefront); rc != PTX_OK) return rc;
 	if (!wavefront) {
 		HIP_TRY(c->queues.ensure(n_slots * (size_t)queue_stride * sizeof(float4)));
 		B.queues = (float4*)c->queues.p;
 	}
-	size_t n_step_ev = 0;   // step events used so far (timing)
-	unsigned long long wf_rays = 0;   // rays the queue-based pipeline traced (slabs that went through)
-	auto step_events = [&]() -> hipEvent_t* {
-		if (!timing) return nullptr;
-		while (c->step_events.size() < n_step_ev + 4) {
-			hipEvent_t ev;
-			if (hipEventCreate(&ev) != hipSuccess) return nullptr;
-			c->step_events.push_back(ev);
-		}
-		n_step_ev += 4;
-		return &c->step_events[n_step_ev - 4];
-	};
 	for (uint32_t p = 0; p < n_pass; p++) {
 		RenderParams P{};
 		P.W = cfg->W; P.H = cfg->H; P.x0 = x0; P.y0 = y0; P.w = w; P.h = h;
@@ -966,102 +1061,9 @@ int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_rende
 		HIP_TRY(hipMemsetAsync(chunk_counter, 0, 8, c->stream));
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
 		if (wavefront) {
-			// queue-based pipeline: the pass in slabs of at most `wf_cap` paths (one per workspace set and stream at a time). The steps of a
-			// slab are enqueued back to back, `wf_round` at a time: every kernel takes its entry count from the device (flow words), and the
-			// host reads them back once per round — whether paths are left (pass-through materials can outlive bounces + 1 steps), whether
-			// some step's pairs overflowed the pool, and the peak demand that sizes the next slab.
-			HIP_TRY(hipEventRecord(c->wf_main_ev, c->stream));
-			for (int k = 0; k < wf_sets; k++) HIP_TRY(hipStreamWaitEvent(c->wf[k].stream, c->wf_main_ev, 0));
-			uint64_t first = 0;
-			while (first < P.n_paths) {
-				wf_cap = std::min(wf_cap, slab_cap());   // never above what the buffers were sized for
-				set_streams(wf_cap);
-				uint32_t n_slab[2] = {0, 0}, slab_first[2] = {0, 0}, n_round[2] = {0, 0};   // paths of the slab, entries when the current round began
-				bool live[2] = {false, false};
-				int cur[2] = {0, 0};
-				for (int k = 0; k < wf_sets; k++) {
-					const uint64_t f = first + (uint64_t)k * wf_cap;
-					slab_first[k] = (uint32_t)f;
-					n_slab[k] = f < P.n_paths ? (uint32_t)std::min<uint64_t>(wf_cap, P.n_paths - f) : 0u;
-					if (!n_slab[k]) continue;
-					ptx_ctx::WfSet& ws = c->wf[k];
-					HIP_TRY(launch_wf_generate(sc->dev, P, wf_st[k][0], wf_cap, slab_first[k], n_slab[k], B.sample_rad, ws.stream));
-					HIP_TRY(hipMemsetAsync(ws.flow.p, 0, kWfFlowWords * 4, ws.stream));
-					HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ws.flow.p, (int)n_slab[k], 1, ws.stream));   // flow[0] = entries of step 0
-					live[k] = P.bounces > 0;
-					n_round[k] = n_slab[k];
-				}
-				bool overflow = false;
-				uint64_t peak = 0;
-				while (live[0] || live[1]) {
-					for (int k = 0; k < wf_sets; k++) {
-						if (!live[k]) continue;
-						ptx_ctx::WfSet& ws = c->wf[k];
-						uint32_t* flow = (uint32_t*)ws.flow.p;
-						HIP_TRY(hipMemsetAsync(ws.ctl.p, 0, (size_t)wf_round * kWfCtlWords * 4, ws.stream));
-						HIP_TRY(hipMemsetAsync(flow + 1, 0, (size_t)wf_round * 4, ws.stream));
-						for (uint32_t st = 0; st < wf_round; st++) {
-							WfBuffers W = WF[k];
-							W.ctl = (uint32_t*)ws.ctl.p + (size_t)st * kWfCtlWords;
-							W.n_in = flow + st;
-							W.wave_clock = timing ? 1u : 0u;
-							HIP_TRY(launch_wf_step(sc->dev, P, W, wf_st[k][cur[k]], wf_st[k][cur[k] ^ 1], wf_cap, n_round[k], slab_first[k], flow + st + 1, B.sample_rad, c->n_cu, ws.stream,
-							                       step_events()));
-							cur[k] ^= 1;
-						}
-						HIP_TRY(hipMemcpyAsync(ws.flow_host, flow, kWfFlowWords * 4, hipMemcpyDeviceToHost, ws.stream));
-					}
-					for (int k = 0; k < wf_sets; k++) {
-						if (!live[k]) continue;
-						ptx_ctx::WfSet& ws = c->wf[k];
-						HIP_TRY(hipStreamSynchronize(ws.stream));
-						peak = std::max<uint64_t>(peak, ws.flow_host[kWfFlowPeak]);
-						if (timing) {   // the traverse waves' own clocks of this round's steps (wavefront.hip: kWfCtlClock)
-							for (uint32_t st = 0; st < wf_round; st++) {
-								uint32_t ck[4];
-								HIP_TRY(hipMemcpy(ck, (uint32_t*)ws.ctl.p + (size_t)st * kWfCtlWords + kWfCtlClock, sizeof ck, hipMemcpyDeviceToHost));
-								const double sum = (double)(((uint64_t)ck[1] << 32) | ck[0]), all = (double)ck[2] * (double)ck[3];
-								clock_busy += sum; clock_all += all;
-							}
-						}
-						if (ws.flow_host[kWfFlowOverflow]) { overflow = true; live[k] = false; continue; }
-						const uint32_t left = ws.flow_host[wf_round];
-						n_round[k] = left;
-						if (left == 0) live[k] = false;
-						else HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ws.flow.p, (int)left, 1, ws.stream));   // next round: flow[0] = what this one left
-					}
-					if (overflow) break;
-				}
-				// what a ray of this scene needs, from the busiest step of these slabs (two rays per path and step)
-				const uint32_t n_big = std::max(n_slab[0], n_slab[1]);
-				if (peak && n_big) sc->wf_pairs_per_ray = std::max(sc->wf_pairs_per_ray, (double)peak / (2.0 * n_big));
-				if (stats) { c->timing.peak_pairs = std::max<uint64_t>(c->timing.peak_pairs, peak); c->timing.slab_paths = std::max<uint64_t>(c->timing.slab_paths, n_big); }
-				if (overflow) {
-					if (stats) c->timing.pool_overflows++;
-					// some step needed more pairs than the pool holds: the same slabs again, smaller (the ratio just learnt says how much). The
-					// samples the aborted attempt already stored are stored again with the same values.
-					for (int k = 0; k < wf_sets; k++) HIP_TRY(hipStreamSynchronize(c->wf[k].stream));
-					const uint32_t smaller = std::min<uint32_t>(slab_cap(), wf_cap - wf_cap / 4);
-					if (wf_cap <= 4096) return set_err(PTX_ERR_HIP, "queue-based pipeline: the pair pool cannot hold one step of a 4096-path slab");
-					wf_cap = std::max<uint32_t>(4096, smaller);
-					continue;
-				}
-				for (int k = 0; k < wf_sets; k++)
-					if (n_slab[k] && P.bounces > 0) { unsigned long long r; memcpy(&r, c->wf[k].flow_host + kWfFlowRays, 8); wf_rays += r; }
-				first += (uint64_t)wf_sets * wf_cap;
-			}
-			for (int k = 0; k < wf_sets; k++) {
-				HIP_TRY(hipEventRecord(c->wf[k].done, c->wf[k].stream));
-				HIP_TRY(hipStreamWaitEvent(c->stream, c->wf[k].done, 0));
-			}
-			if (ratio_at_entry == 0 && sc->wf_pairs_per_ray > 0 && p + 1 == n_pass) {
-				// the scene's first frame has just told what its rays need: bring the workspace to the size the NEXT frame of this kind
-				// will ask for now (a larger slab, a smaller or larger pool), inside the frame that pays for allocations anyway
-				for (int k = 0; k < wf_sets; k++) HIP_TRY(hipStreamSynchronize(c->wf[k].stream));
-				wf_cap = slab_cap();
-				const hipError_t se = allocate();
-				if (se != hipSuccess) (void)hipGetLastError();   // not fatal: the next frame sizes its workspace itself
-			}
+			if (const int rc = wf_pass(c, sc, P, B.sample_rad, stats != nullptr, timing ? &clk : nullptr, plan, wf_rays); rc != PTX_OK) return rc;
+			if (ratio_at_entry == 0 && sc->wf_pairs_per_ray > 0 && p + 1 == n_pass)
+				if (const int rc = wf_resize(c, sc, plan); rc != PTX_OK) return rc;
 		} else {
 			if (!B.queues || !B.sample_rad || !B.spill) return set_err(PTX_ERR_HIP, "ptx_render: workspace of the fused kernel is not allocated");
 			HIP_TRY(launch_render_pass(sc->dev, P, B, sc->mode, sc->lds_bytes, grid, c->stream));
@@ -1071,52 +1073,7 @@ int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_rende
 	}
 	if (!dev_accum) HIP_TRY(hipMemcpyAsync(accum, d_accum, rect_pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
 	if (stats || !dev_accum) HIP_TRY(hipStreamSynchronize(c->stream));
-	if (stats) {
-		unsigned long long rays = 0;
-		HIP_TRY(hipMemcpy(&rays, ray_counter, 8, hipMemcpyDeviceToHost));
-		stats->rays = rays + wf_rays;
-		stats->samples = (uint64_t)cfg->spp * n_pixels;
-		stats->passes = n_pass;
-		double ms = 0;
-		for (uint32_t p = 0; p < n_pass; p++) {
-			float t = 0;
-			HIP_TRY(hipEventElapsedTime(&t, c->events[2 * p], c->events[2 * p + 1]));
-			ms += t;
-		}
-		stats->kernel_ms = ms;
-		ptx_kernel_timing& tm = c->timing;
-		tm.pipeline = wavefront ? 1u : 0u;
-		tm.pool_pairs = wavefront ? WF[0].pool_cap : 0;
-		tm.workspace_bytes = wavefront ? wf_workspace_bytes(c) : c->queues.cap + c->spill.cap;
-		if (!wavefront) { tm.fused_ms = ms; tm.fused_launches = n_pass; }
-		for (size_t k = 0; k + 4 <= n_step_ev; k += 4) {
-			float t0 = 0, t1 = 0, t2 = 0;
-			HIP_TRY(hipEventElapsedTime(&t0, c->step_events[k], c->step_events[k + 1]));
-			HIP_TRY(hipEventElapsedTime(&t1, c->step_events[k + 1], c->step_events[k + 2]));
-			HIP_TRY(hipEventElapsedTime(&t2, c->step_events[k + 2], c->step_events[k + 3]));
-			tm.classify_ms += t0; tm.traverse_ms += t1; tm.shade_ms += t2;
-			tm.steps++;
-		}
-		tm.traverse_drain_frac = clock_all > 0 ? 1.0 - clock_busy / clock_all : 0.0;
-#ifdef PTX_CLK
-		if (!wavefront) {
-			unsigned long long clk[8];
-			HIP_TRY(hipMemcpy(clk, (char*)c->counters.p + 64, sizeof clk, hipMemcpyDeviceToHost));
-			static const char* names[8] = {"kernel", "chunk_fetch", "extend_entry_loads", "extend_sweep_rest", "set_aside_lists", "shade_entry_hit_loads", "shade_hitrec_gathers", "shade_rest"};
-			for (int k = 0; k < 8; k++) fprintf(stderr, "CLK %-22s %12llu kcycles summed over waves (%.2f %% of the waves' time)\n", names[k], clk[k], 100.0 * clk[k] / (double)clk[0]);
-		}
-#endif
-#ifdef PTX_PROF
-		unsigned long long prof[2 * kProfRegions];
-		HIP_TRY(hipMemcpy(prof, (char*)c->counters.p + 64, sizeof prof, hipMemcpyDeviceToHost));
-		static const char* names[kProfRegions] = {"extend_iter", "model_iter", "space_xform", "inline_model", "mesh_call", "mesh_pop", "node_step",
-		                                           "tri_test", "defer_iter", "shade_iter", "defer_mesh_call", "defer_mesh_pop", "defer_node_step", "defer_tri_test",
-		                                           "list_append", "shade_hit"};
-		for (int k = 0; k < kProfRegions; k++)
-			fprintf(stderr, "PROF %-16s trips %12llu lanes %14llu  util %.3f  trips/64rays %.3f\n", names[k], prof[2 * k], prof[2 * k + 1],
-			        prof[2 * k] ? (double)prof[2 * k + 1] / (64.0 * prof[2 * k]) : 0.0, (double)prof[2 * k] / ((double)rays / 64.0));
-#endif
-	}
+	if (stats) return render_stats(c, (uint64_t)cfg->spp * n_pixels, n_pass, wavefront, plan, clk, wf_rays, stats);
 	return PTX_OK;
 }
 
@@ -1167,8 +1124,8 @@ int ptx_intersect_batch(ptx_scene* sc, const ptx_rays* r, size_t n, const ptx_hi
 		auto slice_cap = [&]() { return (size_t)std::max(16384.0, (double)pool_pairs / wf_ratio_guess(sc)); };
 		size_t slice = std::min<size_t>(n, slice_cap());
 		WfBuffers W{};
-		HIP_TRY(wf_workspace(c, 0, slice, pool_pairs, n_surf, 1, W));
-		ptx_ctx::WfSet& ws = c->wf[0];
+		HIP_TRY(wf_workspace(c, slice, pool_pairs, n_surf, 1, W));
+		ptx_ctx::WfSet& ws = c->wf;
 		for (size_t first = 0; first < n;) {
 			const uint32_t m = (uint32_t)std::min(slice, n - first);
 			HIP_TRY(hipMemsetAsync(ws.ctl.p, 0, kWfCtlWords * 4, c->stream));

@@ -8,9 +8,9 @@
 //   k_wf_classify  one ray per lane: local ray per model space, model box, surface boxes (scene::model::intersect, model.cpp:27-60;
 //                  core::mesh::intersect's box test, mesh.cpp:308-315) -> the ray's pairs, written as queue entries (local ray + result
 //                  slot) grouped by surface: pair space comes from a pool sized by demand, one reservation per tile of 1024 rays
-//   k_wf_traverse  persistent waves that eat the queues: every lane walks ONE pair's tree (core::mesh::intersect, mesh.cpp:300-405)
-//                  and takes the next pair as soon as its walk ends, so lanes stay busy whatever the walk lengths; 256-thread
-//                  blocks and a traversal-only register footprint (59 VGPRs, 24 KB of LDS) give 6 waves per SIMD to cover the fetch latency; queues are
+//   k_wf_traverse2 persistent waves that eat the queues: every lane walks ONE pair's tree (core::mesh::intersect, mesh.cpp:300-405),
+//                  one step per trip of a single loop, and takes the next pair as soon as its walk ends, so lanes stay busy whatever
+//                  the walk lengths; 256-thread blocks and a traversal-only register footprint (59 VGPRs, 24 KB of LDS) give 6 waves per SIMD to cover the fetch latency; queues are
 //                  dealt to XCDs surface by surface so that each L2 sees a part of the geometry, and started largest tree first (DevScene::wf_order)
 //                  so that a launch ends on the queues of the short walks
 //   k_wf_merge_* / k_wf_shade   one ray per lane again: the ray's pair results (fetched ahead, four at a time) in surface order = model::intersect's loop (first
@@ -31,10 +31,6 @@ constexpr int kWfClassifyBlock = (int)kWfTile;   // ... of the classify kernel: 
 #endif
 constexpr uint32_t kWfUnit = PTX_WF_UNIT;  // queue entries a wave stages into its LDS slice at a time
 static_assert(kWfUnit >= 1 && kWfUnit <= 64, "a unit is staged by one pass of the wave's 64 lanes");
-#ifndef PTX_WF_LDS_STACK
-#define PTX_WF_LDS_STACK 8
-#endif
-constexpr int kWfLdsStack = PTX_WF_LDS_STACK;         // traversal-stack levels kept in LDS between the register levels and the global-memory overflow
 #ifndef PTX_WF_REFILL_MIN
 #define PTX_WF_REFILL_MIN 8
 #endif
@@ -43,7 +39,7 @@ constexpr int kWfLdsStack = PTX_WF_LDS_STACK;         // traversal-stack levels 
 #endif
 constexpr uint32_t kWfRefillMin = PTX_WF_REFILL_MIN;   // idle lanes that make a hand-out of new pairs worth its instructions
 
-// PTX_WF_PROF builds: wave-level trips and active lanes per region of k_wf_traverse, added into ctl[kWfCtlProf ..] (measurement only)
+// PTX_WF_PROF builds: wave-level trips and active lanes per region of k_wf_traverse2, added into ctl[kWfCtlProf ..] (measurement only)
 #ifdef PTX_WF_PROF
 #define WFPROF(k) do { const uint64_t m_ = __ballot(true); pl[k] += 1u; pt[k] += (lane == (uint32_t)(__ffsll((long long)m_) - 1)) ? 1u : 0u; if ((k) == 2 || (k) == 3) walk_steps++; } while (0)
 // wave-level clock spent per region (kilocycles, lane 0 adds it up): T0 / T1 bracket a region executed under wave-uniform control flow
@@ -220,264 +216,29 @@ DEV int wf_surface_at(const uint32_t* __restrict__ order, uint32_t xcd, uint32_t
 	return u < n_surf ? (int)order[u] : -1;
 }
 
-// The nested-loop form (kept for measurement, PTX_WF_KERNEL=1, and for layouts the one-loop kernel does not read: per-triangle records,
-// geometry beyond 4 GB). Persistent 256-thread workgroups (75 VGPRs, no scratch, 6 waves per SIMD). Every lane walks ONE pair's tree (mesh.cpp:300-405, the
-// loop of mesh_traverse) and takes its next pair from the wave's LDS-staged unit as soon as the walk ends. A wave takes work one
-// SEGMENT (the entries one classify tile queued for one surface: contiguous, <= 1024) at a time with one atomic on the surface's
-// cursor, and stages it in units of 64 entries with coalesced loads — the entries carry the local ray and the result slot, nothing
-// is gathered.
-#ifdef PTX_WF_WAVES
-__attribute__((amdgpu_waves_per_eu(PTX_WF_WAVES, PTX_WF_WAVES)))
-#endif
-__global__ void __launch_bounds__(kWfBlock) k_wf_traverse(DevScene S0, WfBuffers W, const SurfaceRec* __restrict__ t_surfaces) {
-	DevScene S = S0;
-	S.surfaces = t_surfaces;
-	if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(W.peak, W.ctl[0]);   // demand of this step (counted on even when it overflowed the pool)
-	if (W.ctl[1]) return;   // this step's pairs did not fit the pool: the host repeats the slab
-	const Geom g = {S.nodes, S.refs, S.tri_isect, S.glb_leaf_ordered != 0, true};
-	__shared__ float4 s_ray[kWfBlock / 64][kWfUnit][2];
-	// Pending subtrees beyond the register levels. A store to global memory here would sit in the same in-order counter as the node
-	// fetches (gfx9 has one vmcnt for loads and stores): 4 of 10 node steps on these trees push deeper than the registers hold, and each
-	// would make the next fetch wait for a write acknowledgement. LDS has its own counter and a tenth of the latency.
-	__shared__ uint2 s_stack[kWfLdsStack > 0 ? kWfLdsStack : 1][kWfBlock];
-	const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
-	const uint32_t xcd = blockIdx.x & 7u;
-	const Spill spill{W.spill + (size_t)(blockIdx.x * (kWfBlock / 64) + wave) * (kSpillStack * 64) + lane};
-	auto stack_put = [&](int k, uint32_t nn, float mm) {
-		if (k < kWfLdsStack) s_stack[k][threadIdx.x] = make_uint2(nn, __float_as_uint(mm));
-		else spill_put(spill, k - kWfLdsStack, nn, mm);
-	};
-	auto stack_get = [&](int k, uint32_t& nn, float& mm) {
-		if (k < kWfLdsStack) { const uint2 v = s_stack[k][threadIdx.x]; nn = v.x; mm = __uint_as_float(v.y); }
-		else spill_get(spill, k - kWfLdsStack, nn, mm);
-	};
-	const uint32_t n_surf = S.n_surfaces;
-	const uint32_t n_order = ((n_surf + 7u) / 8u) * 8u;
-
-	// wave-uniform: the segment being handed out, and the unit of it staged in LDS
-	uint32_t seg_pos = 0, seg_end = 0, unit_pos = 0, unit_n = 0, order_pos = 0;
-	int unit_surf = -1;
-	bool more = true;
-	// per lane: the walk in progress (core::mesh::intersect's locals, as in mesh_traverse)
-	bool busy = false, have = false;
-	uint32_t slot = 0, node = 0;
-	int sp = 0;
-	uint32_t n0 = 0, n1 = 0, n2 = 0;
-	float m0 = 0, m1 = 0, m2 = 0;
-	float min_dist = 0, max_dist = 0, fr0 = 0;
-	V3 o = {0, 0, 0}, d = {0, 0, 1};
-#ifdef PTX_WF_PROF
-	uint32_t pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pl[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // 0 outer rounds, 1 busy rounds, 2 node steps, 3 triangle tests, 4 hand-outs, 5 unit fetches, 6 pops
-	uint64_t tc[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // clocks: 0 whole kernel, 1 unit fetch, 2 hand-out, 3 pop, 4 descend loops, 5 leaf loops, 6 result stores
-	const uint64_t t_start = __builtin_amdgcn_s_memtime();
-	uint32_t walk_steps = 0, walk_max = 0;   // node steps + triangle tests of the lane's current walk / of its longest one
-#endif
-
-	for (;;) {
-		WFPROF(0);
-		const uint64_t idle_m = __ballot(!busy);
-		if (more && ((uint32_t)__popcll(idle_m) >= kWfRefillMin || ~idle_m == 0)) {
-			if (unit_pos == unit_n) {
-				WFT0();
-				if (seg_pos == seg_end) {
-					// next segment: this XCD's surfaces first; one atomic on the surface's cursor per segment. A wave that finds a cursor past
-					// the surface's last segment never returns to that surface
-					for (;;) {
-						if (unit_surf < 0) {
-							int u = -1;
-							for (; order_pos < n_order; order_pos++) {
-								const int c = wf_surface_at(S.wf_order, xcd, order_pos, n_surf);
-								if (c >= 0 && W.ctl[kWfCtlSeg + c] != 0) { u = c; break; }
-							}
-							u = __builtin_amdgcn_readfirstlane(u);
-							if (u < 0) { more = false; break; }
-							unit_surf = u;
-						}
-						uint32_t k = 0;
-						if (lane == 0) k = atomicAdd(&W.ctl[kWfCtlCur + 64u * (uint32_t)unit_surf], 1u);
-						k = __builtin_amdgcn_readfirstlane(k);
-						if (k < W.ctl[kWfCtlSeg + unit_surf]) {
-							const uint2 sg = W.seg[(size_t)unit_surf * W.seg_cap + k];
-							seg_pos = __builtin_amdgcn_readfirstlane(sg.x);
-							seg_end = seg_pos + __builtin_amdgcn_readfirstlane(sg.y);
-							break;
-						}
-						unit_surf = -1;
-						order_pos++;
-					}
-				}
-				if (more) {
-					WFPROF(5);
-					// stage the next <= 64 entries of the segment into this wave's LDS slice (coalesced: the entries are contiguous)
-					unit_n = seg_end - seg_pos < kWfUnit ? seg_end - seg_pos : kWfUnit;
-					unit_pos = 0;
-					if (lane < unit_n) {
-						const size_t e = (size_t)seg_pos + lane;
-						s_ray[wave][lane][0] = W.qent[2 * e];
-						s_ray[wave][lane][1] = W.qent[2 * e + 1];
-					}
-					seg_pos += unit_n;
-					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-				}
-				WFT1(1);
-			}
-			if (more) {
-				WFT0();
-				const uint32_t avail = unit_n - unit_pos;
-				const uint32_t r = rank_in(idle_m);
-				if (!busy && r < avail) {
-					WFPROF(4);
-#ifdef PTX_WF_PROF
-					walk_max = walk_steps > walk_max ? walk_steps : walk_max; walk_steps = 0;
-#endif
-					const uint32_t e = unit_pos + r;
-					const float4 e0 = s_ray[wave][e][0], e1 = s_ray[wave][e][1];
-					slot = __float_as_uint(e0.w);
-					o = mk(e0.x, e0.y, e0.z);
-					d = mk(e1.x, e1.y, e1.z);
-					const SurfaceRec& sf = S.surfaces[unit_surf];
-					const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-					float nr, fr;
-					if (aabb_test_box(sf.box, o, inv, nr, fr)) {   // mesh.cpp:308-315 (the classification saw the same test pass)
-						busy = true; have = true;
-						node = sf.kd_root; min_dist = nr; max_dist = fr; fr0 = fr; sp = 0;
-					} else {
-						W.pair_hit[slot] = make_float4(-1.0f, 0.f, 0.f, 0.f);
-					}
-				}
-				const uint32_t n_idle = (uint32_t)__popcll(idle_m);
-				unit_pos += n_idle < avail ? n_idle : avail;
-				WFT1(2);
-			}
-		}
-		if (__ballot(busy) == 0) {
-			if (!more) break;
-			continue;
-		}
-		// one round of core::mesh::intersect's loop (mesh.cpp:317-403; see mesh_traverse): pop, descend to a leaf, test it
-		{
-			WFT0();
-			if (busy) {
-				WFPROF(1);
-				if (!have) {
-					if (sp == 0) { W.pair_hit[slot] = make_float4(-1.0f, 0.f, 0.f, 0.f); busy = false; }
-					else {
-						WFPROF(6);
-						sp--;
-						node = n0; min_dist = m0;
-						n0 = n1; m0 = m1; n1 = n2; m1 = m2;
-						if (sp >= kRegStack) stack_get(sp - kRegStack, n2, m2);
-						max_dist = sp > 0 ? m0 : fr0;
-					}
-				}
-			}
-			WFT1(3);
-		}
-		bool valid = false;
-		uint2 nd = make_uint2(0, 0);
-		{
-			WFT0();
-			if (busy) {
-				have = false;
-				valid = true;
-				nd = g.nodes[node];
-				while ((nd.y & 3u) != KD_LEAF) {
-					WFPROF(2);
-					const uint32_t axis = nd.y & 3u;
-					const uint2 kid0 = g.nodes[nd.y >> 4], kid1 = g.nodes[(nd.y >> 4) + 1u];   // both children requested with the parent in hand (fetching only the chosen one afterwards: -5 %)
-					const float split = __uint_as_float(nd.x);
-					const float oa = sel3(o, axis), da = sel3(d, axis);
-					const float split_dist = (split - oa) / da;
-					const bool has_l = nd.y & 4u, has_r = nd.y & 8u;
-					const uint32_t li = nd.y >> 4, ri = li + (has_l ? 1u : 0u);
-					const bool left_first = oa < split;
-					const uint32_t first = left_first ? li : ri, second = left_first ? ri : li;
-					const bool has_first = left_first ? has_l : has_r, has_second = left_first ? has_r : has_l;
-					uint32_t next;
-					bool has_next;
-					if (split_dist < 0 || split_dist > max_dist) { next = first; has_next = has_first; }
-					else if (split_dist < min_dist) { next = second; has_next = has_second; }
-					else {
-						if (has_second && sp < kRegStack + kSpillStack) {
-							if (sp >= kRegStack) { WFPROF(7); stack_put(sp - kRegStack, n2, m2); }
-							n2 = n1; m2 = m1; n1 = n0; m1 = m0; n0 = second; m0 = split_dist;
-							sp++;
-						}
-						next = first; has_next = has_first;
-						max_dist = split_dist;
-					}
-					if (!has_next) { valid = false; break; }
-					node = next;
-					nd = next == li ? kid0 : kid1;
-				}
-			}
-			WFT1(4);
-		}
-		{
-			WFT0();
-			if (busy && valid) {
-				// leaf: nearest triangle with t <= max_dist; ties keep the first (mesh.cpp:381-389)
-				const PRay pr = pack_ray(o, d);
-				const uint32_t first_ref = nd.x, count = nd.y >> 2;
-				float best_t = -1.0f, bb1 = 0, bb2 = 0;
-				uint32_t best_tri = 0;
-				for (uint32_t k = 0; k < count; k++) {
-					WFPROF(3);
-					const uint32_t rslot = g.leaf_ordered ? first_ref + k : g.refs[first_ref + k];
-					const float4 r0 = g.tris[3 * rslot], r1 = g.tris[3 * rslot + 1], r2 = g.tris[3 * rslot + 2];
-					const uint32_t ti = __float_as_uint(r2.z);
-					float be, ga;
-					const float t = tri_test_pk(r0, r1, make_float2(r2.x, r2.y), pr, be, ga);
-					if (t >= 0 && t <= max_dist && (t < best_t || !(best_t >= 0))) { best_t = t; bb1 = be; bb2 = ga; best_tri = ti; }
-				}
-				if (best_t >= 0) {
-					W.pair_hit[slot] = make_float4(best_t, __uint_as_float(best_tri), bb1, bb2);
-					busy = false;
-				}
-			}
-			WFT1(5);
-		}
-	}
-#ifdef PTX_WF_PROF
-	for (int k = 0; k < 8; k++) {
-		if (pt[k]) atomicAdd(&W.ctl[kWfCtlProf + 2 * k], pt[k]);
-		if (pl[k]) atomicAdd(&W.ctl[kWfCtlProf + 2 * k + 1], pl[k]);
-	}
-	tc[0] = __builtin_amdgcn_s_memtime() - t_start;
-	if (lane == 0) for (int k = 0; k < 6; k++) atomicAdd(&W.ctl[kWfCtlProf + 16 + k], (uint32_t)(tc[k] >> 10));
-	// the slowest wave: its clock, its trips (node steps + triangle tests, wave level) and the most trips any single lane-walk took
-	if (lane == 0) { atomicMax(&W.ctl[kWfCtlProf + 24], (uint32_t)(tc[0] >> 10)); atomicMax(&W.ctl[kWfCtlProf + 25], pt[2] + pt[3]); }
-	atomicMax(&W.ctl[kWfCtlProf + 26], walk_steps > walk_max ? walk_steps : walk_max);
-	// when the waves ended: their own clock binned by log2 of kilocycles (ctl[kWfCtlProf + 32 .. + 63])
-	if (lane == 0) { const uint32_t kc = (uint32_t)(tc[0] >> 10); atomicAdd(&W.ctl[kWfCtlProf + 32 + (kc ? 31 - __builtin_clz(kc) : 0)], 1u); if (pt[1] == 0) atomicAdd(&W.ctl[kWfCtlProf + 32 + 31], 1u); }
-#endif
-}
-
-// ------------------------------------------------------------------------------------ traverse, one loop
-// The same walks as k_wf_traverse, organised as ONE loop without inner loops: per trip every busy lane advances by one step of
-// core::mesh::intersect — a node step (mesh.cpp:327-370) when it stands on a branch, a triangle test (mesh.cpp:381-389) when it
-// stands in a leaf — and ALL the trip's fetches (the branch lanes' child pair, the leaf lanes' triangle record) are issued together
-// at the top, so that a trip waits for memory once. In the nested loops a wave made one dependent fetch per node trip and per
-// triangle trip, each at 22-38 % of the lanes (a lane that reached its leaf waited for the slowest descent, and the other way round):
-// 14-26 lane steps per pair took 17-33 M wave trips per 25 M pairs; here the lanes of a wave step together: the same steps in a
-// third of the trips. The pending-subtree stack keeps what the reference's stack keeps (mesh.cpp:317-325: node, min_dist, max_dist)
-// with the node's CONTENT (8 bytes) in place of its pointer — both children are in registers when one of them is set aside, and a
-// pop needs no fetch — as 16-byte entries in LDS (one ds_write_b128 / ds_read_b128; a register-held top would be rotated with a
-// dozen moves on every push and pop of any lane). The surface's root node is read once per staged unit (wave-uniform). Nodes and
-// triangle records live in ONE allocation (upload_scene): every fetch is `base + 32-bit offset`.
+// Persistent 256-thread workgroups (59 VGPRs, 24 KB of LDS, no scratch). Every lane walks ONE pair's tree (core::mesh::intersect,
+// mesh.cpp:300-405) and takes its next pair from the wave's LDS-staged unit as soon as the walk ends. A wave takes work one SEGMENT (the
+// entries one classify tile queued for one surface: contiguous, <= 1024) at a time with one atomic on the surface's cursor, and stages
+// it in units of 64 entries with coalesced loads — the entries carry the local ray and the result slot, nothing is gathered.
+// The walks are organised as ONE loop without inner loops: per trip every busy lane advances by one step of core::mesh::intersect — a
+// node step (mesh.cpp:327-370) when it stands on a branch, a triangle test (mesh.cpp:381-389) when it stands in a leaf — and ALL the
+// trip's fetches (the branch lanes' child pair, the leaf lanes' triangle record) are issued together at the top, so that a trip waits
+// for memory once. An earlier nested-loop form (a descend loop and a leaf loop per round; measured and removed, profiles/EXPERIMENTS.md)
+// made one dependent fetch per node trip and per triangle trip, each at 22-38 % of the lanes (a lane that reached its leaf waited for
+// the slowest descent, and the other way round): 14-26 lane steps per pair took 17-33 M wave trips per 25 M pairs; here the lanes of a
+// wave step together: the same steps in a third of the trips. The pending-subtree stack keeps what the reference's stack keeps
+// (mesh.cpp:317-325: node, min_dist, max_dist) with the node's CONTENT (8 bytes) in place of its pointer — both children are in
+// registers when one of them is set aside, and a pop needs no fetch — as 16-byte entries in LDS (one ds_write_b128 / ds_read_b128; a
+// register-held top would be rotated with a dozen moves on every push and pop of any lane). The surface's root node is read once per
+// staged unit (wave-uniform). Nodes and triangle records live in ONE allocation (upload_scene): every fetch is `base + 32-bit offset`,
+// which is why the kernel reads only leaf-ordered records in an allocation below 4 GB (wf_eligible, ptx_api.cpp).
 #ifndef PTX_WF_LDS_STACK2
 #define PTX_WF_LDS_STACK2 4
 #endif
 constexpr int kWfLdsStack2 = PTX_WF_LDS_STACK2;
-constexpr int kWfMaxStack = kRegStack + kSpillStack;   // entries a walk may set aside (the nested kernels' bound: 27 > mesh.hpp:34's 25 levels)
+constexpr int kWfMaxStack = kRegStack + kSpillStack;   // entries a walk may set aside (the fused kernel's bound, mesh_traverse: 27 > mesh.hpp:34's 25 levels)
 struct alignas(8) NodePair { uint32_t x, y, z, w; };   // two adjacent 8-byte nodes: 8-byte aligned, fetched as one 16-byte load
 
-// BLOCK2 (measurement: PTX_WF_BLOCK2=1): the node array in 2-LEVEL BLOCKS (DevScene::nodes2, upload_scene: a branch at even depth owns 48
-// contiguous bytes = its child pair, then the child pairs of its two children) — a lane that stands on such a branch fetches the whole
-// block with the trip's three loads and makes TWO node steps in the trip: half the dependent fetches per descent, three times the
-// bytes per fetch. Node word 1 there: axis | has-left << 2 | has-right << 3 | block-root << 4 | child pair index << 5.
-template <bool BLOCK2>
 __global__ void __launch_bounds__(kWfBlock) k_wf_traverse2(DevScene S0, WfBuffers W, const SurfaceRec* __restrict__ t_surfaces) {
 	DevScene S = S0;
 	S.surfaces = t_surfaces;
@@ -491,7 +252,6 @@ __global__ void __launch_bounds__(kWfBlock) k_wf_traverse2(DevScene S0, WfBuffer
 	uint4* const spill4 = reinterpret_cast<uint4*>(W.spill) + (size_t)(blockIdx.x * (kWfBlock / 64) + wave) * (kSpillStack * 64) + lane;
 	const unsigned char* const geom = reinterpret_cast<const unsigned char*>(S.nodes);
 	const uint32_t tri_off = (uint32_t)(reinterpret_cast<const unsigned char*>(S.tri_isect) - geom);   // same allocation (upload_scene)
-	[[maybe_unused]] const uint32_t n2_off = BLOCK2 ? (uint32_t)(reinterpret_cast<const unsigned char*>(S.nodes2) - geom) : 0u;
 	const uint32_t n_surf = S.n_surfaces;
 	const uint32_t n_order = ((n_surf + 7u) / 8u) * 8u;
 
@@ -533,7 +293,7 @@ __global__ void __launch_bounds__(kWfBlock) k_wf_traverse2(DevScene S0, WfBuffer
 							u = __builtin_amdgcn_readfirstlane(u);
 							if (u < 0) { more = false; break; }
 							unit_surf = u;
-							const uint2 r = BLOCK2 ? S.roots2[u] : S.nodes[S.surfaces[u].kd_root];
+							const uint2 r = S.nodes[S.surfaces[u].kd_root];
 							root_nd = make_uint2(__builtin_amdgcn_readfirstlane(r.x), __builtin_amdgcn_readfirstlane(r.y));
 						}
 						uint32_t g = 0;
@@ -605,53 +365,38 @@ __global__ void __launch_bounds__(kWfBlock) k_wf_traverse2(DevScene S0, WfBuffer
 		const uint32_t count = nd.y >> 2;   // of a leaf
 		const bool tri = busy && leaf && k < count;
 		// every lane fetches (no join, no copies): a lane with nothing to fetch reads the allocation's first 16 bytes
-		const bool broot = BLOCK2 && branch && (nd.y & 16u);
-		const uint32_t off = branch ? (BLOCK2 ? n2_off + (nd.y >> 5) * 16u : (nd.y >> 4) * 8u) : (tri ? tri_off + (nd.x + k) * 48u : 0u);
+		const uint32_t off = branch ? (nd.y >> 4) * 8u : (tri ? tri_off + (nd.x + k) * 48u : 0u);
 		const NodePair q0 = *reinterpret_cast<const NodePair*>(geom + off);
 		float4 r1, r2;
-		if (tri || broot) { r1 = *reinterpret_cast<const float4*>(geom + off + 16u); r2 = *reinterpret_cast<const float4*>(geom + off + 32u); }
-		// ---- node step (mesh.cpp:327-370; see mesh_traverse): on `cur` with its child pair (kid0, kid1); `on` = the lane makes this step
-		bool descend = false, dead_end = false;
-		uint2 next_nd = nd;
-		bool next_is_kid0 = true;
-		auto node_step = [&](bool on, uint2 cur, uint2 kid0, uint2 kid1) {
-			const uint32_t axis = cur.y & 3u;
-			const float split = __uint_as_float(cur.x);
-			const float oa = sel3(o, axis), da = sel3(d, axis);
-			const float split_dist = (split - oa) / da;
-			const bool has_l = cur.y & 4u, has_r = cur.y & 8u;
-			const bool left_first = oa < split;
-			// children sit at slot 0 (left, or right when there is no left) and slot 1 (right when both exist): kid0 / kid1
-			const bool first_is_kid0 = left_first || !has_l, second_is_kid0 = !left_first || !has_l;
-			const bool has_first = left_first ? has_l : has_r, has_second = left_first ? has_r : has_l;
-			const bool outside = split_dist < 0 || split_dist > max_dist;           // only the near child (mesh.cpp:354-357)
-			const bool far_only = !outside && split_dist < min_dist;                 // only the far child (:358-361)
-			const bool both = on && !outside && !far_only;                           // near child now, far child set aside (:362-369)
-			const bool push = both && has_second && sp < kWfMaxStack;
-			if (push) {
-				WFPROF(7);
-				const uint2 c = second_is_kid0 ? kid0 : kid1;
-				const uint4 ent = make_uint4(c.x, c.y, __float_as_uint(split_dist), __float_as_uint(max_dist));
-				if (sp < kWfLdsStack2) s_stk[sp][threadIdx.x] = ent; else spill4[(sp - kWfLdsStack2) * 64] = ent;
-			}
-			sp += push ? 1 : 0;
-			max_dist = both ? split_dist : max_dist;
-			const bool has_next = far_only ? has_second : has_first;
-			const bool k0 = far_only ? second_is_kid0 : first_is_kid0;
-			descend = on ? has_next : descend;
-			dead_end = on ? !has_next : dead_end;
-			next_is_kid0 = on ? k0 : next_is_kid0;
-			next_nd = (on && has_next) ? (k0 ? kid0 : kid1) : next_nd;
-		};
+		if (tri) { r1 = *reinterpret_cast<const float4*>(geom + off + 16u); r2 = *reinterpret_cast<const float4*>(geom + off + 32u); }
+		// ---- node step (mesh.cpp:327-370; see mesh_traverse) of a branch lane, with the child pair (kid0, kid1) just fetched
 		if (branch) WFPROF(2);
-		node_step(branch, nd, make_uint2(q0.x, q0.y), make_uint2(q0.z, q0.w));
-		if constexpr (BLOCK2) {
-			// second level of the block: the child just chosen is a branch, and its child pair came with the block
-			const bool two = broot && descend && (next_nd.y & 3u) != KD_LEAF;
-			if (two) WFPROF(2);
-			const float4 gk = next_is_kid0 ? r1 : r2;
-			node_step(two, next_nd, make_uint2(__float_as_uint(gk.x), __float_as_uint(gk.y)), make_uint2(__float_as_uint(gk.z), __float_as_uint(gk.w)));
+		const uint2 kid0 = make_uint2(q0.x, q0.y), kid1 = make_uint2(q0.z, q0.w);
+		const uint32_t axis = nd.y & 3u;
+		const float split = __uint_as_float(nd.x);
+		const float oa = sel3(o, axis), da = sel3(d, axis);
+		const float split_dist = (split - oa) / da;
+		const bool has_l = nd.y & 4u, has_r = nd.y & 8u;
+		const bool left_first = oa < split;
+		// children sit at slot 0 (left, or right when there is no left) and slot 1 (right when both exist): kid0 / kid1
+		const bool first_is_kid0 = left_first || !has_l, second_is_kid0 = !left_first || !has_l;
+		const bool has_first = left_first ? has_l : has_r, has_second = left_first ? has_r : has_l;
+		const bool outside = split_dist < 0 || split_dist > max_dist;           // only the near child (mesh.cpp:354-357)
+		const bool far_only = !outside && split_dist < min_dist;                 // only the far child (:358-361)
+		const bool both = branch && !outside && !far_only;                       // near child now, far child set aside (:362-369)
+		const bool push = both && has_second && sp < kWfMaxStack;
+		if (push) {
+			WFPROF(7);
+			const uint2 c = second_is_kid0 ? kid0 : kid1;
+			const uint4 ent = make_uint4(c.x, c.y, __float_as_uint(split_dist), __float_as_uint(max_dist));
+			if (sp < kWfLdsStack2) s_stk[sp][threadIdx.x] = ent; else spill4[(sp - kWfLdsStack2) * 64] = ent;
 		}
+		sp += push ? 1 : 0;
+		max_dist = both ? split_dist : max_dist;
+		const bool has_next = far_only ? has_second : has_first;
+		const bool k0 = far_only ? second_is_kid0 : first_is_kid0;
+		const bool descend = branch && has_next, dead_end = branch && !has_next;
+		const uint2 next_nd = descend ? (k0 ? kid0 : kid1) : nd;
 		// ---- triangle test: nearest triangle of the leaf with t <= max_dist; ties keep the first (mesh.cpp:381-389)
 		if (tri) WFPROF(3);
 		const PRay pr = pack_ray(o, d);
@@ -950,14 +695,8 @@ __global__ void __launch_bounds__(kWfBlock) k_wf_shade(DevScene S0, RenderParams
 // ------------------------------------------------------------------------------------ launchers
 static int wf_classify_grid(int n_cu) { return n_cu * (int)(2048u / kWfTile); }   // persistent 1024-thread workgroups (51 VGPRs: two per CU)
 
-// PTX_WF_KERNEL=1 (measurement): the nested-loop form of the traverse kernel instead of the one-loop form
 static void launch_traverse(const DevScene& S, const WfBuffers& W, int n_cu, hipStream_t stream) {
-	const char* const e = getenv("PTX_WF_KERNEL");   // read per launch: the tests switch it inside one process
-	const bool nested = e && e[0] == '1';
-	// the one-loop kernel reads a leaf's records in place (leaf-ordered copy) at 32-bit offsets from the nodes
-	if (nested || !S.glb_leaf_ordered || S.geom_bytes > 0xFFFFFFFFull) hipLaunchKernelGGL(k_wf_traverse, dim3(wf_traverse_grid(n_cu)), dim3(kWfBlock), 0, stream, S, W, S.surfaces);
-	else if (S.nodes2 && getenv("PTX_WF_BLOCK2")) hipLaunchKernelGGL(k_wf_traverse2<true>, dim3(wf_traverse_grid(n_cu)), dim3(kWfBlock), 0, stream, S, W, S.surfaces);
-	else hipLaunchKernelGGL(k_wf_traverse2<false>, dim3(wf_traverse_grid(n_cu)), dim3(kWfBlock), 0, stream, S, W, S.surfaces);
+	hipLaunchKernelGGL(k_wf_traverse2, dim3(wf_traverse_grid(n_cu)), dim3(kWfBlock), 0, stream, S, W, S.surfaces);
 }
 
 // One slice of a batch: W.ctl must be zeroed, W.n_in == nullptr (the slice's ray count is known to the host)

@@ -717,18 +717,14 @@ def test_queue_pipeline_frames_bitwise_equal_fused_kernel(ptx, ctx, integrator):
                dict(W=160, H=90, spp=5, bounces=4, spp_per_pass=2)):
         a, st = _both_pipelines(atr, integrator=integrator, **kw)
         assert np.isfinite(a).all()
-    # many small slabs per pass (a pair budget of 1 Mi pairs: 65 536-path slabs), and two slabs side by side on two streams
-    import os
-    for var, val in (("PTX_WF_PAIRS_M", "1"), ("PTX_WF_TWO_STREAMS", "1")):
-        os.environ[var] = val
-        try:
-            _both_pipelines(atr, W=480, H=270, spp=3, bounces=5, integrator=integrator)
-            if var == "PTX_WF_PAIRS_M":
-                os.environ["PTX_WF_TWO_STREAMS"] = "1"
-                _both_pipelines(atr, W=480, H=270, spp=2, bounces=4, integrator=integrator, tile=(100, 50, 300, 200))
-                os.environ.pop("PTX_WF_TWO_STREAMS")
-        finally:
-            os.environ.pop(var, None)
+    # many small slabs per pass (a pair budget of 1 Mi pairs: 65 536-path slabs), with and without a tile, then the default pool
+    os.environ["PTX_WF_PAIRS_M"] = "1"
+    try:
+        _both_pipelines(atr, W=480, H=270, spp=3, bounces=5, integrator=integrator)
+        _both_pipelines(atr, W=480, H=270, spp=2, bounces=4, integrator=integrator, tile=(100, 50, 300, 200))
+    finally:
+        os.environ.pop("PTX_WF_PAIRS_M", None)
+    _both_pipelines(atr, W=480, H=270, spp=3, bounces=5, integrator=integrator)
     plaza = product_from_dict(ptx, ctx, _proc().plaza_scene(level=3, sun=True, alpha=True))   # shadow catcher + translucent sphere + sun
     if plaza.info()["lds_resident"] != 1:
         _both_pipelines(plaza, W=160, H=90, spp=4, bounces=6, integrator=integrator)
@@ -785,11 +781,12 @@ def test_two_shards_back_to_back_without_stats(ptx, scene):
         np.testing.assert_array_equal(acc.cpu().numpy(), full)
 
 
-def test_queue_pipeline_pool_overflow_nested_kernel_and_timing(ptx, ctx, monkeypatch):
+def test_queue_pipeline_pool_overflow_and_timing(ptx, ctx, monkeypatch):
     """The pair pool is sized from demand: with a guess of the pairs per ray that is far too low (PTX_WF_RATIO_GUESS) and a small pool the
-    first slab overflows; the library repeats it in smaller slabs and the frame and the ray count are those of the fused kernel. The
-    nested-loop form of the traverse kernel (PTX_WF_KERNEL=1) gives the same frame as the one-loop form; ptx_ctx_get_timing reports the
-    per-kernel split and the workspace."""
+    first slab overflows; the library repeats it in smaller slabs and the frame and the ray count are those of the fused kernel, and so
+    are the hit records of a batch. ptx_ctx_get_timing reports the per-kernel split and the workspace. A scene whose global-memory copy
+    holds one record per triangle (PTX_LEAF_ORDER=0 at creation), which the traverse kernel does not read, renders through the fused
+    kernel even under PTX_WAVEFRONT=1, with the default scene's frame."""
     from conftest import product_from_dict
     kw = dict(W=480, H=270, spp=3, bounces=5)
     with _Pipeline(False):
@@ -808,11 +805,10 @@ def test_queue_pipeline_pool_overflow_nested_kernel_and_timing(ptx, ctx, monkeyp
     assert tm["peak_pairs"] > 0 and tm["pool_pairs"] == 1 << 20 and tm["workspace_bytes"] > 0
     assert tm["pool_overflows"] >= 1                               # the first attempt (the whole pass as one slab) did not fit the pool
     monkeypatch.delenv("PTX_WF_RATIO_GUESS"); monkeypatch.delenv("PTX_WF_PAIRS_M")
-    monkeypatch.setenv("PTX_WF_KERNEL", "1")
     with _Pipeline(True):
-        nested, nst = fresh.render(**kw)
-    np.testing.assert_array_equal(_bits(nested), _bits(ref))
-    assert nst["rays"] == rst["rays"]
+        again, ast = fresh.render(**kw)                            # on the workspace the first frame left behind
+    np.testing.assert_array_equal(_bits(again), _bits(ref))
+    assert ast["rays"] == rst["rays"]
     rng = np.random.default_rng(5)
     cam = fresh.array(ptx.ARR_CAMERA)
     d = rng.standard_normal((50_000, 3)).astype(np.float32)
@@ -820,8 +816,7 @@ def test_queue_pipeline_pool_overflow_nested_kernel_and_timing(ptx, ctx, monkeyp
     org = np.tile(cam[:3].astype(np.float32), (len(d), 1))
     with _Pipeline(True):
         h1 = fresh.intersect(org, d)
-    monkeypatch.delenv("PTX_WF_KERNEL")
-    with _Pipeline(True):
+    with _Pipeline(False):
         h0 = fresh.intersect(org, d)
     for k in h0:
         np.testing.assert_array_equal(np.asarray(h1[k]).view(np.uint32), np.asarray(h0[k]).view(np.uint32), err_msg=k)
@@ -830,32 +825,16 @@ def test_queue_pipeline_pool_overflow_nested_kernel_and_timing(ptx, ctx, monkeyp
         fresh.render(**kw)
         assert ctx.timing()["pipeline"] == 0 and ctx.timing()["fused_ms"] > 0
         ctx.set_timing(False)
-
-
-def test_two_level_node_blocks_variant(ptx, ctx, monkeypatch):
-    """PTX_WF_BLOCK2=1 (measurement switch, read at scene creation and per launch): the traverse kernel fetches a 2-level block of
-    nodes (48 B) per dependent fetch and makes two node steps per trip. Same walks, same results: frame and hit records bitwise equal."""
-    from conftest import product_from_dict
-    kw = dict(W=200, H=120, spp=2, bounces=6)
-    with _Pipeline(False):
-        ref, rst = product_from_dict(ptx, ctx, _proc().atrium_scene(2)).render(**kw)
-    monkeypatch.setenv("PTX_WF_BLOCK2", "1")
-    blk = product_from_dict(ptx, ctx, _proc().atrium_scene(2))
+    monkeypatch.setenv("PTX_LEAF_ORDER", "0")
+    per_tri = product_from_dict(ptx, ctx, _proc().atrium_scene(2))
+    monkeypatch.delenv("PTX_LEAF_ORDER")
     with _Pipeline(True):
-        got, st = blk.render(**kw)
-    np.testing.assert_array_equal(_bits(got), _bits(ref))
-    assert st["rays"] == rst["rays"]
-    rng = np.random.default_rng(11)
-    cam = blk.array(ptx.ARR_CAMERA)
-    d = rng.standard_normal((40_000, 3)).astype(np.float32)
-    d /= np.linalg.norm(d, axis=1, keepdims=True).astype(np.float32)
-    org = np.tile(cam[:3].astype(np.float32), (len(d), 1))
-    with _Pipeline(True):
-        h1 = blk.intersect(org, d)
-    with _Pipeline(False):
-        h0 = blk.intersect(org, d)
-    for k in h0:
-        np.testing.assert_array_equal(np.asarray(h1[k]).view(np.uint32), np.asarray(h0[k]).view(np.uint32), err_msg=k)
+        ctx.set_timing(True)
+        pt, pst = per_tri.render(**kw)
+        assert ctx.timing()["pipeline"] == 0
+        ctx.set_timing(False)
+    np.testing.assert_array_equal(_bits(pt), _bits(ref))
+    assert pst["rays"] == rst["rays"]
 
 
 def test_queue_pipeline_intersections_bitwise_equal_fused_kernel(ptx, ctx):

@@ -26,8 +26,7 @@ from test_gpu_parity import _check_hits, _scene_parity
 
 W, H, SPP, B = 64, 36, 2, 5                 # per-sample radiance against the oracle
 FW, FH, FSPP = 128, 72, 4                   # frames for the ray counts and the route agreement
-ROUTE_VARS = ("PTX_WAVEFRONT", "PTX_FORCE_GLOBAL", "PTX_SURFACE_UNITS", "PTX_NO_HYBRID", "PTX_WF_PAIRS_M", "PTX_WF_RATIO_GUESS",
-              "PTX_WF_TWO_STREAMS", "PTX_WF_KERNEL", "PTX_WF_BLOCK2")
+ROUTE_VARS = ("PTX_WAVEFRONT", "PTX_FORCE_GLOBAL", "PTX_SURFACE_UNITS", "PTX_NO_HYBRID", "PTX_WF_PAIRS_M", "PTX_WF_RATIO_GUESS")
 
 
 def _proc():
