@@ -161,6 +161,7 @@ def lib():
         L.ptx_tonemap_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ptx_pbr_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_camera_rays_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.ptx_material_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_reduce_framebuffer.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         L.ptx_encode_png.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.ptx_free.argtypes = [C.c_void_p]
@@ -357,6 +358,15 @@ class Scene:
         a = np.ascontiguousarray(ndc_ratio, np.float32).reshape(-1, 3)
         out = np.zeros((len(a), 6), np.float32)
         _check(lib().ptx_camera_rays_batch(self.h, a.ctypes.data, len(a), out.ctypes.data))
+        return out
+
+    def material_eval(self, surface, uv):
+        """ptx_material_eval_batch: surface index (scalar or [n] int) and [n,2] float32 uvs -> [n,12] float32 normal_ts(3), albedo(3),
+        opacity, roughness, metallic, emissive(3) * 10 = core::material::get_* as the shading kernels evaluate them."""
+        a = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(surface, np.int32), (len(a),)))
+        out = np.zeros((len(a), 12), np.float32)
+        _check(lib().ptx_material_eval_batch(self.h, s.ctypes.data, a.ctypes.data, len(a), out.ctypes.data))
         return out
 
     def intersect(self, origins, dirs, attributes=True):

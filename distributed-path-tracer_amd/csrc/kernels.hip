@@ -599,6 +599,26 @@ __global__ void k_camera_rays(DevScene S, const float* __restrict__ in, float* _
 	q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = d.x; q[4] = d.y; q[5] = d.z;
 }
 
+// ------------------------------------------------------------------------------------ batch material lookups
+// core::material::get_normal / albedo / opacity / roughness / metallic / emissive * 10 exactly as shade_vertex evaluates them
+// (material_eval<true> on the surface's ShadeRec material), one record per lane (ptx_material_eval_batch). A surface id outside
+// [0, n_surfaces) gives a row of NaNs.
+__global__ void k_material_eval(DevScene S, const int32_t* __restrict__ surface, const float* __restrict__ uv, size_t n, float* __restrict__ out) {
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	float* q = out + 12 * i;
+	const int32_t s = surface[i];
+	if (s < 0 || (uint32_t)s >= S.n_surfaces) {
+		for (int k = 0; k < 12; k++) q[k] = __builtin_nanf("");
+		return;
+	}
+	const MatEval e = material_eval<true>(S, S.shade[s].mat, uv[2 * i], uv[2 * i + 1]);
+	q[0] = e.normal_ts.x; q[1] = e.normal_ts.y; q[2] = e.normal_ts.z;
+	q[3] = e.albedo.x; q[4] = e.albedo.y; q[5] = e.albedo.z;
+	q[6] = e.opacity; q[7] = e.roughness; q[8] = e.metallic;
+	q[9] = e.emissive10.x; q[10] = e.emissive10.y; q[11] = e.emissive10.z;
+}
+
 // ------------------------------------------------------------------------------------ tonemap + encode
 // core::tonemap_approx_aces (core/utils.hpp:29-36) + image::image::write (image/image.cpp:143-154)
 DEV float aces1(float x) {
@@ -698,6 +718,10 @@ hipError_t launch_pbr_eval(const float* in, float* out, size_t n, hipStream_t st
 }
 hipError_t launch_camera_rays(const DevScene& S, const float* in, float* out, size_t n, hipStream_t stream) {
 	hipLaunchKernelGGL(k_camera_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, S, in, out, n);
+	return hipGetLastError();
+}
+hipError_t launch_material_eval(const DevScene& S, const int32_t* surface, const float* uv, size_t n, float* out, hipStream_t stream) {
+	hipLaunchKernelGGL(k_material_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, S, surface, uv, n, out);
 	return hipGetLastError();
 }
 hipError_t launch_tonemap(const float4* accum, uint32_t n_pixels, float spp, const float* thresholds, uchar4* out, hipStream_t stream) {

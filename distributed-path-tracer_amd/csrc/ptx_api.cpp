@@ -1228,6 +1228,38 @@ int ptx_camera_rays_batch(ptx_scene* sc, const float* ndc_ratio, size_t n, float
 	return PTX_OK;
 }
 
+int ptx_material_eval_batch(ptx_scene* sc, const int32_t* surface, const float* uv, size_t n, float* out) {
+	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_material_eval_batch: scene is NULL");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_material_eval_batch: scene was created without a GPU context (no CPU path exists)");
+	if (n == 0) return PTX_OK;
+	if (!surface || !uv || !out) return set_err(PTX_ERR_INVALID, "ptx_material_eval_batch: NULL argument");
+	if (n > (size_t)0x7FFFFFFF) return set_err(PTX_ERR_INVALID, "ptx_material_eval_batch: batch too large");
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	const bool dev = is_device_ptr(out);
+	if (dev != is_device_ptr(surface) || dev != is_device_ptr(uv))
+		return set_err(PTX_ERR_INVALID, "ptx_material_eval_batch: surface, uv and out must all be device or all be host memory");
+	const int32_t* d_surf = surface;
+	const float* d_uv = uv;
+	float* d_out = out;
+	if (!dev) {
+		HIP_TRY(c->stage_a.ensure(n * 12));
+		HIP_TRY(c->stage_b.ensure(n * 12 * 4));
+		HIP_TRY(hipMemcpyAsync(c->stage_a.p, uv, n * 8, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync((char*)c->stage_a.p + n * 8, surface, n * 4, hipMemcpyHostToDevice, c->stream));
+		d_uv = (const float*)c->stage_a.p;
+		d_surf = (const int32_t*)((const char*)c->stage_a.p + n * 8);
+		d_out = (float*)c->stage_b.p;
+	}
+	HIP_TRY(launch_material_eval(sc->dev, d_surf, d_uv, n, d_out, c->stream));
+	if (!dev) {
+		HIP_TRY(hipMemcpyAsync(out, d_out, n * 12 * 4, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+	}
+	return PTX_OK;
+}
+
 int ptx_reduce_framebuffer(ptx_ctx* c, void* nccl_comm, float* accum, size_t n_floats, int root) {
 	if (!c || !nccl_comm || !accum) return set_err(PTX_ERR_INVALID, "ptx_reduce_framebuffer: NULL argument");
 	if (!is_device_ptr(accum)) return set_err(PTX_ERR_INVALID, "ptx_reduce_framebuffer: accum must be device memory");

@@ -237,6 +237,13 @@ int ptx_intersect_batch(ptx_scene* scene, const ptx_rays* rays, size_t n, const 
  * in [n][3]: ndc.x, ndc.y, aspect ratio;  out [n][6]: ray origin(3), direction(3). Pointers device or host (both of one kind). */
 int ptx_camera_rays_batch(ptx_scene* scene, const float* ndc_ratio, size_t n, float* rays);
 
+/* Batch form of core::material::get_normal / get_albedo / get_opacity / get_roughness / get_metallic / get_emissive (LIB/core/material.cpp:6-53,
+ * bilinear image_texture::sample lookups): what the shading kernels compute at a hit, evaluated by the same device function.
+ * surface[n] (surface index in ptx_scene order), uv[n][2];  out[n][12]: normal_ts(3), albedo(3), opacity, roughness, metallic,
+ * emissive(3) * 10 (the factor renderer::trace applies, renderer.cpp:462). A surface index outside [0, n_surfaces) gives a row of NaNs.
+ * Pointers device or host (all of one kind). */
+int ptx_material_eval_batch(ptx_scene* scene, const int32_t* surface, const float* uv, size_t n, float* out);
+
 /* Batch form of the SHADING stage's sampling functions — core::pbr::importance_diffuse / importance_specular / pdf_diffuse /
  * pdf_specular / fresnel (LIB/core/pbr.cpp:71-184), util::rand_cone_vec (LIB/util/rand_cone_vec.cpp:8-35) and core::reflect
  * (LIB/core/utils.hpp:38-40) — evaluated by the same device functions the integrator kernel inlines. Function-level check of the

@@ -8,6 +8,7 @@ fixtures themselves are committed so the tests run anywhere.
 
     python oracle/make_golden.py            # all fixtures (about 2 minutes)
     python oracle/make_golden.py --no-mean  # skip the converged mean images
+    python oracle/make_golden.py --only-textures   # the texture fixture scene and tex_vectors.npz (a few seconds)
 """
 import argparse
 import glob
@@ -190,17 +191,222 @@ def make_hdr_fixtures(env):
     print(f"hdr_vectors.npz written ({os.path.getsize(os.path.join(GOLD, 'hdr_vectors.npz')) / 1024:.0f} KiB)")
 
 
+TEX_DIR = os.path.join(GOLD, "textures")
+TEX_GLTF = os.path.join(TEX_DIR, "textures.gltf")
+
+
+def _texture_images(rng):
+    """The fixture's images: every PNG flavour of test_png_reader_against_pil at sizes that are not powers of two (one 16 x 16 control),
+    and two Radiance .hdr files. -> {file name: (PIL image or float array, size)}"""
+    from PIL import Image
+
+    def px(w, h, c):
+        a = (rng.random((h, w, c)) * 256).astype(np.uint8)
+        a[0, :, 0] = np.linspace(0, 255, w).astype(np.uint8)           # full-range texels on the first row / column
+        a[:, 0, -1] = np.linspace(255, 0, h).astype(np.uint8)
+        return a
+
+    def pal(w, h, trns):
+        im = Image.fromarray((rng.random((h, w)) * 7).astype(np.uint8), "P")
+        im.putpalette(list(px(7, 1, 3).reshape(-1)) + [0] * (3 * 249))
+        if trns:
+            im.info["transparency"] = bytes([0, 90, 255, 13, 200, 255, 41])
+        return im
+    out = {
+        "l_7x1.png": Image.fromarray(px(7, 1, 1)[..., 0], "L"),
+        "la_1x5.png": Image.fromarray(px(1, 5, 2), "LA"),
+        "la_37x53.png": Image.fromarray(px(37, 53, 2), "LA"),
+        "rgb_37x53.png": Image.fromarray(px(37, 53, 3), "RGB"),
+        "rgba_3x5.png": Image.fromarray(px(3, 5, 4), "RGBA"),
+        "rgba_16x16.png": Image.fromarray(px(16, 16, 4), "RGBA"),
+        "p_255x3.png": pal(255, 3, False),
+        "pt_1x1.png": pal(1, 1, True),
+        "l16_255x3.png": Image.fromarray((px(255, 3, 2)[..., 0].astype(np.uint16) * 257 + px(255, 3, 1)[..., 0]).astype("<u2")),
+        "l1_37x53.png": Image.fromarray((px(37, 53, 1)[..., 0] > 127).astype(np.uint8) * 255, "L").convert("1"),
+    }
+    emit = (rng.random((5, 6, 3)) * np.float32(2.5)).astype(np.float32)
+    emit[0, 0] = (0, 0, 0)                                              # e == 0: black
+    mr = (rng.random((3, 13, 3)) * np.float32(1.2)).astype(np.float32)
+    out["emit_6x5.hdr"] = emit
+    out["mr_13x3.hdr"] = mr
+    return out
+
+
+# Surfaces of the fixture scene, in file order (one primitive each): material, grid cell (column, row), depth (BLEND quads sit in
+# front of the quad behind them), uv of the lower-left and upper-right corners. Texture loads go through get_cached_texture
+# (renderer.cpp:33-51): rgb_37x53 is first a normal map (linear) and later a base colour, la_1x5 first a base colour (sRGB) and later
+# a normal map, so both keep the flag of their first use.
+TEX_SURFACES = [
+    ("plain", {"pbrMetallicRoughness": {"baseColorFactor": [0.8, 0.6, 0.4, 1.0], "roughnessFactor": 0.7, "metallicFactor": 0.2},
+               "emissiveFactor": [0.1, 0.05, 0.02]}, (0, 0), 0.0, (-2.3, -2.3), (3.7, 3.7)),
+    ("normal_rgb_base_rgba", {"normalTexture": "rgb_37x53.png", "pbrMetallicRoughness": {"baseColorTexture": "rgba_3x5.png",
+                              "baseColorFactor": [0.9, 0.7, 0.5, 0.6], "roughnessFactor": 0.45, "metallicFactor": 0.3},
+                              "emissiveFactor": [0.05, 0.05, 0.05]}, (1, 0), 0.0, (-2.21, -2.27), (3.69, 3.66)),
+    ("blend_la", {"alphaMode": "BLEND", "pbrMetallicRoughness": {"baseColorTexture": "la_1x5.png", "baseColorFactor": [1.0, 0.9, 0.8, 0.75]},
+                  "emissiveFactor": [0.3, 0.2, 0.1]}, (2, 0), 0.4, (-2.3, -2.1), (3.5, 3.7)),
+    ("mr_grey_emissive_palette", {"normalTexture": "l16_255x3.png", "pbrMetallicRoughness": {"metallicRoughnessTexture": "l_7x1.png",
+                                  "roughnessFactor": 0.8, "metallicFactor": 0.6}, "emissiveTexture": "p_255x3.png",
+                                  "emissiveFactor": [0.5, 0.4, 0.3]}, (2, 0), 0.0, (-2.3, -2.3), (3.7, 3.7)),
+    ("blend_palette_trns", {"alphaMode": "BLEND", "pbrMetallicRoughness": {"baseColorTexture": "pt_1x1.png", "baseColorFactor": [0.6, 0.8, 1.0, 0.9],
+                            "metallicRoughnessTexture": "la_37x53.png", "roughnessFactor": 0.9, "metallicFactor": 0.5},
+                            "emissiveFactor": [0.02, 0.3, 0.2]}, (0, 1), 0.4, (-1.9, -2.3), (3.7, 3.3)),
+    ("cached_linear_base_emissive_1bit", {"occlusionTexture": "la_37x53.png", "pbrMetallicRoughness": {"baseColorTexture": "rgb_37x53.png"},
+                                          "emissiveTexture": "l1_37x53.png", "emissiveFactor": [0.25, 0.5, 0.75]}, (0, 1), 0.0, (-2.3, -2.3), (3.7, 3.7)),
+    ("emissive_hdr_srgb", {"pbrMetallicRoughness": {"baseColorTexture": "rgba_16x16.png", "roughnessFactor": 0.3},
+                           "emissiveTexture": "emit_6x5.hdr", "emissiveFactor": [0.4, 0.3, 0.2]}, (3, 0), 0.0, (-2.3, -2.3), (3.7, 3.7)),
+    ("mr_hdr_linear_normal_la", {"normalTexture": "la_1x5.png", "pbrMetallicRoughness": {"metallicRoughnessTexture": "mr_13x3.hdr",
+                                 "baseColorFactor": [0.5, 0.5, 0.9, 1.0], "roughnessFactor": 0.6, "metallicFactor": 0.9},
+                                 "emissiveFactor": [0.1, 0.1, 0.3]}, (1, 1), 0.0, (-2.0, -2.2), (3.1, 3.6)),
+    ("blend_pow2_unit_uv", {"alphaMode": "BLEND", "normalTexture": "l_7x1.png", "occlusionTexture": "l1_37x53.png",
+                            "pbrMetallicRoughness": {"baseColorTexture": "rgba_16x16.png", "baseColorFactor": [1.0, 1.0, 1.0, 0.8]},
+                            "emissiveFactor": [0.2, 0.2, 0.2]}, (2, 1), 0.4, (0.0, 0.0), (1.0, 1.0)),
+    ("cached_srgb_base_l16", {"pbrMetallicRoughness": {"baseColorTexture": "l16_255x3.png", "roughnessFactor": 0.2, "metallicFactor": 0.0},
+                              "emissiveTexture": "rgba_3x5.png", "emissiveFactor": [0.3, 0.1, 0.2]}, (2, 1), 0.0, (-2.3, -2.3), (3.7, 3.7)),
+]
+
+
+def write_texture_scene():
+    """tests/golden/textures/: a glTF scene of textured 1.4 x 1.4 quads facing a camera on +Z, one primitive per material of
+    TEX_SURFACES, and textures.npz (the surfaces' texture sizes, for the uv sets). Deterministic: rewrites identical files."""
+    from PIL import Image
+    rng = np.random.default_rng(20261016)
+    os.makedirs(TEX_DIR, exist_ok=True)
+    images = _texture_images(rng)
+    for name, im in images.items():
+        if name.endswith(".hdr"):
+            write_hdr(os.path.join(TEX_DIR, name), im, im.shape[1] >= 8)
+        else:
+            im.save(os.path.join(TEX_DIR, name), optimize=True)
+    names = sorted(images)
+    blob = bytearray()
+
+    def view(arr, target=None):
+        off = len(blob)
+        blob.extend(np.ascontiguousarray(arr).tobytes())
+        while len(blob) % 4:
+            blob.append(0)
+        bv = {"buffer": 0, "byteOffset": off, "byteLength": arr.nbytes}
+        if target:
+            bv["target"] = target
+        views.append(bv)
+        return len(views) - 1
+    views, accessors, prims, mats = [], [], [], []
+
+    def accessor(arr, ctype, kind, **kw):
+        accessors.append(dict(bufferView=view(arr), componentType=ctype, count=len(arr), type=kind, **kw))
+        return len(accessors) - 1
+    nrm = accessor(np.tile(np.float32([0, 0, 1]), (4, 1)), 5126, "VEC3")
+    tan = accessor(np.tile(np.float32([1, 0, 0, 1]), (4, 1)), 5126, "VEC4")
+    idx = accessor(np.uint16([0, 1, 2, 0, 2, 3]), 5123, "SCALAR")
+    for k, (mname, m, (cx, cy), z, uv0, uv1) in enumerate(TEX_SURFACES):
+        x0, y0 = -2.4 + 1.6 * cx - 0.7, 0.8 - 1.6 * cy - 0.7
+        p = np.float32([[x0, y0, z], [x0 + 1.4, y0, z], [x0 + 1.4, y0 + 1.4, z], [x0, y0 + 1.4, z]])
+        uv = np.float32([[uv0[0], uv1[1]], [uv1[0], uv1[1]], [uv1[0], uv0[1]], [uv0[0], uv0[1]]])   # glTF v points down the image
+        pa = accessor(p, 5126, "VEC3", min=[float(v) for v in p.min(0)], max=[float(v) for v in p.max(0)])
+        prims.append({"attributes": {"POSITION": pa, "NORMAL": nrm, "TANGENT": tan, "TEXCOORD_0": accessor(uv, 5126, "VEC2")},
+                      "indices": idx, "material": k})
+        mm = json.loads(json.dumps(m))
+        for slot in ("normalTexture", "occlusionTexture", "emissiveTexture"):
+            if slot in mm:
+                mm[slot] = {"index": names.index(mm[slot])}
+        pbr = mm.get("pbrMetallicRoughness", {})
+        for slot in ("baseColorTexture", "metallicRoughnessTexture"):
+            if slot in pbr:
+                pbr[slot] = {"index": names.index(pbr[slot])}
+        mats.append(dict(name=mname, **mm))
+    with open(os.path.join(TEX_DIR, "textures.bin"), "wb") as fh:
+        fh.write(bytes(blob))
+    s = float(np.sin(0.15))
+    g = {"asset": {"version": "2.0", "generator": "oracle/make_golden.py --only-textures"},
+         "extensionsUsed": ["KHR_lights_punctual"],
+         "extensions": {"KHR_lights_punctual": {"lights": [{"name": "sun", "type": "directional", "intensity": 3.0, "color": [1.0, 0.95, 0.9]}]}},
+         "scene": 0, "scenes": [{"nodes": [0, 1, 2]}],
+         "cameras": [{"name": "cam", "type": "perspective", "perspective": {"yfov": 0.9, "znear": 0.01, "aspectRatio": 1.7778}}],
+         "nodes": [{"name": "cam", "camera": 0, "translation": [0.0, 0.0, 6.0]},
+                   {"name": "sun", "rotation": [-s, 0.0, 0.0, float(np.cos(0.15))], "extensions": {"KHR_lights_punctual": {"light": 0}}},
+                   {"name": "quads", "mesh": 0}],
+         "meshes": [{"name": "quads", "primitives": prims}], "materials": mats,
+         "images": [{"uri": n} for n in names], "textures": [{"source": i} for i in range(len(names))],
+         "buffers": [{"uri": "textures.bin", "byteLength": len(blob)}], "bufferViews": views, "accessors": accessors}
+    with open(TEX_GLTF, "w") as fh:
+        json.dump(g, fh, indent=1)
+        fh.write("\n")
+    size = {n: (im.shape[1], im.shape[0]) if isinstance(im, np.ndarray) else im.size for n, im in images.items()}
+    return [[size[t] for t in _texture_files(m)] for _, m, *_ in TEX_SURFACES]
+
+
+def _texture_files(m):
+    pbr = m.get("pbrMetallicRoughness", {})
+    return [x for x in (m.get("normalTexture"), pbr.get("baseColorTexture"), m.get("occlusionTexture"), pbr.get("metallicRoughnessTexture"),
+                        m.get("emissiveTexture")) if x]
+
+
+def texture_uv_sets(sizes, seed=5):
+    """Per surface, the uvs where lookups go wrong first: the random set of `materials` (same recipe), every texel edge k/w and centre
+    (k + 0.5)/w of the surface's textures in both axes, signed zeros, 1 and its neighbours, values out to +-1e4, |u w| in each range
+    of the float -> int64 -> uint32 conversion ([2^24, 2^31), [2^31, 2^32), [2^32, 2^63), >= 2^63), infinities and NaN.
+    sizes: per surface, the (w, h) of its textures. -> float32 [n_surfaces][n][2] (every list padded to the longest with random uvs)."""
+    f = np.float32
+    rng = np.random.default_rng(seed)
+    sets = []
+    for wh in sizes:
+        r = rng.uniform(-1.5, 2.5, (256, 2)).astype(f)
+        r[::4] = rng.random((64, 2)).astype(f)
+        r[::31] = rng.integers(0, 5, (len(r[::31]), 2)).astype(f) - f(2)
+        special = [0.0, -0.0, 1.0, float(np.nextafter(f(1), f(2))), float(np.nextafter(f(1), f(0))), float(np.nextafter(f(0), f(-1))),
+                   -float(np.finfo(f).eps), 0.5, -0.5, 2.0, -2.0, 3.7, -2.3, 123.456, -123.456, 1e4, -1e4, 9999.5, -9999.5,
+                   float("inf"), float("-inf"), float("nan")]
+        axes = []
+        for ax in (0, 1):                                   # u runs along the width, v along the height, from the top (cy = (1 - v) h)
+            vals = set(special)
+            for w in sorted({s[ax] for s in wh} | {1}):
+                k = np.arange(w + 1, dtype=f)
+                e = np.concatenate([k / f(w), (k[:-1] + f(0.5)) / f(w)])
+                vals.update((e if ax == 0 else np.concatenate([e, f(1) - e])).tolist())
+                for m in (2.0 ** 24 * 1.37, 2.0 ** 31 * 1.21, 2.0 ** 32 * 1.5, 2.0 ** 32 * 5 + 2.0 ** 20, 2.0 ** 44 * 1.7, 2.0 ** 62 * 1.5,
+                          2.0 ** 63, 2.0 ** 63 * 1.25, 2.0 ** 64, 2.0 ** 70 * 1.1, 1e30, 3.0e38):
+                    vals.update([float(f(m) / f(w)), float(-(f(m) / f(w))), float(f(1) - f(m) / f(w)), float(f(1) + f(m) / f(w))])
+            axes.append(np.array(sorted(vals, key=lambda x: (np.isnan(x), x)), f))
+        sp = np.array(special, f)
+        uv = [r, np.stack([axes[0], rng.random(len(axes[0])).astype(f)], 1), np.stack([rng.random(len(axes[1])).astype(f), axes[1]], 1),
+              np.stack(np.meshgrid(sp, sp), -1).reshape(-1, 2)]
+        sets.append(np.concatenate(uv).astype(f))
+    n = max(len(s) for s in sets)
+    return np.stack([np.concatenate([s, rng.uniform(-2.3, 3.7, (n - len(s), 2)).astype(f)]) for s in sets])
+
+
+def make_texture_fixtures(env):
+    """The texture fixture scene (write_texture_scene) and tests/golden/tex_vectors.npz: material::get_* of the compiled reference at
+    the uvs of texture_uv_sets, per surface."""
+    uv = texture_uv_sets(write_texture_scene())
+    with tempfile.TemporaryDirectory() as tmp:
+        uvf = os.path.join(tmp, "uv.f32")
+        uv.astype("<f4").tofile(uvf)
+        d = os.path.join(tmp, "out")
+        subprocess.check_call([HARNESS, "materials_at", TEX_GLTF, uvf, d], env=env)
+        out = {k: np.load(os.path.join(d, k + ".npy")) for k in ("mat_in", "mat_out")}
+    assert out["mat_in"].tobytes() == uv.astype("<f4").tobytes()
+    np.savez_compressed(os.path.join(GOLD, "tex_vectors.npz"), **out)
+    total = sum(os.path.getsize(os.path.join(TEX_DIR, x)) for x in os.listdir(TEX_DIR))
+    print(f"textures/: {len(os.listdir(TEX_DIR))} files, {total / 1024:.0f} KiB; tex_vectors.npz: {out['mat_in'].shape}, "
+          f"{os.path.getsize(os.path.join(GOLD, 'tex_vectors.npz')) / 1024:.0f} KiB")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-mean", action="store_true")
     ap.add_argument("--only-trace", action="store_true", help="regenerate trace_vectors.npz only")
     ap.add_argument("--only-jpeg", action="store_true", help="regenerate tests/golden/jpeg/* and jpeg_vectors.npz only")
     ap.add_argument("--only-hdr", action="store_true", help="regenerate tests/golden/hdr/* and hdr_vectors.npz only")
+    ap.add_argument("--only-textures", action="store_true", help="regenerate tests/golden/textures/* and tex_vectors.npz only")
     ap.add_argument("--n", type=int, default=1024)
     args = ap.parse_args()
     subprocess.check_call(["make", "-s", "-j8", "-C", HERE, "ref"])
     os.makedirs(GOLD, exist_ok=True)
     env = dict(os.environ, ORACLE_SEED="20261004")
+    if args.only_textures:
+        make_texture_fixtures(env)
+        return
     if args.only_jpeg:
         make_jpeg_fixtures(env)
         return
@@ -268,6 +474,7 @@ def main():
         pack(d, os.path.join(GOLD, "env_vectors.npz"))
         make_jpeg_fixtures(env)
         make_hdr_fixtures(env)
+        make_texture_fixtures(env)
         # a small deterministic PNG from renderer::render itself (single thread + fixed seed => reproducible)
         png = os.path.join(GOLD, "cornell_ref_64x64_16spp_4b.png")
         r = subprocess.check_output([HARNESS, "render", CORNELL, "64", "64", "16", "4", "1", png], env=env)

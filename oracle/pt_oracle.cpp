@@ -916,6 +916,16 @@ void ora_scene_set_textures(void* p, int n_images, const int* whc_srgb /*[n][4]*
 	for (size_t k = 0; k < s->surfaces.size(); k++)
 		for (int j = 0; j < 7; j++) s->surfaces[k].mat.tex[j] = surf_tex[7 * k + j];
 }
+// ... then image `index` of that set becomes a Radiance .hdr as image::hdr keeps it: the decoded floats (w, h, c; sRGB flag)
+int ora_scene_set_texture_f32(void* p, int index, int w, int h, int c, int srgb, const float* data) {
+	scene_t* s = (scene_t*)p;
+	if (index < 0 || (size_t)index >= s->textures.size() || w < 1 || h < 1 || c < 1 || c > 4 || !data) return -1;
+	texture& t = s->textures[(size_t)index];
+	t.w = w; t.h = h; t.c = c; t.srgb = srgb != 0;
+	t.data.clear();
+	t.fdata.assign(data, data + (size_t)w * h * c);
+	return 0;
+}
 // renderer::environment = image_texture (8-bit image, c channels, sRGB flag); data == nullptr removes it
 void ora_scene_set_environment(void* p, int w, int h, int c, int srgb, const uint8_t* data) {
 	scene_t* s = (scene_t*)p;

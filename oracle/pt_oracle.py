@@ -78,7 +78,7 @@ class SceneArrays:
     material_tex: np.ndarray = None  # [n_surf, 7]    has normal/albedo/opacity/occlusion/roughness/metallic/emissive tex
     camera: np.ndarray = None        # [14]           origin3 basis9 fov tan_half_fov
     sun: np.ndarray = None           # [13] basis9 energy3 angular_radius, or None
-    images: list = field(default_factory=list)       # decoded 8-bit images [H, W, C] (as stb_image returns them)
+    images: list = field(default_factory=list)       # decoded images [H, W, C] as stb_image returns them: uint8, float32 for .hdr
     image_srgb: list = field(default_factory=list)   # sRGB flag each image was FIRST loaded with (renderer.cpp:33-51 cache)
     image_paths: list = field(default_factory=list)
     surf_tex: np.ndarray = None      # [n_surf, 7]    image index per material slot or -1
@@ -170,7 +170,8 @@ def load_gltf(path, camera_index=0, sun_light_index=0, work=None) -> SceneArrays
         path = os.path.join(base, uri).replace("%20", " ")
         if path not in tex_cache:
             tex_cache[path] = len(out_images)
-            out_images.append(_decode_image(path)); out_srgb.append(bool(srgb)); out_paths.append(path)
+            out_images.append(_decode_hdr(path) if _is_hdr(path) else _decode_image(path))   # by content, as image::image::load
+            out_srgb.append(bool(srgb)); out_paths.append(path)
         return tex_cache[path]
 
     def make_entity(ni, parent):
@@ -389,11 +390,15 @@ class OracleScene:
         self.n_models = len(a.model_xform)
         self.n_surf = len(a.surf_range)
         if a.images:
-            self._img = [np.ascontiguousarray(im, np.uint8) for im in a.images]
+            # 8-bit images go in as stb_image's bytes; a .hdr image (float32) is then set with its floats, in the same slot
+            self._img = [np.ascontiguousarray(im, np.float32 if im.dtype == np.float32 else np.uint8) for im in a.images]
             meta = np.array([[im.shape[1], im.shape[0], im.shape[2], int(sr)] for im, sr in zip(self._img, a.image_srgb)], np.int32)
-            ptrs = (C.c_void_p * len(self._img))(*[im.ctypes.data for im in self._img])
+            ptrs = (C.c_void_p * len(self._img))(*[im.ctypes.data for im in self._img])   # a float image's bytes: in bounds, replaced below
             st = np.ascontiguousarray(a.surf_tex, np.int32)
             L.ora_scene_set_textures(self.h, len(self._img), _p(meta), ptrs, _p(st))
+            for i, (im, sr) in enumerate(zip(self._img, a.image_srgb)):
+                if im.dtype == np.float32 and L.ora_scene_set_texture_f32(self.h, i, im.shape[1], im.shape[0], im.shape[2], int(bool(sr)), _p(im)) != 0:
+                    raise RuntimeError(f"ora_scene_set_texture_f32: image {i} refused")
 
     def set_environment(self, png_path, srgb=True):
         """renderer::environment = image_texture::load(path, srgb) (renderer.hpp:28); None removes it."""

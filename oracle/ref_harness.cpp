@@ -13,6 +13,7 @@
 //   scene   <gltf> <outdir>                     dump the loaded scene + KD trees as .npy
 //   vectors <gltf> <outdir> <seed> <n>          function-level known-answer vectors as .npy
 //   materials <gltf> <outdir> <seed> <n>        per surface: material::get_* (texture lookups) at n random uvs
+//   materials_at <gltf> <uvfile> <outdir>       the same at given uvs (raw float32 [n_surfaces][n][2])
 //   envmap <gltf> <png> <srgb> <outdir> <seed> <n>   environment-map lookups: equirectangular_proj + image_texture::sample + trace() on misses
 //   image   <file> <outdir> <seed> <n>               decoded pixels of image::image::load's stb_image call (JPEG / PNG) + n bilinear
 //                                                     image_texture::sample lookups on it (linear and sRGB)
@@ -478,6 +479,39 @@ static int cmd_materials(const char* gltf, const std::string& dir, uint64_t seed
 	return 0;
 }
 
+// The same getters at caller-given uvs: `uvfile` holds raw little-endian float32, [n_surfaces][n][2] (n from the file size), one
+// uv list per surface in visit order.
+static int cmd_materials_at(const char* gltf, const char* uvfile, const std::string& dir) {
+	core::renderer r;
+	load(r, gltf);
+	std::filesystem::create_directories(dir);
+	auto models = visit_order(r);
+	size_t ns = 0;
+	for (auto& m : models) ns += m.model->surfaces.size();
+	std::ifstream f(uvfile, std::ios::binary | std::ios::ate);
+	const size_t bytes = (size_t)f.tellg();
+	if (ns == 0 || bytes % (8 * ns) != 0) { fprintf(stderr, "materials_at: %zu bytes is not [%zu][n][2] float32\n", bytes, ns); return 2; }
+	const size_t n = bytes / (8 * ns);
+	std::vector<float> in(bytes / 4), out;
+	f.seekg(0);
+	f.read((char*)in.data(), (std::streamsize)bytes);
+	size_t s = 0;
+	for (auto& m : models)
+		for (auto& sf : m.model->surfaces) {
+			auto& mt = *sf.material;
+			for (size_t i = 0; i < n; i++) {
+				const fvec2 uv(in[2 * (s * n + i)], in[2 * (s * n + i) + 1]);
+				fvec3 nrm = mt.get_normal(uv), alb = mt.get_albedo(uv), em = mt.get_emissive(uv);
+				push3(out, nrm); push3(out, alb); out.push_back(mt.get_opacity(uv)); out.push_back(mt.get_roughness(uv));
+				out.push_back(mt.get_metallic(uv)); push3(out, em);
+			}
+			s++;
+		}
+	save(dir, "mat_in", in, {ns, n, 2});
+	save(dir, "mat_out", out, {ns, n, 12});
+	return 0;
+}
+
 // renderer::trace's miss branch with an environment map (renderer.cpp:443-449): core::equirectangular_proj
 // (core/utils.hpp:22-27) and image::image_texture::sample on a PNG loaded the way a caller of the library would
 // (image_texture::load(path, srgb)). Also one trace() per direction from far outside the scene, with the map set.
@@ -643,6 +677,7 @@ int main(int argc, char** argv) {
 		if (cmd == "scene" && argc == 4) return cmd_scene(argv[2], argv[3]);
 		if (cmd == "vectors" && argc == 6) return cmd_vectors(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10));
 		if (cmd == "materials" && argc == 6) return cmd_materials(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10));
+		if (cmd == "materials_at" && argc == 5) return cmd_materials_at(argv[2], argv[3], argv[4]);
 		if (cmd == "envmap" && argc == 8) return cmd_envmap(argv[2], argv[3], atoi(argv[4]), argv[5], strtoull(argv[6], 0, 10), strtoull(argv[7], 0, 10));
 		if (cmd == "image" && argc == 6) return cmd_image(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10));
 		if (cmd == "trace" && argc == 7) return cmd_trace(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10), atoi(argv[6]));
