@@ -160,6 +160,7 @@ def lib():
         L.ptx_intersect_batch.argtypes = [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(Hits)]
         L.ptx_tonemap_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ptx_pbr_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.ptx_exact_math_check.argtypes = [C.c_void_p, C.c_void_p]
         L.ptx_camera_rays_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_material_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_reduce_framebuffer.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -227,6 +228,15 @@ class Context:
         out = np.zeros((len(a), 15), np.float32)
         _check(lib().ptx_pbr_eval_batch(self.h, a.ctypes.data, len(a), out.ctypes.data))
         return out
+
+    EXACT_MATH_FORMS = ("rcp", "sqrt", "rsqrt")
+
+    def exact_math_check(self):
+        """ptx_exact_math_check: the kernels' short reciprocal / square-root forms against the IEEE expressions over every float
+        pattern. Returns {form: number of results whose bits differ (NaN equals NaN)}."""
+        out = np.zeros(len(self.EXACT_MATH_FORMS), np.uint64)
+        _check(lib().ptx_exact_math_check(self.h, out.ctypes.data))
+        return {n: int(v) for n, v in zip(self.EXACT_MATH_FORMS, out)}
 
     def tonemap_encode(self, accum, W, H, spp, out=None):
         """accum: [H,W,4] float32 sums (numpy or torch-on-GPU). Returns/filles RGBA8 [H,W,4]."""

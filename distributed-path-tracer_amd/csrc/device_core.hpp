@@ -31,6 +31,46 @@ constexpr float kEps = 0.0001f;                        // math::epsilon (math/ma
 constexpr double kPi = 3.14159265358979323846;         // math::pi is double (math/math.hpp:18)
 constexpr double kInvSqrt3 = 1.0 / 1.7320508075688772; // 1 / math::sqrt3 (util/rand_cone_vec.cpp:23)
 
+// ------------------------------------------------------------------------------------ exact short reciprocal / square root
+// Built without fast math, `1.0f / x` compiles to LLVM's general IEEE division (2 v_div_scale, v_rcp, 5 fma-class, v_mul,
+// v_div_fmas, v_div_fixup: ≈ 33 issue cycles) and sqrtf to 16 instructions (denormal scaling, v_sqrt, a ±1-ulp correction,
+// unscaling, a v_cmp_class fix-up: ≈ 48 cycles). The shorter sequences below give the same bits; each comment states on which
+// operands. tests/test_exact_math.py runs the *_exact forms as compiled here (ptx_exact_math_check) over all 2^32 inputs against the
+// IEEE expressions. (Short divisions a / b by a known RN(1 / b), Markstein's form, were measured too and lost: profiles/EXPERIMENTS.md.)
+// v_rcp_f32 and one Newton step: RN(1 / x) for 2^-125 <= |x| < 2^126. Outside (±0, ±inf, NaN, the denormals, the two edge binades)
+// the value is not IEEE's: rcp_key(x) < kRcpKeyEnd exactly on that range, so a loop may keep the largest key of its operands and
+// take the IEEE division for the whole loop when it ends beyond the range (mesh_traverse's leaf loop).
+DEV float rcp_core(float x) {
+	const float r = __builtin_amdgcn_rcpf(x);
+	return __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
+}
+DEV uint32_t rcp_key(float x) { return (__float_as_uint(x) & 0x7FFFFFFFu) - 0x01000000u; }   // |x| - 2^-125 on the bit patterns
+constexpr uint32_t kRcpKeyEnd = 0x7E800000u - 0x01000000u;                                   // 2^126 - 2^-125 on the bit patterns
+DEV float rcp_exact(float x) { return rcp_key(x) < kRcpKeyEnd ? rcp_core(x) : 1.0f / x; }       // what the leaf loop computes per triangle
+// v_sqrt_f32 (within 1 ulp) and LLVM's ±1-ulp correction by two remainders: RN(sqrt(x)) for 2^-96 <= x <= +inf, and also for ±0,
+// NaN and x < 0 (the correction keeps v_sqrt_f32's ±0 / NaN / +inf: no v_cmp_class fix-up is needed).
+DEV float sqrt_core(float x) {
+	const float s = __builtin_amdgcn_sqrtf(x);
+	const float dn = __uint_as_float(__float_as_uint(s) - 1u), up = __uint_as_float(__float_as_uint(s) + 1u);
+	const float r = __builtin_fmaf(-dn, s, x) <= 0.0f ? dn : s;
+	return __builtin_fmaf(-up, s, x) > 0.0f ? up : r;
+}
+// sqrtf(x) for every x: below 2^-96 the operand is scaled by 2^32 before and the root by 2^-16 after (both exact: a power of 4 in,
+// a power of 2 out, the root stays normal) — sqrtf's own sequence without its class fix-up
+DEV float sqrt_exact(float x) {
+	const bool tiny = x < 0x1p-96f;
+	const float r = sqrt_core(tiny ? x * 0x1p32f : x);
+	return tiny ? r * 0x1p-16f : r;
+}
+// 1.0f / sqrtf(x) (normalize) for every x: the same scaling, so that sqrt_core and rcp_core always work inside their ranges (the
+// reciprocal of the scaled root is normal: x * 2^16 is exact), then v_div_fixup_f32 for ±0 -> ±inf, +inf -> +0, NaN -> NaN
+DEV float rsqrt_exact(float x) {
+	const bool tiny = x < 0x1p-96f;
+	const float l = sqrt_core(tiny ? x * 0x1p32f : x);
+	const float r = rcp_core(l);
+	return __builtin_amdgcn_div_fixupf(tiny ? r * 0x1p16f : r, l, 1.0f);
+}
+
 // 3-vectors keep (x, y) in one register pair so that component-wise + - * compile to packed fp32 instructions (one
 // v_pk_* for x and y, one scalar op for z): the same IEEE operation per component, two per issue slot.
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -52,8 +92,8 @@ DEV V3 operator/(V3 a, float s) { return mk(a.x / s, a.y / s, a.z / s); }
 DEV V3 operator-(V3 a) { return mk2(-a.xy, -a.z); }
 DEV float dot(V3 a, V3 b) { const f2 p = a.xy * b.xy; return p.x + p.y + a.z * b.z; }     // math/vec3.inl:236
 DEV V3 cross(V3 l, V3 r) { return mk((l.y * r.z) - (l.z * r.y), (l.z * r.x) - (l.x * r.z), (l.x * r.y) - (l.y * r.x)); }
-DEV float length(V3 a) { return sqrtf(dot(a, a)); }
-DEV V3 normalize(V3 a) { return a * (1.0f / length(a)); }                                  // math/vec3.inl:251
+DEV float length(V3 a) { return sqrt_exact(dot(a, a)); }
+DEV V3 normalize(V3 a) { return a * rsqrt_exact(dot(a, a)); }                              // a * (1.0f / length(a)), math/vec3.inl:251
 DEV float pmax(float a, float b) { return b > a ? b : a; }                                 // math::max (NaN-asymmetric), math.inl:169
 DEV float pmin(float a, float b) { return b < a ? b : a; }                                 // math::min, math.inl:179
 DEV float lerpf(float a, float b, float w) { return a + (b - a) * w; }                     // math.inl:164
@@ -105,11 +145,14 @@ struct Tables {
 // The record pairs the edge components so that the cofactors come out as (c1, -c2), (c4, -c4), (c6, -c5): a term the
 // reference subtracts is then added with its sign already flipped, and x + (-y) == x - y, -(x*y) == (-x)*y exactly.
 // Returns the distance, or -1 when the barycentric tests fail (a NaN from a zero determinant fails `t >= 0` later).
+// SHORT: 1 / det by rcp_core; `key` keeps the largest rcp_key of the determinants, and when one lies outside rcp_core's range
+// (±0, degenerate or edge-on triangles, NaN) the caller tests the leaf again with the IEEE division — no test in the triangle loop.
 DEV f2 swp(f2 a) { return __builtin_shufflevector(a, a, 1, 0); }
 DEV f2 bc(float a) { return (f2){a, a}; }
 struct PRay { f2 oyz, dyz; float ox, dx; };   // the local ray, arranged for tri_test_pk
 DEV PRay pack_ray(V3 o, V3 d) { return {{o.y, o.z}, {d.y, d.z}, o.x, d.x}; }
-DEV float tri_test_pk(float4 r0, float4 r1, float2 r2, const PRay& r, float& beta, float& gamma) {
+template <bool SHORT>
+DEV float tri_test_pk(float4 r0, float4 r1, float2 r2, const PRay& r, float& beta, float& gamma, uint32_t& key) {
 	const f2 Pa = {r0.x, r0.y}, Pb = {r0.z, r0.w};               // (e2.y, e1.z), (e2.z, e1.y)
 	const f2 Ex = {r1.x, r1.y}, Ayz = {r1.z, r1.w};              // (e1.x, e2.x), (a.y, a.z)
 	const float c3 = r2.y;
@@ -120,7 +163,10 @@ DEV float tri_test_pk(float4 r0, float4 r1, float2 r2, const PRay& r, float& bet
 	const f2 c4s = m4 - swp(m4);                                 // (c4, -c4)
 	const f2 c6n5 = Pa * swp(vyz) - Pb * vyz;                    // (e2.y*v.z - v.y*e2.z, v.y*e1.z - e1.y*v.z) = (c6, -c5)
 	const f2 t12 = Ex * c1n2;                                    // (e1.x*c1, -(e2.x*c2))
-	const float inv_det = 1.0f / ((t12.x + t12.y) + r.dx * c3);
+	const float det = (t12.x + t12.y) + r.dx * c3;
+	float inv_det;
+	if constexpr (SHORT) { inv_det = rcp_core(det); const uint32_t k = rcp_key(det); key = k > key ? k : key; }
+	else inv_det = 1.0f / det;
 	const f2 X = bc(vx) * c1n2 - swp(Ex) * c4s;                  // (v.x*c1 - e2.x*c4, e1.x*c4 - v.x*c2)
 	const f2 N = X - bc(r.dx) * c6n5;                            // (.. - d.x*c6, .. + d.x*c5): numerators of beta, gamma
 	const f2 bg = bc(inv_det) * N;
@@ -129,6 +175,10 @@ DEV float tri_test_pk(float4 r0, float4 r1, float2 r2, const PRay& r, float& bet
 	beta = bg.x; gamma = bg.y;
 	const bool out = (bg.x < 0 - kEps) | (bg.x > 1 + kEps) | (bg.y < 0 - kEps) | (bg.y + bg.x > 1 + kEps);
 	return out ? -1.0f : t;
+}
+DEV float tri_test_pk(float4 r0, float4 r1, float2 r2, const PRay& r, float& beta, float& gamma) {
+	uint32_t unused = 0;
+	return tri_test_pk<false>(r0, r1, r2, r, beta, gamma, unused);
 }
 
 struct MeshHit { float t; float b1, b2; uint32_t tri; };
@@ -278,6 +328,7 @@ DEV bool mesh_traverse(const Geom& g, uint32_t root, float nr, float fr, V3 o, V
 		uint32_t first_ref = nd.x, count = nd.y >> 2;
 		float best_t = -1.0f, bb1 = 0, bb2 = 0;
 		uint32_t best_tri = 0;
+		uint32_t key = 0;
 		// (a software-pipelined form of this loop — triangle i + 1's reference and record requested before triangle i's solve — was
 		// measured: -2.7 % on Cornell, +2 % on jack-of-blades; the extra registers cost more than the latency 4 waves already hide)
 		for (uint32_t i = 0; i < count; i++) {
@@ -286,8 +337,18 @@ DEV bool mesh_traverse(const Geom& g, uint32_t root, float nr, float fr, V3 o, V
 			const float4 r0 = g.tris[3 * slot], r1 = g.tris[3 * slot + 1], r2 = g.tris[3 * slot + 2];
 			const uint32_t ti = __float_as_uint(r2.z);   // global triangle id, carried by every record
 			float be, ga;
-			const float t = tri_test_pk(r0, r1, make_float2(r2.x, r2.y), pr, be, ga);
+			const float t = tri_test_pk<true>(r0, r1, make_float2(r2.x, r2.y), pr, be, ga, key);
 			if (t >= 0 && t <= max_dist && (t < best_t || !(best_t >= 0))) { best_t = t; bb1 = be; bb2 = ga; best_tri = ti; }
+		}
+		if (key >= kRcpKeyEnd) {   // a determinant outside rcp_core's range: this lane's leaf once more, every triangle with the IEEE division
+			best_t = -1.0f; bb1 = 0; bb2 = 0; best_tri = 0;
+			for (uint32_t i = 0; i < count; i++) {
+				const uint32_t slot = g.leaf_ordered ? first_ref + i : g.refs[first_ref + i];
+				const float4 r0 = g.tris[3 * slot], r1 = g.tris[3 * slot + 1], r2 = g.tris[3 * slot + 2];
+				float be, ga;
+				const float t = tri_test_pk<false>(r0, r1, make_float2(r2.x, r2.y), pr, be, ga, key);
+				if (t >= 0 && t <= max_dist && (t < best_t || !(best_t >= 0))) { best_t = t; bb1 = be; bb2 = ga; best_tri = __float_as_uint(r2.z); }
+			}
 		}
 		if (!(best_t >= 0)) continue;
 		out.t = best_t; out.b1 = bb1; out.b2 = bb2; out.tri = best_tri;
@@ -488,7 +549,7 @@ DEV V3 shading_normal(const Surf& s, V3 nts) {
 // util::rand_cone_vec — util/rand_cone_vec.cpp:8-35
 DEV V3 rand_cone_vec(float rnd, float cos_theta, V3 normal) {
 	float phi = (float)((double)(rnd * 2) * kPi);
-	float sin_theta = sqrtf(1 - cos_theta * cos_theta);
+	float sin_theta = sqrt_exact(1 - cos_theta * cos_theta);
 	float sp, cp;
 #ifdef PTX_SEPARATE_SINCOS
 	sp = sinf(phi); cp = cosf(phi);
@@ -521,7 +582,7 @@ DEV V3 importance_sample(bool specular, float u1, float u2, V3 normal, V3 outcom
 	if (specular) {
 		roughness *= roughness;
 		roughness *= roughness;
-		cos_theta = sqrtf((1 - u1) / (1 + (roughness - 1) * u1));
+		cos_theta = sqrt_exact((1 - u1) / (1 + (roughness - 1) * u1));
 	} else {
 		cos_theta = cosf(acosf(2 * u1 - 1) * 0.5F);
 	}
@@ -775,11 +836,11 @@ DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParam
 	if (!(dot(normal, inc) > 0)) return V_DEAD;                              // renderer.cpp:578 / shading_worker.cpp:154,196-199
 	float pdf;
 	const V3 brdf = eval_brdf(normal, outcoming, inc, me.albedo, roughness, me.metallic, spec_prob, pdf);
-	const float ip = pmax(pdf, kEps);
+	const V3 q = brdf / pmax(pdf, kEps);   // brdf / max(pdf, eps), component by component
 	if constexpr (!WORKER) {
-		T = T * mk(clampf(brdf.x / ip, 0, 1), clampf(brdf.y / ip, 0, 1), clampf(brdf.z / ip, 0, 1));  // renderer.cpp:617-620
+		T = T * mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));                         // renderer.cpp:617-620
 	} else {
-		T = T * mk(brdf.x / ip, brdf.y / ip, brdf.z / ip);                                           // shading_worker.cpp:173
+		T = T * q;                                                                                   // shading_worker.cpp:173
 		T = mk(clampf(T.x, 0, 10.0f), clampf(T.y, 0, 10.0f), clampf(T.z, 0, 10.0f));                 // :175
 	}
 	o = sf.pos + inc * kEps;
@@ -789,7 +850,7 @@ DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParam
 			const float4 sr = draws(P, pixel, sample, depth, pass, BLOCK_SUN);   // lane z
 			const float p = pmax(T.x, pmax(T.y, T.z));
 			if (sr.z > p) return V_DEAD;
-			T = mk(T.x / p, T.y / p, T.z / p);
+			T = T / p;
 		}
 	}
 	depth++;

@@ -588,6 +588,23 @@ __global__ void k_pbr_eval(const float* __restrict__ in, float* __restrict__ out
 	q[12] = rf.x; q[13] = rf.y; q[14] = rf.z;
 }
 
+// ------------------------------------------------------------------------------------ exact-math self-check
+// The short reciprocal / square-root forms of device_core.hpp against the IEEE expressions they replace, over every float pattern x
+// (ptx_exact_math_check). Per form, the number of results whose bits differ (a NaN equals any NaN) is added to bad[form]:
+//   0 rcp_exact(x) / 1.0f / x     1 sqrt_exact(x) / sqrtf(x)     2 rsqrt_exact(x) / 1.0f / sqrtf(x)
+DEV uint32_t differs(float u, float v) { return (__float_as_uint(u) != __float_as_uint(v) && !(u != u && v != v)) ? 1u : 0u; }
+__global__ void k_exact_math_check(uint32_t form, unsigned long long* __restrict__ bad) {
+	const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+	uint32_t n_bad = 0;
+	for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < (1ull << 32); k += stride) {
+		const float x = __uint_as_float((uint32_t)k);
+		if (form == 0) n_bad += differs(rcp_exact(x), 1.0f / x);
+		else if (form == 1) n_bad += differs(sqrt_exact(x), sqrtf(x));
+		else n_bad += differs(rsqrt_exact(x), 1.0f / sqrtf(x));
+	}
+	if (n_bad) atomicAdd(bad + form, (unsigned long long)n_bad);
+}
+
 // ------------------------------------------------------------------------------------ batch camera rays
 // scene::camera::get_ray(ndc, ratio) exactly as the integrator kernels inline it, one record per lane (ptx_camera_rays_batch)
 __global__ void k_camera_rays(DevScene S, const float* __restrict__ in, float* __restrict__ out, size_t n) {
@@ -715,6 +732,14 @@ hipError_t launch_intersect(const DevScene& S, const IntersectArgs& A, int mode,
 hipError_t launch_pbr_eval(const float* in, float* out, size_t n, hipStream_t stream) {
 	hipLaunchKernelGGL(k_pbr_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, out, n);
 	return hipGetLastError();
+}
+hipError_t launch_exact_math_check(unsigned long long* bad, hipStream_t stream) {
+	for (uint32_t form = 0; form < kExactMathForms; form++) {
+		hipLaunchKernelGGL(k_exact_math_check, dim3(4096), dim3(256), 0, stream, form, bad);
+		const hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+	}
+	return hipSuccess;
 }
 hipError_t launch_camera_rays(const DevScene& S, const float* in, float* out, size_t n, hipStream_t stream) {
 	hipLaunchKernelGGL(k_camera_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, S, in, out, n);

@@ -165,6 +165,8 @@ hipError_t launch_render_pass(const DevScene& S, const RenderParams& P, const Pa
 hipError_t launch_resolve(const float4* sample_rad, float4* accum, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp, hipStream_t stream);
 hipError_t launch_intersect(const DevScene& S, const IntersectArgs& A, int mode, size_t lds_bytes, int grid, hipStream_t stream);
 hipError_t launch_pbr_eval(const float* in, float* out, size_t n, hipStream_t stream);
+constexpr uint32_t kExactMathForms = 3;   // k_exact_math_check: one counter per form
+hipError_t launch_exact_math_check(unsigned long long* bad /* [kExactMathForms], device, zeroed */, hipStream_t stream);
 hipError_t launch_camera_rays(const DevScene& S, const float* in /* [n][3]: ndc.x ndc.y ratio */, float* out /* [n][6] */, size_t n, hipStream_t stream);
 hipError_t launch_material_eval(const DevScene& S, const int32_t* surface /* [n] */, const float* uv /* [n][2] */, size_t n, float* out /* [n][12] */, hipStream_t stream);
 hipError_t launch_tonemap(const float4* accum, uint32_t n_pixels, float spp, const float* thresholds /* [256], device */, uchar4* out, hipStream_t stream);

@@ -1201,6 +1201,19 @@ int ptx_pbr_eval_batch(ptx_ctx* c, const float* in, size_t n, float* out) {
 	return PTX_OK;
 }
 
+int ptx_exact_math_check(ptx_ctx* c, uint64_t* mismatches) {
+	if (!c) return set_err(PTX_ERR_NO_DEVICE, "ptx_exact_math_check: no GPU context (no CPU path exists)");
+	if (!mismatches) return set_err(PTX_ERR_INVALID, "ptx_exact_math_check: NULL argument");
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	HIP_TRY(c->stage_b.ensure(kExactMathForms * 8));
+	HIP_TRY(hipMemsetAsync(c->stage_b.p, 0, kExactMathForms * 8, c->stream));
+	HIP_TRY(launch_exact_math_check((unsigned long long*)c->stage_b.p, c->stream));
+	HIP_TRY(hipMemcpyAsync(mismatches, c->stage_b.p, kExactMathForms * 8, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return PTX_OK;
+}
+
 int ptx_camera_rays_batch(ptx_scene* sc, const float* ndc_ratio, size_t n, float* rays) {
 	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_camera_rays_batch: scene is NULL");
 	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_camera_rays_batch: scene was created without a GPU context (no CPU path exists)");

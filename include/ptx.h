@@ -254,6 +254,12 @@ int ptx_material_eval_batch(ptx_scene* scene, const int32_t* surface, const floa
  * fresnel(outcoming, reflect(-outcoming, normal), ior), reflect(-outcoming, normal)(3). Pointers device or host (both of one kind). */
 int ptx_pbr_eval_batch(ptx_ctx* ctx, const float* in, size_t n, float* out);
 
+/* Self-check of the short reciprocal / square-root sequences the kernels use in place of the IEEE ones (device_core.hpp), as compiled
+ * into this library, guards and fallbacks included: every float pattern through each form. mismatches[3] receives, per form, the
+ * count of results whose bits differ from the IEEE expression (NaN equals NaN): 1.0f / x, sqrtf(x), 1.0f / sqrtf(x). All zero when
+ * the sequences are exact. */
+int ptx_exact_math_check(ptx_ctx* ctx, uint64_t* mismatches);
+
 /* ---- multi-GPU fan-in ------------------------------------------------------------------------------
  * The one exchange step of the path: the sum of the per-rank accumulation buffers on rank `root`. Replaces the
  * reference's planned (never implemented) SNS/SQS result fan-in (src/models/work_info.hpp:22-23,
