@@ -157,6 +157,7 @@ def lib():
         L.ptx_scene_get_array.restype = C.c_int64
         L.ptx_scene_get_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.ptx_render.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.POINTER(RenderStats)]
+        L.ptx_render_transparent.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.c_void_p, C.POINTER(RenderStats)]
         L.ptx_intersect_batch.argtypes = [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(Hits)]
         L.ptx_tonemap_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ptx_pbr_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -358,6 +359,26 @@ class Scene:
         stats = dict(rays=st.rays, samples=st.samples, passes=st.passes, kernel_ms=st.kernel_ms) if want_stats else None
         return accum, stats
 
+    def render_transparent(self, W, H, spp, bounces, pixels=None, claimed=None, env=(1.0, 1.0, 1.0), seed=0x5EED, tile=None, sample0=0,
+                           spp_per_pass=0, want_stats=True, integrator=INTEGRATOR_LIB, shard=None):
+        """ptx_render_transparent: core::renderer::render() with transparent_background set. Advances the reference's per-pixel blend
+        state — pixels [h,w,4] float32 (running colour and alpha: MEANS, not sums) and claimed [h,w] uint8, numpy or torch-on-GPU, both
+        of one kind — through samples [sample0, sample0+spp) in sample order. A frame starts from zeroed buffers at sample0 = 0 (the
+        default when none are given); later calls must continue with ascending, adjacent sample ranges on the same buffers. Tiles and
+        shards work as in render(); sample ranges rendered into separate buffers cannot be merged. INTEGRATOR_WORKER is refused.
+        Returns (pixels, claimed, stats dict or None)."""
+        x0, y0, w, h = tile if tile else (0, 0, W, H)
+        if (pixels is None) != (claimed is None):
+            raise PtxError(ERR_INVALID, "render_transparent: pass both pixels and claimed, or neither")
+        if pixels is None:
+            pixels, claimed = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.uint8)
+        cfg = RenderCfg(W, H, spp, bounces, (C.c_float * 3)(*env), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                        x0, y0, w, h, sample0, spp_per_pass, integrator, *((tuple(shard) + (0,))[:3] if shard else (0, 0, 0)))
+        st = RenderStats()
+        _check(lib().ptx_render_transparent(self.h, C.byref(cfg), _ptr(pixels), _ptr(claimed), C.byref(st) if want_stats else None))
+        stats = dict(rays=st.rays, samples=st.samples, passes=st.passes, kernel_ms=st.kernel_ms) if want_stats else None
+        return pixels, claimed, stats
+
     def set_environment(self, png_path, srgb=True):
         """renderer::environment = image_texture::load(png_path, srgb): the miss colour becomes map(direction) * environment_factor.
         None removes the map."""
@@ -439,19 +460,28 @@ class Renderer:
         self._ctx = Context(device)
         self._scene = None
         self.last_stats = None
+        self.last_claimed = None
 
     def load_gltf(self, path):
         self._scene = Scene.load_gltf(self._ctx, path, self.camera_index, self.sun_light_index)
 
     def render_accum(self):
+        """Radiance SUMS [H,W,4] of the frame; with transparent_background set, the reference's blended MEANS (colour, alpha) instead
+        (Scene.render_transparent) — `last_claimed` then holds the per-pixel claimed flags."""
         if self._scene is None:
             raise PtxError(ERR_INVALID, "render() before load_gltf()")
-        if self.transparent_background or self.visualize_kd_tree_depth:
-            raise PtxError(ERR_UNSUPPORTED, "transparent_background / visualize_kd_tree_depth are debug paths that are not built")
+        if self.visualize_kd_tree_depth:
+            # mesh.cpp:316-318 seeds each node's colour from the node's heap address: no two runs of the reference agree, so there is
+            # nothing reproducible to be faithful to
+            raise PtxError(ERR_UNSUPPORTED, "visualize_kd_tree_depth is not built: the reference colours KD nodes by their heap addresses (mesh.cpp:316-318)")
         W, H = self.resolution
         if self.environment != getattr(self, "_env_set", None):
             self._scene.set_environment(self.environment)
             self._env_set = self.environment
+        if self.transparent_background:
+            pixels, self.last_claimed, self.last_stats = self._scene.render_transparent(W, H, self.sample_count, self.bounce_count,
+                                                                                        env=self.environment_factor, seed=self.seed)
+            return pixels
         accum, self.last_stats = self._scene.render(W, H, self.sample_count, self.bounce_count,
                                                     env=self.environment_factor, seed=self.seed)
         return accum
@@ -459,4 +489,5 @@ class Renderer:
     def render(self):
         W, H = self.resolution
         accum = self.render_accum()
-        return encode_png(self._ctx.tonemap_encode(accum, W, H, self.sample_count))
+        # the blended means of the transparent mode are written as they are: spp = 1 (x / 1.0f is exact)
+        return encode_png(self._ctx.tonemap_encode(accum, W, H, 1 if self.transparent_background else self.sample_count))

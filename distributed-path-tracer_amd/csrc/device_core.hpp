@@ -858,6 +858,14 @@ DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParam
 	return depth == P.bounces ? V_DEAD : V_ALIVE;                            // trace(0, ..) is black: renderer.cpp:438-439; bounce > 0: shading_worker.cpp:193
 }
 
+// Alpha of a finished sample = trace()'s data.w (renderer.cpp:438-451, 643). 0 only with transparent_background set and a miss as the
+// top-level return: the camera ray missed, or the ray continued behind an opacity / lit-catcher pass-through did (renderer.cpp:471, 518:
+// same `bounce`, so depth is still 0). Bounce exhaustion, back faces, a shadowed catcher and every return below depth 0 are alpha 1.
+// The worker estimator never runs in this mode (ptx_render_transparent refuses it).
+DEV float sample_alpha(bool transparent_background, bool missed, bool depth0) {
+	return (transparent_background && missed && depth0) ? 0.0f : 1.0f;
+}
+
 // ------------------------------------------------------------------------------------ LDS staging
 struct Staged { Geoms g; const ShadeRec* shade; const float4* hot; };
 

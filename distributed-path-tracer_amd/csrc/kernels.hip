@@ -39,7 +39,10 @@ namespace ptx {
 //   EXTEND: (generate or) load ray -> closest hit -> 16-byte hit record        (traversal state only in registers)
 //   SHADE : load ray + hit + path state -> BSDF, radiance, next ray, shadow request -> compacted writes (no traversal)
 //   SHADOW: load request -> any hit? -> add the sun contribution / resolve a pending shadow catcher   (SUN variants)
-template <int MODE, bool SUN, bool ALPHA, bool TEX, bool WORKER, bool SURF>
+// TRANSP (renderer::transparent_background, RenderParams::transparent): a path that ends on a miss at depth 0 stores alpha 0. A template
+// parameter and not a test of the flag: at the 128-register cap the test moved the spills and scratch of most variants, so the
+// default kernels are compiled exactly as before and the mode runs ONE variant per (MODE, SURF) with everything compiled in.
+template <int MODE, bool SUN, bool ALPHA, bool TEX, bool WORKER, bool SURF, bool TRANSP>
 __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParams P, PassBuffers B, const ModelRec* __restrict__ t_models, const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space) {
 	DevScene S = S0;
 	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;  // see struct Tables
@@ -344,8 +347,13 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 					if constexpr (ALPHA) { const uint32_t dp = __float_as_uint(q3.y); depth = dp >> 16; pass = dp & 0xFFFFu; }
 					SceneHit h;
 					h.dist = 0; h.surface = __float_as_int(hq.x); h.tri = __float_as_uint(hq.y); h.b1 = hq.z; h.b2 = hq.w;
+					bool depth0 = false;
+					if constexpr (TRANSP) depth0 = depth == 0;   // before the vertex: a scatter raises depth, a miss leaves it
 					state = shade_vertex<SUN, ALPHA, TEX, WORKER>(S, st.shade, P, __float_as_uint(key_px), __float_as_uint(key_s), depth, pass, h, o, d, T, L, rq);
-					if (state == V_DEAD) B.sample_rad[id] = make_float4(L.x, L.y, L.z, 1.0f);
+					if (state == V_DEAD) {
+						if constexpr (TRANSP) B.sample_rad[id] = make_float4(L.x, L.y, L.z, sample_alpha(true, h.surface < 0, depth0));
+						else B.sample_rad[id] = make_float4(L.x, L.y, L.z, 1.0f);
+					}
 				}
 				const bool alive = state == V_ALIVE;
 				const uint64_t mask = __ballot(alive);
@@ -548,6 +556,40 @@ __global__ void k_resolve(const float4* __restrict__ sample_rad, float4* __restr
 	accum[dst] = a;
 }
 
+// core::renderer::render()'s blend with transparent_background set (renderer.cpp:374-399), for the samples of one pass: every pixel
+// goes through its samples in sample order on the reference's state {color, alpha, claimed}. `s` is the GLOBAL sample index (the
+// reference's loop variable, a uint32_t that the arithmetic promotes to float: vec3.inl:180-200). This is a recurrence, not a sum:
+// one operation per reference operation, binary32, no contraction. Pixels outside a sharded pass's list are not touched.
+__global__ void k_resolve_claim(const float4* __restrict__ sample_rad, float4* __restrict__ pixel_rgba, uint8_t* __restrict__ claimed, const uint32_t* __restrict__ pixels,
+                                uint32_t n_pixels, uint32_t pass_spp, uint32_t sample0) {
+	uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p >= n_pixels) return;
+	const uint32_t dst = pixels ? pixels[p] : p;
+	float4 a = pixel_rgba[dst];
+	bool cl = claimed[dst] != 0;
+	for (uint32_t k = 0; k < pass_spp; k++) {
+		const float4 r = sample_rad[(size_t)k * n_pixels + p];
+		const uint32_t s = sample0 + k;
+		const float fs = (float)s, fs1 = (float)(s + 1u);
+		if (r.w > 0.5f && !cl) {            // :375-380 an opaque sample claims the pixel: colour overwritten, alpha = 1 / (sample + 1) in INTEGERS
+			a.x = r.x; a.y = r.y; a.z = r.z;
+			a.w = (float)(1u / (s + 1u));
+			cl = true;
+		} else if (r.w < 0.5f && cl) {      // :382-386 a transparent sample on a claimed pixel blends alpha only
+			a.w = a.w * fs + r.w;
+			a.w = a.w / fs1;
+		} else if (r.w < 0.5f) {            // :388-391 a transparent sample on an unclaimed pixel: nothing
+		} else {                            // :395-398 an opaque sample on a claimed pixel
+			a.x = a.x * fs + r.x; a.y = a.y * fs + r.y; a.z = a.z * fs + r.z;
+			a.x = a.x / fs1; a.y = a.y / fs1; a.z = a.z / fs1;
+			a.w = a.w * fs + r.w;
+			a.w = a.w / fs1;
+		}
+	}
+	pixel_rgba[dst] = a;
+	claimed[dst] = cl ? 1 : 0;
+}
+
 // ------------------------------------------------------------------------------------ batch intersect
 template <int MODE>
 __global__ void __launch_bounds__(kBlock) k_intersect_batch(DevScene S0, IntersectArgs A, const ModelRec* __restrict__ t_models, const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space) {
@@ -675,22 +717,23 @@ static hipError_t set_lds(const void* fn, size_t bytes) {
 	return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-template <int MODE, bool SURF, bool SUN, bool ALPHA, bool TEX, bool WORKER = false>
+template <int MODE, bool SURF, bool SUN, bool ALPHA, bool TEX, bool WORKER = false, bool TRANSP = false>
 static hipError_t launch_pass_variant(const DevScene& S, const RenderParams& P, const PassBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
 	if (MODE != MODE_GLOBAL) {
-		hipError_t e = set_lds(reinterpret_cast<const void*>(&k_render_pass<MODE, SUN, ALPHA, TEX, WORKER, SURF>), lds_bytes);
+		hipError_t e = set_lds(reinterpret_cast<const void*>(&k_render_pass<MODE, SUN, ALPHA, TEX, WORKER, SURF, TRANSP>), lds_bytes);
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL((k_render_pass<MODE, SUN, ALPHA, TEX, WORKER, SURF>), dim3(grid), dim3(kBlock), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, B, S.models, S.surfaces, S.spaces, S.model_space);
+	hipLaunchKernelGGL((k_render_pass<MODE, SUN, ALPHA, TEX, WORKER, SURF, TRANSP>), dim3(grid), dim3(kBlock), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, B, S.models, S.surfaces, S.spaces, S.model_space);
 	return hipGetLastError();
 }
 
 // Kernel variants: {where the geometry lives} x {units set aside: models | surfaces} x {sun shadow rays} x {opacity / shadow-
 // catcher pass-through}; textured scenes and the worker estimator get one variant with everything compiled in (sun code is
-// skipped at run time without a sun).
+// skipped at run time without a sun), and so does the transparent-background mode (PTX_INTEGRATOR_LIB only: ptx_render_transparent).
 template <int MODE, bool SURF>
 static hipError_t launch_pass_mode(const DevScene& S, const RenderParams& P, const PassBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
 	const bool sun = S.sun.present != 0, alpha = S.any_alpha != 0;
+	if (P.transparent) return launch_pass_variant<MODE, SURF, true, true, true, false, true>(S, P, B, lds_bytes, grid, stream);
 	if (P.integrator == 1u)
 		return S.any_texture ? launch_pass_variant<MODE, SURF, true, true, true, true>(S, P, B, lds_bytes, grid, stream)
 		                     : launch_pass_variant<MODE, SURF, true, true, false, true>(S, P, B, lds_bytes, grid, stream);
@@ -713,6 +756,11 @@ hipError_t launch_render_pass(const DevScene& S, const RenderParams& P, const Pa
 }
 hipError_t launch_resolve(const float4* sample_rad, float4* accum, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp, hipStream_t stream) {
 	hipLaunchKernelGGL(k_resolve, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, sample_rad, accum, pixels, n_pixels, pass_spp);
+	return hipGetLastError();
+}
+hipError_t launch_resolve_claim(const float4* sample_rad, float4* pixel_rgba, uint8_t* claimed, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp, uint32_t sample0,
+                                hipStream_t stream) {
+	hipLaunchKernelGGL(k_resolve_claim, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, sample_rad, pixel_rgba, claimed, pixels, n_pixels, pass_spp, sample0);
 	return hipGetLastError();
 }
 template <int MODE>

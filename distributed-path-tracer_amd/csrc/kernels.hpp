@@ -83,6 +83,8 @@ struct RenderParams {
 	uint32_t sample0;           // first sample index of this pass
 	uint32_t pass_spp;          // samples per pixel in this pass
 	uint32_t bounces;
+	uint32_t transparent;       // renderer::transparent_background (ptx_render_transparent): a sample that ends on a miss at depth 0 stores alpha 0
+	                            // (k_wf_shade tests it; the fused kernel has a variant for it). Sits in what was padding: no other member moves
 	uint64_t n_paths;           // n_pixels * pass_spp
 	uint32_t seed_lo, seed_hi;
 	float env[3];
@@ -163,6 +165,8 @@ hipError_t launch_wf_intersect(const DevScene& S, const IntersectArgs& A, size_t
 hipError_t launch_render_pass(const DevScene& S, const RenderParams& P, const PassBuffers& B, int mode, size_t lds_bytes, int grid,
                               hipStream_t stream);
 hipError_t launch_resolve(const float4* sample_rad, float4* accum, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp, hipStream_t stream);
+hipError_t launch_resolve_claim(const float4* sample_rad, float4* pixel_rgba, uint8_t* claimed, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp,
+                                uint32_t sample0 /* global index of the pass's first sample */, hipStream_t stream);
 hipError_t launch_intersect(const DevScene& S, const IntersectArgs& A, int mode, size_t lds_bytes, int grid, hipStream_t stream);
 hipError_t launch_pbr_eval(const float* in, float* out, size_t n, hipStream_t stream);
 constexpr uint32_t kExactMathForms = 3;   // k_exact_math_check: one counter per form

@@ -976,11 +976,9 @@ int render_stats(ptx_ctx* c, uint64_t samples, uint32_t n_pass, bool wavefront, 
 	return PTX_OK;
 }
 
-}  // namespace
-
-int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_render_stats* stats) {
-	if (!sc || !cfg || !accum) return set_err(PTX_ERR_INVALID, "ptx_render: NULL argument");
-	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render: scene was created without a GPU context (no CPU path exists)");
+// ptx_render (claimed == nullptr: `accum` receives sums) and ptx_render_transparent (`accum` and `claimed` are the reference's per-pixel
+// blend state, advanced through the samples in order) — the same passes, a different resolve kernel behind each
+int render_frame(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, uint8_t* claimed, ptx_render_stats* stats) {
 	if (!cfg->W || !cfg->H) return set_err(PTX_ERR_INVALID, "ptx_render: W and H must be > 0");   // bounces = 0 is legal: a black frame (renderer.cpp:438-439)
 	uint32_t x0 = cfg->x0, y0 = cfg->y0, w = cfg->w, h = cfg->h;
 	if (w == 0 && h == 0) { x0 = 0; y0 = 0; w = cfg->W; h = cfg->H; }
@@ -1025,6 +1023,12 @@ int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_rende
 		d_accum = (float4*)c->stage_a.p;
 		HIP_TRY(hipMemcpyAsync(d_accum, accum, rect_pixels * sizeof(float4), hipMemcpyHostToDevice, c->stream));
 	}
+	uint8_t* d_claimed = claimed;
+	if (claimed && !dev_accum) {
+		HIP_TRY(c->stage_b.ensure(rect_pixels));
+		d_claimed = (uint8_t*)c->stage_b.p;
+		HIP_TRY(hipMemcpyAsync(d_claimed, claimed, rect_pixels, hipMemcpyHostToDevice, c->stream));
+	}
 
 	const uint32_t n_pass = (cfg->spp + pass_spp - 1) / pass_spp;
 	if (stats)
@@ -1053,6 +1057,7 @@ int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_rende
 		P.sample0 = cfg->sample0 + p * pass_spp;
 		P.pass_spp = std::min(pass_spp, cfg->spp - p * pass_spp);
 		P.bounces = cfg->bounces;
+		P.transparent = claimed ? 1u : 0u;
 		P.n_paths = (uint64_t)P.pass_spp * n_pixels;
 		P.seed_lo = cfg->seed_lo; P.seed_hi = cfg->seed_hi;
 		memcpy(P.env, cfg->env, sizeof P.env);
@@ -1069,12 +1074,33 @@ int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_rende
 			HIP_TRY(launch_render_pass(sc->dev, P, B, sc->mode, sc->lds_bytes, grid, c->stream));
 		}
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
-		HIP_TRY(launch_resolve(B.sample_rad, d_accum, d_pixels, P.n_pixels, P.pass_spp, c->stream));
+		if (claimed) HIP_TRY(launch_resolve_claim(B.sample_rad, d_accum, d_claimed, d_pixels, P.n_pixels, P.pass_spp, P.sample0, c->stream));
+		else HIP_TRY(launch_resolve(B.sample_rad, d_accum, d_pixels, P.n_pixels, P.pass_spp, c->stream));
 	}
 	if (!dev_accum) HIP_TRY(hipMemcpyAsync(accum, d_accum, rect_pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+	if (claimed && !dev_accum) HIP_TRY(hipMemcpyAsync(claimed, d_claimed, rect_pixels, hipMemcpyDeviceToHost, c->stream));
 	if (stats || !dev_accum) HIP_TRY(hipStreamSynchronize(c->stream));
 	if (stats) return render_stats(c, (uint64_t)cfg->spp * n_pixels, n_pass, wavefront, plan, clk, wf_rays, stats);
 	return PTX_OK;
+}
+
+}  // namespace
+
+int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_render_stats* stats) {
+	if (!sc || !cfg || !accum) return set_err(PTX_ERR_INVALID, "ptx_render: NULL argument");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render: scene was created without a GPU context (no CPU path exists)");
+	return render_frame(sc, cfg, accum, nullptr, stats);
+}
+
+int ptx_render_transparent(ptx_scene* sc, const ptx_render_cfg* cfg, float* pixel_rgba, uint8_t* claimed, ptx_render_stats* stats) {
+	// every refusal below is decided before any device work
+	if (!sc || !cfg || !pixel_rgba || !claimed) return set_err(PTX_ERR_INVALID, "ptx_render_transparent: NULL argument");
+	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
+		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_transparent: PTX_INTEGRATOR_WORKER has no transparent-background mode here (the worker takes the alpha of the "
+		                                    "path's last vertex and jitters sample 0 in this mode, and nothing pins that); use PTX_INTEGRATOR_LIB");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_transparent: scene was created without a GPU context (no CPU path exists)");
+	if (is_device_ptr(pixel_rgba) != is_device_ptr(claimed)) return set_err(PTX_ERR_INVALID, "ptx_render_transparent: pixel_rgba and claimed must both be device or both be host memory");
+	return render_frame(sc, cfg, pixel_rgba, claimed, stats);
 }
 
 int ptx_intersect_batch(ptx_scene* sc, const ptx_rays* r, size_t n, const ptx_hits* hh) {

@@ -660,11 +660,12 @@ __global__ void __launch_bounds__(kWfBlock) k_wf_shade(DevScene S0, RenderParams
 			else {
 				SceneHit h;
 				wf_closest(S, W, pe, o, d, h);
+				const bool depth0 = depth == 0;   // before the vertex: a scatter raises depth, a miss leaves it
 				const int state = shade_vertex<SUN, ALPHA, TEX, WORKER>(S, S.shade, P, __float_as_uint(key_px), __float_as_uint(key_s), depth, pass, h, o, d, T, L, rq);
 				if (state == V_ALIVE) emit = true;
 				else if (state == V_PENDING) { emit = true; out_flags = kWfPending; o = rq.x; }
 				else if (rq.kind == REQ_ADD) { emit = true; out_flags = kWfZombie; }   // the path is over, its last sun sample is not
-				else *result = make_float4(L.x, L.y, L.z, 1.0f);
+				else *result = make_float4(L.x, L.y, L.z, sample_alpha(!WORKER && P.transparent != 0u, h.surface < 0, depth0));
 				if (rq.kind != REQ_NONE) out_flags |= kWfRequest;
 			}
 		}
@@ -738,7 +739,7 @@ hipError_t launch_wf_step(const DevScene& S, const RenderParams& P, const WfBuff
 	const bool sun = S.sun.present != 0, alpha = S.any_alpha != 0;
 #define WF_SHADE(SUN_, ALPHA_, TEX_, WORKER_) launch_shade_variant<SUN_, ALPHA_, TEX_, WORKER_>(S, P, W, in, out, cap, max_in, slab_first, n_out, sample_rad, stream)
 	if (P.integrator == 1u) { if (S.any_texture) WF_SHADE(true, true, true, true); else WF_SHADE(true, true, false, true); }
-	else if (S.any_texture) WF_SHADE(true, true, true, false);
+	else if (S.any_texture || P.transparent) WF_SHADE(true, true, true, false);   // transparent background: the variant the fused kernel runs it with
 	else if (sun) { if (alpha) WF_SHADE(true, true, false, false); else WF_SHADE(true, false, false, false); }
 	else { if (alpha) WF_SHADE(false, true, false, false); else WF_SHADE(false, false, false, false); }
 #undef WF_SHADE

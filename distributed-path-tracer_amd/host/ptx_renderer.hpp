@@ -25,10 +25,10 @@ public:
 	uint8_t bounce_count = 4;
 	std::filesystem::path environment;     // PNG environment map (the reference holds a loaded image::texture, renderer.hpp:28); empty = none
 	float environment_factor[3] = {1, 1, 1};
-	bool transparent_background = false;   // debug path of the reference; not built: render() throws if set
+	bool transparent_background = false;   // renderer.cpp:340-399, :444: alpha 0 where trace() returns a miss, claim blend over the samples (ptx_render_transparent)
 	uint32_t camera_index = 0;
 	uint32_t sun_light_index = 0;
-	uint8_t visualize_kd_tree_depth = 0;   // debug path; not built
+	uint8_t visualize_kd_tree_depth = 0;   // not built: mesh.cpp:316-318 colours each KD node by its heap address, nothing reproducible to mirror
 	uint64_t seed = 0x5EED;                // key of the counter-based RNG (the reference seeds from random_device)
 
 	explicit renderer(int device = 0) { check(ptx_ctx_create(device, &ctx_)); }
@@ -47,10 +47,10 @@ public:
 		check(ptx_scene_load_gltf(ctx_, path.string().c_str(), &o, &scene_));
 	}
 
-	// radiance sums [H][W][4]; stats optional
+	// radiance sums [H][W][4]; with transparent_background set: the blended means (colour, alpha) of ptx_render_transparent. stats optional
 	std::vector<float> render_accum(ptx_render_stats* stats = nullptr) const {
 		if (!scene_) throw std::runtime_error("render() before load_gltf()");
-		if (transparent_background || visualize_kd_tree_depth) throw std::runtime_error("transparent_background / visualize_kd_tree_depth are not built");
+		if (visualize_kd_tree_depth) throw std::runtime_error("visualize_kd_tree_depth is not built: the reference colours KD nodes by their heap addresses (mesh.cpp:316-318)");
 		if (environment.string() != env_set_) {   // (re)load the map only when the field changed
 			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
 			env_set_ = environment.string();
@@ -60,14 +60,20 @@ public:
 		for (int k = 0; k < 3; k++) c.env[k] = environment_factor[k];
 		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
 		std::vector<float> accum((size_t)c.W * c.H * 4, 0.f);
-		check(ptx_render(scene_, &c, accum.data(), stats));
+		if (transparent_background) {
+			std::vector<uint8_t> claimed((size_t)c.W * c.H, 0);
+			check(ptx_render_transparent(scene_, &c, accum.data(), claimed.data(), stats));
+		} else {
+			check(ptx_render(scene_, &c, accum.data(), stats));
+		}
 		return accum;
 	}
 
 	std::vector<uint8_t> render() const {   // renderer.cpp:334-428: PNG bytes (RGBA8, ACES tonemap, sRGB)
 		std::vector<float> accum = render_accum();
 		std::vector<uint8_t> rgba((size_t)resolution.x * resolution.y * 4);
-		check(ptx_tonemap_encode(ctx_, accum.data(), resolution.x, resolution.y, sample_count, rgba.data()));
+		// the transparent mode's means are written as they are (spp = 1: x / 1.0f is exact)
+		check(ptx_tonemap_encode(ctx_, accum.data(), resolution.x, resolution.y, transparent_background ? 1u : sample_count, rgba.data()));
 		uint8_t* png = nullptr;
 		size_t n = 0;
 		check(ptx_encode_png(rgba.data(), resolution.x, resolution.y, &png, &n));

@@ -1,6 +1,6 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] <scene.gltf> <out.png> [W H spp bounces]       (--transparent: renderer::transparent_background)
 //   ptx_render_cli --event <event.json> <local scene root dir> <out.png>     (the worker's Lambda event, main.cpp:9-25)
 #include <chrono>
 #include <cstdio>
@@ -12,8 +12,10 @@
 #include "ptx_renderer.hpp"
 
 int main(int argc, char** argv) {
+	const bool transparent = argc > 1 && std::string(argv[1]) == "--transparent";
+	if (transparent) { argv[1] = argv[0]; argv++; argc--; }
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (argc == 5 && std::string(argv[1]) == "--event") {
@@ -42,6 +44,7 @@ int main(int argc, char** argv) {
 	}
 	try {
 		core::renderer r(0);
+		r.transparent_background = transparent;
 		if (argc >= 7) {
 			r.resolution = {(uint32_t)std::atoi(argv[3]), (uint32_t)std::atoi(argv[4])};
 			r.sample_count = (uint32_t)std::atoi(argv[5]);

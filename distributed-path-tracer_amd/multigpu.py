@@ -69,11 +69,18 @@ def reduce_accum(accum, dst: int = 0):
     return accum
 
 
-def render_sharded(scene, W, H, spp_per_rank, bounces, accum, rank, world, **kw):
+_NO_SAMPLE_SPLIT = ("transparent_background blends the samples of a pixel in sample order (a recurrence, not a sum: renderer.cpp:374-399): "
+                    "sample ranges rendered into separate buffers cannot be merged — shard the frame by tiles (render_tiles)")
+
+
+def render_sharded(scene, W, H, spp_per_rank, bounces, accum, rank, world, transparent=False, **kw):
     """WEAK scaling: render this rank's own `spp_per_rank` samples (global indices [rank*spp, (rank+1)*spp)) into `accum` (sums)
     and reduce onto rank 0: the frame receives world * spp_per_rank samples. Returns the stats of the local render.
     `scene` is a distributed-path-tracer_amd.Scene (anything with the same .render signature). `accum` must be ready (zeroed)
-    before the call as far as the library's stream is concerned: synchronise torch's stream after preparing it."""
+    before the call as far as the library's stream is concerned: synchronise torch's stream after preparing it.
+    transparent=True raises ValueError: the transparent-background blend does not compose over sample ranges."""
+    if transparent:
+        raise ValueError(_NO_SAMPLE_SPLIT)
     s0, n = sample_range(rank, world, spp_per_rank)
     _, stats = scene.render(W, H, n, bounces, accum=accum, sample0=s0, **kw)
     _order_before_reduce(scene)
@@ -81,9 +88,12 @@ def render_sharded(scene, W, H, spp_per_rank, bounces, accum, rank, world, **kw)
     return stats
 
 
-def render_samples(scene, W, H, spp_total, bounces, accum, rank, world, **kw):
+def render_samples(scene, W, H, spp_total, bounces, accum, rank, world, transparent=False, **kw):
     """STRONG scaling by samples: ONE frame of `spp_total` samples per pixel; this rank traces its contiguous share of the
-    sample indices of every pixel, then the buffers are sum-reduced onto rank 0."""
+    sample indices of every pixel, then the buffers are sum-reduced onto rank 0.
+    transparent=True raises ValueError: the transparent-background blend does not compose over sample ranges."""
+    if transparent:
+        raise ValueError(_NO_SAMPLE_SPLIT)
     s0, n = split_samples(rank, world, spp_total)
     stats = {"rays": 0, "samples": 0, "passes": 0, "kernel_ms": 0.0}
     if n > 0:
@@ -93,11 +103,20 @@ def render_samples(scene, W, H, spp_total, bounces, accum, rank, world, **kw):
     return stats
 
 
-def render_tiles(scene, W, H, spp, bounces, accum, rank, world, tile=TILE, **kw):
+def render_tiles(scene, W, H, spp, bounces, accum, rank, world, tile=TILE, transparent=False, claimed=None, **kw):
     """STRONG scaling by interleaved tiles: this rank renders ALL `spp` samples of the 64 x 64 image tiles t with
     t % world == rank into the full-frame `accum` ([H,W,4], zero elsewhere); the sum-reduce then assembles the frame on rank 0
-    (x + 0 == x: bitwise the single-GPU frame). Returns the stats of the local render."""
-    _, stats = scene.render(W, H, spp, bounces, accum=accum, shard=(rank, world, tile), **kw)
+    (x + 0 == x: bitwise the single-GPU frame). Returns the stats of the local render.
+    transparent=True: renderer::transparent_background. `accum` is then the full-frame blend state of Scene.render_transparent
+    (running colour and alpha: means, to be written with spp = 1) and `claimed` its [H,W] uint8 flags of the same kind (zeroed; this
+    rank's part of them stays local — only `accum` is reduced). Every pixel belongs to one rank, which blends all of its samples in
+    order, so the sum of the ranks' buffers is bitwise the single-GPU frame here too."""
+    if transparent:
+        if claimed is None:
+            raise ValueError("render_tiles(transparent=True) needs a zeroed `claimed` buffer ([H,W] uint8) beside `accum`")
+        _, _, stats = scene.render_transparent(W, H, spp, bounces, pixels=accum, claimed=claimed, shard=(rank, world, tile), **kw)
+    else:
+        _, stats = scene.render(W, H, spp, bounces, accum=accum, shard=(rank, world, tile), **kw)
     _order_before_reduce(scene)
     reduce_accum(accum, 0)
     return stats if stats is not None else {"rays": 0, "samples": 0, "passes": 0, "kernel_ms": 0.0}

@@ -192,6 +192,26 @@ typedef struct ptx_render_stats {
 /* accum_rgba: device or host pointer. stats may be NULL (no device->host sync is then forced). */
 int ptx_render(ptx_scene* scene, const ptx_render_cfg* cfg, float* accum_rgba, ptx_render_stats* stats);
 
+/* core::renderer::render() with transparent_background = true (renderer.cpp:340-399, :444), PTX_INTEGRATOR_LIB only.
+ * A sample's alpha is 0 when trace()'s top-level return is a miss — the camera ray missed, or the ray continued behind an opacity /
+ * lit shadow-catcher pass-through did (renderer.cpp:471, 518) — and 1 for every other ending. The reference then blends the samples
+ * of a pixel IN SAMPLE ORDER on the state {color, alpha, claimed} (renderer.cpp:374-399): the first opaque sample s claims the pixel
+ * (color = sample, alpha = 1 / (s + 1) in INTEGER arithmetic: 1 for s = 0, else 0 — kept as the reference has it); a transparent
+ * sample changes only the alpha of a claimed pixel and nothing of an unclaimed one; an opaque sample on a claimed pixel takes the
+ * running mean of colour and alpha. pixel_rgba[h][w][4] (float32) holds that running color / alpha — MEANS, not sums — and
+ * claimed[h][w] (one byte per pixel, 0 / 1) the flag; both device or both host. The call advances them through samples
+ * [sample0, sample0 + spp) of the rectangle. A frame starts from zeroed buffers at sample0 = 0.
+ * The blend is a recurrence, not a sum. What composes: calls of ASCENDING, adjacent sample ranges on the same buffers (bitwise the
+ * frame of one call, for any spp_per_pass); tile rectangles; shard_* as in ptx_render — other shards' pixels stay as they were, so
+ * the sum of the shards' zero-initialised buffers is bitwise the unsharded frame. What does NOT: sample ranges of one frame rendered
+ * into independent buffers cannot be merged afterwards — split a frame over GPUs by tiles or shards in this mode.
+ * Image write: ptx_tonemap_encode(ctx, pixel_rgba, W, H, 1, rgba8) is the reference's write loop for these means (x / 1.0f is exact;
+ * alpha is quantised without sRGB, image.cpp:143-154).
+ * PTX_ERR_UNSUPPORTED for PTX_INTEGRATOR_WORKER (the worker's alpha is that of the path's last vertex, shading_worker.cpp:36,43, and it
+ * jitters sample 0 in this mode, worker.cpp:125: nothing pins it); PTX_ERR_NO_DEVICE for a host-only scene; PTX_ERR_INVALID for NULL
+ * buffers — all decided before any device work. */
+int ptx_render_transparent(ptx_scene* scene, const ptx_render_cfg* cfg, float* pixel_rgba, uint8_t* claimed, ptx_render_stats* stats);
+
 /* Measurement aid (no counterpart in the reference): where the time of the last ptx_render that was given a stats pointer went.
  * Scenes whose geometry fits the LDS or whose models have few surfaces run ONE fused kernel per pass (pipeline 0: fused_ms);
  * many-surface scenes in global memory run the queue-based pipeline (pipeline 1) — per step of a slab of paths a classify, a
@@ -274,7 +294,8 @@ int ptx_reduce_framebuffer(ptx_ctx* ctx, void* nccl_comm, float* accum_rgba, siz
 /* ---- image write --------------------------------------------------------------------------------
  * Replaces the tonemap + image::write loop of renderer.cpp:409-424 (core::tonemap_approx_aces,
  * LIB/core/utils.hpp:29-36; image::image::write, LIB/image/image.cpp:143-154): divides the sums by
- * `spp`, applies ACES, sRGB (pow 1/2.2) and quantises to RGBA8 row-major. accum/rgba8 device or host. */
+ * `spp`, applies ACES, sRGB (pow 1/2.2) and quantises to RGBA8 row-major; alpha is quantised linearly. accum/rgba8 device or host.
+ * With spp = 1 it writes the means of ptx_render_transparent unchanged (x / 1.0f is exact). */
 int ptx_tonemap_encode(ptx_ctx* ctx, const float* accum_rgba, uint32_t W, uint32_t H, uint32_t spp, uint8_t* rgba8);
 /* Replaces image::image::save_to_memory_png (LIB/image/image.cpp:111-122). Host memory only.
  * *png is malloc'ed; release with ptx_free. Decoded pixels are exact; the byte stream is zlib's, not stb's. */

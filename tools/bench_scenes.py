@@ -10,26 +10,34 @@ import torch
 ap = argparse.ArgumentParser(); ap.add_argument("--spp", type=int, default=32); ap.add_argument("--level7", action="store_true")
 ap.add_argument("--only", default="", help="comma list of: cornell, jack, plaza, atrium, mesh6, mesh7")
 ap.add_argument("--integrator", type=int, default=0)
+ap.add_argument("--transparent", action="store_true", help="renderer::transparent_background: time Scene.render_transparent (alpha output + claim blend)")
 args = ap.parse_args()
 ptx = importlib.import_module("distributed-path-tracer_amd")
 proc = importlib.import_module("distributed-path-tracer_amd.procedural")
 ctx = ptx.Context(0)
 W, H, B = 1920, 1080, 8
 accum = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda:0")
+claimed = torch.zeros((H, W), dtype=torch.uint8, device="cuda:0")
 
 
 only = set(filter(None, args.only.split(",")))
 want = lambda k: not only or k in only
 
 
+def render(scene, spp):
+    if args.transparent:
+        return scene.render_transparent(W, H, spp, B, pixels=accum, claimed=claimed, want_stats=True, integrator=args.integrator)[2]
+    return scene.render(W, H, spp, B, accum=accum, want_stats=True, integrator=args.integrator)[1]
+
+
 def run(name, scene, spp):
-    scene.render(W, H, spp, B, accum=accum, want_stats=True, integrator=args.integrator)        # warm-up: same size, so that every workspace has its final size
-    accum.zero_(); torch.cuda.synchronize()
+    render(scene, spp)        # warm-up: same size, so that every workspace has its final size
+    accum.zero_(); claimed.zero_(); torch.cuda.synchronize()
     t = time.perf_counter()
-    _, st = scene.render(W, H, spp, B, accum=accum, want_stats=True, integrator=args.integrator)
+    st = render(scene, spp)
     dt = time.perf_counter() - t
     info = scene.info()
-    print(json.dumps({"scene": name, "triangles": info["n_triangles"], "kd_nodes": info["n_kd_nodes"], "lds_resident": info["lds_resident"],
+    print(json.dumps({"scene": name, "transparent": bool(args.transparent), "triangles": info["n_triangles"], "kd_nodes": info["n_kd_nodes"], "lds_resident": info["lds_resident"],
                       "spp": spp, "msamples_per_s": round(W * H * spp / dt / 1e6, 1), "mrays_per_s": round(st["rays"] / dt / 1e6, 1),
                       "rays_per_sample": round(st["rays"] / st["samples"], 3), "seconds": round(dt, 3)}), flush=True)
 
