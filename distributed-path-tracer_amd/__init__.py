@@ -162,6 +162,7 @@ def lib():
         L.ptx_tonemap_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ptx_pbr_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_exact_math_check.argtypes = [C.c_void_p, C.c_void_p]
+        L.ptx_leaf_intersect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.ptx_camera_rays_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_material_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_reduce_framebuffer.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -238,6 +239,21 @@ class Context:
         out = np.zeros(len(self.EXACT_MATH_FORMS), np.uint64)
         _check(lib().ptx_exact_math_check(self.h, out.ctypes.data))
         return {n: int(v) for n, v in zip(self.EXACT_MATH_FORMS, out)}
+
+    def leaf_intersect(self, corners, rays, refs=None, leaf_ordered=False):
+        """ptx_leaf_intersect_batch: the fused kernels' leaf loop on one leaf holding the triangles corners [n_tri,9] (a, b, c), tested in
+        the order of refs (a permutation, None = identity), in the per-triangle layout behind refs or the leaf-ordered one; rays [n,7]
+        float32 (origin, unit direction, max_dist). -> {"t", "beta", "gamma": float32 [n], "triangle": int32 [n], -1 = miss}."""
+        c = np.ascontiguousarray(corners, np.float32).reshape(-1, 9)
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 7)
+        p = None if refs is None else np.ascontiguousarray(refs, np.uint32)
+        if p is not None and p.shape != (len(c),):
+            raise ValueError("refs must hold one reference per triangle")
+        out = np.zeros((len(r), 3), np.float32)
+        tri = np.full(len(r), -1, np.int32)
+        _check(lib().ptx_leaf_intersect_batch(self.h, c.ctypes.data, len(c), None if p is None else p.ctypes.data, int(bool(leaf_ordered)),
+                                              r.ctypes.data, len(r), out.ctypes.data, tri.ctypes.data))
+        return {"t": out[:, 0].copy(), "beta": out[:, 1].copy(), "gamma": out[:, 2].copy(), "triangle": tri}
 
     def tonemap_encode(self, accum, W, H, spp, out=None):
         """accum: [H,W,4] float32 sums (numpy or torch-on-GPU). Returns/filles RGBA8 [H,W,4]."""

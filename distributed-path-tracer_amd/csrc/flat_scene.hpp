@@ -38,6 +38,9 @@ struct TriRec { float ax, ay, az; uint32_t ia; float bx, by, bz; uint32_t ib; fl
 // Ordered for packed-fp32 math (v_pk_mul_f32 / v_pk_add_f32 take even-aligned register pairs): every pair the solve
 // multiplies lane-wise sits in one 8-byte slot, so the three LDS / global reads deliver it ready to use.
 struct TriIsect { float e2y, e1z, e2z, e1y; float e1x, e2x, ay, az; float ax, c3, p0, p1; };
+// The record of the triangle (a, b, c) with global triangle id `gid` in its p0 word (what a hit reports): the one place records are
+// made (scene_build.cpp), for finalize_scene and for ptx_leaf_intersect_batch.
+TriIsect make_tri_isect(const float* a, const float* b, const float* c, uint32_t gid);
 
 // ---- hit record: 9 x float4 (144 B) per triangle — everything renderer::intersect interpolates on a hit (renderer.cpp:688-715),
 // gathered per triangle so that a hit costs ONE round of fetches: corners + u | normals + v | tangents. (Fetching the corner

@@ -630,6 +630,40 @@ __global__ void k_pbr_eval(const float* __restrict__ in, float* __restrict__ out
 	q[12] = rf.x; q[13] = rf.y; q[14] = rf.z;
 }
 
+// ------------------------------------------------------------------------------------ batch leaf loop
+// mesh_traverse itself, as the fused kernels inline it, on a one-node tree: a single leaf (first = 0, count = n_tri), so that every
+// ray runs the leaf loop — the short solve, its rcp_key bookkeeping and the IEEE re-test of the leaf — over triangles of the caller's
+// choosing (ptx_leaf_intersect_batch). leaf_ordered = 0: the layout of the LDS-resident copy, staged into LDS here as well: one record per
+// triangle, reached through `refs`. 1: the layout of the global-memory copy: one record per leaf reference, the id in its spare word.
+// rays [n][7]: origin, direction, max_dist (the traversal starts with nr = 0, fr = max_dist); out [n][3]: t, beta, gamma (-1, 0, 0 on a
+// miss); tri [n]: the triangle id, -1 on a miss.
+__global__ void __launch_bounds__(256) k_leaf_intersect(const uint2* __restrict__ nodes, const uint32_t* __restrict__ refs, const float4* __restrict__ tris, uint32_t n_tri,
+                                                        uint32_t leaf_ordered, const float* __restrict__ rays, size_t n, float* __restrict__ out, int32_t* __restrict__ tri,
+                                                        uint2* __restrict__ spill_base) {
+	__shared__ float4 s_tris[3 * kLeafBatchMaxTris];
+	__shared__ uint32_t s_refs[kLeafBatchMaxTris];
+	__shared__ uint2 s_node;
+	if (!leaf_ordered) {
+		for (uint32_t k = threadIdx.x; k < 3u * n_tri; k += blockDim.x) s_tris[k] = tris[k];
+		for (uint32_t k = threadIdx.x; k < n_tri; k += blockDim.x) s_refs[k] = refs[k];
+		if (threadIdx.x == 0) s_node = nodes[0];
+		__syncthreads();
+	}
+	const Geom g = leaf_ordered ? Geom{nodes, refs, tris, true, true} : Geom{&s_node, s_refs, s_tris, false, false};
+	const Spill spill{spill_base + (size_t)(blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6)) * (kSpillStack * 64) + (threadIdx.x & 63u)};
+#ifdef PTX_PROF
+	Prof prof{};
+#endif
+	const size_t stride = (size_t)gridDim.x * blockDim.x;
+	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+		const float* r = rays + 7 * i;
+		MeshHit h;
+		const bool hit = mesh_traverse<4>(g, 0u, 0.0f, r[6], mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), h, spill PROF_PASS);
+		out[3 * i] = hit ? h.t : -1.0f; out[3 * i + 1] = hit ? h.b1 : 0.0f; out[3 * i + 2] = hit ? h.b2 : 0.0f;
+		tri[i] = hit ? (int32_t)h.tri : -1;
+	}
+}
+
 // ------------------------------------------------------------------------------------ exact-math self-check
 // The short reciprocal / square-root forms of device_core.hpp against the IEEE expressions they replace, over every float pattern x
 // (ptx_exact_math_check). Per form, the number of results whose bits differ (a NaN equals any NaN) is added to bad[form]:
@@ -779,6 +813,11 @@ hipError_t launch_intersect(const DevScene& S, const IntersectArgs& A, int mode,
 }
 hipError_t launch_pbr_eval(const float* in, float* out, size_t n, hipStream_t stream) {
 	hipLaunchKernelGGL(k_pbr_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, out, n);
+	return hipGetLastError();
+}
+hipError_t launch_leaf_intersect(const uint2* nodes, const uint32_t* refs, const float4* tris, uint32_t n_tri, bool leaf_ordered, const float* rays, size_t n, float* out,
+                                 int32_t* tri, uint2* spill, int grid, hipStream_t stream) {
+	hipLaunchKernelGGL(k_leaf_intersect, dim3(grid), dim3(256), 0, stream, nodes, refs, tris, n_tri, leaf_ordered ? 1u : 0u, rays, n, out, tri, spill);
 	return hipGetLastError();
 }
 hipError_t launch_exact_math_check(unsigned long long* bad, hipStream_t stream) {

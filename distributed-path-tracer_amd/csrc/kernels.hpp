@@ -169,6 +169,10 @@ hipError_t launch_resolve_claim(const float4* sample_rad, float4* pixel_rgba, ui
                                 uint32_t sample0 /* global index of the pass's first sample */, hipStream_t stream);
 hipError_t launch_intersect(const DevScene& S, const IntersectArgs& A, int mode, size_t lds_bytes, int grid, hipStream_t stream);
 hipError_t launch_pbr_eval(const float* in, float* out, size_t n, hipStream_t stream);
+constexpr uint32_t kLeafBatchMaxTris = 256;   // k_leaf_intersect: triangles of its one leaf at most (48 bytes each in LDS)
+// `spill`: [grid * 4 waves][kSpillWords]; grid workgroups of 256 threads
+hipError_t launch_leaf_intersect(const uint2* nodes, const uint32_t* refs /* [n_tri] */, const float4* tris /* [n_tri][3] */, uint32_t n_tri, bool leaf_ordered,
+                                 const float* rays /* [n][7] */, size_t n, float* out /* [n][3] */, int32_t* tri /* [n] */, uint2* spill, int grid, hipStream_t stream);
 constexpr uint32_t kExactMathForms = 3;   // k_exact_math_check: one counter per form
 hipError_t launch_exact_math_check(unsigned long long* bad /* [kExactMathForms], device, zeroed */, hipStream_t stream);
 hipError_t launch_camera_rays(const DevScene& S, const float* in /* [n][3]: ndc.x ndc.y ratio */, float* out /* [n][6] */, size_t n, hipStream_t stream);

@@ -1227,6 +1227,52 @@ int ptx_pbr_eval_batch(ptx_ctx* c, const float* in, size_t n, float* out) {
 	return PTX_OK;
 }
 
+int ptx_leaf_intersect_batch(ptx_ctx* c, const float* corners, uint32_t n_tri, const uint32_t* refs, int leaf_ordered, const float* rays, size_t n,
+                             float* out, int32_t* tri) {
+	if (!c) return set_err(PTX_ERR_NO_DEVICE, "ptx_leaf_intersect_batch: no GPU context (no CPU path exists)");
+	if (n_tri == 0 || n_tri > kLeafBatchMaxTris) return set_err(PTX_ERR_INVALID, "ptx_leaf_intersect_batch: n_tri must be 1 .. 256");
+	if (!corners) return set_err(PTX_ERR_INVALID, "ptx_leaf_intersect_batch: NULL argument");
+	if (n == 0) return PTX_OK;
+	if (!rays || !out || !tri) return set_err(PTX_ERR_INVALID, "ptx_leaf_intersect_batch: NULL argument");
+	if (n > (size_t)0x7FFFFFFF / 7) return set_err(PTX_ERR_INVALID, "ptx_leaf_intersect_batch: batch too large");
+	if (is_device_ptr(corners) || is_device_ptr(rays) || is_device_ptr(out) || is_device_ptr(tri) || (refs && is_device_ptr(refs)))
+		return set_err(PTX_ERR_INVALID, "ptx_leaf_intersect_batch: host memory only");
+	std::vector<uint32_t> order(n_tri);
+	std::vector<uint8_t> seen(n_tri, 0);
+	for (uint32_t k = 0; k < n_tri; k++) {
+		order[k] = refs ? refs[k] : k;
+		if (order[k] >= n_tri || seen[order[k]]) return set_err(PTX_ERR_INVALID, "ptx_leaf_intersect_batch: refs is not a permutation of 0 .. n_tri-1");
+		seen[order[k]] = 1;
+	}
+	// the records the builder makes for these triangles (ids = their indices), laid out as upload_scene lays out the two copies
+	std::vector<TriIsect> recs(n_tri);
+	for (uint32_t k = 0; k < n_tri; k++) {
+		const uint32_t t = leaf_ordered ? order[k] : k;
+		recs[k] = make_tri_isect(corners + 9 * (size_t)t, corners + 9 * (size_t)t + 3, corners + 9 * (size_t)t + 6, t);
+	}
+	const KdNode node[2] = {kd_make_leaf(0, n_tri), {0, 0}};
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t refs_off = 16, recs_off = refs_off + pad16((size_t)n_tri * 4), rays_off = recs_off + (size_t)n_tri * 48;
+	HIP_TRY(c->stage_a.ensure(rays_off + n * 28));
+	HIP_TRY(c->stage_b.ensure(n * 16));
+	char* in = (char*)c->stage_a.p;
+	HIP_TRY(hipMemcpyAsync(in, node, 16, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(in + refs_off, order.data(), (size_t)n_tri * 4, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(in + recs_off, recs.data(), (size_t)n_tri * 48, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(in + rays_off, rays, n * 28, hipMemcpyHostToDevice, c->stream));
+	const int grid = (int)std::min<size_t>((size_t)c->n_cu, (n + 255) / 256);
+	HIP_TRY(c->spill.ensure((size_t)c->n_cu * 4 * (size_t)kSpillWords * sizeof(uint2)));
+	float* d_out = (float*)c->stage_b.p;
+	int32_t* d_tri = (int32_t*)(d_out + 3 * n);
+	HIP_TRY(launch_leaf_intersect((const uint2*)in, (const uint32_t*)(in + refs_off), (const float4*)(in + recs_off), n_tri, leaf_ordered != 0,
+	                              (const float*)(in + rays_off), n, d_out, d_tri, (uint2*)c->spill.p, grid, c->stream));
+	HIP_TRY(hipMemcpyAsync(out, d_out, n * 12, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(tri, d_tri, n * 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));   // the staged vectors are locals
+	return PTX_OK;
+}
+
 int ptx_exact_math_check(ptx_ctx* c, uint64_t* mismatches) {
 	if (!c) return set_err(PTX_ERR_NO_DEVICE, "ptx_exact_math_check: no GPU context (no CPU path exists)");
 	if (!mismatches) return set_err(PTX_ERR_INVALID, "ptx_exact_math_check: NULL argument");

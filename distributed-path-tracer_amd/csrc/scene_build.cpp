@@ -178,6 +178,14 @@ struct MeshBuilder {
 
 }  // namespace
 
+// e1 = a - b, e2 = a - c and c3 with the reference's float operations (triangle.cpp:136-147), paired as tri_test_pk reads them
+TriIsect make_tri_isect(const float* a, const float* b, const float* c, uint32_t gid) {
+	const float e1[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]}, e2[3] = {a[0] - c[0], a[1] - c[1], a[2] - c[2]};
+	TriIsect rec{e2[1], e1[2], e2[2], e1[1], e1[0], e2[0], a[1], a[2], a[0], e1[1] * e2[2] - e2[1] * e1[2], 0.f, 0.f};
+	memcpy(&rec.p0, &gid, 4);   // every record carries its global triangle id (what a hit reports)
+	return rec;
+}
+
 void finalize_scene(FlatScene& s, const float* cam, const float* sun) {
 	const size_t n_models = s.model_surf.size() / 2;
 	const size_t n_surf = s.surf_range.size() / 8;
@@ -221,11 +229,7 @@ void finalize_scene(FlatScene& s, const float* cam, const float* sun) {
 			s.hitrec.push_back({{a[0], a[1], a[2]}, a[3], {b[0], b[1], b[2]}, b[3], {c[0], c[1], c[2]}, c[3],
 			                    {a[5], a[6], a[7]}, a[4], {b[5], b[6], b[7]}, b[4], {c[5], c[6], c[7]}, c[4],
 			                    {a[8], a[9], a[10]}, 0.f, {b[8], b[9], b[10]}, 0.f, {c[8], c[9], c[10]}, 0.f});
-			const float e1[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]}, e2[3] = {a[0] - c[0], a[1] - c[1], a[2] - c[2]};
-			TriIsect rec{e2[1], e1[2], e2[2], e1[1], e1[0], e2[0], a[1], a[2], a[0], e1[1] * e2[2] - e2[1] * e1[2], 0.f, 0.f};
-			const uint32_t gid = (uint32_t)(t0 + t);   // every record carries its global triangle id (what a hit reports)
-			memcpy(&rec.p0, &gid, 4);
-			s.tri_isect.push_back(rec);
+			s.tri_isect.push_back(make_tri_isect(a, b, c, (uint32_t)(t0 + t)));
 		}
 		{   // a test accepts beta, gamma in [-eps, 1 + eps] (triangle.cpp:160-183): the accepted point (1-b-g) a + b B + g C lies within
 			// 2 eps max_edge of the triangle; 4 eps max_edge (and the eps the box is already padded with) bounds it with room to spare

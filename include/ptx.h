@@ -274,6 +274,17 @@ int ptx_material_eval_batch(ptx_scene* scene, const int32_t* surface, const floa
  * fresnel(outcoming, reflect(-outcoming, normal), ior), reflect(-outcoming, normal)(3). Pointers device or host (both of one kind). */
 int ptx_pbr_eval_batch(ptx_ctx* ctx, const float* in, size_t n, float* out);
 
+/* The leaf loop of core::mesh::intersect (LIB/core/mesh.cpp:381-389: nearest triangle with 0 <= t <= max_dist, the first wins a tie)
+ * exactly as the fused kernels run it, on triangles of the caller's choosing: the records are built by the scene builder's own code
+ * and the kernel calls the traversal on a tree of one leaf holding all n_tri triangles (1 <= n_tri <= 256), so the short reciprocal,
+ * its range bookkeeping and the IEEE re-test of the whole leaf are the shipped ones.
+ * corners[n_tri][9]: a, b, c;  refs[n_tri]: the leaf's reference list, a permutation of 0 .. n_tri-1 (NULL: the identity);
+ * leaf_ordered = 0: one record per triangle behind the references (the LDS-resident layout), != 0: one record per reference, in
+ * leaf order, carrying its triangle id (the global-memory layout);  rays[n_rays][7]: origin, unit direction, max_dist.
+ * out[n_rays][3]: t, beta, gamma (-1, 0, 0 on a miss);  triangle[n_rays]: index into corners, -1 on a miss. Host memory only. */
+int ptx_leaf_intersect_batch(ptx_ctx* ctx, const float* corners, uint32_t n_tri, const uint32_t* refs, int leaf_ordered, const float* rays, size_t n_rays,
+                             float* out, int32_t* triangle);
+
 /* Self-check of the short reciprocal / square-root sequences the kernels use in place of the IEEE ones (device_core.hpp), as compiled
  * into this library, guards and fallbacks included: every float pattern through each form. mismatches[3] receives, per form, the
  * count of results whose bits differ from the IEEE expression (NaN equals NaN): 1.0f / x, sqrtf(x), 1.0f / sqrtf(x). All zero when

@@ -9,6 +9,7 @@ fixtures themselves are committed so the tests run anywhere.
     python oracle/make_golden.py            # all fixtures (about 2 minutes)
     python oracle/make_golden.py --no-mean  # skip the converged mean images
     python oracle/make_golden.py --only-textures   # the texture fixture scene and tex_vectors.npz (a few seconds)
+    python oracle/make_golden.py --only-tri-scaled # tri_scaled_vectors.npz: triangle::intersect at the scales 2^-66 ... 2^66 (a second)
 """
 import argparse
 import glob
@@ -392,6 +393,14 @@ def make_texture_fixtures(env):
           f"{os.path.getsize(os.path.join(GOLD, 'tex_vectors.npz')) / 1024:.0f} KiB")
 
 
+def make_tri_scaled_fixture(env):
+    """tests/golden/tri_scaled_vectors.npz: 256 rows of the tri_in generator at unit scale (tri_in [256][15]), the exponents k
+    (tri_k) and triangle::intersect's distance and barycentrics with corners and ray origin multiplied by 2^k (tri_out [n_k][256][4])."""
+    with tempfile.TemporaryDirectory() as tmp:
+        subprocess.check_call([HARNESS, "tri_scaled", tmp, "3", "256"], env=env)
+        pack(tmp, os.path.join(GOLD, "tri_scaled_vectors.npz"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-mean", action="store_true")
@@ -399,6 +408,7 @@ def main():
     ap.add_argument("--only-jpeg", action="store_true", help="regenerate tests/golden/jpeg/* and jpeg_vectors.npz only")
     ap.add_argument("--only-hdr", action="store_true", help="regenerate tests/golden/hdr/* and hdr_vectors.npz only")
     ap.add_argument("--only-textures", action="store_true", help="regenerate tests/golden/textures/* and tex_vectors.npz only")
+    ap.add_argument("--only-tri-scaled", action="store_true", help="regenerate tri_scaled_vectors.npz only")
     ap.add_argument("--n", type=int, default=1024)
     args = ap.parse_args()
     subprocess.check_call(["make", "-s", "-j8", "-C", HERE, "ref"])
@@ -406,6 +416,9 @@ def main():
     env = dict(os.environ, ORACLE_SEED="20261004")
     if args.only_textures:
         make_texture_fixtures(env)
+        return
+    if args.only_tri_scaled:
+        make_tri_scaled_fixture(env)
         return
     if args.only_jpeg:
         make_jpeg_fixtures(env)
@@ -475,6 +488,7 @@ def main():
         make_jpeg_fixtures(env)
         make_hdr_fixtures(env)
         make_texture_fixtures(env)
+        make_tri_scaled_fixture(env)
         # a small deterministic PNG from renderer::render itself (single thread + fixed seed => reproducible)
         png = os.path.join(GOLD, "cornell_ref_64x64_16spp_4b.png")
         r = subprocess.check_output([HARNESS, "render", CORNELL, "64", "64", "16", "4", "1", png], env=env)

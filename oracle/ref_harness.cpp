@@ -19,6 +19,8 @@
 //                                                     image_texture::sample lookups on it (linear and sRGB)
 //   trace   <gltf> <outdir> <seed> <n> <bounces>      trace() of n rays in sequence, ONE thread, ONE seeded mt19937 stream: pins the
 //                                                     integrator's composition bit for bit (oracle side: ora_trace_mt)
+//   tri_scaled <outdir> <seed> <n>                    triangle::intersect on n rows of the `vectors` triangle generator, each at the
+//                                                     scales 2^k of kTriScales (corners and ray origin scaled, unit direction kept)
 //   mean    <gltf> <out.npy> W H spp bounces threads   float32 mean image by calling trace()
 //   render  <gltf> W H spp bounces threads [out.png]   time renderer::render(), print JSON
 
@@ -614,6 +616,51 @@ static int cmd_trace(const char* gltf, const std::string& dir, uint64_t seed, si
 	return 0;
 }
 
+// geometry::triangle::intersect (triangle.cpp:120-190) far from unit scale. Rows are drawn as cmd_vectors draws its tri_in block (aimed,
+// edge / vertex, axis-aligned, random and collinear kinds); for every k of kTriScales the corners and the ray origin are multiplied by
+// 2^k (exact: no value comes near the denormals or the overflow threshold) and the ray keeps its unit direction. The determinant
+// scales with 4^k, so around k = -63 and k = +63 it crosses the ends of the normal range while the hit stays a valid one.
+static const int kTriScales[] = {-66, -65, -64, -63, -62, -61, -60, -59, -58, -40, 0, 40, 58, 59, 60, 61, 62, 63, 64, 65, 66};
+static int cmd_tri_scaled(const std::string& dir, uint64_t seed, size_t n) {
+	std::filesystem::create_directories(dir);
+	pcg32 g(seed);
+	const size_t nk = sizeof(kTriScales) / sizeof(kTriScales[0]);
+	std::vector<float> in, out(nk * n * 4);
+	std::vector<int32_t> ks(kTriScales, kTriScales + nk);
+	for (size_t i = 0; i < n; i++) {
+		fvec3 a = g.vec(-2, 2), b = g.vec(-2, 2), c = g.vec(-2, 2);
+		fvec3 o = g.vec(-3, 3);
+		fvec3 d;
+		uint32_t kind = g.next() % 8;
+		if (kind < 5) {
+			float u = g.uni(), v = g.uni() * (1 - u);
+			fvec3 p = a * (1 - u - v) + b * u + c * v + g.vec(-0.05f, 0.05f);
+			d = normalize(p - o);
+		} else if (kind == 5) {
+			float u = g.uni();
+			fvec3 p = (g.next() & 1) ? a * (1 - u) + b * u : a;
+			d = normalize(p - o);
+		} else if (kind == 6) {
+			d = fvec3(0, 0, 0); d[g.next() % 3] = (g.next() & 1) ? 1.f : -1.f;
+		} else d = g.dir();
+		if (i % 97 == 0) c = a + (b - a) * 2.0f;
+		const geometry::ray unit(o, d);
+		push3(in, a); push3(in, b); push3(in, c); push3(in, unit.origin); push3(in, unit.get_dir());
+		for (size_t j = 0; j < nk; j++) {
+			const float s = std::ldexp(1.0f, kTriScales[j]);
+			const geometry::ray ray(o * s, d);
+			const fvec3 du = unit.get_dir(), dk = ray.get_dir();
+			if (memcmp(&dk, &du, sizeof(fvec3)) != 0) { fprintf(stderr, "tri_scaled: the direction changed with the scale\n"); return 3; }
+			const geometry::triangle tri(a * s, b * s, c * s);
+			const auto h = tri.intersect(ray);
+			float* q = &out[(j * n + i) * 4];
+			q[0] = h.distance; q[1] = h.barycentric.x; q[2] = h.barycentric.y; q[3] = h.barycentric.z;
+		}
+	}
+	save(dir, "tri_in", in, {n, 15}); save(dir, "tri_k", ks); save(dir, "tri_out", out, {nk, n, 4});
+	return 0;
+}
+
 // float32 mean image: same pixel loop as renderer::render (renderer.cpp:354-402) but keeping the
 // float running mean instead of the 8-bit image; rows are distributed statically over threads.
 static int cmd_mean(const char* gltf, const std::string& out, uint32_t W, uint32_t H, uint32_t spp, uint32_t bounces,
@@ -681,6 +728,7 @@ int main(int argc, char** argv) {
 		if (cmd == "envmap" && argc == 8) return cmd_envmap(argv[2], argv[3], atoi(argv[4]), argv[5], strtoull(argv[6], 0, 10), strtoull(argv[7], 0, 10));
 		if (cmd == "image" && argc == 6) return cmd_image(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10));
 		if (cmd == "trace" && argc == 7) return cmd_trace(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10), atoi(argv[6]));
+		if (cmd == "tri_scaled" && argc == 5) return cmd_tri_scaled(argv[2], strtoull(argv[3], 0, 10), strtoull(argv[4], 0, 10));
 		if (cmd == "mean" && argc == 9)
 			return cmd_mean(argv[2], argv[3], atoi(argv[4]), atoi(argv[5]), atoi(argv[6]), atoi(argv[7]), atoi(argv[8]));
 		if (cmd == "render" && argc >= 8)
@@ -689,6 +737,6 @@ int main(int argc, char** argv) {
 		fprintf(stderr, "ref_harness: %s\n", e.what());
 		return 2;
 	}
-	fprintf(stderr, "usage: ref_harness scene|vectors|materials|envmap|image|trace|mean|render ... (see header comment)\n");
+	fprintf(stderr, "usage: ref_harness scene|vectors|materials|envmap|image|trace|tri_scaled|mean|render ... (see header comment)\n");
 	return 1;
 }
