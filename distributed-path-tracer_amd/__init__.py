@@ -76,6 +76,10 @@ class RenderStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("samples", C.c_uint64), ("passes", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+class AovBuffers(C.Structure):
+    _fields_ = [("albedo_cov", C.c_void_p), ("normal_depth", C.c_void_p)]
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("pipeline", C.c_uint32), ("steps", C.c_uint32), ("classify_ms", C.c_double), ("traverse_ms", C.c_double), ("shade_ms", C.c_double),
                 ("fused_ms", C.c_double), ("fused_launches", C.c_uint32), ("pool_overflows", C.c_uint32), ("pool_pairs", C.c_uint64),
@@ -158,6 +162,7 @@ def lib():
         L.ptx_scene_get_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.ptx_render.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.POINTER(RenderStats)]
         L.ptx_render_transparent.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.c_void_p, C.POINTER(RenderStats)]
+        L.ptx_render_aov.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AovBuffers), C.POINTER(RenderStats)]
         L.ptx_intersect_batch.argtypes = [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(Hits)]
         L.ptx_tonemap_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ptx_pbr_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -395,6 +400,24 @@ class Scene:
         stats = dict(rays=st.rays, samples=st.samples, passes=st.passes, kernel_ms=st.kernel_ms) if want_stats else None
         return pixels, claimed, stats
 
+    def render_aov(self, W, H, spp, albedo=None, normal_depth=None, seed=0x5EED, tile=None, sample0=0, spp_per_pass=0, want_stats=True,
+                   shard=None):
+        """ptx_render_aov: first-hit guide buffers of the camera samples [sample0, sample0+spp) that render() traces. ADDS into
+        albedo [h,w,4] float32 (albedo rgb SUMS over the samples that end on a surface, w = how many did) and normal_depth [h,w,4]
+        (world shading normal SUMS, w = depth sum); numpy or torch-on-GPU, both of one kind. With neither given both are produced from
+        zeros; with one given only that one is produced (the other is returned as None). Tiles, sample ranges and shards compose as
+        in render(). Returns (albedo, normal_depth, stats dict or None)."""
+        x0, y0, w, h = tile if tile else (0, 0, W, H)
+        if albedo is None and normal_depth is None:
+            albedo, normal_depth = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+        cfg = RenderCfg(W, H, spp, 0, (C.c_float * 3)(1.0, 1.0, 1.0), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                        x0, y0, w, h, sample0, spp_per_pass, INTEGRATOR_LIB, *((tuple(shard) + (0,))[:3] if shard else (0, 0, 0)))
+        bufs = AovBuffers(_ptr(albedo), _ptr(normal_depth))
+        st = RenderStats()
+        _check(lib().ptx_render_aov(self.h, C.byref(cfg), C.byref(bufs), C.byref(st) if want_stats else None))
+        stats = dict(rays=st.rays, samples=st.samples, passes=st.passes, kernel_ms=st.kernel_ms) if want_stats else None
+        return albedo, normal_depth, stats
+
     def set_environment(self, png_path, srgb=True):
         """renderer::environment = image_texture::load(png_path, srgb): the miss colour becomes map(direction) * environment_factor.
         None removes the map."""
@@ -501,6 +524,18 @@ class Renderer:
         accum, self.last_stats = self._scene.render(W, H, self.sample_count, self.bounce_count,
                                                     env=self.environment_factor, seed=self.seed)
         return accum
+
+    def render_aov(self):
+        """Guide buffers of the frame's camera samples for a denoiser (Scene.render_aov), as MEANS: (albedo [H,W,3] and normal [H,W,3]
+        over the samples that end on a surface, depth [H,W] over the same samples, coverage [H,W] = their share of sample_count).
+        Pixels no sample covers are zero."""
+        if self._scene is None:
+            raise PtxError(ERR_INVALID, "render_aov() before load_gltf()")
+        W, H = self.resolution
+        alb, nd, self.last_stats = self._scene.render_aov(W, H, self.sample_count, seed=self.seed)
+        cov = alb[..., 3]
+        inv = np.where(cov > 0, 1.0 / np.maximum(cov, 1.0), 0.0).astype(np.float32)
+        return alb[..., :3] * inv[..., None], nd[..., :3] * inv[..., None], nd[..., 3] * inv, cov / np.float32(self.sample_count)
 
     def render(self):
         W, H = self.resolution

@@ -179,4 +179,26 @@ hipError_t launch_camera_rays(const DevScene& S, const float* in /* [n][3]: ndc.
 hipError_t launch_material_eval(const DevScene& S, const int32_t* surface /* [n] */, const float* uv /* [n][2] */, size_t n, float* out /* [n][12] */, hipStream_t stream);
 hipError_t launch_tonemap(const float4* accum, uint32_t n_pixels, float spp, const float* thresholds /* [256], device */, uchar4* out, hipStream_t stream);
 
+// First-hit guide buffers (aov.hip, ptx_render_aov). A ROUND = the live samples' rays through the scene's own intersect route, then one
+// k_aov_shade lane per sample: it either records the sample's surface or appends the ray behind an opacity pass-through to the next
+// round's stream. Rays are SoA of floats — the layout both intersect launches read (IntersectArgs).
+struct AovStream {
+	float *ox, *oy, *oz, *dx, *dy, *dz;   // [cap]
+	uint32_t* id;     // [cap] the sample's id within the pass (sample-major, pixel-minor); nullptr = entry i is sample i, pass 0 (round 0)
+	uint32_t* pass;   // [cap] pass-throughs behind the sample so far
+};
+struct AovHits {   // what the intersect launch wrote for the round's rays
+	const int32_t *surface, *triangle;   // -1 = miss; triangle index within the surface's mesh
+	const float *b1, *b2;
+};
+hipError_t launch_aov_generate(const DevScene& S, const RenderParams& P, const AovStream& out, uint32_t n, hipStream_t stream);
+// rec: [2][rec_stride] per-sample records of the pass, indexed by sample id: (albedo, 1) and (shading normal, depth); zeros for a sample that
+// ends on a miss. *n_out (device, zeroed before the launch) receives the number of entries appended to `out`; untouched when the scene has
+// no pass-through material (DevScene::any_alpha == 0)
+hipError_t launch_aov_shade(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* n_out,
+                            float4* rec, size_t rec_stride, hipStream_t stream);
+// adds the pass's records of each pixel, in sample order, into the caller's buffers (either may be nullptr)
+hipError_t launch_aov_resolve(const float4* rec, size_t rec_stride, float4* albedo_cov, float4* normal_depth, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp,
+                              hipStream_t stream);
+
 }  // namespace ptx

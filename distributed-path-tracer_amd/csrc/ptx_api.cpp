@@ -82,6 +82,7 @@ struct ptx_ctx {
 	int n_cu = 0;
 	std::mutex mu;
 	DevBuf queues, sample_rad, counters, spill, stage_a, stage_b, pixel_list, srgb_thr;
+	DevBuf aov;   // workspace of ptx_render_aov: the streams, hits and per-sample records of one pass
 	// workspace of the queue-based pipeline (wavefront.hip): ptx_render and ptx_intersect_batch run it on the context's stream
 	struct WfSet {
 		DevBuf qent, pair_hit, seg, first, mask, ctl, spill, stream_buf, flow;
@@ -368,7 +369,7 @@ static void ctx_release(ptx_ctx* c) {
 	(void)hipStreamSynchronize(c->stream);
 	for (hipEvent_t ev : c->events) (void)hipEventDestroy(ev);
 	for (hipEvent_t ev : c->step_events) (void)hipEventDestroy(ev);
-	c->queues.release(); c->spill.release(); c->sample_rad.release(); c->counters.release(); c->stage_a.release(); c->stage_b.release(); c->pixel_list.release(); c->srgb_thr.release();
+	c->queues.release(); c->spill.release(); c->sample_rad.release(); c->counters.release(); c->stage_a.release(); c->stage_b.release(); c->pixel_list.release(); c->srgb_thr.release(); c->aov.release();
 	ptx_ctx::WfSet& w = c->wf;
 	for (DevBuf* b : {&w.qent, &w.pair_hit, &w.seg, &w.first, &w.mask, &w.ctl, &w.spill, &w.stream_buf, &w.flow}) b->release();
 	if (w.flow_host) { (void)hipHostFree(w.flow_host); w.flow_host = nullptr; }
@@ -1103,45 +1104,16 @@ int ptx_render_transparent(ptx_scene* sc, const ptx_render_cfg* cfg, float* pixe
 	return render_frame(sc, cfg, pixel_rgba, claimed, stats);
 }
 
-int ptx_intersect_batch(ptx_scene* sc, const ptx_rays* r, size_t n, const ptx_hits* hh) {
-	if (!sc || !r || !hh) return set_err(PTX_ERR_INVALID, "ptx_intersect_batch: NULL argument");
-	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_intersect_batch: scene was created without a GPU context (no CPU path exists)");
-	if (n == 0) return PTX_OK;
-	if (!r->ox || !r->oy || !r->oz || !r->dx || !r->dy || !r->dz || !hh->distance || !hh->surface || !hh->triangle || !hh->b0 || !hh->b1 || !hh->b2)
-		return set_err(PTX_ERR_INVALID, "ptx_intersect_batch: required array is NULL");
-	auto group_ok = [](const void* a, const void* b, const void* c) { return (!a && !b && !c) || (a && b && c); };
-	if (!group_ok(hh->px, hh->py, hh->pz) || !group_ok(hh->nx, hh->ny, hh->nz) || ((hh->u != nullptr) != (hh->v != nullptr)))
-		return set_err(PTX_ERR_INVALID, "ptx_intersect_batch: optional outputs must be given as whole groups");
-	ptx_ctx* c = sc->ctx;
-	std::lock_guard<std::mutex> lk(c->mu);
-	HIP_TRY(hipSetDevice(c->device));
-	const bool dev = is_device_ptr(r->ox);
-	IntersectArgs A{};
-	A.n = n;
-	const int n_out = 6 + (hh->px ? 3 : 0) + (hh->nx ? 3 : 0) + (hh->u ? 2 : 0);
-	if (dev) {
-		A.ox = r->ox; A.oy = r->oy; A.oz = r->oz; A.dx = r->dx; A.dy = r->dy; A.dz = r->dz;
-		A.distance = hh->distance; A.surface = hh->surface; A.triangle = hh->triangle;
-		A.b0 = hh->b0; A.b1 = hh->b1; A.b2 = hh->b2;
-		A.px = hh->px; A.py = hh->py; A.pz = hh->pz; A.nx = hh->nx; A.ny = hh->ny; A.nz = hh->nz; A.u = hh->u; A.v = hh->v;
-	} else {
-		HIP_TRY(c->stage_a.ensure(6 * n * 4));
-		HIP_TRY(c->stage_b.ensure((size_t)n_out * n * 4));
-		float* in = (float*)c->stage_a.p;
-		const float* src[6] = {r->ox, r->oy, r->oz, r->dx, r->dy, r->dz};
-		for (int k = 0; k < 6; k++) HIP_TRY(hipMemcpyAsync(in + k * n, src[k], n * 4, hipMemcpyHostToDevice, c->stream));
-		A.ox = in; A.oy = in + n; A.oz = in + 2 * n; A.dx = in + 3 * n; A.dy = in + 4 * n; A.dz = in + 5 * n;
-		float* o = (float*)c->stage_b.p;
-		A.distance = o; A.surface = (int32_t*)(o + n); A.triangle = (int32_t*)(o + 2 * n);
-		A.b0 = o + 3 * n; A.b1 = o + 4 * n; A.b2 = o + 5 * n;
-		size_t k = 6;
-		if (hh->px) { A.px = o + k * n; A.py = o + (k + 1) * n; A.pz = o + (k + 2) * n; k += 3; }
-		if (hh->nx) { A.nx = o + k * n; A.ny = o + (k + 1) * n; A.nz = o + (k + 2) * n; k += 3; }
-		if (hh->u) { A.u = o + k * n; A.v = o + (k + 1) * n; }
-	}
+namespace {
+
+// Closest hits of the A.n rays of `A` (device memory) on the scene's own route — the routing body of ptx_intersect_batch, shared with
+// ptx_render_aov: the queue-based pipeline in slices with its overflow / retry handling, or the fused kernel's traversal. The caller holds
+// the context's mutex and has set the device.
+int intersect_device(ptx_ctx* c, ptx_scene* sc, IntersectArgs& A) {
 	if (use_wavefront(sc)) {
 		// queue-based pipeline, a slice of the batch at a time: as many rays as the pool serves at the pairs per ray this scene was seen
 		// to need; a slice whose pairs do not fit is repeated smaller (the ratio it reported is remembered on the scene)
+		const size_t n = A.n;
 		const size_t n_surf = sc->host.surfaces.size();
 		// the pool: what the whole batch is expected to need (in steps of 16 Mi pairs), at most kWfBatchPairs — one launch for a batch of
 		// up to ~60 M rays of a 24-surface scene; larger batches go in slices
@@ -1186,17 +1158,194 @@ int ptx_intersect_batch(ptx_scene* sc, const ptx_rays* r, size_t n, const ptx_hi
 			first += m;
 		}
 	} else {
-		const int grid = (int)std::min<size_t>((size_t)c->n_cu, (n + kBlock - 1) / kBlock);
+		const int grid = (int)std::min<size_t>((size_t)c->n_cu, (A.n + kBlock - 1) / kBlock);
 		HIP_TRY(c->spill.ensure((size_t)c->n_cu * (kBlock / 64) * (size_t)kSpillWords * sizeof(uint2)));
 		A.spill = (uint2*)c->spill.p;
 		HIP_TRY(launch_intersect(sc->dev, A, sc->mode, sc->lds_bytes, grid, c->stream));
 	}
+	return PTX_OK;
+}
+
+}  // namespace
+
+int ptx_intersect_batch(ptx_scene* sc, const ptx_rays* r, size_t n, const ptx_hits* hh) {
+	if (!sc || !r || !hh) return set_err(PTX_ERR_INVALID, "ptx_intersect_batch: NULL argument");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_intersect_batch: scene was created without a GPU context (no CPU path exists)");
+	if (n == 0) return PTX_OK;
+	if (!r->ox || !r->oy || !r->oz || !r->dx || !r->dy || !r->dz || !hh->distance || !hh->surface || !hh->triangle || !hh->b0 || !hh->b1 || !hh->b2)
+		return set_err(PTX_ERR_INVALID, "ptx_intersect_batch: required array is NULL");
+	auto group_ok = [](const void* a, const void* b, const void* c) { return (!a && !b && !c) || (a && b && c); };
+	if (!group_ok(hh->px, hh->py, hh->pz) || !group_ok(hh->nx, hh->ny, hh->nz) || ((hh->u != nullptr) != (hh->v != nullptr)))
+		return set_err(PTX_ERR_INVALID, "ptx_intersect_batch: optional outputs must be given as whole groups");
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	const bool dev = is_device_ptr(r->ox);
+	IntersectArgs A{};
+	A.n = n;
+	const int n_out = 6 + (hh->px ? 3 : 0) + (hh->nx ? 3 : 0) + (hh->u ? 2 : 0);
+	if (dev) {
+		A.ox = r->ox; A.oy = r->oy; A.oz = r->oz; A.dx = r->dx; A.dy = r->dy; A.dz = r->dz;
+		A.distance = hh->distance; A.surface = hh->surface; A.triangle = hh->triangle;
+		A.b0 = hh->b0; A.b1 = hh->b1; A.b2 = hh->b2;
+		A.px = hh->px; A.py = hh->py; A.pz = hh->pz; A.nx = hh->nx; A.ny = hh->ny; A.nz = hh->nz; A.u = hh->u; A.v = hh->v;
+	} else {
+		HIP_TRY(c->stage_a.ensure(6 * n * 4));
+		HIP_TRY(c->stage_b.ensure((size_t)n_out * n * 4));
+		float* in = (float*)c->stage_a.p;
+		const float* src[6] = {r->ox, r->oy, r->oz, r->dx, r->dy, r->dz};
+		for (int k = 0; k < 6; k++) HIP_TRY(hipMemcpyAsync(in + k * n, src[k], n * 4, hipMemcpyHostToDevice, c->stream));
+		A.ox = in; A.oy = in + n; A.oz = in + 2 * n; A.dx = in + 3 * n; A.dy = in + 4 * n; A.dz = in + 5 * n;
+		float* o = (float*)c->stage_b.p;
+		A.distance = o; A.surface = (int32_t*)(o + n); A.triangle = (int32_t*)(o + 2 * n);
+		A.b0 = o + 3 * n; A.b1 = o + 4 * n; A.b2 = o + 5 * n;
+		size_t k = 6;
+		if (hh->px) { A.px = o + k * n; A.py = o + (k + 1) * n; A.pz = o + (k + 2) * n; k += 3; }
+		if (hh->nx) { A.nx = o + k * n; A.ny = o + (k + 1) * n; A.nz = o + (k + 2) * n; k += 3; }
+		if (hh->u) { A.u = o + k * n; A.v = o + (k + 1) * n; }
+	}
+	if (const int rc = intersect_device(c, sc, A); rc != PTX_OK) return rc;
 	if (!dev) {
 		void* dst[14] = {hh->distance, hh->surface, hh->triangle, hh->b0, hh->b1, hh->b2, hh->px, hh->py, hh->pz, hh->nx, hh->ny, hh->nz, hh->u, hh->v};
 		const void* srcs[14] = {A.distance, A.surface, A.triangle, A.b0, A.b1, A.b2, A.px, A.py, A.pz, A.nx, A.ny, A.nz, A.u, A.v};
 		for (int k = 0; k < 14; k++)
 			if (dst[k]) HIP_TRY(hipMemcpyAsync(dst[k], srcs[k], n * 4, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
+	}
+	return PTX_OK;
+}
+
+namespace {
+
+// samples of every pixel per AOV pass. The workspace holds two ray streams, the hits and two records per sample (kAovSampleBytes), so the
+// default bounds a pass by samples, not by the frame: 32 Mi (16 spp of a 1080p frame, 3.8 GB)
+constexpr size_t kAovSampleBytes = (2 * 8 + 6 + 8) * 4;
+uint32_t aov_pass_size(const ptx_render_cfg* cfg, uint64_t n_pixels) {
+	uint32_t pass_spp = cfg->spp_per_pass ? cfg->spp_per_pass : (uint32_t)std::max<uint64_t>(1, (32ull << 20) / n_pixels);
+	pass_spp = std::min(pass_spp, cfg->spp);
+	while ((uint64_t)pass_spp * n_pixels > 0xFFFFFFFFull) pass_spp--;   // sample ids are 32-bit
+	return pass_spp;
+}
+
+}  // namespace
+
+int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffers* out, ptx_render_stats* stats) {
+	// every refusal below is decided before any device work
+	if (!sc || !cfg || !out) return set_err(PTX_ERR_INVALID, "ptx_render_aov: NULL argument");
+	if (!out->albedo_cov && !out->normal_depth) return set_err(PTX_ERR_INVALID, "ptx_render_aov: both buffers are NULL (at least one must be given)");
+	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
+		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_aov: PTX_INTEGRATOR_WORKER has no guide buffers here (the worker's opacity handling and its un-jittered "
+		                                    "sample 0 are not pinned); use PTX_INTEGRATOR_LIB");
+	if (cfg->integrator > PTX_INTEGRATOR_WORKER) return set_err(PTX_ERR_INVALID, "ptx_render_aov: unknown integrator");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_aov: scene was created without a GPU context (no CPU path exists)");
+	if (!cfg->W || !cfg->H) return set_err(PTX_ERR_INVALID, "ptx_render_aov: W and H must be > 0");
+	uint32_t x0 = cfg->x0, y0 = cfg->y0, w = cfg->w, h = cfg->h;
+	if (w == 0 && h == 0) { x0 = 0; y0 = 0; w = cfg->W; h = cfg->H; }
+	if (!w || !h || (uint64_t)x0 + w > cfg->W || (uint64_t)y0 + h > cfg->H) return set_err(PTX_ERR_INVALID, "ptx_render_aov: tile outside the image");
+	if (cfg->shard_count > 1 && cfg->shard_index >= cfg->shard_count) return set_err(PTX_ERR_INVALID, "ptx_render_aov: shard_index >= shard_count");
+	const uint64_t rect_pixels = (uint64_t)w * h;
+	if (rect_pixels > 0x7FFFFFFFull) return set_err(PTX_ERR_INVALID, "ptx_render_aov: tile too large");
+	const bool dev_out = is_device_ptr(out->albedo_cov ? out->albedo_cov : out->normal_depth);
+	if (out->albedo_cov && out->normal_depth && is_device_ptr(out->normal_depth) != dev_out)
+		return set_err(PTX_ERR_INVALID, "ptx_render_aov: albedo_cov and normal_depth must both be device or both be host memory");
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	if (stats) *stats = ptx_render_stats{};
+	if (cfg->spp == 0) return PTX_OK;
+	uint64_t n_pixels = 0;
+	const uint32_t* d_pixels = nullptr;
+	if (const int rc = pixel_list(c, sc, cfg, x0, y0, w, h, n_pixels, d_pixels); rc != PTX_OK) return rc;
+	if (n_pixels == 0) return PTX_OK;   // no tile of this shard meets the rectangle
+	const uint32_t pass_spp = aov_pass_size(cfg, n_pixels);
+	if (pass_spp == 0) return set_err(PTX_ERR_INVALID, "ptx_render_aov: tile too large for one pass");
+
+	// workspace of one pass of `cap` samples: [256 B: live counts][stream 0][stream 1][hits][records]
+	const size_t cap = ((size_t)pass_spp * n_pixels + 3) & ~(size_t)3;   // array stride: keeps the float4 records 16-byte aligned
+	HIP_TRY(c->aov.ensure(256 + cap * kAovSampleBytes));
+	uint32_t* const live_count = (uint32_t*)c->aov.p;
+	float* f = (float*)((char*)c->aov.p + 256);
+	AovStream st[2];
+	for (AovStream& s : st) {
+		s.ox = f; s.oy = f + cap; s.oz = f + 2 * cap; s.dx = f + 3 * cap; s.dy = f + 4 * cap; s.dz = f + 5 * cap;
+		s.id = (uint32_t*)(f + 6 * cap); s.pass = (uint32_t*)(f + 7 * cap);
+		f += 8 * cap;
+	}
+	float* const hits = f;
+	float4* const rec = (float4*)(f + 6 * cap);
+
+	float4* d_albedo = (float4*)out->albedo_cov;
+	float4* d_normal = (float4*)out->normal_depth;
+	if (!dev_out) {
+		if (out->albedo_cov) {
+			HIP_TRY(c->stage_a.ensure(rect_pixels * sizeof(float4)));
+			d_albedo = (float4*)c->stage_a.p;
+			HIP_TRY(hipMemcpyAsync(d_albedo, out->albedo_cov, rect_pixels * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+		}
+		if (out->normal_depth) {
+			HIP_TRY(c->stage_b.ensure(rect_pixels * sizeof(float4)));
+			d_normal = (float4*)c->stage_b.p;
+			HIP_TRY(hipMemcpyAsync(d_normal, out->normal_depth, rect_pixels * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+		}
+	}
+
+	const uint32_t n_pass = (cfg->spp + pass_spp - 1) / pass_spp;
+	if (stats)
+		while (c->events.size() < 2 * (size_t)n_pass) {
+			hipEvent_t ev;
+			HIP_TRY(hipEventCreate(&ev));
+			c->events.push_back(ev);
+		}
+	const bool follow = sc->dev.any_alpha != 0;   // some material can pass a sample through: the live count decides when a pass is over
+	uint64_t rays = 0;
+	for (uint32_t p = 0; p < n_pass; p++) {
+		RenderParams P{};
+		P.W = cfg->W; P.H = cfg->H; P.x0 = x0; P.y0 = y0; P.w = w; P.h = h;
+		P.n_pixels = (uint32_t)n_pixels;
+		P.sample0 = cfg->sample0 + p * pass_spp;
+		P.pass_spp = std::min(pass_spp, cfg->spp - p * pass_spp);
+		P.n_paths = (uint64_t)P.pass_spp * n_pixels;
+		P.seed_lo = cfg->seed_lo; P.seed_hi = cfg->seed_hi;
+		P.integrator = PTX_INTEGRATOR_LIB;
+		P.pixels = d_pixels;
+		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
+		HIP_TRY(launch_aov_generate(sc->dev, P, st[0], (uint32_t)P.n_paths, c->stream));
+		uint32_t live = (uint32_t)P.n_paths;
+		for (uint32_t round = 0; live != 0; round++) {
+			AovStream in = st[round & 1u];
+			if (round == 0) { in.id = nullptr; in.pass = nullptr; }   // entry i is sample i
+			IntersectArgs A{};
+			A.n = live;
+			A.ox = in.ox; A.oy = in.oy; A.oz = in.oz; A.dx = in.dx; A.dy = in.dy; A.dz = in.dz;
+			A.distance = hits; A.surface = (int32_t*)(hits + cap); A.triangle = (int32_t*)(hits + 2 * cap);
+			A.b0 = hits + 3 * cap; A.b1 = hits + 4 * cap; A.b2 = hits + 5 * cap;
+			if (const int rc = intersect_device(c, sc, A); rc != PTX_OK) return rc;
+			rays += live;
+			const AovHits H{A.surface, A.triangle, A.b1, A.b2};
+			uint32_t* const n_out = live_count + (round & 1u);
+			if (follow) HIP_TRY(hipMemsetAsync(n_out, 0, 4, c->stream));
+			HIP_TRY(launch_aov_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, cap, c->stream));
+			if (!follow) break;
+			HIP_TRY(hipMemcpyAsync(&live, n_out, 4, hipMemcpyDeviceToHost, c->stream));
+			HIP_TRY(hipStreamSynchronize(c->stream));
+		}
+		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
+		HIP_TRY(launch_aov_resolve(rec, cap, d_albedo, d_normal, d_pixels, P.n_pixels, P.pass_spp, c->stream));
+	}
+	if (!dev_out) {
+		if (out->albedo_cov) HIP_TRY(hipMemcpyAsync(out->albedo_cov, d_albedo, rect_pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+		if (out->normal_depth) HIP_TRY(hipMemcpyAsync(out->normal_depth, d_normal, rect_pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+	}
+	if (stats || !dev_out) HIP_TRY(hipStreamSynchronize(c->stream));
+	if (stats) {
+		stats->rays = rays;
+		stats->samples = (uint64_t)cfg->spp * n_pixels;
+		stats->passes = n_pass;
+		for (uint32_t p = 0; p < n_pass; p++) {
+			float t = 0;
+			HIP_TRY(hipEventElapsedTime(&t, c->events[2 * p], c->events[2 * p + 1]));
+			stats->kernel_ms += t;
+		}
 	}
 	return PTX_OK;
 }

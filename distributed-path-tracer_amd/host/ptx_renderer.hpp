@@ -69,6 +69,20 @@ public:
 		return accum;
 	}
 
+	// Guide buffers of the frame's camera samples for a denoiser (ptx_render_aov): SUMS over sample_count samples, [H][W][4] each —
+	// albedo rgb + coverage count, world shading normal xyz + depth sum. Divide by the coverage count for means. stats optional
+	struct aov { std::vector<float> albedo_cov, normal_depth; };
+	aov render_aov(ptx_render_stats* stats = nullptr) const {
+		if (!scene_) throw std::runtime_error("render_aov() before load_gltf()");
+		ptx_render_cfg c{};
+		c.W = resolution.x; c.H = resolution.y; c.spp = sample_count;
+		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
+		aov a{std::vector<float>((size_t)c.W * c.H * 4, 0.f), std::vector<float>((size_t)c.W * c.H * 4, 0.f)};
+		const ptx_aov_buffers b{a.albedo_cov.data(), a.normal_depth.data()};
+		check(ptx_render_aov(scene_, &c, &b, stats));
+		return a;
+	}
+
 	std::vector<uint8_t> render() const {   // renderer.cpp:334-428: PNG bytes (RGBA8, ACES tonemap, sRGB)
 		std::vector<float> accum = render_accum();
 		std::vector<uint8_t> rgba((size_t)resolution.x * resolution.y * 4);

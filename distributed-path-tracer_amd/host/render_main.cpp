@@ -1,21 +1,44 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] <scene.gltf> <out.png> [W H spp bounces]       (--transparent: renderer::transparent_background)
+//   ptx_render_cli [--transparent] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//       --transparent: renderer::transparent_background
+//       --aov PREFIX:  also writes the denoiser's guide images PREFIX_albedo.png (mean albedo of the covered samples, alpha = coverage)
+//                      and PREFIX_normal.png (mean shading normal * 0.5 + 0.5), quantised linearly to 8 bits
 //   ptx_render_cli --event <event.json> <local scene root dir> <out.png>     (the worker's Lambda event, main.cpp:9-25)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "ptx_renderer.hpp"
 
+// plain linear 8-bit quantiser of a value in [0, 1]
+static uint8_t quant8(float v) {
+	v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+	return (uint8_t)(v * 255.f + 0.5f);
+}
+
+static void write_png(const std::string& path, const std::vector<uint8_t>& rgba, uint32_t W, uint32_t H) {
+	uint8_t* png = nullptr;
+	size_t n = 0;
+	if (ptx_encode_png(rgba.data(), W, H, &png, &n) != PTX_OK) throw std::runtime_error(ptx_last_error());
+	std::ofstream(path, std::ios::binary).write((const char*)png, (std::streamsize)n);
+	ptx_free(png);
+}
+
 int main(int argc, char** argv) {
-	const bool transparent = argc > 1 && std::string(argv[1]) == "--transparent";
-	if (transparent) { argv[1] = argv[0]; argv++; argc--; }
+	bool transparent = false;
+	std::string aov_prefix;
+	for (;;) {   // leading switches
+		if (argc > 1 && std::string(argv[1]) == "--transparent") { transparent = true; argv[1] = argv[0]; argv++; argc--; }
+		else if (argc > 2 && std::string(argv[1]) == "--aov") { aov_prefix = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }
+		else break;
+	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (argc == 5 && std::string(argv[1]) == "--event") {
@@ -57,8 +80,28 @@ int main(int argc, char** argv) {
 		std::vector<uint8_t> png = r.render();
 		double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 		std::ofstream(argv[2], std::ios::binary).write((const char*)png.data(), (std::streamsize)png.size());
-		std::printf("{\"W\": %u, \"H\": %u, \"spp\": %u, \"bounces\": %u, \"seconds\": %.4f, \"png_bytes\": %zu}\n", r.resolution.x, r.resolution.y,
+		double aov_ms = 0;
+		if (!aov_prefix.empty()) {
+			ptx_render_stats st{};
+			const core::renderer::aov a = r.render_aov(&st);
+			aov_ms = st.kernel_ms;
+			const uint32_t W = r.resolution.x, H = r.resolution.y;
+			std::vector<uint8_t> alb((size_t)W * H * 4), nrm((size_t)W * H * 4);
+			for (size_t p = 0; p < (size_t)W * H; p++) {
+				const float cov = a.albedo_cov[4 * p + 3], inv = cov > 0.f ? 1.f / cov : 0.f;
+				for (int k = 0; k < 3; k++) {
+					alb[4 * p + k] = quant8(a.albedo_cov[4 * p + k] * inv);
+					nrm[4 * p + k] = quant8(cov > 0.f ? a.normal_depth[4 * p + k] * inv * 0.5f + 0.5f : 0.f);
+				}
+				alb[4 * p + 3] = nrm[4 * p + 3] = quant8(cov / (float)r.sample_count);
+			}
+			write_png(aov_prefix + "_albedo.png", alb, W, H);
+			write_png(aov_prefix + "_normal.png", nrm, W, H);
+		}
+		std::printf("{\"W\": %u, \"H\": %u, \"spp\": %u, \"bounces\": %u, \"seconds\": %.4f, \"png_bytes\": %zu", r.resolution.x, r.resolution.y,
 		            r.sample_count, (unsigned)r.bounce_count, s, png.size());
+		if (!aov_prefix.empty()) std::printf(", \"aov_kernel_ms\": %.3f", aov_ms);
+		std::printf("}\n");
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "error: %s\n", e.what());
 		return 2;

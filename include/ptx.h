@@ -212,6 +212,34 @@ int ptx_render(ptx_scene* scene, const ptx_render_cfg* cfg, float* accum_rgba, p
  * buffers — all decided before any device work. */
 int ptx_render_transparent(ptx_scene* scene, const ptx_render_cfg* cfg, float* pixel_rgba, uint8_t* claimed, ptx_render_stats* stats);
 
+/* First-hit guide buffers for a denoiser (no counterpart in the reference, which writes the beauty frame only): per camera sample, the albedo,
+ * world shading normal and depth of the first surface the sample ends on, and whether it ends on one (coverage). The camera samples are
+ * exactly those of ptx_render: the same cfg fields (W, H, x0, y0, w, h, sample0, spp, seed_*, spp_per_pass, shard_*) and the same Philox
+ * keys, so sample s of pixel p here is the camera ray of sample s of pixel p in the beauty frame (renderer.cpp:359-370). `bounces` and
+ * `env` are ignored.
+ * One sample: the camera ray goes through renderer::intersect (renderer.cpp:441). On a hit the material is evaluated (renderer.cpp:458-463)
+ * and the opacity rule of renderer.cpp:466-472 applied as the integrator applies it — !is_approx(opacity, 1) && draw > opacity, with the
+ * integrator's own draw for that vertex (depth 0, the sample's pass count) — and a sample that passes through continues from
+ * position + dir * epsilon with the re-normalised direction; after 4096 pass-throughs it ends as a miss, as in ptx_render. The first
+ * vertex that does not pass through is the sample's surface: albedo = material::get_albedo, normal = intersect_result::get_normal()
+ * (renderer.cpp:430-435, what ptx_hits.nx/ny/nz report), depth = length(position - origin of the camera ray). A back-facing hit
+ * (renderer.cpp:478) is recorded like any other. A shadow catcher is an ordinary surface here: whether it passes a sample through depends
+ * on its sun sample (renderer.cpp:513-519), which stays with the beauty path. A miss adds nothing to either buffer.
+ * Both buffers are SUMS over the samples, ADDED to what the caller passes in; a pixel's samples are added in sample order. So calls of
+ * ASCENDING, adjacent sample ranges on the same buffers are bitwise one call (for any spp_per_pass); tile rectangles and shard_* compose as
+ * in ptx_render (other shards' pixels are untouched: the sum of zero-initialised shard buffers is bitwise the unsharded one), and
+ * ptx_reduce_framebuffer applies as it is. Sample ranges rendered into separate buffers agree up to float summation order only.
+ * Either pointer may be NULL (that buffer is not produced), not both; two buffers are both device or both host memory.
+ * stats (may be NULL): rays = intersect queries, continuation rays included; samples; passes; kernel_ms = HIP-event time of the passes.
+ * PTX_ERR_INVALID for a NULL scene, cfg or out or two NULL buffers; PTX_ERR_UNSUPPORTED for PTX_INTEGRATOR_WORKER (its opacity handling,
+ * shading_worker.cpp:54-63, and un-jittered sample 0, worker.cpp:125-126, are not pinned); PTX_ERR_NO_DEVICE for a host-only scene —
+ * all decided before any device work. */
+typedef struct ptx_aov_buffers {
+	float* albedo_cov;    /* [h][w][4]: sum of albedo rgb over the samples that end on a surface; w = how many did (coverage count) */
+	float* normal_depth;  /* [h][w][4]: sum of the world shading normal xyz; w = sum of length(hit position - camera ray origin) */
+} ptx_aov_buffers;
+int ptx_render_aov(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_aov_buffers* out, ptx_render_stats* stats);
+
 /* Measurement aid (no counterpart in the reference): where the time of the last ptx_render that was given a stats pointer went.
  * Scenes whose geometry fits the LDS or whose models have few surfaces run ONE fused kernel per pass (pipeline 0: fused_ms);
  * many-surface scenes in global memory run the queue-based pipeline (pipeline 1) — per step of a slab of paths a classify, a

@@ -1,0 +1,452 @@
+"""ptx_render_aov: first-hit albedo, shading normal, depth and coverage of the camera samples, against the oracle.
+
+The expected values come from the oracle alone, restated here in float32 numpy (`restate`): per sample s the oracle's jittered
+camera rays (OracleScene.primary_rays) go through OracleScene.intersect; OracleScene.material_eval gives albedo and opacity; the
+opacity rule of renderer.cpp:466-472 — !is_approx(opacity, 1) && draw > opacity — takes the integrator's own draw,
+ora.draws(pixel, s, seed, depth 0, pass, BLOCK_SURFACE)[0]; a sample that passes through continues from pos + d * 0.0001f with the
+direction normalised as oracle/pt_oracle.cpp states it, d * (1 / sqrt((x*x + y*y) + z*z)), pass + 1 (more than 4096 passes: a miss); the
+first vertex that does not pass through is recorded: albedo, the shading normal, depth = sqrt((x*x + y*y) + z*z) of pos - camera ray
+origin. Records are accumulated per pixel with += in sample order; a miss adds nothing. Nothing on this path goes through libm, so the
+product is held to BITWISE equality on every pixel of both buffers, on every route; each route is asserted from the scene's residency
+and the pipeline a tiny render reports under the same environment, as tests/test_unit_limits.py does.
+
+Common shape: 96 x 54, tile (13, 9, 67, 35), samples 3 .. 7, two samples per pass, seed 0x5EED: 2345 pixels (no multiple of 64 or 1024),
+4690 rays per full pass, a ragged last pass of one sample, sample indices that do not start at 0.
+"""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+
+from conftest import CORNELL, JACK, oracle_from_dict, product_from_dict
+from test_unit_limits import clean_env  # noqa: F401  (a fixture)
+
+W, H, TILE, S0, SPP, PER_PASS, SEED, B = 96, 54, (13, 9, 67, 35), 3, 5, 2, 0x5EED, 4
+f32 = np.float32
+EPS = f32(0.0001)   # math::epsilon
+
+
+def _proc():
+    return importlib.import_module("distributed-path-tracer_amd.procedural")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _len3(v):
+    """sqrt((x*x + y*y) + z*z) in float32, the parenthesisation of oracle/pt_oracle.cpp (dot, then length)."""
+    v = np.asarray(v, f32)
+    return np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]).astype(f32)
+
+
+def restate(ora, o, W_=W, H_=H, tile=TILE, sample0=S0, spp=SPP, seed=SEED):
+    """-> (albedo_cov [h,w,4], normal_depth [h,w,4], counts) for samples [sample0, sample0 + spp) of the tile; counts: samples, those that
+    passed through at least once, the longest pass-through chain, samples that ended on a miss."""
+    x0, y0, w, h = tile
+    alb, nd = np.zeros((h * w, 4), f32), np.zeros((h * w, 4), f32)
+    yy, xx = np.divmod(np.arange(h * w), w)
+    pixel = (yy + y0) * W_ + (xx + x0)
+    counts = dict(samples=0, through=0, chain=0, miss=0)
+    for s in range(sample0, sample0 + spp):
+        rays = o.primary_rays(ora.make_cfg(W_, H_, 1, 1, seed=seed, tile=tile), s).reshape(-1, 6)
+        origin = rays[:, :3].copy()
+        ra, rn = np.zeros((h * w, 4), f32), np.zeros((h * w, 4), f32)
+        live, cur, pas = np.arange(h * w), rays.copy(), np.zeros(h * w, np.int64)
+        passed = np.zeros(h * w, np.int64)
+        while len(live):
+            out, idx = o.intersect(cur)
+            hit = idx >= 0
+            me = np.zeros((len(live), 12), f32)
+            for u in np.unique(idx[hit]):
+                sel = idx == u
+                me[sel] = o.material_eval(int(u), out[sel, 3:5])
+            op = me[:, 6]
+            through = np.zeros(len(live), bool)
+            for k in np.flatnonzero(hit & ~((op == f32(1)) | (np.abs(op - f32(1)) < EPS))):   # !is_approx(opacity, 1)
+                through[k] = ora.draws(int(pixel[live[k]]), s, seed, 0, int(pas[k]), 0)[0] > op[k]
+            surf = hit & ~through
+            ra[live[surf], :3], ra[live[surf], 3] = me[surf, 3:6], f32(1)
+            rn[live[surf], :3], rn[live[surf], 3] = out[surf, 11:14], _len3(out[surf, :3] - origin[live[surf]])
+            d = cur[through, 3:6]
+            nxt = np.concatenate([out[through, :3] + d * EPS, d * (f32(1) / _len3(d))[:, None]], 1).astype(f32)
+            pas = pas[through] + 1
+            live = live[through]
+            passed[live] = pas
+            keep = pas <= 4096
+            live, cur, pas = live[keep], nxt[keep], pas[keep]
+        covered = ra[:, 3] > 0
+        alb[covered] += ra[covered]
+        nd[covered] += rn[covered]
+        counts["samples"] += h * w
+        counts["through"] += int((passed > 0).sum())
+        counts["chain"] = max(counts["chain"], int(passed.max()))
+        counts["miss"] += int((~covered).sum())
+    return alb.reshape(h, w, 4), nd.reshape(h, w, 4), counts
+
+
+# ---------------------------------------------------------------------------- the scenes and their restatements, computed once
+_oracles, _refs = {}, {}
+
+
+def _source(name):
+    p = _proc()
+    return {"cornell": lambda: CORNELL, "jack": lambda: JACK, "plaza": lambda: p.plaza_scene(level=2), "atrium": lambda: p.atrium_scene(detail=2),
+            "cloud65": lambda: p.cloud_scene(1, 65, 16, layout="overlap"), "cloud64": lambda: p.cloud_scene(1, 64, 24, layout="overlap")}[name]()
+
+
+def _oracle(ora, name):
+    if name not in _oracles:
+        src = _source(name)
+        _oracles[name] = ora.OracleScene(ora.load_gltf(src)) if isinstance(src, str) else oracle_from_dict(ora, src)
+    return _oracles[name]
+
+
+def _ref(ora, name, **kw):
+    """The restatement at the common shape (or the shape given), cached: (albedo_cov, normal_depth, counts). Never modified."""
+    key = (name, tuple(sorted(kw.items())))
+    if key not in _refs:
+        a, n, c = restate(ora, _oracle(ora, name), **kw)
+        a.setflags(write=False), n.setflags(write=False)
+        _refs[key] = (a, n, c)
+    return _refs[key]
+
+
+def _scene(ptx, ctx, name):
+    src = _source(name)
+    return ptx.Scene.load_gltf(ctx, src) if isinstance(src, str) else product_from_dict(ptx, ctx, src)
+
+
+# ---------------------------------------------------------------------------- CPU: the restatement is not vacuous
+def test_restatement_cornell_covers_every_sample(ora):
+    alb, nd, c = _ref(ora, "cornell")
+    assert (alb[..., 3] == SPP).all() and c["miss"] == 0 and c["through"] == 0
+    assert np.isfinite(alb).all() and np.isfinite(nd).all() and (nd[..., 3] > 0).all()
+    nlen = np.linalg.norm(nd[..., :3].astype(np.float64) / SPP, axis=-1)
+    assert (nlen <= 1 + 1e-5).all() and (nlen > 0).all()
+
+
+def test_restatement_plaza_passes_through_misses_and_partly_covers(ora):
+    """Non-vacuity of the GPU comparisons: the plaza's half-transparent sphere passes samples through (some twice: in and out of the
+    sphere), over 30 % of the samples miss, and some pixels are covered by only part of their samples."""
+    alb, nd, c = _ref(ora, "plaza")
+    assert c["samples"] == 11725
+    assert c["through"] >= 100                  # 191 at samples 3 .. 7
+    assert c["chain"] >= 2                      # 2
+    assert c["miss"] >= 0.30 * c["samples"]     # 36 %
+    cov = alb[..., 3]
+    assert ((cov > 0) & (cov < SPP)).sum() >= 1   # 54 pixels
+    assert restate(ora, _oracle(ora, "plaza"), sample0=0)[2]["through"] >= 100   # 164 at samples 0 .. 4
+    # the ground is a shadow catcher: an ordinary surface here, recorded with its own albedo
+    ground, acc = np.asarray(_source("plaza")["materials"][0, :3], f32), np.zeros(3, f32)
+    for _ in range(SPP):
+        acc += ground
+    assert (_bits(alb[..., :3]) == _bits(acc)).all(-1).any()
+
+
+def test_restatement_jack_passes_through(ora, jack_oracle):
+    _oracles.setdefault("jack", jack_oracle)
+    alb, nd, c = _ref(ora, "jack")
+    assert c["through"] >= 200                  # 356
+    assert np.isfinite(alb).all() and np.isfinite(nd).all()
+
+
+def test_two_separate_sums_differ_from_one_by_a_rounding(ora):
+    """What ptx.h promises for sample ranges rendered into SEPARATE buffers: equal up to float summation order only."""
+    alb, nd, _ = _ref(ora, "plaza")
+    o = _oracle(ora, "plaza")
+    a1, n1, _ = restate(ora, o, sample0=S0, spp=2)
+    a2, n2, _ = restate(ora, o, sample0=S0 + 2, spp=3)
+    np.testing.assert_array_equal(a1[..., 3] + a2[..., 3], alb[..., 3])
+    for merged, one in ((a1 + a2, alb), (n1 + n2, nd)):
+        err = np.abs(merged.astype(np.float64) - one) / np.maximum(np.abs(one), 1)
+        assert err.max() <= SPP * 2.0 ** -23
+
+
+# ---------------------------------------------------------------------------- CPU: symbol and refusals
+def test_symbol_is_declared_and_exported(ptx):
+    assert "ptx_render_aov" in ptx.declared_symbols() and hasattr(ptx.lib(), "ptx_render_aov")
+
+
+def test_refusals_before_any_device_work(ptx):
+    """Host-only scene, so nothing here can reach a device: NULL arguments and two NULL buffers are PTX_ERR_INVALID, the worker integrator
+    PTX_ERR_UNSUPPORTED, a valid request PTX_ERR_NO_DEVICE; each sets a message."""
+    L = ptx.lib()
+    s = product_from_dict(ptx, None, _proc().plaza_scene(1, sun=False, alpha=False))
+    x0, y0, w, h = TILE
+    alb, nd = np.zeros((h, w, 4), f32), np.zeros((h, w, 4), f32)
+
+    def cfg(integrator=0):
+        return ptx.RenderCfg(W, H, SPP, 0, (C.c_float * 3)(1, 1, 1), SEED, 0, x0, y0, w, h, S0, PER_PASS, integrator, 0, 0, 0)
+
+    def call(scene, c, bufs):
+        rc = L.ptx_render_aov(scene, C.byref(c) if c is not None else None, C.byref(bufs) if bufs is not None else None, None)
+        return rc, L.ptx_last_error().decode()
+    both = ptx.AovBuffers(alb.ctypes.data, nd.ctypes.data)
+    for args in ((None, cfg(), both), (s.h, None, both), (s.h, cfg(), None), (s.h, cfg(), ptx.AovBuffers(None, None))):
+        rc, msg = call(*args)
+        assert rc == ptx.ERR_INVALID and "ptx_render_aov" in msg
+    rc, msg = call(s.h, cfg(ptx.INTEGRATOR_WORKER), both)
+    assert rc == ptx.ERR_UNSUPPORTED and "WORKER" in msg
+    for bufs in (both, ptx.AovBuffers(alb.ctypes.data, None), ptx.AovBuffers(None, nd.ctypes.data)):
+        rc, msg = call(s.h, cfg(), bufs)
+        assert rc == ptx.ERR_NO_DEVICE and "GPU context" in msg
+    assert not alb.any() and not nd.any()
+    with pytest.raises(ptx.PtxError) as e:
+        s.render_aov(W, H, SPP)
+    assert e.value.code == ptx.ERR_NO_DEVICE
+
+
+# ---------------------------------------------------------------------------- GPU
+@pytest.fixture(scope="module")
+def ctx(ptx):
+    return ptx.Context(0)
+
+
+_products = {}
+
+
+def _product(ptx, ctx, mp, name, force_global=False):
+    if (name, force_global) not in _products:
+        if force_global:
+            mp.setenv("PTX_FORCE_GLOBAL", "1")
+        _products[(name, force_global)] = _scene(ptx, ctx, name)
+        if force_global:
+            mp.delenv("PTX_FORCE_GLOBAL")
+    return _products[(name, force_global)]
+
+
+def _assert_route(ctx, s, resident, pipeline, what):
+    """Residency from info(); the pipeline from a tiny ptx_render under the same environment (ptx_render_aov routes its rays with the rule
+    ptx_intersect_batch and ptx_render share)."""
+    assert s.info()["lds_resident"] == resident, what
+    s.render(32, 18, 1, 2)
+    assert ctx.timing()["pipeline"] == pipeline, what
+
+
+def _aov(s, **kw):
+    args = dict(tile=TILE, sample0=S0, spp_per_pass=PER_PASS, seed=SEED)
+    args.update(kw)
+    return s.render_aov(W, H, args.pop("spp", SPP), **args)
+
+
+def _same(got, want, what):
+    np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=what)
+
+
+# (scene, created under PTX_FORCE_GLOBAL, switches at the call, expected lds_resident, expected pipeline)
+ROUTES = [
+    ("cornell", False, {}, 1, 0),                               # fused, everything in LDS
+    ("plaza", False, {}, 1, 0),
+    ("plaza", True, {}, 0, 1),                                  # global memory: the queue route by default
+    ("plaza", True, {"PTX_WAVEFRONT": "0"}, 0, 0),
+    ("jack", False, {}, 2, 1),                                  # textures, alpha textures, normal maps: its default queue route
+    ("jack", False, {"PTX_WAVEFRONT": "0"}, 2, 0),
+    ("atrium", True, {}, 0, 1),                                 # 24 surfaces, 4090 triangles
+    ("atrium", True, {"PTX_WAVEFRONT": "0"}, 0, 0),
+    ("cloud65", False, {}, 1, 0),                               # past the 64-surface limit of the queues: fused
+    ("cloud64", False, {"PTX_WF_PAIRS_M": "1"}, 2, 1),          # a 1 Mi-pair pool
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,force_global,env,resident,pipeline", ROUTES,
+                         ids=[f"{n}{'-global' if g else ''}{''.join('-' + k[4:].lower() + v for k, v in e.items())}" for n, g, e, _, _ in ROUTES])
+def test_bitwise_equal_to_the_restatement(ptx, ctx, ora, clean_env, name, force_global, env, resident, pipeline):
+    want_a, want_n, counts = _ref(ora, name)
+    s = _product(ptx, ctx, clean_env, name, force_global)
+    for k, v in env.items():
+        clean_env.setenv(k, v)
+    what = f"{name} global={force_global} {env}"
+    _assert_route(ctx, s, resident, pipeline, what)
+    alb, nd, st = _aov(s)
+    _same(alb, want_a, what + ": albedo_cov")
+    _same(nd, want_n, what + ": normal_depth")
+    assert st["samples"] == counts["samples"] and st["passes"] == 3 and st["kernel_ms"] > 0
+    assert st["rays"] >= counts["samples"] + counts["through"]   # one query per sample and per pass-through (chains add more)
+    if counts["through"] == 0:
+        assert st["rays"] == counts["samples"]
+
+
+@pytest.mark.gpu
+def test_slice_overflow_and_retry_inside_the_pass(ptx, ctx, ora, clean_env):
+    """A FRESH 1 x 64 "overlap" scene in a 1 Mi-pair pool, 192 x 108, two samples in one pass: 41 472 camera rays that each enter all 64
+    surface boxes (the oracle's count) ask for 2.6 Mi pairs, so the pass's first slice overflows the pool and is repeated in smaller
+    slices — inside the AOV pass. The buffers are the restatement's, bit for bit, and the fused route's."""
+    shape = dict(W_=192, H_=108, tile=(0, 0, 192, 108), sample0=0, spp=2)
+    o = _oracle(ora, "cloud64")
+    prim = o.primary_rays(ora.make_cfg(192, 108, 1, 1, seed=SEED), 0).reshape(-1, 6)
+    _, _, ost = o.intersect(prim, stats=True)
+    assert int(ost[1]) == 64 * len(prim) and 2 * 64 * len(prim) > 1 << 20 and 2 * len(prim) > 16384
+    want_a, want_n, counts = _ref(ora, "cloud64", **shape)
+    clean_env.setenv("PTX_WF_PAIRS_M", "1")
+    s = _scene(ptx, ctx, "cloud64")
+    assert s.info()["lds_resident"] == 2
+    alb, nd, st = s.render_aov(192, 108, 2, seed=SEED)
+    _assert_route(ctx, s, 2, 1, "queue route")
+    assert st["passes"] == 1 and st["rays"] == counts["samples"]
+    _same(alb, want_a, "albedo_cov")
+    _same(nd, want_n, "normal_depth")
+    clean_env.setenv("PTX_WAVEFRONT", "0")
+    alb0, nd0, _ = s.render_aov(192, 108, 2, seed=SEED)
+    _assert_route(ctx, s, 2, 0, "fused route")
+    _same(alb0, alb, "fused albedo_cov")
+    _same(nd0, nd, "fused normal_depth")
+
+
+@pytest.mark.gpu
+def test_textured_scene_without_pass_through(ptx, ctx, ora, clean_env):
+    """Cornell with an environment map: the texture lookups are compiled in (the map makes it a textured scene) and the pass-through is
+    not (no material can take it) — the one kernel variant the scenes above do not run. `env` is ignored: Cornell's restatement."""
+    import os
+    from conftest import GOLD
+    s = _scene(ptx, ctx, "cornell")
+    s.set_environment(os.path.join(GOLD, "hdr", "tiny.hdr"), False)
+    assert s.info()["n_textures"] == 1
+    _assert_route(ctx, s, 1, 0, "cornell + environment map")
+    alb, nd, st = _aov(s)
+    _same(alb, _ref(ora, "cornell")[0], "albedo_cov")
+    _same(nd, _ref(ora, "cornell")[1], "normal_depth")
+    assert st["rays"] == st["samples"]
+
+
+def _composition_routes(name):
+    return [({}, None)] if name == "plaza" else [({}, 1), ({"PTX_WAVEFRONT": "0"}, 0)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["plaza", "jack"])
+def test_composition(ptx, ctx, ora, clean_env, name):
+    import torch
+    s = _product(ptx, ctx, clean_env, name)
+    x0, y0, w, h = TILE
+    for env, pipeline in _composition_routes(name):
+        for k, v in env.items():
+            clean_env.setenv(k, v)
+        if pipeline is not None:
+            _assert_route(ctx, s, 2, pipeline, f"{name} {env}")
+        one_a, one_n, _ = _aov(s)
+        _same(one_a, _ref(ora, name)[0], "one call: albedo_cov")
+        _same(one_n, _ref(ora, name)[1], "one call: normal_depth")
+        # ascending adjacent sample ranges on the same buffers
+        a, n, _ = _aov(s, sample0=S0, spp=2)
+        _aov(s, sample0=S0 + 2, spp=3, albedo=a, normal_depth=n)
+        _same(a, one_a, "sample ranges: albedo_cov"), _same(n, one_n, "sample ranges: normal_depth")
+        # samples per pass
+        for per_pass in (1, 0):
+            a, n, st = _aov(s, spp_per_pass=per_pass)
+            assert st["passes"] == (SPP if per_pass else 1)
+            _same(a, one_a, f"spp_per_pass {per_pass}: albedo_cov"), _same(n, one_n, f"spp_per_pass {per_pass}: normal_depth")
+        # four rectangles
+        a, n = np.zeros_like(one_a), np.zeros_like(one_n)
+        for (rx, ry, rw, rh) in ((0, 0, 30, 17), (30, 0, w - 30, 17), (0, 17, 30, h - 17), (30, 17, w - 30, h - 17)):
+            ta, tn, _ = _aov(s, tile=(x0 + rx, y0 + ry, rw, rh))
+            a[ry:ry + rh, rx:rx + rw], n[ry:ry + rh, rx:rx + rw] = ta, tn
+        _same(a, one_a, "rectangles: albedo_cov"), _same(n, one_n, "rectangles: normal_depth")
+        # three shards into zeroed full-rectangle buffers
+        parts = [_aov(s, shard=(k, 3, 16)) for k in range(3)]
+        owners = sum((p[0][..., 3] > 0).astype(int) for p in parts)
+        assert owners.max() == 1 and all((p[0][..., 3] > 0).any() for p in parts)   # a pixel belongs to one shard; every shard has some
+        _same(parts[0][0] + parts[1][0] + parts[2][0], one_a, "shards: albedo_cov")
+        _same(parts[0][1] + parts[1][1] + parts[2][1], one_n, "shards: normal_depth")
+        # ... and a shard leaves the other shards' pixels as they were
+        rng = np.random.default_rng(5)
+        init_a, init_n = rng.uniform(0.5, 2.0, one_a.shape).astype(f32), rng.uniform(-2.0, -0.5, one_n.shape).astype(f32)
+        a, n, _ = _aov(s, shard=(1, 3, 16), albedo=init_a.copy(), normal_depth=init_n.copy())
+        other = parts[1][0][..., 3] == 0
+        _same(a[other], init_a[other], "shard: foreign pixels"), _same(n[other], init_n[other], "shard: foreign pixels")
+        # device buffers
+        da, dn = torch.zeros((h, w, 4), device="cuda:0"), torch.zeros((h, w, 4), device="cuda:0")
+        _aov(s, albedo=da, normal_depth=dn)
+        ctx.synchronize()
+        _same(da.cpu().numpy(), one_a, "device: albedo_cov"), _same(dn.cpu().numpy(), one_n, "device: normal_depth")
+        # each buffer alone
+        a, none, _ = _aov(s, albedo=np.zeros_like(one_a))
+        assert none is None
+        _same(a, one_a, "albedo_cov alone")
+        none, n, _ = _aov(s, normal_depth=np.zeros_like(one_n))
+        assert none is None
+        _same(n, one_n, "normal_depth alone")
+        # added to, not overwritten: a pixel's samples are added one by one, in sample order, to what the buffer held
+        a, n, _ = _aov(s, albedo=init_a.copy(), normal_depth=init_n.copy())
+        want_a, want_n = init_a.copy(), init_n.copy()
+        for k in range(SPP):
+            sa, sn, _ = _aov(s, sample0=S0 + k, spp=1)
+            covered = sa[..., 3] > 0
+            want_a[covered] += sa[covered]
+            want_n[covered] += sn[covered]
+        _same(a, want_a, "non-zero start: albedo_cov"), _same(n, want_n, "non-zero start: normal_depth")
+        assert (a != one_a).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["plaza", "jack"])
+def test_no_disturbance(ptx, ctx, ora, clean_env, name):
+    """A beauty frame and a batch of closest hits before and after an AOV call on the same context are bitwise identical."""
+    s = _product(ptx, ctx, clean_env, name)
+    rays = _oracle(ora, name).primary_rays(ora.make_cfg(W, H, 1, 1, seed=SEED, tile=TILE), S0).reshape(-1, 6)
+
+    def frame():
+        return s.render(W, H, SPP, B, tile=TILE, sample0=S0, spp_per_pass=PER_PASS, seed=SEED)
+    f0, st0 = frame()
+    h0 = s.intersect(rays[:, :3], rays[:, 3:])
+    _aov(s)
+    f1, st1 = frame()
+    h1 = s.intersect(rays[:, :3], rays[:, 3:])
+    _same(f1, f0, "ptx_render")
+    assert st1["rays"] == st0["rays"]
+    for k in h0:
+        np.testing.assert_array_equal(h1[k].view(np.uint32), h0[k].view(np.uint32), err_msg=k)
+
+
+@pytest.mark.gpu
+def test_consistent_with_the_beauty_frame(ptx, ctx, clean_env):
+    s = _product(ptx, ctx, clean_env, "cornell")
+    alb, _, _ = _aov(s)
+    frame, _ = s.render(W, H, SPP, B, tile=TILE, sample0=S0, spp_per_pass=PER_PASS, seed=SEED)
+    full = alb[..., 3] == SPP
+    assert full.any() and (frame[..., 3][full] == SPP).all()
+    # transparent background (a frame starts at sample 0): a pixel none of whose samples ends on a surface is never claimed
+    p = _product(ptx, ctx, clean_env, "plaza")
+    alb, _, _ = _aov(p, sample0=0)
+    _, claimed, _ = p.render_transparent(W, H, SPP, B, tile=TILE, spp_per_pass=PER_PASS, seed=SEED)
+    empty = alb[..., 3] == 0
+    assert empty.any() and (~empty).any() and not claimed[empty].any()
+
+
+@pytest.mark.gpu
+def test_renderer_mirror_returns_means(ptx):
+    r = ptx.Renderer(0)
+    r.resolution, r.sample_count, r.seed = (48, 27), 3, SEED
+    r.load_gltf(CORNELL)
+    albedo, normal, depth, coverage = r.render_aov()
+    assert albedo.shape == (27, 48, 3) and normal.shape == (27, 48, 3) and depth.shape == (27, 48) and coverage.shape == (27, 48)
+    assert (coverage == 1).all() and (depth > 0).all() and (albedo >= 0).all() and (albedo <= 1).all()
+    assert np.abs(np.linalg.norm(normal, axis=-1)).max() <= 1 + 1e-5
+
+
+@pytest.mark.gpu
+def test_cli_writes_the_guide_images(ora, tmp_path):
+    """ptx_render_cli --aov PREFIX: PREFIX_albedo.png = the mean albedo of the covered samples, PREFIX_normal.png = mean normal * 0.5 + 0.5,
+    alpha = coverage, through a plain linear quantiser (uint8)(v * 255 + 0.5) — the restatement's sums through the same arithmetic."""
+    import os
+    import subprocess
+    from PIL import Image
+    from conftest import ROOT
+    cw, ch, spp = 48, 27, 3
+    cli = os.path.join(ROOT, "distributed-path-tracer_amd", "ptx_render_cli")
+    r = subprocess.run([cli, "--aov", str(tmp_path / "g"), CORNELL, str(tmp_path / "f.png"), str(cw), str(ch), str(spp), "2"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert "aov_kernel_ms" in r.stdout and Image.open(tmp_path / "f.png").size == (cw, ch)
+    alb, nd, _ = restate(ora, _oracle(ora, "cornell"), W_=cw, H_=ch, tile=(0, 0, cw, ch), sample0=0, spp=spp)
+    cov = alb[..., 3]
+    assert (cov == spp).all()
+    inv = (f32(1) / cov)[..., None]
+
+    def q(v):
+        return (np.clip(v, f32(0), f32(1)) * f32(255) + f32(0.5)).astype(np.uint8)
+    want_a = np.concatenate([q(alb[..., :3] * inv), q(cov / f32(spp))[..., None]], -1)
+    want_n = np.concatenate([q(nd[..., :3] * inv * f32(0.5) + f32(0.5)), q(cov / f32(spp))[..., None]], -1)
+    np.testing.assert_array_equal(np.array(Image.open(tmp_path / "g_albedo.png")), want_a)
+    np.testing.assert_array_equal(np.array(Image.open(tmp_path / "g_normal.png")), want_n)
