@@ -80,6 +80,15 @@ class AovBuffers(C.Structure):
     _fields_ = [("albedo_cov", C.c_void_p), ("normal_depth", C.c_void_p)]
 
 
+class DenoiseCfg(C.Structure):
+    _fields_ = [("W", C.c_uint32), ("H", C.c_uint32), ("spp_a", C.c_uint32), ("spp_b", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float)]
+
+
+class DenoiseStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("iterations", C.c_uint32), ("workspace_bytes", C.c_uint64)]
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("pipeline", C.c_uint32), ("steps", C.c_uint32), ("classify_ms", C.c_double), ("traverse_ms", C.c_double), ("shade_ms", C.c_double),
                 ("fused_ms", C.c_double), ("fused_launches", C.c_uint32), ("pool_overflows", C.c_uint32), ("pool_pairs", C.c_uint64),
@@ -163,6 +172,7 @@ def lib():
         L.ptx_render.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.POINTER(RenderStats)]
         L.ptx_render_transparent.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.c_void_p, C.POINTER(RenderStats)]
         L.ptx_render_aov.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AovBuffers), C.POINTER(RenderStats)]
+        L.ptx_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p, C.POINTER(DenoiseStats)]
         L.ptx_intersect_batch.argtypes = [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(Hits)]
         L.ptx_tonemap_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ptx_pbr_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -265,6 +275,23 @@ class Context:
         ret = out if out is not None else np.zeros((H, W, 4), np.uint8)
         _check(lib().ptx_tonemap_encode(self.h, _ptr(accum), W, H, spp, _ptr(ret)))
         return ret
+
+    def denoise(self, a, b, albedo_cov, normal_depth, spp_a, spp_b, iterations=0, sigma_l=0, sigma_n=0, sigma_z=0, out=None, want_stats=True):
+        """ptx_denoise: variance-guided a-trous filter. a, b: [H,W,4] float32 radiance SUMS of two disjoint sample ranges of one frame
+        (Scene.render of spp_a and spp_b samples); albedo_cov, normal_depth: the Scene.render_aov SUMS over all spp_a + spp_b samples;
+        all numpy or all torch-on-GPU. iterations 0 = 5 (at most 8), sigmas 0 = the defaults 4, 0.5, 0.1. out: [H,W,4] buffer of the same
+        kind for the filtered MEANS (may be a or b itself; None = a new one). Returns (out, stats dict or None)."""
+        bufs = [a, b, albedo_cov, normal_depth] + ([out] if out is not None else [])
+        shape = tuple(a.shape)
+        if len(shape) != 3 or shape[2] != 4 or any(tuple(x.shape) != shape for x in bufs):
+            raise ValueError(f"denoise: every buffer must be [H, W, 4] of one size, got {[tuple(x.shape) for x in bufs]}")
+        if out is None:
+            out = np.empty(shape, np.float32) if isinstance(a, np.ndarray) else a.new_empty(shape)   # no fill kernel on another stream
+        cfg = DenoiseCfg(shape[1], shape[0], spp_a, spp_b, iterations, sigma_l, sigma_n, sigma_z)
+        guides = AovBuffers(_ptr(albedo_cov), _ptr(normal_depth))
+        st = DenoiseStats()
+        _check(lib().ptx_denoise(self.h, C.byref(cfg), _ptr(a), _ptr(b), C.byref(guides), _ptr(out), C.byref(st) if want_stats else None))
+        return out, (dict(kernel_ms=st.kernel_ms, iterations=st.iterations, workspace_bytes=st.workspace_bytes) if want_stats else None)
 
     def close(self):
         if getattr(self, "h", None):
@@ -500,6 +527,7 @@ class Renderer:
         self._scene = None
         self.last_stats = None
         self.last_claimed = None
+        self.last_denoise_stats = None
 
     def load_gltf(self, path):
         self._scene = Scene.load_gltf(self._ctx, path, self.camera_index, self.sun_light_index)
@@ -536,6 +564,27 @@ class Renderer:
         cov = alb[..., 3]
         inv = np.where(cov > 0, 1.0 / np.maximum(cov, 1.0), 0.0).astype(np.float32)
         return alb[..., :3] * inv[..., None], nd[..., :3] * inv[..., None], nd[..., 3] * inv, cov / np.float32(self.sample_count)
+
+    def render_denoised(self, iterations=0, sigma_l=0, sigma_n=0, sigma_z=0):
+        """The frame through the variance-guided a-trous filter (Context.denoise): renders samples [0, n/2) and [n/2, n) of
+        sample_count = n into two buffers, the guide buffers of all n, and returns the filtered MEANS [H,W,4] (write them with
+        tonemap_encode(..., spp=1)). `last_denoise_stats` holds the filter's stats."""
+        if self._scene is None:
+            raise PtxError(ERR_INVALID, "render_denoised() before load_gltf()")
+        if self.transparent_background:
+            raise PtxError(ERR_UNSUPPORTED, "render_denoised: the filter takes radiance sums, which transparent_background does not produce")
+        n = self.sample_count
+        if n < 2:
+            raise PtxError(ERR_INVALID, "render_denoised: sample_count must be at least 2 (the noise estimate needs two half-frames)")
+        W, H = self.resolution
+        if self.environment != getattr(self, "_env_set", None):
+            self._scene.set_environment(self.environment)
+            self._env_set = self.environment
+        a, _ = self._scene.render(W, H, n // 2, self.bounce_count, env=self.environment_factor, seed=self.seed, want_stats=False)
+        b, _ = self._scene.render(W, H, n - n // 2, self.bounce_count, env=self.environment_factor, seed=self.seed, sample0=n // 2, want_stats=False)
+        alb, nd, _ = self._scene.render_aov(W, H, n, seed=self.seed, want_stats=False)
+        out, self.last_denoise_stats = self._ctx.denoise(a, b, alb, nd, n // 2, n - n // 2, iterations, sigma_l, sigma_n, sigma_z, out=a)
+        return out
 
     def render(self):
         W, H = self.resolution

@@ -201,4 +201,15 @@ hipError_t launch_aov_shade(const DevScene& S, const RenderParams& P, const AovS
 hipError_t launch_aov_resolve(const float4* rec, size_t rec_stride, float4* albedo_cov, float4* normal_depth, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp,
                               hipStream_t stream);
 
+// Variance-guided a-trous filter (denoise.hip, ptx_denoise). All buffers [n_pixels] float4 on the device.
+// prepare: the two radiance sums and the guide sums -> col_var (demodulated colour, v0), guide (mean normal, mean depth), remod (albedo, alpha)
+hipError_t launch_denoise_prepare(const float4* a, const float4* b, const float4* albedo_cov, const float4* normal_depth, uint32_t spp_a, uint32_t spp_b, size_t n_pixels,
+                                  float4* col_var, float4* guide, float4* remod, hipStream_t stream);
+// 3 x 3 variance prefilter: in (col, v0) -> out (col, var)
+hipError_t launch_denoise_prefilter(const float4* in, const float4* guide, uint32_t W, uint32_t H, float sigma_n, float sigma_z, float4* out, hipStream_t stream);
+// one iteration at `step`: in (col, var) -> out (col, var), or, with `last`, out = (col * albedo, alpha) of remod. tiled: the LDS-staged form
+// (same arithmetic in the same order). `out` must not be `in`.
+hipError_t launch_denoise_atrous(const float4* in, const float4* guide, const float4* remod, uint32_t W, uint32_t H, uint32_t step, float sigma_l, float sigma_n, float sigma_z,
+                                 bool last, bool tiled, float4* out, hipStream_t stream);
+
 }  // namespace ptx

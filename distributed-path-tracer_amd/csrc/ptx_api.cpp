@@ -83,6 +83,7 @@ struct ptx_ctx {
 	std::mutex mu;
 	DevBuf queues, sample_rad, counters, spill, stage_a, stage_b, pixel_list, srgb_thr;
 	DevBuf aov;   // workspace of ptx_render_aov: the streams, hits and per-sample records of one pass
+	DevBuf denoise;   // workspace of ptx_denoise: four float4 state buffers per pixel, and the staging of host buffers
 	// workspace of the queue-based pipeline (wavefront.hip): ptx_render and ptx_intersect_batch run it on the context's stream
 	struct WfSet {
 		DevBuf qent, pair_hit, seg, first, mask, ctl, spill, stream_buf, flow;
@@ -369,7 +370,7 @@ static void ctx_release(ptx_ctx* c) {
 	(void)hipStreamSynchronize(c->stream);
 	for (hipEvent_t ev : c->events) (void)hipEventDestroy(ev);
 	for (hipEvent_t ev : c->step_events) (void)hipEventDestroy(ev);
-	c->queues.release(); c->spill.release(); c->sample_rad.release(); c->counters.release(); c->stage_a.release(); c->stage_b.release(); c->pixel_list.release(); c->srgb_thr.release(); c->aov.release();
+	c->queues.release(); c->spill.release(); c->sample_rad.release(); c->counters.release(); c->stage_a.release(); c->stage_b.release(); c->pixel_list.release(); c->srgb_thr.release(); c->aov.release(); c->denoise.release();
 	ptx_ctx::WfSet& w = c->wf;
 	for (DevBuf* b : {&w.qent, &w.pair_hit, &w.seg, &w.first, &w.mask, &w.ctl, &w.spill, &w.stream_buf, &w.flow}) b->release();
 	if (w.flow_host) { (void)hipHostFree(w.flow_host); w.flow_host = nullptr; }
@@ -1346,6 +1347,77 @@ int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffe
 			HIP_TRY(hipEventElapsedTime(&t, c->events[2 * p], c->events[2 * p + 1]));
 			stats->kernel_ms += t;
 		}
+	}
+	return PTX_OK;
+}
+
+namespace {
+
+// Which iterations (bit i = step 2^i) run the LDS-tiled a-trous kernel rather than the global gather: the faster of the two per step at
+// 1920 x 1080 on the MI355X (profiles/EXPERIMENTS.md). PTX_DENOISE_TILED=<mask>: measurement switch. Both forms give the same bits.
+constexpr uint32_t kDenoiseTiledSteps = 0x00;
+uint32_t denoise_tiled_steps() {
+	const char* e = getenv("PTX_DENOISE_TILED");
+	return e && *e ? (uint32_t)strtoul(e, nullptr, 0) : kDenoiseTiledSteps;
+}
+
+}  // namespace
+
+int ptx_denoise(ptx_ctx* c, const ptx_denoise_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, float* out_rgba, ptx_denoise_stats* stats) {
+	// every refusal below is decided before any device work
+	if (!c || !cfg || !accum_a || !accum_b || !guides || !out_rgba) return set_err(PTX_ERR_INVALID, "ptx_denoise: NULL argument");
+	if (!guides->albedo_cov || !guides->normal_depth) return set_err(PTX_ERR_INVALID, "ptx_denoise: both guide buffers are required");
+	if (!cfg->W || !cfg->H || cfg->W > 16384 || cfg->H > 16384) return set_err(PTX_ERR_INVALID, "ptx_denoise: W and H must be in 1 .. 16384");
+	if (!cfg->spp_a || !cfg->spp_b) return set_err(PTX_ERR_INVALID, "ptx_denoise: spp_a and spp_b must be > 0 (the noise estimate needs two half-frames)");
+	if (cfg->iterations > 8) return set_err(PTX_ERR_INVALID, "ptx_denoise: at most 8 iterations");
+	if (!(cfg->sigma_l >= 0.0f) || !(cfg->sigma_n >= 0.0f) || !(cfg->sigma_z >= 0.0f)) return set_err(PTX_ERR_INVALID, "ptx_denoise: a sigma is negative or NaN");
+	const bool dev = is_device_ptr(accum_a);
+	if (is_device_ptr(accum_b) != dev || is_device_ptr(guides->albedo_cov) != dev || is_device_ptr(guides->normal_depth) != dev || is_device_ptr(out_rgba) != dev)
+		return set_err(PTX_ERR_INVALID, "ptx_denoise: the five buffers must all be device or all be host memory");
+	const uint32_t W = cfg->W, H = cfg->H, iterations = cfg->iterations ? cfg->iterations : 5u;
+	const float sigma_l = cfg->sigma_l != 0.0f ? cfg->sigma_l : 4.0f, sigma_n = cfg->sigma_n != 0.0f ? cfg->sigma_n : 0.5f, sigma_z = cfg->sigma_z != 0.0f ? cfg->sigma_z : 0.1f;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	if (stats) *stats = ptx_denoise_stats{};
+
+	// workspace: [state 0][state 1][guide][remod], then the staging of the four host inputs; the staged output takes accum_a's place
+	const size_t n = (size_t)W * H, bytes = n * sizeof(float4);
+	const size_t ws_bytes = bytes * (dev ? 4 : 8);
+	HIP_TRY(c->denoise.ensure(ws_bytes));
+	float4* const ws = (float4*)c->denoise.p;
+	float4 *const state[2] = {ws, ws + n}, *const guide = ws + 2 * n, *const remod = ws + 3 * n;
+	const float4 *d_a = (const float4*)accum_a, *d_b = (const float4*)accum_b, *d_alb = (const float4*)guides->albedo_cov, *d_nd = (const float4*)guides->normal_depth;
+	float4* d_out = (float4*)out_rgba;
+	if (!dev) {
+		const void* src[4] = {accum_a, accum_b, guides->albedo_cov, guides->normal_depth};
+		for (int k = 0; k < 4; k++) HIP_TRY(hipMemcpyAsync(ws + (4 + k) * n, src[k], bytes, hipMemcpyHostToDevice, c->stream));
+		d_a = ws + 4 * n; d_b = ws + 5 * n; d_alb = ws + 6 * n; d_nd = ws + 7 * n;
+		d_out = ws + 4 * n;   // prepare has consumed the inputs before the last iteration writes
+	}
+	if (stats)
+		while (c->events.size() < 2) {
+			hipEvent_t ev;
+			HIP_TRY(hipEventCreate(&ev));
+			c->events.push_back(ev);
+		}
+	const uint32_t tiled = denoise_tiled_steps();
+	if (stats) HIP_TRY(hipEventRecord(c->events[0], c->stream));
+	HIP_TRY(launch_denoise_prepare(d_a, d_b, d_alb, d_nd, cfg->spp_a, cfg->spp_b, n, state[0], guide, remod, c->stream));
+	HIP_TRY(launch_denoise_prefilter(state[0], guide, W, H, sigma_n, sigma_z, state[1], c->stream));
+	for (uint32_t i = 0; i < iterations; i++) {
+		const bool last = i + 1 == iterations;
+		const float4* in = state[(i + 1) & 1u];
+		HIP_TRY(launch_denoise_atrous(in, guide, remod, W, H, 1u << i, sigma_l, sigma_n, sigma_z, last, (tiled >> i) & 1u, last ? d_out : state[i & 1u], c->stream));
+	}
+	if (stats) HIP_TRY(hipEventRecord(c->events[1], c->stream));
+	if (!dev) HIP_TRY(hipMemcpyAsync(out_rgba, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+	if (stats || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
+	if (stats) {
+		float t = 0;
+		HIP_TRY(hipEventElapsedTime(&t, c->events[0], c->events[1]));
+		stats->kernel_ms = t;
+		stats->iterations = iterations;
+		stats->workspace_bytes = ws_bytes;
 	}
 	return PTX_OK;
 }

@@ -83,11 +83,43 @@ public:
 		return a;
 	}
 
+	// The frame through the variance-guided a-trous filter (ptx_denoise): samples [0, n/2) and [n/2, n) of sample_count = n rendered into two
+	// buffers, the guide buffers of all n; returns the filtered MEANS [H][W][4] (write them with ptx_tonemap_encode(..., spp = 1)). stats optional
+	std::vector<float> render_denoised(ptx_denoise_stats* stats = nullptr, const ptx_denoise_cfg* filter = nullptr) const {
+		if (!scene_) throw std::runtime_error("render_denoised() before load_gltf()");
+		if (transparent_background) throw std::runtime_error("render_denoised: the filter takes radiance sums, which transparent_background does not produce");
+		if (sample_count < 2) throw std::runtime_error("render_denoised: sample_count must be at least 2 (the noise estimate needs two half-frames)");
+		if (environment.string() != env_set_) {
+			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
+			env_set_ = environment.string();
+		}
+		ptx_render_cfg c{};
+		c.W = resolution.x; c.H = resolution.y; c.bounces = bounce_count;
+		for (int k = 0; k < 3; k++) c.env[k] = environment_factor[k];
+		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
+		const size_t floats = (size_t)c.W * c.H * 4;
+		std::vector<float> a(floats, 0.f), b(floats, 0.f), alb(floats, 0.f), nd(floats, 0.f);
+		c.spp = sample_count / 2;
+		check(ptx_render(scene_, &c, a.data(), nullptr));
+		c.sample0 = c.spp; c.spp = sample_count - c.sample0;
+		check(ptx_render(scene_, &c, b.data(), nullptr));
+		c.sample0 = 0; c.spp = sample_count;
+		const ptx_aov_buffers g{alb.data(), nd.data()};
+		check(ptx_render_aov(scene_, &c, &g, nullptr));
+		ptx_denoise_cfg d = filter ? *filter : ptx_denoise_cfg{};   // iterations and sigmas; the rest is set here
+		d.W = c.W; d.H = c.H; d.spp_a = sample_count / 2; d.spp_b = sample_count - d.spp_a;
+		check(ptx_denoise(ctx_, &d, a.data(), b.data(), &g, a.data(), stats));
+		return a;
+	}
+
 	std::vector<uint8_t> render() const {   // renderer.cpp:334-428: PNG bytes (RGBA8, ACES tonemap, sRGB)
-		std::vector<float> accum = render_accum();
+		return encode(render_accum(), transparent_background ? 1u : sample_count);
+	}
+	// the same image write for a buffer of sums over `spp` samples; the transparent mode's and the filter's means are written as they are
+	// (spp = 1: x / 1.0f is exact)
+	std::vector<uint8_t> encode(const std::vector<float>& accum, uint32_t spp) const {
 		std::vector<uint8_t> rgba((size_t)resolution.x * resolution.y * 4);
-		// the transparent mode's means are written as they are (spp = 1: x / 1.0f is exact)
-		check(ptx_tonemap_encode(ctx_, accum.data(), resolution.x, resolution.y, transparent_background ? 1u : sample_count, rgba.data()));
+		check(ptx_tonemap_encode(ctx_, accum.data(), resolution.x, resolution.y, spp, rgba.data()));
 		uint8_t* png = nullptr;
 		size_t n = 0;
 		check(ptx_encode_png(rgba.data(), resolution.x, resolution.y, &png, &n));

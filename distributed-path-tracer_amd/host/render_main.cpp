@@ -1,7 +1,8 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
+//       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
 //       --aov PREFIX:  also writes the denoiser's guide images PREFIX_albedo.png (mean albedo of the covered samples, alpha = coverage)
 //                      and PREFIX_normal.png (mean shading normal * 0.5 + 0.5), quantised linearly to 8 bits
 //   ptx_render_cli --event <event.json> <local scene root dir> <out.png>     (the worker's Lambda event, main.cpp:9-25)
@@ -30,15 +31,16 @@ static void write_png(const std::string& path, const std::vector<uint8_t>& rgba,
 }
 
 int main(int argc, char** argv) {
-	bool transparent = false;
+	bool transparent = false, denoise = false;
 	std::string aov_prefix;
 	for (;;) {   // leading switches
 		if (argc > 1 && std::string(argv[1]) == "--transparent") { transparent = true; argv[1] = argv[0]; argv++; argc--; }
+		else if (argc > 1 && std::string(argv[1]) == "--denoise") { denoise = true; argv[1] = argv[0]; argv++; argc--; }
 		else if (argc > 2 && std::string(argv[1]) == "--aov") { aov_prefix = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (argc == 5 && std::string(argv[1]) == "--event") {
@@ -77,7 +79,8 @@ int main(int argc, char** argv) {
 		}
 		r.load_gltf(argv[1]);
 		auto t0 = std::chrono::steady_clock::now();
-		std::vector<uint8_t> png = r.render();
+		ptx_denoise_stats dst{};
+		std::vector<uint8_t> png = denoise ? r.encode(r.render_denoised(&dst), 1) : r.render();
 		double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 		std::ofstream(argv[2], std::ios::binary).write((const char*)png.data(), (std::streamsize)png.size());
 		double aov_ms = 0;
@@ -101,6 +104,7 @@ int main(int argc, char** argv) {
 		std::printf("{\"W\": %u, \"H\": %u, \"spp\": %u, \"bounces\": %u, \"seconds\": %.4f, \"png_bytes\": %zu", r.resolution.x, r.resolution.y,
 		            r.sample_count, (unsigned)r.bounce_count, s, png.size());
 		if (!aov_prefix.empty()) std::printf(", \"aov_kernel_ms\": %.3f", aov_ms);
+		if (denoise) std::printf(", \"denoise_kernel_ms\": %.3f", dst.kernel_ms);
 		std::printf("}\n");
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "error: %s\n", e.what());

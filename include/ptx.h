@@ -240,6 +240,49 @@ typedef struct ptx_aov_buffers {
 } ptx_aov_buffers;
 int ptx_render_aov(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_aov_buffers* out, ptx_render_stats* stats);
 
+/* Variance-guided edge-avoiding a-trous filter on the guide buffers (no counterpart in the reference, which has no denoiser): turns a noisy
+ * low-spp frame into a usable one. It takes its noise estimate from two half-frames, which ptx_render gives for free — sample ranges compose.
+ *   accum_a, accum_b [H][W][4]: ptx_render radiance SUMS of two disjoint sample ranges of the same frame (e.g. [0, n/2) and [n/2, n)), of
+ *                               spp_a and spp_b samples;
+ *   guides:                     the ptx_render_aov SUMS over all spp_a + spp_b samples; both buffers are required;
+ *   out_rgba [H][W][4]:         receives MEANS (ptx_tonemap_encode(..., spp = 1, ...) writes them unchanged); may be accum_a or accum_b itself.
+ * The five buffers are all device or all host memory; the filter works on whole W x H buffers, not on tiles. Multi-GPU: reduce the buffers
+ * first (ptx_reduce_framebuffer applies as it is), then filter on the root.
+ * The filter, which is its own specification (IEEE binary32, every operation rounded on its own in the parenthesisation written here;
+ * max(a, b) returns the other operand when one is NaN):
+ *   bw(x) = t * t, t = max(0, 1 - x);  lum(c) = (0.2126f*c.r + 0.7152f*c.g) + 0.0722f*c.b;  n = float(spp_a + spp_b), na, nb likewise.
+ *   1. per pixel: cov = albedo_cov.w; alb_c = max((albedo_cov.c + (n - cov)) / n, 0.001f) (missed samples count as albedo 1);
+ *      col_c = ((a.c + b.c) / n) / alb_c; ma_c = (a.c / na) / alb_c, mb_c likewise; d = (lum(ma) - lum(mb)) * 0.5f; v0 = d * d;
+ *      alpha = (a.w + b.w) / n; nrm = normal_depth.xyz / cov and z = normal_depth.w / cov when cov > 0, else all 0.
+ *   2. geometric weight of tap q seen from p: geo = bw(xn) * bw(xz); dn = nrm_p - nrm_q; xn = ((dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z) /
+ *      (sigma_n*sigma_n); zm = max(z_p, z_q); rel = zm > 0 ? (z_p - z_q) / zm : 0; xz = (rel*rel) / (sigma_z*sigma_z). A missed pixel and
+ *      a surface pixel never mix; two missed pixels mix freely.
+ *   3. variance prefilter, 3 x 3, taps in row-major order (dy outer), taps outside the image skipped: g = 1 for the centre, geo otherwise;
+ *      s0 += g; s1 += g * v0_q; var = s1 / s0.
+ *   4. iteration i = 0 .. iterations-1, step = 2^i: the 25 taps q = p + step * (dx, dy), dy outer and dx inner from -2 to 2, taps outside
+ *      the image skipped; k = {3/8, 1/4, 1/16}; h = k[|dx|] * k[|dy|]; L = lum(col); den = ((sigma_l*sigma_l) * var_p) + 1e-8f; the centre
+ *      tap has w = h, any other dl = L_p - L_q and w = (h * geo) * bw((dl*dl) / den); a tap with !(w > 0) is skipped (NaN weights too: a
+ *      non-finite pixel stays itself and contaminates no neighbour); acc.c += w * col_q.c; ws += w; av += (w*w) * var_q; after the taps
+ *      col = acc / ws and var = av / (ws*ws).
+ *   5. out.c = col.c * alb_c; out.w = alpha.
+ * What to expect: the filter helps a great deal where there is noise (Cornell at 16 spp: about 4x lower mean squared error), does no harm
+ * on a sun-lit open scene, and costs some texture detail on a nearly noise-free textured frame (DESIGN.md has the table).
+ * PTX_ERR_INVALID — each decided before any device work — for a NULL ctx, cfg, buffer or guide pointer; W or H of 0 or above 16384; spp_a
+ * or spp_b of 0; iterations above 8; a sigma that is negative or NaN; pointers of mixed kinds. */
+typedef struct ptx_denoise_cfg {
+	uint32_t W, H;             /* buffer size */
+	uint32_t spp_a, spp_b;     /* samples summed in accum_a / accum_b; the guides hold spp_a + spp_b samples */
+	uint32_t iterations;       /* 0 = 5; at most 8 (step 1, 2, 4 ... 128) */
+	float sigma_l, sigma_n, sigma_z;   /* 0 = default 4, 0.5, 0.1 */
+} ptx_denoise_cfg;
+typedef struct ptx_denoise_stats {
+	double kernel_ms;          /* HIP-event time of the filter's kernels on the context stream */
+	uint32_t iterations;       /* iterations run */
+	uint64_t workspace_bytes;  /* device memory the call used on the context (state buffers, and the staging of host buffers) */
+} ptx_denoise_stats;
+int ptx_denoise(ptx_ctx* ctx, const ptx_denoise_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, float* out_rgba,
+                ptx_denoise_stats* stats /* NULL ok */);
+
 /* Measurement aid (no counterpart in the reference): where the time of the last ptx_render that was given a stats pointer went.
  * Scenes whose geometry fits the LDS or whose models have few surfaces run ONE fused kernel per pass (pipeline 0: fused_ms);
  * many-surface scenes in global memory run the queue-based pipeline (pipeline 1) — per step of a slab of paths a classify, a
