@@ -577,6 +577,24 @@ DEV float fresnel_schlick(V3 outcoming, V3 incoming, float ior) {  // core/pbr.c
 // pbr::importance_diffuse (core/pbr.cpp:71-77) and pbr::importance_specular (:79-91) differ in the cone angle they hand to
 // rand_cone_vec and in the final reflection; the cone construction itself (sin / cos of the azimuth, tangent frame) is the
 // same code — run it once for the whole wave instead of once per lobe under complementary lane masks.
+// The cosine of the diffuse lobe's polar angle t = acos(..) / 2. rand_cone_vec takes sqrt(1 - cos^2) of it, which near the pole turns one
+// ulp of the cosine into t / ulp times as much of the sine: at u1 = 1 - 2^-24, t = 2^-12 and cos t = 1 - 2^-25 + 1.5e-16 lies next to a
+// rounding midpoint; the reference's cosf (glibc: a double evaluation rounded once) returns 1, the sample is the normal, and a cosf that
+// is an ulp off puts it 3.5e-4 rad away. So below t = 1/16 — 0.4 % of the draws, where an ulp of the cosine is more than 16 ulp of the
+// sine — the cosine is evaluated in double (Taylor series to t^8: the next term is below 3e-19) and rounded once, which is the correctly
+// rounded value for every float of that range; above it ocml's cosf stays.
+DEV float cos_polar(float t) {
+	if (t < 0.0625F) {
+		const double x = (double)t * (double)t;
+		double p = 1.0 / 40320.0;
+		p = __builtin_fma(p, x, -1.0 / 720.0);
+		p = __builtin_fma(p, x, 1.0 / 24.0);
+		p = __builtin_fma(p, x, -0.5);
+		p = __builtin_fma(p, x, 1.0);
+		return (float)p;
+	}
+	return cosf(t);
+}
 DEV V3 importance_sample(bool specular, float u1, float u2, V3 normal, V3 outcoming, float roughness) {
 	float cos_theta;
 	if (specular) {
@@ -584,7 +602,7 @@ DEV V3 importance_sample(bool specular, float u1, float u2, V3 normal, V3 outcom
 		roughness *= roughness;
 		cos_theta = sqrt_exact((1 - u1) / (1 + (roughness - 1) * u1));
 	} else {
-		cos_theta = cosf(acosf(2 * u1 - 1) * 0.5F);
+		cos_theta = cos_polar(acosf(2 * u1 - 1) * 0.5F);
 	}
 	const V3 h = rand_cone_vec(u2, cos_theta, normal);
 	return specular ? reflect3(-outcoming, h) : h;

@@ -312,3 +312,77 @@ def cloud_scene(n_models: int = 1, surfaces_per_model: int = 64, tris_per_surfac
     return dict(model_xform=model_xform, model_surf=model_surf, surf_range=np.array(sr, np.int32),
                 vertices=np.concatenate(verts).astype(np.float32), triangles=np.concatenate(tris).astype(np.uint32),
                 materials=mats, camera=cam, sun=sun13)
+
+
+# ---------------------------------------------------------------------------- the material chart
+_NEAR1 = float(np.nextafter(np.float32(1), np.float32(0)))
+_BASE = (0.9, 0.6, 0.3)
+# One patch per regime of the shading vertex: (name, albedo, opacity, roughness, metallic, emissive, ior, shadow catcher, flipped).
+# The three opacities next to 1 all fall on the `is_approx(opacity, 1)` side of renderer.cpp:466 (|opacity - 1| < 0.0001): opaque.
+CHART_REGIMES = (
+    [(f"rough{r:g}_metal{m:g}", _BASE, 1.0, r, m, (0, 0, 0), 1.33, 0, False) for r in (0.0, 0.01, 0.05, 0.3, 1.0) for m in (0.0, 0.5, 1.0)]
+    + [(f"opacity_{tag}", (0.3, 0.7, 0.9), op, 0.5, 0.0, em, 1.33, 0, False)      # emissive and half-transparent: the worker adds it first
+       for tag, op, em in (("0", 0.0, (0, 0, 0)), ("0.5", 0.5, (0.05, 0.02, 0.01)), ("below1", _NEAR1, (0, 0, 0)),
+                           ("1m5e-7", 1 - 5e-7, (0, 0, 0)), ("1m2e-6", 1 - 2e-6, (0, 0, 0)))]
+    + [("emissive_dielectric", (0.6, 0.6, 0.6), 1.0, 0.5, 0.0, (0.5, 0.3, 0.1), 1.33, 0, False),
+       ("emissive_metal", (0.9, 0.7, 0.4), 1.0, 0.3, 1.0, (0.2, 0.4, 0.8), 1.33, 0, False),
+       ("albedo0", (0.0, 0.0, 0.0), 1.0, 0.5, 0.0, (0, 0, 0), 1.33, 0, False),
+       ("albedo1", (1.0, 1.0, 1.0), 1.0, 0.5, 0.0, (0, 0, 0), 1.33, 0, False),
+       ("ior1", _BASE, 1.0, 0.3, 0.0, (0, 0, 0), 1.0, 0, False),
+       ("ior2.5", _BASE, 1.0, 0.3, 0.0, (0, 0, 0), 2.5, 0, False),
+       ("backface", _BASE, 1.0, 0.5, 0.0, (0.1, 0.1, 0.1), 1.33, 0, True),
+       ("catcher", (0.7, 0.7, 0.7), 1.0, 0.6, 0.0, (0, 0, 0), 1.33, 1, False),            # columns 3 and 4: in the blocker's shadow
+       ("catcher_opacity0.5", (0.7, 0.7, 0.7), 0.5, 0.6, 0.0, (0, 0, 0), 1.33, 1, False)]
+)
+CHART_COLS, CHART_ROWS, CHART_HALF = 6, 5, 0.45       # unit cells centred on the origin, patches of 0.9 x 0.9: gaps of 0.1
+CHART_EYE, CHART_FOV = (0.0137, 1.6, -0.0091), 2.0    # the 5 cells of a column fill the frame's height; off the cell grid
+CHART_TOP = 6.4                                       # height of the facing chart (the camera is below it)
+CHART_SUN_DIR = (0.5, 0.866, 0.05)
+CHART_BLOCKER = (1.3, 1.3 * 0.5 / 0.866, 5.1, -3.4, 3.4)   # y, x0, x1, z0, z1: the shadow of the edge x0 falls on x = 0
+
+
+def chart_scene(sun=None, blocker=False, facing=False, alpha=True):
+    """Material chart: one square patch (two triangles, its own surface and material) per row of CHART_REGIMES, coplanar on y = 0 with
+    normals up, in open space, seen straight down by a camera at CHART_EYE (row `backface` has winding and normals turned over).
+    Patch k sits in cell (k % 6, k // 6) of the full table whatever the options, one model for everything.
+      sun:     None, or the angular radius of one directional light (towards CHART_SUN_DIR, 60 degrees above the plane).
+      blocker: one opaque quad at y = 1.3 over x >= 0.75, outside the camera's view of every patch. With a sharp sun its shadow ends at
+               x = 0, in the gap between columns 2 and 3: columns 3-5 are shadowed, columns 0-2 lit. A sun of radius 0.5 leaves columns
+               4-5 wholly in the umbra (the quad reaches 2.1 past them in x and 0.95 in z) and column 0 wholly lit.
+      facing:  a second chart at y = CHART_TOP, above the camera, normals down, same materials: bounce rays hit it or leave through
+               the gaps (and it shadows parts of the lower chart from the sun).
+      alpha:   False leaves out every patch with an opacity below 1 or a shadow catcher (no material can pass a ray through).
+    -> dict of arrays as plaza_scene, plus `names` (per surface) and `cells` (per surface: column, row, level; -1 for the blocker)."""
+    rows = [r for r in CHART_REGIMES if alpha or (r[2] == 1.0 and not r[7])]
+    cell = {r[0]: divmod(k, CHART_COLS)[::-1] for k, r in enumerate(CHART_REGIMES)}
+    verts, tris, mats, names, cells = [], [], [], [], []
+
+    def add(name, x0, x1, z0, z1, y, up, mat, where):
+        v = np.zeros((4, 11), np.float32)
+        v[:, 0:3] = [[x0, y, z0], [x1, y, z0], [x1, y, z1], [x0, y, z1]]
+        v[:, 3:5] = [[0, 0], [1, 0], [1, 1], [0, 1]]
+        v[:, 5:8] = [0, 1 if up else -1, 0]
+        v[:, 8:11] = [1, 0, 0]
+        verts.append(v)
+        tris.append(np.array([[0, 2, 1], [0, 3, 2]] if up else [[0, 1, 2], [0, 2, 3]], np.uint32))   # counter-clockwise seen from the normal's side
+        mats.append(mat); names.append(name); cells.append(where)
+    for level in range(2 if facing else 1):
+        for name, alb, op, rough, metal, em, ior, catcher, flipped in rows:
+            cx, cz = cell[name][0] - (CHART_COLS - 1) / 2, cell[name][1] - (CHART_ROWS - 1) / 2
+            add(name + ("_top" if level else ""), cx - CHART_HALF, cx + CHART_HALF, cz - CHART_HALF, cz + CHART_HALF, CHART_TOP * level,
+                (level == 0) != flipped, [*alb, op, rough, metal, *em, ior, catcher], (*cell[name], level))
+    if blocker:
+        y, x0, x1, z0, z1 = CHART_BLOCKER
+        add("blocker", x0, x1, z0, z1, y, True, [0.5, 0.5, 0.5, 1.0, 0.5, 0.0, 0, 0, 0, 1.33, 0], (-1, -1, -1))
+    n = len(verts)
+    sun13 = None
+    if sun is not None:
+        d = np.array(CHART_SUN_DIR) / np.linalg.norm(CHART_SUN_DIR)
+        x = np.cross([0, 1, 0], d); x /= np.linalg.norm(x)
+        sun13 = np.concatenate([x, np.cross(d, x), d, [3.0, 2.7, 2.2], [sun]]).astype(np.float32)
+    cam = np.array([*CHART_EYE, 1, 0, 0, 0, 0, -1, 0, 1, 0, CHART_FOV], np.float32)      # -z of the camera points down, image up is world -z
+    ident = [1, 0, 0, 0, 1, 0, 0, 0, 1]
+    return dict(model_xform=np.array([[0, 0, 0] + ident], np.float32), model_surf=np.array([[0, n]], np.int32),
+                surf_range=np.array([[4 * k, 4, 2 * k, 2] for k in range(n)], np.int32), vertices=np.concatenate(verts),
+                triangles=np.concatenate(tris), materials=np.array(mats, np.float32), camera=cam, sun=sun13,
+                names=names, cells=np.array(cells, np.int32))

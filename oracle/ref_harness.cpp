@@ -21,6 +21,7 @@
 //                                                     integrator's composition bit for bit (oracle side: ora_trace_mt)
 //   tri_scaled <outdir> <seed> <n>                    triangle::intersect on n rows of the `vectors` triangle generator, each at the
 //                                                     scales 2^k of kTriScales (corners and ray origin scaled, unit direction kept)
+//   pbr_edges <outdir>                                core::pbr::* / rand_cone_vec / reflect on a deterministic cross of domain edges
 //   mean    <gltf> <out.npy> W H spp bounces threads   float32 mean image by calling trace()
 //   render  <gltf> W H spp bounces threads [out.png]   time renderer::render(), print JSON
 
@@ -616,6 +617,67 @@ static int cmd_trace(const char* gltf, const std::string& dir, uint64_t seed, si
 	return 0;
 }
 
+// core::pbr::*, util::rand_cone_vec, core::reflect at the EDGES of their domains, in the 14-in / 15-out layout of cmd_vectors' pbr block
+// (whose random rows keep away from every edge). Deterministic, no generator: per normal two passes (axis normals: one) over the cross
+//   u1 {0, 2^-24, 0.5, 1 - 2^-24} x u2 {0, 0.25, 0.5, 0.75, 1 - 2^-24} x cos_theta {-1, 0, cos(0.004732), 1},
+// with ior {1, 1.33, 2.5, 1e6} and the 27 combinations of roughness {0.05, 0.5, 1}, outcoming (dot(n, o) = 1 exactly / about 1e-3 /
+// about 1e-6) and incoming (= outcoming / opposite the outcoming: exactly in the first pass, so the halfway vector is 0 / 0, nearly in
+// the second / grazing) cycled along the rows with periods coprime to the cross. Normals: the six axes, |component| = 1/sqrt(3) one
+// ulp below / above (the tangent-frame switch of rand_cone_vec, which compares against the float 1 / math::sqrt3), 24 generic ones.
+static int cmd_pbr_edges(const std::string& dir) {
+	std::filesystem::create_directories(dir);
+	const float one_m = 1.f - 1.f / 16777216.f;
+	const float U1[4] = {0.f, 1.f / 16777216.f, 0.5f, one_m};
+	const float U2[5] = {0.f, 0.25f, 0.5f, 0.75f, one_m};
+	const float CT[4] = {-1.f, 0.f, std::cos(0.004732f), 1.f};
+	const float IOR[4] = {1.f, 1.33f, 2.5f, 1e6f};
+	const float RGH[3] = {0.05f, 0.5f, 1.f};
+	const float thr = 1 / math::sqrt3;
+	const float lo = std::nextafterf(thr, 0.f), hi = std::nextafterf(thr, 1.f);
+	std::vector<fvec3> normals = {fvec3(1, 0, 0), fvec3(-1, 0, 0), fvec3(0, 1, 0), fvec3(0, -1, 0), fvec3(0, 0, 1), fvec3(0, 0, -1),
+	                              fvec3(lo, lo, lo), fvec3(hi, lo, lo), fvec3(hi, hi, lo), fvec3(hi, hi, hi), fvec3(-hi, -lo, hi), fvec3(-lo, hi, -hi),
+	                              };
+	for (int g = 0; g < 24; g++) {   // generic: a spiral over the sphere
+		const float z = 1 - (2 * g + 1) / 24.f, phi = 2.399963f * g + 0.5f, s = std::sqrt(1 - z * z);
+		normals.push_back(normalize(fvec3(std::cos(phi) * s, std::sin(phi) * s, z)));
+	}
+	std::vector<float> in, out;
+	size_t i = 0;
+	for (size_t ni = 0; ni < normals.size(); ni++)
+		// an axis normal gives exact zeros in nearly every sample (the GPU test can check those rows absolutely only): one pass each
+		for (int pass = ni < 6 ? (int)(ni & 1) : 0, last = ni < 6 ? pass : 1; pass <= last; pass++)
+			for (int j = 0; j < 80; j++, i++) {
+				const fvec3 nrm = normals[ni];
+				const float u1 = U1[j % 4], u2 = U2[(j / 4) % 5], cos_theta = CT[j / 20];
+				const float ior = IOR[(i / 7) % 4];
+				const size_t k = i % 27;
+				const float rough = RGH[k % 3];
+				// two unit vectors perpendicular to the normal
+				fvec3 ax = math::abs(nrm.x) < 0.5f ? fvec3(1, 0, 0) : fvec3(0, 1, 0);
+				fvec3 t1 = normalize(cross(nrm, ax)), t2 = cross(nrm, t1);
+				fvec3 side = normalize(t1 * 0.6f + t2 * 0.8f);
+				const float c = (k / 3) % 3 == 0 ? 1.f : (k / 3) % 3 == 1 ? 1e-3f : 1e-6f;
+				fvec3 o = c == 1.f ? nrm : normalize(nrm * c + side * std::sqrt(1 - c * c));
+				fvec3 inc;
+				switch (k / 9) {
+					case 0: inc = o; break;
+					case 1: inc = pass == 0 ? -o : normalize(-o + t1 * 1e-4f); break;
+					default: inc = normalize(t2 + nrm * 1e-4f); break;
+				}
+				push3(in, nrm); push3(in, o); push3(in, inc);
+				in.push_back(u1); in.push_back(u2); in.push_back(rough); in.push_back(cos_theta); in.push_back(ior);
+				push3(out, util::rand_cone_vec(u2, cos_theta, nrm));
+				push3(out, core::pbr::importance_diffuse(fvec2(u1, u2), nrm, o));
+				push3(out, core::pbr::importance_specular(fvec2(u1, u2), nrm, o, rough));
+				out.push_back(core::pbr::pdf_diffuse(nrm, inc));
+				out.push_back(core::pbr::pdf_specular(nrm, o, inc, rough));
+				out.push_back(core::pbr::fresnel(o, core::reflect(-o, nrm), ior));
+				push3(out, core::reflect(-o, nrm));
+			}
+	save(dir, "pbr_in", in, {i, 14}); save(dir, "pbr_out", out, {i, 15});
+	return 0;
+}
+
 // geometry::triangle::intersect (triangle.cpp:120-190) far from unit scale. Rows are drawn as cmd_vectors draws its tri_in block (aimed,
 // edge / vertex, axis-aligned, random and collinear kinds); for every k of kTriScales the corners and the ray origin are multiplied by
 // 2^k (exact: no value comes near the denormals or the overflow threshold) and the ray keeps its unit direction. The determinant
@@ -728,6 +790,7 @@ int main(int argc, char** argv) {
 		if (cmd == "envmap" && argc == 8) return cmd_envmap(argv[2], argv[3], atoi(argv[4]), argv[5], strtoull(argv[6], 0, 10), strtoull(argv[7], 0, 10));
 		if (cmd == "image" && argc == 6) return cmd_image(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10));
 		if (cmd == "trace" && argc == 7) return cmd_trace(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10), atoi(argv[6]));
+		if (cmd == "pbr_edges" && argc == 3) return cmd_pbr_edges(argv[2]);
 		if (cmd == "tri_scaled" && argc == 5) return cmd_tri_scaled(argv[2], strtoull(argv[3], 0, 10), strtoull(argv[4], 0, 10));
 		if (cmd == "mean" && argc == 9)
 			return cmd_mean(argv[2], argv[3], atoi(argv[4]), atoi(argv[5]), atoi(argv[6]), atoi(argv[7]), atoi(argv[8]));
@@ -737,6 +800,6 @@ int main(int argc, char** argv) {
 		fprintf(stderr, "ref_harness: %s\n", e.what());
 		return 2;
 	}
-	fprintf(stderr, "usage: ref_harness scene|vectors|materials|envmap|image|trace|tri_scaled|mean|render ... (see header comment)\n");
+	fprintf(stderr, "usage: ref_harness scene|vectors|materials|envmap|image|trace|tri_scaled|pbr_edges|mean|render ... (see header comment)\n");
 	return 1;
 }
