@@ -14,7 +14,8 @@ namespace ptx {
 #define DEV __device__ __forceinline__
 
 // PTX_PROF builds (tools/build_variant.sh prof -DPTX_PROF): count wave-level trips and active lanes per code region, to
-// weigh the static instruction counts of the ISA. Not compiled into the product.
+// weigh the static instruction counts of the ISA; regions 16-19 are the kinds of shade_vertex's vertices (miss, back face, last, full).
+// Not compiled into the product.
 #ifdef PTX_PROF
 struct Prof { uint32_t t[kProfRegions], l[kProfRegions]; };
 #define PROF_ARG , Prof& prof
@@ -775,15 +776,22 @@ struct ShadowReq {
 
 // PTX_INTEGRATOR_LIB — renderer::trace (core/renderer.cpp:437-643) in iterative throughput form (DESIGN.md "Estimator"):
 //   L += T * (direct + emissive);  T *= clamp(brdf / max(pdf, eps), 0, 1);  next ray.
+//   The vertex at depth == bounces - 1 is the path's last: it computes the hit record, the material, the opacity draw (ALPHA), the
+//   back-face test, the sun request (SUN) and the emission term, and ends there — no Fresnel term without a sun, no BSDF sample,
+//   no BSDF value, no throughput update, no next ray. Miss, pass-through, back face and shadow catcher are as at any depth.
 // PTX_INTEGRATOR_WORKER — one vertex of the HOST worker's stage pipeline: INTERSECT's sun sample
 // (src/processors/worker/intersection_worker.cpp:22-39), SHADING (shading_worker.cpp:27-199); `L` is cloud_ray::color,
 // `T` cloud_ray::scale, `depth` = bounce_count - cloud_ray::bounce.
 // `h` is the closest hit of (o, d) found by the extend sweep. SUN / ALPHA compile the request / pass-through code in.
-template <bool SUN, bool ALPHA, bool TEX, bool WORKER>
+// LAST: what the caller knows about `depth + 1 == P.bounces`. The fused kernel without ALPHA knows it per sweep and compiles one loop
+// for each answer; everyone else leaves the test to the vertex.
+enum : int { LAST_NEVER = 0, LAST_ALWAYS = 1, LAST_BY_DEPTH = 2 };
+template <bool SUN, bool ALPHA, bool TEX, bool WORKER, int LAST = LAST_BY_DEPTH>
 DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParams& P, uint32_t pixel, uint32_t sample,
-                     uint32_t& depth, uint32_t& pass, SceneHit h, V3& o, V3& d, V3& T, V3& L, ShadowReq& rq) {
+                     uint32_t& depth, uint32_t& pass, SceneHit h, V3& o, V3& d, V3& T, V3& L, ShadowReq& rq PROF_ARG) {
 	rq.kind = REQ_NONE;
 	if (h.surface < 0) {   // miss: environment_factor, times the environment map when one is set (renderer.cpp:443-451, shading_worker.cpp:28-41)
+		PROF(16);
 		V3 env = mk(P.env[0], P.env[1], P.env[2]);
 		if constexpr (TEX) {
 			if (S.env_tex >= 0) {   // core::equirectangular_proj (core/utils.hpp:22-27) of ray::get_dir()
@@ -800,7 +808,11 @@ DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParam
 	const MaterialRec& mt = R.mat;
 	const MatEval me = material_eval<TEX>(S, mt, sf.u, sf.v);   // renderer.cpp:458-462
 	float roughness = me.roughness;
-	const float4 rnd = draws(P, pixel, sample, depth, pass, BLOCK_SURFACE);  // x opacity, y lobe, z/w BSDF sample
+	// LIB: the vertex at depth == bounces - 1 is the path's last one: the ray it would sample is traced by trace(0, ..), which is black
+	// (renderer.cpp:438-439).
+	const bool last = !WORKER && (LAST == LAST_ALWAYS || (LAST == LAST_BY_DEPTH && depth + 1 == P.bounces));
+	float4 rnd = make_float4(0, 0, 0, 0);                                    // x opacity, y lobe, z/w BSDF sample
+	if (ALPHA || !last) rnd = draws(P, pixel, sample, depth, pass, BLOCK_SURFACE);   // a last vertex reads lane x alone
 	if constexpr (WORKER) L = L + T * me.emissive10;                         // shading_worker.cpp:52 — before the opacity test
 
 	if constexpr (ALPHA) {
@@ -813,10 +825,13 @@ DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParam
 		}
 	}
 	const V3 normal = shading_normal(sf, me.normal_ts), outcoming = -d;
-	if (dot(normal, outcoming) <= 0) return V_DEAD;                          // renderer.cpp:478-479: black, path ends
+	if (dot(normal, outcoming) <= 0) { PROF(17); return V_DEAD; }            // renderer.cpp:478-479: black, path ends
 	roughness = pmax(roughness, 0.05F);
-	float spec_prob = fresnel_schlick(outcoming, reflect3(-outcoming, normal), mt.ior);
-	spec_prob = pmax(spec_prob, me.metallic);
+	float spec_prob = 0;   // read by the sun's eval_brdf and by the sampling below: a last vertex without a sun needs neither
+	if (!last || (SUN && S.sun.present)) {
+		spec_prob = fresnel_schlick(outcoming, reflect3(-outcoming, normal), mt.ior);
+		spec_prob = pmax(spec_prob, me.metallic);
+	}
 
 	V3 direct_out = mk(0, 0, 0);   // LIB without a request: stays 0
 	if constexpr (SUN) {
@@ -849,8 +864,16 @@ DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParam
 			rq.x = T * direct_out;
 		}
 	}
+	if constexpr (!WORKER) {
+		L = L + T * me.emissive10;
+		// The sample's value is final here (plus the request above, if any). Everything below only prepares the next vertex, and both
+		// ways out of it return V_DEAD for a last vertex. No caller reads o, d, T, depth or pass of a dead path: the fused kernel
+		// (kernels.hip) stores L and, for a request, rq and the sample id; k_wf_shade (wavefront.hip) stores L, or emits a zombie entry
+		// of which the next step reads L and the request alone; aov.hip walks its own first vertex and does not call this function.
+		if (last) { PROF(18); return V_DEAD; }
+	}
+	PROF(19);
 	const V3 inc = importance_sample(rnd.y < spec_prob, rnd.z, rnd.w, normal, outcoming, roughness);
-	if constexpr (!WORKER) L = L + T * me.emissive10;
 	if (!(dot(normal, inc) > 0)) return V_DEAD;                              // renderer.cpp:578 / shading_worker.cpp:154,196-199
 	float pdf;
 	const V3 brdf = eval_brdf(normal, outcoming, inc, me.albedo, roughness, me.metallic, spec_prob, pdf);

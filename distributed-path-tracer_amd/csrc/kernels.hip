@@ -16,6 +16,8 @@
 // Numerics: IEEE binary32 in the reference's operation order, no FMA contraction (-ffp-contract=off),
 // correctly rounded divide / sqrt, the reference's double-precision islands kept in double. Each device
 // function cites what it restates (paths relative to path-tracer-core/path_tracer_lib/path_tracer/).
+#include <type_traits>
+
 #include "device_core.hpp"
 
 namespace ptx {
@@ -315,74 +317,82 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 
 			// ---------------- SHADE + wave-level stream compaction (rays and shadow requests)
 			uint32_t n_out = 0, n_sh = 0;
-			for (uint32_t base = 0; base < n_in; base += 64) {
-				const uint32_t i = base + lane;
-				const bool active = i < n_in;
-				V3 o = {0, 0, 0}, d = {0, 0, 1}, T = {1, 1, 1}, L = {0, 0, 0};
-				uint32_t id = 0, depth = ALPHA ? 0u : step, pass = 0;
-				float key_px = 0.f, key_s = 0.f;   // RNG key words, carried as raw bits
-				int state = V_DEAD;
-				ShadowReq rq;
-				rq.kind = REQ_NONE;
-				if (active) {
-					PROF(9);
-					const float4 q0 = qin[i], q1 = qin[kChunk + i], q2 = qin[2 * kChunk + i], q3 = qin[3 * kChunk + i], hq = hbuf[i];
+			// Without ALPHA every entry of the sweep is at depth == step, so whether its vertices are the paths' last ones (shade_vertex) is
+			// known per sweep: the last sweep of the library estimator gets a loop of its own, built for the short vertex, and the loop of all
+			// other sweeps carries no trace of it. With ALPHA the depth is the entry's, and shade_vertex tests it.
+			auto shade_sweep = [&](auto last_kind) __attribute__((always_inline)) {
+				for (uint32_t base = 0; base < n_in; base += 64) {
+					const uint32_t i = base + lane;
+					const bool active = i < n_in;
+					V3 o = {0, 0, 0}, d = {0, 0, 1}, T = {1, 1, 1}, L = {0, 0, 0};
+					uint32_t id = 0, depth = ALPHA ? 0u : step, pass = 0;
+					float key_px = 0.f, key_s = 0.f;   // RNG key words, carried as raw bits
+					int state = V_DEAD;
+					ShadowReq rq;
+					rq.kind = REQ_NONE;
+					if (active) {
+						PROF(9);
+						const float4 q0 = qin[i], q1 = qin[kChunk + i], q2 = qin[2 * kChunk + i], q3 = qin[3 * kChunk + i], hq = hbuf[i];
 #ifdef PTX_CLK
-					{ CLK_T0(); CLK_WAIT(); CLK_T1(5); }
-					{   // the hit record's nine 16-byte pieces, fetched here so that the wait for them has a region of its own (shade_vertex then finds them in L1)
-						CLK_T0();
-						float acc = 0;
-						if (__float_as_int(hq.x) >= 0 && !(S.hot_lds && S.tri_id_mask == 0x00FFFFFFu && (__float_as_uint(hq.y) >> 24) != 0xFFu)) { const float4* Hh = S.tris + 9 * (size_t)(__float_as_uint(hq.y) & S.tri_id_mask);   // (hot records come from LDS inside shade_vertex)
-						 for (int k = 0; k < 9; k++) acc += Hh[k].w; }
-						CLK_WAIT();
-						if (acc == 1.2345e-30f) rays++;   // keeps the fetches alive
-						CLK_T1(6);
-					}
+						{ CLK_T0(); CLK_WAIT(); CLK_T1(5); }
+						{   // the hit record's nine 16-byte pieces, fetched here so that the wait for them has a region of its own (shade_vertex then finds them in L1)
+							CLK_T0();
+							float acc = 0;
+							if (__float_as_int(hq.x) >= 0 && !(S.hot_lds && S.tri_id_mask == 0x00FFFFFFu && (__float_as_uint(hq.y) >> 24) != 0xFFu)) { const float4* Hh = S.tris + 9 * (size_t)(__float_as_uint(hq.y) & S.tri_id_mask);   // (hot records come from LDS inside shade_vertex)
+							 for (int k = 0; k < 9; k++) acc += Hh[k].w; }
+							CLK_WAIT();
+							if (acc == 1.2345e-30f) rays++;   // keeps the fetches alive
+							CLK_T1(6);
+						}
 #endif
-					o = mk(q0.x, q0.y, q0.z); id = __float_as_uint(q0.w);
-					d = mk(q1.x, q1.y, q1.z);
-					T = mk(q1.w, q2.x, q2.y);
-					L = mk(q2.z, q2.w, q3.x);
-					key_px = q3.z; key_s = q3.w;
-					if constexpr (ALPHA) { const uint32_t dp = __float_as_uint(q3.y); depth = dp >> 16; pass = dp & 0xFFFFu; }
-					SceneHit h;
-					h.dist = 0; h.surface = __float_as_int(hq.x); h.tri = __float_as_uint(hq.y); h.b1 = hq.z; h.b2 = hq.w;
-					bool depth0 = false;
-					if constexpr (TRANSP) depth0 = depth == 0;   // before the vertex: a scatter raises depth, a miss leaves it
-					state = shade_vertex<SUN, ALPHA, TEX, WORKER>(S, st.shade, P, __float_as_uint(key_px), __float_as_uint(key_s), depth, pass, h, o, d, T, L, rq);
-					if (state == V_DEAD) {
-						if constexpr (TRANSP) B.sample_rad[id] = make_float4(L.x, L.y, L.z, sample_alpha(true, h.surface < 0, depth0));
-						else B.sample_rad[id] = make_float4(L.x, L.y, L.z, 1.0f);
-					}
-				}
-				const bool alive = state == V_ALIVE;
-				const uint64_t mask = __ballot(alive);
-				const uint32_t pos = n_out + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-				if (alive) {
-					qout[pos] = make_float4(o.x, o.y, o.z, __uint_as_float(id));
-					qout[kChunk + pos] = make_float4(d.x, d.y, d.z, T.x);
-					qout[2 * kChunk + pos] = make_float4(T.y, T.z, L.x, L.y);
-					qout[3 * kChunk + pos] = make_float4(L.z, __uint_as_float((depth << 16) | pass), key_px, key_s);
-				}
-				n_out += (uint32_t)__popcll(mask);
-				if constexpr (SUN) {
-					const bool want = rq.kind != REQ_NONE;
-					const uint64_t sm = __ballot(want);
-					if (want) {
-						const uint32_t sp = n_sh + __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
-						// where the answer goes: the path's new stream entry, its final sample (0xFFFFFFFF), or — shadow catcher — its current entry
-						const uint32_t target = rq.kind == REQ_CATCHER ? i : (alive ? pos : 0xFFFFFFFFu);
-						sreq[sp] = make_float4(rq.o.x, rq.o.y, rq.o.z, __uint_as_float(target));
-						sreq[kChunk + sp] = make_float4(rq.d.x, rq.d.y, rq.d.z, __uint_as_float(rq.kind));
-						sreq[2 * kChunk + sp] = make_float4(rq.x.x, rq.x.y, rq.x.z, __uint_as_float(id));
-						if (rq.kind == REQ_CATCHER) {   // the pass-through entry is built from the current one: make its path state complete
-							qin[2 * kChunk + i] = make_float4(T.y, T.z, L.x, L.y);
-							qin[3 * kChunk + i] = make_float4(L.z, __uint_as_float((depth << 16) | pass), key_px, key_s);
+						o = mk(q0.x, q0.y, q0.z); id = __float_as_uint(q0.w);
+						d = mk(q1.x, q1.y, q1.z);
+						T = mk(q1.w, q2.x, q2.y);
+						L = mk(q2.z, q2.w, q3.x);
+						key_px = q3.z; key_s = q3.w;
+						if constexpr (ALPHA) { const uint32_t dp = __float_as_uint(q3.y); depth = dp >> 16; pass = dp & 0xFFFFu; }
+						SceneHit h;
+						h.dist = 0; h.surface = __float_as_int(hq.x); h.tri = __float_as_uint(hq.y); h.b1 = hq.z; h.b2 = hq.w;
+						bool depth0 = false;
+						if constexpr (TRANSP) depth0 = depth == 0;   // before the vertex: a scatter raises depth, a miss leaves it
+						state = shade_vertex<SUN, ALPHA, TEX, WORKER, decltype(last_kind)::value>(S, st.shade, P, __float_as_uint(key_px), __float_as_uint(key_s), depth, pass, h, o, d, T, L, rq PROF_PASS);
+						if (state == V_DEAD) {
+							if constexpr (TRANSP) B.sample_rad[id] = make_float4(L.x, L.y, L.z, sample_alpha(true, h.surface < 0, depth0));
+							else B.sample_rad[id] = make_float4(L.x, L.y, L.z, 1.0f);
 						}
 					}
-					n_sh += (uint32_t)__popcll(sm);
+					const bool alive = state == V_ALIVE;
+					const uint64_t mask = __ballot(alive);
+					const uint32_t pos = n_out + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+					if (alive) {
+						qout[pos] = make_float4(o.x, o.y, o.z, __uint_as_float(id));
+						qout[kChunk + pos] = make_float4(d.x, d.y, d.z, T.x);
+						qout[2 * kChunk + pos] = make_float4(T.y, T.z, L.x, L.y);
+						qout[3 * kChunk + pos] = make_float4(L.z, __uint_as_float((depth << 16) | pass), key_px, key_s);
+					}
+					n_out += (uint32_t)__popcll(mask);
+					if constexpr (SUN) {
+						const bool want = rq.kind != REQ_NONE;
+						const uint64_t sm = __ballot(want);
+						if (want) {
+							const uint32_t sp = n_sh + __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+							// where the answer goes: the path's new stream entry, its final sample (0xFFFFFFFF), or — shadow catcher — its current entry
+							const uint32_t target = rq.kind == REQ_CATCHER ? i : (alive ? pos : 0xFFFFFFFFu);
+							sreq[sp] = make_float4(rq.o.x, rq.o.y, rq.o.z, __uint_as_float(target));
+							sreq[kChunk + sp] = make_float4(rq.d.x, rq.d.y, rq.d.z, __uint_as_float(rq.kind));
+							sreq[2 * kChunk + sp] = make_float4(rq.x.x, rq.x.y, rq.x.z, __uint_as_float(id));
+							if (rq.kind == REQ_CATCHER) {   // the pass-through entry is built from the current one: make its path state complete
+								qin[2 * kChunk + i] = make_float4(T.y, T.z, L.x, L.y);
+								qin[3 * kChunk + i] = make_float4(L.z, __uint_as_float((depth << 16) | pass), key_px, key_s);
+							}
+						}
+						n_sh += (uint32_t)__popcll(sm);
+					}
 				}
-			}
+			};
+			if constexpr (ALPHA || WORKER) shade_sweep(std::integral_constant<int, LAST_BY_DEPTH>{});
+			else if (__builtin_expect(step + 1 != P.bounces, 1)) shade_sweep(std::integral_constant<int, LAST_NEVER>{});
+			else shade_sweep(std::integral_constant<int, LAST_ALWAYS>{});
 			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #ifdef PTX_CLK

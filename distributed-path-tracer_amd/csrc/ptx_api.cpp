@@ -970,7 +970,7 @@ int render_stats(ptx_ctx* c, uint64_t samples, uint32_t n_pass, bool wavefront, 
 	HIP_TRY(hipMemcpy(prof, (char*)c->counters.p + 64, sizeof prof, hipMemcpyDeviceToHost));
 	static const char* names[kProfRegions] = {"extend_iter", "model_iter", "space_xform", "inline_model", "mesh_call", "mesh_pop", "node_step",
 	                                           "tri_test", "defer_iter", "shade_iter", "defer_mesh_call", "defer_mesh_pop", "defer_node_step", "defer_tri_test",
-	                                           "list_append", "shade_hit"};
+	                                           "list_append", "shade_hit", "vertex_miss", "vertex_back_face", "vertex_last", "vertex_full"};
 	for (int k = 0; k < kProfRegions; k++)
 		fprintf(stderr, "PROF %-16s trips %12llu lanes %14llu  util %.3f  trips/64rays %.3f\n", names[k], prof[2 * k], prof[2 * k + 1],
 		        prof[2 * k] ? (double)prof[2 * k + 1] / (64.0 * prof[2 * k]) : 0.0, (double)prof[2 * k] / ((double)rays / 64.0));

@@ -607,6 +607,9 @@ template <bool SUN, bool ALPHA, bool TEX, bool WORKER>
 __global__ void __launch_bounds__(kWfBlock) k_wf_shade(DevScene S0, RenderParams P, WfBuffers W, WfStream in, WfStream out, uint32_t cap, uint32_t slab_first,
                                                       uint32_t* __restrict__ n_out, float4* __restrict__ sample_rad, const ModelRec* __restrict__ t_models,
                                                       const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space) {
+#ifdef PTX_PROF
+	Prof prof{};   // not reported: only the fused kernel's vertices are counted
+#endif
 	DevScene S = S0;
 	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;
 	if (W.ctl[1]) return;   // this step's pairs did not fit the pool: nothing is emitted, the later steps of the slab find no entries
@@ -661,7 +664,7 @@ __global__ void __launch_bounds__(kWfBlock) k_wf_shade(DevScene S0, RenderParams
 				SceneHit h;
 				wf_closest(S, W, pe, o, d, h);
 				const bool depth0 = depth == 0;   // before the vertex: a scatter raises depth, a miss leaves it
-				const int state = shade_vertex<SUN, ALPHA, TEX, WORKER>(S, S.shade, P, __float_as_uint(key_px), __float_as_uint(key_s), depth, pass, h, o, d, T, L, rq);
+				const int state = shade_vertex<SUN, ALPHA, TEX, WORKER>(S, S.shade, P, __float_as_uint(key_px), __float_as_uint(key_s), depth, pass, h, o, d, T, L, rq PROF_PASS);
 				if (state == V_ALIVE) emit = true;
 				else if (state == V_PENDING) { emit = true; out_flags = kWfPending; o = rq.x; }
 				else if (rq.kind == REQ_ADD) { emit = true; out_flags = kWfZombie; }   // the path is over, its last sun sample is not
