@@ -186,13 +186,14 @@ struct MeshHit { float t; float b1, b2; uint32_t tri; };
 
 constexpr int kRegStack = 3;    // pending KD subtrees kept in registers (covers > 99 % of traversals)
 constexpr int kSpillStack = 24; // deeper entries go to a per-lane overflow area in global memory (touched by < 1 % of
-                                // traversals): the reference pushes at most one entry per level and its trees are at
-                                // most 26 levels deep (mesh.hpp:34, max_depth = 25)
+                                // traversals): at most one entry per level (the reference's, plus mesh_traverse's placeholders
+                                // where the reference pushes none) and trees at most 26 levels deep (mesh.hpp:34, max_depth = 25)
 
 // Overflow stack of one lane: entry k lives at base[k * 64] (uint2 = node, min_dist bits), so that the 64 lanes of a wave
 // touch one 512-byte row per level. An explicit global array, not a private one: a private array would be turned into
 // registers + compare/select chains, or into scratch whose address arithmetic sits in every push and pop.
 struct Spill { uint2* base; };
+constexpr uint32_t kNoNode = 0xFFFFFFFFu;   // node of a placeholder entry (mesh_traverse)
 DEV void spill_put(const Spill& sp, int k, uint32_t node, float m) { sp.base[k * 64] = make_uint2(node, __float_as_uint(m)); }
 DEV void spill_get(const Spill& sp, int k, uint32_t& node, float& m) { uint2 v = sp.base[k * 64]; node = v.x; m = __uint_as_float(v.y); }
 
@@ -251,9 +252,15 @@ DEV bool aabb_test_box(const float* b, V3 o, V3 inv, float& nr, float& fr) {
 
 // core::mesh::intersect — core/mesh.cpp:300-405: front-to-back stack traversal, returns at the first
 // leaf that yields a hit within [.., max_dist].
-// Stack entries are (node, min_dist) only: the max_dist the reference stores with an entry is always the
-// min_dist of the entry beneath it (each push hands its old max_dist to the pushed subtree and continues
-// with max_dist = split_dist = the pushed min_dist), and the AABB exit distance for the bottom one.
+// Stack entries are (node, min_dist) only; the max_dist the reference stores with an entry is rebuilt at the pop as the
+// min_dist of the entry beneath it (the AABB exit distance for the bottom one). That is the stored value only if EVERY
+// "both children" step leaves an entry behind: such a step continues with max_dist = split_dist, and the next push hands that
+// value to its subtree. The reference pushes nothing when the far child is absent (an empty-space cut of the builder) and still
+// cuts max_dist (mesh.cpp:364-368), so such a step pushes a placeholder here: (kNoNode, split_dist), dropped when it is popped.
+// Without it the rebuilt bound is the looser one of an older entry, and a leaf popped later accepts a triangle beyond the cut
+// plane that the reference rejects (seen on rays aimed at triangle corners of meshes at coordinates of 1e3 and more, where the
+// rounding of t exceeds the 1e-4 the builder leaves between geometry and cut). One entry per level either way: the reference's
+// trees are at most 26 levels deep, so at most 25 entries are pending.
 // (nr, fr) = the surface box's entry / exit distances (mesh.cpp:308-315): tested by the caller, which may decide with the
 // result whether the lane traverses now or is set aside for a full-wave sweep.
 template <int PB>
@@ -275,6 +282,7 @@ DEV bool mesh_traverse(const Geom& g, uint32_t root, float nr, float fr, V3 o, V
 			n0 = n1; m0 = m1; n1 = n2; m1 = m2;
 			if (sp >= kRegStack) spill_get(spill, sp - kRegStack, n2, m2);
 			max_dist = sp > 0 ? m0 : fr;
+			if (node == kNoNode) continue;   // a placeholder: it only carried its split_dist for the entries above it
 		}
 		have = false;
 		bool valid = true;
@@ -308,9 +316,9 @@ DEV bool mesh_traverse(const Geom& g, uint32_t root, float nr, float fr, V3 o, V
 			if (split_dist < 0 || split_dist > max_dist) { next = first; has_next = has_first; }
 			else if (split_dist < min_dist) { next = second; has_next = has_second; }
 			else {
-				if (has_second && sp < kRegStack + kSpillStack) {
+				if (sp < kRegStack + kSpillStack) {
 					if (sp >= kRegStack) spill_put(spill, sp - kRegStack, n2, m2);
-					n2 = n1; m2 = m1; n1 = n0; m1 = m0; n0 = second; m0 = split_dist;
+					n2 = n1; m2 = m1; n1 = n0; m1 = m0; n0 = has_second ? second : kNoNode; m0 = split_dist;
 					sp++;
 				}
 				next = first; has_next = has_first;

@@ -386,3 +386,101 @@ def chart_scene(sun=None, blocker=False, facing=False, alpha=True):
                 surf_range=np.array([[4 * k, 4, 2 * k, 2] for k in range(n)], np.int32), vertices=np.concatenate(verts),
                 triangles=np.concatenate(tris), materials=np.array(mats, np.float32), camera=cam, sun=sun13,
                 names=names, cells=np.array(cells, np.int32))
+
+
+# ---------------------------------------------------------------------------- the corner cluster (deep KD walks)
+def _flat_vertices(p):
+    """[n, 3, 3] float32 corner positions -> vertices [3 n, 11] (per-triangle normal, tangent along the first edge), triangles [n, 3]."""
+    p64 = p.astype(np.float64)
+    fn = np.cross(p64[:, 1] - p64[:, 0], p64[:, 2] - p64[:, 0])
+    fn /= np.maximum(np.linalg.norm(fn, axis=1, keepdims=True), 1e-300)
+    tw = p64[:, 1] - p64[:, 0]
+    tw /= np.maximum(np.linalg.norm(tw, axis=1, keepdims=True), 1e-300)
+    v = np.zeros((3 * len(p), 11), np.float32)
+    v[:, 0:3] = p.reshape(-1, 3)
+    v[:, 3:5] = np.tile(np.array([[0, 0], [1, 0], [0, 1]], np.float32), (len(p), 1))
+    v[:, 5:8] = np.repeat(fn, 3, axis=0)
+    v[:, 8:11] = np.repeat(tw, 3, axis=0)
+    return v, np.arange(3 * len(p), dtype=np.uint32).reshape(-1, 3)
+
+
+def corner_cluster(n: int, ratio: float, size: float, scale: float, seed: int = 0):
+    """Corner positions [n, 3, 3] float32 of n triangles clustered self-similarly toward the origin: triangle i has
+    s_i = scale * ratio**i and corners s_i * (1, 1, 1) + size * s_i * U_i, U_i uniform in [-1, 1]^(3 x 3), drawn in triangle
+    order from default_rng(seed); all arithmetic in float32. -> (corners, s [n] float32)"""
+    f = np.float32
+    rng = np.random.default_rng(seed)
+    s = (f(scale) * f(ratio) ** np.arange(n, dtype=np.float32)).astype(np.float32)
+    u = rng.uniform(-1.0, 1.0, (n, 3, 3)).astype(np.float32)
+    return (s[:, None, None] + f(size) * s[:, None, None] * u).astype(np.float32), s
+
+
+def corner_cluster_scene(n: int = 60, ratio: float = 0.8, size: float = 0.1, scale: float = 1e3, seed: int = 0, sun: bool = False,
+                         surfaces: int = 1, backdrop: int = 0):
+    """One model (identity transform) whose surface is a corner_cluster: with the builder's 1e-4 empty-space cuts and child boxes
+    that shrink by `ratio`, the SAH tree is a comb that reaches the depth limit, and a ray that starts in the innermost cell and
+    runs outwards sets aside one subtree per level (walks with ~20 pending entries; Cornell's rays reach 8).
+      surfaces: that many clusters in the one model, surface j drawn with seed + j (all along the same diagonal);
+      backdrop: > 0 adds one more surface, a backdrop x backdrop grid across the diagonal beyond the outermost triangle: at 48
+                (4608 triangles) it does not fit LDS next to the clusters, so the scene is hybrid-resident.
+    The camera sits inside the innermost cell and looks along (1, 1, 1). -> dict of arrays as plaza_scene."""
+    f = np.float32
+    parts = []
+    for j in range(surfaces):
+        p, s = corner_cluster(n, ratio, size, scale, seed + j)
+        parts.append(_flat_vertices(p))
+    if backdrop > 0:
+        d = np.array([1.0, 1.0, 1.0]) / np.sqrt(3.0)
+        ex = np.array([1.0, -1.0, 0.0]) / np.sqrt(2.0)
+        ey = np.cross(d, ex)
+        half = 1.5 * scale
+        gv, gt = _grid(backdrop, 2.0 * scale * np.ones(3) - half * (ex + ey), 2 * half * ey, 2 * half * ex)   # normal towards the origin
+        parts.append((gv, gt))
+    sr, v0, t0 = [], 0, 0
+    for v, t in parts:
+        sr.append([v0, len(v), t0, len(t)])
+        v0 += len(v); t0 += len(t)
+    k = len(parts)
+    rng = np.random.default_rng(seed + 1000)
+    mats = np.zeros((k, 11), np.float32)
+    mats[:, 0:3] = 0.4 + 0.5 * rng.random((k, 3))
+    mats[:, 3] = 1.0
+    mats[:, 4] = 0.3 + 0.6 * rng.random(k)
+    mats[:, 5] = (np.arange(k) % 3) == 1
+    mats[:, 9] = 1.45
+    eye = (s[-1] * f(1.0 - size) * f(0.5)) * np.ones(3, np.float32)
+    cam = np.concatenate([_look_at(eye, eye.astype(np.float64) + 1.0), [f(2.5 * size)]]).astype(np.float32)
+    sun13 = None
+    if sun:
+        dd = np.array([0.2, 0.9, 0.4])
+        dd /= np.linalg.norm(dd)
+        x = np.cross([0, 1, 0], dd); x /= np.linalg.norm(x)
+        sun13 = np.concatenate([x, np.cross(dd, x), dd, [3.0, 2.8, 2.5], [0.004732]]).astype(np.float32)
+    ident = [1, 0, 0, 0, 1, 0, 0, 0, 1]
+    return dict(model_xform=np.array([[0, 0, 0] + ident], np.float32), model_surf=np.array([[0, k]], np.int32),
+                surf_range=np.array(sr, np.int32), vertices=np.concatenate([p[0] for p in parts]).astype(np.float32),
+                triangles=np.concatenate([p[1] for p in parts]).astype(np.uint32), materials=mats, camera=cam, sun=sun13)
+
+
+def corner_cluster_rays(n: int, ratio: float, size: float, scale: float, count: int, seed: int = 0, rng_seed: int = 1, corner_f=None,
+                        any_cell: bool = False):
+    """Rays for corner_cluster_scene(n, ratio, size, scale, seed): origins s_{n-1} * (1 - size) * u, u uniform in [0.2, 1]^3 (inside the
+    innermost cell), aimed at a vertex of a random triangle: at vertex * U(0.7, 1.3), or, with corner_f = a list of fractions f, just
+    inside the corner: vertex + (centroid - vertex) * f, f cycling through the list. any_cell: the origin scales with a random triangle's
+    s_k instead of the innermost one's (walks of every depth up to the deepest). Directions normalised in float32. -> [count, 6]"""
+    f = np.float32
+    p, s = corner_cluster(n, ratio, size, scale, seed)
+    rng = np.random.default_rng(rng_seed)
+    cell = rng.integers(0, n, count) if any_cell else np.full(count, n - 1)
+    org = (s[cell, None] * f(1.0 - size) * rng.uniform(0.2, 1.0, (count, 3)).astype(np.float32)).astype(np.float32)
+    ti, vi = rng.integers(0, n, count), rng.integers(0, 3, count)
+    vert = p[ti, vi]
+    if corner_f is None:
+        tgt = vert * rng.uniform(0.7, 1.3, (count, 3)).astype(np.float32)
+    else:
+        cen = p[ti].mean(1, dtype=np.float32)
+        fr = np.asarray(corner_f, np.float32)[np.arange(count) % len(corner_f)]
+        tgt = vert + (cen - vert) * fr[:, None]
+    d = (tgt - org).astype(np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True).astype(np.float32)
+    return np.concatenate([org, d], 1).astype(np.float32)

@@ -282,15 +282,17 @@ struct mesh_hit { float t = -1; v3 bary{0, 0, 0}; uint32_t index = 0; };
 struct trav_stats { uint64_t branches = 0, leaves = 0, tris = 0, pushes = 0, mesh_tests = 0, model_tests = 0, hits = 0; uint64_t depth_hist[32] = {0}; };
 
 // mesh::intersect — mesh.cpp:300-405
-static mesh_hit mesh_intersect(const mesh& m, const ray& r, trav_stats* st) {
+// `depth` (optional): the deepest simultaneous number of pending entries of this walk (0 when the box is missed)
+static mesh_hit mesh_intersect(const mesh& m, const ray& r, trav_stats* st, int* depth = nullptr) {
 	if (st) st->mesh_tests++;
+	if (depth) *depth = 0;
 	aabb_hit bh = aabb_intersect(m.box, r);
 	if (!bh.hit) return {};
 	struct ent { int node; float mn, mx; };
 	ent stack[64];
 	int sp = 0;
 	int max_sp = 0;   // diagnostics only: deepest simultaneous number of PENDING entries (root excluded)
-	struct depth_rec { trav_stats* st; int* m; ~depth_rec() { if (st) st->depth_hist[*m < 31 ? *m : 31]++; } } rec{st, &max_sp};
+	struct depth_rec { trav_stats* st; int* m; int* d; ~depth_rec() { if (st) st->depth_hist[*m < 31 ? *m : 31]++; if (d) *d = *m; } } rec{st, &max_sp, depth};
 	stack[sp++] = {0, bh.nr, bh.fr};
 	while (sp > 0) {
 		ent e = stack[--sp];
@@ -331,6 +333,60 @@ static mesh_hit mesh_intersect(const mesh& m, const ray& r, trav_stats* st) {
 		return {nearest.t, nearest.bary, m.refs[leaf.first + index]};
 	}
 	return {};
+}
+
+// A FOIL, never an expected value: mesh_intersect with the far bound of a popped entry not stored but rebuilt from the entry
+// beneath it (that entry's min_dist, or the box's exit distance for the bottom one) -- the form a walker takes that keeps
+// (node, min_dist) only. The two differ after a "both children" step whose far child is absent (an empty-space cut): the
+// reference cuts max_dist to split_dist there and pushes nothing, so the next push stores a bound that no entry's min_dist
+// repeats. `differed`: whether any pop of this walk rebuilt a bound other than the stored one.
+static mesh_hit mesh_intersect_recon(const mesh& m, const ray& r, bool* differed) {
+	*differed = false;
+	aabb_hit bh = aabb_intersect(m.box, r);
+	if (!bh.hit) return {};
+	struct ent { int node; float mn, mx; };
+	ent stack[64];   // pending entries only; `mx` is kept for the comparison, never used
+	int sp = 0;
+	int node = 0;
+	float min_dist = bh.nr, max_dist = bh.fr;
+	for (bool have = true;; have = false) {
+		if (!have) {
+			if (sp == 0) return {};
+			ent e = stack[--sp];
+			node = e.node; min_dist = e.mn;
+			max_dist = sp > 0 ? stack[sp - 1].mn : bh.fr;
+			if (memcmp(&max_dist, &e.mx, 4) != 0) *differed = true;
+		}
+		while (node >= 0 && !m.nodes[node].leaf) {
+			const kd_node& b = m.nodes[node];
+			float o = get(r.o, b.axis), d = get(r.d, b.axis);
+			float split_dist = (b.split - o) / d;
+			int first, second;
+			if (o < b.split) { first = b.left; second = b.right; }
+			else { first = b.right; second = b.left; }
+			if (split_dist < 0 || split_dist > max_dist) node = first;
+			else if (split_dist < min_dist) node = second;
+			else {
+				if (second >= 0) stack[sp++] = {second, split_dist, max_dist};
+				node = first;
+				max_dist = split_dist;
+			}
+		}
+		if (node < 0) continue;
+		const kd_node& leaf = m.nodes[node];
+		tri_hit nearest{-1, {0, 0, 0}};
+		uint32_t index = 0;
+		for (int i = 0; i < leaf.count; i++) {
+			uint32_t ti = m.refs[leaf.first + i];
+			tri_hit h = tri_intersect(m.verts[m.tris[3 * ti]].pos, m.verts[m.tris[3 * ti + 1]].pos,
+			                          m.verts[m.tris[3 * ti + 2]].pos, r);
+			if (h.t >= 0 && h.t <= max_dist && (h.t < nearest.t || !(nearest.t >= 0))) {
+				nearest = h;
+				index = (uint32_t)i;
+			}
+		}
+		if (nearest.t >= 0) return {nearest.t, nearest.bary, m.refs[leaf.first + index]};
+	}
 }
 
 // ---------------------------------------------------------------- image/image.cpp, image/image_texture.cpp
@@ -1035,6 +1091,34 @@ void ora_mesh_intersect(void* p, int surf, size_t n, const float* rays /*[n][6]*
 		bool hit = h.t >= 0;
 		o[0] = h.t; o[1] = hit ? h.bary.x : 0; o[2] = hit ? h.bary.y : 0; o[3] = hit ? h.bary.z : 0;
 		idx[i] = hit ? (int)h.index : -1;
+	}
+}
+// ora_mesh_intersect plus, per ray, the deepest number of pending entries of its walk, and their histogram (hist[32], last bin = 31+)
+void ora_mesh_intersect_depth(void* p, int surf, size_t n, const float* rays, float* out /*[n][4]*/, int* idx, int* depth /*[n]*/, uint64_t* hist /*[32]*/) {
+	const mesh& m = ((scene_t*)p)->surfaces[surf].m;
+	trav_stats st;
+	for (size_t i = 0; i < n; i++) {
+		const float* q = rays + 6 * i;
+		mesh_hit h = mesh_intersect(m, {{q[0], q[1], q[2]}, {q[3], q[4], q[5]}}, &st, depth + i);
+		float* o = out + 4 * i;
+		bool hit = h.t >= 0;
+		o[0] = h.t; o[1] = hit ? h.bary.x : 0; o[2] = hit ? h.bary.y : 0; o[3] = hit ? h.bary.z : 0;
+		idx[i] = hit ? (int)h.index : -1;
+	}
+	for (int k = 0; k < 32; k++) hist[k] = st.depth_hist[k];
+}
+// the foil (mesh_intersect_recon): records in ora_mesh_intersect's layout, and per ray whether a rebuilt bound differed from the stored one
+void ora_mesh_intersect_recon(void* p, int surf, size_t n, const float* rays, float* out /*[n][4]*/, int* idx, uint8_t* differed /*[n]*/) {
+	const mesh& m = ((scene_t*)p)->surfaces[surf].m;
+	for (size_t i = 0; i < n; i++) {
+		const float* q = rays + 6 * i;
+		bool df;
+		mesh_hit h = mesh_intersect_recon(m, {{q[0], q[1], q[2]}, {q[3], q[4], q[5]}}, &df);
+		float* o = out + 4 * i;
+		bool hit = h.t >= 0;
+		o[0] = h.t; o[1] = hit ? h.bary.x : 0; o[2] = hit ? h.bary.y : 0; o[3] = hit ? h.bary.z : 0;
+		idx[i] = hit ? (int)h.index : -1;
+		differed[i] = df;
 	}
 }
 void ora_model_intersect(void* p, int mdl, size_t n, const float* rays, float* out /*[n][4]*/, int* idx /*[n][2]*/) {

@@ -449,12 +449,27 @@ class OracleScene:
         lib().ora_material_eval(self.h, surf, C.c_size_t(len(uv)), _p(uv), _p(out))
         return out
 
-    def mesh_intersect(self, surf, rays):
+    def mesh_intersect(self, surf, rays, stats=False):
+        """mesh::intersect of surface `surf` (rays in its model's space) -> (out [n,4] = distance, barycentrics; triangle or -1).
+        With stats: also the deepest number of pending stack entries of every ray's walk [n], and its histogram [32]."""
         rays = np.ascontiguousarray(rays, np.float32)
         n = len(rays)
         out = np.zeros((n, 4), np.float32); idx = np.zeros(n, np.int32)
+        if stats:
+            depth = np.zeros(n, np.int32); hist = np.zeros(32, np.uint64)
+            lib().ora_mesh_intersect_depth(self.h, surf, C.c_size_t(n), _p(rays), _p(out), _p(idx), _p(depth), _p(hist))
+            return out, idx, depth, hist
         lib().ora_mesh_intersect(self.h, surf, C.c_size_t(n), _p(rays), _p(out), _p(idx))
         return out, idx
+
+    def mesh_intersect_recon(self, surf, rays):
+        """A FOIL for searches, never an expected value: mesh_intersect with every popped far bound rebuilt from the entry beneath
+        (ora_mesh_intersect_recon) -> (out, idx as mesh_intersect; per ray whether a rebuilt bound differed from the stored one)."""
+        rays = np.ascontiguousarray(rays, np.float32)
+        n = len(rays)
+        out = np.zeros((n, 4), np.float32); idx = np.zeros(n, np.int32); diff = np.zeros(n, np.uint8)
+        lib().ora_mesh_intersect_recon(self.h, surf, C.c_size_t(n), _p(rays), _p(out), _p(idx), _p(diff))
+        return out, idx, diff.astype(bool)
 
     def model_intersect(self, mdl, rays):
         rays = np.ascontiguousarray(rays, np.float32)

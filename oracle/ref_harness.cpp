@@ -14,6 +14,7 @@
 //   vectors <gltf> <outdir> <seed> <n>          function-level known-answer vectors as .npy
 //   materials <gltf> <outdir> <seed> <n>        per surface: material::get_* (texture lookups) at n random uvs
 //   materials_at <gltf> <uvfile> <outdir>       the same at given uvs (raw float32 [n_surfaces][n][2])
+//   intersect_at <gltf> <rayfile> <outdir>    renderer::intersect and model::intersect of given rays (raw float32 [n][6]: origin, direction)
 //   envmap <gltf> <png> <srgb> <outdir> <seed> <n>   environment-map lookups: equirectangular_proj + image_texture::sample + trace() on misses
 //   image   <file> <outdir> <seed> <n>               decoded pixels of image::image::load's stb_image call (JPEG / PNG) + n bilinear
 //                                                     image_texture::sample lookups on it (linear and sRGB)
@@ -515,6 +516,49 @@ static int cmd_materials_at(const char* gltf, const char* uvfile, const std::str
 	return 0;
 }
 
+// renderer::intersect (renderer.cpp:645-725) and every model's scene::model::intersect (model.cpp:20-72) at caller-given rays: `rayfile`
+// holds raw little-endian float32 [n][6] (origin, direction). geometry::ray normalises the direction it is given, so the rays are
+// written back as used (at_rays); the records have the layout of `vectors`' scene_out / scene_idx / model_out / model_idx.
+static int cmd_intersect_at(const char* gltf, const char* rayfile, const std::string& dir) {
+	core::renderer r;
+	load(r, gltf);
+	std::filesystem::create_directories(dir);
+	auto models = visit_order(r);
+	std::ifstream f(rayfile, std::ios::binary | std::ios::ate);
+	const size_t bytes = (size_t)f.tellg();
+	if (!f || bytes == 0 || bytes % 24 != 0) { fprintf(stderr, "intersect_at: %s is not [n][6] float32\n", rayfile); return 2; }
+	const size_t n = bytes / 24;
+	std::vector<float> in(bytes / 4), used, mout, rout;
+	std::vector<int32_t> midx, ridx;
+	f.seekg(0);
+	f.read((char*)in.data(), (std::streamsize)bytes);
+	std::map<const scene::model::surface*, int32_t> surf_id;
+	std::map<const core::material*, int32_t> mat_id;
+	int32_t sid = 0;
+	for (auto& m : models) for (auto& s : m.model->surfaces) { surf_id[&s] = sid; mat_id[s.material.get()] = sid; sid++; }
+	for (size_t i = 0; i < n; i++) {
+		const float* q = &in[6 * i];
+		const geometry::ray ray(fvec3(q[0], q[1], q[2]), fvec3(q[3], q[4], q[5]));
+		push3(used, ray.origin); push3(used, ray.get_dir());
+		for (auto& m : models) {
+			auto h = m.model->intersect(ray);
+			mout.push_back(h.distance);
+			if (h.has_hit()) { push3(mout, h.barycentric); midx.push_back(surf_id[h.surface]); midx.push_back((int32_t)h.triangle_index); }
+			else { push3(mout, fvec3(0)); midx.push_back(-1); midx.push_back(-1); }
+		}
+		auto res = r.intersect(ray);
+		ridx.push_back(res.hit ? mat_id[res.material.get()] : -1);
+		if (res.hit) {
+			push3(rout, res.position); rout.push_back(res.tex_coord.x); rout.push_back(res.tex_coord.y);
+			push3(rout, res.normal); push3(rout, res.tangent); push3(rout, res.get_normal());
+		} else for (int k = 0; k < 14; k++) rout.push_back(0);
+	}
+	save(dir, "at_rays", used, {n, 6});
+	save(dir, "at_model_out", mout, {n, models.size(), 4}); save(dir, "at_model_idx", midx, {n, models.size(), 2});
+	save(dir, "at_scene_out", rout, {n, 14}); save(dir, "at_scene_idx", ridx, {n});
+	return 0;
+}
+
 // renderer::trace's miss branch with an environment map (renderer.cpp:443-449): core::equirectangular_proj
 // (core/utils.hpp:22-27) and image::image_texture::sample on a PNG loaded the way a caller of the library would
 // (image_texture::load(path, srgb)). Also one trace() per direction from far outside the scene, with the map set.
@@ -787,6 +831,7 @@ int main(int argc, char** argv) {
 		if (cmd == "vectors" && argc == 6) return cmd_vectors(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10));
 		if (cmd == "materials" && argc == 6) return cmd_materials(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10));
 		if (cmd == "materials_at" && argc == 5) return cmd_materials_at(argv[2], argv[3], argv[4]);
+		if (cmd == "intersect_at" && argc == 5) return cmd_intersect_at(argv[2], argv[3], argv[4]);
 		if (cmd == "envmap" && argc == 8) return cmd_envmap(argv[2], argv[3], atoi(argv[4]), argv[5], strtoull(argv[6], 0, 10), strtoull(argv[7], 0, 10));
 		if (cmd == "image" && argc == 6) return cmd_image(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10));
 		if (cmd == "trace" && argc == 7) return cmd_trace(argv[2], argv[3], strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10), atoi(argv[6]));
@@ -800,6 +845,6 @@ int main(int argc, char** argv) {
 		fprintf(stderr, "ref_harness: %s\n", e.what());
 		return 2;
 	}
-	fprintf(stderr, "usage: ref_harness scene|vectors|materials|envmap|image|trace|tri_scaled|pbr_edges|mean|render ... (see header comment)\n");
+	fprintf(stderr, "usage: ref_harness scene|vectors|materials|intersect_at|envmap|image|trace|tri_scaled|pbr_edges|mean|render ... (see header comment)\n");
 	return 1;
 }
