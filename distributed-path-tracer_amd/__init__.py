@@ -89,6 +89,14 @@ class DenoiseStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("iterations", C.c_uint32), ("workspace_bytes", C.c_uint64)]
 
 
+class AdaptiveCfg(C.Structure):
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("threshold", C.c_float)]
+
+
+class AdaptiveStats(C.Structure):
+    _fields_ = [("render", RenderStats), ("rounds", C.c_uint32), ("active_last", C.c_uint32), ("select_ms", C.c_double)]
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("pipeline", C.c_uint32), ("steps", C.c_uint32), ("classify_ms", C.c_double), ("traverse_ms", C.c_double), ("shade_ms", C.c_double),
                 ("fused_ms", C.c_double), ("fused_launches", C.c_uint32), ("pool_overflows", C.c_uint32), ("pool_pairs", C.c_uint64),
@@ -173,6 +181,9 @@ def lib():
         L.ptx_render_transparent.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.c_void_p, C.POINTER(RenderStats)]
         L.ptx_render_aov.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AovBuffers), C.POINTER(RenderStats)]
         L.ptx_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p, C.POINTER(DenoiseStats)]
+        L.ptx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AdaptiveCfg), C.c_void_p, C.c_void_p, C.POINTER(AdaptiveStats)]
+        L.ptx_adaptive_select.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.ptx_accum_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_intersect_batch.argtypes = [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(Hits)]
         L.ptx_tonemap_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ptx_pbr_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -190,6 +201,11 @@ def lib():
 def _check(rc):
     if rc != OK:
         raise PtxError(rc, lib().ptx_last_error().decode(errors="replace"))
+
+
+def _torch():
+    import torch
+    return torch
 
 
 def _ptr(x):
@@ -292,6 +308,32 @@ class Context:
         st = DenoiseStats()
         _check(lib().ptx_denoise(self.h, C.byref(cfg), _ptr(a), _ptr(b), C.byref(guides), _ptr(out), C.byref(st) if want_stats else None))
         return out, (dict(kernel_ms=st.kernel_ms, iterations=st.iterations, workspace_bytes=st.workspace_bytes) if want_stats else None)
+
+    def adaptive_select(self, a, b, threshold, done=None, want_list=True):
+        """ptx_adaptive_select: one decision of ptx_render_adaptive's loop (include/ptx.h has the rule). a, b: [h,w,4] float32 radiance SUMS of
+        the two halves; done: [h,w] uint8, read and updated in place (None = zeros); all numpy or all torch-on-GPU. Returns (done, the active
+        list — tile-local indices ly * w + lx in the specified order, uint32 numpy or int32 torch; None without want_list —, its length)."""
+        shape = tuple(a.shape)
+        if len(shape) != 3 or shape[2] != 4 or tuple(b.shape) != shape or (done is not None and tuple(done.shape) != shape[:2]):
+            raise ValueError("adaptive_select: a and b must be [h, w, 4] of one size and done [h, w]")
+        host = isinstance(a, np.ndarray)
+        if done is None:
+            done = np.zeros(shape[:2], np.uint8) if host else a.new_zeros(shape[:2], dtype=_torch().uint8)
+        pixels = None
+        if want_list:
+            pixels = np.empty(shape[0] * shape[1], np.uint32) if host else a.new_empty(shape[0] * shape[1], dtype=_torch().int32)
+        n = C.c_uint32()
+        _check(lib().ptx_adaptive_select(self.h, shape[1], shape[0], _ptr(a), _ptr(b), threshold, _ptr(done), _ptr(pixels), C.byref(n)))
+        return done, (pixels[:n.value] if want_list else None), n.value
+
+    def accum_mean(self, a, b=None, out=None):
+        """ptx_accum_mean: the MEANS (a + b) / (a.w + b.w) of radiance sums with per-pixel sample counts ([..., 4] float32), or a / a.w
+        without b; all numpy or all torch-on-GPU; out may be a or b (None = a new buffer). Write them with tonemap_encode(..., spp=1)."""
+        if out is None:
+            out = np.empty(a.shape, np.float32) if isinstance(a, np.ndarray) else a.new_empty(tuple(a.shape))
+        n = int(np.prod(tuple(a.shape)[:-1]))
+        _check(lib().ptx_accum_mean(self.h, _ptr(a), _ptr(b), n, _ptr(out)))
+        return out
 
     def close(self):
         if getattr(self, "h", None):
@@ -445,6 +487,25 @@ class Scene:
         stats = dict(rays=st.rays, samples=st.samples, passes=st.passes, kernel_ms=st.kernel_ms) if want_stats else None
         return albedo, normal_depth, stats
 
+    def render_adaptive(self, W, H, spp, bounces, min_spp=8, step_spp=0, threshold=0.1, a=None, b=None, env=(1.0, 1.0, 1.0), seed=0x5EED, tile=None,
+                        sample0=0, spp_per_pass=0, want_stats=True, integrator=INTEGRATOR_LIB, shard=None):
+        """ptx_render_adaptive: noise-driven per-pixel sample counts. `spp` is the cap; every pixel gets min_spp samples, then rounds of
+        step_spp (0 = min_spp) go to the pixels whose two halves still disagree by more than `threshold` (include/ptx.h has the rule).
+        ADDS radiance SUMS into the half-buffers a and b ([h,w,4] float32, numpy or torch-on-GPU, both of one kind; None = zeros): a
+        pixel's count is a[..., 3] + b[..., 3]. The frame: Context.accum_mean(a, b), then tonemap_encode(..., spp=1). Always synchronises.
+        Returns (a, b, stats dict or None)."""
+        x0, y0, w, h = tile if tile else (0, 0, W, H)
+        if a is None and b is None:
+            a, b = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+        cfg = RenderCfg(W, H, spp, bounces, (C.c_float * 3)(*env), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                        x0, y0, w, h, sample0, spp_per_pass, integrator, *((tuple(shard) + (0,))[:3] if shard else (0, 0, 0)))
+        acfg = AdaptiveCfg(min_spp, step_spp, threshold)
+        st = AdaptiveStats()
+        _check(lib().ptx_render_adaptive(self.h, C.byref(cfg), C.byref(acfg), _ptr(a), _ptr(b), C.byref(st) if want_stats else None))
+        stats = dict(rays=st.render.rays, samples=st.render.samples, passes=st.render.passes, kernel_ms=st.render.kernel_ms, rounds=st.rounds,
+                     active_last=st.active_last, select_ms=st.select_ms) if want_stats else None
+        return a, b, stats
+
     def set_environment(self, png_path, srgb=True):
         """renderer::environment = image_texture::load(png_path, srgb): the miss colour becomes map(direction) * environment_factor.
         None removes the map."""
@@ -528,6 +589,7 @@ class Renderer:
         self.last_stats = None
         self.last_claimed = None
         self.last_denoise_stats = None
+        self.last_adaptive_stats = None
 
     def load_gltf(self, path):
         self._scene = Scene.load_gltf(self._ctx, path, self.camera_index, self.sun_light_index)
@@ -585,6 +647,21 @@ class Renderer:
         alb, nd, _ = self._scene.render_aov(W, H, n, seed=self.seed, want_stats=False)
         out, self.last_denoise_stats = self._ctx.denoise(a, b, alb, nd, n // 2, n - n // 2, iterations, sigma_l, sigma_n, sigma_z, out=a)
         return out
+
+    def render_adaptive(self, threshold=0.1, min_spp=8, step_spp=0):
+        """The frame with noise-driven per-pixel sample counts (Scene.render_adaptive, sample_count = the cap), as MEANS [H,W,4] (write them
+        with tonemap_encode(..., spp=1)); the alpha channel is 1. `last_adaptive_stats` holds the stats; samples / (W * H) is the mean count."""
+        if self._scene is None:
+            raise PtxError(ERR_INVALID, "render_adaptive() before load_gltf()")
+        if self.transparent_background:
+            raise PtxError(ERR_UNSUPPORTED, "render_adaptive: the decision takes radiance sums, which transparent_background does not produce")
+        W, H = self.resolution
+        if self.environment != getattr(self, "_env_set", None):
+            self._scene.set_environment(self.environment)
+            self._env_set = self.environment
+        a, b, self.last_adaptive_stats = self._scene.render_adaptive(W, H, self.sample_count, self.bounce_count, min_spp, step_spp, threshold,
+                                                                     env=self.environment_factor, seed=self.seed)
+        return self._ctx.accum_mean(a, b, out=a)
 
     def render(self):
         W, H = self.resolution

@@ -212,4 +212,21 @@ hipError_t launch_denoise_prefilter(const float4* in, const float4* guide, uint3
 hipError_t launch_denoise_atrous(const float4* in, const float4* guide, const float4* remod, uint32_t W, uint32_t H, uint32_t step, float sigma_l, float sigma_n, float sigma_z,
                                  bool last, bool tiled, float4* out, hipStream_t stream);
 
+// Noise-driven per-pixel sample counts (adaptive.hip; ptx_render_adaptive, ptx_adaptive_select, ptx_accum_mean). A TILE is 32 x 32 pixels of the
+// rectangle, anchored at its origin (one workgroup), a BLOCK 8 x 8 (one wave-iteration): 16 blocks per tile, row-major.
+constexpr uint32_t kAdTile = 32, kAdBlocksPerTile = 16, kAdMaxSide = 16384;   // 2^18 tiles at most: one workgroup scans their counts
+struct AdaptiveBuffers {   // device workspace of one decision on a w x h rectangle
+	uint8_t* noisy;                  // [w * h] 1 = the two halves disagree by more than the threshold
+	unsigned long long* block_mask;  // [tiles][16] active lanes of the block (lane = ry * 8 + rx)
+	uint32_t* block_off;             // [tiles][16] active pixels of the tile before the block
+	uint32_t* tile_count;            // [tiles]
+	uint32_t* tile_off;              // [tiles] active pixels before the tile
+	uint32_t* n_active;              // one word: the list's length
+};
+// one decision: a, b [w * h] radiance sums; `done` [w * h] in/out; `pixels` [w * h] receives the active list (nullptr: none is written)
+hipError_t launch_adaptive_select(const float4* a, const float4* b, uint32_t w, uint32_t h, float threshold, const AdaptiveBuffers& B, uint8_t* done, uint32_t* pixels,
+                                  hipStream_t stream);
+// out = (a + b) / (a.w + b.w) for all four channels, or a / a.w when b == nullptr; out may be a or b
+hipError_t launch_accum_mean(const float4* a, const float4* b, size_t n_pixels, float4* out, hipStream_t stream);
+
 }  // namespace ptx

@@ -84,6 +84,10 @@ struct ptx_ctx {
 	DevBuf queues, sample_rad, counters, spill, stage_a, stage_b, pixel_list, srgb_thr;
 	DevBuf aov;   // workspace of ptx_render_aov: the streams, hits and per-sample records of one pass
 	DevBuf denoise;   // workspace of ptx_denoise: four float4 state buffers per pixel, and the staging of host buffers
+	// workspace of ptx_render_adaptive / ptx_adaptive_select: the decision's buffers (noisy bytes, block masks and offsets, tile counts and
+	// offsets, the count word), the loop's `done` bytes and active list, and the staging of host buffers
+	DevBuf adaptive, adaptive_state, adaptive_stage;
+	hipEvent_t adaptive_ev[2] = {nullptr, nullptr};   // around the decision kernels (select_ms)
 	// workspace of the queue-based pipeline (wavefront.hip): ptx_render and ptx_intersect_batch run it on the context's stream
 	struct WfSet {
 		DevBuf qent, pair_hit, seg, first, mask, ctl, spill, stream_buf, flow;
@@ -371,6 +375,8 @@ static void ctx_release(ptx_ctx* c) {
 	for (hipEvent_t ev : c->events) (void)hipEventDestroy(ev);
 	for (hipEvent_t ev : c->step_events) (void)hipEventDestroy(ev);
 	c->queues.release(); c->spill.release(); c->sample_rad.release(); c->counters.release(); c->stage_a.release(); c->stage_b.release(); c->pixel_list.release(); c->srgb_thr.release(); c->aov.release(); c->denoise.release();
+	c->adaptive.release(); c->adaptive_state.release(); c->adaptive_stage.release();
+	for (hipEvent_t ev : c->adaptive_ev) if (ev) (void)hipEventDestroy(ev);
 	ptx_ctx::WfSet& w = c->wf;
 	for (DevBuf* b : {&w.qent, &w.pair_hit, &w.seg, &w.first, &w.mask, &w.ctl, &w.spill, &w.stream_buf, &w.flow}) b->release();
 	if (w.flow_host) { (void)hipHostFree(w.flow_host); w.flow_host = nullptr; }
@@ -978,26 +984,39 @@ int render_stats(ptx_ctx* c, uint64_t samples, uint32_t n_pass, bool wavefront, 
 	return PTX_OK;
 }
 
-// ptx_render (claimed == nullptr: `accum` receives sums) and ptx_render_transparent (`accum` and `claimed` are the reference's per-pixel
-// blend state, advanced through the samples in order) — the same passes, a different resolve kernel behind each
-int render_frame(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, uint8_t* claimed, ptx_render_stats* stats) {
+// what every render entry point refuses in a cfg, decided before any device work; -> the rectangle
+int render_rect(const ptx_render_cfg* cfg, uint32_t& x0, uint32_t& y0, uint32_t& w, uint32_t& h) {
 	if (!cfg->W || !cfg->H) return set_err(PTX_ERR_INVALID, "ptx_render: W and H must be > 0");   // bounces = 0 is legal: a black frame (renderer.cpp:438-439)
-	uint32_t x0 = cfg->x0, y0 = cfg->y0, w = cfg->w, h = cfg->h;
+	x0 = cfg->x0; y0 = cfg->y0; w = cfg->w; h = cfg->h;
 	if (w == 0 && h == 0) { x0 = 0; y0 = 0; w = cfg->W; h = cfg->H; }
 	if (!w || !h || (uint64_t)x0 + w > cfg->W || (uint64_t)y0 + h > cfg->H) return set_err(PTX_ERR_INVALID, "ptx_render: tile outside the image");
 	if (cfg->bounces > 0xFFFFu) return set_err(PTX_ERR_INVALID, "ptx_render: bounces > 65535");
 	if (cfg->integrator > PTX_INTEGRATOR_WORKER) return set_err(PTX_ERR_INVALID, "ptx_render: unknown integrator");
 	if (cfg->shard_count > 1 && cfg->shard_index >= cfg->shard_count) return set_err(PTX_ERR_INVALID, "ptx_render: shard_index >= shard_count");
+	if ((uint64_t)w * h > 0x7FFFFFFFull) return set_err(PTX_ERR_INVALID, "ptx_render: tile too large");
+	return PTX_OK;
+}
+
+// An explicit device list of tile-local pixel indices for a pass to render in place of pixel_list()'s (ptx_render_adaptive's active list)
+struct PixelSubset {
+	const uint32_t* d_pixels;
+	uint32_t n_pixels;
+};
+
+// The caller holds the context's mutex and has set its device.
+int render_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, uint8_t* claimed, ptx_render_stats* stats, const PixelSubset* subset) {
+	uint32_t x0, y0, w, h;
+	if (const int rc = render_rect(cfg, x0, y0, w, h); rc != PTX_OK) return rc;
 	ptx_ctx* c = sc->ctx;
-	std::lock_guard<std::mutex> lk(c->mu);
-	HIP_TRY(hipSetDevice(c->device));
 	const uint64_t rect_pixels = (uint64_t)w * h;
-	if (rect_pixels > 0x7FFFFFFFull) return set_err(PTX_ERR_INVALID, "ptx_render: tile too large");
 	if (stats) *stats = ptx_render_stats{};
 	if (cfg->spp == 0) return PTX_OK;
 	uint64_t n_pixels = 0;
 	const uint32_t* d_pixels = nullptr;
-	if (const int rc = pixel_list(c, sc, cfg, x0, y0, w, h, n_pixels, d_pixels); rc != PTX_OK) return rc;
+	if (subset) {
+		n_pixels = subset->n_pixels;
+		d_pixels = subset->d_pixels;
+	} else if (const int rc = pixel_list(c, sc, cfg, x0, y0, w, h, n_pixels, d_pixels); rc != PTX_OK) return rc;
 	if (n_pixels == 0) return PTX_OK;   // no tile of this shard meets the rectangle
 	const uint32_t pass_spp = pass_size(cfg, n_pixels);
 	if (pass_spp == 0) return set_err(PTX_ERR_INVALID, "ptx_render: tile too large for one pass");
@@ -1084,6 +1103,17 @@ int render_frame(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, uint8_t
 	if (stats || !dev_accum) HIP_TRY(hipStreamSynchronize(c->stream));
 	if (stats) return render_stats(c, (uint64_t)cfg->spp * n_pixels, n_pass, wavefront, plan, clk, wf_rays, stats);
 	return PTX_OK;
+}
+
+// ptx_render (claimed == nullptr: `accum` receives sums) and ptx_render_transparent (`accum` and `claimed` are the reference's per-pixel
+// blend state, advanced through the samples in order) — the same passes, a different resolve kernel behind each
+int render_frame(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, uint8_t* claimed, ptx_render_stats* stats) {
+	uint32_t x0, y0, w, h;
+	if (const int rc = render_rect(cfg, x0, y0, w, h); rc != PTX_OK) return rc;
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	return render_frame_locked(sc, cfg, accum, claimed, stats, nullptr);
 }
 
 }  // namespace
@@ -1418,6 +1448,170 @@ int ptx_denoise(ptx_ctx* c, const ptx_denoise_cfg* cfg, const float* accum_a, co
 		stats->kernel_ms = t;
 		stats->iterations = iterations;
 		stats->workspace_bytes = ws_bytes;
+	}
+	return PTX_OK;
+}
+
+namespace {
+
+// One decision on device buffers (adaptive.hip), its count read back: the stream is synchronised. The caller holds the context's mutex.
+// select_ms: nullptr, or where the HIP-event time of the decision kernels is added.
+int adaptive_decide_locked(ptx_ctx* c, uint32_t w, uint32_t h, const float4* d_a, const float4* d_b, float threshold, uint8_t* d_done, uint32_t* d_pixels, uint32_t& n_active,
+                           double* select_ms) {
+	const size_t n = (size_t)w * h, tiles = (size_t)((w + kAdTile - 1) / kAdTile) * ((h + kAdTile - 1) / kAdTile), blocks = tiles * kAdBlocksPerTile;
+	const size_t o_mask = pad16(n), o_boff = o_mask + blocks * 8, o_tcnt = o_boff + blocks * 4, o_toff = o_tcnt + pad16(tiles * 4), o_cnt = o_toff + pad16(tiles * 4);
+	HIP_TRY(c->adaptive.ensure(o_cnt + 16));
+	char* const ws = (char*)c->adaptive.p;
+	const AdaptiveBuffers B{(uint8_t*)ws, (unsigned long long*)(ws + o_mask), (uint32_t*)(ws + o_boff), (uint32_t*)(ws + o_tcnt), (uint32_t*)(ws + o_toff), (uint32_t*)(ws + o_cnt)};
+	if (select_ms)
+		for (hipEvent_t& ev : c->adaptive_ev)
+			if (!ev) HIP_TRY(hipEventCreate(&ev));
+	if (select_ms) HIP_TRY(hipEventRecord(c->adaptive_ev[0], c->stream));
+	HIP_TRY(launch_adaptive_select(d_a, d_b, w, h, threshold, B, d_done, d_pixels, c->stream));
+	if (select_ms) HIP_TRY(hipEventRecord(c->adaptive_ev[1], c->stream));
+	HIP_TRY(hipMemcpyAsync(&n_active, B.n_active, 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (select_ms) {
+		float t = 0;
+		HIP_TRY(hipEventElapsedTime(&t, c->adaptive_ev[0], c->adaptive_ev[1]));
+		*select_ms += t;
+	}
+	return PTX_OK;
+}
+
+}  // namespace
+
+int ptx_adaptive_select(ptx_ctx* c, uint32_t w, uint32_t h, const float* accum_a, const float* accum_b, float threshold, uint8_t* done, uint32_t* pixels, uint32_t* n_active) {
+	// every refusal below is decided before any device work
+	if (!c || !accum_a || !accum_b || !done || !n_active) return set_err(PTX_ERR_INVALID, "ptx_adaptive_select: NULL argument");
+	if (!w || !h || w > kAdMaxSide || h > kAdMaxSide) return set_err(PTX_ERR_INVALID, "ptx_adaptive_select: w and h must be in 1 .. 16384");
+	if (!(threshold >= 0.0f)) return set_err(PTX_ERR_INVALID, "ptx_adaptive_select: threshold is negative or NaN");
+	const bool dev = is_device_ptr(accum_a);
+	if (is_device_ptr(accum_b) != dev || is_device_ptr(done) != dev || (pixels && is_device_ptr(pixels) != dev))
+		return set_err(PTX_ERR_INVALID, "ptx_adaptive_select: the buffers must all be device or all be host memory");
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t n = (size_t)w * h, bytes = n * sizeof(float4);
+	const float4 *d_a = (const float4*)accum_a, *d_b = (const float4*)accum_b;
+	uint8_t* d_done = done;
+	uint32_t* d_pixels = pixels;
+	if (!dev) {
+		HIP_TRY(c->adaptive_stage.ensure(2 * bytes));
+		HIP_TRY(c->adaptive_state.ensure(n * 4 + pad16(n)));
+		d_a = (const float4*)c->adaptive_stage.p; d_b = d_a + n;
+		if (pixels) d_pixels = (uint32_t*)c->adaptive_state.p;
+		d_done = (uint8_t*)c->adaptive_state.p + n * 4;
+		HIP_TRY(hipMemcpyAsync((void*)d_a, accum_a, bytes, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync((void*)d_b, accum_b, bytes, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync(d_done, done, n, hipMemcpyHostToDevice, c->stream));
+	}
+	uint32_t count = 0;
+	if (const int rc = adaptive_decide_locked(c, w, h, d_a, d_b, threshold, d_done, d_pixels, count, nullptr); rc != PTX_OK) return rc;
+	if (!dev) {
+		HIP_TRY(hipMemcpyAsync(done, d_done, n, hipMemcpyDeviceToHost, c->stream));
+		if (pixels && count) HIP_TRY(hipMemcpyAsync(pixels, d_pixels, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+	}
+	*n_active = count;
+	return PTX_OK;
+}
+
+int ptx_accum_mean(ptx_ctx* c, const float* accum_a, const float* accum_b, size_t n_pixels, float* out_rgba) {
+	if (!c || !accum_a || !out_rgba) return set_err(PTX_ERR_INVALID, "ptx_accum_mean: NULL argument");
+	if (n_pixels > (size_t)0x7FFFFFFF) return set_err(PTX_ERR_INVALID, "ptx_accum_mean: buffer too large");
+	const bool dev = is_device_ptr(accum_a);
+	if ((accum_b && is_device_ptr(accum_b) != dev) || is_device_ptr(out_rgba) != dev)
+		return set_err(PTX_ERR_INVALID, "ptx_accum_mean: the buffers must all be device or all be host memory");
+	if (n_pixels == 0) return PTX_OK;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t bytes = n_pixels * sizeof(float4);
+	const float4 *d_a = (const float4*)accum_a, *d_b = (const float4*)accum_b;
+	float4* d_out = (float4*)out_rgba;
+	if (!dev) {
+		HIP_TRY(c->adaptive_stage.ensure(2 * bytes));
+		float4* const st = (float4*)c->adaptive_stage.p;
+		HIP_TRY(hipMemcpyAsync(st, accum_a, bytes, hipMemcpyHostToDevice, c->stream));
+		if (accum_b) HIP_TRY(hipMemcpyAsync(st + n_pixels, accum_b, bytes, hipMemcpyHostToDevice, c->stream));
+		d_a = st; d_b = accum_b ? st + n_pixels : nullptr; d_out = st;
+	}
+	HIP_TRY(launch_accum_mean(d_a, d_b, n_pixels, d_out, c->stream));
+	if (!dev) {
+		HIP_TRY(hipMemcpyAsync(out_rgba, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+	}
+	return PTX_OK;
+}
+
+int ptx_render_adaptive(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_adaptive_cfg* acfg, float* accum_a, float* accum_b, ptx_adaptive_stats* stats) {
+	// every refusal below is decided before any device work
+	if (!sc || !cfg || !acfg || !accum_a || !accum_b) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: NULL argument");
+	if (acfg->min_spp < 2 || (acfg->min_spp & 1u)) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: min_spp must be even and >= 2 (each round is split into two halves)");
+	if (acfg->step_spp & 1u) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: step_spp must be even (0 = min_spp)");
+	if ((cfg->spp & 1u) || cfg->spp < acfg->min_spp) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: spp (the cap) must be even and >= min_spp");
+	const uint32_t step = acfg->step_spp ? acfg->step_spp : acfg->min_spp;
+	if ((uint64_t)1 + ((uint64_t)(cfg->spp - acfg->min_spp) + step - 1) / step > 4096) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: more than 4096 rounds");
+	if (!(acfg->threshold >= 0.0f)) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: threshold is negative or NaN");
+	if ((uint64_t)cfg->sample0 + cfg->spp > 0xFFFFFFFFull) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: sample0 + spp overflows");
+	uint32_t x0, y0, w, h;
+	if (const int rc = render_rect(cfg, x0, y0, w, h); rc != PTX_OK) return rc;
+	if (w > kAdMaxSide || h > kAdMaxSide) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: the rectangle's sides must be at most 16384");
+	if (cfg->shard_count > 1)
+		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_adaptive: shard_count > 1 is not supported (the 3 x 3 block of the decision would need other shards' pixels); "
+		                                    "split a frame over GPUs by rectangles instead");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_adaptive: scene was created without a GPU context (no CPU path exists)");
+	const bool dev = is_device_ptr(accum_a);
+	if (is_device_ptr(accum_b) != dev) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: accum_a and accum_b must both be device or both be host memory");
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	if (stats) *stats = ptx_adaptive_stats{};
+
+	const size_t n = (size_t)w * h, bytes = n * sizeof(float4);
+	float4 *d_a = (float4*)accum_a, *d_b = (float4*)accum_b;
+	if (!dev) {   // staged once for the whole call
+		HIP_TRY(c->adaptive_stage.ensure(2 * bytes));
+		d_a = (float4*)c->adaptive_stage.p; d_b = d_a + n;
+		HIP_TRY(hipMemcpyAsync(d_a, accum_a, bytes, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync(d_b, accum_b, bytes, hipMemcpyHostToDevice, c->stream));
+	}
+	HIP_TRY(c->adaptive_state.ensure(n * 4 + pad16(n)));
+	uint32_t* const d_list = (uint32_t*)c->adaptive_state.p;
+	uint8_t* const d_done = (uint8_t*)c->adaptive_state.p + n * 4;
+	HIP_TRY(hipMemsetAsync(d_done, 0, n, c->stream));
+
+	ptx_render_cfg half = *cfg;
+	half.x0 = x0; half.y0 = y0; half.w = w; half.h = h;
+	PixelSubset active{d_list, 0};
+	uint32_t given = 0, rounds = 0, n_active = 0;
+	double select_ms = 0;
+	while (given < cfg->spp) {
+		const uint32_t k = rounds == 0 ? acfg->min_spp : std::min(step, cfg->spp - given);
+		float4* const target[2] = {d_a, d_b};
+		for (uint32_t part = 0; part < 2; part++) {   // the first half of the round's samples into A, the second into B
+			half.sample0 = cfg->sample0 + given + part * (k / 2);
+			half.spp = k / 2;
+			ptx_render_stats st{};
+			if (const int rc = render_frame_locked(sc, &half, (float*)target[part], nullptr, stats ? &st : nullptr, rounds == 0 ? nullptr : &active); rc != PTX_OK) return rc;
+			if (stats) {
+				stats->render.rays += st.rays; stats->render.samples += st.samples; stats->render.passes += st.passes; stats->render.kernel_ms += st.kernel_ms;
+			}
+		}
+		given += k;
+		rounds++;
+		if (const int rc = adaptive_decide_locked(c, w, h, d_a, d_b, acfg->threshold, d_done, d_list, n_active, stats ? &select_ms : nullptr); rc != PTX_OK) return rc;
+		active.n_pixels = n_active;
+		if (n_active == 0) break;
+	}
+	if (!dev) {
+		HIP_TRY(hipMemcpyAsync(accum_a, d_a, bytes, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipMemcpyAsync(accum_b, d_b, bytes, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+	}
+	if (stats) {
+		stats->rounds = rounds;
+		stats->active_last = n_active;
+		stats->select_ms = select_ms;
 	}
 	return PTX_OK;
 }

@@ -30,6 +30,10 @@ public:
 	uint32_t sun_light_index = 0;
 	uint8_t visualize_kd_tree_depth = 0;   // not built: mesh.cpp:316-318 colours each KD node by its heap address, nothing reproducible to mirror
 	uint64_t seed = 0x5EED;                // key of the counter-based RNG (the reference seeds from random_device)
+	// render_adaptive (no counterpart in the reference): the threshold of the stopping rule, the samples every pixel gets first and the samples
+	// per further round (0 = adaptive_min); sample_count is the cap
+	float adaptive_threshold = 0.1f;
+	uint32_t adaptive_min = 8, adaptive_step = 0;
 
 	explicit renderer(int device = 0) { check(ptx_ctx_create(device, &ctx_)); }
 	renderer(const renderer&) = delete;
@@ -109,6 +113,27 @@ public:
 		ptx_denoise_cfg d = filter ? *filter : ptx_denoise_cfg{};   // iterations and sigmas; the rest is set here
 		d.W = c.W; d.H = c.H; d.spp_a = sample_count / 2; d.spp_b = sample_count - d.spp_a;
 		check(ptx_denoise(ctx_, &d, a.data(), b.data(), &g, a.data(), stats));
+		return a;
+	}
+
+	// The frame with noise-driven per-pixel sample counts (ptx_render_adaptive; sample_count is the cap): returns the MEANS [H][W][4] (write them
+	// with ptx_tonemap_encode(..., spp = 1)). stats optional: render.samples / (W * H) is the mean count
+	std::vector<float> render_adaptive(ptx_adaptive_stats* stats = nullptr) const {
+		if (!scene_) throw std::runtime_error("render_adaptive() before load_gltf()");
+		if (transparent_background) throw std::runtime_error("render_adaptive: the decision takes radiance sums, which transparent_background does not produce");
+		if (environment.string() != env_set_) {
+			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
+			env_set_ = environment.string();
+		}
+		ptx_render_cfg c{};
+		c.W = resolution.x; c.H = resolution.y; c.spp = sample_count; c.bounces = bounce_count;
+		for (int k = 0; k < 3; k++) c.env[k] = environment_factor[k];
+		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
+		const ptx_adaptive_cfg ac{adaptive_min, adaptive_step, adaptive_threshold};
+		const size_t floats = (size_t)c.W * c.H * 4;
+		std::vector<float> a(floats, 0.f), b(floats, 0.f);
+		check(ptx_render_adaptive(scene_, &c, &ac, a.data(), b.data(), stats));
+		check(ptx_accum_mean(ctx_, a.data(), b.data(), floats / 4, a.data()));
 		return a;
 	}
 

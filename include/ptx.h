@@ -283,6 +283,58 @@ typedef struct ptx_denoise_stats {
 int ptx_denoise(ptx_ctx* ctx, const ptx_denoise_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, float* out_rgba,
                 ptx_denoise_stats* stats /* NULL ok */);
 
+/* Noise-driven per-pixel sample counts (no counterpart in the reference, which gives every pixel sample_count samples): a frame is rendered in
+ * rounds, and a pixel whose two half-frames already agree, with all its neighbours, gets no further samples. On open, sun-lit scenes most
+ * pixels stop at the first round; on a scene whose pixels are all about equally noisy (the Cornell box: there is no next-event estimation
+ * towards its area light) nothing is gained over a uniform frame of the same mean count (DESIGN.md has the tables).
+ * There are two half-buffers, A and B: accum_a, accum_b [h][w][4] float32 radiance SUMS of the rectangle, in ptx_render's accum format (w counts
+ * the samples: the sums carry their own per-pixel sample count). This text is the specification:
+ *   Rounds. cfg->spp is the cap. Round 0 gives every pixel of the rectangle the samples [sample0, sample0 + min_spp): the first half is ADDED to
+ *   A, the second half to B. Round r >= 1 gives every still-active pixel the next k = min(step_spp, samples left to the cap) samples, split the
+ *   same way. Each half is added exactly as ptx_render adds it (in sample order), so a pixel with n samples holds, bit for bit, what ptx_render
+ *   calls of the same half ranges leave in it. After each round comes one decision; the loop ends when no pixel is active or the cap is reached.
+ *   Decision (IEEE binary32, every operation rounded on its own in the parenthesisation written here; max(a, b) returns the other operand when
+ *   one is NaN):
+ *     ma.c = a.c / a.w and mb.c = b.c / b.w for c = r, g, b;
+ *     d = (|ma.r - mb.r| + |ma.g - mb.g|) + |ma.b - mb.b|;   m = ((ma.r + mb.r) + (ma.g + mb.g)) + (ma.b + mb.b);
+ *     e2 = ((d * d) * 0.25f) / max(m * 0.5f, 0.01f);   noisy_p = !(e2 <= threshold * threshold) — a NaN (a zero count, a non-finite sum) is
+ *     noisy: a pixel is never stopped on garbage;
+ *     active_p = !done_p && (some q in the 3 x 3 block around p, clipped to the RECTANGLE, is noisy);   done_p |= !active_p.
+ *   The latch means that a pixel that stopped never restarts: its samples are always a prefix [sample0, sample0 + n_p), n_p = a.w + b.w.
+ *   Active list. The active pixels as tile-local indices ly * w + lx, in this order: the 32 x 32 tiles of the rectangle, row-major, anchored at
+ *   the rectangle's origin; inside a tile its 8 x 8 blocks, row-major; inside a block its rows. The list is a function of the mask alone.
+ * ptx_adaptive_cfg: min_spp even and >= 2; step_spp even, 0 = min_spp; threshold 0 is legal (only pixels with d == 0 stop), +inf is legal
+ * (everything but NaN pixels stops after round 0).
+ * ptx_adaptive_stats: render = sums over all rounds' render calls (render.samples = the sum of the per-pixel counts); rounds = rounds rendered;
+ * active_last = pixels still active after the last decision (at the cap: those that would have gone on); select_ms = HIP-event time of the
+ * decision kernels.
+ * The two buffers are both device or both host memory; host buffers are staged once for the whole call. The call ALWAYS synchronises: once per
+ * round for the 4-byte active count (with stats, once more per render call). Tile rectangles (at most 16384 x 16384) and spp_per_pass work as
+ * in ptx_render, and both integrators are accepted. A rectangle is decided on its own: the 3 x 3 block is clipped to it, so along the cuts a
+ * frame rendered in rectangles may stop pixels that the whole frame's decision keeps.
+ * Image write: ptx_accum_mean, then ptx_tonemap_encode(..., spp = 1, ...).
+ * Out of scope: ptx_render_transparent's blend (a recurrence, not a sum), ptx_denoise on the result (it takes one count per buffer, not one per
+ * pixel), and the multi-process driver (multigpu.py).
+ * Refusals, all decided before any device work: PTX_ERR_INVALID for NULL arguments, an odd or zero min_spp, an odd step_spp, cfg->spp odd or
+ * below min_spp, more than 4096 rounds, a negative or NaN threshold, pointers of mixed kinds, and whatever ptx_render refuses in cfg;
+ * PTX_ERR_UNSUPPORTED for shard_count > 1 (the 3 x 3 block would need other shards' pixels: split a frame over GPUs by rectangles instead);
+ * PTX_ERR_NO_DEVICE for a host-only scene. */
+typedef struct ptx_adaptive_cfg { uint32_t min_spp, step_spp; float threshold; } ptx_adaptive_cfg;
+typedef struct ptx_adaptive_stats { ptx_render_stats render; uint32_t rounds, active_last; double select_ms; } ptx_adaptive_stats;
+int ptx_render_adaptive(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_adaptive_cfg* acfg, float* accum_a, float* accum_b,
+                        ptx_adaptive_stats* stats /* NULL ok */);
+/* One decision of the specification above on the caller's buffers — the kernels ptx_render_adaptive's loop runs; for callers that drive their
+ * own loop. accum_a, accum_b [h][w][4]; done [h][w] (one byte per pixel, 0 / 1) is read and updated; pixels [w * h] receives the active list
+ * (NULL: none is written); the four are all device or all host memory. *n_active (host memory) receives the list's length: the call
+ * synchronises. PTX_ERR_INVALID for a NULL ctx, buffer, done or n_active, w or h of 0 or above 16384, a negative or NaN threshold, pointers of
+ * mixed kinds. */
+int ptx_adaptive_select(ptx_ctx* ctx, uint32_t w, uint32_t h, const float* accum_a, const float* accum_b, float threshold,
+                        uint8_t* done /* in/out [h][w] */, uint32_t* pixels /* out [w*h], NULL ok */, uint32_t* n_active);
+/* out.c = (a.c + b.c) / (a.w + b.w) for all four channels (IEEE binary32, each operation rounded on its own); with accum_b == NULL
+ * out.c = a.c / a.w. A pixel of zero count gives NaNs. out_rgba [n_pixels][4] may be accum_a or accum_b itself; all pointers device or all
+ * host. PTX_ERR_INVALID for a NULL ctx, accum_a or out_rgba, n_pixels above 2^31 - 1, or pointers of mixed kinds. */
+int ptx_accum_mean(ptx_ctx* ctx, const float* accum_a, const float* accum_b /* NULL ok */, size_t n_pixels, float* out_rgba);
+
 /* Measurement aid (no counterpart in the reference): where the time of the last ptx_render that was given a stats pointer went.
  * Scenes whose geometry fits the LDS or whose models have few surfaces run ONE fused kernel per pass (pipeline 0: fused_ms);
  * many-surface scenes in global memory run the queue-based pipeline (pipeline 1) — per step of a slab of paths a classify, a

@@ -1,0 +1,636 @@
+"""ptx_render_adaptive, ptx_adaptive_select, ptx_accum_mean: noise-driven per-pixel sample counts.
+
+The stopping rule is its own specification (include/ptx.h). It is restated here in float32 numpy (`restate_select`, `restate_mean`): every
+operation is a float32 numpy operation in the written parenthesisation, `np.fmax` is the max that returns the other operand when one is NaN.
+Nothing on this path goes through libm, so the product is held to BITWISE equality with the restatement: the mask, the list, the count.
+
+The renderer's loop is checked against the product's own ptx_render: a pixel that received n samples must hold, in A and in B, exactly what
+ptx_render calls of the same half ranges on the whole frame leave in it (`_snapshots`), and the per-pixel counts must be those the restated
+decision gives when it is replayed on those snapshots (`_replay`).
+
+Common shape: 96 x 54, 4 bounces, seed 0x5EED, 8 samples first, 8 per round.
+"""
+import ctypes as C
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+from conftest import CORNELL, ROOT, oracle_from_dict, product_from_dict
+from test_unit_limits import clean_env  # noqa: F401  (a fixture)
+
+W, H, B, SEED, MIN, STEP = 96, 54, 4, 0x5EED, 8, 8
+f32 = np.float32
+INF = float("inf")
+
+
+def _proc():
+    return importlib.import_module("distributed-path-tracer_amd.procedural")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _same(got, want, what):
+    np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=what)
+
+
+# ---------------------------------------------------------------------------- the restatement
+def restate_noisy(a, b, thr):
+    """[h,w] bool: the two halves' means disagree by more than thr (NaN: noisy)."""
+    a, b = np.asarray(a, f32), np.asarray(b, f32)
+    with np.errstate(all="ignore"):
+        ma = [a[..., c] / a[..., 3] for c in range(3)]
+        mb = [b[..., c] / b[..., 3] for c in range(3)]
+        d = (np.abs(ma[0] - mb[0]) + np.abs(ma[1] - mb[1])) + np.abs(ma[2] - mb[2])
+        m = ((ma[0] + mb[0]) + (ma[1] + mb[1])) + (ma[2] + mb[2])
+        e2 = ((d * d) * f32(0.25)) / np.fmax(m * f32(0.5), f32(0.01))
+        assert e2.dtype == np.float32
+        return ~(e2 <= f32(thr) * f32(thr))
+
+
+def restate_order(h, w):
+    """The tile-local indices ly * w + lx of an h x w rectangle in list order: 32 x 32 tiles row-major, anchored at the rectangle's origin;
+    inside a tile its 8 x 8 blocks row-major; inside a block rows."""
+    out = []
+    for ty in range(0, h, 32):
+        for tx in range(0, w, 32):
+            for by in range(ty, min(ty + 32, h), 8):
+                for bx in range(tx, min(tx + 32, w), 8):
+                    ys, xs = np.arange(by, min(by + 8, h)), np.arange(bx, min(bx + 8, w))
+                    out.append((ys[:, None] * w + xs[None, :]).ravel())
+    return np.concatenate(out).astype(np.uint32)
+
+
+def restate_select(a, b, done, thr):
+    """One decision. -> (done' [h,w] uint8, the active list uint32). active = !done && (a noisy pixel in the 3 x 3 block clipped to the
+    rectangle); done' = done | !active."""
+    noisy = restate_noisy(a, b, thr)
+    h, w = noisy.shape
+    pad = np.zeros((h + 2, w + 2), bool)
+    pad[1:-1, 1:-1] = noisy
+    near = np.zeros((h, w), bool)
+    for dy in range(3):
+        for dx in range(3):
+            near |= pad[dy:dy + h, dx:dx + w]
+    active = (np.asarray(done) == 0) & near
+    order = restate_order(h, w)
+    return np.where(active, 0, 1).astype(np.uint8), order[active.ravel()[order]]
+
+
+def restate_mean(a, b=None):
+    a = np.asarray(a, f32)
+    with np.errstate(all="ignore"):
+        if b is None:
+            return (a / a[..., 3:4]).astype(f32)
+        b = np.asarray(b, f32)
+        return ((a + b) / (a[..., 3:4] + b[..., 3:4])).astype(f32)
+
+
+def _round_sizes(cap, min_spp=MIN, step=STEP):
+    out, given = [], 0
+    while given < cap:
+        out.append(min_spp if not given else min(step, cap - given))
+        given += out[-1]
+    return out
+
+
+def _replay(snaps, thr):
+    """The loop on full-rectangle snapshots [(A_r, B_r)] of the rounds: -> (a, b, rounds, active_last). A pixel active after round r - 1 takes
+    round r's snapshot; a stopped one keeps what it has."""
+    a, b = snaps[0][0].copy(), snaps[0][1].copy()
+    done = np.zeros(a.shape[:2], np.uint8)
+    for r in range(len(snaps)):
+        if r:
+            act = done == 0
+            a[act], b[act] = snaps[r][0][act], snaps[r][1][act]
+        done, pix = restate_select(a, b, done, thr)
+        assert len(pix) == int((done == 0).sum())
+        if not len(pix):
+            break
+    return a, b, r + 1, len(pix)
+
+
+# ---------------------------------------------------------------------------- CPU: the restatement itself
+def _flat(h, w, rgb=(2.0, 1.0, 4.0), n=4.0):
+    return np.broadcast_to(np.array(rgb + (n,), f32), (h, w, 4)).copy()
+
+
+def test_equal_halves_stop_at_threshold_zero():
+    a = _flat(9, 11)
+    b = _flat(9, 11, (1.0, 0.5, 2.0), 2.0)   # the same means from another count
+    done, pix = restate_select(a, b, np.zeros((9, 11), np.uint8), 0.0)
+    assert done.all() and len(pix) == 0
+    b[4, 5, 0] = np.nextafter(f32(1.0), f32(2.0))   # one ulp of difference is noise at threshold 0 ...
+    done, pix = restate_select(a, b, np.zeros((9, 11), np.uint8), 0.0)
+    assert int((done == 0).sum()) == 9
+    done, pix = restate_select(a, b, np.zeros((9, 11), np.uint8), 0.1)   # ... and none at 0.1
+    assert done.all()
+
+
+@pytest.mark.parametrize("kind", ["nan", "inf", "zero_count"])
+def test_garbage_keeps_exactly_its_block_active_and_the_block_is_clipped(kind):
+    for (y, x), n_active in (((4, 5), 9), ((0, 0), 4), ((8, 5), 6), ((3, 10), 6)):
+        a, b = _flat(9, 11), _flat(9, 11)
+        a[y, x] = {"nan": (np.nan, 1, 1, 4), "inf": (np.inf, 1, 1, 4), "zero_count": (0, 0, 0, 0)}[kind]
+        for thr in (0.0, 0.1, INF):
+            done, pix = restate_select(a, b, np.zeros((9, 11), np.uint8), thr)
+            act = done == 0
+            assert int(act.sum()) == n_active == len(pix)
+            ys, xs = np.nonzero(act)
+            assert (np.abs(ys - y) <= 1).all() and (np.abs(xs - x) <= 1).all()
+
+
+def test_latch_a_stopped_pixel_never_restarts():
+    a, b = _flat(9, 11), _flat(9, 11)
+    a[4, 5, 1] = 3.0
+    entry = np.zeros((9, 11), np.uint8)
+    entry[3:5, 4:6] = 1
+    done, pix = restate_select(a, b, entry, 0.1)
+    assert (done[3:5, 4:6] == 1).all() and int((done == 0).sum()) == 5
+    assert set(pix.tolist()) == {y * 11 + x for y in range(3, 6) for x in range(4, 7)} - {y * 11 + x for y in range(3, 5) for x in range(4, 6)}
+    a[4, 5, 1] = 1.0   # the noise is gone: everything stops, and stays stopped when it comes back
+    done, _ = restate_select(a, b, done, 0.1)
+    assert done.all()
+    a[4, 5, 1] = 3.0
+    done, pix = restate_select(a, b, done, 0.1)
+    assert done.all() and len(pix) == 0
+
+
+def test_list_order_on_a_70_x_40_mask():
+    h, w = 40, 70
+    order = restate_order(h, w)
+    assert sorted(order.tolist()) == list(range(h * w))
+    assert order[:8].tolist() == list(range(8)) and order[8] == w          # rows inside a block
+    assert order[64] == 8 and order[4 * 64] == 8 * w                        # blocks of a tile, row-major
+    assert order[1024] == 32 and order[2048] == 64                          # tiles row-major; the third is 6 wide
+    assert order[2048 + 6] == w + 64 and order[2048 + 6 * 8] == 8 * w + 64
+    assert order[2048 + 6 * 32] == 32 * w                                   # second tile row: 8 rows high
+    assert order[2048 + 6 * 32 + 4 * 64] == 32 * w + 32
+    rng = np.random.default_rng(1)
+    a, b = _flat(h, w), _flat(h, w)
+    hot = rng.random((h, w)) < 0.03
+    a[hot, 0] = 9.0
+    done, pix = restate_select(a, b, np.zeros((h, w), np.uint8), 0.1)
+    assert 0 < len(pix) < h * w
+    pos = np.empty(h * w, np.int64)
+    pos[order] = np.arange(h * w)
+    assert (np.diff(pos[pix]) > 0).all() and set(pix.tolist()) == set(np.flatnonzero(done.ravel() == 0).tolist())
+
+
+# ---------------------------------------------------------------------------- CPU: the loop on the oracle's samples
+_sim = {}
+
+
+def _plaza_oracle(ora):
+    if "scene" not in _sim:
+        _sim["scene"] = oracle_from_dict(ora, _proc().plaza_scene(level=2, sun=True, alpha=False))
+    return _sim["scene"]
+
+
+def _samples(ora):
+    """The oracle's per-sample radiance of the plaza frame, samples 0 .. 63: [H,W,64,3]. Never modified."""
+    if "samples" not in _sim:
+        s = _plaza_oracle(ora).render_samples(ora.make_cfg(W, H, 64, B, seed=SEED))
+        s.setflags(write=False)
+        _sim["samples"] = s
+    return _sim["samples"]
+
+
+def _add(buf, samples, s0, n, mask=None):
+    """What k_resolve does: the samples one by one, in order; w counts them."""
+    for s in range(s0, s0 + n):
+        inc = np.concatenate([samples[:, :, s], np.ones(samples.shape[:2] + (1,), f32)], -1)
+        if mask is None:
+            buf += inc
+        else:
+            buf[mask] += inc[mask]
+
+
+def _simulate(ora, thr, cap=64):
+    """The loop with per-round full-frame increments masked by the restated decision. -> (a, b, counts, the full-frame running snapshots)."""
+    samples = _samples(ora)
+    a, b = np.zeros((H, W, 4), f32), np.zeros((H, W, 4), f32)
+    fa, fb = a.copy(), b.copy()
+    done, snaps, given = np.zeros((H, W), np.uint8), [], 0
+    for k in _round_sizes(cap):
+        act = done == 0
+        _add(a, samples, given, k // 2, act), _add(b, samples, given + k // 2, k // 2, act)
+        _add(fa, samples, given, k // 2), _add(fb, samples, given + k // 2, k // 2)
+        snaps.append((fa.copy(), fb.copy()))
+        given += k
+        done, pix = restate_select(a, b, done, thr)
+        if not len(pix):
+            break
+    return a, b, (a[..., 3] + b[..., 3]).astype(np.int64), snaps
+
+
+def _reference_frame(ora):
+    return _plaza_oracle(ora).render(ora.make_cfg(W, H, 1024, B, seed=77), threads=0)[0]
+
+
+def _uniform(ora, n):
+    buf = np.zeros((H, W, 4), f32)
+    _add(buf, _samples(ora), 0, n)
+    return restate_mean(buf)
+
+
+def _mse(ora, mean, ref):
+    d = ora.tonemap_write(mean)[..., :3].astype(np.float64) / 255 - ora.tonemap_write(ref)[..., :3].astype(np.float64) / 255
+    return float(np.mean(d * d))
+
+
+def test_simulation_on_the_oracle_plaza(ora):
+    """Threshold 0.1, cap 64. Measured on the oracle: mean 20.0 spp, 50.4 % of the pixels stop at 8, 6.5 % reach 64, 43 % lie between;
+    mean squared error of the tonemapped bytes / 255 against a 1024-spp frame of another seed 1.36e-5, the uniform 22-spp frame's 2.17e-5."""
+    a, b, counts, snaps = _simulate(ora, 0.1)
+    assert (counts % 2 == 0).all() and counts.min() >= 8 and counts.max() <= 64 and (counts % 8 == 0).all()
+    for r, (fa, fb) in enumerate(snaps):
+        at = counts == 8 * (r + 1)
+        _same(a[at], fa[at], f"A at {8 * (r + 1)} samples")
+        _same(b[at], fb[at], f"B at {8 * (r + 1)} samples")
+    assert sum(int((counts == 8 * (r + 1)).sum()) for r in range(len(snaps))) == W * H
+    at_min, at_cap = (counts == 8).mean(), (counts == 64).mean()
+    between = ((counts > 8) & (counts < 64)).mean()
+    print(f"mean {counts.mean():.2f} spp, at 8: {at_min:.3f}, at 64: {at_cap:.3f}, between: {between:.3f}")
+    assert at_min >= 0.20 and at_cap >= 0.02 and between >= 0.10
+    ref = _reference_frame(ora)
+    n_uniform = 2 * int(counts.mean() // 2) + 2   # the next even count above the mean
+    assert counts.mean() < n_uniform <= counts.mean() + 2
+    mse_adaptive, mse_uniform = _mse(ora, restate_mean(a, b), ref), _mse(ora, _uniform(ora, n_uniform), ref)
+    print(f"adaptive MSE {mse_adaptive:.3e}, uniform {n_uniform} spp MSE {mse_uniform:.3e}")
+    assert mse_adaptive < mse_uniform
+
+
+# ---------------------------------------------------------------------------- CPU: symbols and refusals
+SYMBOLS = ("ptx_render_adaptive", "ptx_adaptive_select", "ptx_accum_mean")
+
+
+def test_symbols_are_declared_and_exported(ptx):
+    for name in SYMBOLS:
+        assert name in ptx.declared_symbols() and hasattr(ptx.lib(), name)
+    assert C.sizeof(ptx.AdaptiveCfg) == 12 and C.sizeof(ptx.AdaptiveStats) == C.sizeof(ptx.RenderStats) + 16
+
+
+def _cfg(ptx, spp=40, shard=(0, 0, 0), tile=(0, 0, W, H), integrator=0):
+    return ptx.RenderCfg(W, H, spp, B, (C.c_float * 3)(1, 1, 1), SEED, 0, *tile, 0, 0, integrator, *shard)
+
+
+def _refusal_cases(ptx, scene_h, a, b):
+    """(arguments of ptx_render_adaptive, expected status, a word of the message) decided before any device work, whatever the scene."""
+    ok = ptx.AdaptiveCfg(MIN, STEP, 0.1)
+    pa, pb = a.ctypes.data, b.ctypes.data
+    return [
+        ((None, _cfg(ptx), ok, pa, pb), ptx.ERR_INVALID, "NULL"), ((scene_h, None, ok, pa, pb), ptx.ERR_INVALID, "NULL"),
+        ((scene_h, _cfg(ptx), None, pa, pb), ptx.ERR_INVALID, "NULL"), ((scene_h, _cfg(ptx), ok, None, pb), ptx.ERR_INVALID, "NULL"),
+        ((scene_h, _cfg(ptx), ok, pa, None), ptx.ERR_INVALID, "NULL"),
+        ((scene_h, _cfg(ptx), ptx.AdaptiveCfg(0, STEP, 0.1), pa, pb), ptx.ERR_INVALID, "min_spp"),
+        ((scene_h, _cfg(ptx), ptx.AdaptiveCfg(7, STEP, 0.1), pa, pb), ptx.ERR_INVALID, "min_spp"),
+        ((scene_h, _cfg(ptx), ptx.AdaptiveCfg(MIN, 3, 0.1), pa, pb), ptx.ERR_INVALID, "step_spp"),
+        ((scene_h, _cfg(ptx, spp=41), ok, pa, pb), ptx.ERR_INVALID, "cap"),
+        ((scene_h, _cfg(ptx, spp=6), ok, pa, pb), ptx.ERR_INVALID, "cap"),
+        ((scene_h, _cfg(ptx, spp=8 + 2 * 4096), ptx.AdaptiveCfg(MIN, 2, 0.1), pa, pb), ptx.ERR_INVALID, "4096 rounds"),
+        ((scene_h, _cfg(ptx), ptx.AdaptiveCfg(MIN, STEP, -0.1), pa, pb), ptx.ERR_INVALID, "threshold"),
+        ((scene_h, _cfg(ptx), ptx.AdaptiveCfg(MIN, STEP, float("nan")), pa, pb), ptx.ERR_INVALID, "threshold"),
+        ((scene_h, _cfg(ptx, tile=(90, 0, 10, 10)), ok, pa, pb), ptx.ERR_INVALID, "tile"),
+        ((scene_h, _cfg(ptx, shard=(0, 2, 16)), ok, pa, pb), ptx.ERR_UNSUPPORTED, "rectangles"),
+    ]
+
+
+def _call_adaptive(ptx, args):
+    s, c, ac, pa, pb = args
+    rc = ptx.lib().ptx_render_adaptive(s, C.byref(c) if c is not None else None, C.byref(ac) if ac is not None else None, pa, pb, None)
+    return rc, ptx.lib().ptx_last_error().decode()
+
+
+def test_refusals_without_a_context(ptx):
+    """A host-only scene: nothing here can reach a device. The legal extremes (threshold 0 and +inf, 4096 rounds) pass the argument checks
+    and end at PTX_ERR_NO_DEVICE."""
+    L = ptx.lib()
+    s = product_from_dict(ptx, None, _proc().plaza_scene(1, sun=False, alpha=False))
+    a, b = np.zeros((H, W, 4), f32), np.zeros((H, W, 4), f32)
+    for args, status, word in _refusal_cases(ptx, s.h, a, b):
+        rc, msg = _call_adaptive(ptx, args)
+        assert rc == status and "ptx_render" in msg and word in msg, (rc, msg)
+    for c, ac in ((_cfg(ptx), ptx.AdaptiveCfg(MIN, 0, 0.0)), (_cfg(ptx), ptx.AdaptiveCfg(MIN, STEP, INF)), (_cfg(ptx, spp=8 + 2 * 4095), ptx.AdaptiveCfg(MIN, 2, 0.1)),
+                  (_cfg(ptx, integrator=ptx.INTEGRATOR_WORKER), ptx.AdaptiveCfg(2, 2, 0.1))):
+        rc, msg = _call_adaptive(ptx, (s.h, c, ac, a.ctypes.data, b.ctypes.data))
+        assert rc == ptx.ERR_NO_DEVICE and "GPU context" in msg, (rc, msg)
+    assert not a.any() and not b.any()
+    with pytest.raises(ptx.PtxError) as e:
+        s.render_adaptive(W, H, 40, B)
+    assert e.value.code == ptx.ERR_NO_DEVICE
+    # the two context entry points refuse a NULL context and bad arguments before they look at it
+    n, done = C.c_uint32(), np.zeros((H, W), np.uint8)
+    assert L.ptx_adaptive_select(None, W, H, a.ctypes.data, b.ctypes.data, 0.1, done.ctypes.data, None, C.byref(n)) == ptx.ERR_INVALID
+    assert L.ptx_accum_mean(None, a.ctypes.data, None, W * H, a.ctypes.data) == ptx.ERR_INVALID
+
+
+# ---------------------------------------------------------------------------- GPU
+@pytest.fixture(scope="module")
+def ctx(ptx):
+    return ptx.Context(0)
+
+
+def _synthetic(h, w, seed):
+    """Random positive sums with unequal counts: most pixels quiet, a few noisy ones, a constant region whose halves have the same means
+    from different counts, a NaN, an inf and a zero-count pixel, and `done` partly set on entry."""
+    rng = np.random.default_rng(seed)
+    n = h * w
+    na, nb = rng.integers(1, 9, (h, w)).astype(f32), rng.integers(1, 9, (h, w)).astype(f32)
+    mean = rng.uniform(0.05, 2.0, (h, w, 3)).astype(f32)
+    dev = np.where(rng.random((h, w, 1)) < 0.04, 0.4, 0.01).astype(f32) * rng.uniform(-1, 1, (h, w, 3)).astype(f32)
+    a = np.concatenate([mean * na[..., None], na[..., None]], -1).astype(f32)
+    b = np.concatenate([(mean * (f32(1) + dev)) * nb[..., None], nb[..., None]], -1).astype(f32)
+    flat_a, flat_b = a.reshape(n, 4), b.reshape(n, 4)
+    const = rng.random(n) < 0.3
+    flat_a[const], flat_b[const] = (2.0, 1.0, 4.0, 4.0), (1.0, 0.5, 2.0, 2.0)
+    if n > 1:
+        flat_a[(n * 3) // 7] = (np.nan, 1.0, 1.0, 2.0)
+        flat_b[(n * 5) // 7] = (1.0, np.inf, 1.0, 2.0)
+        flat_a[n - 1] = (0.0, 0.0, 0.0, 0.0)
+    done = (rng.random((h, w)) < 0.25).astype(np.uint8)
+    return a, b, done
+
+
+SIZES = [(1, 1), (5, 3), (33, 9), (67, 35), (130, 70)]   # w x h: one pixel, less than a block, two tiles, ragged tiles in both directions, 15 tiles
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", SIZES, ids=[f"{w}x{h}" for w, h in SIZES])
+def test_select_bitwise_against_the_restatement(ptx, ctx, w, h):
+    import torch
+    a, b, done0 = _synthetic(h, w, 100 + w)
+    seen = set()
+    for thr in (0.0, 0.1, INF):
+        want_done, want_pix = restate_select(a, b, done0, thr)
+        seen.add(len(want_pix))
+        got_done, got_pix, n = ctx.adaptive_select(a, b, thr, done=done0.copy())
+        assert n == len(want_pix), (thr, n, len(want_pix))
+        np.testing.assert_array_equal(got_done, want_done, err_msg=f"host done thr={thr}")
+        np.testing.assert_array_equal(got_pix, want_pix, err_msg=f"host list thr={thr}")
+        _, none, n = ctx.adaptive_select(a, b, thr, done=done0.copy(), want_list=False)
+        assert none is None and n == len(want_pix)
+        da, db, dd = torch.from_numpy(a).to("cuda:0"), torch.from_numpy(b).to("cuda:0"), torch.from_numpy(done0).to("cuda:0")
+        torch.cuda.synchronize()
+        _, dpix, n = ctx.adaptive_select(da, db, thr, done=dd)
+        assert n == len(want_pix)
+        np.testing.assert_array_equal(dd.cpu().numpy(), want_done, err_msg=f"device done thr={thr}")
+        np.testing.assert_array_equal(dpix.cpu().numpy().view(np.uint32), want_pix, err_msg=f"device list thr={thr}")
+    if w * h > 1000:   # the thresholds tell apart: the garbage pixels' blocks only, the noisy pixels' too, every pixel but the constant region's inside
+        assert len(seen) == 3 and min(seen) > 0
+
+
+@pytest.mark.gpu
+def test_accum_mean_bitwise(ptx, ctx):
+    import torch
+    a, b, _ = _synthetic(35, 67, 7)
+    for bb in (b, None):
+        want = restate_mean(a, bb)
+        _same(ctx.accum_mean(a, bb), want, "host")
+        da, db = torch.from_numpy(a).to("cuda:0"), None if bb is None else torch.from_numpy(bb).to("cuda:0")
+        torch.cuda.synchronize()
+        out = ctx.accum_mean(da, db)
+        ctx.synchronize()
+        _same(out.cpu().numpy(), want, "device")
+        _same(ctx.accum_mean(a.copy(), bb, out=None), want, "fresh output")
+        mine = a.copy()
+        assert ctx.accum_mean(mine, bb, out=mine) is mine   # in place
+        _same(mine, want, "in place")
+    assert np.isnan(restate_mean(a, b)).any() and np.isnan(restate_mean(a)[-1, -1]).all()
+
+
+_products, _snaps = {}, {}
+
+
+def _source(name):
+    """plaza: the scene of the CPU simulation above (opaque ground), which the non-vacuity bounds were measured on; plaza_alpha: tests/test_aov.py's
+    plaza (shadow-catcher ground, half-transparent sphere)."""
+    return {"plaza": lambda: _proc().plaza_scene(level=2, sun=True, alpha=False), "plaza_alpha": lambda: _proc().plaza_scene(level=2),
+            "atrium": lambda: _proc().atrium_scene(detail=2)}[name]()
+
+
+def _product(ptx, ctx, mp, name, force_global=False):
+    if (name, force_global) not in _products:
+        if force_global:
+            mp.setenv("PTX_FORCE_GLOBAL", "1")
+        _products[(name, force_global)] = product_from_dict(ptx, ctx, _source(name))
+        if force_global:
+            mp.delenv("PTX_FORCE_GLOBAL")
+    return _products[(name, force_global)]
+
+
+def _assert_route(ctx, s, resident, pipeline, what):
+    assert s.info()["lds_resident"] == resident, what
+    s.render(32, 18, 1, 2)
+    assert ctx.timing()["pipeline"] == pipeline, what
+
+
+def _snapshots(s, key, cap, min_spp=MIN, step=STEP):
+    """The product's own ptx_render of the rounds' half ranges of the WHOLE frame, snapshotted after every round: [(A_r, B_r)]. Cached per
+    route; never modified."""
+    key = (key, cap, min_spp, step)
+    if key not in _snaps:
+        a, b = np.zeros((H, W, 4), f32), np.zeros((H, W, 4), f32)
+        out, given = [], 0
+        for k in _round_sizes(cap, min_spp, step):
+            s.render(W, H, k // 2, B, accum=a, seed=SEED, sample0=given, want_stats=False)
+            s.render(W, H, k // 2, B, accum=b, seed=SEED, sample0=given + k // 2, want_stats=False)
+            given += k
+            fa, fb = a.copy(), b.copy()
+            fa.setflags(write=False), fb.setflags(write=False)
+            out.append((fa, fb))
+        _snaps[key] = out
+    return _snaps[key]
+
+
+def _crop(snaps, tile):
+    x0, y0, w, h = tile
+    return [(fa[y0:y0 + h, x0:x0 + w], fb[y0:y0 + h, x0:x0 + w]) for fa, fb in snaps]
+
+
+# (scene, created under PTX_FORCE_GLOBAL, switches at the call, expected lds_resident, expected pipeline): tests/test_aov.py's plaza routes and
+# the atrium on the queue route
+ROUTES = [
+    ("plaza", False, {}, 1, 0),                         # fused, everything in LDS
+    ("plaza", True, {}, 0, 1),                          # global memory: the queue route
+    ("plaza", True, {"PTX_WAVEFRONT": "0"}, 0, 0),      # global memory, fused
+    ("atrium", True, {}, 0, 1),                         # 24 surfaces: the queue route
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,force_global,env,resident,pipeline", ROUTES,
+                         ids=[f"{n}{'-global' if g else ''}{''.join('-' + k[4:].lower() + v for k, v in e.items())}" for n, g, e, _, _ in ROUTES])
+def test_render_adaptive_against_ptx_render_and_the_restated_decision(ptx, ctx, clean_env, name, force_global, env, resident, pipeline):
+    cap, thr = 40, 0.1
+    s = _product(ptx, ctx, clean_env, name, force_global)
+    for k, v in env.items():
+        clean_env.setenv(k, v)
+    what = f"{name} global={force_global} {env}"
+    _assert_route(ctx, s, resident, pipeline, what)
+    snaps = _snapshots(s, (name, force_global, tuple(env.items())), cap)
+    a, b, st = s.render_adaptive(W, H, cap, B, MIN, STEP, thr, seed=SEED)
+    assert ctx.timing()["pipeline"] == pipeline, what
+    counts = (a[..., 3] + b[..., 3]).astype(np.int64)
+    assert (counts % 8 == 0).all() and counts.min() >= 8 and counts.max() <= cap
+    # every pixel with count n_r equals snapshot r, in A and in B
+    for r, (fa, fb) in enumerate(snaps):
+        at = counts == 8 * (r + 1)
+        _same(a[at], fa[at], f"{what}: A at {8 * (r + 1)} samples")
+        _same(b[at], fb[at], f"{what}: B at {8 * (r + 1)} samples")
+    # the count map is the restated decision's, applied to those snapshots
+    want_a, want_b, want_rounds, want_last = _replay(snaps, thr)
+    np.testing.assert_array_equal(counts, (want_a[..., 3] + want_b[..., 3]).astype(np.int64), err_msg=what)
+    _same(a, want_a, what + ": A"), _same(b, want_b, what + ": B")
+    # stats
+    assert st["samples"] == counts.sum() and st["rounds"] == want_rounds == 5 and st["active_last"] == want_last
+    assert st["rays"] > st["samples"] and st["kernel_ms"] > 0 and st["select_ms"] > 0 and st["passes"] >= 2 * st["rounds"]
+    # not vacuous
+    at_min, at_cap, between = (counts == 8).mean(), (counts == cap).mean(), ((counts > 8) & (counts < cap)).mean()
+    print(f"{what}: mean {counts.mean():.2f} spp, at 8: {at_min:.3f}, at {cap}: {at_cap:.3f}, between: {between:.3f}, active_last {want_last}")
+    if name == "plaza":
+        # the CPU simulation's bounds, loosened: they describe this open, sun-lit scene (the oracle at cap 40: 50.4 %, 16.7 %, 32.9 %)
+        assert at_min >= 0.10 and at_cap >= 0.01 and between >= 0.05, what
+    else:
+        # an interior in which most pixels stay noisy (the oracle: 6.1 % stop at 8, 83.2 % reach 40, 10.7 % lie between): every class is met
+        assert at_min > 0 and at_cap >= 0.01 and between >= 0.05, what
+
+
+@pytest.mark.gpu
+def test_same_bits_for_tile_pass_size_buffer_kind_and_ragged_cap(ptx, ctx, clean_env):
+    import torch
+    s = _product(ptx, ctx, clean_env, "plaza_alpha")   # pass-through material and shadow catcher: 88.9 % of the pixels stop at 8, 7.7 % reach 40
+    _assert_route(ctx, s, 1, 0, "plaza_alpha")
+    cap, thr = 40, 0.1
+    snaps = _snapshots(s, ("plaza_alpha", False, ()), cap)
+    one_a, one_b, one_st = s.render_adaptive(W, H, cap, B, MIN, STEP, thr, seed=SEED)
+    want_a, want_b, _, _ = _replay(snaps, thr)
+    _same(one_a, want_a, "whole frame: A"), _same(one_b, want_b, "whole frame: B")
+    # a tile is decided on its own rectangle: the restatement on the crop of the whole frame's snapshots
+    tile = (13, 7, 45, 29)
+    ta, tb, tst = s.render_adaptive(W, H, cap, B, MIN, STEP, thr, seed=SEED, tile=tile)
+    want_a, want_b, want_rounds, want_last = _replay(_crop(snaps, tile), thr)
+    _same(ta, want_a, "tile: A"), _same(tb, want_b, "tile: B")
+    assert tst["rounds"] == want_rounds and tst["active_last"] == want_last and tst["samples"] == (ta[..., 3] + tb[..., 3]).sum()
+    # one sample per pass
+    pa, pb, pst = s.render_adaptive(W, H, cap, B, MIN, STEP, thr, seed=SEED, spp_per_pass=1)
+    _same(pa, one_a, "spp_per_pass 1: A"), _same(pb, one_b, "spp_per_pass 1: B")
+    assert pst["passes"] == pst["rounds"] * 8 and pst["passes"] > one_st["passes"]
+    # device buffers, with and without stats
+    for want_stats in (True, False):
+        da, db = torch.zeros((H, W, 4), device="cuda:0"), torch.zeros((H, W, 4), device="cuda:0")
+        torch.cuda.synchronize()
+        _, _, dst = s.render_adaptive(W, H, cap, B, MIN, STEP, thr, a=da, b=db, seed=SEED, want_stats=want_stats)
+        _same(da.cpu().numpy(), one_a, "device: A"), _same(db.cpu().numpy(), one_b, "device: B")
+        assert dst is None or dst["samples"] == one_st["samples"]
+    # added to what the buffers hold, as ptx_render adds
+    init, _ = s.render(W, H, 2, B, seed=SEED + 1)
+    ia, ib, _ = s.render_adaptive(W, H, 16, B, MIN, STEP, INF, a=init.copy(), b=init.copy(), seed=SEED)
+    wa, wb = init.copy(), init.copy()
+    s.render(W, H, 4, B, accum=wa, seed=SEED), s.render(W, H, 4, B, accum=wb, seed=SEED, sample0=4)
+    _same(ia, wa, "non-zero start: A"), _same(ib, wb, "non-zero start: B")
+    # a cap that is no multiple of the step: rounds of 8, 8, 8, 6
+    snaps30 = _snapshots(s, ("plaza_alpha", False, ()), 30)
+    assert [int(fa[0, 0, 3] + fb[0, 0, 3]) for fa, fb in snaps30] == [8, 16, 24, 30]
+    ra, rb, rst = s.render_adaptive(W, H, 30, B, MIN, STEP, thr, seed=SEED)
+    want_a, want_b, want_rounds, want_last = _replay(snaps30, thr)
+    _same(ra, want_a, "cap 30: A"), _same(rb, want_b, "cap 30: B")
+    assert rst["rounds"] == want_rounds == 4 and rst["active_last"] == want_last and (ra[..., 3] + rb[..., 3]).max() == 30
+    # a step of its own, and sample0
+    sa, sb, sst = s.render_adaptive(W, H, 12, B, 8, 4, thr, seed=SEED)
+    want_a, want_b, want_rounds, _ = _replay(_snapshots(s, ("plaza_alpha", False, ()), 12, 8, 4), thr)
+    _same(sa, want_a, "step 4: A"), _same(sb, want_b, "step 4: B")
+    assert sst["rounds"] == want_rounds == 2
+    # ... and a first sample of its own: the prefix starts there
+    oa, ob, _ = s.render_adaptive(W, H, 8, B, 8, 0, thr, seed=SEED, sample0=5)
+    wa, _ = s.render(W, H, 4, B, seed=SEED, sample0=5)
+    wb, _ = s.render(W, H, 4, B, seed=SEED, sample0=9)
+    _same(oa, wa, "sample0 5: A"), _same(ob, wb, "sample0 5: B")
+
+
+@pytest.mark.gpu
+def test_thresholds_infinity_and_zero(ptx, ctx, clean_env):
+    s = _product(ptx, ctx, clean_env, "plaza")
+    cap = 40
+    snaps = _snapshots(s, ("plaza", False, ()), cap)
+    # +inf: one round, the frame of two ptx_render halves of 4 samples
+    a, b, st = s.render_adaptive(W, H, cap, B, MIN, STEP, INF, seed=SEED)
+    assert st["rounds"] == 1 and st["active_last"] == 0 and st["samples"] == 8 * W * H
+    h0, _ = s.render(W, H, 4, B, seed=SEED)
+    h1, _ = s.render(W, H, 4, B, seed=SEED, sample0=4)
+    _same(a, h0, "A"), _same(b, h1, "B")
+    # 0: only pixels whose halves agree exactly, with all their neighbours, stop — the sky; whatever differs goes to the cap
+    a, b, st = s.render_adaptive(W, H, cap, B, MIN, STEP, 0.0, seed=SEED)
+    want_a, want_b, want_rounds, want_last = _replay(snaps, 0.0)
+    _same(a, want_a, "threshold 0: A"), _same(b, want_b, "threshold 0: B")
+    counts = (a[..., 3] + b[..., 3]).astype(np.int64)
+    differs = restate_noisy(a, b, 0.0)
+    assert (counts[differs] == cap).all() and differs.mean() > 0.05
+    sky = counts == 8
+    assert sky.mean() > 0.05 and not differs[sky].any()
+    _same(restate_mean(a)[sky][:, :3], restate_mean(b)[sky][:, :3], "a pixel that stopped at threshold 0 has equal halves")
+    assert st["rounds"] == want_rounds == 5 and st["active_last"] == want_last > 0 and st["samples"] == counts.sum()
+
+
+@pytest.mark.gpu
+def test_refusals_with_a_live_context(ptx, ctx, clean_env):
+    import torch
+    s = _product(ptx, ctx, clean_env, "plaza")
+    a, b = np.zeros((H, W, 4), f32), np.zeros((H, W, 4), f32)
+    for args, status, word in _refusal_cases(ptx, s.h, a, b):
+        rc, msg = _call_adaptive(ptx, args)
+        assert rc == status and word in msg, (rc, msg)
+    da = torch.zeros((H, W, 4), device="cuda:0")
+    dd = torch.zeros((H, W), dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    with pytest.raises(ptx.PtxError) as e:
+        s.render_adaptive(W, H, 40, B, a=a, b=da)
+    assert e.value.code == ptx.ERR_INVALID and "both" in str(e.value)
+    L, n = ptx.lib(), C.c_uint32()
+    done = np.zeros((H, W), np.uint8)
+    for args in ((W, H, a.ctypes.data, da.data_ptr(), 0.1, done.ctypes.data, None), (W, H, a.ctypes.data, b.ctypes.data, 0.1, dd.data_ptr(), None),
+                 (0, H, a.ctypes.data, b.ctypes.data, 0.1, done.ctypes.data, None), (W, 16385, a.ctypes.data, b.ctypes.data, 0.1, done.ctypes.data, None),
+                 (W, H, a.ctypes.data, b.ctypes.data, -1.0, done.ctypes.data, None), (W, H, a.ctypes.data, b.ctypes.data, float("nan"), done.ctypes.data, None),
+                 (W, H, None, b.ctypes.data, 0.1, done.ctypes.data, None), (W, H, a.ctypes.data, b.ctypes.data, 0.1, None, None)):
+        assert L.ptx_adaptive_select(ctx.h, *args, C.byref(n)) == ptx.ERR_INVALID, args
+        assert "ptx_adaptive_select" in L.ptx_last_error().decode()
+    assert L.ptx_adaptive_select(ctx.h, W, H, a.ctypes.data, b.ctypes.data, 0.1, done.ctypes.data, None, None) == ptx.ERR_INVALID
+    assert L.ptx_accum_mean(ctx.h, a.ctypes.data, da.data_ptr(), W * H, a.ctypes.data) == ptx.ERR_INVALID
+    assert L.ptx_accum_mean(ctx.h, None, None, W * H, a.ctypes.data) == ptx.ERR_INVALID
+    assert not a.any() and not b.any() and not done.any()
+
+
+@pytest.mark.gpu
+def test_renderer_mirror_equals_the_call_composition(ptx):
+    r = ptx.Renderer(0)
+    r.resolution, r.sample_count, r.bounce_count, r.seed = (48, 27), 24, 3, SEED
+    r.load_gltf(CORNELL)
+    got = r.render_adaptive(threshold=0.2, min_spp=8, step_spp=4)
+    a, b, st = r._scene.render_adaptive(48, 27, 24, 3, 8, 4, 0.2, seed=SEED)
+    _same(got, restate_mean(a, b), "Renderer.render_adaptive")
+    _same(got, r._ctx.accum_mean(a, b), "accum_mean")
+    assert all(r.last_adaptive_stats[k] == st[k] for k in ("rays", "samples", "passes", "rounds", "active_last"))
+    assert st["samples"] == (a[..., 3] + b[..., 3]).sum()
+    assert (got[..., 3] == 1).all()
+
+
+@pytest.mark.gpu
+def test_cli_flag_writes_the_frame_of_means(ptx, ctx, tmp_path):
+    """ptx_render_cli --adaptive THR:MIN:STEP with spp as the cap: the PNG is ptx_accum_mean + ptx_tonemap_encode(spp = 1) of the call's buffers."""
+    import json
+    import subprocess
+    from PIL import Image
+    cw, ch, cap = 48, 27, 24
+    cli = os.path.join(ROOT, "distributed-path-tracer_amd", "ptx_render_cli")
+    r = subprocess.run([cli, "--adaptive", "0.2:8:4", CORNELL, str(tmp_path / "f.png"), str(cw), str(ch), str(cap), "3"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    s = ptx.Scene.load_gltf(ctx, CORNELL)
+    a, b, st = s.render_adaptive(cw, ch, cap, 3, 8, 4, 0.2, seed=SEED)
+    want = ctx.tonemap_encode(ctx.accum_mean(a, b), cw, ch, 1)
+    np.testing.assert_array_equal(np.array(Image.open(tmp_path / "f.png")), want)
+    out = json.loads(r.stdout)
+    assert out["adaptive_rounds"] == st["rounds"] and out["adaptive_active_last"] == st["active_last"]
+    assert out["adaptive_mean_spp"] == pytest.approx(st["samples"] / (cw * ch), abs=1e-3)
