@@ -27,7 +27,8 @@ OK, ERR_INVALID, ERR_IO, ERR_PARSE, ERR_NO_CAMERA, ERR_NO_DEVICE, ERR_HIP, ERR_U
 NO_SUN_LIGHT = 0xFFFFFFFF  # core::renderer::no_sun_light, renderer.hpp:19
 
 (ARR_MODEL_XFORM, ARR_MODEL_AABB, ARR_MODEL_SURF, ARR_SURF_RANGE, ARR_MESH_AABB, ARR_VERTICES, ARR_TRIANGLES,
- ARR_MATERIALS, ARR_KD_NODES, ARR_KD_REFS, ARR_CAMERA, ARR_SUN, ARR_MODEL_NAMES, ARR_TEXTURES, ARR_TEXELS, ARR_SURF_TEX, ARR_TEXELS_F32) = range(17)
+ ARR_MATERIALS, ARR_KD_NODES, ARR_KD_REFS, ARR_CAMERA, ARR_SUN, ARR_MODEL_NAMES, ARR_TEXTURES, ARR_TEXELS, ARR_SURF_TEX, ARR_TEXELS_F32,
+ ARR_LIGHT_TRIS, ARR_LIGHT_CDF, ARR_LIGHT_GEOM) = range(20)
 
 
 class PtxError(RuntimeError):
@@ -95,6 +96,18 @@ class AdaptiveCfg(C.Structure):
 
 class AdaptiveStats(C.Structure):
     _fields_ = [("render", RenderStats), ("rounds", C.c_uint32), ("active_last", C.c_uint32), ("select_ms", C.c_double)]
+
+
+class NeeCfg(C.Structure):
+    _fields_ = [("flags", C.c_uint32)]
+
+
+class NeeStats(C.Structure):
+    _fields_ = [("render", RenderStats), ("n_lights", C.c_uint32), ("light_area", C.c_float), ("light_samples", C.c_uint64),
+                ("light_visible", C.c_uint64)]
+
+
+NEE_NO_LIGHT_SAMPLES = 1   # ptx_nee_cfg.flags
 
 
 class KernelTiming(C.Structure):
@@ -182,6 +195,7 @@ def lib():
         L.ptx_render_aov.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AovBuffers), C.POINTER(RenderStats)]
         L.ptx_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p, C.POINTER(DenoiseStats)]
         L.ptx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AdaptiveCfg), C.c_void_p, C.c_void_p, C.POINTER(AdaptiveStats)]
+        L.ptx_render_nee.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(NeeCfg), C.c_void_p, C.POINTER(NeeStats)]
         L.ptx_adaptive_select.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.ptx_accum_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_intersect_batch.argtypes = [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(Hits)]
@@ -351,7 +365,8 @@ _ARR_DTYPE = {ARR_MODEL_XFORM: (np.float32, 12), ARR_MODEL_AABB: (np.float32, 6)
               ARR_SURF_RANGE: (np.int32, 8), ARR_MESH_AABB: (np.float32, 6), ARR_VERTICES: (np.float32, 11),
               ARR_TRIANGLES: (np.uint32, 3), ARR_MATERIALS: (np.float32, 11), ARR_KD_NODES: (np.uint32, 2),
               ARR_KD_REFS: (np.uint32, 1), ARR_CAMERA: (np.float32, 1), ARR_SUN: (np.float32, 1),
-              ARR_TEXTURES: (np.uint32, 4), ARR_TEXELS: (np.uint8, 1), ARR_SURF_TEX: (np.int32, 7), ARR_TEXELS_F32: (np.float32, 1)}
+              ARR_TEXTURES: (np.uint32, 4), ARR_TEXELS: (np.uint8, 1), ARR_SURF_TEX: (np.int32, 7), ARR_TEXELS_F32: (np.float32, 1),
+              ARR_LIGHT_TRIS: (np.uint32, 2), ARR_LIGHT_CDF: (np.float32, 1), ARR_LIGHT_GEOM: (np.float32, 4)}
 
 
 class Scene:
@@ -505,6 +520,24 @@ class Scene:
         stats = dict(rays=st.render.rays, samples=st.render.samples, passes=st.render.passes, kernel_ms=st.render.kernel_ms, rounds=st.rounds,
                      active_last=st.active_last, select_ms=st.select_ms) if want_stats else None
         return a, b, stats
+
+    def render_nee(self, W, H, spp, bounces, accum=None, env=(1.0, 1.0, 1.0), seed=0x5EED, tile=None, sample0=0, spp_per_pass=0,
+                   want_stats=True, integrator=INTEGRATOR_LIB, shard=None, flags=0):
+        """ptx_render_nee: render()'s samples with the LIB estimator plus one light sample towards the listed emissive triangles per
+        continuing vertex, MIS-weighted (include/ptx.h has the estimator). ADDS radiance SUMS into accum as render() does; tiles, sample
+        ranges and shards compose the same way. flags: NEE_NO_LIGHT_SAMPLES runs with an empty list (bitwise render()'s frame).
+        Returns (accum, stats dict or None)."""
+        x0, y0, w, h = tile if tile else (0, 0, W, H)
+        if accum is None:
+            accum = np.zeros((h, w, 4), np.float32)
+        cfg = RenderCfg(W, H, spp, bounces, (C.c_float * 3)(*env), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                        x0, y0, w, h, sample0, spp_per_pass, integrator, *((tuple(shard) + (0,))[:3] if shard else (0, 0, 0)))
+        ncfg = NeeCfg(flags)
+        st = NeeStats()
+        _check(lib().ptx_render_nee(self.h, C.byref(cfg), C.byref(ncfg), _ptr(accum), C.byref(st) if want_stats else None))
+        stats = dict(rays=st.render.rays, samples=st.render.samples, passes=st.render.passes, kernel_ms=st.render.kernel_ms, n_lights=st.n_lights,
+                     light_area=st.light_area, light_samples=st.light_samples, light_visible=st.light_visible) if want_stats else None
+        return accum, stats
 
     def set_environment(self, png_path, srgb=True):
         """renderer::environment = image_texture::load(png_path, srgb): the miss colour becomes map(direction) * environment_factor.
@@ -662,6 +695,20 @@ class Renderer:
         a, b, self.last_adaptive_stats = self._scene.render_adaptive(W, H, self.sample_count, self.bounce_count, min_spp, step_spp, threshold,
                                                                      env=self.environment_factor, seed=self.seed)
         return self._ctx.accum_mean(a, b, out=a)
+
+    def render_nee(self):
+        """Radiance SUMS [H,W,4] of the frame with next-event estimation towards the scene's emissive triangles (Scene.render_nee):
+        render_accum()'s samples plus one MIS-weighted light sample per continuing vertex. `last_nee_stats` holds the stats."""
+        if self._scene is None:
+            raise PtxError(ERR_INVALID, "render_nee() before load_gltf()")
+        if self.transparent_background:
+            raise PtxError(ERR_UNSUPPORTED, "render_nee: transparent_background's blend is not built on this estimator")
+        W, H = self.resolution
+        if self.environment != getattr(self, "_env_set", None):
+            self._scene.set_environment(self.environment)
+            self._env_set = self.environment
+        accum, self.last_nee_stats = self._scene.render_nee(W, H, self.sample_count, self.bounce_count, env=self.environment_factor, seed=self.seed)
+        return accum
 
     def render(self):
         W, H = self.resolution

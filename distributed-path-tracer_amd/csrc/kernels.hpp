@@ -201,6 +201,42 @@ hipError_t launch_aov_shade(const DevScene& S, const RenderParams& P, const AovS
 hipError_t launch_aov_resolve(const float4* rec, size_t rec_stride, float4* albedo_cov, float4* normal_depth, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp,
                               hipStream_t stream);
 
+// Next-event estimation towards emissive triangles (nee.hip, ptx_render_nee). A ROUND = the live paths' rays through the scene's own intersect
+// route, k_nee_shade (one path vertex per lane), the round's shadow rays through the same route, k_nee_settle (their answers).
+struct NeeStream {   // path state, SoA, `cap` entries per array; the six ray arrays are what the intersect launches read
+	float *ox, *oy, *oz, *dx, *dy, *dz;
+	float *tx, *ty, *tz;   // throughput
+	float* pp;             // max(pdf, eps) of the direction sampled at the previous vertex
+	uint32_t* id;          // the sample's id within the pass (sample-major, pixel-minor)
+	uint32_t* dp;          // depth << 16 | pass
+};
+struct NeeHits {   // what an intersect launch wrote
+	const float* distance;
+	const int32_t *surface, *triangle;   // -1 = miss; triangle index within the surface's mesh
+	const float *b1, *b2;
+};
+constexpr uint32_t kNeeNone = 0x7FFFFFFFu, kNeeCatcher = 0x80000000u;   // sun_pos / light_pos: no such ray | the sun ray is a shadow catcher's
+struct NeeShadow {
+	float *ox, *oy, *oz, *dx, *dy, *dz;   // [2 cap] the round's shadow rays, dense
+	float *sx, *sy, *sz;                  // [cap] by path: radiance the sun adds when unoccluded | origin of a lit catcher's pass-through ray
+	float *lx, *ly, *lz;                  // [cap] by path: radiance the light sample adds when visible
+	uint32_t *sun_pos, *light_pos;        // [cap] by path: the ray's position in the shadow stream (< 2^31), or kNeeNone
+	uint32_t *exp_surf, *exp_tri;         // [cap] by path: the sampled triangle (surface, local triangle)
+};
+struct NeeLights {   // the scene's light list (ptx_api.cpp: build_lights); n == 0: no light samples, every emission weight is 1
+	const uint2* tris;           // [n] (surface, local triangle), ordered by surface, then triangle
+	const float* cdf;            // [n] cumulative area share, the last entry 1
+	const float4* geom;          // [n] geometric normal (world), area
+	const int32_t* surf_first;   // [n_surfaces] first entry of the surface, or -1
+	uint32_t n;
+	float area;                  // A_total
+};
+// cnt (device, 8 words): [0] entries appended to `out`, [1] shadow rays of the round, [2..3] light samples (64-bit), [4..5] visible ones
+hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, hipStream_t stream);
+hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeStream& in, const NeeHits& H, uint32_t n, const NeeStream& out,
+                            const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
+hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, hipStream_t stream);
+
 // Variance-guided a-trous filter (denoise.hip, ptx_denoise). All buffers [n_pixels] float4 on the device.
 // prepare: the two radiance sums and the guide sums -> col_var (demodulated colour, v0), guide (mean normal, mean depth), remod (albedo, alpha)
 hipError_t launch_denoise_prepare(const float4* a, const float4* b, const float4* albedo_cov, const float4* normal_depth, uint32_t spp_a, uint32_t spp_b, size_t n_pixels,

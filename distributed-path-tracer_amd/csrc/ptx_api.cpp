@@ -115,6 +115,17 @@ struct ptx_scene {
 	bool leaf_ordered = true; // global-memory copy of the triangle records: per leaf reference (true) or per triangle (false)
 	int mode = MODE_GLOBAL;   // where the traversal arrays live: MODE_GLOBAL / MODE_LDS / MODE_HYBRID (kernels.hip)
 	size_t lds_bytes = 0;     // dynamic LDS of the kernels (resident arrays + shade records)
+	// The light list of ptx_render_nee (build_lights): built at the first call that asks for it, then kept. Host copies serve
+	// ptx_scene_get_array; the device copies are made by the first ptx_render_nee.
+	struct LightList {
+		bool built = false, on_device = false;
+		std::vector<uint32_t> tris;        // [n][2] surface, local triangle
+		std::vector<float> cdf, geom;      // [n], [n][4] geometric normal + area
+		std::vector<int32_t> surf_first;   // [n_surfaces] first entry or -1
+		float area = 0;                    // A_total
+	} lights;
+	std::mutex lights_mu;   // host-only scenes have no context whose mutex could guard the build
+	DevBuf d_light_tris, d_light_cdf, d_light_geom, d_light_first;
 };
 
 namespace {
@@ -321,8 +332,10 @@ int upload_scene(ptx_scene* sc) {
 
 void release_scene_buffers(ptx_scene* sc) {
 	for (DevBuf* b : {&sc->d_models, &sc->d_surfaces, &sc->d_materials, &sc->d_nodes, &sc->d_refs, &sc->d_tris, &sc->d_shade, &sc->d_tex,
-	                  &sc->d_texels, &sc->d_texels_f, &sc->d_lut, &sc->d_spaces, &sc->d_model_space, &sc->d_wf_order, &sc->d_res_nodes, &sc->d_res_refs, &sc->d_res_tris, &sc->d_hot})
+	                  &sc->d_texels, &sc->d_texels_f, &sc->d_lut, &sc->d_spaces, &sc->d_model_space, &sc->d_wf_order, &sc->d_res_nodes, &sc->d_res_refs, &sc->d_res_tris, &sc->d_hot,
+	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first})
 		b->release();
+	sc->lights.on_device = false;
 }
 
 int finish_scene(ptx_ctx* ctx, ptx_scene* sc, ptx_scene** out) {
@@ -576,6 +589,53 @@ int ptx_scene_get_info(const ptx_scene* sc, ptx_scene_info* info) {
 	return PTX_OK;
 }
 
+namespace {
+
+// The emissive triangles ptx_render_nee samples (include/ptx.h: the listing rules). World corners, areas and normals in float64 in the
+// written order, stored as float32.
+const ptx_scene::LightList* build_lights(ptx_scene* sc) {
+	std::lock_guard<std::mutex> lk(sc->lights_mu);
+	ptx_scene::LightList& ll = sc->lights;
+	if (ll.built) return &ll;
+	const FlatScene& h = sc->host;
+	const size_t n_surf = h.surfaces.size();
+	ll.surf_first.assign(n_surf, -1);
+	std::vector<double> cum;
+	double total = 0;
+	for (size_t s = 0; s < n_surf; s++) {
+		const MaterialRec& m = h.materials[s];
+		if (!(m.emissive[0] > 0 || m.emissive[1] > 0 || m.emissive[2] > 0)) continue;
+		if (m.tex[2] >= 0 || !(m.opacity == 1.0f || std::fabs(m.opacity - 1.0f) < 0.0001f) || m.shadow_catcher) continue;   // can pass a sample through
+		const float* X = h.model_xform.data() + 12 * (size_t)h.surfaces[s].model;
+		const int32_t* rg = h.surf_range.data() + 8 * s;
+		for (int32_t t = 0; t < rg[3]; t++) {
+			double c[3][3];
+			for (int k = 0; k < 3; k++) {
+				const float* v = h.vertices.data() + 11 * (size_t)(rg[0] + (int32_t)h.triangles[3 * (size_t)(rg[2] + t) + k]);
+				for (int a = 0; a < 3; a++) c[k][a] = ((double)X[3 + a] * (double)v[0] + (double)X[6 + a] * (double)v[1]) + (double)X[9 + a] * (double)v[2] + (double)X[a];
+			}
+			const double e1[3] = {c[1][0] - c[0][0], c[1][1] - c[0][1], c[1][2] - c[0][2]}, e2[3] = {c[2][0] - c[0][0], c[2][1] - c[0][1], c[2][2] - c[0][2]};
+			const double cr[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+			const double len = std::sqrt((cr[0] * cr[0] + cr[1] * cr[1]) + cr[2] * cr[2]);
+			const double area = 0.5 * len;
+			if (!(area > 0)) continue;
+			if (ll.surf_first[s] < 0) ll.surf_first[s] = (int32_t)(ll.tris.size() / 2);
+			ll.tris.push_back((uint32_t)s); ll.tris.push_back((uint32_t)t);
+			for (int a = 0; a < 3; a++) ll.geom.push_back((float)(cr[a] / len));
+			ll.geom.push_back((float)area);
+			total += area;
+			cum.push_back(total);
+		}
+	}
+	for (double v : cum) ll.cdf.push_back((float)(v / total));
+	if (!ll.cdf.empty()) ll.cdf.back() = 1.0f;
+	ll.area = (float)total;
+	ll.built = true;
+	return &ll;
+}
+
+}  // namespace
+
 int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, size_t dst_bytes) {
 	if (!sc) { set_err(PTX_ERR_INVALID, "scene is NULL"); return -1; }
 	const FlatScene& h = sc->host;
@@ -612,6 +672,9 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 	case PTX_ARR_TEXELS: src = h.texels.data(); bytes = h.texels.size(); elem = 1; break;
 	case PTX_ARR_SURF_TEX: src = h.surf_tex.data(); bytes = h.surf_tex.size() * 4; break;
 	case PTX_ARR_TEXELS_F32: src = h.texels_f.data(); bytes = h.texels_f.size() * 4; break;
+	case PTX_ARR_LIGHT_TRIS: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.tris.data(); bytes = ll.tris.size() * 4; break; }
+	case PTX_ARR_LIGHT_CDF: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.cdf.data(); bytes = ll.cdf.size() * 4; break; }
+	case PTX_ARR_LIGHT_GEOM: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.geom.data(); bytes = ll.geom.size() * 4; break; }
 	default: set_err(PTX_ERR_INVALID, "unknown array id"); return -1;
 	}
 	if (dst) {
@@ -1182,6 +1245,7 @@ int intersect_device(ptx_ctx* c, ptx_scene* sc, IntersectArgs& A) {
 			for (int k = 0; k < 6; k++) fprintf(stderr, "WFCLK %-10s %10u kcycles summed over waves (%.1f %%)\n", tn[k], pr[16 + k], 100.0 * pr[16 + k] / (double)pr[16]);
 #endif
 			if (ws.flow_host[kWfFlowOverflow]) {
+				c->timing.pool_overflows++;
 				if (slice <= 16384) return set_err(PTX_ERR_HIP, "queue-based pipeline: the pair pool cannot hold a 16384-ray slice");
 				slice = std::max<size_t>(16384, std::min(slice_cap(), slice - slice / 4));
 				continue;   // the same rays again, fewer at a time
@@ -1376,6 +1440,179 @@ int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffe
 			float t = 0;
 			HIP_TRY(hipEventElapsedTime(&t, c->events[2 * p], c->events[2 * p + 1]));
 			stats->kernel_ms += t;
+		}
+	}
+	return PTX_OK;
+}
+
+namespace {
+
+// words per sample of ptx_render_nee's workspace: two path streams (12 each), the hits (6), the radiance record (4), the shadow stream
+// (2 x 6 rays + 2 x 6 hits) and the per-path shadow records (10)
+constexpr size_t kNeeSampleWords = 2 * 12 + 6 + 4 + 2 * 6 + 2 * 6 + 10;
+// samples of every pixel per pass: by default 16 Mi samples (8 spp of a 1080p frame, 4.6 GB); at most 2^30, so that the positions of
+// a round's shadow rays (two per path at most) stay below 2^31
+uint32_t nee_pass_size(const ptx_render_cfg* cfg, uint64_t n_pixels) {
+	uint32_t pass_spp = cfg->spp_per_pass ? cfg->spp_per_pass : (uint32_t)std::max<uint64_t>(1, (16ull << 20) / n_pixels);
+	pass_spp = std::min(pass_spp, cfg->spp);
+	while ((uint64_t)pass_spp * n_pixels > 0x3FFFFFFFull) pass_spp--;
+	return pass_spp;
+}
+
+}  // namespace
+
+int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* ncfg, float* accum, ptx_nee_stats* stats) {
+	// every refusal below is decided before any device work
+	if (!sc || !cfg || !accum) return set_err(PTX_ERR_INVALID, "ptx_render_nee: NULL argument");
+	const uint32_t flags = ncfg ? ncfg->flags : 0u;
+	if (flags & ~(uint32_t)PTX_NEE_NO_LIGHT_SAMPLES) return set_err(PTX_ERR_INVALID, "ptx_render_nee: unknown flag");
+	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
+		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_nee: PTX_INTEGRATOR_WORKER has no light sampling here (the estimator is defined on PTX_INTEGRATOR_LIB's vertex)");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_nee: scene was created without a GPU context (no CPU path exists)");
+	uint32_t x0, y0, w, h;
+	if (const int rc = render_rect(cfg, x0, y0, w, h); rc != PTX_OK) return rc;
+	const uint64_t rect_pixels = (uint64_t)w * h;
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	if (stats) { *stats = ptx_nee_stats{}; c->timing = ptx_kernel_timing{}; c->timing.pipeline = use_wavefront(sc) ? 1u : 0u; }
+	const ptx_scene::LightList& ll = *build_lights(sc);
+	const uint32_t n_lights = (uint32_t)ll.cdf.size();
+	if (stats) { stats->n_lights = n_lights; stats->light_area = ll.area; }
+	if (cfg->spp == 0) return PTX_OK;
+	uint64_t n_pixels = 0;
+	const uint32_t* d_pixels = nullptr;
+	if (const int rc = pixel_list(c, sc, cfg, x0, y0, w, h, n_pixels, d_pixels); rc != PTX_OK) return rc;
+	if (n_pixels == 0) return PTX_OK;   // no tile of this shard meets the rectangle
+	const uint32_t pass_spp = nee_pass_size(cfg, n_pixels);
+	if (pass_spp == 0) return set_err(PTX_ERR_INVALID, "ptx_render_nee: tile too large for one pass");
+
+	NeeLights Lt{};
+	if (n_lights && !(flags & PTX_NEE_NO_LIGHT_SAMPLES)) {
+		if (!sc->lights.on_device) {
+			HIP_TRY(sc->d_light_tris.ensure(ll.tris.size() * 4));
+			HIP_TRY(sc->d_light_cdf.ensure(ll.cdf.size() * 4));
+			HIP_TRY(sc->d_light_geom.ensure(ll.geom.size() * 4));
+			HIP_TRY(sc->d_light_first.ensure(ll.surf_first.size() * 4));
+			HIP_TRY(hipMemcpyAsync(sc->d_light_tris.p, ll.tris.data(), ll.tris.size() * 4, hipMemcpyHostToDevice, c->stream));
+			HIP_TRY(hipMemcpyAsync(sc->d_light_cdf.p, ll.cdf.data(), ll.cdf.size() * 4, hipMemcpyHostToDevice, c->stream));
+			HIP_TRY(hipMemcpyAsync(sc->d_light_geom.p, ll.geom.data(), ll.geom.size() * 4, hipMemcpyHostToDevice, c->stream));
+			HIP_TRY(hipMemcpyAsync(sc->d_light_first.p, ll.surf_first.data(), ll.surf_first.size() * 4, hipMemcpyHostToDevice, c->stream));
+			HIP_TRY(hipStreamSynchronize(c->stream));
+			sc->lights.on_device = true;
+		}
+		Lt.tris = (const uint2*)sc->d_light_tris.p; Lt.cdf = (const float*)sc->d_light_cdf.p; Lt.geom = (const float4*)sc->d_light_geom.p;
+		Lt.surf_first = (const int32_t*)sc->d_light_first.p; Lt.n = n_lights; Lt.area = ll.area;
+	}
+
+	// workspace of one pass of `cap` samples: [256 B: counters][radiance records][stream 0][stream 1][hits][shadow rays][shadow hits][shadow records]
+	const size_t cap = ((size_t)pass_spp * n_pixels + 3) & ~(size_t)3;   // array stride: keeps every array 16-byte aligned
+	HIP_TRY(c->aov.ensure(256 + cap * kNeeSampleWords * 4));
+	uint32_t* const cnt = (uint32_t*)c->aov.p;
+	float* f = (float*)((char*)c->aov.p + 256);
+	float4* const Lrec = (float4*)f;
+	f += 4 * cap;
+	NeeStream st[2];
+	for (NeeStream& s : st) {
+		s.ox = f; s.oy = f + cap; s.oz = f + 2 * cap; s.dx = f + 3 * cap; s.dy = f + 4 * cap; s.dz = f + 5 * cap;
+		s.tx = f + 6 * cap; s.ty = f + 7 * cap; s.tz = f + 8 * cap; s.pp = f + 9 * cap;
+		s.id = (uint32_t*)(f + 10 * cap); s.dp = (uint32_t*)(f + 11 * cap);
+		f += 12 * cap;
+	}
+	float* const hits = f;
+	f += 6 * cap;
+	NeeShadow W{};
+	W.ox = f; W.oy = f + 2 * cap; W.oz = f + 4 * cap; W.dx = f + 6 * cap; W.dy = f + 8 * cap; W.dz = f + 10 * cap;
+	f += 12 * cap;
+	float* const shits = f;
+	f += 12 * cap;
+	W.sx = f; W.sy = f + cap; W.sz = f + 2 * cap; W.lx = f + 3 * cap; W.ly = f + 4 * cap; W.lz = f + 5 * cap;
+	W.sun_pos = (uint32_t*)(f + 6 * cap); W.light_pos = (uint32_t*)(f + 7 * cap); W.exp_surf = (uint32_t*)(f + 8 * cap); W.exp_tri = (uint32_t*)(f + 9 * cap);
+
+	const bool dev_accum = is_device_ptr(accum);
+	float4* d_accum = (float4*)accum;
+	if (!dev_accum) {
+		HIP_TRY(c->stage_a.ensure(rect_pixels * sizeof(float4)));
+		d_accum = (float4*)c->stage_a.p;
+		HIP_TRY(hipMemcpyAsync(d_accum, accum, rect_pixels * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+	}
+	const uint32_t n_pass = (cfg->spp + pass_spp - 1) / pass_spp;
+	if (stats)
+		while (c->events.size() < 2 * (size_t)n_pass) {
+			hipEvent_t ev;
+			HIP_TRY(hipEventCreate(&ev));
+			c->events.push_back(ev);
+		}
+	HIP_TRY(hipMemsetAsync(cnt, 0, 256, c->stream));
+	// a lit shadow catcher's pass-through ray is appended by the settle kernel: only then is the live count read a second time in a round
+	const bool catchers = sc->dev.any_alpha != 0 && sc->dev.sun.present != 0;
+	uint64_t rays = 0;
+	for (uint32_t p = 0; p < n_pass; p++) {
+		RenderParams P{};
+		P.W = cfg->W; P.H = cfg->H; P.x0 = x0; P.y0 = y0; P.w = w; P.h = h;
+		P.n_pixels = (uint32_t)n_pixels;
+		P.sample0 = cfg->sample0 + p * pass_spp;
+		P.pass_spp = std::min(pass_spp, cfg->spp - p * pass_spp);
+		P.bounces = cfg->bounces;
+		P.n_paths = (uint64_t)P.pass_spp * n_pixels;
+		P.seed_lo = cfg->seed_lo; P.seed_hi = cfg->seed_hi;
+		memcpy(P.env, cfg->env, sizeof P.env);
+		P.integrator = PTX_INTEGRATOR_LIB;
+		P.pixels = d_pixels;
+		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
+		HIP_TRY(launch_nee_generate(sc->dev, P, st[0], Lrec, (uint32_t)P.n_paths, c->stream));
+		uint32_t live = P.bounces > 0 ? (uint32_t)P.n_paths : 0u;
+		for (uint32_t round = 0; live != 0; round++) {
+			const NeeStream& in = st[round & 1u];
+			const NeeStream& out = st[(round + 1u) & 1u];
+			IntersectArgs A{};
+			A.n = live;
+			A.ox = in.ox; A.oy = in.oy; A.oz = in.oz; A.dx = in.dx; A.dy = in.dy; A.dz = in.dz;
+			A.distance = hits; A.surface = (int32_t*)(hits + cap); A.triangle = (int32_t*)(hits + 2 * cap);
+			A.b0 = hits + 3 * cap; A.b1 = hits + 4 * cap; A.b2 = hits + 5 * cap;
+			if (const int rc = intersect_device(c, sc, A); rc != PTX_OK) return rc;
+			rays += live;
+			const NeeHits H{A.distance, A.surface, A.triangle, A.b1, A.b2};
+			HIP_TRY(hipMemsetAsync(cnt, 0, 8, c->stream));
+			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, in, H, live, out, W, cnt, Lrec, c->stream));
+			uint32_t got[2] = {0, 0};   // continuations, shadow rays
+			HIP_TRY(hipMemcpyAsync(got, cnt, 8, hipMemcpyDeviceToHost, c->stream));
+			HIP_TRY(hipStreamSynchronize(c->stream));
+			if (got[0] > live || got[1] > 2ull * live) return set_err(PTX_ERR_HIP, "ptx_render_nee: a round appended more entries than its paths allow");
+			if (got[1]) {
+				IntersectArgs B{};
+				B.n = got[1];
+				B.ox = W.ox; B.oy = W.oy; B.oz = W.oz; B.dx = W.dx; B.dy = W.dy; B.dz = W.dz;
+				B.distance = shits; B.surface = (int32_t*)(shits + 2 * cap); B.triangle = (int32_t*)(shits + 4 * cap);
+				B.b0 = shits + 6 * cap; B.b1 = shits + 8 * cap; B.b2 = shits + 10 * cap;
+				if (const int rc = intersect_device(c, sc, B); rc != PTX_OK) return rc;
+				rays += got[1];
+				const NeeHits SH{B.distance, B.surface, B.triangle, B.b1, B.b2};
+				HIP_TRY(launch_nee_settle(in, live, W, SH, out, cnt, Lrec, c->stream));
+				if (catchers) {
+					HIP_TRY(hipMemcpyAsync(got, cnt, 4, hipMemcpyDeviceToHost, c->stream));
+					HIP_TRY(hipStreamSynchronize(c->stream));
+					if (got[0] > live) return set_err(PTX_ERR_HIP, "ptx_render_nee: a round appended more entries than its paths allow");
+				}
+			}
+			live = got[0];
+		}
+		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
+		HIP_TRY(launch_resolve(Lrec, d_accum, d_pixels, P.n_pixels, P.pass_spp, c->stream));
+	}
+	if (!dev_accum) HIP_TRY(hipMemcpyAsync(accum, d_accum, rect_pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+	if (stats || !dev_accum) HIP_TRY(hipStreamSynchronize(c->stream));
+	if (stats) {
+		unsigned long long ls[2] = {0, 0};
+		HIP_TRY(hipMemcpy(ls, cnt + 2, 16, hipMemcpyDeviceToHost));
+		stats->light_samples = ls[0]; stats->light_visible = ls[1];
+		stats->render.rays = rays;
+		stats->render.samples = (uint64_t)cfg->spp * n_pixels;
+		stats->render.passes = n_pass;
+		for (uint32_t p = 0; p < n_pass; p++) {
+			float t = 0;
+			HIP_TRY(hipEventElapsedTime(&t, c->events[2 * p], c->events[2 * p + 1]));
+			stats->render.kernel_ms += t;
 		}
 	}
 	return PTX_OK;

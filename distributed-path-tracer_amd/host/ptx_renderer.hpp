@@ -137,6 +137,25 @@ public:
 		return a;
 	}
 
+	// Radiance sums [H][W][4] of the frame with next-event estimation towards the scene's emissive triangles (ptx_render_nee): render_accum()'s
+	// samples plus one MIS-weighted light sample per continuing vertex; the same expectation, less noise where emitters light the scene.
+	// Write them with encode(sums, sample_count). stats optional
+	std::vector<float> render_nee(ptx_nee_stats* stats = nullptr) const {
+		if (!scene_) throw std::runtime_error("render_nee() before load_gltf()");
+		if (transparent_background) throw std::runtime_error("render_nee: transparent_background's blend is not built on this estimator");
+		if (environment.string() != env_set_) {
+			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
+			env_set_ = environment.string();
+		}
+		ptx_render_cfg c{};
+		c.W = resolution.x; c.H = resolution.y; c.spp = sample_count; c.bounces = bounce_count;
+		for (int k = 0; k < 3; k++) c.env[k] = environment_factor[k];
+		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
+		std::vector<float> accum((size_t)c.W * c.H * 4, 0.f);
+		check(ptx_render_nee(scene_, &c, nullptr, accum.data(), stats));
+		return accum;
+	}
+
 	std::vector<uint8_t> render() const {   // renderer.cpp:334-428: PNG bytes (RGBA8, ACES tonemap, sRGB)
 		return encode(render_accum(), transparent_background ? 1u : sample_count);
 	}

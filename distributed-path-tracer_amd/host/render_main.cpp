@@ -1,6 +1,6 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--denoise] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--nee] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
 //       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
 //       --adaptive THR[:MIN[:STEP]]: noise-driven per-pixel sample counts (renderer::render_adaptive) with spp as the cap: every pixel gets MIN
@@ -33,13 +33,14 @@ static void write_png(const std::string& path, const std::vector<uint8_t>& rgba,
 }
 
 int main(int argc, char** argv) {
-	bool transparent = false, denoise = false, adaptive = false;
+	bool transparent = false, denoise = false, adaptive = false, nee = false;
 	float ad_thr = 0.1f;
 	unsigned ad_min = 8, ad_step = 0;
 	std::string aov_prefix;
 	for (;;) {   // leading switches
 		if (argc > 1 && std::string(argv[1]) == "--transparent") { transparent = true; argv[1] = argv[0]; argv++; argc--; }
 		else if (argc > 1 && std::string(argv[1]) == "--denoise") { denoise = true; argv[1] = argv[0]; argv++; argc--; }
+		else if (argc > 1 && std::string(argv[1]) == "--nee") { nee = true; argv[1] = argv[0]; argv++; argc--; }   // renderer::render_nee: light sampling
 		else if (argc > 2 && std::string(argv[1]) == "--adaptive") {
 			if (std::sscanf(argv[2], "%f:%u:%u", &ad_thr, &ad_min, &ad_step) < 1) { std::fprintf(stderr, "error: --adaptive THR[:MIN[:STEP]]\n"); return 1; }
 			adaptive = true; argv[2] = argv[0]; argv += 2; argc -= 2;
@@ -48,7 +49,7 @@ int main(int argc, char** argv) {
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (argc == 5 && std::string(argv[1]) == "--event") {
@@ -91,7 +92,10 @@ int main(int argc, char** argv) {
 		ptx_adaptive_stats ast{};
 		r.adaptive_threshold = ad_thr; r.adaptive_min = ad_min; r.adaptive_step = ad_step;
 		if (adaptive && denoise) throw std::runtime_error("--adaptive and --denoise do not combine: the filter takes one sample count per buffer");
-		std::vector<uint8_t> png = adaptive ? r.encode(r.render_adaptive(&ast), 1) : denoise ? r.encode(r.render_denoised(&dst), 1) : r.render();
+		ptx_nee_stats nst{};
+		if (nee && (adaptive || denoise || transparent)) throw std::runtime_error("--nee does not combine with --adaptive, --denoise or --transparent");
+		std::vector<uint8_t> png = nee ? r.encode(r.render_nee(&nst), r.sample_count)
+		                               : adaptive ? r.encode(r.render_adaptive(&ast), 1) : denoise ? r.encode(r.render_denoised(&dst), 1) : r.render();
 		double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 		std::ofstream(argv[2], std::ios::binary).write((const char*)png.data(), (std::streamsize)png.size());
 		double aov_ms = 0;
@@ -119,6 +123,9 @@ int main(int argc, char** argv) {
 		if (adaptive)
 			std::printf(", \"adaptive_mean_spp\": %.3f, \"adaptive_rounds\": %u, \"adaptive_active_last\": %u, \"adaptive_select_ms\": %.3f",
 			            (double)ast.render.samples / ((double)r.resolution.x * r.resolution.y), ast.rounds, ast.active_last, ast.select_ms);
+		if (nee)
+			std::printf(", \"nee_lights\": %u, \"nee_light_samples\": %llu, \"nee_light_visible\": %llu, \"nee_kernel_ms\": %.3f", nst.n_lights,
+			            (unsigned long long)nst.light_samples, (unsigned long long)nst.light_visible, nst.render.kernel_ms);
 		std::printf("}\n");
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "error: %s\n", e.what());

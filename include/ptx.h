@@ -145,7 +145,11 @@ typedef enum ptx_array {
 	PTX_ARR_TEXTURES = 13,    /* uint32[n_textures][4]: width, height, channels | srgb << 8 | float << 16, byte offset into TEXELS (float offset into TEXELS_F32) */
 	PTX_ARR_TEXELS = 14,      /* uint8[]: 8-bit texels of all textures (rows top to bottom, as decoded) */
 	PTX_ARR_SURF_TEX = 15,    /* int32[n_surfaces][7]: texture id per material slot (normal, albedo, opacity, occlusion, roughness, metallic, emissive), -1 = none */
-	PTX_ARR_TEXELS_F32 = 16   /* float[]: texels of Radiance .hdr images (TEXTURES entries with bit 16 of the third word; their offset counts floats here) */
+	PTX_ARR_TEXELS_F32 = 16,  /* float[]: texels of Radiance .hdr images (TEXTURES entries with bit 16 of the third word; their offset counts floats here) */
+	/* the light list of ptx_render_nee (built at the first request, on host-only scenes too) */
+	PTX_ARR_LIGHT_TRIS = 17,  /* uint32[n_lights][2]: surface, triangle index within the surface's mesh */
+	PTX_ARR_LIGHT_CDF = 18,   /* float[n_lights]: cumulative share of the listed area, the last entry 1 */
+	PTX_ARR_LIGHT_GEOM = 19   /* float[n_lights][4]: geometric normal (world), area (world) */
 } ptx_array;
 int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, size_t dst_bytes);
 
@@ -334,6 +338,49 @@ int ptx_adaptive_select(ptx_ctx* ctx, uint32_t w, uint32_t h, const float* accum
  * out.c = a.c / a.w. A pixel of zero count gives NaNs. out_rgba [n_pixels][4] may be accum_a or accum_b itself; all pointers device or all
  * host. PTX_ERR_INVALID for a NULL ctx, accum_a or out_rgba, n_pixels above 2^31 - 1, or pointers of mixed kinds. */
 int ptx_accum_mean(ptx_ctx* ctx, const float* accum_a, const float* accum_b /* NULL ok */, size_t n_pixels, float* out_rgba);
+
+/* Next-event estimation towards emissive triangles (no counterpart in the reference, whose estimators collect emission only where a
+ * BSDF-sampled ray happens to hit an emitter). ptx_render_nee renders the samples of ptx_render with the PTX_INTEGRATOR_LIB estimator plus
+ * one light sample per continuing vertex: same cfg fields, Philox keys and camera rays, sums in ptx_render's accum format, alpha + 1 per
+ * sample. The light sample is combined with the BSDF-sampled emission by the balance heuristic so that ITS EXPECTATION IS LIB'S.
+ * LIB's clamp T *= clamp(brdf / max(pdf, eps), 0, 1) means LIB integrates brdf' = qc * pe with pe = max(pdf, eps) and
+ * qc = clamp(brdf / pe, 0, 1) per channel; the light sample uses the same brdf' and introduces no other clamp.
+ * A vertex runs LIB's rules exactly as ptx_render has them (miss and environment, opacity pass-through with pass + 1 and the 4096 bound,
+ * back face, sun request, shadow catcher pending then pass-through, last vertex, T update, depth++, pass = 0). Two things change:
+ *   EMISSION WEIGHT. L += (T * emissive10) * w. w = 1 (no arithmetic) when depth == 0, or pass > 0 (the ray came through a surface: no
+ *     light sample can produce that path), or the hit triangle is not listed. Otherwise w = p_prev / (p_prev + p_l) with
+ *     p_l = (dist * dist) / (cg * A_total), cg = |dot(ng, d)|, ng the listed triangle's geometric normal, dist the hit distance and
+ *     p_prev the pe of the direction sampled at the previous vertex.
+ *   LIGHT SAMPLE, at every vertex that reaches LIB's BSDF sample, before it and whatever its outcome (a last vertex takes none; none at
+ *     all when the list is empty): r = draws(pixel, sample, depth, pass, block 3); triangle i = the first with r.x < cdf[i] (index clamped
+ *     to n - 1); su = sqrt(r.y), beta = su * (1 - r.z), gamma = su * r.z; position pos_y, shading normal n_y and Le = 10 * emissive(uv) of
+ *     the point (beta, gamma) of triangle i, as a hit there would give them; v = pos_y - pos_x, dist2 = dot(v, v), w = v / sqrt(dist2).
+ *     No contribution and no shadow ray unless dist2 > 0, dot(n_x, w) > 0, dot(n_y, -w) > 0, cg = |dot(ng_i, w)| > 0 and max(Le) > 0.
+ *     brdf, pdf = LIB's BSDF value for w with the vertex's own specular probability and roughness; pe = max(pdf, eps),
+ *     qc = clamp(brdf / pe, 0, 1), p_l = dist2 / (cg * A_total), wl = pe / (pe + p_l); x = ((T * qc) * wl) * Le with T before its update.
+ *     The shadow ray (origin pos_x + w * eps, direction w) is a CLOSEST-hit query on the scene's route; x is added iff that hit is
+ *     triangle i of that surface (identity, no distance epsilon).
+ * Order of the additions of one sample, fixed and without float atomics: vertex k's emission, its sun term if unoccluded, its light term
+ * if visible, then vertex k + 1. With an empty list every w is exactly 1 and no light term exists: the frame is bitwise ptx_render's.
+ * THE LIGHT LIST (PTX_ARR_LIGHT_*): a surface is listed iff its emissive factor has a positive component, it cannot pass a sample
+ * through (constant opacity approximately 1, no texture feeding opacity) and it is not a shadow catcher; unlisted emitters keep w = 1, so
+ * nothing is lost or counted twice. Per listed surface in surface order and triangle in mesh order, in float64: world corners, area =
+ * |e1 x e2| / 2 (a triangle whose area is not > 0 is left out), ng = normalize(e1 x e2), running sum; stored as float32.
+ * Tiles, sample0, spp_per_pass, shard_*, host or device accum and bounces == 0 work as in ptx_render.
+ * Refusals, all decided before any device work: PTX_ERR_UNSUPPORTED for PTX_INTEGRATOR_WORKER; PTX_ERR_NO_DEVICE for a host-only scene;
+ * PTX_ERR_INVALID for NULL scene, cfg or accum, unknown flags and whatever ptx_render refuses in cfg.
+ * Out of scope: ptx_render_transparent's blend, ptx_render_adaptive on this estimator, the worker estimator, sampling the environment
+ * map, and multigpu.py (its shards and sample ranges already compose through the accum format). */
+#define PTX_NEE_NO_LIGHT_SAMPLES 1u   /* run with an empty list */
+typedef struct ptx_nee_cfg { uint32_t flags; } ptx_nee_cfg;
+typedef struct ptx_nee_stats {
+	ptx_render_stats render;   /* rays = closest-hit + shadow queries */
+	uint32_t n_lights;         /* listed triangles */
+	float light_area;          /* A_total */
+	uint64_t light_samples, light_visible;   /* light shadow rays traced, and how many found their triangle */
+} ptx_nee_stats;
+int ptx_render_nee(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_nee_cfg* ncfg /* NULL = defaults */, float* accum_rgba,
+                   ptx_nee_stats* stats /* NULL ok */);
 
 /* Measurement aid (no counterpart in the reference): where the time of the last ptx_render that was given a stats pointer went.
  * Scenes whose geometry fits the LDS or whose models have few surfaces run ONE fused kernel per pass (pipeline 0: fused_ms);
