@@ -28,7 +28,9 @@ NO_SUN_LIGHT = 0xFFFFFFFF  # core::renderer::no_sun_light, renderer.hpp:19
 
 (ARR_MODEL_XFORM, ARR_MODEL_AABB, ARR_MODEL_SURF, ARR_SURF_RANGE, ARR_MESH_AABB, ARR_VERTICES, ARR_TRIANGLES,
  ARR_MATERIALS, ARR_KD_NODES, ARR_KD_REFS, ARR_CAMERA, ARR_SUN, ARR_MODEL_NAMES, ARR_TEXTURES, ARR_TEXELS, ARR_SURF_TEX, ARR_TEXELS_F32,
- ARR_LIGHT_TRIS, ARR_LIGHT_CDF, ARR_LIGHT_GEOM) = range(20)
+ ARR_LIGHT_TRIS, ARR_LIGHT_CDF, ARR_LIGHT_GEOM, ARR_TRI_ISECT, ARR_RES_NODES, ARR_RES_REFS, ARR_RES_TRIS, ARR_LDS_ROOT,
+ ARR_RES_PLAN) = range(26)
+LDS_LEAF_ORDER_BIT = 0x80000000  # ARR_LDS_ROOT: the surface's resident records are leaf-ordered (flat_scene.hpp)
 
 
 class PtxError(RuntimeError):
@@ -287,7 +289,8 @@ class Context:
 
     def leaf_intersect(self, corners, rays, refs=None, leaf_ordered=False):
         """ptx_leaf_intersect_batch: the fused kernels' leaf loop on one leaf holding the triangles corners [n_tri,9] (a, b, c), tested in
-        the order of refs (a permutation, None = identity), in the per-triangle layout behind refs or the leaf-ordered one; rays [n,7]
+        the order of refs (a permutation, None = identity), in the per-triangle layout behind refs (leaf_ordered 0 / False), the
+        leaf-ordered one in global memory (1 / True) or the leaf-ordered one staged into LDS (2); rays [n,7]
         float32 (origin, unit direction, max_dist). -> {"t", "beta", "gamma": float32 [n], "triangle": int32 [n], -1 = miss}."""
         c = np.ascontiguousarray(corners, np.float32).reshape(-1, 9)
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 7)
@@ -296,7 +299,7 @@ class Context:
             raise ValueError("refs must hold one reference per triangle")
         out = np.zeros((len(r), 3), np.float32)
         tri = np.full(len(r), -1, np.int32)
-        _check(lib().ptx_leaf_intersect_batch(self.h, c.ctypes.data, len(c), None if p is None else p.ctypes.data, int(bool(leaf_ordered)),
+        _check(lib().ptx_leaf_intersect_batch(self.h, c.ctypes.data, len(c), None if p is None else p.ctypes.data, int(leaf_ordered),
                                               r.ctypes.data, len(r), out.ctypes.data, tri.ctypes.data))
         return {"t": out[:, 0].copy(), "beta": out[:, 1].copy(), "gamma": out[:, 2].copy(), "triangle": tri}
 
@@ -366,7 +369,9 @@ _ARR_DTYPE = {ARR_MODEL_XFORM: (np.float32, 12), ARR_MODEL_AABB: (np.float32, 6)
               ARR_TRIANGLES: (np.uint32, 3), ARR_MATERIALS: (np.float32, 11), ARR_KD_NODES: (np.uint32, 2),
               ARR_KD_REFS: (np.uint32, 1), ARR_CAMERA: (np.float32, 1), ARR_SUN: (np.float32, 1),
               ARR_TEXTURES: (np.uint32, 4), ARR_TEXELS: (np.uint8, 1), ARR_SURF_TEX: (np.int32, 7), ARR_TEXELS_F32: (np.float32, 1),
-              ARR_LIGHT_TRIS: (np.uint32, 2), ARR_LIGHT_CDF: (np.float32, 1), ARR_LIGHT_GEOM: (np.float32, 4)}
+              ARR_LIGHT_TRIS: (np.uint32, 2), ARR_LIGHT_CDF: (np.float32, 1), ARR_LIGHT_GEOM: (np.float32, 4),
+              ARR_TRI_ISECT: (np.uint32, 12), ARR_RES_NODES: (np.uint32, 2), ARR_RES_REFS: (np.uint32, 1), ARR_RES_TRIS: (np.uint32, 12),
+              ARR_LDS_ROOT: (np.uint32, 1), ARR_RES_PLAN: (np.uint32, 1)}
 
 
 class Scene:

@@ -119,7 +119,8 @@ struct Geom {
 	const float4* tris;   // TriIsect records, three float4 each (flat_scene.hpp)
 	// true (global-memory kernels): `tris` holds one record per LEAF REFERENCE, in leaf order, with the triangle id in its
 	// spare word — a leaf's records are contiguous and the refs -> record indirection (a second dependent fetch from
-	// L2/HBM per triangle) disappears. false (LDS kernels): one record per triangle, reached through `refs`.
+	// L2/HBM per triangle) disappears. false: one record per triangle, reached through `refs`. The LDS copy holds surfaces of
+	// both kinds; mesh_traverse_m sets the flag per surface (lds_geom).
 	bool leaf_ordered;
 	// true (the global-memory copy): a branch node's two children (adjacent, 16 bytes) are requested as soon as the parent arrives
 	bool pair;
@@ -250,6 +251,41 @@ DEV bool aabb_test_box(const float* b, V3 o, V3 inv, float& nr, float& fr) {
 	return fr >= 0;
 }
 
+// One trip through a leaf: the nearest triangle among its `count` records that is hit within max_dist, the first one on a tie.
+// Geom::leaf_ordered (wave-uniform: the copy and, in LDS, the surface decide it) says where record i is: at first + i, or behind the
+// reference first + i — a dependent read in front of the record's. PTX_LEAF_ONE_LOOP: one loop that selects per record instead of a
+// scalar branch in front of two loops (measurement; profiles/EXPERIMENTS.md, round 9).
+template <bool SHORT, bool LO>
+DEV void leaf_records(const Geom& g, uint32_t first, uint32_t count, const PRay& pr, float max_dist, float& best_t, float& bb1, float& bb2,
+                      uint32_t& best_tri, uint32_t& key) {
+	for (uint32_t i = 0; i < count; i++) {
+		const uint32_t slot = LO ? first + i : g.refs[first + i];
+		const float4 r0 = g.tris[3 * slot], r1 = g.tris[3 * slot + 1], r2 = g.tris[3 * slot + 2];
+		float be, ga;
+		const float t = tri_test_pk<SHORT>(r0, r1, make_float2(r2.x, r2.y), pr, be, ga, key);
+		if (t >= 0 && t <= max_dist && (t < best_t || !(best_t >= 0))) { best_t = t; bb1 = be; bb2 = ga; best_tri = __float_as_uint(r2.z); }   // r2.z: global triangle id, carried by every record
+	}
+}
+template <bool SHORT, int PB>
+DEV void leaf_trip(const Geom& g, uint32_t first, uint32_t count, const PRay& pr, float max_dist, float& best_t, float& bb1, float& bb2,
+                   uint32_t& best_tri, uint32_t& key PROF_ARG) {
+#ifdef PTX_PROF
+	if (SHORT) for (uint32_t i = 0; i < count; i++) PROF(PB + 3);
+#endif
+#ifdef PTX_LEAF_ONE_LOOP
+	for (uint32_t i = 0; i < count; i++) {
+		const uint32_t slot = g.leaf_ordered ? first + i : g.refs[first + i];
+		const float4 r0 = g.tris[3 * slot], r1 = g.tris[3 * slot + 1], r2 = g.tris[3 * slot + 2];
+		float be, ga;
+		const float t = tri_test_pk<SHORT>(r0, r1, make_float2(r2.x, r2.y), pr, be, ga, key);
+		if (t >= 0 && t <= max_dist && (t < best_t || !(best_t >= 0))) { best_t = t; bb1 = be; bb2 = ga; best_tri = __float_as_uint(r2.z); }
+	}
+#else
+	if (g.leaf_ordered) leaf_records<SHORT, true>(g, first, count, pr, max_dist, best_t, bb1, bb2, best_tri, key);
+	else leaf_records<SHORT, false>(g, first, count, pr, max_dist, best_t, bb1, bb2, best_tri, key);
+#endif
+}
+
 // core::mesh::intersect — core/mesh.cpp:300-405: front-to-back stack traversal, returns at the first
 // leaf that yields a hit within [.., max_dist].
 // Stack entries are (node, min_dist) only; the max_dist the reference stores with an entry is rebuilt at the pop as the
@@ -340,24 +376,10 @@ DEV bool mesh_traverse(const Geom& g, uint32_t root, float nr, float fr, V3 o, V
 		uint32_t key = 0;
 		// (a software-pipelined form of this loop — triangle i + 1's reference and record requested before triangle i's solve — was
 		// measured: -2.7 % on Cornell, +2 % on jack-of-blades; the extra registers cost more than the latency 4 waves already hide)
-		for (uint32_t i = 0; i < count; i++) {
-			PROF(PB + 3);
-			const uint32_t slot = g.leaf_ordered ? first_ref + i : g.refs[first_ref + i];
-			const float4 r0 = g.tris[3 * slot], r1 = g.tris[3 * slot + 1], r2 = g.tris[3 * slot + 2];
-			const uint32_t ti = __float_as_uint(r2.z);   // global triangle id, carried by every record
-			float be, ga;
-			const float t = tri_test_pk<true>(r0, r1, make_float2(r2.x, r2.y), pr, be, ga, key);
-			if (t >= 0 && t <= max_dist && (t < best_t || !(best_t >= 0))) { best_t = t; bb1 = be; bb2 = ga; best_tri = ti; }
-		}
+		leaf_trip<true, PB>(g, first_ref, count, pr, max_dist, best_t, bb1, bb2, best_tri, key PROF_PASS);
 		if (key >= kRcpKeyEnd) {   // a determinant outside rcp_core's range: this lane's leaf once more, every triangle with the IEEE division
 			best_t = -1.0f; bb1 = 0; bb2 = 0; best_tri = 0;
-			for (uint32_t i = 0; i < count; i++) {
-				const uint32_t slot = g.leaf_ordered ? first_ref + i : g.refs[first_ref + i];
-				const float4 r0 = g.tris[3 * slot], r1 = g.tris[3 * slot + 1], r2 = g.tris[3 * slot + 2];
-				float be, ga;
-				const float t = tri_test_pk<false>(r0, r1, make_float2(r2.x, r2.y), pr, be, ga, key);
-				if (t >= 0 && t <= max_dist && (t < best_t || !(best_t >= 0))) { best_t = t; bb1 = be; bb2 = ga; best_tri = __float_as_uint(r2.z); }
-			}
+			leaf_trip<false, PB>(g, first_ref, count, pr, max_dist, best_t, bb1, bb2, best_tri, key PROF_PASS);
 		}
 		if (!(best_t >= 0)) continue;
 		out.t = best_t; out.b1 = bb1; out.b2 = bb2; out.tri = best_tri;
@@ -365,13 +387,16 @@ DEV bool mesh_traverse(const Geom& g, uint32_t root, float nr, float fr, V3 o, V
 	}
 }
 
+// The LDS copy as one resident surface lays it out: SurfaceRec::lds_root carries the layout of the surface's records in bit 31
+// (plan_residency). The surface record is scalar-loaded, so the flag is wave-uniform.
+DEV Geom lds_geom(const Geom& lds, uint32_t lds_root) { return {lds.nodes, lds.refs, lds.tris, (lds_root & kLdsLeafOrderBit) != 0, lds.pair}; }
 // core::mesh::intersect on whichever copy of the surface's tree the scene's MODE prescribes; (nr, fr) from the box test
 template <int MODE, int PB>
 DEV bool mesh_traverse_m(const Geoms& G, const SurfaceRec& sf, float nr, float fr, V3 o, V3 d, MeshHit& out, const Spill& spill PROF_ARG) {
 	if constexpr (MODE == MODE_GLOBAL) return mesh_traverse<PB>(G.glb, sf.kd_root, nr, fr, o, d, out, spill PROF_PASS);
-	else if constexpr (MODE == MODE_LDS) return mesh_traverse<PB>(G.lds, sf.lds_root, nr, fr, o, d, out, spill PROF_PASS);
+	else if constexpr (MODE == MODE_LDS) return mesh_traverse<PB>(lds_geom(G.lds, sf.lds_root), sf.lds_root & ~kLdsLeafOrderBit, nr, fr, o, d, out, spill PROF_PASS);
 	else {
-		if (sf.lds_root != 0xFFFFFFFFu) return mesh_traverse<PB>(G.lds, sf.lds_root, nr, fr, o, d, out, spill PROF_PASS);
+		if (sf.lds_root != 0xFFFFFFFFu) return mesh_traverse<PB>(lds_geom(G.lds, sf.lds_root), sf.lds_root & ~kLdsLeafOrderBit, nr, fr, o, d, out, spill PROF_PASS);
 		return mesh_traverse<PB>(G.glb, sf.kd_root, nr, fr, o, d, out, spill PROF_PASS);
 	}
 }

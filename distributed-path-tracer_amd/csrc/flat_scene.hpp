@@ -70,12 +70,14 @@ struct SurfaceRec {
 	float bmin[3], bmax[3];  // mesh AABB (mesh.cpp:254-261)
 	uint32_t kd_root;        // index of the root KD node in the full node array
 	uint32_t tri_base;       // global id of the mesh's triangle 0
-	uint32_t lds_root;       // index of the root in the LDS-resident node array, 0xFFFFFFFF when the surface is not resident
+	uint32_t lds_root;       // 0xFFFFFFFF when the surface is not resident (tested first); else bits 30:0 = index of the root in the LDS-resident
+	                         // node array, bit 31 (kLdsLeafOrderBit) = its resident records are leaf-ordered (plan_residency)
 	uint32_t model;          // the model this surface belongs to
 	float pbmin[3], pbmax[3];  // mesh AABB grown by the reach of the barycentric slack (see ModelRec)
 	float box[6], pbox[6];     // both boxes as (min, max) pairs per axis (see ModelRec)
 };
 static_assert(sizeof(SurfaceRec) == 28 * 4, "SurfaceRec layout");
+constexpr uint32_t kLdsLeafOrderBit = 0x80000000u;
 template <class Rec> inline void interleave_boxes(Rec& r) {
 	for (int k = 0; k < 3; k++) { r.box[2 * k] = r.bmin[k]; r.box[2 * k + 1] = r.bmax[k]; r.pbox[2 * k] = r.pbmin[k]; r.pbox[2 * k + 1] = r.pbmax[k]; }
 }
@@ -157,8 +159,8 @@ struct FlatScene {
 
 	// LDS residency plan (plan_residency): the traversal arrays of the surfaces that fit one CU's LDS, indices local to them
 	std::vector<KdNode> res_nodes;
-	std::vector<uint32_t> res_refs;      // indices into res_tris
-	std::vector<TriIsect> res_tris;      // p0 = global triangle id
+	std::vector<uint32_t> res_refs;      // indices into res_tris (ref-indexed surfaces only)
+	std::vector<TriIsect> res_tris;      // p0 = global triangle id; per triangle (ref-indexed surface) or per leaf reference (leaf-ordered one)
 	uint32_t n_resident = 0;             // surfaces with SurfaceRec::lds_root valid
 	size_t res_bytes = 0;                // LDS bytes the resident arrays + shade records take
 
@@ -166,8 +168,12 @@ struct FlatScene {
 };
 
 // Chooses which surfaces are staged into LDS (smallest first, while they fit `lds_budget` together with the shade records)
-// and builds their compact arrays; sets SurfaceRec::lds_root. All surfaces resident => the compact arrays equal the full ones.
-void plan_residency(FlatScene& s, size_t lds_budget);
+// and builds their compact arrays; sets SurfaceRec::lds_root. With `lds_leaf_order`, the resident surfaces whose records cost little
+// more per leaf reference than per triangle get the leaf-ordered layout (bit 31 of lds_root): their leaves index res_tris directly, one
+// record per reference, and they add nothing to res_refs. Ref-indexed surfaces keep one record per triangle behind res_refs. The two
+// kinds share the three arrays, so the compact arrays differ from the full ones even when every surface is resident.
+constexpr size_t kLdsLeafOrderCap = 4096;   // bytes the leaf-ordered layouts may cost together: 28 hot hit records (144 B) at the most
+void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order = true);
 
 // Builds everything derived (AABBs, KD-trees, records) from the "as loaded" arrays + camera/sun floats.
 // camera13: origin(3) basis(9) fov ; sun13: basis(9) energy(3) angular_radius or nullptr.

@@ -645,6 +645,7 @@ __global__ void k_pbr_eval(const float* __restrict__ in, float* __restrict__ out
 // ray runs the leaf loop — the short solve, its rcp_key bookkeeping and the IEEE re-test of the leaf — over triangles of the caller's
 // choosing (ptx_leaf_intersect_batch). leaf_ordered = 0: the layout of the LDS-resident copy, staged into LDS here as well: one record per
 // triangle, reached through `refs`. 1: the layout of the global-memory copy: one record per leaf reference, the id in its spare word.
+// 2: the layout of a leaf-ordered surface of the LDS-resident copy: the records of 1, staged into LDS, no references.
 // rays [n][7]: origin, direction, max_dist (the traversal starts with nr = 0, fr = max_dist); out [n][3]: t, beta, gamma (-1, 0, 0 on a
 // miss); tri [n]: the triangle id, -1 on a miss.
 __global__ void __launch_bounds__(256) k_leaf_intersect(const uint2* __restrict__ nodes, const uint32_t* __restrict__ refs, const float4* __restrict__ tris, uint32_t n_tri,
@@ -653,13 +654,13 @@ __global__ void __launch_bounds__(256) k_leaf_intersect(const uint2* __restrict_
 	__shared__ float4 s_tris[3 * kLeafBatchMaxTris];
 	__shared__ uint32_t s_refs[kLeafBatchMaxTris];
 	__shared__ uint2 s_node;
-	if (!leaf_ordered) {
+	if (leaf_ordered != 1u) {
 		for (uint32_t k = threadIdx.x; k < 3u * n_tri; k += blockDim.x) s_tris[k] = tris[k];
-		for (uint32_t k = threadIdx.x; k < n_tri; k += blockDim.x) s_refs[k] = refs[k];
+		if (!leaf_ordered) for (uint32_t k = threadIdx.x; k < n_tri; k += blockDim.x) s_refs[k] = refs[k];
 		if (threadIdx.x == 0) s_node = nodes[0];
 		__syncthreads();
 	}
-	const Geom g = leaf_ordered ? Geom{nodes, refs, tris, true, true} : Geom{&s_node, s_refs, s_tris, false, false};
+	const Geom g = leaf_ordered == 1u ? Geom{nodes, refs, tris, true, true} : Geom{&s_node, s_refs, s_tris, leaf_ordered == 2u, false};
 	const Spill spill{spill_base + (size_t)(blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6)) * (kSpillStack * 64) + (threadIdx.x & 63u)};
 #ifdef PTX_PROF
 	Prof prof{};
@@ -825,9 +826,9 @@ hipError_t launch_pbr_eval(const float* in, float* out, size_t n, hipStream_t st
 	hipLaunchKernelGGL(k_pbr_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, out, n);
 	return hipGetLastError();
 }
-hipError_t launch_leaf_intersect(const uint2* nodes, const uint32_t* refs, const float4* tris, uint32_t n_tri, bool leaf_ordered, const float* rays, size_t n, float* out,
+hipError_t launch_leaf_intersect(const uint2* nodes, const uint32_t* refs, const float4* tris, uint32_t n_tri, uint32_t leaf_ordered, const float* rays, size_t n, float* out,
                                  int32_t* tri, uint2* spill, int grid, hipStream_t stream) {
-	hipLaunchKernelGGL(k_leaf_intersect, dim3(grid), dim3(256), 0, stream, nodes, refs, tris, n_tri, leaf_ordered ? 1u : 0u, rays, n, out, tri, spill);
+	hipLaunchKernelGGL(k_leaf_intersect, dim3(grid), dim3(256), 0, stream, nodes, refs, tris, n_tri, leaf_ordered, rays, n, out, tri, spill);
 	return hipGetLastError();
 }
 hipError_t launch_exact_math_check(unsigned long long* bad, hipStream_t stream) {

@@ -171,7 +171,7 @@ hipError_t launch_intersect(const DevScene& S, const IntersectArgs& A, int mode,
 hipError_t launch_pbr_eval(const float* in, float* out, size_t n, hipStream_t stream);
 constexpr uint32_t kLeafBatchMaxTris = 256;   // k_leaf_intersect: triangles of its one leaf at most (48 bytes each in LDS)
 // `spill`: [grid * 4 waves][kSpillWords]; grid workgroups of 256 threads
-hipError_t launch_leaf_intersect(const uint2* nodes, const uint32_t* refs /* [n_tri] */, const float4* tris /* [n_tri][3] */, uint32_t n_tri, bool leaf_ordered,
+hipError_t launch_leaf_intersect(const uint2* nodes, const uint32_t* refs /* [n_tri] */, const float4* tris /* [n_tri][3] */, uint32_t n_tri, uint32_t leaf_ordered /* 0 refs + LDS, 1 leaf order in global memory, 2 leaf order in LDS */,
                                  const float* rays /* [n][7] */, size_t n, float* out /* [n][3] */, int32_t* tri /* [n] */, uint2* spill, int grid, hipStream_t stream);
 constexpr uint32_t kExactMathForms = 3;   // k_exact_math_check: one counter per form
 hipError_t launch_exact_math_check(unsigned long long* bad /* [kExactMathForms], device, zeroed */, hipStream_t stream);

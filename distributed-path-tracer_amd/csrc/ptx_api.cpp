@@ -113,6 +113,8 @@ struct ptx_scene {
 	double lds_area_share = 0;     // share of the surfaces' box area (sum over surfaces) that belongs to LDS-resident surfaces: how much of what a ray can enter is served from LDS
 	double wf_pairs_per_ray = 0;   // queue-based pipeline: pairs (ray, entered surface) per ray seen so far on this scene, 0 = not yet measured
 	bool leaf_ordered = true; // global-memory copy of the triangle records: per leaf reference (true) or per triangle (false)
+	int lds_leaf_order = -1;  // LDS-resident copy: leaf-ordered records for the surfaces where they are cheap (1) or all ref-indexed (0); -1 = not decided yet
+	size_t lds_budget = 0;    // what plan_residency may fill (decide_mode)
 	int mode = MODE_GLOBAL;   // where the traversal arrays live: MODE_GLOBAL / MODE_LDS / MODE_HYBRID (kernels.hip)
 	size_t lds_bytes = 0;     // dynamic LDS of the kernels (resident arrays + shade records)
 	// The light list of ptx_render_nee (build_lights): built at the first call that asks for it, then kept. Host copies serve
@@ -135,7 +137,15 @@ size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 // Residency plan -> kernel family. PTX_FORCE_GLOBAL / PTX_NO_HYBRID: measurement switches.
 void decide_mode(ptx_scene* sc) {
 	FlatScene& h = sc->host;
-	plan_residency(h, kLdsBudget);
+	// PTX_LDS_LEAF_ORDER=0/1: the resident copy all ref-indexed / leaf-ordered where it is cheap (the default); PTX_LDS_BUDGET: a smaller
+	// budget for the residency plan, in bytes (measurement and tests; read once, here)
+	if (sc->lds_leaf_order < 0) {
+		const char* e = getenv("PTX_LDS_LEAF_ORDER");
+		sc->lds_leaf_order = (e && e[0] == '0') ? 0 : 1;
+		sc->lds_budget = kLdsBudget;
+		if (const char* b = getenv("PTX_LDS_BUDGET")) sc->lds_budget = std::min<size_t>(kLdsBudget, (size_t)strtoull(b, nullptr, 10));
+	}
+	plan_residency(h, sc->lds_budget, sc->lds_leaf_order != 0);
 	if (getenv("PTX_FORCE_GLOBAL") || h.n_resident == 0) sc->mode = MODE_GLOBAL;
 	else if (h.n_resident == h.surfaces.size()) sc->mode = MODE_LDS;
 	else sc->mode = getenv("PTX_NO_HYBRID") ? MODE_GLOBAL : MODE_HYBRID;
@@ -675,6 +685,18 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 	case PTX_ARR_LIGHT_TRIS: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.tris.data(); bytes = ll.tris.size() * 4; break; }
 	case PTX_ARR_LIGHT_CDF: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.cdf.data(); bytes = ll.cdf.size() * 4; break; }
 	case PTX_ARR_LIGHT_GEOM: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.geom.data(); bytes = ll.geom.size() * 4; break; }
+	case PTX_ARR_TRI_ISECT: src = h.tri_isect.data(); bytes = h.tri_isect.size() * sizeof(TriIsect); break;
+	case PTX_ARR_RES_NODES: src = h.res_nodes.data(); bytes = h.res_nodes.size() * 8; break;
+	case PTX_ARR_RES_REFS: src = h.res_refs.data(); bytes = h.res_refs.size() * 4; break;
+	case PTX_ARR_RES_TRIS: src = h.res_tris.data(); bytes = h.res_tris.size() * sizeof(TriIsect); break;
+	case PTX_ARR_LDS_ROOT:
+		for (auto& s : h.surfaces) { float f; memcpy(&f, &s.lds_root, 4); tmp.push_back(f); }
+		src = tmp.data(); bytes = tmp.size() * 4; break;
+	case PTX_ARR_RES_PLAN: {
+		const uint32_t w[4] = {(uint32_t)h.res_bytes, h.n_resident, (uint32_t)sc->lds_bytes, (uint32_t)h.hot_hitrec.size()};
+		tmp.resize(4); memcpy(tmp.data(), w, 16);
+		src = tmp.data(); bytes = 16; break;
+	}
 	default: set_err(PTX_ERR_INVALID, "unknown array id"); return -1;
 	}
 	if (dst) {
@@ -1917,7 +1939,7 @@ int ptx_leaf_intersect_batch(ptx_ctx* c, const float* corners, uint32_t n_tri, c
 	HIP_TRY(c->spill.ensure((size_t)c->n_cu * 4 * (size_t)kSpillWords * sizeof(uint2)));
 	float* d_out = (float*)c->stage_b.p;
 	int32_t* d_tri = (int32_t*)(d_out + 3 * n);
-	HIP_TRY(launch_leaf_intersect((const uint2*)in, (const uint32_t*)(in + refs_off), (const float4*)(in + recs_off), n_tri, leaf_ordered != 0,
+	HIP_TRY(launch_leaf_intersect((const uint2*)in, (const uint32_t*)(in + refs_off), (const float4*)(in + recs_off), n_tri, leaf_ordered == 0 ? 0u : (leaf_ordered == 2 ? 2u : 1u),
 	                              (const float*)(in + rays_off), n, d_out, d_tri, (uint2*)c->spill.p, grid, c->stream));
 	HIP_TRY(hipMemcpyAsync(out, d_out, n * 12, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipMemcpyAsync(tri, d_tri, n * 4, hipMemcpyDeviceToHost, c->stream));

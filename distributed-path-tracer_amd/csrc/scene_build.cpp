@@ -12,6 +12,7 @@
 #include "flat_scene.hpp"
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -413,7 +414,7 @@ void finalize_scene(FlatScene& s, const float* cam, const float* sun) {
 	}
 }
 
-void plan_residency(FlatScene& s, size_t lds_budget) {
+void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order) {
 	const size_t n_surf = s.surfaces.size();
 	s.res_nodes.clear(); s.res_refs.clear(); s.res_tris.clear();
 	s.n_resident = 0;
@@ -433,20 +434,52 @@ void plan_residency(FlatScene& s, size_t lds_budget) {
 		used += bytes_of(si);
 		take[si] = 1;
 	}
-	for (size_t si = 0; si < n_surf; si++) {   // original surface order: with everything resident the copy is the identity
+	// Layout of each resident surface's records. Ref-indexed: one record per triangle behind the leaf references. Leaf-ordered: one record
+	// per leaf REFERENCE, in leaf order, and no references — a leaf trip then reads its records at first + i instead of through a dependent
+	// LDS read of the reference. That costs (refs - triangles) * 48 - refs * 4 bytes more (less, where no leaf shares a triangle), so it goes
+	// to the surfaces where it is cheapest, while the positive extras together stay within kLdsLeafOrderCap and within what the residency
+	// choice above left of the budget: every byte spent here is taken from the hot hit records (upload_scene), at most 28 of them at the
+	// cap. Residency itself is never changed by this.
+	std::vector<char> leaf_order(n_surf, 0);
+	if (lds_leaf_order) {
+		auto extra_of = [&](size_t si) {
+			const int32_t* rg = &s.surf_range[8 * si];
+			return ((int64_t)rg[7] - rg[3]) * 48 - (int64_t)rg[7] * 4;
+		};
+		std::vector<size_t> cand;
+		for (size_t si = 0; si < n_surf; si++) if (take[si]) cand.push_back(si);
+		std::stable_sort(cand.begin(), cand.end(), [&](size_t a, size_t b) { return extra_of(a) < extra_of(b); });   // ties: surface index
+		const int64_t cap = (int64_t)std::min(kLdsLeafOrderCap, lds_budget > used ? lds_budget - used : (size_t)0);
+		int64_t spent = 0;
+		for (size_t si : cand) {
+			const int64_t e = extra_of(si);
+			if (e > 0) {
+				if (spent + e > cap) break;
+				spent += e;
+			}
+			leaf_order[si] = 1;
+		}
+	}
+	for (size_t si = 0; si < n_surf; si++) {   // original surface order
 		if (!take[si]) continue;
 		const int32_t* rg = &s.surf_range[8 * si];
 		const uint32_t t0 = (uint32_t)rg[2], nt = (uint32_t)rg[3], node0 = (uint32_t)rg[4], nn = (uint32_t)rg[5], ref0 = (uint32_t)rg[6], nr = (uint32_t)rg[7];
 		const uint32_t nb = (uint32_t)s.res_nodes.size(), rb = (uint32_t)s.res_refs.size(), tb = (uint32_t)s.res_tris.size();
 		for (uint32_t k = 0; k < nn; k++) {
 			KdNode nd = s.kd_nodes[node0 + k];
-			if ((nd.w1 & 3u) == KD_LEAF) nd.w0 = nd.w0 - ref0 + rb;                         // first ref
+			if ((nd.w1 & 3u) == KD_LEAF) nd.w0 = nd.w0 - ref0 + (leaf_order[si] ? tb : rb);  // first record (leaf order) / first ref
 			else nd.w1 = (nd.w1 & 15u) | ((((nd.w1 >> 4) - node0) + nb) << 4);              // first child
 			s.res_nodes.push_back(nd);
 		}
-		for (uint32_t k = 0; k < nr; k++) s.res_refs.push_back(s.kd_refs[ref0 + k] - t0 + tb);
-		for (uint32_t k = 0; k < nt; k++) s.res_tris.push_back(s.tri_isect[t0 + k]);
-		s.surfaces[si].lds_root = (s.surfaces[si].kd_root - node0) + nb;
+		if (leaf_order[si]) {
+			for (uint32_t k = 0; k < nr; k++) s.res_tris.push_back(s.tri_isect[s.kd_refs[ref0 + k]]);
+		} else {
+			for (uint32_t k = 0; k < nr; k++) s.res_refs.push_back(s.kd_refs[ref0 + k] - t0 + tb);
+			for (uint32_t k = 0; k < nt; k++) s.res_tris.push_back(s.tri_isect[t0 + k]);
+		}
+		const uint32_t root = (s.surfaces[si].kd_root - node0) + nb;
+		assert(root < kLdsLeafOrderBit);   // a resident tree fits LDS: a few thousand nodes
+		s.surfaces[si].lds_root = root | (leaf_order[si] ? kLdsLeafOrderBit : 0u);
 		s.n_resident++;
 	}
 	s.res_bytes = s.res_tris.size() * 48 + shade_bytes + ((s.res_nodes.size() * 8 + 15) & ~(size_t)15) + ((s.res_refs.size() * 4 + 15) & ~(size_t)15);

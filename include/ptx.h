@@ -149,7 +149,17 @@ typedef enum ptx_array {
 	/* the light list of ptx_render_nee (built at the first request, on host-only scenes too) */
 	PTX_ARR_LIGHT_TRIS = 17,  /* uint32[n_lights][2]: surface, triangle index within the surface's mesh */
 	PTX_ARR_LIGHT_CDF = 18,   /* float[n_lights]: cumulative share of the listed area, the last entry 1 */
-	PTX_ARR_LIGHT_GEOM = 19   /* float[n_lights][4]: geometric normal (world), area (world) */
+	PTX_ARR_LIGHT_GEOM = 19,  /* float[n_lights][4]: geometric normal (world), area (world) */
+	/* the LDS residency plan (read-only; what the fused kernels stage into each CU's LDS) */
+	PTX_ARR_TRI_ISECT = 20,   /* uint32[n_triangles][12]: the 48-byte intersection records, one per triangle (bit patterns; word 10 = triangle id,
+	                           * on an uploaded scene | hot-record slot << 24) */
+	PTX_ARR_RES_NODES = 21,   /* uint32[.][2]: KD nodes of the resident surfaces; a leaf's first word indexes RES_REFS (ref-indexed surface)
+	                           * or RES_TRIS (leaf-ordered surface) */
+	PTX_ARR_RES_REFS = 22,    /* uint32[.]: leaf references of the ref-indexed resident surfaces, indices into RES_TRIS */
+	PTX_ARR_RES_TRIS = 23,    /* uint32[.][12]: resident records: one per triangle (ref-indexed surface) or per leaf reference (leaf-ordered) */
+	PTX_ARR_LDS_ROOT = 24,    /* uint32[n_surfaces]: 0xFFFFFFFF = not resident, else root index in RES_NODES | leaf-ordered << 31 */
+	PTX_ARR_RES_PLAN = 25     /* uint32[4]: bytes of the resident arrays + shade records, resident surfaces, dynamic LDS bytes of the fused
+	                           * kernels (0 on a host-only scene), hot hit records */
 } ptx_array;
 int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, size_t dst_bytes);
 
@@ -449,7 +459,8 @@ int ptx_pbr_eval_batch(ptx_ctx* ctx, const float* in, size_t n, float* out);
  * and the kernel calls the traversal on a tree of one leaf holding all n_tri triangles (1 <= n_tri <= 256), so the short reciprocal,
  * its range bookkeeping and the IEEE re-test of the whole leaf are the shipped ones.
  * corners[n_tri][9]: a, b, c;  refs[n_tri]: the leaf's reference list, a permutation of 0 .. n_tri-1 (NULL: the identity);
- * leaf_ordered = 0: one record per triangle behind the references (the LDS-resident layout), != 0: one record per reference, in
+ * leaf_ordered = 0: one record per triangle behind the references (the ref-indexed LDS-resident layout), 2: one record per reference,
+ * in leaf order, staged into LDS without references (the leaf-ordered LDS-resident layout), any other value: one record per reference, in
  * leaf order, carrying its triangle id (the global-memory layout);  rays[n_rays][7]: origin, unit direction, max_dist.
  * out[n_rays][3]: t, beta, gamma (-1, 0, 0 on a miss);  triangle[n_rays]: index into corners, -1 on a miss. Host memory only. */
 int ptx_leaf_intersect_batch(ptx_ctx* ctx, const float* corners, uint32_t n_tri, const uint32_t* refs, int leaf_ordered, const float* rays, size_t n_rays,
