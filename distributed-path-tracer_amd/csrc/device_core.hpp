@@ -196,7 +196,15 @@ constexpr int kSpillStack = 24; // deeper entries go to a per-lane overflow area
 struct Spill { uint2* base; };
 constexpr uint32_t kNoNode = 0xFFFFFFFFu;   // node of a placeholder entry (mesh_traverse)
 DEV void spill_put(const Spill& sp, int k, uint32_t node, float m) { sp.base[k * 64] = make_uint2(node, __float_as_uint(m)); }
-DEV void spill_get(const Spill& sp, int k, uint32_t& node, float& m) { uint2 v = sp.base[k * 64]; node = v.x; m = __uint_as_float(v.y); }
+// The pair is consumed (by an empty asm) where it is loaded, inside the caller's rare `sp >= kRegStack` branch, so the wait for the load
+// sits in that branch. Left pending, it reaches the join, and since the pair is first read a whole pop later the compiler puts
+// s_waitcnt vmcnt(0) in front of every later write of (n2, m2) — the pop, the start of every walk, the next surface's box test — where
+// it also waits for every store the wave has in flight (vmcnt counts them too).
+DEV void spill_get(const Spill& sp, int k, uint32_t& node, float& m) {
+	uint2 v = sp.base[k * 64];
+	asm volatile("" : "+v"(v.x), "+v"(v.y));
+	node = v.x; m = __uint_as_float(v.y);
+}
 
 // geometry::aabb::intersect with the reciprocal direction hoisted: the same local ray is tested against the
 // model box and every surface box, and 1/dir has one value per ray whatever box it meets.

@@ -131,6 +131,11 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 						qin[3 * kChunk + i] = make_float4(0.f, __uint_as_float(0u), __uint_as_float(py * P.W + px), __uint_as_float(P.sample0 + s_local));
 					} else {
 						float4 q0 = qin[i], q1 = qin[kChunk + i];
+						// the entry is consumed where it is loaded (an empty asm), so that no path leaves this block with the loads pending: left to
+						// their first use, they put s_waitcnt vmcnt(0) at the head of the loop — where it waits for the previous wave-iteration's
+						// hit-record store before this one's loads are even issued — and in front of the model loop, where at step 0 it waits
+						// for the four stores of the camera ray
+						asm volatile("" : "+v"(q0.x), "+v"(q0.y), "+v"(q0.z), "+v"(q1.x), "+v"(q1.y), "+v"(q1.z));
 						o = mk(q0.x, q0.y, q0.z);
 						d = mk(q1.x, q1.y, q1.z);
 					}
