@@ -1,4 +1,4 @@
-// Kernel argument blocks and launchers shared by kernels.hip and ptx_api.cpp.
+// Kernel argument blocks and launchers shared by the .hip files and the C ABI (ptx_api.cpp, api_render.cpp, api_batch.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

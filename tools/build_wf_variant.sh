@@ -7,5 +7,5 @@ C=$(dirname $0)/../distributed-path-tracer_amd/csrc; O=$C/build/var_$name; mkdir
 F="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-unroll-loops -fno-slp-vectorize $*"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 $F -c -o $O/wavefront.o $C/wavefront.hip
 B=$C/build
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $C/../exp/libptx_$name.so $B/kernels.o $O/wavefront.o $B/ptx_api.o $B/scene_build.o $B/gltf_load.o $B/png_read.o $B/jpeg_read.o $B/hdr_read.o -lz
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $C/../exp/libptx_$name.so $B/kernels.o $O/wavefront.o $B/aov.o $B/nee.o $B/denoise.o $B/adaptive.o $B/ptx_api.o $B/api_render.o $B/api_batch.o $B/scene_build.o $B/gltf_load.o $B/png_read.o $B/jpeg_read.o $B/hdr_read.o -lz
 echo built exp/libptx_$name.so
