@@ -110,6 +110,7 @@ class NeeStats(C.Structure):
 
 
 NEE_NO_LIGHT_SAMPLES = 1   # ptx_nee_cfg.flags
+NEE_FUSED = 4              # one kernel launch per pass where render() runs the fused kernel; ignored on the queue route
 
 
 class KernelTiming(C.Structure):
@@ -530,7 +531,9 @@ class Scene:
                    want_stats=True, integrator=INTEGRATOR_LIB, shard=None, flags=0):
         """ptx_render_nee: render()'s samples with the LIB estimator plus one light sample towards the listed emissive triangles per
         continuing vertex, MIS-weighted (include/ptx.h has the estimator). ADDS radiance SUMS into accum as render() does; tiles, sample
-        ranges and shards compose the same way. flags: NEE_NO_LIGHT_SAMPLES runs with an empty list (bitwise render()'s frame).
+        ranges and shards compose the same way. flags: NEE_NO_LIGHT_SAMPLES runs with an empty list (bitwise render()'s frame);
+        NEE_FUSED renders each pass with one kernel launch where render() runs its fused kernel (bitwise the unflagged frame; ignored on
+        scenes of the queue route).
         Returns (accum, stats dict or None)."""
         x0, y0, w, h = tile if tile else (0, 0, W, H)
         if accum is None:
@@ -701,9 +704,10 @@ class Renderer:
                                                                      env=self.environment_factor, seed=self.seed)
         return self._ctx.accum_mean(a, b, out=a)
 
-    def render_nee(self):
+    def render_nee(self, flags=0):
         """Radiance SUMS [H,W,4] of the frame with next-event estimation towards the scene's emissive triangles (Scene.render_nee):
-        render_accum()'s samples plus one MIS-weighted light sample per continuing vertex. `last_nee_stats` holds the stats."""
+        render_accum()'s samples plus one MIS-weighted light sample per continuing vertex. flags: ptx_nee_cfg.flags (NEE_FUSED: the same
+        frame from one kernel launch per pass). `last_nee_stats` holds the stats."""
         if self._scene is None:
             raise PtxError(ERR_INVALID, "render_nee() before load_gltf()")
         if self.transparent_background:
@@ -712,7 +716,8 @@ class Renderer:
         if self.environment != getattr(self, "_env_set", None):
             self._scene.set_environment(self.environment)
             self._env_set = self.environment
-        accum, self.last_nee_stats = self._scene.render_nee(W, H, self.sample_count, self.bounce_count, env=self.environment_factor, seed=self.seed)
+        accum, self.last_nee_stats = self._scene.render_nee(W, H, self.sample_count, self.bounce_count, env=self.environment_factor, seed=self.seed,
+                                                                    flags=flags)
         return accum
 
     def render(self):

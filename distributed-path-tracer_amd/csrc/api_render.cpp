@@ -651,11 +651,54 @@ int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffe
 	return PTX_OK;
 }
 
+namespace {
+
+// ptx_render_nee with PTX_NEE_FUSED on a scene of the fused route: one launch of k_nee_fused per pass, then the resolve. No round trips to the
+// host and no streams: the workspace is ptx_render's radiance records, overflow stacks and counters. The caller holds the context's mutex, has
+// set the device, planned the passes and uploaded the light list.
+int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeLights& Lt, float* accum, ptx_nee_stats* stats) {
+	const int grid = c->n_cu;
+	HIP_TRY(c->sample_rad.ensure((size_t)f.pass_spp * f.n_pixels * sizeof(float4)));
+	HIP_TRY(c->counters.ensure(1024));   // [0] chunk counter, [16] rays, [24] light samples, [32] visible light samples
+	HIP_TRY(c->spill.ensure((size_t)grid * (kBlock / 64) * (size_t)kSpillWords * sizeof(uint2)));
+	HIP_TRY(hipMemsetAsync(c->counters.p, 0, 1024, c->stream));
+	const NeeFusedBuffers B{(float4*)c->sample_rad.p, (uint2*)c->spill.p, (unsigned long long*)c->counters.p, (unsigned long long*)((char*)c->counters.p + 16)};
+	const bool dev_accum = is_device_ptr(accum);
+	Staged s_accum;
+	HIP_TRY(s_accum.bind(c, dev_accum, accum, f.rect_pixels() * sizeof(float4), c->stage_a));
+	if (stats)
+		if (const int rc = PassFrame::ensure_events(c, f.n_pass); rc != PTX_OK) return rc;
+	for (uint32_t p = 0; p < f.n_pass; p++) {
+		RenderParams P = f.params(p, true);
+		P.integrator = PTX_INTEGRATOR_LIB;
+		HIP_TRY(hipMemsetAsync(B.chunk_counter, 0, 8, c->stream));
+		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
+		HIP_TRY(launch_nee_fused(sc->dev, P, Lt, B, sc->mode, sc->lds_bytes, grid, c->stream));
+		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
+		HIP_TRY(launch_resolve(B.sample_rad, s_accum.as<float4>(), f.d_pixels, P.n_pixels, P.pass_spp, c->stream));
+	}
+	HIP_TRY(s_accum.copy_back(c));
+	if (stats || !dev_accum) HIP_TRY(hipStreamSynchronize(c->stream));
+	if (stats) {
+		unsigned long long cnt[3] = {0, 0, 0};   // rays, light samples, visible ones
+		HIP_TRY(hipMemcpy(cnt, B.counters, sizeof cnt, hipMemcpyDeviceToHost));
+		stats->light_samples = cnt[1]; stats->light_visible = cnt[2];
+		if (const int rc = f.stats(c, cnt[0], &stats->render); rc != PTX_OK) return rc;
+		c->timing.pipeline = 0u;
+		c->timing.workspace_bytes = c->spill.cap;
+		c->timing.fused_ms = stats->render.kernel_ms;
+		c->timing.fused_launches = f.n_pass;
+	}
+	return PTX_OK;
+}
+
+}  // namespace
+
 int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* ncfg, float* accum, ptx_nee_stats* stats) {
 	// every refusal below is decided before any device work
 	if (!sc || !cfg || !accum) return set_err(PTX_ERR_INVALID, "ptx_render_nee: NULL argument");
 	const uint32_t flags = ncfg ? ncfg->flags : 0u;
-	if (flags & ~(uint32_t)PTX_NEE_NO_LIGHT_SAMPLES) return set_err(PTX_ERR_INVALID, "ptx_render_nee: unknown flag");
+	if (flags & ~(uint32_t)(PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED)) return set_err(PTX_ERR_INVALID, "ptx_render_nee: unknown flag");
 	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
 		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_nee: PTX_INTEGRATOR_WORKER has no light sampling here (the estimator is defined on PTX_INTEGRATOR_LIB's vertex)");
 	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_nee: scene was created without a GPU context (no CPU path exists)");
@@ -669,9 +712,12 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 	const ptx_scene::LightList& ll = *build_lights(sc);
 	const uint32_t n_lights = (uint32_t)ll.cdf.size();
 	if (stats) { stats->n_lights = n_lights; stats->light_area = ll.area; }
-	// The workspace takes 68 words per sample, so by default a pass has 16 Mi samples (8 spp of a 1080p frame, 4.6 GB); at most 2^30, so that
-	// the positions of a round's shadow rays (two per path at most) stay below 2^31
-	if (const int rc = f.plan(c, sc, "ptx_render_nee", nullptr, 16ull << 20, 0x3FFFFFFFull); rc != PTX_OK || !f.n_pass) return rc;
+	// PTX_NEE_FUSED: one launch per pass wherever ptx_render would run the fused kernel; a scene of the queue route renders as without the flag
+	const bool fused = (flags & PTX_NEE_FUSED) != 0 && !use_wavefront(sc);
+	// The wavefront form's workspace takes 68 words per sample, so by default a pass has 16 Mi samples (8 spp of a 1080p frame, 4.6 GB); at most
+	// 2^30, so that the positions of a round's shadow rays (two per path at most) stay below 2^31. The fused form keeps only the 16-byte
+	// radiance record per sample: ptx_render's pass size and id limit.
+	if (const int rc = f.plan(c, sc, "ptx_render_nee", nullptr, fused ? 128ull << 20 : 16ull << 20, fused ? 0xFFFFFFFFull : 0x3FFFFFFFull); rc != PTX_OK || !f.n_pass) return rc;
 
 	NeeLights Lt{};
 	if (n_lights && !(flags & PTX_NEE_NO_LIGHT_SAMPLES)) {
@@ -690,6 +736,8 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 		Lt.tris = (const uint2*)sc->d_light_tris.p; Lt.cdf = (const float*)sc->d_light_cdf.p; Lt.geom = (const float4*)sc->d_light_geom.p;
 		Lt.surf_first = (const int32_t*)sc->d_light_first.p; Lt.n = n_lights; Lt.area = ll.area;
 	}
+
+	if (fused) return nee_fused_frame(c, sc, f, Lt, accum, stats);
 
 	// workspace of one pass of `cap` samples: [256 B: counters][radiance records][stream 0][stream 1][hits][shadow rays][shadow hits][shadow records]
 	const size_t cap = ((size_t)f.pass_spp * f.n_pixels + 3) & ~(size_t)3;   // array stride: keeps every array 16-byte aligned

@@ -237,6 +237,16 @@ hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeL
                             const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
 hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, hipStream_t stream);
 
+// The same estimator in one launch per pass (nee_fused.hip, PTX_NEE_FUSED): persistent workgroups as launch_render_pass sizes them, a lane per path,
+// no streams. The only per-sample memory is sample_rad.
+struct NeeFusedBuffers {
+	float4* sample_rad;                  // [pass_spp][n_pixels]: (L, 1) of every sample of the pass
+	uint2* spill;                        // [grid * kBlock / 64][kSpillWords]: traversal-stack overflow, lane-interleaved
+	unsigned long long* chunk_counter;   // paths handed out so far; zeroed before each pass
+	unsigned long long* counters;        // [3] accumulate: rays (closest + both shadow kinds), light samples, visible light samples
+};
+hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream);
+
 // Variance-guided a-trous filter (denoise.hip, ptx_denoise). All buffers [n_pixels] float4 on the device.
 // prepare: the two radiance sums and the guide sums -> col_var (demodulated colour, v0), guide (mean normal, mean depth), remod (albedo, alpha)
 hipError_t launch_denoise_prepare(const float4* a, const float4* b, const float4* albedo_cov, const float4* normal_depth, uint32_t spp_a, uint32_t spp_b, size_t n_pixels,

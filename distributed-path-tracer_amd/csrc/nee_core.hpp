@@ -1,0 +1,199 @@
+// The path vertex of ptx_render_nee (include/ptx.h has the estimator), shared by its two forms: k_nee_shade (nee.hip) loads the hit and the
+// path state from the round's arrays and stores what nee_vertex returns; k_nee_fused (nee_fused.hip) calls it on registers.
+// Numerics as in kernels.hip: IEEE binary32 in the written order, no contraction.
+#pragma once
+#include "device_core.hpp"
+
+namespace ptx {
+
+enum { BLOCK_LIGHT = 3 };   // Philox block of the light sample's draws (BLOCK_SURFACE / BLOCK_SUN / BLOCK_JITTER: device_core.hpp)
+
+// sample id within the pass (sample-major, pixel-minor) -> image pixel and global sample index, as k_render_pass enumerates them
+DEV void nee_sample_of(const RenderParams& P, uint32_t id, uint32_t& px, uint32_t& py, uint32_t& sample) {
+	const uint32_t s_local = id / P.n_pixels;
+	uint32_t p_local = id - s_local * P.n_pixels;
+	if (P.pixels) p_local = P.pixels[p_local];
+	px = P.x0 + p_local % P.w; py = P.y0 + p_local / P.w;
+	sample = P.sample0 + s_local;
+}
+
+// entry of (surface, local triangle) in the light list, or -1: the list is ordered by surface, then by triangle
+DEV int nee_find_light(const NeeLights& Lt, uint32_t surface, uint32_t tri) {
+	const int first = Lt.surf_first[surface];
+	if (first < 0) return -1;
+	uint32_t lo = (uint32_t)first, hi = Lt.n;   // the entry, if any, is in [lo, hi)
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo) / 2;
+		const uint2 e = Lt.tris[mid];
+		if (e.x < surface || (e.x == surface && e.y < tri)) lo = mid + 1; else hi = mid;
+	}
+	if (lo >= Lt.n) return -1;
+	const uint2 e = Lt.tris[lo];
+	return (e.x == surface && e.y == tri) ? (int)lo : -1;
+}
+
+// What a vertex leaves besides the path state: whether the path goes on, and its up-to-two shadow requests
+struct NeeVertex {
+	bool alive = false;         // the path continues with (o, d, T, p_prev, depth, pass) as the vertex left them
+	bool want_sun = false;      // sun ray (sun_o, sun_d): unoccluded adds sun_x = T * direct_out ...
+	bool catcher_req = false;   // ... or, a shadow catcher's: unoccluded lets the path through from sun_x, occluded ends it
+	bool want_light = false;    // light ray (lo, ld): lx is added iff its closest hit is triangle exp_tri of surface exp_surf
+	V3 sun_o = {0, 0, 0}, sun_d = {0, 0, 1}, sun_x = {0, 0, 0}, lo = {0, 0, 0}, ld = {0, 0, 1}, lx = {0, 0, 0};
+	uint32_t exp_surf = 0, exp_tri = 0;
+};
+
+// One vertex of one path. The hit: surface (< 0: miss), triangle within the surface's mesh, barycentrics b1, b2 and the world distance, as the
+// scene's intersect route reports them. TEX / ALPHA / SUN compile the texture lookups / the pass-through and catcher code / the sun request
+// in, as the render variants do. The statements are shade_vertex<SUN, ALPHA, TEX, false>'s, in its order, with the emission weighted and the
+// light sample taken before the BSDF sample. Returns whether L received a term (the record-based form stores its record then).
+template <bool TEX, bool ALPHA, bool SUN>
+DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& Lt, uint32_t pixel, uint32_t sample, int32_t surf, uint32_t tri, float b1, float b2,
+                    float hit_dist, V3& o, V3& d, V3& T, V3& L, float& p_prev, uint32_t& depth, uint32_t& pass, NeeVertex& out) {
+	bool& alive = out.alive;
+	bool& want_sun = out.want_sun;
+	bool& want_light = out.want_light;
+	bool& catcher_req = out.catcher_req;
+	V3 &sun_o = out.sun_o, &sun_d = out.sun_d, &sun_x = out.sun_x, &lo = out.lo, &ld = out.ld, &lx = out.lx;
+	uint32_t &exp_surf = out.exp_surf, &exp_tri = out.exp_tri;
+	bool store = false;
+	do {
+		if (surf < 0) {   // miss: environment
+			V3 env = mk(P.env[0], P.env[1], P.env[2]);
+			if constexpr (TEX) {
+				if (S.env_tex >= 0) {
+					const float4 e = tex_sample(S, S.env_tex, atan2f(d.z, d.x) * 0.1591F + 0.5F, asinf(d.y) * 0.3183F + 0.5F);
+					env = mk(e.x, e.y, e.z) * env;
+				}
+			}
+			L = L + T * env;
+			store = true;
+			break;
+		}
+		const ShadeRec& R = S.shade[surf];
+		Surf sf;
+		hit_attributes(S, R, tri + S.surfaces[surf].tri_base, b1, b2, sf);
+		const MaterialRec& mt = R.mat;
+		const MatEval me = material_eval<TEX>(S, mt, sf.u, sf.v);
+		float roughness = me.roughness;
+		const bool last = depth + 1 == P.bounces;
+		float4 rnd = make_float4(0, 0, 0, 0);
+		if (ALPHA || !last) rnd = draws(P, pixel, sample, depth, pass, BLOCK_SURFACE);
+		if constexpr (ALPHA) {
+			const bool transparent = !(me.opacity == 1.0f || fabsf(me.opacity - 1.0f) < kEps) && rnd.x > me.opacity;
+			if (transparent) {
+				o = sf.pos + d * kEps;
+				d = normalize(d);
+				pass++;
+				alive = pass <= 4096;
+				break;
+			}
+		}
+		const V3 normal = shading_normal(sf, me.normal_ts), outcoming = -d;
+		if (dot(normal, outcoming) <= 0) break;
+		roughness = pmax(roughness, 0.05F);
+		float spec_prob = 0;
+		if (!last || (SUN && S.sun.present)) {
+			spec_prob = fresnel_schlick(outcoming, reflect3(-outcoming, normal), mt.ior);
+			spec_prob = pmax(spec_prob, me.metallic);
+		}
+		if constexpr (SUN) {
+			const bool catcher = ALPHA && mt.shadow_catcher && depth == 0;
+			bool sampled = false;
+			V3 din = mk(0, 0, 0);
+			if (S.sun.present) {
+				const float4 sr = draws(P, pixel, sample, depth, pass, BLOCK_SUN);
+				V3 c = mulmv(S.sun.basis, mk(0, 0, 1));
+				c = rand_cone_vec(sr.x, cosf(sr.y * S.sun.angular_radius), c);
+				const V3 cn = normalize(c);
+				din = c;
+				sampled = dot(normal, c) > 0;
+				if (sampled) { sun_o = sf.pos + c * kEps; sun_d = cn; }
+			}
+			if (sampled) {
+				want_sun = true;
+				if (catcher) {   // the answer decides between the pass-through and the end of the path
+					catcher_req = true;
+					sun_x = sf.pos + d * kEps;
+					break;
+				}
+				float pdf_unused;
+				const V3 brdf = eval_brdf(normal, outcoming, din, me.albedo, roughness, me.metallic, spec_prob, pdf_unused);
+				const V3 e = mk(S.sun.energy[0], S.sun.energy[1], S.sun.energy[2]);
+				const float pdf = lerpf(1.0f, 1.0f, spec_prob);
+				const V3 v = brdf * e / pmax(pdf, kEps);
+				const V3 direct_out = mk(clampf(v.x, 0, e.x), clampf(v.y, 0, e.y), clampf(v.z, 0, e.z));
+				sun_x = T * direct_out;
+			}
+		}
+		// ---- emission, weighted against the light sample that could have produced this path
+		V3 em = T * me.emissive10;
+		if (Lt.n != 0 && depth != 0 && pass == 0) {
+			const int k = nee_find_light(Lt, (uint32_t)surf, tri);
+			if (k >= 0) {
+				const float4 g = Lt.geom[k];
+				const float cg = fabsf(dot(mk(g.x, g.y, g.z), d));
+				const float dist = hit_dist;
+				const float p_l = (dist * dist) / (cg * Lt.area);
+				em = em * (p_prev / (p_prev + p_l));
+			}
+		}
+		L = L + em;
+		store = true;
+		if (last) break;
+		// ---- light sample
+		if (Lt.n != 0) {
+			const float4 r = draws(P, pixel, sample, depth, pass, BLOCK_LIGHT);
+			uint32_t a = 0, b = Lt.n;   // first entry with r.x < cdf
+			while (a < b) {
+				const uint32_t mid = a + (b - a) / 2;
+				if (r.x < Lt.cdf[mid]) b = mid; else a = mid + 1;
+			}
+			const uint32_t k = a < Lt.n - 1 ? a : Lt.n - 1;
+			const float su = sqrt_exact(r.y), beta = su * (1 - r.z), gamma = su * r.z;
+			const uint2 lt = Lt.tris[k];
+			const ShadeRec& Ry = S.shade[lt.x];
+			Surf sy;
+			hit_attributes(S, Ry, lt.y + S.surfaces[lt.x].tri_base, beta, gamma, sy);
+			const MatEval my = material_eval<TEX>(S, Ry.mat, sy.u, sy.v);
+			const V3 n_y = shading_normal(sy, my.normal_ts), Le = my.emissive10;
+			const V3 v = sy.pos - sf.pos;
+			const float dist2 = dot(v, v);
+			if (dist2 > 0) {
+				const V3 w = v / sqrt_exact(dist2);
+				const float4 g = Lt.geom[k];
+				const float cg = fabsf(dot(mk(g.x, g.y, g.z), w));
+				if (dot(normal, w) > 0 && dot(n_y, -w) > 0 && cg > 0 && pmax(Le.x, pmax(Le.y, Le.z)) > 0) {
+					float pdf;
+					const V3 brdf = eval_brdf(normal, outcoming, w, me.albedo, roughness, me.metallic, spec_prob, pdf);
+					const float pe = pmax(pdf, kEps);
+					const V3 q = brdf / pe;
+					const V3 qc = mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));
+					const float p_l = dist2 / (cg * Lt.area);
+					const float wl = pe / (pe + p_l);
+					lx = ((T * qc) * wl) * Le;
+					lo = sf.pos + w * kEps;
+					ld = w;
+					exp_surf = lt.x; exp_tri = lt.y;
+					want_light = true;
+				}
+			}
+		}
+		// ---- BSDF sample
+		const V3 inc = importance_sample(rnd.y < spec_prob, rnd.z, rnd.w, normal, outcoming, roughness);
+		if (!(dot(normal, inc) > 0)) break;
+		float pdf;
+		const V3 brdf = eval_brdf(normal, outcoming, inc, me.albedo, roughness, me.metallic, spec_prob, pdf);
+		const float pe = pmax(pdf, kEps);
+		const V3 q = brdf / pe;
+		T = T * mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));
+		p_prev = pe;
+		o = sf.pos + inc * kEps;
+		d = normalize(inc);
+		depth++;
+		pass = 0;
+		alive = depth != P.bounces;
+	} while (false);
+	return store;
+}
+
+}  // namespace ptx

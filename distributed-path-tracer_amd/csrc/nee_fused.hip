@@ -1,0 +1,198 @@
+// ptx_render_nee in one launch per pass (PTX_NEE_FUSED): the estimator of nee.hip — the same vertex function, nee_core.hpp — without the
+// host-driven rounds and their streams. Persistent workgroups, one per CU, stage the geometry as k_render_pass does; after that every LANE
+// owns one path from its camera ray to its end: closest hit (scene_traverse), nee_vertex, the sun ray if the vertex asked for one, the light
+// ray if it asked for one, next vertex. The path state and the sample's radiance stay in registers; the only per-sample memory is the final
+// float4 (L, 1) of sample_rad[id], which k_resolve adds up as for every other renderer.
+// Work: a wave takes chunks of sample ids from the pass's counter (one 64-bit atomic per chunk, guided self-scheduling as in k_render_pass);
+// a lane whose path has ended takes the chunk's next unstarted id at the head of the loop (wave-uniform cursor + ballot + lane prefix
+// count), so waves stay full while paths die. Everything a sample computes is keyed by its id — pixel, sample index, Philox key — so which
+// lane runs it changes no bit, and L receives vertex k's emission, sun term and light term, then vertex k + 1's: the additions of the
+// record-based form in its order. The frame is bitwise that of the unflagged call.
+// Numerics as in kernels.hip: IEEE binary32 in the written order, no contraction.
+#include "nee_core.hpp"
+
+namespace ptx {
+
+// Threads per workgroup (one workgroup per CU) of a variant. One vertex's registers plus a traversal do not fit the 128 VGPRs of k_render_pass's
+// 1024-thread workgroup, so the kernel has launch bounds of its own: the largest workgroup at which the variant compiles WITHOUT scratch.
+// 768 threads = 3 waves per SIMD = 168 VGPRs hold the variants without texture and sun code (158-165 VGPRs); the others need 174-210 and
+// get 512 threads = 2 waves per SIMD = 256 VGPRs. Occupancy is what the kernel runs on (Cornell: 256 threads 185, 512 353, 768 465 Msamples/s;
+// DESIGN.md 5.7 has the resource table and the measurement). Staging is per workgroup and there is one workgroup per CU either way; the
+// overflow stacks are sized per wave slot of the larger k_render_pass workgroup. -DPTX_NEE_FUSED_BLOCK=n: one size for all (measurement).
+constexpr int nee_fused_block(bool tex, bool sun) {
+#ifdef PTX_NEE_FUSED_BLOCK
+	return PTX_NEE_FUSED_BLOCK;
+#else
+	return (tex || sun) ? 512 : 768;
+#endif
+}
+static_assert(nee_fused_block(false, false) % 64 == 0 && nee_fused_block(true, true) % 64 == 0 && nee_fused_block(false, false) <= kBlock && nee_fused_block(true, true) <= kBlock,
+              "whole waves, and the spill area is sized for kBlock / 64 waves per workgroup");
+
+DEV uint32_t wave_sum(uint32_t v) {
+	for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+	return v;   // lane 0 holds the sum
+}
+
+template <int MODE, bool TEX, bool ALPHA, bool SUN>
+__global__ void __launch_bounds__(nee_fused_block(TEX, SUN)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
+                                                              const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space) {
+	constexpr int kThreads = nee_fused_block(TEX, SUN);
+	DevScene S = S0;
+	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;  // see struct Tables
+	const Staged st = stage_geometry<MODE>(S, g_smem);
+	// S.hot_lds stays unset: nee_vertex names a triangle by its index within the mesh, as the intersect route reports it, and reads its hit record from S.tris
+	const Geoms g = st.g;
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t wave_slot = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+	const Spill spill{B.spill + (size_t)wave_slot * (kSpillStack * 64) + lane};
+	uint32_t rays = 0, light_samples = 0, light_visible = 0;   // of this lane
+
+	// wave-uniform: the chunk's ids [chunk_first + cursor, chunk_first + chunk_n) are unstarted; dry = the pass has no chunk left
+	uint32_t chunk_first = 0, chunk_n = 0, cursor = 0;
+	bool dry = false;
+	// the lane's path
+	bool have = false;
+	uint32_t id = 0, pixel = 0, sample = 0, depth = 0, pass = 0;
+	V3 o = {0, 0, 0}, d = {0, 0, 1}, T = {1, 1, 1}, L = {0, 0, 0};
+	float p_prev = 0;
+
+	for (;;) {
+		// ---------------- idle lanes take the next unstarted ids
+		for (;;) {
+			const uint64_t idle = __ballot(!have);
+			if (idle == 0 || dry) break;
+			if (cursor == chunk_n) {
+				// Guided self-scheduling (k_render_pass): full chunks while plenty of paths are left, then chunks that shrink with what remains
+				uint32_t first_lo = 0, first_hi = 0, take = 0;
+				if (lane == 0) {
+					const unsigned long long seen = __hip_atomic_load(B.chunk_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+					const unsigned long long left = seen < P.n_paths ? P.n_paths - seen : 0ull;
+					const unsigned long long n_waves = (unsigned long long)gridDim.x * (kThreads / 64);
+					unsigned long long want = P.n_paths >= 16ull * n_waves * kChunk ? (unsigned long long)kChunk : left / n_waves;
+					want = (want + 63ull) & ~63ull;
+					take = (uint32_t)(want < 128ull ? 128ull : (want > (unsigned long long)kChunk ? (unsigned long long)kChunk : want));
+					const unsigned long long f = atomicAdd(B.chunk_counter, (unsigned long long)take);
+					first_lo = (uint32_t)f; first_hi = (uint32_t)(f >> 32);
+				}
+				first_lo = __builtin_amdgcn_readfirstlane(first_lo);
+				first_hi = __builtin_amdgcn_readfirstlane(first_hi);
+				take = __builtin_amdgcn_readfirstlane(take);
+				const uint64_t first = ((uint64_t)first_hi << 32) | first_lo;
+				if (first >= P.n_paths) { dry = true; break; }
+				chunk_first = (uint32_t)first;
+				chunk_n = (uint32_t)((P.n_paths - first) < (uint64_t)take ? (P.n_paths - first) : take);
+				cursor = 0;
+				if (P.bounces == 0) {   // trace(0, ..) is black with alpha 1 (renderer.cpp:438-439): no vertex ever runs
+					for (uint32_t i = lane; i < chunk_n; i += 64) B.sample_rad[chunk_first + i] = make_float4(0.f, 0.f, 0.f, 1.0f);
+					cursor = chunk_n;
+					continue;
+				}
+			}
+			const uint32_t avail = chunk_n - cursor, n_idle = (uint32_t)__popcll(idle);
+			const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));   // idle lanes below this one
+			if (!have && rank < avail) {
+				id = chunk_first + cursor + rank;
+				uint32_t px, py;
+				nee_sample_of(P, id, px, py, sample);
+				pixel = py * P.W + px;
+				camera_ray(S, P, px, py, sample, o, d);
+				T = mk(1.0f, 1.0f, 1.0f); L = mk(0.f, 0.f, 0.f);
+				p_prev = 0.0f; depth = 0; pass = 0;
+				have = true;
+			}
+			cursor += n_idle < avail ? n_idle : avail;
+		}
+		if (__ballot(have) == 0) break;   // dry, and every path of the wave has ended
+
+		if (have) {
+			// ---------------- closest hit, as the intersect route reports it (write_hit_outputs)
+			SceneHit h;
+			const bool hit = scene_traverse<MODE>(S, g, o, d, h, spill);
+			rays++;
+			const int32_t surf = hit ? h.surface : -1;
+			const uint32_t tri = hit ? (h.tri & S.tri_id_mask) - S.surfaces[h.surface].tri_base : 0u;
+			NeeVertex v;
+			nee_vertex<TEX, ALPHA, SUN>(S, P, Lt, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v);
+			bool alive = v.alive;
+			// ---------------- the sun ray: occluded = any hit
+			if constexpr (SUN) {
+				if (v.want_sun) {
+					SceneHit sh;
+					const bool occluded = scene_traverse<MODE>(S, g, v.sun_o, v.sun_d, sh, spill);
+					rays++;
+					if (v.catcher_req) {
+						// lit catcher = fully transparent: same depth, next pass (the vertex left the path state as it found it); shadowed: the path ends with what it has
+						if (!occluded && pass + 1u <= 4096u) {
+							o = v.sun_x;
+							d = normalize(d);
+							pass++;
+							alive = true;
+						}
+					} else if (!occluded) {
+						L.x += v.sun_x.x; L.y += v.sun_x.y; L.z += v.sun_x.z;
+					}
+				}
+			}
+			// ---------------- the light ray: visible = its closest hit is the sampled triangle
+			if (v.want_light) {
+				SceneHit lh;
+				const bool lhit = scene_traverse<MODE>(S, g, v.lo, v.ld, lh, spill);
+				rays++;
+				light_samples++;
+				if (lhit && lh.surface == (int32_t)v.exp_surf && (int32_t)((lh.tri & S.tri_id_mask) - S.surfaces[lh.surface].tri_base) == (int32_t)v.exp_tri) {
+					light_visible++;
+					L.x += v.lx.x; L.y += v.lx.y; L.z += v.lx.z;
+				}
+			}
+			if (!alive) {
+				B.sample_rad[id] = make_float4(L.x, L.y, L.z, 1.0f);
+				have = false;
+			}
+		}
+	}
+
+	// the wave has run dry: its counts, one vector atomic per counter
+	const uint32_t r = wave_sum(rays), ls = wave_sum(light_samples), lv = wave_sum(light_visible);
+	if (lane == 0) {
+		if (r) atomicAdd(B.counters, (unsigned long long)r);
+		if (ls) atomicAdd(B.counters + 1, (unsigned long long)ls);
+		if (lv) atomicAdd(B.counters + 2, (unsigned long long)lv);
+	}
+}
+
+// ------------------------------------------------------------------------------------ launcher
+static hipError_t set_lds(const void* fn, size_t bytes) {
+	return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+template <int MODE, bool TEX, bool ALPHA, bool SUN>
+static hipError_t launch_nee_fused_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
+	if (MODE != MODE_GLOBAL) {
+		hipError_t e = set_lds(reinterpret_cast<const void*>(&k_nee_fused<MODE, TEX, ALPHA, SUN>), lds_bytes);
+		if (e != hipSuccess) return e;
+	}
+	hipLaunchKernelGGL((k_nee_fused<MODE, TEX, ALPHA, SUN>), dim3(grid), dim3(nee_fused_block(TEX, SUN)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces, S.spaces,
+	                   S.model_space);
+	return hipGetLastError();
+}
+
+// the variants of launch_nee_shade, per place of the geometry
+template <int MODE>
+static hipError_t launch_nee_fused_mode(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
+	const bool sun = S.sun.present != 0;
+	if (S.any_texture) {
+		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, true, true, true>(S, P, Lt, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, true, false>(S, P, Lt, B, lds_bytes, grid, stream);
+		return sun ? launch_nee_fused_variant<MODE, true, false, true>(S, P, Lt, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, false, false>(S, P, Lt, B, lds_bytes, grid, stream);
+	}
+	if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, false, true, true>(S, P, Lt, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, false, true, false>(S, P, Lt, B, lds_bytes, grid, stream);
+	return sun ? launch_nee_fused_variant<MODE, false, false, true>(S, P, Lt, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, false, false, false>(S, P, Lt, B, lds_bytes, grid, stream);
+}
+
+hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream) {
+	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS>(S, P, Lt, B, lds_bytes, grid, stream);
+	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID>(S, P, Lt, B, lds_bytes, grid, stream);
+	return launch_nee_fused_mode<MODE_GLOBAL>(S, P, Lt, B, lds_bytes, grid, stream);
+}
+
+}  // namespace ptx

@@ -139,8 +139,8 @@ public:
 
 	// Radiance sums [H][W][4] of the frame with next-event estimation towards the scene's emissive triangles (ptx_render_nee): render_accum()'s
 	// samples plus one MIS-weighted light sample per continuing vertex; the same expectation, less noise where emitters light the scene.
-	// Write them with encode(sums, sample_count). stats optional
-	std::vector<float> render_nee(ptx_nee_stats* stats = nullptr) const {
+	// Write them with encode(sums, sample_count). stats optional; flags: ptx_nee_cfg::flags (PTX_NEE_FUSED: the same frame from one kernel launch per pass)
+	std::vector<float> render_nee(ptx_nee_stats* stats = nullptr, uint32_t flags = 0) const {
 		if (!scene_) throw std::runtime_error("render_nee() before load_gltf()");
 		if (transparent_background) throw std::runtime_error("render_nee: transparent_background's blend is not built on this estimator");
 		if (environment.string() != env_set_) {
@@ -152,7 +152,8 @@ public:
 		for (int k = 0; k < 3; k++) c.env[k] = environment_factor[k];
 		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
 		std::vector<float> accum((size_t)c.W * c.H * 4, 0.f);
-		check(ptx_render_nee(scene_, &c, nullptr, accum.data(), stats));
+		const ptx_nee_cfg n{flags};
+		check(ptx_render_nee(scene_, &c, &n, accum.data(), stats));
 		return accum;
 	}
 

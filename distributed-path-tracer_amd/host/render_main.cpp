@@ -1,8 +1,10 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--denoise] [--nee] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
 //       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
+//       --nee:         light sampling towards the scene's emissive triangles (renderer::render_nee)
+//       --nee-fused:   --nee with one kernel launch per pass (PTX_NEE_FUSED): the same frame; ignored on scenes of the queue pipeline
 //       --adaptive THR[:MIN[:STEP]]: noise-driven per-pixel sample counts (renderer::render_adaptive) with spp as the cap: every pixel gets MIN
 //                      samples (8), then rounds of STEP (MIN) go to the pixels whose half-frames still disagree by more than THR
 //       --aov PREFIX:  also writes the denoiser's guide images PREFIX_albedo.png (mean albedo of the covered samples, alpha = coverage)
@@ -33,7 +35,7 @@ static void write_png(const std::string& path, const std::vector<uint8_t>& rgba,
 }
 
 int main(int argc, char** argv) {
-	bool transparent = false, denoise = false, adaptive = false, nee = false;
+	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false;
 	float ad_thr = 0.1f;
 	unsigned ad_min = 8, ad_step = 0;
 	std::string aov_prefix;
@@ -41,6 +43,7 @@ int main(int argc, char** argv) {
 		if (argc > 1 && std::string(argv[1]) == "--transparent") { transparent = true; argv[1] = argv[0]; argv++; argc--; }
 		else if (argc > 1 && std::string(argv[1]) == "--denoise") { denoise = true; argv[1] = argv[0]; argv++; argc--; }
 		else if (argc > 1 && std::string(argv[1]) == "--nee") { nee = true; argv[1] = argv[0]; argv++; argc--; }   // renderer::render_nee: light sampling
+		else if (argc > 1 && std::string(argv[1]) == "--nee-fused") { nee = nee_fused = true; argv[1] = argv[0]; argv++; argc--; }   // ... one launch per pass
 		else if (argc > 2 && std::string(argv[1]) == "--adaptive") {
 			if (std::sscanf(argv[2], "%f:%u:%u", &ad_thr, &ad_min, &ad_step) < 1) { std::fprintf(stderr, "error: --adaptive THR[:MIN[:STEP]]\n"); return 1; }
 			adaptive = true; argv[2] = argv[0]; argv += 2; argc -= 2;
@@ -49,7 +52,7 @@ int main(int argc, char** argv) {
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (argc == 5 && std::string(argv[1]) == "--event") {
@@ -94,7 +97,7 @@ int main(int argc, char** argv) {
 		if (adaptive && denoise) throw std::runtime_error("--adaptive and --denoise do not combine: the filter takes one sample count per buffer");
 		ptx_nee_stats nst{};
 		if (nee && (adaptive || denoise || transparent)) throw std::runtime_error("--nee does not combine with --adaptive, --denoise or --transparent");
-		std::vector<uint8_t> png = nee ? r.encode(r.render_nee(&nst), r.sample_count)
+		std::vector<uint8_t> png = nee ? r.encode(r.render_nee(&nst, nee_fused ? PTX_NEE_FUSED : 0u), r.sample_count)
 		                               : adaptive ? r.encode(r.render_adaptive(&ast), 1) : denoise ? r.encode(r.render_denoised(&dst), 1) : r.render();
 		double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 		std::ofstream(argv[2], std::ios::binary).write((const char*)png.data(), (std::streamsize)png.size());

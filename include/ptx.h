@@ -382,6 +382,16 @@ int ptx_accum_mean(ptx_ctx* ctx, const float* accum_a, const float* accum_b /* N
  * Out of scope: ptx_render_transparent's blend, ptx_render_adaptive on this estimator, the worker estimator, sampling the environment
  * map, and multigpu.py (its shards and sample ranges already compose through the accum format). */
 #define PTX_NEE_NO_LIGHT_SAMPLES 1u   /* run with an empty list */
+/* PTX_NEE_FUSED: render with ONE kernel launch per pass wherever ptx_render would run this scene on its fused kernel (pipeline 0: LDS-resident and
+ * hybrid scenes, global-memory scenes under PTX_WAVEFRONT=0): a lane carries a path from its camera ray to its end in registers, without the
+ * per-round host synchronisation and the 68 words of stream workspace per sample of the default form. The estimator above is the specification
+ * of both forms, order of the additions included: for every cfg, accum is bit for bit what the unflagged call leaves, and rays, samples,
+ * n_lights, light_area, light_samples and light_visible of the stats are equal. render.passes = the launches (the pass size and id limit are
+ * ptx_render's, since the only per-sample workspace is the 16-byte radiance record), render.kernel_ms = their event time; ptx_ctx_get_timing
+ * then reports pipeline 0, fused_launches == passes and fused_ms == kernel_ms. On a scene of the queue route (pipeline 1) the flag is ignored
+ * and the call runs exactly as without it (fused_launches == 0) — not a refusal, so a caller may always set it. May be combined with
+ * PTX_NEE_NO_LIGHT_SAMPLES. Value 2u is unassigned and refused as unknown. */
+#define PTX_NEE_FUSED 4u
 typedef struct ptx_nee_cfg { uint32_t flags; } ptx_nee_cfg;
 typedef struct ptx_nee_stats {
 	ptx_render_stats render;   /* rays = closest-hit + shadow queries */

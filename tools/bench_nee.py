@@ -6,6 +6,10 @@
                                         a warm-up call), Msamples/s, and the mean squared error of the written bytes (the product's own
                                         image write, bytes / 255) against the product's ref_spp ptx_render frame (4096) of another seed;
                                         next to it ptx_render at equal spp, and ptx_render at the spp that takes the same time.
+                                        The same for ptx_render_nee with PTX_NEE_FUSED (fused_*): its calls alternate with the unflagged
+                                        ones in the same process, each kept with the spread of its repeats (*_s_max), and with ptx_render at
+                                        the spp that takes the flagged call's time; fused_launches tells which route ran (0: the scene is on
+                                        the queue route, where the flag is ignored).
 Prints one JSON line per measurement. A scene without listed emitters (atrium) shows the cost of the wavefront form alone.
 """
 import importlib
@@ -41,17 +45,22 @@ def main(ref_spp, reps):
     def image(acc, spp):
         return ctx.tonemap_encode(acc, W, H, spp)[..., :3].astype(np.float64) / 255
 
-    def timed(call, spp):
-        """-> (seconds: the smallest of `reps` synchronised calls after one warm-up, the last call's buffer and stats)"""
-        best, acc, st = 1e30, None, None
+    def timed(calls, spp):
+        """calls: {key: call}, run alternately -> {key: (seconds: the smallest of `reps` synchronised calls after one warm-up, the largest of
+        them, the last call's buffer and stats)}"""
+        out = {k: [1e30, 0.0, None, None] for k in calls}
         for rep in range(reps + 1):
-            acc = zeros()
-            t0 = time.perf_counter()
-            _, st = call(spp, acc)
-            ctx.synchronize()
-            if rep:
-                best = min(best, time.perf_counter() - t0)
-        return best, acc, st
+            for k, call in calls.items():
+                acc = zeros()
+                t0 = time.perf_counter()
+                _, st = call(spp, acc)
+                ctx.synchronize()
+                dt = time.perf_counter() - t0
+                if rep:
+                    out[k][0] = min(out[k][0], dt)
+                    out[k][1] = max(out[k][1], dt)
+                out[k][2:] = [acc, st]
+        return out
 
     for name, make in scenes.items():
         s = make()
@@ -67,18 +76,30 @@ def main(ref_spp, reps):
         def nee(spp, acc):
             return s.render_nee(W, H, spp, BOUNCES, accum=acc, seed=SEED)
 
+        def fused(spp, acc):
+            r = s.render_nee(W, H, spp, BOUNCES, accum=acc, seed=SEED, flags=ptx.NEE_FUSED)
+            fused.launches = ctx.timing()["fused_launches"]
+            return r
+
         def lib(spp, acc):
             return s.render(W, H, spp, BOUNCES, accum=acc, seed=SEED)
         for spp in (16, 64):
-            t_nee, a_nee, st = timed(nee, spp)
-            t_lib, a_lib, st_lib = timed(lib, spp)
-            spp_eq = max(1, int(round(spp * t_nee / t_lib)))
-            t_eq, a_eq, _ = timed(lib, spp_eq)
-            print(json.dumps(dict(scene=name, W=W, H=H, bounces=BOUNCES, spp=spp, n_lights=st["n_lights"], nee_s=round(t_nee, 4),
+            t = timed({"nee": nee, "fused": fused, "lib": lib}, spp)
+            (t_nee, t_nee_max, a_nee, st), (t_fus, t_fus_max, a_fus, st_fus), (t_lib, _, a_lib, st_lib) = t["nee"], t["fused"], t["lib"]
+            same = bool((a_fus == a_nee).all()) and all(st_fus[k] == st[k] for k in ("rays", "light_samples", "light_visible"))
+            spp_eq, spp_eq_f = max(1, int(round(spp * t_nee / t_lib))), max(1, int(round(spp * t_fus / t_lib)))
+            t_eq, _, a_eq, _ = timed({"lib": lib}, spp_eq)["lib"]
+            t_eq_f, _, a_eq_f, _ = timed({"lib": lib}, spp_eq_f)["lib"]
+            print(json.dumps(dict(scene=name, W=W, H=H, bounces=BOUNCES, spp=spp, n_lights=st["n_lights"], nee_s=round(t_nee, 4), nee_s_max=round(t_nee_max, 4),
                                   nee_msamples_s=round(W * H * spp / t_nee / 1e6, 1), nee_rays=st["rays"], nee_light_samples=st["light_samples"],
-                                  nee_light_visible=st["light_visible"], nee_mse=mse(a_nee, spp), lib_s=round(t_lib, 4),
+                                  nee_light_visible=st["light_visible"], nee_mse=mse(a_nee, spp),
+                                  fused_s=round(t_fus, 4), fused_s_max=round(t_fus_max, 4), fused_msamples_s=round(W * H * spp / t_fus / 1e6, 1),
+                                  fused_launches=fused.launches, fused_mse=mse(a_fus, spp), fused_bitwise_nee=same, fused_speedup=round(t_nee / t_fus, 3),
+                                  lib_s=round(t_lib, 4),
                                   lib_msamples_s=round(W * H * spp / t_lib / 1e6, 1), lib_rays=st_lib["rays"], lib_mse=mse(a_lib, spp),
-                                  lib_equal_time_spp=spp_eq, lib_equal_time_s=round(t_eq, 4), lib_equal_time_mse=mse(a_eq, spp_eq), ref_spp=ref_spp)), flush=True)
+                                  lib_equal_time_spp=spp_eq, lib_equal_time_s=round(t_eq, 4), lib_equal_time_mse=mse(a_eq, spp_eq),
+                                  lib_equal_fused_time_spp=spp_eq_f, lib_equal_fused_time_s=round(t_eq_f, 4), lib_equal_fused_time_mse=mse(a_eq_f, spp_eq_f),
+                                  ref_spp=ref_spp)), flush=True)
         s.close()
 
 
