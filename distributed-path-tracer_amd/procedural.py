@@ -314,8 +314,55 @@ def cloud_scene(n_models: int = 1, surfaces_per_model: int = 64, tris_per_surfac
                 materials=mats, camera=cam, sun=sun13)
 
 
+def emitter_cloud_scene(sun: bool = True, alpha: bool = True, seed: int = 17):
+    """cloud_scene(3, 21, 16, layout="scattered", tri_size=0.15) with many small emitters, for ptx_render_nee's light list: a list of a
+    few hundred triangles spread over surfaces far from index 0, under three rotated, non-uniformly scaled models.
+      emissive:  surfaces u % 4 == 1, surface 0 and surface 62, factors in [0.05, 0.45]; surface 5 has one non-zero channel only.
+      surface 9: opacity 0.5 when `alpha` (an emitter that must stay off the list: the only pass-through material), opaque otherwise.
+      triangle 5 of surface 1 is collapsed to zero area (its third corner moved onto its second): the list has a gap there.
+      a fourth model of one surface, under a transform of its own: a 6 x 6 receiver quad at world z = -0.6 behind the cloud, facing
+      the camera. 64 surfaces in all, so the queue route still takes the scene.
+      sun:       False removes the directional light.
+    -> dict of arrays as cloud_scene, plus `emissive` (surface ids), `unlisted` (emissive surfaces that must not be listed) and
+    `collapsed` ((surface, triangle))."""
+    d = cloud_scene(3, 21, 16, layout="scattered", tri_size=0.15)
+    rng = np.random.default_rng(seed)
+    mats = d["materials"].copy()
+    n_cloud = len(mats)
+    emissive = sorted({u for u in range(n_cloud) if u % 4 == 1} | {0, n_cloud - 1})
+    mats[emissive, 6:9] = rng.uniform(0.05, 0.45, (len(emissive), 3)).astype(np.float32)
+    mats[5, 6], mats[5, 8] = 0.0, 0.0
+    if alpha:
+        mats[9, 3] = 0.5
+    verts = d["vertices"].copy()
+    v0, _, t0, _ = (int(x) for x in d["surf_range"][1][:4])
+    c = v0 + d["triangles"][t0 + 5].astype(np.int64)
+    verts[c[2], 0:3] = verts[c[1], 0:3]
+    # the receiver: laid out in world space, stored in its model's local space, as cloud_scene does
+    basis = (_rotation(rng) * rng.uniform(0.6, 1.6, 3)[None, :]).astype(np.float32).astype(np.float64)
+    origin = rng.uniform(-0.5, 0.5, 3).astype(np.float32).astype(np.float64)
+    inv = np.linalg.inv(basis)
+    p = np.array([[-3, -3, -0.6], [3, -3, -0.6], [3, 3, -0.6], [-3, 3, -0.6]], np.float64)
+    q = np.zeros((4, 11), np.float64)
+    q[:, 0:3] = (p - origin) @ inv.T
+    q[:, 3:5] = [[0, 0], [1, 0], [1, 1], [0, 1]]
+    nl = np.array([0.0, 0.0, 1.0]) @ basis
+    q[:, 5:8] = nl / np.linalg.norm(nl)
+    tl = np.array([1.0, 0.0, 0.0]) @ inv.T
+    q[:, 8:11] = tl / np.linalg.norm(tl)
+    nv, nt = len(verts), len(d["triangles"])
+    quad_mat = np.array([[0.7, 0.7, 0.65, 1.0, 0.6, 0.0, 0, 0, 0, 1.45, 0]], np.float32)
+    return dict(model_xform=np.concatenate([d["model_xform"], np.concatenate([origin, basis.T.ravel()])[None].astype(np.float32)]),
+                model_surf=np.concatenate([d["model_surf"], np.array([[n_cloud, 1]], np.int32)]),
+                surf_range=np.concatenate([d["surf_range"], np.array([[nv, 4, nt, 2]], np.int32)]),
+                vertices=np.concatenate([verts, q.astype(np.float32)]),
+                triangles=np.concatenate([d["triangles"], np.array([[0, 1, 2], [0, 2, 3]], np.uint32)]),
+                materials=np.concatenate([mats, quad_mat]), camera=d["camera"], sun=d["sun"] if sun else None,
+                emissive=np.array(emissive, np.int32), unlisted=np.array([9] if alpha else [], np.int32), collapsed=(1, 5))
+
+
 # ---------------------------------------------------------------------------- the material chart
-_NEAR1 = float(np.nextafter(np.float32(1), np.float32(0)))
+_NEAR1 =float(np.nextafter(np.float32(1), np.float32(0)))
 _BASE = (0.9, 0.6, 0.3)
 # One patch per regime of the shading vertex: (name, albedo, opacity, roughness, metallic, emissive, ior, shadow catcher, flipped).
 # The three opacities next to 1 all fall on the `is_approx(opacity, 1)` side of renderer.cpp:466 (|opacity - 1| < 0.0001): opaque.

@@ -9,6 +9,7 @@ fixtures themselves are committed so the tests run anywhere.
     python oracle/make_golden.py            # all fixtures (about 2 minutes)
     python oracle/make_golden.py --no-mean  # skip the converged mean images
     python oracle/make_golden.py --only-textures   # the texture fixture scene and tex_vectors.npz (a few seconds)
+    python oracle/make_golden.py --only-lit-textures # tests/golden/textures/lit.gltf: textured emitters and receivers for ptx_render_nee (no reference needed)
     python oracle/make_golden.py --only-tri-scaled # tri_scaled_vectors.npz: triangle::intersect at the scales 2^-66 ... 2^66 (a second)
     python oracle/make_golden.py --only-pbr-edges  # pbr_edges.npz: the BSDF functions at the edges of their domains (a second)
     python oracle/make_golden.py --only-deep-walk  # deep_walk_vectors.npz: renderer::intersect on the corner-cluster meshes (a few seconds)
@@ -339,6 +340,101 @@ def write_texture_scene():
     return [[size[t] for t in _texture_files(m)] for _, m, *_ in TEX_SURFACES]
 
 
+LIT_GLTF = os.path.join(TEX_DIR, "lit.gltf")
+LIT_BLACK = "black_8x8.png"
+# Primitives of the mesh "lit" of lit.gltf, in file order: material, lower-left corner (x, y), edge, depth, uv of the lower-left and
+# upper-right corners. The mesh is instanced twice, the instances face each other (see write_lit_texture_scene): emitters of one light
+# the other. Primitives 0-7 are opaque (LIT_OPAQUE), 8 and 9 can pass a ray through; 1 is the float sRGB emitter.
+LIT_SURFACES = [
+    ("emit_palette_normal", {"normalTexture": "rgb_37x53.png", "pbrMetallicRoughness": {"baseColorFactor": [0.7, 0.7, 0.7, 1.0],
+                             "roughnessFactor": 0.6, "metallicFactor": 0.1}, "emissiveTexture": "p_255x3.png", "emissiveFactor": [0.5, 0.4, 0.3]},
+     (-3.1, 0.1), 1.4, 0.0, (-2.3, -2.3), (3.7, 3.7)),
+    ("emit_hdr_srgb", {"pbrMetallicRoughness": {"baseColorTexture": "rgba_16x16.png", "roughnessFactor": 0.3, "metallicFactor": 0.2},
+                       "emissiveTexture": "emit_6x5.hdr", "emissiveFactor": [0.4, 0.3, 0.2]}, (-1.5, 0.1), 1.4, 0.0, (-2.3, -2.3), (3.7, 3.7)),
+    ("emit_factor", {"pbrMetallicRoughness": {"baseColorFactor": [0.8, 0.6, 0.4, 1.0], "roughnessFactor": 0.7, "metallicFactor": 0.2},
+                     "emissiveFactor": [0.3, 0.25, 0.1]}, (0.1, 0.1), 1.4, 0.0, (0.0, 0.0), (1.0, 1.0)),
+    ("emit_black_region", {"pbrMetallicRoughness": {"baseColorFactor": [0.6, 0.6, 0.7, 1.0], "roughnessFactor": 0.5, "metallicFactor": 0.0},
+                           "emissiveTexture": LIT_BLACK, "emissiveFactor": [0.6, 0.6, 0.6]}, (1.7, 0.1), 1.4, 0.0, (-1.21, -0.7), (2.3, 1.9)),
+    ("recv_base_mr", {"pbrMetallicRoughness": {"baseColorTexture": "rgb_37x53.png", "metallicRoughnessTexture": "la_37x53.png",
+                      "roughnessFactor": 0.9, "metallicFactor": 0.5}}, (-3.1, -1.5), 1.4, 0.0, (-2.21, -2.27), (3.69, 3.66)),
+    ("recv_normal_mr_hdr", {"normalTexture": "la_1x5.png", "pbrMetallicRoughness": {"metallicRoughnessTexture": "mr_13x3.hdr",
+                            "baseColorFactor": [0.5, 0.5, 0.9, 1.0], "roughnessFactor": 0.6, "metallicFactor": 0.9}},
+     (-1.5, -1.5), 1.4, 0.0, (-2.0, -2.2), (3.1, 3.6)),
+    ("recv_plain", {"pbrMetallicRoughness": {"baseColorFactor": [0.8, 0.8, 0.8, 1.0], "roughnessFactor": 0.8, "metallicFactor": 0.0}},
+     (0.1, -1.5), 1.4, 0.0, (0.0, 0.0), (1.0, 1.0)),
+    ("occluder", {"pbrMetallicRoughness": {"baseColorFactor": [0.2, 0.2, 0.2, 1.0], "roughnessFactor": 0.9, "metallicFactor": 0.0}},
+     (0.3, -0.9), 1.6, 0.7, (0.0, 0.0), (1.0, 1.0)),
+    ("blend_emissive_alpha_tex", {"alphaMode": "BLEND", "pbrMetallicRoughness": {"baseColorTexture": "rgba_3x5.png",
+                                  "baseColorFactor": [1.0, 0.9, 0.8, 0.9], "roughnessFactor": 0.5, "metallicFactor": 0.0},
+                                  "emissiveFactor": [0.3, 0.2, 0.1]}, (-3.1, -1.5), 1.4, 0.4, (-2.3, -2.1), (3.5, 3.7)),
+    ("blend_factor", {"alphaMode": "BLEND", "pbrMetallicRoughness": {"baseColorFactor": [0.6, 0.8, 1.0, 0.5], "roughnessFactor": 0.4,
+                      "metallicFactor": 0.0}}, (0.1, -1.5), 1.4, 0.4, (0.0, 0.0), (1.0, 1.0)),
+]
+LIT_OPAQUE = list(range(8))
+
+
+def write_lit_texture_scene():
+    """tests/golden/textures/lit.gltf, lit.bin and black_8x8.png: textured emitters facing textured receivers, for ptx_render_nee. One
+    mesh "lit" of the quads of LIT_SURFACES facing +Z, instanced by two nodes: "lit_a" as it is, "lit_b" turned half round about Y,
+    scaled (1.3, 0.8, 1) and moved to z = 3, so that the two face each other with the camera (at z = 2.2, looking at lit_a) between
+    them. Light 0 is a sun. It reuses the images of write_texture_scene (they must exist) and needs nothing of the reference.
+    black_8x8.png: an RGB emissive image whose columns 0-5 are solid black (a bilinear footprint inside them gives Le = 0 exactly).
+    Deterministic: rewrites identical files."""
+    from PIL import Image
+    black = np.zeros((8, 8, 3), np.uint8)
+    black[:, 6:] = (np.arange(48).reshape(8, 2, 3) * 5 + 16).astype(np.uint8)
+    Image.fromarray(black, "RGB").save(os.path.join(TEX_DIR, LIT_BLACK), optimize=True)
+    names = sorted({t for _, m, *_ in LIT_SURFACES for t in _texture_files(m)})
+    assert all(os.path.exists(os.path.join(TEX_DIR, n)) for n in names), "run --only-textures first"
+    blob = bytearray()
+    views, accessors, prims, mats = [], [], [], []
+
+    def accessor(arr, ctype, kind, **kw):
+        views.append({"buffer": 0, "byteOffset": len(blob), "byteLength": arr.nbytes})
+        blob.extend(np.ascontiguousarray(arr).tobytes())
+        while len(blob) % 4:
+            blob.append(0)
+        accessors.append(dict(bufferView=len(views) - 1, componentType=ctype, count=len(arr), type=kind, **kw))
+        return len(accessors) - 1
+    nrm = accessor(np.tile(np.float32([0, 0, 1]), (4, 1)), 5126, "VEC3")
+    tan = accessor(np.tile(np.float32([1, 0, 0, 1]), (4, 1)), 5126, "VEC4")
+    idx = accessor(np.uint16([0, 1, 2, 0, 2, 3]), 5123, "SCALAR")
+    for k, (mname, m, (x0, y0), edge, z, uv0, uv1) in enumerate(LIT_SURFACES):
+        p = np.float32([[x0, y0, z], [x0 + edge, y0, z], [x0 + edge, y0 + edge, z], [x0, y0 + edge, z]])
+        uv = np.float32([[uv0[0], uv1[1]], [uv1[0], uv1[1]], [uv1[0], uv0[1]], [uv0[0], uv0[1]]])   # glTF v points down the image
+        pa = accessor(p, 5126, "VEC3", min=[float(v) for v in p.min(0)], max=[float(v) for v in p.max(0)])
+        prims.append({"attributes": {"POSITION": pa, "NORMAL": nrm, "TANGENT": tan, "TEXCOORD_0": accessor(uv, 5126, "VEC2")},
+                      "indices": idx, "material": k})
+        mm = json.loads(json.dumps(m))
+        for slot in ("normalTexture", "occlusionTexture", "emissiveTexture"):
+            if slot in mm:
+                mm[slot] = {"index": names.index(mm[slot])}
+        pbr = mm.get("pbrMetallicRoughness", {})
+        for slot in ("baseColorTexture", "metallicRoughnessTexture"):
+            if slot in pbr:
+                pbr[slot] = {"index": names.index(pbr[slot])}
+        mats.append(dict(name=mname, **mm))
+    with open(os.path.join(TEX_DIR, "lit.bin"), "wb") as fh:
+        fh.write(bytes(blob))
+    g = {"asset": {"version": "2.0", "generator": "oracle/make_golden.py --only-lit-textures"},
+         "extensionsUsed": ["KHR_lights_punctual"],
+         "extensions": {"KHR_lights_punctual": {"lights": [{"name": "sun", "type": "directional", "intensity": 2.0, "color": [1.0, 0.95, 0.9]}]}},
+         "scene": 0, "scenes": [{"nodes": [0, 1, 2, 3]}],
+         "cameras": [{"name": "cam", "type": "perspective", "perspective": {"yfov": 0.9, "znear": 0.01, "aspectRatio": 1.5}}],
+         "nodes": [{"name": "cam", "camera": 0, "translation": [0.0, 0.0, 2.2]},
+                   {"name": "sun", "rotation": [-float(np.sin(0.2)), 0.0, 0.0, float(np.cos(0.2))], "extensions": {"KHR_lights_punctual": {"light": 0}}},
+                   {"name": "lit_a", "mesh": 0},
+                   {"name": "lit_b", "mesh": 0, "rotation": [0.0, 1.0, 0.0, 0.0], "translation": [0.3, 0.2, 3.0], "scale": [1.3, 0.8, 1.0]}],
+         "meshes": [{"name": "lit", "primitives": prims}], "materials": mats,
+         "images": [{"uri": n} for n in names], "textures": [{"source": i} for i in range(len(names))],
+         "buffers": [{"uri": "lit.bin", "byteLength": len(blob)}], "bufferViews": views, "accessors": accessors}
+    with open(LIT_GLTF, "w") as fh:
+        json.dump(g, fh, indent=1)
+        fh.write("\n")
+    print(f"{LIT_GLTF}: {len(prims)} primitives x 2 nodes, {len(names)} images, lit.bin {len(blob)} bytes, "
+          f"{LIT_BLACK} {os.path.getsize(os.path.join(TEX_DIR, LIT_BLACK))} bytes")
+
+
 def _texture_files(m):
     pbr = m.get("pbrMetallicRoughness", {})
     return [x for x in (m.get("normalTexture"), pbr.get("baseColorTexture"), m.get("occlusionTexture"), pbr.get("metallicRoughnessTexture"),
@@ -583,12 +679,17 @@ def main():
     ap.add_argument("--only-jpeg", action="store_true", help="regenerate tests/golden/jpeg/* and jpeg_vectors.npz only")
     ap.add_argument("--only-hdr", action="store_true", help="regenerate tests/golden/hdr/* and hdr_vectors.npz only")
     ap.add_argument("--only-textures", action="store_true", help="regenerate tests/golden/textures/* and tex_vectors.npz only")
+    ap.add_argument("--only-lit-textures", action="store_true",
+                    help="rewrite tests/golden/textures/lit.gltf, lit.bin and black_8x8.png only (no reference needed)")
     ap.add_argument("--only-tri-scaled", action="store_true", help="regenerate tri_scaled_vectors.npz only")
     ap.add_argument("--only-pbr-edges", action="store_true", help="regenerate pbr_edges.npz only")
     ap.add_argument("--only-chart", action="store_true", help="regenerate tests/golden/chart/* and chart_trace.npz only")
     ap.add_argument("--only-deep-walk", action="store_true", help="regenerate deep_walk_vectors.npz only")
     ap.add_argument("--n", type=int, default=1024)
     args = ap.parse_args()
+    if args.only_lit_textures:
+        write_lit_texture_scene()
+        return
     subprocess.check_call(["make", "-s", "-j8", "-C", HERE, "ref"])
     os.makedirs(GOLD, exist_ok=True)
     env = dict(os.environ, ORACLE_SEED="20261004")
@@ -675,6 +776,7 @@ def main():
         make_jpeg_fixtures(env)
         make_hdr_fixtures(env)
         make_texture_fixtures(env)
+        write_lit_texture_scene()
         make_tri_scaled_fixture(env)
         make_chart_fixture(env)
         make_pbr_edges_fixture(env)

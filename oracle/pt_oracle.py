@@ -403,6 +403,7 @@ class OracleScene:
     def set_environment(self, png_path, srgb=True):
         """renderer::environment = image_texture::load(path, srgb) (renderer.hpp:28); None removes it."""
         if png_path is None:
+            self._env = None
             lib().ora_scene_set_environment(self.h, 0, 0, 0, 0, None)
             return
         if _is_hdr(png_path):                                 # image::hdr: float texels

@@ -10,6 +10,9 @@ Switches: lights=False runs with an empty list (LIB itself), mis=False sets ever
 drops the light term but keeps the weights (energy lost). fold="recursive" (lights=False only) adds a path's vertices back to front
 as renderer::trace returns them, which is what OracleScene.render_samples computes bit for bit; fold="throughput" is the product's
 order: vertex k's emission, its sun term, its light term, then vertex k + 1.
+
+A miss adds T * env; when the oracle scene has an environment map (OracleScene.set_environment), env is OracleScene.env_lookup of the
+ray's direction times the factor, per ray (renderer.cpp:443-449).
 """
 import numpy as np
 
@@ -208,13 +211,15 @@ def _eval_brdf(ora, n, outc, inc, albedo, rough, metallic, spec_prob, ior):
 
 # ---------------------------------------------------------------------------- the estimator
 def render_samples(ora, o, a, W, H, spp, bounces, seed=0x5EED, env=(1.0, 1.0, 1.0), tile=None, sample0=0, lights=True, mis=True,
-                   light_term=True, fold="throughput"):
+                   light_term=True, fold="throughput", light_draws=None):
     """-> dict(rad [h, w, spp, 3] float32 per-sample radiance, v1_listed [h, w, spp] bool: the sample's vertex at depth 1 lies on a listed
-    triangle, light_samples, light_visible, rays)."""
+    triangle, light_samples, light_visible, rays). light_draws: None, or a list that receives, per round, the Philox keys (pixel, sample,
+    depth, pass: uint32 [n, 4]) of the vertices that drew a light sample, accepted or not."""
     assert fold in ("throughput", "recursive") and (fold == "throughput" or not lights)
     x0, y0, w, h = tile if tile else (0, 0, W, H)
     npix, N = w * h, w * h * spp
     env = np.asarray(env, f32)
+    env_map = getattr(o, "_env", None) is not None
     attr = _Attr(a)
     model_of = attr.model_of
     mats = np.asarray(a.materials, f32)
@@ -250,11 +255,16 @@ def render_samples(ora, o, a, W, H, spp, bounces, seed=0x5EED, env=(1.0, 1.0, 1.
         out, surf, tri, dist = _closest(o, model_of, np.concatenate([O[live], D[live]], 1))
         stats["rays"] += len(live)
         nxt = np.zeros(len(live), bool)
-        R = dict(ids=live, kind=np.zeros(len(live), np.int8), e=np.zeros((len(live), 3), f32), dsun=np.zeros((len(live), 3), f32),
+        R = dict(ids=live, kind=np.zeros(len(live), np.int8), e=np.zeros((len(live), 3), f32), dsun=np.zeros((len(live), 3), f32), env=env,
                  brdf=np.zeros((len(live), 3), f32), pe=np.ones(len(live), f32), cont=np.zeros(len(live), bool))   # kind 0 zero, 1 miss, 2 pass, 3 vertex
         rec.append(R)
         miss = surf < 0
-        L[live[miss]] = L[live[miss]] + T[live[miss]] * env
+        if env_map and miss.any():
+            R["env"] = np.zeros((len(live), 3), f32)
+            R["env"][miss] = o.env_lookup(D[live[miss]], env)[2]
+            L[live[miss]] = L[live[miss]] + T[live[miss]] * R["env"][miss]
+        else:
+            L[live[miss]] = L[live[miss]] + T[live[miss]] * env
         R["kind"][miss] = 1
         hi = np.flatnonzero(~miss)          # positions within `live`
         if len(hi):
@@ -338,6 +348,8 @@ def render_samples(ora, o, a, W, H, spp, bounces, seed=0x5EED, env=(1.0, 1.0, 1.
             gc = g[ci]
             if n_l and len(ci):
                 r = draws(ora, pixel[gc], sample[gc], dep[ci], pa[ci], BLOCK_LIGHT, seed)
+                if light_draws is not None:
+                    light_draws.append(np.stack([pixel[gc], sample[gc], dep[ci], pa[ci]], -1).astype(np.uint32))
                 k = np.minimum(np.searchsorted(ll["cdf"], r[:, 0], side="right"), n_l - 1)
                 su = np.sqrt(r[:, 1])
                 beta, gamma = su * (f32(1) - r[:, 2]), su * r[:, 2]
@@ -394,7 +406,7 @@ def render_samples(ora, o, a, W, H, spp, bounces, seed=0x5EED, env=(1.0, 1.0, 1.
         for R in reversed(rec):
             ids, kind = R["ids"], R["kind"]
             val[ids[kind == 0]] = 0
-            val[ids[kind == 1]] = env
+            val[ids[kind == 1]] = R["env"] if R["env"].ndim == 1 else R["env"][kind == 1]
             v = kind == 3
             iv = ids[v]
             inn = val[iv]

@@ -84,7 +84,8 @@ def _pair(ptx, ctx, s, W, H, spp, bounces, fused=True, flags=0, **kw):
 @pytest.mark.parametrize("route", ["lds fused", "global fused"])
 @pytest.mark.parametrize("name,W,H,bounces", [("cornell", 32, 32, (1, 2, 3, 5)), ("chart", 48, 40, (4,)), ("chart_alpha_sun", 48, 40, (4,))])
 def test_flagged_frame_is_the_unflagged_frame_bitwise(ptx, ctx, clean_env, route, name, W, H, bounces):
-    """chart: textures; chart_alpha_sun: pass-through, shadow catcher, sun and light in one path"""
+    """chart: 12 listed triangles facing every material regime, no textures (the TEX = false kernels; tests/test_nee_lights.py runs the
+    TEX = true ones); chart_alpha_sun: pass-through, shadow catcher, sun and light in one path"""
     s, _ = _route(ptx, ctx, clean_env, name, route)
     for b in bounces:
         _, st = _pair(ptx, ctx, s, W, H, 4, b)
