@@ -29,7 +29,7 @@ NO_SUN_LIGHT = 0xFFFFFFFF  # core::renderer::no_sun_light, renderer.hpp:19
 (ARR_MODEL_XFORM, ARR_MODEL_AABB, ARR_MODEL_SURF, ARR_SURF_RANGE, ARR_MESH_AABB, ARR_VERTICES, ARR_TRIANGLES,
  ARR_MATERIALS, ARR_KD_NODES, ARR_KD_REFS, ARR_CAMERA, ARR_SUN, ARR_MODEL_NAMES, ARR_TEXTURES, ARR_TEXELS, ARR_SURF_TEX, ARR_TEXELS_F32,
  ARR_LIGHT_TRIS, ARR_LIGHT_CDF, ARR_LIGHT_GEOM, ARR_TRI_ISECT, ARR_RES_NODES, ARR_RES_REFS, ARR_RES_TRIS, ARR_LDS_ROOT,
- ARR_RES_PLAN) = range(26)
+ ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF) = range(28)
 LDS_LEAF_ORDER_BIT = 0x80000000  # ARR_LDS_ROOT: the surface's resident records are leaf-ordered (flat_scene.hpp)
 
 
@@ -111,6 +111,7 @@ class NeeStats(C.Structure):
 
 NEE_NO_LIGHT_SAMPLES = 1   # ptx_nee_cfg.flags
 NEE_FUSED = 4              # one kernel launch per pass where render() runs the fused kernel; ignored on the queue route
+NEE_ENV_SAMPLES = 16       # the light sample may go towards the environment map; ignored without a map or with a black one
 
 
 class KernelTiming(C.Structure):
@@ -372,7 +373,7 @@ _ARR_DTYPE = {ARR_MODEL_XFORM: (np.float32, 12), ARR_MODEL_AABB: (np.float32, 6)
               ARR_TEXTURES: (np.uint32, 4), ARR_TEXELS: (np.uint8, 1), ARR_SURF_TEX: (np.int32, 7), ARR_TEXELS_F32: (np.float32, 1),
               ARR_LIGHT_TRIS: (np.uint32, 2), ARR_LIGHT_CDF: (np.float32, 1), ARR_LIGHT_GEOM: (np.float32, 4),
               ARR_TRI_ISECT: (np.uint32, 12), ARR_RES_NODES: (np.uint32, 2), ARR_RES_REFS: (np.uint32, 1), ARR_RES_TRIS: (np.uint32, 12),
-              ARR_LDS_ROOT: (np.uint32, 1), ARR_RES_PLAN: (np.uint32, 1)}
+              ARR_LDS_ROOT: (np.uint32, 1), ARR_RES_PLAN: (np.uint32, 1), ARR_ENV_ROW_CDF: (np.float32, 1), ARR_ENV_CELL_CDF: (np.float32, 1)}
 
 
 class Scene:
@@ -533,7 +534,8 @@ class Scene:
         continuing vertex, MIS-weighted (include/ptx.h has the estimator). ADDS radiance SUMS into accum as render() does; tiles, sample
         ranges and shards compose the same way. flags: NEE_NO_LIGHT_SAMPLES runs with an empty list (bitwise render()'s frame);
         NEE_FUSED renders each pass with one kernel launch where render() runs its fused kernel (bitwise the unflagged frame; ignored on
-        scenes of the queue route).
+        scenes of the queue route); NEE_ENV_SAMPLES lets the light sample go towards the environment map (set_environment), importance-
+        sampled by luminance and MIS-weighted against the map's radiance on a miss (ignored without a map or with a black one).
         Returns (accum, stats dict or None)."""
         x0, y0, w, h = tile if tile else (0, 0, W, H)
         if accum is None:
@@ -707,7 +709,7 @@ class Renderer:
     def render_nee(self, flags=0):
         """Radiance SUMS [H,W,4] of the frame with next-event estimation towards the scene's emissive triangles (Scene.render_nee):
         render_accum()'s samples plus one MIS-weighted light sample per continuing vertex. flags: ptx_nee_cfg.flags (NEE_FUSED: the same
-        frame from one kernel launch per pass). `last_nee_stats` holds the stats."""
+        frame from one kernel launch per pass; NEE_ENV_SAMPLES: light samples towards `environment` too). `last_nee_stats` holds the stats."""
         if self._scene is None:
             raise PtxError(ERR_INVALID, "render_nee() before load_gltf()")
         if self.transparent_background:

@@ -104,9 +104,18 @@ struct ptx_scene {
 	} lights;
 	std::mutex lights_mu;   // host-only scenes have no context whose mutex could guard the build
 	DevBuf d_light_tris, d_light_cdf, d_light_geom, d_light_first;
+	// The sampling table of the environment map (build_env_table, PTX_NEE_ENV_SAMPLES): built at the first request under lights_mu, dropped
+	// by ptx_scene_set_environment. Empty vectors: no map, or a black one. The device copies are made by the first flagged ptx_render_nee.
+	struct EnvTable {
+		bool built = false, on_device = false;
+		uint32_t w = 0, h = 0;
+		std::vector<float> row_cdf, cell_cdf;   // [h], [h][w]
+	} env_table;
+	DevBuf d_env_row, d_env_cell;
 };
 
 const ptx_scene::LightList* build_lights(ptx_scene* sc);   // ptx_api.cpp
+const ptx_scene::EnvTable* build_env_table(ptx_scene* sc);   // ptx_api.cpp
 void srgb_thresholds(float thr[256]);                      // ptx_api.cpp
 // api_batch.cpp: one decision on device buffers (adaptive.hip), its count read back: the stream is synchronised. The caller holds the
 // context's mutex. select_ms: nullptr, or where the HIP-event time of the decision kernels is added.

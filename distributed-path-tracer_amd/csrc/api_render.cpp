@@ -655,8 +655,8 @@ namespace {
 
 // ptx_render_nee with PTX_NEE_FUSED on a scene of the fused route: one launch of k_nee_fused per pass, then the resolve. No round trips to the
 // host and no streams: the workspace is ptx_render's radiance records, overflow stacks and counters. The caller holds the context's mutex, has
-// set the device, planned the passes and uploaded the light list.
-int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeLights& Lt, float* accum, ptx_nee_stats* stats) {
+// set the device, planned the passes and uploaded the light list and, for PTX_NEE_ENV_SAMPLES, the environment table.
+int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeLights& Lt, const NeeEnv& Ev, float* accum, ptx_nee_stats* stats) {
 	const int grid = c->n_cu;
 	HIP_TRY(c->sample_rad.ensure((size_t)f.pass_spp * f.n_pixels * sizeof(float4)));
 	HIP_TRY(c->counters.ensure(1024));   // [0] chunk counter, [16] rays, [24] light samples, [32] visible light samples
@@ -673,7 +673,7 @@ int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeLigh
 		P.integrator = PTX_INTEGRATOR_LIB;
 		HIP_TRY(hipMemsetAsync(B.chunk_counter, 0, 8, c->stream));
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
-		HIP_TRY(launch_nee_fused(sc->dev, P, Lt, B, sc->mode, sc->lds_bytes, grid, c->stream));
+		HIP_TRY(launch_nee_fused(sc->dev, P, Lt, Ev, B, sc->mode, sc->lds_bytes, grid, c->stream));
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
 		HIP_TRY(launch_resolve(B.sample_rad, s_accum.as<float4>(), f.d_pixels, P.n_pixels, P.pass_spp, c->stream));
 	}
@@ -698,7 +698,7 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 	// every refusal below is decided before any device work
 	if (!sc || !cfg || !accum) return set_err(PTX_ERR_INVALID, "ptx_render_nee: NULL argument");
 	const uint32_t flags = ncfg ? ncfg->flags : 0u;
-	if (flags & ~(uint32_t)(PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED)) return set_err(PTX_ERR_INVALID, "ptx_render_nee: unknown flag");
+	if (flags & ~(uint32_t)(PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED | PTX_NEE_ENV_SAMPLES)) return set_err(PTX_ERR_INVALID, "ptx_render_nee: unknown flag");
 	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
 		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_nee: PTX_INTEGRATOR_WORKER has no light sampling here (the estimator is defined on PTX_INTEGRATOR_LIB's vertex)");
 	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_nee: scene was created without a GPU context (no CPU path exists)");
@@ -737,7 +737,24 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 		Lt.surf_first = (const int32_t*)sc->d_light_first.p; Lt.n = n_lights; Lt.area = ll.area;
 	}
 
-	if (fused) return nee_fused_frame(c, sc, f, Lt, accum, stats);
+	// PTX_NEE_ENV_SAMPLES: the ENV variants wherever the map has a table; no map or a black one: the call runs exactly as without the flag
+	NeeEnv Ev{};
+	if (flags & PTX_NEE_ENV_SAMPLES) {
+		const ptx_scene::EnvTable& et = *build_env_table(sc);
+		if (!et.row_cdf.empty() && sc->dev.env_tex >= 0) {
+			if (!sc->env_table.on_device) {
+				HIP_TRY(sc->d_env_row.ensure(et.row_cdf.size() * 4));
+				HIP_TRY(sc->d_env_cell.ensure(et.cell_cdf.size() * 4));
+				HIP_TRY(hipMemcpyAsync(sc->d_env_row.p, et.row_cdf.data(), et.row_cdf.size() * 4, hipMemcpyHostToDevice, c->stream));
+				HIP_TRY(hipMemcpyAsync(sc->d_env_cell.p, et.cell_cdf.data(), et.cell_cdf.size() * 4, hipMemcpyHostToDevice, c->stream));
+				HIP_TRY(hipStreamSynchronize(c->stream));
+				sc->env_table.on_device = true;
+			}
+			Ev.row_cdf = (const float*)sc->d_env_row.p; Ev.cell_cdf = (const float*)sc->d_env_cell.p; Ev.w = et.w; Ev.h = et.h;
+		}
+	}
+
+	if (fused) return nee_fused_frame(c, sc, f, Lt, Ev, accum, stats);
 
 	// workspace of one pass of `cap` samples: [256 B: counters][radiance records][stream 0][stream 1][hits][shadow rays][shadow hits][shadow records]
 	const size_t cap = ((size_t)f.pass_spp * f.n_pixels + 3) & ~(size_t)3;   // array stride: keeps every array 16-byte aligned
@@ -794,7 +811,7 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 			rays += live;
 			const NeeHits H{A.distance, A.surface, A.triangle, A.b1, A.b2};
 			HIP_TRY(hipMemsetAsync(cnt, 0, 8, c->stream));
-			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, in, H, live, out, W, cnt, Lrec, c->stream));
+			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, Ev, in, H, live, out, W, cnt, Lrec, c->stream));
 			uint32_t got[2] = {0, 0};   // continuations, shadow rays
 			HIP_TRY(hipMemcpyAsync(got, cnt, 8, hipMemcpyDeviceToHost, c->stream));
 			HIP_TRY(hipStreamSynchronize(c->stream));

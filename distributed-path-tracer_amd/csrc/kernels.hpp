@@ -231,9 +231,16 @@ struct NeeLights {   // the scene's light list (ptx_api.cpp: build_lights); n ==
 	uint32_t n;
 	float area;                  // A_total
 };
+// The environment map's sampling table (ptx_api.cpp: build_env_table), PTX_NEE_ENV_SAMPLES. row_cdf == nullptr: no table, the unflagged estimator
+struct NeeEnv {
+	const float* row_cdf;    // [h] cumulative share of the rows' mass, top row first, the last entry 1
+	const float* cell_cdf;   // [h][w] cumulative share of the boxes within their row, the last entry 1 (a row of zero mass: all 0)
+	uint32_t w, h;           // the map's size in texels
+};
+constexpr uint32_t kNeeEnvRay = 0xFFFFFFFFu;   // exp_surf of an environment sample's shadow ray: the sample is visible iff the ray hits nothing
 // cnt (device, 8 words): [0] entries appended to `out`, [1] shadow rays of the round, [2..3] light samples (64-bit), [4..5] visible ones
 hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, hipStream_t stream);
-hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeStream& in, const NeeHits& H, uint32_t n, const NeeStream& out,
+hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeStream& in, const NeeHits& H, uint32_t n, const NeeStream& out,
                             const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
 hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, hipStream_t stream);
 
@@ -245,7 +252,7 @@ struct NeeFusedBuffers {
 	unsigned long long* chunk_counter;   // paths handed out so far; zeroed before each pass
 	unsigned long long* counters;        // [3] accumulate: rays (closest + both shadow kinds), light samples, visible light samples
 };
-hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream);
+hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream);
 
 // Variance-guided a-trous filter (denoise.hip, ptx_denoise). All buffers [n_pixels] float4 on the device.
 // prepare: the two radiance sums and the guide sums -> col_var (demodulated colour, v0), guide (mean normal, mean depth), remod (albedo, alpha)

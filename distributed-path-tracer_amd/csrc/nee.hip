@@ -7,7 +7,7 @@
 //                    sample. Shadow rays (sun or shadow catcher, and light) are appended densely to the round's shadow stream, the
 //                    continuation to the next round's path stream (wave ballot + lane prefix count, one atomic per wave and stream)
 //   k_nee_settle     one lane per path of the round: adds the sun term if unoccluded, then the light term if the shadow ray's closest hit
-//                    is the sampled triangle; appends the pass-through ray of a lit shadow catcher
+//                    is the sampled triangle (an environment sample's: if it hit nothing); appends the pass-through ray of a lit shadow catcher
 // A sample's radiance lives in a record by sample id: vertex k's emission is added by round k's shade kernel, its sun and light terms by
 // round k's settle kernel, vertex k + 1's by the next round — a fixed order without float atomics. The pass ends with k_resolve.
 // Numerics as in kernels.hip: IEEE binary32 in the written order, no contraction.
@@ -47,10 +47,12 @@ DEV void nee_append2(bool first, bool second, uint32_t* counter, uint32_t& pos_f
 }
 
 // One vertex of every live path: loads the hit and the path state of entry i, runs nee_vertex (nee_core.hpp) and stores what it returns.
-// TEX / ALPHA / SUN compile the texture lookups / the pass-through and catcher code / the sun request in, as the render variants do.
-template <bool TEX, bool ALPHA, bool SUN>
+// TEX / ALPHA / SUN compile the texture lookups / the pass-through and catcher code / the sun request in, as the render variants do;
+// ENV the environment sample and the miss weight (PTX_NEE_ENV_SAMPLES; TEX only: a map implies the TEX variants). Ev, the last argument, is
+// read by the ENV variants alone.
+template <bool TEX, bool ALPHA, bool SUN, bool ENV>
 __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParams P, NeeLights Lt, NeeStream in, NeeHits H, uint32_t n, NeeStream out, NeeShadow W,
-                                                         uint32_t* __restrict__ cnt, float4* __restrict__ Lrec) {
+                                                         uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeeEnv Ev) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
 	NeeVertex v;
 	V3 o = {0, 0, 0}, d = {0, 0, 1}, T = {1, 1, 1};
@@ -68,7 +70,7 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 		const uint32_t pixel = py * P.W + px;
 		const float4 l4 = Lrec[id];
 		V3 L = mk(l4.x, l4.y, l4.z);
-		if (nee_vertex<TEX, ALPHA, SUN>(S, P, Lt, pixel, sample, H.surface[i], (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v))
+		if (nee_vertex<TEX, ALPHA, SUN, ENV>(S, P, Lt, Ev, pixel, sample, H.surface[i], (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v))
 			Lrec[id] = make_float4(L.x, L.y, L.z, l4.w);
 	}
 	// shadow rays of the round: at most two per path, so every position is below twice the round's paths
@@ -118,7 +120,8 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_settle(NeeStream in, uint32_t
 				else if (!occluded) { v.x += W.sx[i]; v.y += W.sy[i]; v.z += W.sz[i]; store = true; }
 			}
 			if (lp != kNeeNone) {
-				visible = SH.surface[lp] == (int32_t)W.exp_surf[i] && SH.triangle[lp] == (int32_t)W.exp_tri[i];
+				const uint32_t es = W.exp_surf[i];
+				visible = es == kNeeEnvRay ? SH.surface[lp] < 0 : (SH.surface[lp] == (int32_t)es && SH.triangle[lp] == (int32_t)W.exp_tri[i]);
 				if (visible) { v.x += W.lx[i]; v.y += W.ly[i]; v.z += W.lz[i]; store = true; }
 			}
 			if (store) Lrec[id] = v;
@@ -144,23 +147,27 @@ hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const N
 	return hipGetLastError();
 }
 
-template <bool TEX, bool ALPHA>
-static void nee_shade_sun(bool sun, dim3 grid, hipStream_t stream, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeStream& in, const NeeHits& H, uint32_t n,
-                          const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L) {
-	if (sun) hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, true>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L);
-	else hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, false>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L);
+template <bool TEX, bool ALPHA, bool ENV>
+static void nee_shade_sun(bool sun, dim3 grid, hipStream_t stream, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeStream& in, const NeeHits& H,
+                          uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L) {
+	if (sun) hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, true, ENV>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev);
+	else hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, false, ENV>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev);
 }
 
-hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeStream& in, const NeeHits& H, uint32_t n, const NeeStream& out,
+hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeStream& in, const NeeHits& H, uint32_t n, const NeeStream& out,
                             const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
 	const dim3 grid((n + kNeeBlock - 1) / kNeeBlock);
 	const bool sun = S.sun.present != 0;
-	if (S.any_texture) {
-		if (S.any_alpha) nee_shade_sun<true, true>(sun, grid, stream, S, P, Lt, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<true, false>(sun, grid, stream, S, P, Lt, in, H, n, out, W, cnt, L);
+	if (Ev.row_cdf) {   // a table means a map, and a map means the TEX variants
+		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
+		if (S.any_alpha) nee_shade_sun<true, true, true>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
+		else nee_shade_sun<true, false, true>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
+	} else if (S.any_texture) {
+		if (S.any_alpha) nee_shade_sun<true, true, false>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
+		else nee_shade_sun<true, false, false>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
 	} else {
-		if (S.any_alpha) nee_shade_sun<false, true>(sun, grid, stream, S, P, Lt, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<false, false>(sun, grid, stream, S, P, Lt, in, H, n, out, W, cnt, L);
+		if (S.any_alpha) nee_shade_sun<false, true, false>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
+		else nee_shade_sun<false, false, false>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
 	}
 	return hipGetLastError();
 }

@@ -6,7 +6,7 @@
 
 namespace ptx {
 
-enum { BLOCK_LIGHT = 3 };   // Philox block of the light sample's draws (BLOCK_SURFACE / BLOCK_SUN / BLOCK_JITTER: device_core.hpp)
+enum { BLOCK_LIGHT = 3, BLOCK_ENV = 4 };   // Philox blocks of the light sample's and the environment sample's draws (BLOCK_SURFACE / BLOCK_SUN / BLOCK_JITTER: device_core.hpp)
 
 // sample id within the pass (sample-major, pixel-minor) -> image pixel and global sample index, as k_render_pass enumerates them
 DEV void nee_sample_of(const RenderParams& P, uint32_t id, uint32_t& px, uint32_t& py, uint32_t& sample) {
@@ -32,12 +32,47 @@ DEV int nee_find_light(const NeeLights& Lt, uint32_t surface, uint32_t tri) {
 	return (e.x == surface && e.y == tri) ? (int)lo : -1;
 }
 
+// ---- the environment map as a light (PTX_NEE_ENV_SAMPLES; include/ptx.h has the table and the pdf)
+// (u, v) of the miss lookup for direction d, and the table's box (i, j) they fall into
+DEV void env_box(const NeeEnv& E, V3 d, float& u, float& v, uint32_t& i, uint32_t& j) {
+	u = atan2f(d.z, d.x) * 0.1591F + 0.5F;
+	v = asinf(d.y) * 0.3183F + 0.5F;
+	const uint32_t bi = (uint32_t)(u * (float)E.w), bj = (uint32_t)((1 - v) * (float)E.h);
+	i = bi < E.w - 1 ? bi : E.w - 1;
+	j = bj < E.h - 1 ? bj : E.h - 1;
+}
+// solid-angle density with which the environment sample produces a direction d of box (i, j): the box's probability as the STORED
+// float32 tables give it (what the sampler realises), over the box's solid angle
+DEV float env_pdf_box(const NeeEnv& E, V3 d, uint32_t i, uint32_t j) {
+	const float c = sqrt_exact(pmax(0.0f, 1 - d.y * d.y));
+	if (!(c > 0)) return 0.0f;
+	const float* row = E.cell_cdf + (size_t)j * E.w;
+	const float pr = E.row_cdf[j] - (j ? E.row_cdf[j - 1] : 0.0f), pc = row[i] - (i ? row[i - 1] : 0.0f);
+	const float Pb = pr * pc;
+	return ((Pb * (float)(E.w * E.h)) * (0.1591F * 0.3183F)) / c;
+}
+DEV float env_pdf(const NeeEnv& E, V3 d) {
+	float u, v;
+	uint32_t i, j;
+	env_box(E, d, u, v, i, j);
+	return env_pdf_box(E, d, i, j);
+}
+// first entry of cdf[0 .. n) with x < cdf[entry], clamped to n - 1
+DEV uint32_t env_pick(const float* __restrict__ cdf, uint32_t n, float x) {
+	uint32_t a = 0, b = n;
+	while (a < b) {
+		const uint32_t mid = a + (b - a) / 2;
+		if (x < cdf[mid]) b = mid; else a = mid + 1;
+	}
+	return a < n - 1 ? a : n - 1;
+}
+
 // What a vertex leaves besides the path state: whether the path goes on, and its up-to-two shadow requests
 struct NeeVertex {
 	bool alive = false;         // the path continues with (o, d, T, p_prev, depth, pass) as the vertex left them
 	bool want_sun = false;      // sun ray (sun_o, sun_d): unoccluded adds sun_x = T * direct_out ...
 	bool catcher_req = false;   // ... or, a shadow catcher's: unoccluded lets the path through from sun_x, occluded ends it
-	bool want_light = false;    // light ray (lo, ld): lx is added iff its closest hit is triangle exp_tri of surface exp_surf
+	bool want_light = false;    // light ray (lo, ld): lx is added iff its closest hit is triangle exp_tri of surface exp_surf (kNeeEnvRay: iff it hits nothing)
 	V3 sun_o = {0, 0, 0}, sun_d = {0, 0, 1}, sun_x = {0, 0, 0}, lo = {0, 0, 0}, ld = {0, 0, 1}, lx = {0, 0, 0};
 	uint32_t exp_surf = 0, exp_tri = 0;
 };
@@ -46,8 +81,10 @@ struct NeeVertex {
 // scene's intersect route reports them. TEX / ALPHA / SUN compile the texture lookups / the pass-through and catcher code / the sun request
 // in, as the render variants do. The statements are shade_vertex<SUN, ALPHA, TEX, false>'s, in its order, with the emission weighted and the
 // light sample taken before the BSDF sample. Returns whether L received a term (the record-based form stores its record then).
-template <bool TEX, bool ALPHA, bool SUN>
-DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& Lt, uint32_t pixel, uint32_t sample, int32_t surf, uint32_t tri, float b1, float b2,
+// ENV (PTX_NEE_ENV_SAMPLES with a table, Ev): the light sample may go towards the environment map, and the map's radiance on a miss is weighted
+// against that sample. Without ENV, Ev is not read and the statements are the unflagged estimator's.
+template <bool TEX, bool ALPHA, bool SUN, bool ENV = false>
+DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t pixel, uint32_t sample, int32_t surf, uint32_t tri, float b1, float b2,
                     float hit_dist, V3& o, V3& d, V3& T, V3& L, float& p_prev, uint32_t& depth, uint32_t& pass, NeeVertex& out) {
 	bool& alive = out.alive;
 	bool& want_sun = out.want_sun;
@@ -56,6 +93,7 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 	V3 &sun_o = out.sun_o, &sun_d = out.sun_d, &sun_x = out.sun_x, &lo = out.lo, &ld = out.ld, &lx = out.lx;
 	uint32_t &exp_surf = out.exp_surf, &exp_tri = out.exp_tri;
 	bool store = false;
+	const float c_env = (ENV && Lt.n != 0) ? 0.5F : 1.0F;   // share of the vertices whose light sample goes to the map (ENV only)
 	do {
 		if (surf < 0) {   // miss: environment
 			V3 env = mk(P.env[0], P.env[1], P.env[2]);
@@ -65,7 +103,11 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 					env = mk(e.x, e.y, e.z) * env;
 				}
 			}
-			L = L + T * env;
+			V3 add = T * env;
+			if constexpr (ENV) {   // a BSDF-sampled direction that the environment sample of the previous vertex could have produced
+				if (depth != 0 && pass == 0) add = add * (p_prev / (p_prev + c_env * env_pdf(Ev, d)));
+			}
+			L = L + add;
 			store = true;
 			break;
 		}
@@ -133,7 +175,8 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 				const float4 g = Lt.geom[k];
 				const float cg = fabsf(dot(mk(g.x, g.y, g.z), d));
 				const float dist = hit_dist;
-				const float p_l = (dist * dist) / (cg * Lt.area);
+				float p_l = (dist * dist) / (cg * Lt.area);
+				if constexpr (ENV) p_l = (1 - c_env) * p_l;
 				em = em * (p_prev / (p_prev + p_l));
 			}
 		}
@@ -141,7 +184,41 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 		store = true;
 		if (last) break;
 		// ---- light sample
-		if (Lt.n != 0) {
+		bool to_env = false;
+		if constexpr (ENV) {
+			to_env = Lt.n == 0 || draws(P, pixel, sample, depth, pass, BLOCK_LIGHT).w < 0.5F;
+			if (to_env) {
+				const float4 q = draws(P, pixel, sample, depth, pass, BLOCK_ENV);
+				const uint32_t j = env_pick(Ev.row_cdf, Ev.h, q.x);
+				const uint32_t i = env_pick(Ev.cell_cdf + (size_t)j * Ev.w, Ev.w, q.y);
+				const float u = ((float)i + q.z) / (float)Ev.w, v = 1 - ((float)j + q.w) / (float)Ev.h;
+				const float phi = (u - 0.5F) / 0.1591F, lat = (v - 0.5F) / 0.3183F;
+				const float cl = cosf(lat);
+				const V3 w = mk(cl * cosf(phi), sinf(lat), cl * sinf(phi));
+				float fu, fv;
+				uint32_t fi, fj;
+				env_box(Ev, w, fu, fv, fi, fj);   // the lookup's own (u, v): a sample it maps to another box is dropped, so the pdf stays a function of direction
+				if (fi == i && fj == j && dot(normal, w) > 0) {
+					const float p = env_pdf_box(Ev, w, fi, fj);
+					const float4 e = tex_sample(S, S.env_tex, fu, fv);
+					const V3 Le = mk(e.x, e.y, e.z) * mk(P.env[0], P.env[1], P.env[2]);
+					if (p > 0 && pmax(Le.x, pmax(Le.y, Le.z)) > 0) {
+						float pdf;
+						const V3 brdf = eval_brdf(normal, outcoming, w, me.albedo, roughness, me.metallic, spec_prob, pdf);
+						const float pe = pmax(pdf, kEps);
+						const V3 qv = brdf / pe;
+						const V3 qc = mk(clampf(qv.x, 0, 1), clampf(qv.y, 0, 1), clampf(qv.z, 0, 1));
+						const float wl = pe / (pe + c_env * p);
+						lx = ((T * qc) * wl) * Le;
+						lo = sf.pos + w * kEps;
+						ld = w;
+						exp_surf = kNeeEnvRay; exp_tri = 0;
+						want_light = true;
+					}
+				}
+			}
+		}
+		if (Lt.n != 0 && !to_env) {
 			const float4 r = draws(P, pixel, sample, depth, pass, BLOCK_LIGHT);
 			uint32_t a = 0, b = Lt.n;   // first entry with r.x < cdf
 			while (a < b) {
@@ -168,7 +245,8 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 					const float pe = pmax(pdf, kEps);
 					const V3 q = brdf / pe;
 					const V3 qc = mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));
-					const float p_l = dist2 / (cg * Lt.area);
+					float p_l = dist2 / (cg * Lt.area);
+					if constexpr (ENV) p_l = (1 - c_env) * p_l;
 					const float wl = pe / (pe + p_l);
 					lx = ((T * qc) * wl) * Le;
 					lo = sf.pos + w * kEps;

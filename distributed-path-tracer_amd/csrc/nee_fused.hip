@@ -16,14 +16,14 @@ namespace ptx {
 // Threads per workgroup (one workgroup per CU) of a variant. One vertex's registers plus a traversal do not fit the 128 VGPRs of k_render_pass's
 // 1024-thread workgroup, so the kernel has launch bounds of its own: the largest workgroup at which the variant compiles WITHOUT scratch.
 // 768 threads = 3 waves per SIMD = 168 VGPRs hold the variants without texture and sun code (158-165 VGPRs); the others need 174-210 and
-// get 512 threads = 2 waves per SIMD = 256 VGPRs. Occupancy is what the kernel runs on (Cornell: 256 threads 185, 512 353, 768 465 Msamples/s;
+// get 512 threads = 2 waves per SIMD = 256 VGPRs; so do the ENV variants (always TEX: 207-228 VGPRs). Occupancy is what the kernel runs on (Cornell: 256 threads 185, 512 353, 768 465 Msamples/s;
 // DESIGN.md 5.7 has the resource table and the measurement). Staging is per workgroup and there is one workgroup per CU either way; the
 // overflow stacks are sized per wave slot of the larger k_render_pass workgroup. -DPTX_NEE_FUSED_BLOCK=n: one size for all (measurement).
-constexpr int nee_fused_block(bool tex, bool sun) {
+constexpr int nee_fused_block(bool tex, bool sun, bool env = false) {
 #ifdef PTX_NEE_FUSED_BLOCK
 	return PTX_NEE_FUSED_BLOCK;
 #else
-	return (tex || sun) ? 512 : 768;
+	return (tex || sun || env) ? 512 : 768;
 #endif
 }
 static_assert(nee_fused_block(false, false) % 64 == 0 && nee_fused_block(true, true) % 64 == 0 && nee_fused_block(false, false) <= kBlock && nee_fused_block(true, true) <= kBlock,
@@ -34,10 +34,12 @@ DEV uint32_t wave_sum(uint32_t v) {
 	return v;   // lane 0 holds the sum
 }
 
-template <int MODE, bool TEX, bool ALPHA, bool SUN>
-__global__ void __launch_bounds__(nee_fused_block(TEX, SUN)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
-                                                              const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space) {
-	constexpr int kThreads = nee_fused_block(TEX, SUN);
+// ENV: the variants of PTX_NEE_ENV_SAMPLES (TEX only); Ev, the last argument, is read by them alone.
+template <int MODE, bool TEX, bool ALPHA, bool SUN, bool ENV>
+__global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
+                                                              const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space,
+                                                              NeeEnv Ev) {
+	constexpr int kThreads = nee_fused_block(TEX, SUN, ENV);
 	DevScene S = S0;
 	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;  // see struct Tables
 	const Staged st = stage_geometry<MODE>(S, g_smem);
@@ -113,7 +115,7 @@ __global__ void __launch_bounds__(nee_fused_block(TEX, SUN)) k_nee_fused(DevScen
 			const int32_t surf = hit ? h.surface : -1;
 			const uint32_t tri = hit ? (h.tri & S.tri_id_mask) - S.surfaces[h.surface].tri_base : 0u;
 			NeeVertex v;
-			nee_vertex<TEX, ALPHA, SUN>(S, P, Lt, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v);
+			nee_vertex<TEX, ALPHA, SUN, ENV>(S, P, Lt, Ev, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v);
 			bool alive = v.alive;
 			// ---------------- the sun ray: occluded = any hit
 			if constexpr (SUN) {
@@ -140,7 +142,10 @@ __global__ void __launch_bounds__(nee_fused_block(TEX, SUN)) k_nee_fused(DevScen
 				const bool lhit = scene_traverse<MODE>(S, g, v.lo, v.ld, lh, spill);
 				rays++;
 				light_samples++;
-				if (lhit && lh.surface == (int32_t)v.exp_surf && (int32_t)((lh.tri & S.tri_id_mask) - S.surfaces[lh.surface].tri_base) == (int32_t)v.exp_tri) {
+				bool visible;
+				if (ENV && v.exp_surf == kNeeEnvRay) visible = !lhit;   // an environment sample
+				else visible = lhit && lh.surface == (int32_t)v.exp_surf && (int32_t)((lh.tri & S.tri_id_mask) - S.surfaces[lh.surface].tri_base) == (int32_t)v.exp_tri;
+				if (visible) {
 					light_visible++;
 					L.x += v.lx.x; L.y += v.lx.y; L.z += v.lx.z;
 				}
@@ -166,33 +171,38 @@ static hipError_t set_lds(const void* fn, size_t bytes) {
 	return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-template <int MODE, bool TEX, bool ALPHA, bool SUN>
-static hipError_t launch_nee_fused_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
+template <int MODE, bool TEX, bool ALPHA, bool SUN, bool ENV = false>
+static hipError_t launch_nee_fused_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
 	if (MODE != MODE_GLOBAL) {
-		hipError_t e = set_lds(reinterpret_cast<const void*>(&k_nee_fused<MODE, TEX, ALPHA, SUN>), lds_bytes);
+		hipError_t e = set_lds(reinterpret_cast<const void*>(&k_nee_fused<MODE, TEX, ALPHA, SUN, ENV>), lds_bytes);
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL((k_nee_fused<MODE, TEX, ALPHA, SUN>), dim3(grid), dim3(nee_fused_block(TEX, SUN)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces, S.spaces,
-	                   S.model_space);
+	hipLaunchKernelGGL((k_nee_fused<MODE, TEX, ALPHA, SUN, ENV>), dim3(grid), dim3(nee_fused_block(TEX, SUN, ENV)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces,
+	                   S.spaces, S.model_space, Ev);
 	return hipGetLastError();
 }
 
 // the variants of launch_nee_shade, per place of the geometry
 template <int MODE>
-static hipError_t launch_nee_fused_mode(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
+static hipError_t launch_nee_fused_mode(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
 	const bool sun = S.sun.present != 0;
-	if (S.any_texture) {
-		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, true, true, true>(S, P, Lt, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, true, false>(S, P, Lt, B, lds_bytes, grid, stream);
-		return sun ? launch_nee_fused_variant<MODE, true, false, true>(S, P, Lt, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, false, false>(S, P, Lt, B, lds_bytes, grid, stream);
+	if (Ev.row_cdf) {   // a table means a map, and a map means the TEX variants
+		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
+		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, true, true, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, true, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+		return sun ? launch_nee_fused_variant<MODE, true, false, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, false, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
 	}
-	if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, false, true, true>(S, P, Lt, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, false, true, false>(S, P, Lt, B, lds_bytes, grid, stream);
-	return sun ? launch_nee_fused_variant<MODE, false, false, true>(S, P, Lt, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, false, false, false>(S, P, Lt, B, lds_bytes, grid, stream);
+	if (S.any_texture) {
+		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, true, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, true, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+		return sun ? launch_nee_fused_variant<MODE, true, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, false, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+	}
+	if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, false, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, false, true, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+	return sun ? launch_nee_fused_variant<MODE, false, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, false, false, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
 }
 
-hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream) {
-	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS>(S, P, Lt, B, lds_bytes, grid, stream);
-	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID>(S, P, Lt, B, lds_bytes, grid, stream);
-	return launch_nee_fused_mode<MODE_GLOBAL>(S, P, Lt, B, lds_bytes, grid, stream);
+hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream) {
+	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+	return launch_nee_fused_mode<MODE_GLOBAL>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
 }
 
 }  // namespace ptx

@@ -245,9 +245,10 @@ int upload_scene(ptx_scene* sc) {
 void release_scene_buffers(ptx_scene* sc) {
 	for (DevBuf* b : {&sc->d_models, &sc->d_surfaces, &sc->d_materials, &sc->d_nodes, &sc->d_refs, &sc->d_tris, &sc->d_shade, &sc->d_tex,
 	                  &sc->d_texels, &sc->d_texels_f, &sc->d_lut, &sc->d_spaces, &sc->d_model_space, &sc->d_wf_order, &sc->d_res_nodes, &sc->d_res_refs, &sc->d_res_tris, &sc->d_hot,
-	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first})
+	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell})
 		b->release();
 	sc->lights.on_device = false;
+	sc->env_table.on_device = false;
 }
 
 int finish_scene(ptx_ctx* ctx, ptx_scene* sc, ptx_scene** out) {
@@ -307,6 +308,71 @@ const ptx_scene::LightList* build_lights(ptx_scene* sc) {
 	ll.area = (float)total;
 	ll.built = true;
 	return &ll;
+}
+
+// The sampling table of the environment map (include/ptx.h: THE ENVIRONMENT TABLE). Luminances as the kernels' tex_pixel reads the texels,
+// sums and shares in float64, stored as float32.
+const ptx_scene::EnvTable* build_env_table(ptx_scene* sc) {
+	std::lock_guard<std::mutex> lk(sc->lights_mu);
+	ptx_scene::EnvTable& et = sc->env_table;
+	if (et.built) return &et;
+	et.built = true;
+	const FlatScene& h = sc->host;
+	if (h.env_tex < 0) return &et;
+	const TexRec t = h.textures[(size_t)h.env_tex];
+	const uint32_t w = t.w, hh = t.h, c = t.c_srgb & 255u;
+	if (!w || !hh || !c) return &et;
+	float lut[256];
+	for (int b = 0; b < 256; b++) lut[b] = std::pow(b / 255.0F, 2.2F);
+	auto chan = [&](uint32_t px, uint32_t py, uint32_t ch) -> double {   // tex_chan / tex_pixel: channels the image does not have are 1
+		if (ch >= c) return 1.0;
+		const bool srgb = (t.c_srgb & kTexSrgb) != 0 && ch < 3;
+		const size_t at = (size_t)t.offset + ((size_t)py * w + px) * c + ch;
+		if (t.c_srgb & kTexFloat) { const float v = h.texels_f[at]; return srgb ? std::pow(v, 2.2F) : v; }
+		const uint32_t b = h.texels[at];
+		return srgb ? lut[b] : (float)b / 255.0F;
+	};
+	std::vector<double> lum((size_t)w * hh);
+	for (uint32_t j = 0; j < hh; j++)
+		for (uint32_t i = 0; i < w; i++) {
+			const double l = (0.2126 * chan(i, j, 0) + 0.7152 * chan(i, j, 1)) + 0.0722 * chan(i, j, 2);
+			lum[(size_t)j * w + i] = l > 0 ? l : 0.0;   // negative and NaN count as 0
+		}
+	// weight = (luminance over the 3 x 3 texels the bilinear lookup can touch from inside the box, wrapped as tex_sample wraps) * cos(latitude of the row's centre)
+	std::vector<double> wgt((size_t)w * hh), row_mass(hh);
+	double total = 0;
+	for (uint32_t j = 0; j < hh; j++) {
+		const double lat = ((1.0 - ((double)j + 0.5) / (double)hh) - 0.5) / 0.3183;
+		const double cl = std::max(std::cos(lat), 0.0);
+		double mass = 0;
+		for (uint32_t i = 0; i < w; i++) {
+			double s = 0;
+			for (int dj = -1; dj <= 1; dj++)
+				for (int di = -1; di <= 1; di++) s += lum[(size_t)((j + hh + dj) % hh) * w + (i + w + di) % w];
+			wgt[(size_t)j * w + i] = s * cl;
+			mass += s * cl;
+		}
+		row_mass[j] = mass;
+		total += mass;
+	}
+	if (!(total > 0) || !std::isfinite(total)) return &et;   // a black map: no table
+	et.w = w; et.h = hh;
+	et.row_cdf.resize(hh);
+	et.cell_cdf.assign((size_t)w * hh, 0.0f);
+	double cum = 0;
+	for (uint32_t j = 0; j < hh; j++) {
+		cum += row_mass[j];
+		et.row_cdf[j] = (float)(cum / total);
+		if (!(row_mass[j] > 0)) continue;   // a row of zero mass: all zeros
+		double cc = 0;
+		for (uint32_t i = 0; i < w; i++) {
+			cc += wgt[(size_t)j * w + i];
+			et.cell_cdf[(size_t)j * w + i] = (float)(cc / row_mass[j]);
+		}
+		et.cell_cdf[(size_t)j * w + w - 1] = 1.0f;
+	}
+	et.row_cdf[hh - 1] = 1.0f;
+	return &et;
 }
 
 extern "C" {
@@ -451,6 +517,10 @@ int ptx_scene_set_environment(ptx_scene* sc, const char* png_path, int srgb) {
 	std::unique_lock<std::mutex> lk;
 	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);
 	FlatScene& h = sc->host;
+	{   // the sampling table belongs to the map that goes
+		std::lock_guard<std::mutex> tl(sc->lights_mu);
+		sc->env_table = ptx_scene::EnvTable{};
+	}
 	if (h.env_tex >= 0) {   // the previous map is always the last texture (appended below): drop it instead of letting them pile up
 		const TexRec old = h.textures[(size_t)h.env_tex];
 		if (old.c_srgb & kTexFloat) h.texels_f.resize(old.offset); else h.texels.resize(old.offset);
@@ -583,6 +653,8 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 	case PTX_ARR_LIGHT_TRIS: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.tris.data(); bytes = ll.tris.size() * 4; break; }
 	case PTX_ARR_LIGHT_CDF: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.cdf.data(); bytes = ll.cdf.size() * 4; break; }
 	case PTX_ARR_LIGHT_GEOM: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.geom.data(); bytes = ll.geom.size() * 4; break; }
+	case PTX_ARR_ENV_ROW_CDF: { const auto& et = *build_env_table(const_cast<ptx_scene*>(sc)); src = et.row_cdf.data(); bytes = et.row_cdf.size() * 4; break; }
+	case PTX_ARR_ENV_CELL_CDF: { const auto& et = *build_env_table(const_cast<ptx_scene*>(sc)); src = et.cell_cdf.data(); bytes = et.cell_cdf.size() * 4; break; }
 	case PTX_ARR_TRI_ISECT: src = h.tri_isect.data(); bytes = h.tri_isect.size() * sizeof(TriIsect); break;
 	case PTX_ARR_RES_NODES: src = h.res_nodes.data(); bytes = h.res_nodes.size() * 8; break;
 	case PTX_ARR_RES_REFS: src = h.res_refs.data(); bytes = h.res_refs.size() * 4; break;

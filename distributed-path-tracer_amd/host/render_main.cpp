@@ -1,10 +1,12 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
 //       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
 //       --nee:         light sampling towards the scene's emissive triangles (renderer::render_nee)
 //       --nee-fused:   --nee with one kernel launch per pass (PTX_NEE_FUSED): the same frame; ignored on scenes of the queue pipeline
+//       --nee-env MAP: --nee under the environment map MAP (renderer::environment; PNG, JPEG or Radiance .hdr), the light sample going
+//                      towards the map too (PTX_NEE_ENV_SAMPLES); combines with --nee-fused
 //       --adaptive THR[:MIN[:STEP]]: noise-driven per-pixel sample counts (renderer::render_adaptive) with spp as the cap: every pixel gets MIN
 //                      samples (8), then rounds of STEP (MIN) go to the pixels whose half-frames still disagree by more than THR
 //       --aov PREFIX:  also writes the denoiser's guide images PREFIX_albedo.png (mean albedo of the covered samples, alpha = coverage)
@@ -38,12 +40,13 @@ int main(int argc, char** argv) {
 	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false;
 	float ad_thr = 0.1f;
 	unsigned ad_min = 8, ad_step = 0;
-	std::string aov_prefix;
+	std::string aov_prefix, nee_env;
 	for (;;) {   // leading switches
 		if (argc > 1 && std::string(argv[1]) == "--transparent") { transparent = true; argv[1] = argv[0]; argv++; argc--; }
 		else if (argc > 1 && std::string(argv[1]) == "--denoise") { denoise = true; argv[1] = argv[0]; argv++; argc--; }
 		else if (argc > 1 && std::string(argv[1]) == "--nee") { nee = true; argv[1] = argv[0]; argv++; argc--; }   // renderer::render_nee: light sampling
 		else if (argc > 1 && std::string(argv[1]) == "--nee-fused") { nee = nee_fused = true; argv[1] = argv[0]; argv++; argc--; }   // ... one launch per pass
+		else if (argc > 2 && std::string(argv[1]) == "--nee-env") { nee = true; nee_env = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }   // ... the map as a light
 		else if (argc > 2 && std::string(argv[1]) == "--adaptive") {
 			if (std::sscanf(argv[2], "%f:%u:%u", &ad_thr, &ad_min, &ad_step) < 1) { std::fprintf(stderr, "error: --adaptive THR[:MIN[:STEP]]\n"); return 1; }
 			adaptive = true; argv[2] = argv[0]; argv += 2; argc -= 2;
@@ -52,7 +55,7 @@ int main(int argc, char** argv) {
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (argc == 5 && std::string(argv[1]) == "--event") {
@@ -90,6 +93,7 @@ int main(int argc, char** argv) {
 			r.sample_count = 64;
 		}
 		r.load_gltf(argv[1]);
+		if (!nee_env.empty()) r.environment = nee_env;
 		auto t0 = std::chrono::steady_clock::now();
 		ptx_denoise_stats dst{};
 		ptx_adaptive_stats ast{};
@@ -97,7 +101,7 @@ int main(int argc, char** argv) {
 		if (adaptive && denoise) throw std::runtime_error("--adaptive and --denoise do not combine: the filter takes one sample count per buffer");
 		ptx_nee_stats nst{};
 		if (nee && (adaptive || denoise || transparent)) throw std::runtime_error("--nee does not combine with --adaptive, --denoise or --transparent");
-		std::vector<uint8_t> png = nee ? r.encode(r.render_nee(&nst, nee_fused ? PTX_NEE_FUSED : 0u), r.sample_count)
+		std::vector<uint8_t> png = nee ? r.encode(r.render_nee(&nst, (nee_fused ? PTX_NEE_FUSED : 0u) | (nee_env.empty() ? 0u : PTX_NEE_ENV_SAMPLES)), r.sample_count)
 		                               : adaptive ? r.encode(r.render_adaptive(&ast), 1) : denoise ? r.encode(r.render_denoised(&dst), 1) : r.render();
 		double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 		std::ofstream(argv[2], std::ios::binary).write((const char*)png.data(), (std::streamsize)png.size());

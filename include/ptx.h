@@ -158,8 +158,12 @@ typedef enum ptx_array {
 	PTX_ARR_RES_REFS = 22,    /* uint32[.]: leaf references of the ref-indexed resident surfaces, indices into RES_TRIS */
 	PTX_ARR_RES_TRIS = 23,    /* uint32[.][12]: resident records: one per triangle (ref-indexed surface) or per leaf reference (leaf-ordered) */
 	PTX_ARR_LDS_ROOT = 24,    /* uint32[n_surfaces]: 0xFFFFFFFF = not resident, else root index in RES_NODES | leaf-ordered << 31 */
-	PTX_ARR_RES_PLAN = 25     /* uint32[4]: bytes of the resident arrays + shade records, resident surfaces, dynamic LDS bytes of the fused
+	PTX_ARR_RES_PLAN = 25,    /* uint32[4]: bytes of the resident arrays + shade records, resident surfaces, dynamic LDS bytes of the fused
 	                           * kernels (0 on a host-only scene), hot hit records */
+	/* the environment map's sampling table of PTX_NEE_ENV_SAMPLES (built at the first request, on host-only scenes too; both empty when the
+	 * scene has no map or the map is black; ptx_scene_set_environment drops the table) */
+	PTX_ARR_ENV_ROW_CDF = 26, /* float[h]: cumulative share of the rows' mass, top row first, the last entry 1 */
+	PTX_ARR_ENV_CELL_CDF = 27 /* float[h][w]: cumulative share of the boxes within their row, the last entry 1; a row of zero mass is all 0 */
 } ptx_array;
 int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, size_t dst_bytes);
 
@@ -379,8 +383,8 @@ int ptx_accum_mean(ptx_ctx* ctx, const float* accum_a, const float* accum_b /* N
  * Tiles, sample0, spp_per_pass, shard_*, host or device accum and bounces == 0 work as in ptx_render.
  * Refusals, all decided before any device work: PTX_ERR_UNSUPPORTED for PTX_INTEGRATOR_WORKER; PTX_ERR_NO_DEVICE for a host-only scene;
  * PTX_ERR_INVALID for NULL scene, cfg or accum, unknown flags and whatever ptx_render refuses in cfg.
- * Out of scope: ptx_render_transparent's blend, ptx_render_adaptive on this estimator, the worker estimator, sampling the environment
- * map, and multigpu.py (its shards and sample ranges already compose through the accum format). */
+ * Out of scope: ptx_render_transparent's blend, ptx_render_adaptive on this estimator, the worker estimator, and multigpu.py (its shards
+ * and sample ranges already compose through the accum format). */
 #define PTX_NEE_NO_LIGHT_SAMPLES 1u   /* run with an empty list */
 /* PTX_NEE_FUSED: render with ONE kernel launch per pass wherever ptx_render would run this scene on its fused kernel (pipeline 0: LDS-resident and
  * hybrid scenes, global-memory scenes under PTX_WAVEFRONT=0): a lane carries a path from its camera ray to its end in registers, without the
@@ -392,6 +396,37 @@ int ptx_accum_mean(ptx_ctx* ctx, const float* accum_a, const float* accum_b /* N
  * and the call runs exactly as without it (fused_launches == 0) — not a refusal, so a caller may always set it. May be combined with
  * PTX_NEE_NO_LIGHT_SAMPLES. Value 2u is unassigned and refused as unknown. */
 #define PTX_NEE_FUSED 4u
+/* PTX_NEE_ENV_SAMPLES: the light sample of a vertex may go towards the environment map (ptx_scene_set_environment), importance-sampled by
+ * luminance; the map's radiance collected on a miss is weighted against that sample, so the expectation of the frame is still LIB's
+ * (as far as LIB's pdf is the density of LIB's sampler, which its specular lobe's is not: DESIGN.md 5.7 has the measured shift).
+ * Ignored when the scene has no map or the map is black: the call is then bit for bit the one without the flag. Combines with
+ * PTX_NEE_FUSED (bitwise the same frame; ignored on the queue route as above) and with PTX_NEE_NO_LIGHT_SAMPLES, which empties the
+ * triangle list only. Values 2u and 8u are unassigned and refused as unknown.
+ *   THE ENVIRONMENT TABLE (PTX_ARR_ENV_*), for a map of w x h texels, built on the host in float64 and stored as float32. Box (i, j) is
+ *     u in [i / w, (i + 1) / w), 1 - v in [j / h, (j + 1) / h) of the miss lookup u = atan2f(d.z, d.x) * 0.1591F + 0.5F,
+ *     v = asinf(d.y) * 0.3183F + 0.5F. lum(i, j) = 0.2126 r + 0.7152 g + 0.0722 b of the texel as the kernels read it (sRGB table, missing
+ *     channels 1), a negative or NaN luminance counting as 0. weight(i, j) = (sum of lum over the 3 x 3 texels around (i, j), wrapped modulo
+ *     w and h as the bilinear lookup wraps: every texel the lookup can touch from inside the box) * max(cos(lat_j), 0) with
+ *     lat_j = ((1 - (j + 0.5) / h) - 0.5) / 0.3183. row_cdf[j] = cumulative row mass / total, cell_cdf[j][i] = cumulative weight of row j /
+ *     its mass, last entries 1, a row of zero mass all 0. Total mass 0: no table.
+ *   THE PDF env_pdf(d), a function of the direction alone, used by both sides: (u, v) by the lookup's expressions; i = min((uint32_t)(u * w),
+ *     w - 1), j likewise from (1 - v) * h; P = (row_cdf[j] - row_cdf[j - 1]) * (cell_cdf[j][i] - cell_cdf[j][i - 1]) from the stored values
+ *     with cdf[-1] = 0; c = sqrt(max(0, 1 - d.y * d.y)); env_pdf = ((P * (float)(w * h)) * (0.1591F * 0.3183F)) / c, and 0 when c is not
+ *     > 0. P from the stored differences is exactly what the sampler realises: a box that float32 rounds to probability 0 is never sampled
+ *     and has weight 1 on the BSDF side.
+ *   SELECTION. c_env = 1 when the triangle list is empty, 0.5 when both strategies exist. With r = draws(.., block 3) the vertex samples the
+ *     map iff the list is empty or r.w < 0.5F; otherwise a triangle as above. Wherever the formulas above have p_l, (1 - c_env) * p_l
+ *     takes its place (the emission weight and wl).
+ *   ENVIRONMENT SAMPLE: q = draws(pixel, sample, depth, pass, block 4); row j = the first with q.x < row_cdf[j] (clamped to h - 1), column
+ *     i = the first with q.y < cell_cdf[j][i] (clamped to w - 1); u = (i + q.z) / w, v = 1 - (j + q.w) / h; phi = (u - 0.5F) / 0.1591F,
+ *     lat = (v - 0.5F) / 0.3183F; w_dir = (cos lat * cos phi, sin lat, cos lat * sin phi). No contribution and no shadow ray unless the
+ *     lookup maps w_dir to box (i, j) again (this drops the sliver of (u, v), about 3e-4 of the domain, that the truncated constants make
+ *     unreachable for the lookup, and keeps the pdf a function of direction), dot(n_x, w_dir) > 0, p = env_pdf(w_dir) > 0 and max(Le) > 0
+ *     with Le = lookup(w_dir).rgb * cfg.env. brdf, pe, qc as for a triangle sample; wl = pe / (pe + c_env * p); x = ((T * qc) * wl) * Le.
+ *     The shadow ray (origin pos_x + w_dir * eps, direction w_dir) is a closest-hit query; x is added iff it finds nothing.
+ *   MISS WEIGHT. L += (T * env) * wm. wm = 1 (no arithmetic) when depth == 0 or pass > 0; otherwise wm = p_prev / (p_prev + c_env * env_pdf(d)).
+ * Order of the additions and the stats are unchanged: light_samples and light_visible count both kinds of light ray. */
+#define PTX_NEE_ENV_SAMPLES 16u
 typedef struct ptx_nee_cfg { uint32_t flags; } ptx_nee_cfg;
 typedef struct ptx_nee_stats {
 	ptx_render_stats render;   /* rays = closest-hit + shadow queries */

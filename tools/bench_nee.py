@@ -10,6 +10,13 @@
                                         ones in the same process, each kept with the spread of its repeats (*_s_max), and with ptx_render at
                                         the spp that takes the flagged call's time; fused_launches tells which route ran (0: the scene is on
                                         the queue route, where the flag is ignored).
+  tools/bench_nee.py --env [ref_spp] [reps]
+                                        PTX_NEE_ENV_SAMPLES on the open plaza (level 3, no alpha, no analytic sun) at 960 x 540, 8 bounces, under a
+                                        512 x 256 sky map with a sun disc of 2.5 degrees radius written to a temporary .hdr: ptx_render_nee with
+                                        and without the flag (both with PTX_NEE_FUSED) at 16 and 64 spp — time, mean squared error of the
+                                        written bytes against the product's ref_spp ptx_render frame (1024) of another seed: at equal
+                                        samples, and the unflagged call at the spp that takes the flagged call's time; and the flagged call
+                                        fused against unfused (time, bitwise). Also writes the lines to profiles/nee_env_bench.txt.
 Prints one JSON line per measurement. A scene without listed emitters (atrium) shows the cost of the wavefront form alone.
 """
 import importlib
@@ -103,5 +110,81 @@ def main(ref_spp, reps):
         s.close()
 
 
+def sun_disc_map(path, w=512, h=256, radius_deg=2.5, elevation_deg=40.0, azimuth_deg=60.0, sky=(0.25, 0.35, 0.55), sun=(6000.0, 5400.0, 4200.0)):
+    """an uncompressed Radiance .hdr: a dim sky and a sun disc, texel centres through the inverse of the miss lookup"""
+    import struct
+    v = 1 - (np.arange(h) + 0.5) / h
+    u = (np.arange(w) + 0.5) / w
+    lat, phi = (v - 0.5) / 0.3183, (u - 0.5) / 0.1591
+    d = np.stack([np.cos(lat)[:, None] * np.cos(phi)[None], np.repeat(np.sin(lat)[:, None], w, 1), np.cos(lat)[:, None] * np.sin(phi)[None]], -1)
+    el, az = np.radians(elevation_deg), np.radians(azimuth_deg)
+    c = np.array([np.cos(el) * np.cos(az), np.sin(el), np.cos(el) * np.sin(az)])
+    rgb = np.where((d @ c >= np.cos(np.radians(radius_deg)))[..., None], np.array(sun), np.array(sky))
+    mant, ex = np.frexp(rgb.max(-1))
+    sc = mant * 256.0 / rgb.max(-1)
+    px = np.concatenate([(rgb * sc[..., None]).astype(np.uint8), (ex + 128).astype(np.uint8)[..., None]], -1)
+    with open(path, "wb") as f:
+        f.write(b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n" + f"-Y {h} +X {w}\n".encode() + px.tobytes())
+    return path
+
+
+def main_env(ref_spp, reps):
+    import tempfile
+    global W, H
+    W, H = 960, 540
+    ctx = ptx.Context(0)
+    s = ptx.Scene.from_arrays(ctx, *[proc.plaza_scene(alpha=False, sun=False)[k] for k in KEYS])
+    with tempfile.TemporaryDirectory() as tmp:
+        s.set_environment(sun_disc_map(os.path.join(tmp, "sun_disc.hdr")), srgb=False)
+    lines = []
+
+    def image(acc, spp):
+        return ctx.tonemap_encode(acc, W, H, spp)[..., :3].astype(np.float64) / 255
+
+    def timed(call, spp):
+        best, acc, st = 1e30, None, None
+        for rep in range(reps + 1):
+            acc = zeros()
+            t0 = time.perf_counter()
+            _, st = call(spp, acc)
+            ctx.synchronize()
+            if rep:
+                best = min(best, time.perf_counter() - t0)
+        return best, acc, st
+    ref_acc = zeros()
+    s.render(W, H, ref_spp, BOUNCES, accum=ref_acc, seed=REF_SEED, want_stats=False)
+    ctx.synchronize()
+    ref = image(ref_acc, ref_spp)
+    del ref_acc
+
+    def mse(acc, spp):
+        return float(np.mean((image(acc, spp) - ref) ** 2))
+
+    def call(flags):
+        return lambda spp, acc: s.render_nee(W, H, spp, BOUNCES, accum=acc, seed=SEED, flags=flags)
+    for spp in (16, 64):
+        t_env, a_env, st_env = timed(call(ptx.NEE_ENV_SAMPLES | ptx.NEE_FUSED), spp)
+        launches = ctx.timing()["fused_launches"]
+        t_un, a_un, st_un = timed(call(ptx.NEE_FUSED), spp)
+        t_envu, a_envu, st_envu = timed(call(ptx.NEE_ENV_SAMPLES), spp)
+        spp_eq = max(1, int(round(spp * t_env / t_un)))
+        t_eq, a_eq, _ = timed(call(ptx.NEE_FUSED), spp_eq)
+        same = bool((a_env == a_envu).all()) and all(st_env[k] == st_envu[k] for k in ("rays", "light_samples", "light_visible"))
+        lines.append(json.dumps(dict(scene="plaza3_opaque_nosun", map="sun disc 512x256", W=W, H=H, bounces=BOUNCES, spp=spp, n_lights=st_env["n_lights"],
+                                     env_s=round(t_env, 4), env_msamples_s=round(W * H * spp / t_env / 1e6, 1), env_rays=st_env["rays"],
+                                     env_light_samples=st_env["light_samples"], env_light_visible=st_env["light_visible"], env_mse=mse(a_env, spp),
+                                     unflagged_s=round(t_un, 4), unflagged_rays=st_un["rays"], unflagged_mse=mse(a_un, spp),
+                                     unflagged_equal_time_spp=spp_eq, unflagged_equal_time_s=round(t_eq, 4), unflagged_equal_time_mse=mse(a_eq, spp_eq),
+                                     env_unfused_s=round(t_envu, 4), env_fused_launches=launches, env_fused_bitwise_unfused=same,
+                                     env_fused_speedup=round(t_envu / t_env, 3), ref_spp=ref_spp)))
+        print(lines[-1], flush=True)
+    s.close()
+    with open(os.path.join(ROOT, "profiles", "nee_env_bench.txt"), "w") as f:
+        f.write("tools/bench_nee.py --env: PTX_NEE_ENV_SAMPLES against the unflagged ptx_render_nee (both PTX_NEE_FUSED), MI355X\n" + "\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--env":
+        main_env(int(sys.argv[2]) if len(sys.argv) > 2 else 1024, int(sys.argv[3]) if len(sys.argv) > 3 else 3)
+        sys.exit(0)
     main(int(sys.argv[1]) if len(sys.argv) > 1 else 4096, int(sys.argv[2]) if len(sys.argv) > 2 else 3)
