@@ -182,7 +182,11 @@ int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, 
  *                        ACCUMULATE (src/processors/worker/intersection_worker.cpp:10-67, shading_worker.cpp:10-201,
  *                        worker.cpp:114-149): emissive added before the opacity test, throughput clamped to [0,10],
  *                        Russian roulette once bounce < bounce_count-2, un-jittered sample 0, and a shadow catcher that
- *                        is black unless its sun sample is unoccluded. HOST cannot be built here: parity unpinned. */
+ *                        is black unless its sun sample is unoccluded. Pinned: the oracle the kernels are tested against replays
+ *                        the compiled worker stages' own random streams bit for bit, and the un-jittered first sample at one
+ *                        bounce is compared with compiled worker output at zero tolerance (tests/test_worker_pin.py). Not
+ *                        replicated: entity visit order on exact distance ties between models, thread timing, and
+ *                        bounce_count = 0 (the reference's uint8_t bounce wraps; here the render is black). */
 typedef enum ptx_integrator { PTX_INTEGRATOR_LIB = 0, PTX_INTEGRATOR_WORKER = 1 } ptx_integrator;
 typedef struct ptx_render_cfg {
 	uint32_t W, H;          /* renderer::resolution (1920 x 1080) */

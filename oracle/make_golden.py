@@ -14,6 +14,7 @@ fixtures themselves are committed so the tests run anywhere.
     python oracle/make_golden.py --only-pbr-edges  # pbr_edges.npz: the BSDF functions at the edges of their domains (a second)
     python oracle/make_golden.py --only-deep-walk  # deep_walk_vectors.npz: renderer::intersect on the corner-cluster meshes (a few seconds)
     python oracle/make_golden.py --only-chart      # the material chart as glTF (tests/golden/chart/) and chart_trace.npz (a few seconds)
+    python oracle/make_golden.py --only-worker     # worker_trace.npz, worker_frame.npz, worker_scene.npz: the compiled HOST worker (seconds)
 """
 import argparse
 import glob
@@ -496,7 +497,10 @@ CHART_DIR = os.path.join(GOLD, "chart")
 # fixture tag -> (chart_scene options, rays). The reference's sun radius is fixed. The harness aims half its rays from the camera at
 # points of the scene's box: with the facing chart the box is tall and few of them reach a given patch of the upper chart, hence more
 # rays there, and no blocker (it widens the box); the blocker has the flat chart to itself.
-CHART_FIXTURES = {"chart": (dict(sun=0.004732, blocker=True), 4000), "chart_facing": (dict(sun=0.004732, facing=True), 10000)}
+# chart_plain (no sun, no patch a ray can pass through) is not traced here (0 rays): it is the frame of worker_frame.npz in which no
+# random draw reaches the colour.
+CHART_FIXTURES = {"chart": (dict(sun=0.004732, blocker=True), 4000), "chart_facing": (dict(sun=0.004732, facing=True), 10000),
+                  "chart_plain": (dict(alpha=False), 0)}
 
 
 def _quat_from_z(d):
@@ -544,16 +548,18 @@ def write_chart_scene(tag):
     with open(os.path.join(CHART_DIR, tag + ".bin"), "wb") as fh:
         fh.write(bytes(blob))
     sun = d["sun"]
-    g = {"asset": {"version": "2.0", "generator": "oracle/make_golden.py --only-chart"},
-         "extensionsUsed": ["KHR_lights_punctual"],
-         "extensions": {"KHR_lights_punctual": {"lights": [{"name": "sun", "type": "directional", "intensity": 1.0, "color": fl(sun[9:12])}]}},
-         "scene": 0, "scenes": [{"nodes": [0, 1, 2]}],
-         "cameras": [{"name": "cam", "type": "perspective", "perspective": {"yfov": float(d["camera"][12]), "znear": 0.01, "aspectRatio": 1.7778}}],
-         "nodes": [{"name": "cam", "camera": 0, "translation": fl(d["camera"][0:3]), "rotation": [-float(np.sqrt(0.5)), 0.0, 0.0, float(np.sqrt(0.5))]},
-                   {"name": "sun", "rotation": fl(_quat_from_z(sun[6:9].astype(np.float64))), "extensions": {"KHR_lights_punctual": {"light": 0}}},
-                   {"name": "chart", "mesh": 0}],
-         "meshes": [{"name": "chart", "primitives": prims}], "materials": mats,
-         "buffers": [{"uri": tag + ".bin", "byteLength": len(blob)}], "bufferViews": views, "accessors": accessors}
+    nodes = [{"name": "cam", "camera": 0, "translation": fl(d["camera"][0:3]), "rotation": [-float(np.sqrt(0.5)), 0.0, 0.0, float(np.sqrt(0.5))]}]
+    g = {"asset": {"version": "2.0", "generator": "oracle/make_golden.py --only-chart"}}
+    if sun is not None:
+        g["extensionsUsed"] = ["KHR_lights_punctual"]
+        g["extensions"] = {"KHR_lights_punctual": {"lights": [{"name": "sun", "type": "directional", "intensity": 1.0, "color": fl(sun[9:12])}]}}
+        nodes.append({"name": "sun", "rotation": fl(_quat_from_z(sun[6:9].astype(np.float64))), "extensions": {"KHR_lights_punctual": {"light": 0}}})
+    nodes.append({"name": "chart", "mesh": 0})
+    g.update({"scene": 0, "scenes": [{"nodes": list(range(len(nodes)))}],
+              "cameras": [{"name": "cam", "type": "perspective", "perspective": {"yfov": float(d["camera"][12]), "znear": 0.01, "aspectRatio": 1.7778}}],
+              "nodes": nodes,
+              "meshes": [{"name": "chart", "primitives": prims}], "materials": mats,
+              "buffers": [{"uri": tag + ".bin", "byteLength": len(blob)}], "bufferViews": views, "accessors": accessors})
     with open(os.path.join(CHART_DIR, tag + ".gltf"), "w") as fh:
         json.dump(g, fh, indent=1)
         fh.write("\n")
@@ -566,6 +572,8 @@ def make_chart_fixture(env, bounces=6):
     with tempfile.TemporaryDirectory() as tmp:
         for k, (tag, (_, n)) in enumerate(CHART_FIXTURES.items()):
             write_chart_scene(tag)
+            if n == 0:
+                continue
             d = os.path.join(tmp, tag)
             subprocess.check_call([HARNESS, "trace", os.path.join(CHART_DIR, tag + ".gltf"), d, str(11 + k), str(n), str(bounces)],
                                   env=dict(env, ORACLE_SEED=str(31337 + k)))
@@ -573,6 +581,63 @@ def make_chart_fixture(env, bounces=6):
     dst = os.path.join(GOLD, "chart_trace.npz")
     np.savez_compressed(dst, **out)
     print(f"chart/ and chart_trace.npz written ({os.path.getsize(dst) / 1024:.0f} KiB)")
+
+
+# ---- the HOST worker (oracle/host_harness.cpp): fixtures that pin ora_trace_worker_mt and the loader's primitive filter
+HOST_HARNESS = os.path.join(HERE, "_ref", "host_harness")
+# tag -> (glTF, harness ray seed, rays, bounces, ORACLE_SEED)
+WORKER_TRACE = {"cornell": (CORNELL, 19, 2000, 8, 515151), "jack": (JACK, 20, 4000, 6, 888),
+                "chart": (os.path.join(CHART_DIR, "chart.gltf"), 21, 4000, 6, 41414), "chart_facing": (os.path.join(CHART_DIR, "chart_facing.gltf"), 22, 10000, 6, 41415)}
+# tag -> (glTF, X, Y, spp, bounces, ORACLE_SEED)
+WORKER_FRAME = {"cornell_3spp": (CORNELL, 32, 32, 3, 5, 61616), "cornell_first": (CORNELL, 32, 32, 1, 1, 61617),
+                "chart_plain_first": (os.path.join(CHART_DIR, "chart_plain.gltf"), 48, 40, 1, 1, 61618)}
+# tag -> (glTF, scene_work or None = every primitive)
+LIT_GLTF = os.path.join(GOLD, "textures", "lit.gltf")
+WORKER_SCENE = {"lit_047": (LIT_GLTF, {"lit": [0, 4, 7]}), "lit_rest": (LIT_GLTF, {"lit": [1, 2, 3, 5, 6, 8, 9]}),
+                "chart": (os.path.join(CHART_DIR, "chart.gltf"), None),
+                "cornell_work": (CORNELL, {"Cube.003": [0, 2], "Sphere": [0], "No.Such.Mesh": [0]})}
+WORKER_SCENE_KEYS = ("model_names", "model_xform", "model_surf", "surf_range", "vertices", "triangles", "materials", "material_tex", "camera",
+                     "sun", "ws_rays", "ws_out", "ws_idx", "ws_min")
+
+
+def worker_trace_arrays(env, tag, tmp):
+    gltf, pcg, n, b, seed = WORKER_TRACE[tag]
+    d = os.path.join(tmp, "wt_" + tag)
+    subprocess.check_call([HOST_HARNESS, "worker-trace", gltf, d, str(pcg), str(n), str(b)], env=dict(env, ORACLE_SEED=str(seed)))
+    return {f"{tag}_{a}": np.load(os.path.join(d, f"wt_{a}.npy")) for a in ("rays", "out", "meta")}
+
+
+def worker_frame_arrays(env, tag, tmp):
+    gltf, X, Y, spp, b, seed = WORKER_FRAME[tag]
+    d = os.path.join(tmp, "wf_" + tag)
+    subprocess.check_call([HOST_HARNESS, "worker-frame", gltf, d, str(X), str(Y), str(spp), str(b)], env=dict(env, ORACLE_SEED=str(seed)))
+    return {f"{tag}_{a}": np.load(os.path.join(d, f"wf_{a}.npy")) for a in ("uuid", "rays", "out", "meta")}
+
+
+def worker_scene_arrays(env, tag, tmp):
+    gltf, work = WORKER_SCENE[tag]
+    d = os.path.join(tmp, "ws_" + tag)
+    args = [] if work is None else [f"{m}=" + ",".join(str(i) for i in p) for m, p in work.items()]
+    subprocess.check_call([HOST_HARNESS, "worker-scene", gltf, d] + args, env=env)
+    return {f"{tag}_{a}": np.load(os.path.join(d, a + ".npy")) for a in WORKER_SCENE_KEYS}
+
+
+def make_worker_fixtures(env):
+    """tests/golden/worker_trace.npz, worker_frame.npz, worker_scene.npz: the compiled HOST worker's stage functions, one sample at a
+    time on one thread (oracle/host_harness.cpp). meta = [ORACLE_SEED, k of the jitter / sun-cone / shading stream (the k-th seeded
+    mt19937 has the seed ORACLE_SEED + 7919 k; 0xFFFFFFFF: never seeded), X, Y, spp, bounces]."""
+    subprocess.check_call(["make", "-s", "-j8", "-C", HERE, "ref-host"])
+    for tag in ("chart", "chart_facing", "chart_plain"):
+        write_chart_scene(tag)
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, table, fn in (("worker_trace", WORKER_TRACE, worker_trace_arrays), ("worker_frame", WORKER_FRAME, worker_frame_arrays),
+                                ("worker_scene", WORKER_SCENE, worker_scene_arrays)):
+            out = {}
+            for tag in table:
+                out.update(fn(env, tag, tmp))
+            dst = os.path.join(GOLD, name + ".npz")
+            np.savez_compressed(dst, **out)
+            print(f"{name}.npz written ({os.path.getsize(dst)} bytes)")
 
 
 def write_arrays_scene(path, d, name):
@@ -685,6 +750,7 @@ def main():
     ap.add_argument("--only-pbr-edges", action="store_true", help="regenerate pbr_edges.npz only")
     ap.add_argument("--only-chart", action="store_true", help="regenerate tests/golden/chart/* and chart_trace.npz only")
     ap.add_argument("--only-deep-walk", action="store_true", help="regenerate deep_walk_vectors.npz only")
+    ap.add_argument("--only-worker", action="store_true", help="regenerate worker_trace.npz, worker_frame.npz and worker_scene.npz only (the HOST worker)")
     ap.add_argument("--n", type=int, default=1024)
     args = ap.parse_args()
     if args.only_lit_textures:
@@ -701,6 +767,9 @@ def main():
         return
     if args.only_chart:
         make_chart_fixture(env)
+        return
+    if args.only_worker:
+        make_worker_fixtures(env)
         return
     if args.only_pbr_edges:
         make_pbr_edges_fixture(env)
@@ -779,6 +848,7 @@ def main():
         write_lit_texture_scene()
         make_tri_scaled_fixture(env)
         make_chart_fixture(env)
+        make_worker_fixtures(env)
         make_pbr_edges_fixture(env)
         make_deep_walk_fixture(env)
         # a small deterministic PNG from renderer::render itself (single thread + fixed seed => reproducible)

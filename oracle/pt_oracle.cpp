@@ -673,7 +673,16 @@ struct mt_stream {
 		else { first = next(); second = next(); }
 	}
 };
-struct trace_ctx { const scene_t* s; const render_cfg* cfg; uint64_t rays = 0; trav_stats* st = nullptr; mt_stream* mt = nullptr; };
+// What a replay of trace_worker went through (tests/test_worker_pin.py asserts that the fixtures reach every branch).
+struct worker_counts {
+	uint64_t opacity_pass = 0, catcher_lit = 0, catcher_black = 0, rr_ended = 0, rr_survived = 0, clamp_active = 0, shadow_rays = 0;
+	std::vector<uint64_t> first_hit;   // per surface: paths whose first vertex lies on it
+};
+struct trace_ctx {
+	const scene_t* s; const render_cfg* cfg; uint64_t rays = 0; trav_stats* st = nullptr; mt_stream* mt = nullptr;
+	// trace_worker only: the reference's per-translation-unit streams (intersection_worker.cpp / shading_worker.cpp) and the counters
+	mt_stream* mt_sun = nullptr; mt_stream* mt_shade = nullptr; worker_counts* wc = nullptr;
+};
 
 static v3 trace(trace_ctx& c, const path_key& key, uint32_t bounce, const ray& r, uint32_t pass) {
 	if (bounce == 0) return V(0, 0, 0);                      // fvec4::future = (0,0,0,1)
@@ -764,12 +773,17 @@ static v3 trace(trace_ctx& c, const path_key& key, uint32_t bounce, const ray& r
 	return direct_out + indirect_out + emissive;
 }
 
-// ---------------------------------------------------------------- the HOST worker's integrator ("parity unpinned")
+// ---------------------------------------------------------------- the HOST worker's integrator (pinned: ora_trace_worker_mt)
 // src/processors/worker/{worker,intersection_worker,shading_worker,accumulation_worker}.cpp run one camera sample as a
 // message passed between stage queues: INTERSECT (closest hit + sun sample, intersection_worker.cpp:10-47) ->
 // DIRECT_LIGHTING (shadow query, :49-67) -> SHADING (shading_worker.cpp:10-201) -> ... -> ACCUMULATE. With
 // num_workers = 1 the two merge stages (intersection_worker.cpp:69-147) forward their input unchanged, so a sample is
-// the loop below. HOST links the AWS SDK and cannot be built here: this restatement is checked against the text only.
+// the loop below. Pinned bit for bit against the compiled stage functions (oracle/host_harness.cpp, tests/test_worker_pin.py):
+// with c.mt_sun / c.mt_shade set, the draws come from the reference's own streams at the points where it calls core::rand() —
+// intersection_worker.cpp:26 (a pair, on every hit of a scene with a sun, pass-throughs included) and shading_worker.cpp:54
+// (only when opacity is not approximately 1), :110, :149 (a pair), :184 (only below bounce_count - 2).
+// Not a function of the input and so not replicated: with bounce_count = 0 the reference's uint8_t bounce wraps to 255 after the
+// first vertex; here (and in the product) such a render is black.
 // Differences from renderer::trace: emissive is added before the opacity test; throughput is clamped to [0,10], not
 // [0,incoming]; Russian roulette below bounce_count-2; a shadow catcher without a lit sun sample turns the sample black.
 static v3 trace_worker(trace_ctx& c, const path_key& key, ray r) {
@@ -790,27 +804,34 @@ static v3 trace_worker(trace_ctx& c, const path_key& key, ray r) {
 		float opacity = ms.opacity, roughness = ms.roughness, metallic = ms.metallic;
 		v3 emissive = ms.emissive * 10;
 		float ior = mt.ior;
-		f4 rnd = draws(key, depth, pass, BLOCK_SURFACE);     // x: opacity, y: lobe, z,w: BSDF sample
-		f4 sr = draws(key, depth, pass, BLOCK_SUN);          // x: azimuth, y: cone angle, z: Russian roulette
+		const bool mtw = c.mt_shade != nullptr;
+		f4 rnd = mtw ? f4{0, 0, 0, 0} : draws(key, depth, pass, BLOCK_SURFACE);   // x: opacity, y: lobe, z,w: BSDF sample
+		f4 sr = mtw ? f4{0, 0, 0, 0} : draws(key, depth, pass, BLOCK_SUN);        // x: azimuth, y: cone angle, z: Russian roulette
+		if (c.wc && bounce == B && pass == 0) c.wc->first_hit[res.surface]++;
 		v3 normal = shading_normal(res, ms.normal_ts);       // intersect_min_result's normal == result.get_normal()
 
 		// INTERSECT stage, intersection_worker.cpp:22-39: the sun sample of this vertex
 		bool have_direct = false, direct_hit = false;
 		v3 direct_incoming = V(0, 0, 0);
+		ray direct_ray = r;
 		if (c.s->has_sun) {
+			if (mtw) c.mt_sun->pair(sr.x, sr.y);               // :26: rand_cone_vec(rand(), cos(rand() * radius), ..)
 			v3 din = c.s->sun_basis * V(0, 0, 1);
 			din = rand_cone_vec(sr.x, std::cos(sr.y * c.s->sun_radius), din);
-			ray direct_ray = make_ray(res.pos + din * EPS, din);
+			direct_ray = make_ray(res.pos + din * EPS, din);
 			if (dot(normal, din) > 0) {
 				have_direct = true;
 				direct_incoming = direct_ray.d;                  // ray::get_dir(): normalised
-				// the DIRECT_LIGHTING stage (:58-64) runs for every such ray; the result is only read further down
+				// the DIRECT_LIGHTING stage (:58-64) traces direct_ray for every such vertex, before SHADING looks at the opacity;
+				// the query draws nothing, so it is made (and counted in c.rays) further down, where its result is first read
+				if (c.wc) c.wc->shadow_rays++;
 			}
 		}
 
 		color = color + scale * emissive;                    // shading_worker.cpp:52
 
-		if (!is_approx(opacity, 1) && rnd.x > opacity) {     // :54-63 — back to INTERSECT, bounce unchanged
+		if (!is_approx(opacity, 1) && (mtw ? c.mt_shade->next() : rnd.x) > opacity) {     // :54-63 — back to INTERSECT, bounce unchanged
+			if (c.wc) c.wc->opacity_pass++;
 			r = make_ray(res.pos + r.d * EPS, r.d);
 			pass++;
 			continue;
@@ -818,12 +839,15 @@ static v3 trace_worker(trace_ctx& c, const path_key& key, ray r) {
 		v3 outcoming = -r.d;
 		if (dot(normal, outcoming) <= 0) break;              // :68-72
 		if (have_direct) {
+			// cloud_ray::direct_light_ray as the INTERSECT stage stored it: the origin offset along the cone vector AS DRAWN, the
+			// direction normalised once (rebuilding the ray from its normalised direction moves both by an ulp now and then)
 			c.rays++;
-			direct_hit = scene_intersect(*c.s, make_ray(res.pos + direct_incoming * EPS, direct_incoming), c.st).hit;
+			direct_hit = scene_intersect(*c.s, direct_ray, c.st).hit;
 		}
 		const bool lit = have_direct && dot(normal, direct_incoming) > 0 && !direct_hit;   // :77-87, :112-118
 		if (mt.shadow_catcher && bounce == B) {              // :74-105
-			if (!lit) { color = V(0, 0, 0); break; }
+			if (!lit) { if (c.wc) c.wc->catcher_black++; color = V(0, 0, 0); break; }
+			if (c.wc) c.wc->catcher_lit++;
 			r = make_ray(res.pos + r.d * EPS, r.d);
 			pass++;
 			continue;
@@ -831,7 +855,7 @@ static v3 trace_worker(trace_ctx& c, const path_key& key, ray r) {
 		roughness = fmax2(roughness, 0.05F);
 		float specular_probability = fresnel(outcoming, reflect(-outcoming, normal), ior);
 		specular_probability = fmax2(specular_probability, metallic);
-		bool specular_sample = rnd.y < specular_probability;
+		bool specular_sample = (mtw ? c.mt_shade->next() : rnd.y) < specular_probability;   // :110
 		if (lit) {                                           // :119-143
 			float diffuse_pdf = pdf_diffuse(normal, direct_incoming);
 			v3 diffuse_brdf = diffuse_pdf * albedo;
@@ -852,6 +876,7 @@ static v3 trace_worker(trace_ctx& c, const path_key& key, ray r) {
 			              clampf(direct_out.z, 0, direct_in.z)};
 			color = color + scale * direct_out;
 		}
+		if (mtw) c.mt_shade->pair(rnd.z, rnd.w);             // :149: fvec2 rand_val(core::rand(), core::rand())
 		v3 indirect_incoming = specular_sample ? importance_specular(rnd.z, rnd.w, normal, outcoming, roughness)
 		                                       : importance_diffuse(rnd.z, rnd.w, normal);
 		if (!(dot(normal, indirect_incoming) > 0)) break;    // :154, :196-199
@@ -869,11 +894,13 @@ static v3 trace_worker(trace_ctx& c, const path_key& key, ray r) {
 		v3 brdf = vlerp(diffuse_brdf, specular_brdf, fr);
 		float pdf = lerp(diffuse_pdf, specular_pdf, specular_probability);
 		scale = scale * (brdf / fmax2(pdf, EPS));            // :173
+		if (c.wc && (!(scale.x >= 0 && scale.x <= 10.0f) || !(scale.y >= 0 && scale.y <= 10.0f) || !(scale.z >= 0 && scale.z <= 10.0f))) c.wc->clamp_active++;
 		scale = {clampf(scale.x, 0, 10.0f), clampf(scale.y, 0, 10.0f), clampf(scale.z, 0, 10.0f)};   // :175
 		r = make_ray(res.pos + indirect_incoming * EPS, indirect_incoming);
 		if ((int)bounce < (int)B - 2) {                      // :182-190 (uint8_t operands promote to int)
 			float p = fmax2(scale.x, fmax2(scale.y, scale.z));
-			if (sr.z > p) break;
+			if ((mtw ? c.mt_shade->next() : sr.z) > p) { if (c.wc) c.wc->rr_ended++; break; }   // :184
+			if (c.wc) c.wc->rr_survived++;
 			scale = scale / p;
 		}
 		bounce -= 1;
@@ -882,18 +909,28 @@ static v3 trace_worker(trace_ctx& c, const path_key& key, ray r) {
 	return color;
 }
 
+// The camera ray of pixel (x, y) at the sub-pixel offset (jx, jy): renderer.cpp:363-370, worker.cpp:131-135
+static ray primary_ray(const scene_t& s, uint32_t W, uint32_t H, uint32_t x, uint32_t y, float jx, float jy) {
+	float ndc_x = (((float)x + jx) / (float)W) * 2 - 1;
+	float ndc_y = (((float)y + jy) / (float)H) * 2 - 1;
+	ndc_y = -ndc_y;
+	float ratio = (float)W / (float)H;
+	return camera_ray(s, ndc_x, ndc_y, ratio);
+}
+// The offset of one camera sample on the counter-based stream; worker.cpp:125-126: the worker's first sample is not offset
+static f4 sample_jitter(const render_cfg& cfg, const path_key& key, uint32_t s) {
+	f4 j = draws(key, 0, 0, BLOCK_JITTER);
+	if (cfg.integrator == 1 && s == 0) j.x = j.y = 0;
+	return j;
+}
 // One camera sample: jitter -> NDC -> camera ray -> trace. renderer.cpp:359-371
 static v3 sample_pixel(trace_ctx& c, uint32_t x, uint32_t y, uint32_t s) {
 	const render_cfg& cfg = *c.cfg;
 	path_key key = {y * cfg.W + x, s, cfg.seed_lo, cfg.seed_hi};
-	f4 j = draws(key, 0, 0, BLOCK_JITTER);
-	if (cfg.integrator == 1 && s == 0) j.x = j.y = 0;       // worker.cpp:125-126: the first sample is not offset
-	float ndc_x = (((float)x + j.x) / (float)cfg.W) * 2 - 1;
-	float ndc_y = (((float)y + j.y) / (float)cfg.H) * 2 - 1;
-	ndc_y = -ndc_y;
-	float ratio = (float)cfg.W / (float)cfg.H;
-	if (cfg.integrator == 1) return trace_worker(c, key, camera_ray(*c.s, ndc_x, ndc_y, ratio));
-	return trace(c, key, cfg.bounces, camera_ray(*c.s, ndc_x, ndc_y, ratio), 0);
+	const f4 j = sample_jitter(cfg, key, s);
+	const ray r = primary_ray(*c.s, cfg.W, cfg.H, x, y, j.x, j.y);
+	if (cfg.integrator == 1) return trace_worker(c, key, r);
+	return trace(c, key, cfg.bounces, r, 0);
 }
 
 // tonemap_approx_aces (utils.hpp:29-36) + image::write (image.cpp:143-154)
@@ -1232,11 +1269,8 @@ void ora_primary_rays(void* p, const render_cfg* cfg, uint32_t sample, float* ou
 		for (uint32_t xx = 0; xx < cfg->w; xx++) {
 			uint32_t x = cfg->x0 + xx, y = cfg->y0 + yy;
 			path_key key = {y * cfg->W + x, sample, cfg->seed_lo, cfg->seed_hi};
-			f4 j = draws(key, 0, 0, BLOCK_JITTER);
-			if (cfg->integrator == 1 && sample == 0) j.x = j.y = 0;
-			float ndc_x = (((float)x + j.x) / (float)cfg->W) * 2 - 1;
-			float ndc_y = -((((float)y + j.y) / (float)cfg->H) * 2 - 1);
-			ray r = camera_ray(s, ndc_x, ndc_y, (float)cfg->W / (float)cfg->H);
+			const f4 j = sample_jitter(*cfg, key, sample);
+			ray r = primary_ray(s, cfg->W, cfg->H, x, y, j.x, j.y);
 			float v[6] = {r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z};
 			memcpy(out + 6 * ((size_t)yy * cfg->w + xx), v, sizeof v);
 		}
@@ -1305,6 +1339,61 @@ void ora_trace_mt(void* p, size_t n, const float* rays /*[n][6]*/, uint32_t boun
 		out[4 * i] = d.x; out[4 * i + 1] = d.y; out[4 * i + 2] = d.z; out[4 * i + 3] = 1.0f;
 	}
 	if (n_draws) *n_draws = mt.n_draws;
+}
+
+// The HOST worker's stage pipeline for n rays IN SEQUENCE, one ray at a time, on the reference's own streams — what
+// oracle/_ref/host_harness computes (`worker-trace`, `worker-frame`). seeds[2] = mt19937 seeds of the sun-cone stream
+// (intersection_worker.cpp) and of the shading stream (shading_worker.cpp); a stream the run never seeded is never drawn from here
+// either (n_draws[k] stays 0). args_rtl[2] = argument order of the pair at intersection_worker.cpp:26 and at shading_worker.cpp:149.
+// out[n][4] = colour + alpha (1 on every way to ACCUMULATE with transparent_background = false, shading_worker.cpp:36,43,91).
+// counts (optional) [7 + n_surf]: opacity pass-throughs, lit catcher pass-throughs, catcher samples turned black, paths ended by
+// Russian roulette, vertices that survived it, vertices at which the [0, 10] clamp changed the throughput, shadow rays; then per
+// surface the paths whose first vertex lies on it.
+void ora_trace_worker_mt(void* p, size_t n, const float* rays /*[n][6]*/, uint32_t bounces, const float* env3, const uint32_t* seeds,
+                         const int* args_rtl, float* out /*[n][4]*/, uint64_t* n_draws /*[2]*/, uint64_t* counts) {
+	const scene_t& s = *(scene_t*)p;
+	render_cfg cfg{};
+	cfg.bounces = bounces;
+	cfg.integrator = 1;
+	cfg.env[0] = env3[0]; cfg.env[1] = env3[1]; cfg.env[2] = env3[2];
+	mt_stream sun(seeds[0], args_rtl[0] != 0), shade(seeds[1], args_rtl[1] != 0);
+	worker_counts wc;
+	wc.first_hit.assign(s.surfaces.size(), 0);
+	trace_ctx c{&s, &cfg};
+	c.mt_sun = &sun; c.mt_shade = &shade; c.wc = &wc;
+	const path_key unused{0, 0, 0, 0};
+	for (size_t i = 0; i < n; i++) {
+		const float* r = rays + 6 * i;
+		const v3 d = trace_worker(c, unused, ray{V(r[0], r[1], r[2]), V(r[3], r[4], r[5])});   // direction as stored (ora_trace_mt)
+		out[4 * i] = d.x; out[4 * i + 1] = d.y; out[4 * i + 2] = d.z; out[4 * i + 3] = 1.0f;
+	}
+	if (n_draws) { n_draws[0] = sun.n_draws; n_draws[1] = shade.n_draws; }
+	if (counts) {
+		const uint64_t v[7] = {wc.opacity_pass, wc.catcher_lit, wc.catcher_black, wc.rr_ended, wc.rr_survived, wc.clamp_active, wc.shadow_rays};
+		memcpy(counts, v, sizeof v);
+		for (size_t k = 0; k < wc.first_hit.size(); k++) counts[7 + k] = wc.first_hit[k];
+	}
+}
+// worker::generate_rays' jitter stream (worker.cpp:117-136): offsets[X][Y][spp][2] in ITS order (x outer, y, sample); sample 0 is not
+// offset and draws nothing. args_rtl = argument order of fvec2(core::rand(), core::rand()) at worker.cpp:128.
+void ora_worker_jitter_mt(uint32_t X, uint32_t Y, uint32_t spp, uint32_t seed, int args_rtl, float* offsets) {
+	mt_stream mt(seed, args_rtl != 0);
+	for (uint32_t x = 0; x < X; x++)
+		for (uint32_t y = 0; y < Y; y++)
+			for (uint32_t k = 0; k < spp; k++) {
+				float* o = offsets + 2 * (((size_t)x * Y + y) * spp + k);
+				o[0] = o[1] = 0;
+				if (k != 0) mt.pair(o[0], o[1]);
+			}
+}
+// primary_ray — the function sample_pixel and ora_primary_rays go through — at GIVEN offsets: pix[n][2] = x, y; off[n][2] -> out[n][6]
+void ora_primary_rays_at(void* p, uint32_t W, uint32_t H, size_t n, const uint32_t* pix, const float* off, float* out) {
+	const scene_t& s = *(scene_t*)p;
+	for (size_t i = 0; i < n; i++) {
+		ray r = primary_ray(s, W, H, pix[2 * i], pix[2 * i + 1], off[2 * i], off[2 * i + 1]);
+		float v[6] = {r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z};
+		memcpy(out + 6 * i, v, sizeof v);
+	}
 }
 
 // Per-sample radiance (no averaging): out[h][w][spp][3]. Used to compare individual paths with the GPU.

@@ -34,6 +34,8 @@ def build(force=False):
         subprocess.check_call(["make", "-s", "-C", HERE, "oracle"])
     if os.path.isdir("/root/reference/path-tracer-core/path_tracer_lib"):
         subprocess.check_call(["make", "-s", "-j8", "-C", HERE, "ref"])
+        if os.path.isdir("/root/reference/path-tracer-core/src/processors/worker"):
+            subprocess.check_call(["make", "-s", "-j8", "-C", HERE, "ref-host"])
 
 
 def lib():
@@ -516,10 +518,61 @@ class OracleScene:
                            _p(out), C.byref(nd))
         return out, int(nd.value)
 
+    WORKER_COUNTS = ("opacity_pass", "catcher_lit", "catcher_black", "rr_ended", "rr_survived", "clamp_active", "shadow_rays")
+
+    def trace_worker_mt(self, rays, bounces, seeds, env=(1.0, 1.0, 1.0), args_rtl=(True, True)):
+        """The HOST worker's stage pipeline for every ray in sequence, one at a time, on the reference's own streams (what
+        oracle/_ref/host_harness `worker-trace` computes). seeds = (sun-cone stream, shading stream): std::mt19937 seeds; None for a
+        stream the reference never seeded (it must then not be drawn from). args_rtl = argument order of the two-draw calls at
+        intersection_worker.cpp:26 and shading_worker.cpp:149. -> (rgba [n,4] float32, draws per stream (2), counts: dict of
+        WORKER_COUNTS plus "first_hit" [n_surf])"""
+        rays = np.ascontiguousarray(rays, np.float32)
+        out = np.zeros((len(rays), 4), np.float32)
+        nd = np.zeros(2, np.uint64)
+        cnt = np.zeros(7 + self.n_surf, np.uint64)
+        e = np.asarray(env, np.float32)
+        sd = np.array([0 if v is None else int(v) for v in seeds], np.uint32)
+        rtl = np.array([1 if v else 0 for v in args_rtl], np.int32)
+        lib().ora_trace_worker_mt(self.h, C.c_size_t(len(rays)), _p(rays), C.c_uint32(bounces), _p(e), _p(sd), _p(rtl), _p(out), _p(nd), _p(cnt))
+        for k, v in enumerate(seeds):
+            if v is None and int(nd[k]) != 0:
+                raise RuntimeError(f"stream {k} was drawn from, but the reference never seeded it")
+        counts = {k: int(cnt[i]) for i, k in enumerate(self.WORKER_COUNTS)}
+        counts["first_hit"] = cnt[7:].astype(np.int64)
+        return out, (int(nd[0]), int(nd[1])), counts
+
+    def primary_rays_at(self, W, H, pixels, offsets):
+        """primary_rays' formula at given pixel coordinates [n,2] (x, y) and sub-pixel offsets [n,2] -> camera rays [n,6]"""
+        px = np.ascontiguousarray(pixels, np.uint32); off = np.ascontiguousarray(offsets, np.float32)
+        out = np.zeros((len(px), 6), np.float32)
+        lib().ora_primary_rays_at(self.h, C.c_uint32(W), C.c_uint32(H), C.c_size_t(len(px)), _p(px), _p(off), _p(out))
+        return out
+
+    def trace_worker_frame_mt(self, X, Y, spp, bounces, seeds, env=(1.0, 1.0, 1.0), args_rtl=(True, True, True)):
+        """worker::generate_rays + the stage pipeline (oracle/_ref/host_harness `worker-frame`): seeds and args_rtl = (jitter
+        stream, sun-cone stream, shading stream). Samples in generate_rays' order: x outer, y, sample.
+        -> (uuid [n] uint64, offsets [n,2], rays [n,6], rgba [n,4])"""
+        off = worker_jitter_mt(X, Y, spp, seeds[0], args_rtl[0]).reshape(-1, 2)
+        x, y, k = np.meshgrid(np.arange(X, dtype=np.uint64), np.arange(Y, dtype=np.uint64), np.arange(spp, dtype=np.uint64), indexing="ij")
+        uuid = ((x << np.uint64(40)) | (y << np.uint64(20)) | k).reshape(-1)          # worker.cpp:120
+        rays = self.primary_rays_at(X, Y, np.stack([x.reshape(-1), y.reshape(-1)], 1), off)
+        out, _, _ = self.trace_worker_mt(rays, bounces, seeds[1:], env, args_rtl[1:])
+        return uuid, off, rays, out
+
     def render_samples(self, cfg, threads=0):
         out = np.zeros((cfg.h, cfg.w, cfg.spp, 3), np.float32)
         lib().ora_render_samples(self.h, C.byref(cfg), _p(out), C.c_int(threads))
         return out
+
+
+def worker_jitter_mt(X, Y, spp, seed, args_rtl=True):
+    """The sub-pixel offsets worker::generate_rays draws (worker.cpp:124-129): [X, Y, spp, 2] in its order; sample 0 gets none and
+    draws nothing. seed None: the stream was never seeded (spp must be 1)."""
+    if seed is None and spp > 1:
+        raise RuntimeError("the jitter stream is drawn from when spp > 1")
+    out = np.zeros((X, Y, spp, 2), np.float32)
+    lib().ora_worker_jitter_mt(C.c_uint32(X), C.c_uint32(Y), C.c_uint32(spp), C.c_uint32(seed or 0), C.c_int(1 if args_rtl else 0), _p(out))
+    return out
 
 
 def tri_intersect(inp):

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import CORNELL, ROOT
+from conftest import CORNELL, GOLD, ROOT
 
 
 def test_library_exports_every_declared_symbol(ptx):
@@ -340,14 +340,19 @@ def _event(tmp_path, work, samples=5, bounces=3, X=48, Y=32):
 
 
 def test_worker_event_and_primitive_filter(ptx, ora, tmp_path):
-    """models::worker_info JSON + scene_info.work filter (host logic; the reference's HOST needs the AWS SDK and cannot be
-    built here, so this row is checked against the oracle's restatement of src/scene/load_gltf.cpp:93-99 — parity unpinned)."""
+    """models::worker_info JSON + scene_info.work filter (host logic), against what the reference's own HOST loader built under the
+    same filter: the `cornell_work` dump of tests/golden/worker_scene.npz (cloud::distributed_scene::load_scene, compiled unmodified
+    by oracle/host_harness.cpp; tests/test_worker_pin.py pins the oracle's load_gltf(work = ...) to the same dump)."""
     work = {"Cube.003": [0, 2], "Sphere": [0], "No.Such.Mesh": [0]}
     ev, root = _event(tmp_path, work)
     s, cfg, info = ptx.Scene.load_event(None, ev, root)
     assert (cfg.W, cfg.H, cfg.spp, cfg.bounces) == (48, 32, 5, 3) and tuple(cfg.env) == (1.0, 1.0, 1.0)
     assert info["worker_id"] == "1" and info["num_workers"] == 1 and info["n_work_meshes"] == 3 and info["scene_root"] == "scenes/cornell-box/"
-    a = ora.load_gltf(os.path.join(root, "scene.gltf"), work=work)
+    g = np.load(os.path.join(GOLD, "worker_scene.npz"))
+    a = ora.SceneArrays()
+    for k in ("model_xform", "model_surf", "surf_range", "vertices", "triangles", "materials", "camera"):
+        setattr(a, k, g["cornell_work_" + k])
+    assert g["cornell_work_sun"].size == 0
     assert a.model_surf.tolist() == [[0, 0], [0, 0], [0, 2], [2, 0], [2, 1]]   # unlisted meshes keep an empty model
     np.testing.assert_array_equal(s.array(ptx.ARR_MODEL_SURF), a.model_surf)
     np.testing.assert_array_equal(s.array(ptx.ARR_SURF_RANGE)[:, :4], a.surf_range)

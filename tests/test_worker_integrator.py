@@ -1,10 +1,11 @@
 """PTX_INTEGRATOR_WORKER: the estimator of the HOST worker's stage pipeline (src/processors/worker/intersection_worker.cpp,
 shading_worker.cpp, worker.cpp:114-149) for one worker.
 
-PARITY UNPINNED: the HOST program links the AWS SDK and cannot be built in this image, so the oracle's restatement
-(oracle/pt_oracle.cpp, trace_worker) is checked against the source text and against the properties below that follow from
-that text and from the pinned LIB estimator it shares every building block with — not against reference output.
-The GPU tests then compare the product with that oracle on the same Philox keys, as for the LIB estimator."""
+The oracle's restatement (oracle/pt_oracle.cpp, trace_worker) is PINNED in tests/test_worker_pin.py: it replays the random streams
+of the compiled, unmodified worker stages (oracle/host_harness.cpp) and returns their colours bit for bit. Not replicated, because not
+a function of the input: entity visit order on exact distance ties between models, thread timing, bounce_count = 0 (uint8_t wrap).
+Below: properties of that estimator that follow from the reference's text and from the LIB estimator it shares every building block
+with, and the GPU tests that compare the product with the oracle on the same Philox keys, as for the LIB estimator."""
 import numpy as np
 import pytest
 
