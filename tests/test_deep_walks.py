@@ -23,40 +23,21 @@ and 9 rays of the 262 144-ray batches at 1e3 and 1e6, while the queue walk, whic
 leaves a placeholder entry behind at such a step, which makes the rebuilt bound the stored one.
 """
 import functools
-import importlib
 import os
 
 import numpy as np
 import pytest
 
+from _checks import _check_records, _same_hits
+from _common import _bits, _proc
+from _routes import assert_route, clean_env, ctx, forced_routes, under_force_global  # noqa: F401  (clean_env and ctx are fixtures)
 from conftest import GOLD, kd_stream_packed, kd_stream_preorder, oracle_from_dict, product_from_dict
 from oracle import deep_walk as dw
-from test_unit_limits import ROUTE_VARS, _check_records, _routes, _same_hits
 
 N_BATCH = 262_144                  # > 8 waves per CU on 256 CUs
 W, H, SPP, B = 64, 36, 3, 5
 FIXTURE = os.path.join(GOLD, "deep_walk_vectors.npz")
 VARIANT = dict(surfaces=9, backdrop=48)      # 9 clusters and a 4608-triangle backdrop in one model: hybrid residency, queue pipeline by default
-
-
-def _proc():
-    return importlib.import_module("distributed-path-tracer_amd.procedural")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-@pytest.fixture
-def clean_env(monkeypatch):
-    for v in ROUTE_VARS:
-        monkeypatch.delenv(v, raising=False)
-    return monkeypatch
-
-
-@pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
 
 
 # ---------------------------------------------------------------------------- shared, computed once, never modified
@@ -251,21 +232,18 @@ def test_the_two_walkers_agree_where_no_bound_differs(ora):
 
 # ---------------------------------------------------------------------------- GPU
 def _route_scenes(ptx, ctx, mp, d, n_surf=1):
-    """(name, scene, expected pipeline) per route of test_unit_limits._routes, each asserted from the scene's residency; leaves
-    PTX_WAVEFRONT set for the route when the caller iterates (generator)."""
+    """(name, scene, expected pipeline) per forced route, each asserted from the scene's residency and from the pipeline a tiny render
+    reports; leaves PTX_WAVEFRONT set for the route when the caller iterates (generator). The scenes are the test's own: created under the
+    route's PTX_WAVEFRONT, one LDS scene for the test."""
     s_lds = None
-    for name, force_global, wf, mode, pipeline in _routes(n_surf):
-        mp.setenv("PTX_WAVEFRONT", wf)
-        if force_global:
-            mp.setenv("PTX_FORCE_GLOBAL", "1")
-            s = product_from_dict(ptx, ctx, d)
-            mp.delenv("PTX_FORCE_GLOBAL")
+    for route in forced_routes(n_surf):
+        mp.setenv("PTX_WAVEFRONT", route.env["PTX_WAVEFRONT"])
+        if route.force_global:
+            s = under_force_global(mp, True, lambda: product_from_dict(ptx, ctx, d))
         else:
             s = s_lds = s_lds or product_from_dict(ptx, ctx, d)
-        assert s.info()["lds_resident"] == mode, name
-        s.render(32, 18, 1, 2)                              # ptx_intersect_batch picks its pipeline by the rule the render reports
-        assert ctx.timing()["pipeline"] == pipeline, name
-        yield name, s, pipeline
+        assert_route(ctx, s, route, route.name)
+        yield route.name, s, route.pipeline
 
 
 @pytest.mark.gpu

@@ -1,8 +1,8 @@
 """ptx_denoise: the variance-guided a-trous filter on the guide buffers, against a float32 numpy restatement of its specification.
 
-The reference has no denoiser, so the specification in include/ptx.h is the contract and `restate` below restates it: vectorised over
-pixels, one loop over the taps in the stated order (dy outer, dx inner), every constant and intermediate a float32, np.where so that a
-skipped tap adds nothing (not even 0 * NaN), np.fmax for max (the other operand when one is NaN). Nothing on this path goes through
+The reference has no denoiser, so the specification in include/ptx.h is the contract and `restate` (tests/_denoise_restatement.py)
+restates it: vectorised over pixels, one loop over the taps in the stated order (dy outer, dx inner), every constant and intermediate
+a float32, np.where so that a skipped tap adds nothing (not even 0 * NaN), np.fmax for max (the other operand when one is NaN). Nothing on this path goes through
 libm, so the product is held to BITWISE equality with it, NaN positions included.
 """
 import ctypes as C
@@ -11,105 +11,11 @@ import importlib
 import numpy as np
 import pytest
 
+from _aov_restatement import restate as aov_restate
+from _common import _same
+from _denoise_restatement import QB, QH, QSEED, QW, _shift, f32, restate
+from _routes import ctx  # noqa: F401  (a fixture)
 from conftest import CORNELL, product_from_dict
-
-f32 = np.float32
-KERN = (f32(0.375), f32(0.25), f32(0.0625))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=what)
-
-
-def _shift(arr, dx, dy):
-    """q[y, x] = arr[y + dy, x + dx] where that lies inside the image (zeros elsewhere), and the mask of where it does."""
-    H, W = arr.shape[:2]
-    out, ok = np.zeros_like(arr), np.zeros((H, W), bool)
-    y0, y1, x0, x1 = max(0, -dy), min(H, H - dy), max(0, -dx), min(W, W - dx)
-    if y0 < y1 and x0 < x1:
-        out[y0:y1, x0:x1] = arr[y0 + dy:y1 + dy, x0 + dx:x1 + dx]
-        ok[y0:y1, x0:x1] = True
-    return out, ok
-
-
-def _bw(x):
-    t = np.fmax(f32(0), f32(1) - x)
-    return t * t
-
-
-def _lum(c):
-    return (f32(0.2126) * c[..., 0] + f32(0.7152) * c[..., 1]) + f32(0.0722) * c[..., 2]
-
-
-def _geo(gp, gq, sn2, sz2):
-    dn = gp[..., :3] - gq[..., :3]
-    xn = ((dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1]) + dn[..., 2] * dn[..., 2]) / sn2
-    zm = np.fmax(gp[..., 3], gq[..., 3])
-    rel = np.where(zm > 0, (gp[..., 3] - gq[..., 3]) / np.where(zm > 0, zm, f32(1)), f32(0))
-    xz = (rel * rel) / sz2
-    return _bw(xn) * _bw(xz)
-
-
-def restate(a, b, albedo_cov, normal_depth, spp_a, spp_b, iterations=5, sigma_l=4.0, sigma_n=0.5, sigma_z=0.1):
-    """The specification of ptx_denoise in float32 numpy -> out [H,W,4] (filtered means, alpha)."""
-    a, b, A, N = (np.asarray(x, f32) for x in (a, b, albedo_cov, normal_depth))
-    sl, sn, sz = f32(sigma_l), f32(sigma_n), f32(sigma_z)
-    sl2, sn2, sz2 = sl * sl, sn * sn, sz * sz
-    n, na, nb = f32(spp_a + spp_b), f32(spp_a), f32(spp_b)
-    with np.errstate(all="ignore"):
-        # 1. prepare
-        cov = A[..., 3]
-        alb = np.fmax((A[..., :3] + (n - cov)[..., None]) / n, f32(0.001))
-        col = ((a[..., :3] + b[..., :3]) / n) / alb
-        d = (_lum((a[..., :3] / na) / alb) - _lum((b[..., :3] / nb) / alb)) * f32(0.5)
-        v0 = d * d
-        alpha = (a[..., 3] + b[..., 3]) / n
-        hit = cov > 0
-        g = np.where(hit[..., None], N / np.where(hit, cov, f32(1))[..., None], f32(0)).astype(f32)
-        # 3. variance prefilter
-        s0, s1 = np.zeros_like(v0), np.zeros_like(v0)
-        for dy in (-1, 0, 1):
-            for dx in (-1, 0, 1):
-                gq, ok = _shift(g, dx, dy)
-                vq, _ = _shift(v0, dx, dy)
-                w = np.ones_like(v0) if dx == 0 and dy == 0 else _geo(g, gq, sn2, sz2)
-                s0 = np.where(ok, s0 + w, s0)
-                s1 = np.where(ok, s1 + w * vq, s1)
-        var = s1 / s0
-        # 4. iterations
-        for i in range(iterations):
-            step = 1 << i
-            L = _lum(col)
-            den = (sl2 * var) + f32(1e-8)
-            acc, ws, av = np.zeros_like(col), np.zeros_like(var), np.zeros_like(var)
-            for dy in range(-2, 3):
-                for dx in range(-2, 3):
-                    cq, ok = _shift(col, dx * step, dy * step)
-                    if not ok.any():
-                        continue
-                    h = KERN[abs(dx)] * KERN[abs(dy)]
-                    if dx == 0 and dy == 0:
-                        w = np.full_like(var, h)
-                    else:
-                        gq, _ = _shift(g, dx * step, dy * step)
-                        Lq, _ = _shift(L, dx * step, dy * step)
-                        dl = L - Lq
-                        w = (h * _geo(g, gq, sn2, sz2)) * _bw((dl * dl) / den)
-                    vq, _ = _shift(var, dx * step, dy * step)
-                    take = ok & (w > 0)
-                    acc = np.where(take[..., None], acc + w[..., None] * cq, acc)
-                    ws = np.where(take, ws + w, ws)
-                    av = np.where(take, av + (w * w) * vq, av)
-            col = acc / ws[..., None]
-            var = av / (ws * ws)
-        # 5. output
-        out = np.concatenate([col * alb, alpha[..., None]], -1)
-    assert out.dtype == f32
-    return out
 
 
 def _tm(x):
@@ -214,13 +120,9 @@ def test_isolated_nan_pixel_stays_alone():
     assert (out[~nan_at][:, :3] != mean[~nan_at][:, :3]).mean() > 0.9
 
 
-QW, QH, QB, QSEED = 96, 54, 8, 0x5EED
-
-
 def test_quality_of_the_specified_filter_on_cornell(ora, cornell_oracle):
-    """The oracle alone: Cornell 96 x 54, 8 bounces, halves of samples 0..7 and 8..15, guides from test_aov's restatement, against a
+    """The oracle alone: Cornell 96 x 54, 8 bounces, halves of samples 0..7 and 8..15, guides from tests/_aov_restatement.py, against a
     512-spp frame of another seed. Mean squared error after x / (1 + x), noisy / denoised: measured 3.97."""
-    from test_aov import restate as aov_restate
     o = cornell_oracle
     a = o.render(ora.make_cfg(QW, QH, 8, QB, seed=QSEED, sample0=0))[0] * f32(8)
     b = o.render(ora.make_cfg(QW, QH, 8, QB, seed=QSEED, sample0=8))[0] * f32(8)
@@ -256,11 +158,6 @@ def test_refusals_without_a_context(ptx):
 
 
 # ---------------------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
-
-
 SIGMAS = dict(sigma_l=3.0, sigma_n=0.7, sigma_z=0.25)
 
 

@@ -16,35 +16,17 @@ import io
 import numpy as np
 import pytest
 
+from _checks import _check_hits, _event, _scene_parity
+from _common import _bits, _proc
+from _routes import ctx  # noqa: F401  (a fixture)
 from conftest import CORNELL, ulp_diff
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
-
-
-@pytest.fixture(scope="module")
 def scene(ptx, ctx):
     return ptx.Scene.load_gltf(ctx, CORNELL)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _check_hits(hits, oracle_out, oracle_idx):
-    np.testing.assert_array_equal(hits["surface"], oracle_idx)
-    hit = oracle_idx >= 0
-    pos = np.stack([hits["px"], hits["py"], hits["pz"]], 1)
-    nrm = np.stack([hits["nx"], hits["ny"], hits["nz"]], 1)
-    uv = np.stack([hits["u"], hits["v"]], 1)
-    np.testing.assert_array_equal(_bits(pos[hit]), _bits(oracle_out[hit, 0:3]))
-    np.testing.assert_array_equal(_bits(uv[hit]), _bits(oracle_out[hit, 3:5]))
-    np.testing.assert_array_equal(_bits(nrm[hit]), _bits(oracle_out[hit, 11:14]))
-    assert (hits["distance"][~hit] == -1).all()
 
 
 def test_intersect_batch_matches_reference_vectors(scene, gold_vec):
@@ -400,40 +382,6 @@ def test_cpp_host_cli(cornell_oracle, ora, tmp_path):
 
 
 # ---------------------------------------------------------------------------- scenes beyond the Cornell asset
-def _proc():
-    import importlib
-    return importlib.import_module("distributed-path-tracer_amd.procedural")
-
-
-def _scene_parity(ptx, ctx, ora, d, W, H, spp, b, n_rays=60_000, seed=11):
-    from conftest import oracle_from_dict, product_from_dict
-    s = product_from_dict(ptx, ctx, d)
-    o = oracle_from_dict(ora, d)
-    cfg = ora.make_cfg(W, H, 1, b)
-    prim = o.primary_rays(cfg, 0).reshape(-1, 6)
-    out, idx = o.intersect(prim)
-    rng = np.random.default_rng(seed)
-    hit = idx >= 0
-    k = min(n_rays, int(hit.sum()))
-    sel = rng.choice(np.flatnonzero(hit), k, replace=True)
-    dd = rng.standard_normal((k, 3)).astype(np.float32)
-    dd /= np.linalg.norm(dd, axis=1, keepdims=True).astype(np.float32)
-    dd = np.where((dd * out[sel, 11:14]).sum(1, keepdims=True) < 0, -dd, dd).astype(np.float32)
-    sec = np.concatenate([out[sel, :3] + out[sel, 11:14] * np.float32(1e-4), dd], 1).astype(np.float32)
-    rays = np.concatenate([prim, sec])
-    out, idx = o.intersect(rays)
-    hits = s.intersect(rays[:, :3], rays[:, 3:])
-    _check_hits(hits, out, idx)
-    ref = o.render_samples(ora.make_cfg(W, H, spp, b), threads=0)
-    got = np.zeros_like(ref)
-    for kk in range(spp):
-        a, _ = s.render(W, H, 1, b, sample0=kk)
-        got[:, :, kk] = a[..., :3]
-    err = np.abs(got - ref).max(-1) / np.maximum(np.abs(ref).max(-1), 1e-3)
-    assert (err < 1e-3).mean() > 0.995, f"{(err < 1e-3).mean():.4%} of samples agree"
-    return s, o
-
-
 @pytest.mark.parametrize("level", [2, 3])          # level 2 fits one CU's LDS (LDS kernels), level 3 does not (global-memory kernels)
 @pytest.mark.parametrize("sun,alpha", [(True, True), (True, False), (False, True), (False, False)])
 def test_plaza_sun_and_alpha_variants(ptx, ctx, ora, sun, alpha, level):
@@ -569,7 +517,6 @@ def test_worker_event_render_and_cli(ptx, ctx, ora, tmp_path):
     import subprocess
     from PIL import Image
     from conftest import ROOT
-    from test_host_logic import _event
     work = {"Cube.003": [0, 1, 2], "Cube.004": [0], "Sphere": [0]}
     ev, root = _event(tmp_path, work, samples=6, bounces=4, X=96, Y=64)
     s, cfg, info = ptx.Scene.load_event(ctx, ev, root)

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from _checks import _event
 from conftest import CORNELL, GOLD, ROOT
 
 
@@ -326,19 +327,6 @@ def test_png_reader_against_pil(ptx, tmp_path):
 
 
 # ---------------------------------------------------------------------------- worker event front-end
-def _event(tmp_path, work, samples=5, bounces=3, X=48, Y=32):
-    import json, shutil
-    root = tmp_path / "scene-root"
-    root.mkdir()
-    shutil.copyfile(CORNELL, root / "scene.gltf")                       # the worker downloads <scene_root>scene.gltf (worker.cpp:108-112)
-    shutil.copyfile(os.path.join(os.path.dirname(CORNELL), "cornell.bin"), root / "cornell.bin")
-    ev = {"scene_info": {"work": work, "total_size": 0.05}, "scene_bucket": "distributed-path-tracer", "scene_root": "scenes/cornell-box/",
-          "worker_id": "1", "sqs_queue_arn": "", "sns_topic_arn": "", "num_workers": 1, "samples": samples, "bounces": bounces, "X": X, "Y": Y}
-    p = tmp_path / "event.json"
-    p.write_text(json.dumps(ev, indent=4))
-    return str(p), str(root)
-
-
 def test_worker_event_and_primitive_filter(ptx, ora, tmp_path):
     """models::worker_info JSON + scene_info.work filter (host logic), against what the reference's own HOST loader built under the
     same filter: the `cornell_work` dump of tests/golden/worker_scene.npz (cloud::distributed_scene::load_scene, compiled unmodified

@@ -21,28 +21,20 @@ cannot be produced through the C ABI anyway (T starts at 1 and is multiplied by 
 The non-GPU tests at the top check, by the oracle alone, that the chosen shapes really contain the cases named above, so that a later
 change of scene or seed cannot hollow the GPU tests out.
 """
-import importlib
 import os
 
 import numpy as np
 import pytest
 
+from _common import _bits, _proc
+from _routes import Scenes, clean_env, ctx, each_route, forced_routes, resident_by_creation  # noqa: F401  (clean_env and ctx are fixtures)
+from _transparent_restatement import _alpha_of, _oracle, _product_of
 from conftest import CORNELL, JACK, oracle_from_dict, product_from_dict, ulp_diff
-from test_transparent_background import _alpha_of, _oracle, _source
-from test_unit_limits import _routes, clean_env  # noqa: F401  (clean_env is a fixture)
 
 # Cornell, bounces = 1: a sample is `emissive * 10` of the first hit (no sun, no textures, closed box), a product of two stored
 # floats, and no libm function lies on the path. Measured on the parent commit (96 x 54, 4 samples): every one of the 20 736 samples
 # equals the oracle's bit for bit. So the test asserts exact equality there, and the project's bars at bounces 2 and 3.
 LAST_VERTEX_EXACT = True
-
-
-def _proc():
-    return importlib.import_module("distributed-path-tracer_amd.procedural")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _rel_err(got, ref):
@@ -135,11 +127,6 @@ def test_jack_shape_reaches_emitting_and_dark_first_hits(ora, jack_oracle, jack_
 
 # ---------------------------------------------------------------------------- GPU
 @pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
-
-
-@pytest.fixture(scope="module")
 def cornell(ptx, ctx):
     return ptx.Scene.load_gltf(ctx, CORNELL)
 
@@ -229,24 +216,14 @@ def test_queue_pipeline_bitwise_equals_fused_kernel_at_the_last_vertex(ptx, ctx,
         assert s1["rays"] == s0["rays"] and s1["samples"] == s0["samples"], kw
 
 
+PRODUCTS = Scenes(_product_of)
+
+
 def _each_route(ptx, ctx, mp, name):
-    """(route name, scene, expected pipeline) over test_unit_limits._routes, with the route's switches set. The scenes are this module's
-    own: they belong to this module's context, whose timing() the caller reads."""
-    def product(force_global):
-        if ("product", name, force_global) not in _cache:
-            kind, src = _source(name)
-            if force_global:
-                mp.setenv("PTX_FORCE_GLOBAL", "1")
-            _cache[("product", name, force_global)] = product_from_dict(ptx, ctx, src) if kind == "dict" else ptx.Scene.load_gltf(ctx, src)
-            if force_global:
-                mp.delenv("PTX_FORCE_GLOBAL")
-        return _cache[("product", name, force_global)]
-    for route, force_global, wf, _, pipeline in _routes(product(False).info()["n_surfaces"]):
-        s = product(force_global)
-        mp.setenv("PTX_WAVEFRONT", wf)
-        resident = s.info()["lds_resident"]
-        assert (resident == 0) if force_global else (resident in (1, 2)), (route, resident)
-        yield route, s, pipeline
+    """(route name, scene, expected pipeline) over the forced routes, with the route's switches set."""
+    n_surf = PRODUCTS.get(ptx, ctx, mp, name).info()["n_surfaces"]
+    for r, s in each_route(PRODUCTS, ptx, ctx, mp, name, forced_routes(n_surf), resident_by_creation):
+        yield r.name, s, r.pipeline
 
 
 @pytest.mark.gpu

@@ -12,12 +12,13 @@ in which order, so everything a kernel computes must be bit-identical between PT
      re-test loop runs in the new layout; Cornell frames, a ray batch and a hybrid plaza frame under both settings.
 Everything is bitwise.
 """
-import importlib
 import os
 
 import numpy as np
 import pytest
 
+from _common import _proc
+from _routes import ctx  # noqa: F401  (a fixture)
 from conftest import CORNELL, GOLD, product_from_dict
 
 F = np.float32
@@ -27,10 +28,6 @@ CAP = 4096                      # kLdsLeafOrderCap (flat_scene.hpp)
 LDS_BUDGET = 160 * 1024         # kLdsBudget (ptx_api.cpp)
 SHADE_BYTES = 176               # sizeof(ShadeRec)
 VARS = ("PTX_LDS_LEAF_ORDER", "PTX_LDS_BUDGET", "PTX_WAVEFRONT", "PTX_FORCE_GLOBAL", "PTX_SURFACE_UNITS", "PTX_NO_HYBRID", "PTX_NO_HOT_HITREC")
-
-
-def _proc():
-    return importlib.import_module("distributed-path-tracer_amd.procedural")
 
 
 @pytest.fixture
@@ -186,11 +183,6 @@ def test_plaza_level_3_plan_is_hybrid_under_both_settings(ptx, env):
 
 
 # ---------------------------------------------------------------------------- 2. the kernels
-@pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
-
-
 RCP_LO, RCP_HI = F(2.0 ** -125), F(2.0 ** 126)        # rcp_core's range (device_core.hpp)
 LEAF_SCALES = (-65, -64, -63, -40, 0, 40, 62, 63)
 N_LEAVES = {1: 160, 2: 80, 8: 20, 64: 6}

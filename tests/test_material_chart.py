@@ -17,29 +17,21 @@ What is asserted:
   2. The three routes give bitwise the same samples, whole frame, in every configuration of 1 and 3.
   3. Bounces 2 and 4, sun None / 0.004732 / 0.5, flat and facing charts, both integrators: the bars of test_gpu_parity PER PATCH — all
      samples finite and >= 0, >= 99.5 % within 1e-3 relative (floor 1e-3), >= 98 % within 1e-5.
-  4. ptx_render_transparent and ptx_render_aov on the chart, bitwise the restatements of test_transparent_background and test_aov.
+  4. ptx_render_transparent and ptx_render_aov on the chart, bitwise the restatements (tests/_transparent_restatement.py,
+     tests/_aov_restatement.py).
 """
-import importlib
-
 import numpy as np
 import pytest
 
+from _aov_restatement import restate as aov_restatement
+from _common import _bits, _proc
+from _routes import Scenes, clean_env, ctx, each_route  # noqa: F401  (clean_env and ctx are fixtures)
+from _transparent_restatement import _alpha_of, blend_restatement
 from conftest import oracle_from_dict, product_from_dict
-from test_aov import restate as aov_restatement
-from test_transparent_background import _alpha_of, blend_restatement
-from test_unit_limits import ROUTE_VARS, clean_env  # noqa: F401  (clean_env is a fixture)
 
 W, H, SPP = 192, 160, 4
 ENV = (0.5, 0.25, 1.0)
 RADIUS = 0.004732                    # the reference's sun
-
-
-def _proc():
-    return importlib.import_module("distributed-path-tracer_amd.procedural")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _variant(sun=None, blocker=False, facing=False, alpha=True):
@@ -230,36 +222,19 @@ def test_catchers_lit_and_shadowed_in_the_oracle(ora, ig):
 
 
 # ---------------------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
-
-
-_products = {}
-# (route, created under PTX_FORCE_GLOBAL, switches at the call, expected lds_resident, expected pipeline)
-ROUTES = [("lds fused", False, {}, 1, 0), ("queue", True, {}, 0, 1), ("global fused", True, {"PTX_WAVEFRONT": "0"}, 0, 0)]
+PRODUCTS = Scenes(lambda ptx, ctx, v: product_from_dict(ptx, ctx, _scene(v)))
 
 
 def _product(ptx, ctx, mp, v, force_global):
-    if (v, force_global) not in _products:
-        if force_global:
-            mp.setenv("PTX_FORCE_GLOBAL", "1")
-        _products[(v, force_global)] = product_from_dict(ptx, ctx, _scene(v))
-        if force_global:
-            mp.delenv("PTX_FORCE_GLOBAL")
-    return _products[(v, force_global)]
+    return PRODUCTS.get(ptx, ctx, mp, v, force_global)
 
 
 def _each_route(ptx, ctx, mp, v):
-    """(route, scene, expected pipeline) with the route's switches set and its residency asserted; the call sites assert the pipeline."""
-    for route, force_global, env, resident, pipeline in ROUTES:
-        s = _product(ptx, ctx, mp, v, force_global)
-        for k in ROUTE_VARS:
-            mp.delenv(k, raising=False)
-        for k, val in env.items():
-            mp.setenv(k, val)
-        assert s.info()["lds_resident"] == resident and s.info()["n_surfaces"] == len(_scene(v)["names"]), route
-        yield route, s, pipeline
+    """(route, scene, expected pipeline) over the default-choice routes, with the route's switches set and its residency asserted; the call
+    sites assert the pipeline."""
+    for r, s in each_route(PRODUCTS, ptx, ctx, mp, v):
+        assert s.info()["n_surfaces"] == len(_scene(v)["names"]), r.name
+        yield r.name, s, r.pipeline
 
 
 def _gpu_samples(ctx, s, ig, bounces, pipeline, what):
@@ -356,9 +331,9 @@ def test_throughput_and_multi_vertex_paths_per_patch(ptx, ctx, ora, clean_env, s
 @pytest.mark.gpu
 @pytest.mark.parametrize("blocker", [False, True], ids=["lit", "blocker"])
 def test_transparent_render_and_guide_buffers_on_the_chart(ptx, ctx, ora, clean_env, blocker):
-    """Check 5, a sharp sun, one bounce, LIB, default route: ptx_render_transparent is bitwise the blend restatement of
-    test_transparent_background fed with the oracle's samples and alphas (opacity 0, the opacities next to 1, the catchers lit without
-    the blocker and shadowed under it), ptx_render_aov bitwise the restatement of test_aov; interior pixels."""
+    """Check 5, a sharp sun, one bounce, LIB, default route: ptx_render_transparent is bitwise the blend restatement
+    (tests/_transparent_restatement.py) fed with the oracle's samples and alphas (opacity 0, the opacities next to 1, the catchers lit without
+    the blocker and shadowed under it), ptx_render_aov bitwise tests/_aov_restatement.py's; interior pixels."""
     v = _variant(0.0, blocker)
     d, o, inner = _scene(v), _oracle(ora, v), _interior_of(ora, v)
     one, zero = _ref(ora, v, 0, 1, env=(1.0, 1.0, 1.0)), _ref(ora, v, 0, 1, env=(0.0, 0.0, 0.0))

@@ -24,6 +24,8 @@ import pytest
 from conftest import ROOT
 
 import _dist_product_worker as wk
+from _common import _same
+from _denoise_restatement import QB, QH, QSEED, QW, restate
 
 f32 = np.float32
 WORKER = os.path.join(ROOT, "tests", "_dist_product_worker.py")
@@ -36,14 +38,6 @@ _broken = []     # why a job failed: nothing more is started on the GPU after th
 
 def _mg():
     return importlib.import_module("distributed-path-tracer_amd.multigpu")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=what)
 
 
 # ---------------------------------------------------------------------------- CPU
@@ -70,7 +64,6 @@ def test_chosen_frames_give_every_rank_tiles():
 @pytest.fixture(scope="module")
 def single(ptx):
     """Everything the jobs are compared with, rendered once by this process on Context(0)."""
-    from test_denoise import QB, QH, QSEED, QW, restate
     assert (wk.D_W, wk.D_H, wk.D_B, wk.D_SEED) == (QW, QH, QB, QSEED)
     ctx = ptx.Context(0)
     sc = wk.build_scenes(ptx, ctx)

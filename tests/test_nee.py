@@ -13,62 +13,16 @@ Share of Cornell 32 x 24 samples at 2 bounces whose vertex 1 is not on a listed 
 Measured on the MI355X: no comparable sample of the first-light-sample test differs (Cornell 3038, chart 7641); 100 % of the samples of
 Cornell, the chart with alpha and sun, and the jack-of-blades tile are within 1e-3 of the restatement (worst 4.95e-05, 5.6e-06, 3.7e-04).
 """
-import importlib
 import os
 
 import numpy as np
 import pytest
 
 import _nee_restatement as R
-from conftest import CORNELL, JACK, ROOT, oracle_from_dict, product_from_dict
-from test_unit_limits import ROUTE_VARS, clean_env  # noqa: F401  (clean_env is a fixture)
-
-SEED = 0x5EED
-
-
-def _proc():
-    return importlib.import_module("distributed-path-tracer_amd.procedural")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-# ---------------------------------------------------------------------------- scenes, built once
-_dicts, _oracles = {}, {}
-_MAKERS = {"chart": lambda p: p.chart_scene(facing=True, alpha=False), "chart_alpha": lambda p: p.chart_scene(facing=True, alpha=True),
-           "chart_sun": lambda p: p.chart_scene(facing=True, sun=0.5), "chart_alpha_sun": lambda p: p.chart_scene(facing=True, alpha=True, sun=0.004732),
-           "plaza": lambda p: p.plaza_scene(level=1, sun=True, alpha=True), "plaza_opaque": lambda p: p.plaza_scene(level=1, sun=True, alpha=False),
-           "atrium": lambda p: p.atrium_scene(0)}
-
-
-def _dict(name):
-    if name not in _dicts:
-        _dicts[name] = _MAKERS[name](_proc())
-    return _dicts[name]
-
-
-def _oracle(ora, name):
-    """(oracle scene, its arrays)"""
-    if name not in _oracles:
-        if name == "cornell":
-            a = ora.load_gltf(CORNELL)
-            _oracles[name] = (ora.OracleScene(a), a)
-        elif name == "jack":
-            a = ora.load_gltf(JACK)
-            _oracles[name] = (ora.OracleScene(a), a)
-        else:
-            o = oracle_from_dict(ora, _dict(name))
-            _oracles[name] = (o, o.a)
-    return _oracles[name]
-
-
-def _host_scene(ptx, name, ctx=None):
-    if name == "cornell":
-        return ptx.Scene.load_gltf(ctx, CORNELL)
-    if name == "jack":
-        return ptx.Scene.load_gltf(ctx, JACK)
-    return product_from_dict(ptx, ctx, _dict(name))
+from _common import _bits
+from _nee_common import K_BATCH, SEED, _batch_stat, _check_list, _dict, _err, _host_scene, _make, _oracle, _same_expectation
+from _routes import Scenes, clean_env, ctx, each_route, under_force_global  # noqa: F401  (clean_env and ctx are fixtures)
+from conftest import CORNELL, ROOT
 
 
 # ---------------------------------------------------------------------------- no GPU
@@ -82,16 +36,6 @@ def test_restatement_without_lights_is_the_pinned_oracle(ora, name, W, H, bounce
     # the product's order of additions gives the same radiance to rounding
     thr = R.render_samples(ora, o, a, W, H, 3, bounces, seed=SEED, lights=False)["rad"]
     assert np.abs(thr - ref).max() <= 1e-5 * max(1.0, float(np.abs(ref).max()))
-
-
-def _check_list(ll, n_surf):
-    n = len(ll["cdf"])
-    assert ll["tris"].shape == (n, 2) and ll["geom"].shape == (n, 4) and n > 0
-    assert (np.diff(ll["cdf"]) >= 0).all() and ll["cdf"][-1] == 1 and ll["cdf"][0] > 0
-    assert (ll["geom"][:, 3] > 0).all() and abs(float(ll["geom"][:, 3].astype(np.float64).sum()) / float(ll["area"]) - 1) < 1e-5
-    np.testing.assert_allclose(np.linalg.norm(ll["geom"][:, :3].astype(np.float64), axis=1), 1, atol=1e-6)
-    key = ll["tris"][:, 0].astype(np.int64) << 32 | ll["tris"][:, 1]
-    assert (np.diff(key) > 0).all() and ll["tris"][:, 0].max() < n_surf
 
 
 @pytest.mark.parametrize("name", ["cornell", "chart_alpha", "plaza_opaque", "plaza"])
@@ -131,21 +75,6 @@ def test_light_list_rules_and_arrays(ptx, ora, name):
         assert abs(float(ll["area"]) / (0.36 * local) - 1) < 1e-5
 
 
-def _batch_stat(frames):
-    """frames [K, h, w, 3] batch means per pixel -> (means [K, 5, 3]: the frame and its four quadrants)"""
-    K, h, w, _ = frames.shape
-    regions = [frames, frames[:, :h // 2, :w // 2], frames[:, :h // 2, w // 2:], frames[:, h // 2:, :w // 2], frames[:, h // 2:, w // 2:]]
-    return np.stack([r.reshape(K, -1, 3).mean(1, dtype=np.float64) for r in regions], 1)
-
-
-def _same_expectation(a, b):
-    """|m_a - m_b| <= 4 sqrt(s2_a / K + s2_b / K) on the frame mean of each channel, 5 sigma on the quadrants. -> (ok, worst z frame, worst z quadrant)"""
-    K = len(a)
-    z = np.abs(a.mean(0) - b.mean(0)) / np.sqrt(a.var(0, ddof=1) / K + b.var(0, ddof=1) / K)
-    return bool((z[0] <= 4).all() and (z[1:] <= 5).all()), float(z[0].max()), float(z[1:].max())
-
-
-K_BATCH = 16
 _lib_stats = {}
 
 
@@ -212,34 +141,16 @@ def test_refusals_without_a_device(ptx):
 
 
 # ---------------------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
-
-
-# (route, created under PTX_FORCE_GLOBAL, switches at the call, expected lds_resident, expected pipeline) — tests/test_material_chart.py's ROUTES
-ROUTES = [("lds fused", False, {}, 1, 0), ("queue", True, {}, 0, 1), ("global fused", True, {"PTX_WAVEFRONT": "0"}, 0, 0)]
-_products = {}
+PRODUCTS = Scenes(_make)
 
 
 def _product(ptx, ctx, mp, name, force_global=False):
-    if (name, force_global) not in _products:
-        if force_global:
-            mp.setenv("PTX_FORCE_GLOBAL", "1")
-        _products[(name, force_global)] = _host_scene(ptx, name, ctx)
-        mp.delenv("PTX_FORCE_GLOBAL", raising=False)
-    return _products[(name, force_global)]
+    return PRODUCTS.get(ptx, ctx, mp, name, force_global)
 
 
 def _each_route(ptx, ctx, mp, name):
-    for route, force_global, env, resident, pipeline in ROUTES:
-        s = _product(ptx, ctx, mp, name, force_global)
-        for k in ROUTE_VARS:
-            mp.delenv(k, raising=False)
-        for k, val in env.items():
-            mp.setenv(k, val)
-        assert s.info()["lds_resident"] == resident, route
-        yield route, s, pipeline
+    for r, s in each_route(PRODUCTS, ptx, ctx, mp, name):
+        yield r.name, s, r.pipeline
 
 
 @pytest.mark.gpu
@@ -303,10 +214,6 @@ def test_first_light_sample_bitwise(ptx, ctx, ora, clean_env, name, W, H):
     assert tot["rays"] >= tot["light_samples"] and abs(tot["rays"] - ref["rays"]) <= 0.005 * ref["rays"] + 1
 
 
-def _err(got, ref):
-    return np.abs(got - ref).max(-1) / np.maximum(np.abs(ref).max(-1), 1e-3)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,W,H,tile", [("cornell", 32, 32, None), ("chart_alpha_sun", 48, 40, None), ("jack", 192, 108, (80, 30, 32, 32))])
 def test_per_sample_radiance_against_the_restatement(ptx, ctx, ora, clean_env, name, W, H, tile):
@@ -360,9 +267,7 @@ def test_forced_pool_overflow_is_bitwise_the_unforced_frame(ptx, ctx, clean_env)
     W, H, spp, b = 400, 300, 4, 3
     s = _product(ptx, ctx, clean_env, "atrium", True)
     assert s.info()["n_surfaces"] == 24 and s.info()["lds_resident"] == 0
-    clean_env.setenv("PTX_FORCE_GLOBAL", "1")
-    fresh = _host_scene(ptx, "atrium", ctx)          # no pairs-per-ray measurement yet: the guess below decides the first slice
-    clean_env.delenv("PTX_FORCE_GLOBAL")
+    fresh = under_force_global(clean_env, True, lambda: _host_scene(ptx, "atrium", ctx))   # no pairs-per-ray measurement yet: the guess below decides the first slice
     clean_env.setenv("PTX_WF_PAIRS_M", "1")
     clean_env.setenv("PTX_WF_RATIO_GUESS", "0.25")
     forced, st = fresh.render_nee(W, H, spp, b, seed=SEED)

@@ -15,12 +15,10 @@ import numpy as np
 import pytest
 
 import _nee_restatement as R
+from _common import _bits
+from _nee_common import SEED, _err, _host_scene, _make, _oracle, _pair
+from _routes import DEFAULT_ROUTES, Scenes, clean_env, ctx, on_route, route_named  # noqa: F401  (clean_env and ctx are fixtures)
 from conftest import CORNELL, ROOT
-from test_nee import ROUTES, SEED, _bits, _err, _host_scene, _oracle
-from test_nee import ctx  # noqa: F401  (module-scoped fixture)
-from test_unit_limits import ROUTE_VARS, clean_env  # noqa: F401  (clean_env is a fixture)
-
-SAME_STATS = ("rays", "samples", "n_lights", "light_area", "light_samples", "light_visible")
 
 
 # ---------------------------------------------------------------------------- no GPU
@@ -41,43 +39,13 @@ def test_flag_values_and_refusals_without_a_device(ptx):
 
 
 # ---------------------------------------------------------------------------- GPU
-_products = {}   # this module's scenes: they live on this module's context (ptx_ctx_get_timing is the context's), so test_nee's are not shared
-
-
-def _product(ptx, ctx, mp, name, force_global=False):
-    if (name, force_global) not in _products:
-        if force_global:
-            mp.setenv("PTX_FORCE_GLOBAL", "1")
-        _products[(name, force_global)] = _host_scene(ptx, name, ctx)
-        mp.delenv("PTX_FORCE_GLOBAL", raising=False)
-    return _products[(name, force_global)]
+PRODUCTS = Scenes(_make)
 
 
 def _route(ptx, ctx, mp, name, route):
-    """the scene of `name` for one entry of test_nee.ROUTES, with the route's switches set"""
-    _, force_global, env, resident, pipeline = next(r for r in ROUTES if r[0] == route)
-    s = _product(ptx, ctx, mp, name, force_global)
-    for k in ROUTE_VARS:
-        mp.delenv(k, raising=False)
-    for k, val in env.items():
-        mp.setenv(k, val)
-    assert s.info()["lds_resident"] == resident, route
-    return s, pipeline
-
-
-def _pair(ptx, ctx, s, W, H, spp, bounces, fused=True, flags=0, **kw):
-    """the unflagged and the flagged call: asserts bitwise equal frames, equal stats and what ptx_ctx_get_timing tells about the route"""
-    want, st0 = s.render_nee(W, H, spp, bounces, seed=SEED, flags=flags, **kw)
-    assert ctx.timing()["fused_launches"] == 0
-    got, st = s.render_nee(W, H, spp, bounces, seed=SEED, flags=flags | ptx.NEE_FUSED, **kw)
-    tm = ctx.timing()
-    np.testing.assert_array_equal(_bits(got), _bits(want))
-    assert all(st[k] == st0[k] for k in SAME_STATS), (st, st0)
-    if fused:
-        assert tm["pipeline"] == 0 and tm["fused_launches"] == st["passes"] > 0 and tm["fused_ms"] == st["kernel_ms"]
-    else:
-        assert tm["pipeline"] == 1 and tm["fused_launches"] == 0 and st["passes"] == st0["passes"]
-    return got, st
+    """the scene of `name` for one of the default-choice routes, with the route's switches set"""
+    r = route_named(DEFAULT_ROUTES, route)
+    return on_route(PRODUCTS, ptx, ctx, mp, name, r), r.pipeline
 
 
 @pytest.mark.gpu
@@ -95,8 +63,6 @@ def test_flagged_frame_is_the_unflagged_frame_bitwise(ptx, ctx, clean_env, route
 @pytest.mark.gpu
 def test_hybrid_scene_bitwise(ptx, ctx, clean_env):
     """plaza_opaque with a budget one byte short of its resident geometry: some surface stays in global memory, the rest in LDS"""
-    for k in ROUTE_VARS:
-        clean_env.delenv(k, raising=False)
     full = int(_host_scene(ptx, "plaza_opaque").array(ptx.ARR_RES_PLAN)[0])
     clean_env.setenv("PTX_LDS_BUDGET", str(full - 1))
     s = _host_scene(ptx, "plaza_opaque", ctx)
@@ -173,7 +139,7 @@ def test_composition_bitwise(ptx, ctx, clean_env):
 @pytest.mark.gpu
 def test_per_sample_radiance_against_the_restatement(ptx, ctx, ora, clean_env):
     """test_nee.test_per_sample_radiance_against_the_restatement's comparison and bar, on the flagged call: all samples finite and >= 0,
-    >= 99.5 % within 1e-3 relative (floor 1e-3, test_nee._err)."""
+    >= 99.5 % within 1e-3 relative (floor 1e-3, _nee_common._err)."""
     W, H, spp, b = 32, 32, 8, 3
     o, a = _oracle(ora, "cornell")
     ref = R.render_samples(ora, o, a, W, H, spp, b, seed=SEED)

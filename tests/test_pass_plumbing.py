@@ -4,33 +4,25 @@ bytes whichever way a frame is asked for.
 Per entry point the baseline is the host-buffer, single-pass frame with stats requested — the configuration the per-feature tests pin
 against the oracle or the restatement (test_gpu_parity, test_transparent_background, test_aov, test_nee, test_adaptive). Asserted bitwise
 equal to it: torch device buffers with stats = NULL (the call returns without a sync), an uneven last pass, an odd tile against the same
-crop, two interleaved shards rendered into one buffer. Cornell runs on the fused kernel and through the queue pipeline (tests/test_nee.py's
-ROUTES); the alpha chart with a sun makes ptx_render_aov's pass-through rounds and ptx_render_nee's second read-back of a round run.
+crop, two interleaved shards rendered into one buffer. Cornell runs on the fused kernel and through the queue pipeline (two of
+tests/_routes.py's DEFAULT_ROUTES); the alpha chart with a sun makes ptx_render_aov's pass-through rounds and ptx_render_nee's second
+read-back of a round run.
 tests/test_nee.py::test_composition_bitwise_on_cornell and its siblings in test_aov / test_adaptive hold the wider sweeps per feature.
 """
 import numpy as np
 import pytest
 
-from test_nee import ROUTES, SEED, _host_scene
-from test_unit_limits import clean_env  # noqa: F401  (clean_env is a fixture)
+from _nee_common import SEED, _make
+from _routes import DEFAULT_ROUTES, Scenes, clean_env, ctx, use_route  # noqa: F401  (clean_env and ctx are fixtures)
 
 ENTRIES = ("render", "render_transparent", "render_aov", "render_nee")
 TILE = (5, 3, 17, 11)
-_scenes = {}
-
-
-@pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
+ROUTES = [r for r in DEFAULT_ROUTES if r.name in ("lds fused", "queue")]
+SCENES = Scenes(_make)
 
 
 def _scene(ptx, ctx, mp, name, force_global):
-    if (name, force_global) not in _scenes:
-        if force_global:
-            mp.setenv("PTX_FORCE_GLOBAL", "1")
-        _scenes[(name, force_global)] = _host_scene(ptx, name, ctx)
-        mp.delenv("PTX_FORCE_GLOBAL", raising=False)
-    return _scenes[(name, force_global)]
+    return SCENES.get(ptx, ctx, mp, name, force_global)
 
 
 def _frame(s, entry, W, H, spp, bounces, device=False, shards=(None,), min_spp=2, **kw):
@@ -84,13 +76,12 @@ def _check_entry(s, entry, W, H, spp, bounces, what):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("route", [r for r in ROUTES if r[0] in ("lds fused", "queue")], ids=lambda r: r[0])
+@pytest.mark.parametrize("route", ROUTES, ids=lambda r: r.name)
 @pytest.mark.parametrize("entry", ENTRIES)
 def test_cornell_frames_are_bitwise_the_baseline(ptx, ctx, clean_env, entry, route):
     name, force_global, env, resident, pipeline = route
     s = _scene(ptx, ctx, clean_env, "cornell", force_global)
-    for k, v in env.items():
-        clean_env.setenv(k, v)
+    use_route(clean_env, route)
     assert s.info()["lds_resident"] == resident
     s.render(8, 8, 1, 1)
     assert ctx.timing()["pipeline"] == pipeline, name
@@ -105,7 +96,7 @@ def test_alpha_chart_rounds_are_bitwise_the_baseline(ptx, ctx, clean_env, entry)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("route", [r for r in ROUTES if r[0] in ("lds fused", "queue")], ids=lambda r: r[0])
+@pytest.mark.parametrize("route", ROUTES, ids=lambda r: r.name)
 @pytest.mark.parametrize("min_spp,spp", [(2, 6), (4, 8)])
 def test_adaptive_subset_rounds(ptx, ctx, clean_env, route, min_spp, spp):
     """threshold = 0: every round after the first renders the active list (PixelSubset) into the halves staged once. min_spp = 4 gives

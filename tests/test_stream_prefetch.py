@@ -22,6 +22,8 @@ import importlib
 import numpy as np
 import pytest
 
+from _common import _proc
+from _routes import ctx, under_force_global  # noqa: F401  (ctx is a fixture)
 from conftest import CORNELL, oracle_from_dict, product_from_dict
 
 W, H, B = 96, 54, 8
@@ -46,20 +48,11 @@ PASSES = [
 PARTITION = [(0, 0, 89, 23), (89, 0, 7, 23), (0, 23, 96, 31)]
 
 
-def _proc():
-    return importlib.import_module("distributed-path-tracer_amd.procedural")
-
-
 @pytest.fixture
 def env(monkeypatch):
     for v in VARS:
         monkeypatch.delenv(v, raising=False)
     return monkeypatch
-
-
-@pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
 
 
 @pytest.fixture(scope="module")
@@ -159,9 +152,7 @@ def test_hybrid_and_global_plaza_agree_and_match_the_oracle(ptx, ctx, ora, env):
     spp = 4
     env.setenv("PTX_WAVEFRONT", "0")
     hyb = product_from_dict(ptx, ctx, d)
-    env.setenv("PTX_FORCE_GLOBAL", "1")
-    glb = product_from_dict(ptx, ctx, d)
-    env.delenv("PTX_FORCE_GLOBAL")
+    glb = under_force_global(env, True, lambda: product_from_dict(ptx, ctx, d))
     assert hyb.info()["lds_resident"] == 2 and glb.info()["lds_resident"] == 0 and hyb.info()["has_sun"] == 1
     frames = {}
     for name, s in (("hybrid", hyb), ("global", glb)):

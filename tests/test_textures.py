@@ -16,6 +16,9 @@ import os
 import numpy as np
 import pytest
 
+from _checks import _check_hits
+from _common import _bits
+from _routes import Route, clean_env, ctx, under_force_global  # noqa: F401  (clean_env and ctx are fixtures)
 from conftest import GOLD
 
 TEX_GLTF = os.path.join(GOLD, "textures", "textures.gltf")
@@ -28,10 +31,6 @@ SLOT_COLS = ((0, slice(0, 3), (0, 1, 2)), (1, slice(3, 6), (0, 1, 2)), (2, slice
 # a 1-ulp texel difference stays about 1 ulp at that scale, but lerp's a + (b - a) w cancels where the taps differ, so in ulps of the
 # output itself it can grow without a useful bound (the tests print both histograms)
 SRGB_FLOAT_ULP = 4
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _device_form(ref):
@@ -143,11 +142,6 @@ def test_texture_fixture_lookups_bit_exact_in_the_oracle(tex_oracle, tex_gold):
 
 # ---------------------------------------------------------------------------- GPU: ptx_material_eval_batch
 @pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
-
-
-@pytest.fixture(scope="module")
 def tex_scene(ptx, ctx):
     return ptx.Scene.load_gltf(ctx, TEX_GLTF)
 
@@ -251,29 +245,20 @@ def test_random_uv_sweep_against_the_oracle(ora, tex_scene, tex_oracle, tex_host
 
 
 # ---------------------------------------------------------------------------- GPU: renders of the fixture scene on every route
-ROUTES = [("lds fused", False, "0", 1, 0), ("global fused", True, "0", 0, 0), ("queue", True, "1", 0, 1)]
+# this file's table: every route with PTX_WAVEFRONT set (as the forced routes of tests/_routes.py), the queue route last
+ROUTES = [Route("lds fused", False, {"PTX_WAVEFRONT": "0"}, 1, 0), Route("global fused", True, {"PTX_WAVEFRONT": "0"}, 0, 0),
+          Route("queue", True, {"PTX_WAVEFRONT": "1"}, 0, 1)]
 W, H, SPP = 96, 54, 4
 FW, FH, FSPP = 160, 90, 8
 
 
-@pytest.fixture
-def clean_env(monkeypatch):
-    from test_unit_limits import ROUTE_VARS
-    for v in ROUTE_VARS:
-        monkeypatch.delenv(v, raising=False)
-    return monkeypatch
-
-
 def _route_scenes(ptx, ctx, mp, sun):
     out = []
-    for name, force_global, wf, mode, pipeline in ROUTES:
-        if force_global:
-            mp.setenv("PTX_FORCE_GLOBAL", "1")
-        s = ptx.Scene.load_gltf(ctx, TEX_GLTF, sun_light_index=0 if sun else 1)
-        mp.delenv("PTX_FORCE_GLOBAL", raising=False)
+    for r in ROUTES:
+        s = under_force_global(mp, r.force_global, lambda: ptx.Scene.load_gltf(ctx, TEX_GLTF, sun_light_index=0 if sun else 1))
         info = s.info()
-        assert info["lds_resident"] == mode and info["has_sun"] == int(sun) and info["n_textures"] == 12, name
-        out.append((name, s, wf, pipeline))
+        assert info["lds_resident"] == r.resident and info["has_sun"] == int(sun) and info["n_textures"] == 12, r.name
+        out.append((r.name, s, r.env["PTX_WAVEFRONT"], r.pipeline))
     return out
 
 
@@ -298,7 +283,6 @@ def test_fixture_scene_on_every_route(ptx, ctx, ora, tex_host, clean_env, sun):
         draws, the opacity test, the normal map's sign test and the emissive lookup — no libm call), except the samples whose
         camera ray hits the sRGB .hdr emissive quad;
       * 4 bounces: >= 99.5 % of samples within 1e-3, ray counts within 1e-4, the three routes bitwise equal to each other."""
-    from test_gpu_parity import _check_hits
     mp = clean_env
     o = ora.OracleScene(ora.load_gltf(TEX_GLTF, sun_light_index=0 if sun else 1))
     routes = _route_scenes(ptx, ctx, mp, sun)

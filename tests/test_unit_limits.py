@@ -16,32 +16,16 @@ asserted from the scene's residency and the pipeline the render reports, so a si
 Bars as in test_gpu_parity: hit records bit-exact, >= 99.5 % of samples within 1e-3 relative, ray counts within 2e-4, and
 the routes bitwise equal to each other.
 """
-import importlib
-
 import numpy as np
 import pytest
 
+from _checks import _check_records, _same_hits, _scene_parity
+from _common import _bits, _proc
+from _routes import clean_env, ctx, forced_routes, under_force_global  # noqa: F401  (clean_env and ctx are fixtures)
 from conftest import oracle_from_dict, product_from_dict
-from test_gpu_parity import _check_hits, _scene_parity
 
 W, H, SPP, B = 64, 36, 2, 5                 # per-sample radiance against the oracle
 FW, FH, FSPP = 128, 72, 4                   # frames for the ray counts and the route agreement
-ROUTE_VARS = ("PTX_WAVEFRONT", "PTX_FORCE_GLOBAL", "PTX_SURFACE_UNITS", "PTX_NO_HYBRID", "PTX_WF_PAIRS_M", "PTX_WF_RATIO_GUESS")
-
-
-def _proc():
-    return importlib.import_module("distributed-path-tracer_amd.procedural")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-@pytest.fixture
-def clean_env(monkeypatch):
-    for v in ROUTE_VARS:
-        monkeypatch.delenv(v, raising=False)
-    return monkeypatch
 
 
 # ---------------------------------------------------------------------------- the generator and the oracle (no GPU)
@@ -157,11 +141,6 @@ def test_host_scene_reports_surface_counts(ptx, n_surf):
 
 
 # ---------------------------------------------------------------------------- GPU: every route against the oracle
-@pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
-
-
 def _inside_rays(o, n, rng):
     """Rays whose origins lie inside every "overlap" surface box: camera rays, then random points of the inner cube with finite unit
     directions."""
@@ -186,38 +165,6 @@ def _hit_rays(o, ora, rng, n_bounce=20_000):
     return np.concatenate([prim, sec]).astype(np.float32)
 
 
-def _check_records(hits, o, rays, out, idx):
-    """Surface, position, uv and shading normal (_check_hits), then distance, triangle and barycentrics against the winning model's
-    model::intersect record (the first model wins ties, renderer.cpp:645-671)."""
-    _check_hits(hits, out, idx)
-    n_models = o.n_models
-    mo = np.zeros((len(rays), n_models, 4), np.float32)
-    mi = np.zeros((len(rays), n_models, 2), np.int32)
-    for m in range(n_models):
-        mo[:, m], mi[:, m] = o.model_intersect(m, rays)
-    hit = idx >= 0
-    win = np.argmax((mi[:, :, 0] == idx[:, None]) & (mo[:, :, 0] >= 0), axis=1)
-    r = np.arange(len(rays))
-    np.testing.assert_array_equal(_bits(hits["distance"][hit]), _bits(mo[r, win, 0][hit]))
-    np.testing.assert_array_equal(hits["triangle"][hit], mi[r, win, 1][hit])
-    bary = np.stack([hits["b0"], hits["b1"], hits["b2"]], 1)
-    np.testing.assert_array_equal(_bits(bary[hit]), _bits(mo[r, win, 1:4][hit]))
-
-
-def _same_hits(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        np.testing.assert_array_equal(np.asarray(a[k]).view(np.uint32), np.asarray(b[k]).view(np.uint32), err_msg=f"{what}: {k}")
-
-
-def _routes(n_surf):
-    """(name, PTX_FORCE_GLOBAL at creation, PTX_WAVEFRONT, expected lds_resident, expected pipeline)."""
-    r = [("lds fused", False, "0", 1, 0), ("global fused", True, "0", 0, 0)]
-    # the queue pipeline takes at most 64 surfaces: above that PTX_WAVEFRONT=1 must leave the fused kernel in charge
-    r.append(("queue", True, "1", 0, 1) if n_surf <= 64 else ("queue refused", True, "1", 0, 0))
-    return r
-
-
 SHAPES = [(1, 63, None), (1, 64, None), (1, 65, None), (64, 1, None), (65, 1, None), (2, 32, 1), (3, 21, None), (8, 8, 2), (5, 13, None)]
 
 
@@ -238,14 +185,9 @@ def test_unit_limits_every_route_against_oracle(ptx, ctx, ora, clean_env, n_mode
     oray = {ig: int(o.render(ora.make_cfg(FW, FH, FSPP, B, integrator=ig), threads=0)[1][0]) for ig in (0, 1)}
     units = ["0", "1"] if n_surf <= 64 else ["0"]        # surface units only where the 64-lane lists can hold every surface
     hits0, frames0, rays0 = None, {}, {}
-    for name, force_global, wf, mode, pipeline in _routes(n_surf):
-        mp.setenv("PTX_WAVEFRONT", wf)
-        if force_global:
-            mp.setenv("PTX_FORCE_GLOBAL", "1")
-            s = product_from_dict(ptx, ctx, d)
-            mp.delenv("PTX_FORCE_GLOBAL")
-        else:
-            s = s_lds
+    for name, force_global, env, mode, pipeline in forced_routes(n_surf):
+        mp.setenv("PTX_WAVEFRONT", env["PTX_WAVEFRONT"])       # the other switches stay as the route before left them
+        s = under_force_global(mp, True, lambda: product_from_dict(ptx, ctx, d)) if force_global else s_lds
         info = s.info()
         assert info["lds_resident"] == mode and info["n_surfaces"] == n_surf and info["n_models"] == n_models, name
         hits = s.intersect(rays[:, :3], rays[:, 3:])

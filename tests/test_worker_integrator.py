@@ -9,10 +9,8 @@ with, and the GPU tests that compare the product with the oracle on the same Phi
 import numpy as np
 import pytest
 
-
-def _proc():
-    import importlib
-    return importlib.import_module("distributed-path-tracer_amd.procedural")
+from _common import _proc
+from _routes import ctx  # noqa: F401  (a fixture)
 
 
 def _samples(o, ora, W, H, spp, b, integrator, **kw):
@@ -107,11 +105,6 @@ def test_lit_shadow_catcher_passes_through(ora):
 
 
 # ------------------------------------------------------------------------------------------------ product (GPU)
-@pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
-
-
 @pytest.fixture(scope="module")
 def scene(ptx, ctx):
     from conftest import CORNELL

@@ -17,6 +17,8 @@ import os
 import numpy as np
 import pytest
 
+from _common import _bits
+from _routes import Scenes, clean_env, ctx, each_route  # noqa: F401  (clean_env and ctx are fixtures)
 from conftest import CORNELL, GOLD, JACK, ROOT
 
 NEVER = 0xFFFFFFFF
@@ -28,10 +30,6 @@ SCENE_WORK = {"lit_047": (LIT, {"lit": [0, 4, 7]}), "lit_rest": (LIT, {"lit": [1
               "chart": (os.path.join(CHART, "chart.gltf"), None),
               "cornell_work": (CORNELL, {"Cube.003": [0, 2], "Sphere": [0], "No.Such.Mesh": [0]})}
 HOST_HARNESS = os.path.join(ROOT, "oracle", "_ref", "host_harness")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _seed(meta, i):
@@ -212,35 +210,18 @@ def test_regenerating_a_fixture_gives_the_committed_bytes(gold_wf, tmp_path):
 
 
 # ---------------------------------------------------------------------------- GPU: the kernels against compiled worker output
-@pytest.fixture(scope="module")
-def ctx(ptx):
-    return ptx.Context(0)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("tag", ["cornell_first", "chart_plain_first"])
-def test_gpu_first_sample_is_bitwise_the_compiled_worker(ptx, ctx, gold_wf, monkeypatch, tag):
+def test_gpu_first_sample_is_bitwise_the_compiled_worker(ptx, ctx, gold_wf, clean_env, tag):
     """ptx_render with integrator = 1, spp = 1, sample0 = 0, bounces = 1 against worker_frame.npz, ZERO tolerance, on every route (the
-    route table of test_material_chart): the product's own glTF loader, camera, un-jittered primary ray, closest hit, material
+    default-choice routes of tests/_routes.py): the product's own glTF loader, camera, un-jittered primary ray, closest hit, material
     lookup, emissive x 10 / environment / back face, straight against what the reference's worker computed."""
-    from test_material_chart import ROUTES
-    from test_unit_limits import ROUTE_VARS
     meta = gold_wf[tag + "_meta"]
     X, Y, spp, b = (int(v) for v in meta[4:8])
     ref = gold_wf[tag + "_out"].reshape(X, Y, 4).transpose(1, 0, 2)
-    scenes = {}
-    for route, force_global, env, resident, pipeline in ROUTES:
-        for k in ROUTE_VARS:
-            monkeypatch.delenv(k, raising=False)
-        if force_global not in scenes:
-            if force_global:
-                monkeypatch.setenv("PTX_FORCE_GLOBAL", "1")
-            scenes[force_global] = ptx.Scene.load_gltf(ctx, FRAME_SCENES[tag])
-            monkeypatch.delenv("PTX_FORCE_GLOBAL", raising=False)
-        s = scenes[force_global]
-        for k, val in env.items():
-            monkeypatch.setenv(k, val)
-        assert s.info()["lds_resident"] == resident, route
+    scenes = Scenes(lambda ptx, ctx, tag: ptx.Scene.load_gltf(ctx, FRAME_SCENES[tag]))      # this test's own
+    for r, s in each_route(scenes, ptx, ctx, clean_env, tag):
+        route, pipeline = r.name, r.pipeline
         a, _ = s.render(X, Y, spp, b, env=(1.0, 1.0, 1.0), sample0=0, integrator=1)
         assert ctx.timing()["pipeline"] == pipeline, route
         np.testing.assert_array_equal(_bits(a), _bits(ref), err_msg=f"{tag} / {route}")
