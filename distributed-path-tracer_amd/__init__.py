@@ -92,6 +92,11 @@ class DenoiseStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("iterations", C.c_uint32), ("workspace_bytes", C.c_uint64)]
 
 
+class DenoiseCountsCfg(C.Structure):
+    _fields_ = [("W", C.c_uint32), ("H", C.c_uint32), ("guide_spp", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float)]
+
+
 class AdaptiveCfg(C.Structure):
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("threshold", C.c_float)]
 
@@ -107,6 +112,10 @@ class NeeCfg(C.Structure):
 class NeeStats(C.Structure):
     _fields_ = [("render", RenderStats), ("n_lights", C.c_uint32), ("light_area", C.c_float), ("light_samples", C.c_uint64),
                 ("light_visible", C.c_uint64)]
+
+
+class AdaptiveNeeStats(C.Structure):
+    _fields_ = [("nee", NeeStats), ("rounds", C.c_uint32), ("active_last", C.c_uint32), ("select_ms", C.c_double)]
 
 
 NEE_NO_LIGHT_SAMPLES = 1   # ptx_nee_cfg.flags
@@ -200,6 +209,8 @@ def lib():
         L.ptx_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p, C.POINTER(DenoiseStats)]
         L.ptx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AdaptiveCfg), C.c_void_p, C.c_void_p, C.POINTER(AdaptiveStats)]
         L.ptx_render_nee.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(NeeCfg), C.c_void_p, C.POINTER(NeeStats)]
+        L.ptx_render_adaptive_nee.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AdaptiveCfg), C.POINTER(NeeCfg), C.c_void_p, C.c_void_p, C.POINTER(AdaptiveNeeStats)]
+        L.ptx_denoise_counts.argtypes = [C.c_void_p, C.POINTER(DenoiseCountsCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p, C.POINTER(DenoiseStats)]
         L.ptx_adaptive_select.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.ptx_accum_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_intersect_batch.argtypes = [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(Hits)]
@@ -326,6 +337,22 @@ class Context:
         guides = AovBuffers(_ptr(albedo_cov), _ptr(normal_depth))
         st = DenoiseStats()
         _check(lib().ptx_denoise(self.h, C.byref(cfg), _ptr(a), _ptr(b), C.byref(guides), _ptr(out), C.byref(st) if want_stats else None))
+        return out, (dict(kernel_ms=st.kernel_ms, iterations=st.iterations, workspace_bytes=st.workspace_bytes) if want_stats else None)
+
+    def denoise_counts(self, a, b, albedo_cov, normal_depth, guide_spp, iterations=0, sigma_l=0, sigma_n=0, sigma_z=0, out=None, want_stats=True):
+        """ptx_denoise_counts: denoise() for half-buffers whose alpha channel is the per-pixel sample count (Scene.render_adaptive,
+        Scene.render_adaptive_nee). albedo_cov, normal_depth: the Scene.render_aov SUMS over guide_spp samples of every pixel — for an adaptive
+        frame the first min_spp samples. Everything else as in denoise(). Returns (out, stats dict or None)."""
+        bufs = [a, b, albedo_cov, normal_depth] + ([out] if out is not None else [])
+        shape = tuple(a.shape)
+        if len(shape) != 3 or shape[2] != 4 or any(tuple(x.shape) != shape for x in bufs):
+            raise ValueError(f"denoise_counts: every buffer must be [H, W, 4] of one size, got {[tuple(x.shape) for x in bufs]}")
+        if out is None:
+            out = np.empty(shape, np.float32) if isinstance(a, np.ndarray) else a.new_empty(shape)   # no fill kernel on another stream
+        cfg = DenoiseCountsCfg(shape[1], shape[0], guide_spp, iterations, sigma_l, sigma_n, sigma_z)
+        guides = AovBuffers(_ptr(albedo_cov), _ptr(normal_depth))
+        st = DenoiseStats()
+        _check(lib().ptx_denoise_counts(self.h, C.byref(cfg), _ptr(a), _ptr(b), C.byref(guides), _ptr(out), C.byref(st) if want_stats else None))
         return out, (dict(kernel_ms=st.kernel_ms, iterations=st.iterations, workspace_bytes=st.workspace_bytes) if want_stats else None)
 
     def adaptive_select(self, a, b, threshold, done=None, want_list=True):
@@ -549,6 +576,25 @@ class Scene:
                      light_area=st.light_area, light_samples=st.light_samples, light_visible=st.light_visible) if want_stats else None
         return accum, stats
 
+    def render_adaptive_nee(self, W, H, spp, bounces, min_spp=8, step_spp=0, threshold=0.1, a=None, b=None, env=(1.0, 1.0, 1.0), seed=0x5EED, tile=None,
+                            sample0=0, spp_per_pass=0, want_stats=True, integrator=INTEGRATOR_LIB, shard=None, flags=0):
+        """ptx_render_adaptive_nee: render_adaptive()'s loop on render_nee()'s estimator with `flags`, one sequence of passes per round resolved
+        into both halves. A pixel with n samples holds, bit for bit, what render_nee() calls of the same half ranges leave in a and b. Filter
+        the result with Context.denoise_counts. Returns (a, b, stats dict or None)."""
+        x0, y0, w, h = tile if tile else (0, 0, W, H)
+        if a is None and b is None:
+            a, b = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+        cfg = RenderCfg(W, H, spp, bounces, (C.c_float * 3)(*env), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                        x0, y0, w, h, sample0, spp_per_pass, integrator, *((tuple(shard) + (0,))[:3] if shard else (0, 0, 0)))
+        acfg, ncfg = AdaptiveCfg(min_spp, step_spp, threshold), NeeCfg(flags)
+        st = AdaptiveNeeStats()
+        _check(lib().ptx_render_adaptive_nee(self.h, C.byref(cfg), C.byref(acfg), C.byref(ncfg), _ptr(a), _ptr(b), C.byref(st) if want_stats else None))
+        r = st.nee.render
+        stats = dict(rays=r.rays, samples=r.samples, passes=r.passes, kernel_ms=r.kernel_ms, n_lights=st.nee.n_lights, light_area=st.nee.light_area,
+                     light_samples=st.nee.light_samples, light_visible=st.nee.light_visible, rounds=st.rounds, active_last=st.active_last,
+                     select_ms=st.select_ms) if want_stats else None
+        return a, b, stats
+
     def set_environment(self, png_path, srgb=True):
         """renderer::environment = image_texture::load(png_path, srgb): the miss colour becomes map(direction) * environment_factor.
         None removes the map."""
@@ -691,9 +737,17 @@ class Renderer:
         out, self.last_denoise_stats = self._ctx.denoise(a, b, alb, nd, n // 2, n - n // 2, iterations, sigma_l, sigma_n, sigma_z, out=a)
         return out
 
-    def render_adaptive(self, threshold=0.1, min_spp=8, step_spp=0):
+    def _denoise_counts(self, a, b, min_spp):
+        """The adaptive halves through Context.denoise_counts, with the guides of the first min_spp samples (every pixel has them)."""
+        W, H = self.resolution
+        alb, nd, _ = self._scene.render_aov(W, H, min_spp, seed=self.seed, want_stats=False)
+        out, self.last_denoise_stats = self._ctx.denoise_counts(a, b, alb, nd, min_spp, out=a)
+        return out
+
+    def render_adaptive(self, threshold=0.1, min_spp=8, step_spp=0, denoise=False):
         """The frame with noise-driven per-pixel sample counts (Scene.render_adaptive, sample_count = the cap), as MEANS [H,W,4] (write them
-        with tonemap_encode(..., spp=1)); the alpha channel is 1. `last_adaptive_stats` holds the stats; samples / (W * H) is the mean count."""
+        with tonemap_encode(..., spp=1)); the alpha channel is 1. `last_adaptive_stats` holds the stats; samples / (W * H) is the mean count.
+        denoise: the frame through the filter (Context.denoise_counts, guides of the first min_spp samples); `last_denoise_stats` holds its stats."""
         if self._scene is None:
             raise PtxError(ERR_INVALID, "render_adaptive() before load_gltf()")
         if self.transparent_background:
@@ -704,7 +758,22 @@ class Renderer:
             self._env_set = self.environment
         a, b, self.last_adaptive_stats = self._scene.render_adaptive(W, H, self.sample_count, self.bounce_count, min_spp, step_spp, threshold,
                                                                      env=self.environment_factor, seed=self.seed)
-        return self._ctx.accum_mean(a, b, out=a)
+        return self._denoise_counts(a, b, min_spp) if denoise else self._ctx.accum_mean(a, b, out=a)
+
+    def render_adaptive_nee(self, flags=0, threshold=0.1, min_spp=8, step_spp=0, denoise=False):
+        """render_adaptive() on render_nee()'s estimator (Scene.render_adaptive_nee; flags: ptx_nee_cfg.flags): the MEANS [H,W,4], through the
+        filter with denoise. `last_adaptive_stats` holds the stats, the light-sampling ones included."""
+        if self._scene is None:
+            raise PtxError(ERR_INVALID, "render_adaptive_nee() before load_gltf()")
+        if self.transparent_background:
+            raise PtxError(ERR_UNSUPPORTED, "render_adaptive_nee: the decision takes radiance sums, which transparent_background does not produce")
+        W, H = self.resolution
+        if self.environment != getattr(self, "_env_set", None):
+            self._scene.set_environment(self.environment)
+            self._env_set = self.environment
+        a, b, self.last_adaptive_stats = self._scene.render_adaptive_nee(W, H, self.sample_count, self.bounce_count, min_spp, step_spp, threshold,
+                                                                         env=self.environment_factor, seed=self.seed, flags=flags)
+        return self._denoise_counts(a, b, min_spp) if denoise else self._ctx.accum_mean(a, b, out=a)
 
     def render_nee(self, flags=0):
         """Radiance SUMS [H,W,4] of the frame with next-event estimation towards the scene's emissive triangles (Scene.render_nee):

@@ -1,4 +1,4 @@
-// The batch entry points of the C ABI: ptx_denoise, the adaptive decision, the mean of two half-frames, the kernels' unit-test batches
+// The batch entry points of the C ABI: ptx_denoise and ptx_denoise_counts, the adaptive decision, the mean of two half-frames, the kernels' unit-test batches
 // (PBR, leaf intersection, exact math, camera rays, materials), the framebuffer reduction, tone mapping and PNG encoding.
 #include <dlfcn.h>
 #include <zlib.h>
@@ -15,21 +15,31 @@ uint32_t denoise_tiled_steps() {
 	return e && *e ? (uint32_t)strtoul(e, nullptr, 0) : kDenoiseTiledSteps;
 }
 
-}  // namespace
+// ptx_denoise and ptx_denoise_counts: the same refusals, workspace and kernels but for step 1 of the filter. counts = false: `spp_a` and `spp_b`
+// are the halves' sample counts (k_dn_prepare); counts = true: the halves carry per-pixel counts in .w and `spp_a` is guide_spp (k_dn_prepare_counts).
+struct DenoiseCall {
+	const char* who;
+	uint32_t W, H, iterations;
+	float sigma_l, sigma_n, sigma_z;
+	bool counts;
+	uint32_t spp_a, spp_b;
+};
 
-int ptx_denoise(ptx_ctx* c, const ptx_denoise_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, float* out_rgba, ptx_denoise_stats* stats) {
+int denoise_frame(ptx_ctx* c, const DenoiseCall& D, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, float* out_rgba, ptx_denoise_stats* stats) {
+	const std::string who = D.who;
 	// every refusal below is decided before any device work
-	if (!c || !cfg || !accum_a || !accum_b || !guides || !out_rgba) return set_err(PTX_ERR_INVALID, "ptx_denoise: NULL argument");
-	if (!guides->albedo_cov || !guides->normal_depth) return set_err(PTX_ERR_INVALID, "ptx_denoise: both guide buffers are required");
-	if (!cfg->W || !cfg->H || cfg->W > 16384 || cfg->H > 16384) return set_err(PTX_ERR_INVALID, "ptx_denoise: W and H must be in 1 .. 16384");
-	if (!cfg->spp_a || !cfg->spp_b) return set_err(PTX_ERR_INVALID, "ptx_denoise: spp_a and spp_b must be > 0 (the noise estimate needs two half-frames)");
-	if (cfg->iterations > 8) return set_err(PTX_ERR_INVALID, "ptx_denoise: at most 8 iterations");
-	if (!(cfg->sigma_l >= 0.0f) || !(cfg->sigma_n >= 0.0f) || !(cfg->sigma_z >= 0.0f)) return set_err(PTX_ERR_INVALID, "ptx_denoise: a sigma is negative or NaN");
+	if (!c || !accum_a || !accum_b || !guides || !out_rgba) return set_err(PTX_ERR_INVALID, who + ": NULL argument");
+	if (!guides->albedo_cov || !guides->normal_depth) return set_err(PTX_ERR_INVALID, who + ": both guide buffers are required");
+	if (!D.W || !D.H || D.W > 16384 || D.H > 16384) return set_err(PTX_ERR_INVALID, who + ": W and H must be in 1 .. 16384");
+	if (D.counts && !D.spp_a) return set_err(PTX_ERR_INVALID, who + ": guide_spp must be > 0 (the samples of every pixel the guides hold)");
+	if (!D.counts && (!D.spp_a || !D.spp_b)) return set_err(PTX_ERR_INVALID, who + ": spp_a and spp_b must be > 0 (the noise estimate needs two half-frames)");
+	if (D.iterations > 8) return set_err(PTX_ERR_INVALID, who + ": at most 8 iterations");
+	if (!(D.sigma_l >= 0.0f) || !(D.sigma_n >= 0.0f) || !(D.sigma_z >= 0.0f)) return set_err(PTX_ERR_INVALID, who + ": a sigma is negative or NaN");
 	const bool dev = is_device_ptr(accum_a);
 	if (is_device_ptr(accum_b) != dev || is_device_ptr(guides->albedo_cov) != dev || is_device_ptr(guides->normal_depth) != dev || is_device_ptr(out_rgba) != dev)
-		return set_err(PTX_ERR_INVALID, "ptx_denoise: the five buffers must all be device or all be host memory");
-	const uint32_t W = cfg->W, H = cfg->H, iterations = cfg->iterations ? cfg->iterations : 5u;
-	const float sigma_l = cfg->sigma_l != 0.0f ? cfg->sigma_l : 4.0f, sigma_n = cfg->sigma_n != 0.0f ? cfg->sigma_n : 0.5f, sigma_z = cfg->sigma_z != 0.0f ? cfg->sigma_z : 0.1f;
+		return set_err(PTX_ERR_INVALID, who + ": the five buffers must all be device or all be host memory");
+	const uint32_t W = D.W, H = D.H, iterations = D.iterations ? D.iterations : 5u;
+	const float sigma_l = D.sigma_l != 0.0f ? D.sigma_l : 4.0f, sigma_n = D.sigma_n != 0.0f ? D.sigma_n : 0.5f, sigma_z = D.sigma_z != 0.0f ? D.sigma_z : 0.1f;
 	std::lock_guard<std::mutex> lk(c->mu);
 	HIP_TRY(hipSetDevice(c->device));
 	if (stats) *stats = ptx_denoise_stats{};
@@ -50,7 +60,8 @@ int ptx_denoise(ptx_ctx* c, const ptx_denoise_cfg* cfg, const float* accum_a, co
 		if (const int rc = PassFrame::ensure_events(c, 1); rc != PTX_OK) return rc;
 	const uint32_t tiled = denoise_tiled_steps();
 	if (stats) HIP_TRY(hipEventRecord(c->events[0], c->stream));
-	HIP_TRY(launch_denoise_prepare(in[0].as<float4>(), in[1].as<float4>(), in[2].as<float4>(), in[3].as<float4>(), cfg->spp_a, cfg->spp_b, n, state[0], guide, remod, c->stream));
+	if (D.counts) HIP_TRY(launch_denoise_prepare_counts(in[0].as<float4>(), in[1].as<float4>(), in[2].as<float4>(), in[3].as<float4>(), D.spp_a, n, state[0], guide, remod, c->stream));
+	else HIP_TRY(launch_denoise_prepare(in[0].as<float4>(), in[1].as<float4>(), in[2].as<float4>(), in[3].as<float4>(), D.spp_a, D.spp_b, n, state[0], guide, remod, c->stream));
 	HIP_TRY(launch_denoise_prefilter(state[0], guide, W, H, sigma_n, sigma_z, state[1], c->stream));
 	for (uint32_t i = 0; i < iterations; i++) {
 		const bool last = i + 1 == iterations;
@@ -66,6 +77,21 @@ int ptx_denoise(ptx_ctx* c, const ptx_denoise_cfg* cfg, const float* accum_a, co
 		stats->workspace_bytes = ws_bytes;
 	}
 	return PTX_OK;
+}
+
+}  // namespace
+
+int ptx_denoise(ptx_ctx* c, const ptx_denoise_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, float* out_rgba, ptx_denoise_stats* stats) {
+	if (!cfg) return set_err(PTX_ERR_INVALID, "ptx_denoise: NULL argument");
+	return denoise_frame(c, DenoiseCall{"ptx_denoise", cfg->W, cfg->H, cfg->iterations, cfg->sigma_l, cfg->sigma_n, cfg->sigma_z, false, cfg->spp_a, cfg->spp_b}, accum_a, accum_b, guides,
+	                     out_rgba, stats);
+}
+
+int ptx_denoise_counts(ptx_ctx* c, const ptx_denoise_counts_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, float* out_rgba,
+                       ptx_denoise_stats* stats) {
+	if (!cfg) return set_err(PTX_ERR_INVALID, "ptx_denoise_counts: NULL argument");
+	return denoise_frame(c, DenoiseCall{"ptx_denoise_counts", cfg->W, cfg->H, cfg->iterations, cfg->sigma_l, cfg->sigma_n, cfg->sigma_z, true, cfg->guide_spp, 0u}, accum_a, accum_b,
+	                     guides, out_rgba, stats);
 }
 
 int adaptive_decide_locked(ptx_ctx* c, uint32_t w, uint32_t h, const float4* d_a, const float4* d_b, float threshold, uint8_t* d_done, uint32_t* d_pixels, uint32_t& n_active,

@@ -1,5 +1,5 @@
 // The render entry points of the C ABI: which pipeline renders a scene, the pixel list, the queue pipeline's plan / pass / stats, and
-// ptx_render, ptx_render_transparent, ptx_render_aov, ptx_render_nee, ptx_render_adaptive and ptx_intersect_batch.
+// ptx_render, ptx_render_transparent, ptx_render_aov, ptx_render_nee, ptx_render_adaptive, ptx_render_adaptive_nee and ptx_intersect_batch.
 #include <cmath>
 
 #include "api_internal.hpp"
@@ -653,73 +653,38 @@ int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffe
 
 namespace {
 
-// ptx_render_nee with PTX_NEE_FUSED on a scene of the fused route: one launch of k_nee_fused per pass, then the resolve. No round trips to the
-// host and no streams: the workspace is ptx_render's radiance records, overflow stacks and counters. The caller holds the context's mutex, has
-// set the device, planned the passes and uploaded the light list and, for PTX_NEE_ENV_SAMPLES, the environment table.
-int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeLights& Lt, const NeeEnv& Ev, float* accum, ptx_nee_stats* stats) {
-	const int grid = c->n_cu;
-	HIP_TRY(c->sample_rad.ensure((size_t)f.pass_spp * f.n_pixels * sizeof(float4)));
-	HIP_TRY(c->counters.ensure(1024));   // [0] chunk counter, [16] rays, [24] light samples, [32] visible light samples
-	HIP_TRY(c->spill.ensure((size_t)grid * (kBlock / 64) * (size_t)kSpillWords * sizeof(uint2)));
-	HIP_TRY(hipMemsetAsync(c->counters.p, 0, 1024, c->stream));
-	const NeeFusedBuffers B{(float4*)c->sample_rad.p, (uint2*)c->spill.p, (unsigned long long*)c->counters.p, (unsigned long long*)((char*)c->counters.p + 16)};
-	const bool dev_accum = is_device_ptr(accum);
-	Staged s_accum;
-	HIP_TRY(s_accum.bind(c, dev_accum, accum, f.rect_pixels() * sizeof(float4), c->stage_a));
-	if (stats)
-		if (const int rc = PassFrame::ensure_events(c, f.n_pass); rc != PTX_OK) return rc;
-	for (uint32_t p = 0; p < f.n_pass; p++) {
-		RenderParams P = f.params(p, true);
-		P.integrator = PTX_INTEGRATOR_LIB;
-		HIP_TRY(hipMemsetAsync(B.chunk_counter, 0, 8, c->stream));
-		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
-		HIP_TRY(launch_nee_fused(sc->dev, P, Lt, Ev, B, sc->mode, sc->lds_bytes, grid, c->stream));
-		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
-		HIP_TRY(launch_resolve(B.sample_rad, s_accum.as<float4>(), f.d_pixels, P.n_pixels, P.pass_spp, c->stream));
-	}
-	HIP_TRY(s_accum.copy_back(c));
-	if (stats || !dev_accum) HIP_TRY(hipStreamSynchronize(c->stream));
-	if (stats) {
-		unsigned long long cnt[3] = {0, 0, 0};   // rays, light samples, visible ones
-		HIP_TRY(hipMemcpy(cnt, B.counters, sizeof cnt, hipMemcpyDeviceToHost));
-		stats->light_samples = cnt[1]; stats->light_visible = cnt[2];
-		if (const int rc = f.stats(c, cnt[0], &stats->render); rc != PTX_OK) return rc;
-		c->timing.pipeline = 0u;
-		c->timing.workspace_bytes = c->spill.cap;
-		c->timing.fused_ms = stats->render.kernel_ms;
-		c->timing.fused_launches = f.n_pass;
-	}
-	return PTX_OK;
+// What ptx_render_nee's passes read besides the scene: the light list and the environment table on the device, and which form renders.
+// Made once per call (nee_setup_locked); ptx_render_adaptive_nee shares one over its rounds.
+struct NeeSetup {
+	NeeLights Lt{};
+	NeeEnv Ev{};
+	uint32_t n_lights = 0;   // listed triangles, whatever the flags
+	float light_area = 0;
+	bool fused = false;      // PTX_NEE_FUSED on a scene of the fused route
+};
+// Where a pass's samples go. b == nullptr: all of them into a (k_resolve). Otherwise the call's samples [0, split) into a and the rest into b
+// (k_resolve_halves): pass p, whose first sample is p * pass_spp, gives a its first clamp(split - p * pass_spp, 0, samples of the pass).
+struct NeeTargets {
+	float4 *a, *b;
+	uint32_t split;
+};
+
+hipError_t nee_resolve(const float4* rad, const NeeTargets& T, const PassFrame& f, const RenderParams& P, uint32_t p, hipStream_t stream) {
+	if (!T.b) return launch_resolve(rad, T.a, f.d_pixels, P.n_pixels, P.pass_spp, stream);
+	const int64_t left = (int64_t)T.split - (int64_t)p * f.pass_spp;
+	const uint32_t n_a = (uint32_t)std::clamp<int64_t>(left, 0, (int64_t)P.pass_spp);
+	return launch_resolve_halves(rad, T.a, T.b, f.d_pixels, P.n_pixels, P.pass_spp, n_a, stream);
 }
 
-}  // namespace
-
-int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* ncfg, float* accum, ptx_nee_stats* stats) {
-	// every refusal below is decided before any device work
-	if (!sc || !cfg || !accum) return set_err(PTX_ERR_INVALID, "ptx_render_nee: NULL argument");
-	const uint32_t flags = ncfg ? ncfg->flags : 0u;
-	if (flags & ~(uint32_t)(PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED | PTX_NEE_ENV_SAMPLES)) return set_err(PTX_ERR_INVALID, "ptx_render_nee: unknown flag");
-	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
-		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_nee: PTX_INTEGRATOR_WORKER has no light sampling here (the estimator is defined on PTX_INTEGRATOR_LIB's vertex)");
-	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_nee: scene was created without a GPU context (no CPU path exists)");
-	PassFrame f;
-	f.cfg = cfg;
-	if (const int rc = render_rect(cfg, "ptx_render_nee", true, f.x0, f.y0, f.w, f.h); rc != PTX_OK) return rc;
+// The light list and, for PTX_NEE_ENV_SAMPLES, the environment table: built and uploaded at the first call that asks, then kept on the scene.
+// The caller holds the context's mutex and has set the device.
+int nee_setup_locked(ptx_scene* sc, uint32_t flags, NeeSetup& S) {
 	ptx_ctx* c = sc->ctx;
-	std::lock_guard<std::mutex> lk(c->mu);
-	HIP_TRY(hipSetDevice(c->device));
-	if (stats) { *stats = ptx_nee_stats{}; c->timing = ptx_kernel_timing{}; c->timing.pipeline = use_wavefront(sc) ? 1u : 0u; }
 	const ptx_scene::LightList& ll = *build_lights(sc);
 	const uint32_t n_lights = (uint32_t)ll.cdf.size();
-	if (stats) { stats->n_lights = n_lights; stats->light_area = ll.area; }
+	S.n_lights = n_lights; S.light_area = ll.area;
 	// PTX_NEE_FUSED: one launch per pass wherever ptx_render would run the fused kernel; a scene of the queue route renders as without the flag
-	const bool fused = (flags & PTX_NEE_FUSED) != 0 && !use_wavefront(sc);
-	// The wavefront form's workspace takes 68 words per sample, so by default a pass has 16 Mi samples (8 spp of a 1080p frame, 4.6 GB); at most
-	// 2^30, so that the positions of a round's shadow rays (two per path at most) stay below 2^31. The fused form keeps only the 16-byte
-	// radiance record per sample: ptx_render's pass size and id limit.
-	if (const int rc = f.plan(c, sc, "ptx_render_nee", nullptr, fused ? 128ull << 20 : 16ull << 20, fused ? 0xFFFFFFFFull : 0x3FFFFFFFull); rc != PTX_OK || !f.n_pass) return rc;
-
-	NeeLights Lt{};
+	S.fused = (flags & PTX_NEE_FUSED) != 0 && !use_wavefront(sc);
 	if (n_lights && !(flags & PTX_NEE_NO_LIGHT_SAMPLES)) {
 		if (!sc->lights.on_device) {
 			HIP_TRY(sc->d_light_tris.ensure(ll.tris.size() * 4));
@@ -733,12 +698,11 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 			HIP_TRY(hipStreamSynchronize(c->stream));
 			sc->lights.on_device = true;
 		}
+		NeeLights& Lt = S.Lt;
 		Lt.tris = (const uint2*)sc->d_light_tris.p; Lt.cdf = (const float*)sc->d_light_cdf.p; Lt.geom = (const float4*)sc->d_light_geom.p;
 		Lt.surf_first = (const int32_t*)sc->d_light_first.p; Lt.n = n_lights; Lt.area = ll.area;
 	}
-
 	// PTX_NEE_ENV_SAMPLES: the ENV variants wherever the map has a table; no map or a black one: the call runs exactly as without the flag
-	NeeEnv Ev{};
 	if (flags & PTX_NEE_ENV_SAMPLES) {
 		const ptx_scene::EnvTable& et = *build_env_table(sc);
 		if (!et.row_cdf.empty() && sc->dev.env_tex >= 0) {
@@ -750,11 +714,67 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 				HIP_TRY(hipStreamSynchronize(c->stream));
 				sc->env_table.on_device = true;
 			}
+			NeeEnv& Ev = S.Ev;
 			Ev.row_cdf = (const float*)sc->d_env_row.p; Ev.cell_cdf = (const float*)sc->d_env_cell.p; Ev.w = et.w; Ev.h = et.h;
 		}
 	}
+	return PTX_OK;
+}
 
-	if (fused) return nee_fused_frame(c, sc, f, Lt, Ev, accum, stats);
+// ptx_render_nee with PTX_NEE_FUSED on a scene of the fused route: one launch of k_nee_fused per pass, then the resolve. No round trips to the
+// host and no streams: the workspace is ptx_render's radiance records, overflow stacks and counters. The caller holds the context's mutex, has
+// set the device, planned the passes and made the setup. With stats the stream is synchronised.
+int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeSetup& S, const NeeTargets& T, ptx_nee_stats* stats) {
+	const int grid = c->n_cu;
+	HIP_TRY(c->sample_rad.ensure((size_t)f.pass_spp * f.n_pixels * sizeof(float4)));
+	HIP_TRY(c->counters.ensure(1024));   // [0] chunk counter, [16] rays, [24] light samples, [32] visible light samples
+	HIP_TRY(c->spill.ensure((size_t)grid * (kBlock / 64) * (size_t)kSpillWords * sizeof(uint2)));
+	HIP_TRY(hipMemsetAsync(c->counters.p, 0, 1024, c->stream));
+	const NeeFusedBuffers B{(float4*)c->sample_rad.p, (uint2*)c->spill.p, (unsigned long long*)c->counters.p, (unsigned long long*)((char*)c->counters.p + 16)};
+	if (stats)
+		if (const int rc = PassFrame::ensure_events(c, f.n_pass); rc != PTX_OK) return rc;
+	for (uint32_t p = 0; p < f.n_pass; p++) {
+		RenderParams P = f.params(p, true);
+		P.integrator = PTX_INTEGRATOR_LIB;
+		HIP_TRY(hipMemsetAsync(B.chunk_counter, 0, 8, c->stream));
+		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
+		HIP_TRY(launch_nee_fused(sc->dev, P, S.Lt, S.Ev, B, sc->mode, sc->lds_bytes, grid, c->stream));
+		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
+		HIP_TRY(nee_resolve(B.sample_rad, T, f, P, p, c->stream));
+	}
+	if (stats) {
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		unsigned long long cnt[3] = {0, 0, 0};   // rays, light samples, visible ones
+		HIP_TRY(hipMemcpy(cnt, B.counters, sizeof cnt, hipMemcpyDeviceToHost));
+		stats->light_samples = cnt[1]; stats->light_visible = cnt[2];
+		if (const int rc = f.stats(c, cnt[0], &stats->render); rc != PTX_OK) return rc;
+		c->timing.pipeline = 0u;
+		c->timing.workspace_bytes = c->spill.cap;
+		c->timing.fused_ms = stats->render.kernel_ms;
+		c->timing.fused_launches = f.n_pass;
+	}
+	return PTX_OK;
+}
+
+// The passes of one ptx_render_nee call — the samples [cfg->sample0, cfg->sample0 + cfg->spp) of cfg's rectangle, or of `subset`'s pixels of
+// it — into the DEVICE buffers of `T`. The caller holds the context's mutex, has set the device, checked cfg and made the setup. With stats
+// (zeroed here, and the context's timing with them) the stream is synchronised; without, nothing waits for the last pass.
+int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, const NeeSetup& S, const NeeTargets& T, const PixelSubset* subset, ptx_nee_stats* stats) {
+	PassFrame f;
+	f.cfg = cfg;
+	if (const int rc = render_rect(cfg, who, true, f.x0, f.y0, f.w, f.h); rc != PTX_OK) return rc;
+	ptx_ctx* c = sc->ctx;
+	if (stats) {
+		*stats = ptx_nee_stats{}; c->timing = ptx_kernel_timing{}; c->timing.pipeline = use_wavefront(sc) ? 1u : 0u;
+		stats->n_lights = S.n_lights; stats->light_area = S.light_area;
+	}
+	// The wavefront form's workspace takes 68 words per sample, so by default a pass has 16 Mi samples (8 spp of a 1080p frame, 4.6 GB); at most
+	// 2^30, so that the positions of a round's shadow rays (two per path at most) stay below 2^31. The fused form keeps only the 16-byte
+	// radiance record per sample: ptx_render's pass size and id limit.
+	if (const int rc = f.plan(c, sc, who, subset, S.fused ? 128ull << 20 : 16ull << 20, S.fused ? 0xFFFFFFFFull : 0x3FFFFFFFull); rc != PTX_OK || !f.n_pass) return rc;
+	if (S.fused) return nee_fused_frame(c, sc, f, S, T, stats);
+	const NeeLights& Lt = S.Lt;
+	const NeeEnv& Ev = S.Ev;
 
 	// workspace of one pass of `cap` samples: [256 B: counters][radiance records][stream 0][stream 1][hits][shadow rays][shadow hits][shadow records]
 	const size_t cap = ((size_t)f.pass_spp * f.n_pixels + 3) & ~(size_t)3;   // array stride: keeps every array 16-byte aligned
@@ -785,9 +805,6 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 	HIP_TRY(c->round_ws.ensure(carve(nullptr)));
 	carve(c->round_ws.p);
 
-	const bool dev_accum = is_device_ptr(accum);
-	Staged s_accum;
-	HIP_TRY(s_accum.bind(c, dev_accum, accum, f.rect_pixels() * sizeof(float4), c->stage_a));
 	if (stats)
 		if (const int rc = PassFrame::ensure_events(c, f.n_pass); rc != PTX_OK) return rc;
 	HIP_TRY(hipMemsetAsync(cnt, 0, 256, c->stream));
@@ -815,7 +832,7 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 			uint32_t got[2] = {0, 0};   // continuations, shadow rays
 			HIP_TRY(hipMemcpyAsync(got, cnt, 8, hipMemcpyDeviceToHost, c->stream));
 			HIP_TRY(hipStreamSynchronize(c->stream));
-			if (got[0] > live || got[1] > 2ull * live) return set_err(PTX_ERR_HIP, "ptx_render_nee: a round appended more entries than its paths allow");
+			if (got[0] > live || got[1] > 2ull * live) return set_err(PTX_ERR_HIP, std::string(who) + ": a round appended more entries than its paths allow");
 			if (got[1]) {
 				IntersectArgs B{};
 				B.n = got[1];
@@ -828,17 +845,16 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 				if (catchers) {
 					HIP_TRY(hipMemcpyAsync(got, cnt, 4, hipMemcpyDeviceToHost, c->stream));
 					HIP_TRY(hipStreamSynchronize(c->stream));
-					if (got[0] > live) return set_err(PTX_ERR_HIP, "ptx_render_nee: a round appended more entries than its paths allow");
+					if (got[0] > live) return set_err(PTX_ERR_HIP, std::string(who) + ": a round appended more entries than its paths allow");
 				}
 			}
 			live = got[0];
 		}
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
-		HIP_TRY(launch_resolve(Lrec, s_accum.as<float4>(), f.d_pixels, P.n_pixels, P.pass_spp, c->stream));
+		HIP_TRY(nee_resolve(Lrec, T, f, P, p, c->stream));
 	}
-	HIP_TRY(s_accum.copy_back(c));
-	if (stats || !dev_accum) HIP_TRY(hipStreamSynchronize(c->stream));
 	if (stats) {
+		HIP_TRY(hipStreamSynchronize(c->stream));
 		unsigned long long ls[2] = {0, 0};
 		HIP_TRY(hipMemcpy(ls, cnt + 2, 16, hipMemcpyDeviceToHost));
 		stats->light_samples = ls[0]; stats->light_visible = ls[1];
@@ -847,19 +863,60 @@ int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* 
 	return PTX_OK;
 }
 
+constexpr uint32_t kNeeFlags = PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED | PTX_NEE_ENV_SAMPLES;
+
+}  // namespace
+
+int ptx_render_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_nee_cfg* ncfg, float* accum, ptx_nee_stats* stats) {
+	// every refusal below is decided before any device work
+	if (!sc || !cfg || !accum) return set_err(PTX_ERR_INVALID, "ptx_render_nee: NULL argument");
+	const uint32_t flags = ncfg ? ncfg->flags : 0u;
+	if (flags & ~kNeeFlags) return set_err(PTX_ERR_INVALID, "ptx_render_nee: unknown flag");
+	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
+		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_nee: PTX_INTEGRATOR_WORKER has no light sampling here (the estimator is defined on PTX_INTEGRATOR_LIB's vertex)");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_nee: scene was created without a GPU context (no CPU path exists)");
+	uint32_t x0, y0, w, h;
+	if (const int rc = render_rect(cfg, "ptx_render_nee", true, x0, y0, w, h); rc != PTX_OK) return rc;
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	NeeSetup S;
+	if (const int rc = nee_setup_locked(sc, flags, S); rc != PTX_OK) return rc;
+	const bool dev_accum = is_device_ptr(accum);
+	Staged s_accum;
+	if (cfg->spp) HIP_TRY(s_accum.bind(c, dev_accum, accum, (size_t)w * h * sizeof(float4), c->stage_a));
+	if (const int rc = nee_frame_locked(sc, cfg, "ptx_render_nee", S, NeeTargets{s_accum.as<float4>(), nullptr, 0u}, nullptr, stats); rc != PTX_OK) return rc;
+	if (cfg->spp) HIP_TRY(s_accum.copy_back(c));
+	if (cfg->spp && !dev_accum) HIP_TRY(hipStreamSynchronize(c->stream));
+	return PTX_OK;
+}
+
+namespace {
+
+// What ptx_render_adaptive and ptx_render_adaptive_nee refuse in their arguments with PTX_ERR_INVALID, decided before any device work;
+// -> the rectangle and the round size
+int adaptive_args(const char* who, const void* sc, const ptx_render_cfg* cfg, const ptx_adaptive_cfg* acfg, const float* accum_a, const float* accum_b, uint32_t& x0, uint32_t& y0,
+                  uint32_t& w, uint32_t& h, uint32_t& step) {
+	auto bad = [who](const char* m) { return set_err(PTX_ERR_INVALID, std::string(who) + ": " + m); };
+	if (!sc || !cfg || !acfg || !accum_a || !accum_b) return bad("NULL argument");
+	if (acfg->min_spp < 2 || (acfg->min_spp & 1u)) return bad("min_spp must be even and >= 2 (each round is split into two halves)");
+	if (acfg->step_spp & 1u) return bad("step_spp must be even (0 = min_spp)");
+	if ((cfg->spp & 1u) || cfg->spp < acfg->min_spp) return bad("spp (the cap) must be even and >= min_spp");
+	step = acfg->step_spp ? acfg->step_spp : acfg->min_spp;
+	if ((uint64_t)1 + ((uint64_t)(cfg->spp - acfg->min_spp) + step - 1) / step > 4096) return bad("more than 4096 rounds");
+	if (!(acfg->threshold >= 0.0f)) return bad("threshold is negative or NaN");
+	if ((uint64_t)cfg->sample0 + cfg->spp > 0xFFFFFFFFull) return bad("sample0 + spp overflows");
+	if (const int rc = render_rect(cfg, who, true, x0, y0, w, h); rc != PTX_OK) return rc;
+	if (w > kAdMaxSide || h > kAdMaxSide) return bad("the rectangle's sides must be at most 16384");
+	return PTX_OK;
+}
+
+}  // namespace
+
 int ptx_render_adaptive(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_adaptive_cfg* acfg, float* accum_a, float* accum_b, ptx_adaptive_stats* stats) {
 	// every refusal below is decided before any device work
-	if (!sc || !cfg || !acfg || !accum_a || !accum_b) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: NULL argument");
-	if (acfg->min_spp < 2 || (acfg->min_spp & 1u)) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: min_spp must be even and >= 2 (each round is split into two halves)");
-	if (acfg->step_spp & 1u) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: step_spp must be even (0 = min_spp)");
-	if ((cfg->spp & 1u) || cfg->spp < acfg->min_spp) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: spp (the cap) must be even and >= min_spp");
-	const uint32_t step = acfg->step_spp ? acfg->step_spp : acfg->min_spp;
-	if ((uint64_t)1 + ((uint64_t)(cfg->spp - acfg->min_spp) + step - 1) / step > 4096) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: more than 4096 rounds");
-	if (!(acfg->threshold >= 0.0f)) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: threshold is negative or NaN");
-	if ((uint64_t)cfg->sample0 + cfg->spp > 0xFFFFFFFFull) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: sample0 + spp overflows");
-	uint32_t x0, y0, w, h;
-	if (const int rc = render_rect(cfg, "ptx_render_adaptive", true, x0, y0, w, h); rc != PTX_OK) return rc;
-	if (w > kAdMaxSide || h > kAdMaxSide) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: the rectangle's sides must be at most 16384");
+	uint32_t x0, y0, w, h, step;
+	if (const int rc = adaptive_args("ptx_render_adaptive", sc, cfg, acfg, accum_a, accum_b, x0, y0, w, h, step); rc != PTX_OK) return rc;
 	if (cfg->shard_count > 1)
 		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_adaptive: shard_count > 1 is not supported (the 3 x 3 block of the decision would need other shards' pixels); "
 		                                    "split a frame over GPUs by rectangles instead");
@@ -912,6 +969,90 @@ int ptx_render_adaptive(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_adap
 		stats->rounds = rounds;
 		stats->active_last = n_active;
 		stats->select_ms = select_ms;
+	}
+	return PTX_OK;
+}
+
+// ptx_render_adaptive's loop on ptx_render_nee's estimator. A round is ONE sequence of passes over its k samples, resolved into both halves
+// (k_resolve_halves: the first k / 2 samples into A, the rest into B), not one sequence per half: half the launches' fixed price per round.
+int ptx_render_adaptive_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_adaptive_cfg* acfg, const ptx_nee_cfg* ncfg, float* accum_a, float* accum_b,
+                            ptx_adaptive_nee_stats* stats) {
+	// every refusal below is decided before any device work
+	uint32_t x0, y0, w, h, step;
+	if (const int rc = adaptive_args("ptx_render_adaptive_nee", sc, cfg, acfg, accum_a, accum_b, x0, y0, w, h, step); rc != PTX_OK) return rc;
+	const uint32_t flags = ncfg ? ncfg->flags : 0u;
+	if (flags & ~kNeeFlags) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive_nee: unknown flag");
+	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
+		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_adaptive_nee: PTX_INTEGRATOR_WORKER has no light sampling here (the estimator is defined on PTX_INTEGRATOR_LIB's vertex)");
+	if (cfg->shard_count > 1)
+		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_adaptive_nee: shard_count > 1 is not supported (the 3 x 3 block of the decision would need other shards' pixels); "
+		                                    "split a frame over GPUs by rectangles instead");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_adaptive_nee: scene was created without a GPU context (no CPU path exists)");
+	const bool dev = is_device_ptr(accum_a);
+	if (is_device_ptr(accum_b) != dev) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive_nee: accum_a and accum_b must both be device or both be host memory");
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	if (stats) *stats = ptx_adaptive_nee_stats{};
+	NeeSetup S;   // the light list and the environment table: once for all rounds
+	if (const int rc = nee_setup_locked(sc, flags, S); rc != PTX_OK) return rc;
+
+	const size_t n = (size_t)w * h, bytes = n * sizeof(float4);
+	Staged s_a, s_b;   // staged once for the whole call, both in one buffer
+	if (!dev) HIP_TRY(c->adaptive_stage.ensure(2 * bytes));
+	HIP_TRY(s_a.bind(c, dev, accum_a, bytes, c->adaptive_stage));
+	HIP_TRY(s_b.bind(c, dev, accum_b, bytes, c->adaptive_stage, bytes));
+	float4 *const d_a = s_a.as<float4>(), *const d_b = s_b.as<float4>();
+	HIP_TRY(c->adaptive_state.ensure(n * 4 + pad16(n)));
+	uint32_t* const d_list = (uint32_t*)c->adaptive_state.p;
+	uint8_t* const d_done = (uint8_t*)c->adaptive_state.p + n * 4;
+	HIP_TRY(hipMemsetAsync(d_done, 0, n, c->stream));
+
+	ptx_render_cfg round = *cfg;
+	round.x0 = x0; round.y0 = y0; round.w = w; round.h = h;
+	PixelSubset active{d_list, 0};
+	uint32_t given = 0, rounds = 0, n_active = 0;
+	double select_ms = 0;
+	ptx_kernel_timing timing{};
+	// PTX_ADAPTIVE_NEE_HALVES=1 (measurement, tools/bench_adaptive.py): every round as ptx_render_adaptive drives it, one sequence of passes per
+	// half through k_resolve. The same bits; twice the launches. What the one-sequence form saves is the difference.
+	const char* const halves_env = getenv("PTX_ADAPTIVE_NEE_HALVES");
+	const bool two_sequences = halves_env && halves_env[0] == '1';
+	while (given < cfg->spp) {
+		const uint32_t k = rounds == 0 ? acfg->min_spp : std::min(step, cfg->spp - given);   // even: min_spp, step_spp and the cap are
+		// one sequence of passes over the round's k samples, resolved into both halves; under the measurement switch one sequence per half
+		for (uint32_t part = 0; part < (two_sequences ? 2u : 1u); part++) {
+			round.sample0 = cfg->sample0 + given + part * (k / 2);
+			round.spp = two_sequences ? k / 2 : k;
+			const NeeTargets T = two_sequences ? NeeTargets{part ? d_b : d_a, nullptr, 0u} : NeeTargets{d_a, d_b, k / 2};
+			ptx_nee_stats st{};
+			if (const int rc = nee_frame_locked(sc, &round, "ptx_render_adaptive_nee", S, T, rounds == 0 ? nullptr : &active, stats ? &st : nullptr); rc != PTX_OK) return rc;
+			if (stats) {
+				ptx_nee_stats& t = stats->nee;
+				t.render.rays += st.render.rays; t.render.samples += st.render.samples; t.render.passes += st.render.passes; t.render.kernel_ms += st.render.kernel_ms;
+				t.light_samples += st.light_samples; t.light_visible += st.light_visible;
+				timing.pipeline = c->timing.pipeline;
+				timing.workspace_bytes = std::max(timing.workspace_bytes, c->timing.workspace_bytes);
+				timing.fused_ms += c->timing.fused_ms;
+				timing.fused_launches += c->timing.fused_launches;
+			}
+		}
+		given += k;
+		rounds++;
+		if (const int rc = adaptive_decide_locked(c, w, h, d_a, d_b, acfg->threshold, d_done, d_list, n_active, stats ? &select_ms : nullptr); rc != PTX_OK) return rc;
+		active.n_pixels = n_active;
+		if (n_active == 0) break;
+	}
+	HIP_TRY(s_a.copy_back(c));
+	HIP_TRY(s_b.copy_back(c));
+	if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
+	if (stats) {
+		stats->nee.n_lights = S.n_lights;
+		stats->nee.light_area = S.light_area;
+		stats->rounds = rounds;
+		stats->active_last = n_active;
+		stats->select_ms = select_ms;
+		c->timing = timing;   // the rounds' sums: with the fused form fused_launches == nee.render.passes and fused_ms == nee.render.kernel_ms
 	}
 	return PTX_OK;
 }

@@ -2,6 +2,7 @@
 // has no denoiser: every value here is defined by that text, IEEE binary32, one rounding per operation in the written parenthesisation.
 //   k_dn_prepare     per pixel: demodulated colour (col), the half-frame luminance variance estimate v0, the filter's guide (mean normal,
 //                    mean depth) and what the last pass needs to re-modulate (albedo, alpha)
+//   k_dn_prepare_counts   the same for half-buffers with per-pixel sample counts (ptx_denoise_counts); everything after it is shared
 //   k_dn_prefilter   3 x 3 geometry-weighted mean of v0 -> var
 //   k_dn_atrous      one iteration: 25 taps at distance `step`, in row-major order. Two forms of the same arithmetic (atrous_pixel):
 //                    TILED = false gathers the taps from global memory; TILED = true stages them in LDS first. The pixels congruent
@@ -42,6 +43,23 @@ __global__ void __launch_bounds__(256) k_dn_prepare(const float4* __restrict__ a
 	const float4 A = a[p], B = b[p], G = albedo_cov[p], N = normal_depth[p];
 	const float cov = G.w, miss = n - cov;   // missed samples count as albedo 1
 	const float ax = fmaxf((G.x + miss) / n, 0.001f), ay = fmaxf((G.y + miss) / n, 0.001f), az = fmaxf((G.z + miss) / n, 0.001f);
+	const float d = (dn_lum((A.x / na) / ax, (A.y / na) / ay, (A.z / na) / az) - dn_lum((B.x / nb) / ax, (B.y / nb) / ay, (B.z / nb) / az)) * 0.5f;
+	col_var[p] = make_float4(((A.x + B.x) / n) / ax, ((A.y + B.y) / n) / ay, ((A.z + B.z) / n) / az, d * d);
+	guide[p] = cov > 0.0f ? make_float4(N.x / cov, N.y / cov, N.z / cov, N.w / cov) : make_float4(0.f, 0.f, 0.f, 0.f);
+	remod[p] = make_float4(ax, ay, az, (A.w + B.w) / n);
+}
+
+// k_dn_prepare for half-buffers that carry their own per-pixel sample counts in .w (ptx_denoise_counts: what ptx_render_adaptive and
+// ptx_render_adaptive_nee leave); the guides are sums over ng samples of every pixel. A zero half count gives a non-finite pixel.
+__global__ void __launch_bounds__(256) k_dn_prepare_counts(const float4* __restrict__ a, const float4* __restrict__ b, const float4* __restrict__ albedo_cov,
+                                                           const float4* __restrict__ normal_depth, float ng, size_t n_pixels, float4* __restrict__ col_var,
+                                                           float4* __restrict__ guide, float4* __restrict__ remod) {
+	const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (p >= n_pixels) return;
+	const float4 A = a[p], B = b[p], G = albedo_cov[p], N = normal_depth[p];
+	const float na = A.w, nb = B.w, n = na + nb;
+	const float cov = G.w, miss = ng - cov;   // missed samples count as albedo 1
+	const float ax = fmaxf((G.x + miss) / ng, 0.001f), ay = fmaxf((G.y + miss) / ng, 0.001f), az = fmaxf((G.z + miss) / ng, 0.001f);
 	const float d = (dn_lum((A.x / na) / ax, (A.y / na) / ay, (A.z / na) / az) - dn_lum((B.x / nb) / ax, (B.y / nb) / ay, (B.z / nb) / az)) * 0.5f;
 	col_var[p] = make_float4(((A.x + B.x) / n) / ax, ((A.y + B.y) / n) / ay, ((A.z + B.z) / n) / az, d * d);
 	guide[p] = cov > 0.0f ? make_float4(N.x / cov, N.y / cov, N.z / cov, N.w / cov) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -168,6 +186,13 @@ hipError_t launch_denoise_prepare(const float4* a, const float4* b, const float4
                                   float4* col_var, float4* guide, float4* remod, hipStream_t stream) {
 	hipLaunchKernelGGL(k_dn_prepare, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, a, b, albedo_cov, normal_depth, (float)(spp_a + spp_b), (float)spp_a,
 	                   (float)spp_b, n_pixels, col_var, guide, remod);
+	return hipGetLastError();
+}
+
+hipError_t launch_denoise_prepare_counts(const float4* a, const float4* b, const float4* albedo_cov, const float4* normal_depth, uint32_t guide_spp, size_t n_pixels,
+                                         float4* col_var, float4* guide, float4* remod, hipStream_t stream) {
+	hipLaunchKernelGGL(k_dn_prepare_counts, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, a, b, albedo_cov, normal_depth, (float)guide_spp, n_pixels, col_var, guide,
+	                   remod);
 	return hipGetLastError();
 }
 

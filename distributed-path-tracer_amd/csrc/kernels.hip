@@ -571,6 +571,32 @@ __global__ void k_resolve(const float4* __restrict__ sample_rad, float4* __restr
 	accum[dst] = a;
 }
 
+// k_resolve on two targets (ptx_render_adaptive_nee: a round's two halves from one sequence of passes): the pass's samples s < n_a of each
+// pixel go into accum_a, the rest into accum_b, each in sample order and each with k_resolve's load, adds and store — so a buffer holds,
+// bit for bit, what k_resolve calls over its own samples leave. A buffer that receives no sample of this pass is not touched.
+__global__ void k_resolve_halves(const float4* __restrict__ sample_rad, float4* accum_a, float4* accum_b, const uint32_t* __restrict__ pixels,
+                                 uint32_t n_pixels, uint32_t pass_spp, uint32_t n_a) {
+	uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p >= n_pixels) return;
+	const uint32_t dst = pixels ? pixels[p] : p;
+	if (n_a > 0) {
+		float4 a = accum_a[dst];
+		for (uint32_t s = 0; s < n_a; s++) {
+			float4 r = sample_rad[(size_t)s * n_pixels + p];
+			a.x += r.x; a.y += r.y; a.z += r.z; a.w += r.w;
+		}
+		accum_a[dst] = a;
+	}
+	if (n_a < pass_spp) {
+		float4 b = accum_b[dst];
+		for (uint32_t s = n_a; s < pass_spp; s++) {
+			float4 r = sample_rad[(size_t)s * n_pixels + p];
+			b.x += r.x; b.y += r.y; b.z += r.z; b.w += r.w;
+		}
+		accum_b[dst] = b;
+	}
+}
+
 // core::renderer::render()'s blend with transparent_background set (renderer.cpp:374-399), for the samples of one pass: every pixel
 // goes through its samples in sample order on the reference's state {color, alpha, claimed}. `s` is the GLOBAL sample index (the
 // reference's loop variable, a uint32_t that the arithmetic promotes to float: vec3.inl:180-200). This is a recurrence, not a sum:
@@ -806,6 +832,11 @@ hipError_t launch_render_pass(const DevScene& S, const RenderParams& P, const Pa
 }
 hipError_t launch_resolve(const float4* sample_rad, float4* accum, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp, hipStream_t stream) {
 	hipLaunchKernelGGL(k_resolve, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, sample_rad, accum, pixels, n_pixels, pass_spp);
+	return hipGetLastError();
+}
+hipError_t launch_resolve_halves(const float4* sample_rad, float4* accum_a, float4* accum_b, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp, uint32_t n_a,
+                                 hipStream_t stream) {
+	hipLaunchKernelGGL(k_resolve_halves, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, sample_rad, accum_a, accum_b, pixels, n_pixels, pass_spp, n_a);
 	return hipGetLastError();
 }
 hipError_t launch_resolve_claim(const float4* sample_rad, float4* pixel_rgba, uint8_t* claimed, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp, uint32_t sample0,

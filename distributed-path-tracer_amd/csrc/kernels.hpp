@@ -165,6 +165,9 @@ hipError_t launch_wf_intersect(const DevScene& S, const IntersectArgs& A, size_t
 hipError_t launch_render_pass(const DevScene& S, const RenderParams& P, const PassBuffers& B, int mode, size_t lds_bytes, int grid,
                               hipStream_t stream);
 hipError_t launch_resolve(const float4* sample_rad, float4* accum, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp, hipStream_t stream);
+// the pass's samples s < n_a (<= pass_spp) of each pixel into accum_a, the rest into accum_b, each as launch_resolve adds them
+hipError_t launch_resolve_halves(const float4* sample_rad, float4* accum_a, float4* accum_b, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp, uint32_t n_a,
+                                 hipStream_t stream);
 hipError_t launch_resolve_claim(const float4* sample_rad, float4* pixel_rgba, uint8_t* claimed, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp,
                                 uint32_t sample0 /* global index of the pass's first sample */, hipStream_t stream);
 hipError_t launch_intersect(const DevScene& S, const IntersectArgs& A, int mode, size_t lds_bytes, int grid, hipStream_t stream);
@@ -258,6 +261,9 @@ hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeL
 // prepare: the two radiance sums and the guide sums -> col_var (demodulated colour, v0), guide (mean normal, mean depth), remod (albedo, alpha)
 hipError_t launch_denoise_prepare(const float4* a, const float4* b, const float4* albedo_cov, const float4* normal_depth, uint32_t spp_a, uint32_t spp_b, size_t n_pixels,
                                   float4* col_var, float4* guide, float4* remod, hipStream_t stream);
+// the same with per-pixel sample counts: a.w and b.w are the halves' counts, the guides hold guide_spp samples of every pixel (ptx_denoise_counts)
+hipError_t launch_denoise_prepare_counts(const float4* a, const float4* b, const float4* albedo_cov, const float4* normal_depth, uint32_t guide_spp, size_t n_pixels,
+                                         float4* col_var, float4* guide, float4* remod, hipStream_t stream);
 // 3 x 3 variance prefilter: in (col, v0) -> out (col, var)
 hipError_t launch_denoise_prefilter(const float4* in, const float4* guide, uint32_t W, uint32_t H, float sigma_n, float sigma_z, float4* out, hipStream_t stream);
 // one iteration at `step`: in (col, var) -> out (col, var), or, with `last`, out = (col * albedo, alpha) of remod. tiled: the LDS-staged form

@@ -10,6 +10,7 @@
 #include <filesystem>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace core {
@@ -117,8 +118,9 @@ public:
 	}
 
 	// The frame with noise-driven per-pixel sample counts (ptx_render_adaptive; sample_count is the cap): returns the MEANS [H][W][4] (write them
-	// with ptx_tonemap_encode(..., spp = 1)). stats optional: render.samples / (W * H) is the mean count
-	std::vector<float> render_adaptive(ptx_adaptive_stats* stats = nullptr) const {
+	// with ptx_tonemap_encode(..., spp = 1)). stats optional: render.samples / (W * H) is the mean count. denoise: the frame through the filter
+	// (ptx_denoise_counts on the guides of the first adaptive_min samples, which every pixel has); dstats optional
+	std::vector<float> render_adaptive(ptx_adaptive_stats* stats = nullptr, bool denoise = false, ptx_denoise_stats* dstats = nullptr) const {
 		if (!scene_) throw std::runtime_error("render_adaptive() before load_gltf()");
 		if (transparent_background) throw std::runtime_error("render_adaptive: the decision takes radiance sums, which transparent_background does not produce");
 		if (environment.string() != env_set_) {
@@ -133,7 +135,57 @@ public:
 		const size_t floats = (size_t)c.W * c.H * 4;
 		std::vector<float> a(floats, 0.f), b(floats, 0.f);
 		check(ptx_render_adaptive(scene_, &c, &ac, a.data(), b.data(), stats));
-		check(ptx_accum_mean(ctx_, a.data(), b.data(), floats / 4, a.data()));
+		return adaptive_frame(c, a, b, denoise, dstats);
+	}
+
+	// render_adaptive on render_nee's estimator (ptx_render_adaptive_nee; flags: ptx_nee_cfg::flags): one sequence of passes per round, resolved
+	// into both halves. Returns the MEANS [H][W][4], through the filter with denoise. stats, dstats optional
+	std::vector<float> render_adaptive_nee(ptx_adaptive_nee_stats* stats = nullptr, uint32_t flags = 0, bool denoise = false, ptx_denoise_stats* dstats = nullptr) const {
+		if (!scene_) throw std::runtime_error("render_adaptive_nee() before load_gltf()");
+		if (transparent_background) throw std::runtime_error("render_adaptive_nee: the decision takes radiance sums, which transparent_background does not produce");
+		if (environment.string() != env_set_) {
+			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
+			env_set_ = environment.string();
+		}
+		ptx_render_cfg c{};
+		c.W = resolution.x; c.H = resolution.y; c.spp = sample_count; c.bounces = bounce_count;
+		for (int k = 0; k < 3; k++) c.env[k] = environment_factor[k];
+		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
+		const ptx_adaptive_cfg ac{adaptive_min, adaptive_step, adaptive_threshold};
+		const ptx_nee_cfg n{flags};
+		const size_t floats = (size_t)c.W * c.H * 4;
+		std::vector<float> a(floats, 0.f), b(floats, 0.f);
+		check(ptx_render_adaptive_nee(scene_, &c, &ac, &n, a.data(), b.data(), stats));
+		return adaptive_frame(c, a, b, denoise, dstats);
+	}
+
+	// The light-sampled frame through the filter (ptx_denoise): samples [0, n/2) and [n/2, n) of sample_count = n rendered with ptx_render_nee
+	// into two buffers, the guide buffers of all n; returns the filtered MEANS [H][W][4]. stats optional
+	std::vector<float> render_nee_denoised(uint32_t flags = 0, ptx_denoise_stats* stats = nullptr) const {
+		if (!scene_) throw std::runtime_error("render_nee_denoised() before load_gltf()");
+		if (transparent_background) throw std::runtime_error("render_nee_denoised: transparent_background's blend is not built on this estimator");
+		if (sample_count < 2) throw std::runtime_error("render_nee_denoised: sample_count must be at least 2 (the noise estimate needs two half-frames)");
+		if (environment.string() != env_set_) {
+			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
+			env_set_ = environment.string();
+		}
+		ptx_render_cfg c{};
+		c.W = resolution.x; c.H = resolution.y; c.bounces = bounce_count;
+		for (int k = 0; k < 3; k++) c.env[k] = environment_factor[k];
+		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
+		const size_t floats = (size_t)c.W * c.H * 4;
+		std::vector<float> a(floats, 0.f), b(floats, 0.f), alb(floats, 0.f), nd(floats, 0.f);
+		const ptx_nee_cfg n{flags};
+		c.spp = sample_count / 2;
+		check(ptx_render_nee(scene_, &c, &n, a.data(), nullptr));
+		c.sample0 = c.spp; c.spp = sample_count - c.sample0;
+		check(ptx_render_nee(scene_, &c, &n, b.data(), nullptr));
+		c.sample0 = 0; c.spp = sample_count;
+		const ptx_aov_buffers g{alb.data(), nd.data()};
+		check(ptx_render_aov(scene_, &c, &g, nullptr));
+		ptx_denoise_cfg d{};
+		d.W = c.W; d.H = c.H; d.spp_a = sample_count / 2; d.spp_b = sample_count - d.spp_a;
+		check(ptx_denoise(ctx_, &d, a.data(), b.data(), &g, a.data(), stats));
 		return a;
 	}
 
@@ -175,6 +227,21 @@ public:
 	}
 
 private:
+	// the means of two adaptive half-buffers, or the halves through ptx_denoise_counts with the guides of the first adaptive_min samples
+	std::vector<float> adaptive_frame(ptx_render_cfg c, std::vector<float>& a, std::vector<float>& b, bool denoise, ptx_denoise_stats* dstats) const {
+		if (!denoise) {
+			check(ptx_accum_mean(ctx_, a.data(), b.data(), a.size() / 4, a.data()));
+			return std::move(a);
+		}
+		std::vector<float> alb(a.size(), 0.f), nd(a.size(), 0.f);
+		const ptx_aov_buffers g{alb.data(), nd.data()};
+		c.spp = adaptive_min;
+		check(ptx_render_aov(scene_, &c, &g, nullptr));
+		ptx_denoise_counts_cfg d{};
+		d.W = c.W; d.H = c.H; d.guide_spp = adaptive_min;
+		check(ptx_denoise_counts(ctx_, &d, a.data(), b.data(), &g, a.data(), dstats));
+		return std::move(a);
+	}
 	static void check(int rc) {
 		if (rc != PTX_OK) throw std::runtime_error(std::string(ptx_last_error()));
 	}

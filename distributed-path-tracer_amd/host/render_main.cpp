@@ -9,6 +9,10 @@
 //                      towards the map too (PTX_NEE_ENV_SAMPLES); combines with --nee-fused
 //       --adaptive THR[:MIN[:STEP]]: noise-driven per-pixel sample counts (renderer::render_adaptive) with spp as the cap: every pixel gets MIN
 //                      samples (8), then rounds of STEP (MIN) go to the pixels whose half-frames still disagree by more than THR
+//       combinations:  --adaptive with --nee / --nee-fused / --nee-env renders the adaptive loop on the light-sampling estimator
+//                      (renderer::render_adaptive_nee); --adaptive --denoise, with or without --nee*, filters the adaptive frame
+//                      (ptx_denoise_counts on the guides of the first MIN samples); --nee* --denoise filters two light-sampled half-frames
+//                      (renderer::render_nee_denoised). --transparent combines with none of them
 //       --aov PREFIX:  also writes the denoiser's guide images PREFIX_albedo.png (mean albedo of the covered samples, alpha = coverage)
 //                      and PREFIX_normal.png (mean shading normal * 0.5 + 0.5), quantised linearly to 8 bits
 //   ptx_render_cli --event <event.json> <local scene root dir> <out.png>     (the worker's Lambda event, main.cpp:9-25)
@@ -97,12 +101,23 @@ int main(int argc, char** argv) {
 		auto t0 = std::chrono::steady_clock::now();
 		ptx_denoise_stats dst{};
 		ptx_adaptive_stats ast{};
+		ptx_adaptive_nee_stats anst{};
 		r.adaptive_threshold = ad_thr; r.adaptive_min = ad_min; r.adaptive_step = ad_step;
-		if (adaptive && denoise) throw std::runtime_error("--adaptive and --denoise do not combine: the filter takes one sample count per buffer");
 		ptx_nee_stats nst{};
-		if (nee && (adaptive || denoise || transparent)) throw std::runtime_error("--nee does not combine with --adaptive, --denoise or --transparent");
-		std::vector<uint8_t> png = nee ? r.encode(r.render_nee(&nst, (nee_fused ? PTX_NEE_FUSED : 0u) | (nee_env.empty() ? 0u : PTX_NEE_ENV_SAMPLES)), r.sample_count)
-		                               : adaptive ? r.encode(r.render_adaptive(&ast), 1) : denoise ? r.encode(r.render_denoised(&dst), 1) : r.render();
+		if (transparent && (nee || adaptive || denoise)) throw std::runtime_error("--transparent does not combine with --nee, --adaptive or --denoise");
+		const uint32_t nee_flags = (nee_fused ? PTX_NEE_FUSED : 0u) | (nee_env.empty() ? 0u : PTX_NEE_ENV_SAMPLES);
+		std::vector<uint8_t> png;
+		if (nee && adaptive) {
+			png = r.encode(r.render_adaptive_nee(&anst, nee_flags, denoise, &dst), 1);
+			nst = anst.nee;
+			ast.render = anst.nee.render; ast.rounds = anst.rounds; ast.active_last = anst.active_last; ast.select_ms = anst.select_ms;
+		} else if (nee) {
+			png = denoise ? r.encode(r.render_nee_denoised(nee_flags, &dst), 1) : r.encode(r.render_nee(&nst, nee_flags), r.sample_count);
+		} else if (adaptive) {
+			png = r.encode(r.render_adaptive(&ast, denoise, &dst), 1);
+		} else {
+			png = denoise ? r.encode(r.render_denoised(&dst), 1) : r.render();
+		}
 		double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 		std::ofstream(argv[2], std::ios::binary).write((const char*)png.data(), (std::streamsize)png.size());
 		double aov_ms = 0;
@@ -130,7 +145,7 @@ int main(int argc, char** argv) {
 		if (adaptive)
 			std::printf(", \"adaptive_mean_spp\": %.3f, \"adaptive_rounds\": %u, \"adaptive_active_last\": %u, \"adaptive_select_ms\": %.3f",
 			            (double)ast.render.samples / ((double)r.resolution.x * r.resolution.y), ast.rounds, ast.active_last, ast.select_ms);
-		if (nee)
+		if (nee && (adaptive || !denoise))   // the two half-frames of --nee --denoise are rendered without stats
 			std::printf(", \"nee_lights\": %u, \"nee_light_samples\": %llu, \"nee_light_visible\": %llu, \"nee_kernel_ms\": %.3f", nst.n_lights,
 			            (unsigned long long)nst.light_samples, (unsigned long long)nst.light_visible, nst.render.kernel_ms);
 		std::printf("}\n");

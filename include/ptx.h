@@ -304,11 +304,36 @@ typedef struct ptx_denoise_stats {
 } ptx_denoise_stats;
 int ptx_denoise(ptx_ctx* ctx, const ptx_denoise_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, float* out_rgba,
                 ptx_denoise_stats* stats /* NULL ok */);
+/* ptx_denoise for half-buffers whose .w is the PER-PIXEL sample count: what ptx_render_adaptive and ptx_render_adaptive_nee leave (and what
+ * ptx_render leaves too: a frame of uniform counts spp_a, spp_b with guide_spp = spp_a + spp_b is filtered bit for bit as ptx_denoise filters it).
+ *   accum_a, accum_b [H][W][4]: the two halves' radiance SUMS, .w = the samples summed in that pixel;
+ *   guides:                     the ptx_render_aov SUMS over guide_spp samples of EVERY pixel. For an adaptive frame render them over
+ *                               [sample0, sample0 + min_spp): every pixel's samples are a prefix at least that long, so the guide samples are
+ *                               camera samples of the beauty frame;
+ *   out_rgba, buffer kinds, iterations, sigmas, stats: as in ptx_denoise.
+ * Only step 1 of the filter's specification changes (same rounding rules); per pixel:
+ *   1. na = a.w, nb = b.w, n = na + nb, ng = float(guide_spp); cov = albedo_cov.w; alb_c = max((albedo_cov.c + (ng - cov)) / ng, 0.001f);
+ *      col_c = ((a.c + b.c) / n) / alb_c; ma_c = (a.c / na) / alb_c, mb_c likewise; d = (lum(ma) - lum(mb)) * 0.5f; v0 = d * d;
+ *      alpha = (a.w + b.w) / n; nrm and z as in ptx_denoise.
+ * Steps 2 to 5, their kernels and the workspace are ptx_denoise's. Zero counts (no adaptive frame has them: every half of a round holds a
+ * sample): a pixel with n = 0 is non-finite and is treated as the filter treats every non-finite pixel — it stays itself and contaminates no
+ * neighbour. A pixel with ONE empty half has a finite colour and a NaN noise estimate: the output stays finite; the pixel is never
+ * filtered, and the pixels that take it as a tap inherit the NaN variance and are not filtered further.
+ * PTX_ERR_INVALID, each decided before any device work, for what ptx_denoise refuses, with guide_spp == 0 in place of its spp_a / spp_b rule. */
+typedef struct ptx_denoise_counts_cfg {
+	uint32_t W, H;             /* buffer size */
+	uint32_t guide_spp;        /* samples of every pixel summed in the guides */
+	uint32_t iterations;       /* 0 = 5; at most 8 */
+	float sigma_l, sigma_n, sigma_z;   /* 0 = default 4, 0.5, 0.1 */
+} ptx_denoise_counts_cfg;
+int ptx_denoise_counts(ptx_ctx* ctx, const ptx_denoise_counts_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides,
+                       float* out_rgba, ptx_denoise_stats* stats /* NULL ok */);
 
 /* Noise-driven per-pixel sample counts (no counterpart in the reference, which gives every pixel sample_count samples): a frame is rendered in
  * rounds, and a pixel whose two half-frames already agree, with all its neighbours, gets no further samples. On open, sun-lit scenes most
- * pixels stop at the first round; on a scene whose pixels are all about equally noisy (the Cornell box: there is no next-event estimation
- * towards its area light) nothing is gained over a uniform frame of the same mean count (DESIGN.md has the tables).
+ * pixels stop at the first round; on a scene whose pixels are all about equally noisy (the Cornell box under this estimator, which has no
+ * next-event estimation towards its area light: ptx_render_adaptive_nee below runs the same loop with it) nothing is gained over a uniform
+ * frame of the same mean count (DESIGN.md has the tables).
  * There are two half-buffers, A and B: accum_a, accum_b [h][w][4] float32 radiance SUMS of the rectangle, in ptx_render's accum format (w counts
  * the samples: the sums carry their own per-pixel sample count). This text is the specification:
  *   Rounds. cfg->spp is the cap. Round 0 gives every pixel of the rectangle the samples [sample0, sample0 + min_spp): the first half is ADDED to
@@ -335,8 +360,8 @@ int ptx_denoise(ptx_ctx* ctx, const ptx_denoise_cfg* cfg, const float* accum_a, 
  * in ptx_render, and both integrators are accepted. A rectangle is decided on its own: the 3 x 3 block is clipped to it, so along the cuts a
  * frame rendered in rectangles may stop pixels that the whole frame's decision keeps.
  * Image write: ptx_accum_mean, then ptx_tonemap_encode(..., spp = 1, ...).
- * Out of scope: ptx_render_transparent's blend (a recurrence, not a sum), ptx_denoise on the result (it takes one count per buffer, not one per
- * pixel), and the multi-process driver (multigpu.py).
+ * The result is filtered by ptx_denoise_counts (ptx_denoise takes one count per buffer, not one per pixel).
+ * Out of scope: ptx_render_transparent's blend (a recurrence, not a sum) and the multi-process driver (multigpu.py).
  * Refusals, all decided before any device work: PTX_ERR_INVALID for NULL arguments, an odd or zero min_spp, an odd step_spp, cfg->spp odd or
  * below min_spp, more than 4096 rounds, a negative or NaN threshold, pointers of mixed kinds, and whatever ptx_render refuses in cfg;
  * PTX_ERR_UNSUPPORTED for shard_count > 1 (the 3 x 3 block would need other shards' pixels: split a frame over GPUs by rectangles instead);
@@ -387,8 +412,9 @@ int ptx_accum_mean(ptx_ctx* ctx, const float* accum_a, const float* accum_b /* N
  * Tiles, sample0, spp_per_pass, shard_*, host or device accum and bounces == 0 work as in ptx_render.
  * Refusals, all decided before any device work: PTX_ERR_UNSUPPORTED for PTX_INTEGRATOR_WORKER; PTX_ERR_NO_DEVICE for a host-only scene;
  * PTX_ERR_INVALID for NULL scene, cfg or accum, unknown flags and whatever ptx_render refuses in cfg.
- * Out of scope: ptx_render_transparent's blend, ptx_render_adaptive on this estimator, the worker estimator, and multigpu.py (its shards
- * and sample ranges already compose through the accum format). */
+ * ptx_render_adaptive_nee (below the flags) runs ptx_render_adaptive's loop on this estimator.
+ * Out of scope: ptx_render_transparent's blend, the worker estimator, and multigpu.py (its shards and sample ranges already compose through
+ * the accum format). */
 #define PTX_NEE_NO_LIGHT_SAMPLES 1u   /* run with an empty list */
 /* PTX_NEE_FUSED: render with ONE kernel launch per pass wherever ptx_render would run this scene on its fused kernel (pipeline 0: LDS-resident and
  * hybrid scenes, global-memory scenes under PTX_WAVEFRONT=0): a lane carries a path from its camera ray to its end in registers, without the
@@ -440,6 +466,27 @@ typedef struct ptx_nee_stats {
 } ptx_nee_stats;
 int ptx_render_nee(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_nee_cfg* ncfg /* NULL = defaults */, float* accum_rgba,
                    ptx_nee_stats* stats /* NULL ok */);
+
+/* Noise-driven per-pixel sample counts on the light-sampling estimator: the specification is ptx_render_adaptive's text (rounds, decision,
+ * latch, active list, clipping to the rectangle; the same decision kernels) with "ptx_render" read as "ptx_render_nee with ncfg->flags". After
+ * the call a pixel with n samples holds, bit for bit, what ptx_render_nee calls of the same half ranges with the same flags leave in A and
+ * in B — for every flag combination, on every route and for any spp_per_pass.
+ * One sequence of passes per round, not two: a round's k samples [s, s + k) are planned as ptx_render_nee plans a call of spp = k on the
+ * round's pixels (each form with its own default pass size and id limit), and every pass is resolved into BOTH halves: the round's samples
+ * below s + k / 2 are added to A and the others to B, each in sample order. A sample's radiance is keyed by (pixel, sample) and each buffer
+ * receives its samples in ascending order, so the result is bitwise that of two calls per round at half the launches.
+ * Stats: nee.render and light_samples / light_visible are sums over the rounds (render.samples = the sum of the per-pixel counts,
+ * render.passes = the passes launched: with the default pass size on a small frame passes == rounds); n_lights and light_area as in
+ * ptx_render_nee; rounds, active_last, select_ms as in ptx_adaptive_stats. ptx_ctx_get_timing after a call with stats reports the pipeline;
+ * when the fused form ran, fused_launches == nee.render.passes and fused_ms == nee.render.kernel_ms, otherwise fused_launches == 0.
+ * Host buffers are staged once for the whole call; the light list and the environment table are uploaded once. The call always synchronises,
+ * as ptx_render_adaptive does. Filter the result with ptx_denoise_counts; image write as for ptx_render_adaptive.
+ * Refusals, all decided before any device work: everything ptx_render_adaptive refuses (PTX_ERR_UNSUPPORTED for shard_count > 1) and
+ * everything ptx_render_nee refuses (PTX_ERR_INVALID for an unknown flag, PTX_ERR_UNSUPPORTED for PTX_INTEGRATOR_WORKER, PTX_ERR_NO_DEVICE for
+ * a host-only scene). */
+typedef struct ptx_adaptive_nee_stats { ptx_nee_stats nee; uint32_t rounds, active_last; double select_ms; } ptx_adaptive_nee_stats;
+int ptx_render_adaptive_nee(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_adaptive_cfg* acfg, const ptx_nee_cfg* ncfg /* NULL = defaults */,
+                            float* accum_a, float* accum_b, ptx_adaptive_nee_stats* stats /* NULL ok */);
 
 /* Measurement aid (no counterpart in the reference): where the time of the last ptx_render that was given a stats pointer went.
  * Scenes whose geometry fits the LDS or whose models have few surfaces run ONE fused kernel per pass (pipeline 0: fused_ms);

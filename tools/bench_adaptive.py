@@ -9,6 +9,17 @@
                                              wall time and tonemapped mean squared error (the product's own image write, bytes / 255)
                                              against the product's ref_spp frame (4096, seed 77) of the adaptive render and of the uniform
                                              ptx_render at the next even count above the adaptive mean.
+  tools/bench_adaptive.py --nee [out] [ref_spp]   ptx_render_adaptive_nee and ptx_denoise_counts on Cornell (threshold 0.2) and plaza (level 3,
+                                             threshold 0.1) at 1920 x 1080, 8 samples first, 8 per round, cap 64, device buffers; wall times are the
+                                             smallest of 3 synchronised calls after a warm-up, the variants alternated call by call:
+                                             (a) the call with and without PTX_NEE_FUSED, against the same rounds rendered as one sequence of
+                                                 passes per half (PTX_ADAPTIVE_NEE_HALVES=1: two ptx_render_nee pass sequences per round plus the
+                                                 decision) — the difference over the rounds is the fixed price per round that the one-sequence
+                                                 form saves;
+                                             (b) error and wall time against the uniform ptx_render_nee frame at the next even count above the
+                                                 adaptive mean (tonemapped mean squared error against the product's ref_spp frame, 1024, seed 77);
+                                             (c) ptx_denoise_counts: kernel time, and the error after it.
+                                             The JSON lines go to `out` (profiles/adaptive_nee_bench.txt) too.
 Prints one JSON line per measurement.
 """
 import importlib
@@ -91,8 +102,99 @@ def payoff(ref_spp):
         s.close()
 
 
+def nee(out_path, ref_spp):
+    ctx = ptx.Context(0)
+    W, H, reps = 1920, 1080, 3
+    FUSED = ptx.NEE_FUSED
+    scenes = {"cornell": (lambda: ptx.Scene.load_gltf(ctx, CORNELL), 0.2),
+              "plaza3": (lambda: ptx.Scene.from_arrays(ctx, *[proc.plaza_scene()[k] for k in KEYS]), 0.1)}
+    lines = []
+
+    def emit(**kw):
+        lines.append(json.dumps(kw))
+        print(lines[-1], flush=True)
+
+    def image(mean):
+        return ctx.tonemap_encode(mean, W, H, 1)[..., :3].astype(np.float64) / 255
+
+    def mse(x, ref):
+        return float(np.mean((x - ref) ** 2))
+
+    def timed(call):
+        """wall seconds of one synchronised call on fresh device buffers"""
+        a, b = zeros(W, H), zeros(W, H)
+        t0 = time.perf_counter()
+        out = call(a, b)
+        ctx.synchronize()
+        return time.perf_counter() - t0, a, b, out
+    for name, (make, thr) in scenes.items():
+        s = make()
+
+        def adaptive(flags, halves):
+            def call(a, b):
+                if halves:
+                    os.environ["PTX_ADAPTIVE_NEE_HALVES"] = "1"
+                try:
+                    return s.render_adaptive_nee(W, H, CAP, BOUNCES, MIN, STEP, thr, a=a, b=b, seed=SEED, want_stats=False, flags=flags)
+                finally:
+                    os.environ.pop("PTX_ADAPTIVE_NEE_HALVES", None)
+            return call
+        variants = {"fused": adaptive(FUSED, False), "fused_two_sequences": adaptive(FUSED, True), "unfused": adaptive(0, False), "unfused_two_sequences": adaptive(0, True)}
+        # (a) alternated: a warm-up of every variant, then `reps` rounds over the variants
+        best, keep = {k: 1e9 for k in variants}, None
+        for rep_i in range(reps + 1):
+            for k, call in variants.items():
+                t, a, b, _ = timed(call)
+                if rep_i:
+                    best[k] = min(best[k], t)
+                if k == "fused":
+                    keep = (a, b)
+        a, b = keep
+        _, _, st = s.render_adaptive_nee(W, H, CAP, BOUNCES, MIN, STEP, thr, a=zeros(W, H), b=zeros(W, H), seed=SEED, flags=FUSED)
+        rounds = st["rounds"]
+        counts = (a[..., 3] + b[..., 3]).cpu().numpy()
+        emit(part="a", scene=name, W=W, H=H, threshold=thr, cap=CAP, rounds=rounds, passes=st["passes"], mean_spp=round(float(counts.mean()), 2),
+             at_min=round(float((counts == MIN).mean()), 4), at_cap=round(float((counts == CAP).mean()), 4), **{k + "_s": round(v, 4) for k, v in best.items()},
+             fused_saved_ms_per_round=round((best["fused_two_sequences"] - best["fused"]) * 1e3 / rounds, 3),
+             unfused_saved_ms_per_round=round((best["unfused_two_sequences"] - best["unfused"]) * 1e3 / rounds, 3), select_ms_per_round=round(st["select_ms"] / rounds, 4))
+        # (b) against the uniform frame at the next even count above the mean
+        acc = zeros(W, H)
+        s.render_nee(W, H, ref_spp, BOUNCES, accum=acc, seed=77, want_stats=False, flags=FUSED)
+        ref = image(ctx.accum_mean(acc))
+        n = 2 * int(counts.mean() // 2) + 2
+        t_uniform, u = 1e9, None
+        for rep_i in range(reps + 1):
+            u = zeros(W, H)
+            t0 = time.perf_counter()
+            s.render_nee(W, H, n, BOUNCES, accum=u, seed=SEED, want_stats=False, flags=FUSED)
+            ctx.synchronize()
+            if rep_i:
+                t_uniform = min(t_uniform, time.perf_counter() - t0)
+        mse_adaptive = mse(image(ctx.accum_mean(a, b)), ref)
+        emit(part="b", scene=name, threshold=thr, mean_spp=round(float(counts.mean()), 2), adaptive_s=round(best["fused"], 4), adaptive_mse=mse_adaptive, uniform_spp=n,
+             uniform_s=round(t_uniform, 4), uniform_mse=mse(image(ctx.accum_mean(u)), ref), ref_spp=ref_spp)
+        # (c) the filter on the adaptive halves, guides over the first MIN samples
+        alb, nd = zeros(W, H), zeros(W, H)
+        t0 = time.perf_counter()
+        s.render_aov(W, H, MIN, albedo=alb, normal_depth=nd, seed=SEED, want_stats=False)
+        ctx.synchronize()
+        t_guides = time.perf_counter() - t0
+        out, filter_ms = zeros(W, H), 1e9
+        for rep_i in range(reps + 1):
+            _, dst = ctx.denoise_counts(a, b, alb, nd, MIN, out=out)
+            if rep_i:
+                filter_ms = min(filter_ms, dst["kernel_ms"])
+        emit(part="c", scene=name, guides_s=round(t_guides, 4), denoise_counts_kernel_ms=round(filter_ms, 3), unfiltered_mse=mse_adaptive, filtered_mse=mse(image(out), ref))
+        s.close()
+    with open(out_path, "w") as fh:
+        fh.write("# tools/bench_adaptive.py --nee: 1920 x 1080, 4 bounces, 8 + 8 per round, cap 64; wall seconds are the smallest of 3 synchronised calls\n")
+        fh.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "payoff":
+    if len(sys.argv) > 1 and sys.argv[1] == "--nee":
+        nee(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "adaptive_nee_bench.txt"), int(sys.argv[3]) if len(sys.argv) > 3 else 1024)
+    elif len(sys.argv) > 1 and sys.argv[1] == "payoff":
         payoff(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     else:
         cost(int(sys.argv[2]) if len(sys.argv) > 2 else 5)
