@@ -121,6 +121,7 @@ class AdaptiveNeeStats(C.Structure):
 NEE_NO_LIGHT_SAMPLES = 1   # ptx_nee_cfg.flags
 NEE_FUSED = 4              # one kernel launch per pass where render() runs the fused kernel; ignored on the queue route
 NEE_ENV_SAMPLES = 16       # the light sample may go towards the environment map; ignored without a map or with a black one
+NEE_SAMPLER_PDF = 64       # MIS weights on the density of LIB's BSDF sampler instead of LIB's pdf value: the frame's expectation is LIB's
 
 
 class KernelTiming(C.Structure):
@@ -562,7 +563,9 @@ class Scene:
         ranges and shards compose the same way. flags: NEE_NO_LIGHT_SAMPLES runs with an empty list (bitwise render()'s frame);
         NEE_FUSED renders each pass with one kernel launch where render() runs its fused kernel (bitwise the unflagged frame; ignored on
         scenes of the queue route); NEE_ENV_SAMPLES lets the light sample go towards the environment map (set_environment), importance-
-        sampled by luminance and MIS-weighted against the map's radiance on a miss (ignored without a map or with a black one).
+        sampled by luminance and MIS-weighted against the map's radiance on a miss (ignored without a map or with a black one);
+        NEE_SAMPLER_PDF builds the MIS weights on the density of LIB's BSDF sampler instead of LIB's pdf value, which removes the shift of
+        the expectation at glossy vertices that see a light (bitwise the unflagged frame when no light sample is possible).
         Returns (accum, stats dict or None)."""
         x0, y0, w, h = tile if tile else (0, 0, W, H)
         if accum is None:

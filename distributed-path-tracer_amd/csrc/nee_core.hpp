@@ -67,6 +67,20 @@ DEV uint32_t env_pick(const float* __restrict__ cdf, uint32_t n, float x) {
 	return a < n - 1 ? a : n - 1;
 }
 
+// ---- the density of LIB's BSDF sampler (PTX_NEE_SAMPLER_PDF; include/ptx.h has the derivation)
+// Solid-angle density with which importance_sample produces direction w at a vertex: the GGX half-vector density D(h) (n.h) / (4 (o.h)) of
+// the specular draw and the cosine density of the diffuse draw, mixed as the draw rnd.y < spec_prob mixes them. roughness is the clamped one
+// importance_sample receives. pdf_specular, LIB's pdf VALUE, is not this density; pdf_diffuse is.
+DEV float sampler_pdf(V3 normal, V3 outcoming, V3 w, float roughness, float spec_prob) {
+	const float a = roughness * roughness, a2 = a * a;
+	const V3 hv = outcoming + w;
+	const V3 h = hv / sqrt_exact(dot(hv, hv));
+	const float nh = dot(normal, h), oh = dot(outcoming, h);
+	const float t = (nh * nh) * (a2 - 1) + 1;
+	const float ps_spec = (nh > 0 && oh > 0) ? (a2 * nh) / ((((float)kPi * t) * t) * (4 * oh)) : 0.0f;
+	return lerpf(pdf_diffuse(normal, w), ps_spec, spec_prob);
+}
+
 // What a vertex leaves besides the path state: whether the path goes on, and its up-to-two shadow requests
 struct NeeVertex {
 	bool alive = false;         // the path continues with (o, d, T, p_prev, depth, pass) as the vertex left them
@@ -83,7 +97,8 @@ struct NeeVertex {
 // light sample taken before the BSDF sample. Returns whether L received a term (the record-based form stores its record then).
 // ENV (PTX_NEE_ENV_SAMPLES with a table, Ev): the light sample may go towards the environment map, and the map's radiance on a miss is weighted
 // against that sample. Without ENV, Ev is not read and the statements are the unflagged estimator's.
-template <bool TEX, bool ALPHA, bool SUN, bool ENV = false>
+// SPDF (PTX_NEE_SAMPLER_PDF): sampler_pdf takes pe's place in the two wl and in p_prev, and nowhere else. Without SPDF no statement changes.
+template <bool TEX, bool ALPHA, bool SUN, bool ENV = false, bool SPDF = false>
 DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t pixel, uint32_t sample, int32_t surf, uint32_t tri, float b1, float b2,
                     float hit_dist, V3& o, V3& d, V3& T, V3& L, float& p_prev, uint32_t& depth, uint32_t& pass, NeeVertex& out) {
 	bool& alive = out.alive;
@@ -208,12 +223,16 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 						const float pe = pmax(pdf, kEps);
 						const V3 qv = brdf / pe;
 						const V3 qc = mk(clampf(qv.x, 0, 1), clampf(qv.y, 0, 1), clampf(qv.z, 0, 1));
-						const float wl = pe / (pe + c_env * p);
-						lx = ((T * qc) * wl) * Le;
-						lo = sf.pos + w * kEps;
-						ld = w;
-						exp_surf = kNeeEnvRay; exp_tri = 0;
-						want_light = true;
+						float pw = pe;
+						if constexpr (SPDF) pw = sampler_pdf(normal, outcoming, w, roughness, spec_prob);
+						if (!SPDF || pw > 0) {   // a direction the BSDF sampler cannot produce carries nothing
+							const float wl = pw / (pw + c_env * p);
+							lx = ((T * qc) * wl) * Le;
+							lo = sf.pos + w * kEps;
+							ld = w;
+							exp_surf = kNeeEnvRay; exp_tri = 0;
+							want_light = true;
+						}
 					}
 				}
 			}
@@ -247,12 +266,16 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 					const V3 qc = mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));
 					float p_l = dist2 / (cg * Lt.area);
 					if constexpr (ENV) p_l = (1 - c_env) * p_l;
-					const float wl = pe / (pe + p_l);
-					lx = ((T * qc) * wl) * Le;
-					lo = sf.pos + w * kEps;
-					ld = w;
-					exp_surf = lt.x; exp_tri = lt.y;
-					want_light = true;
+					float pw = pe;
+					if constexpr (SPDF) pw = sampler_pdf(normal, outcoming, w, roughness, spec_prob);
+					if (!SPDF || pw > 0) {
+						const float wl = pw / (pw + p_l);
+						lx = ((T * qc) * wl) * Le;
+						lo = sf.pos + w * kEps;
+						ld = w;
+						exp_surf = lt.x; exp_tri = lt.y;
+						want_light = true;
+					}
 				}
 			}
 		}
@@ -265,6 +288,10 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 		const V3 q = brdf / pe;
 		T = T * mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));
 		p_prev = pe;
+		if constexpr (SPDF) {
+			const float ps = sampler_pdf(normal, outcoming, inc, roughness, spec_prob);
+			if (ps > 0 && ps < __builtin_inff()) p_prev = ps;
+		}
 		o = sf.pos + inc * kEps;
 		d = normalize(inc);
 		depth++;

@@ -35,7 +35,9 @@ DEV uint32_t wave_sum(uint32_t v) {
 }
 
 // ENV: the variants of PTX_NEE_ENV_SAMPLES (TEX only); Ev, the last argument, is read by them alone.
-template <int MODE, bool TEX, bool ALPHA, bool SUN, bool ENV>
+// SPDF: the variants of PTX_NEE_SAMPLER_PDF. sampler_pdf costs them 0 to 2 VGPRs, and each compiles without scratch at its unflagged
+// twin's workgroup size, so nee_fused_block holds for them too (DESIGN.md 5.7 has their rows).
+template <int MODE, bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false>
 __global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
                                                               const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space,
                                                               NeeEnv Ev) {
@@ -115,7 +117,7 @@ __global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV)) k_nee_fused(De
 			const int32_t surf = hit ? h.surface : -1;
 			const uint32_t tri = hit ? (h.tri & S.tri_id_mask) - S.surfaces[h.surface].tri_base : 0u;
 			NeeVertex v;
-			nee_vertex<TEX, ALPHA, SUN, ENV>(S, P, Lt, Ev, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v);
+			nee_vertex<TEX, ALPHA, SUN, ENV, SPDF>(S, P, Lt, Ev, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v);
 			bool alive = v.alive;
 			// ---------------- the sun ray: occluded = any hit
 			if constexpr (SUN) {
@@ -171,38 +173,56 @@ static hipError_t set_lds(const void* fn, size_t bytes) {
 	return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-template <int MODE, bool TEX, bool ALPHA, bool SUN, bool ENV = false>
+template <int MODE, bool SPDF, bool TEX, bool ALPHA, bool SUN, bool ENV = false>
 static hipError_t launch_nee_fused_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
+	const auto kernel = &k_nee_fused<MODE, TEX, ALPHA, SUN, ENV, SPDF>;
 	if (MODE != MODE_GLOBAL) {
-		hipError_t e = set_lds(reinterpret_cast<const void*>(&k_nee_fused<MODE, TEX, ALPHA, SUN, ENV>), lds_bytes);
+		hipError_t e = set_lds(reinterpret_cast<const void*>(kernel), lds_bytes);
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL((k_nee_fused<MODE, TEX, ALPHA, SUN, ENV>), dim3(grid), dim3(nee_fused_block(TEX, SUN, ENV)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces,
-	                   S.spaces, S.model_space, Ev);
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(nee_fused_block(TEX, SUN, ENV)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces, S.spaces, S.model_space, Ev);
 	return hipGetLastError();
 }
 
 // the variants of launch_nee_shade, per place of the geometry
-template <int MODE>
+template <int MODE, bool SPDF>
 static hipError_t launch_nee_fused_mode(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
 	const bool sun = S.sun.present != 0;
 	if (Ev.row_cdf) {   // a table means a map, and a map means the TEX variants
 		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
-		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, true, true, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, true, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
-		return sun ? launch_nee_fused_variant<MODE, true, false, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, false, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, true, true, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, true, true, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+		return sun ? launch_nee_fused_variant<MODE, SPDF, true, false, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, true, false, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
 	}
 	if (S.any_texture) {
-		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, true, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, true, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
-		return sun ? launch_nee_fused_variant<MODE, true, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, true, false, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, true, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, true, true, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+		return sun ? launch_nee_fused_variant<MODE, SPDF, true, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, true, false, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
 	}
-	if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, false, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, false, true, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
-	return sun ? launch_nee_fused_variant<MODE, false, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, false, false, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+	if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, false, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, false, true, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+	return sun ? launch_nee_fused_variant<MODE, SPDF, false, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, false, false, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
 }
 
-hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream) {
-	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
-	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
-	return launch_nee_fused_mode<MODE_GLOBAL>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+template <bool SPDF>
+static hipError_t launch_nee_fused_all(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream) {
+	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS, SPDF>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID, SPDF>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+	return launch_nee_fused_mode<MODE_GLOBAL, SPDF>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
 }
+
+// This file is compiled twice, so that the two halves of the variants build side by side: as itself (the unflagged variants and
+// launch_nee_fused), and through nee_fused_spdf.hip, which defines PTX_NEE_FUSED_SPDF_TU (the variants of PTX_NEE_SAMPLER_PDF).
+hipError_t launch_nee_fused_sampler_pdf(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
+                                        hipStream_t stream);
+#ifdef PTX_NEE_FUSED_SPDF_TU
+hipError_t launch_nee_fused_sampler_pdf(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
+                                        hipStream_t stream) {
+	return launch_nee_fused_all<true>(S, P, Lt, Ev, B, mode, lds_bytes, grid, stream);
+}
+#else
+// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF
+hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
+                            hipStream_t stream) {
+	return sampler_pdf ? launch_nee_fused_sampler_pdf(S, P, Lt, Ev, B, mode, lds_bytes, grid, stream) : launch_nee_fused_all<false>(S, P, Lt, Ev, B, mode, lds_bytes, grid, stream);
+}
+#endif
 
 }  // namespace ptx

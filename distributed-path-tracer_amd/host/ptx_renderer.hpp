@@ -192,7 +192,7 @@ public:
 	// Radiance sums [H][W][4] of the frame with next-event estimation towards the scene's emissive triangles (ptx_render_nee): render_accum()'s
 	// samples plus one MIS-weighted light sample per continuing vertex; the same expectation, less noise where emitters light the scene.
 	// Write them with encode(sums, sample_count). stats optional; flags: ptx_nee_cfg::flags (PTX_NEE_FUSED: the same frame from one kernel launch per pass;
-	// PTX_NEE_ENV_SAMPLES: the light sample may go towards `environment` too)
+	// PTX_NEE_ENV_SAMPLES: the light sample may go towards `environment` too; PTX_NEE_SAMPLER_PDF: MIS weights on the density of LIB's BSDF sampler)
 	std::vector<float> render_nee(ptx_nee_stats* stats = nullptr, uint32_t flags = 0) const {
 		if (!scene_) throw std::runtime_error("render_nee() before load_gltf()");
 		if (transparent_background) throw std::runtime_error("render_nee: transparent_background's blend is not built on this estimator");

@@ -1,15 +1,17 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
 //       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
 //       --nee:         light sampling towards the scene's emissive triangles (renderer::render_nee)
 //       --nee-fused:   --nee with one kernel launch per pass (PTX_NEE_FUSED): the same frame; ignored on scenes of the queue pipeline
 //       --nee-env MAP: --nee under the environment map MAP (renderer::environment; PNG, JPEG or Radiance .hdr), the light sample going
 //                      towards the map too (PTX_NEE_ENV_SAMPLES); combines with --nee-fused
+//       --nee-sampler-pdf: --nee with the MIS weights built on the density of the BSDF sampler (PTX_NEE_SAMPLER_PDF): the frame's expectation
+//                      is the plain renderer's at glossy vertices too; combines with --nee-fused, --nee-env and --adaptive
 //       --adaptive THR[:MIN[:STEP]]: noise-driven per-pixel sample counts (renderer::render_adaptive) with spp as the cap: every pixel gets MIN
 //                      samples (8), then rounds of STEP (MIN) go to the pixels whose half-frames still disagree by more than THR
-//       combinations:  --adaptive with --nee / --nee-fused / --nee-env renders the adaptive loop on the light-sampling estimator
+//       combinations:  --adaptive with --nee / --nee-fused / --nee-env / --nee-sampler-pdf renders the adaptive loop on the light-sampling estimator
 //                      (renderer::render_adaptive_nee); --adaptive --denoise, with or without --nee*, filters the adaptive frame
 //                      (ptx_denoise_counts on the guides of the first MIN samples); --nee* --denoise filters two light-sampled half-frames
 //                      (renderer::render_nee_denoised). --transparent combines with none of them
@@ -41,7 +43,7 @@ static void write_png(const std::string& path, const std::vector<uint8_t>& rgba,
 }
 
 int main(int argc, char** argv) {
-	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false;
+	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false, nee_sampler_pdf = false;
 	float ad_thr = 0.1f;
 	unsigned ad_min = 8, ad_step = 0;
 	std::string aov_prefix, nee_env;
@@ -50,6 +52,7 @@ int main(int argc, char** argv) {
 		else if (argc > 1 && std::string(argv[1]) == "--denoise") { denoise = true; argv[1] = argv[0]; argv++; argc--; }
 		else if (argc > 1 && std::string(argv[1]) == "--nee") { nee = true; argv[1] = argv[0]; argv++; argc--; }   // renderer::render_nee: light sampling
 		else if (argc > 1 && std::string(argv[1]) == "--nee-fused") { nee = nee_fused = true; argv[1] = argv[0]; argv++; argc--; }   // ... one launch per pass
+		else if (argc > 1 && std::string(argv[1]) == "--nee-sampler-pdf") { nee = nee_sampler_pdf = true; argv[1] = argv[0]; argv++; argc--; }   // ... weights on the sampler's density
 		else if (argc > 2 && std::string(argv[1]) == "--nee-env") { nee = true; nee_env = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }   // ... the map as a light
 		else if (argc > 2 && std::string(argv[1]) == "--adaptive") {
 			if (std::sscanf(argv[2], "%f:%u:%u", &ad_thr, &ad_min, &ad_step) < 1) { std::fprintf(stderr, "error: --adaptive THR[:MIN[:STEP]]\n"); return 1; }
@@ -59,7 +62,7 @@ int main(int argc, char** argv) {
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (argc == 5 && std::string(argv[1]) == "--event") {
@@ -105,7 +108,7 @@ int main(int argc, char** argv) {
 		r.adaptive_threshold = ad_thr; r.adaptive_min = ad_min; r.adaptive_step = ad_step;
 		ptx_nee_stats nst{};
 		if (transparent && (nee || adaptive || denoise)) throw std::runtime_error("--transparent does not combine with --nee, --adaptive or --denoise");
-		const uint32_t nee_flags = (nee_fused ? PTX_NEE_FUSED : 0u) | (nee_env.empty() ? 0u : PTX_NEE_ENV_SAMPLES);
+		const uint32_t nee_flags = (nee_fused ? PTX_NEE_FUSED : 0u) | (nee_env.empty() ? 0u : PTX_NEE_ENV_SAMPLES) | (nee_sampler_pdf ? PTX_NEE_SAMPLER_PDF : 0u);
 		std::vector<uint8_t> png;
 		if (nee && adaptive) {
 			png = r.encode(r.render_adaptive_nee(&anst, nee_flags, denoise, &dst), 1);

@@ -428,10 +428,10 @@ int ptx_accum_mean(ptx_ctx* ctx, const float* accum_a, const float* accum_b /* N
 #define PTX_NEE_FUSED 4u
 /* PTX_NEE_ENV_SAMPLES: the light sample of a vertex may go towards the environment map (ptx_scene_set_environment), importance-sampled by
  * luminance; the map's radiance collected on a miss is weighted against that sample, so the expectation of the frame is still LIB's
- * (as far as LIB's pdf is the density of LIB's sampler, which its specular lobe's is not: DESIGN.md 5.7 has the measured shift).
+ * (as far as LIB's pdf is the density of LIB's sampler, which its specular lobe's is not: DESIGN.md 5.7 has the measured shift, PTX_NEE_SAMPLER_PDF below removes it).
  * Ignored when the scene has no map or the map is black: the call is then bit for bit the one without the flag. Combines with
  * PTX_NEE_FUSED (bitwise the same frame; ignored on the queue route as above) and with PTX_NEE_NO_LIGHT_SAMPLES, which empties the
- * triangle list only. Values 2u and 8u are unassigned and refused as unknown.
+ * triangle list only. Values 2u, 8u and 32u are unassigned and refused as unknown.
  *   THE ENVIRONMENT TABLE (PTX_ARR_ENV_*), for a map of w x h texels, built on the host in float64 and stored as float32. Box (i, j) is
  *     u in [i / w, (i + 1) / w), 1 - v in [j / h, (j + 1) / h) of the miss lookup u = atan2f(d.z, d.x) * 0.1591F + 0.5F,
  *     v = asinf(d.y) * 0.3183F + 0.5F. lum(i, j) = 0.2126 r + 0.7152 g + 0.0722 b of the texel as the kernels read it (sRGB table, missing
@@ -457,6 +457,32 @@ int ptx_accum_mean(ptx_ctx* ctx, const float* accum_a, const float* accum_b /* N
  *   MISS WEIGHT. L += (T * env) * wm. wm = 1 (no arithmetic) when depth == 0 or pass > 0; otherwise wm = p_prev / (p_prev + c_env * env_pdf(d)).
  * Order of the additions and the stats are unchanged: light_samples and light_visible count both kinds of light ray. */
 #define PTX_NEE_ENV_SAMPLES 16u
+/* PTX_NEE_SAMPLER_PDF: the MIS weights are built on the density of LIB's BSDF SAMPLER instead of pe, LIB's pdf VALUE. The two differ in the
+ * specular lobe: importance_ggx draws a half vector h with cos_theta = sqrt((1 - u) / (1 + (a2 - 1) u)), a2 = roughness^4, a uniform azimuth,
+ * and returns reflect(-o, h), so the density of its direction w is D(h) (n.h) / (4 (o.h)) with D = a2 / (pi ((n.h)^2 (a2 - 1) + 1)^2), which
+ * LIB's pdf_specular is not (E[cos / pdf_specular] over the sampler's directions is 2.9 to 62 where pi is expected). The
+ * diffuse draw is exactly cosine-weighted, so pdf_diffuse is its density. With weights on pe the two techniques do not sum to LIB's integrand
+ * wherever a glossy vertex sees a light; with this flag they do, and the expectation of the frame is LIB's.
+ *   THE DENSITY ps(w) of a vertex, from its own normal, outcoming, spec_prob and the roughness importance_sample receives (after
+ *     max(roughness, 0.05F)), IEEE binary32, each operation rounded on its own:
+ *       a = roughness * roughness;  a2 = a * a
+ *       hv = outcoming + w;  h = hv / sqrt(dot(hv, hv))
+ *       nh = dot(normal, h);  oh = dot(outcoming, h)
+ *       t = (nh * nh) * (a2 - 1) + 1
+ *       ps_spec = (nh > 0 && oh > 0) ? (a2 * nh) / ((((float)pi * t) * t) * (4 * oh)) : 0
+ *       ps_diff = pdf_diffuse(normal, w), the value eval_brdf uses
+ *       ps = lerpf(ps_diff, ps_spec, spec_prob), the mixture the draw rnd.y < spec_prob realises
+ *   ps takes pe's place in the weights and only there:
+ *     p_prev = ps(inc) after the BSDF sample; if that is not a positive finite number, p_prev = pe as without the flag.
+ *     wl = ps / (ps + p_l') for the triangle sample and for the environment sample, p_l' being p_l, (1 - c_env) * p_l or c_env * p as above.
+ *     A light sample with !(ps > 0) contributes nothing and traces no shadow ray (and is not counted in light_samples).
+ *     qc, the T update, the sun term, the draws, their Philox blocks and the order of the additions are unchanged; the emission weight and
+ *     the miss weight keep their formulas and read the new p_prev.
+ *   The sum of the two techniques is then the integral of ps * qc * Le, which is what LIB's vertex integrates.
+ * Combines with PTX_NEE_FUSED (bitwise the same frame; ignored on the queue route as above), with PTX_NEE_ENV_SAMPLES and with
+ * PTX_NEE_NO_LIGHT_SAMPLES; ptx_render_adaptive_nee passes it through. With no light sample possible (empty list and no environment table)
+ * every weight is exactly 1 and the call is bit for bit the one without the flag. Without the flag nothing changes. */
+#define PTX_NEE_SAMPLER_PDF 64u
 typedef struct ptx_nee_cfg { uint32_t flags; } ptx_nee_cfg;
 typedef struct ptx_nee_stats {
 	ptx_render_stats render;   /* rays = closest-hit + shadow queries */

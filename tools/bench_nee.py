@@ -17,6 +17,14 @@
                                         written bytes against the product's ref_spp ptx_render frame (1024) of another seed: at equal
                                         samples, and the unflagged call at the spp that takes the flagged call's time; and the flagged call
                                         fused against unfused (time, bitwise). Also writes the lines to profiles/nee_env_bench.txt.
+  tools/bench_nee.py --sampler-pdf [ref_spp] [reps]
+                                        PTX_NEE_SAMPLER_PDF against the same call without it, on Cornell at 1920 x 1080 (triangle list) and on the
+                                        --env scene at 960 x 540 (both with PTX_NEE_ENV_SAMPLES), 8 bounces, 16 and 64 spp, in both forms (with and
+                                        without PTX_NEE_FUSED): the four calls alternate in one process, each kept at the smallest of `reps`
+                                        synchronised calls after a warm-up; the time ratio flagged / unflagged, the mean squared error of the
+                                        written bytes of each against the product's ref_spp ptx_render frame of another seed, and the ratio of
+                                        each frame's mean linear radiance (R, G, B) to that frame's. Also writes the lines to
+                                        profiles/nee_sampler_pdf_bench.txt.
 Prints one JSON line per measurement. A scene without listed emitters (atrium) shows the cost of the wavefront form alone.
 """
 import importlib
@@ -183,7 +191,61 @@ def main_env(ref_spp, reps):
         f.write("tools/bench_nee.py --env: PTX_NEE_ENV_SAMPLES against the unflagged ptx_render_nee (both PTX_NEE_FUSED), MI355X\n" + "\n".join(lines) + "\n")
 
 
+def main_sampler_pdf(ref_spp, reps):
+    import tempfile
+    global W, H
+    ctx = ptx.Context(0)
+    lines = []
+    with tempfile.TemporaryDirectory() as tmp:
+        sun_map = sun_disc_map(os.path.join(tmp, "sun_disc.hdr"))
+        cases = [("cornell", 1920, 1080, 0, lambda: ptx.Scene.load_gltf(ctx, CORNELL), None),
+                 ("plaza3_opaque_nosun", 960, 540, ptx.NEE_ENV_SAMPLES, lambda: ptx.Scene.from_arrays(ctx, *[proc.plaza_scene(alpha=False, sun=False)[k] for k in KEYS]), sun_map)]
+        for name, W, H, base, make, env_map in cases:
+            s = make()
+            if env_map:
+                s.set_environment(env_map, srgb=False)
+            ref_acc = zeros()
+            s.render(W, H, ref_spp, BOUNCES, accum=ref_acc, seed=REF_SEED, want_stats=False)
+            ctx.synchronize()
+            ref = ctx.tonemap_encode(ref_acc, W, H, ref_spp)[..., :3].astype(np.float64) / 255
+            ref_mean = ref_acc.cpu().numpy()[..., :3].astype(np.float64).reshape(-1, 3).mean(0) / ref_spp
+            del ref_acc
+            forms = {"unfused": base, "unfused_spdf": base | ptx.NEE_SAMPLER_PDF, "fused": base | ptx.NEE_FUSED, "fused_spdf": base | ptx.NEE_FUSED | ptx.NEE_SAMPLER_PDF}
+            for spp in (16, 64):
+                best = {k: 1e30 for k in forms}
+                acc, st, launches = {}, {}, {}
+                for rep in range(reps + 1):
+                    for k, flags in forms.items():   # the four calls alternate
+                        a = zeros()
+                        t0 = time.perf_counter()
+                        _, st[k] = s.render_nee(W, H, spp, BOUNCES, accum=a, seed=SEED, flags=flags)
+                        ctx.synchronize()
+                        dt = time.perf_counter() - t0
+                        if rep:
+                            best[k] = min(best[k], dt)
+                        acc[k], launches[k] = a, ctx.timing()["fused_launches"]
+                out = dict(scene=name, W=W, H=H, bounces=BOUNCES, spp=spp, n_lights=st["fused"]["n_lights"], base_flags=base, ref_spp=ref_spp,
+                           fused_launches=launches["fused_spdf"], spdf_fused_bitwise_unfused=bool((acc["fused_spdf"] == acc["unfused_spdf"]).all()))
+                for k in forms:
+                    img = ctx.tonemap_encode(acc[k], W, H, spp)[..., :3].astype(np.float64) / 255
+                    mean = acc[k].cpu().numpy()[..., :3].astype(np.float64).reshape(-1, 3).mean(0) / spp
+                    out[k + "_s"] = round(best[k], 4)
+                    out[k + "_mse"] = float(np.mean((img - ref) ** 2))
+                    out[k + "_mean_ratio_rgb"] = [round(float(x), 5) for x in mean / ref_mean]
+                    out[k + "_light_samples"] = st[k]["light_samples"]
+                out["fused_time_ratio_spdf"] = round(best["fused_spdf"] / best["fused"], 4)
+                out["unfused_time_ratio_spdf"] = round(best["unfused_spdf"] / best["unfused"], 4)
+                lines.append(json.dumps(out))
+                print(lines[-1], flush=True)
+            s.close()
+    with open(os.path.join(ROOT, "profiles", "nee_sampler_pdf_bench.txt"), "w") as f:
+        f.write("tools/bench_nee.py --sampler-pdf: PTX_NEE_SAMPLER_PDF against the same ptx_render_nee call without it, fused and unfused, MI355X\n" + "\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--sampler-pdf":
+        main_sampler_pdf(int(sys.argv[2]) if len(sys.argv) > 2 else 1024, int(sys.argv[3]) if len(sys.argv) > 3 else 3)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--env":
         main_env(int(sys.argv[2]) if len(sys.argv) > 2 else 1024, int(sys.argv[3]) if len(sys.argv) > 3 else 3)
         sys.exit(0)
