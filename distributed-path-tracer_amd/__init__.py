@@ -139,6 +139,9 @@ class Hits(C.Structure):
                                           "nx", "ny", "nz", "u", "v")]
 
 
+MASK_EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)   # ptx_mask_exchange_fn(user, mask, n_bytes) -> status
+
+
 _lib = None
 _live = weakref.WeakSet()   # scenes and contexts still open; closed before interpreter teardown (atexit)
                             # so that no HIP call is made after the HIP runtime's own static destructors ran
@@ -214,6 +217,8 @@ def lib():
         L.ptx_denoise_counts.argtypes = [C.c_void_p, C.POINTER(DenoiseCountsCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p, C.POINTER(DenoiseStats)]
         L.ptx_adaptive_select.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.ptx_accum_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.ptx_ctx_set_mask_exchange.argtypes = [C.c_void_p, MASK_EXCHANGE_FN, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.ptx_ctx_get_mask_exchange_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.ptx_intersect_batch.argtypes = [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(Hits)]
         L.ptx_tonemap_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ptx_pbr_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -382,10 +387,44 @@ class Context:
         _check(lib().ptx_accum_mean(self.h, _ptr(a), _ptr(b), n, _ptr(out)))
         return out
 
+    def set_mask_exchange(self, exchange, mask=None):
+        """ptx_ctx_set_mask_exchange: the merge of the noisy bytes over the ranks that Scene.render_adaptive / render_adaptive_nee with
+        shard=(index, count > 1, ...) need (include/ptx.h has the sharded loop). exchange(mask, n_bytes) is called once per round after the
+        library wrote this rank's bytes into `mask` (a uint8 numpy array or torch-on-GPU tensor of at least w * h elements, kept alive here)
+        and synchronised its stream; it returns when `mask` holds the element-wise MAX over the ranks, and returns None / 0 for success or a
+        non-zero int. An exception inside it counts as a failure (status -1; it is kept in `mask_exchange_error`). It must not call this
+        context. None clears the registration."""
+        if exchange is None:
+            _check(lib().ptx_ctx_set_mask_exchange(self.h, MASK_EXCHANGE_FN(), None, None, 0))
+            self._mask_exchange = None
+            return
+        if mask is None:
+            raise PtxError(ERR_INVALID, "set_mask_exchange: a callback needs a mask buffer")
+        self.mask_exchange_error = None
+
+        def thunk(_user, _mask, n_bytes):
+            try:
+                return int(exchange(mask, n_bytes) or 0)
+            except BaseException as e:   # ctypes would swallow it: the render call fails instead
+                self.mask_exchange_error = e
+                return -1
+
+        fn = MASK_EXCHANGE_FN(thunk)
+        n = int(mask.numel()) if hasattr(mask, "numel") else int(mask.size)
+        _check(lib().ptx_ctx_set_mask_exchange(self.h, fn, None, _ptr(mask), n))
+        self._mask_exchange = (fn, mask)   # the CFUNCTYPE object and the buffer live as long as the registration
+
+    def mask_exchange_stats(self):
+        """ptx_ctx_get_mask_exchange_stats: {"calls", "wall_ms"} of the exchange in this context's last adaptive call."""
+        calls, ms = C.c_uint64(), C.c_double()
+        _check(lib().ptx_ctx_get_mask_exchange_stats(self.h, C.byref(calls), C.byref(ms)))
+        return {"calls": calls.value, "wall_ms": ms.value}
+
     def close(self):
         if getattr(self, "h", None):
             lib().ptx_ctx_destroy(self.h)
             self.h = None
+            self._mask_exchange = None
 
     def __del__(self):
         try:
@@ -543,6 +582,7 @@ class Scene:
         step_spp (0 = min_spp) go to the pixels whose two halves still disagree by more than `threshold` (include/ptx.h has the rule).
         ADDS radiance SUMS into the half-buffers a and b ([h,w,4] float32, numpy or torch-on-GPU, both of one kind; None = zeros): a
         pixel's count is a[..., 3] + b[..., 3]. The frame: Context.accum_mean(a, b), then tonemap_encode(..., spp=1). Always synchronises.
+        shard=(index, count > 1[, tile]) needs Context.set_mask_exchange: the ranks' zeroed buffers then sum to the unsharded frame, bit for bit.
         Returns (a, b, stats dict or None)."""
         x0, y0, w, h = tile if tile else (0, 0, W, H)
         if a is None and b is None:

@@ -3,6 +3,8 @@
 #include <dlfcn.h>
 #include <zlib.h>
 
+#include <chrono>
+
 #include "api_internal.hpp"
 
 namespace {
@@ -94,26 +96,109 @@ int ptx_denoise_counts(ptx_ctx* c, const ptx_denoise_counts_cfg* cfg, const floa
 	                     guides, out_rgba, stats);
 }
 
-int adaptive_decide_locked(ptx_ctx* c, uint32_t w, uint32_t h, const float4* d_a, const float4* d_b, float threshold, uint8_t* d_done, uint32_t* d_pixels, uint32_t& n_active,
-                           double* select_ms) {
+namespace {
+
+// the decision's workspace on the context, laid out for a w x h rectangle; tile_count_all: the sharded decision's second count per tile
+int adaptive_workspace(ptx_ctx* c, uint32_t w, uint32_t h, AdaptiveBuffers& B, uint32_t*& tile_count_all) {
 	const size_t n = (size_t)w * h, tiles = (size_t)((w + kAdTile - 1) / kAdTile) * ((h + kAdTile - 1) / kAdTile), blocks = tiles * kAdBlocksPerTile;
 	const size_t o_mask = pad16(n), o_boff = o_mask + blocks * 8, o_tcnt = o_boff + blocks * 4, o_toff = o_tcnt + pad16(tiles * 4), o_cnt = o_toff + pad16(tiles * 4);
-	HIP_TRY(c->adaptive.ensure(o_cnt + 16));
+	const size_t o_tall = o_cnt + 16;
+	HIP_TRY(c->adaptive.ensure(o_tall + pad16(tiles * 4)));
 	char* const ws = (char*)c->adaptive.p;
-	const AdaptiveBuffers B{(uint8_t*)ws, (unsigned long long*)(ws + o_mask), (uint32_t*)(ws + o_boff), (uint32_t*)(ws + o_tcnt), (uint32_t*)(ws + o_toff), (uint32_t*)(ws + o_cnt)};
+	B = AdaptiveBuffers{(uint8_t*)ws, (unsigned long long*)(ws + o_mask), (uint32_t*)(ws + o_boff), (uint32_t*)(ws + o_tcnt), (uint32_t*)(ws + o_toff), (uint32_t*)(ws + o_cnt)};
+	tile_count_all = (uint32_t*)(ws + o_tall);
+	return PTX_OK;
+}
+
+int adaptive_events(ptx_ctx* c) {
+	for (hipEvent_t& ev : c->adaptive_ev)
+		if (!ev) HIP_TRY(hipEventCreate(&ev));
+	return PTX_OK;
+}
+
+// adds the time between the two events to *select_ms; the stream is synchronised
+int adaptive_elapsed(ptx_ctx* c, double* select_ms) {
+	float t = 0;
+	HIP_TRY(hipEventElapsedTime(&t, c->adaptive_ev[0], c->adaptive_ev[1]));
+	*select_ms += t;
+	return PTX_OK;
+}
+
+}  // namespace
+
+int adaptive_decide_locked(ptx_ctx* c, uint32_t w, uint32_t h, const float4* d_a, const float4* d_b, float threshold, uint8_t* d_done, uint32_t* d_pixels, uint32_t& n_active,
+                           double* select_ms) {
+	AdaptiveBuffers B{};
+	uint32_t* unused = nullptr;
+	if (const int rc = adaptive_workspace(c, w, h, B, unused); rc != PTX_OK) return rc;
 	if (select_ms)
-		for (hipEvent_t& ev : c->adaptive_ev)
-			if (!ev) HIP_TRY(hipEventCreate(&ev));
+		if (const int rc = adaptive_events(c); rc != PTX_OK) return rc;
 	if (select_ms) HIP_TRY(hipEventRecord(c->adaptive_ev[0], c->stream));
 	HIP_TRY(launch_adaptive_select(d_a, d_b, w, h, threshold, B, d_done, d_pixels, c->stream));
 	if (select_ms) HIP_TRY(hipEventRecord(c->adaptive_ev[1], c->stream));
 	HIP_TRY(hipMemcpyAsync(&n_active, B.n_active, 4, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (select_ms) {
-		float t = 0;
-		HIP_TRY(hipEventElapsedTime(&t, c->adaptive_ev[0], c->adaptive_ev[1]));
-		*select_ms += t;
+	if (select_ms) return adaptive_elapsed(c, select_ms);
+	return PTX_OK;
+}
+
+int adaptive_decide_sharded_locked(ptx_ctx* c, uint32_t w, uint32_t h, const AdaptiveShard& shard, bool mask_on_device, const float4* d_a, const float4* d_b, float threshold,
+                                   uint8_t* d_done, uint32_t* d_pixels, uint32_t& n_own, uint32_t& n_all, double* select_ms, bool& exchange_failed) {
+	exchange_failed = false;
+	ptx_ctx::MaskExchange& X = c->mask_exchange;
+	const size_t n = (size_t)w * h;
+	AdaptiveBuffers B{};
+	uint32_t* tile_count_all = nullptr;
+	if (const int rc = adaptive_workspace(c, w, h, B, tile_count_all); rc != PTX_OK) return rc;
+	if (select_ms)
+		if (const int rc = adaptive_events(c); rc != PTX_OK) return rc;
+	// a device mask is written and read where the caller keeps it; a host one goes through the workspace's noisy bytes
+	uint8_t* const d_mask = mask_on_device ? X.mask : B.noisy;
+	if (select_ms) HIP_TRY(hipEventRecord(c->adaptive_ev[0], c->stream));
+	HIP_TRY(launch_adaptive_noisy_shard(d_a, d_b, w, h, threshold, shard, d_mask, c->stream));
+	if (select_ms) HIP_TRY(hipEventRecord(c->adaptive_ev[1], c->stream));
+	if (!mask_on_device) HIP_TRY(hipMemcpyAsync(X.mask, d_mask, n, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (select_ms)
+		if (const int rc = adaptive_elapsed(c, select_ms); rc != PTX_OK) return rc;
+	const auto t0 = std::chrono::steady_clock::now();
+	const int status = X.fn(X.user, X.mask, n);
+	X.wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	X.calls++;
+	if (status != 0) {
+		exchange_failed = true;
+		return set_err(PTX_ERR_HIP, "mask exchange failed (status " + std::to_string(status) + ")");
 	}
+	if (!mask_on_device) HIP_TRY(hipMemcpyAsync(d_mask, X.mask, n, hipMemcpyHostToDevice, c->stream));
+	if (select_ms) HIP_TRY(hipEventRecord(c->adaptive_ev[0], c->stream));
+	HIP_TRY(launch_adaptive_decide_shard(d_mask, w, h, shard, B, tile_count_all, d_done, d_pixels, c->stream));
+	if (select_ms) HIP_TRY(hipEventRecord(c->adaptive_ev[1], c->stream));
+	uint32_t counts[2] = {0, 0};
+	HIP_TRY(hipMemcpyAsync(counts, B.n_active, 8, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	n_own = counts[0];
+	n_all = counts[1];
+	if (select_ms) return adaptive_elapsed(c, select_ms);
+	return PTX_OK;
+}
+
+int ptx_ctx_set_mask_exchange(ptx_ctx* c, ptx_mask_exchange_fn fn, void* user, uint8_t* mask, size_t mask_bytes) {
+	if (!c) return set_err(PTX_ERR_INVALID, "ptx_ctx_set_mask_exchange: NULL context");
+	if (fn && !mask) return set_err(PTX_ERR_INVALID, "ptx_ctx_set_mask_exchange: a callback needs a mask buffer");
+	std::lock_guard<std::mutex> lk(c->mu);
+	ptx_ctx::MaskExchange& X = c->mask_exchange;
+	X.fn = fn;
+	X.user = fn ? user : nullptr;
+	X.mask = fn ? mask : nullptr;
+	X.bytes = fn ? mask_bytes : 0;
+	return PTX_OK;
+}
+
+int ptx_ctx_get_mask_exchange_stats(ptx_ctx* c, uint64_t* calls, double* wall_ms) {
+	if (!c) return set_err(PTX_ERR_INVALID, "ptx_ctx_get_mask_exchange_stats: NULL context");
+	std::lock_guard<std::mutex> lk(c->mu);
+	if (calls) *calls = c->mask_exchange.calls;
+	if (wall_ms) *wall_ms = c->mask_exchange.wall_ms;
 	return PTX_OK;
 }
 

@@ -64,6 +64,15 @@ struct ptx_ctx {
 	// offsets, the count word), the loop's `done` bytes and active list, and the staging of host buffers
 	DevBuf adaptive, adaptive_state, adaptive_stage;
 	hipEvent_t adaptive_ev[2] = {nullptr, nullptr};   // around the decision kernels (select_ms)
+	// ptx_ctx_set_mask_exchange: the caller's merge of the noisy bytes over the ranks of a sharded adaptive call, and its buffer
+	struct MaskExchange {
+		ptx_mask_exchange_fn fn = nullptr;
+		void* user = nullptr;
+		uint8_t* mask = nullptr;
+		size_t bytes = 0;
+		uint64_t calls = 0;    // of the last adaptive call (ptx_ctx_get_mask_exchange_stats)
+		double wall_ms = 0;
+	} mask_exchange;
 	// workspace of the queue-based pipeline (wavefront.hip): ptx_render and ptx_intersect_batch run it on the context's stream
 	struct WfSet {
 		DevBuf qent, pair_hit, seg, first, mask, ctl, spill, stream_buf, flow;
@@ -121,6 +130,13 @@ void srgb_thresholds(float thr[256]);                      // ptx_api.cpp
 // context's mutex. select_ms: nullptr, or where the HIP-event time of the decision kernels is added.
 int adaptive_decide_locked(ptx_ctx* c, uint32_t w, uint32_t h, const float4* d_a, const float4* d_b, float threshold, uint8_t* d_done, uint32_t* d_pixels, uint32_t& n_active,
                            double* select_ms);
+// The same for a rank of a sharded call: the noisy bytes of its own pixels -> the registered exchange (c->mask_exchange; the stream is
+// synchronised before the callback) -> the decision of the whole rectangle from the merged mask. d_pixels receives the rank's own active
+// pixels, n_own their number, n_all the number of all active pixels of the rectangle: 8 bytes read back with one more synchronisation.
+// mask_on_device: what the caller's mask buffer is; a host one is copied out of and back into the workspace. A callback that returns
+// non-zero ends the decision with PTX_ERR_HIP and `exchange_failed` set.
+int adaptive_decide_sharded_locked(ptx_ctx* c, uint32_t w, uint32_t h, const AdaptiveShard& shard, bool mask_on_device, const float4* d_a, const float4* d_b, float threshold,
+                                   uint8_t* d_done, uint32_t* d_pixels, uint32_t& n_own, uint32_t& n_all, double* select_ms, bool& exchange_failed);
 
 // A caller's buffer as the kernels take it. Device memory is used where it is. Host memory is staged at `off` in `buf` — copied in on
 // the context's stream unless the buffer is output-only — and copy_back() queues the copy out; the entry point synchronises once, after

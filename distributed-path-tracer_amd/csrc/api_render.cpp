@@ -914,24 +914,42 @@ int adaptive_args(const char* who, const void* sc, const ptx_render_cfg* cfg, co
 	return PTX_OK;
 }
 
-}  // namespace
+// The refusal of shard_count > 1 on a scene without a context, where no exchange can be registered; with one the registration is looked at
+// under its lock (adaptive_loop).
+std::string no_exchange(const char* who) {
+	return std::string(who) + ": shard_count > 1 needs a mask exchange (the 3 x 3 block of the decision reads the noisy bytes of pixels that other shards own): register one "
+	       "with ptx_ctx_set_mask_exchange, and the shards' buffers sum to the unsharded frame bit for bit, which rectangles decided on their own do not";
+}
 
-int ptx_render_adaptive(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_adaptive_cfg* acfg, float* accum_a, float* accum_b, ptx_adaptive_stats* stats) {
-	// every refusal below is decided before any device work
-	uint32_t x0, y0, w, h, step;
-	if (const int rc = adaptive_args("ptx_render_adaptive", sc, cfg, acfg, accum_a, accum_b, x0, y0, w, h, step); rc != PTX_OK) return rc;
-	if (cfg->shard_count > 1)
-		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_adaptive: shard_count > 1 is not supported (the 3 x 3 block of the decision would need other shards' pixels); "
-		                                    "split a frame over GPUs by rectangles instead");
-	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_adaptive: scene was created without a GPU context (no CPU path exists)");
-	const bool dev = is_device_ptr(accum_a);
-	if (is_device_ptr(accum_b) != dev) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: accum_a and accum_b must both be device or both be host memory");
+struct AdaptiveRun {
+	uint32_t rounds = 0, active_last = 0;
+	double select_ms = 0;
+};
+
+// What ptx_render_adaptive and ptx_render_adaptive_nee share: the half-buffers staged once, the `done` bytes and the active list, the round
+// sizes, the decision after every round, the sharded form of it, the copy back. render_round(round_cfg, given, k, subset, d_a, d_b) adds
+// the samples [sample0 + given, sample0 + given + k) of the subset's pixels (nullptr: pixel_list()'s, which honours shard_*) to the two
+// halves; round_cfg holds the validated rectangle. The caller holds the context's mutex; the device is set here, after the last refusal.
+template <class RenderRound>
+int adaptive_loop(ptx_scene* sc, const char* who, const ptx_render_cfg* cfg, const ptx_adaptive_cfg* acfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t step,
+                  float* accum_a, float* accum_b, bool dev, bool want_ms, RenderRound&& render_round, AdaptiveRun& run) {
 	ptx_ctx* c = sc->ctx;
-	std::lock_guard<std::mutex> lk(c->mu);
-	HIP_TRY(hipSetDevice(c->device));
-	if (stats) *stats = ptx_adaptive_stats{};
-
 	const size_t n = (size_t)w * h, bytes = n * sizeof(float4);
+	ptx_ctx::MaskExchange& X = c->mask_exchange;
+	const bool sharded = cfg->shard_count > 1;
+	AdaptiveShard shard{};
+	if (sharded) {
+		if (!X.fn) return set_err(PTX_ERR_UNSUPPORTED, no_exchange(who));
+		if (X.bytes < n) return set_err(PTX_ERR_INVALID, std::string(who) + ": the mask of ptx_ctx_set_mask_exchange is smaller than w * h bytes of the rectangle");
+		const uint32_t ts = cfg->shard_tile ? cfg->shard_tile : 64u;
+		shard = AdaptiveShard{x0, y0, ts, (cfg->W + ts - 1) / ts, cfg->shard_index, cfg->shard_count};
+		if ((uint64_t)shard.tiles_x * ((cfg->H + ts - 1) / ts) > 0xFFFFFFFFull) return set_err(PTX_ERR_INVALID, std::string(who) + ": more than 2^32 - 1 shard tiles in the image");
+	}
+	X.calls = 0;
+	X.wall_ms = 0;
+	HIP_TRY(hipSetDevice(c->device));
+	const bool mask_on_device = sharded && is_device_ptr(X.mask);
+
 	Staged s_a, s_b;   // staged once for the whole call, both in one buffer
 	if (!dev) HIP_TRY(c->adaptive_stage.ensure(2 * bytes));
 	HIP_TRY(s_a.bind(c, dev, accum_a, bytes, c->adaptive_stage));
@@ -942,36 +960,77 @@ int ptx_render_adaptive(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_adap
 	uint8_t* const d_done = (uint8_t*)c->adaptive_state.p + n * 4;
 	HIP_TRY(hipMemsetAsync(d_done, 0, n, c->stream));
 
-	ptx_render_cfg half = *cfg;
-	half.x0 = x0; half.y0 = y0; half.w = w; half.h = h;
+	ptx_render_cfg round = *cfg;
+	round.x0 = x0; round.y0 = y0; round.w = w; round.h = h;
 	PixelSubset active{d_list, 0};
-	uint32_t given = 0, rounds = 0, n_active = 0;
-	double select_ms = 0;
+	uint32_t given = 0, n_active = 0, n_all = 0;
 	while (given < cfg->spp) {
-		const uint32_t k = rounds == 0 ? acfg->min_spp : std::min(step, cfg->spp - given);
-		float4* const target[2] = {d_a, d_b};
-		for (uint32_t part = 0; part < 2; part++) {   // the first half of the round's samples into A, the second into B
-			half.sample0 = cfg->sample0 + given + part * (k / 2);
-			half.spp = k / 2;
-			ptx_render_stats st{};
-			if (const int rc = render_frame_locked(sc, &half, "ptx_render_adaptive", (float*)target[part], nullptr, stats ? &st : nullptr, rounds == 0 ? nullptr : &active); rc != PTX_OK) return rc;
-			if (stats) {
-				stats->render.rays += st.rays; stats->render.samples += st.samples; stats->render.passes += st.passes; stats->render.kernel_ms += st.kernel_ms;
-			}
-		}
+		const uint32_t k = run.rounds == 0 ? acfg->min_spp : std::min(step, cfg->spp - given);   // even: min_spp, step_spp and the cap are
+		// a rank that owns no active pixel renders nothing in this round and still takes part in the exchange
+		if (run.rounds == 0 || active.n_pixels)
+			if (const int rc = render_round(round, given, k, run.rounds == 0 ? nullptr : &active, d_a, d_b); rc != PTX_OK) return rc;
 		given += k;
-		rounds++;
-		if (const int rc = adaptive_decide_locked(c, w, h, d_a, d_b, acfg->threshold, d_done, d_list, n_active, stats ? &select_ms : nullptr); rc != PTX_OK) return rc;
+		run.rounds++;
+		if (sharded) {
+			bool exchange_failed = false;
+			if (const int rc = adaptive_decide_sharded_locked(c, w, h, shard, mask_on_device, d_a, d_b, acfg->threshold, d_done, d_list, n_active, n_all, want_ms ? &run.select_ms : nullptr,
+			                                                  exchange_failed);
+			    rc != PTX_OK) {
+				if (exchange_failed && !dev) {   // the buffers hold the completed rounds
+					const std::string msg = ptx_last_error();
+					if (s_a.copy_back(c) == hipSuccess && s_b.copy_back(c) == hipSuccess) (void)hipStreamSynchronize(c->stream);
+					return set_err(rc, msg);
+				}
+				return rc;
+			}
+		} else {
+			if (const int rc = adaptive_decide_locked(c, w, h, d_a, d_b, acfg->threshold, d_done, d_list, n_active, want_ms ? &run.select_ms : nullptr); rc != PTX_OK) return rc;
+			n_all = n_active;
+		}
 		active.n_pixels = n_active;
-		if (n_active == 0) break;
+		if (n_all == 0) break;
 	}
 	HIP_TRY(s_a.copy_back(c));
 	HIP_TRY(s_b.copy_back(c));
 	if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
+	run.active_last = n_active;
+	return PTX_OK;
+}
+
+}  // namespace
+
+int ptx_render_adaptive(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_adaptive_cfg* acfg, float* accum_a, float* accum_b, ptx_adaptive_stats* stats) {
+	// every refusal below is decided before any device work
+	uint32_t x0, y0, w, h, step;
+	if (const int rc = adaptive_args("ptx_render_adaptive", sc, cfg, acfg, accum_a, accum_b, x0, y0, w, h, step); rc != PTX_OK) return rc;
+	if (cfg->shard_count > 1 && !sc->ctx) return set_err(PTX_ERR_UNSUPPORTED, no_exchange("ptx_render_adaptive"));
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_adaptive: scene was created without a GPU context (no CPU path exists)");
+	const bool dev = is_device_ptr(accum_a);
+	if (is_device_ptr(accum_b) != dev) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive: accum_a and accum_b must both be device or both be host memory");
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	if (stats) *stats = ptx_adaptive_stats{};
+
+	// the first half of the round's samples into A, the second into B: one sequence of passes each
+	auto render_round = [&](ptx_render_cfg& half, uint32_t given, uint32_t k, const PixelSubset* subset, float4* d_a, float4* d_b) {
+		float4* const target[2] = {d_a, d_b};
+		for (uint32_t part = 0; part < 2; part++) {
+			half.sample0 = cfg->sample0 + given + part * (k / 2);
+			half.spp = k / 2;
+			ptx_render_stats st{};
+			if (const int rc = render_frame_locked(sc, &half, "ptx_render_adaptive", (float*)target[part], nullptr, stats ? &st : nullptr, subset); rc != PTX_OK) return rc;
+			if (stats) {
+				stats->render.rays += st.rays; stats->render.samples += st.samples; stats->render.passes += st.passes; stats->render.kernel_ms += st.kernel_ms;
+			}
+		}
+		return (int)PTX_OK;
+	};
+	AdaptiveRun run;
+	if (const int rc = adaptive_loop(sc, "ptx_render_adaptive", cfg, acfg, x0, y0, w, h, step, accum_a, accum_b, dev, stats != nullptr, render_round, run); rc != PTX_OK) return rc;
 	if (stats) {
-		stats->rounds = rounds;
-		stats->active_last = n_active;
-		stats->select_ms = select_ms;
+		stats->rounds = run.rounds;
+		stats->active_last = run.active_last;
+		stats->select_ms = run.select_ms;
 	}
 	return PTX_OK;
 }
@@ -987,49 +1046,33 @@ int ptx_render_adaptive_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_
 	if (flags & ~kNeeFlags) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive_nee: unknown flag");
 	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
 		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_adaptive_nee: PTX_INTEGRATOR_WORKER has no light sampling here (the estimator is defined on PTX_INTEGRATOR_LIB's vertex)");
-	if (cfg->shard_count > 1)
-		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_adaptive_nee: shard_count > 1 is not supported (the 3 x 3 block of the decision would need other shards' pixels); "
-		                                    "split a frame over GPUs by rectangles instead");
+	if (cfg->shard_count > 1 && !sc->ctx) return set_err(PTX_ERR_UNSUPPORTED, no_exchange("ptx_render_adaptive_nee"));
 	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_adaptive_nee: scene was created without a GPU context (no CPU path exists)");
 	const bool dev = is_device_ptr(accum_a);
 	if (is_device_ptr(accum_b) != dev) return set_err(PTX_ERR_INVALID, "ptx_render_adaptive_nee: accum_a and accum_b must both be device or both be host memory");
 	ptx_ctx* c = sc->ctx;
 	std::lock_guard<std::mutex> lk(c->mu);
-	HIP_TRY(hipSetDevice(c->device));
 	if (stats) *stats = ptx_adaptive_nee_stats{};
-	NeeSetup S;   // the light list and the environment table: once for all rounds
-	if (const int rc = nee_setup_locked(sc, flags, S); rc != PTX_OK) return rc;
 
-	const size_t n = (size_t)w * h, bytes = n * sizeof(float4);
-	Staged s_a, s_b;   // staged once for the whole call, both in one buffer
-	if (!dev) HIP_TRY(c->adaptive_stage.ensure(2 * bytes));
-	HIP_TRY(s_a.bind(c, dev, accum_a, bytes, c->adaptive_stage));
-	HIP_TRY(s_b.bind(c, dev, accum_b, bytes, c->adaptive_stage, bytes));
-	float4 *const d_a = s_a.as<float4>(), *const d_b = s_b.as<float4>();
-	HIP_TRY(c->adaptive_state.ensure(n * 4 + pad16(n)));
-	uint32_t* const d_list = (uint32_t*)c->adaptive_state.p;
-	uint8_t* const d_done = (uint8_t*)c->adaptive_state.p + n * 4;
-	HIP_TRY(hipMemsetAsync(d_done, 0, n, c->stream));
-
-	ptx_render_cfg round = *cfg;
-	round.x0 = x0; round.y0 = y0; round.w = w; round.h = h;
-	PixelSubset active{d_list, 0};
-	uint32_t given = 0, rounds = 0, n_active = 0;
-	double select_ms = 0;
+	NeeSetup S;   // the light list and the environment table: once for all rounds, made by the first round
+	bool have_setup = false;
 	ptx_kernel_timing timing{};
 	// PTX_ADAPTIVE_NEE_HALVES=1 (measurement, tools/bench_adaptive.py): every round as ptx_render_adaptive drives it, one sequence of passes per
 	// half through k_resolve. The same bits; twice the launches. What the one-sequence form saves is the difference.
 	const char* const halves_env = getenv("PTX_ADAPTIVE_NEE_HALVES");
 	const bool two_sequences = halves_env && halves_env[0] == '1';
-	while (given < cfg->spp) {
-		const uint32_t k = rounds == 0 ? acfg->min_spp : std::min(step, cfg->spp - given);   // even: min_spp, step_spp and the cap are
+	auto render_round = [&](ptx_render_cfg& round, uint32_t given, uint32_t k, const PixelSubset* subset, float4* d_a, float4* d_b) {
+		if (!have_setup) {
+			if (const int rc = nee_setup_locked(sc, flags, S); rc != PTX_OK) return rc;
+			have_setup = true;
+		}
 		// one sequence of passes over the round's k samples, resolved into both halves; under the measurement switch one sequence per half
 		for (uint32_t part = 0; part < (two_sequences ? 2u : 1u); part++) {
 			round.sample0 = cfg->sample0 + given + part * (k / 2);
 			round.spp = two_sequences ? k / 2 : k;
 			const NeeTargets T = two_sequences ? NeeTargets{part ? d_b : d_a, nullptr, 0u} : NeeTargets{d_a, d_b, k / 2};
 			ptx_nee_stats st{};
-			if (const int rc = nee_frame_locked(sc, &round, "ptx_render_adaptive_nee", S, T, rounds == 0 ? nullptr : &active, stats ? &st : nullptr); rc != PTX_OK) return rc;
+			if (const int rc = nee_frame_locked(sc, &round, "ptx_render_adaptive_nee", S, T, subset, stats ? &st : nullptr); rc != PTX_OK) return rc;
 			if (stats) {
 				ptx_nee_stats& t = stats->nee;
 				t.render.rays += st.render.rays; t.render.samples += st.render.samples; t.render.passes += st.render.passes; t.render.kernel_ms += st.render.kernel_ms;
@@ -1040,21 +1083,16 @@ int ptx_render_adaptive_nee(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_
 				timing.fused_launches += c->timing.fused_launches;
 			}
 		}
-		given += k;
-		rounds++;
-		if (const int rc = adaptive_decide_locked(c, w, h, d_a, d_b, acfg->threshold, d_done, d_list, n_active, stats ? &select_ms : nullptr); rc != PTX_OK) return rc;
-		active.n_pixels = n_active;
-		if (n_active == 0) break;
-	}
-	HIP_TRY(s_a.copy_back(c));
-	HIP_TRY(s_b.copy_back(c));
-	if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
+		return (int)PTX_OK;
+	};
+	AdaptiveRun run;
+	if (const int rc = adaptive_loop(sc, "ptx_render_adaptive_nee", cfg, acfg, x0, y0, w, h, step, accum_a, accum_b, dev, stats != nullptr, render_round, run); rc != PTX_OK) return rc;
 	if (stats) {
 		stats->nee.n_lights = S.n_lights;
 		stats->nee.light_area = S.light_area;
-		stats->rounds = rounds;
-		stats->active_last = n_active;
-		stats->select_ms = select_ms;
+		stats->rounds = run.rounds;
+		stats->active_last = run.active_last;
+		stats->select_ms = run.select_ms;
 		c->timing = timing;   // the rounds' sums: with the fused form fused_launches == nee.render.passes and fused_ms == nee.render.kernel_ms
 	}
 	return PTX_OK;

@@ -287,6 +287,18 @@ struct AdaptiveBuffers {   // device workspace of one decision on a w x h rectan
 // one decision: a, b [w * h] radiance sums; `done` [w * h] in/out; `pixels` [w * h] receives the active list (nullptr: none is written)
 hipError_t launch_adaptive_select(const float4* a, const float4* b, uint32_t w, uint32_t h, float threshold, const AdaptiveBuffers& B, uint8_t* done, uint32_t* pixels,
                                   hipStream_t stream);
+// Interleaved tile sharding of a decision (ptx_ctx_set_mask_exchange): the rectangle's origin in the image, the shard tile's side, the shard
+// tiles per image row and the rank. A pixel (x, y) of the image is the rank's own when ((y / ts) * tiles_x + x / ts) % count == index; the
+// caller has checked that the image's tile indices fit 32 bits.
+struct AdaptiveShard {
+	uint32_t x0, y0, ts, tiles_x, index, count;
+};
+// the noisy bytes of the rank's own pixels, 0 for the others -> mask [w * h]
+hipError_t launch_adaptive_noisy_shard(const float4* a, const float4* b, uint32_t w, uint32_t h, float threshold, const AdaptiveShard& shard, uint8_t* mask, hipStream_t stream);
+// the decision of the whole rectangle from the merged mask (nonzero = noisy): `done` for every pixel, `pixels` the rank's own active pixels in
+// list order; B.n_active receives two words, the own count and the count of all active pixels. tile_count_all: [tiles] scratch.
+hipError_t launch_adaptive_decide_shard(const uint8_t* merged, uint32_t w, uint32_t h, const AdaptiveShard& shard, const AdaptiveBuffers& B, uint32_t* tile_count_all, uint8_t* done,
+                                        uint32_t* pixels, hipStream_t stream);
 // out = (a + b) / (a.w + b.w) for all four channels, or a / a.w when b == nullptr; out may be a or b
 hipError_t launch_accum_mean(const float4* a, const float4* b, size_t n_pixels, float4* out, hipStream_t stream);
 

@@ -138,6 +138,39 @@ public:
 		return adaptive_frame(c, a, b, denoise, dstats);
 	}
 
+	// The adaptive frame over several processes, interleaved tiles (ptx_ctx_set_mask_exchange in include/ptx.h has the loop): the exchange
+	// that merges the ranks' noisy bytes after every round. mask: the caller's buffer of at least W * H bytes, host or device memory; fn ==
+	// nullptr clears the registration. The callback runs inside render_adaptive_shard and must not call this renderer; one that enqueues its
+	// collective (ncclAllReduce(mask, mask, n, ncclUint8, ncclMax, comm, stream)) takes stream() beforehand.
+	void set_mask_exchange(ptx_mask_exchange_fn fn, void* user, uint8_t* mask, size_t mask_bytes) { check(ptx_ctx_set_mask_exchange(ctx_, fn, user, mask, mask_bytes)); }
+	void* stream() const { return ptx_ctx_stream(ctx_); }
+	// Rank `index` of `count`'s share of render_adaptive's frame (tile: the shard tile's side, 0 = 64): ADDS the radiance sums of its own
+	// pixels to the half-buffers a and b ([H][W][4], zero-initialised by the caller; host or device memory) and leaves the others untouched.
+	// The sum of the ranks' buffers is bitwise the one-process frame's halves: reduce them onto the root, then ptx_accum_mean or
+	// ptx_denoise_counts there. nee_flags: nullptr = ptx_render_adaptive, else ptx_render_adaptive_nee with those flags.
+	void render_adaptive_shard(uint32_t index, uint32_t count, uint32_t tile, float* a, float* b, const uint32_t* nee_flags = nullptr, ptx_adaptive_stats* stats = nullptr,
+	                           ptx_adaptive_nee_stats* nee_stats = nullptr) const {
+		if (!scene_) throw std::runtime_error("render_adaptive_shard() before load_gltf()");
+		if (transparent_background) throw std::runtime_error("render_adaptive_shard: the decision takes radiance sums, which transparent_background does not produce");
+		if (environment.string() != env_set_) {
+			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
+			env_set_ = environment.string();
+		}
+		ptx_render_cfg c{};
+		c.W = resolution.x; c.H = resolution.y; c.spp = sample_count; c.bounces = bounce_count;
+		for (int k = 0; k < 3; k++) c.env[k] = environment_factor[k];
+		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
+		c.shard_index = index; c.shard_count = count; c.shard_tile = tile;
+		const ptx_adaptive_cfg ac{adaptive_min, adaptive_step, adaptive_threshold};
+		if (nee_flags) {
+			ptx_nee_cfg n{};
+			n.flags = *nee_flags;
+			check(ptx_render_adaptive_nee(scene_, &c, &ac, &n, a, b, nee_stats));
+		} else {
+			check(ptx_render_adaptive(scene_, &c, &ac, a, b, stats));
+		}
+	}
+
 	// render_adaptive on render_nee's estimator (ptx_render_adaptive_nee; flags: ptx_nee_cfg::flags): one sequence of passes per round, resolved
 	// into both halves. Returns the MEANS [H][W][4], through the filter with denoise. stats, dstats optional
 	std::vector<float> render_adaptive_nee(ptx_adaptive_nee_stats* stats = nullptr, uint32_t flags = 0, bool denoise = false, ptx_denoise_stats* dstats = nullptr) const {

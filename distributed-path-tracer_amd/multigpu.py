@@ -13,6 +13,9 @@ The scene is replicated on every GPU (it is small next to 288 GB of HBM). ONE fr
     dealt out evenly; each rank renders all samples of its tiles in ONE launch sequence (ptx_render_cfg.shard_*: a pixel list
     inside the library) straight into a zeroed full-frame buffer; the sum (x + 0 = x) is bitwise the single-GPU frame.
 
+`render_adaptive_tiles` is the tile split for frames of noise-driven per-pixel sample counts (Scene.render_adaptive*): besides the sum at
+the end the ranks exchange one byte per pixel per round, and the result is bitwise the frame of one process.
+
 `render_sharded` is the weak-scaling variant (every rank adds `spp` samples of its own: the frame gets world * spp).
 This replaces the reference's planned (never implemented) SNS/SQS fan-in — path-tracer-core/src/models/work_info.hpp:22-23,
 intersection_worker.cpp:78-110.
@@ -120,3 +123,52 @@ def render_tiles(scene, W, H, spp, bounces, accum, rank, world, tile=TILE, trans
     _order_before_reduce(scene)
     reduce_accum(accum, 0)
     return stats if stats is not None else {"rays": 0, "samples": 0, "passes": 0, "kernel_ms": 0.0}
+
+
+def render_adaptive_tiles(scene, W, H, cap, bounces, a, b, rank, world, tile=TILE, min_spp=8, step_spp=0, threshold=0.1, nee_flags=None,
+                          transparent=False, **kw):
+    """Noise-driven per-pixel sample counts over interleaved tiles: this rank runs the adaptive loop on the `tile` x `tile` image tiles t
+    with t % world == rank, into the zeroed full-frame half-buffers `a` and `b` ([H,W,4], both host memory — numpy, or CPU tensors for gloo — or both torch-on-GPU). After every
+    round the ranks merge one byte per pixel — which pixels are still noisy — with an all-reduce (MAX), and each decides the whole frame
+    from the merged mask, so all ranks run the same number of rounds; then `a` and `b` are sum-reduced onto rank 0. The result there is
+    BITWISE Scene.render_adaptive (nee_flags=None) or Scene.render_adaptive_nee (nee_flags: an int, its flags) of one process with the
+    same arguments: every pixel belongs to one rank, which gives it the samples the one-process loop gives it. Returns the stats of the
+    local render: rays, samples, passes and the light-sample counts are this rank's own, `rounds` is the same on every rank, and
+    `active_last` sums over the ranks to the one-process value.
+    The mask lives in the same kind of memory as `a`: a device tensor is reduced in place by the process group (nccl = RCCL on ROCm), a
+    numpy array through gloo. transparent=True raises ValueError: the adaptive decision takes radiance sums, which the transparent-background
+    blend does not produce."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    if transparent:
+        raise ValueError("render_adaptive_tiles: the adaptive decision takes radiance sums, which transparent_background's blend does not produce")
+    ctx = scene.ctx
+    x0, y0, w, h = kw.get("tile") or (0, 0, W, H)   # Scene.render_adaptive's rectangle (kw["tile"]), not the shard tile
+    on_host = isinstance(a, np.ndarray) or a.device.type == "cpu"
+    # the mask in the kind of memory `a` is in, and as the tensor the collective takes (torch.from_numpy shares the array's memory)
+    mask = np.zeros(w * h, np.uint8) if isinstance(a, np.ndarray) else torch.zeros(w * h, dtype=torch.uint8, device=a.device)
+    wire = torch.from_numpy(mask) if isinstance(mask, np.ndarray) else mask
+    live = dist.is_available() and dist.is_initialized()
+
+    def exchange(_mask, _n_bytes):
+        if live:
+            dist.all_reduce(wire, op=dist.ReduceOp.MAX)
+            if not on_host:
+                torch.cuda.synchronize(a.device)   # the collective ran on torch's stream: the library reads the mask on its own
+        return 0
+
+    if not on_host:
+        torch.cuda.synchronize(a.device)   # the fill of `mask` ran on torch's stream
+    ctx.set_mask_exchange(exchange, mask)
+    try:
+        if nee_flags is None:
+            _, _, stats = scene.render_adaptive(W, H, cap, bounces, min_spp, step_spp, threshold, a=a, b=b, shard=(rank, world, tile), **kw)
+        else:
+            _, _, stats = scene.render_adaptive_nee(W, H, cap, bounces, min_spp, step_spp, threshold, a=a, b=b, shard=(rank, world, tile), flags=nee_flags, **kw)
+    finally:
+        ctx.set_mask_exchange(None)
+    _order_before_reduce(scene)
+    for buf in (a, b):
+        reduce_accum(torch.from_numpy(buf) if isinstance(buf, np.ndarray) else buf, 0)
+    return stats

@@ -361,11 +361,16 @@ int ptx_denoise_counts(ptx_ctx* ctx, const ptx_denoise_counts_cfg* cfg, const fl
  * frame rendered in rectangles may stop pixels that the whole frame's decision keeps.
  * Image write: ptx_accum_mean, then ptx_tonemap_encode(..., spp = 1, ...).
  * The result is filtered by ptx_denoise_counts (ptx_denoise takes one count per buffer, not one per pixel).
- * Out of scope: ptx_render_transparent's blend (a recurrence, not a sum) and the multi-process driver (multigpu.py).
+ * Interleaved tile sharding (cfg->shard_count > 1): with a mask exchange registered on the scene's context the call runs the SHARDED loop
+ * specified at ptx_ctx_set_mask_exchange below, and the sum of the ranks' zero-initialised half-buffers is bitwise this call's unsharded result
+ * (multigpu.render_adaptive_tiles is the multi-process driver). With shard_count <= 1 a registration is ignored: the same bits, and the
+ * exchange is never called.
+ * Out of scope: ptx_render_transparent's blend (a recurrence, not a sum).
  * Refusals, all decided before any device work: PTX_ERR_INVALID for NULL arguments, an odd or zero min_spp, an odd step_spp, cfg->spp odd or
  * below min_spp, more than 4096 rounds, a negative or NaN threshold, pointers of mixed kinds, and whatever ptx_render refuses in cfg;
- * PTX_ERR_UNSUPPORTED for shard_count > 1 (the 3 x 3 block would need other shards' pixels: split a frame over GPUs by rectangles instead);
- * PTX_ERR_NO_DEVICE for a host-only scene. */
+ * PTX_ERR_UNSUPPORTED for shard_count > 1 with no mask exchange registered (the 3 x 3 block reads the noisy bytes of pixels that other shards
+ * own: see ptx_ctx_set_mask_exchange); PTX_ERR_INVALID for shard_count > 1 with a registered mask of fewer than w * h bytes of the rectangle, or
+ * an image of more than 2^32 - 1 shard tiles; PTX_ERR_NO_DEVICE for a host-only scene. */
 typedef struct ptx_adaptive_cfg { uint32_t min_spp, step_spp; float threshold; } ptx_adaptive_cfg;
 typedef struct ptx_adaptive_stats { ptx_render_stats render; uint32_t rounds, active_last; double select_ms; } ptx_adaptive_stats;
 int ptx_render_adaptive(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_adaptive_cfg* acfg, float* accum_a, float* accum_b,
@@ -381,6 +386,44 @@ int ptx_adaptive_select(ptx_ctx* ctx, uint32_t w, uint32_t h, const float* accum
  * out.c = a.c / a.w. A pixel of zero count gives NaNs. out_rgba [n_pixels][4] may be accum_a or accum_b itself; all pointers device or all
  * host. PTX_ERR_INVALID for a NULL ctx, accum_a or out_rgba, n_pixels above 2^31 - 1, or pointers of mixed kinds. */
 int ptx_accum_mean(ptx_ctx* ctx, const float* accum_a, const float* accum_b /* NULL ok */, size_t n_pixels, float* out_rgba);
+
+/* ptx_render_adaptive and ptx_render_adaptive_nee over interleaved tile shards: the one thing the decision needs from the other ranks is the
+ * NOISY BYTE of the pixels they own, one byte per pixel per round (2 MB at 1080p). The library does not talk to the other ranks itself: the
+ * caller registers an exchange on the context, and calls with cfg->shard_count > 1 on that context's scenes run the loop below. This text is
+ * the specification; everything it does not change is ptx_render_adaptive's text.
+ *   Ownership. ts = shard_tile ? shard_tile : 64, tiles_x = (W + ts - 1) / ts. Rank shard_index owns the pixel (x, y) of the FULL image (the
+ *   rectangle's x0, y0 added to its local coordinates) when ((y / ts) * tiles_x + x / ts) % shard_count == shard_index: the pixels ptx_render
+ *   gives it under the same shard_* fields.
+ *   Own pixels only. Rendering, both half-buffers and the active list cover the rank's own pixels only; other shards' pixels of accum_a and
+ *   accum_b are left untouched, as in ptx_render.
+ *   The mask. After a round the rank writes mask[ly * w + lx] = noisy_p (0 / 1) for its own pixels of the rectangle and 0 for all others,
+ *   synchronises the context's stream, and calls fn(user, mask, w * h). On return the mask must hold, for every pixel of the rectangle, a
+ *   nonzero byte iff some rank wrote a nonzero one: an element-wise MAX or OR over the ranks (a byte SUM serves for up to 255 ranks). The
+ *   library reads the merged mask only as "nonzero = noisy".
+ *   The decision. Every rank decides the WHOLE rectangle from the merged mask, with the `done` latch over all of its pixels, so `done`, the
+ *   number of active pixels and the number of rounds are the same on every rank without a second collective. The rank's active list is the
+ *   specified list order restricted to its own pixels. The loop ends when no pixel of the rectangle is active, or at the cap. A rank that owns
+ *   no active pixel, or no pixel at all, renders nothing in that round and still calls the exchange: exactly one call per round on every rank.
+ *   By induction over the rounds, own pixels hold what the unsharded call leaves in them and the merged mask is the unsharded call's noisy mask:
+ *   the sum of the ranks' zero-initialised buffers is bitwise the unsharded result.
+ * The mask buffer is the CALLER's, at least w * h bytes of the rendered rectangle, device or host memory (the library looks at the pointer): a
+ * device buffer is written and read in place, so that a framework can hand its own tensor to a collective; a host buffer makes the library
+ * copy its device mask out before the callback and back in after it. fn == NULL clears the registration (user, mask and mask_bytes are then
+ * ignored).
+ * The callback. Before it is called the library has synchronised the context's stream. It returns when the merged mask is in the buffer: it
+ * has either synchronised itself, or enqueued its collective on ptx_ctx_stream(ctx), which it obtained BEFOREHAND: the callback runs under
+ * the context's lock and must not call the library on that context (it would wait for itself). A non-zero return ends the render call with
+ * PTX_ERR_HIP and the message "mask exchange failed (status n)"; the half-buffers then hold the completed rounds.
+ * Stats of a sharded call: render.*, light_samples and light_visible are the rank's own sums; rounds is the same on all ranks; active_last is
+ * the rank's own active pixels after the last decision (the sum over the ranks is the unsharded value). The sharded loop synchronises twice per
+ * round: before the callback, and for the 8 bytes of the two counts.
+ * ptx_ctx_get_mask_exchange_stats: the number of callback calls of the context's last adaptive call (0 after an unsharded one) and the wall
+ * time spent inside them; either pointer may be NULL.
+ * PTX_ERR_INVALID for a NULL ctx, and for a callback with a NULL mask. Out of scope: a library-owned RCCL path for the mask, and
+ * ptx_adaptive_select with shards. */
+typedef int (*ptx_mask_exchange_fn)(void* user, uint8_t* mask, size_t n_bytes);
+int ptx_ctx_set_mask_exchange(ptx_ctx* ctx, ptx_mask_exchange_fn fn /* NULL clears */, void* user, uint8_t* mask, size_t mask_bytes);
+int ptx_ctx_get_mask_exchange_stats(ptx_ctx* ctx, uint64_t* calls /* NULL ok */, double* wall_ms /* NULL ok */);
 
 /* Next-event estimation towards emissive triangles (no counterpart in the reference, whose estimators collect emission only where a
  * BSDF-sampled ray happens to hit an emitter). ptx_render_nee renders the samples of ptx_render with the PTX_INTEGRATOR_LIB estimator plus
@@ -413,8 +456,8 @@ int ptx_accum_mean(ptx_ctx* ctx, const float* accum_a, const float* accum_b /* N
  * Refusals, all decided before any device work: PTX_ERR_UNSUPPORTED for PTX_INTEGRATOR_WORKER; PTX_ERR_NO_DEVICE for a host-only scene;
  * PTX_ERR_INVALID for NULL scene, cfg or accum, unknown flags and whatever ptx_render refuses in cfg.
  * ptx_render_adaptive_nee (below the flags) runs ptx_render_adaptive's loop on this estimator.
- * Out of scope: ptx_render_transparent's blend, the worker estimator, and multigpu.py (its shards and sample ranges already compose through
- * the accum format). */
+ * Out of scope: ptx_render_transparent's blend and the worker estimator. multigpu.py needs no function of its own for this call: its shards
+ * and sample ranges already compose through the accum format. */
 #define PTX_NEE_NO_LIGHT_SAMPLES 1u   /* run with an empty list */
 /* PTX_NEE_FUSED: render with ONE kernel launch per pass wherever ptx_render would run this scene on its fused kernel (pipeline 0: LDS-resident and
  * hybrid scenes, global-memory scenes under PTX_WAVEFRONT=0): a lane carries a path from its camera ray to its end in registers, without the
@@ -507,7 +550,9 @@ int ptx_render_nee(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_nee_cf
  * when the fused form ran, fused_launches == nee.render.passes and fused_ms == nee.render.kernel_ms, otherwise fused_launches == 0.
  * Host buffers are staged once for the whole call; the light list and the environment table are uploaded once. The call always synchronises,
  * as ptx_render_adaptive does. Filter the result with ptx_denoise_counts; image write as for ptx_render_adaptive.
- * Refusals, all decided before any device work: everything ptx_render_adaptive refuses (PTX_ERR_UNSUPPORTED for shard_count > 1) and
+ * shard_count > 1 runs the sharded loop of ptx_ctx_set_mask_exchange, as in ptx_render_adaptive.
+ * Refusals, all decided before any device work: everything ptx_render_adaptive refuses (PTX_ERR_UNSUPPORTED for shard_count > 1 without a
+ * registered mask exchange) and
  * everything ptx_render_nee refuses (PTX_ERR_INVALID for an unknown flag, PTX_ERR_UNSUPPORTED for PTX_INTEGRATOR_WORKER, PTX_ERR_NO_DEVICE for
  * a host-only scene). */
 typedef struct ptx_adaptive_nee_stats { ptx_nee_stats nee; uint32_t rounds, active_last; double select_ms; } ptx_adaptive_nee_stats;

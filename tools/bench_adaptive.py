@@ -20,6 +20,15 @@
                                                  adaptive mean (tonemapped mean squared error against the product's ref_spp frame, 1024, seed 77);
                                              (c) ptx_denoise_counts: kernel time, and the error after it.
                                              The JSON lines go to `out` (profiles/adaptive_nee_bench.txt) too.
+  tools/bench_adaptive.py --sharded [out]    the sharded decision (ptx_ctx_set_mask_exchange) on ONE GPU: plaza (level 3), threshold 0.1, device
+                                             buffers and a device mask, at 1920 x 1080 and 3840 x 2160. The rank is 0 of 2 with a shard tile of
+                                             16384, so it owns every pixel and the exchange is the identity: the frame is the unsharded one, and
+                                             what is timed is the sharded kernels and the callback's round trip. select_ms per round of the two
+                                             forms, alternated call by call (the smallest of 3 after a warm-up), and the exchange's wall time per
+                                             round. Then the balance figure: from the per-pixel counts of that 1080p frame and of a Cornell
+                                             frame with light sampling, the per-rank sample share (max / mean) of 8 ranks under interleaved
+                                             64 x 64 tiles and under 8 horizontal strips. The JSON lines go to `out`
+                                             (profiles/adaptive_sharded_bench.txt) too.
 Prints one JSON line per measurement.
 """
 import importlib
@@ -191,8 +200,63 @@ def nee(out_path, ref_spp):
         fh.write("\n".join(lines) + "\n")
 
 
+def sharded(out_path):
+    import torch
+    mg = importlib.import_module("distributed-path-tracer_amd.multigpu")
+    ctx = ptx.Context(0)
+    s = ptx.Scene.from_arrays(ctx, *[proc.plaza_scene()[k] for k in KEYS])
+    lines, reps = [], 3
+
+    def emit(**kw):
+        lines.append(json.dumps(kw))
+        print(lines[-1], flush=True)
+
+    def balance(name, counts):
+        H, W = counts.shape
+        total = float(counts.sum(dtype=np.float64))
+        tiles = [float(counts[mg.tile_mask(r, 8, W, H, 64)].sum(dtype=np.float64)) for r in range(8)]
+        strips = [float(c.sum(dtype=np.float64)) for c in np.array_split(counts, 8, axis=0)]
+        emit(part="balance", scene=name, W=W, H=H, ranks=8, mean_spp=round(float(counts.mean()), 2), tiles64_max_over_mean=round(max(tiles) / (total / 8), 4),
+             strips_max_over_mean=round(max(strips) / (total / 8), 4))
+    for W, H in ((1920, 1080), (3840, 2160)):
+        mask = torch.zeros(W * H, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        best = {"unsharded": None, "sharded": None}
+        wall, frames = 1e9, {}
+        for rep_i in range(reps + 1):   # the first call of each form warms up
+            for form in best:
+                if form == "sharded":
+                    ctx.set_mask_exchange(lambda m, n: 0, mask)
+                try:
+                    a, b, st = s.render_adaptive(W, H, CAP, BOUNCES, MIN, STEP, 0.1, a=zeros(W, H), b=zeros(W, H), seed=SEED, shard=(0, 2, 16384) if form == "sharded" else None)
+                finally:
+                    ctx.set_mask_exchange(None)
+                frames[form] = (a, b)
+                if rep_i and (best[form] is None or st["select_ms"] < best[form]["select_ms"]):
+                    best[form] = st
+                if rep_i and form == "sharded":
+                    wall = min(wall, ctx.mask_exchange_stats()["wall_ms"] / st["rounds"])
+        same = all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(frames["unsharded"], frames["sharded"]))
+        u, sh = best["unsharded"], best["sharded"]
+        emit(part="cost", scene="plaza3", W=W, H=H, rounds=u["rounds"], same_bits=same, unsharded_select_ms_per_round=round(u["select_ms"] / u["rounds"], 4),
+             sharded_select_ms_per_round=round(sh["select_ms"] / sh["rounds"], 4), ratio=round(sh["select_ms"] / u["select_ms"], 3), exchange_wall_ms_per_round=round(wall, 4),
+             render_kernel_ms_per_round=round(u["kernel_ms"] / u["rounds"], 3))
+        if W == 1920:
+            a, b = frames["unsharded"]
+            balance("plaza3", (a[..., 3] + b[..., 3]).cpu().numpy())
+    s.close()
+    c = ptx.Scene.load_gltf(ctx, CORNELL)
+    a, b, _ = c.render_adaptive_nee(1920, 1080, CAP, BOUNCES, MIN, STEP, 0.2, a=zeros(1920, 1080), b=zeros(1920, 1080), seed=SEED, want_stats=False, flags=ptx.NEE_FUSED)
+    balance("cornell_nee", (a[..., 3] + b[..., 3]).cpu().numpy())
+    with open(out_path, "w") as fh:
+        fh.write("# tools/bench_adaptive.py --sharded: one GPU, 4 bounces, 8 + 8 per round, cap 64; select_ms is HIP-event time of the decision kernels, the smallest of 3 calls\n")
+        fh.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "--nee":
+    if len(sys.argv) > 1 and sys.argv[1] == "--sharded":
+        sharded(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "adaptive_sharded_bench.txt"))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--nee":
         nee(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "adaptive_nee_bench.txt"), int(sys.argv[3]) if len(sys.argv) > 3 else 1024)
     elif len(sys.argv) > 1 and sys.argv[1] == "payoff":
         payoff(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
