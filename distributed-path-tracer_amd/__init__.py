@@ -124,6 +124,14 @@ NEE_ENV_SAMPLES = 16       # the light sample may go towards the environment map
 NEE_SAMPLER_PDF = 64       # MIS weights on the density of LIB's BSDF sampler instead of LIB's pdf value: the frame's expectation is LIB's
 
 
+def NEE_CANDIDATES(m):
+    """PTX_NEE_CANDIDATES(m): bits 8..11 of ptx_nee_cfg.flags. The light sample of a vertex is picked among m = 1 .. 16 candidates in
+    proportion to their unshadowed contributions, one shadow ray for the pick; m = 1 is 0, the call without the bits."""
+    if not 1 <= int(m) <= 16:
+        raise ValueError(f"NEE_CANDIDATES: m = {m} is outside 1 .. 16")
+    return (int(m) - 1) << 8
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("pipeline", C.c_uint32), ("steps", C.c_uint32), ("classify_ms", C.c_double), ("traverse_ms", C.c_double), ("shade_ms", C.c_double),
                 ("fused_ms", C.c_double), ("fused_launches", C.c_uint32), ("pool_overflows", C.c_uint32), ("pool_pairs", C.c_uint64),
@@ -597,7 +605,7 @@ class Scene:
         return a, b, stats
 
     def render_nee(self, W, H, spp, bounces, accum=None, env=(1.0, 1.0, 1.0), seed=0x5EED, tile=None, sample0=0, spp_per_pass=0,
-                   want_stats=True, integrator=INTEGRATOR_LIB, shard=None, flags=0):
+                   want_stats=True, integrator=INTEGRATOR_LIB, shard=None, flags=0, candidates=1):
         """ptx_render_nee: render()'s samples with the LIB estimator plus one light sample towards the listed emissive triangles per
         continuing vertex, MIS-weighted (include/ptx.h has the estimator). ADDS radiance SUMS into accum as render() does; tiles, sample
         ranges and shards compose the same way. flags: NEE_NO_LIGHT_SAMPLES runs with an empty list (bitwise render()'s frame);
@@ -606,13 +614,14 @@ class Scene:
         sampled by luminance and MIS-weighted against the map's radiance on a miss (ignored without a map or with a black one);
         NEE_SAMPLER_PDF builds the MIS weights on the density of LIB's BSDF sampler instead of LIB's pdf value, which removes the shift of
         the expectation at glossy vertices that see a light (bitwise the unflagged frame when no light sample is possible).
+        candidates = m ors NEE_CANDIDATES(m) into flags: the light sample picked among m candidates, still one shadow ray per vertex.
         Returns (accum, stats dict or None)."""
         x0, y0, w, h = tile if tile else (0, 0, W, H)
         if accum is None:
             accum = np.zeros((h, w, 4), np.float32)
         cfg = RenderCfg(W, H, spp, bounces, (C.c_float * 3)(*env), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
                         x0, y0, w, h, sample0, spp_per_pass, integrator, *((tuple(shard) + (0,))[:3] if shard else (0, 0, 0)))
-        ncfg = NeeCfg(flags)
+        ncfg = NeeCfg(flags | NEE_CANDIDATES(candidates))
         st = NeeStats()
         _check(lib().ptx_render_nee(self.h, C.byref(cfg), C.byref(ncfg), _ptr(accum), C.byref(st) if want_stats else None))
         stats = dict(rays=st.render.rays, samples=st.render.samples, passes=st.render.passes, kernel_ms=st.render.kernel_ms, n_lights=st.n_lights,
@@ -620,8 +629,8 @@ class Scene:
         return accum, stats
 
     def render_adaptive_nee(self, W, H, spp, bounces, min_spp=8, step_spp=0, threshold=0.1, a=None, b=None, env=(1.0, 1.0, 1.0), seed=0x5EED, tile=None,
-                            sample0=0, spp_per_pass=0, want_stats=True, integrator=INTEGRATOR_LIB, shard=None, flags=0):
-        """ptx_render_adaptive_nee: render_adaptive()'s loop on render_nee()'s estimator with `flags`, one sequence of passes per round resolved
+                            sample0=0, spp_per_pass=0, want_stats=True, integrator=INTEGRATOR_LIB, shard=None, flags=0, candidates=1):
+        """ptx_render_adaptive_nee: render_adaptive()'s loop on render_nee()'s estimator with `flags` (and `candidates`, as there), one sequence of passes per round resolved
         into both halves. A pixel with n samples holds, bit for bit, what render_nee() calls of the same half ranges leave in a and b. Filter
         the result with Context.denoise_counts. Returns (a, b, stats dict or None)."""
         x0, y0, w, h = tile if tile else (0, 0, W, H)
@@ -629,7 +638,7 @@ class Scene:
             a, b = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
         cfg = RenderCfg(W, H, spp, bounces, (C.c_float * 3)(*env), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
                         x0, y0, w, h, sample0, spp_per_pass, integrator, *((tuple(shard) + (0,))[:3] if shard else (0, 0, 0)))
-        acfg, ncfg = AdaptiveCfg(min_spp, step_spp, threshold), NeeCfg(flags)
+        acfg, ncfg = AdaptiveCfg(min_spp, step_spp, threshold), NeeCfg(flags | NEE_CANDIDATES(candidates))
         st = AdaptiveNeeStats()
         _check(lib().ptx_render_adaptive_nee(self.h, C.byref(cfg), C.byref(acfg), C.byref(ncfg), _ptr(a), _ptr(b), C.byref(st) if want_stats else None))
         r = st.nee.render
@@ -803,8 +812,8 @@ class Renderer:
                                                                      env=self.environment_factor, seed=self.seed)
         return self._denoise_counts(a, b, min_spp) if denoise else self._ctx.accum_mean(a, b, out=a)
 
-    def render_adaptive_nee(self, flags=0, threshold=0.1, min_spp=8, step_spp=0, denoise=False):
-        """render_adaptive() on render_nee()'s estimator (Scene.render_adaptive_nee; flags: ptx_nee_cfg.flags): the MEANS [H,W,4], through the
+    def render_adaptive_nee(self, flags=0, threshold=0.1, min_spp=8, step_spp=0, denoise=False, candidates=1):
+        """render_adaptive() on render_nee()'s estimator (Scene.render_adaptive_nee; flags: ptx_nee_cfg.flags, candidates: NEE_CANDIDATES): the MEANS [H,W,4], through the
         filter with denoise. `last_adaptive_stats` holds the stats, the light-sampling ones included."""
         if self._scene is None:
             raise PtxError(ERR_INVALID, "render_adaptive_nee() before load_gltf()")
@@ -815,13 +824,14 @@ class Renderer:
             self._scene.set_environment(self.environment)
             self._env_set = self.environment
         a, b, self.last_adaptive_stats = self._scene.render_adaptive_nee(W, H, self.sample_count, self.bounce_count, min_spp, step_spp, threshold,
-                                                                         env=self.environment_factor, seed=self.seed, flags=flags)
+                                                                         env=self.environment_factor, seed=self.seed, flags=flags, candidates=candidates)
         return self._denoise_counts(a, b, min_spp) if denoise else self._ctx.accum_mean(a, b, out=a)
 
-    def render_nee(self, flags=0):
+    def render_nee(self, flags=0, candidates=1):
         """Radiance SUMS [H,W,4] of the frame with next-event estimation towards the scene's emissive triangles (Scene.render_nee):
         render_accum()'s samples plus one MIS-weighted light sample per continuing vertex. flags: ptx_nee_cfg.flags (NEE_FUSED: the same
-        frame from one kernel launch per pass; NEE_ENV_SAMPLES: light samples towards `environment` too). `last_nee_stats` holds the stats."""
+        frame from one kernel launch per pass; NEE_ENV_SAMPLES: light samples towards `environment` too); candidates: the light sample picked among that many (NEE_CANDIDATES).
+        `last_nee_stats` holds the stats."""
         if self._scene is None:
             raise PtxError(ERR_INVALID, "render_nee() before load_gltf()")
         if self.transparent_background:
@@ -831,7 +841,7 @@ class Renderer:
             self._scene.set_environment(self.environment)
             self._env_set = self.environment
         accum, self.last_nee_stats = self._scene.render_nee(W, H, self.sample_count, self.bounce_count, env=self.environment_factor, seed=self.seed,
-                                                                    flags=flags)
+                                                                    flags=flags, candidates=candidates)
         return accum
 
     def render(self):

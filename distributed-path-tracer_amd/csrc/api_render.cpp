@@ -662,6 +662,7 @@ struct NeeSetup {
 	float light_area = 0;
 	bool fused = false;      // PTX_NEE_FUSED on a scene of the fused route
 	bool sampler_pdf = false;   // PTX_NEE_SAMPLER_PDF where a light sample is possible
+	uint32_t candidates = 1;    // M of PTX_NEE_CANDIDATES where a light sample is possible; above 1 the RIS variants run
 };
 // Where a pass's samples go. b == nullptr: all of them into a (k_resolve). Otherwise the call's samples [0, split) into a and the rest into b
 // (k_resolve_halves): pass p, whose first sample is p * pass_spp, gives a its first clamp(split - p * pass_spp, 0, samples of the pass).
@@ -721,6 +722,8 @@ int nee_setup_locked(ptx_scene* sc, uint32_t flags, NeeSetup& S) {
 	}
 	// PTX_NEE_SAMPLER_PDF changes weights only: with no light sample possible every weight is 1, and the unflagged variants run
 	S.sampler_pdf = (flags & PTX_NEE_SAMPLER_PDF) != 0 && (S.Lt.n != 0 || S.Ev.row_cdf != nullptr);
+	// PTX_NEE_CANDIDATES: with no light sample possible no candidate is drawn, and the unflagged variants run
+	S.candidates = (S.Lt.n != 0 || S.Ev.row_cdf != nullptr) ? ((flags >> 8) & 15u) + 1u : 1u;
 	return PTX_OK;
 }
 
@@ -741,7 +744,7 @@ int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeSetu
 		P.integrator = PTX_INTEGRATOR_LIB;
 		HIP_TRY(hipMemsetAsync(B.chunk_counter, 0, 8, c->stream));
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
-		HIP_TRY(launch_nee_fused(sc->dev, P, S.Lt, S.Ev, S.sampler_pdf, B, sc->mode, sc->lds_bytes, grid, c->stream));
+		HIP_TRY(launch_nee_fused(sc->dev, P, S.Lt, S.Ev, S.sampler_pdf, S.candidates, B, sc->mode, sc->lds_bytes, grid, c->stream));
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
 		HIP_TRY(nee_resolve(B.sample_rad, T, f, P, p, c->stream));
 	}
@@ -831,7 +834,7 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 			rays += live;
 			const NeeHits H{A.distance, A.surface, A.triangle, A.b1, A.b2};
 			HIP_TRY(hipMemsetAsync(cnt, 0, 8, c->stream));
-			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, Ev, S.sampler_pdf, in, H, live, out, W, cnt, Lrec, c->stream));
+			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, Ev, S.sampler_pdf, S.candidates, in, H, live, out, W, cnt, Lrec, c->stream));
 			uint32_t got[2] = {0, 0};   // continuations, shadow rays
 			HIP_TRY(hipMemcpyAsync(got, cnt, 8, hipMemcpyDeviceToHost, c->stream));
 			HIP_TRY(hipStreamSynchronize(c->stream));
@@ -866,7 +869,7 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 	return PTX_OK;
 }
 
-constexpr uint32_t kNeeFlags = PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED | PTX_NEE_ENV_SAMPLES | PTX_NEE_SAMPLER_PDF;
+constexpr uint32_t kNeeFlags = PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED | PTX_NEE_ENV_SAMPLES | PTX_NEE_SAMPLER_PDF | PTX_NEE_CANDIDATES(16);   // bits 8..11: the candidate count
 
 }  // namespace
 

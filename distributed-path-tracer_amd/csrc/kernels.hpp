@@ -244,7 +244,8 @@ constexpr uint32_t kNeeEnvRay = 0xFFFFFFFFu;   // exp_surf of an environment sam
 // cnt (device, 8 words): [0] entries appended to `out`, [1] shadow rays of the round, [2..3] light samples (64-bit), [4..5] visible ones
 hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, hipStream_t stream);
 // sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF (nee_core.hpp: sampler_pdf in pe's place in the weights)
-hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, const NeeStream& in, const NeeHits& H, uint32_t n,
+// candidates: M of PTX_NEE_CANDIDATES, 1 .. 16; above 1 the RIS variants run (nee_core.hpp: the candidate loop of nee_vertex)
+hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, uint32_t candidates, const NeeStream& in, const NeeHits& H, uint32_t n,
                             const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
 hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, hipStream_t stream);
 
@@ -256,8 +257,8 @@ struct NeeFusedBuffers {
 	unsigned long long* chunk_counter;   // paths handed out so far; zeroed before each pass
 	unsigned long long* counters;        // [3] accumulate: rays (closest + both shadow kinds), light samples, visible light samples
 };
-hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
-                            hipStream_t stream);
+hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, uint32_t candidates, const NeeFusedBuffers& B, int mode,
+                            size_t lds_bytes, int grid, hipStream_t stream);
 
 // Variance-guided a-trous filter (denoise.hip, ptx_denoise). All buffers [n_pixels] float4 on the device.
 // prepare: the two radiance sums and the guide sums -> col_var (demodulated colour, v0), guide (mean normal, mean depth), remod (albedo, alpha)

@@ -49,10 +49,11 @@ DEV void nee_append2(bool first, bool second, uint32_t* counter, uint32_t& pos_f
 // One vertex of every live path: loads the hit and the path state of entry i, runs nee_vertex (nee_core.hpp) and stores what it returns.
 // TEX / ALPHA / SUN compile the texture lookups / the pass-through and catcher code / the sun request in, as the render variants do;
 // ENV the environment sample and the miss weight (PTX_NEE_ENV_SAMPLES; TEX only: a map implies the TEX variants). Ev, the last argument, is
-// read by the ENV variants alone. SPDF: the weights of PTX_NEE_SAMPLER_PDF.
-template <bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false>
+// read by the ENV variants alone. SPDF: the weights of PTX_NEE_SAMPLER_PDF. RIS: the light sample chosen among ris_m candidates
+// (PTX_NEE_CANDIDATES); the other variants do not read ris_m.
+template <bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false, bool RIS = false>
 __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParams P, NeeLights Lt, NeeStream in, NeeHits H, uint32_t n, NeeStream out, NeeShadow W,
-                                                         uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeeEnv Ev) {
+                                                         uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeeEnv Ev, uint32_t ris_m) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
 	NeeVertex v;
 	V3 o = {0, 0, 0}, d = {0, 0, 1}, T = {1, 1, 1};
@@ -70,7 +71,7 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 		const uint32_t pixel = py * P.W + px;
 		const float4 l4 = Lrec[id];
 		V3 L = mk(l4.x, l4.y, l4.z);
-		if (nee_vertex<TEX, ALPHA, SUN, ENV, SPDF>(S, P, Lt, Ev, pixel, sample, H.surface[i], (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v))
+		if (nee_vertex<TEX, ALPHA, SUN, ENV, SPDF, RIS>(S, P, Lt, Ev, ris_m, pixel, sample, H.surface[i], (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v))
 			Lrec[id] = make_float4(L.x, L.y, L.z, l4.w);
 	}
 	// shadow rays of the round: at most two per path, so every position is below twice the round's paths
@@ -147,36 +148,39 @@ hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const N
 	return hipGetLastError();
 }
 
-template <bool TEX, bool ALPHA, bool ENV, bool SPDF>
-static void nee_shade_sun(bool sun, dim3 grid, hipStream_t stream, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeStream& in, const NeeHits& H,
+template <bool TEX, bool ALPHA, bool ENV, bool SPDF, bool RIS>
+static void nee_shade_sun(bool sun, dim3 grid, hipStream_t stream, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeStream& in, const NeeHits& H,
                           uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L) {
-	if (sun) hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, true, ENV, SPDF>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev);
-	else hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, false, ENV, SPDF>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev);
+	if (sun) hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, true, ENV, SPDF, RIS>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m);
+	else hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, false, ENV, SPDF, RIS>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m);
 }
 
-template <bool SPDF>
-static hipError_t launch_nee_shade_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeStream& in, const NeeHits& H, uint32_t n, const NeeStream& out,
+template <bool SPDF, bool RIS>
+static hipError_t launch_nee_shade_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeStream& in, const NeeHits& H, uint32_t n, const NeeStream& out,
                                         const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
 	const dim3 grid((n + kNeeBlock - 1) / kNeeBlock);
 	const bool sun = S.sun.present != 0;
 	if (Ev.row_cdf) {   // a table means a map, and a map means the TEX variants
 		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
-		if (S.any_alpha) nee_shade_sun<true, true, true, SPDF>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<true, false, true, SPDF>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
+		if (S.any_alpha) nee_shade_sun<true, true, true, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
+		else nee_shade_sun<true, false, true, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
 	} else if (S.any_texture) {
-		if (S.any_alpha) nee_shade_sun<true, true, false, SPDF>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<true, false, false, SPDF>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
+		if (S.any_alpha) nee_shade_sun<true, true, false, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
+		else nee_shade_sun<true, false, false, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
 	} else {
-		if (S.any_alpha) nee_shade_sun<false, true, false, SPDF>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<false, false, false, SPDF>(sun, grid, stream, S, P, Lt, Ev, in, H, n, out, W, cnt, L);
+		if (S.any_alpha) nee_shade_sun<false, true, false, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
+		else nee_shade_sun<false, false, false, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
 	}
 	return hipGetLastError();
 }
 
-// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF
-hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, const NeeStream& in, const NeeHits& H, uint32_t n,
+// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF; candidates > 1: the RIS variants with M = candidates (PTX_NEE_CANDIDATES)
+hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, uint32_t candidates, const NeeStream& in, const NeeHits& H, uint32_t n,
                             const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
-	return sampler_pdf ? launch_nee_shade_variant<true>(S, P, Lt, Ev, in, H, n, out, W, cnt, L, stream) : launch_nee_shade_variant<false>(S, P, Lt, Ev, in, H, n, out, W, cnt, L, stream);
+	if (candidates > 1)
+		return sampler_pdf ? launch_nee_shade_variant<true, true>(S, P, Lt, Ev, candidates, in, H, n, out, W, cnt, L, stream)
+		                   : launch_nee_shade_variant<false, true>(S, P, Lt, Ev, candidates, in, H, n, out, W, cnt, L, stream);
+	return sampler_pdf ? launch_nee_shade_variant<true, false>(S, P, Lt, Ev, 1u, in, H, n, out, W, cnt, L, stream) : launch_nee_shade_variant<false, false>(S, P, Lt, Ev, 1u, in, H, n, out, W, cnt, L, stream);
 }
 
 hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, hipStream_t stream) {

@@ -7,6 +7,7 @@
 namespace ptx {
 
 enum { BLOCK_LIGHT = 3, BLOCK_ENV = 4 };   // Philox blocks of the light sample's and the environment sample's draws (BLOCK_SURFACE / BLOCK_SUN / BLOCK_JITTER: device_core.hpp)
+enum { BLOCK_RIS = 0x100 };                // PTX_NEE_CANDIDATES: candidate j draws from blocks BLOCK_LIGHT + 2 j and BLOCK_ENV + 2 j, selection j from component j & 3 of block BLOCK_RIS + (j >> 2)
 
 // sample id within the pass (sample-major, pixel-minor) -> image pixel and global sample index, as k_render_pass enumerates them
 DEV void nee_sample_of(const RenderParams& P, uint32_t id, uint32_t& px, uint32_t& py, uint32_t& sample) {
@@ -91,6 +92,97 @@ struct NeeVertex {
 	uint32_t exp_surf = 0, exp_tri = 0;
 };
 
+// One candidate light sample of a vertex (include/ptx.h: LIGHT SAMPLE, and SELECTION / ENVIRONMENT SAMPLE with ENV, ps with SPDF), drawn from the
+// Philox blocks block_light / block_env: the vertex's position and frame, its material terms and T before its update. A candidate that
+// contributes sets `want`; then lx is its x, (lo, ld) its shadow ray and (exp_surf, exp_tri) its visibility rule. Otherwise nothing is written.
+// The unflagged vertex takes one, from BLOCK_LIGHT / BLOCK_ENV, straight into its NeeVertex — `want` is set in place, not returned: the
+// statements are then the former ones, and the unflagged kernels keep their registers. The RIS vertex takes M of them.
+template <bool TEX, bool ENV, bool SPDF>
+DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, float c_env, uint32_t pixel, uint32_t sample, uint32_t depth, uint32_t pass,
+                       uint32_t block_light, uint32_t block_env, const Surf& sf, V3 normal, V3 outcoming, V3 T, const MatEval& me, float roughness, float spec_prob, V3& lx, V3& lo, V3& ld,
+                       uint32_t& exp_surf, uint32_t& exp_tri, bool& want) {
+	bool to_env = false;
+	if constexpr (ENV) {
+		to_env = Lt.n == 0 || draws(P, pixel, sample, depth, pass, block_light).w < 0.5F;
+		if (to_env) {
+			const float4 q = draws(P, pixel, sample, depth, pass, block_env);
+			const uint32_t j = env_pick(Ev.row_cdf, Ev.h, q.x);
+			const uint32_t i = env_pick(Ev.cell_cdf + (size_t)j * Ev.w, Ev.w, q.y);
+			const float u = ((float)i + q.z) / (float)Ev.w, v = 1 - ((float)j + q.w) / (float)Ev.h;
+			const float phi = (u - 0.5F) / 0.1591F, lat = (v - 0.5F) / 0.3183F;
+			const float cl = cosf(lat);
+			const V3 w = mk(cl * cosf(phi), sinf(lat), cl * sinf(phi));
+			float fu, fv;
+			uint32_t fi, fj;
+			env_box(Ev, w, fu, fv, fi, fj);   // the lookup's own (u, v): a sample it maps to another box is dropped, so the pdf stays a function of direction
+			if (fi == i && fj == j && dot(normal, w) > 0) {
+				const float p = env_pdf_box(Ev, w, fi, fj);
+				const float4 e = tex_sample(S, S.env_tex, fu, fv);
+				const V3 Le = mk(e.x, e.y, e.z) * mk(P.env[0], P.env[1], P.env[2]);
+				if (p > 0 && pmax(Le.x, pmax(Le.y, Le.z)) > 0) {
+					float pdf;
+					const V3 brdf = eval_brdf(normal, outcoming, w, me.albedo, roughness, me.metallic, spec_prob, pdf);
+					const float pe = pmax(pdf, kEps);
+					const V3 qv = brdf / pe;
+					const V3 qc = mk(clampf(qv.x, 0, 1), clampf(qv.y, 0, 1), clampf(qv.z, 0, 1));
+					float pw = pe;
+					if constexpr (SPDF) pw = sampler_pdf(normal, outcoming, w, roughness, spec_prob);
+					if (!SPDF || pw > 0) {   // a direction the BSDF sampler cannot produce carries nothing
+						const float wl = pw / (pw + c_env * p);
+						lx = ((T * qc) * wl) * Le;
+						lo = sf.pos + w * kEps;
+						ld = w;
+						exp_surf = kNeeEnvRay; exp_tri = 0;
+						want = true;
+					}
+				}
+			}
+		}
+	}
+	if (Lt.n != 0 && !to_env) {
+		const float4 r = draws(P, pixel, sample, depth, pass, block_light);
+		uint32_t a = 0, b = Lt.n;   // first entry with r.x < cdf
+		while (a < b) {
+			const uint32_t mid = a + (b - a) / 2;
+			if (r.x < Lt.cdf[mid]) b = mid; else a = mid + 1;
+		}
+		const uint32_t k = a < Lt.n - 1 ? a : Lt.n - 1;
+		const float su = sqrt_exact(r.y), beta = su * (1 - r.z), gamma = su * r.z;
+		const uint2 lt = Lt.tris[k];
+		const ShadeRec& Ry = S.shade[lt.x];
+		Surf sy;
+		hit_attributes(S, Ry, lt.y + S.surfaces[lt.x].tri_base, beta, gamma, sy);
+		const MatEval my = material_eval<TEX>(S, Ry.mat, sy.u, sy.v);
+		const V3 n_y = shading_normal(sy, my.normal_ts), Le = my.emissive10;
+		const V3 v = sy.pos - sf.pos;
+		const float dist2 = dot(v, v);
+		if (dist2 > 0) {
+			const V3 w = v / sqrt_exact(dist2);
+			const float4 g = Lt.geom[k];
+			const float cg = fabsf(dot(mk(g.x, g.y, g.z), w));
+			if (dot(normal, w) > 0 && dot(n_y, -w) > 0 && cg > 0 && pmax(Le.x, pmax(Le.y, Le.z)) > 0) {
+				float pdf;
+				const V3 brdf = eval_brdf(normal, outcoming, w, me.albedo, roughness, me.metallic, spec_prob, pdf);
+				const float pe = pmax(pdf, kEps);
+				const V3 q = brdf / pe;
+				const V3 qc = mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));
+				float p_l = dist2 / (cg * Lt.area);
+				if constexpr (ENV) p_l = (1 - c_env) * p_l;
+				float pw = pe;
+				if constexpr (SPDF) pw = sampler_pdf(normal, outcoming, w, roughness, spec_prob);
+				if (!SPDF || pw > 0) {
+					const float wl = pw / (pw + p_l);
+					lx = ((T * qc) * wl) * Le;
+					lo = sf.pos + w * kEps;
+					ld = w;
+					exp_surf = lt.x; exp_tri = lt.y;
+					want = true;
+				}
+			}
+		}
+	}
+}
+
 // One vertex of one path. The hit: surface (< 0: miss), triangle within the surface's mesh, barycentrics b1, b2 and the world distance, as the
 // scene's intersect route reports them. TEX / ALPHA / SUN compile the texture lookups / the pass-through and catcher code / the sun request
 // in, as the render variants do. The statements are shade_vertex<SUN, ALPHA, TEX, false>'s, in its order, with the emission weighted and the
@@ -98,8 +190,9 @@ struct NeeVertex {
 // ENV (PTX_NEE_ENV_SAMPLES with a table, Ev): the light sample may go towards the environment map, and the map's radiance on a miss is weighted
 // against that sample. Without ENV, Ev is not read and the statements are the unflagged estimator's.
 // SPDF (PTX_NEE_SAMPLER_PDF): sampler_pdf takes pe's place in the two wl and in p_prev, and nowhere else. Without SPDF no statement changes.
-template <bool TEX, bool ALPHA, bool SUN, bool ENV = false, bool SPDF = false>
-DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t pixel, uint32_t sample, int32_t surf, uint32_t tri, float b1, float b2,
+// RIS (PTX_NEE_CANDIDATES(m), m > 1): the light sample is chosen among ris_m candidates. Without RIS ris_m is not read and no statement changes.
+template <bool TEX, bool ALPHA, bool SUN, bool ENV = false, bool SPDF = false, bool RIS = false>
+DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, uint32_t pixel, uint32_t sample, int32_t surf, uint32_t tri, float b1, float b2,
                     float hit_dist, V3& o, V3& d, V3& T, V3& L, float& p_prev, uint32_t& depth, uint32_t& pass, NeeVertex& out) {
 	bool& alive = out.alive;
 	bool& want_sun = out.want_sun;
@@ -199,84 +292,36 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 		store = true;
 		if (last) break;
 		// ---- light sample
-		bool to_env = false;
-		if constexpr (ENV) {
-			to_env = Lt.n == 0 || draws(P, pixel, sample, depth, pass, BLOCK_LIGHT).w < 0.5F;
-			if (to_env) {
-				const float4 q = draws(P, pixel, sample, depth, pass, BLOCK_ENV);
-				const uint32_t j = env_pick(Ev.row_cdf, Ev.h, q.x);
-				const uint32_t i = env_pick(Ev.cell_cdf + (size_t)j * Ev.w, Ev.w, q.y);
-				const float u = ((float)i + q.z) / (float)Ev.w, v = 1 - ((float)j + q.w) / (float)Ev.h;
-				const float phi = (u - 0.5F) / 0.1591F, lat = (v - 0.5F) / 0.3183F;
-				const float cl = cosf(lat);
-				const V3 w = mk(cl * cosf(phi), sinf(lat), cl * sinf(phi));
-				float fu, fv;
-				uint32_t fi, fj;
-				env_box(Ev, w, fu, fv, fi, fj);   // the lookup's own (u, v): a sample it maps to another box is dropped, so the pdf stays a function of direction
-				if (fi == i && fj == j && dot(normal, w) > 0) {
-					const float p = env_pdf_box(Ev, w, fi, fj);
-					const float4 e = tex_sample(S, S.env_tex, fu, fv);
-					const V3 Le = mk(e.x, e.y, e.z) * mk(P.env[0], P.env[1], P.env[2]);
-					if (p > 0 && pmax(Le.x, pmax(Le.y, Le.z)) > 0) {
-						float pdf;
-						const V3 brdf = eval_brdf(normal, outcoming, w, me.albedo, roughness, me.metallic, spec_prob, pdf);
-						const float pe = pmax(pdf, kEps);
-						const V3 qv = brdf / pe;
-						const V3 qc = mk(clampf(qv.x, 0, 1), clampf(qv.y, 0, 1), clampf(qv.z, 0, 1));
-						float pw = pe;
-						if constexpr (SPDF) pw = sampler_pdf(normal, outcoming, w, roughness, spec_prob);
-						if (!SPDF || pw > 0) {   // a direction the BSDF sampler cannot produce carries nothing
-							const float wl = pw / (pw + c_env * p);
-							lx = ((T * qc) * wl) * Le;
-							lo = sf.pos + w * kEps;
-							ld = w;
-							exp_surf = kNeeEnvRay; exp_tri = 0;
-							want_light = true;
-						}
-					}
+		if constexpr (!RIS) {
+			nee_candidate<TEX, ENV, SPDF>(S, P, Lt, Ev, c_env, pixel, sample, depth, pass, BLOCK_LIGHT, BLOCK_ENV, sf, normal, outcoming, T, me, roughness, spec_prob, lx, lo, ld,
+			                              exp_surf, exp_tri, want_light);
+		} else {
+			// M candidates, one kept by weighted reservoir selection (include/ptx.h: PTX_NEE_CANDIDATES). The reservoir is lx, ld, the visibility
+			// rule, wsum and the chosen weight; lo follows from ld.
+			float wsum = 0, w_y = 0;
+			for (uint32_t j = 0; j < ris_m; j++) {
+				V3 cx = {0, 0, 0}, co = {0, 0, 0}, cd = {0, 0, 1};
+				uint32_t cs = 0, ct = 0;
+				bool cw = false;
+				nee_candidate<TEX, ENV, SPDF>(S, P, Lt, Ev, c_env, pixel, sample, depth, pass, BLOCK_LIGHT + 2 * j, BLOCK_ENV + 2 * j, sf, normal, outcoming, T, me, roughness, spec_prob, cx, co, cd,
+				                              cs, ct, cw);
+				if (!cw) continue;
+				const float w_j = pmax(cx.x, pmax(cx.y, cx.z));
+				if (!(w_j > 0 && w_j < __builtin_inff())) continue;
+				wsum = wsum + w_j;
+				bool take = !want_light;   // the first kept candidate is chosen outright
+				if (!take) {
+					const float4 u4 = draws(P, pixel, sample, depth, pass, BLOCK_RIS + (j >> 2));
+					const uint32_t c = j & 3u;
+					const float u = c == 0 ? u4.x : c == 1 ? u4.y : c == 2 ? u4.z : u4.w;
+					take = u * wsum < w_j;
 				}
+				if (take) { lx = cx; ld = cd; exp_surf = cs; exp_tri = ct; w_y = w_j; }
+				want_light = true;
 			}
-		}
-		if (Lt.n != 0 && !to_env) {
-			const float4 r = draws(P, pixel, sample, depth, pass, BLOCK_LIGHT);
-			uint32_t a = 0, b = Lt.n;   // first entry with r.x < cdf
-			while (a < b) {
-				const uint32_t mid = a + (b - a) / 2;
-				if (r.x < Lt.cdf[mid]) b = mid; else a = mid + 1;
-			}
-			const uint32_t k = a < Lt.n - 1 ? a : Lt.n - 1;
-			const float su = sqrt_exact(r.y), beta = su * (1 - r.z), gamma = su * r.z;
-			const uint2 lt = Lt.tris[k];
-			const ShadeRec& Ry = S.shade[lt.x];
-			Surf sy;
-			hit_attributes(S, Ry, lt.y + S.surfaces[lt.x].tri_base, beta, gamma, sy);
-			const MatEval my = material_eval<TEX>(S, Ry.mat, sy.u, sy.v);
-			const V3 n_y = shading_normal(sy, my.normal_ts), Le = my.emissive10;
-			const V3 v = sy.pos - sf.pos;
-			const float dist2 = dot(v, v);
-			if (dist2 > 0) {
-				const V3 w = v / sqrt_exact(dist2);
-				const float4 g = Lt.geom[k];
-				const float cg = fabsf(dot(mk(g.x, g.y, g.z), w));
-				if (dot(normal, w) > 0 && dot(n_y, -w) > 0 && cg > 0 && pmax(Le.x, pmax(Le.y, Le.z)) > 0) {
-					float pdf;
-					const V3 brdf = eval_brdf(normal, outcoming, w, me.albedo, roughness, me.metallic, spec_prob, pdf);
-					const float pe = pmax(pdf, kEps);
-					const V3 q = brdf / pe;
-					const V3 qc = mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));
-					float p_l = dist2 / (cg * Lt.area);
-					if constexpr (ENV) p_l = (1 - c_env) * p_l;
-					float pw = pe;
-					if constexpr (SPDF) pw = sampler_pdf(normal, outcoming, w, roughness, spec_prob);
-					if (!SPDF || pw > 0) {
-						const float wl = pw / (pw + p_l);
-						lx = ((T * qc) * wl) * Le;
-						lo = sf.pos + w * kEps;
-						ld = w;
-						exp_surf = lt.x; exp_tri = lt.y;
-						want_light = true;
-					}
-				}
+			if (want_light) {
+				lx = lx * ((wsum / (float)ris_m) / w_y);
+				lo = sf.pos + ld * kEps;
 			}
 		}
 		// ---- BSDF sample

@@ -18,12 +18,14 @@ namespace ptx {
 // 768 threads = 3 waves per SIMD = 168 VGPRs hold the variants without texture and sun code (158-165 VGPRs); the others need 174-210 and
 // get 512 threads = 2 waves per SIMD = 256 VGPRs; so do the ENV variants (always TEX: 207-228 VGPRs). Occupancy is what the kernel runs on (Cornell: 256 threads 185, 512 353, 768 465 Msamples/s;
 // DESIGN.md 5.7 has the resource table and the measurement). Staging is per workgroup and there is one workgroup per CU either way; the
-// overflow stacks are sized per wave slot of the larger k_render_pass workgroup. -DPTX_NEE_FUSED_BLOCK=n: one size for all (measurement).
-constexpr int nee_fused_block(bool tex, bool sun, bool env = false) {
+// overflow stacks are sized per wave slot of the larger k_render_pass workgroup. The RIS variants (PTX_NEE_CANDIDATES) carry the reservoir across the
+// candidate loop: those without texture and sun code spill 2 to 4 VGPRs at 768 threads and get 512 as well; the others stay without scratch at 512 (198-255 VGPRs).
+// -DPTX_NEE_FUSED_BLOCK=n: one size for all (measurement).
+constexpr int nee_fused_block(bool tex, bool sun, bool env = false, bool ris = false) {
 #ifdef PTX_NEE_FUSED_BLOCK
 	return PTX_NEE_FUSED_BLOCK;
 #else
-	return (tex || sun || env) ? 512 : 768;
+	return (tex || sun || env || ris) ? 512 : 768;
 #endif
 }
 static_assert(nee_fused_block(false, false) % 64 == 0 && nee_fused_block(true, true) % 64 == 0 && nee_fused_block(false, false) <= kBlock && nee_fused_block(true, true) <= kBlock,
@@ -37,11 +39,12 @@ DEV uint32_t wave_sum(uint32_t v) {
 // ENV: the variants of PTX_NEE_ENV_SAMPLES (TEX only); Ev, the last argument, is read by them alone.
 // SPDF: the variants of PTX_NEE_SAMPLER_PDF. sampler_pdf costs them 0 to 2 VGPRs, and each compiles without scratch at its unflagged
 // twin's workgroup size, so nee_fused_block holds for them too (DESIGN.md 5.7 has their rows).
-template <int MODE, bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false>
-__global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
+// RIS: the variants of PTX_NEE_CANDIDATES, the light sample chosen among ris_m candidates; the other variants do not read ris_m.
+template <int MODE, bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false, bool RIS = false>
+__global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV, RIS)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
                                                               const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space,
-                                                              NeeEnv Ev) {
-	constexpr int kThreads = nee_fused_block(TEX, SUN, ENV);
+                                                              NeeEnv Ev, uint32_t ris_m) {
+	constexpr int kThreads = nee_fused_block(TEX, SUN, ENV, RIS);
 	DevScene S = S0;
 	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;  // see struct Tables
 	const Staged st = stage_geometry<MODE>(S, g_smem);
@@ -117,7 +120,7 @@ __global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV)) k_nee_fused(De
 			const int32_t surf = hit ? h.surface : -1;
 			const uint32_t tri = hit ? (h.tri & S.tri_id_mask) - S.surfaces[h.surface].tri_base : 0u;
 			NeeVertex v;
-			nee_vertex<TEX, ALPHA, SUN, ENV, SPDF>(S, P, Lt, Ev, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v);
+			nee_vertex<TEX, ALPHA, SUN, ENV, SPDF, RIS>(S, P, Lt, Ev, ris_m, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v);
 			bool alive = v.alive;
 			// ---------------- the sun ray: occluded = any hit
 			if constexpr (SUN) {
@@ -173,55 +176,73 @@ static hipError_t set_lds(const void* fn, size_t bytes) {
 	return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-template <int MODE, bool SPDF, bool TEX, bool ALPHA, bool SUN, bool ENV = false>
-static hipError_t launch_nee_fused_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
-	const auto kernel = &k_nee_fused<MODE, TEX, ALPHA, SUN, ENV, SPDF>;
+template <int MODE, bool SPDF, bool RIS, bool TEX, bool ALPHA, bool SUN, bool ENV = false>
+static hipError_t launch_nee_fused_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
+	const auto kernel = &k_nee_fused<MODE, TEX, ALPHA, SUN, ENV, SPDF, RIS>;
 	if (MODE != MODE_GLOBAL) {
 		hipError_t e = set_lds(reinterpret_cast<const void*>(kernel), lds_bytes);
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL(kernel, dim3(grid), dim3(nee_fused_block(TEX, SUN, ENV)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces, S.spaces, S.model_space, Ev);
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(nee_fused_block(TEX, SUN, ENV, RIS)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces, S.spaces, S.model_space, Ev, ris_m);
 	return hipGetLastError();
 }
 
 // the variants of launch_nee_shade, per place of the geometry
-template <int MODE, bool SPDF>
-static hipError_t launch_nee_fused_mode(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
+template <int MODE, bool SPDF, bool RIS>
+static hipError_t launch_nee_fused_mode(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
 	const bool sun = S.sun.present != 0;
 	if (Ev.row_cdf) {   // a table means a map, and a map means the TEX variants
 		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
-		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, true, true, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, true, true, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
-		return sun ? launch_nee_fused_variant<MODE, SPDF, true, false, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, true, false, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, true, true, true, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, true, true, false, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
+		return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, true, false, true, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, true, false, false, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
 	}
 	if (S.any_texture) {
-		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, true, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, true, true, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
-		return sun ? launch_nee_fused_variant<MODE, SPDF, true, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, true, false, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, true, true, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, true, true, false>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
+		return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, true, false, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, true, false, false>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
 	}
-	if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, false, true, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, false, true, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
-	return sun ? launch_nee_fused_variant<MODE, SPDF, false, false, true>(S, P, Lt, Ev, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, false, false, false>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+	if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, false, true, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, false, true, false>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
+	return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, false, false, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, false, false, false>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
 }
 
-template <bool SPDF>
-static hipError_t launch_nee_fused_all(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream) {
-	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS, SPDF>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
-	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID, SPDF>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
-	return launch_nee_fused_mode<MODE_GLOBAL, SPDF>(S, P, Lt, Ev, B, lds_bytes, grid, stream);
+template <bool SPDF, bool RIS>
+static hipError_t launch_nee_fused_all(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
+                                       hipStream_t stream) {
+	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS, SPDF, RIS>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
+	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID, SPDF, RIS>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
+	return launch_nee_fused_mode<MODE_GLOBAL, SPDF, RIS>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
 }
 
-// This file is compiled twice, so that the two halves of the variants build side by side: as itself (the unflagged variants and
-// launch_nee_fused), and through nee_fused_spdf.hip, which defines PTX_NEE_FUSED_SPDF_TU (the variants of PTX_NEE_SAMPLER_PDF).
+// This file is compiled four times, so that the four quarters of the variants build side by side: as itself (the unflagged variants and
+// launch_nee_fused), through nee_fused_spdf.hip, which defines PTX_NEE_FUSED_SPDF_TU (the variants of PTX_NEE_SAMPLER_PDF), through
+// nee_fused_ris.hip, which defines PTX_NEE_FUSED_RIS_TU (the variants of PTX_NEE_CANDIDATES), and through nee_fused_ris_spdf.hip, which defines both.
 hipError_t launch_nee_fused_sampler_pdf(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
                                         hipStream_t stream);
-#ifdef PTX_NEE_FUSED_SPDF_TU
+hipError_t launch_nee_fused_ris(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
+                                hipStream_t stream);
+hipError_t launch_nee_fused_ris_sampler_pdf(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, int mode, size_t lds_bytes,
+                                            int grid, hipStream_t stream);
+#if defined(PTX_NEE_FUSED_RIS_TU) && defined(PTX_NEE_FUSED_SPDF_TU)
+hipError_t launch_nee_fused_ris_sampler_pdf(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, int mode, size_t lds_bytes,
+                                            int grid, hipStream_t stream) {
+	return launch_nee_fused_all<true, true>(S, P, Lt, Ev, ris_m, B, mode, lds_bytes, grid, stream);
+}
+#elif defined(PTX_NEE_FUSED_RIS_TU)
+hipError_t launch_nee_fused_ris(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
+                                hipStream_t stream) {
+	return launch_nee_fused_all<false, true>(S, P, Lt, Ev, ris_m, B, mode, lds_bytes, grid, stream);
+}
+#elif defined(PTX_NEE_FUSED_SPDF_TU)
 hipError_t launch_nee_fused_sampler_pdf(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
                                         hipStream_t stream) {
-	return launch_nee_fused_all<true>(S, P, Lt, Ev, B, mode, lds_bytes, grid, stream);
+	return launch_nee_fused_all<true, false>(S, P, Lt, Ev, 1u, B, mode, lds_bytes, grid, stream);
 }
 #else
-// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF
-hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
-                            hipStream_t stream) {
-	return sampler_pdf ? launch_nee_fused_sampler_pdf(S, P, Lt, Ev, B, mode, lds_bytes, grid, stream) : launch_nee_fused_all<false>(S, P, Lt, Ev, B, mode, lds_bytes, grid, stream);
+// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF; candidates > 1: the RIS variants with M = candidates (PTX_NEE_CANDIDATES)
+hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, uint32_t candidates, const NeeFusedBuffers& B, int mode,
+                            size_t lds_bytes, int grid, hipStream_t stream) {
+	if (candidates > 1)
+		return sampler_pdf ? launch_nee_fused_ris_sampler_pdf(S, P, Lt, Ev, candidates, B, mode, lds_bytes, grid, stream) : launch_nee_fused_ris(S, P, Lt, Ev, candidates, B, mode, lds_bytes, grid, stream);
+	return sampler_pdf ? launch_nee_fused_sampler_pdf(S, P, Lt, Ev, B, mode, lds_bytes, grid, stream) : launch_nee_fused_all<false, false>(S, P, Lt, Ev, 1u, B, mode, lds_bytes, grid, stream);
 }
 #endif
 

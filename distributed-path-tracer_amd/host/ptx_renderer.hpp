@@ -31,6 +31,7 @@ public:
 	uint32_t sun_light_index = 0;
 	uint8_t visualize_kd_tree_depth = 0;   // not built: mesh.cpp:316-318 colours each KD node by its heap address, nothing reproducible to mirror
 	uint64_t seed = 0x5EED;                // key of the counter-based RNG (the reference seeds from random_device)
+	uint32_t nee_candidates = 1;           // render_nee and its kin: the light sample is picked among this many candidates, 1 .. 16 (PTX_NEE_CANDIDATES)
 	// render_adaptive (no counterpart in the reference): the threshold of the stopping rule, the samples every pixel gets first and the samples
 	// per further round (0 = adaptive_min); sample_count is the cap
 	float adaptive_threshold = 0.1f;
@@ -185,7 +186,7 @@ public:
 		for (int k = 0; k < 3; k++) c.env[k] = environment_factor[k];
 		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
 		const ptx_adaptive_cfg ac{adaptive_min, adaptive_step, adaptive_threshold};
-		const ptx_nee_cfg n{flags};
+		const ptx_nee_cfg n{flags | nee_bits()};
 		const size_t floats = (size_t)c.W * c.H * 4;
 		std::vector<float> a(floats, 0.f), b(floats, 0.f);
 		check(ptx_render_adaptive_nee(scene_, &c, &ac, &n, a.data(), b.data(), stats));
@@ -208,7 +209,7 @@ public:
 		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
 		const size_t floats = (size_t)c.W * c.H * 4;
 		std::vector<float> a(floats, 0.f), b(floats, 0.f), alb(floats, 0.f), nd(floats, 0.f);
-		const ptx_nee_cfg n{flags};
+		const ptx_nee_cfg n{flags | nee_bits()};
 		c.spp = sample_count / 2;
 		check(ptx_render_nee(scene_, &c, &n, a.data(), nullptr));
 		c.sample0 = c.spp; c.spp = sample_count - c.sample0;
@@ -222,10 +223,17 @@ public:
 		return a;
 	}
 
+	// nee_candidates as the bits of ptx_nee_cfg::flags
+	uint32_t nee_bits() const {
+		if (nee_candidates < 1 || nee_candidates > 16) throw std::runtime_error("nee_candidates must be 1 .. 16");
+		return PTX_NEE_CANDIDATES(nee_candidates);
+	}
+
 	// Radiance sums [H][W][4] of the frame with next-event estimation towards the scene's emissive triangles (ptx_render_nee): render_accum()'s
 	// samples plus one MIS-weighted light sample per continuing vertex; the same expectation, less noise where emitters light the scene.
 	// Write them with encode(sums, sample_count). stats optional; flags: ptx_nee_cfg::flags (PTX_NEE_FUSED: the same frame from one kernel launch per pass;
-	// PTX_NEE_ENV_SAMPLES: the light sample may go towards `environment` too; PTX_NEE_SAMPLER_PDF: MIS weights on the density of LIB's BSDF sampler)
+	// PTX_NEE_ENV_SAMPLES: the light sample may go towards `environment` too; PTX_NEE_SAMPLER_PDF: MIS weights on the density of LIB's BSDF sampler),
+	// to which nee_candidates adds its bits
 	std::vector<float> render_nee(ptx_nee_stats* stats = nullptr, uint32_t flags = 0) const {
 		if (!scene_) throw std::runtime_error("render_nee() before load_gltf()");
 		if (transparent_background) throw std::runtime_error("render_nee: transparent_background's blend is not built on this estimator");
@@ -238,7 +246,7 @@ public:
 		for (int k = 0; k < 3; k++) c.env[k] = environment_factor[k];
 		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
 		std::vector<float> accum((size_t)c.W * c.H * 4, 0.f);
-		const ptx_nee_cfg n{flags};
+		const ptx_nee_cfg n{flags | nee_bits()};
 		check(ptx_render_nee(scene_, &c, &n, accum.data(), stats));
 		return accum;
 	}

@@ -1,6 +1,6 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
 //       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
 //       --nee:         light sampling towards the scene's emissive triangles (renderer::render_nee)
@@ -9,9 +9,11 @@
 //                      towards the map too (PTX_NEE_ENV_SAMPLES); combines with --nee-fused
 //       --nee-sampler-pdf: --nee with the MIS weights built on the density of the BSDF sampler (PTX_NEE_SAMPLER_PDF): the frame's expectation
 //                      is the plain renderer's at glossy vertices too; combines with --nee-fused, --nee-env and --adaptive
+//       --nee-candidates M: --nee with the light sample of a vertex picked among M = 1 .. 16 candidates, still one shadow ray
+//                      (PTX_NEE_CANDIDATES); combines with --nee-fused, --nee-env, --nee-sampler-pdf and --adaptive
 //       --adaptive THR[:MIN[:STEP]]: noise-driven per-pixel sample counts (renderer::render_adaptive) with spp as the cap: every pixel gets MIN
 //                      samples (8), then rounds of STEP (MIN) go to the pixels whose half-frames still disagree by more than THR
-//       combinations:  --adaptive with --nee / --nee-fused / --nee-env / --nee-sampler-pdf renders the adaptive loop on the light-sampling estimator
+//       combinations:  --adaptive with --nee / --nee-fused / --nee-env / --nee-sampler-pdf / --nee-candidates renders the adaptive loop on the light-sampling estimator
 //                      (renderer::render_adaptive_nee); --adaptive --denoise, with or without --nee*, filters the adaptive frame
 //                      (ptx_denoise_counts on the guides of the first MIN samples); --nee* --denoise filters two light-sampled half-frames
 //                      (renderer::render_nee_denoised). --transparent combines with none of them
@@ -45,7 +47,7 @@ static void write_png(const std::string& path, const std::vector<uint8_t>& rgba,
 int main(int argc, char** argv) {
 	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false, nee_sampler_pdf = false;
 	float ad_thr = 0.1f;
-	unsigned ad_min = 8, ad_step = 0;
+	unsigned ad_min = 8, ad_step = 0, nee_candidates = 1;
 	std::string aov_prefix, nee_env;
 	for (;;) {   // leading switches
 		if (argc > 1 && std::string(argv[1]) == "--transparent") { transparent = true; argv[1] = argv[0]; argv++; argc--; }
@@ -54,6 +56,10 @@ int main(int argc, char** argv) {
 		else if (argc > 1 && std::string(argv[1]) == "--nee-fused") { nee = nee_fused = true; argv[1] = argv[0]; argv++; argc--; }   // ... one launch per pass
 		else if (argc > 1 && std::string(argv[1]) == "--nee-sampler-pdf") { nee = nee_sampler_pdf = true; argv[1] = argv[0]; argv++; argc--; }   // ... weights on the sampler's density
 		else if (argc > 2 && std::string(argv[1]) == "--nee-env") { nee = true; nee_env = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }   // ... the map as a light
+		else if (argc > 2 && std::string(argv[1]) == "--nee-candidates") {   // ... picked among M candidates
+			if (std::sscanf(argv[2], "%u", &nee_candidates) < 1 || nee_candidates < 1 || nee_candidates > 16) { std::fprintf(stderr, "error: --nee-candidates M, M = 1 .. 16\n"); return 1; }
+			nee = true; argv[2] = argv[0]; argv += 2; argc -= 2;
+		}
 		else if (argc > 2 && std::string(argv[1]) == "--adaptive") {
 			if (std::sscanf(argv[2], "%f:%u:%u", &ad_thr, &ad_min, &ad_step) < 1) { std::fprintf(stderr, "error: --adaptive THR[:MIN[:STEP]]\n"); return 1; }
 			adaptive = true; argv[2] = argv[0]; argv += 2; argc -= 2;
@@ -62,7 +68,7 @@ int main(int argc, char** argv) {
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (argc == 5 && std::string(argv[1]) == "--event") {
@@ -101,6 +107,7 @@ int main(int argc, char** argv) {
 		}
 		r.load_gltf(argv[1]);
 		if (!nee_env.empty()) r.environment = nee_env;
+		r.nee_candidates = nee_candidates;
 		auto t0 = std::chrono::steady_clock::now();
 		ptx_denoise_stats dst{};
 		ptx_adaptive_stats ast{};

@@ -526,6 +526,33 @@ int ptx_ctx_get_mask_exchange_stats(ptx_ctx* ctx, uint64_t* calls /* NULL ok */,
  * PTX_NEE_NO_LIGHT_SAMPLES; ptx_render_adaptive_nee passes it through. With no light sample possible (empty list and no environment table)
  * every weight is exactly 1 and the call is bit for bit the one without the flag. Without the flag nothing changes. */
 #define PTX_NEE_SAMPLER_PDF 64u
+/* PTX_NEE_CANDIDATES(m), m = 1 .. 16: the light sample of a vertex is picked among M = m candidates in proportion to their unshadowed
+ * contributions (resampled importance sampling), and ONE shadow ray is traced for it. The count travels in bits 8..11 of flags:
+ * M = ((flags >> 8) & 15) + 1, so PTX_NEE_CANDIDATES(1) is 0, the call without it. Bits at 4096 and above, and the values 2, 8, 32 and 128,
+ * stay unassigned and refused as unknown. The estimator for M > 1 is the text of ptx_render_nee above with the LIGHT SAMPLE paragraph
+ * replaced by the following; IEEE binary32, each operation rounded on its own, in the order written.
+ *   CANDIDATES. Candidate j = 0 .. M - 1 is the light sample of the call without these bits, taken verbatim (with PTX_NEE_ENV_SAMPLES its
+ *     SELECTION and ENVIRONMENT SAMPLE, with PTX_NEE_SAMPLER_PDF its ps), with Philox block 3 + 2 j in the place of block 3 and block
+ *     4 + 2 j in the place of block 4: candidate 0 is that call's sample. A candidate that there contributes nothing and traces no shadow
+ *     ray is dropped. A surviving one yields its x_j, its shadow ray and its visibility rule (the closest hit is triangle i of that surface,
+ *     or: the ray hits nothing).
+ *   WEIGHT AND SELECTION. W_j = max(x_j.r, x_j.g, x_j.b); a candidate whose W_j is not a positive finite number is dropped. For every kept
+ *     candidate, in the order of j: wsum = wsum + W_j; u_j = component j & 3 of draws(pixel, sample, depth, pass, block 0x100 + (j >> 2));
+ *     the first kept candidate is chosen outright, a later one replaces the choice iff u_j * wsum < W_j.
+ *   ESTIMATE. No kept candidate: no light ray. Otherwise, for the chosen y, x = x_y * ((wsum / (float)M) / W_y), with y's shadow ray and
+ *     visibility rule. M counts all candidates, the dropped ones included.
+ * Nothing else changes: the emission weight, the miss weight, p_prev, qc, the T update, the sun term, the order of the additions and the
+ * draws of every other block. In particular p_l and env_pdf in the BSDF-side weights stay the densities of a SINGLE candidate.
+ * light_samples and light_visible count the light rays traced: at most one per vertex.
+ * The expectation is still LIB's. Every x_j is already F(y_j) / p(y_j), with F the MIS-weighted integrand of the light side and p the
+ * density of one candidate (the mixture over triangles and map, selection probability included). Resampling with the target
+ * W = max(F) / p is unbiased for the integral of F: E[(F(y) / max(F(y))) * (1 / M) sum_j W_j * V(y)] = integral of F V. The light-side and
+ * the BSDF-side weights are functions of the direction alone that still add to one, so the two sides together integrate LIB's vertex.
+ * What falls is the variance (DESIGN.md 5.7 has the measurement), at the price of M - 1 further candidates' arithmetic and no further ray.
+ * Combines with every other flag; ptx_render_adaptive_nee passes the bits through. With PTX_NEE_FUSED the frame and the stats equal the
+ * unfused call's with the same bits (on the queue route PTX_NEE_FUSED is ignored as above). With no light sample possible (empty list and
+ * no environment table) no candidate is drawn, and the call is bit for bit the one without the bits, and ptx_render. */
+#define PTX_NEE_CANDIDATES(m) ((((uint32_t)(m)) - 1u) << 8)   /* m = 1 .. 16; m = 1 is 0: today's call */
 typedef struct ptx_nee_cfg { uint32_t flags; } ptx_nee_cfg;
 typedef struct ptx_nee_stats {
 	ptx_render_stats render;   /* rays = closest-hit + shadow queries */

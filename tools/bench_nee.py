@@ -25,6 +25,13 @@
                                         written bytes of each against the product's ref_spp ptx_render frame of another seed, and the ratio of
                                         each frame's mean linear radiance (R, G, B) to that frame's. Also writes the lines to
                                         profiles/nee_sampler_pdf_bench.txt.
+  tools/bench_nee.py --ris [ref_spp] [reps] [spp]
+                                        PTX_NEE_CANDIDATES on Cornell and on procedural.emitter_cloud_scene (271 listed triangles) at 1920 x 1080,
+                                        8 bounces, 16 spp, with and without PTX_NEE_FUSED: M = 1, 2, 4, 8 alternate in one process, each kept at
+                                        the smallest of `reps` synchronised calls after a warm-up. Per row: the time, light rays traced per sample,
+                                        the mean squared error of the written bytes against the product's ref_spp ptx_render frame (4096) of
+                                        another seed, and the error of M = 1 in the same form at the spp that takes the row's time. Also writes the
+                                        lines to profiles/nee_ris_bench.txt.
 Prints one JSON line per measurement. A scene without listed emitters (atrium) shows the cost of the wavefront form alone.
 """
 import importlib
@@ -242,7 +249,57 @@ def main_sampler_pdf(ref_spp, reps):
         f.write("tools/bench_nee.py --sampler-pdf: PTX_NEE_SAMPLER_PDF against the same ptx_render_nee call without it, fused and unfused, MI355X\n" + "\n".join(lines) + "\n")
 
 
+def main_ris(ref_spp, reps, spp):
+    ctx = ptx.Context(0)
+    lines = []
+    cases = [("cornell", lambda: ptx.Scene.load_gltf(ctx, CORNELL)),
+             ("emitter_cloud", lambda: ptx.Scene.from_arrays(ctx, *[proc.emitter_cloud_scene()[k] for k in KEYS]))]
+    for name, make in cases:
+        s = make()
+        ref_acc = zeros()
+        s.render(W, H, ref_spp, BOUNCES, accum=ref_acc, seed=REF_SEED, want_stats=False)
+        ctx.synchronize()
+        ref = ctx.tonemap_encode(ref_acc, W, H, ref_spp)[..., :3].astype(np.float64) / 255
+        del ref_acc
+
+        def mse(acc, n):
+            return float(np.mean((ctx.tonemap_encode(acc, W, H, n)[..., :3].astype(np.float64) / 255 - ref) ** 2))
+
+        def timed(forms, n):
+            """forms: {key: flags}, run alternately -> {key: (the smallest of `reps` synchronised calls after a warm-up, buffer, stats, launches)}"""
+            best = {k: 1e30 for k in forms}
+            acc, st, launches = {}, {}, {}
+            for rep in range(reps + 1):
+                for k, flags in forms.items():
+                    a = zeros()
+                    t0 = time.perf_counter()
+                    _, st[k] = s.render_nee(W, H, n, BOUNCES, accum=a, seed=SEED, flags=flags)
+                    ctx.synchronize()
+                    dt = time.perf_counter() - t0
+                    if rep:
+                        best[k] = min(best[k], dt)
+                    acc[k], launches[k] = a, ctx.timing()["fused_launches"]
+            return {k: (best[k], acc[k], st[k], launches[k]) for k in forms}
+        for form, base in (("fused", ptx.NEE_FUSED), ("unfused", 0)):
+            t = timed({m: base | ptx.NEE_CANDIDATES(m) for m in (1, 2, 4, 8)}, spp)
+            t1 = t[1][0]
+            for m, (sec, acc, st, launches) in t.items():
+                spp_eq = max(1, int(round(spp * sec / t1)))
+                eq_s, eq_acc, _, _ = timed({1: base}, spp_eq)[1] if m > 1 else (sec, acc, None, None)
+                lines.append(json.dumps(dict(scene=name, form=form, M=m, W=W, H=H, bounces=BOUNCES, spp=spp, n_lights=st["n_lights"], fused_launches=launches,
+                                             s=round(sec, 4), time_ratio_to_m1=round(sec / t1, 4), rays=st["rays"], light_samples_per_sample=round(st["light_samples"] / st["samples"], 4),
+                                             light_visible_per_sample=round(st["light_visible"] / st["samples"], 4), mse=mse(acc, spp),
+                                             m1_equal_time_spp=spp_eq, m1_equal_time_s=round(eq_s, 4), m1_equal_time_mse=mse(eq_acc, spp_eq), ref_spp=ref_spp)))
+                print(lines[-1], flush=True)
+        s.close()
+    with open(os.path.join(ROOT, "profiles", "nee_ris_bench.txt"), "w") as f:
+        f.write("tools/bench_nee.py --ris: PTX_NEE_CANDIDATES(M) against M = 1, fused and unfused, MI355X\n" + "\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--ris":
+        main_ris(int(sys.argv[2]) if len(sys.argv) > 2 else 4096, int(sys.argv[3]) if len(sys.argv) > 3 else 3, int(sys.argv[4]) if len(sys.argv) > 4 else 16)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--sampler-pdf":
         main_sampler_pdf(int(sys.argv[2]) if len(sys.argv) > 2 else 1024, int(sys.argv[3]) if len(sys.argv) > 3 else 3)
         sys.exit(0)
