@@ -29,7 +29,7 @@ NO_SUN_LIGHT = 0xFFFFFFFF  # core::renderer::no_sun_light, renderer.hpp:19
 (ARR_MODEL_XFORM, ARR_MODEL_AABB, ARR_MODEL_SURF, ARR_SURF_RANGE, ARR_MESH_AABB, ARR_VERTICES, ARR_TRIANGLES,
  ARR_MATERIALS, ARR_KD_NODES, ARR_KD_REFS, ARR_CAMERA, ARR_SUN, ARR_MODEL_NAMES, ARR_TEXTURES, ARR_TEXELS, ARR_SURF_TEX, ARR_TEXELS_F32,
  ARR_LIGHT_TRIS, ARR_LIGHT_CDF, ARR_LIGHT_GEOM, ARR_TRI_ISECT, ARR_RES_NODES, ARR_RES_REFS, ARR_RES_TRIS, ARR_LDS_ROOT,
- ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF) = range(28)
+ ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF, ARR_PUNCTUAL, ARR_PUNCTUAL_CDF) = range(30)
 LDS_LEAF_ORDER_BIT = 0x80000000  # ARR_LDS_ROOT: the surface's resident records are leaf-ordered (flat_scene.hpp)
 
 
@@ -212,6 +212,9 @@ def lib():
         L.ptx_scene_from_arrays.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_void_p)]
         L.ptx_scene_destroy.argtypes = [C.c_void_p]
         L.ptx_scene_set_environment.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        L.ptx_scene_set_punctual_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ptx_gltf_read_punctual_lights.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
+        L.ptx_gltf_read_punctual_lights.restype = C.c_int64
         L.ptx_scene_get_info.argtypes = [C.c_void_p, C.POINTER(SceneInfo)]
         L.ptx_scene_get_array.restype = C.c_int64
         L.ptx_scene_get_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -448,7 +451,8 @@ _ARR_DTYPE = {ARR_MODEL_XFORM: (np.float32, 12), ARR_MODEL_AABB: (np.float32, 6)
               ARR_TEXTURES: (np.uint32, 4), ARR_TEXELS: (np.uint8, 1), ARR_SURF_TEX: (np.int32, 7), ARR_TEXELS_F32: (np.float32, 1),
               ARR_LIGHT_TRIS: (np.uint32, 2), ARR_LIGHT_CDF: (np.float32, 1), ARR_LIGHT_GEOM: (np.float32, 4),
               ARR_TRI_ISECT: (np.uint32, 12), ARR_RES_NODES: (np.uint32, 2), ARR_RES_REFS: (np.uint32, 1), ARR_RES_TRIS: (np.uint32, 12),
-              ARR_LDS_ROOT: (np.uint32, 1), ARR_RES_PLAN: (np.uint32, 1), ARR_ENV_ROW_CDF: (np.float32, 1), ARR_ENV_CELL_CDF: (np.float32, 1)}
+              ARR_LDS_ROOT: (np.uint32, 1), ARR_RES_PLAN: (np.uint32, 1), ARR_ENV_ROW_CDF: (np.float32, 1), ARR_ENV_CELL_CDF: (np.float32, 1),
+              ARR_PUNCTUAL: (np.float32, 16), ARR_PUNCTUAL_CDF: (np.float32, 1)}
 
 
 class Scene:
@@ -652,6 +656,16 @@ class Scene:
         None removes the map."""
         _check(lib().ptx_scene_set_environment(self.h, os.fsencode(png_path) if png_path is not None else None, int(bool(srgb))))
 
+    def set_punctual_lights(self, lights):
+        """ptx_scene_set_punctual_lights: [n, 16] float32 records (position, range, direction, kind 0 point / 1 spot, intensity rgb, cos_inner,
+        cos_outer, three zeros), e.g. read_punctual_lights(path)'s. render_nee and render_adaptive_nee then sample them as a third strategy;
+        every other render ignores them. None or an empty array removes them."""
+        a = np.zeros((0, 16), np.float32) if lights is None else np.ascontiguousarray(lights, np.float32)
+        if a.size % 16:
+            raise PtxError(ERR_INVALID, "set_punctual_lights: the array is not [n, 16]")
+        a = a.reshape(-1, 16)
+        _check(lib().ptx_scene_set_punctual_lights(self.h, a.ctypes.data if len(a) else None, len(a)))
+
     def camera_rays(self, ndc_ratio):
         """ptx_camera_rays_batch: [n,3] float32 (ndc.x, ndc.y, aspect ratio) -> [n,6] float32 (origin, direction) = scene::camera::get_ray."""
         a = np.ascontiguousarray(ndc_ratio, np.float32).reshape(-1, 3)
@@ -695,6 +709,21 @@ class Scene:
             pass
 
 
+def read_punctual_lights(path):
+    """ptx_gltf_read_punctual_lights: the `point` and `spot` lights of a glTF file (KHR_lights_punctual), one [16] float32 record per node that
+    references one, in the loader's pre-order and placed by the loader's node transforms -> [n, 16] float32 for Scene.set_punctual_lights.
+    Host only. `directional` lights are skipped."""
+    n = lib().ptx_gltf_read_punctual_lights(os.fsencode(path), None, 0)
+    if n < 0:
+        _check(int(-n))
+    out = np.zeros((n, 16), np.float32)
+    if n:
+        got = lib().ptx_gltf_read_punctual_lights(os.fsencode(path), out.ctypes.data, out.size)
+        if got < 0:
+            _check(int(-got))
+    return out
+
+
 def encode_png(rgba8):
     """image::image::save_to_memory_png — RGBA8 [H,W,4] numpy -> PNG bytes."""
     a = np.ascontiguousarray(rgba8, np.uint8)
@@ -734,6 +763,13 @@ class Renderer:
 
     def load_gltf(self, path):
         self._scene = Scene.load_gltf(self._ctx, path, self.camera_index, self.sun_light_index)
+
+    def set_punctual_lights(self, lights):
+        """Scene.set_punctual_lights on the loaded scene: render_nee() and render_adaptive_nee() sample these point and spot lights; render()
+        and the other calls ignore them. read_punctual_lights(path) reads a glTF file's. None removes them."""
+        if self._scene is None:
+            raise PtxError(ERR_INVALID, "set_punctual_lights() before load_gltf()")
+        self._scene.set_punctual_lights(lights)
 
     def render_accum(self):
         """Radiance SUMS [H,W,4] of the frame; with transparent_background set, the reference's blended MEANS (colour, alpha) instead

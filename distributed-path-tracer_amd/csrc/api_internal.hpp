@@ -121,6 +121,14 @@ struct ptx_scene {
 		std::vector<float> row_cdf, cell_cdf;   // [h], [h][w]
 	} env_table;
 	DevBuf d_env_row, d_env_cell;
+	// The punctual lights of ptx_scene_set_punctual_lights, as stored, and their CDF; both empty: none. Guarded by lights_mu (and, on a scene
+	// with a context, set under the context's mutex as well, so that no render is in flight). The device copies are made by the first
+	// ptx_render_nee after a set.
+	struct Punctual {
+		bool on_device = false;
+		std::vector<float> recs, cdf;   // [n][16], [n]
+	} punctual;
+	DevBuf d_punctual, d_punctual_cdf;
 };
 
 const ptx_scene::LightList* build_lights(ptx_scene* sc);   // ptx_api.cpp

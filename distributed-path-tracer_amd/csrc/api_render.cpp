@@ -658,6 +658,7 @@ namespace {
 struct NeeSetup {
 	NeeLights Lt{};
 	NeeEnv Ev{};
+	NeePunctual Pn{};        // the scene's punctual lights; n != 0: the PUN variants run
 	uint32_t n_lights = 0;   // listed triangles, whatever the flags
 	float light_area = 0;
 	bool fused = false;      // PTX_NEE_FUSED on a scene of the fused route
@@ -720,10 +721,27 @@ int nee_setup_locked(ptx_scene* sc, uint32_t flags, NeeSetup& S) {
 			Ev.row_cdf = (const float*)sc->d_env_row.p; Ev.cell_cdf = (const float*)sc->d_env_cell.p; Ev.w = et.w; Ev.h = et.h;
 		}
 	}
-	// PTX_NEE_SAMPLER_PDF changes weights only: with no light sample possible every weight is 1, and the unflagged variants run
+	// punctual lights on the scene: a third kind of candidate, whatever the flags. The copy goes up at the first call after a set.
+	{
+		std::lock_guard<std::mutex> tl(sc->lights_mu);
+		ptx_scene::Punctual& pl = sc->punctual;
+		if (!pl.cdf.empty()) {
+			if (!pl.on_device) {
+				HIP_TRY(sc->d_punctual.ensure(pl.recs.size() * 4));
+				HIP_TRY(sc->d_punctual_cdf.ensure(pl.cdf.size() * 4));
+				HIP_TRY(hipMemcpyAsync(sc->d_punctual.p, pl.recs.data(), pl.recs.size() * 4, hipMemcpyHostToDevice, c->stream));
+				HIP_TRY(hipMemcpyAsync(sc->d_punctual_cdf.p, pl.cdf.data(), pl.cdf.size() * 4, hipMemcpyHostToDevice, c->stream));
+				HIP_TRY(hipStreamSynchronize(c->stream));
+				pl.on_device = true;
+			}
+			S.Pn.recs = (const float4*)sc->d_punctual.p; S.Pn.cdf = (const float*)sc->d_punctual_cdf.p; S.Pn.n = (uint32_t)pl.cdf.size();
+		}
+	}
+	// PTX_NEE_SAMPLER_PDF changes weights only: with no light sample that has a weight possible every weight is 1, and the unflagged variants
+	// run (a punctual sample has none: alone it leaves every weight 1)
 	S.sampler_pdf = (flags & PTX_NEE_SAMPLER_PDF) != 0 && (S.Lt.n != 0 || S.Ev.row_cdf != nullptr);
 	// PTX_NEE_CANDIDATES: with no light sample possible no candidate is drawn, and the unflagged variants run
-	S.candidates = (S.Lt.n != 0 || S.Ev.row_cdf != nullptr) ? ((flags >> 8) & 15u) + 1u : 1u;
+	S.candidates = (S.Lt.n != 0 || S.Ev.row_cdf != nullptr || S.Pn.n != 0) ? ((flags >> 8) & 15u) + 1u : 1u;
 	return PTX_OK;
 }
 
@@ -744,7 +762,7 @@ int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeSetu
 		P.integrator = PTX_INTEGRATOR_LIB;
 		HIP_TRY(hipMemsetAsync(B.chunk_counter, 0, 8, c->stream));
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
-		HIP_TRY(launch_nee_fused(sc->dev, P, S.Lt, S.Ev, S.sampler_pdf, S.candidates, B, sc->mode, sc->lds_bytes, grid, c->stream));
+		HIP_TRY(launch_nee_fused(sc->dev, P, S.Lt, S.Ev, S.Pn, S.sampler_pdf, S.candidates, B, sc->mode, sc->lds_bytes, grid, c->stream));
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
 		HIP_TRY(nee_resolve(B.sample_rad, T, f, P, p, c->stream));
 	}
@@ -834,7 +852,7 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 			rays += live;
 			const NeeHits H{A.distance, A.surface, A.triangle, A.b1, A.b2};
 			HIP_TRY(hipMemsetAsync(cnt, 0, 8, c->stream));
-			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, Ev, S.sampler_pdf, S.candidates, in, H, live, out, W, cnt, Lrec, c->stream));
+			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, Ev, S.Pn, S.sampler_pdf, S.candidates, in, H, live, out, W, cnt, Lrec, c->stream));
 			uint32_t got[2] = {0, 0};   // continuations, shadow rays
 			HIP_TRY(hipMemcpyAsync(got, cnt, 8, hipMemcpyDeviceToHost, c->stream));
 			HIP_TRY(hipStreamSynchronize(c->stream));
@@ -847,7 +865,7 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 				if (const int rc = intersect_device(c, sc, B); rc != PTX_OK) return rc;
 				rays += got[1];
 				const NeeHits SH{B.distance, B.surface, B.triangle, B.b1, B.b2};
-				HIP_TRY(launch_nee_settle(in, live, W, SH, out, cnt, Lrec, c->stream));
+				HIP_TRY(launch_nee_settle(in, live, W, SH, out, cnt, Lrec, S.Pn.n != 0, c->stream));
 				if (catchers) {
 					HIP_TRY(hipMemcpyAsync(got, cnt, 4, hipMemcpyDeviceToHost, c->stream));
 					HIP_TRY(hipStreamSynchronize(c->stream));

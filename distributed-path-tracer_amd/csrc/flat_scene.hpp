@@ -199,6 +199,8 @@ struct WorkFilter {
 	std::vector<std::pair<std::string, std::vector<int32_t>>> work;
 };
 void load_gltf(const std::string& path, uint32_t camera_index, uint32_t sun_light_index, const WorkFilter& work, FlatScene& out);
+// the file's point and spot lights, 16 floats each (include/ptx.h: ptx_gltf_read_punctual_lights); reads the .gltf only, no buffer or image
+void read_gltf_punctual_lights(const std::string& path, std::vector<float>& out);
 
 // The Lambda event of the reference's worker (models::worker_info, src/models/work_info.hpp:17-32; sample:
 // path-tracer-core/events/event.json)

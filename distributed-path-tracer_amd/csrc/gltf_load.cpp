@@ -167,6 +167,9 @@ struct Loader {
 	Entity* sun = nullptr;
 	const JVal* lights = nullptr;
 	const WorkFilter* work = nullptr;
+	// read_gltf_punctual_lights: no primitive is loaded, and every node that references a light is noted in pre-order with the light's index
+	bool lights_only = false;
+	std::vector<std::pair<Entity*, size_t>> light_nodes;
 	// get_cached_texture (renderer.cpp:33-51): one texture object per file path; the sRGB flag of the FIRST request sticks
 	std::unordered_map<std::string, int32_t> tex_by_path;
 	FlatScene tex_store;   // textures / texels / texels_f / texture_paths as load_texture fills them
@@ -276,7 +279,8 @@ struct Loader {
 		for (int c = 0; c < 3; c++) for (int k = 0; k < 3; k++) e->local.b[3 * c + k] = b[3 * c + k] * sc[c];  // make_basis
 		memcpy(e->local.o, tr, 12);
 
-		if (n.has("mesh")) {
+		if (light_ref && lights) light_nodes.emplace_back(e, (size_t)light_ref->i());
+		if (n.has("mesh") && !lights_only) {
 			e->is_model = true;
 			const JVal& mesh = g.root.at("meshes").el((size_t)n.at("mesh").i());
 			const JVal& prims = mesh.at("primitives");
@@ -393,6 +397,50 @@ void load_gltf(const std::string& path, uint32_t camera_index, uint32_t sun_ligh
 	out.texels_f = std::move(L.tex_store.texels_f);
 	out.texture_paths = std::move(L.tex_store.texture_paths);
 	finalize_scene(out, cam13, have_sun ? sun13 : nullptr);
+}
+
+// The `point` and `spot` lights of KHR_lights_punctual as ptx_scene_set_punctual_lights takes them (include/ptx.h has the record): one per
+// referencing node of scenes[0], in process_node's pre-order, placed by the loader's own transforms. `directional` lights are the sun's.
+void read_gltf_punctual_lights(const std::string& path, std::vector<float>& out) {
+	Loader L;
+	static const WorkFilter no_filter{};
+	L.work = &no_filter;
+	L.lights_only = true;
+	L.g.root = JsonReader(read_file(path, false)).parse();
+	L.g.dir = dir_of(path);
+	if (const JVal* ext = L.g.root.find("extensions"))
+		if (const JVal* kl = ext->find("KHR_lights_punctual")) L.lights = kl->find("lights");
+	out.clear();
+	if (!L.lights) return;
+	const JVal& scene_nodes = L.g.root.at("scenes").el(0).at("nodes");
+	for (size_t k = 0; k < scene_nodes.size(); k++) L.process_node((size_t)scene_nodes.el(k).i(), nullptr);
+	for (const auto& ln : L.light_nodes) {
+		const JVal& l = L.lights->el(ln.second);
+		const std::string type = l.has("type") ? l.at("type").s() : std::string();
+		const bool spot = type == "spot";
+		if (!spot && type != "point") continue;
+		const Xf gx = Loader::global_of(ln.first);
+		float rec[16] = {0};
+		memcpy(rec, gx.o, 12);
+		if (const JVal* r = l.find("range")) rec[3] = r->f();
+		const double z[3] = {-(double)gx.b[6], -(double)gx.b[7], -(double)gx.b[8]};   // world image of the local -Z axis
+		const double len = std::sqrt((z[0] * z[0] + z[1] * z[1]) + z[2] * z[2]);
+		for (int k = 0; k < 3; k++) rec[4 + k] = len > 0 ? (float)(z[k] / len) : 0.0f;
+		rec[7] = spot ? 1.0f : 0.0f;
+		float col[3] = {1, 1, 1}, inten = 1;
+		if (const JVal* c = l.find("color")) for (int k = 0; k < 3; k++) col[k] = c->el(k).f();
+		if (const JVal* i = l.find("intensity")) inten = i->f();
+		for (int k = 0; k < 3; k++) rec[8 + k] = col[k] * inten;
+		double inner = 0.0, outer = 0.78539816339744830962;   // KHR_lights_punctual: innerConeAngle 0, outerConeAngle pi / 4
+		if (spot)
+			if (const JVal* sp = l.find("spot")) {
+				if (const JVal* a = sp->find("innerConeAngle")) inner = (double)a->f();
+				if (const JVal* a = sp->find("outerConeAngle")) outer = (double)a->f();
+			}
+		rec[11] = (float)std::cos(inner);
+		rec[12] = (float)std::cos(outer);
+		out.insert(out.end(), rec, rec + 16);
+	}
 }
 
 }  // namespace ptx

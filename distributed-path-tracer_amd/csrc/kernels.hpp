@@ -241,13 +241,22 @@ struct NeeEnv {
 	uint32_t w, h;           // the map's size in texels
 };
 constexpr uint32_t kNeeEnvRay = 0xFFFFFFFFu;   // exp_surf of an environment sample's shadow ray: the sample is visible iff the ray hits nothing
+// The scene's punctual lights (ptx_scene_set_punctual_lights). n == 0: none, and the kernels without the punctual branch run. The variants
+// with the branch (template parameter PUN) are the only readers: every other kernel takes no argument of this kind.
+struct NeePunctual {
+	const float4* recs;   // [n][4] the 16-float records as stored: (position, range) (direction, kind) (intensity, cos_inner) (cos_outer, 0, 0, 0)
+	const float* cdf;     // [n] cumulative share of lum(intensity), the last entry 1
+	uint32_t n;
+};
+constexpr uint32_t kNeePunctualRay = 0xFFFFFFFEu;   // exp_surf of a punctual sample's shadow ray: exp_tri holds the bits of dist, and the sample is visible iff the ray hits nothing nearer than dist
 // cnt (device, 8 words): [0] entries appended to `out`, [1] shadow rays of the round, [2..3] light samples (64-bit), [4..5] visible ones
 hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, hipStream_t stream);
 // sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF (nee_core.hpp: sampler_pdf in pe's place in the weights)
 // candidates: M of PTX_NEE_CANDIDATES, 1 .. 16; above 1 the RIS variants run (nee_core.hpp: the candidate loop of nee_vertex)
-hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, uint32_t candidates, const NeeStream& in, const NeeHits& H, uint32_t n,
-                            const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
-hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, hipStream_t stream);
+// Pn.n != 0: the PUN variants run (nee_punctual.hip), and launch_nee_settle is told so: its punctual form knows kNeePunctualRay
+hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
+                            const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
+hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, bool punctual, hipStream_t stream);
 
 // The same estimator in one launch per pass (nee_fused.hip, PTX_NEE_FUSED): persistent workgroups as launch_render_pass sizes them, a lane per path,
 // no streams. The only per-sample memory is sample_rad.
@@ -257,8 +266,8 @@ struct NeeFusedBuffers {
 	unsigned long long* chunk_counter;   // paths handed out so far; zeroed before each pass
 	unsigned long long* counters;        // [3] accumulate: rays (closest + both shadow kinds), light samples, visible light samples
 };
-hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, uint32_t candidates, const NeeFusedBuffers& B, int mode,
-                            size_t lds_bytes, int grid, hipStream_t stream);
+hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates,
+                            const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream);
 
 // Variance-guided a-trous filter (denoise.hip, ptx_denoise). All buffers [n_pixels] float4 on the device.
 // prepare: the two radiance sums and the guide sums -> col_var (demodulated colour, v0), guide (mean normal, mean depth), remod (albedo, alpha)

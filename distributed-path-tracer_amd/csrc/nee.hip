@@ -17,6 +17,9 @@ namespace ptx {
 
 constexpr int kNeeBlock = 256;
 
+// This file is compiled twice, so that the two halves of k_nee_shade's variants build side by side: as itself (everything but the PUN
+// variants) and through nee_punctual.hip, which defines PTX_NEE_PUNCTUAL_TU (the PUN variants and launch_nee_shade_punctual alone).
+#ifndef PTX_NEE_PUNCTUAL_TU
 __global__ void __launch_bounds__(kNeeBlock) k_nee_generate(DevScene S, RenderParams P, NeeStream out, float4* __restrict__ L, uint32_t n) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
 	if (i >= n) return;
@@ -30,6 +33,7 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_generate(DevScene S, RenderPa
 	out.id[i] = i; out.dp[i] = 0u;
 	L[i] = make_float4(0.f, 0.f, 0.f, 1.0f);
 }
+#endif
 
 // dense append: one atomic per wave reserves the wave's entries, the lane prefix count places them. `second` entries follow the wave's
 // `first` entries. Returns the lane's positions (valid where its flag is set).
@@ -50,10 +54,11 @@ DEV void nee_append2(bool first, bool second, uint32_t* counter, uint32_t& pos_f
 // TEX / ALPHA / SUN compile the texture lookups / the pass-through and catcher code / the sun request in, as the render variants do;
 // ENV the environment sample and the miss weight (PTX_NEE_ENV_SAMPLES; TEX only: a map implies the TEX variants). Ev, the last argument, is
 // read by the ENV variants alone. SPDF: the weights of PTX_NEE_SAMPLER_PDF. RIS: the light sample chosen among ris_m candidates
-// (PTX_NEE_CANDIDATES); the other variants do not read ris_m.
-template <bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false, bool RIS = false>
+// (PTX_NEE_CANDIDATES); the other variants do not read ris_m. PUN: punctual lights on the scene (Pn), a third kind of candidate; the other
+// variants do not read Pn.
+template <bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false, bool RIS = false, bool PUN = false>
 __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParams P, NeeLights Lt, NeeStream in, NeeHits H, uint32_t n, NeeStream out, NeeShadow W,
-                                                         uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeeEnv Ev, uint32_t ris_m) {
+                                                         uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeeEnv Ev, uint32_t ris_m, NeePunctual Pn) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
 	NeeVertex v;
 	V3 o = {0, 0, 0}, d = {0, 0, 1}, T = {1, 1, 1};
@@ -71,7 +76,7 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 		const uint32_t pixel = py * P.W + px;
 		const float4 l4 = Lrec[id];
 		V3 L = mk(l4.x, l4.y, l4.z);
-		if (nee_vertex<TEX, ALPHA, SUN, ENV, SPDF, RIS>(S, P, Lt, Ev, ris_m, pixel, sample, H.surface[i], (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v))
+		if (nee_vertex<TEX, ALPHA, SUN, ENV, SPDF, RIS, PUN>(S, P, Lt, Ev, ris_m, pixel, sample, H.surface[i], (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v, Pn))
 			Lrec[id] = make_float4(L.x, L.y, L.z, l4.w);
 	}
 	// shadow rays of the round: at most two per path, so every position is below twice the round's paths
@@ -105,7 +110,10 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 	}
 }
 
+#ifndef PTX_NEE_PUNCTUAL_TU
 // The answers of the round's shadow rays (SH: their closest hits). One lane per path of the round, sun before light.
+// PUN: the round may hold punctual samples' rays (kNeePunctualRay): visible iff nothing is hit nearer than the light.
+template <bool PUN>
 __global__ void __launch_bounds__(kNeeBlock) k_nee_settle(NeeStream in, uint32_t n, NeeShadow W, NeeHits SH, NeeStream out, uint32_t* __restrict__ cnt, float4* __restrict__ Lrec) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
 	bool through = false, visible = false;
@@ -122,7 +130,8 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_settle(NeeStream in, uint32_t
 			}
 			if (lp != kNeeNone) {
 				const uint32_t es = W.exp_surf[i];
-				visible = es == kNeeEnvRay ? SH.surface[lp] < 0 : (SH.surface[lp] == (int32_t)es && SH.triangle[lp] == (int32_t)W.exp_tri[i]);
+				if (PUN && es == kNeePunctualRay) visible = SH.surface[lp] < 0 || !(SH.distance[lp] < __uint_as_float(W.exp_tri[i]));
+				else visible = es == kNeeEnvRay ? SH.surface[lp] < 0 : (SH.surface[lp] == (int32_t)es && SH.triangle[lp] == (int32_t)W.exp_tri[i]);
 				if (visible) { v.x += W.lx[i]; v.y += W.ly[i]; v.z += W.lz[i]; store = true; }
 			}
 			if (store) Lrec[id] = v;
@@ -142,50 +151,73 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_settle(NeeStream in, uint32_t
 	}
 }
 
+#endif
+
 // ------------------------------------------------------------------------------------ launchers
+#ifndef PTX_NEE_PUNCTUAL_TU
 hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, hipStream_t stream) {
 	hipLaunchKernelGGL(k_nee_generate, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, S, P, out, L, n);
 	return hipGetLastError();
 }
+#endif
 
-template <bool TEX, bool ALPHA, bool ENV, bool SPDF, bool RIS>
-static void nee_shade_sun(bool sun, dim3 grid, hipStream_t stream, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeStream& in, const NeeHits& H,
-                          uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L) {
-	if (sun) hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, true, ENV, SPDF, RIS>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m);
-	else hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, false, ENV, SPDF, RIS>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m);
+template <bool TEX, bool ALPHA, bool ENV, bool SPDF, bool RIS, bool PUN>
+static void nee_shade_sun(bool sun, dim3 grid, hipStream_t stream, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeStream& in,
+                          const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L) {
+	if (sun) hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, true, ENV, SPDF, RIS, PUN>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m, Pn);
+	else hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, false, ENV, SPDF, RIS, PUN>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m, Pn);
 }
 
-template <bool SPDF, bool RIS>
-static hipError_t launch_nee_shade_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeStream& in, const NeeHits& H, uint32_t n, const NeeStream& out,
-                                        const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
+template <bool SPDF, bool RIS, bool PUN>
+static hipError_t launch_nee_shade_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeStream& in, const NeeHits& H, uint32_t n,
+                                        const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
 	const dim3 grid((n + kNeeBlock - 1) / kNeeBlock);
 	const bool sun = S.sun.present != 0;
 	if (Ev.row_cdf) {   // a table means a map, and a map means the TEX variants
 		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
-		if (S.any_alpha) nee_shade_sun<true, true, true, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<true, false, true, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
+		if (S.any_alpha) nee_shade_sun<true, true, true, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
+		else nee_shade_sun<true, false, true, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
 	} else if (S.any_texture) {
-		if (S.any_alpha) nee_shade_sun<true, true, false, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<true, false, false, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
+		if (S.any_alpha) nee_shade_sun<true, true, false, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
+		else nee_shade_sun<true, false, false, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
 	} else {
-		if (S.any_alpha) nee_shade_sun<false, true, false, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<false, false, false, SPDF, RIS>(sun, grid, stream, S, P, Lt, Ev, ris_m, in, H, n, out, W, cnt, L);
+		if (S.any_alpha) nee_shade_sun<false, true, false, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
+		else nee_shade_sun<false, false, false, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
 	}
 	return hipGetLastError();
 }
 
-// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF; candidates > 1: the RIS variants with M = candidates (PTX_NEE_CANDIDATES)
-hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, uint32_t candidates, const NeeStream& in, const NeeHits& H, uint32_t n,
-                            const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
+// the four quarters (SPDF x RIS) of one half (PUN) of the variants
+template <bool PUN>
+static hipError_t launch_nee_shade_half(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
+                                        const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
 	if (candidates > 1)
-		return sampler_pdf ? launch_nee_shade_variant<true, true>(S, P, Lt, Ev, candidates, in, H, n, out, W, cnt, L, stream)
-		                   : launch_nee_shade_variant<false, true>(S, P, Lt, Ev, candidates, in, H, n, out, W, cnt, L, stream);
-	return sampler_pdf ? launch_nee_shade_variant<true, false>(S, P, Lt, Ev, 1u, in, H, n, out, W, cnt, L, stream) : launch_nee_shade_variant<false, false>(S, P, Lt, Ev, 1u, in, H, n, out, W, cnt, L, stream);
+		return sampler_pdf ? launch_nee_shade_variant<true, true, PUN>(S, P, Lt, Ev, Pn, candidates, in, H, n, out, W, cnt, L, stream)
+		                   : launch_nee_shade_variant<false, true, PUN>(S, P, Lt, Ev, Pn, candidates, in, H, n, out, W, cnt, L, stream);
+	return sampler_pdf ? launch_nee_shade_variant<true, false, PUN>(S, P, Lt, Ev, Pn, 1u, in, H, n, out, W, cnt, L, stream)
+	                   : launch_nee_shade_variant<false, false, PUN>(S, P, Lt, Ev, Pn, 1u, in, H, n, out, W, cnt, L, stream);
 }
 
-hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, hipStream_t stream) {
-	hipLaunchKernelGGL(k_nee_settle, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, in, n, W, SH, out, cnt, L);
+hipError_t launch_nee_shade_punctual(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
+                                     const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
+#ifdef PTX_NEE_PUNCTUAL_TU
+hipError_t launch_nee_shade_punctual(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
+                                     const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
+	return launch_nee_shade_half<true>(S, P, Lt, Ev, Pn, sampler_pdf, candidates, in, H, n, out, W, cnt, L, stream);
+}
+#else
+// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF; candidates > 1: the RIS variants with M = candidates (PTX_NEE_CANDIDATES); Pn.n != 0: the PUN variants
+hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
+                            const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
+	if (Pn.n != 0) return launch_nee_shade_punctual(S, P, Lt, Ev, Pn, sampler_pdf, candidates, in, H, n, out, W, cnt, L, stream);
+	return launch_nee_shade_half<false>(S, P, Lt, Ev, Pn, sampler_pdf, candidates, in, H, n, out, W, cnt, L, stream);
+}
+
+hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, bool punctual, hipStream_t stream) {
+	if (punctual) hipLaunchKernelGGL(k_nee_settle<true>, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, in, n, W, SH, out, cnt, L);
+	else hipLaunchKernelGGL(k_nee_settle<false>, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, in, n, W, SH, out, cnt, L);
 	return hipGetLastError();
 }
+#endif
 
 }  // namespace ptx

@@ -7,6 +7,7 @@
 namespace ptx {
 
 enum { BLOCK_LIGHT = 3, BLOCK_ENV = 4 };   // Philox blocks of the light sample's and the environment sample's draws (BLOCK_SURFACE / BLOCK_SUN / BLOCK_JITTER: device_core.hpp)
+enum { BLOCK_PUNCTUAL = 0x200 };           // punctual lights on the scene: candidate j draws its strategy (x) and its light (y) from block BLOCK_PUNCTUAL + j
 enum { BLOCK_RIS = 0x100 };                // PTX_NEE_CANDIDATES: candidate j draws from blocks BLOCK_LIGHT + 2 j and BLOCK_ENV + 2 j, selection j from component j & 3 of block BLOCK_RIS + (j >> 2)
 
 // sample id within the pass (sample-major, pixel-minor) -> image pixel and global sample index, as k_render_pass enumerates them
@@ -97,10 +98,47 @@ struct NeeVertex {
 // contributes sets `want`; then lx is its x, (lo, ld) its shadow ray and (exp_surf, exp_tri) its visibility rule. Otherwise nothing is written.
 // The unflagged vertex takes one, from BLOCK_LIGHT / BLOCK_ENV, straight into its NeeVertex — `want` is set in place, not returned: the
 // statements are then the former ones, and the unflagged kernels keep their registers. The RIS vertex takes M of them.
-template <bool TEX, bool ENV, bool SPDF>
+// PUN (punctual lights on the scene, Pn; include/ptx.h: PUNCTUAL LIGHTS): the candidate is a punctual sample with probability c_p, drawn from
+// block_pun, and the other strategies' densities carry (1 - c_p). Without PUN, Pn, c_p and block_pun are not read and no statement changes.
+template <bool TEX, bool ENV, bool SPDF, bool PUN = false>
 DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, float c_env, uint32_t pixel, uint32_t sample, uint32_t depth, uint32_t pass,
                        uint32_t block_light, uint32_t block_env, const Surf& sf, V3 normal, V3 outcoming, V3 T, const MatEval& me, float roughness, float spec_prob, V3& lx, V3& lo, V3& ld,
-                       uint32_t& exp_surf, uint32_t& exp_tri, bool& want) {
+                       uint32_t& exp_surf, uint32_t& exp_tri, bool& want, const NeePunctual& Pn = NeePunctual{}, float c_p = 0.0f, uint32_t block_pun = 0u) {
+	if constexpr (PUN) {
+		const float4 q = draws(P, pixel, sample, depth, pass, block_pun);
+		if (c_p == 1.0F || q.x < 0.5F) {
+			const uint32_t k = env_pick(Pn.cdf, Pn.n, q.y);
+			const float pmf = Pn.cdf[k] - (k ? Pn.cdf[k - 1] : 0.0f);   // from the stored values: what the pick realises
+			const float4 r0 = Pn.recs[4 * (size_t)k], r1 = Pn.recs[4 * (size_t)k + 1], r2 = Pn.recs[4 * (size_t)k + 2], r3 = Pn.recs[4 * (size_t)k + 3];
+			const V3 v = mk(r0.x, r0.y, r0.z) - sf.pos;
+			const float dist2 = dot(v, v);
+			if (dist2 > 0) {
+				const float dist = sqrt_exact(dist2);
+				const V3 w = v / dist;
+				float att = 1.0f;
+				if (r1.w != 0.0f) {   // a spot: the cone's smooth edge
+					const float cd = dot(mk(r1.x, r1.y, r1.z), -w);
+					const float sm = clampf((cd - r3.x) / pmax(r2.w - r3.x, 1e-6F), 0, 1);
+					att = sm * sm;
+				}
+				const V3 E = (mk(r2.x, r2.y, r2.z) * att) / dist2;
+				if (dot(normal, w) > 0 && pmf > 0 && (r0.w == 0.0f || dist <= r0.w) && att > 0 && pmax(E.x, pmax(E.y, E.z)) > 0) {
+					float pdf;
+					const V3 brdf = eval_brdf(normal, outcoming, w, me.albedo, roughness, me.metallic, spec_prob, pdf);
+					const float pe = pmax(pdf, kEps);
+					const V3 qv = brdf / pe;
+					const V3 qc = mk(clampf(qv.x, 0, 1), clampf(qv.y, 0, 1), clampf(qv.z, 0, 1));
+					const V3 b = qc * pe;   // LIB's integrand at w, cosine included
+					lx = ((T * b) * E) / (c_p * pmf);
+					lo = sf.pos + w * kEps;
+					ld = w;
+					exp_surf = kNeePunctualRay; exp_tri = __float_as_uint(dist);
+					want = true;
+				}
+			}
+			return;
+		}
+	}
 	bool to_env = false;
 	if constexpr (ENV) {
 		to_env = Lt.n == 0 || draws(P, pixel, sample, depth, pass, block_light).w < 0.5F;
@@ -128,7 +166,9 @@ DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights
 					float pw = pe;
 					if constexpr (SPDF) pw = sampler_pdf(normal, outcoming, w, roughness, spec_prob);
 					if (!SPDF || pw > 0) {   // a direction the BSDF sampler cannot produce carries nothing
-						const float wl = pw / (pw + c_env * p);
+						float p_e = c_env * p;
+						if constexpr (PUN) p_e = (1 - c_p) * p_e;
+						const float wl = pw / (pw + p_e);
 						lx = ((T * qc) * wl) * Le;
 						lo = sf.pos + w * kEps;
 						ld = w;
@@ -168,6 +208,7 @@ DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights
 				const V3 qc = mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));
 				float p_l = dist2 / (cg * Lt.area);
 				if constexpr (ENV) p_l = (1 - c_env) * p_l;
+				if constexpr (PUN) p_l = (1 - c_p) * p_l;
 				float pw = pe;
 				if constexpr (SPDF) pw = sampler_pdf(normal, outcoming, w, roughness, spec_prob);
 				if (!SPDF || pw > 0) {
@@ -191,9 +232,11 @@ DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights
 // against that sample. Without ENV, Ev is not read and the statements are the unflagged estimator's.
 // SPDF (PTX_NEE_SAMPLER_PDF): sampler_pdf takes pe's place in the two wl and in p_prev, and nowhere else. Without SPDF no statement changes.
 // RIS (PTX_NEE_CANDIDATES(m), m > 1): the light sample is chosen among ris_m candidates. Without RIS ris_m is not read and no statement changes.
-template <bool TEX, bool ALPHA, bool SUN, bool ENV = false, bool SPDF = false, bool RIS = false>
+// PUN (punctual lights on the scene, Pn): a candidate may be a punctual sample, and the other strategies' densities carry (1 - c_p) in every
+// weight. Without PUN, Pn is not read and no statement changes.
+template <bool TEX, bool ALPHA, bool SUN, bool ENV = false, bool SPDF = false, bool RIS = false, bool PUN = false>
 DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, uint32_t pixel, uint32_t sample, int32_t surf, uint32_t tri, float b1, float b2,
-                    float hit_dist, V3& o, V3& d, V3& T, V3& L, float& p_prev, uint32_t& depth, uint32_t& pass, NeeVertex& out) {
+                    float hit_dist, V3& o, V3& d, V3& T, V3& L, float& p_prev, uint32_t& depth, uint32_t& pass, NeeVertex& out, const NeePunctual& Pn = NeePunctual{}) {
 	bool& alive = out.alive;
 	bool& want_sun = out.want_sun;
 	bool& want_light = out.want_light;
@@ -202,6 +245,7 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 	uint32_t &exp_surf = out.exp_surf, &exp_tri = out.exp_tri;
 	bool store = false;
 	const float c_env = (ENV && Lt.n != 0) ? 0.5F : 1.0F;   // share of the vertices whose light sample goes to the map (ENV only)
+	const float c_p = (ENV || Lt.n != 0) ? 0.5F : 1.0F;     // share of the candidates that are punctual samples (PUN only): all of them when no other strategy exists
 	do {
 		if (surf < 0) {   // miss: environment
 			V3 env = mk(P.env[0], P.env[1], P.env[2]);
@@ -213,7 +257,11 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 			}
 			V3 add = T * env;
 			if constexpr (ENV) {   // a BSDF-sampled direction that the environment sample of the previous vertex could have produced
-				if (depth != 0 && pass == 0) add = add * (p_prev / (p_prev + c_env * env_pdf(Ev, d)));
+				if (depth != 0 && pass == 0) {
+					float p_e = c_env * env_pdf(Ev, d);
+					if constexpr (PUN) p_e = (1 - c_p) * p_e;
+					add = add * (p_prev / (p_prev + p_e));
+				}
 			}
 			L = L + add;
 			store = true;
@@ -285,6 +333,7 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 				const float dist = hit_dist;
 				float p_l = (dist * dist) / (cg * Lt.area);
 				if constexpr (ENV) p_l = (1 - c_env) * p_l;
+				if constexpr (PUN) p_l = (1 - c_p) * p_l;
 				em = em * (p_prev / (p_prev + p_l));
 			}
 		}
@@ -293,8 +342,8 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 		if (last) break;
 		// ---- light sample
 		if constexpr (!RIS) {
-			nee_candidate<TEX, ENV, SPDF>(S, P, Lt, Ev, c_env, pixel, sample, depth, pass, BLOCK_LIGHT, BLOCK_ENV, sf, normal, outcoming, T, me, roughness, spec_prob, lx, lo, ld,
-			                              exp_surf, exp_tri, want_light);
+			nee_candidate<TEX, ENV, SPDF, PUN>(S, P, Lt, Ev, c_env, pixel, sample, depth, pass, BLOCK_LIGHT, BLOCK_ENV, sf, normal, outcoming, T, me, roughness, spec_prob, lx, lo, ld,
+			                                   exp_surf, exp_tri, want_light, Pn, c_p, BLOCK_PUNCTUAL);
 		} else {
 			// M candidates, one kept by weighted reservoir selection (include/ptx.h: PTX_NEE_CANDIDATES). The reservoir is lx, ld, the visibility
 			// rule, wsum and the chosen weight; lo follows from ld.
@@ -303,8 +352,8 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 				V3 cx = {0, 0, 0}, co = {0, 0, 0}, cd = {0, 0, 1};
 				uint32_t cs = 0, ct = 0;
 				bool cw = false;
-				nee_candidate<TEX, ENV, SPDF>(S, P, Lt, Ev, c_env, pixel, sample, depth, pass, BLOCK_LIGHT + 2 * j, BLOCK_ENV + 2 * j, sf, normal, outcoming, T, me, roughness, spec_prob, cx, co, cd,
-				                              cs, ct, cw);
+				nee_candidate<TEX, ENV, SPDF, PUN>(S, P, Lt, Ev, c_env, pixel, sample, depth, pass, BLOCK_LIGHT + 2 * j, BLOCK_ENV + 2 * j, sf, normal, outcoming, T, me, roughness, spec_prob, cx, co, cd,
+				                                   cs, ct, cw, Pn, c_p, BLOCK_PUNCTUAL + j);
 				if (!cw) continue;
 				const float w_j = pmax(cx.x, pmax(cx.y, cx.z));
 				if (!(w_j > 0 && w_j < __builtin_inff())) continue;

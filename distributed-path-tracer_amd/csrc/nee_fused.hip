@@ -20,12 +20,15 @@ namespace ptx {
 // DESIGN.md 5.7 has the resource table and the measurement). Staging is per workgroup and there is one workgroup per CU either way; the
 // overflow stacks are sized per wave slot of the larger k_render_pass workgroup. The RIS variants (PTX_NEE_CANDIDATES) carry the reservoir across the
 // candidate loop: those without texture and sun code spill 2 to 4 VGPRs at 768 threads and get 512 as well; the others stay without scratch at 512 (198-255 VGPRs).
+// The PUN variants (punctual lights on the scene) carry the punctual branch of the candidate besides the others and get 512 threads: 166-231
+// VGPRs without RIS, 184-256 with. One is too full for that: with ENV, SUN, RIS and SPDF together the global-memory variant with ALPHA spills
+// 3 VGPRs at 512, so the variants of that combination get 256 (up to 260 VGPRs). All 144 were compiled; none uses scratch.
 // -DPTX_NEE_FUSED_BLOCK=n: one size for all (measurement).
-constexpr int nee_fused_block(bool tex, bool sun, bool env = false, bool ris = false) {
+constexpr int nee_fused_block(bool tex, bool sun, bool env = false, bool ris = false, bool pun = false, bool spdf = false) {
 #ifdef PTX_NEE_FUSED_BLOCK
 	return PTX_NEE_FUSED_BLOCK;
 #else
-	return (tex || sun || env || ris) ? 512 : 768;
+	return (pun && ris && spdf && env && sun) ? 256 : (tex || sun || env || ris || pun) ? 512 : 768;
 #endif
 }
 static_assert(nee_fused_block(false, false) % 64 == 0 && nee_fused_block(true, true) % 64 == 0 && nee_fused_block(false, false) <= kBlock && nee_fused_block(true, true) <= kBlock,
@@ -40,11 +43,12 @@ DEV uint32_t wave_sum(uint32_t v) {
 // SPDF: the variants of PTX_NEE_SAMPLER_PDF. sampler_pdf costs them 0 to 2 VGPRs, and each compiles without scratch at its unflagged
 // twin's workgroup size, so nee_fused_block holds for them too (DESIGN.md 5.7 has their rows).
 // RIS: the variants of PTX_NEE_CANDIDATES, the light sample chosen among ris_m candidates; the other variants do not read ris_m.
-template <int MODE, bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false, bool RIS = false>
-__global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV, RIS)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
+// PUN: the variants for scenes with punctual lights (Pn), a third kind of candidate; the other variants do not read Pn.
+template <int MODE, bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false, bool RIS = false, bool PUN = false>
+__global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV, RIS, PUN, SPDF)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
                                                               const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space,
-                                                              NeeEnv Ev, uint32_t ris_m) {
-	constexpr int kThreads = nee_fused_block(TEX, SUN, ENV, RIS);
+                                                              NeeEnv Ev, uint32_t ris_m, NeePunctual Pn) {
+	constexpr int kThreads = nee_fused_block(TEX, SUN, ENV, RIS, PUN, SPDF);
 	DevScene S = S0;
 	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;  // see struct Tables
 	const Staged st = stage_geometry<MODE>(S, g_smem);
@@ -120,7 +124,7 @@ __global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV, RIS)) k_nee_fus
 			const int32_t surf = hit ? h.surface : -1;
 			const uint32_t tri = hit ? (h.tri & S.tri_id_mask) - S.surfaces[h.surface].tri_base : 0u;
 			NeeVertex v;
-			nee_vertex<TEX, ALPHA, SUN, ENV, SPDF, RIS>(S, P, Lt, Ev, ris_m, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v);
+			nee_vertex<TEX, ALPHA, SUN, ENV, SPDF, RIS, PUN>(S, P, Lt, Ev, ris_m, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v, Pn);
 			bool alive = v.alive;
 			// ---------------- the sun ray: occluded = any hit
 			if constexpr (SUN) {
@@ -148,7 +152,8 @@ __global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV, RIS)) k_nee_fus
 				rays++;
 				light_samples++;
 				bool visible;
-				if (ENV && v.exp_surf == kNeeEnvRay) visible = !lhit;   // an environment sample
+				if (PUN && v.exp_surf == kNeePunctualRay) visible = !lhit || !(lh.dist < __uint_as_float(v.exp_tri));   // a punctual sample: nothing nearer than the light
+				else if (ENV && v.exp_surf == kNeeEnvRay) visible = !lhit;   // an environment sample
 				else visible = lhit && lh.surface == (int32_t)v.exp_surf && (int32_t)((lh.tri & S.tri_id_mask) - S.surfaces[lh.surface].tri_base) == (int32_t)v.exp_tri;
 				if (visible) {
 					light_visible++;
@@ -176,73 +181,87 @@ static hipError_t set_lds(const void* fn, size_t bytes) {
 	return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-template <int MODE, bool SPDF, bool RIS, bool TEX, bool ALPHA, bool SUN, bool ENV = false>
-static hipError_t launch_nee_fused_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
-	const auto kernel = &k_nee_fused<MODE, TEX, ALPHA, SUN, ENV, SPDF, RIS>;
+template <int MODE, bool SPDF, bool RIS, bool PUN, bool TEX, bool ALPHA, bool SUN, bool ENV = false>
+static hipError_t launch_nee_fused_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeFusedBuffers& B, size_t lds_bytes, int grid,
+                                           hipStream_t stream) {
+	const auto kernel = &k_nee_fused<MODE, TEX, ALPHA, SUN, ENV, SPDF, RIS, PUN>;
 	if (MODE != MODE_GLOBAL) {
 		hipError_t e = set_lds(reinterpret_cast<const void*>(kernel), lds_bytes);
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL(kernel, dim3(grid), dim3(nee_fused_block(TEX, SUN, ENV, RIS)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces, S.spaces, S.model_space, Ev, ris_m);
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(nee_fused_block(TEX, SUN, ENV, RIS, PUN, SPDF)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces, S.spaces, S.model_space, Ev, ris_m, Pn);
 	return hipGetLastError();
 }
 
 // the variants of launch_nee_shade, per place of the geometry
-template <int MODE, bool SPDF, bool RIS>
-static hipError_t launch_nee_fused_mode(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, size_t lds_bytes, int grid, hipStream_t stream) {
+template <int MODE, bool SPDF, bool RIS, bool PUN>
+static hipError_t launch_nee_fused_mode(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeFusedBuffers& B, size_t lds_bytes, int grid,
+                                        hipStream_t stream) {
+#define PTX_NEE_FUSED_LAUNCH(...) launch_nee_fused_variant<MODE, SPDF, RIS, PUN, __VA_ARGS__>(S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream)
 	const bool sun = S.sun.present != 0;
 	if (Ev.row_cdf) {   // a table means a map, and a map means the TEX variants
 		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
-		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, true, true, true, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, true, true, false, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
-		return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, true, false, true, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, true, false, false, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
+		if (S.any_alpha) return sun ? PTX_NEE_FUSED_LAUNCH(true, true, true, true) : PTX_NEE_FUSED_LAUNCH(true, true, false, true);
+		return sun ? PTX_NEE_FUSED_LAUNCH(true, false, true, true) : PTX_NEE_FUSED_LAUNCH(true, false, false, true);
 	}
 	if (S.any_texture) {
-		if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, true, true, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, true, true, false>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
-		return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, true, false, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, true, false, false>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
+		if (S.any_alpha) return sun ? PTX_NEE_FUSED_LAUNCH(true, true, true) : PTX_NEE_FUSED_LAUNCH(true, true, false);
+		return sun ? PTX_NEE_FUSED_LAUNCH(true, false, true) : PTX_NEE_FUSED_LAUNCH(true, false, false);
 	}
-	if (S.any_alpha) return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, false, true, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, false, true, false>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
-	return sun ? launch_nee_fused_variant<MODE, SPDF, RIS, false, false, true>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream) : launch_nee_fused_variant<MODE, SPDF, RIS, false, false, false>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
+	if (S.any_alpha) return sun ? PTX_NEE_FUSED_LAUNCH(false, true, true) : PTX_NEE_FUSED_LAUNCH(false, true, false);
+	return sun ? PTX_NEE_FUSED_LAUNCH(false, false, true) : PTX_NEE_FUSED_LAUNCH(false, false, false);
+#undef PTX_NEE_FUSED_LAUNCH
 }
 
-template <bool SPDF, bool RIS>
-static hipError_t launch_nee_fused_all(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
-                                       hipStream_t stream) {
-	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS, SPDF, RIS>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
-	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID, SPDF, RIS>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
-	return launch_nee_fused_mode<MODE_GLOBAL, SPDF, RIS>(S, P, Lt, Ev, ris_m, B, lds_bytes, grid, stream);
-}
-
-// This file is compiled four times, so that the four quarters of the variants build side by side: as itself (the unflagged variants and
-// launch_nee_fused), through nee_fused_spdf.hip, which defines PTX_NEE_FUSED_SPDF_TU (the variants of PTX_NEE_SAMPLER_PDF), through
-// nee_fused_ris.hip, which defines PTX_NEE_FUSED_RIS_TU (the variants of PTX_NEE_CANDIDATES), and through nee_fused_ris_spdf.hip, which defines both.
-hipError_t launch_nee_fused_sampler_pdf(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
-                                        hipStream_t stream);
-hipError_t launch_nee_fused_ris(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
-                                hipStream_t stream);
-hipError_t launch_nee_fused_ris_sampler_pdf(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, int mode, size_t lds_bytes,
-                                            int grid, hipStream_t stream);
-#if defined(PTX_NEE_FUSED_RIS_TU) && defined(PTX_NEE_FUSED_SPDF_TU)
-hipError_t launch_nee_fused_ris_sampler_pdf(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, int mode, size_t lds_bytes,
-                                            int grid, hipStream_t stream) {
-	return launch_nee_fused_all<true, true>(S, P, Lt, Ev, ris_m, B, mode, lds_bytes, grid, stream);
-}
-#elif defined(PTX_NEE_FUSED_RIS_TU)
-hipError_t launch_nee_fused_ris(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
-                                hipStream_t stream) {
-	return launch_nee_fused_all<false, true>(S, P, Lt, Ev, ris_m, B, mode, lds_bytes, grid, stream);
-}
-#elif defined(PTX_NEE_FUSED_SPDF_TU)
-hipError_t launch_nee_fused_sampler_pdf(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid,
-                                        hipStream_t stream) {
-	return launch_nee_fused_all<true, false>(S, P, Lt, Ev, 1u, B, mode, lds_bytes, grid, stream);
-}
+// This file is compiled eight times, so that the eight parts of the variants build side by side: as itself (the unflagged variants and
+// launch_nee_fused) and through nee_fused_{spdf, ris, ris_spdf, pun, pun_spdf, pun_ris, pun_ris_spdf}.hip, which define PTX_NEE_FUSED_SPDF_TU
+// (the variants of PTX_NEE_SAMPLER_PDF), PTX_NEE_FUSED_RIS_TU (those of PTX_NEE_CANDIDATES) and PTX_NEE_FUSED_PUN_TU (those for scenes with
+// punctual lights) in every combination. Each compilation defines launch_nee_fused_part_<spdf><ris><pun> for its own three digits, 0 or 1
+// each: launch_nee_fused_part_101 is the SPDF + PUN part. The macros below only paste that name together and spell the argument list once;
+// a further dimension is one more PTX_TU_* digit, eight more declarations and one more level in launch_nee_fused's choice.
+#ifdef PTX_NEE_FUSED_SPDF_TU
+#define PTX_TU_SPDF 1
 #else
-// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF; candidates > 1: the RIS variants with M = candidates (PTX_NEE_CANDIDATES)
-hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, bool sampler_pdf, uint32_t candidates, const NeeFusedBuffers& B, int mode,
-                            size_t lds_bytes, int grid, hipStream_t stream) {
-	if (candidates > 1)
-		return sampler_pdf ? launch_nee_fused_ris_sampler_pdf(S, P, Lt, Ev, candidates, B, mode, lds_bytes, grid, stream) : launch_nee_fused_ris(S, P, Lt, Ev, candidates, B, mode, lds_bytes, grid, stream);
-	return sampler_pdf ? launch_nee_fused_sampler_pdf(S, P, Lt, Ev, B, mode, lds_bytes, grid, stream) : launch_nee_fused_all<false, false>(S, P, Lt, Ev, 1u, B, mode, lds_bytes, grid, stream);
+#define PTX_TU_SPDF 0
+#endif
+#ifdef PTX_NEE_FUSED_RIS_TU
+#define PTX_TU_RIS 1
+#else
+#define PTX_TU_RIS 0
+#endif
+#ifdef PTX_NEE_FUSED_PUN_TU
+#define PTX_TU_PUN 1
+#else
+#define PTX_TU_PUN 0
+#endif
+#define PTX_NEE_FUSED_PART_(s, r, p) launch_nee_fused_part_##s##r##p
+#define PTX_NEE_FUSED_PART(s, r, p) PTX_NEE_FUSED_PART_(s, r, p)
+#define PTX_NEE_FUSED_PART_ARGS                                                                                                                                                        \
+	const DevScene &S, const RenderParams &P, const NeeLights &Lt, const NeeEnv &Ev, const NeePunctual &Pn, uint32_t ris_m, const NeeFusedBuffers &B, int mode, size_t lds_bytes, int grid, \
+		hipStream_t stream
+hipError_t launch_nee_fused_part_000(PTX_NEE_FUSED_PART_ARGS);
+hipError_t launch_nee_fused_part_100(PTX_NEE_FUSED_PART_ARGS);
+hipError_t launch_nee_fused_part_010(PTX_NEE_FUSED_PART_ARGS);
+hipError_t launch_nee_fused_part_110(PTX_NEE_FUSED_PART_ARGS);
+hipError_t launch_nee_fused_part_001(PTX_NEE_FUSED_PART_ARGS);
+hipError_t launch_nee_fused_part_101(PTX_NEE_FUSED_PART_ARGS);
+hipError_t launch_nee_fused_part_011(PTX_NEE_FUSED_PART_ARGS);
+hipError_t launch_nee_fused_part_111(PTX_NEE_FUSED_PART_ARGS);
+hipError_t PTX_NEE_FUSED_PART(PTX_TU_SPDF, PTX_TU_RIS, PTX_TU_PUN)(PTX_NEE_FUSED_PART_ARGS) {
+	constexpr bool SPDF = PTX_TU_SPDF != 0, RIS = PTX_TU_RIS != 0, PUN = PTX_TU_PUN != 0;
+	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS, SPDF, RIS, PUN>(S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream);
+	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID, SPDF, RIS, PUN>(S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream);
+	return launch_nee_fused_mode<MODE_GLOBAL, SPDF, RIS, PUN>(S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream);
+}
+
+#if !PTX_TU_SPDF && !PTX_TU_RIS && !PTX_TU_PUN
+// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF; candidates > 1: the RIS variants with M = candidates (PTX_NEE_CANDIDATES); Pn.n != 0: the PUN variants
+hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeFusedBuffers& B,
+                            int mode, size_t lds_bytes, int grid, hipStream_t stream) {
+	const uint32_t ris_m = candidates > 1 ? candidates : 1u;
+	const auto part = Pn.n != 0 ? (candidates > 1 ? (sampler_pdf ? launch_nee_fused_part_111 : launch_nee_fused_part_011) : (sampler_pdf ? launch_nee_fused_part_101 : launch_nee_fused_part_001))
+	                            : (candidates > 1 ? (sampler_pdf ? launch_nee_fused_part_110 : launch_nee_fused_part_010) : (sampler_pdf ? launch_nee_fused_part_100 : launch_nee_fused_part_000));
+	return part(S, P, Lt, Ev, Pn, ris_m, B, mode, lds_bytes, grid, stream);
 }
 #endif
 

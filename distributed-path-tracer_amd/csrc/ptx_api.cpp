@@ -245,10 +245,11 @@ int upload_scene(ptx_scene* sc) {
 void release_scene_buffers(ptx_scene* sc) {
 	for (DevBuf* b : {&sc->d_models, &sc->d_surfaces, &sc->d_materials, &sc->d_nodes, &sc->d_refs, &sc->d_tris, &sc->d_shade, &sc->d_tex,
 	                  &sc->d_texels, &sc->d_texels_f, &sc->d_lut, &sc->d_spaces, &sc->d_model_space, &sc->d_wf_order, &sc->d_res_nodes, &sc->d_res_refs, &sc->d_res_tris, &sc->d_hot,
-	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell})
+	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell, &sc->d_punctual, &sc->d_punctual_cdf})
 		b->release();
 	sc->lights.on_device = false;
 	sc->env_table.on_device = false;
+	sc->punctual.on_device = false;
 }
 
 int finish_scene(ptx_ctx* ctx, ptx_scene* sc, ptx_scene** out) {
@@ -539,6 +540,61 @@ int ptx_scene_set_environment(ptx_scene* sc, const char* png_path, int srgb) {
 	return PTX_OK;
 }
 
+int ptx_scene_set_punctual_lights(ptx_scene* sc, const float* lights, uint32_t n) {
+	// every refusal is decided before any device work; the call itself does none (ptx_render_nee uploads the lights when it next runs)
+	auto bad = [](const std::string& m) { return set_err(PTX_ERR_INVALID, "ptx_scene_set_punctual_lights: " + m); };
+	if (!sc) return bad("scene is NULL");
+	if (n && !lights) return bad("lights is NULL with n > 0");
+	if (n > 65536u) return bad("more than 65536 lights");
+	std::vector<double> cum(n);
+	double total = 0;
+	for (uint32_t k = 0; k < n; k++) {
+		const float* r = lights + 16 * (size_t)k;
+		const std::string at = "light " + std::to_string(k) + ": ";
+		for (int a = 0; a < 16; a++)
+			if (!std::isfinite(r[a])) return bad(at + "a field is not finite");
+		if (r[7] != 0.0f && r[7] != 1.0f) return bad(at + "kind must be 0 (point) or 1 (spot)");
+		if (r[8] < 0 || r[9] < 0 || r[10] < 0) return bad(at + "negative intensity");
+		if (r[3] < 0) return bad(at + "negative range");
+		if (r[7] == 1.0f) {
+			const double len = std::sqrt(((double)r[4] * r[4] + (double)r[5] * r[5]) + (double)r[6] * r[6]);
+			if (!(std::fabs(len - 1.0) <= 1e-3)) return bad(at + "a spot's direction must have unit length (within 1e-3)");
+			if (r[11] < r[12]) return bad(at + "cos_inner < cos_outer");
+		}
+		total += (0.2126 * (double)r[8] + 0.7152 * (double)r[9]) + 0.0722 * (double)r[10];
+		cum[k] = total;
+	}
+	ptx_scene::Punctual next;
+	if (n && total > 0) {   // all lights black: no lights, as n = 0
+		next.recs.assign(lights, lights + 16 * (size_t)n);
+		next.cdf.resize(n);
+		for (uint32_t k = 0; k < n; k++) next.cdf[k] = (float)(cum[k] / total);
+		next.cdf[n - 1] = 1.0f;
+	}
+	std::unique_lock<std::mutex> lk;
+	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);   // no render of this scene is in flight
+	std::lock_guard<std::mutex> tl(sc->lights_mu);
+	sc->punctual = std::move(next);
+	return PTX_OK;
+}
+
+int64_t ptx_gltf_read_punctual_lights(const char* gltf_path, float* dst, size_t dst_floats) {
+	if (!gltf_path) return -(int64_t)set_err(PTX_ERR_INVALID, "ptx_gltf_read_punctual_lights: path is NULL");
+	std::vector<float> recs;
+	try {
+		read_gltf_punctual_lights(gltf_path, recs);
+	} catch (const Error& e) {
+		return -(int64_t)set_err(e.code, e.msg);
+	} catch (const std::exception& e) {
+		return -(int64_t)set_err(PTX_ERR_PARSE, e.what());
+	}
+	if (dst) {
+		if (dst_floats < recs.size()) return -(int64_t)set_err(PTX_ERR_INVALID, "ptx_gltf_read_punctual_lights: destination too small");
+		if (!recs.empty()) memcpy(dst, recs.data(), recs.size() * 4);
+	}
+	return (int64_t)(recs.size() / 16);
+}
+
 int ptx_scene_from_arrays(ptx_ctx* ctx, const ptx_scene_desc* d, ptx_scene** out) {
 	if (!d || !out) return set_err(PTX_ERR_INVALID, "ptx_scene_from_arrays: NULL argument");
 	if (!d->camera || (d->n_models && (!d->model_xform || !d->model_surf)) ||
@@ -655,6 +711,8 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 	case PTX_ARR_LIGHT_GEOM: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.geom.data(); bytes = ll.geom.size() * 4; break; }
 	case PTX_ARR_ENV_ROW_CDF: { const auto& et = *build_env_table(const_cast<ptx_scene*>(sc)); src = et.row_cdf.data(); bytes = et.row_cdf.size() * 4; break; }
 	case PTX_ARR_ENV_CELL_CDF: { const auto& et = *build_env_table(const_cast<ptx_scene*>(sc)); src = et.cell_cdf.data(); bytes = et.cell_cdf.size() * 4; break; }
+	case PTX_ARR_PUNCTUAL: { std::lock_guard<std::mutex> tl(const_cast<ptx_scene*>(sc)->lights_mu); tmp = sc->punctual.recs; src = tmp.data(); bytes = tmp.size() * 4; break; }
+	case PTX_ARR_PUNCTUAL_CDF: { std::lock_guard<std::mutex> tl(const_cast<ptx_scene*>(sc)->lights_mu); tmp = sc->punctual.cdf; src = tmp.data(); bytes = tmp.size() * 4; break; }
 	case PTX_ARR_TRI_ISECT: src = h.tri_isect.data(); bytes = h.tri_isect.size() * sizeof(TriIsect); break;
 	case PTX_ARR_RES_NODES: src = h.res_nodes.data(); bytes = h.res_nodes.size() * 8; break;
 	case PTX_ARR_RES_REFS: src = h.res_refs.data(); bytes = h.res_refs.size() * 4; break;

@@ -53,6 +53,23 @@ public:
 		check(ptx_scene_load_gltf(ctx_, path.string().c_str(), &o, &scene_));
 	}
 
+	// The `point` and `spot` lights of a glTF file (KHR_lights_punctual) as 16-float records (ptx_gltf_read_punctual_lights; include/ptx.h has
+	// the record). Host only.
+	static std::vector<float> read_punctual_lights(const std::filesystem::path& path) {
+		const int64_t n = ptx_gltf_read_punctual_lights(path.string().c_str(), nullptr, 0);
+		if (n < 0) throw std::runtime_error(ptx_last_error());
+		std::vector<float> recs((size_t)n * 16);
+		if (n && ptx_gltf_read_punctual_lights(path.string().c_str(), recs.data(), recs.size()) < 0) throw std::runtime_error(ptx_last_error());
+		return recs;
+	}
+	// Point and spot lights for render_nee and its kin, which sample them as a third strategy (ptx_scene_set_punctual_lights); render() and the
+	// other calls ignore them. An empty vector removes them.
+	void set_punctual_lights(const std::vector<float>& records) {
+		if (!scene_) throw std::runtime_error("set_punctual_lights() before load_gltf()");
+		if (records.size() % 16) throw std::runtime_error("set_punctual_lights: the records are 16 floats each");
+		check(ptx_scene_set_punctual_lights(scene_, records.empty() ? nullptr : records.data(), (uint32_t)(records.size() / 16)));
+	}
+
 	// radiance sums [H][W][4]; with transparent_background set: the blended means (colour, alpha) of ptx_render_transparent. stats optional
 	std::vector<float> render_accum(ptx_render_stats* stats = nullptr) const {
 		if (!scene_) throw std::runtime_error("render() before load_gltf()");

@@ -1,6 +1,6 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
 //       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
 //       --nee:         light sampling towards the scene's emissive triangles (renderer::render_nee)
@@ -13,6 +13,8 @@
 //                      (PTX_NEE_CANDIDATES); combines with --nee-fused, --nee-env, --nee-sampler-pdf and --adaptive
 //       --adaptive THR[:MIN[:STEP]]: noise-driven per-pixel sample counts (renderer::render_adaptive) with spp as the cap: every pixel gets MIN
 //                      samples (8), then rounds of STEP (MIN) go to the pixels whose half-frames still disagree by more than THR
+//       --nee-punctual: with --nee (or a switch that implies it): the `point` and `spot` lights of the glTF being rendered (KHR_lights_punctual)
+//                      are read and set on the scene, and the light sample takes them as a third strategy; without --nee it is an error
 //       combinations:  --adaptive with --nee / --nee-fused / --nee-env / --nee-sampler-pdf / --nee-candidates renders the adaptive loop on the light-sampling estimator
 //                      (renderer::render_adaptive_nee); --adaptive --denoise, with or without --nee*, filters the adaptive frame
 //                      (ptx_denoise_counts on the guides of the first MIN samples); --nee* --denoise filters two light-sampled half-frames
@@ -45,7 +47,7 @@ static void write_png(const std::string& path, const std::vector<uint8_t>& rgba,
 }
 
 int main(int argc, char** argv) {
-	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false, nee_sampler_pdf = false;
+	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false, nee_sampler_pdf = false, nee_punctual = false;
 	float ad_thr = 0.1f;
 	unsigned ad_min = 8, ad_step = 0, nee_candidates = 1;
 	std::string aov_prefix, nee_env;
@@ -55,6 +57,7 @@ int main(int argc, char** argv) {
 		else if (argc > 1 && std::string(argv[1]) == "--nee") { nee = true; argv[1] = argv[0]; argv++; argc--; }   // renderer::render_nee: light sampling
 		else if (argc > 1 && std::string(argv[1]) == "--nee-fused") { nee = nee_fused = true; argv[1] = argv[0]; argv++; argc--; }   // ... one launch per pass
 		else if (argc > 1 && std::string(argv[1]) == "--nee-sampler-pdf") { nee = nee_sampler_pdf = true; argv[1] = argv[0]; argv++; argc--; }   // ... weights on the sampler's density
+		else if (argc > 1 && std::string(argv[1]) == "--nee-punctual") { nee_punctual = true; argv[1] = argv[0]; argv++; argc--; }   // ... the file's point and spot lights too; does not imply --nee
 		else if (argc > 2 && std::string(argv[1]) == "--nee-env") { nee = true; nee_env = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }   // ... the map as a light
 		else if (argc > 2 && std::string(argv[1]) == "--nee-candidates") {   // ... picked among M candidates
 			if (std::sscanf(argv[2], "%u", &nee_candidates) < 1 || nee_candidates < 1 || nee_candidates > 16) { std::fprintf(stderr, "error: --nee-candidates M, M = 1 .. 16\n"); return 1; }
@@ -68,7 +71,11 @@ int main(int argc, char** argv) {
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		return 1;
+	}
+	if (nee_punctual && !nee) {
+		std::fprintf(stderr, "error: --nee-punctual needs --nee (or --nee-fused, --nee-env, --nee-sampler-pdf, --nee-candidates): only the light-sampling estimator renders point and spot lights\n");
 		return 1;
 	}
 	if (argc == 5 && std::string(argv[1]) == "--event") {
@@ -108,6 +115,12 @@ int main(int argc, char** argv) {
 		r.load_gltf(argv[1]);
 		if (!nee_env.empty()) r.environment = nee_env;
 		r.nee_candidates = nee_candidates;
+		size_t n_punctual = 0;
+		if (nee_punctual) {
+			const std::vector<float> lamps = core::renderer::read_punctual_lights(argv[1]);
+			r.set_punctual_lights(lamps);
+			n_punctual = lamps.size() / 16;
+		}
 		auto t0 = std::chrono::steady_clock::now();
 		ptx_denoise_stats dst{};
 		ptx_adaptive_stats ast{};
@@ -158,6 +171,7 @@ int main(int argc, char** argv) {
 		if (nee && (adaptive || !denoise))   // the two half-frames of --nee --denoise are rendered without stats
 			std::printf(", \"nee_lights\": %u, \"nee_light_samples\": %llu, \"nee_light_visible\": %llu, \"nee_kernel_ms\": %.3f", nst.n_lights,
 			            (unsigned long long)nst.light_samples, (unsigned long long)nst.light_visible, nst.render.kernel_ms);
+		if (nee_punctual) std::printf(", \"nee_punctual_lights\": %zu", n_punctual);
 		std::printf("}\n");
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "error: %s\n", e.what());

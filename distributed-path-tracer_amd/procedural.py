@@ -435,6 +435,71 @@ def chart_scene(sun=None, blocker=False, facing=False, alpha=True):
                 names=names, cells=np.array(cells, np.int32))
 
 
+# ---------------------------------------------------------------------------- lamps (punctual lights, ptx_scene_set_punctual_lights)
+LAMP_BLOCKER = (1.0, 0.3, 1.5, -0.9, 0.9)   # y, x0, x1, z0, z1 of the floor scene's blocker quad
+LAMP_FIRST = (-0.6, 2.0, 0.3)               # lamp 0 of every lamp_scene: left of the blocker, whose shadow then falls on x > 0.7 of the floor
+
+
+def lamp_scene(n_lamps: int = 1, chart: bool = False, emitters: bool = False, blocker: bool = True, spots: bool = False, lamp_range: float = 0.0,
+               power: float = 10.0, seed: int = 23):
+    """A scene lit by point and spot lights -> (dict of arrays as plaza_scene, lights [n_lamps, 16] float32 for Scene.set_punctual_lights).
+      chart:    False: a diffuse floor (8 x 8 on y = 0) seen from above at an angle, a blocker quad at y = 1 (LAMP_BLOCKER) when `blocker`, and
+                with `emitters` one small bright emissive quad (0.2 x 0.2) at y = 3 facing down. True: chart_scene(facing=True, alpha=False), its emissive
+                factors set to zero unless `emitters`.
+      lamps:    lamp 0 at LAMP_FIRST, the others scattered (seeded) over |x|, |z| < 2.2 at heights 1.4 .. 2.6 (chart: 2 .. 4.4, between
+                the two charts); colours in [0.4, 1], intensities log-uniform over a decade around power / n_lamps.
+      spots:    odd lamps (all of them when n_lamps == 1) are spots shining down, tilted by up to 0.35 rad, cones 0.35 / 0.6 rad.
+      lamp_range: the range field of every lamp (0 = unlimited)."""
+    rng = np.random.default_rng(seed)
+    if chart:
+        d = chart_scene(facing=True, alpha=False, blocker=blocker)
+        if not emitters:
+            d["materials"] = d["materials"].copy()
+            d["materials"][:, 6:9] = 0
+        y_lo, y_hi = 2.0, 4.4
+    else:
+        verts, tris, mats = [], [], []
+
+        def add(x0, x1, z0, z1, y, up, mat):
+            v = np.zeros((4, 11), np.float32)
+            v[:, 0:3] = [[x0, y, z0], [x1, y, z0], [x1, y, z1], [x0, y, z1]]
+            v[:, 3:5] = [[0, 0], [1, 0], [1, 1], [0, 1]]
+            v[:, 5:8] = [0, 1 if up else -1, 0]
+            v[:, 8:11] = [1, 0, 0]
+            verts.append(v)
+            tris.append(np.array([[0, 2, 1], [0, 3, 2]] if up else [[0, 1, 2], [0, 2, 3]], np.uint32))
+            mats.append(mat)
+        add(-4, 4, -4, 4, 0.0, True, [0.7, 0.7, 0.7, 1.0, 0.6, 0.0, 0, 0, 0, 1.33, 0])
+        if blocker:
+            y, x0, x1, z0, z1 = LAMP_BLOCKER
+            add(x0, x1, z0, z1, y, True, [0.4, 0.5, 0.6, 1.0, 0.5, 0.0, 0, 0, 0, 1.33, 0])
+        if emitters:
+            add(-1.7, -1.5, -1.4, -1.2, 3.0, False, [0.8, 0.8, 0.8, 1.0, 0.5, 0.0, 5.0, 4.5, 3.5, 1.33, 0])
+        n = len(verts)
+        ident = [1, 0, 0, 0, 1, 0, 0, 0, 1]
+        cam = np.concatenate([_look_at([0.0, 5.0, 4.5], [0.0, 0.0, 0.0]), [np.float32(0.8)]]).astype(np.float32)
+        d = dict(model_xform=np.array([[0, 0, 0] + ident], np.float32), model_surf=np.array([[0, n]], np.int32),
+                 surf_range=np.array([[4 * k, 4, 2 * k, 2] for k in range(n)], np.int32), vertices=np.concatenate(verts),
+                 triangles=np.concatenate(tris), materials=np.array(mats, np.float32), camera=cam, sun=None)
+        y_lo, y_hi = 1.4, 2.6
+    lights = np.zeros((n_lamps, 16), np.float32)
+    for k in range(n_lamps):
+        pos = LAMP_FIRST if k == 0 else (rng.uniform(-2.2, 2.2), rng.uniform(y_lo, y_hi), rng.uniform(-2.2, 2.2))
+        if chart and k == 0:
+            pos = (LAMP_FIRST[0], 0.5 * (y_lo + y_hi), LAMP_FIRST[2])
+        tilt, turn = rng.uniform(0.0, 0.35), rng.uniform(0.0, 2 * np.pi)
+        colour = rng.uniform(0.4, 1.0, 3)
+        inten = (power / n_lamps) * 10.0 ** rng.uniform(-0.5, 0.5)
+        spot = spots and (k % 2 == 1 or n_lamps == 1)
+        direction = np.array([np.sin(tilt) * np.cos(turn), -np.cos(tilt), np.sin(tilt) * np.sin(turn)])
+        lights[k, 0:3], lights[k, 3] = pos, lamp_range
+        lights[k, 4:7] = (direction / np.linalg.norm(direction)) if spot else (0, 0, -1)
+        lights[k, 7] = 1.0 if spot else 0.0
+        lights[k, 8:11] = colour * inten
+        lights[k, 11], lights[k, 12] = (np.cos(0.35), np.cos(0.6)) if spot else (1.0, np.cos(np.pi / 4))
+    return d, lights
+
+
 # ---------------------------------------------------------------------------- the corner cluster (deep KD walks)
 def _flat_vertices(p):
     """[n, 3, 3] float32 corner positions -> vertices [3 n, 11] (per-triangle normal, tangent along the first edge), triangles [n, 3]."""

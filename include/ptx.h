@@ -113,6 +113,28 @@ void ptx_scene_destroy(ptx_scene* scene);
  * Radiance .hdr (by content, as stb_image decides); an .hdr keeps its float texels (image::hdr). */
 int ptx_scene_set_environment(ptx_scene* scene, const char* png_path, int srgb);
 
+/* Point and spot lights (glTF KHR_lights_punctual; no counterpart in the reference, which reads only the `directional` sun). They are
+ * scene state that ptx_render_nee and ptx_render_adaptive_nee sample as a third light-sampling strategy (PUNCTUAL LIGHTS below
+ * ptx_render_nee's flags has the estimator); ptx_render, ptx_render_transparent, ptx_render_aov and the PTX_INTEGRATOR_WORKER estimator
+ * ignore them. A light is a record of 16 floats:
+ *   [0..2] position   [3] range (0 = unlimited)   [4..6] direction: the unit direction the light shines in (ignored for a point light)
+ *   [7] kind: 0 point, 1 spot   [8..10] intensity rgb = colour x intensity   [11] cos_inner   [12] cos_outer   [13..15] zero
+ * n = 0 (lights may be NULL) removes them. Works on host-only scenes too; the call does no device work. PTX_ERR_INVALID for a NULL scene,
+ * NULL lights with n > 0, n > 65536, a non-finite field, a kind other than 0 or 1, a negative intensity component or range, a spot whose
+ * direction is not within 1e-3 of unit length, and a spot with cos_inner < cos_outer; a refused call leaves the scene's lights as they were.
+ *   THE CDF (PTX_ARR_PUNCTUAL_CDF), built on the host in float64 and stored as float32: the cumulative share of
+ *     lum(intensity) = 0.2126 r + 0.7152 g + 0.0722 b, the last entry 1. A light of zero luminance has probability 0; if all have, the call
+ *     stores no lights, exactly as n = 0. pmf_k is the difference of the STORED entries with cdf[-1] = 0: the probability the sampler realises. */
+int ptx_scene_set_punctual_lights(ptx_scene* scene, const float* lights /* [n][16], host */, uint32_t n);
+/* The `point` and `spot` lights of a glTF file as records for ptx_scene_set_punctual_lights. Host only, no context; only the .gltf is read.
+ * One record per node of scenes[0] that references such a light, in the loader's pre-order, placed by the loader's own node transforms
+ * (TRS only): position = the node's world origin, direction = the normalised world image of the local -Z axis, intensity = color (default
+ * 1, 1, 1) x intensity (default 1), range default 0, cos_inner = cos(innerConeAngle) (default 0), cos_outer = cos(outerConeAngle) (default
+ * pi / 4), computed in float64 and stored as float32 (a point light's are the defaults'). `directional` lights are skipped: the sun stays
+ * where it is (ptx_load_opts::sun_light_index). Returns the number of records; dst == NULL only counts. Returns -(ptx_status) on a file or
+ * parse error and when dst_floats < 16 x the count. ptx_scene_load_gltf does not pick the lights up: the caller reads and sets them. */
+int64_t ptx_gltf_read_punctual_lights(const char* gltf_path, float* dst /* NULL = count only */, size_t dst_floats);
+
 typedef struct ptx_scene_info {
 	uint32_t n_models, n_surfaces, n_vertices, n_triangles;
 	uint32_t n_kd_nodes;      /* flattened 8-byte nodes (branches + leaves) */
@@ -163,7 +185,10 @@ typedef enum ptx_array {
 	/* the environment map's sampling table of PTX_NEE_ENV_SAMPLES (built at the first request, on host-only scenes too; both empty when the
 	 * scene has no map or the map is black; ptx_scene_set_environment drops the table) */
 	PTX_ARR_ENV_ROW_CDF = 26, /* float[h]: cumulative share of the rows' mass, top row first, the last entry 1 */
-	PTX_ARR_ENV_CELL_CDF = 27 /* float[h][w]: cumulative share of the boxes within their row, the last entry 1; a row of zero mass is all 0 */
+	PTX_ARR_ENV_CELL_CDF = 27,/* float[h][w]: cumulative share of the boxes within their row, the last entry 1; a row of zero mass is all 0 */
+	/* the punctual lights of ptx_scene_set_punctual_lights (host-only scenes too; both empty when none are set) */
+	PTX_ARR_PUNCTUAL = 28,    /* float[n][16], as stored */
+	PTX_ARR_PUNCTUAL_CDF = 29 /* float[n]: cumulative share of lum(intensity), the last entry 1 */
 } ptx_array;
 int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, size_t dst_bytes);
 
@@ -553,6 +578,31 @@ int ptx_ctx_get_mask_exchange_stats(ptx_ctx* ctx, uint64_t* calls /* NULL ok */,
  * unfused call's with the same bits (on the queue route PTX_NEE_FUSED is ignored as above). With no light sample possible (empty list and
  * no environment table) no candidate is drawn, and the call is bit for bit the one without the bits, and ptx_render. */
 #define PTX_NEE_CANDIDATES(m) ((((uint32_t)(m)) - 1u) << 8)   /* m = 1 .. 16; m = 1 is 0: today's call */
+/* PUNCTUAL LIGHTS. With punctual lights on the scene (ptx_scene_set_punctual_lights) ptx_render_nee and ptx_render_adaptive_nee take them into
+ * the LIGHT SAMPLE of a vertex as a third strategy. No flag exists for it: a scene on which none were set (or on which they were cleared) runs
+ * the kernels without the branch and renders every bit as before. ptx_render, ptx_render_transparent, ptx_render_aov and the WORKER estimator
+ * ignore the lights. IEEE binary32, each operation rounded on its own, in the order written.
+ *   SELECTION. "Other strategies exist" means: the triangle list is non-empty, or PTX_NEE_ENV_SAMPLES is set and a table exists. c_p = 1 when
+ *     no other strategy exists, else 0.5. Candidate j draws q = draws(pixel, sample, depth, pass, block 0x200 + j); the call without
+ *     PTX_NEE_CANDIDATES is j = 0. Candidate j is a punctual sample iff c_p == 1 or q.x < 0.5F; otherwise it is the candidate of the text
+ *     above, from its blocks 3 + 2 j and 4 + 2 j, unchanged. Light k is the first entry with q.y < cdf[k], the index clamped to n - 1.
+ *   PUNCTUAL SAMPLE. v = position_k - pos_x, dist2 = dot(v, v), dist = sqrt(dist2), w = v / dist. att = 1 for a point light; for a spot
+ *     cd = dot(direction_k, -w), s = clamp((cd - cos_outer) / max(cos_inner - cos_outer, 1e-6F), 0, 1), att = s * s.
+ *     E = (intensity_k * att) / dist2. No contribution and no shadow ray unless dist2 > 0, dot(n_x, w) > 0, pmf_k > 0,
+ *     range == 0 || dist <= range, att > 0 and max(E) > 0. brdf, pdf, pe and qc are those of a triangle sample; b = qc * pe, LIB's integrand
+ *     brdf' at w, cosine included (eval_brdf carries it); x = ((T * b) * E) / (c_p * pmf_k) with T before its update. A delta light has no
+ *     MIS partner: its weight is 1, and PTX_NEE_SAMPLER_PDF changes nothing in this sample. The shadow ray (origin pos_x + w * eps,
+ *     direction w) is a closest-hit query on the scene's route; x is added iff it finds nothing or its hit distance t is not < dist. A
+ *     surface of opacity < 1 in the way blocks the light, as it blocks a triangle sample.
+ *   THE OTHER WEIGHTS. The other strategies take only 1 - c_p of the candidates. CONVENTION: wherever the text above has a light-side density
+ *     in a weight — p_l, (1 - c_env) * p_l or c_env * p in wl, in the emission weight and in the miss weight — that density is first computed
+ *     exactly as written there, its c_env factor included, and the result is then multiplied from the left: p' = (1 - c_p) * p. With c_p == 1
+ *     no other strategy exists and none of these weights is evaluated.
+ *   CANDIDATES. Under PTX_NEE_CANDIDATES(m) a punctual candidate is one more kind of candidate: the same W_j = max(x_j), the same reservoir,
+ *     one shadow ray for the pick, with the punctual visibility rule when the pick is punctual. PTX_NEE_NO_LIGHT_SAMPLES empties the triangle
+ *     list only. light_samples and light_visible count punctual rays like the others; the order of the additions of a sample is unchanged.
+ *   EXPECTATION. A punctual candidate has selection probability c_p * pmf_k and returns brdf'(w_k) E_k V_k over it: unbiased for the sum over
+ *     the lights. The other strategies' light-side and BSDF-side weights still add to one over the directions they share. */
 typedef struct ptx_nee_cfg { uint32_t flags; } ptx_nee_cfg;
 typedef struct ptx_nee_stats {
 	ptx_render_stats render;   /* rays = closest-hit + shadow queries */

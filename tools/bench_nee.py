@@ -32,6 +32,13 @@
                                         the mean squared error of the written bytes against the product's ref_spp ptx_render frame (4096) of
                                         another seed, and the error of M = 1 in the same form at the spp that takes the row's time. Also writes the
                                         lines to profiles/nee_ris_bench.txt.
+  tools/bench_nee.py --punctual [ref_spp] [reps] [spp]
+                                        Point and spot lights (Scene.set_punctual_lights) on procedural.lamp_scene with an emitter, with 1 lamp and
+                                        with 64 (half of them spots), at 1920 x 1080, 8 bounces, 16 spp, M = 1 and M = 4, with and without
+                                        PTX_NEE_FUSED: the four calls of a scene alternate in one process, each kept at the smallest of `reps`
+                                        synchronised calls after a warm-up. Per row: the time, light rays traced per sample, and the mean squared
+                                        error of the written bytes against a ref_spp (1024) frame of the SAME call (unfused, M = 1) of another seed:
+                                        ptx_render cannot see the lamps. The lines are the first part of profiles/nee_punctual_bench.txt.
 Prints one JSON line per measurement. A scene without listed emitters (atrium) shows the cost of the wavefront form alone.
 """
 import importlib
@@ -296,7 +303,43 @@ def main_ris(ref_spp, reps, spp):
         f.write("tools/bench_nee.py --ris: PTX_NEE_CANDIDATES(M) against M = 1, fused and unfused, MI355X\n" + "\n".join(lines) + "\n")
 
 
+def main_punctual(ref_spp, reps, spp):
+    ctx = ptx.Context(0)
+    for n_lamps in (1, 64):
+        d, lamps = proc.lamp_scene(n_lamps, emitters=True, spots=True)
+        s = ptx.Scene.from_arrays(ctx, *[d[k] for k in KEYS])
+        s.set_punctual_lights(lamps)
+        ref_acc = zeros()
+        s.render_nee(W, H, ref_spp, BOUNCES, accum=ref_acc, seed=REF_SEED, want_stats=False)
+        ctx.synchronize()
+        ref = ctx.tonemap_encode(ref_acc, W, H, ref_spp)[..., :3].astype(np.float64) / 255
+        del ref_acc
+        forms = {(form, m): base | ptx.NEE_CANDIDATES(m) for form, base in (("fused", ptx.NEE_FUSED), ("unfused", 0)) for m in (1, 4)}
+        best, acc, st, launches = {k: 1e30 for k in forms}, {}, {}, {}
+        for r in range(reps + 1):
+            for k, flags in forms.items():
+                a = zeros()
+                t0 = time.perf_counter()
+                _, st[k] = s.render_nee(W, H, spp, BOUNCES, accum=a, seed=SEED, flags=flags)
+                ctx.synchronize()
+                dt = time.perf_counter() - t0
+                if r:
+                    best[k] = min(best[k], dt)
+                acc[k], launches[k] = a, ctx.timing()["fused_launches"]
+        for (form, m), sec in best.items():
+            k = (form, m)
+            mse = float(np.mean((ctx.tonemap_encode(acc[k], W, H, spp)[..., :3].astype(np.float64) / 255 - ref) ** 2))
+            print(json.dumps(dict(scene="lamp_scene", lamps=n_lamps, form=form, M=m, W=W, H=H, bounces=BOUNCES, spp=spp, n_lights=st[k]["n_lights"],
+                                  fused_launches=launches[k], s=round(sec, 4), msamples_s=round(W * H * spp / sec / 1e6, 1), rays=st[k]["rays"],
+                                  light_samples_per_sample=round(st[k]["light_samples"] / st[k]["samples"], 4),
+                                  light_visible_per_sample=round(st[k]["light_visible"] / st[k]["samples"], 4), mse=mse, ref_spp=ref_spp)), flush=True)
+        s.close()
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--punctual":
+        main_punctual(int(sys.argv[2]) if len(sys.argv) > 2 else 1024, int(sys.argv[3]) if len(sys.argv) > 3 else 3, int(sys.argv[4]) if len(sys.argv) > 4 else 16)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--ris":
         main_ris(int(sys.argv[2]) if len(sys.argv) > 2 else 4096, int(sys.argv[3]) if len(sys.argv) > 3 else 3, int(sys.argv[4]) if len(sys.argv) > 4 else 16)
         sys.exit(0)
