@@ -253,7 +253,7 @@ constexpr uint32_t kNeePunctualRay = 0xFFFFFFFEu;   // exp_surf of a punctual sa
 hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, hipStream_t stream);
 // sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF (nee_core.hpp: sampler_pdf in pe's place in the weights)
 // candidates: M of PTX_NEE_CANDIDATES, 1 .. 16; above 1 the RIS variants run (nee_core.hpp: the candidate loop of nee_vertex)
-// Pn.n != 0: the PUN variants run (nee_punctual.hip), and launch_nee_settle is told so: its punctual form knows kNeePunctualRay
+// Pn.n != 0: the PUN variants run (part 1 of nee.hip), and launch_nee_settle is told so: its punctual form knows kNeePunctualRay
 hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
                             const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
 hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, bool punctual, hipStream_t stream);

@@ -17,9 +17,17 @@ namespace ptx {
 
 constexpr int kNeeBlock = 256;
 
-// This file is compiled twice, so that the two halves of k_nee_shade's variants build side by side: as itself (everything but the PUN
-// variants) and through nee_punctual.hip, which defines PTX_NEE_PUNCTUAL_TU (the PUN variants and launch_nee_shade_punctual alone).
-#ifndef PTX_NEE_PUNCTUAL_TU
+// This file is compiled twice, with -DPTX_NEE_PART=0 and 1, so that the two halves of k_nee_shade's variants build side by side. Here a part
+// is the PUN bit of the mask alone (nee_core.hpp), 48 kernels each: part 0 is everything but the PUN variants, part 1 the PUN variants and
+// launch_nee_shade_part<1> alone.
+#ifndef PTX_NEE_PART
+#error "nee.hip is compiled once per half of the variants: -DPTX_NEE_PART=<0..1> (the Makefile's NEE_SHADE_PARTS)"
+#endif
+static_assert(PTX_NEE_PART == 0 || PTX_NEE_PART == 1, "a part of this file is the PUN bit of a variant");
+constexpr uint32_t kNeeShadePartShift = 6, kNeeShadePartMask = (1u << kNeeShadePartShift) - 1;
+static_assert(NEE_PUN == 1u << kNeeShadePartShift, "the two parts are split by PUN");
+
+#if PTX_NEE_PART == 0
 __global__ void __launch_bounds__(kNeeBlock) k_nee_generate(DevScene S, RenderParams P, NeeStream out, float4* __restrict__ L, uint32_t n) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
 	if (i >= n) return;
@@ -51,12 +59,8 @@ DEV void nee_append2(bool first, bool second, uint32_t* counter, uint32_t& pos_f
 }
 
 // One vertex of every live path: loads the hit and the path state of entry i, runs nee_vertex (nee_core.hpp) and stores what it returns.
-// TEX / ALPHA / SUN compile the texture lookups / the pass-through and catcher code / the sun request in, as the render variants do;
-// ENV the environment sample and the miss weight (PTX_NEE_ENV_SAMPLES; TEX only: a map implies the TEX variants). Ev, the last argument, is
-// read by the ENV variants alone. SPDF: the weights of PTX_NEE_SAMPLER_PDF. RIS: the light sample chosen among ris_m candidates
-// (PTX_NEE_CANDIDATES); the other variants do not read ris_m. PUN: punctual lights on the scene (Pn), a third kind of candidate; the other
-// variants do not read Pn.
-template <bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false, bool RIS = false, bool PUN = false>
+// V: the variant (nee_core.hpp has the bits). Ev is read by the ENV variants alone, ris_m by the RIS variants, Pn by the PUN variants.
+template <uint32_t V>
 __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParams P, NeeLights Lt, NeeStream in, NeeHits H, uint32_t n, NeeStream out, NeeShadow W,
                                                          uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeeEnv Ev, uint32_t ris_m, NeePunctual Pn) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
@@ -76,7 +80,7 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 		const uint32_t pixel = py * P.W + px;
 		const float4 l4 = Lrec[id];
 		V3 L = mk(l4.x, l4.y, l4.z);
-		if (nee_vertex<TEX, ALPHA, SUN, ENV, SPDF, RIS, PUN>(S, P, Lt, Ev, ris_m, pixel, sample, H.surface[i], (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v, Pn))
+		if (nee_vertex<V>(S, P, Lt, Ev, ris_m, pixel, sample, H.surface[i], (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v, Pn))
 			Lrec[id] = make_float4(L.x, L.y, L.z, l4.w);
 	}
 	// shadow rays of the round: at most two per path, so every position is below twice the round's paths
@@ -110,7 +114,7 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 	}
 }
 
-#ifndef PTX_NEE_PUNCTUAL_TU
+#if PTX_NEE_PART == 0
 // The answers of the round's shadow rays (SH: their closest hits). One lane per path of the round, sun before light.
 // PUN: the round may hold punctual samples' rays (kNeePunctualRay): visible iff nothing is hit nearer than the light.
 template <bool PUN>
@@ -154,63 +158,51 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_settle(NeeStream in, uint32_t
 #endif
 
 // ------------------------------------------------------------------------------------ launchers
-#ifndef PTX_NEE_PUNCTUAL_TU
+#if PTX_NEE_PART == 0
 hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, hipStream_t stream) {
 	hipLaunchKernelGGL(k_nee_generate, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, S, P, out, L, n);
 	return hipGetLastError();
 }
 #endif
 
-template <bool TEX, bool ALPHA, bool ENV, bool SPDF, bool RIS, bool PUN>
-static void nee_shade_sun(bool sun, dim3 grid, hipStream_t stream, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeStream& in,
-                          const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L) {
-	if (sun) hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, true, ENV, SPDF, RIS, PUN>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m, Pn);
-	else hipLaunchKernelGGL((k_nee_shade<TEX, ALPHA, false, ENV, SPDF, RIS, PUN>), grid, dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m, Pn);
+using NeeShadeKernel = decltype(&k_nee_shade<0u>);
+struct NeeShadeTable { NeeShadeKernel fn[kNeeShadePartMask + 1]; };   // by the bits below PUN; nullptr: no such variant
+
+// the kernels of this part: one entry for every mask of kNeeVariants that lies in it
+template <size_t... I>
+static NeeShadeTable nee_shade_table(std::index_sequence<I...>) {
+	NeeShadeTable t{};
+	([&] {
+		constexpr uint32_t V = kNeeVariants.v[I];
+		if constexpr ((V >> kNeeShadePartShift) == PTX_NEE_PART) t.fn[V & kNeeShadePartMask] = &k_nee_shade<V>;
+	}(), ...);
+	return t;
 }
 
-template <bool SPDF, bool RIS, bool PUN>
-static hipError_t launch_nee_shade_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeStream& in, const NeeHits& H, uint32_t n,
-                                        const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
-	const dim3 grid((n + kNeeBlock - 1) / kNeeBlock);
-	const bool sun = S.sun.present != 0;
-	if (Ev.row_cdf) {   // a table means a map, and a map means the TEX variants
-		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
-		if (S.any_alpha) nee_shade_sun<true, true, true, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<true, false, true, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
-	} else if (S.any_texture) {
-		if (S.any_alpha) nee_shade_sun<true, true, false, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<true, false, false, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
-	} else {
-		if (S.any_alpha) nee_shade_sun<false, true, false, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
-		else nee_shade_sun<false, false, false, SPDF, RIS, PUN>(sun, grid, stream, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L);
-	}
+// Declared for both parts, defined by the one compilation of that part, as an explicit specialisation of a template without a body
+// (nee_fused.hip has the reason): the linker puts the two together.
+template <uint32_t PART>
+hipError_t launch_nee_shade_part(uint32_t V, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeStream& in, const NeeHits& H,
+                                 uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
+template <>
+hipError_t launch_nee_shade_part<PTX_NEE_PART>(uint32_t V, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeStream& in,
+                                               const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
+	static const NeeShadeTable table = nee_shade_table(std::make_index_sequence<kNeeVariantCount>{});
+	const NeeShadeKernel kernel = table.fn[V & kNeeShadePartMask];
+	if (!kernel) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(kernel, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m, Pn);
 	return hipGetLastError();
 }
 
-// the four quarters (SPDF x RIS) of one half (PUN) of the variants
-template <bool PUN>
-static hipError_t launch_nee_shade_half(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
-                                        const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
-	if (candidates > 1)
-		return sampler_pdf ? launch_nee_shade_variant<true, true, PUN>(S, P, Lt, Ev, Pn, candidates, in, H, n, out, W, cnt, L, stream)
-		                   : launch_nee_shade_variant<false, true, PUN>(S, P, Lt, Ev, Pn, candidates, in, H, n, out, W, cnt, L, stream);
-	return sampler_pdf ? launch_nee_shade_variant<true, false, PUN>(S, P, Lt, Ev, Pn, 1u, in, H, n, out, W, cnt, L, stream)
-	                   : launch_nee_shade_variant<false, false, PUN>(S, P, Lt, Ev, Pn, 1u, in, H, n, out, W, cnt, L, stream);
-}
-
-hipError_t launch_nee_shade_punctual(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
-                                     const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
-#ifdef PTX_NEE_PUNCTUAL_TU
-hipError_t launch_nee_shade_punctual(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
-                                     const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
-	return launch_nee_shade_half<true>(S, P, Lt, Ev, Pn, sampler_pdf, candidates, in, H, n, out, W, cnt, L, stream);
-}
-#else
-// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF; candidates > 1: the RIS variants with M = candidates (PTX_NEE_CANDIDATES); Pn.n != 0: the PUN variants
+#if PTX_NEE_PART == 0
+// the variant: nee_select_variant (nee_core.hpp), as for launch_nee_fused
 hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
                             const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
-	if (Pn.n != 0) return launch_nee_shade_punctual(S, P, Lt, Ev, Pn, sampler_pdf, candidates, in, H, n, out, W, cnt, L, stream);
-	return launch_nee_shade_half<false>(S, P, Lt, Ev, Pn, sampler_pdf, candidates, in, H, n, out, W, cnt, L, stream);
+	uint32_t V, ris_m;
+	const hipError_t e = nee_select_variant(S, Ev, Pn, sampler_pdf, candidates, V, ris_m);
+	if (e != hipSuccess) return e;
+	const auto part = (V >> kNeeShadePartShift) ? launch_nee_shade_part<1> : launch_nee_shade_part<0>;
+	return part(V, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L, stream);
 }
 
 hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, bool punctual, hipStream_t stream) {

@@ -2,9 +2,57 @@
 // path state from the round's arrays and stores what nee_vertex returns; k_nee_fused (nee_fused.hip) calls it on registers.
 // Numerics as in kernels.hip: IEEE binary32 in the written order, no contraction.
 #pragma once
+#include <utility>
 #include "device_core.hpp"
 
 namespace ptx {
+
+// ---- the variant mask. What a scene and a call compile into the vertex is one uint32_t of these bits: the only template argument of a variant
+// (V) from the kernels down to nee_candidate, the argument of nee_fused_block, and the index of the launchers' tables.
+// Low four bits, the scene: TEX / ALPHA / SUN compile the texture lookups / the pass-through and catcher code / the sun request in, as the
+// render variants do; ENV the environment sample (PTX_NEE_ENV_SAMPLES with a table; TEX only: a map implies the TEX variants).
+// High three bits, the PART (V >> kNeePartShift): SPDF the weights of PTX_NEE_SAMPLER_PDF, RIS the light sample chosen among ris_m candidates
+// (PTX_NEE_CANDIDATES), PUN punctual lights on the scene. nee_fused.hip is compiled once per part.
+enum : uint32_t { NEE_TEX = 1u, NEE_ALPHA = 2u, NEE_SUN = 4u, NEE_ENV = 8u, NEE_SPDF = 16u, NEE_RIS = 32u, NEE_PUN = 64u };
+constexpr uint32_t kNeePartShift = 4, kNeeSceneMask = (1u << kNeePartShift) - 1, kNeeParts = 8;
+
+// The variants that exist, as data: every mask but those with ENV and without TEX, ascending, so 12 per part. The launchers' tables are built
+// from this list and from nothing else; a mask that is not in it has no kernel.
+constexpr uint32_t kNeeVariantCount = 96;
+struct NeeVariantList { uint32_t v[kNeeVariantCount]; uint32_t n; };
+constexpr NeeVariantList nee_variant_list() {
+	NeeVariantList l{};
+	for (uint32_t v = 0; v < (kNeeParts << kNeePartShift); v++) {
+		if ((v & NEE_ENV) && !(v & NEE_TEX)) continue;
+		if (l.n < kNeeVariantCount) l.v[l.n] = v;
+		l.n++;
+	}
+	return l;
+}
+constexpr NeeVariantList kNeeVariants = nee_variant_list();
+// whether `pred` holds for every entry of the list
+template <typename Pred>
+constexpr bool nee_all_variants(Pred pred) {
+	for (uint32_t i = 0; i < kNeeVariantCount; i++)
+		if (!pred(kNeeVariants.v[i])) return false;
+	return true;
+}
+constexpr bool nee_env_has_tex(uint32_t v) { return !(v & NEE_ENV) || (v & NEE_TEX); }
+static_assert(kNeeVariants.n == kNeeVariantCount, "96 variants: 12 scene masks in each of the 8 parts");
+static_assert(nee_all_variants(nee_env_has_tex), "ENV reads the map through the TEX code");
+
+// The one rule from a scene and a call to a variant, for both forms. A table (Ev) means a map, and a map means the ENV variants, which are TEX
+// variants: a scene without textures or without an environment texture cannot have one. sampler_pdf: SPDF. candidates > 1: RIS with
+// M = candidates; ris_m is what the kernel receives. Pn.n != 0: PUN.
+inline hipError_t nee_select_variant(const DevScene& S, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, uint32_t& V, uint32_t& ris_m) {
+	V = (S.any_texture ? NEE_TEX : 0u) | (S.any_alpha ? NEE_ALPHA : 0u) | (S.sun.present != 0 ? NEE_SUN : 0u) | (sampler_pdf ? NEE_SPDF : 0u) | (candidates > 1 ? NEE_RIS : 0u) | (Pn.n != 0 ? NEE_PUN : 0u);
+	ris_m = candidates > 1 ? candidates : 1u;
+	if (Ev.row_cdf) {
+		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
+		V |= NEE_ENV;
+	}
+	return hipSuccess;
+}
 
 enum { BLOCK_LIGHT = 3, BLOCK_ENV = 4 };   // Philox blocks of the light sample's and the environment sample's draws (BLOCK_SURFACE / BLOCK_SUN / BLOCK_JITTER: device_core.hpp)
 enum { BLOCK_PUNCTUAL = 0x200 };           // punctual lights on the scene: candidate j draws its strategy (x) and its light (y) from block BLOCK_PUNCTUAL + j
@@ -100,10 +148,11 @@ struct NeeVertex {
 // statements are then the former ones, and the unflagged kernels keep their registers. The RIS vertex takes M of them.
 // PUN (punctual lights on the scene, Pn; include/ptx.h: PUNCTUAL LIGHTS): the candidate is a punctual sample with probability c_p, drawn from
 // block_pun, and the other strategies' densities carry (1 - c_p). Without PUN, Pn, c_p and block_pun are not read and no statement changes.
-template <bool TEX, bool ENV, bool SPDF, bool PUN = false>
+template <uint32_t V>
 DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, float c_env, uint32_t pixel, uint32_t sample, uint32_t depth, uint32_t pass,
                        uint32_t block_light, uint32_t block_env, const Surf& sf, V3 normal, V3 outcoming, V3 T, const MatEval& me, float roughness, float spec_prob, V3& lx, V3& lo, V3& ld,
                        uint32_t& exp_surf, uint32_t& exp_tri, bool& want, const NeePunctual& Pn = NeePunctual{}, float c_p = 0.0f, uint32_t block_pun = 0u) {
+	constexpr bool TEX = (V & NEE_TEX) != 0, ENV = (V & NEE_ENV) != 0, SPDF = (V & NEE_SPDF) != 0, PUN = (V & NEE_PUN) != 0;   // ALPHA, SUN and RIS are not read here
 	if constexpr (PUN) {
 		const float4 q = draws(P, pixel, sample, depth, pass, block_pun);
 		if (c_p == 1.0F || q.x < 0.5F) {
@@ -234,9 +283,11 @@ DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights
 // RIS (PTX_NEE_CANDIDATES(m), m > 1): the light sample is chosen among ris_m candidates. Without RIS ris_m is not read and no statement changes.
 // PUN (punctual lights on the scene, Pn): a candidate may be a punctual sample, and the other strategies' densities carry (1 - c_p) in every
 // weight. Without PUN, Pn is not read and no statement changes.
-template <bool TEX, bool ALPHA, bool SUN, bool ENV = false, bool SPDF = false, bool RIS = false, bool PUN = false>
+template <uint32_t V>
 DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, uint32_t pixel, uint32_t sample, int32_t surf, uint32_t tri, float b1, float b2,
                     float hit_dist, V3& o, V3& d, V3& T, V3& L, float& p_prev, uint32_t& depth, uint32_t& pass, NeeVertex& out, const NeePunctual& Pn = NeePunctual{}) {
+	constexpr bool TEX = (V & NEE_TEX) != 0, ALPHA = (V & NEE_ALPHA) != 0, SUN = (V & NEE_SUN) != 0, ENV = (V & NEE_ENV) != 0;
+	constexpr bool SPDF = (V & NEE_SPDF) != 0, RIS = (V & NEE_RIS) != 0, PUN = (V & NEE_PUN) != 0;
 	bool& alive = out.alive;
 	bool& want_sun = out.want_sun;
 	bool& want_light = out.want_light;
@@ -342,7 +393,7 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 		if (last) break;
 		// ---- light sample
 		if constexpr (!RIS) {
-			nee_candidate<TEX, ENV, SPDF, PUN>(S, P, Lt, Ev, c_env, pixel, sample, depth, pass, BLOCK_LIGHT, BLOCK_ENV, sf, normal, outcoming, T, me, roughness, spec_prob, lx, lo, ld,
+			nee_candidate<V>(S, P, Lt, Ev, c_env, pixel, sample, depth, pass, BLOCK_LIGHT, BLOCK_ENV, sf, normal, outcoming, T, me, roughness, spec_prob, lx, lo, ld,
 			                                   exp_surf, exp_tri, want_light, Pn, c_p, BLOCK_PUNCTUAL);
 		} else {
 			// M candidates, one kept by weighted reservoir selection (include/ptx.h: PTX_NEE_CANDIDATES). The reservoir is lx, ld, the visibility
@@ -352,7 +403,7 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 				V3 cx = {0, 0, 0}, co = {0, 0, 0}, cd = {0, 0, 1};
 				uint32_t cs = 0, ct = 0;
 				bool cw = false;
-				nee_candidate<TEX, ENV, SPDF, PUN>(S, P, Lt, Ev, c_env, pixel, sample, depth, pass, BLOCK_LIGHT + 2 * j, BLOCK_ENV + 2 * j, sf, normal, outcoming, T, me, roughness, spec_prob, cx, co, cd,
+				nee_candidate<V>(S, P, Lt, Ev, c_env, pixel, sample, depth, pass, BLOCK_LIGHT + 2 * j, BLOCK_ENV + 2 * j, sf, normal, outcoming, T, me, roughness, spec_prob, cx, co, cd,
 				                                   cs, ct, cw, Pn, c_p, BLOCK_PUNCTUAL + j);
 				if (!cw) continue;
 				const float w_j = pmax(cx.x, pmax(cx.y, cx.z));

@@ -24,31 +24,34 @@ namespace ptx {
 // VGPRs without RIS, 184-256 with. One is too full for that: with ENV, SUN, RIS and SPDF together the global-memory variant with ALPHA spills
 // 3 VGPRs at 512, so the variants of that combination get 256 (up to 260 VGPRs). All 144 were compiled; none uses scratch.
 // -DPTX_NEE_FUSED_BLOCK=n: one size for all (measurement).
-constexpr int nee_fused_block(bool tex, bool sun, bool env = false, bool ris = false, bool pun = false, bool spdf = false) {
+constexpr int nee_fused_block(uint32_t V) {
 #ifdef PTX_NEE_FUSED_BLOCK
 	return PTX_NEE_FUSED_BLOCK;
 #else
-	return (pun && ris && spdf && env && sun) ? 256 : (tex || sun || env || ris || pun) ? 512 : 768;
+	constexpr uint32_t kFullest = NEE_PUN | NEE_RIS | NEE_SPDF | NEE_ENV | NEE_SUN;
+	return (V & kFullest) == kFullest ? 256 : (V & (NEE_TEX | NEE_SUN | NEE_ENV | NEE_RIS | NEE_PUN)) ? 512 : 768;
 #endif
 }
-static_assert(nee_fused_block(false, false) % 64 == 0 && nee_fused_block(true, true) % 64 == 0 && nee_fused_block(false, false) <= kBlock && nee_fused_block(true, true) <= kBlock,
-              "whole waves, and the spill area is sized for kBlock / 64 waves per workgroup");
+constexpr bool nee_fused_block_fits(uint32_t V) { return nee_fused_block(V) % 64 == 0 && nee_fused_block(V) <= kBlock; }
+static_assert(nee_all_variants(nee_fused_block_fits), "whole waves, and the spill area is sized for kBlock / 64 waves per workgroup");
 
 DEV uint32_t wave_sum(uint32_t v) {
 	for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
 	return v;   // lane 0 holds the sum
 }
 
+// V: the variant (nee_core.hpp has the bits).
 // ENV: the variants of PTX_NEE_ENV_SAMPLES (TEX only); Ev, the last argument, is read by them alone.
 // SPDF: the variants of PTX_NEE_SAMPLER_PDF. sampler_pdf costs them 0 to 2 VGPRs, and each compiles without scratch at its unflagged
 // twin's workgroup size, so nee_fused_block holds for them too (DESIGN.md 5.7 has their rows).
 // RIS: the variants of PTX_NEE_CANDIDATES, the light sample chosen among ris_m candidates; the other variants do not read ris_m.
 // PUN: the variants for scenes with punctual lights (Pn), a third kind of candidate; the other variants do not read Pn.
-template <int MODE, bool TEX, bool ALPHA, bool SUN, bool ENV, bool SPDF = false, bool RIS = false, bool PUN = false>
-__global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV, RIS, PUN, SPDF)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
+template <int MODE, uint32_t V>
+__global__ void __launch_bounds__(nee_fused_block(V)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
                                                               const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space,
                                                               NeeEnv Ev, uint32_t ris_m, NeePunctual Pn) {
-	constexpr int kThreads = nee_fused_block(TEX, SUN, ENV, RIS, PUN, SPDF);
+	constexpr bool SUN = (V & NEE_SUN) != 0, ENV = (V & NEE_ENV) != 0, PUN = (V & NEE_PUN) != 0;
+	constexpr int kThreads = nee_fused_block(V);
 	DevScene S = S0;
 	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;  // see struct Tables
 	const Staged st = stage_geometry<MODE>(S, g_smem);
@@ -124,7 +127,7 @@ __global__ void __launch_bounds__(nee_fused_block(TEX, SUN, ENV, RIS, PUN, SPDF)
 			const int32_t surf = hit ? h.surface : -1;
 			const uint32_t tri = hit ? (h.tri & S.tri_id_mask) - S.surfaces[h.surface].tri_base : 0u;
 			NeeVertex v;
-			nee_vertex<TEX, ALPHA, SUN, ENV, SPDF, RIS, PUN>(S, P, Lt, Ev, ris_m, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v, Pn);
+			nee_vertex<V>(S, P, Lt, Ev, ris_m, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v, Pn);
 			bool alive = v.alive;
 			// ---------------- the sun ray: occluded = any hit
 			if constexpr (SUN) {
@@ -181,87 +184,70 @@ static hipError_t set_lds(const void* fn, size_t bytes) {
 	return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-template <int MODE, bool SPDF, bool RIS, bool PUN, bool TEX, bool ALPHA, bool SUN, bool ENV = false>
-static hipError_t launch_nee_fused_variant(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeFusedBuffers& B, size_t lds_bytes, int grid,
-                                           hipStream_t stream) {
-	const auto kernel = &k_nee_fused<MODE, TEX, ALPHA, SUN, ENV, SPDF, RIS, PUN>;
+// This file is compiled once per part (nee_core.hpp: the SPDF, RIS and PUN bits of the mask), with -DPTX_NEE_PART=<part>, so that the eight
+// parts of the variants build side by side. Each compilation holds the 36 kernels of its part and defines launch_nee_fused_part<its part>;
+// part 0 holds launch_nee_fused as well, which picks the part by the mask's high bits.
+#ifndef PTX_NEE_PART
+#error "nee_fused.hip is compiled once per part of the variants: -DPTX_NEE_PART=<0..7> (the Makefile's NEE_FUSED_PARTS)"
+#endif
+static_assert(PTX_NEE_PART >= 0 && PTX_NEE_PART < (int)kNeeParts, "a part is the SPDF, RIS and PUN bits of a variant");
+
+using NeeFusedKernel = decltype(&k_nee_fused<MODE_GLOBAL, 0u>);
+struct NeeFusedTable { NeeFusedKernel fn[kNeeSceneMask + 1]; };   // by the low four bits; nullptr: no such variant
+
+// the kernels of MODE in this part: one entry for every mask of kNeeVariants that lies in it
+template <int MODE, size_t... I>
+static NeeFusedTable nee_fused_table(std::index_sequence<I...>) {
+	NeeFusedTable t{};
+	([&] {
+		constexpr uint32_t V = kNeeVariants.v[I];
+		if constexpr ((V >> kNeePartShift) == PTX_NEE_PART) t.fn[V & kNeeSceneMask] = &k_nee_fused<MODE, V>;
+	}(), ...);
+	return t;
+}
+
+template <int MODE>
+static hipError_t launch_nee_fused_mode(uint32_t V, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeFusedBuffers& B, size_t lds_bytes,
+                                        int grid, hipStream_t stream) {
+	static const NeeFusedTable table = nee_fused_table<MODE>(std::make_index_sequence<kNeeVariantCount>{});
+	const NeeFusedKernel kernel = table.fn[V & kNeeSceneMask];
+	if (!kernel) return hipErrorInvalidValue;
 	if (MODE != MODE_GLOBAL) {
 		hipError_t e = set_lds(reinterpret_cast<const void*>(kernel), lds_bytes);
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL(kernel, dim3(grid), dim3(nee_fused_block(TEX, SUN, ENV, RIS, PUN, SPDF)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces, S.spaces, S.model_space, Ev, ris_m, Pn);
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(nee_fused_block(V)), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, Lt, B, S.models, S.surfaces, S.spaces, S.model_space, Ev, ris_m, Pn);
 	return hipGetLastError();
 }
 
-// the variants of launch_nee_shade, per place of the geometry
-template <int MODE, bool SPDF, bool RIS, bool PUN>
-static hipError_t launch_nee_fused_mode(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeFusedBuffers& B, size_t lds_bytes, int grid,
-                                        hipStream_t stream) {
-#define PTX_NEE_FUSED_LAUNCH(...) launch_nee_fused_variant<MODE, SPDF, RIS, PUN, __VA_ARGS__>(S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream)
-	const bool sun = S.sun.present != 0;
-	if (Ev.row_cdf) {   // a table means a map, and a map means the TEX variants
-		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
-		if (S.any_alpha) return sun ? PTX_NEE_FUSED_LAUNCH(true, true, true, true) : PTX_NEE_FUSED_LAUNCH(true, true, false, true);
-		return sun ? PTX_NEE_FUSED_LAUNCH(true, false, true, true) : PTX_NEE_FUSED_LAUNCH(true, false, false, true);
-	}
-	if (S.any_texture) {
-		if (S.any_alpha) return sun ? PTX_NEE_FUSED_LAUNCH(true, true, true) : PTX_NEE_FUSED_LAUNCH(true, true, false);
-		return sun ? PTX_NEE_FUSED_LAUNCH(true, false, true) : PTX_NEE_FUSED_LAUNCH(true, false, false);
-	}
-	if (S.any_alpha) return sun ? PTX_NEE_FUSED_LAUNCH(false, true, true) : PTX_NEE_FUSED_LAUNCH(false, true, false);
-	return sun ? PTX_NEE_FUSED_LAUNCH(false, false, true) : PTX_NEE_FUSED_LAUNCH(false, false, false);
-#undef PTX_NEE_FUSED_LAUNCH
+// Declared for every part, defined by the one compilation of that part: the linker puts the eight together. The definition is an explicit
+// specialisation and the template has no body: with one, part 0 naming launch_nee_fused_part<5> would instantiate part 5's kernels itself.
+template <uint32_t PART>
+hipError_t launch_nee_fused_part(uint32_t V, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeFusedBuffers& B, int mode,
+                                 size_t lds_bytes, int grid, hipStream_t stream);
+template <>
+hipError_t launch_nee_fused_part<PTX_NEE_PART>(uint32_t V, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeFusedBuffers& B,
+                                               int mode, size_t lds_bytes, int grid, hipStream_t stream) {
+	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS>(V, S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream);
+	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID>(V, S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream);
+	return launch_nee_fused_mode<MODE_GLOBAL>(V, S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream);
 }
 
-// This file is compiled eight times, so that the eight parts of the variants build side by side: as itself (the unflagged variants and
-// launch_nee_fused) and through nee_fused_{spdf, ris, ris_spdf, pun, pun_spdf, pun_ris, pun_ris_spdf}.hip, which define PTX_NEE_FUSED_SPDF_TU
-// (the variants of PTX_NEE_SAMPLER_PDF), PTX_NEE_FUSED_RIS_TU (those of PTX_NEE_CANDIDATES) and PTX_NEE_FUSED_PUN_TU (those for scenes with
-// punctual lights) in every combination. Each compilation defines launch_nee_fused_part_<spdf><ris><pun> for its own three digits, 0 or 1
-// each: launch_nee_fused_part_101 is the SPDF + PUN part. The macros below only paste that name together and spell the argument list once;
-// a further dimension is one more PTX_TU_* digit, eight more declarations and one more level in launch_nee_fused's choice.
-#ifdef PTX_NEE_FUSED_SPDF_TU
-#define PTX_TU_SPDF 1
-#else
-#define PTX_TU_SPDF 0
-#endif
-#ifdef PTX_NEE_FUSED_RIS_TU
-#define PTX_TU_RIS 1
-#else
-#define PTX_TU_RIS 0
-#endif
-#ifdef PTX_NEE_FUSED_PUN_TU
-#define PTX_TU_PUN 1
-#else
-#define PTX_TU_PUN 0
-#endif
-#define PTX_NEE_FUSED_PART_(s, r, p) launch_nee_fused_part_##s##r##p
-#define PTX_NEE_FUSED_PART(s, r, p) PTX_NEE_FUSED_PART_(s, r, p)
-#define PTX_NEE_FUSED_PART_ARGS                                                                                                                                                        \
-	const DevScene &S, const RenderParams &P, const NeeLights &Lt, const NeeEnv &Ev, const NeePunctual &Pn, uint32_t ris_m, const NeeFusedBuffers &B, int mode, size_t lds_bytes, int grid, \
-		hipStream_t stream
-hipError_t launch_nee_fused_part_000(PTX_NEE_FUSED_PART_ARGS);
-hipError_t launch_nee_fused_part_100(PTX_NEE_FUSED_PART_ARGS);
-hipError_t launch_nee_fused_part_010(PTX_NEE_FUSED_PART_ARGS);
-hipError_t launch_nee_fused_part_110(PTX_NEE_FUSED_PART_ARGS);
-hipError_t launch_nee_fused_part_001(PTX_NEE_FUSED_PART_ARGS);
-hipError_t launch_nee_fused_part_101(PTX_NEE_FUSED_PART_ARGS);
-hipError_t launch_nee_fused_part_011(PTX_NEE_FUSED_PART_ARGS);
-hipError_t launch_nee_fused_part_111(PTX_NEE_FUSED_PART_ARGS);
-hipError_t PTX_NEE_FUSED_PART(PTX_TU_SPDF, PTX_TU_RIS, PTX_TU_PUN)(PTX_NEE_FUSED_PART_ARGS) {
-	constexpr bool SPDF = PTX_TU_SPDF != 0, RIS = PTX_TU_RIS != 0, PUN = PTX_TU_PUN != 0;
-	if (mode == MODE_LDS) return launch_nee_fused_mode<MODE_LDS, SPDF, RIS, PUN>(S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream);
-	if (mode == MODE_HYBRID) return launch_nee_fused_mode<MODE_HYBRID, SPDF, RIS, PUN>(S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream);
-	return launch_nee_fused_mode<MODE_GLOBAL, SPDF, RIS, PUN>(S, P, Lt, Ev, Pn, ris_m, B, lds_bytes, grid, stream);
+#if PTX_NEE_PART == 0
+template <size_t... PART>
+static hipError_t launch_nee_fused_in_part(std::index_sequence<PART...>, uint32_t V, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m,
+                                           const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream) {
+	static constexpr decltype(&launch_nee_fused_part<0>) parts[] = {&launch_nee_fused_part<PART>...};
+	return parts[V >> kNeePartShift](V, S, P, Lt, Ev, Pn, ris_m, B, mode, lds_bytes, grid, stream);
 }
 
-#if !PTX_TU_SPDF && !PTX_TU_RIS && !PTX_TU_PUN
-// sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF; candidates > 1: the RIS variants with M = candidates (PTX_NEE_CANDIDATES); Pn.n != 0: the PUN variants
+// the variant: nee_select_variant (nee_core.hpp), as for launch_nee_shade
 hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeFusedBuffers& B,
                             int mode, size_t lds_bytes, int grid, hipStream_t stream) {
-	const uint32_t ris_m = candidates > 1 ? candidates : 1u;
-	const auto part = Pn.n != 0 ? (candidates > 1 ? (sampler_pdf ? launch_nee_fused_part_111 : launch_nee_fused_part_011) : (sampler_pdf ? launch_nee_fused_part_101 : launch_nee_fused_part_001))
-	                            : (candidates > 1 ? (sampler_pdf ? launch_nee_fused_part_110 : launch_nee_fused_part_010) : (sampler_pdf ? launch_nee_fused_part_100 : launch_nee_fused_part_000));
-	return part(S, P, Lt, Ev, Pn, ris_m, B, mode, lds_bytes, grid, stream);
+	uint32_t V, ris_m;
+	const hipError_t e = nee_select_variant(S, Ev, Pn, sampler_pdf, candidates, V, ris_m);
+	if (e != hipSuccess) return e;
+	return launch_nee_fused_in_part(std::make_index_sequence<kNeeParts>{}, V, S, P, Lt, Ev, Pn, ris_m, B, mode, lds_bytes, grid, stream);
 }
 #endif
 

@@ -1,5 +1,5 @@
 """Point and spot lights in ptx_render_nee on the MI355X (include/ptx.h: PUNCTUAL LIGHTS; csrc/nee_core.hpp nee_candidate's PUN branch,
-nee_punctual.hip, nee_fused_pun*.hip). The yardstick is tests/_nee_punctual_restatement.py; the CPU side of it is tests/test_nee_punctual.py.
+the PUN parts of nee.hip and nee_fused.hip). The yardstick is tests/_nee_punctual_restatement.py; the CPU side of it is tests/test_nee_punctual.py.
 
 Scenes: procedural.lamp_scene (a floor, a blocker, optionally an emitter, lamps above) and the material chart with pass-through patches and a
 sun under six lamps; the golden sky as the map. Bars are the project's: the per-sample bar of test_nee.py / test_nee_lights.py, bitwise
