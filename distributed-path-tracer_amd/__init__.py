@@ -234,6 +234,7 @@ def lib():
         L.ptx_tonemap_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ptx_pbr_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_exact_math_check.argtypes = [C.c_void_p, C.c_void_p]
+        L.ptx_shade_consts_check.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_leaf_intersect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.ptx_camera_rays_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_material_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -316,6 +317,15 @@ class Context:
         out = np.zeros(len(self.EXACT_MATH_FORMS), np.uint64)
         _check(lib().ptx_exact_math_check(self.h, out.ctypes.data))
         return {n: int(v) for n, v in zip(self.EXACT_MATH_FORMS, out)}
+
+    def shade_consts_check(self, materials):
+        """ptx_shade_consts_check: materials [n,9] float32 (roughness, metallic, ior, albedo rgb, emissive rgb). The per-material constants
+        the scene builder puts into a shade record for each row against the path vertex's own expressions evaluated on the device.
+        Returns the number of words whose bits differ (NaN equals NaN)."""
+        a = np.ascontiguousarray(materials, np.float32).reshape(-1, 9)
+        out = np.zeros(1, np.uint64)
+        _check(lib().ptx_shade_consts_check(self.h, a.ctypes.data, len(a), out.ctypes.data))
+        return int(out[0])
 
     def leaf_intersect(self, corners, rays, refs=None, leaf_ordered=False):
         """ptx_leaf_intersect_batch: the fused kernels' leaf loop on one leaf holding the triangles corners [n_tri,9] (a, b, c), tested in

@@ -329,6 +329,34 @@ int ptx_exact_math_check(ptx_ctx* c, uint64_t* mismatches) {
 	return PTX_OK;
 }
 
+int ptx_shade_consts_check(ptx_ctx* c, const float* materials, size_t n, uint64_t* mismatches) {
+	if (!c) return set_err(PTX_ERR_NO_DEVICE, "ptx_shade_consts_check: no GPU context (no CPU path exists)");
+	if (!mismatches || (n && !materials)) return set_err(PTX_ERR_INVALID, "ptx_shade_consts_check: NULL argument");
+	if (n > (size_t)1 << 24) return set_err(PTX_ERR_INVALID, "ptx_shade_consts_check: batch too large");
+	if (n && is_device_ptr(materials)) return set_err(PTX_ERR_INVALID, "ptx_shade_consts_check: host memory only");
+	*mismatches = 0;
+	if (n == 0) return PTX_OK;
+	std::vector<ShadeRec> recs(n, ShadeRec{});
+	for (size_t k = 0; k < n; k++) {
+		recs[k].mat.roughness = materials[9 * k];
+		recs[k].mat.ior = materials[9 * k + 2];
+		fill_shade_consts(recs[k]);
+	}
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t rec_off = pad16(n * 36);
+	HIP_TRY(c->stage_a.ensure(rec_off + n * sizeof(ShadeRec)));
+	HIP_TRY(c->stage_b.ensure(8));
+	char* in = (char*)c->stage_a.p;
+	HIP_TRY(hipMemcpyAsync(in, materials, n * 36, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(in + rec_off, recs.data(), n * sizeof(ShadeRec), hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemsetAsync(c->stage_b.p, 0, 8, c->stream));
+	HIP_TRY(launch_shade_consts_check((const float*)in, (const ShadeRec*)(in + rec_off), n, (unsigned long long*)c->stage_b.p, c->stream));
+	HIP_TRY(hipMemcpyAsync(mismatches, c->stage_b.p, 8, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));   // the staged records are locals
+	return PTX_OK;
+}
+
 int ptx_camera_rays_batch(ptx_scene* sc, const float* ndc_ratio, size_t n, float* rays) {
 	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_camera_rays_batch: scene is NULL");
 	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_camera_rays_batch: scene was created without a GPU context (no CPU path exists)");

@@ -609,13 +609,14 @@ DEV V3 rand_cone_vec(float rnd, float cos_theta, V3 normal) {
 	return {tangent.x * cone.x + binormal.x * cone.y + normal.x * cone.z, tangent.y * cone.x + binormal.y * cone.y + normal.y * cone.z,
 	        tangent.z * cone.x + binormal.z * cone.y + normal.z * cone.z};
 }
-DEV float fresnel_schlick(V3 outcoming, V3 incoming, float ior) {  // core/pbr.cpp:13-25
+// The functions of the roughness and of the ior take what depends on the material alone as RoughConsts / f0sq (flat_scene.hpp): computed
+// here from the value by the overload below, or read from the surface's shade record by the untextured shade_vertex.
+DEV float fresnel_schlick_f0(V3 outcoming, V3 incoming, float f0sq) {  // core/pbr.cpp:13-25
 	V3 halfway = normalize(outcoming + incoming);
 	float cos_theta = dot(outcoming, halfway);
-	float f0 = (ior - 1) / (ior + 1);
-	f0 *= f0;
-	return lerpf(f0, 1, pow5(1 - cos_theta));
+	return lerpf(f0sq, 1, pow5(1 - cos_theta));
 }
+DEV float fresnel_schlick(V3 outcoming, V3 incoming, float ior) { return fresnel_schlick_f0(outcoming, incoming, fresnel_f0sq(ior)); }
 // pbr::importance_diffuse (core/pbr.cpp:71-77) and pbr::importance_specular (:79-91) differ in the cone angle they hand to
 // rand_cone_vec and in the final reflection; the cone construction itself (sin / cos of the azimuth, tangent frame) is the
 // same code — run it once for the whole wave instead of once per lobe under complementary lane masks.
@@ -637,42 +638,40 @@ DEV float cos_polar(float t) {
 	}
 	return cosf(t);
 }
-DEV V3 importance_sample(bool specular, float u1, float u2, V3 normal, V3 outcoming, float roughness) {
+DEV V3 importance_sample(bool specular, float u1, float u2, V3 normal, V3 outcoming, const RoughConsts& rc) {
 	float cos_theta;
 	if (specular) {
-		roughness *= roughness;
-		roughness *= roughness;
-		cos_theta = sqrt_exact((1 - u1) / (1 + (roughness - 1) * u1));
+		cos_theta = sqrt_exact((1 - u1) / (1 + rc.r4m1 * u1));
 	} else {
 		cos_theta = cos_polar(acosf(2 * u1 - 1) * 0.5F);
 	}
 	const V3 h = rand_cone_vec(u2, cos_theta, normal);
 	return specular ? reflect3(-outcoming, h) : h;
 }
+DEV V3 importance_sample(bool specular, float u1, float u2, V3 normal, V3 outcoming, float roughness) {
+	return importance_sample(specular, u1, u2, normal, outcoming, rough_consts(roughness));
+}
 DEV float smith_g1(V3 n, V3 l, float k) { float c = dot(n, l); return c / pmax(lerpf(k, 1, c), kEps); }  // pbr.cpp:95-102
 DEV float pdf_diffuse(V3 n, V3 i) { return (float)((double)dot(n, i) / kPi); }                           // pbr.cpp:118-123
-DEV float pdf_specular(V3 n, V3 o, V3 i, float roughness) {  // core/pbr.cpp:172-184 (+ distribution_ggx :125-140, geometry_smith :104-114)
-	float r4 = roughness * roughness;
-	r4 *= r4;
+DEV float pdf_specular(V3 n, V3 o, V3 i, const RoughConsts& rc) {  // core/pbr.cpp:172-184 (+ distribution_ggx :125-140, geometry_smith :104-114)
 	V3 halfway = normalize(o + i);
 	float cos_phi = dot(n, halfway);
-	float denom = 1 + (r4 - 1) * (cos_phi * cos_phi);
+	float denom = 1 + rc.r4m1 * (cos_phi * cos_phi);
 	float cos_theta = dot(n, i);
 	double dd = kPi * (double)denom * (double)denom;
 	double mxd = (double)kEps > dd ? (double)kEps : dd;
-	float dist = (float)((double)(cos_theta * r4) / mxd);
-	float r = roughness + 1;
-	float k = (r * r) / 8;
-	float geo = smith_g1(n, o, k) * smith_g1(n, i, k);
+	float dist = (float)((double)(cos_theta * rc.r4) / mxd);
+	float geo = smith_g1(n, o, rc.smith_k) * smith_g1(n, i, rc.smith_k);
 	float ndo = dot(n, o), ndi = dot(n, i);
 	return (dist * geo) / pmax(4 * ndo * ndi, kEps);
 }
+DEV float pdf_specular(V3 n, V3 o, V3 i, float roughness) { return pdf_specular(n, o, i, rough_consts(roughness)); }
 // BRDF / PDF combination, inline in renderer::trace (core/renderer.cpp:521-556 and :579-606).
 // Returns brdf (rgb); pdf_mix = lerp(pdf_d, pdf_s, specular_probability).
-DEV V3 eval_brdf(V3 n, V3 o, V3 i, V3 albedo, float roughness, float metallic, float spec_prob, float& pdf_mix) {
+DEV V3 eval_brdf(V3 n, V3 o, V3 i, V3 albedo, const RoughConsts& rc, float metallic, float spec_prob, float& pdf_mix) {
 	float diffuse_pdf = pdf_diffuse(n, i);
 	V3 diffuse_brdf = diffuse_pdf * albedo;
-	float specular_pdf = pdf_specular(n, o, i, roughness);
+	float specular_pdf = pdf_specular(n, o, i, rc);
 	V3 fr = lerp3(mk(0.04F, 0.04F, 0.04F), albedo, metallic);
 	V3 halfway = normalize(o + i);
 	float cos_theta = dot(o, halfway);
@@ -680,6 +679,9 @@ DEV V3 eval_brdf(V3 n, V3 o, V3 i, V3 albedo, float roughness, float metallic, f
 	diffuse_brdf = lerp3(diffuse_brdf, mk(0, 0, 0), metallic);
 	pdf_mix = lerpf(diffuse_pdf, specular_pdf, spec_prob);
 	return lerp3(diffuse_brdf, mk(specular_pdf, specular_pdf, specular_pdf), fr);
+}
+DEV V3 eval_brdf(V3 n, V3 o, V3 i, V3 albedo, float roughness, float metallic, float spec_prob, float& pdf_mix) {
+	return eval_brdf(n, o, i, albedo, rough_consts(roughness), metallic, spec_prob, pdf_mix);
 }
 
 // ------------------------------------------------------------------------------------ RNG
@@ -827,6 +829,11 @@ struct ShadowReq {
 // LAST: what the caller knows about `depth + 1 == P.bounces`. The fused kernel without ALPHA knows it per sweep and compiles one loop
 // for each answer; everyone else leaves the test to the vertex.
 enum : int { LAST_NEVER = 0, LAST_ALWAYS = 1, LAST_BY_DEPTH = 2 };
+#ifndef PTX_NO_SHADE_CONSTS
+constexpr bool kShadeConsts = true;
+#else
+constexpr bool kShadeConsts = false;   // the A/B build: every vertex computes the constants, as before they were in the record
+#endif
 template <bool SUN, bool ALPHA, bool TEX, bool WORKER, int LAST = LAST_BY_DEPTH>
 DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParams& P, uint32_t pixel, uint32_t sample,
                      uint32_t& depth, uint32_t& pass, SceneHit h, V3& o, V3& d, V3& T, V3& L, ShadowReq& rq PROF_ARG) {
@@ -848,7 +855,6 @@ DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParam
 	hit_attributes(S, R, h.tri, h.b1, h.b2, sf);
 	const MaterialRec& mt = R.mat;
 	const MatEval me = material_eval<TEX>(S, mt, sf.u, sf.v);   // renderer.cpp:458-462
-	float roughness = me.roughness;
 	// LIB: the vertex at depth == bounces - 1 is the path's last one: the ray it would sample is traced by trace(0, ..), which is black
 	// (renderer.cpp:438-439).
 	const bool last = !WORKER && (LAST == LAST_ALWAYS || (LAST == LAST_BY_DEPTH && depth + 1 == P.bounces));
@@ -867,10 +873,14 @@ DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParam
 	}
 	const V3 normal = shading_normal(sf, me.normal_ts), outcoming = -d;
 	if (dot(normal, outcoming) <= 0) { PROF(17); return V_DEAD; }            // renderer.cpp:478-479: black, path ends
-	roughness = pmax(roughness, 0.05F);
+	// Without textures the roughness is the material's factor, and what the vertex needs of it and of the ior was computed by the scene
+	// builder with these expressions (flat_scene.hpp, fill_shade_consts). A texture scales the roughness per hit: TEX computes them here.
+	constexpr bool from_record = kShadeConsts && !TEX;
+	const RoughConsts rc = from_record ? R.rc : rough_consts(clamp_roughness(me.roughness));
+	const float f0sq = from_record ? mt.f0sq : fresnel_f0sq(mt.ior);
 	float spec_prob = 0;   // read by the sun's eval_brdf and by the sampling below: a last vertex without a sun needs neither
 	if (!last || (SUN && S.sun.present)) {
-		spec_prob = fresnel_schlick(outcoming, reflect3(-outcoming, normal), mt.ior);
+		spec_prob = fresnel_schlick_f0(outcoming, reflect3(-outcoming, normal), f0sq);
 		spec_prob = pmax(spec_prob, me.metallic);
 	}
 
@@ -896,7 +906,7 @@ DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParam
 				return V_PENDING;
 			}
 			float pdf_unused;
-			const V3 brdf = eval_brdf(normal, outcoming, din, me.albedo, roughness, me.metallic, spec_prob, pdf_unused);
+			const V3 brdf = eval_brdf(normal, outcoming, din, me.albedo, rc, me.metallic, spec_prob, pdf_unused);
 			const V3 e = mk(S.sun.energy[0], S.sun.energy[1], S.sun.energy[2]);
 			const float pdf = lerpf(1.0f, 1.0f, spec_prob);
 			const V3 v = brdf * e / pmax(pdf, kEps);
@@ -914,10 +924,10 @@ DEV int shade_vertex(const DevScene& S, const ShadeRec* shade, const RenderParam
 		if (last) { PROF(18); return V_DEAD; }
 	}
 	PROF(19);
-	const V3 inc = importance_sample(rnd.y < spec_prob, rnd.z, rnd.w, normal, outcoming, roughness);
+	const V3 inc = importance_sample(rnd.y < spec_prob, rnd.z, rnd.w, normal, outcoming, rc);
 	if (!(dot(normal, inc) > 0)) return V_DEAD;                              // renderer.cpp:578 / shading_worker.cpp:154,196-199
 	float pdf;
-	const V3 brdf = eval_brdf(normal, outcoming, inc, me.albedo, roughness, me.metallic, spec_prob, pdf);
+	const V3 brdf = eval_brdf(normal, outcoming, inc, me.albedo, rc, me.metallic, spec_prob, pdf);
 	const V3 q = brdf / pmax(pdf, kEps);   // brdf / max(pdf, eps), component by component
 	if constexpr (!WORKER) {
 		T = T * mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));                         // renderer.cpp:617-620
@@ -987,13 +997,55 @@ extern __shared__ __attribute__((aligned(16))) unsigned char g_smem[];
 // 16 K waves have pushed ~1.6 GB through the caches: the accesses carry the non-temporal hint, so that they do
 // not displace the scene's nodes and triangle records from L2 / Infinity Cache. Same-box A/B: +1.5 % on Cornell 1080p, neutral to
 // +2 % on the large-mesh scenes, images bit-identical (profiles/round2_ab_nt_streams.txt); -DPTX_PLAIN_STREAMS builds the plain form.
-#ifndef PTX_PLAIN_STREAMS
+//
+// Addressing: every array of a wave lives in the wave's one area, so an element is the area's base — wave-uniform, an SGPR pair — plus a
+// 32-bit byte offset (kStreamAreaMaxBytes fits 32 bits: kernels.hpp). `base + zext(offset)` is what the compiler selects the scalar-base
+// form of global_load / global_store for: one 32-bit VGPR per address instead of a 64-bit pair per array, and no 64-bit lane arithmetic.
+// All offset arithmetic is uint32_t on purpose. -DPTX_PTR_STREAMS keeps the earlier form, a 64-bit pointer per array and lane, for the A/B.
 typedef float f4n __attribute__((ext_vector_type(4)));
 typedef float f2n __attribute__((ext_vector_type(2)));
+#ifndef PTX_PLAIN_STREAMS
+DEV float4 stream_load4(const float4* p) { const f4n v = __builtin_nontemporal_load(reinterpret_cast<const f4n*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
+DEV float2 stream_load2(const float2* p) { const f2n v = __builtin_nontemporal_load(reinterpret_cast<const f2n*>(p)); return make_float2(v.x, v.y); }
+DEV void stream_store4(float4* p, float4 v) { const f4n w = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(w, reinterpret_cast<f4n*>(p)); }
+DEV void stream_store2(float2* p, float2 v) { const f2n w = {v.x, v.y}; __builtin_nontemporal_store(w, reinterpret_cast<f2n*>(p)); }
+#else
+DEV float4 stream_load4(const float4* p) { return *p; }
+DEV float2 stream_load2(const float2* p) { return *p; }
+DEV void stream_store4(float4* p, float4 v) { *p = v; }
+DEV void stream_store2(float2* p, float2 v) { *p = v; }
+#endif
+#ifndef PTX_PTR_STREAMS
+struct Q4Ref {
+	char* b; uint32_t o;
+	DEV operator float4() const { return stream_load4(reinterpret_cast<const float4*>(b + o)); }
+	DEV void operator=(float4 v) const { stream_store4(reinterpret_cast<float4*>(b + o), v); }
+	DEV void operator=(const Q4Ref& r) const { *this = (float4)r; }
+};
+struct Q4 {
+	char* b; uint32_t o;   // the area's base (uniform), the array's first byte in it
+	DEV Q4Ref operator[](uint32_t i) const { return {b, o + i * 16u}; }
+	DEV Q4 operator+(uint32_t k) const { return {b, o + k * 16u}; }
+};
+struct Q2Ref {
+	char* b; uint32_t o;
+	DEV operator float2() const { return stream_load2(reinterpret_cast<const float2*>(b + o)); }
+	DEV void operator=(float2 v) const { stream_store2(reinterpret_cast<float2*>(b + o), v); }
+};
+struct Q2 {
+	char* b; uint32_t o;
+	DEV Q2Ref operator[](uint32_t i) const { return {b, o + i * 8u}; }
+};
+DEV Q4 stream_area(float4* area) { return {reinterpret_cast<char*>(area), 0u}; }
+DEV Q2 as_q2(Q4 q) { return {q.b, q.o}; }
+// one 32-bit word of an element, for the plain read-modify-writes of a single field
+DEV float* word(Q4 q, uint32_t i, uint32_t w) { return reinterpret_cast<float*>(q.b + (q.o + i * 16u + w * 4u)); }
+DEV float* word(Q2 q, uint32_t i, uint32_t w) { return reinterpret_cast<float*>(q.b + (q.o + i * 8u + w * 4u)); }
+#else
 struct Q4Ref {
 	float4* p;
-	DEV operator float4() const { const f4n v = __builtin_nontemporal_load(reinterpret_cast<const f4n*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
-	DEV void operator=(float4 v) const { const f4n w = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(w, reinterpret_cast<f4n*>(p)); }
+	DEV operator float4() const { return stream_load4(p); }
+	DEV void operator=(float4 v) const { stream_store4(p, v); }
 	DEV void operator=(const Q4Ref& o) const { *this = (float4)o; }
 };
 struct Q4 {
@@ -1003,20 +1055,17 @@ struct Q4 {
 };
 struct Q2Ref {
 	float2* p;
-	DEV operator float2() const { const f2n v = __builtin_nontemporal_load(reinterpret_cast<const f2n*>(p)); return make_float2(v.x, v.y); }
-	DEV void operator=(float2 v) const { const f2n w = {v.x, v.y}; __builtin_nontemporal_store(w, reinterpret_cast<f2n*>(p)); }
+	DEV operator float2() const { return stream_load2(p); }
+	DEV void operator=(float2 v) const { stream_store2(p, v); }
 };
 struct Q2 {
 	float2* p;
 	DEV Q2Ref operator[](size_t i) const { return {p + i}; }
 };
-DEV float4* raw(Q4 q) { return q.p; }
-DEV float2* raw(Q2 q) { return q.p; }
-#else
-typedef float4* Q4;
-typedef float2* Q2;
-DEV float4* raw(Q4 q) { return q; }
-DEV float2* raw(Q2 q) { return q; }
+DEV Q4 stream_area(float4* area) { return {area}; }
+DEV Q2 as_q2(Q4 q) { return {reinterpret_cast<float2*>(q.p)}; }
+DEV float* word(Q4 q, uint32_t i, uint32_t w) { return reinterpret_cast<float*>(q.p + i) + w; }
+DEV float* word(Q2 q, uint32_t i, uint32_t w) { return reinterpret_cast<float*>(q.p + i) + w; }
 #endif
 
 // ------------------------------------------------------------------------------------ batch intersect outputs

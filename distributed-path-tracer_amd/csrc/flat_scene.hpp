@@ -82,13 +82,41 @@ template <class Rec> inline void interleave_boxes(Rec& r) {
 	for (int k = 0; k < 3; k++) { r.box[2 * k] = r.bmin[k]; r.box[2 * k + 1] = r.bmax[k]; r.pbox[2 * k] = r.pbmin[k]; r.pbox[2 * k + 1] = r.pbmax[k]; }
 }
 
+// ---- what a path vertex computes from the material's roughness and ior alone (core/pbr.cpp:13-25, 79-91, 104-114, 125-140, 172-184).
+// One definition for both sides: the kernels evaluate these per vertex where a texture can scale the roughness, and the scene builder
+// evaluates them once per surface into the shade record, which the untextured kernels read instead (-DPTX_NO_SHADE_CONSTS: they
+// evaluate them too). IEEE binary32, one rounding per operation on the host as on the device (-ffp-contract=off), so the record
+// holds the bits the vertex would compute.
+#ifdef __HIP__
+#define PTX_HD __attribute__((host)) __attribute__((device))
+#else
+#define PTX_HD
+#endif
+struct RoughConsts { float r4, r4m1, smith_k; };   // roughness^4, roughness^4 - 1, (roughness + 1)^2 / 8
+PTX_HD inline float pmax_hd(float a, float b) { return b > a ? b : a; }   // math::max (NaN-asymmetric), math.inl:169: the device's pmax
+PTX_HD inline float clamp_roughness(float roughness) { return pmax_hd(roughness, 0.05F); }   // renderer.cpp:486
+PTX_HD inline RoughConsts rough_consts(float roughness) {   // of the clamped roughness
+	RoughConsts c;
+	c.r4 = roughness * roughness;
+	c.r4 *= c.r4;
+	c.r4m1 = c.r4 - 1;
+	const float r = roughness + 1;
+	c.smith_k = (r * r) / 8;
+	return c;
+}
+PTX_HD inline float fresnel_f0sq(float ior) {
+	float f0 = (ior - 1) / (ior + 1);
+	f0 *= f0;
+	return f0;
+}
+
 // ---- material factors (core/material.hpp:11-17) and texture slots ----
 struct MaterialRec {
 	float albedo[3]; float opacity;
 	float emissive[3]; float roughness;   // emissive factor; the shader multiplies the looked-up value by 10 (renderer.cpp:462)
 	float metallic; float ior; uint32_t shadow_catcher; uint32_t tex_mask;
 	int32_t tex[7];   // texture id per slot: normal, albedo, opacity, occlusion, roughness, metallic, emissive; -1 = none
-	int32_t pad;
+	float f0sq;       // fresnel_f0sq(ior)
 };
 static_assert(sizeof(MaterialRec) == 80, "MaterialRec layout");
 
@@ -105,9 +133,14 @@ struct ShadeRec {
 	float basis[9];   // model global basis, columns
 	float origin[3];
 	float nmat[9];    // transpose(inverse(basis)), columns
-	float pad[3];
+	RoughConsts rc;   // rough_consts(clamp_roughness(mat.roughness)): the factor's, valid where no texture scales it
 	MaterialRec mat;
 };
+// the constants of a surface's material, as the untextured vertex would compute them
+inline void fill_shade_consts(ShadeRec& r) {
+	r.rc = rough_consts(clamp_roughness(r.mat.roughness));
+	r.mat.f0sq = fresnel_f0sq(r.mat.ior);
+}
 static_assert(sizeof(ShadeRec) == 176 && sizeof(ShadeRec) % 16 == 0, "ShadeRec layout: staged into LDS in 16-byte units");
 
 // ---- ray space: a distinct world->local transform. Models whose entity transforms are bitwise equal

@@ -52,11 +52,16 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 	S.hot_lds = st.hot;
 	const Geoms g = st.g;
 	const uint32_t lane = threadIdx.x & 63u;
+#ifndef PTX_PTR_STREAMS
+	// threadIdx.x >> 6 is the same in all lanes of a wave, which the compiler cannot know: said here, so that the stream area's base is scalar
+	const uint32_t wave_slot = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
+#else
 	const uint32_t wave_slot = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+#endif
 	// wave-private streams: 2 ray buffers x 4 float4 arrays x kChunk entries, then 1 hit array
-	const Q4 qbase = Q4{B.queues + (size_t)wave_slot * B.queue_stride};
+	const Q4 qbase = stream_area(B.queues + (size_t)wave_slot * B.queue_stride);
 	const Q4 hbuf = qbase + 2u * 4u * kChunk;
-	const Q2 hdist = Q2{reinterpret_cast<float2*>(raw(hbuf) + kChunk)};               // [kChunk] (world distance, local t) of the current best hit (deferral)
+	const Q2 hdist = as_q2(hbuf + kChunk);                                      // [kChunk] (world distance, local t) of the current best hit (deferral)
 	const Q4 sreq = hbuf + (kChunk + kChunk / 2u);                              // [3][kChunk] shadow requests: (origin, target) (dir, kind) (x, path id)
 	const Q4 lists = sreq + 3u * kChunk;                                      // [units][2][kListCap]: (local origin, ray index), (local dir, -); units = models, or surfaces (SURF)
 	const Spill spill{B.spill + (size_t)wave_slot * (kSpillStack * 64) + lane};
@@ -99,8 +104,8 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 		// One step = every live path of the chunk advances by one stream entry: a scatter (depth + 1) or, with ALPHA, a
 		// pass-through (same depth, pass + 1). Without pass-through all paths of a step have depth == step.
 		for (uint32_t step = 0; P.bounces > 0 && n_in > 0; step++) {
-			const Q4 qin = qbase + (size_t)(step & 1u) * (4u * kChunk);
-			const Q4 qout = qbase + (size_t)((step + 1u) & 1u) * (4u * kChunk);
+			const Q4 qin = qbase + (step & 1u) * (4u * kChunk);
+			const Q4 qout = qbase + ((step + 1u) & 1u) * (4u * kChunk);
 
 			// ---------------- EXTEND
 			// lists live in the unused part of the wave's stream area: hdist (kChunk words) + n_models lists
@@ -184,7 +189,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 								if (ent) {
 									PROF(14);
 									const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
-									const Q4 L0 = lists + (size_t)u * 2u * kListCap;
+									const Q4 L0 = lists + (uint32_t)u * 2u * kListCap;
 									L0[len + r] = make_float4(lo.x, lo.y, lo.z, __uint_as_float(i));
 									L0[kListCap + len + r] = make_float4(ld.x, ld.y, ld.z, 0.f);
 								}
@@ -229,7 +234,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 								PROF(14);
 								const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
 								// the deferred sweep gets the LOCAL ray: no gather of the stream entry, no second transform
-								const Q4 L0 = lists + (size_t)m * 2u * kListCap;
+								const Q4 L0 = lists + (uint32_t)m * 2u * kListCap;
 								L0[len + r] = make_float4(lo.x, lo.y, lo.z, __uint_as_float(i));
 								L0[kListCap + len + r] = make_float4(ld.x, ld.y, ld.z, 0.f);
 							}
@@ -237,7 +242,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 						}
 					}
 				}
-				if (active) { hbuf[i] = make_float4(__int_as_float(h.surface), __uint_as_float(h.tri), h.b1, h.b2); if (defer && !SURF) raw(hdist)[i].x = h.dist; }
+				if (active) { hbuf[i] = make_float4(__int_as_float(h.surface), __uint_as_float(h.tri), h.b1, h.b2); if (defer && !SURF) *word(hdist, i, 0) = h.dist; }
 			}
 #ifdef PTX_CLK
 			CLK_WAIT();
@@ -255,7 +260,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 						const SurfaceRec& sf = S.surfaces[u];
 						const int m = (int)sf.model;
 						const ModelRec& M = S.models[m];
-						const Q4 L0 = lists + (size_t)u * 2u * kListCap;
+						const Q4 L0 = lists + (uint32_t)u * 2u * kListCap;
 						for (uint32_t base = 0; base < len; base += 64) {
 							if (base + lane < len) {
 								PROF(8);
@@ -286,14 +291,14 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 					const uint32_t len = __builtin_amdgcn_readlane(list_len, m);
 					if (len == 0) continue;
 					const ModelRec& M = S.models[m];
-					const Q4 L0 = lists + (size_t)m * 2u * kListCap;
+					const Q4 L0 = lists + (uint32_t)m * 2u * kListCap;
 					for (uint32_t base = 0; base < len; base += 64) {
 						if (base + lane < len) {
 							PROF(8);
 							const float4 e0 = L0[base + lane], e1 = L0[kListCap + base + lane];
 							const uint32_t i = __float_as_uint(e0.w);
-							const float bd = raw(hdist)[i].x;                     // current best of this ray: issued before the traversal
-							const int bs = __float_as_int(raw(hbuf)[i].x);
+							const float bd = *word(hdist, i, 0);                    // current best of this ray: issued before the traversal
+							const int bs = __float_as_int(*word(hbuf, i, 0));
 							const V3 lo = mk(e0.x, e0.y, e0.z), ld = mk(e1.x, e1.y, e1.z);
 							const V3 inv = mk(1.0f / ld.x, 1.0f / ld.y, 1.0f / ld.z);
 							float wd, b1, b2; int surf; uint32_t tri;
@@ -301,7 +306,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 							    model_traverse<MODE, 10>(S, g, M, lo, ld, inv, wd, surf, tri, b1, b2, spill PROF_PASS) &&
 							    (wd < bd || !(bd >= 0) || (wd == bd && surf < bs))) {
 								hbuf[i] = make_float4(__int_as_float(surf), __uint_as_float(tri), b1, b2);
-								raw(hdist)[i].x = wd;
+								*word(hdist, i, 0) = wd;
 							}
 						}
 					}
@@ -337,7 +342,14 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 					rq.kind = REQ_NONE;
 					if (active) {
 						PROF(9);
-						const float4 q0 = qin[i], q1 = qin[kChunk + i], q2 = qin[2 * kChunk + i], q3 = qin[3 * kChunk + i], hq = hbuf[i];
+						float4 q0 = qin[i], q1 = qin[kChunk + i], q2 = qin[2 * kChunk + i], q3 = qin[3 * kChunk + i], hq = hbuf[i];
+						// consumed where they are loaded, as in EXTEND: a load left pending on some path out of this block (a miss reads no hit
+						// words, a dead path no path state) puts s_waitcnt vmcnt(0) at the head of the loop, in front of the defaults that share its
+						// registers — where it drains the previous wave-iteration's stores before this one's loads are issued
+#ifndef PTX_PTR_STREAMS
+						asm volatile("" : "+v"(q0.x), "+v"(q0.y), "+v"(q0.z), "+v"(q0.w), "+v"(q1.x), "+v"(q1.y), "+v"(q1.z), "+v"(q1.w), "+v"(q2.x), "+v"(q2.y),
+						                  "+v"(q2.z), "+v"(q2.w), "+v"(q3.x), "+v"(q3.y), "+v"(q3.z), "+v"(q3.w), "+v"(hq.x), "+v"(hq.y), "+v"(hq.z), "+v"(hq.w));
+#endif
 #ifdef PTX_CLK
 						{ CLK_T0(); CLK_WAIT(); CLK_T1(5); }
 						{   // the hit record's nine 16-byte pieces, fetched here so that the wait for them has a region of its own (shade_vertex then finds them in L1)
@@ -451,7 +463,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 									const uint32_t len = __builtin_amdgcn_readlane(list_len, u);
 									if (ent) {
 										const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
-										const Q4 L0 = lists + (size_t)u * 2u * kListCap;
+										const Q4 L0 = lists + (uint32_t)u * 2u * kListCap;
 										L0[len + r] = make_float4(lo.x, lo.y, lo.z, __uint_as_float(j));
 										L0[kListCap + len + r] = make_float4(ld.x, ld.y, ld.z, 0.f);
 									}
@@ -459,7 +471,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 								}
 							}
 						}
-						if (active && occ) { uint32_t* kw = reinterpret_cast<uint32_t*>(raw(sreq) + kChunk + j) + 3; *kw = *kw | kOccluded; }
+						if (active && occ) { uint32_t* kw = reinterpret_cast<uint32_t*>(word(sreq + kChunk, j, 3)); *kw = *kw | kOccluded; }
 					}
 					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -468,12 +480,12 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 						if (len == 0) continue;
 						const SurfaceRec& sf = S.surfaces[u];
 						const ModelRec& M = S.models[sf.model];
-						const Q4 L0 = lists + (size_t)u * 2u * kListCap;
+						const Q4 L0 = lists + (uint32_t)u * 2u * kListCap;
 						for (uint32_t base = 0; base < len; base += 64) {
 							if (base + lane < len) {
 								const float4 e0 = L0[base + lane], e1 = L0[kListCap + base + lane];
 								const uint32_t j = __float_as_uint(e0.w);
-								uint32_t* kw = reinterpret_cast<uint32_t*>(raw(sreq) + kChunk + j) + 3;
+								uint32_t* kw = reinterpret_cast<uint32_t*>(word(sreq + kChunk, j, 3));
 								if (!(*kw & kOccluded)) {
 									const V3 lo = mk(e0.x, e0.y, e0.z), ld = mk(e1.x, e1.y, e1.z);
 									const V3 inv = mk(1.0f / ld.x, 1.0f / ld.y, 1.0f / ld.z);
@@ -504,7 +516,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 									B.sample_rad[id] = make_float4(v.x + x.x, v.y + x.y, v.z + x.z, v.w);
 								} else {
 									float4 q2 = qout[2 * kChunk + target];
-									float* lz = reinterpret_cast<float*>(raw(qout) + 3 * kChunk + target);
+									float* lz = word(qout + 3 * kChunk, target, 0);
 									qout[2 * kChunk + target] = make_float4(q2.x, q2.y, q2.z + x.x, q2.w + x.y);
 									*lz = *lz + x.z;
 								}
@@ -723,6 +735,20 @@ __global__ void k_exact_math_check(uint32_t form, unsigned long long* __restrict
 	if (n_bad) atomicAdd(bad + form, (unsigned long long)n_bad);
 }
 
+// ------------------------------------------------------------------------------------ shade-constants self-check
+// What the scene builder put into the shade records (flat_scene.hpp, fill_shade_consts) against the same expressions evaluated here, as
+// shade_vertex<.., TEX = true, ..> evaluates them per vertex (ptx_shade_consts_check). Row k of `in` is a material (roughness, metallic, ior,
+// albedo[3], emissive[3]) and rec[k] the record the host filled for it; the record holds constants of the roughness and the ior alone, so
+// these two are read. The number of words whose bits differ (a NaN equals any NaN) is added to *bad.
+__global__ void k_shade_consts_check(const float* __restrict__ in, const ShadeRec* __restrict__ rec, size_t n, unsigned long long* __restrict__ bad) {
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const RoughConsts rc = rough_consts(clamp_roughness(in[9 * i]));
+	const float f0sq = fresnel_f0sq(in[9 * i + 2]);
+	const uint32_t n_bad = differs(rc.r4, rec[i].rc.r4) + differs(rc.r4m1, rec[i].rc.r4m1) + differs(rc.smith_k, rec[i].rc.smith_k) + differs(f0sq, rec[i].mat.f0sq);
+	if (n_bad) atomicAdd(bad, (unsigned long long)n_bad);
+}
+
 // ------------------------------------------------------------------------------------ batch camera rays
 // scene::camera::get_ray(ndc, ratio) exactly as the integrator kernels inline it, one record per lane (ptx_camera_rays_batch)
 __global__ void k_camera_rays(DevScene S, const float* __restrict__ in, float* __restrict__ out, size_t n) {
@@ -874,6 +900,10 @@ hipError_t launch_exact_math_check(unsigned long long* bad, hipStream_t stream) 
 		if (e != hipSuccess) return e;
 	}
 	return hipSuccess;
+}
+hipError_t launch_shade_consts_check(const float* in, const ShadeRec* rec, size_t n, unsigned long long* bad, hipStream_t stream) {
+	hipLaunchKernelGGL(k_shade_consts_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, rec, n, bad);
+	return hipGetLastError();
 }
 hipError_t launch_camera_rays(const DevScene& S, const float* in, float* out, size_t n, hipStream_t stream) {
 	hipLaunchKernelGGL(k_camera_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, S, in, out, n);

@@ -28,6 +28,9 @@ constexpr uint32_t kListCap = (kChunk / 64u) * (kInlineMin - 1u) + 16u;   // ent
 constexpr int kMaxDeferModels = 64;
 constexpr uint32_t kQueueFixedFloat4 = 12u * kChunk + kChunk / 2u;
 inline uint32_t queue_float4_per_wave(uint32_t n_units) { return kQueueFixedFloat4 + (n_units <= (uint32_t)kMaxDeferModels ? n_units : 0u) * 2u * kListCap; }
+// the kernel addresses a wave's area with 32-bit byte offsets (device_core.hpp, Q4)
+constexpr uint64_t kStreamAreaMaxBytes = ((uint64_t)kQueueFixedFloat4 + (uint64_t)kMaxDeferModels * 2u * kListCap) * 16u;
+static_assert(kStreamAreaMaxBytes <= 0xFFFFFFFFull, "a wave's stream area must be addressable with a 32-bit byte offset");
 constexpr uint32_t kSpillWords = 24u * 64u;  // uint2 per wave: kSpillStack levels x 64 lanes
 
 // Device view of a FlatScene (all pointers are device pointers).
@@ -178,6 +181,7 @@ hipError_t launch_leaf_intersect(const uint2* nodes, const uint32_t* refs /* [n_
                                  const float* rays /* [n][7] */, size_t n, float* out /* [n][3] */, int32_t* tri /* [n] */, uint2* spill, int grid, hipStream_t stream);
 constexpr uint32_t kExactMathForms = 3;   // k_exact_math_check: one counter per form
 hipError_t launch_exact_math_check(unsigned long long* bad /* [kExactMathForms], device, zeroed */, hipStream_t stream);
+hipError_t launch_shade_consts_check(const float* in /* [n][9] */, const ShadeRec* rec /* [n] */, size_t n, unsigned long long* bad /* device, zeroed */, hipStream_t stream);
 hipError_t launch_camera_rays(const DevScene& S, const float* in /* [n][3]: ndc.x ndc.y ratio */, float* out /* [n][6] */, size_t n, hipStream_t stream);
 hipError_t launch_material_eval(const DevScene& S, const int32_t* surface /* [n] */, const float* uv /* [n][2] */, size_t n, float* out /* [n][12] */, hipStream_t stream);
 hipError_t launch_tonemap(const float4* accum, uint32_t n_pixels, float spp, const float* thresholds /* [256], device */, uchar4* out, hipStream_t stream);

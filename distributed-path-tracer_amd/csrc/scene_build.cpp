@@ -341,7 +341,7 @@ void finalize_scene(FlatScene& s, const float* cam, const float* sun) {
 			mr.tex[k] = s.surf_tex.size() >= 7 * (si + 1) ? s.surf_tex[7 * si + k] : -1;
 			if (mr.tex[k] >= 0) mr.tex_mask |= 1u << k;
 		}
-		mr.pad = 0;
+		mr.f0sq = fresnel_f0sq(mr.ior);
 		if (mr.tex_mask) s.any_texture = true;
 		if (mr.tex[2] >= 0) s.any_alpha = true;   // opacity comes from a texture: the pass-through branch is reachable
 		// math::is_approx(opacity, 1) (renderer.cpp:466) false, or a shadow catcher => pass-through code is needed
@@ -399,6 +399,7 @@ void finalize_scene(FlatScene& s, const float* cam, const float* sun) {
 			memcpy(r.origin, s.models[mi].origin, 12);
 			memcpy(r.nmat, s.models[mi].nmat, 36);
 			r.mat = s.materials[s.models[mi].first_surface + k];
+			fill_shade_consts(r);
 		}
 
 	memcpy(s.camera.origin, cam, 12);

@@ -716,6 +716,14 @@ int ptx_leaf_intersect_batch(ptx_ctx* ctx, const float* corners, uint32_t n_tri,
  * the sequences are exact. */
 int ptx_exact_math_check(ptx_ctx* ctx, uint64_t* mismatches);
 
+/* Self-check of the per-material constants of the shade records: the scene builder computes, once per surface, what a path vertex
+ * needs of the material's roughness and ior alone (roughness^4 of the clamped roughness, that minus 1, the Smith k, the squared
+ * Fresnel f0), and the untextured kernels read them instead of computing them. materials[n][9]: roughness, metallic, ior, albedo rgb,
+ * emissive rgb (the record holds nothing of the last seven; they are ignored). For every row the builder's own function fills a record
+ * on the host and the device evaluates the vertex's expressions; *mismatches receives the number of words whose bits differ (NaN
+ * equals NaN). Zero when the records hold what the vertex would compute. Host memory only. */
+int ptx_shade_consts_check(ptx_ctx* ctx, const float* materials, size_t n, uint64_t* mismatches);
+
 /* ---- multi-GPU fan-in ------------------------------------------------------------------------------
  * The one exchange step of the path: the sum of the per-rank accumulation buffers on rank `root`. Replaces the
  * reference's planned (never implemented) SNS/SQS result fan-in (src/models/work_info.hpp:22-23,
