@@ -29,7 +29,7 @@ NO_SUN_LIGHT = 0xFFFFFFFF  # core::renderer::no_sun_light, renderer.hpp:19
 (ARR_MODEL_XFORM, ARR_MODEL_AABB, ARR_MODEL_SURF, ARR_SURF_RANGE, ARR_MESH_AABB, ARR_VERTICES, ARR_TRIANGLES,
  ARR_MATERIALS, ARR_KD_NODES, ARR_KD_REFS, ARR_CAMERA, ARR_SUN, ARR_MODEL_NAMES, ARR_TEXTURES, ARR_TEXELS, ARR_SURF_TEX, ARR_TEXELS_F32,
  ARR_LIGHT_TRIS, ARR_LIGHT_CDF, ARR_LIGHT_GEOM, ARR_TRI_ISECT, ARR_RES_NODES, ARR_RES_REFS, ARR_RES_TRIS, ARR_LDS_ROOT,
- ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF, ARR_PUNCTUAL, ARR_PUNCTUAL_CDF) = range(30)
+ ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF, ARR_PUNCTUAL, ARR_PUNCTUAL_CDF, ARR_LENS) = range(31)
 LDS_LEAF_ORDER_BIT = 0x80000000  # ARR_LDS_ROOT: the surface's resident records are leaf-ordered (flat_scene.hpp)
 
 
@@ -57,6 +57,11 @@ class SceneDesc(C.Structure):
     _fields_ = [("n_models", C.c_uint32), ("model_xform", C.c_void_p), ("model_surf", C.c_void_p),
                 ("n_surfaces", C.c_uint32), ("surf_range", C.c_void_p), ("vertices", C.c_void_p),
                 ("triangles", C.c_void_p), ("materials", C.c_void_p), ("camera", C.c_void_p), ("sun", C.c_void_p)]
+
+
+class Camera(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("basis", C.c_float * 9), ("yfov", C.c_float), ("lens_radius", C.c_float),
+                ("focus_distance", C.c_float), ("blades", C.c_uint32), ("blade_rotation", C.c_float)]
 
 
 class SceneInfo(C.Structure):
@@ -213,6 +218,10 @@ def lib():
         L.ptx_scene_destroy.argtypes = [C.c_void_p]
         L.ptx_scene_set_environment.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.ptx_scene_set_punctual_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ptx_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        L.ptx_scene_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        L.ptx_scene_set_model_xforms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ptx_camera_lens_rays_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_gltf_read_punctual_lights.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
         L.ptx_gltf_read_punctual_lights.restype = C.c_int64
         L.ptx_scene_get_info.argtypes = [C.c_void_p, C.POINTER(SceneInfo)]
@@ -462,7 +471,7 @@ _ARR_DTYPE = {ARR_MODEL_XFORM: (np.float32, 12), ARR_MODEL_AABB: (np.float32, 6)
               ARR_LIGHT_TRIS: (np.uint32, 2), ARR_LIGHT_CDF: (np.float32, 1), ARR_LIGHT_GEOM: (np.float32, 4),
               ARR_TRI_ISECT: (np.uint32, 12), ARR_RES_NODES: (np.uint32, 2), ARR_RES_REFS: (np.uint32, 1), ARR_RES_TRIS: (np.uint32, 12),
               ARR_LDS_ROOT: (np.uint32, 1), ARR_RES_PLAN: (np.uint32, 1), ARR_ENV_ROW_CDF: (np.float32, 1), ARR_ENV_CELL_CDF: (np.float32, 1),
-              ARR_PUNCTUAL: (np.float32, 16), ARR_PUNCTUAL_CDF: (np.float32, 1)}
+              ARR_PUNCTUAL: (np.float32, 16), ARR_PUNCTUAL_CDF: (np.float32, 1), ARR_LENS: (np.float32, 2)}
 
 
 class Scene:
@@ -676,6 +685,39 @@ class Scene:
         a = a.reshape(-1, 16)
         _check(lib().ptx_scene_set_punctual_lights(self.h, a.ctypes.data if len(a) else None, len(a)))
 
+    def set_camera(self, origin, basis, yfov, lens_radius=0.0, focus_distance=0.0, blades=0, blade_rotation=0.0):
+        """ptx_scene_set_camera: origin [3], basis [9] (columns x, y, z) and yfov as from_arrays' camera [13]; lens_radius > 0 gives a thin
+        lens with a polygonal aperture of `blades` corners (0 = 16) focused at focus_distance. No tree is built and nothing is re-uploaded."""
+        o, b = np.asarray(origin, np.float32).reshape(-1), np.asarray(basis, np.float32).reshape(-1)
+        if len(o) != 3 or len(b) != 9:
+            raise PtxError(ERR_INVALID, "set_camera: origin is [3], basis is [9]")
+        cam = Camera((C.c_float * 3)(*o), (C.c_float * 9)(*b), yfov, lens_radius, focus_distance, blades, blade_rotation)
+        _check(lib().ptx_scene_set_camera(self.h, C.byref(cam)))
+
+    def camera(self):
+        """ptx_scene_get_camera -> dict(origin [3], basis [9], yfov, lens_radius, focus_distance, blades, blade_rotation), as stored."""
+        cam = Camera()
+        _check(lib().ptx_scene_get_camera(self.h, C.byref(cam)))
+        return dict(origin=np.array(cam.origin, np.float32), basis=np.array(cam.basis, np.float32), yfov=np.float32(cam.yfov),
+                    lens_radius=np.float32(cam.lens_radius), focus_distance=np.float32(cam.focus_distance), blades=int(cam.blades),
+                    blade_rotation=np.float32(cam.blade_rotation))
+
+    def set_model_xforms(self, model_xform):
+        """ptx_scene_set_model_xforms: [n_models, 12] float32 in ARR_MODEL_XFORM's layout. The scene then equals one created from the same
+        arrays with these transforms; no KD tree is built."""
+        a = np.ascontiguousarray(model_xform, np.float32)
+        if a.size % 12:
+            raise PtxError(ERR_INVALID, "set_model_xforms: the array is not [n, 12]")
+        _check(lib().ptx_scene_set_model_xforms(self.h, a.ctypes.data, a.size // 12))
+
+    def lens_rays(self, in5):
+        """ptx_camera_lens_rays_batch: [n,5] float32 (ndc.x, ndc.y, aspect ratio, u, v) -> [n,6] float32 (origin, direction): the lens ray the
+        integrators compute from the lens draws (u, v); the pinhole ray on a scene without a lens."""
+        a = np.ascontiguousarray(in5, np.float32).reshape(-1, 5)
+        out = np.zeros((len(a), 6), np.float32)
+        _check(lib().ptx_camera_lens_rays_batch(self.h, a.ctypes.data, len(a), out.ctypes.data))
+        return out
+
     def camera_rays(self, ndc_ratio):
         """ptx_camera_rays_batch: [n,3] float32 (ndc.x, ndc.y, aspect ratio) -> [n,6] float32 (origin, direction) = scene::camera::get_ray."""
         a = np.ascontiguousarray(ndc_ratio, np.float32).reshape(-1, 3)
@@ -764,6 +806,12 @@ class Renderer:
         self.sun_light_index = 0
         self.visualize_kd_tree_depth = 0
         self.seed = 0x5EED
+        # thin lens of the loaded camera (Scene.set_camera), applied before a render; lens_radius 0 = the pinhole
+        self.lens_radius = 0.0
+        self.focus_distance = 0.0
+        self.blades = 0
+        self.blade_rotation = 0.0
+        self._lens_set = (0.0, 0.0, 0, 0.0)
         self._ctx = Context(device)
         self._scene = None
         self.last_stats = None
@@ -773,6 +821,15 @@ class Renderer:
 
     def load_gltf(self, path):
         self._scene = Scene.load_gltf(self._ctx, path, self.camera_index, self.sun_light_index)
+        self._lens_set = (0.0, 0.0, 0, 0.0)
+
+    def _apply_lens(self):
+        """the lens fields onto the loaded camera, when they changed since the last render"""
+        lens = (self.lens_radius, self.focus_distance, self.blades, self.blade_rotation)
+        if lens != self._lens_set:
+            cam = self._scene.camera()
+            self._scene.set_camera(cam["origin"], cam["basis"], cam["yfov"], *lens)
+            self._lens_set = lens
 
     def set_punctual_lights(self, lights):
         """Scene.set_punctual_lights on the loaded scene: render_nee() and render_adaptive_nee() sample these point and spot lights; render()
@@ -791,6 +848,7 @@ class Renderer:
             # nothing reproducible to be faithful to
             raise PtxError(ERR_UNSUPPORTED, "visualize_kd_tree_depth is not built: the reference colours KD nodes by their heap addresses (mesh.cpp:316-318)")
         W, H = self.resolution
+        self._apply_lens()
         if self.environment != getattr(self, "_env_set", None):
             self._scene.set_environment(self.environment)
             self._env_set = self.environment
@@ -809,6 +867,7 @@ class Renderer:
         if self._scene is None:
             raise PtxError(ERR_INVALID, "render_aov() before load_gltf()")
         W, H = self.resolution
+        self._apply_lens()
         alb, nd, self.last_stats = self._scene.render_aov(W, H, self.sample_count, seed=self.seed)
         cov = alb[..., 3]
         inv = np.where(cov > 0, 1.0 / np.maximum(cov, 1.0), 0.0).astype(np.float32)
@@ -826,6 +885,7 @@ class Renderer:
         if n < 2:
             raise PtxError(ERR_INVALID, "render_denoised: sample_count must be at least 2 (the noise estimate needs two half-frames)")
         W, H = self.resolution
+        self._apply_lens()
         if self.environment != getattr(self, "_env_set", None):
             self._scene.set_environment(self.environment)
             self._env_set = self.environment
@@ -851,6 +911,7 @@ class Renderer:
         if self.transparent_background:
             raise PtxError(ERR_UNSUPPORTED, "render_adaptive: the decision takes radiance sums, which transparent_background does not produce")
         W, H = self.resolution
+        self._apply_lens()
         if self.environment != getattr(self, "_env_set", None):
             self._scene.set_environment(self.environment)
             self._env_set = self.environment
@@ -866,6 +927,7 @@ class Renderer:
         if self.transparent_background:
             raise PtxError(ERR_UNSUPPORTED, "render_adaptive_nee: the decision takes radiance sums, which transparent_background does not produce")
         W, H = self.resolution
+        self._apply_lens()
         if self.environment != getattr(self, "_env_set", None):
             self._scene.set_environment(self.environment)
             self._env_set = self.environment
@@ -883,6 +945,7 @@ class Renderer:
         if self.transparent_background:
             raise PtxError(ERR_UNSUPPORTED, "render_nee: transparent_background's blend is not built on this estimator")
         W, H = self.resolution
+        self._apply_lens()
         if self.environment != getattr(self, "_env_set", None):
             self._scene.set_environment(self.environment)
             self._env_set = self.environment

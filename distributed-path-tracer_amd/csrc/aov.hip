@@ -71,8 +71,9 @@ __global__ void __launch_bounds__(kAovBlock) k_aov_shade(DevScene S, RenderParam
 			}
 			if (!transparent) {   // the sample's surface, back-facing or not (renderer.cpp:478 is the integrator's business)
 				const V3 nrm = shading_normal(sf, me.normal_ts);   // intersect_result::get_normal()
-				const V3 z = {0, 0, 0};
-				const V3 co = mulmv(S.cam.basis, z) + mk(S.cam.origin[0], S.cam.origin[1], S.cam.origin[2]);   // origin of the camera ray (camera_get_ray)
+				uint32_t cx, cy, csample;
+				aov_sample_of(P, id, cx, cy, csample);
+				const V3 co = camera_ray_origin(S, P, cx, cy, csample);   // origin of THIS sample's camera ray: with a lens, its lens point
 				ra = make_float4(me.albedo.x, me.albedo.y, me.albedo.z, 1.0f);
 				rn = make_float4(nrm.x, nrm.y, nrm.z, length(sf.pos - co));
 			}

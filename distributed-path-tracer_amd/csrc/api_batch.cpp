@@ -376,6 +376,25 @@ int ptx_camera_rays_batch(ptx_scene* sc, const float* ndc_ratio, size_t n, float
 	return PTX_OK;
 }
 
+int ptx_camera_lens_rays_batch(ptx_scene* sc, const float* in, size_t n, float* rays) {
+	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_camera_lens_rays_batch: scene is NULL");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_camera_lens_rays_batch: scene was created without a GPU context (no CPU path exists)");
+	if (n == 0) return PTX_OK;
+	if (!in || !rays) return set_err(PTX_ERR_INVALID, "ptx_camera_lens_rays_batch: NULL argument");
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	const bool dev = is_device_ptr(in);
+	if (dev != is_device_ptr(rays)) return set_err(PTX_ERR_INVALID, "ptx_camera_lens_rays_batch: in and out must both be device or both be host memory");
+	Staged s_in, s_out;
+	HIP_TRY(s_in.bind(c, dev, in, n * 5 * 4, c->stage_a));
+	HIP_TRY(s_out.bind(c, dev, rays, n * 6 * 4, c->stage_b, 0, kOutputOnly));
+	HIP_TRY(launch_camera_lens_rays(sc->dev, s_in.as<float>(), s_out.as<float>(), n, c->stream));
+	HIP_TRY(s_out.copy_back(c));
+	if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
+	return PTX_OK;
+}
+
 int ptx_material_eval_batch(ptx_scene* sc, const int32_t* surface, const float* uv, size_t n, float* out) {
 	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_material_eval_batch: scene is NULL");
 	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_material_eval_batch: scene was created without a GPU context (no CPU path exists)");

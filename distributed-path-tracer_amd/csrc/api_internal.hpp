@@ -129,6 +129,7 @@ struct ptx_scene {
 		std::vector<float> recs, cdf;   // [n][16], [n]
 	} punctual;
 	DevBuf d_punctual, d_punctual_cdf;
+	DevBuf d_lens;   // the aperture table (kLensMaxBlades + 1 corners), allocated by upload_scene, refreshed in stream order by ptx_scene_set_camera
 };
 
 const ptx_scene::LightList* build_lights(ptx_scene* sc);   // ptx_api.cpp

@@ -715,7 +715,32 @@ DEV void camera_get_ray(const DevScene& S, float ndc_x, float ndc_y, float ratio
 	o = mulmv(S.cam.basis, z) + mk(S.cam.origin[0], S.cam.origin[1], S.cam.origin[2]);
 	d = normalize(mulmv(S.cam.basis, dir));
 }
-// pixel loop of renderer::render — core/renderer.cpp:359-370: jitter -> NDC -> camera ray
+// The point of the aperture that the draws (u, v) pick, in camera space (include/ptx.h: THE LENS): corner k of the polygon by u, then a
+// uniform point of the triangle (centre, corner k, corner k + 1). Called only where S.cam.lens_radius > 0.
+DEV V3 lens_point(const DevScene& S, float u, float v) {
+	const uint32_t n = S.cam.blades;
+	const float a = u * (float)n;
+	uint32_t k = (uint32_t)a;
+	if (k > n - 1u) k = n - 1u;
+	const float su = sqrt_exact(a - (float)k);
+	const float beta = su * (1 - v), gamma = su * v;
+	const float2 v0 = S.lens[k], v1 = S.lens[k + 1u];
+	return mk(beta * v0.x + gamma * v1.x, beta * v0.y + gamma * v1.y, 0);
+}
+// The thin lens: the ray from the lens point through the pinhole ray's point on the plane of focus
+DEV void camera_lens_ray(const DevScene& S, float ndc_x, float ndc_y, float ratio, float u, float v, V3& o, V3& d) {
+	float dx = S.cam.tan_half_fov * ndc_x, dy = S.cam.tan_half_fov * ndc_y;
+	dx *= ratio;
+	const V3 dir = normalize(mk(dx, dy, -1));
+	const float t = S.cam.focus_distance / (0 - dir.z);
+	const V3 pf = dir * t;
+	const V3 lp = lens_point(S, u, v);
+	const V3 dl = normalize(pf - lp);
+	o = mulmv(S.cam.basis, lp) + mk(S.cam.origin[0], S.cam.origin[1], S.cam.origin[2]);
+	d = normalize(mulmv(S.cam.basis, dl));
+}
+// pixel loop of renderer::render — core/renderer.cpp:359-370: jitter -> NDC -> camera ray. With a lens (a wave-uniform branch on a kernel
+// argument) the two spare values of the jitter block pick the lens point.
 DEV void camera_ray(const DevScene& S, const RenderParams& P, uint32_t x, uint32_t y, uint32_t sample, V3& o, V3& d) {
 	float4 j = draws(P, y * P.W + x, sample, 0, 0, BLOCK_JITTER);
 	if (P.integrator == 1u && sample == 0) j.x = j.y = 0;   // HOST worker.cpp:125-126: the first sample is not offset
@@ -723,7 +748,17 @@ DEV void camera_ray(const DevScene& S, const RenderParams& P, uint32_t x, uint32
 	float ndc_y = (((float)y + j.y) / (float)P.H) * 2 - 1;
 	ndc_y = -ndc_y;
 	float ratio = (float)P.W / (float)P.H;
-	camera_get_ray(S, ndc_x, ndc_y, ratio, o, d);
+	if (S.cam.lens_radius > 0) camera_lens_ray(S, ndc_x, ndc_y, ratio, j.z, j.w, o, d);
+	else camera_get_ray(S, ndc_x, ndc_y, ratio, o, d);
+}
+// origin of the camera ray of (pixel, sample): what camera_ray gives as `o`, without the direction (ptx_render_aov's depth)
+DEV V3 camera_ray_origin(const DevScene& S, const RenderParams& P, uint32_t x, uint32_t y, uint32_t sample) {
+	V3 lp = {0, 0, 0};
+	if (S.cam.lens_radius > 0) {
+		const float4 j = draws(P, y * P.W + x, sample, 0, 0, BLOCK_JITTER);
+		lp = lens_point(S, j.z, j.w);
+	}
+	return mulmv(S.cam.basis, lp) + mk(S.cam.origin[0], S.cam.origin[1], S.cam.origin[2]);
 }
 
 // ------------------------------------------------------------------------------------ textures

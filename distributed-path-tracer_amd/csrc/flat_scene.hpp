@@ -151,7 +151,9 @@ struct SpaceRec {
 	float inv_origin[3];
 };
 
-struct CameraRec { float origin[3]; float basis[9]; float fov; float tan_half_fov; };
+// The lens fields (ptx_scene_set_camera, include/ptx.h: THE LENS) are all zero on a scene never given a lens: lens_radius == 0 is the pinhole.
+struct CameraRec { float origin[3]; float basis[9]; float fov; float tan_half_fov; float lens_radius, focus_distance; uint32_t blades; float blade_rotation; };
+constexpr uint32_t kLensMaxBlades = 32;   // the aperture table holds blades + 1 corners, the last a copy of the first
 struct SunRec { float basis[9]; float energy[3]; float angular_radius; uint32_t present; };
 
 // ---- host-side container ----
@@ -211,6 +213,12 @@ void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order = true)
 // Builds everything derived (AABBs, KD-trees, records) from the "as loaded" arrays + camera/sun floats.
 // camera13: origin(3) basis(9) fov ; sun13: basis(9) energy(3) angular_radius or nullptr.
 void finalize_scene(FlatScene& s, const float* camera13, const float* sun13);
+// The transform-dependent tail of finalize_scene, from s.model_xform: model records (inverse and normal matrices, boxes), the distinct ray
+// spaces, and the shade records. Builds no tree; ptx_scene_set_model_xforms reruns it on a finished scene.
+void apply_model_xforms(FlatScene& s);
+// The aperture table of a camera with a lens (include/ptx.h: THE APERTURE TABLE): blades + 1 corners (x, y), float64 arithmetic, stored as
+// float32, the last entry a bitwise copy of the first. Empty when lens_radius == 0.
+std::vector<float> lens_table(const CameraRec& cam);
 
 // glTF loader (throws ptx::Error)
 struct Error {

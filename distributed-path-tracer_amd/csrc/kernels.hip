@@ -759,6 +759,18 @@ __global__ void k_camera_rays(DevScene S, const float* __restrict__ in, float* _
 	float* q = out + 6 * i;
 	q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = d.x; q[4] = d.y; q[5] = d.z;
 }
+// the camera ray of (ndc, ratio) and the lens draws (u, v) by camera_ray's own branch: the lens ray, or without a lens the pinhole ray
+// (ptx_camera_lens_rays_batch)
+__global__ void k_camera_lens_rays(DevScene S, const float* __restrict__ in, float* __restrict__ out, size_t n) {
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	V3 o, d;
+	const float* p = in + 5 * i;
+	if (S.cam.lens_radius > 0) camera_lens_ray(S, p[0], p[1], p[2], p[3], p[4], o, d);
+	else camera_get_ray(S, p[0], p[1], p[2], o, d);
+	float* q = out + 6 * i;
+	q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = d.x; q[4] = d.y; q[5] = d.z;
+}
 
 // ------------------------------------------------------------------------------------ batch material lookups
 // core::material::get_normal / albedo / opacity / roughness / metallic / emissive * 10 exactly as shade_vertex evaluates them
@@ -903,6 +915,10 @@ hipError_t launch_exact_math_check(unsigned long long* bad, hipStream_t stream) 
 }
 hipError_t launch_shade_consts_check(const float* in, const ShadeRec* rec, size_t n, unsigned long long* bad, hipStream_t stream) {
 	hipLaunchKernelGGL(k_shade_consts_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, rec, n, bad);
+	return hipGetLastError();
+}
+hipError_t launch_camera_lens_rays(const DevScene& S, const float* in, float* out, size_t n, hipStream_t stream) {
+	hipLaunchKernelGGL(k_camera_lens_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, S, in, out, n);
 	return hipGetLastError();
 }
 hipError_t launch_camera_rays(const DevScene& S, const float* in, float* out, size_t n, hipStream_t stream) {

@@ -77,6 +77,7 @@ struct DevScene {
 	uint32_t n_spaces;
 	CameraRec cam;
 	SunRec sun;
+	const float2* lens;      // [kLensMaxBlades + 1] the aperture's corners (ptx_scene_set_camera); read only where cam.lens_radius > 0
 };
 
 struct RenderParams {
@@ -183,6 +184,7 @@ constexpr uint32_t kExactMathForms = 3;   // k_exact_math_check: one counter per
 hipError_t launch_exact_math_check(unsigned long long* bad /* [kExactMathForms], device, zeroed */, hipStream_t stream);
 hipError_t launch_shade_consts_check(const float* in /* [n][9] */, const ShadeRec* rec /* [n] */, size_t n, unsigned long long* bad /* device, zeroed */, hipStream_t stream);
 hipError_t launch_camera_rays(const DevScene& S, const float* in /* [n][3]: ndc.x ndc.y ratio */, float* out /* [n][6] */, size_t n, hipStream_t stream);
+hipError_t launch_camera_lens_rays(const DevScene& S, const float* in /* [n][5]: ndc.x ndc.y ratio u v */, float* out /* [n][6] */, size_t n, hipStream_t stream);
 hipError_t launch_material_eval(const DevScene& S, const int32_t* surface /* [n] */, const float* uv /* [n][2] */, size_t n, float* out /* [n][12] */, hipStream_t stream);
 hipError_t launch_tonemap(const float4* accum, uint32_t n_pixels, float spp, const float* thresholds /* [256], device */, uchar4* out, hipStream_t stream);
 

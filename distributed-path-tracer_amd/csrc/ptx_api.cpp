@@ -201,6 +201,10 @@ int upload_scene(ptx_scene* sc) {
 		fill(order.data() + ns, ob ? atoi(ob) : 0);
 		HIP_TRY(up(sc->d_wf_order, order.data(), order.size() * 4, order.size() * 4));
 	}
+	{   // the aperture table: always the full 33 corners, so that ptx_scene_set_camera never has to allocate
+		const std::vector<float> lens = lens_table(h.camera);
+		HIP_TRY(up(sc->d_lens, lens.data(), lens.size() * 4, (kLensMaxBlades + 1) * 8));
+	}
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	DevScene& d = sc->dev;
 	d.models = (const ModelRec*)sc->d_models.p;
@@ -239,13 +243,14 @@ int upload_scene(ptx_scene* sc) {
 	d.n_tris = (uint32_t)h.tris.size();
 	d.cam = h.camera;
 	d.sun = h.sun;
+	d.lens = (const float2*)sc->d_lens.p;
 	return PTX_OK;
 }
 
 void release_scene_buffers(ptx_scene* sc) {
 	for (DevBuf* b : {&sc->d_models, &sc->d_surfaces, &sc->d_materials, &sc->d_nodes, &sc->d_refs, &sc->d_tris, &sc->d_shade, &sc->d_tex,
 	                  &sc->d_texels, &sc->d_texels_f, &sc->d_lut, &sc->d_spaces, &sc->d_model_space, &sc->d_wf_order, &sc->d_res_nodes, &sc->d_res_refs, &sc->d_res_tris, &sc->d_hot,
-	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell, &sc->d_punctual, &sc->d_punctual_cdf})
+	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell, &sc->d_punctual, &sc->d_punctual_cdf, &sc->d_lens})
 		b->release();
 	sc->lights.on_device = false;
 	sc->env_table.on_device = false;
@@ -578,6 +583,79 @@ int ptx_scene_set_punctual_lights(ptx_scene* sc, const float* lights, uint32_t n
 	return PTX_OK;
 }
 
+int ptx_scene_set_camera(ptx_scene* sc, const ptx_camera* cam) {
+	// every refusal is decided before any device work and before the scene is touched
+	auto bad = [](const char* m) { return set_err(PTX_ERR_INVALID, std::string("ptx_scene_set_camera: ") + m); };
+	if (!sc || !cam) return bad("NULL argument");
+	for (int k = 0; k < 3; k++) if (!std::isfinite(cam->origin[k])) return bad("origin is not finite");
+	for (int k = 0; k < 9; k++) if (!std::isfinite(cam->basis[k])) return bad("basis is not finite");
+	if (!std::isfinite(cam->yfov) || !std::isfinite(cam->lens_radius) || !std::isfinite(cam->focus_distance) || !std::isfinite(cam->blade_rotation))
+		return bad("a field is not finite");
+	if (!(cam->yfov > 0) || !((double)cam->yfov < 3.14159265358979323846)) return bad("yfov must lie in (0, pi)");
+	if (cam->lens_radius < 0) return bad("lens_radius < 0");
+	if (cam->lens_radius > 0 && !(cam->focus_distance > 0)) return bad("a lens needs focus_distance > 0");
+	if (cam->blades != 0 && (cam->blades < 3 || cam->blades > kLensMaxBlades)) return bad("blades must be 0 or 3 .. 32");
+	CameraRec next{};
+	memcpy(next.origin, cam->origin, 12);
+	memcpy(next.basis, cam->basis, 36);
+	next.fov = cam->yfov;
+	next.tan_half_fov = std::tan(cam->yfov * 0.5F);   // as finalize_scene computes it
+	if (cam->lens_radius > 0) {   // without a lens the lens fields are stored as zeros: the scene is the pinhole scene, whatever they held
+		next.lens_radius = cam->lens_radius;
+		next.focus_distance = cam->focus_distance;
+		next.blades = cam->blades ? cam->blades : 16u;
+		next.blade_rotation = cam->blade_rotation;
+	}
+	std::unique_lock<std::mutex> lk;
+	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);   // no render of this scene is being queued
+	if (sc->ctx && next.lens_radius > 0) {
+		// the table goes into the scene's own buffer behind whatever is queued on the stream; nothing is freed or allocated. The source is
+		// a local: the stream is synchronised before it goes
+		ptx_ctx* c = sc->ctx;
+		HIP_TRY(hipSetDevice(c->device));
+		const std::vector<float> lens = lens_table(next);
+		HIP_TRY(hipMemcpyAsync(sc->d_lens.p, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+	}
+	sc->host.camera = next;
+	if (sc->ctx) sc->dev.cam = next;   // a kernel argument: the next launch takes it
+	return PTX_OK;
+}
+
+int ptx_scene_get_camera(const ptx_scene* sc, ptx_camera* out) {
+	if (!sc || !out) return set_err(PTX_ERR_INVALID, "ptx_scene_get_camera: NULL argument");
+	std::unique_lock<std::mutex> lk;
+	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);
+	const CameraRec& c = sc->host.camera;
+	memcpy(out->origin, c.origin, 12);
+	memcpy(out->basis, c.basis, 36);
+	out->yfov = c.fov;
+	out->lens_radius = c.lens_radius;
+	out->focus_distance = c.focus_distance;
+	out->blades = c.blades;
+	out->blade_rotation = c.blade_rotation;
+	return PTX_OK;
+}
+
+int ptx_scene_set_model_xforms(ptx_scene* sc, const float* model_xform, uint32_t n_models) {
+	auto bad = [](const char* m) { return set_err(PTX_ERR_INVALID, std::string("ptx_scene_set_model_xforms: ") + m); };
+	if (!sc || !model_xform) return bad("NULL argument");
+	if ((size_t)n_models * 12 != sc->host.model_xform.size()) return bad("n_models differs from the scene's");   // the size never changes after creation
+	for (size_t k = 0; k < (size_t)n_models * 12; k++)
+		if (!std::isfinite(model_xform[k])) return bad("a value is not finite");
+	std::unique_lock<std::mutex> lk;
+	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);
+	FlatScene& h = sc->host;
+	h.model_xform.assign(model_xform, model_xform + (size_t)n_models * 12);
+	apply_model_xforms(h);   // model, space and shade records; no tree is built
+	{   // world normals and areas of the emissive triangles moved with the models: the list is rebuilt at the next request
+		std::lock_guard<std::mutex> tl(sc->lights_mu);
+		sc->lights = ptx_scene::LightList{};
+	}
+	if (sc->ctx) return upload_scene(sc);   // every record goes up again, in stream order, into the buffers the scene already owns
+	return PTX_OK;
+}
+
 int64_t ptx_gltf_read_punctual_lights(const char* gltf_path, float* dst, size_t dst_floats) {
 	if (!gltf_path) return -(int64_t)set_err(PTX_ERR_INVALID, "ptx_gltf_read_punctual_lights: path is NULL");
 	std::vector<float> recs;
@@ -713,6 +791,7 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 	case PTX_ARR_ENV_CELL_CDF: { const auto& et = *build_env_table(const_cast<ptx_scene*>(sc)); src = et.cell_cdf.data(); bytes = et.cell_cdf.size() * 4; break; }
 	case PTX_ARR_PUNCTUAL: { std::lock_guard<std::mutex> tl(const_cast<ptx_scene*>(sc)->lights_mu); tmp = sc->punctual.recs; src = tmp.data(); bytes = tmp.size() * 4; break; }
 	case PTX_ARR_PUNCTUAL_CDF: { std::lock_guard<std::mutex> tl(const_cast<ptx_scene*>(sc)->lights_mu); tmp = sc->punctual.cdf; src = tmp.data(); bytes = tmp.size() * 4; break; }
+	case PTX_ARR_LENS: tmp = lens_table(h.camera); src = tmp.data(); bytes = tmp.size() * 4; break;
 	case PTX_ARR_TRI_ISECT: src = h.tri_isect.data(); bytes = h.tri_isect.size() * sizeof(TriIsect); break;
 	case PTX_ARR_RES_NODES: src = h.res_nodes.data(); bytes = h.res_nodes.size() * 8; break;
 	case PTX_ARR_RES_REFS: src = h.res_refs.data(); bytes = h.res_refs.size() * 4; break;

@@ -348,6 +348,26 @@ void finalize_scene(FlatScene& s, const float* cam, const float* sun) {
 		if (!(mr.opacity == 1.0f || std::fabs(mr.opacity - 1.0f) < kEps) || mr.shadow_catcher) s.any_alpha = true;
 	}
 
+	apply_model_xforms(s);
+
+	memcpy(s.camera.origin, cam, 12);
+	memcpy(s.camera.basis, cam + 3, 36);
+	s.camera.fov = cam[12];
+	s.camera.tan_half_fov = std::tan(cam[12] * 0.5F);  // camera::set_fov, LIB/scene/camera.cpp:27-30
+	s.camera.lens_radius = s.camera.focus_distance = s.camera.blade_rotation = 0;   // a pinhole until ptx_scene_set_camera says otherwise
+	s.camera.blades = 0;
+	s.sun = SunRec{};
+	if (sun) {
+		memcpy(s.sun.basis, sun, 36);
+		memcpy(s.sun.energy, sun + 9, 12);
+		s.sun.angular_radius = sun[12];
+		s.sun.present = 1;
+	}
+}
+
+void apply_model_xforms(FlatScene& s) {
+	const size_t n_models = s.model_surf.size() / 2;
+	const size_t n_surf = s.surf_range.size() / 8;
 	for (size_t mi = 0; mi < n_models; mi++) {
 		ModelRec& mr = s.models[mi];
 		const float* x = &s.model_xform[12 * mi];
@@ -401,18 +421,19 @@ void finalize_scene(FlatScene& s, const float* cam, const float* sun) {
 			r.mat = s.materials[s.models[mi].first_surface + k];
 			fill_shade_consts(r);
 		}
+}
 
-	memcpy(s.camera.origin, cam, 12);
-	memcpy(s.camera.basis, cam + 3, 36);
-	s.camera.fov = cam[12];
-	s.camera.tan_half_fov = std::tan(cam[12] * 0.5F);  // camera::set_fov, LIB/scene/camera.cpp:27-30
-	s.sun = SunRec{};
-	if (sun) {
-		memcpy(s.sun.basis, sun, 36);
-		memcpy(s.sun.energy, sun + 9, 12);
-		s.sun.angular_radius = sun[12];
-		s.sun.present = 1;
+std::vector<float> lens_table(const CameraRec& cam) {
+	std::vector<float> t;
+	if (!(cam.lens_radius > 0)) return t;
+	const uint32_t n = cam.blades;
+	for (uint32_t k = 0; k < n; k++) {
+		const double th = (double)cam.blade_rotation + 2.0 * 3.14159265358979323846 * (double)k / (double)n;
+		t.push_back((float)((double)cam.lens_radius * std::cos(th)));
+		t.push_back((float)((double)cam.lens_radius * std::sin(th)));
 	}
+	t.push_back(t[0]); t.push_back(t[1]);
+	return t;
 }
 
 void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order) {

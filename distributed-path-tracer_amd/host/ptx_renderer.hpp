@@ -36,6 +36,11 @@ public:
 	// per further round (0 = adaptive_min); sample_count is the cap
 	float adaptive_threshold = 0.1f;
 	uint32_t adaptive_min = 8, adaptive_step = 0;
+	// thin lens of the loaded camera (ptx_scene_set_camera; no counterpart in the reference), applied before a render: circumradius of the
+	// aperture (0 = the pinhole), distance of the plane of focus, corners of the aperture polygon (0 = 16), angle of corner 0
+	float lens_radius = 0, focus_distance = 0;
+	uint32_t blades = 0;
+	float blade_rotation = 0;
 
 	explicit renderer(int device = 0) { check(ptx_ctx_create(device, &ctx_)); }
 	renderer(const renderer&) = delete;
@@ -50,7 +55,18 @@ public:
 		ptx_scene_destroy(scene_);
 		scene_ = nullptr;
 		env_set_.clear();
+		lens_set_ = lens{};
 		check(ptx_scene_load_gltf(ctx_, path.string().c_str(), &o, &scene_));
+	}
+	// the lens fields onto the loaded camera, when they changed since the last render
+	void apply_lens() const {
+		const lens want{lens_radius, focus_distance, blades, blade_rotation};
+		if (want.radius == lens_set_.radius && want.focus == lens_set_.focus && want.blades == lens_set_.blades && want.rotation == lens_set_.rotation) return;
+		ptx_camera cam{};
+		check(ptx_scene_get_camera(scene_, &cam));
+		cam.lens_radius = lens_radius; cam.focus_distance = focus_distance; cam.blades = blades; cam.blade_rotation = blade_rotation;
+		check(ptx_scene_set_camera(scene_, &cam));
+		lens_set_ = want;
 	}
 
 	// The `point` and `spot` lights of a glTF file (KHR_lights_punctual) as 16-float records (ptx_gltf_read_punctual_lights; include/ptx.h has
@@ -74,6 +90,7 @@ public:
 	std::vector<float> render_accum(ptx_render_stats* stats = nullptr) const {
 		if (!scene_) throw std::runtime_error("render() before load_gltf()");
 		if (visualize_kd_tree_depth) throw std::runtime_error("visualize_kd_tree_depth is not built: the reference colours KD nodes by their heap addresses (mesh.cpp:316-318)");
+		apply_lens();
 		if (environment.string() != env_set_) {   // (re)load the map only when the field changed
 			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
 			env_set_ = environment.string();
@@ -97,6 +114,7 @@ public:
 	struct aov { std::vector<float> albedo_cov, normal_depth; };
 	aov render_aov(ptx_render_stats* stats = nullptr) const {
 		if (!scene_) throw std::runtime_error("render_aov() before load_gltf()");
+		apply_lens();
 		ptx_render_cfg c{};
 		c.W = resolution.x; c.H = resolution.y; c.spp = sample_count;
 		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
@@ -112,6 +130,7 @@ public:
 		if (!scene_) throw std::runtime_error("render_denoised() before load_gltf()");
 		if (transparent_background) throw std::runtime_error("render_denoised: the filter takes radiance sums, which transparent_background does not produce");
 		if (sample_count < 2) throw std::runtime_error("render_denoised: sample_count must be at least 2 (the noise estimate needs two half-frames)");
+		apply_lens();
 		if (environment.string() != env_set_) {
 			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
 			env_set_ = environment.string();
@@ -141,6 +160,7 @@ public:
 	std::vector<float> render_adaptive(ptx_adaptive_stats* stats = nullptr, bool denoise = false, ptx_denoise_stats* dstats = nullptr) const {
 		if (!scene_) throw std::runtime_error("render_adaptive() before load_gltf()");
 		if (transparent_background) throw std::runtime_error("render_adaptive: the decision takes radiance sums, which transparent_background does not produce");
+		apply_lens();
 		if (environment.string() != env_set_) {
 			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
 			env_set_ = environment.string();
@@ -170,6 +190,7 @@ public:
 	                           ptx_adaptive_nee_stats* nee_stats = nullptr) const {
 		if (!scene_) throw std::runtime_error("render_adaptive_shard() before load_gltf()");
 		if (transparent_background) throw std::runtime_error("render_adaptive_shard: the decision takes radiance sums, which transparent_background does not produce");
+		apply_lens();
 		if (environment.string() != env_set_) {
 			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
 			env_set_ = environment.string();
@@ -194,6 +215,7 @@ public:
 	std::vector<float> render_adaptive_nee(ptx_adaptive_nee_stats* stats = nullptr, uint32_t flags = 0, bool denoise = false, ptx_denoise_stats* dstats = nullptr) const {
 		if (!scene_) throw std::runtime_error("render_adaptive_nee() before load_gltf()");
 		if (transparent_background) throw std::runtime_error("render_adaptive_nee: the decision takes radiance sums, which transparent_background does not produce");
+		apply_lens();
 		if (environment.string() != env_set_) {
 			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
 			env_set_ = environment.string();
@@ -216,6 +238,7 @@ public:
 		if (!scene_) throw std::runtime_error("render_nee_denoised() before load_gltf()");
 		if (transparent_background) throw std::runtime_error("render_nee_denoised: transparent_background's blend is not built on this estimator");
 		if (sample_count < 2) throw std::runtime_error("render_nee_denoised: sample_count must be at least 2 (the noise estimate needs two half-frames)");
+		apply_lens();
 		if (environment.string() != env_set_) {
 			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
 			env_set_ = environment.string();
@@ -254,6 +277,7 @@ public:
 	std::vector<float> render_nee(ptx_nee_stats* stats = nullptr, uint32_t flags = 0) const {
 		if (!scene_) throw std::runtime_error("render_nee() before load_gltf()");
 		if (transparent_background) throw std::runtime_error("render_nee: transparent_background's blend is not built on this estimator");
+		apply_lens();
 		if (environment.string() != env_set_) {
 			check(ptx_scene_set_environment(scene_, environment.empty() ? nullptr : environment.string().c_str(), 1));
 			env_set_ = environment.string();
@@ -306,6 +330,8 @@ private:
 	ptx_ctx* ctx_ = nullptr;
 	ptx_scene* scene_ = nullptr;
 	mutable std::string env_set_;
+	struct lens { float radius = 0, focus = 0; uint32_t blades = 0; float rotation = 0; };
+	mutable lens lens_set_;
 };
 
 }  // namespace core

@@ -1,6 +1,6 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
 //       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
 //       --nee:         light sampling towards the scene's emissive triangles (renderer::render_nee)
@@ -19,6 +19,9 @@
 //                      (renderer::render_adaptive_nee); --adaptive --denoise, with or without --nee*, filters the adaptive frame
 //                      (ptx_denoise_counts on the guides of the first MIN samples); --nee* --denoise filters two light-sampled half-frames
 //                      (renderer::render_nee_denoised). --transparent combines with none of them
+//       --lens R:F[:BLADES[:ROT]]: a thin lens on the loaded camera (renderer::lens_radius ...): aperture circumradius R > 0 in scene units, focused
+//                      at distance F > 0, the aperture a regular polygon of BLADES corners (3 .. 32, default 16) turned by ROT radians;
+//                      combines with every other switch
 //       --aov PREFIX:  also writes the denoiser's guide images PREFIX_albedo.png (mean albedo of the covered samples, alpha = coverage)
 //                      and PREFIX_normal.png (mean shading normal * 0.5 + 0.5), quantised linearly to 8 bits
 //   ptx_render_cli --event <event.json> <local scene root dir> <out.png>     (the worker's Lambda event, main.cpp:9-25)
@@ -51,6 +54,8 @@ int main(int argc, char** argv) {
 	float ad_thr = 0.1f;
 	unsigned ad_min = 8, ad_step = 0, nee_candidates = 1;
 	std::string aov_prefix, nee_env;
+	float lens_r = 0, lens_f = 0, lens_rot = 0;
+	unsigned lens_blades = 0;
 	for (;;) {   // leading switches
 		if (argc > 1 && std::string(argv[1]) == "--transparent") { transparent = true; argv[1] = argv[0]; argv++; argc--; }
 		else if (argc > 1 && std::string(argv[1]) == "--denoise") { denoise = true; argv[1] = argv[0]; argv++; argc--; }
@@ -67,11 +72,20 @@ int main(int argc, char** argv) {
 			if (std::sscanf(argv[2], "%f:%u:%u", &ad_thr, &ad_min, &ad_step) < 1) { std::fprintf(stderr, "error: --adaptive THR[:MIN[:STEP]]\n"); return 1; }
 			adaptive = true; argv[2] = argv[0]; argv += 2; argc -= 2;
 		}
+		else if (argc > 2 && std::string(argv[1]) == "--lens") {
+			char tail = 0;
+			const int got = std::sscanf(argv[2], "%f:%f:%u:%f%c", &lens_r, &lens_f, &lens_blades, &lens_rot, &tail);
+			if (got < 2 || got > 4 || !(lens_r > 0) || !(lens_f > 0) || (got >= 3 && (lens_blades < 3 || lens_blades > 32))) {
+				std::fprintf(stderr, "error: --lens R:F[:BLADES[:ROT]], R > 0, F > 0, BLADES = 3 .. 32\n");
+				return 1;
+			}
+			argv[2] = argv[0]; argv += 2; argc -= 2;
+		}
 		else if (argc > 2 && std::string(argv[1]) == "--aov") { aov_prefix = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (nee_punctual && !nee) {
@@ -115,6 +129,7 @@ int main(int argc, char** argv) {
 		r.load_gltf(argv[1]);
 		if (!nee_env.empty()) r.environment = nee_env;
 		r.nee_candidates = nee_candidates;
+		r.lens_radius = lens_r; r.focus_distance = lens_f; r.blades = lens_blades; r.blade_rotation = lens_rot;
 		size_t n_punctual = 0;
 		if (nee_punctual) {
 			const std::vector<float> lamps = core::renderer::read_punctual_lights(argv[1]);

@@ -113,6 +113,53 @@ void ptx_scene_destroy(ptx_scene* scene);
  * Radiance .hdr (by content, as stb_image decides); an .hdr keeps its float texels (image::hdr). */
 int ptx_scene_set_environment(ptx_scene* scene, const char* png_path, int srgb);
 
+/* ---- moving a loaded scene ------------------------------------------------------------------------
+ * The camera and the model transforms of a scene can be set after creation; neither call builds a KD tree (the trees are mesh-local).
+ *
+ * THE CAMERA. origin, basis and yfov are ptx_scene_desc::camera [13], same order and meaning; tan_half_fov = std::tan(yfov * 0.5F) as at
+ * creation. PTX_ARR_CAMERA reports the new values. The call works on host-only scenes. On a scene with a context it waits for no render
+ * and re-uploads nothing but the aperture table: the camera is a kernel argument of the next launch. PTX_ERR_INVALID for a NULL argument,
+ * a non-finite field, yfov outside (0, pi), lens_radius < 0, lens_radius > 0 with focus_distance not > 0, blades other than 0 or 3 .. 32;
+ * decided before any device work, and a refused call leaves the camera as it was. With lens_radius == 0 the other lens fields are ignored
+ * and stored as 0: the scene renders every bit as a scene never given a lens.
+ *
+ * THE APERTURE TABLE (PTX_ARR_LENS): float[blades + 1][2], empty while lens_radius == 0. Built on the host in float64 from the stored
+ * float32 fields and stored as float32: v_k = (R cos th_k, R sin th_k), th_k = blade_rotation + 2 pi k / blades, k = 0 .. blades - 1;
+ * entry `blades` is a bitwise copy of entry 0.
+ *
+ * THE LENS: what every integrator's camera sample computes (ptx_render with both integrators, ptx_render_transparent, ptx_render_aov,
+ * ptx_render_nee in both forms, both adaptive calls). IEEE binary32, each operation rounded on its own, in the order written; normalize
+ * and mulmv are the device's own, as scene::camera::get_ray uses them.
+ *   j = draws(pixel, sample, 0, 0, BLOCK_JITTER); j.x, j.y are the pixel jitter (the worker estimator's un-jittered sample 0 zeroes j.x,
+ *   j.y only); ndc_x, ndc_y, ratio, dx, dy and dir = normalize((dx, dy, -1)) as in camera::get_ray.
+ *   lens_radius == 0: o and d as camera::get_ray gives them.
+ *   lens_radius > 0, n = blades, v = the aperture table:
+ *     t = focus_distance / (0 - dir.z);   pf = dir * t
+ *     a = j.z * (float)n;   k = min((uint32_t)a, n - 1);   u = a - (float)k;   su = sqrt(u)
+ *     beta = su * (1 - j.w);   gamma = su * j.w
+ *     lx = beta * v[k].x + gamma * v[k+1].x;   ly = beta * v[k].y + gamma * v[k+1].y;   lp = (lx, ly, 0)
+ *     dl = normalize(pf - lp);   o = mulmv(basis, lp) + origin;   d = normalize(mulmv(basis, dl))
+ *   The lens point is uniform on the polygon (E[|lp|^2] = R^2 (2 + cos(2 pi / n)) / 6), and every lens ray of one (ndc_x, ndc_y) passes
+ *   through pf, the pinhole ray's point on the plane of focus. ptx_render_aov's depth is the distance from the sample's own lens point. */
+typedef struct ptx_camera {
+	float origin[3]; float basis[9]; float yfov;
+	float lens_radius;      /* circumradius of the aperture, scene units; 0 = pinhole */
+	float focus_distance;   /* distance of the plane of focus in front of the camera, along its -Z axis */
+	uint32_t blades;        /* the aperture is a regular polygon of 3 .. 32 corners; 0 = 16 */
+	float blade_rotation;   /* radians, angle of corner 0 from the camera's +X axis */
+} ptx_camera;
+int ptx_scene_set_camera(ptx_scene* scene, const ptx_camera* camera);
+/* as stored: blades resolved, the lens fields 0 on a scene never given a lens */
+int ptx_scene_get_camera(const ptx_scene* scene, ptx_camera* camera);
+
+/* THE MODEL TRANSFORMS, in the layout and order of PTX_ARR_MODEL_XFORM. Afterwards the scene is indistinguishable from one created by
+ * ptx_scene_from_arrays from the same arrays with these transforms: every ptx_scene_get_array, ptx_scene_get_info and every render is
+ * bitwise equal. The model, ray-space and shade records are recomputed; the light list of ptx_render_nee is dropped and rebuilt at the
+ * next request; on a scene with a context the records go up again into the buffers the scene owns. The environment map, the punctual
+ * lights (world-space state: they do not move with models) and the camera stay as set. Works on host-only scenes. PTX_ERR_INVALID for a
+ * NULL argument, n_models different from the scene's, and a non-finite value; decided before the scene is touched. */
+int ptx_scene_set_model_xforms(ptx_scene* scene, const float* model_xform /* [n_models][12], host */, uint32_t n_models);
+
 /* Point and spot lights (glTF KHR_lights_punctual; no counterpart in the reference, which reads only the `directional` sun). They are
  * scene state that ptx_render_nee and ptx_render_adaptive_nee sample as a third light-sampling strategy (PUNCTUAL LIGHTS below
  * ptx_render_nee's flags has the estimator); ptx_render, ptx_render_transparent, ptx_render_aov and the PTX_INTEGRATOR_WORKER estimator
@@ -188,7 +235,8 @@ typedef enum ptx_array {
 	PTX_ARR_ENV_CELL_CDF = 27,/* float[h][w]: cumulative share of the boxes within their row, the last entry 1; a row of zero mass is all 0 */
 	/* the punctual lights of ptx_scene_set_punctual_lights (host-only scenes too; both empty when none are set) */
 	PTX_ARR_PUNCTUAL = 28,    /* float[n][16], as stored */
-	PTX_ARR_PUNCTUAL_CDF = 29 /* float[n]: cumulative share of lum(intensity), the last entry 1 */
+	PTX_ARR_PUNCTUAL_CDF = 29,/* float[n]: cumulative share of lum(intensity), the last entry 1 */
+	PTX_ARR_LENS = 30         /* float[blades + 1][2]: the aperture table of ptx_scene_set_camera; empty while lens_radius == 0 */
 } ptx_array;
 int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, size_t dst_bytes);
 
@@ -678,8 +726,13 @@ int ptx_intersect_batch(ptx_scene* scene, const ptx_rays* rays, size_t n, const 
 
 /* Batch form of scene::camera::get_ray(ndc, ratio) (LIB/scene/camera.cpp:10-21): what the integrator kernels compute for every camera
  * sample after the pixel jitter (renderer.cpp:359-370), evaluated by the same device function.
- * in [n][3]: ndc.x, ndc.y, aspect ratio;  out [n][6]: ray origin(3), direction(3). Pointers device or host (both of one kind). */
+ * in [n][3]: ndc.x, ndc.y, aspect ratio;  out [n][6]: ray origin(3), direction(3). Pointers device or host (both of one kind).
+ * It stays the pinhole function of (ndc, ratio) on a scene whose camera has a lens as well. */
 int ptx_camera_rays_batch(ptx_scene* scene, const float* ndc_ratio, size_t n, float* rays);
+/* The lens branch of THE LENS (ptx_scene_set_camera) with (j.z, j.w) = (u, v), evaluated by the same device function the integrators
+ * inline; on a scene without a lens the pinhole rays. in [n][5]: ndc.x, ndc.y, aspect ratio, u, v;  out [n][6]. Pointers and refusals as
+ * in ptx_camera_rays_batch. */
+int ptx_camera_lens_rays_batch(ptx_scene* scene, const float* in, size_t n, float* rays);
 
 /* Batch form of core::material::get_normal / get_albedo / get_opacity / get_roughness / get_metallic / get_emissive (LIB/core/material.cpp:6-53,
  * bilinear image_texture::sample lookups): what the shading kernels compute at a hit, evaluated by the same device function.

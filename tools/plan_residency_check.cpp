@@ -155,6 +155,32 @@ int main(int argc, char** argv) {
 		FlatScene proc;
 		procedural(proc);
 		sweep(proc, "procedural");
+		// moving the models (ptx_scene_set_model_xforms' host part): the records are those of a scene finalized with the moved transforms,
+		// the residency plan still holds, and moving back restores the first records; the aperture table of every blade count
+		FlatScene moved;
+		procedural(moved);
+		const std::vector<ModelRec> first = moved.models;
+		std::swap_ranges(moved.model_xform.begin(), moved.model_xform.begin() + 12, moved.model_xform.begin() + 12);
+		apply_model_xforms(moved);
+		FlatScene fresh;
+		procedural(fresh);   // procedural() finalizes with its own transforms: swap them and redo the tail on a second scene
+		fresh.model_xform = moved.model_xform;
+		apply_model_xforms(fresh);
+		CHECK(moved.models.size() == fresh.models.size() && !memcmp(moved.models.data(), fresh.models.data(), moved.models.size() * sizeof(ModelRec)), "moved model records");
+		CHECK(moved.shade.size() == fresh.shade.size() && !memcmp(moved.shade.data(), fresh.shade.data(), moved.shade.size() * sizeof(ShadeRec)), "moved shade records");
+		CHECK(moved.spaces.size() == 2 && moved.model_space.size() == 2, "moved ray spaces: %zu", moved.spaces.size());
+		sweep(moved, "procedural, models moved");
+		std::swap_ranges(moved.model_xform.begin(), moved.model_xform.begin() + 12, moved.model_xform.begin() + 12);
+		apply_model_xforms(moved);
+		CHECK(!memcmp(moved.models.data(), first.data(), first.size() * sizeof(ModelRec)), "models moved back");
+		for (uint32_t n = 3; n <= kLensMaxBlades; n++) {
+			CameraRec cam{};
+			cam.lens_radius = 0.5f; cam.focus_distance = 2; cam.blades = n; cam.blade_rotation = 0.1f * n;
+			const std::vector<float> t = lens_table(cam);
+			CHECK(t.size() == 2 * (size_t)(n + 1) && !memcmp(&t[0], &t[2 * n], 8), "aperture table of %u blades", n);
+			for (uint32_t k = 0; k < n; k++) CHECK(std::fabs(std::hypot(t[2 * k], t[2 * k + 1]) - 0.5f) < 1e-6f, "corner %u of %u", k, n);
+		}
+		CHECK(lens_table(CameraRec{}).empty(), "no table without a lens");
 	} catch (const Error& e) {
 		fprintf(stderr, "error %d: %s\n", e.code, e.msg.c_str());
 		return 2;

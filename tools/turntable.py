@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""A turntable of a loaded scene: N frames with the camera orbiting the scene's centre (Scene.set_camera), optionally with one model spinning
+about the vertical axis through its origin (Scene.set_model_xforms). The scene is created once; the time of each setter is printed next to
+the time of creating the scene, which is what a second view cost before the setters existed.
+
+  tools/turntable.py [--scene cornell|jack|atrium|PATH.gltf] [--frames N] [--size WxH] [--spp S] [--bounces B] [--spin MODEL] [--lens R:F[:BLADES[:ROT]]]
+                     [--nee] [--out PREFIX]
+--out PREFIX writes PREFIX_000.png ...; without it the frames are rendered and dropped. The last line is one JSON record."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+ptx = importlib.import_module("distributed-path-tracer_amd")
+proc = importlib.import_module("distributed-path-tracer_amd.procedural")
+SCENES = {"cornell": os.path.join(ROOT, "scenes", "cornell-box", "cornell.gltf"), "jack": os.path.join(ROOT, "scenes", "jack-of-blades", "jack-of-blades.gltf")}
+
+
+def create(ctx, name):
+    if name == "atrium":
+        d = proc.atrium_scene()
+        return ptx.Scene.from_arrays(ctx, d["model_xform"], d["model_surf"], d["surf_range"], d["vertices"], d["triangles"], d["materials"], d["camera"], d.get("sun"))
+    return ptx.Scene.load_gltf(ctx, SCENES.get(name, name))
+
+
+def orbit(origin, basis, centre, angle):
+    """the camera turned by `angle` about the vertical axis through `centre`: origin and basis columns"""
+    c, s = np.cos(angle), np.sin(angle)
+    Ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
+    o = Ry @ (np.asarray(origin, np.float64) - centre) + centre
+    B = Ry @ np.asarray(basis, np.float64).reshape(3, 3).T          # columns x, y, z
+    return o.astype(np.float32), B.T.reshape(-1).astype(np.float32)
+
+
+def spin(xform, model, angle):
+    """model `model` turned by `angle` about the vertical axis through its own origin"""
+    c, s = np.cos(angle), np.sin(angle)
+    Ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
+    x = np.array(xform, np.float32)
+    x[model, 3:12] = (Ry @ x[model, 3:12].astype(np.float64).reshape(3, 3).T).T.reshape(-1).astype(np.float32)
+    return x
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--scene", default="cornell")
+    ap.add_argument("--frames", type=int, default=12)
+    ap.add_argument("--size", default="480x270")
+    ap.add_argument("--spp", type=int, default=16)
+    ap.add_argument("--bounces", type=int, default=4)
+    ap.add_argument("--spin", type=int, default=-1, metavar="MODEL", help="index of a model to spin (default: none)")
+    ap.add_argument("--lens", default=None, metavar="R:F[:BLADES[:ROT]]")
+    ap.add_argument("--nee", action="store_true", help="render with ptx_render_nee (fused form)")
+    ap.add_argument("--out", default=None, metavar="PREFIX")
+    a = ap.parse_args()
+    W, H = (int(v) for v in a.size.split("x"))
+    lens = [float(v) for v in a.lens.split(":")] if a.lens else []
+    if lens and not 2 <= len(lens) <= 4:
+        ap.error("--lens R:F[:BLADES[:ROT]]")
+    lens_kw = dict(zip(("lens_radius", "focus_distance", "blades", "blade_rotation"), lens))
+    if "blades" in lens_kw:
+        lens_kw["blades"] = int(lens_kw["blades"])
+
+    ctx = ptx.Context(0)
+    t0 = time.perf_counter()
+    s = create(ctx, a.scene)
+    ctx.synchronize()
+    create_ms = (time.perf_counter() - t0) * 1e3
+    info = s.info()
+    cam, xform0 = s.camera(), s.array(ptx.ARR_MODEL_XFORM)
+    box = s.array(ptx.ARR_MODEL_AABB).astype(np.float64)
+    corners = []   # world corners of the model boxes: the centre the camera orbits
+    for m, x in enumerate(xform0.astype(np.float64)):
+        B = x[3:12].reshape(3, 3).T
+        for k in range(8):
+            p = np.array([box[m, 3 * ((k >> i) & 1) + i] for i in range(3)])
+            corners.append(B @ p + x[:3])
+    centre = (np.min(corners, 0) + np.max(corners, 0)) / 2
+    print(f"{a.scene}: {info['n_models']} models, {info['n_triangles']} triangles, {info['n_kd_nodes']} KD nodes; created in {create_ms:.1f} ms")
+    cam_ms, xf_ms, render_ms = [], [], []
+    for f in range(a.frames):
+        ang = 2 * np.pi * f / a.frames
+        o, b = orbit(cam["origin"], cam["basis"], centre, ang)
+        t = time.perf_counter()
+        s.set_camera(o, b, cam["yfov"], **lens_kw)
+        cam_ms.append((time.perf_counter() - t) * 1e3)
+        line = f"frame {f:3d}: set_camera {cam_ms[-1]:7.3f} ms"
+        if a.spin >= 0:
+            t = time.perf_counter()
+            s.set_model_xforms(spin(xform0, a.spin, 3 * ang))
+            xf_ms.append((time.perf_counter() - t) * 1e3)
+            line += f", set_model_xforms {xf_ms[-1]:8.3f} ms ({xf_ms[-1] / create_ms * 100:.2f} % of creating the scene)"
+        t = time.perf_counter()
+        acc, _ = (s.render_nee(W, H, a.spp, a.bounces, flags=ptx.NEE_FUSED) if a.nee else s.render(W, H, a.spp, a.bounces))
+        render_ms.append((time.perf_counter() - t) * 1e3)
+        print(line + f", render {render_ms[-1]:8.2f} ms")
+        if a.out:
+            with open(f"{a.out}_{f:03d}.png", "wb") as fh:
+                fh.write(ptx.encode_png(ctx.tonemap_encode(acc, W, H, a.spp)))
+    med = lambda v: float(np.median(v)) if v else None
+    out = dict(scene=a.scene, frames=a.frames, W=W, H=H, spp=a.spp, create_ms=round(create_ms, 3), set_camera_ms=round(med(cam_ms), 4),
+               set_model_xforms_ms=round(med(xf_ms), 3) if xf_ms else None, render_ms=round(med(render_ms), 3),
+               set_model_xforms_share_of_create=round(med(xf_ms) / create_ms, 5) if xf_ms else None)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
