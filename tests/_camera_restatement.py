@@ -1,6 +1,6 @@
 """The camera of include/ptx.h (THE LENS, THE APERTURE TABLE) restated in float32 numpy: the pinhole ray of scene::camera::get_ray, the thin
 lens with its polygonal aperture, and a proxy around an OracleScene whose primary_rays are lens rays, so that the restatements that take
-their camera rays from primary_rays (tests/_aov_restatement.restate, tests/_nee_restatement.render_samples) restate the lens renders as they
+their camera rays from primary_rays (tests/_aov_restatement.restate, tests/_nee_estimator.render_samples) restate the lens renders as they
 are. Not collected (underscore prefix).
 
 Every operation is one float32 operation, in the order the header writes them. tan_half_fov is taken from ARR_CAMERA [13] (std::tan of the

@@ -1,16 +1,30 @@
 """The scenes of tests/test_nee_lights.py — the loads of lit.gltf, the emitter clouds, the chart under an environment map, the glass stacks
 before a listed wall — with their oracles, and the LDS budget that makes one of them a hybrid scene (tests/test_nee_env.py uses the loads
 and the budget too). Not collected (underscore prefix). Oracles and flat arrays are kept here once; product scenes are kept per test module.
+
+Below them, what the modules that set maps on their scenes share (test_nee_env.py, test_nee_sampler_pdf.py, test_nee_ris.py,
+test_nee_punctual_gpu.py, test_nee_restatement_bits.py): the flag values, the `maps` fixture, fresh oracle and product scenes under a map, the
+product's environment table, the variance ratio.
 """
 import os
 
 import numpy as np
+import pytest
 
+import _nee_common
+import _nee_env_restatement as E
 from _checks import _glass_stack
 from _common import _proc
-from conftest import GOLD, oracle_from_dict, product_from_dict
+from conftest import CORNELL, GOLD, oracle_from_dict, product_from_dict
 
 f32 = np.float32
+NO_LIGHTS, FUSED, ENV, SPDF = 1, 4, 16, 64   # PTX_NEE_NO_LIGHT_SAMPLES, PTX_NEE_FUSED, PTX_NEE_ENV_SAMPLES, PTX_NEE_SAMPLER_PDF
+
+
+def CAND(m):
+    return (m - 1) << 8
+
+
 LIT = os.path.join(GOLD, "textures", "lit.gltf")
 SKY = os.path.join(GOLD, "hdr", "sky_rle.hdr")
 NO_SUN = 0xFFFFFFFF
@@ -97,3 +111,73 @@ def _hybrid_budget(ptx, mp, name):
         budget = int(_host_scene(ptx, name).array(ptx.ARR_RES_PLAN)[0]) - 1
         mp.delenv("PTX_LDS_LEAF_ORDER")
     return budget
+
+
+# ---------------------------------------------------------------------------- scenes under a map: fresh ones, since a map is set on them
+@pytest.fixture(scope="module")
+def maps(tmp_path_factory):
+    """name -> (path, srgb). .hdr maps are read linearly: a float sRGB texel goes through powf, ocml's on the device and glibc's in the oracle.
+    Small uncompressed Radiance files written into tmp (a 16 x 8 grey map with one hot texel in the top-left corner, the same with a black
+    background, a uniform map of value 1, a black map), and tests/golden's."""
+    d = tmp_path_factory.mktemp("env_maps")
+    tex = os.path.join(GOLD, "textures")
+    return {"hot": (E.write_hdr(d / "hot.hdr", E.hot_texel()), False), "hot_only": (E.write_hdr(d / "hot_only.hdr", E.hot_texel(base=0.0)), False),
+            "uniform": (E.write_hdr(d / "uniform.hdr", np.full((8, 16, 3), 1.0)), False), "black": (E.write_hdr(d / "black.hdr", np.zeros((4, 8, 3))), False),
+            "sky": (SKY, False), "emit_6x5": (os.path.join(tex, "emit_6x5.hdr"), False), "l1_37x53": (os.path.join(tex, "l1_37x53.png"), True),
+            "pt_1x1": (os.path.join(tex, "pt_1x1.png"), True)}
+
+
+def _any_dict(name):
+    return _dict(name) if name in CLOUDS or name.startswith("glass") else _nee_common._dict(name)
+
+
+def _new_oracle(ora, name, env_map=None):
+    if name == "cornell":
+        o = ora.OracleScene(ora.load_gltf(CORNELL))
+    elif name in LIT_LOADS:
+        sun, work = LIT_LOADS[name]
+        o = ora.OracleScene(ora.load_gltf(LIT, sun_light_index=sun, work=work))
+    else:
+        o = oracle_from_dict(ora, _any_dict(name))
+    if env_map:
+        o.set_environment(env_map[0], srgb=env_map[1])
+    return o
+
+
+def _new_scene(ptx, name, ctx=None, env_map=None):
+    if name == "cornell":
+        s = ptx.Scene.load_gltf(ctx, CORNELL)
+    elif name in LIT_LOADS:
+        sun, work = LIT_LOADS[name]
+        s = ptx.Scene.load_gltf(ctx, LIT, sun_light_index=sun, work=work)
+    else:
+        s = product_from_dict(ptx, ctx, _any_dict(name))
+    if env_map:
+        s.set_environment(env_map[0], srgb=env_map[1])
+    return s
+
+
+def _tables(ptx, s):
+    return s.array(ptx.ARR_ENV_ROW_CDF), s.array(ptx.ARR_ENV_CELL_CDF)
+
+
+def _table(ptx, s):
+    return E.table(*_tables(ptx, s))
+
+
+_under_maps = {}
+
+
+def _oracle_and_table(ptx, ora, maps, name, map_name, flags):
+    """(oracle scene under the map, the environment table if the flags ask for one), kept"""
+    key = (name, map_name, bool(flags & ENV))
+    if key not in _under_maps:
+        o = _new_oracle(ora, name, maps[map_name] if map_name else None)
+        tab = _table(ptx, _new_scene(ptx, name, env_map=maps[map_name])) if flags & ENV else None
+        _under_maps[key] = (o, tab)
+    return _under_maps[key]
+
+
+def _variance_ratio(flagged, unflagged):
+    """mean over pixels and channels of the per-pixel sample variance, flagged / unflagged; rad [h, w, spp, 3]"""
+    return float(flagged.var(2, ddof=1, dtype=np.float64).mean() / unflagged.var(2, ddof=1, dtype=np.float64).mean())

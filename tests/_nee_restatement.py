@@ -1,18 +1,12 @@
-"""numpy float32 wavefront restatement of ptx_render_nee's estimator and light list (include/ptx.h), for tests/test_nee.py.
+"""What tests/_nee_estimator.py's vertex is built from, in numpy float32: the float32 helpers (oracle/pt_oracle.cpp:44-72), the Philox draws,
+the light list (include/ptx.h: THE LIGHT LIST), the attributes of a point of a triangle (renderer.cpp:688-715), the material and closest-hit
+batches over the oracle, and the BRDF / PDF combination of renderer::trace (renderer.cpp:521-556, 579-606). Not collected (underscore prefix).
 
 Built on the oracle's batch primitives only: OracleScene.intersect (closest hit: position, uv, shading normal, surface),
 OracleScene.model_intersect (the same hit's triangle index and distance: the closest hit inside the model of the surface that
-OracleScene.intersect reported is that hit), material_eval, primary_rays, pt_oracle.pbr (importance samples, pdfs, Fresnel: every call
-that goes through libm), pt_oracle.philox and the scene arrays. Everything else is written out here on np.float32 arrays in the
-operation order of the specification (numpy neither contracts nor reorders).
-
-Switches: lights=False runs with an empty list (LIB itself), mis=False sets every weight to 1 (double counting), light_term=False
-drops the light term but keeps the weights (energy lost). fold="recursive" (lights=False only) adds a path's vertices back to front
-as renderer::trace returns them, which is what OracleScene.render_samples computes bit for bit; fold="throughput" is the product's
-order: vertex k's emission, its sun term, its light term, then vertex k + 1.
-
-A miss adds T * env; when the oracle scene has an environment map (OracleScene.set_environment), env is OracleScene.env_lookup of the
-ray's direction times the factor, per ray (renderer.cpp:443-449).
+OracleScene.intersect reported is that hit), material_eval, pt_oracle.pbr (importance samples, pdfs, Fresnel: every call that goes through
+libm), pt_oracle.philox and the scene arrays. Everything else is written out here on np.float32 arrays in the operation order of the
+specification (numpy neither contracts nor reorders).
 """
 import numpy as np
 
@@ -207,214 +201,3 @@ def _eval_brdf(ora, n, outc, inc, albedo, rough, metallic, spec_prob, ior):
         brdf = _lerp(dbrdf, spdf[:, None], fr)
         pdf = _lerp(dpdf, spdf, spec_prob)
     return brdf.astype(f32), pdf.astype(f32)
-
-
-# ---------------------------------------------------------------------------- the estimator
-def render_samples(ora, o, a, W, H, spp, bounces, seed=0x5EED, env=(1.0, 1.0, 1.0), tile=None, sample0=0, lights=True, mis=True,
-                   light_term=True, fold="throughput", light_draws=None):
-    """-> dict(rad [h, w, spp, 3] float32 per-sample radiance, v1_listed [h, w, spp] bool: the sample's vertex at depth 1 lies on a listed
-    triangle, light_samples, light_visible, rays). light_draws: None, or a list that receives, per round, the Philox keys (pixel, sample,
-    depth, pass: uint32 [n, 4]) of the vertices that drew a light sample, accepted or not."""
-    assert fold in ("throughput", "recursive") and (fold == "throughput" or not lights)
-    x0, y0, w, h = tile if tile else (0, 0, W, H)
-    npix, N = w * h, w * h * spp
-    env = np.asarray(env, f32)
-    env_map = getattr(o, "_env", None) is not None
-    attr = _Attr(a)
-    model_of = attr.model_of
-    mats = np.asarray(a.materials, f32)
-    ll = light_list(a) if lights else dict(tris=np.zeros((0, 2), np.uint32), cdf=np.zeros(0, f32), geom=np.zeros((0, 4), f32), area=f32(0),
-                                           surf_first=np.full(len(mats), -1, np.int32))
-    n_l = len(ll["cdf"])
-    light_key = ll["tris"][:, 0].astype(np.int64) << 32 | ll["tris"][:, 1].astype(np.int64)
-    has_sun = a.sun is not None
-    # state by sample id = s * npix + p
-    O, D = np.zeros((N, 3), f32), np.zeros((N, 3), f32)
-    for s in range(spp):
-        r = o.primary_rays(ora.make_cfg(W, H, 1, 1, seed=seed, tile=(x0, y0, w, h)), sample0 + s).reshape(-1, 6)
-        O[s * npix:(s + 1) * npix], D[s * npix:(s + 1) * npix] = r[:, :3], r[:, 3:]
-    p_local = np.tile(np.arange(npix), spp)
-    pixel = ((y0 + p_local // w) * W + (x0 + p_local % w)).astype(np.uint32)
-    sample = (sample0 + np.repeat(np.arange(spp), npix)).astype(np.uint32)
-    T, L = np.ones((N, 3), f32), np.zeros((N, 3), f32)
-    PP = np.zeros(N, f32)
-    depth, pas = np.zeros(N, np.int64), np.zeros(N, np.int64)
-    v1_listed = np.zeros(N, bool)
-    live = np.arange(N) if bounces > 0 else np.zeros(0, np.int64)
-    rec = []   # per round, for the recursive fold
-    stats = dict(light_samples=0, light_visible=0, rays=0)
-
-    def listed(surf, tri):
-        if n_l == 0:
-            return np.full(len(surf), -1, np.int64)
-        key = surf.astype(np.int64) << 32 | tri.astype(np.int64)
-        k = np.minimum(np.searchsorted(light_key, key), n_l - 1)
-        return np.where(light_key[k] == key, k, -1)
-
-    while len(live):
-        out, surf, tri, dist = _closest(o, model_of, np.concatenate([O[live], D[live]], 1))
-        stats["rays"] += len(live)
-        nxt = np.zeros(len(live), bool)
-        R = dict(ids=live, kind=np.zeros(len(live), np.int8), e=np.zeros((len(live), 3), f32), dsun=np.zeros((len(live), 3), f32), env=env,
-                 brdf=np.zeros((len(live), 3), f32), pe=np.ones(len(live), f32), cont=np.zeros(len(live), bool))   # kind 0 zero, 1 miss, 2 pass, 3 vertex
-        rec.append(R)
-        miss = surf < 0
-        if env_map and miss.any():
-            R["env"] = np.zeros((len(live), 3), f32)
-            R["env"][miss] = o.env_lookup(D[live[miss]], env)[2]
-            L[live[miss]] = L[live[miss]] + T[live[miss]] * R["env"][miss]
-        else:
-            L[live[miss]] = L[live[miss]] + T[live[miss]] * env
-        R["kind"][miss] = 1
-        hi = np.flatnonzero(~miss)          # positions within `live`
-        if len(hi):
-            g = live[hi]
-            pos, uv, sn = out[hi, 0:3], out[hi, 3:5], out[hi, 11:14]
-            sf, tr, di = surf[hi], tri[hi], dist[hi]
-            me = _material(o, sf, uv)
-            albedo, opacity, rough, metallic, e10 = me[:, 3:6], me[:, 6], me[:, 7], me[:, 8], me[:, 9:12] * f32(10)
-            ior, catcher_m = mats[sf, 9], mats[sf, 10] != 0
-            d = D[g]
-            dep, pa = depth[g], pas[g]
-            k_l = listed(sf, tr)
-            v1_listed[g[(dep == 1) & (k_l >= 0)]] = True
-            last = dep + 1 == bounces
-            rnd = draws(ora, pixel[g], sample[g], dep, pa, BLOCK_SURFACE, seed)
-            approx1 = (opacity == f32(1)) | (np.abs(opacity - f32(1)) < EPS)
-            through = ~approx1 & (rnd[:, 0] > opacity)
-            normal, outc = sn, -d
-            back = ~through & (_dot(normal, outc) <= 0)
-            act = ~through & ~back                                   # vertices that shade
-            rough = _fmax2(rough, f32(0.05))
-            pb = _pbr(ora, normal, outc, normal, rnd[:, 2], rnd[:, 3], rough, 1, ior)
-            spec_prob = _fmax2(pb[:, 11], metallic)
-            # ---- sun
-            sun_add = np.zeros((len(g), 3), f32)
-            sun_raw = np.zeros((len(g), 3), f32)
-            pending_dead, add = np.zeros(len(g), bool), np.zeros(len(g), bool)
-            if has_sun:
-                sun = np.asarray(a.sun, f32)
-                sr = draws(ora, pixel[g], sample[g], dep, pa, BLOCK_SUN, seed)
-                c0 = _mulmv((sun[0:3][None], sun[3:6][None], sun[6:9][None]), np.array([[0, 0, 1]], f32))
-                ct = np.cos((sr[:, 1] * sun[12]).astype(np.float64)).astype(f32)
-                c = _pbr(ora, np.repeat(c0, len(g), 0), outc, outc, 0, sr[:, 0], rough, ct, ior)[:, 0:3]
-                sampled = act & (_dot(normal, c) > 0)
-                si = np.flatnonzero(sampled)
-                occl = np.zeros(len(g), bool)
-                if len(si):
-                    _, ssurf = o.intersect(np.concatenate([pos[si] + c[si] * EPS, _normalize(c[si])], 1))
-                    stats["rays"] += len(si)
-                    occl[si] = ssurf >= 0
-                catcher = catcher_m & (dep == 0)
-                lit_catcher = sampled & catcher & ~occl
-                pending_dead = sampled & catcher & occl
-                through = through | lit_catcher
-                add = sampled & ~catcher & ~occl
-                if add.any():
-                    brdf, _ = _eval_brdf(ora, normal[add], outc[add], c[add], albedo[add], rough[add], metallic[add], spec_prob[add], ior[add])
-                    e = sun[9:12]
-                    pdf = _lerp(f32(1), f32(1), spec_prob[add])
-                    v = brdf * e / _fmax2(pdf, EPS)[:, None]
-                    sun_raw[add] = _clamp(v, f32(0), e)
-                    sun_add[add] = T[g[add]] * sun_raw[add]
-                act = act & ~lit_catcher & ~pending_dead
-            # ---- pass-through (opacity, or a lit catcher): same depth, pass + 1
-            ti = np.flatnonzero(through)
-            O[g[ti]] = pos[ti] + d[ti] * EPS
-            D[g[ti]] = _normalize(d[ti])
-            pas[g[ti]] = pa[ti] + 1
-            nxt[hi[ti]] = pas[g[ti]] <= 4096
-            R["kind"][hi[ti]] = 2
-            # ---- emission, sun
-            ai = np.flatnonzero(act)
-            ga = g[ai]
-            em = T[ga] * e10[ai]
-            wsel = (k_l[ai] >= 0) & (dep[ai] != 0) & (pa[ai] == 0)
-            if wsel.any() and mis:
-                kk = k_l[ai][wsel]
-                cg = np.abs(_dot(ll["geom"][kk, 0:3], d[ai][wsel]))
-                with np.errstate(all="ignore"):
-                    p_l = (di[ai][wsel] * di[ai][wsel]) / (cg * ll["area"])
-                    wgt = PP[ga[wsel]] / (PP[ga[wsel]] + p_l)
-                em[wsel] = em[wsel] * wgt[:, None]
-            L[ga] = L[ga] + em
-            sa = np.flatnonzero(add)
-            L[g[sa]] = L[g[sa]] + sun_add[sa]
-            R["kind"][hi[ai]] = 3
-            R["e"][hi[ai]] = e10[ai]
-            R["dsun"][hi[ai]] = sun_raw[ai]
-            # ---- the vertices that sample a direction
-            ci = ai[~last[ai]]
-            gc = g[ci]
-            if n_l and len(ci):
-                r = draws(ora, pixel[gc], sample[gc], dep[ci], pa[ci], BLOCK_LIGHT, seed)
-                if light_draws is not None:
-                    light_draws.append(np.stack([pixel[gc], sample[gc], dep[ci], pa[ci]], -1).astype(np.uint32))
-                k = np.minimum(np.searchsorted(ll["cdf"], r[:, 0], side="right"), n_l - 1)
-                su = np.sqrt(r[:, 1])
-                beta, gamma = su * (f32(1) - r[:, 2]), su * r[:, 2]
-                ls, lt = ll["tris"][k, 0].astype(np.int64), ll["tris"][k, 1].astype(np.int64)
-                ypos, yuv, ynrm, ytan = attr.at(ls, lt, beta, gamma)
-                my = _material(o, ls, yuv)
-                n_y, Le = _shading_normal(ynrm, ytan, my[:, 0:3]), my[:, 9:12] * f32(10)
-                v = ypos - pos[ci]
-                dist2 = _dot(v, v)
-                with np.errstate(all="ignore"):
-                    wdir = v / np.sqrt(dist2)[:, None]
-                    cg = np.abs(_dot(ll["geom"][k, 0:3], wdir))
-                    ok = (dist2 > 0) & (_dot(normal[ci], wdir) > 0) & (_dot(n_y, -wdir) > 0) & (cg > 0) & (_fmax2(Le[:, 0], _fmax2(Le[:, 1], Le[:, 2])) > 0)
-                oi = np.flatnonzero(ok)
-                if len(oi):
-                    c2 = ci[oi]
-                    brdf, pdf = _eval_brdf(ora, normal[c2], outc[c2], wdir[oi], albedo[c2], rough[c2], metallic[c2], spec_prob[c2], ior[c2])
-                    pe = _fmax2(pdf, EPS)
-                    qc = _clamp(brdf / pe[:, None], f32(0), f32(1))
-                    p_l = dist2[oi] / (cg[oi] * ll["area"])
-                    wl = pe / (pe + p_l) if mis else np.ones(len(oi), f32)
-                    x = ((T[g[c2]] * qc) * wl[:, None]) * Le[oi]
-                    _, hs, ht, _ = _closest(o, model_of, np.concatenate([pos[c2] + wdir[oi] * EPS, wdir[oi]], 1))
-                    stats["rays"] += len(oi)
-                    vis = (hs == ls[oi]) & (ht == lt[oi])
-                    stats["light_samples"] += len(oi)
-                    stats["light_visible"] += int(vis.sum())
-                    if light_term:
-                        L[g[c2[vis]]] = L[g[c2[vis]]] + x[vis]
-            if len(ci):
-                spec = rnd[ci, 1] < spec_prob[ci]
-                inc = np.where(spec[:, None], pb[ci, 6:9], pb[ci, 3:6])
-                ok = _dot(normal[ci], inc) > 0
-                oi = np.flatnonzero(ok)
-                c2 = ci[oi]
-                brdf, pdf = _eval_brdf(ora, normal[c2], outc[c2], inc[oi], albedo[c2], rough[c2], metallic[c2], spec_prob[c2], ior[c2])
-                pe = _fmax2(pdf, EPS)
-                with np.errstate(all="ignore"):
-                    q = brdf / pe[:, None]
-                T[g[c2]] = T[g[c2]] * _clamp(q, f32(0), f32(1))
-                PP[g[c2]] = pe
-                O[g[c2]] = pos[c2] + inc[oi] * EPS
-                D[g[c2]] = _normalize(inc[oi])
-                depth[g[c2]] = dep[c2] + 1
-                pas[g[c2]] = 0
-                nxt[hi[c2]] = depth[g[c2]] != bounces
-                R["cont"][hi[c2]] = True
-                R["brdf"][hi[c2]] = brdf
-                R["pe"][hi[c2]] = pe
-        live = live[nxt]
-
-    if fold == "recursive":
-        val = np.zeros((N, 3), f32)
-        for R in reversed(rec):
-            ids, kind = R["ids"], R["kind"]
-            val[ids[kind == 0]] = 0
-            val[ids[kind == 1]] = R["env"] if R["env"].ndim == 1 else R["env"][kind == 1]
-            v = kind == 3
-            iv = ids[v]
-            inn = val[iv]
-            with np.errstate(all="ignore"):
-                ind = _clamp((R["brdf"][v] * inn) / R["pe"][v][:, None], f32(0), inn)
-            ind = np.where(R["cont"][v][:, None], ind, f32(0)).astype(f32)
-            val[iv] = (R["dsun"][v] + ind) + R["e"][v]
-        L = val
-    res = dict(rad=L.reshape(spp, h, w, 3).transpose(1, 2, 0, 3).copy(), v1_listed=v1_listed.reshape(spp, h, w).transpose(1, 2, 0).copy())
-    res.update(stats)
-    return res

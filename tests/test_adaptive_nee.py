@@ -19,9 +19,9 @@ import pytest
 
 import _adaptive_restatement as AR
 import _denoise_counts_restatement as DR
-import _nee_restatement as NR
 from _common import _bits, _proc, _same
 from _nee_common import SAME_STATS, _host_scene, _oracle
+from _nee_estimator import render_samples
 from _routes import Route, Scenes, assert_route, clean_env, ctx, use_route  # noqa: F401  (clean_env and ctx are fixtures)
 from conftest import CORNELL, GOLD, ROOT, product_from_dict
 
@@ -105,11 +105,11 @@ _sim = {}
 
 
 def _cornell_samples(ora):
-    """tests/_nee_restatement.py's per-sample radiance of Cornell, samples 0 .. 39: [SH, SW, 40, 3]. Never modified."""
+    """tests/_nee_estimator.py's per-sample radiance of Cornell, samples 0 .. 39: [SH, SW, 40, 3]. Never modified."""
     if "samples" not in _sim:
         o, a = _oracle(ora, "cornell")
         t0 = time.time()
-        s = NR.render_samples(ora, o, a, SW, SH, CAP, B, seed=SEED)["rad"]
+        s = render_samples(ora, o, a, SW, SH, CAP, B, seed=SEED)["rad"]
         print(f"restated samples of Cornell {SW} x {SH} x {CAP}: {time.time() - t0:.1f} s")
         s.setflags(write=False)
         _sim["samples"] = s
@@ -168,7 +168,7 @@ def test_simulation_on_the_restated_cornell(ora):
     # the adaptive frame and the uniform one at the next even count above its mean, against the restated 64-sample frame of another seed:
     # a reference this short carries noise of its own, so the two figures are printed for DESIGN.md and nothing is asserted on them
     o, arr = _oracle(ora, "cornell")
-    ref = NR.render_samples(ora, o, arr, SW, SH, 64, B, seed=77)["rad"].mean(2, dtype=np.float64).astype(f32)
+    ref = render_samples(ora, o, arr, SW, SH, 64, B, seed=77)["rad"].mean(2, dtype=np.float64).astype(f32)
     n_uniform = 2 * int(counts.mean() // 2) + 2
     uni = np.zeros((SH, SW, 4), f32)
     _add(uni, samples, 0, n_uniform)

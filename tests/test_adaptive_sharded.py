@@ -21,9 +21,9 @@ import pytest
 
 import _adaptive_restatement as AR
 import _adaptive_shard_restatement as SR
-import _nee_restatement as NR
 from _common import _bits, _proc, _same
 from _nee_common import _oracle
+from _nee_estimator import render_samples
 from _routes import Route, Scenes, assert_route, clean_env, ctx, use_route  # noqa: F401  (clean_env and ctx are fixtures)
 from conftest import CORNELL, oracle_from_dict, product_from_dict
 
@@ -111,7 +111,7 @@ def _oracle_samples(ora, c):
     if key not in _sim:
         if c.nee:
             o, a = _oracle(ora, c.scene)
-            s = NR.render_samples(ora, o, a, c.W, c.H, c.cap, B, seed=SEED)["rad"]
+            s = render_samples(ora, o, a, c.W, c.H, c.cap, B, seed=SEED)["rad"]
         else:
             if ("scene", c.scene) not in _sim:
                 _sim["scene", c.scene] = oracle_from_dict(ora, _scene_dict(c.scene))

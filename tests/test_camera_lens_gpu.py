@@ -19,11 +19,11 @@ import numpy as np
 import pytest
 
 import _adaptive_restatement as AR
-import _nee_restatement as R
 from _aov_restatement import restate
 from _camera_restatement import Camera, LensOracle, moved_xforms
 from _common import _bits, _proc, _same
 from _nee_common import SEED, _err
+from _nee_estimator import render_samples
 from _nee_lit_scenes import LIT
 from _routes import (DEFAULT_ROUTES, ROUTE_VARS, Scenes, assert_route, clean_env, ctx, forced_routes, on_route, route_named,  # noqa: F401
                      under_force_global, use_route)
@@ -179,7 +179,7 @@ def _rad_ref(ptx, ora, name, s, which, lights):
     key = (name, which, lights)
     if key not in _rad_refs:
         proxy, a = _proxy(ptx, ora, name, s, _lens(ora, name, s.array(ptx.ARR_CAMERA), which))
-        _rad_refs[key] = R.render_samples(ora, proxy, a, RW, RH, RSPP, RB, seed=SEED, lights=lights)["rad"]
+        _rad_refs[key] = render_samples(ora, proxy, a, RW, RH, RSPP, RB, seed=SEED, lights=lights)["rad"]
     return _rad_refs[key]
 
 

@@ -1,9 +1,9 @@
 """ptx_render_nee: next-event estimation towards emissive triangles, MIS-weighted (include/ptx.h has the estimator).
 
-The yardstick is tests/_nee_restatement.py, a numpy float32 restatement of the estimator and the light list on the oracle's batch
-primitives. Without a GPU: the restatement with an empty list IS the pinned oracle (bit for bit, so the restated vertex is pinned before
+The yardstick is tests/_nee_estimator.py with tests/_nee_restatement.py, a numpy float32 restatement of the estimator and the light list on
+the oracle's batch primitives. Without a GPU: the restatement with an empty list IS the pinned oracle (bit for bit, so the restated vertex is pinned before
 anything is built on it), the light list's rules and arrays, the estimator's expectation against LIB's with a batch statistic that is
-shown to catch both double counting (mis=False) and lost energy (light_term=False), the variance gain on Cornell, the refusals.
+shown to catch both double counting (no_mis) and lost energy (no_light_term), the variance gain on Cornell, the refusals.
 On the GPU: an empty list gives ptx_render's bytes on every route, the arrays and the first light sample are the restatement's bit for
 bit, per-sample radiance meets test_gpu_parity's bar, tiles / sample ranges / passes / host and device buffers / shards / a forced pool
 overflow compose bitwise, product against product has the same expectation, and the mirrors give the C call's bytes.
@@ -21,6 +21,7 @@ import pytest
 import _nee_restatement as R
 from _common import _bits
 from _nee_common import K_BATCH, SEED, _batch_stat, _check_list, _dict, _err, _host_scene, _make, _oracle, _same_expectation
+from _nee_estimator import render_samples
 from _routes import Scenes, clean_env, ctx, each_route, under_force_global  # noqa: F401  (clean_env and ctx are fixtures)
 from conftest import CORNELL, ROOT
 
@@ -31,10 +32,10 @@ from conftest import CORNELL, ROOT
 def test_restatement_without_lights_is_the_pinned_oracle(ora, name, W, H, bounces):
     o, a = _oracle(ora, name)
     ref = o.render_samples(ora.make_cfg(W, H, 3, bounces, seed=SEED), threads=0)
-    got = R.render_samples(ora, o, a, W, H, 3, bounces, seed=SEED, lights=False, fold="recursive")["rad"]
+    got = render_samples(ora, o, a, W, H, 3, bounces, seed=SEED, lights=False, fold="recursive")["rad"]
     np.testing.assert_array_equal(_bits(got), _bits(ref))
     # the product's order of additions gives the same radiance to rounding
-    thr = R.render_samples(ora, o, a, W, H, 3, bounces, seed=SEED, lights=False)["rad"]
+    thr = render_samples(ora, o, a, W, H, 3, bounces, seed=SEED, lights=False)["rad"]
     assert np.abs(thr - ref).max() <= 1e-5 * max(1.0, float(np.abs(ref).max()))
 
 
@@ -92,22 +93,22 @@ def test_same_expectation_as_lib(ora, name, W, H):
     lib = _lib_batches(ora, name, W, H, 4)
 
     def nee(**kw):
-        return _batch_stat(np.stack([R.render_samples(ora, o, a, W, H, 16, 4, seed=0xA000 + k, **kw)["rad"].mean(2) for k in range(K_BATCH)]))
+        return _batch_stat(np.stack([render_samples(ora, o, a, W, H, 16, 4, seed=0xA000 + k, **kw)["rad"].mean(2) for k in range(K_BATCH)]))
     ok, zf, zq = _same_expectation(nee(), lib)
     print(f"{name}: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert ok, (zf, zq)
-    bad, zf, zq = _same_expectation(nee(mis=False), lib)          # double counting must be caught
-    print(f"{name} mis=False: worst z frame {zf:.2f} quadrant {zq:.2f}")
+    bad, zf, zq = _same_expectation(nee(wrong=("no_mis",)), lib)          # double counting must be caught
+    print(f"{name} no_mis: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert not bad
-    bad, zf, zq = _same_expectation(nee(light_term=False), lib)   # lost energy must be caught
-    print(f"{name} light_term=False: worst z frame {zf:.2f} quadrant {zq:.2f}")
+    bad, zf, zq = _same_expectation(nee(wrong=("no_light_term",)), lib)   # lost energy must be caught
+    print(f"{name} no_light_term: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert not bad
 
 
 def test_it_helps_on_cornell(ora):
     o, a = _oracle(ora, "cornell")
     ref = o.render_samples(ora.make_cfg(32, 32, 4096, 4, seed=99), threads=0).mean(2, dtype=np.float64)
-    e_nee = ((R.render_samples(ora, o, a, 32, 32, 16, 4, seed=7)["rad"].mean(2, dtype=np.float64) - ref) ** 2).mean()
+    e_nee = ((render_samples(ora, o, a, 32, 32, 16, 4, seed=7)["rad"].mean(2, dtype=np.float64) - ref) ** 2).mean()
     e_lib = ((o.render_samples(ora.make_cfg(32, 32, 16, 4, seed=7), threads=0).mean(2, dtype=np.float64) - ref) ** 2).mean()
     print(f"mean squared error: LIB {e_lib:.5f} NEE {e_nee:.5f} ratio {e_lib / e_nee:.2f}")
     assert e_nee < e_lib
@@ -115,7 +116,7 @@ def test_it_helps_on_cornell(ora):
 
 def test_share_of_bitwise_comparable_samples(ora):
     o, a = _oracle(ora, "cornell")
-    r = R.render_samples(ora, o, a, 32, 24, 4, 2, seed=SEED)
+    r = render_samples(ora, o, a, 32, 24, 4, 2, seed=SEED)
     share = 1 - r["v1_listed"].mean()
     print(f"share of samples whose vertex 1 is not on a listed emitter: {share:.4f}")
     assert share >= 0.5 and r["light_visible"] <= r["light_samples"] and r["light_visible"] > 0
@@ -201,7 +202,7 @@ def test_first_light_sample_bitwise(ptx, ctx, ora, clean_env, name, W, H):
     trigonometry on that path. The environment is black, so that a vertex-1 miss of the open chart adds T * 0 (T carries the sampled
     direction's last bits); the chart without alpha has no unlisted emitter."""
     o, a = _oracle(ora, name)
-    ref = R.render_samples(ora, o, a, W, H, 4, 2, seed=SEED, env=(0.0, 0.0, 0.0))
+    ref = render_samples(ora, o, a, W, H, 4, 2, seed=SEED, env=(0.0, 0.0, 0.0))
     s = _product(ptx, ctx, clean_env, name)
     got, tot = _gpu_samples(s, W, H, 4, 2, env=(0.0, 0.0, 0.0))
     sel = ~ref["v1_listed"]
@@ -219,7 +220,7 @@ def test_first_light_sample_bitwise(ptx, ctx, ora, clean_env, name, W, H):
 def test_per_sample_radiance_against_the_restatement(ptx, ctx, ora, clean_env, name, W, H, tile):
     """test_gpu_parity's bar for ptx_render: all samples finite and >= 0, >= 99.5 % within 1e-3 relative (floor 1e-3)."""
     o, a = _oracle(ora, name)
-    ref = R.render_samples(ora, o, a, W, H, 2, 4, seed=SEED, tile=tile)
+    ref = render_samples(ora, o, a, W, H, 2, 4, seed=SEED, tile=tile)
     s = _product(ptx, ctx, clean_env, name)
     h, w = (tile[3], tile[2]) if tile else (H, W)
     got = np.zeros((h, w, 2, 3), np.float32)

@@ -1,9 +1,9 @@
 """PTX_NEE_ENV_SAMPLES: ptx_render_nee's light sample may go towards the environment map, MIS-weighted (include/ptx.h has the table, the pdf and
 the estimator's changes; csrc/nee_core.hpp the vertex, csrc/ptx_api.cpp build_env_table).
 
-The yardstick is tests/_nee_env_restatement.py: the table rebuilt with numpy from the texels, and the flagged estimator restated on
-tests/_nee_restatement.py's vertex with (u, v) and Le from the oracle's env_lookup. Maps: tests/golden's, and small uncompressed Radiance
-files written into tmp (a 16 x 8 grey map with one hot texel in the top-left corner, the same with a black background, a black map).
+The yardstick is tests/_nee_env_restatement.py, the table rebuilt with numpy from the texels, and tests/_nee_estimator.py, the flagged estimator
+(tab) with (u, v) and Le from the oracle's env_lookup. Maps: _nee_lit_scenes' (tests/golden's, and small uncompressed Radiance files written
+into tmp).
 
 Without a GPU: the flag's value, the tables of host-only scenes, their structure and life cycle, the pdf's self-consistency, the
 expectation and the variance on the restatement.
@@ -22,70 +22,17 @@ import numpy as np
 import pytest
 
 import _nee_env_restatement as E
-from _common import _bits, _proc
+from _common import _bits
 from _nee_common import K_BATCH, SAME_STATS, SEED, _batch_stat, _err, _pair, _same_expectation
-from _nee_lit_scenes import LIT, LIT_LOADS, _hybrid_budget
+from _nee_estimator import render_samples
+from _nee_lit_scenes import ENV, LIT, SKY, _hybrid_budget, _new_oracle, _new_scene, _tables, _variance_ratio
+from _nee_lit_scenes import maps  # noqa: F401  (fixture)
 from _routes import clean_env, ctx  # noqa: F401  (fixtures)
 from _routes import DEFAULT_ROUTES, ROUTE_VARS, Scenes, on_route, route_named
-from conftest import CORNELL, GOLD, ROOT, oracle_from_dict, product_from_dict
+from conftest import ROOT
 
 f32 = np.float32
-ENV = 16
-SKY = os.path.join(GOLD, "hdr", "sky_rle.hdr")
-EMIT_6X5 = os.path.join(GOLD, "textures", "emit_6x5.hdr")
-L1_37X53 = os.path.join(GOLD, "textures", "l1_37x53.png")
-PT_1X1 = os.path.join(GOLD, "textures", "pt_1x1.png")
 MEASURED_BOX_REJECTS = 5.0e-5   # test_pdf_is_self_consistent prints the share; the sliver of (u, v) is about 3e-4 of the domain
-
-
-@pytest.fixture(scope="module")
-def maps(tmp_path_factory):
-    """name -> (path, srgb). .hdr maps are read linearly: a float sRGB texel goes through powf, ocml's on the device and glibc's in the oracle."""
-    d = tmp_path_factory.mktemp("env_maps")
-    return {"hot": (E.write_hdr(d / "hot.hdr", E.hot_texel()), False), "hot_only": (E.write_hdr(d / "hot_only.hdr", E.hot_texel(base=0.0)), False),
-            "black": (E.write_hdr(d / "black.hdr", np.zeros((4, 8, 3))), False), "sky": (SKY, False), "emit_6x5": (EMIT_6X5, False),
-            "l1_37x53": (L1_37X53, True), "pt_1x1": (PT_1X1, True)}
-
-
-# ---------------------------------------------------------------------------- scenes: this module's own (it sets maps on them)
-_dicts = {}
-_MAKERS = {"chart": lambda p: p.chart_scene(facing=True, alpha=False), "chart_sun": lambda p: p.chart_scene(facing=True, sun=0.5)}
-
-
-def _dict(name):
-    if name not in _dicts:
-        _dicts[name] = _MAKERS[name](_proc())
-    return _dicts[name]
-
-
-def _new_oracle(ora, name, env_map):
-    if name == "cornell":
-        o = ora.OracleScene(ora.load_gltf(CORNELL))
-    elif name in LIT_LOADS:
-        sun, work = LIT_LOADS[name]
-        o = ora.OracleScene(ora.load_gltf(LIT, sun_light_index=sun, work=work))
-    else:
-        o = oracle_from_dict(ora, _dict(name))
-    if env_map:
-        o.set_environment(env_map[0], srgb=env_map[1])
-    return o
-
-
-def _new_scene(ptx, name, ctx=None, env_map=None):
-    if name == "cornell":
-        s = ptx.Scene.load_gltf(ctx, CORNELL)
-    elif name in LIT_LOADS:
-        sun, work = LIT_LOADS[name]
-        s = ptx.Scene.load_gltf(ctx, LIT, sun_light_index=sun, work=work)
-    else:
-        s = product_from_dict(ptx, ctx, _dict(name))
-    if env_map:
-        s.set_environment(env_map[0], srgb=env_map[1])
-    return s
-
-
-def _tables(ptx, s):
-    return s.array(ptx.ARR_ENV_ROW_CDF), s.array(ptx.ARR_ENV_CELL_CDF)
 
 
 # ---------------------------------------------------------------------------- no GPU
@@ -167,16 +114,11 @@ def test_pdf_is_self_consistent(ptx, ora, maps):
     assert (E.env_pdf(tab, wdir, fuv)[(fi == i) & (fj == j)] > 0).all()   # what the sampler produces has a positive pdf
 
 
-def _variance_ratio(flagged, unflagged):
-    """mean over pixels and channels of the per-pixel sample variance, flagged / unflagged; rad [h, w, spp, 3]"""
-    return float(flagged.var(2, ddof=1, dtype=np.float64).mean() / unflagged.var(2, ddof=1, dtype=np.float64).mean())
-
-
 def test_expectation_and_variance_on_the_restatement(ptx, ora, maps):
     """The open chart scene (12 listed triangles: both strategies exist, c_env = 0.5) under the hot-texel map: the flagged per-pixel mean
     agrees with the unflagged one by test_nee's batch statistic (16 batches of 16 spp: |z| <= 4 on the frame, 5 on the quadrants).
-    Shown once, and asserted here: with wm = 1 (miss_weight=False) the statistic fails, worst z 11.2 / 6.6; with every weight computed for
-    c_env = 1 (use_c_env=False) it fails, worst z 2.9 / 6.6.
+    Shown once, and asserted here: with wm = 1 (no_miss_weight) the statistic fails, worst z 11.2 / 6.6; with every weight computed for
+    c_env = 1 (c_env_one) it fails, worst z 2.9 / 6.6.
     What the statistic does not resolve at this size: the specular lobe's pdf that LIB's vertex computes is not the density of LIB's
     specular sampler (E[cos / pdf] over its samples is 2.9 - 62 instead of pi for roughness 0.2 - 0.05), so any MIS weight built on it,
     this one and the triangle list's alike, moves the mean where glossy vertices see the light: 64 batches of 64 spp put the flagged
@@ -188,19 +130,19 @@ def test_expectation_and_variance_on_the_restatement(ptx, ora, maps):
     tab = E.table(*_tables(ptx, s))
 
     def batches(seed0, tab, **kw):
-        return _batch_stat(np.stack([E.render_samples(ora, o, o.a, W, H, 16, b, tab, seed=seed0 + k, **kw)["rad"].mean(2) for k in range(K_BATCH)]))
+        return _batch_stat(np.stack([render_samples(ora, o, o.a, W, H, 16, b, tab=tab, seed=seed0 + k, **kw)["rad"].mean(2) for k in range(K_BATCH)]))
     unflagged = batches(0xB000, None)
     ok, zf, zq = _same_expectation(batches(0xA000, tab), unflagged)
     print(f"flagged against unflagged: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert ok, (zf, zq)
-    bad, zf, zq = _same_expectation(batches(0xA000, tab, miss_weight=False), unflagged)
+    bad, zf, zq = _same_expectation(batches(0xA000, tab, wrong=("no_miss_weight",)), unflagged)
     print(f"wm = 1: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert not bad
-    bad, zf, zq = _same_expectation(batches(0xA000, tab, use_c_env=False), unflagged)
+    bad, zf, zq = _same_expectation(batches(0xA000, tab, wrong=("c_env_one",)), unflagged)
     print(f"weights with c_env = 1: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert not bad
     spp, seed = E.VARIANCE_CASE["spp"], E.VARIANCE_CASE["seed"]
-    r0 = _variance_ratio(E.render_samples(ora, o, o.a, W, H, spp, b, tab, seed=seed)["rad"], E.render_samples(ora, o, o.a, W, H, spp, b, None, seed=seed)["rad"])
+    r0 = _variance_ratio(render_samples(ora, o, o.a, W, H, spp, b, tab=tab, seed=seed)["rad"], render_samples(ora, o, o.a, W, H, spp, b, seed=seed)["rad"])
     print(f"per-sample variance flagged / unflagged: r0 = {r0:.4f}")
     assert r0 < 1 and abs(r0 / E.R0 - 1) < 0.02   # E.R0 is this figure, written down for the GPU test
 
@@ -256,7 +198,7 @@ def test_per_sample_radiance_against_the_restatement(ptx, ctx, ora, clean_env, m
     s = _product(ptx, ctx, clean_env, name, map_name, maps)
     tab = E.table(*_tables(ptx, s))
     o = _new_oracle(ora, name, maps[map_name])
-    ref = E.render_samples(ora, o, o.a, W, H, spp, b, tab, seed=SEED, lights=not extra)
+    ref = render_samples(ora, o, o.a, W, H, spp, b, tab=tab, seed=SEED, lights=not extra)
     got = np.zeros((H, W, spp, 3), np.float32)
     tot = dict(light_samples=0, light_visible=0, rays=0)
     for k in range(spp):
@@ -289,7 +231,7 @@ def test_first_environment_sample(ptx, ctx, ora, clean_env, maps):
     s = _product(ptx, ctx, clean_env, "chart", "hot_only", maps)
     o = _new_oracle(ora, "chart", maps["hot_only"])
     first = {}
-    ref = E.render_samples(ora, o, o.a, W, H, spp, 2, E.table(*_tables(ptx, s)), seed=SEED, first_env=first)
+    ref = render_samples(ora, o, o.a, W, H, spp, 2, tab=E.table(*_tables(ptx, s)), seed=SEED, first_env=first)
     flat = ref["rad"].transpose(2, 0, 1, 3).reshape(-1, 3)      # by sample id
     ids, x = first["ids"][first["visible"]], first["x"][first["visible"]]
     only = (_bits(flat[ids]) == _bits(x)).all(-1)               # nothing else was added to the sample

@@ -14,9 +14,9 @@ import os
 import numpy as np
 import pytest
 
-import _nee_restatement as R
 from _common import _bits
 from _nee_common import SEED, _err, _host_scene, _make, _oracle, _pair
+from _nee_estimator import render_samples
 from _routes import DEFAULT_ROUTES, Scenes, clean_env, ctx, on_route, route_named  # noqa: F401  (clean_env and ctx are fixtures)
 from conftest import CORNELL, ROOT
 
@@ -142,7 +142,7 @@ def test_per_sample_radiance_against_the_restatement(ptx, ctx, ora, clean_env):
     >= 99.5 % within 1e-3 relative (floor 1e-3, _nee_common._err)."""
     W, H, spp, b = 32, 32, 8, 3
     o, a = _oracle(ora, "cornell")
-    ref = R.render_samples(ora, o, a, W, H, spp, b, seed=SEED)
+    ref = render_samples(ora, o, a, W, H, spp, b, seed=SEED)
     s, _ = _route(ptx, ctx, clean_env, "cornell", "lds fused")
     got = np.zeros((H, W, spp, 3), np.float32)
     for k in range(spp):

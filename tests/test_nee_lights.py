@@ -10,7 +10,7 @@ Two scenes carry it:
   procedural.emitter_cloud_scene: 64 surfaces under four rotated, non-uniformly scaled models, 18 emissive surfaces spread over surface ids
       0 ... 62 (271 listed triangles, one collapsed triangle left out, one half-transparent emitter left out). Its four (sun, alpha)
       combinations give the four (F, ., .) kernels.
-The yardstick is tests/_nee_restatement.py (pinned here, on these scenes and under an environment map, to OracleScene.render_samples bit for
+The yardstick is tests/_nee_estimator.py on tests/_nee_restatement.py (pinned here, on these scenes and under an environment map, to OracleScene.render_samples bit for
 bit). Bars are the project's: test_gpu_parity's per-sample bar (_nee_common._err), bitwise equality between the two forms and between routes.
 
 Without a GPU: the fixtures' light lists, kernel triples and sample statistics, the pin, the host-only light arrays.
@@ -26,6 +26,7 @@ import pytest
 import _nee_restatement as R
 from _common import _bits, _proc
 from _nee_common import SAME_STATS, SEED, _check_list, _err, _pair
+from _nee_estimator import render_samples
 from _nee_lit_scenes import CLOUDS, LIT, LIT_LOADS, LIT_OPAQUE, LIT_PRIMS, SKY, _dict, _host_scene, _hybrid_budget, _oracle, f32
 from _routes import clean_env, ctx  # noqa: F401  (fixtures)
 from _routes import DEFAULT_ROUTES, ROUTE_VARS, Route, Scenes, on_route, route_named, under_force_global
@@ -187,7 +188,7 @@ def _ref(ora, name, **kw):
     if key not in _refs:
         o, a = _oracle(ora, name)
         log = []
-        _refs[key] = R.render_samples(ora, o, a, *SIZE[name], 2, 4, seed=SEED, light_draws=log, **kw)
+        _refs[key] = render_samples(ora, o, a, *SIZE[name], 2, 4, seed=SEED, light_draws=log, **kw)
         _refs[key]["draw_keys"] = np.concatenate(log) if log else np.zeros((0, 4), np.uint32)
     return _refs[key]
 
@@ -233,13 +234,13 @@ def test_restatement_without_lights_is_the_pinned_oracle(ora, name):
     o, a = _oracle(ora, name)
     W, H = SIZE[name]
     ref = o.render_samples(ora.make_cfg(W, H, 2, 4, seed=SEED), threads=0)
-    got = R.render_samples(ora, o, a, W, H, 2, 4, seed=SEED, lights=False, fold="recursive")["rad"]
+    got = render_samples(ora, o, a, W, H, 2, 4, seed=SEED, lights=False, fold="recursive")["rad"]
     np.testing.assert_array_equal(_bits(got), _bits(ref))
     if name == "chart_env":      # the map is in use: the frame is not the constant environment's, and a scaled factor scales the misses
-        flat = R.render_samples(ora, oracle_from_dict(ora, _dict(name)), a, W, H, 2, 4, seed=SEED, lights=False)["rad"]
+        flat = render_samples(ora, oracle_from_dict(ora, _dict(name)), a, W, H, 2, 4, seed=SEED, lights=False)["rad"]
         assert (_bits(flat) != _bits(got)).any(-1).mean() > 0.05
         ref = o.render_samples(ora.make_cfg(W, H, 2, 4, env=(0.5, 1.25, 2.0), seed=SEED), threads=0)
-        got = R.render_samples(ora, o, a, W, H, 2, 4, seed=SEED, env=(0.5, 1.25, 2.0), lights=False, fold="recursive")["rad"]
+        got = render_samples(ora, o, a, W, H, 2, 4, seed=SEED, env=(0.5, 1.25, 2.0), lights=False, fold="recursive")["rad"]
         np.testing.assert_array_equal(_bits(got), _bits(ref))
 
 
@@ -417,7 +418,7 @@ def test_first_light_sample_bitwise(ptx, ctx, ora, clean_env, name):
     Measured on the MI355X: none differs (cloud 0 of 8819, 1269 of them not black; lit.gltf 0 of 5967, 945 not black)."""
     o, a = _oracle(ora, name)
     W, H = SIZE[name]
-    ref = R.render_samples(ora, o, a, W, H, 4, 2, seed=SEED, env=(0.0, 0.0, 0.0))
+    ref = render_samples(ora, o, a, W, H, 4, 2, seed=SEED, env=(0.0, 0.0, 0.0))
     s, pipeline = _route(ptx, ctx, clean_env, name, "lds fused")
     got, tot = _samples(ptx, ctx, s, name, 4, 2, 0, pipeline, env=(0.0, 0.0, 0.0))
     sel = ~ref["v1_listed"]

@@ -1,6 +1,6 @@
 """Point and spot lights as a third light-sampling strategy of ptx_render_nee (include/ptx.h: ptx_scene_set_punctual_lights,
 ptx_gltf_read_punctual_lights, PUNCTUAL LIGHTS), without a GPU: the symbols and the setter's refusals on a host-only scene, the stored arrays,
-the glTF reader on tests/golden/lights/lamps.gltf, and the estimator on tests/_nee_punctual_restatement.py.
+the glTF reader on tests/golden/lights/lamps.gltf, and the estimator on tests/_nee_estimator.py.
 
 The expectation is pinned to a stand-in: the point light replaced by a small emissive triangle at the light's position that faces the test
 region, with Le * area = the light's intensity, rendered by the restatement of the existing estimator (no punctual lights). The test region is
@@ -15,17 +15,15 @@ import os
 import numpy as np
 import pytest
 
-import _nee_env_restatement as E
 import _nee_punctual_restatement as PU
-import _nee_ris_restatement as RIS
 from _common import _bits, _proc
 from _nee_common import K_BATCH, SEED, _batch_stat, _oracle, _same_expectation
-from _nee_lit_scenes import SKY
+from _nee_estimator import render_samples
+from _nee_lit_scenes import SKY, _table
 from conftest import GOLD, oracle_from_dict, product_from_dict
 
 f32 = np.float32
 LAMPS = os.path.join(GOLD, "lights", "lamps.gltf")
-ENV = 16
 
 
 def _lamp(pos=(0, 1, 0), rng=0.0, direction=(0, 0, -1), kind=0, intensity=(1, 1, 1), ci=1.0, co=0.70710677):
@@ -203,13 +201,13 @@ def _same(a, b, what):
 
 @pytest.mark.parametrize("name,M", [("cornell", 1), ("cornell", 4), ("chart", 2)])
 def test_without_lights_the_restatement_is_the_one_it_extends(ora, name, M):
-    """punctual=None, an empty array and all-black lights: _nee_ris_restatement's frame and counts bit for bit, on scenes of the existing tests"""
+    """punctual=None, an empty array and all-black lights: the frame and counts without the argument bit for bit, on scenes of the existing tests"""
     o, a = _oracle(ora, name)
     W, H, spp, b = 16, 12, 2, 3
-    want = RIS.render_samples(ora, o, a, W, H, spp, b, None, M, seed=SEED)
+    want = render_samples(ora, o, a, W, H, spp, b, M=M, seed=SEED)
     black = np.stack([_lamp(intensity=(0, 0, 0))])
     for tag, lights in (("None", None), ("empty", np.zeros((0, 16), f32)), ("black", black)):
-        got = PU.render_samples(ora, o, a, W, H, spp, b, None, M, seed=SEED, punctual=lights)
+        got = render_samples(ora, o, a, W, H, spp, b, M=M, seed=SEED, punctual=lights)
         _same(got["rad"], want["rad"], f"{name} M = {M}: {tag}")
         assert all(got[k] == want[k] for k in ("light_samples", "light_visible", "rays")), (tag, got, want)
     assert want["light_samples"] > 0
@@ -264,7 +262,7 @@ def _case(ptx, ora, name):
                 o.set_environment(SKY, srgb=False)
             s = product_from_dict(ptx, None, d)
             s.set_environment(SKY, srgb=False)
-            tab = E.table(s.array(ptx.ARR_ENV_ROW_CDF), s.array(ptx.ARR_ENV_CELL_CDF))
+            tab = _table(ptx, s)
         _cases[name] = (*scenes, lights, tab)
     return _cases[name]
 
@@ -281,15 +279,15 @@ def _stand_in(ptx, ora, name, half=False):
     if (name, half) not in _stand_in_batches:
         _, full, small, _, tab = _case(ptx, ora, name)
         o = small if half else full
-        ref = _batches(lambda seed, spp: PU.render_samples(ora, o, o.a, EXP_W, EXP_H, spp, EXP_B, tab, 1, seed=seed), 0xB000)
+        ref = _batches(lambda seed, spp: render_samples(ora, o, o.a, EXP_W, EXP_H, spp, EXP_B, tab=tab, seed=seed), 0xB000)
         ref.setflags(write=False)
         _stand_in_batches[(name, half)] = ref
     return _stand_in_batches[(name, half)]
 
 
-def _punctual_batches(ptx, ora, name, M=1, **wrong):
+def _punctual_batches(ptx, ora, name, M=1, wrong=()):
     o, _, _, lights, tab = _case(ptx, ora, name)
-    return _batches(lambda seed, spp: PU.render_samples(ora, o, o.a, EXP_W, EXP_H, spp, EXP_B, tab, M, seed=seed, punctual=lights, **wrong), 0xA000)
+    return _batches(lambda seed, spp: render_samples(ora, o, o.a, EXP_W, EXP_H, spp, EXP_B, tab=tab, M=M, seed=seed, punctual=lights, wrong=wrong), 0xA000)
 
 
 @pytest.mark.parametrize("name", ["bare", "emitter", "map"])
@@ -314,7 +312,7 @@ def test_the_statistic_can_tell(ptx, ora, wrong, name):
     lamp): both fail the statistic the right form passes, on the scenes where c_p = 0.5.
     Measured, worst z frame / quadrant: forget_bsdf_side under the map 5.57 / 3.60; forget_cp with the emitter 14.96 / 8.42, under the map
     7.28 / 4.44 (the right form: 0.29 - 1.67 / 0.69 - 1.51)."""
-    got = _punctual_batches(ptx, ora, name, **{wrong: True})
+    got = _punctual_batches(ptx, ora, name, wrong=(wrong,))
     ok, zf, zq = _same_expectation(got, _stand_in(ptx, ora, name))
     print(f"{wrong} on {name}: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert not ok, (zf, zq)
@@ -329,7 +327,7 @@ def test_candidates_same_expectation_and_no_more_variance_on_many_lamps(ora):
     W, H, b = 24, 16, 3
 
     def render(M):
-        return lambda seed, spp: PU.render_samples(ora, o, o.a, W, H, spp, b, None, M, seed=seed, punctual=lights)
+        return lambda seed, spp: render_samples(ora, o, o.a, W, H, spp, b, M=M, seed=seed, punctual=lights)
     ok, zf, zq = _same_expectation(_batches(render(4), 0xA000), _batches(render(1), 0xB000))
     print(f"64 lamps, M = 4 against M = 1: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert ok, (zf, zq)

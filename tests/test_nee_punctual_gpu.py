@@ -1,5 +1,5 @@
 """Point and spot lights in ptx_render_nee on the MI355X (include/ptx.h: PUNCTUAL LIGHTS; csrc/nee_core.hpp nee_candidate's PUN branch,
-the PUN parts of nee.hip and nee_fused.hip). The yardstick is tests/_nee_punctual_restatement.py; the CPU side of it is tests/test_nee_punctual.py.
+the PUN parts of nee.hip and nee_fused.hip). The yardstick is tests/_nee_estimator.py; the CPU side of it is tests/test_nee_punctual.py.
 
 Scenes: procedural.lamp_scene (a floor, a blocker, optionally an emitter, lamps above) and the material chart with pass-through patches and a
 sun under six lamps; the golden sky as the map. Bars are the project's: the per-sample bar of test_nee.py / test_nee_lights.py, bitwise
@@ -14,23 +14,17 @@ import numpy as np
 import pytest
 
 import _adaptive_restatement as AR
-import _nee_env_restatement as E
-import _nee_punctual_restatement as PU
 from _common import _bits, _proc, _same
 from _nee_common import SAME_STATS, SEED, _err, _pair
-from _nee_lit_scenes import CLOUDS, LIT, LIT_LOADS, SKY
+from _nee_estimator import render_samples
+from _nee_lit_scenes import CAND, CLOUDS, ENV, FUSED, LIT, LIT_LOADS, NO_LIGHTS, SKY, SPDF, _table
 from _nee_lit_scenes import _dict as _lit_dict
 from _routes import clean_env, ctx  # noqa: F401  (fixtures)
 from _routes import DEFAULT_ROUTES, ROUTE_VARS, Scenes, on_route, route_named, under_force_global
 from conftest import GOLD, ROOT, oracle_from_dict, product_from_dict
 
 f32 = np.float32
-NO_LIGHTS, FUSED, ENV, SPDF = 1, 4, 16, 64
 LAMPS = os.path.join(GOLD, "lights", "lamps.gltf")
-
-
-def CAND(m):
-    return (m - 1) << 8
 
 
 # name -> (lamp_scene arguments, under the sky map)
@@ -118,7 +112,7 @@ def _oracle_and_table(ptx, ora, name, flags):
             o.set_environment(SKY, srgb=False)
             if flags & ENV:
                 s = _make(ptx, None, name)
-                tab = E.table(s.array(ptx.ARR_ENV_ROW_CDF), s.array(ptx.ARR_ENV_CELL_CDF))
+                tab = _table(ptx, s)
         _oracles[key] = (o, tab)
     return _oracles[key]
 
@@ -128,7 +122,7 @@ def _restated(ptx, ora, name, flags, M, W, H, spp, b, **kw):
     key = (name, flags, M, W, H, spp, b, tuple(sorted(kw.items())))
     if key not in _refs:
         o, tab = _oracle_and_table(ptx, ora, name, flags)
-        ref = PU.render_samples(ora, o, o.a, W, H, spp, b, tab, M, spdf=bool(flags & SPDF), seed=SEED, punctual=_dict_and_lights(name)[1], **kw)
+        ref = render_samples(ora, o, o.a, W, H, spp, b, tab=tab, M=M, spdf=bool(flags & SPDF), seed=SEED, punctual=_dict_and_lights(name)[1], **kw)
         ref["rad"].setflags(write=False)
         _refs[key] = ref
     return _refs[key]

@@ -2,11 +2,11 @@
 ray for the pick (include/ptx.h has the candidates, the selection rule and the estimate; csrc/nee_core.hpp nee_candidate and nee_vertex's RIS
 parameter).
 
-The yardstick is tests/_nee_ris_restatement.py: _nee_pdf_restatement's vertex for both light kinds and both weight bases with the light
-sample made a function of the candidate's index, and the selection in float32. Maps: _nee_env_restatement's hot-texel map, written into tmp,
-and the golden sky.
+The yardstick is tests/_nee_estimator.py: the vertex for both light kinds and both weight bases with the light sample a function of the
+candidate's index, and the selection in float32 (M = 1 against the estimators it extends: tests/test_nee_restatement_bits.py). Maps:
+_nee_lit_scenes' hot-texel map, written into tmp, and the golden sky.
 
-Without a GPU: the macro's values and the refusals, M = 1 as the restatement it extends, the expectation at M = 2 and M = 4 against M = 1 on
+Without a GPU: the macro's values and the refusals, the expectation at M = 2 and M = 4 against M = 1 on
 four scenes with the power of that check against two wrong forms, the variance ratio, the bitwise LIB frame where no light sample is
 possible, the selection rule's frequencies.
 On the GPU: per-sample radiance against the restatement on three routes, fused against unfused with the bits on every RIS variant of
@@ -23,88 +23,17 @@ import numpy as np
 import pytest
 
 import _adaptive_restatement as AR
-import _nee_env_restatement as E
-import _nee_pdf_restatement as P
-import _nee_restatement as R
 import _nee_ris_restatement as RIS
-from _common import _bits, _proc, _same
+from _common import _bits, _same
 from _nee_common import K_BATCH, SAME_STATS, SEED, _batch_stat, _err, _pair, _same_expectation
-from _nee_lit_scenes import CLOUDS, LIT, LIT_LOADS, SKY, _hybrid_budget
+from _nee_estimator import render_samples
+from _nee_lit_scenes import CAND, CLOUDS, ENV, FUSED, LIT, LIT_LOADS, NO_LIGHTS, SPDF, _hybrid_budget, _new_oracle, _new_scene, _oracle_and_table, _variance_ratio
+from _nee_lit_scenes import maps  # noqa: F401  (fixture)
 from _routes import clean_env, ctx  # noqa: F401  (fixtures)
 from _routes import DEFAULT_ROUTES, ROUTE_VARS, Scenes, on_route, route_named
-from conftest import CORNELL, ROOT, oracle_from_dict, product_from_dict
+from conftest import ROOT
 
 f32 = np.float32
-NO_LIGHTS, FUSED, ENV, SPDF = 1, 4, 16, 64
-
-
-def CAND(m):
-    return (m - 1) << 8
-
-
-@pytest.fixture(scope="module")
-def maps(tmp_path_factory):
-    """name -> (path, srgb); .hdr maps are read linearly"""
-    d = tmp_path_factory.mktemp("ris_maps")
-    return {"hot": (E.write_hdr(d / "hot.hdr", E.hot_texel()), False), "sky": (SKY, False)}
-
-
-# ---------------------------------------------------------------------------- scenes: this module's own (it sets maps on them)
-_dicts = {}
-
-
-def _dict(name):
-    if name not in _dicts:
-        if name in CLOUDS:
-            sun, alpha = CLOUDS[name]
-            _dicts[name] = _proc().emitter_cloud_scene(sun=sun, alpha=alpha)
-        else:
-            assert name == "chart", name
-            _dicts[name] = _proc().chart_scene(facing=True, alpha=False)
-    return _dicts[name]
-
-
-def _new_oracle(ora, name, env_map=None):
-    if name == "cornell":
-        o = ora.OracleScene(ora.load_gltf(CORNELL))
-    elif name in LIT_LOADS:
-        sun, work = LIT_LOADS[name]
-        o = ora.OracleScene(ora.load_gltf(LIT, sun_light_index=sun, work=work))
-    else:
-        o = oracle_from_dict(ora, _dict(name))
-    if env_map:
-        o.set_environment(env_map[0], srgb=env_map[1])
-    return o
-
-
-def _new_scene(ptx, name, ctx=None, env_map=None):
-    if name == "cornell":
-        s = ptx.Scene.load_gltf(ctx, CORNELL)
-    elif name in LIT_LOADS:
-        sun, work = LIT_LOADS[name]
-        s = ptx.Scene.load_gltf(ctx, LIT, sun_light_index=sun, work=work)
-    else:
-        s = product_from_dict(ptx, ctx, _dict(name))
-    if env_map:
-        s.set_environment(env_map[0], srgb=env_map[1])
-    return s
-
-
-def _table(ptx, s):
-    return E.table(s.array(ptx.ARR_ENV_ROW_CDF), s.array(ptx.ARR_ENV_CELL_CDF))
-
-
-_oracles = {}
-
-
-def _oracle_and_table(ptx, ora, maps, name, map_name, flags):
-    """(oracle scene under the map, the environment table if the flags ask for one), kept"""
-    key = (name, map_name, bool(flags & ENV))
-    if key not in _oracles:
-        o = _new_oracle(ora, name, maps[map_name] if map_name else None)
-        tab = _table(ptx, _new_scene(ptx, name, env_map=maps[map_name])) if flags & ENV else None
-        _oracles[key] = (o, tab)
-    return _oracles[key]
 
 
 # ---------------------------------------------------------------------------- no GPU
@@ -134,18 +63,6 @@ def test_flag_values_and_refusals_without_a_device(ptx):
     assert (acc == 0).all() and (acc_b == 0).all()
 
 
-def test_one_candidate_is_the_restatement_it_extends(ptx, ora, maps):
-    """M = 1 is the call without the bits: bit for bit _nee_pdf_restatement's frame and counts, for the triangle list on pe and for the map
-    with the list on ps"""
-    W, H, spp, b = 16, 12, 2, 3
-    for name, map_name, flags in (("cornell", None, 0), ("lit_opaque_nosun", "hot", ENV | SPDF)):
-        o, tab = _oracle_and_table(ptx, ora, maps, name, map_name, flags)
-        got = RIS.render_samples(ora, o, o.a, W, H, spp, b, tab, 1, spdf=bool(flags & SPDF), seed=SEED)
-        want = P.render_samples(ora, o, o.a, W, H, spp, b, tab, seed=SEED, use_pe=not flags & SPDF)
-        _same(got["rad"], want["rad"], f"{name}: M = 1")
-        assert all(got[k] == want[k] for k in ("light_samples", "light_visible", "rays")) and got["light_samples"] > 0, (name, got, want)
-
-
 def _batches(render, seed0, K=K_BATCH, spp=16, **kw):
     return _batch_stat(np.stack([render(seed=seed0 + k, spp=spp, **kw)["rad"].mean(2) for k in range(K)]))
 
@@ -161,7 +78,7 @@ def _reference_batches(ptx, ora, maps, case):
     if case not in _one_candidate:
         name, map_name, flags, W, H, b = case
         o, tab = _oracle_and_table(ptx, ora, maps, name, map_name, flags)
-        ref = _batches(lambda seed, spp: RIS.render_samples(ora, o, o.a, W, H, spp, b, tab, 1, spdf=bool(flags & SPDF), seed=seed), 0xB000)
+        ref = _batches(lambda seed, spp: render_samples(ora, o, o.a, W, H, spp, b, tab=tab, M=1, spdf=bool(flags & SPDF), seed=seed), 0xB000)
         ref.setflags(write=False)
         _one_candidate[case] = ref
     return _one_candidate[case]
@@ -175,7 +92,7 @@ def test_expectation_is_the_one_candidate_estimators_on_the_restatement(ptx, ora
     and the same with PTX_NEE_SAMPLER_PDF."""
     name, map_name, flags, W, H, b = case
     o, tab = _oracle_and_table(ptx, ora, maps, name, map_name, flags)
-    got = _batches(lambda seed, spp: RIS.render_samples(ora, o, o.a, W, H, spp, b, tab, M, spdf=bool(flags & SPDF), seed=seed), 0xA000)
+    got = _batches(lambda seed, spp: render_samples(ora, o, o.a, W, H, spp, b, tab=tab, M=M, spdf=bool(flags & SPDF), seed=seed), 0xA000)
     ok, zf, zq = _same_expectation(got, _reference_batches(ptx, ora, maps, case))
     print(f"{name} / {map_name} / {flags}: M = {M} against M = 1: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert ok, (zf, zq)
@@ -189,15 +106,10 @@ def test_the_statistic_can_tell(ptx, ora, maps, wrong):
     case = EXPECTATION_CASES[0]
     name, map_name, flags, W, H, b = case
     o, tab = _oracle_and_table(ptx, ora, maps, name, map_name, flags)
-    got = _batches(lambda seed, spp: RIS.render_samples(ora, o, o.a, W, H, spp, b, tab, 4, seed=seed, **{wrong: True}), 0xA000)
+    got = _batches(lambda seed, spp: render_samples(ora, o, o.a, W, H, spp, b, tab=tab, M=4, seed=seed, wrong=(wrong,)), 0xA000)
     ok, zf, zq = _same_expectation(got, _reference_batches(ptx, ora, maps, case))
     print(f"{wrong}: M = 4 against M = 1: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert not ok, (zf, zq)
-
-
-def _variance_ratio(flagged, unflagged):
-    """mean over pixels and channels of the per-pixel sample variance, flagged / unflagged; rad [h, w, spp, 3]"""
-    return float(flagged.var(2, ddof=1, dtype=np.float64).mean() / unflagged.var(2, ddof=1, dtype=np.float64).mean())
 
 
 def test_variance_falls_on_the_restatement(ptx, ora, maps):
@@ -206,7 +118,7 @@ def test_variance_falls_on_the_restatement(ptx, ora, maps):
     Measured: variance ratio 0.9036 = RIS.R0 (the GPU test's bar is twice that), light samples 86179 against 44050."""
     v = RIS.VARIANCE_CASE
     o, tab = _oracle_and_table(ptx, ora, maps, v["name"], None, 0)
-    r = {M: RIS.render_samples(ora, o, o.a, v["W"], v["H"], v["spp"], v["bounces"], None, M, seed=v["seed"]) for M in (1, v["M"])}
+    r = {M: render_samples(ora, o, o.a, v["W"], v["H"], v["spp"], v["bounces"], M=M, seed=v["seed"]) for M in (1, v["M"])}
     r0 = _variance_ratio(r[v["M"]]["rad"], r[1]["rad"])
     print(f"per-sample variance M = {v['M']} / M = 1: r0 = {r0:.4f}; light samples {r[v['M']]['light_samples']} against {r[1]['light_samples']}")
     assert r0 < 1 and abs(r0 / RIS.R0 - 1) < 0.02   # RIS.R0 is this figure, written down for the GPU test
@@ -214,10 +126,10 @@ def test_variance_falls_on_the_restatement(ptx, ora, maps):
 
 
 def test_without_a_possible_light_sample_the_restatement_is_lib_bitwise(ora):
-    """lights=False, tab=None: no candidate is drawn, so the restatement at M = 4 is _nee_restatement's LIB frame bit for bit"""
+    """lights=False, tab=None: no candidate is drawn, so the restatement at M = 4 is the LIB frame of M = 1 bit for bit"""
     o = _new_oracle(ora, "chart")
-    got = RIS.render_samples(ora, o, o.a, 24, 16, 4, 3, None, 4, seed=SEED, lights=False)
-    want = R.render_samples(ora, o, o.a, 24, 16, 4, 3, seed=SEED, lights=False)
+    got = render_samples(ora, o, o.a, 24, 16, 4, 3, M=4, seed=SEED, lights=False)
+    want = render_samples(ora, o, o.a, 24, 16, 4, 3, seed=SEED, lights=False)
     _same(got["rad"], want["rad"], "M = 4 without lights against LIB")
     assert got["light_samples"] == 0 and got["rays"] == want["rays"]
 
@@ -262,7 +174,7 @@ def _restated(ptx, ora, maps, name, map_name, flags, M, W, H, spp, b):
     key = (name, map_name, flags, M)
     if key not in _refs:
         o, tab = _oracle_and_table(ptx, ora, maps, name, map_name, flags)
-        ref = RIS.render_samples(ora, o, o.a, W, H, spp, b, tab, M, spdf=bool(flags & SPDF), seed=SEED)
+        ref = render_samples(ora, o, o.a, W, H, spp, b, tab=tab, M=M, spdf=bool(flags & SPDF), seed=SEED)
         ref["rad"].setflags(write=False)
         _refs[key] = ref
     return _refs[key]

@@ -1,8 +1,8 @@
 """PTX_NEE_SAMPLER_PDF: ptx_render_nee's MIS weights built on the density of LIB's BSDF sampler in place of LIB's pdf value (include/ptx.h has
 the density and the three places; csrc/nee_core.hpp sampler_pdf and nee_vertex's SPDF parameter).
 
-The yardstick is tests/_nee_pdf_restatement.py: the flagged estimator for both light kinds on tests/_nee_env_restatement.py's vertex, with a
-switch (use_pe) that puts pe back. Maps: a uniform 16 x 8 map of value 1 and _nee_env_restatement's hot-texel map, written into tmp.
+The yardstick is tests/_nee_pdf_restatement.py, the density, and tests/_nee_estimator.py, the estimator for both light kinds, whose spdf=False
+puts pe back. Maps: _nee_lit_scenes' uniform 16 x 8 map of value 1 and its hot-texel map, written into tmp.
 
 Without a GPU: the flag's value and the refusals, the density against the oracle's importance_specular draws (and LIB's pdf_specular failing
 the same check), the expectation under a map and under the triangle list alone with the power of both checks, the bitwise LIB frame where no
@@ -20,71 +20,18 @@ import numpy as np
 import pytest
 
 import _adaptive_restatement as AR
-import _nee_env_restatement as E
 import _nee_pdf_restatement as P
 import _nee_restatement as R
-from _common import _bits, _proc, _same
+from _common import _bits, _same
 from _nee_common import K_BATCH, SAME_STATS, SEED, _batch_stat, _err, _pair, _same_expectation
-from _nee_lit_scenes import CLOUDS, LIT, LIT_LOADS, SKY, _hybrid_budget
+from _nee_estimator import render_samples
+from _nee_lit_scenes import CLOUDS, ENV, FUSED, LIT, LIT_LOADS, NO_LIGHTS, SPDF, _hybrid_budget, _new_oracle, _new_scene, _table
+from _nee_lit_scenes import maps  # noqa: F401  (fixture)
 from _routes import clean_env, ctx  # noqa: F401  (fixtures)
 from _routes import DEFAULT_ROUTES, ROUTE_VARS, Scenes, on_route, route_named
-from conftest import CORNELL, ROOT, oracle_from_dict, product_from_dict
+from conftest import ROOT
 
 f32 = np.float32
-NO_LIGHTS, FUSED, ENV, SPDF = 1, 4, 16, 64
-
-
-@pytest.fixture(scope="module")
-def maps(tmp_path_factory):
-    """name -> (path, srgb); .hdr maps are read linearly"""
-    d = tmp_path_factory.mktemp("spdf_maps")
-    return {"uniform": (E.write_hdr(d / "uniform.hdr", np.full((8, 16, 3), 1.0)), False), "hot": (E.write_hdr(d / "hot.hdr", E.hot_texel()), False),
-            "sky": (SKY, False)}
-
-
-# ---------------------------------------------------------------------------- scenes: this module's own (it sets maps on them)
-_dicts = {}
-
-
-def _dict(name):
-    if name not in _dicts:
-        if name in CLOUDS:
-            sun, alpha = CLOUDS[name]
-            _dicts[name] = _proc().emitter_cloud_scene(sun=sun, alpha=alpha)
-        else:
-            assert name == "chart", name
-            _dicts[name] = _proc().chart_scene(facing=True, alpha=False)
-    return _dicts[name]
-
-
-def _new_oracle(ora, name, env_map=None):
-    if name == "cornell":
-        o = ora.OracleScene(ora.load_gltf(CORNELL))
-    elif name in LIT_LOADS:
-        sun, work = LIT_LOADS[name]
-        o = ora.OracleScene(ora.load_gltf(LIT, sun_light_index=sun, work=work))
-    else:
-        o = oracle_from_dict(ora, _dict(name))
-    if env_map:
-        o.set_environment(env_map[0], srgb=env_map[1])
-    return o
-
-
-def _new_scene(ptx, name, ctx=None, env_map=None):
-    if name == "cornell":
-        s = ptx.Scene.load_gltf(ctx, CORNELL)
-    elif name in LIT_LOADS:
-        sun, work = LIT_LOADS[name]
-        s = ptx.Scene.load_gltf(ctx, LIT, sun_light_index=sun, work=work)
-    else:
-        s = product_from_dict(ptx, ctx, _dict(name))
-    if env_map:
-        s.set_environment(env_map[0], srgb=env_map[1])
-    return s
-
-
-def _table(ptx, s):
-    return E.table(s.array(ptx.ARR_ENV_ROW_CDF), s.array(ptx.ARR_ENV_CELL_CDF))
 
 
 # ---------------------------------------------------------------------------- no GPU
@@ -191,16 +138,16 @@ def test_expectation_under_a_map_on_the_restatement(ptx, ora, maps, map_name):
     o = _new_oracle(ora, "chart", maps[map_name])
     tab = _table(ptx, _new_scene(ptx, "chart", env_map=maps[map_name]))
 
-    def flagged(seed, spp, **kw):
-        return P.render_samples(ora, o, o.a, W, H, spp, b, tab, seed=seed, **kw)
+    def flagged(seed, spp, spdf=True):
+        return render_samples(ora, o, o.a, W, H, spp, b, tab=tab, spdf=spdf, seed=seed)
 
     def unflagged(seed, spp):
-        return E.render_samples(ora, o, o.a, W, H, spp, b, None, seed=seed)
+        return render_samples(ora, o, o.a, W, H, spp, b, seed=seed)
     ref = _batches(ora, unflagged, 0xB000)
     ok, zf, zq = _same_expectation(_batches(ora, flagged, 0xA000), ref)
     print(f"{map_name}: weights on the sampler's density against unflagged: worst z frame {zf:.2f} quadrant {zq:.2f}")
     assert ok, (zf, zq)
-    pe_ok, zf, zq = _same_expectation(_batches(ora, flagged, 0xA000, use_pe=True), ref)
+    pe_ok, zf, zq = _same_expectation(_batches(ora, flagged, 0xA000, spdf=False), ref)
     print(f"{map_name}: weights on pe against unflagged: worst z frame {zf:.2f} quadrant {zq:.2f}")
     if map_name == "uniform":
         assert not pe_ok, (zf, zq)
@@ -220,11 +167,11 @@ def test_expectation_under_the_triangle_list_alone_on_the_restatement(ora):
     W, H, b = 24, 16, 3
     o = _new_oracle(ora, "chart")
 
-    def nee(seed, spp, **kw):
-        return P.render_samples(ora, o, o.a, W, H, spp, b, None, seed=seed, **kw)
+    def nee(seed, spp):
+        return render_samples(ora, o, o.a, W, H, spp, b, spdf=True, seed=seed)
 
     def lib(seed, spp):
-        return R.render_samples(ora, o, o.a, W, H, spp, b, seed=seed, lights=False)
+        return render_samples(ora, o, o.a, W, H, spp, b, seed=seed, lights=False)
     ref = _batches(ora, lib, 0xB000, TRI_K, TRI_SPP)
     ok, zf, zq = _same_expectation(_batches(ora, nee, 0xA000, TRI_K, TRI_SPP), ref)
     print(f"triangle list, weights on the sampler's density against LIB: worst z frame {zf:.2f} quadrant {zq:.2f}")
@@ -232,10 +179,10 @@ def test_expectation_under_the_triangle_list_alone_on_the_restatement(ora):
 
 
 def test_without_a_possible_light_sample_the_restatement_is_lib_bitwise(ora):
-    """lights=False, tab=None: every weight is 1, so the flagged restatement is _nee_restatement's LIB frame bit for bit"""
+    """lights=False, tab=None: every weight is 1, so the flagged restatement (spdf) is the unflagged one's LIB frame bit for bit"""
     o = _new_oracle(ora, "chart")
-    got = P.render_samples(ora, o, o.a, 24, 16, 4, 3, None, seed=SEED, lights=False)
-    want = R.render_samples(ora, o, o.a, 24, 16, 4, 3, seed=SEED, lights=False)
+    got = render_samples(ora, o, o.a, 24, 16, 4, 3, spdf=True, seed=SEED, lights=False)
+    want = render_samples(ora, o, o.a, 24, 16, 4, 3, seed=SEED, lights=False)
     _same(got["rad"], want["rad"], "flagged restatement without lights against LIB")
     assert got["light_samples"] == 0 and got["rays"] == want["rays"]
 
@@ -258,7 +205,7 @@ def _restated(ptx, ora, maps, name, map_name, flags, W, H, spp, b):
     if key not in _refs:
         o = _new_oracle(ora, name, maps[map_name] if map_name else None)
         tab = _table(ptx, _new_scene(ptx, name, env_map=maps[map_name])) if flags & ENV else None
-        ref = P.render_samples(ora, o, o.a, W, H, spp, b, tab, seed=SEED)
+        ref = render_samples(ora, o, o.a, W, H, spp, b, tab=tab, spdf=True, seed=SEED)
         ref["rad"].setflags(write=False)
         _refs[key] = ref
     return _refs[key]
