@@ -64,6 +64,10 @@ class Camera(C.Structure):
                 ("focus_distance", C.c_float), ("blades", C.c_uint32), ("blade_rotation", C.c_float)]
 
 
+class MotionPrev(C.Structure):
+    _fields_ = [("camera", C.POINTER(Camera)), ("model_xform", C.c_void_p), ("n_models", C.c_uint32)]
+
+
 class SceneInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_models", "n_surfaces", "n_vertices", "n_triangles", "n_kd_nodes", "n_kd_refs",
                                           "kd_max_depth", "has_sun", "geometry_bytes", "lds_resident", "n_textures")]
@@ -100,6 +104,20 @@ class DenoiseStats(C.Structure):
 class DenoiseCountsCfg(C.Structure):
     _fields_ = [("W", C.c_uint32), ("H", C.c_uint32), ("guide_spp", C.c_uint32), ("iterations", C.c_uint32),
                 ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float)]
+
+
+class TemporalHistory(C.Structure):
+    _fields_ = [("color", C.c_void_p), ("moments", C.c_void_p), ("geometry", C.c_void_p)]
+
+
+class TemporalCfg(C.Structure):
+    _fields_ = [("W", C.c_uint32), ("H", C.c_uint32), ("spp_a", C.c_uint32), ("spp_b", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float), ("max_history", C.c_uint32),
+                ("tau_z", C.c_float), ("tau_n", C.c_float)]
+
+
+class TemporalStats(C.Structure):
+    _fields_ = [("filter", DenoiseStats), ("accumulate_ms", C.c_double), ("reprojected", C.c_uint64), ("reset", C.c_uint64)]
 
 
 class AdaptiveCfg(C.Structure):
@@ -230,11 +248,14 @@ def lib():
         L.ptx_render.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.POINTER(RenderStats)]
         L.ptx_render_transparent.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.c_void_p, C.POINTER(RenderStats)]
         L.ptx_render_aov.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AovBuffers), C.POINTER(RenderStats)]
+        L.ptx_render_motion.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(MotionPrev), C.c_void_p, C.POINTER(RenderStats)]
         L.ptx_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p, C.POINTER(DenoiseStats)]
         L.ptx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AdaptiveCfg), C.c_void_p, C.c_void_p, C.POINTER(AdaptiveStats)]
         L.ptx_render_nee.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(NeeCfg), C.c_void_p, C.POINTER(NeeStats)]
         L.ptx_render_adaptive_nee.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AdaptiveCfg), C.POINTER(NeeCfg), C.c_void_p, C.c_void_p, C.POINTER(AdaptiveNeeStats)]
         L.ptx_denoise_counts.argtypes = [C.c_void_p, C.POINTER(DenoiseCountsCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p, C.POINTER(DenoiseStats)]
+        L.ptx_denoise_temporal.argtypes = [C.c_void_p, C.POINTER(TemporalCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p,
+                                           C.POINTER(TemporalHistory), C.POINTER(TemporalHistory), C.c_void_p, C.POINTER(TemporalStats)]
         L.ptx_adaptive_select.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.ptx_accum_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_ctx_set_mask_exchange.argtypes = [C.c_void_p, MASK_EXCHANGE_FN, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -390,6 +411,40 @@ class Context:
         st = DenoiseStats()
         _check(lib().ptx_denoise_counts(self.h, C.byref(cfg), _ptr(a), _ptr(b), C.byref(guides), _ptr(out), C.byref(st) if want_stats else None))
         return out, (dict(kernel_ms=st.kernel_ms, iterations=st.iterations, workspace_bytes=st.workspace_bytes) if want_stats else None)
+
+    def denoise_temporal(self, a, b, albedo_cov, normal_depth, motion, spp_a, spp_b, prev=None, next=None, iterations=0, sigma_l=0, sigma_n=0,
+                         sigma_z=0, max_history=0, tau_z=0, tau_n=0, out=None, want_out=True, want_stats=True):
+        """ptx_denoise_temporal: denoise() with last frame's history reprojected through `motion` and blended in before the filter.
+        a, b, albedo_cov, normal_depth as in denoise(); motion: [H,W,4] per-pixel sums of (previous minus current screen position, distance
+        from the previous camera, 1). prev: the (color [H,W,4], moments [H,W,2], geometry [H,W,4]) a previous call returned, None for the
+        first frame; next: three buffers to receive this frame's history (None = new ones), none of them one of prev's. All numpy or all
+        torch-on-GPU. max_history 0 = 32, tau_z and tau_n 0 = 0.1 and 0.9. want_out = False: advance the history only.
+        Returns (out or None, next, stats dict or None)."""
+        bufs = [a, b, albedo_cov, normal_depth, motion] + ([out] if out is not None else [])
+        shape = tuple(a.shape)
+        if len(shape) != 3 or shape[2] != 4 or any(tuple(x.shape) != shape for x in bufs):
+            raise ValueError(f"denoise_temporal: every buffer must be [H, W, 4] of one size, got {[tuple(x.shape) for x in bufs]}")
+        hist_shapes = (shape, shape[:2] + (2,), shape)
+        for name, h in (("prev", prev), ("next", next)):
+            if h is not None and (len(h) != 3 or any(tuple(x.shape) != s for x, s in zip(h, hist_shapes))):
+                raise ValueError(f"denoise_temporal: {name} must be (color [H,W,4], moments [H,W,2], geometry [H,W,4]) of the frame's size")
+        new = (lambda s: np.empty(s, np.float32)) if isinstance(a, np.ndarray) else a.new_empty   # no fill kernel on another stream
+        if next is None:
+            next = tuple(new(s) for s in hist_shapes)
+        if out is None and want_out:
+            out = new(shape)
+        cfg = TemporalCfg(shape[1], shape[0], spp_a, spp_b, iterations, sigma_l, sigma_n, sigma_z, max_history, tau_z, tau_n)
+        guides = AovBuffers(_ptr(albedo_cov), _ptr(normal_depth))
+        h_prev = None if prev is None else C.byref(TemporalHistory(*(_ptr(x) for x in prev)))
+        h_next = TemporalHistory(*(_ptr(x) for x in next))
+        st = TemporalStats()
+        _check(lib().ptx_denoise_temporal(self.h, C.byref(cfg), _ptr(a), _ptr(b), C.byref(guides), _ptr(motion), h_prev, C.byref(h_next),
+                                          _ptr(out) if want_out else None, C.byref(st) if want_stats else None))
+        stats = None
+        if want_stats:
+            stats = dict(kernel_ms=st.filter.kernel_ms, iterations=st.filter.iterations, workspace_bytes=st.filter.workspace_bytes,
+                         accumulate_ms=st.accumulate_ms, reprojected=st.reprojected, reset=st.reset)
+        return (out if want_out else None), tuple(next), stats
 
     def adaptive_select(self, a, b, threshold, done=None, want_list=True):
         """ptx_adaptive_select: one decision of ptx_render_adaptive's loop (include/ptx.h has the rule). a, b: [h,w,4] float32 radiance SUMS of
@@ -606,6 +661,37 @@ class Scene:
         _check(lib().ptx_render_aov(self.h, C.byref(cfg), C.byref(bufs), C.byref(st) if want_stats else None))
         stats = dict(rays=st.rays, samples=st.samples, passes=st.passes, kernel_ms=st.kernel_ms) if want_stats else None
         return albedo, normal_depth, stats
+
+    def render_motion(self, W, H, spp, prev_camera=None, prev_model_xform=None, motion=None, seed=0x5EED, tile=None, sample0=0, spp_per_pass=0,
+                      want_stats=True, shard=None):
+        """ptx_render_motion: per-pixel SUMS, over the camera samples [sample0, sample0+spp) that render() and render_aov() trace, of
+        (previous minus current screen position in pixels, distance from the previous camera, 1), ADDED into motion [h,w,4] float32 (numpy or
+        torch-on-GPU; None = zeros). prev_camera: what camera() returned one frame earlier (a dict with origin [3], basis [9], yfov; its lens
+        fields are ignored), None = the camera did not move. prev_model_xform: [n_models,12] float32 as array(ARR_MODEL_XFORM) held one frame
+        earlier, None = no model moved. Tiles, sample ranges and shards compose as in render_aov(). Returns (motion, stats dict or None)."""
+        x0, y0, w, h = tile if tile else (0, 0, W, H)
+        if motion is None:
+            motion = np.zeros((h, w, 4), np.float32)
+        cfg = RenderCfg(W, H, spp, 0, (C.c_float * 3)(1.0, 1.0, 1.0), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                        x0, y0, w, h, sample0, spp_per_pass, INTEGRATOR_LIB, *((tuple(shard) + (0,))[:3] if shard else (0, 0, 0)))
+        cam = xf = None
+        if prev_camera is not None:
+            o, b = np.asarray(prev_camera["origin"], np.float32).reshape(-1), np.asarray(prev_camera["basis"], np.float32).reshape(-1)
+            if len(o) != 3 or len(b) != 9:
+                raise PtxError(ERR_INVALID, "render_motion: the previous camera's origin is [3], its basis [9]")
+            cam = Camera((C.c_float * 3)(*o), (C.c_float * 9)(*b), prev_camera["yfov"], 0.0, 0.0, 0, 0.0)
+        if prev_model_xform is not None:
+            xf = np.ascontiguousarray(prev_model_xform, np.float32)
+            if xf.size % 12:
+                raise PtxError(ERR_INVALID, "render_motion: the previous transforms are not [n, 12]")
+        prev = None
+        if cam is not None or xf is not None:
+            prev = C.byref(MotionPrev(C.pointer(cam) if cam is not None else None, xf.ctypes.data if xf is not None else None,
+                                      xf.size // 12 if xf is not None else 0))
+        st = RenderStats()
+        _check(lib().ptx_render_motion(self.h, C.byref(cfg), prev, _ptr(motion), C.byref(st) if want_stats else None))
+        stats = dict(rays=st.rays, samples=st.samples, passes=st.passes, kernel_ms=st.kernel_ms) if want_stats else None
+        return motion, stats
 
     def render_adaptive(self, W, H, spp, bounces, min_spp=8, step_spp=0, threshold=0.1, a=None, b=None, env=(1.0, 1.0, 1.0), seed=0x5EED, tile=None,
                         sample0=0, spp_per_pass=0, want_stats=True, integrator=INTEGRATOR_LIB, shard=None):

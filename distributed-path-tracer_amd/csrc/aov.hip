@@ -8,6 +8,8 @@
 //                    two float4 records are stored by sample id. Samples that pass through are appended densely to the next round's stream
 //                    (wave ballot + lane prefix count, one atomic per wave)
 //   k_aov_resolve    adds a pixel's records in sample order into the caller's buffers (sums, bitwise reproducible, no float atomics)
+// ptx_render_motion walks the same samples through the same body (aov_shade_sample) and records, in place of the two guide records, where
+// the sample's surface point was on the previous frame's screen (k_aov_motion_shade); k_aov_resolve adds those records up as well.
 // Numerics as in kernels.hip: IEEE binary32 in the reference's operation order, no contraction.
 #include "device_core.hpp"
 
@@ -36,10 +38,45 @@ __global__ void __launch_bounds__(kAovBlock) k_aov_generate(DevScene S, RenderPa
 	out.dx[i] = d.x; out.dy[i] = d.y; out.dz[i] = d.z;
 }
 
-// One vertex of every live sample. TEX / ALPHA compile the texture lookups / the pass-through in, as the render variants do.
-template <bool TEX, bool ALPHA>
-__global__ void __launch_bounds__(kAovBlock) k_aov_shade(DevScene S, RenderParams P, AovStream in, AovHits H, uint32_t n, AovStream out, uint32_t* __restrict__ n_out,
-                                                         float4* __restrict__ rec, size_t rec_stride) {
+// project(cam, p) of ptx_render_motion (include/ptx.h): the pixel coordinates at which the pinhole camera sees the world point p; false
+// when p is not in front of it. The inverse of camera_get_ray for a basis that is a rotation times a uniform scale.
+DEV bool motion_project(const float* origin, const float* basis, float tan_half_fov, const RenderParams& P, V3 p, float& fx, float& fy) {
+	const V3 q = p - mk(origin[0], origin[1], origin[2]);
+	const float cx = dot(mk(basis[0], basis[1], basis[2]), q), cy = dot(mk(basis[3], basis[4], basis[5]), q), cz = dot(mk(basis[6], basis[7], basis[8]), q);
+	const float iz = 0 - cz;
+	const float ratio = (float)P.W / (float)P.H;
+	const float ndc_x = ((cx / iz) / ratio) / tan_half_fov, ndc_y = (cy / iz) / tan_half_fov;
+	fx = ((ndc_x + 1) * 0.5F) * (float)P.W;
+	fy = ((1 - ndc_y) * 0.5F) * (float)P.H;
+	return cz < 0;
+}
+
+// The motion record of a sample that ends on `surf` at `pos` (hit_attributes' position; its local point is recomputed from the same
+// corners with the same operations): (previous - current pixel position, distance from the previous camera, 1), or zeros when either
+// camera does not have the point in front of it.
+DEV float4 motion_record(const DevScene& S, const RenderParams& P, const AovMotion& Mo, int32_t surf, uint32_t tri_word, float b1, float b2, V3 pos) {
+	V3 pos_prev = pos;
+	const uint32_t m = S.surfaces[surf].model;
+	if (Mo.prev_xform && Mo.moved[m]) {
+		const float b0 = 1 - b1 - b2;
+		const float4* T = S.tris + 9 * (size_t)(tri_word & S.tri_id_mask);
+		const float4 A = T[0], B = T[1], C = T[2];
+		const V3 lp = mk(A.x, A.y, A.z) * b0 + mk(B.x, B.y, B.z) * b1 + mk(C.x, C.y, C.z) * b2;
+		const float* x = Mo.prev_xform + 12 * (size_t)m;   // origin, then the basis' columns
+		pos_prev = mulmv(x + 3, lp) + mk(x[0], x[1], x[2]);
+	}
+	float cx, cy, qx, qy;
+	const bool cur = motion_project(S.cam.origin, S.cam.basis, S.cam.tan_half_fov, P, pos, cx, cy);
+	const bool prv = motion_project(Mo.origin, Mo.basis, Mo.tan_half_fov, P, pos_prev, qx, qy);
+	if (!(cur && prv)) return make_float4(0.f, 0.f, 0.f, 0.f);
+	return make_float4(qx - cx, qy - cy, length(pos_prev - mk(Mo.origin[0], Mo.origin[1], Mo.origin[2])), 1.0f);
+}
+
+// One vertex of every live sample. TEX / ALPHA compile the texture lookups / the pass-through in, as the render variants do. MOTION: the
+// sample's surface is recorded as one motion record (rec[id]) instead of the two guide records.
+template <bool TEX, bool ALPHA, bool MOTION>
+DEV void aov_shade_sample(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* __restrict__ n_out,
+                          float4* __restrict__ rec, size_t rec_stride, const AovMotion* Mo) {
 	const uint32_t i = blockIdx.x * kAovBlock + threadIdx.x;
 	bool through = false;
 	V3 o = {0, 0, 0}, d = {0, 0, 1};
@@ -70,15 +107,22 @@ __global__ void __launch_bounds__(kAovBlock) k_aov_shade(DevScene S, RenderParam
 				}
 			}
 			if (!transparent) {   // the sample's surface, back-facing or not (renderer.cpp:478 is the integrator's business)
-				const V3 nrm = shading_normal(sf, me.normal_ts);   // intersect_result::get_normal()
-				uint32_t cx, cy, csample;
-				aov_sample_of(P, id, cx, cy, csample);
-				const V3 co = camera_ray_origin(S, P, cx, cy, csample);   // origin of THIS sample's camera ray: with a lens, its lens point
-				ra = make_float4(me.albedo.x, me.albedo.y, me.albedo.z, 1.0f);
-				rn = make_float4(nrm.x, nrm.y, nrm.z, length(sf.pos - co));
+				if constexpr (MOTION) {
+					ra = motion_record(S, P, *Mo, surf, (uint32_t)H.triangle[i] + S.surfaces[surf].tri_base, H.b1[i], H.b2[i], sf.pos);
+				} else {
+					const V3 nrm = shading_normal(sf, me.normal_ts);   // intersect_result::get_normal()
+					uint32_t cx, cy, csample;
+					aov_sample_of(P, id, cx, cy, csample);
+					const V3 co = camera_ray_origin(S, P, cx, cy, csample);   // origin of THIS sample's camera ray: with a lens, its lens point
+					ra = make_float4(me.albedo.x, me.albedo.y, me.albedo.z, 1.0f);
+					rn = make_float4(nrm.x, nrm.y, nrm.z, length(sf.pos - co));
+				}
 			}
 		}
-		if (!through) { rec[id] = ra; rec[rec_stride + id] = rn; }
+		if (!through) {
+			rec[id] = ra;
+			if constexpr (!MOTION) rec[rec_stride + id] = rn;
+		}
 	}
 	if constexpr (ALPHA) {
 		// dense append: one atomic per wave reserves the wave's entries, the lane prefix count places them
@@ -95,6 +139,18 @@ __global__ void __launch_bounds__(kAovBlock) k_aov_shade(DevScene S, RenderParam
 			out.id[pos] = id; out.pass[pos] = pass;
 		}
 	}
+}
+
+template <bool TEX, bool ALPHA>
+__global__ void __launch_bounds__(kAovBlock) k_aov_shade(DevScene S, RenderParams P, AovStream in, AovHits H, uint32_t n, AovStream out, uint32_t* __restrict__ n_out,
+                                                         float4* __restrict__ rec, size_t rec_stride) {
+	aov_shade_sample<TEX, ALPHA, false>(S, P, in, H, n, out, n_out, rec, rec_stride, nullptr);
+}
+
+template <bool TEX, bool ALPHA>
+__global__ void __launch_bounds__(kAovBlock) k_aov_motion_shade(DevScene S, RenderParams P, AovStream in, AovHits H, uint32_t n, AovStream out, uint32_t* __restrict__ n_out,
+                                                                float4* __restrict__ rec, AovMotion Mo) {
+	aov_shade_sample<TEX, ALPHA, true>(S, P, in, H, n, out, n_out, rec, 0, &Mo);
 }
 
 // Adds the pass's records of each pixel, in sample order, into the caller's buffers, as k_resolve does for radiance. A sample that ended on
@@ -136,6 +192,19 @@ hipError_t launch_aov_shade(const DevScene& S, const RenderParams& P, const AovS
 	} else {
 		if (S.any_alpha) hipLaunchKernelGGL((k_aov_shade<false, true>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, rec_stride);
 		else hipLaunchKernelGGL((k_aov_shade<false, false>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, rec_stride);
+	}
+	return hipGetLastError();
+}
+
+hipError_t launch_aov_motion_shade(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* n_out, float4* rec,
+                                   const AovMotion& Mo, hipStream_t stream) {
+	const dim3 grid((n + kAovBlock - 1) / kAovBlock), block(kAovBlock);
+	if (S.any_texture) {
+		if (S.any_alpha) hipLaunchKernelGGL((k_aov_motion_shade<true, true>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, Mo);
+		else hipLaunchKernelGGL((k_aov_motion_shade<true, false>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, Mo);
+	} else {
+		if (S.any_alpha) hipLaunchKernelGGL((k_aov_motion_shade<false, true>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, Mo);
+		else hipLaunchKernelGGL((k_aov_motion_shade<false, false>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, Mo);
 	}
 	return hipGetLastError();
 }

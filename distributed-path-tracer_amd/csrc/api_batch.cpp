@@ -27,6 +27,20 @@ struct DenoiseCall {
 	uint32_t spp_a, spp_b;
 };
 
+// Steps 2 to 5 of the filter on a prepared state: state[0] holds (col, v0), guide and remod what step 1 left. What ptx_denoise,
+// ptx_denoise_counts and ptx_denoise_temporal share after their own step 1. The caller holds the context's mutex.
+int denoise_filter(ptx_ctx* c, uint32_t W, uint32_t H, uint32_t iterations, float sigma_l, float sigma_n, float sigma_z, float4* const state[2], const float4* guide,
+                   const float4* remod, float4* d_out) {
+	const uint32_t tiled = denoise_tiled_steps();
+	HIP_TRY(launch_denoise_prefilter(state[0], guide, W, H, sigma_n, sigma_z, state[1], c->stream));
+	for (uint32_t i = 0; i < iterations; i++) {
+		const bool last = i + 1 == iterations;
+		const float4* in = state[(i + 1) & 1u];
+		HIP_TRY(launch_denoise_atrous(in, guide, remod, W, H, 1u << i, sigma_l, sigma_n, sigma_z, last, (tiled >> i) & 1u, last ? d_out : state[i & 1u], c->stream));
+	}
+	return PTX_OK;
+}
+
 int denoise_frame(ptx_ctx* c, const DenoiseCall& D, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, float* out_rgba, ptx_denoise_stats* stats) {
 	const std::string who = D.who;
 	// every refusal below is decided before any device work
@@ -60,16 +74,10 @@ int denoise_frame(ptx_ctx* c, const DenoiseCall& D, const float* accum_a, const 
 	float4* const d_out = s_out.as<float4>();
 	if (stats)
 		if (const int rc = PassFrame::ensure_events(c, 1); rc != PTX_OK) return rc;
-	const uint32_t tiled = denoise_tiled_steps();
 	if (stats) HIP_TRY(hipEventRecord(c->events[0], c->stream));
 	if (D.counts) HIP_TRY(launch_denoise_prepare_counts(in[0].as<float4>(), in[1].as<float4>(), in[2].as<float4>(), in[3].as<float4>(), D.spp_a, n, state[0], guide, remod, c->stream));
 	else HIP_TRY(launch_denoise_prepare(in[0].as<float4>(), in[1].as<float4>(), in[2].as<float4>(), in[3].as<float4>(), D.spp_a, D.spp_b, n, state[0], guide, remod, c->stream));
-	HIP_TRY(launch_denoise_prefilter(state[0], guide, W, H, sigma_n, sigma_z, state[1], c->stream));
-	for (uint32_t i = 0; i < iterations; i++) {
-		const bool last = i + 1 == iterations;
-		const float4* in = state[(i + 1) & 1u];
-		HIP_TRY(launch_denoise_atrous(in, guide, remod, W, H, 1u << i, sigma_l, sigma_n, sigma_z, last, (tiled >> i) & 1u, last ? d_out : state[i & 1u], c->stream));
-	}
+	if (const int rc = denoise_filter(c, W, H, iterations, sigma_l, sigma_n, sigma_z, state, guide, remod, d_out); rc != PTX_OK) return rc;
 	if (stats) HIP_TRY(hipEventRecord(c->events[1], c->stream));
 	HIP_TRY(s_out.copy_back(c));
 	if (stats || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
@@ -94,6 +102,112 @@ int ptx_denoise_counts(ptx_ctx* c, const ptx_denoise_counts_cfg* cfg, const floa
 	if (!cfg) return set_err(PTX_ERR_INVALID, "ptx_denoise_counts: NULL argument");
 	return denoise_frame(c, DenoiseCall{"ptx_denoise_counts", cfg->W, cfg->H, cfg->iterations, cfg->sigma_l, cfg->sigma_n, cfg->sigma_z, true, cfg->guide_spp, 0u}, accum_a, accum_b,
 	                     guides, out_rgba, stats);
+}
+
+int ptx_denoise_temporal(ptx_ctx* c, const ptx_temporal_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, const float* motion,
+                         const ptx_temporal_history* prev, const ptx_temporal_history* next, float* out_rgba, ptx_temporal_stats* stats) {
+	const std::string who = "ptx_denoise_temporal";
+	// every refusal below is decided before any device work; the context comes last of the arguments, so that a caller without a GPU meets
+	// every other refusal first
+	if (!cfg || !accum_a || !accum_b || !guides || !motion || !next) return set_err(PTX_ERR_INVALID, who + ": NULL argument");
+	if (!guides->albedo_cov || !guides->normal_depth) return set_err(PTX_ERR_INVALID, who + ": both guide buffers are required");
+	if (!next->color || !next->moments || !next->geometry) return set_err(PTX_ERR_INVALID, who + ": a member of next is NULL");
+	if (prev && (!prev->color || !prev->moments || !prev->geometry)) return set_err(PTX_ERR_INVALID, who + ": a member of prev is NULL (pass prev = NULL for the first frame)");
+	if (prev) {
+		const float* const np[3] = {next->color, next->moments, next->geometry};
+		const float* const pp[3] = {prev->color, prev->moments, prev->geometry};
+		for (const float* a : np)
+			for (const float* b : pp)
+				if (a == b) return set_err(PTX_ERR_INVALID, who + ": next shares a buffer with prev (neighbouring pixels of prev are read while next is written)");
+	}
+	if (!cfg->W || !cfg->H || cfg->W > 16384 || cfg->H > 16384) return set_err(PTX_ERR_INVALID, who + ": W and H must be in 1 .. 16384");
+	if (!cfg->spp_a || !cfg->spp_b) return set_err(PTX_ERR_INVALID, who + ": spp_a and spp_b must be > 0 (the noise estimate needs two half-frames)");
+	if (cfg->iterations > 8) return set_err(PTX_ERR_INVALID, who + ": at most 8 iterations");
+	if (!(cfg->sigma_l >= 0.0f) || !(cfg->sigma_n >= 0.0f) || !(cfg->sigma_z >= 0.0f)) return set_err(PTX_ERR_INVALID, who + ": a sigma is negative or NaN");
+	if (cfg->max_history > 1024) return set_err(PTX_ERR_INVALID, who + ": max_history above 1024");
+	if (!(cfg->tau_z >= 0.0f) || !(cfg->tau_n >= 0.0f)) return set_err(PTX_ERR_INVALID, who + ": a tau is negative or NaN");
+	if (!c) return set_err(PTX_ERR_INVALID, who + ": NULL context");
+	const bool dev = is_device_ptr(accum_a);
+	{
+		const void* all[12] = {accum_b, guides->albedo_cov, guides->normal_depth, motion, next->color, next->moments, next->geometry, prev ? prev->color : nullptr,
+		                       prev ? prev->moments : nullptr, prev ? prev->geometry : nullptr, out_rgba, nullptr};
+		for (const void* p : all)
+			if (p && is_device_ptr(p) != dev) return set_err(PTX_ERR_INVALID, who + ": the buffers must all be device or all be host memory");
+	}
+	const uint32_t W = cfg->W, H = cfg->H, iterations = cfg->iterations ? cfg->iterations : 5u;
+	const float sigma_l = cfg->sigma_l != 0.0f ? cfg->sigma_l : 4.0f, sigma_n = cfg->sigma_n != 0.0f ? cfg->sigma_n : 0.5f, sigma_z = cfg->sigma_z != 0.0f ? cfg->sigma_z : 0.1f;
+	TemporalParams T{};
+	T.W = (int)W; T.H = (int)H;
+	T.n = (float)(cfg->spp_a + cfg->spp_b); T.na = (float)cfg->spp_a; T.nb = (float)cfg->spp_b;
+	T.max_history = (float)(cfg->max_history ? cfg->max_history : 32u);
+	T.tau_z = cfg->tau_z != 0.0f ? cfg->tau_z : 0.1f;
+	T.tau_n = cfg->tau_n != 0.0f ? cfg->tau_n : 0.9f;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	if (stats) *stats = ptx_temporal_stats{};
+
+	// workspace: [state 0][state 1][guide][remod][counter slots], then the staging of host buffers: the five inputs, prev, next and the output
+	const size_t n = (size_t)W * H, b16 = n * sizeof(float4), b8 = n * sizeof(float2);
+	const size_t o_counter = 4 * b16, o_stage = o_counter + kTpCounterBytes;
+	const size_t ws_bytes = dev ? o_stage : o_stage + 5 * b16 + 2 * (2 * b16 + pad16(b8)) + b16;
+	HIP_TRY(c->denoise.ensure(ws_bytes));
+	float4* const ws = (float4*)c->denoise.p;
+	float4 *const state[2] = {ws, ws + n}, *const guide = ws + 2 * n, *const remod = ws + 3 * n;
+	unsigned long long* const counter = (unsigned long long*)((char*)c->denoise.p + o_counter);
+	size_t off = o_stage;
+	auto stage = [&](Staged& s, const void* p, size_t bytes, bool copy_in) {
+		const hipError_t e = s.bind(c, dev, p, bytes, c->denoise, off, copy_in);
+		off += pad16(bytes);   // an odd pixel count leaves the moments 8 bytes short of a float4 boundary
+		return e;
+	};
+	const void* const src[5] = {accum_a, accum_b, guides->albedo_cov, guides->normal_depth, motion};
+	Staged in[5], s_prev[3], s_next[3], s_out;
+	for (int k = 0; k < 5; k++) HIP_TRY(stage(in[k], src[k], b16, true));
+	const size_t hist_bytes[3] = {b16, b8, b16};
+	const void* const pp[3] = {prev ? prev->color : nullptr, prev ? prev->moments : nullptr, prev ? prev->geometry : nullptr};
+	const void* const np[3] = {next->color, next->moments, next->geometry};
+	for (int k = 0; k < 3; k++) {
+		if (prev) HIP_TRY(stage(s_prev[k], pp[k], hist_bytes[k], true));
+		else off += pad16(hist_bytes[k]);
+	}
+	for (int k = 0; k < 3; k++) HIP_TRY(stage(s_next[k], np[k], hist_bytes[k], kOutputOnly));
+	if (out_rgba) HIP_TRY(stage(s_out, out_rgba, b16, kOutputOnly));
+	const TemporalHistory d_prev{s_prev[0].as<float4>(), s_prev[1].as<float2>(), s_prev[2].as<float4>()};   // all nullptr without prev
+	const TemporalHistory d_next{s_next[0].as<float4>(), s_next[1].as<float2>(), s_next[2].as<float4>()};
+	if (stats)
+		if (const int rc = PassFrame::ensure_events(c, 2); rc != PTX_OK) return rc;
+	HIP_TRY(hipMemsetAsync(counter, 0, kTpCounterBytes, c->stream));
+	if (stats) HIP_TRY(hipEventRecord(c->events[0], c->stream));
+	HIP_TRY(launch_temporal_accumulate(in[0].as<float4>(), in[1].as<float4>(), in[2].as<float4>(), in[3].as<float4>(), in[4].as<float4>(), d_prev, d_next, T,
+	                                   out_rgba ? state[0] : nullptr, guide, remod, counter, c->stream));
+	if (stats) HIP_TRY(hipEventRecord(c->events[1], c->stream));   // the end of the accumulation and the start of the filter
+	if (out_rgba)
+		if (const int rc = denoise_filter(c, W, H, iterations, sigma_l, sigma_n, sigma_z, state, guide, remod, s_out.as<float4>()); rc != PTX_OK) return rc;
+	if (stats) HIP_TRY(hipEventRecord(c->events[2], c->stream));
+	for (const Staged& s : s_next) HIP_TRY(s.copy_back(c));
+	HIP_TRY(s_out.copy_back(c));
+	std::vector<unsigned long long> slots;
+	if (stats) {
+		slots.resize(kTpCounterSlots * kTpCounterStride);
+		HIP_TRY(hipMemcpyAsync(slots.data(), counter, kTpCounterBytes, hipMemcpyDeviceToHost, c->stream));
+	}
+	if (stats || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
+	if (stats) {
+		float t = 0;
+		HIP_TRY(hipEventElapsedTime(&t, c->events[0], c->events[1]));
+		stats->accumulate_ms = t;
+		if (out_rgba) {
+			HIP_TRY(hipEventElapsedTime(&t, c->events[1], c->events[2]));
+			stats->filter.kernel_ms = t;
+			stats->filter.iterations = iterations;
+		}
+		stats->filter.workspace_bytes = ws_bytes;
+		for (uint32_t k = 0; k < kTpCounterSlots; k++) {
+			stats->reprojected += slots[(size_t)k * kTpCounterStride] & 0xFFFFFFFFull;
+			stats->reset += slots[(size_t)k * kTpCounterStride] >> 32;
+		}
+	}
+	return PTX_OK;
 }
 
 namespace {

@@ -566,35 +566,65 @@ int ptx_intersect_batch(ptx_scene* sc, const ptx_rays* r, size_t n, const ptx_hi
 	return PTX_OK;
 }
 
-int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffers* out, ptx_render_stats* stats) {
-	// every refusal below is decided before any device work
-	if (!sc || !cfg || !out) return set_err(PTX_ERR_INVALID, "ptx_render_aov: NULL argument");
-	if (!out->albedo_cov && !out->normal_depth) return set_err(PTX_ERR_INVALID, "ptx_render_aov: both buffers are NULL (at least one must be given)");
+namespace {
+
+// ptx_render_aov and ptx_render_motion: the same refusals about the cfg and the scene, the same passes and rounds. motion == false: the two
+// guide buffers (either may be NULL); else `albedo_cov` is the motion buffer, k_aov_motion_shade writes one record per sample, and `prev`
+// (checked by the caller; may be NULL) is the previous frame.
+int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float* albedo_cov, float* normal_depth, bool motion, const ptx_motion_prev* prev,
+              ptx_render_stats* stats) {
+	const std::string who = who_c;
 	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
-		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_aov: PTX_INTEGRATOR_WORKER has no guide buffers here (the worker's opacity handling and its un-jittered "
+		return set_err(PTX_ERR_UNSUPPORTED, who + ": PTX_INTEGRATOR_WORKER has no first-hit buffers here (the worker's opacity handling and its un-jittered "
 		                                    "sample 0 are not pinned); use PTX_INTEGRATOR_LIB");
-	if (cfg->integrator > PTX_INTEGRATOR_WORKER) return set_err(PTX_ERR_INVALID, "ptx_render_aov: unknown integrator");
-	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_aov: scene was created without a GPU context (no CPU path exists)");
+	if (cfg->integrator > PTX_INTEGRATOR_WORKER) return set_err(PTX_ERR_INVALID, who + ": unknown integrator");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, who + ": scene was created without a GPU context (no CPU path exists)");
 	PassFrame f;
 	f.cfg = cfg;
-	if (const int rc = render_rect(cfg, "ptx_render_aov", false /* bounces are ignored */, f.x0, f.y0, f.w, f.h); rc != PTX_OK) return rc;
-	const bool dev_out = is_device_ptr(out->albedo_cov ? out->albedo_cov : out->normal_depth);
-	if (out->albedo_cov && out->normal_depth && is_device_ptr(out->normal_depth) != dev_out)
-		return set_err(PTX_ERR_INVALID, "ptx_render_aov: albedo_cov and normal_depth must both be device or both be host memory");
+	if (const int rc = render_rect(cfg, who_c, false /* bounces are ignored */, f.x0, f.y0, f.w, f.h); rc != PTX_OK) return rc;
+	const bool dev_out = is_device_ptr(albedo_cov ? albedo_cov : normal_depth);
+	if (albedo_cov && normal_depth && is_device_ptr(normal_depth) != dev_out)
+		return set_err(PTX_ERR_INVALID, who + ": albedo_cov and normal_depth must both be device or both be host memory");
 	ptx_ctx* c = sc->ctx;
 	std::lock_guard<std::mutex> lk(c->mu);
 	HIP_TRY(hipSetDevice(c->device));
 	if (stats) *stats = ptx_render_stats{};
 	// The workspace holds two ray streams, the hits and two records per sample (120 B), so the default bounds a pass by samples, not by the
 	// frame: 32 Mi (16 spp of a 1080p frame, 3.8 GB); sample ids are 32-bit
-	if (const int rc = f.plan(c, sc, "ptx_render_aov", nullptr, 32ull << 20, 0xFFFFFFFFull); rc != PTX_OK || !f.n_pass) return rc;
+	if (const int rc = f.plan(c, sc, who_c, nullptr, 32ull << 20, 0xFFFFFFFFull); rc != PTX_OK || !f.n_pass) return rc;
 
-	// workspace of one pass of `cap` samples: [256 B: live counts][stream 0][stream 1][hits][records]
+	// workspace of one pass of `cap` samples: [256 B: live counts][stream 0][stream 1][hits][records: two per sample, one for
+	// ptx_render_motion], then the previous transforms and the moved words of ptx_render_motion
 	const size_t cap = ((size_t)f.pass_spp * f.n_pixels + 3) & ~(size_t)3;   // array stride: keeps the float4 records 16-byte aligned
+	// the previous frame, read under the mutex the setters take: the camera (the scene's own when it did not move) and which models moved
+	const FlatScene& h = sc->host;
+	AovMotion Mo{};
+	std::vector<uint32_t> moved;
+	const float* prev_xform = nullptr;
+	if (motion) {
+		memcpy(Mo.origin, h.camera.origin, 12);
+		memcpy(Mo.basis, h.camera.basis, 36);
+		Mo.tan_half_fov = h.camera.tan_half_fov;
+		if (prev && prev->camera) {
+			memcpy(Mo.origin, prev->camera->origin, 12);
+			memcpy(Mo.basis, prev->camera->basis, 36);
+			Mo.tan_half_fov = std::tan(prev->camera->yfov * 0.5F);   // as ptx_scene_set_camera computes it
+		}
+		if (prev && prev->model_xform) {
+			moved.resize(prev->n_models);
+			for (size_t m = 0; m < moved.size(); m++) {
+				moved[m] = memcmp(prev->model_xform + 12 * m, &h.model_xform[12 * m], 48) != 0;
+				if (moved[m]) prev_xform = prev->model_xform;
+			}
+		}
+	}
+	const size_t n_models = prev_xform ? moved.size() : 0;
 	uint32_t* live_count = nullptr;
 	AovStream st[2];
 	float* hits = nullptr;
 	float4* rec = nullptr;
+	float* d_xform = nullptr;
+	uint32_t* d_moved = nullptr;
 	auto carve = [&](void* base) {
 		Carver k(base);
 		live_count = k.take<uint32_t>(64);
@@ -604,15 +634,24 @@ int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffe
 			s.id = k.take<uint32_t>(cap); s.pass = k.take<uint32_t>(cap);
 		}
 		hits = k.take<float>(6 * cap);
-		rec = k.take<float4>(2 * cap);
+		rec = k.take<float4>((motion ? 1 : 2) * cap);
+		d_xform = k.take<float>(12 * n_models);
+		d_moved = k.take<uint32_t>(n_models);
 		return k.off;
 	};
 	HIP_TRY(c->round_ws.ensure(carve(nullptr)));
 	carve(c->round_ws.p);
+	if (prev_xform) {   // behind whatever still reads the workspace; the sources are the caller's array and a local: synchronised before they go
+		HIP_TRY(hipMemcpyAsync(d_xform, prev_xform, 48 * n_models, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync(d_moved, moved.data(), 4 * n_models, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		Mo.prev_xform = d_xform;
+		Mo.moved = d_moved;
+	}
 
 	Staged s_albedo, s_normal;
-	if (out->albedo_cov) HIP_TRY(s_albedo.bind(c, dev_out, out->albedo_cov, f.rect_pixels() * sizeof(float4), c->stage_a));
-	if (out->normal_depth) HIP_TRY(s_normal.bind(c, dev_out, out->normal_depth, f.rect_pixels() * sizeof(float4), c->stage_b));
+	if (albedo_cov) HIP_TRY(s_albedo.bind(c, dev_out, albedo_cov, f.rect_pixels() * sizeof(float4), c->stage_a));
+	if (normal_depth) HIP_TRY(s_normal.bind(c, dev_out, normal_depth, f.rect_pixels() * sizeof(float4), c->stage_b));
 
 	if (stats)
 		if (const int rc = PassFrame::ensure_events(c, f.n_pass); rc != PTX_OK) return rc;
@@ -636,7 +675,8 @@ int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffe
 			const AovHits H{A.surface, A.triangle, A.b1, A.b2};
 			uint32_t* const n_out = live_count + (round & 1u);
 			if (follow) HIP_TRY(hipMemsetAsync(n_out, 0, 4, c->stream));
-			HIP_TRY(launch_aov_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, cap, c->stream));
+			if (motion) HIP_TRY(launch_aov_motion_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, Mo, c->stream));
+			else HIP_TRY(launch_aov_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, cap, c->stream));
 			if (!follow) break;
 			HIP_TRY(hipMemcpyAsync(&live, n_out, 4, hipMemcpyDeviceToHost, c->stream));
 			HIP_TRY(hipStreamSynchronize(c->stream));
@@ -649,6 +689,34 @@ int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffe
 	if (stats || !dev_out) HIP_TRY(hipStreamSynchronize(c->stream));
 	if (stats) return f.stats(c, rays, stats);
 	return PTX_OK;
+}
+
+}  // namespace
+
+int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffers* out, ptx_render_stats* stats) {
+	// every refusal, here and in aov_frame, is decided before any device work
+	if (!sc || !cfg || !out) return set_err(PTX_ERR_INVALID, "ptx_render_aov: NULL argument");
+	if (!out->albedo_cov && !out->normal_depth) return set_err(PTX_ERR_INVALID, "ptx_render_aov: both buffers are NULL (at least one must be given)");
+	return aov_frame(sc, cfg, "ptx_render_aov", out->albedo_cov, out->normal_depth, false, nullptr, stats);
+}
+
+int ptx_render_motion(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_motion_prev* prev, float* motion, ptx_render_stats* stats) {
+	// every refusal, here and in aov_frame, is decided before any device work
+	auto bad = [](const char* m) { return set_err(PTX_ERR_INVALID, std::string("ptx_render_motion: ") + m); };
+	if (!sc || !cfg || !motion) return bad("NULL argument");
+	if (prev && prev->model_xform) {
+		const size_t n_models = sc->host.model_xform.size() / 12;   // the size never changes after creation
+		if (prev->n_models != n_models) return bad("n_models differs from the scene's");
+		for (size_t k = 0; k < 12 * n_models; k++)
+			if (!std::isfinite(prev->model_xform[k])) return bad("a previous transform value is not finite");
+	}
+	if (prev && prev->camera) {   // what ptx_scene_set_camera refuses of a pinhole camera; the lens fields are ignored
+		const ptx_camera& pc = *prev->camera;
+		for (int k = 0; k < 3; k++) if (!std::isfinite(pc.origin[k])) return bad("the previous camera's origin is not finite");
+		for (int k = 0; k < 9; k++) if (!std::isfinite(pc.basis[k])) return bad("the previous camera's basis is not finite");
+		if (!std::isfinite(pc.yfov) || !(pc.yfov > 0) || !((double)pc.yfov < 3.14159265358979323846)) return bad("the previous camera's yfov must lie in (0, pi)");
+	}
+	return aov_frame(sc, cfg, "ptx_render_motion", motion, nullptr, true, prev, stats);
 }
 
 namespace {

@@ -206,6 +206,17 @@ hipError_t launch_aov_generate(const DevScene& S, const RenderParams& P, const A
 // no pass-through material (DevScene::any_alpha == 0)
 hipError_t launch_aov_shade(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* n_out,
                             float4* rec, size_t rec_stride, hipStream_t stream);
+// ptx_render_motion: the previous frame as k_aov_motion_shade takes it. The camera travels in the kernel argument; the transforms live in
+// context workspace.
+struct AovMotion {
+	float origin[3], basis[9], tan_half_fov;   // the previous camera (the current one when it did not move); a lens is ignored
+	const float* prev_xform;                   // [n_models][12] (origin, basis columns: PTX_ARR_MODEL_XFORM), or nullptr: no model moved
+	const uint32_t* moved;                     // [n_models] non-zero: the model's previous transform differs bitwise from its current one
+};
+// the same walk as launch_aov_shade; rec: [rec_stride] ONE record per sample, (previous - current pixel position, distance from the previous
+// camera, 1), zeros for a sample that contributes nothing. launch_aov_resolve(rec, ..., motion, nullptr, ...) adds them up.
+hipError_t launch_aov_motion_shade(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* n_out, float4* rec,
+                                   const AovMotion& Mo, hipStream_t stream);
 // adds the pass's records of each pixel, in sample order, into the caller's buffers (either may be nullptr)
 hipError_t launch_aov_resolve(const float4* rec, size_t rec_stride, float4* albedo_cov, float4* normal_depth, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp,
                               hipStream_t stream);
@@ -288,6 +299,28 @@ hipError_t launch_denoise_prefilter(const float4* in, const float4* guide, uint3
 // (same arithmetic in the same order). `out` must not be `in`.
 hipError_t launch_denoise_atrous(const float4* in, const float4* guide, const float4* remod, uint32_t W, uint32_t H, uint32_t step, float sigma_l, float sigma_n, float sigma_z,
                                  bool last, bool tiled, float4* out, hipStream_t stream);
+
+// Temporal accumulation in front of the filter (temporal.hip, ptx_denoise_temporal): k_tp_accumulate in k_dn_prepare's place.
+struct TemporalHistory {   // [n_pixels] each, device; all nullptr: no history (the first frame)
+	float4* color;      // integrated demodulated colour, history length
+	float2* moments;    // integrated first and second moment of the luminance
+	float4* geometry;   // mean normal, mean depth
+};
+struct TemporalParams {
+	int W, H;
+	float n, na, nb;   // float(spp_a + spp_b), float(spp_a), float(spp_b)
+	float max_history, tau_z, tau_n;
+};
+// The two pixel counts of a launch are spread over kTpCounterSlots words, kTpCounterStride words apart (a cache line each): every wave adds
+// to the slot of its workgroup with one atomic. With ONE word for the 32 400 waves of a 1080p frame the kernel took 0.40 ms on the MI355X, with
+// the slots 0.075 ms. The host adds the slots up.
+constexpr uint32_t kTpCounterSlots = 128, kTpCounterStride = 16;
+constexpr size_t kTpCounterBytes = (size_t)kTpCounterSlots * kTpCounterStride * sizeof(unsigned long long);
+// col_var == nullptr: only the history is advanced (guide and remod are not written either). counter (device, kTpCounterBytes, zeroed before
+// the launch): each slot receives pixels that took history in its low 32 bits and pixels that started over in its high 32.
+hipError_t launch_temporal_accumulate(const float4* a, const float4* b, const float4* albedo_cov, const float4* normal_depth, const float4* motion, const TemporalHistory& prev,
+                                      const TemporalHistory& next, const TemporalParams& T, float4* col_var, float4* guide, float4* remod, unsigned long long* counter,
+                                      hipStream_t stream);
 
 // Noise-driven per-pixel sample counts (adaptive.hip; ptx_render_adaptive, ptx_adaptive_select, ptx_accum_mean). A TILE is 32 x 32 pixels of the
 // rectangle, anchored at its origin (one workgroup), a BLOCK 8 x 8 (one wave-iteration): 16 blocks per tile, row-major.

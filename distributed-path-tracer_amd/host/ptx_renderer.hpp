@@ -263,6 +263,112 @@ public:
 		return a;
 	}
 
+	// Per-pixel motion SUMS of the frame's sample_count camera samples against the previous frame (ptx_render_motion), [H][W][4]: previous minus
+	// current screen position, distance from the previous camera, 1. prev_camera: the camera one frame earlier (nullptr: it did not move);
+	// prev_model_xform: the [n_models][12] transforms one frame earlier (nullptr or empty: no model moved). stats optional
+	std::vector<float> render_motion(const ptx_camera* prev_camera = nullptr, const std::vector<float>* prev_model_xform = nullptr, ptx_render_stats* stats = nullptr) const {
+		if (!scene_) throw std::runtime_error("render_motion() before load_gltf()");
+		apply_lens();
+		ptx_render_cfg c{};
+		c.W = resolution.x; c.H = resolution.y; c.spp = sample_count;
+		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
+		std::vector<float> motion((size_t)c.W * c.H * 4, 0.f);
+		const bool xf = prev_model_xform && !prev_model_xform->empty();
+		const ptx_motion_prev prev{prev_camera, xf ? prev_model_xform->data() : nullptr, xf ? (uint32_t)(prev_model_xform->size() / 12) : 0u};
+		check(ptx_render_motion(scene_, &c, (prev_camera || xf) ? &prev : nullptr, motion.data(), stats));
+		return motion;
+	}
+	// the loaded camera as stored, and the model transforms in PTX_ARR_MODEL_XFORM's layout: what a caller keeps as "one frame earlier"
+	ptx_camera camera() const {
+		if (!scene_) throw std::runtime_error("camera() before load_gltf()");
+		ptx_camera cam{};
+		check(ptx_scene_get_camera(scene_, &cam));
+		return cam;
+	}
+	std::vector<float> model_xforms() const {
+		if (!scene_) throw std::runtime_error("model_xforms() before load_gltf()");
+		const int64_t n = ptx_scene_get_array(scene_, PTX_ARR_MODEL_XFORM, nullptr, 0);
+		if (n < 0) throw std::runtime_error(ptx_last_error());
+		std::vector<float> x((size_t)n);
+		if (n && ptx_scene_get_array(scene_, PTX_ARR_MODEL_XFORM, x.data(), x.size() * sizeof(float)) != n) throw std::runtime_error(ptx_last_error());
+		return x;
+	}
+
+	// An animation through ptx_denoise_temporal: owns the two ping-ponged histories and the previous frame's camera and model transforms.
+	// frame() moves the scene (optionally), renders the two half-frames, the guides and the motion against the previous frame, accumulates and
+	// filters, and returns the filtered MEANS [H][W][4]. Frame k is rendered with the key seed + k, so that the frames' noise is independent.
+	// A change of resolution starts the history over. The renderer must outlive the sequence.
+	class temporal_sequence {
+	public:
+		explicit temporal_sequence(renderer& r) : r_(r) {}
+		ptx_temporal_cfg filter{};   // iterations, sigmas, max_history, taus (0 = the defaults); W, H and the sample counts are set per frame
+		uint32_t frames() const { return frames_; }
+		void restart() { have_ = false; }
+		// camera: the frame's pose (origin, basis, yfov; the lens stays the renderer's fields), nullptr = where it is; model_xform: the frame's
+		// [n_models][12] transforms, nullptr = where they are. stats optional
+		std::vector<float> frame(const ptx_camera* camera = nullptr, const std::vector<float>* model_xform = nullptr, ptx_temporal_stats* stats = nullptr) {
+			if (!r_.scene_) throw std::runtime_error("temporal_sequence::frame() before load_gltf()");
+			if (r_.transparent_background) throw std::runtime_error("temporal_sequence: the filter takes radiance sums, which transparent_background does not produce");
+			if (r_.sample_count < 2) throw std::runtime_error("temporal_sequence: sample_count must be at least 2 (the noise estimate needs two half-frames)");
+			if (camera) {
+				ptx_camera cam = *camera;
+				cam.lens_radius = r_.lens_radius; cam.focus_distance = r_.focus_distance; cam.blades = r_.blades; cam.blade_rotation = r_.blade_rotation;
+				check(ptx_scene_set_camera(r_.scene_, &cam));
+				r_.lens_set_ = lens{r_.lens_radius, r_.focus_distance, r_.blades, r_.blade_rotation};
+			} else {
+				r_.apply_lens();
+			}
+			if (model_xform) check(ptx_scene_set_model_xforms(r_.scene_, model_xform->data(), (uint32_t)(model_xform->size() / 12)));
+			if (r_.environment.string() != r_.env_set_) {
+				check(ptx_scene_set_environment(r_.scene_, r_.environment.empty() ? nullptr : r_.environment.string().c_str(), 1));
+				r_.env_set_ = r_.environment.string();
+			}
+			const uint32_t W = r_.resolution.x, H = r_.resolution.y, n = r_.sample_count;
+			const size_t px = (size_t)W * H;
+			if (W != w_ || H != h_) {
+				have_ = false; w_ = W; h_ = H;
+				for (history& h : hist_) { h.color.assign(px * 4, 0.f); h.moments.assign(px * 2, 0.f); h.geometry.assign(px * 4, 0.f); }
+			}
+			ptx_render_cfg c{};
+			c.W = W; c.H = H; c.bounces = r_.bounce_count;
+			for (int k = 0; k < 3; k++) c.env[k] = r_.environment_factor[k];
+			const uint64_t key = r_.seed + frames_;
+			c.seed_lo = (uint32_t)key; c.seed_hi = (uint32_t)(key >> 32);
+			std::vector<float> a(px * 4, 0.f), b(px * 4, 0.f), alb(px * 4, 0.f), nd(px * 4, 0.f), motion(px * 4, 0.f), out(px * 4, 0.f);
+			c.spp = n / 2;
+			check(ptx_render(r_.scene_, &c, a.data(), nullptr));
+			c.sample0 = c.spp; c.spp = n - c.sample0;
+			check(ptx_render(r_.scene_, &c, b.data(), nullptr));
+			c.sample0 = 0; c.spp = n;
+			const ptx_aov_buffers g{alb.data(), nd.data()};
+			check(ptx_render_aov(r_.scene_, &c, &g, nullptr));
+			const ptx_motion_prev mp{&prev_cam_, prev_xf_.empty() ? nullptr : prev_xf_.data(), (uint32_t)(prev_xf_.size() / 12)};
+			check(ptx_render_motion(r_.scene_, &c, have_ ? &mp : nullptr, motion.data(), nullptr));
+			ptx_temporal_cfg t = filter;
+			t.W = W; t.H = H; t.spp_a = n / 2; t.spp_b = n - n / 2;
+			history &hp = hist_[cur_], &hn = hist_[cur_ ^ 1u];
+			const ptx_temporal_history prev{hp.color.data(), hp.moments.data(), hp.geometry.data()}, next{hn.color.data(), hn.moments.data(), hn.geometry.data()};
+			check(ptx_denoise_temporal(r_.ctx_, &t, a.data(), b.data(), &g, motion.data(), have_ ? &prev : nullptr, &next, out.data(), stats));
+			cur_ ^= 1u;
+			have_ = true;
+			frames_++;
+			prev_cam_ = r_.camera();
+			prev_xf_ = r_.model_xforms();
+			return out;
+		}
+		// this frame's history: integrated demodulated colour + history length, luminance moments, mean normal + depth
+		const std::vector<float>& history_color() const { return hist_[cur_].color; }
+
+	private:
+		struct history { std::vector<float> color, moments, geometry; };
+		renderer& r_;
+		history hist_[2];
+		uint32_t cur_ = 0, w_ = 0, h_ = 0, frames_ = 0;
+		bool have_ = false;
+		ptx_camera prev_cam_{};
+		std::vector<float> prev_xf_;
+	};
+
 	// nee_candidates as the bits of ptx_nee_cfg::flags
 	uint32_t nee_bits() const {
 		if (nee_candidates < 1 || nee_candidates > 16) throw std::runtime_error("nee_candidates must be 1 .. 16");

@@ -335,6 +335,45 @@ typedef struct ptx_aov_buffers {
 } ptx_aov_buffers;
 int ptx_render_aov(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_aov_buffers* out, ptx_render_stats* stats);
 
+/* Per-sample screen-space motion for temporal reprojection (ptx_denoise_temporal; no counterpart in the reference): where on the PREVIOUS
+ * frame's screen the surface point of each camera sample was, given the previous camera and the previous model transforms. The scene is the
+ * current frame's (ptx_scene_set_camera, ptx_scene_set_model_xforms); `prev` is what the caller set one frame earlier.
+ * The camera samples, the walk through opacity pass-throughs (pass + 1, the 4096 bound) and the rule "the first vertex that does not pass
+ * through is the sample's surface" are ptx_render_aov's, word for word: the same cfg fields, the same Philox keys, the same intersect route.
+ * Per sample that ends on a surface, triangle (A, B, C) of model m, barycentrics b1, b2 (IEEE binary32, each operation rounded on its
+ * own, in the order written; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; M * v = per row (m.x*v.x + m.y*v.y) + m.z*v.z):
+ *   lp = A*b0 + B*b1 + C*b2 with b0 = 1 - b1 - b2 (local corners), pos = basis_m * lp + origin_m: the position ptx_hits reports.
+ *   pos_prev = pos — no arithmetic — if prev or prev->model_xform is NULL or model m's 12 previous floats are bitwise equal to its current
+ *   ones; else pos_prev = prev_basis_m * lp + prev_origin_m.
+ *   project(cam, p): q = p - cam.origin; c = (dot(basis.x, q), dot(basis.y, q), dot(basis.z, q)) with basis.x/y/z the basis' columns;
+ *     defined iff c.z < 0; iz = 0 - c.z; ndc_x = ((c.x / iz) / ratio) / tan_half_fov; ndc_y = (c.y / iz) / tan_half_fov;
+ *     fx = ((ndc_x + 1) * 0.5f) * float(W); fy = ((1 - ndc_y) * 0.5f) * float(H); ratio = float(W) / float(H);
+ *     tan_half_fov = std::tan(yfov * 0.5f) on the host, as at creation.
+ *     This is the inverse of the camera's ray (scene::camera::get_ray) for a basis that is a rotation times a uniform scale: the camera
+ *     sample through pixel position (fx, fy) sees p. Other bases are out of scope. A lens is ignored on both cameras: both projections go
+ *     through the camera's centre.
+ *   record = (fx_prev - fx_cur, fy_prev - fy_cur, length(pos_prev - prev_cam.origin), 1) with (fx_cur, fy_cur) = project(current camera,
+ *   pos) and (fx_prev, fy_prev) = project(previous camera, pos_prev). A sample contributes nothing if either projection is undefined, or
+ *   if it ends on a miss.
+ * The buffer holds SUMS, ADDED to what the caller passes in; a pixel's samples are added in sample order, so tiles, ascending adjacent
+ * sample ranges, spp_per_pass and shard_* compose exactly as in ptx_render_aov. .w counts the contributing samples: it equals
+ * albedo_cov.w wherever every surface sample lies in front of both cameras.
+ * Consequence: when nothing moved (prev NULL, or equal to the current state), .xy is exactly 0 in every pixel — identical operations on
+ * identical inputs.
+ * A call in which some model moved uploads the previous transforms and synchronises the context's stream once before its passes, device
+ * buffers and a NULL stats included; a call in which none did synchronises as ptx_render_aov does.
+ * stats as in ptx_render_aov. Refusals, all decided before any device work: everything ptx_render_aov refuses (PTX_ERR_UNSUPPORTED for
+ * PTX_INTEGRATOR_WORKER, PTX_ERR_NO_DEVICE for a host-only scene, ...); PTX_ERR_INVALID for a NULL motion, for n_models different from the
+ * scene's when model_xform is given, for a transform value that is not finite, and for a previous camera that ptx_scene_set_camera would
+ * refuse (its lens fields are ignored). */
+typedef struct ptx_motion_prev {
+	const ptx_camera* camera;   /* NULL: the camera did not move (the scene's current camera is used) */
+	const float* model_xform;   /* NULL: no model moved; else [n_models][12], host, layout of PTX_ARR_MODEL_XFORM */
+	uint32_t n_models;
+} ptx_motion_prev;
+int ptx_render_motion(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_motion_prev* prev /* NULL = nothing moved */,
+                      float* motion /* [h][w][4], device or host */, ptx_render_stats* stats /* NULL ok */);
+
 /* Variance-guided edge-avoiding a-trous filter on the guide buffers (no counterpart in the reference, which has no denoiser): turns a noisy
  * low-spp frame into a usable one. It takes its noise estimate from two half-frames, which ptx_render gives for free — sample ranges compose.
  *   accum_a, accum_b [H][W][4]: ptx_render radiance SUMS of two disjoint sample ranges of the same frame (e.g. [0, n/2) and [n/2, n)), of
@@ -401,6 +440,63 @@ typedef struct ptx_denoise_counts_cfg {
 } ptx_denoise_counts_cfg;
 int ptx_denoise_counts(ptx_ctx* ctx, const ptx_denoise_counts_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides,
                        float* out_rgba, ptx_denoise_stats* stats /* NULL ok */);
+
+/* ptx_denoise with a memory: the temporal half of SVGF in front of the filter. Last frame's integrated colour and luminance moments are
+ * reprojected through per-pixel motion, rejected where the geometry disagrees, and blended with the current frame; the filter then runs on
+ * the blend, with a variance taken from the integrated moments once a pixel's history is long enough. The frames of an animation stop
+ * boiling, and the samples earlier frames paid for are kept.
+ *   accum_a, accum_b, guides:  the current frame's two half-frame sums and its guide sums, as for ptx_denoise;
+ *   motion [H][W][4]:          per pixel, SUMS over the frame's samples of (previous minus current screen position in pixels, x and y;
+ *                              the surface point's distance from the previous camera; 1): the mean motion is .xy / .w, the depth the
+ *                              history is expected to hold is .z / .w. A pixel with .w not > 0 has no history;
+ *   prev:                      last frame's `next`, NULL for the first frame;
+ *   next:                      receives this frame's history. It must not share a buffer with prev: neighbouring pixels of prev are read;
+ *   out_rgba [H][W][4]:        receives MEANS, as ptx_denoise's; NULL = advance the history only (the filter is not run).
+ * All buffers are device memory or all are host memory. The history holds the accumulated UNFILTERED demodulated colour: the filter's
+ * output never feeds back, so its blur does not compound over the frames.
+ * Only step 1 of the filter's specification changes (same rounding rules: IEEE binary32, each operation rounded on its own, in the order
+ * written; max(a, b) and min(a, b) return the other operand when one is NaN). Per pixel p = (x, y):
+ *   1. alb, col, v0, alpha, nrm, z: exactly step 1 of ptx_denoise. L = lum(col).
+ *   2. Reprojection. No history if prev == NULL or !(motion.w > 0). Else mvx = motion.x / motion.w, mvy = motion.y / motion.w,
+ *      zexp = motion.z / motion.w; gx = ((float(x) + 0.5f) + mvx) - 0.5f, gy likewise; no history unless |gx| < 32768 and |gy| < 32768
+ *      (NaN fails). ix = floor(gx), wx = gx - ix; iy, wy likewise. The four taps q = (ix + dx, iy + dy), dy outer and dx inner from 0 to 1,
+ *      bq = (dx ? wx : 1 - wx) * (dy ? wy : 1 - wy). A tap is taken iff it lies inside the image, bq > 0, N_q > 0 (prev.color.w),
+ *      z_q > 0 (prev.geometry.w), |zexp - z_q| <= tau_z * max(zexp, z_q), and ((nrm.x*nq.x + nrm.y*nq.y) + nrm.z*nq.z) >= tau_n. A taken
+ *      tap adds sw += bq and acc += bq * h_q for each of colour r, g, b, N, mu1, mu2; a tap not taken adds nothing. sw > 0: h = acc / sw,
+ *      else no history. (A pixel without a surface sample has nrm = 0 and takes no tap.)
+ *   3. Blend. No history: col' = col, mu1' = L, mu2' = L * L, N' = 1 (assignments). With history: N' = min(h.N + 1, float(max_history)),
+ *      a = 1 / N', col' = h.col + (col - h.col) * a, mu1' = h.mu1 + (L - h.mu1) * a, mu2' = h.mu2 + (L*L - h.mu2) * a. If
+ *      ((col'.r + col'.g) + col'.b) + (mu1' + mu2') is not finite the pixel starts over as one without history: no recurrence keeps a NaN.
+ *   4. vf = N' < 4 ? v0 : max(0, mu2' - mu1' * mu1'); var = vf * (1 / N') — exactly v0 at N' = 1.
+ *   5. next.color = (col', N'), next.moments = (mu1', mu2'), next.geometry = (nrm, z); the filter's state is (col', var), its guide
+ *      (nrm, z), its re-modulation record (alb, alpha).
+ * Steps 2 to 5 of the filter, their kernels and both a-trous forms are ptx_denoise's.
+ * Consequences: with prev == NULL the output is bit for bit ptx_denoise's. With zero motion and a history equal to the frame (N = 1),
+ * col' is bitwise col and N' = 2: one tap has weight exactly 1, the three taps of weight 0 are skipped, and col + (col - col) * a = col.
+ * stats (may be NULL; NULL forces no synchronisation on device buffers): filter = ptx_denoise's stats of steps 2 to 5; accumulate_ms =
+ * HIP-event time of the accumulation kernel; reprojected + reset = W * H.
+ * PTX_ERR_INVALID — each decided before any device work — for what ptx_denoise refuses (out_rgba may be NULL here); a NULL motion or next
+ * or member of next; a NULL member of a non-NULL prev; next sharing a buffer with prev; max_history above 1024; a tau that is negative
+ * or NaN; pointers of mixed kinds. Out of scope: per-pixel sample counts, a wider search when all four taps fail, motion blur. */
+typedef struct ptx_temporal_history {
+	float* color;      /* [H][W][4]: integrated DEMODULATED colour rgb, w = history length N (float) */
+	float* moments;    /* [H][W][2]: integrated first and second moment of lum(col) */
+	float* geometry;   /* [H][W][4]: the frame's mean normal xyz and mean depth z, 0 for a pixel without a surface sample */
+} ptx_temporal_history;
+typedef struct ptx_temporal_cfg {
+	uint32_t W, H, spp_a, spp_b, iterations;   /* as in ptx_denoise_cfg */
+	float sigma_l, sigma_n, sigma_z;           /* as in ptx_denoise_cfg */
+	uint32_t max_history;                      /* 0 = 32; at most 1024 */
+	float tau_z, tau_n;                        /* 0 = 0.1, 0.9 */
+} ptx_temporal_cfg;
+typedef struct ptx_temporal_stats {
+	ptx_denoise_stats filter;
+	double accumulate_ms;
+	uint64_t reprojected, reset;   /* pixels that took history / that started over */
+} ptx_temporal_stats;
+int ptx_denoise_temporal(ptx_ctx* ctx, const ptx_temporal_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides,
+                         const float* motion, const ptx_temporal_history* prev /* NULL = first frame */, const ptx_temporal_history* next,
+                         float* out_rgba /* NULL = advance the history only */, ptx_temporal_stats* stats /* NULL ok */);
 
 /* Noise-driven per-pixel sample counts (no counterpart in the reference, which gives every pixel sample_count samples): a frame is rendered in
  * rounds, and a pixel whose two half-frames already agree, with all its neighbours, gets no further samples. On open, sun-lit scenes most

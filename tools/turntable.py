@@ -4,8 +4,13 @@ about the vertical axis through its origin (Scene.set_model_xforms). The scene i
 the time of creating the scene, which is what a second view cost before the setters existed.
 
   tools/turntable.py [--scene cornell|jack|atrium|PATH.gltf] [--frames N] [--size WxH] [--spp S] [--bounces B] [--spin MODEL] [--lens R:F[:BLADES[:ROT]]]
-                     [--nee] [--out PREFIX]
---out PREFIX writes PREFIX_000.png ...; without it the frames are rendered and dropped. The last line is one JSON record."""
+                     [--nee] [--out PREFIX] [--arc DEG] [--temporal [--ref-spp N]]
+--out PREFIX writes PREFIX_000.png ...; without it the frames are rendered and dropped. The last line is one JSON record.
+--arc DEG: the angle the camera covers over the frames (default: the full circle).
+--temporal: every frame goes through ptx_denoise_temporal — its two half-frames, its guides, its motion against the previous frame's camera
+and transforms (Scene.render_motion), the history of the frame before. Per frame: the accumulation kernel's and the filter's time, the share
+of pixels that took history, and the mean squared error (after x / (1 + x)) of the unfiltered frame, the ptx_denoise frame and the temporal
+frame against a frame of --ref-spp samples (default 512) of the same view. --out then writes the temporal frames."""
 import argparse
 import importlib
 import json
@@ -58,6 +63,9 @@ def main():
     ap.add_argument("--lens", default=None, metavar="R:F[:BLADES[:ROT]]")
     ap.add_argument("--nee", action="store_true", help="render with ptx_render_nee (fused form)")
     ap.add_argument("--out", default=None, metavar="PREFIX")
+    ap.add_argument("--arc", type=float, default=360.0, metavar="DEG")
+    ap.add_argument("--temporal", action="store_true", help="accumulate over the frames with ptx_denoise_temporal and compare with ptx_denoise")
+    ap.add_argument("--ref-spp", type=int, default=512)
     a = ap.parse_args()
     W, H = (int(v) for v in a.size.split("x"))
     lens = [float(v) for v in a.lens.split(":")] if a.lens else []
@@ -84,8 +92,17 @@ def main():
     centre = (np.min(corners, 0) + np.max(corners, 0)) / 2
     print(f"{a.scene}: {info['n_models']} models, {info['n_triangles']} triangles, {info['n_kd_nodes']} KD nodes; created in {create_ms:.1f} ms")
     cam_ms, xf_ms, render_ms = [], [], []
+    if a.temporal and a.spp < 2:
+        ap.error("--temporal needs --spp of at least 2 (two half-frames)")
+    render = (lambda **kw: s.render_nee(W, H, bounces=a.bounces, flags=ptx.NEE_FUSED, want_stats=False, **kw)[0]) if a.nee else \
+             (lambda **kw: s.render(W, H, bounces=a.bounces, want_stats=False, **kw)[0])
+    hist, prev_cam, prev_xf, acc_ms, filt_ms, share, mse = None, None, None, [], [], [], []
+
+    def err(x, ref):
+        tm = lambda v: np.asarray(v[..., :3], np.float64) / (1 + np.asarray(v[..., :3], np.float64))
+        return float(np.mean((tm(x) - tm(ref)) ** 2))
     for f in range(a.frames):
-        ang = 2 * np.pi * f / a.frames
+        ang = np.radians(a.arc) * f / a.frames
         o, b = orbit(cam["origin"], cam["basis"], centre, ang)
         t = time.perf_counter()
         s.set_camera(o, b, cam["yfov"], **lens_kw)
@@ -97,16 +114,38 @@ def main():
             xf_ms.append((time.perf_counter() - t) * 1e3)
             line += f", set_model_xforms {xf_ms[-1]:8.3f} ms ({xf_ms[-1] / create_ms * 100:.2f} % of creating the scene)"
         t = time.perf_counter()
-        acc, _ = (s.render_nee(W, H, a.spp, a.bounces, flags=ptx.NEE_FUSED) if a.nee else s.render(W, H, a.spp, a.bounces))
-        render_ms.append((time.perf_counter() - t) * 1e3)
-        print(line + f", render {render_ms[-1]:8.2f} ms")
+        if a.temporal:
+            half, seed = a.spp // 2, 0x5EED + f   # every frame its own key: the frames' noise is independent
+            ha, hb = render(spp=half, seed=seed), render(spp=a.spp - half, seed=seed, sample0=half)
+            A, N, _ = s.render_aov(W, H, a.spp, seed=seed, want_stats=False)
+            M, _ = s.render_motion(W, H, a.spp, prev_camera=prev_cam, prev_model_xform=prev_xf, seed=seed, want_stats=False)
+            out, hist, st = ctx.denoise_temporal(ha, hb, A, N, M, half, a.spp - half, prev=hist)
+            render_ms.append((time.perf_counter() - t) * 1e3)
+            prev_cam, prev_xf = s.camera(), s.array(ptx.ARR_MODEL_XFORM)
+            single, _ = ctx.denoise(ha, hb, A, N, half, a.spp - half)
+            ref = render(spp=a.ref_spp, seed=77) / np.float32(a.ref_spp)
+            acc_ms.append(st["accumulate_ms"]), filt_ms.append(st["kernel_ms"]), share.append(st["reprojected"] / (W * H))
+            mse.append((err((ha + hb) / np.float32(a.spp), ref), err(single, ref), err(out, ref)))
+            print(line + f", frame {render_ms[-1]:8.2f} ms; accumulate {acc_ms[-1]:.4f} ms, filter {filt_ms[-1]:.4f} ms, reprojected {share[-1] * 100:5.1f} %; "
+                  f"mse unfiltered {mse[-1][0]:.3e}, ptx_denoise {mse[-1][1]:.3e}, temporal {mse[-1][2]:.3e}")
+            acc, acc_spp = out, 1
+        else:
+            acc, _ = (s.render_nee(W, H, a.spp, a.bounces, flags=ptx.NEE_FUSED) if a.nee else s.render(W, H, a.spp, a.bounces))
+            render_ms.append((time.perf_counter() - t) * 1e3)
+            print(line + f", render {render_ms[-1]:8.2f} ms")
+            acc_spp = a.spp
         if a.out:
             with open(f"{a.out}_{f:03d}.png", "wb") as fh:
-                fh.write(ptx.encode_png(ctx.tonemap_encode(acc, W, H, a.spp)))
+                fh.write(ptx.encode_png(ctx.tonemap_encode(acc, W, H, acc_spp)))
     med = lambda v: float(np.median(v)) if v else None
     out = dict(scene=a.scene, frames=a.frames, W=W, H=H, spp=a.spp, create_ms=round(create_ms, 3), set_camera_ms=round(med(cam_ms), 4),
                set_model_xforms_ms=round(med(xf_ms), 3) if xf_ms else None, render_ms=round(med(render_ms), 3),
                set_model_xforms_share_of_create=round(med(xf_ms) / create_ms, 5) if xf_ms else None)
+    if a.temporal:   # medians over the frames that have a history
+        m = np.array(mse[1:] or mse)
+        out.update(temporal=dict(accumulate_ms=round(med(acc_ms[1:] or acc_ms), 4), filter_ms=round(med(filt_ms), 4), reprojected_share=round(med(share[1:] or share), 4),
+                                 ref_spp=a.ref_spp, mse_unfiltered=float(np.median(m[:, 0])), mse_denoise=float(np.median(m[:, 1])), mse_temporal=float(np.median(m[:, 2])),
+                                 last_frame_denoise_over_temporal=round(mse[-1][1] / mse[-1][2], 3)))
     print(json.dumps(out))
 
 
