@@ -116,6 +116,15 @@ class TemporalCfg(C.Structure):
                 ("tau_z", C.c_float), ("tau_n", C.c_float)]
 
 
+TEMPORAL_SEARCH_3X3, TEMPORAL_UNIT_NORMALS = 1, 2   # ptx_temporal_counts_cfg.flags
+
+
+class TemporalCountsCfg(C.Structure):
+    _fields_ = [("W", C.c_uint32), ("H", C.c_uint32), ("guide_spp", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float), ("max_history", C.c_uint32),
+                ("tau_z", C.c_float), ("tau_n", C.c_float), ("flags", C.c_uint32)]
+
+
 class TemporalStats(C.Structure):
     _fields_ = [("filter", DenoiseStats), ("accumulate_ms", C.c_double), ("reprojected", C.c_uint64), ("reset", C.c_uint64)]
 
@@ -256,6 +265,8 @@ def lib():
         L.ptx_denoise_counts.argtypes = [C.c_void_p, C.POINTER(DenoiseCountsCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p, C.POINTER(DenoiseStats)]
         L.ptx_denoise_temporal.argtypes = [C.c_void_p, C.POINTER(TemporalCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p,
                                            C.POINTER(TemporalHistory), C.POINTER(TemporalHistory), C.c_void_p, C.POINTER(TemporalStats)]
+        L.ptx_denoise_temporal_counts.argtypes = [C.c_void_p, C.POINTER(TemporalCountsCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p,
+                                                  C.POINTER(TemporalHistory), C.POINTER(TemporalHistory), C.c_void_p, C.POINTER(TemporalStats)]
         L.ptx_adaptive_select.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.ptx_accum_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_ctx_set_mask_exchange.argtypes = [C.c_void_p, MASK_EXCHANGE_FN, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -420,26 +431,41 @@ class Context:
         first frame; next: three buffers to receive this frame's history (None = new ones), none of them one of prev's. All numpy or all
         torch-on-GPU. max_history 0 = 32, tau_z and tau_n 0 = 0.1 and 0.9. want_out = False: advance the history only.
         Returns (out or None, next, stats dict or None)."""
+        return self._temporal(lib().ptx_denoise_temporal, "denoise_temporal", a, b, albedo_cov, normal_depth, motion, prev, next, out, want_out, want_stats,
+                              lambda W, H: TemporalCfg(W, H, spp_a, spp_b, iterations, sigma_l, sigma_n, sigma_z, max_history, tau_z, tau_n))
+
+    def denoise_temporal_counts(self, a, b, albedo_cov, normal_depth, motion, guide_spp, prev=None, next=None, iterations=0, sigma_l=0, sigma_n=0,
+                                sigma_z=0, max_history=0, tau_z=0, tau_n=0, flags=0, out=None, want_out=True, want_stats=True):
+        """ptx_denoise_temporal_counts: denoise_temporal() for half-buffers whose alpha channel is the per-pixel sample count
+        (Scene.render_adaptive, Scene.render_adaptive_nee), with a history counted in samples. albedo_cov, normal_depth, motion: the
+        Scene.render_aov and Scene.render_motion SUMS over guide_spp samples of every pixel, for an adaptive frame its first min_spp samples.
+        max_history is in samples (0 = min(32 * guide_spp, 1048576)); flags: TEMPORAL_SEARCH_3X3 | TEMPORAL_UNIT_NORMALS. prev is a history this
+        call returned, not denoise_temporal's. Everything else, and what is returned, as in denoise_temporal()."""
+        return self._temporal(lib().ptx_denoise_temporal_counts, "denoise_temporal_counts", a, b, albedo_cov, normal_depth, motion, prev, next, out, want_out,
+                              want_stats, lambda W, H: TemporalCountsCfg(W, H, guide_spp, iterations, sigma_l, sigma_n, sigma_z, max_history, tau_z, tau_n, flags))
+
+    def _temporal(self, fn, who, a, b, albedo_cov, normal_depth, motion, prev, next, out, want_out, want_stats, make_cfg):
+        """What denoise_temporal and denoise_temporal_counts share: the shape checks, the buffers they make, the call and the stats."""
         bufs = [a, b, albedo_cov, normal_depth, motion] + ([out] if out is not None else [])
         shape = tuple(a.shape)
         if len(shape) != 3 or shape[2] != 4 or any(tuple(x.shape) != shape for x in bufs):
-            raise ValueError(f"denoise_temporal: every buffer must be [H, W, 4] of one size, got {[tuple(x.shape) for x in bufs]}")
+            raise ValueError(f"{who}: every buffer must be [H, W, 4] of one size, got {[tuple(x.shape) for x in bufs]}")
         hist_shapes = (shape, shape[:2] + (2,), shape)
         for name, h in (("prev", prev), ("next", next)):
             if h is not None and (len(h) != 3 or any(tuple(x.shape) != s for x, s in zip(h, hist_shapes))):
-                raise ValueError(f"denoise_temporal: {name} must be (color [H,W,4], moments [H,W,2], geometry [H,W,4]) of the frame's size")
+                raise ValueError(f"{who}: {name} must be (color [H,W,4], moments [H,W,2], geometry [H,W,4]) of the frame's size")
         new = (lambda s: np.empty(s, np.float32)) if isinstance(a, np.ndarray) else a.new_empty   # no fill kernel on another stream
         if next is None:
             next = tuple(new(s) for s in hist_shapes)
         if out is None and want_out:
             out = new(shape)
-        cfg = TemporalCfg(shape[1], shape[0], spp_a, spp_b, iterations, sigma_l, sigma_n, sigma_z, max_history, tau_z, tau_n)
+        cfg = make_cfg(shape[1], shape[0])
         guides = AovBuffers(_ptr(albedo_cov), _ptr(normal_depth))
         h_prev = None if prev is None else C.byref(TemporalHistory(*(_ptr(x) for x in prev)))
         h_next = TemporalHistory(*(_ptr(x) for x in next))
         st = TemporalStats()
-        _check(lib().ptx_denoise_temporal(self.h, C.byref(cfg), _ptr(a), _ptr(b), C.byref(guides), _ptr(motion), h_prev, C.byref(h_next),
-                                          _ptr(out) if want_out else None, C.byref(st) if want_stats else None))
+        _check(fn(self.h, C.byref(cfg), _ptr(a), _ptr(b), C.byref(guides), _ptr(motion), h_prev, C.byref(h_next), _ptr(out) if want_out else None,
+                  C.byref(st) if want_stats else None))
         stats = None
         if want_stats:
             stats = dict(kernel_ms=st.filter.kernel_ms, iterations=st.filter.iterations, workspace_bytes=st.filter.workspace_bytes,

@@ -1,4 +1,4 @@
-// The batch entry points of the C ABI: ptx_denoise and ptx_denoise_counts, the adaptive decision, the mean of two half-frames, the kernels' unit-test batches
+// The batch entry points of the C ABI: ptx_denoise, ptx_denoise_counts and the two temporal calls, the adaptive decision, the mean of two half-frames, the kernels' unit-test batches
 // (PBR, leaf intersection, exact math, camera rays, materials), the framebuffer reduction, tone mapping and PNG encoding.
 #include <dlfcn.h>
 #include <zlib.h>
@@ -104,12 +104,27 @@ int ptx_denoise_counts(ptx_ctx* c, const ptx_denoise_counts_cfg* cfg, const floa
 	                     guides, out_rgba, stats);
 }
 
-int ptx_denoise_temporal(ptx_ctx* c, const ptx_temporal_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, const float* motion,
-                         const ptx_temporal_history* prev, const ptx_temporal_history* next, float* out_rgba, ptx_temporal_stats* stats) {
-	const std::string who = "ptx_denoise_temporal";
+namespace {
+
+// ptx_denoise_temporal and ptx_denoise_temporal_counts: the same refusals, workspace, staging and counters; they differ in step 1 and the
+// blend of the accumulation kernel. counts = false: spp_a, spp_b are the halves' sample counts and max_history counts frames; counts = true:
+// the halves carry per-pixel counts in .w, spp_a is guide_spp, max_history counts samples and flags are the PTX_TEMPORAL_* bits.
+struct TemporalCall {
+	const char* who;
+	uint32_t W, H, iterations;
+	float sigma_l, sigma_n, sigma_z;
+	bool counts;
+	uint32_t spp_a, spp_b, max_history;
+	float tau_z, tau_n;
+	uint32_t flags;
+};
+
+int temporal_frame(ptx_ctx* c, const TemporalCall* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, const float* motion,
+                   const ptx_temporal_history* prev, const ptx_temporal_history* next, float* out_rgba, ptx_temporal_stats* stats) {
+	const std::string who = cfg->who;
 	// every refusal below is decided before any device work; the context comes last of the arguments, so that a caller without a GPU meets
 	// every other refusal first
-	if (!cfg || !accum_a || !accum_b || !guides || !motion || !next) return set_err(PTX_ERR_INVALID, who + ": NULL argument");
+	if (!accum_a || !accum_b || !guides || !motion || !next) return set_err(PTX_ERR_INVALID, who + ": NULL argument");
 	if (!guides->albedo_cov || !guides->normal_depth) return set_err(PTX_ERR_INVALID, who + ": both guide buffers are required");
 	if (!next->color || !next->moments || !next->geometry) return set_err(PTX_ERR_INVALID, who + ": a member of next is NULL");
 	if (prev && (!prev->color || !prev->moments || !prev->geometry)) return set_err(PTX_ERR_INVALID, who + ": a member of prev is NULL (pass prev = NULL for the first frame)");
@@ -121,11 +136,14 @@ int ptx_denoise_temporal(ptx_ctx* c, const ptx_temporal_cfg* cfg, const float* a
 				if (a == b) return set_err(PTX_ERR_INVALID, who + ": next shares a buffer with prev (neighbouring pixels of prev are read while next is written)");
 	}
 	if (!cfg->W || !cfg->H || cfg->W > 16384 || cfg->H > 16384) return set_err(PTX_ERR_INVALID, who + ": W and H must be in 1 .. 16384");
-	if (!cfg->spp_a || !cfg->spp_b) return set_err(PTX_ERR_INVALID, who + ": spp_a and spp_b must be > 0 (the noise estimate needs two half-frames)");
+	if (cfg->counts && !cfg->spp_a) return set_err(PTX_ERR_INVALID, who + ": guide_spp must be > 0 (the samples of every pixel the guides and the motion hold)");
+	if (!cfg->counts && (!cfg->spp_a || !cfg->spp_b)) return set_err(PTX_ERR_INVALID, who + ": spp_a and spp_b must be > 0 (the noise estimate needs two half-frames)");
 	if (cfg->iterations > 8) return set_err(PTX_ERR_INVALID, who + ": at most 8 iterations");
 	if (!(cfg->sigma_l >= 0.0f) || !(cfg->sigma_n >= 0.0f) || !(cfg->sigma_z >= 0.0f)) return set_err(PTX_ERR_INVALID, who + ": a sigma is negative or NaN");
-	if (cfg->max_history > 1024) return set_err(PTX_ERR_INVALID, who + ": max_history above 1024");
+	if (cfg->counts && cfg->max_history > 1048576) return set_err(PTX_ERR_INVALID, who + ": max_history above 1048576 samples");
+	if (!cfg->counts && cfg->max_history > 1024) return set_err(PTX_ERR_INVALID, who + ": max_history above 1024");
 	if (!(cfg->tau_z >= 0.0f) || !(cfg->tau_n >= 0.0f)) return set_err(PTX_ERR_INVALID, who + ": a tau is negative or NaN");
+	if (cfg->flags & ~(PTX_TEMPORAL_SEARCH_3X3 | PTX_TEMPORAL_UNIT_NORMALS)) return set_err(PTX_ERR_INVALID, who + ": unknown bit in flags");
 	if (!c) return set_err(PTX_ERR_INVALID, who + ": NULL context");
 	const bool dev = is_device_ptr(accum_a);
 	{
@@ -138,8 +156,13 @@ int ptx_denoise_temporal(ptx_ctx* c, const ptx_temporal_cfg* cfg, const float* a
 	const float sigma_l = cfg->sigma_l != 0.0f ? cfg->sigma_l : 4.0f, sigma_n = cfg->sigma_n != 0.0f ? cfg->sigma_n : 0.5f, sigma_z = cfg->sigma_z != 0.0f ? cfg->sigma_z : 0.1f;
 	TemporalParams T{};
 	T.W = (int)W; T.H = (int)H;
-	T.n = (float)(cfg->spp_a + cfg->spp_b); T.na = (float)cfg->spp_a; T.nb = (float)cfg->spp_b;
-	T.max_history = (float)(cfg->max_history ? cfg->max_history : 32u);
+	if (cfg->counts) {   // n = float(guide_spp); the history is counted in samples
+		T.n = (float)cfg->spp_a;
+		T.max_history = (float)(cfg->max_history ? cfg->max_history : (uint32_t)std::min<uint64_t>(32ull * cfg->spp_a, 1048576ull));
+	} else {
+		T.n = (float)(cfg->spp_a + cfg->spp_b); T.na = (float)cfg->spp_a; T.nb = (float)cfg->spp_b;
+		T.max_history = (float)(cfg->max_history ? cfg->max_history : 32u);
+	}
 	T.tau_z = cfg->tau_z != 0.0f ? cfg->tau_z : 0.1f;
 	T.tau_n = cfg->tau_n != 0.0f ? cfg->tau_n : 0.9f;
 	std::lock_guard<std::mutex> lk(c->mu);
@@ -178,8 +201,13 @@ int ptx_denoise_temporal(ptx_ctx* c, const ptx_temporal_cfg* cfg, const float* a
 		if (const int rc = PassFrame::ensure_events(c, 2); rc != PTX_OK) return rc;
 	HIP_TRY(hipMemsetAsync(counter, 0, kTpCounterBytes, c->stream));
 	if (stats) HIP_TRY(hipEventRecord(c->events[0], c->stream));
-	HIP_TRY(launch_temporal_accumulate(in[0].as<float4>(), in[1].as<float4>(), in[2].as<float4>(), in[3].as<float4>(), in[4].as<float4>(), d_prev, d_next, T,
-	                                   out_rgba ? state[0] : nullptr, guide, remod, counter, c->stream));
+	if (cfg->counts)
+		HIP_TRY(launch_temporal_accumulate_counts(in[0].as<float4>(), in[1].as<float4>(), in[2].as<float4>(), in[3].as<float4>(), in[4].as<float4>(), d_prev, d_next, T,
+		                                          (cfg->flags & PTX_TEMPORAL_SEARCH_3X3) != 0, (cfg->flags & PTX_TEMPORAL_UNIT_NORMALS) != 0, out_rgba ? state[0] : nullptr, guide,
+		                                          remod, counter, c->stream));
+	else
+		HIP_TRY(launch_temporal_accumulate(in[0].as<float4>(), in[1].as<float4>(), in[2].as<float4>(), in[3].as<float4>(), in[4].as<float4>(), d_prev, d_next, T,
+		                                   out_rgba ? state[0] : nullptr, guide, remod, counter, c->stream));
 	if (stats) HIP_TRY(hipEventRecord(c->events[1], c->stream));   // the end of the accumulation and the start of the filter
 	if (out_rgba)
 		if (const int rc = denoise_filter(c, W, H, iterations, sigma_l, sigma_n, sigma_z, state, guide, remod, s_out.as<float4>()); rc != PTX_OK) return rc;
@@ -208,6 +236,24 @@ int ptx_denoise_temporal(ptx_ctx* c, const ptx_temporal_cfg* cfg, const float* a
 		}
 	}
 	return PTX_OK;
+}
+
+}  // namespace
+
+int ptx_denoise_temporal(ptx_ctx* c, const ptx_temporal_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, const float* motion,
+                         const ptx_temporal_history* prev, const ptx_temporal_history* next, float* out_rgba, ptx_temporal_stats* stats) {
+	if (!cfg) return set_err(PTX_ERR_INVALID, "ptx_denoise_temporal: NULL argument");
+	const TemporalCall call{"ptx_denoise_temporal", cfg->W, cfg->H, cfg->iterations, cfg->sigma_l, cfg->sigma_n, cfg->sigma_z, false, cfg->spp_a, cfg->spp_b, cfg->max_history,
+	                        cfg->tau_z, cfg->tau_n, 0u};
+	return temporal_frame(c, &call, accum_a, accum_b, guides, motion, prev, next, out_rgba, stats);
+}
+
+int ptx_denoise_temporal_counts(ptx_ctx* c, const ptx_temporal_counts_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides, const float* motion,
+                                const ptx_temporal_history* prev, const ptx_temporal_history* next, float* out_rgba, ptx_temporal_stats* stats) {
+	if (!cfg) return set_err(PTX_ERR_INVALID, "ptx_denoise_temporal_counts: NULL argument");
+	const TemporalCall call{"ptx_denoise_temporal_counts", cfg->W, cfg->H, cfg->iterations, cfg->sigma_l, cfg->sigma_n, cfg->sigma_z, true, cfg->guide_spp, 0u, cfg->max_history,
+	                        cfg->tau_z, cfg->tau_n, cfg->flags};
+	return temporal_frame(c, &call, accum_a, accum_b, guides, motion, prev, next, out_rgba, stats);
 }
 
 namespace {

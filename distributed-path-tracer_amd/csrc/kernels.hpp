@@ -321,6 +321,11 @@ constexpr size_t kTpCounterBytes = (size_t)kTpCounterSlots * kTpCounterStride * 
 hipError_t launch_temporal_accumulate(const float4* a, const float4* b, const float4* albedo_cov, const float4* normal_depth, const float4* motion, const TemporalHistory& prev,
                                       const TemporalHistory& next, const TemporalParams& T, float4* col_var, float4* guide, float4* remod, unsigned long long* counter,
                                       hipStream_t stream);
+// The same kernel for half-buffers with per-pixel sample counts in .w (ptx_denoise_temporal_counts): T.n = float(guide_spp), T.na and T.nb
+// are not read, T.max_history and the history length count samples. search, unit_normals: PTX_TEMPORAL_SEARCH_3X3, PTX_TEMPORAL_UNIT_NORMALS.
+hipError_t launch_temporal_accumulate_counts(const float4* a, const float4* b, const float4* albedo_cov, const float4* normal_depth, const float4* motion,
+                                             const TemporalHistory& prev, const TemporalHistory& next, const TemporalParams& T, bool search, bool unit_normals, float4* col_var,
+                                             float4* guide, float4* remod, unsigned long long* counter, hipStream_t stream);
 
 // Noise-driven per-pixel sample counts (adaptive.hip; ptx_render_adaptive, ptx_adaptive_select, ptx_accum_mean). A TILE is 32 x 32 pixels of the
 // rectangle, anchored at its origin (one workgroup), a BLOCK 8 x 8 (one wave-iteration): 16 blocks per tile, row-major.

@@ -294,7 +294,8 @@ public:
 		return x;
 	}
 
-	// An animation through ptx_denoise_temporal: owns the two ping-ponged histories and the previous frame's camera and model transforms.
+	// An animation through ptx_denoise_temporal (or, after set_adaptive, ptx_denoise_temporal_counts): owns the two ping-ponged histories and
+	// the previous frame's camera and model transforms.
 	// frame() moves the scene (optionally), renders the two half-frames, the guides and the motion against the previous frame, accumulates and
 	// filters, and returns the filtered MEANS [H][W][4]. Frame k is rendered with the key seed + k, so that the frames' noise is independent.
 	// A change of resolution starts the history over. The renderer must outlive the sequence.
@@ -335,32 +336,71 @@ public:
 			const uint64_t key = r_.seed + frames_;
 			c.seed_lo = (uint32_t)key; c.seed_hi = (uint32_t)(key >> 32);
 			std::vector<float> a(px * 4, 0.f), b(px * 4, 0.f), alb(px * 4, 0.f), nd(px * 4, 0.f), motion(px * 4, 0.f), out(px * 4, 0.f);
+			history &hp = hist_[cur_], &hn = hist_[cur_ ^ 1u];
+			const ptx_temporal_history prev{hp.color.data(), hp.moments.data(), hp.geometry.data()}, next{hn.color.data(), hn.moments.data(), hn.geometry.data()};
+			const ptx_aov_buffers g{alb.data(), nd.data()};
+			const ptx_motion_prev mp{&prev_cam_, prev_xf_.empty() ? nullptr : prev_xf_.data(), (uint32_t)(prev_xf_.size() / 12)};
+			if (adaptive_) {
+				// the halves with per-pixel counts (sample_count is the cap), the guides and the motion over the min_spp samples every pixel has
+				c.spp = n;
+				const ptx_adaptive_cfg ac{ad_min_, ad_step_, ad_threshold_};
+				if (ad_nee_) {
+					const ptx_nee_cfg nc{ad_nee_flags_ | r_.nee_bits()};
+					check(ptx_render_adaptive_nee(r_.scene_, &c, &ac, &nc, a.data(), b.data(), nullptr));
+				} else {
+					check(ptx_render_adaptive(r_.scene_, &c, &ac, a.data(), b.data(), nullptr));
+				}
+				c.spp = ad_min_;
+				check(ptx_render_aov(r_.scene_, &c, &g, nullptr));
+				check(ptx_render_motion(r_.scene_, &c, have_ ? &mp : nullptr, motion.data(), nullptr));
+				ptx_temporal_counts_cfg t{};
+				t.W = W; t.H = H; t.guide_spp = ad_min_; t.iterations = filter.iterations;
+				t.sigma_l = filter.sigma_l; t.sigma_n = filter.sigma_n; t.sigma_z = filter.sigma_z;
+				t.max_history = filter.max_history; t.tau_z = filter.tau_z; t.tau_n = filter.tau_n; t.flags = ad_temporal_flags_;
+				check(ptx_denoise_temporal_counts(r_.ctx_, &t, a.data(), b.data(), &g, motion.data(), have_ ? &prev : nullptr, &next, out.data(), stats));
+				return finish(out);
+			}
 			c.spp = n / 2;
 			check(ptx_render(r_.scene_, &c, a.data(), nullptr));
 			c.sample0 = c.spp; c.spp = n - c.sample0;
 			check(ptx_render(r_.scene_, &c, b.data(), nullptr));
 			c.sample0 = 0; c.spp = n;
-			const ptx_aov_buffers g{alb.data(), nd.data()};
 			check(ptx_render_aov(r_.scene_, &c, &g, nullptr));
-			const ptx_motion_prev mp{&prev_cam_, prev_xf_.empty() ? nullptr : prev_xf_.data(), (uint32_t)(prev_xf_.size() / 12)};
 			check(ptx_render_motion(r_.scene_, &c, have_ ? &mp : nullptr, motion.data(), nullptr));
 			ptx_temporal_cfg t = filter;
 			t.W = W; t.H = H; t.spp_a = n / 2; t.spp_b = n - n / 2;
-			history &hp = hist_[cur_], &hn = hist_[cur_ ^ 1u];
-			const ptx_temporal_history prev{hp.color.data(), hp.moments.data(), hp.geometry.data()}, next{hn.color.data(), hn.moments.data(), hn.geometry.data()};
 			check(ptx_denoise_temporal(r_.ctx_, &t, a.data(), b.data(), &g, motion.data(), have_ ? &prev : nullptr, &next, out.data(), stats));
-			cur_ ^= 1u;
-			have_ = true;
-			frames_++;
-			prev_cam_ = r_.camera();
-			prev_xf_ = r_.model_xforms();
-			return out;
+			return finish(out);
+		}
+		// Adaptive frames (ptx_denoise_temporal_counts): frame() renders the halves with ptx_render_adaptive, or with ptx_render_adaptive_nee when
+		// nee_flags is given (ptx_nee_cfg::flags, to which the renderer's nee_candidates adds its bits), the renderer's sample_count being the
+		// cap; the guides and the motion over the first min_spp samples; and keeps a history counted in samples: filter.max_history is then in
+		// samples. temporal_flags: PTX_TEMPORAL_*. The two kinds of history do not mix: the call starts the history over.
+		void set_adaptive(uint32_t min_spp, uint32_t step_spp, float threshold, const uint32_t* nee_flags = nullptr, uint32_t temporal_flags = 0) {
+			adaptive_ = true;
+			ad_min_ = min_spp; ad_step_ = step_spp; ad_threshold_ = threshold;
+			ad_nee_ = nee_flags != nullptr;
+			ad_nee_flags_ = nee_flags ? *nee_flags : 0u;
+			ad_temporal_flags_ = temporal_flags;
+			have_ = false;
 		}
 		// this frame's history: integrated demodulated colour + history length, luminance moments, mean normal + depth
 		const std::vector<float>& history_color() const { return hist_[cur_].color; }
 
 	private:
 		struct history { std::vector<float> color, moments, geometry; };
+		// the frame is in `next`: swap the histories and remember the scene's state as "one frame earlier"
+		std::vector<float> finish(std::vector<float>& out) {
+			cur_ ^= 1u;
+			have_ = true;
+			frames_++;
+			prev_cam_ = r_.camera();
+			prev_xf_ = r_.model_xforms();
+			return std::move(out);
+		}
+		bool adaptive_ = false, ad_nee_ = false;
+		uint32_t ad_min_ = 0, ad_step_ = 0, ad_nee_flags_ = 0, ad_temporal_flags_ = 0;
+		float ad_threshold_ = 0;
 		renderer& r_;
 		history hist_[2];
 		uint32_t cur_ = 0, w_ = 0, h_ = 0, frames_ = 0;

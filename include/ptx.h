@@ -477,7 +477,8 @@ int ptx_denoise_counts(ptx_ctx* ctx, const ptx_denoise_counts_cfg* cfg, const fl
  * HIP-event time of the accumulation kernel; reprojected + reset = W * H.
  * PTX_ERR_INVALID — each decided before any device work — for what ptx_denoise refuses (out_rgba may be NULL here); a NULL motion or next
  * or member of next; a NULL member of a non-NULL prev; next sharing a buffer with prev; max_history above 1024; a tau that is negative
- * or NaN; pointers of mixed kinds. Out of scope: per-pixel sample counts, a wider search when all four taps fail, motion blur. */
+ * or NaN; pointers of mixed kinds. Out of scope: motion blur. Per-pixel sample counts, a wider search when all four taps fail and a
+ * normal test on unit normals: ptx_denoise_temporal_counts below. */
 typedef struct ptx_temporal_history {
 	float* color;      /* [H][W][4]: integrated DEMODULATED colour rgb, w = history length N (float) */
 	float* moments;    /* [H][W][2]: integrated first and second moment of lum(col) */
@@ -497,6 +498,56 @@ typedef struct ptx_temporal_stats {
 int ptx_denoise_temporal(ptx_ctx* ctx, const ptx_temporal_cfg* cfg, const float* accum_a, const float* accum_b, const ptx_aov_buffers* guides,
                          const float* motion, const ptx_temporal_history* prev /* NULL = first frame */, const ptx_temporal_history* next,
                          float* out_rgba /* NULL = advance the history only */, ptx_temporal_stats* stats /* NULL ok */);
+/* ptx_denoise_temporal for ADAPTIVE frames: half-buffers whose .w is the per-pixel sample count (ptx_render_adaptive,
+ * ptx_render_adaptive_nee), and a history whose length is counted in SAMPLES, so that a frame, or a pixel of it, weighs what it holds.
+ *   accum_a, accum_b:  as for ptx_denoise_counts: the two halves' radiance SUMS, .w = the samples summed in that pixel;
+ *   guides, motion:    the ptx_render_aov and ptx_render_motion SUMS over [sample0, sample0 + guide_spp) of EVERY pixel (for an adaptive
+ *                      frame: over its min_spp samples), as for ptx_denoise_counts;
+ *   prev, next:        as for ptx_denoise_temporal, but history.color.w counts samples. A history of ptx_denoise_temporal is not one of
+ *                      this call's, nor the other way round;
+ *   buffers, kinds of memory, prev == NULL, out_rgba == NULL, stats, synchronisation, the workspace and the counters: ptx_denoise_temporal's.
+ * The specification is ptx_denoise_temporal's (same rounding rules) with these replacements. Per pixel p = (x, y):
+ *   1. Step 1 of ptx_denoise_counts: na = a.w, nb = b.w, n = na + nb, ng = float(guide_spp); alb, col, v0, alpha, nrm, z follow from
+ *      those as there. L = lum(col).
+ *   2. The four bilinear taps, unchanged, and the two flags.
+ *      PTX_TEMPORAL_UNIT_NORMALS: the normal test of every tap is ((u_p.x*u_q.x + u_p.y*u_q.y) + u_p.z*u_q.z) >= tau_n with
+ *      u = v.xyz / sqrt((v.x*v.x + v.y*v.y) + v.z*v.z) (three divisions by the exact square root) of nrm_p and of the tap's stored normal.
+ *      A zero normal gives NaN and fails. The stored geometry and the filter's guide stay the unnormalised means. (A normal-mapped or
+ *      curved pixel's mean normal is shorter than 1; against tau_n = 0.9 it cannot even match itself without this flag.)
+ *      PTX_TEMPORAL_SEARCH_3X3: if the motion was usable (motion.w > 0, |gx| < 32768 and |gy| < 32768) and sw is still 0 after the
+ *      four taps: rx = (int)floor(gx + 0.5f), ry likewise; the nine taps q = (rx + dx, ry + dy), dy outer and dx inner from -1 to 1. A tap
+ *      is taken iff it lies inside the image, N_q > 0, z_q > 0 and it passes the same depth and normal tests. A taken tap adds sw += 1
+ *      and acc += h_q (no multiplication). Then h = acc / sw if sw > 0, else no history.
+ *   3. Blend. No history: col' = col, mu1' = L, mu2' = L * L, N' = n. With history: N' = min(h.N + n, max(float(max_history), n)),
+ *      a = n / N', col' = h.col + (col - h.col) * a, mu1' and mu2' likewise. A blend that is not finite starts over, as before.
+ *   4. vf = N' < 4 * n ? v0 : max(0, mu2' - mu1' * mu1'); var = vf * (n / N').
+ *   5. As before, with next.color.w = N'.
+ * Consequences. (a) With flags == 0, uniform counts spp_a, spp_b whose sum n is a power of two, guide_spp = n and max_history = n * M,
+ * out_rgba, next.color.rgb, next.moments and next.geometry are bit for bit those of ptx_denoise_temporal with max_history = M, frame
+ * after frame, and next.color.w is n times its value: a scaling by a power of two commutes with every rounding, and n / (n x) and 1 / x
+ * round the same real number. (b) With prev == NULL the output is bit for bit ptx_denoise_counts'. (c) At zero motion over the same
+ * guides the history's colour is the pooled mean of all frames' samples, up to rounding: each frame enters with weight n / N'. (d) A
+ * pixel with n == 0 is non-finite, starts over every frame and is never taken as a tap (N_q > 0 fails); no adaptive frame has one.
+ * max_history below n gives N' = n and a = 1: the frame replaces the history.
+ * PTX_ERR_INVALID — each decided before any device work, in ptx_denoise_temporal's order — for what ptx_denoise_temporal refuses, with
+ * guide_spp == 0 in place of its spp_a / spp_b rule; max_history above 1048576; a bit of flags other than the two below.
+ * Out of scope: carrying history through pixels given no samples, seeding the adaptive loop from the history, transparent blends,
+ * several GPUs (reduce first, as for every filter here). */
+#define PTX_TEMPORAL_SEARCH_3X3   1u   /* a pixel whose four taps all fail searches the 3 x 3 texels around the rounded previous position */
+#define PTX_TEMPORAL_UNIT_NORMALS 2u   /* the normal test compares directions: both mean normals are normalised first */
+typedef struct ptx_temporal_counts_cfg {
+	uint32_t W, H;
+	uint32_t guide_spp;            /* samples of EVERY pixel summed in the guides and in motion */
+	uint32_t iterations;           /* as ptx_denoise_cfg */
+	float sigma_l, sigma_n, sigma_z;
+	uint32_t max_history;          /* in SAMPLES; 0 = min(32 * guide_spp, 1048576); at most 1048576 */
+	float tau_z, tau_n;            /* 0 = 0.1, 0.9 */
+	uint32_t flags;                /* PTX_TEMPORAL_* */
+} ptx_temporal_counts_cfg;
+int ptx_denoise_temporal_counts(ptx_ctx* ctx, const ptx_temporal_counts_cfg* cfg, const float* accum_a, const float* accum_b,
+                                const ptx_aov_buffers* guides, const float* motion, const ptx_temporal_history* prev /* NULL = first frame */,
+                                const ptx_temporal_history* next, float* out_rgba /* NULL = advance the history only */,
+                                ptx_temporal_stats* stats /* NULL ok */);
 
 /* Noise-driven per-pixel sample counts (no counterpart in the reference, which gives every pixel sample_count samples): a frame is rendered in
  * rounds, and a pixel whose two half-frames already agree, with all its neighbours, gets no further samples. On open, sun-lit scenes most

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Kernel time of k_tp_accumulate (ptx_denoise_temporal) next to the kernel it replaces, k_dn_prepare, and one a-trous iteration.
+"""Kernel time of k_tp_accumulate (ptx_denoise_temporal, and the instantiations of ptx_denoise_temporal_counts) next to the kernel it replaces, k_dn_prepare, and one a-trous iteration.
 
   tools/bench_temporal.py [W H reps]     Cornell, 8 + 8 spp, device buffers, default 1920 1080 20
 
@@ -11,7 +11,13 @@ The calls are alternated in one process, `reps` rounds after one warm-up round, 
   a-trous iteration            ptx_denoise(iterations = 2).kernel_ms - ptx_denoise(iterations = 1).kernel_ms: the iteration at step 2
 Bytes per pixel the algorithm needs: accumulate reads the frame's five float4 (80 B) and, with history, each history texel once (40 B: the
 four taps of neighbouring pixels overlap), and writes the history (40 B) and the filter's state, guide and re-modulation record (48 B);
-prepare reads 64 B and writes 48 B. Prints one JSON line.
+prepare reads 64 B and writes 48 B.
+  counts, ...                  ptx_denoise_temporal_counts' accumulate_ms on the same buffers (the halves' .w is 8 in every pixel, guide_spp 16): the
+                               instantiation with per-pixel counts, without a flag, with each and with both; the same 208 bytes per pixel
+  counts search, holes         the same with PTX_TEMPORAL_SEARCH_3X3 on a history whose N is 0 in the 2 x 2 blocks with (x // 2 + y // 2) % 3 == 0: at
+                               zero motion those pixels' one tap fails and they search (searched_share, counted as the reprojected pixels the flag
+                               adds); the searching pixels fetch 27 texels more, which the 208 bytes do not count
+Prints one JSON line.
 """
 import importlib
 import json
@@ -42,6 +48,13 @@ def main(W, H, reps):
     out = mk()
     hists = [(mk(), mk(2), mk()), (mk(), mk(2), mk())]
     ctx.denoise_temporal(a, b, A, N, M, 8, 8, next=hists[0], out=out)
+    holed = (hists[0][0].clone(), hists[0][1], hists[0][2])
+    yy, xx = torch.meshgrid(torch.arange(H, device="cuda:0"), torch.arange(W, device="cuda:0"), indexing="ij")
+    holed[0][..., 3][(xx // 2 + yy // 2) % 3 == 0] = 0
+    torch.cuda.synchronize()
+    counts_rows = (("counts_history", 0), ("counts_unit", ptx.TEMPORAL_UNIT_NORMALS), ("counts_search", ptx.TEMPORAL_SEARCH_3X3),
+                   ("counts_search_unit", ptx.TEMPORAL_SEARCH_3X3 | ptx.TEMPORAL_UNIT_NORMALS))
+    shares = {}
     best = {}
 
     def keep(k, v):
@@ -50,6 +63,16 @@ def main(W, H, reps):
         _, _, st = ctx.denoise_temporal(a, b, A, N, M, 8, 8, prev=hists[0], next=hists[1], iterations=1, out=out)
         share = st["reprojected"] / (W * H)
         _, _, s0 = ctx.denoise_temporal(a, b, A, N, M, 8, 8, next=hists[1], iterations=1, out=out)
+        for name, flags in counts_rows:
+            _, _, sc = ctx.denoise_temporal_counts(a, b, A, N, M, 16, prev=hists[0], next=hists[1], iterations=1, out=out, flags=flags)
+            if rep:
+                keep(name + "_ms", sc["accumulate_ms"])
+        _, _, sc = ctx.denoise_temporal_counts(a, b, A, N, M, 16, next=hists[1], iterations=1, out=out)
+        _, _, sh0 = ctx.denoise_temporal_counts(a, b, A, N, M, 16, prev=holed, next=hists[1], iterations=1, out=out)
+        _, _, sh1 = ctx.denoise_temporal_counts(a, b, A, N, M, 16, prev=holed, next=hists[1], iterations=1, out=out, flags=ptx.TEMPORAL_SEARCH_3X3)
+        shares = dict(holes_reprojected=sh0["reprojected"] / (W * H), holes_search_reprojected=sh1["reprojected"] / (W * H))
+        if rep:
+            keep("counts_first_ms", sc["accumulate_ms"]), keep("counts_holes_ms", sh0["accumulate_ms"]), keep("counts_search_holes_ms", sh1["accumulate_ms"])
         _, d1 = ctx.denoise(a, b, A, N, 8, 8, iterations=1, out=out)
         _, d2 = ctx.denoise(a, b, A, N, 8, 8, iterations=2, out=out)
         if rep:
@@ -64,7 +87,12 @@ def main(W, H, reps):
                           accumulate_first_ms=round(best["accumulate_first_ms"], 4), accumulate_first_bytes_per_pixel=168,
                           accumulate_first_GBs=gbs(168, best["accumulate_first_ms"]),
                           prepare_ms=round(prepare_ms, 4), prepare_bytes_per_pixel=112, prepare_GBs=gbs(112, prepare_ms),
-                          atrous_step2_ms=round(best["denoise2_ms"] - best["denoise1_ms"], 4))))
+                          atrous_step2_ms=round(best["denoise2_ms"] - best["denoise1_ms"], 4),
+                          **{k: round(best[k], 4) for k in sorted(best) if k.startswith("counts_")},
+                          **{name + "_GBs": gbs(208, best[name + "_ms"]) for name, _ in counts_rows},
+                          counts_first_GBs=gbs(168, best["counts_first_ms"]),
+                          searched_share=round(shares["holes_search_reprojected"] - shares["holes_reprojected"], 4),
+                          **{k: round(v, 4) for k, v in shares.items()})))
 
 
 if __name__ == "__main__":

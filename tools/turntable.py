@@ -4,13 +4,18 @@ about the vertical axis through its origin (Scene.set_model_xforms). The scene i
 the time of creating the scene, which is what a second view cost before the setters existed.
 
   tools/turntable.py [--scene cornell|jack|atrium|PATH.gltf] [--frames N] [--size WxH] [--spp S] [--bounces B] [--spin MODEL] [--lens R:F[:BLADES[:ROT]]]
-                     [--nee] [--out PREFIX] [--arc DEG] [--temporal [--ref-spp N]]
+                     [--nee] [--out PREFIX] [--arc DEG] [--temporal [--ref-spp N] [--adaptive MIN:CAP:THRESHOLD [--search] [--unit-normals]]]
 --out PREFIX writes PREFIX_000.png ...; without it the frames are rendered and dropped. The last line is one JSON record.
 --arc DEG: the angle the camera covers over the frames (default: the full circle).
 --temporal: every frame goes through ptx_denoise_temporal — its two half-frames, its guides, its motion against the previous frame's camera
 and transforms (Scene.render_motion), the history of the frame before. Per frame: the accumulation kernel's and the filter's time, the share
 of pixels that took history, and the mean squared error (after x / (1 + x)) of the unfiltered frame, the ptx_denoise frame and the temporal
-frame against a frame of --ref-spp samples (default 512) of the same view. --out then writes the temporal frames."""
+frame against a frame of --ref-spp samples (default 512) of the same view. --out then writes the temporal frames.
+--temporal --adaptive MIN:CAP:THRESHOLD: the halves come from ptx_render_adaptive (with --nee: ptx_render_adaptive_nee, fused form) with MIN
+samples at least and CAP at most, the guides and the motion from the first MIN samples, and the frames go through
+ptx_denoise_temporal_counts, whose history counts samples; --search and --unit-normals set PTX_TEMPORAL_SEARCH_3X3 and
+PTX_TEMPORAL_UNIT_NORMALS. Per frame: the mean count, the reprojected share, and the error of the unfiltered frame, the ptx_denoise_counts
+frame and the temporal-counts frame against the --ref-spp frame. --spp is not used."""
 import argparse
 import importlib
 import json
@@ -66,6 +71,9 @@ def main():
     ap.add_argument("--arc", type=float, default=360.0, metavar="DEG")
     ap.add_argument("--temporal", action="store_true", help="accumulate over the frames with ptx_denoise_temporal and compare with ptx_denoise")
     ap.add_argument("--ref-spp", type=int, default=512)
+    ap.add_argument("--adaptive", default=None, metavar="MIN:CAP:THRESHOLD", help="with --temporal: adaptive frames through ptx_denoise_temporal_counts")
+    ap.add_argument("--search", action="store_true", help="with --adaptive: PTX_TEMPORAL_SEARCH_3X3")
+    ap.add_argument("--unit-normals", action="store_true", help="with --adaptive: PTX_TEMPORAL_UNIT_NORMALS")
     a = ap.parse_args()
     W, H = (int(v) for v in a.size.split("x"))
     lens = [float(v) for v in a.lens.split(":")] if a.lens else []
@@ -92,6 +100,19 @@ def main():
     centre = (np.min(corners, 0) + np.max(corners, 0)) / 2
     print(f"{a.scene}: {info['n_models']} models, {info['n_triangles']} triangles, {info['n_kd_nodes']} KD nodes; created in {create_ms:.1f} ms")
     cam_ms, xf_ms, render_ms = [], [], []
+    adaptive = None
+    if a.adaptive:
+        if not a.temporal:
+            ap.error("--adaptive goes with --temporal")
+        try:
+            lo, cap, thr = a.adaptive.split(":")
+            adaptive = (int(lo), int(cap), float(thr))
+        except ValueError:
+            ap.error("--adaptive MIN:CAP:THRESHOLD")
+    elif a.search or a.unit_normals:
+        ap.error("--search and --unit-normals go with --adaptive")
+    tflags = (ptx.TEMPORAL_SEARCH_3X3 if a.search else 0) | (ptx.TEMPORAL_UNIT_NORMALS if a.unit_normals else 0)
+    mean_counts = []
     if a.temporal and a.spp < 2:
         ap.error("--temporal needs --spp of at least 2 (two half-frames)")
     render = (lambda **kw: s.render_nee(W, H, bounces=a.bounces, flags=ptx.NEE_FUSED, want_stats=False, **kw)[0]) if a.nee else \
@@ -114,7 +135,26 @@ def main():
             xf_ms.append((time.perf_counter() - t) * 1e3)
             line += f", set_model_xforms {xf_ms[-1]:8.3f} ms ({xf_ms[-1] / create_ms * 100:.2f} % of creating the scene)"
         t = time.perf_counter()
-        if a.temporal:
+        if adaptive:
+            lo, cap, thr = adaptive
+            seed = 0x5EED + f
+            ha, hb, _ = (s.render_adaptive_nee(W, H, cap, a.bounces, min_spp=lo, threshold=thr, seed=seed, flags=ptx.NEE_FUSED, want_stats=False) if a.nee else
+                         s.render_adaptive(W, H, cap, a.bounces, min_spp=lo, threshold=thr, seed=seed, want_stats=False))
+            A, N, _ = s.render_aov(W, H, lo, seed=seed, want_stats=False)
+            M, _ = s.render_motion(W, H, lo, prev_camera=prev_cam, prev_model_xform=prev_xf, seed=seed, want_stats=False)
+            out, hist, st = ctx.denoise_temporal_counts(ha, hb, A, N, M, lo, prev=hist, flags=tflags)
+            render_ms.append((time.perf_counter() - t) * 1e3)
+            prev_cam, prev_xf = s.camera(), s.array(ptx.ARR_MODEL_XFORM)
+            single, _ = ctx.denoise_counts(ha, hb, A, N, lo)
+            ref = render(spp=a.ref_spp, seed=77) / np.float32(a.ref_spp)
+            n = ha[..., 3:] + hb[..., 3:]
+            mean_counts.append(float(n.mean()))
+            acc_ms.append(st["accumulate_ms"]), filt_ms.append(st["kernel_ms"]), share.append(st["reprojected"] / (W * H))
+            mse.append((err((ha + hb) / n, ref), err(single, ref), err(out, ref)))
+            print(line + f", frame {render_ms[-1]:8.2f} ms; mean count {mean_counts[-1]:6.2f}, accumulate {acc_ms[-1]:.4f} ms, filter {filt_ms[-1]:.4f} ms, "
+                  f"reprojected {share[-1] * 100:5.1f} %; mse unfiltered {mse[-1][0]:.3e}, ptx_denoise_counts {mse[-1][1]:.3e}, temporal-counts {mse[-1][2]:.3e}")
+            acc, acc_spp = out, 1
+        elif a.temporal:
             half, seed = a.spp // 2, 0x5EED + f   # every frame its own key: the frames' noise is independent
             ha, hb = render(spp=half, seed=seed), render(spp=a.spp - half, seed=seed, sample0=half)
             A, N, _ = s.render_aov(W, H, a.spp, seed=seed, want_stats=False)
@@ -146,6 +186,8 @@ def main():
         out.update(temporal=dict(accumulate_ms=round(med(acc_ms[1:] or acc_ms), 4), filter_ms=round(med(filt_ms), 4), reprojected_share=round(med(share[1:] or share), 4),
                                  ref_spp=a.ref_spp, mse_unfiltered=float(np.median(m[:, 0])), mse_denoise=float(np.median(m[:, 1])), mse_temporal=float(np.median(m[:, 2])),
                                  last_frame_denoise_over_temporal=round(mse[-1][1] / mse[-1][2], 3)))
+        if adaptive:
+            out["temporal"].update(adaptive=a.adaptive, flags=tflags, mean_count=round(float(np.mean(mean_counts)), 3), mse_last=[float(v) for v in mse[-1]])
     print(json.dumps(out))
 
 
