@@ -258,6 +258,9 @@ def lib():
         L.ptx_render_transparent.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.c_void_p, C.POINTER(RenderStats)]
         L.ptx_render_aov.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AovBuffers), C.POINTER(RenderStats)]
         L.ptx_render_motion.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(MotionPrev), C.c_void_p, C.POINTER(RenderStats)]
+        L.ptx_render_emission.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.POINTER(RenderStats)]
+        L.ptx_emission_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.ptx_emission_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p]
         L.ptx_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseCfg), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_void_p, C.POINTER(DenoiseStats)]
         L.ptx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(AdaptiveCfg), C.c_void_p, C.c_void_p, C.POINTER(AdaptiveStats)]
         L.ptx_render_nee.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.POINTER(NeeCfg), C.c_void_p, C.POINTER(NeeStats)]
@@ -498,6 +501,28 @@ class Context:
         _check(lib().ptx_accum_mean(self.h, _ptr(a), _ptr(b), n, _ptr(out)))
         return out
 
+    def emission_split(self, emission, guide_spp, a, b=None):
+        """ptx_emission_split: takes the first-hit emission out of radiance sums before a filter call, in place. emission: [..., 4] float32
+        Scene.render_emission SUMS over guide_spp samples of every pixel; a, b: radiance SUMS of the same shape whose alpha channel is the
+        per-pixel sample count (b may be None); all numpy or all torch-on-GPU. Per channel with e = emission / guide_spp > 0:
+        a -= a.w * e. Returns (a, b)."""
+        self._emission_shapes("emission_split", emission, a, *([b] if b is not None else []))
+        _check(lib().ptx_emission_split(self.h, _ptr(emission), guide_spp, int(np.prod(tuple(a.shape)[:-1])), _ptr(a), _ptr(b)))
+        return a, b
+
+    def emission_merge(self, emission, guide_spp, out):
+        """ptx_emission_merge: adds the first-hit emission MEAN (emission / guide_spp, where > 0) to the MEANS a filter call returned for
+        halves that went through emission_split, in place. Buffers as in emission_split(). Returns out."""
+        self._emission_shapes("emission_merge", emission, out)
+        _check(lib().ptx_emission_merge(self.h, _ptr(emission), guide_spp, int(np.prod(tuple(out.shape)[:-1])), _ptr(out)))
+        return out
+
+    @staticmethod
+    def _emission_shapes(who, *bufs):
+        shape = tuple(bufs[0].shape)
+        if len(shape) < 1 or shape[-1] != 4 or any(tuple(x.shape) != shape for x in bufs):
+            raise ValueError(f"{who}: every buffer must be [..., 4] of one size, got {[tuple(x.shape) for x in bufs]}")
+
     def set_mask_exchange(self, exchange, mask=None):
         """ptx_ctx_set_mask_exchange: the merge of the noisy bytes over the ranks that Scene.render_adaptive / render_adaptive_nee with
         shard=(index, count > 1, ...) need (include/ptx.h has the sharded loop). exchange(mask, n_bytes) is called once per round after the
@@ -718,6 +743,21 @@ class Scene:
         _check(lib().ptx_render_motion(self.h, C.byref(cfg), prev, _ptr(motion), C.byref(st) if want_stats else None))
         stats = dict(rays=st.rays, samples=st.samples, passes=st.passes, kernel_ms=st.kernel_ms) if want_stats else None
         return motion, stats
+
+    def render_emission(self, W, H, spp, emission=None, seed=0x5EED, tile=None, sample0=0, spp_per_pass=0, want_stats=True, shard=None):
+        """ptx_render_emission: per-pixel SUMS, over the camera samples [sample0, sample0+spp) that render() and render_aov() trace, of what
+        each sample's surface emits towards the camera (emissive * 10, 1), ADDED into emission [h,w,4] float32 (numpy or torch-on-GPU;
+        None = zeros); a back-facing surface and a miss add nothing. On a scene without a sun the rgb is bitwise render(bounces=1,
+        env=(0, 0, 0)). Tiles, sample ranges and shards compose as in render_aov(). Returns (emission, stats dict or None)."""
+        x0, y0, w, h = tile if tile else (0, 0, W, H)
+        if emission is None:
+            emission = np.zeros((h, w, 4), np.float32)
+        cfg = RenderCfg(W, H, spp, 0, (C.c_float * 3)(1.0, 1.0, 1.0), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                        x0, y0, w, h, sample0, spp_per_pass, INTEGRATOR_LIB, *((tuple(shard) + (0,))[:3] if shard else (0, 0, 0)))
+        st = RenderStats()
+        _check(lib().ptx_render_emission(self.h, C.byref(cfg), _ptr(emission), C.byref(st) if want_stats else None))
+        stats = dict(rays=st.rays, samples=st.samples, passes=st.passes, kernel_ms=st.kernel_ms) if want_stats else None
+        return emission, stats
 
     def render_adaptive(self, W, H, spp, bounces, min_spp=8, step_spp=0, threshold=0.1, a=None, b=None, env=(1.0, 1.0, 1.0), seed=0x5EED, tile=None,
                         sample0=0, spp_per_pass=0, want_stats=True, integrator=INTEGRATOR_LIB, shard=None):
@@ -985,10 +1025,12 @@ class Renderer:
         inv = np.where(cov > 0, 1.0 / np.maximum(cov, 1.0), 0.0).astype(np.float32)
         return alb[..., :3] * inv[..., None], nd[..., :3] * inv[..., None], nd[..., 3] * inv, cov / np.float32(self.sample_count)
 
-    def render_denoised(self, iterations=0, sigma_l=0, sigma_n=0, sigma_z=0):
+    def render_denoised(self, iterations=0, sigma_l=0, sigma_n=0, sigma_z=0, split_emission=False):
         """The frame through the variance-guided a-trous filter (Context.denoise): renders samples [0, n/2) and [n/2, n) of
         sample_count = n into two buffers, the guide buffers of all n, and returns the filtered MEANS [H,W,4] (write them with
-        tonemap_encode(..., spp=1)). `last_denoise_stats` holds the filter's stats."""
+        tonemap_encode(..., spp=1)). `last_denoise_stats` holds the filter's stats. split_emission: the first-hit emission of the same n
+        samples (Scene.render_emission) is taken out of the halves before the filter and added to its output (Context.emission_split,
+        emission_merge)."""
         if self._scene is None:
             raise PtxError(ERR_INVALID, "render_denoised() before load_gltf()")
         if self.transparent_background:
@@ -1004,20 +1046,30 @@ class Renderer:
         a, _ = self._scene.render(W, H, n // 2, self.bounce_count, env=self.environment_factor, seed=self.seed, want_stats=False)
         b, _ = self._scene.render(W, H, n - n // 2, self.bounce_count, env=self.environment_factor, seed=self.seed, sample0=n // 2, want_stats=False)
         alb, nd, _ = self._scene.render_aov(W, H, n, seed=self.seed, want_stats=False)
+        em = None
+        if split_emission:
+            em, _ = self._scene.render_emission(W, H, n, seed=self.seed, want_stats=False)
+            self._ctx.emission_split(em, n, a, b)
         out, self.last_denoise_stats = self._ctx.denoise(a, b, alb, nd, n // 2, n - n // 2, iterations, sigma_l, sigma_n, sigma_z, out=a)
-        return out
+        return self._ctx.emission_merge(em, n, out) if split_emission else out
 
-    def _denoise_counts(self, a, b, min_spp):
-        """The adaptive halves through Context.denoise_counts, with the guides of the first min_spp samples (every pixel has them)."""
+    def _denoise_counts(self, a, b, min_spp, split_emission=False):
+        """The adaptive halves through Context.denoise_counts, with the guides of the first min_spp samples (every pixel has them).
+        split_emission: the first-hit emission of the same min_spp samples goes round the filter."""
         W, H = self.resolution
         alb, nd, _ = self._scene.render_aov(W, H, min_spp, seed=self.seed, want_stats=False)
+        em = None
+        if split_emission:
+            em, _ = self._scene.render_emission(W, H, min_spp, seed=self.seed, want_stats=False)
+            self._ctx.emission_split(em, min_spp, a, b)
         out, self.last_denoise_stats = self._ctx.denoise_counts(a, b, alb, nd, min_spp, out=a)
-        return out
+        return self._ctx.emission_merge(em, min_spp, out) if split_emission else out
 
-    def render_adaptive(self, threshold=0.1, min_spp=8, step_spp=0, denoise=False):
+    def render_adaptive(self, threshold=0.1, min_spp=8, step_spp=0, denoise=False, split_emission=False):
         """The frame with noise-driven per-pixel sample counts (Scene.render_adaptive, sample_count = the cap), as MEANS [H,W,4] (write them
         with tonemap_encode(..., spp=1)); the alpha channel is 1. `last_adaptive_stats` holds the stats; samples / (W * H) is the mean count.
-        denoise: the frame through the filter (Context.denoise_counts, guides of the first min_spp samples); `last_denoise_stats` holds its stats."""
+        denoise: the frame through the filter (Context.denoise_counts, guides of the first min_spp samples); `last_denoise_stats` holds its stats.
+        split_emission (with denoise): as in render_denoised(), over the first min_spp samples."""
         if self._scene is None:
             raise PtxError(ERR_INVALID, "render_adaptive() before load_gltf()")
         if self.transparent_background:
@@ -1029,11 +1081,11 @@ class Renderer:
             self._env_set = self.environment
         a, b, self.last_adaptive_stats = self._scene.render_adaptive(W, H, self.sample_count, self.bounce_count, min_spp, step_spp, threshold,
                                                                      env=self.environment_factor, seed=self.seed)
-        return self._denoise_counts(a, b, min_spp) if denoise else self._ctx.accum_mean(a, b, out=a)
+        return self._denoise_counts(a, b, min_spp, split_emission) if denoise else self._ctx.accum_mean(a, b, out=a)
 
-    def render_adaptive_nee(self, flags=0, threshold=0.1, min_spp=8, step_spp=0, denoise=False, candidates=1):
+    def render_adaptive_nee(self, flags=0, threshold=0.1, min_spp=8, step_spp=0, denoise=False, candidates=1, split_emission=False):
         """render_adaptive() on render_nee()'s estimator (Scene.render_adaptive_nee; flags: ptx_nee_cfg.flags, candidates: NEE_CANDIDATES): the MEANS [H,W,4], through the
-        filter with denoise. `last_adaptive_stats` holds the stats, the light-sampling ones included."""
+        filter with denoise, and with split_emission as in render_adaptive(). `last_adaptive_stats` holds the stats, the light-sampling ones included."""
         if self._scene is None:
             raise PtxError(ERR_INVALID, "render_adaptive_nee() before load_gltf()")
         if self.transparent_background:
@@ -1045,7 +1097,7 @@ class Renderer:
             self._env_set = self.environment
         a, b, self.last_adaptive_stats = self._scene.render_adaptive_nee(W, H, self.sample_count, self.bounce_count, min_spp, step_spp, threshold,
                                                                          env=self.environment_factor, seed=self.seed, flags=flags, candidates=candidates)
-        return self._denoise_counts(a, b, min_spp) if denoise else self._ctx.accum_mean(a, b, out=a)
+        return self._denoise_counts(a, b, min_spp, split_emission) if denoise else self._ctx.accum_mean(a, b, out=a)
 
     def render_nee(self, flags=0, candidates=1):
         """Radiance SUMS [H,W,4] of the frame with next-event estimation towards the scene's emissive triangles (Scene.render_nee):

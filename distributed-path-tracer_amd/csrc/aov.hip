@@ -10,6 +10,8 @@
 //   k_aov_resolve    adds a pixel's records in sample order into the caller's buffers (sums, bitwise reproducible, no float atomics)
 // ptx_render_motion walks the same samples through the same body (aov_shade_sample) and records, in place of the two guide records, where
 // the sample's surface point was on the previous frame's screen (k_aov_motion_shade); k_aov_resolve adds those records up as well.
+// ptx_render_emission does the same with what the integrator adds at that surface: its emission, when the surface faces the ray
+// (k_aov_emission_shade).
 // Numerics as in kernels.hip: IEEE binary32 in the reference's operation order, no contraction.
 #include "device_core.hpp"
 
@@ -72,9 +74,11 @@ DEV float4 motion_record(const DevScene& S, const RenderParams& P, const AovMoti
 	return make_float4(qx - cx, qy - cy, length(pos_prev - mk(Mo.origin[0], Mo.origin[1], Mo.origin[2])), 1.0f);
 }
 
-// One vertex of every live sample. TEX / ALPHA compile the texture lookups / the pass-through in, as the render variants do. MOTION: the
-// sample's surface is recorded as one motion record (rec[id]) instead of the two guide records.
-template <bool TEX, bool ALPHA, bool MOTION>
+// What a sample's surface is recorded as: the two guide records, or ONE record (rec[id]) of motion or of emission.
+enum : int { AOV_GUIDES = 0, AOV_MOTION = 1, AOV_EMISSION = 2 };
+
+// One vertex of every live sample. TEX / ALPHA compile the texture lookups / the pass-through in, as the render variants do.
+template <bool TEX, bool ALPHA, int KIND>
 DEV void aov_shade_sample(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* __restrict__ n_out,
                           float4* __restrict__ rec, size_t rec_stride, const AovMotion* Mo) {
 	const uint32_t i = blockIdx.x * kAovBlock + threadIdx.x;
@@ -107,7 +111,12 @@ DEV void aov_shade_sample(const DevScene& S, const RenderParams& P, const AovStr
 				}
 			}
 			if (!transparent) {   // the sample's surface, back-facing or not (renderer.cpp:478 is the integrator's business)
-				if constexpr (MOTION) {
+				if constexpr (KIND == AOV_EMISSION) {
+					// shade_vertex at depth 0: L = 0 + 1 * emissive10 unless the surface faces away (renderer.cpp:478-479). d is the direction
+					// of the ray that found the surface, as the stream holds it
+					const V3 nrm = shading_normal(sf, me.normal_ts), outcoming = -mk(in.dx[i], in.dy[i], in.dz[i]);
+					if (dot(nrm, outcoming) > 0) ra = make_float4(me.emissive10.x, me.emissive10.y, me.emissive10.z, 1.0f);
+				} else if constexpr (KIND == AOV_MOTION) {
 					ra = motion_record(S, P, *Mo, surf, (uint32_t)H.triangle[i] + S.surfaces[surf].tri_base, H.b1[i], H.b2[i], sf.pos);
 				} else {
 					const V3 nrm = shading_normal(sf, me.normal_ts);   // intersect_result::get_normal()
@@ -121,7 +130,7 @@ DEV void aov_shade_sample(const DevScene& S, const RenderParams& P, const AovStr
 		}
 		if (!through) {
 			rec[id] = ra;
-			if constexpr (!MOTION) rec[rec_stride + id] = rn;
+			if constexpr (KIND == AOV_GUIDES) rec[rec_stride + id] = rn;
 		}
 	}
 	if constexpr (ALPHA) {
@@ -144,13 +153,19 @@ DEV void aov_shade_sample(const DevScene& S, const RenderParams& P, const AovStr
 template <bool TEX, bool ALPHA>
 __global__ void __launch_bounds__(kAovBlock) k_aov_shade(DevScene S, RenderParams P, AovStream in, AovHits H, uint32_t n, AovStream out, uint32_t* __restrict__ n_out,
                                                          float4* __restrict__ rec, size_t rec_stride) {
-	aov_shade_sample<TEX, ALPHA, false>(S, P, in, H, n, out, n_out, rec, rec_stride, nullptr);
+	aov_shade_sample<TEX, ALPHA, AOV_GUIDES>(S, P, in, H, n, out, n_out, rec, rec_stride, nullptr);
 }
 
 template <bool TEX, bool ALPHA>
 __global__ void __launch_bounds__(kAovBlock) k_aov_motion_shade(DevScene S, RenderParams P, AovStream in, AovHits H, uint32_t n, AovStream out, uint32_t* __restrict__ n_out,
                                                                 float4* __restrict__ rec, AovMotion Mo) {
-	aov_shade_sample<TEX, ALPHA, true>(S, P, in, H, n, out, n_out, rec, 0, &Mo);
+	aov_shade_sample<TEX, ALPHA, AOV_MOTION>(S, P, in, H, n, out, n_out, rec, 0, &Mo);
+}
+
+template <bool TEX, bool ALPHA>
+__global__ void __launch_bounds__(kAovBlock) k_aov_emission_shade(DevScene S, RenderParams P, AovStream in, AovHits H, uint32_t n, AovStream out, uint32_t* __restrict__ n_out,
+                                                                  float4* __restrict__ rec) {
+	aov_shade_sample<TEX, ALPHA, AOV_EMISSION>(S, P, in, H, n, out, n_out, rec, 0, nullptr);
 }
 
 // Adds the pass's records of each pixel, in sample order, into the caller's buffers, as k_resolve does for radiance. A sample that ended on
@@ -205,6 +220,19 @@ hipError_t launch_aov_motion_shade(const DevScene& S, const RenderParams& P, con
 	} else {
 		if (S.any_alpha) hipLaunchKernelGGL((k_aov_motion_shade<false, true>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, Mo);
 		else hipLaunchKernelGGL((k_aov_motion_shade<false, false>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, Mo);
+	}
+	return hipGetLastError();
+}
+
+hipError_t launch_aov_emission_shade(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* n_out, float4* rec,
+                                     hipStream_t stream) {
+	const dim3 grid((n + kAovBlock - 1) / kAovBlock), block(kAovBlock);
+	if (S.any_texture) {
+		if (S.any_alpha) hipLaunchKernelGGL((k_aov_emission_shade<true, true>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec);
+		else hipLaunchKernelGGL((k_aov_emission_shade<true, false>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec);
+	} else {
+		if (S.any_alpha) hipLaunchKernelGGL((k_aov_emission_shade<false, true>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec);
+		else hipLaunchKernelGGL((k_aov_emission_shade<false, false>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec);
 	}
 	return hipGetLastError();
 }

@@ -412,6 +412,58 @@ int ptx_accum_mean(ptx_ctx* c, const float* accum_a, const float* accum_b, size_
 	return PTX_OK;
 }
 
+namespace {
+
+// What ptx_emission_split and ptx_emission_merge refuse, in one order, before any device work; the context is looked at last. `x`, `y`: the
+// buffers worked on in place (y may be NULL). -> whether they are device memory.
+int emission_args(const char* who_c, const ptx_ctx* c, const float* emission, uint32_t guide_spp, size_t n_pixels, const float* x, const float* y, bool& dev) {
+	const std::string who = who_c;
+	if (!emission || !x) return set_err(PTX_ERR_INVALID, who + ": NULL argument");
+	if (guide_spp == 0) return set_err(PTX_ERR_INVALID, who + ": guide_spp must be > 0");
+	if (n_pixels == 0 || n_pixels > (size_t)0x7FFFFFFF) return set_err(PTX_ERR_INVALID, who + ": n_pixels must lie in 1 .. 2^31 - 1");
+	if (emission == x || emission == y || x == y) return set_err(PTX_ERR_INVALID, who + ": a buffer shares its memory with another");
+	if (!c) return set_err(PTX_ERR_INVALID, who + ": NULL context");
+	dev = is_device_ptr(emission);
+	if (is_device_ptr(x) != dev || (y && is_device_ptr(y) != dev)) return set_err(PTX_ERR_INVALID, who + ": the buffers must all be device or all be host memory");
+	return PTX_OK;
+}
+
+}  // namespace
+
+int ptx_emission_split(ptx_ctx* c, const float* emission, uint32_t guide_spp, size_t n_pixels, float* accum_a, float* accum_b) {
+	bool dev = false;
+	if (const int rc = emission_args("ptx_emission_split", c, emission, guide_spp, n_pixels, accum_a, accum_b, dev); rc != PTX_OK) return rc;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t bytes = n_pixels * sizeof(float4);
+	Staged s_e, s_a, s_b;
+	if (!dev) HIP_TRY(c->adaptive_stage.ensure(3 * bytes));
+	HIP_TRY(s_e.bind(c, dev, emission, bytes, c->adaptive_stage));
+	HIP_TRY(s_a.bind(c, dev, accum_a, bytes, c->adaptive_stage, bytes));
+	if (accum_b) HIP_TRY(s_b.bind(c, dev, accum_b, bytes, c->adaptive_stage, 2 * bytes));
+	HIP_TRY(launch_emission_split(s_e.as<float4>(), guide_spp, n_pixels, s_a.as<float4>(), s_b.as<float4>(), c->stream));
+	HIP_TRY(s_a.copy_back(c));
+	HIP_TRY(s_b.copy_back(c));
+	if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
+	return PTX_OK;
+}
+
+int ptx_emission_merge(ptx_ctx* c, const float* emission, uint32_t guide_spp, size_t n_pixels, float* out_rgba) {
+	bool dev = false;
+	if (const int rc = emission_args("ptx_emission_merge", c, emission, guide_spp, n_pixels, out_rgba, nullptr, dev); rc != PTX_OK) return rc;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t bytes = n_pixels * sizeof(float4);
+	Staged s_e, s_out;
+	if (!dev) HIP_TRY(c->adaptive_stage.ensure(2 * bytes));
+	HIP_TRY(s_e.bind(c, dev, emission, bytes, c->adaptive_stage));
+	HIP_TRY(s_out.bind(c, dev, out_rgba, bytes, c->adaptive_stage, bytes));
+	HIP_TRY(launch_emission_merge(s_e.as<float4>(), guide_spp, n_pixels, s_out.as<float4>(), c->stream));
+	HIP_TRY(s_out.copy_back(c));
+	if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
+	return PTX_OK;
+}
+
 int ptx_pbr_eval_batch(ptx_ctx* c, const float* in, size_t n, float* out) {
 	if (!c) return set_err(PTX_ERR_NO_DEVICE, "ptx_pbr_eval_batch: no GPU context (no CPU path exists)");
 	if (n == 0) return PTX_OK;

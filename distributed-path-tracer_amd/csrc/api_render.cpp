@@ -568,11 +568,13 @@ int ptx_intersect_batch(ptx_scene* sc, const ptx_rays* r, size_t n, const ptx_hi
 
 namespace {
 
-// ptx_render_aov and ptx_render_motion: the same refusals about the cfg and the scene, the same passes and rounds. motion == false: the two
-// guide buffers (either may be NULL); else `albedo_cov` is the motion buffer, k_aov_motion_shade writes one record per sample, and `prev`
-// (checked by the caller; may be NULL) is the previous frame.
-int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float* albedo_cov, float* normal_depth, bool motion, const ptx_motion_prev* prev,
+// ptx_render_aov, ptx_render_motion and ptx_render_emission: the same refusals about the cfg and the scene, the same passes and rounds.
+// AovKind::guides: the two guide buffers (either may be NULL); else `albedo_cov` is the motion or the emission buffer and the shade kernel
+// writes one record per sample. `prev` (motion alone; checked by the caller; may be NULL) is the previous frame.
+enum class AovKind { guides, motion, emission };
+int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float* albedo_cov, float* normal_depth, AovKind kind, const ptx_motion_prev* prev,
               ptx_render_stats* stats) {
+	const bool motion = kind == AovKind::motion;
 	const std::string who = who_c;
 	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
 		return set_err(PTX_ERR_UNSUPPORTED, who + ": PTX_INTEGRATOR_WORKER has no first-hit buffers here (the worker's opacity handling and its un-jittered "
@@ -594,7 +596,7 @@ int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float
 	if (const int rc = f.plan(c, sc, who_c, nullptr, 32ull << 20, 0xFFFFFFFFull); rc != PTX_OK || !f.n_pass) return rc;
 
 	// workspace of one pass of `cap` samples: [256 B: live counts][stream 0][stream 1][hits][records: two per sample, one for
-	// ptx_render_motion], then the previous transforms and the moved words of ptx_render_motion
+	// ptx_render_motion and ptx_render_emission], then the previous transforms and the moved words of ptx_render_motion
 	const size_t cap = ((size_t)f.pass_spp * f.n_pixels + 3) & ~(size_t)3;   // array stride: keeps the float4 records 16-byte aligned
 	// the previous frame, read under the mutex the setters take: the camera (the scene's own when it did not move) and which models moved
 	const FlatScene& h = sc->host;
@@ -634,7 +636,7 @@ int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float
 			s.id = k.take<uint32_t>(cap); s.pass = k.take<uint32_t>(cap);
 		}
 		hits = k.take<float>(6 * cap);
-		rec = k.take<float4>((motion ? 1 : 2) * cap);
+		rec = k.take<float4>((kind == AovKind::guides ? 2 : 1) * cap);
 		d_xform = k.take<float>(12 * n_models);
 		d_moved = k.take<uint32_t>(n_models);
 		return k.off;
@@ -676,6 +678,7 @@ int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float
 			uint32_t* const n_out = live_count + (round & 1u);
 			if (follow) HIP_TRY(hipMemsetAsync(n_out, 0, 4, c->stream));
 			if (motion) HIP_TRY(launch_aov_motion_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, Mo, c->stream));
+			else if (kind == AovKind::emission) HIP_TRY(launch_aov_emission_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, c->stream));
 			else HIP_TRY(launch_aov_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, cap, c->stream));
 			if (!follow) break;
 			HIP_TRY(hipMemcpyAsync(&live, n_out, 4, hipMemcpyDeviceToHost, c->stream));
@@ -697,7 +700,7 @@ int ptx_render_aov(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_aov_buffe
 	// every refusal, here and in aov_frame, is decided before any device work
 	if (!sc || !cfg || !out) return set_err(PTX_ERR_INVALID, "ptx_render_aov: NULL argument");
 	if (!out->albedo_cov && !out->normal_depth) return set_err(PTX_ERR_INVALID, "ptx_render_aov: both buffers are NULL (at least one must be given)");
-	return aov_frame(sc, cfg, "ptx_render_aov", out->albedo_cov, out->normal_depth, false, nullptr, stats);
+	return aov_frame(sc, cfg, "ptx_render_aov", out->albedo_cov, out->normal_depth, AovKind::guides, nullptr, stats);
 }
 
 int ptx_render_motion(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_motion_prev* prev, float* motion, ptx_render_stats* stats) {
@@ -716,7 +719,13 @@ int ptx_render_motion(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_motion
 		for (int k = 0; k < 9; k++) if (!std::isfinite(pc.basis[k])) return bad("the previous camera's basis is not finite");
 		if (!std::isfinite(pc.yfov) || !(pc.yfov > 0) || !((double)pc.yfov < 3.14159265358979323846)) return bad("the previous camera's yfov must lie in (0, pi)");
 	}
-	return aov_frame(sc, cfg, "ptx_render_motion", motion, nullptr, true, prev, stats);
+	return aov_frame(sc, cfg, "ptx_render_motion", motion, nullptr, AovKind::motion, prev, stats);
+}
+
+int ptx_render_emission(ptx_scene* sc, const ptx_render_cfg* cfg, float* emission, ptx_render_stats* stats) {
+	// every refusal, here and in aov_frame, is decided before any device work
+	if (!sc || !cfg || !emission) return set_err(PTX_ERR_INVALID, "ptx_render_emission: NULL argument");
+	return aov_frame(sc, cfg, "ptx_render_emission", emission, nullptr, AovKind::emission, nullptr, stats);
 }
 
 namespace {

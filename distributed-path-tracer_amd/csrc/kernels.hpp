@@ -217,6 +217,10 @@ struct AovMotion {
 // camera, 1), zeros for a sample that contributes nothing. launch_aov_resolve(rec, ..., motion, nullptr, ...) adds them up.
 hipError_t launch_aov_motion_shade(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* n_out, float4* rec,
                                    const AovMotion& Mo, hipStream_t stream);
+// ptx_render_emission: the same walk again; rec: [rec_stride] ONE record per sample, (emissive10, 1) of a surface that faces the ray that
+// found it, zeros for a back-facing surface and for a miss. launch_aov_resolve(rec, ..., emission, nullptr, ...) adds them up.
+hipError_t launch_aov_emission_shade(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* n_out, float4* rec,
+                                     hipStream_t stream);
 // adds the pass's records of each pixel, in sample order, into the caller's buffers (either may be nullptr)
 hipError_t launch_aov_resolve(const float4* rec, size_t rec_stride, float4* albedo_cov, float4* normal_depth, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp,
                               hipStream_t stream);
@@ -355,5 +359,12 @@ hipError_t launch_adaptive_decide_shard(const uint8_t* merged, uint32_t w, uint3
                                         uint32_t* pixels, hipStream_t stream);
 // out = (a + b) / (a.w + b.w) for all four channels, or a / a.w when b == nullptr; out may be a or b
 hipError_t launch_accum_mean(const float4* a, const float4* b, size_t n_pixels, float4* out, hipStream_t stream);
+
+// First-hit emission around the filters (emission.hip; ptx_emission_split, ptx_emission_merge). e = emission.rgb / float(guide_spp); a
+// channel whose e is not > 0 is left without arithmetic; .w of every buffer is untouched.
+// a.c -= a.w * e.c, and the same for b unless it is nullptr; in place
+hipError_t launch_emission_split(const float4* emission, uint32_t guide_spp, size_t n_pixels, float4* a, float4* b, hipStream_t stream);
+// out.c += e.c; in place
+hipError_t launch_emission_merge(const float4* emission, uint32_t guide_spp, size_t n_pixels, float4* out, hipStream_t stream);
 
 }  // namespace ptx

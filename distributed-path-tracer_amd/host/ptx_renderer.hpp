@@ -41,6 +41,9 @@ public:
 	float lens_radius = 0, focus_distance = 0;
 	uint32_t blades = 0;
 	float blade_rotation = 0;
+	// render_denoised, render_adaptive(denoise) and render_adaptive_nee(denoise): the first-hit emission of the guides' samples
+	// (ptx_render_emission) is taken out of the halves before the filter and added to its output (ptx_emission_split, ptx_emission_merge)
+	bool split_emission = false;
 
 	explicit renderer(int device = 0) { check(ptx_ctx_create(device, &ctx_)); }
 	renderer(const renderer&) = delete;
@@ -124,6 +127,29 @@ public:
 		return a;
 	}
 
+	// First-hit emission SUMS of the frame's sample_count camera samples (ptx_render_emission), [H][W][4]: emissive * 10 of every sample's
+	// surface that faces the camera + the count of those samples. stats optional
+	std::vector<float> render_emission(ptx_render_stats* stats = nullptr) const {
+		if (!scene_) throw std::runtime_error("render_emission() before load_gltf()");
+		apply_lens();
+		ptx_render_cfg c{};
+		c.W = resolution.x; c.H = resolution.y; c.spp = sample_count;
+		c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
+		std::vector<float> emission((size_t)c.W * c.H * 4, 0.f);
+		check(ptx_render_emission(scene_, &c, emission.data(), stats));
+		return emission;
+	}
+	// ptx_emission_split / ptx_emission_merge on host buffers of [..][4] floats: emission SUMS over guide_spp samples of every pixel out of the
+	// radiance sums a and b (b may be nullptr) before a filter call, and back into the MEANS it returned
+	void emission_split(const std::vector<float>& emission, uint32_t guide_spp, std::vector<float>& a, std::vector<float>* b = nullptr) const {
+		if (a.size() != emission.size() || (b && b->size() != emission.size())) throw std::runtime_error("emission_split: the buffers differ in size");
+		check(ptx_emission_split(ctx_, emission.data(), guide_spp, emission.size() / 4, a.data(), b ? b->data() : nullptr));
+	}
+	void emission_merge(const std::vector<float>& emission, uint32_t guide_spp, std::vector<float>& out) const {
+		if (out.size() != emission.size()) throw std::runtime_error("emission_merge: the buffers differ in size");
+		check(ptx_emission_merge(ctx_, emission.data(), guide_spp, emission.size() / 4, out.data()));
+	}
+
 	// The frame through the variance-guided a-trous filter (ptx_denoise): samples [0, n/2) and [n/2, n) of sample_count = n rendered into two
 	// buffers, the guide buffers of all n; returns the filtered MEANS [H][W][4] (write them with ptx_tonemap_encode(..., spp = 1)). stats optional
 	std::vector<float> render_denoised(ptx_denoise_stats* stats = nullptr, const ptx_denoise_cfg* filter = nullptr) const {
@@ -150,7 +176,14 @@ public:
 		check(ptx_render_aov(scene_, &c, &g, nullptr));
 		ptx_denoise_cfg d = filter ? *filter : ptx_denoise_cfg{};   // iterations and sigmas; the rest is set here
 		d.W = c.W; d.H = c.H; d.spp_a = sample_count / 2; d.spp_b = sample_count - d.spp_a;
+		std::vector<float> em;
+		if (split_emission) {
+			em.assign(floats, 0.f);
+			check(ptx_render_emission(scene_, &c, em.data(), nullptr));
+			emission_split(em, sample_count, a, &b);
+		}
 		check(ptx_denoise(ctx_, &d, a.data(), b.data(), &g, a.data(), stats));
+		if (split_emission) emission_merge(em, sample_count, a);
 		return a;
 	}
 
@@ -353,11 +386,13 @@ public:
 				c.spp = ad_min_;
 				check(ptx_render_aov(r_.scene_, &c, &g, nullptr));
 				check(ptx_render_motion(r_.scene_, &c, have_ ? &mp : nullptr, motion.data(), nullptr));
+				const std::vector<float> em = split(c, ad_min_, a, b);
 				ptx_temporal_counts_cfg t{};
 				t.W = W; t.H = H; t.guide_spp = ad_min_; t.iterations = filter.iterations;
 				t.sigma_l = filter.sigma_l; t.sigma_n = filter.sigma_n; t.sigma_z = filter.sigma_z;
 				t.max_history = filter.max_history; t.tau_z = filter.tau_z; t.tau_n = filter.tau_n; t.flags = ad_temporal_flags_;
 				check(ptx_denoise_temporal_counts(r_.ctx_, &t, a.data(), b.data(), &g, motion.data(), have_ ? &prev : nullptr, &next, out.data(), stats));
+				if (split_) r_.emission_merge(em, ad_min_, out);
 				return finish(out);
 			}
 			c.spp = n / 2;
@@ -367,9 +402,11 @@ public:
 			c.sample0 = 0; c.spp = n;
 			check(ptx_render_aov(r_.scene_, &c, &g, nullptr));
 			check(ptx_render_motion(r_.scene_, &c, have_ ? &mp : nullptr, motion.data(), nullptr));
+			const std::vector<float> em = split(c, n, a, b);
 			ptx_temporal_cfg t = filter;
 			t.W = W; t.H = H; t.spp_a = n / 2; t.spp_b = n - n / 2;
 			check(ptx_denoise_temporal(r_.ctx_, &t, a.data(), b.data(), &g, motion.data(), have_ ? &prev : nullptr, &next, out.data(), stats));
+			if (split_) r_.emission_merge(em, n, out);
 			return finish(out);
 		}
 		// Adaptive frames (ptx_denoise_temporal_counts): frame() renders the halves with ptx_render_adaptive, or with ptx_render_adaptive_nee when
@@ -383,6 +420,12 @@ public:
 			ad_nee_flags_ = nee_flags ? *nee_flags : 0u;
 			ad_temporal_flags_ = temporal_flags;
 			have_ = false;
+		}
+		// The first-hit emission of the guides' samples goes round the temporal call: split before it, merged after it. The history then holds
+		// the residual, which does not mix with a history built without the split: a change starts the history over.
+		void set_split_emission(bool on) {
+			if (on != split_) have_ = false;
+			split_ = on;
 		}
 		// this frame's history: integrated demodulated colour + history length, luminance moments, mean normal + depth
 		const std::vector<float>& history_color() const { return hist_[cur_].color; }
@@ -398,7 +441,16 @@ public:
 			prev_xf_ = r_.model_xforms();
 			return std::move(out);
 		}
-		bool adaptive_ = false, ad_nee_ = false;
+		// with the split on: the emission sums of the guides' samples (c as the guides were rendered with), taken out of the halves
+		std::vector<float> split(const ptx_render_cfg& c, uint32_t guide_spp, std::vector<float>& a, std::vector<float>& b) const {
+			std::vector<float> em;
+			if (!split_) return em;
+			em.assign(a.size(), 0.f);
+			check(ptx_render_emission(r_.scene_, &c, em.data(), nullptr));
+			r_.emission_split(em, guide_spp, a, &b);
+			return em;
+		}
+		bool adaptive_ = false, ad_nee_ = false, split_ = false;
 		uint32_t ad_min_ = 0, ad_step_ = 0, ad_nee_flags_ = 0, ad_temporal_flags_ = 0;
 		float ad_threshold_ = 0;
 		renderer& r_;
@@ -467,7 +519,14 @@ private:
 		check(ptx_render_aov(scene_, &c, &g, nullptr));
 		ptx_denoise_counts_cfg d{};
 		d.W = c.W; d.H = c.H; d.guide_spp = adaptive_min;
+		std::vector<float> em;
+		if (split_emission) {
+			em.assign(a.size(), 0.f);
+			check(ptx_render_emission(scene_, &c, em.data(), nullptr));
+			emission_split(em, adaptive_min, a, &b);
+		}
 		check(ptx_denoise_counts(ctx_, &d, a.data(), b.data(), &g, a.data(), dstats));
+		if (split_emission) emission_merge(em, adaptive_min, a);
 		return std::move(a);
 	}
 	static void check(int rc) {

@@ -1,8 +1,11 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--split-emission] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
 //       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
+//       --split-emission: with --denoise, alone or with --adaptive (with or without --nee*): the first-hit emission of the guides' samples is
+//                      taken out of the half-frames before the filter and added, unfiltered, to its output (renderer::split_emission);
+//                      an error without --denoise and with --nee --denoise, whose half-frames renderer::render_nee_denoised filters as they are
 //       --nee:         light sampling towards the scene's emissive triangles (renderer::render_nee)
 //       --nee-fused:   --nee with one kernel launch per pass (PTX_NEE_FUSED): the same frame; ignored on scenes of the queue pipeline
 //       --nee-env MAP: --nee under the environment map MAP (renderer::environment; PNG, JPEG or Radiance .hdr), the light sample going
@@ -50,6 +53,7 @@ static void write_png(const std::string& path, const std::vector<uint8_t>& rgba,
 }
 
 int main(int argc, char** argv) {
+	bool split_emission = false;
 	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false, nee_sampler_pdf = false, nee_punctual = false;
 	float ad_thr = 0.1f;
 	unsigned ad_min = 8, ad_step = 0, nee_candidates = 1;
@@ -59,6 +63,7 @@ int main(int argc, char** argv) {
 	for (;;) {   // leading switches
 		if (argc > 1 && std::string(argv[1]) == "--transparent") { transparent = true; argv[1] = argv[0]; argv++; argc--; }
 		else if (argc > 1 && std::string(argv[1]) == "--denoise") { denoise = true; argv[1] = argv[0]; argv++; argc--; }
+		else if (argc > 1 && std::string(argv[1]) == "--split-emission") { split_emission = true; argv[1] = argv[0]; argv++; argc--; }
 		else if (argc > 1 && std::string(argv[1]) == "--nee") { nee = true; argv[1] = argv[0]; argv++; argc--; }   // renderer::render_nee: light sampling
 		else if (argc > 1 && std::string(argv[1]) == "--nee-fused") { nee = nee_fused = true; argv[1] = argv[0]; argv++; argc--; }   // ... one launch per pass
 		else if (argc > 1 && std::string(argv[1]) == "--nee-sampler-pdf") { nee = nee_sampler_pdf = true; argv[1] = argv[0]; argv++; argc--; }   // ... weights on the sampler's density
@@ -85,11 +90,15 @@ int main(int argc, char** argv) {
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--split-emission] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (nee_punctual && !nee) {
 		std::fprintf(stderr, "error: --nee-punctual needs --nee (or --nee-fused, --nee-env, --nee-sampler-pdf, --nee-candidates): only the light-sampling estimator renders point and spot lights\n");
+		return 1;
+	}
+	if (split_emission && (!denoise || (nee && !adaptive))) {
+		std::fprintf(stderr, "error: --split-emission needs --denoise, alone or with --adaptive: it takes the first-hit emission round the filter\n");
 		return 1;
 	}
 	if (argc == 5 && std::string(argv[1]) == "--event") {
@@ -129,6 +138,7 @@ int main(int argc, char** argv) {
 		r.load_gltf(argv[1]);
 		if (!nee_env.empty()) r.environment = nee_env;
 		r.nee_candidates = nee_candidates;
+		r.split_emission = split_emission;
 		r.lens_radius = lens_r; r.focus_distance = lens_f; r.blades = lens_blades; r.blade_rotation = lens_rot;
 		size_t n_punctual = 0;
 		if (nee_punctual) {

@@ -374,6 +374,29 @@ typedef struct ptx_motion_prev {
 int ptx_render_motion(ptx_scene* scene, const ptx_render_cfg* cfg, const ptx_motion_prev* prev /* NULL = nothing moved */,
                       float* motion /* [h][w][4], device or host */, ptx_render_stats* stats /* NULL ok */);
 
+/* First-hit emission (ptx_emission_split / ptx_emission_merge below; no counterpart in the reference): what every camera sample's surface
+ * emits towards the camera, which is what every estimator here adds at a path's first vertex.
+ * The camera samples, the walk through opacity pass-throughs (pass + 1, the 4096 bound), the rule "the first vertex that does not pass
+ * through is the sample's surface" and the intersect route are ptx_render_aov's, word for word: the same cfg fields, the same Philox keys.
+ * A sample that ends on a surface forms normal = the shading normal ptx_render_aov records and outcoming = -d, with d the direction of the
+ * ray that found the surface (the camera ray's, or the normalised direction behind a pass-through). If
+ * dot(normal, outcoming) = (n.x*o.x + n.y*o.y) + n.z*o.z > 0 the sample records (emissive10.r, emissive10.g, emissive10.b, 1), with emissive10
+ * = material::get_emissive(uv) * 10 as ptx_material_eval_batch reports it (floats 9 .. 11). A back-facing surface records nothing (the
+ * integrator's path ends there before its emission term, renderer.cpp:478); a miss records nothing. A shadow catcher is an ordinary surface
+ * here, as in ptx_render_aov: whether ptx_render passes it through depends on its sun sample, so an emissive catcher only leaves a residual
+ * for the filter.
+ * The buffer holds SUMS, ADDED to what the caller passes in; a pixel's samples are added in sample order, so tiles, ascending adjacent
+ * sample ranges, spp_per_pass, shard_* and host or device buffers compose exactly as in ptx_render_aov. .w counts the recording samples:
+ * .w <= albedo_cov.w, with equality where no sample's surface is back-facing.
+ * Consequence: on a scene without a sun (ptx_scene_info.has_sun == 0), emission.rgb is bit for bit accum.rgb of ptx_render with the same
+ * cfg, bounces = 1, env = (0, 0, 0) and PTX_INTEGRATOR_LIB: at depth 0 the throughput is 1, and 1 * x and 0 + x are exact; a miss adds +0
+ * there and nothing here; both add in sample order. (ptx_render_nee weights emission only at depth != 0: its first vertex adds the same.)
+ * cfg->bounces and cfg->env are ignored. stats and refusals as in ptx_render_aov, all decided before any device work: PTX_ERR_UNSUPPORTED
+ * for PTX_INTEGRATOR_WORKER, PTX_ERR_NO_DEVICE for a host-only scene, PTX_ERR_INVALID for a NULL scene, cfg or buffer and for whatever
+ * ptx_render refuses in cfg. */
+int ptx_render_emission(ptx_scene* scene, const ptx_render_cfg* cfg, float* emission /* [h][w][4], device or host */,
+                        ptx_render_stats* stats /* NULL ok */);
+
 /* Variance-guided edge-avoiding a-trous filter on the guide buffers (no counterpart in the reference, which has no denoiser): turns a noisy
  * low-spp frame into a usable one. It takes its noise estimate from two half-frames, which ptx_render gives for free — sample ranges compose.
  *   accum_a, accum_b [H][W][4]: ptx_render radiance SUMS of two disjoint sample ranges of the same frame (e.g. [0, n/2) and [n/2, n)), of
@@ -548,6 +571,36 @@ int ptx_denoise_temporal_counts(ptx_ctx* ctx, const ptx_temporal_counts_cfg* cfg
                                 const ptx_aov_buffers* guides, const float* motion, const ptx_temporal_history* prev /* NULL = first frame */,
                                 const ptx_temporal_history* next, float* out_rgba /* NULL = advance the history only */,
                                 ptx_temporal_stats* stats /* NULL ok */);
+
+/* Keeping first-hit emission out of the four filter calls above. They work on radiance / albedo; on an emissive texel the radiance is not
+ * proportional to the albedo texture, so the a-trous taps and the history taps would mix quotients that mean nothing once re-modulated with
+ * another pixel's albedo. col = (col - e) + e is exact for any estimate e, so the emission is taken out of the half-buffers before a filter
+ * call and added, unfiltered, to its output.
+ *   emission [n_pixels][4]: the ptx_render_emission SUMS over guide_spp samples of EVERY pixel: all samples of a uniform frame, the min_spp
+ *   prefix of an adaptive one (as the guides of ptx_denoise_counts).
+ *   accum_a, accum_b [n_pixels][4]: radiance SUMS whose .w is the per-pixel sample count, as ptx_render and the adaptive calls leave them.
+ *   out_rgba [n_pixels][4]: the MEANS a filter call wrote.
+ * Per pixel, per channel c of r, g, b (IEEE binary32, each operation rounded on its own, in the order written, no contraction):
+ *   ng = float(guide_spp);  e.c = emission.c / ng
+ *   split:  if (e.c > 0) { a.c = a.c - (a.w * e.c);  b.c = b.c - (b.w * e.c); }      (b only when accum_b is given)
+ *   merge:  if (e.c > 0)   out.c = out.c + e.c
+ * .w of every buffer is untouched. A channel whose e.c is not > 0 (zero, negative or NaN) is left without arithmetic. Both calls work in
+ * place. All pointers are device memory or all are host memory; host buffers are staged as ptx_accum_mean stages its own.
+ * The pipeline: render the halves; render the guides, the emission buffer and, for the temporal calls, the motion buffer;
+ * ptx_emission_split on the halves; any ONE of ptx_denoise, ptx_denoise_counts, ptx_denoise_temporal, ptx_denoise_temporal_counts,
+ * unchanged: every text of theirs now reads "colour" as "colour minus e" (a negative residual is legal input: they are specified on
+ * arbitrary floats); ptx_emission_merge on the filter's out_rgba. A temporal history then holds the residual: it is NOT interchangeable
+ * with a history built without the split, and a sequence splits either every frame or none.
+ * Consequences:
+ *   (a) With an emission buffer whose rgb is all zero neither call changes a bit of any buffer, signed zeros and NaNs included.
+ *   (b) On a frame with a.c = a.w * e.c + d.c and b.c = b.w * e.c - d.c, all factors dyadic so that every product and difference is
+ *       exact, split, any filter call and merge return e bit for bit on every pixel where e.c > 0, whatever d, the iterations and the
+ *       sigmas: the residual's sum is +0, a filter of zeros is zero, and 0 + e = e.
+ * Refusals, all PTX_ERR_INVALID and all decided before any device work, the context looked at last: a NULL emission, accum_a or out_rgba;
+ * guide_spp == 0; n_pixels of 0 or above 2^31 - 1; emission equal to one of the other pointers, or accum_a == accum_b; a NULL ctx; pointers of
+ * mixed kinds. */
+int ptx_emission_split(ptx_ctx* ctx, const float* emission, uint32_t guide_spp, size_t n_pixels, float* accum_a, float* accum_b /* NULL ok */);
+int ptx_emission_merge(ptx_ctx* ctx, const float* emission, uint32_t guide_spp, size_t n_pixels, float* out_rgba);
 
 /* Noise-driven per-pixel sample counts (no counterpart in the reference, which gives every pixel sample_count samples): a frame is rendered in
  * rounds, and a pixel whose two half-frames already agree, with all its neighbours, gets no further samples. On open, sun-lit scenes most

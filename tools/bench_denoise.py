@@ -6,6 +6,11 @@
                                              cost of the iteration at step 2^(k-1) (t(1) also holds the prepare and prefilter kernels).
   tools/bench_denoise.py quality             mean squared error after x / (1 + x) against the product's 512-spp frame (seed 77), noisy /
                                              denoised, on Cornell, plaza level 2 and jack-of-blades at 96 x 54 and 240 x 135, 2+2 and 8+8 spp.
+  tools/bench_denoise.py emission [W H reps] k_em_split (two halves) and k_em_merge (ptx_emission_split, ptx_emission_merge) on device buffers
+                                             next to one a-trous iteration, alternated in one process. The two calls take no stats, so a batch
+                                             of 100 back-to-back calls is timed on the host and divided (the smallest of `reps` batches); the
+                                             bytes are 16 per pixel and buffer, read and written: 80 for the split, 48 for the merge. The
+                                             a-trous row is kernel_ms(iterations = 2) - kernel_ms(iterations = 1) of ptx_denoise.
 Prints one JSON line per measurement.
 """
 import importlib
@@ -59,6 +64,36 @@ def time_forms(W, H, reps):
                               step_ms=[round(t[k] - t[k - 1], 4) for k in range(1, 5)], hbm_floor_ms_per_iteration=round(floor_ms, 4))))
 
 
+def time_emission(W, H, reps, batch=100):
+    import time
+    import torch
+    ctx = ptx.Context(0)
+    s = ptx.Scene.load_gltf(ctx, CORNELL)
+    a, b, A, N = frames(s, W, H, 8, device=True)
+    E, _ = s.render_emission(W, H, 16, emission=torch.zeros_like(a), seed=SEED)
+    out = torch.empty_like(a)
+    torch.cuda.synchronize()
+    n = W * H
+    best = dict(split=1e9, merge=1e9, atrous=1e9)
+
+    def batch_ms(call):
+        ctx.synchronize()
+        t = time.perf_counter()
+        for _ in range(batch):
+            call()
+        ctx.synchronize()
+        return (time.perf_counter() - t) * 1e3 / batch
+    for rep in range(reps + 1):   # the first round warms up; the halves drift by batch * a.w * e, which no timing depends on
+        t_split = batch_ms(lambda: ctx.emission_split(E, 16, a, b))
+        t_merge = batch_ms(lambda: ctx.emission_merge(E, 16, out))
+        k = [ctx.denoise(a, b, A, N, 8, 8, iterations=i, out=out)[1]["kernel_ms"] for i in (1, 2)]
+        if rep:
+            best["split"], best["merge"], best["atrous"] = min(best["split"], t_split), min(best["merge"], t_merge), min(best["atrous"], k[1] - k[0])
+    for name, nbytes in (("k_em_split", 80 * n), ("k_em_merge", 48 * n), ("atrous_iteration", None)):
+        ms = best[name.replace("k_em_", "").replace("_iteration", "")]
+        print(json.dumps(dict(kernel=name, W=W, H=H, reps=reps, ms=round(ms, 4), gbytes_per_s=round(nbytes / ms / 1e6, 1) if nbytes else None)))
+
+
 def quality():
     ctx = ptx.Context(0)
     scenes = {"cornell": lambda: ptx.Scene.load_gltf(ctx, CORNELL),
@@ -84,6 +119,9 @@ def quality():
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "quality":
         quality()
+    elif len(sys.argv) > 1 and sys.argv[1] == "emission":
+        argv = sys.argv[2:]
+        time_emission(int(argv[0]) if argv else 1920, int(argv[1]) if len(argv) > 1 else 1080, int(argv[2]) if len(argv) > 2 else 10)
     else:
         argv = sys.argv[2:]
         time_forms(int(argv[0]) if argv else 1920, int(argv[1]) if len(argv) > 1 else 1080, int(argv[2]) if len(argv) > 2 else 20)

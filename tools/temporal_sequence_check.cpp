@@ -1,8 +1,10 @@
 // Drives core::renderer::temporal_sequence and core::renderer::render_motion (host/ptx_renderer.hpp), the C++ mirror of
 // ptx_denoise_temporal and ptx_render_motion, for tests/test_temporal_gpu.py, which compares what it writes with the Python mirror's frames.
-//   temporal_sequence_check SCENE.gltf W H SPP BOUNCES POSES.bin OUT.bin [MIN:STEP:THRESHOLD:NEE_FLAGS:TEMPORAL_FLAGS]
+//   temporal_sequence_check SCENE.gltf W H SPP BOUNCES POSES.bin OUT.bin [MIN:STEP:THRESHOLD:NEE_FLAGS:TEMPORAL_FLAGS | -] [split]
 // The optional argument makes the sequence adaptive (temporal_sequence::set_adaptive; tests/test_temporal_counts_gpu.py): SPP is then the cap,
 // NEE_FLAGS = - renders with ptx_render_adaptive, a number with ptx_render_adaptive_nee and those flags.
+// A second optional argument, the word split, keeps first-hit emission out of the temporal call (temporal_sequence::set_split_emission;
+// tests/test_emission_gpu.py); a uniform sequence with the split takes - as the first.
 // POSES.bin: one camera per frame, 13 float32 each (origin, basis columns, yfov). OUT.bin receives, as float32: per frame the filtered
 // means [H][W][4]; then the last frame's integrated colour [H][W][4]; then render_motion of the last frame against the first camera.
 #include <cstdio>
@@ -13,7 +15,10 @@
 #include "../distributed-path-tracer_amd/host/ptx_renderer.hpp"
 
 int main(int argc, char** argv) {
-	if (argc != 8 && argc != 9) { fprintf(stderr, "usage: %s SCENE.gltf W H SPP BOUNCES POSES.bin OUT.bin [MIN:STEP:THRESHOLD:NEE_FLAGS:TEMPORAL_FLAGS]\n", argv[0]); return 2; }
+	if (argc < 8 || argc > 10 || (argc == 10 && strcmp(argv[9], "split"))) {
+		fprintf(stderr, "usage: %s SCENE.gltf W H SPP BOUNCES POSES.bin OUT.bin [MIN:STEP:THRESHOLD:NEE_FLAGS:TEMPORAL_FLAGS | -] [split]\n", argv[0]);
+		return 2;
+	}
 	try {
 		std::vector<float> poses;
 		if (FILE* f = fopen(argv[6], "rb")) {
@@ -37,7 +42,8 @@ int main(int argc, char** argv) {
 		FILE* out = fopen(argv[7], "wb");
 		if (!out) { fprintf(stderr, "cannot write %s\n", argv[7]); return 2; }
 		core::renderer::temporal_sequence seq(r);
-		if (argc == 9) {
+		if (argc == 10) seq.set_split_emission(true);
+		if (argc >= 9 && strcmp(argv[8], "-")) {
 			unsigned min_spp = 0, step_spp = 0, temporal_flags = 0;
 			float threshold = 0;
 			char nee[32] = "";

@@ -4,7 +4,7 @@ about the vertical axis through its origin (Scene.set_model_xforms). The scene i
 the time of creating the scene, which is what a second view cost before the setters existed.
 
   tools/turntable.py [--scene cornell|jack|atrium|PATH.gltf] [--frames N] [--size WxH] [--spp S] [--bounces B] [--spin MODEL] [--lens R:F[:BLADES[:ROT]]]
-                     [--nee] [--out PREFIX] [--arc DEG] [--temporal [--ref-spp N] [--adaptive MIN:CAP:THRESHOLD [--search] [--unit-normals]]]
+                     [--nee] [--out PREFIX] [--arc DEG] [--temporal [--ref-spp N] [--adaptive MIN:CAP:THRESHOLD [--search] [--unit-normals]] [--split-emission]]
 --out PREFIX writes PREFIX_000.png ...; without it the frames are rendered and dropped. The last line is one JSON record.
 --arc DEG: the angle the camera covers over the frames (default: the full circle).
 --temporal: every frame goes through ptx_denoise_temporal — its two half-frames, its guides, its motion against the previous frame's camera
@@ -15,7 +15,11 @@ frame against a frame of --ref-spp samples (default 512) of the same view. --out
 samples at least and CAP at most, the guides and the motion from the first MIN samples, and the frames go through
 ptx_denoise_temporal_counts, whose history counts samples; --search and --unit-normals set PTX_TEMPORAL_SEARCH_3X3 and
 PTX_TEMPORAL_UNIT_NORMALS. Per frame: the mean count, the reprojected share, and the error of the unfiltered frame, the ptx_denoise_counts
-frame and the temporal-counts frame against the --ref-spp frame. --spp is not used."""
+frame and the temporal-counts frame against the --ref-spp frame. --spp is not used.
+--temporal --split-emission (uniform or --adaptive): next to the columns above, the same single-frame filter and a second temporal chain with
+a history of its own run on halves from which the first-hit emission of the guides' samples was taken (Scene.render_emission,
+Context.emission_split), and get it back afterwards (Context.emission_merge): one run gives the rows with and without the split. --out
+then writes the split temporal frames."""
 import argparse
 import importlib
 import json
@@ -74,6 +78,7 @@ def main():
     ap.add_argument("--adaptive", default=None, metavar="MIN:CAP:THRESHOLD", help="with --temporal: adaptive frames through ptx_denoise_temporal_counts")
     ap.add_argument("--search", action="store_true", help="with --adaptive: PTX_TEMPORAL_SEARCH_3X3")
     ap.add_argument("--unit-normals", action="store_true", help="with --adaptive: PTX_TEMPORAL_UNIT_NORMALS")
+    ap.add_argument("--split-emission", action="store_true", help="with --temporal: also the filters with first-hit emission kept out of them")
     a = ap.parse_args()
     W, H = (int(v) for v in a.size.split("x"))
     lens = [float(v) for v in a.lens.split(":")] if a.lens else []
@@ -112,7 +117,15 @@ def main():
     elif a.search or a.unit_normals:
         ap.error("--search and --unit-normals go with --adaptive")
     tflags = (ptx.TEMPORAL_SEARCH_3X3 if a.search else 0) | (ptx.TEMPORAL_UNIT_NORMALS if a.unit_normals else 0)
-    mean_counts = []
+    if a.split_emission and not a.temporal:
+        ap.error("--split-emission goes with --temporal")
+    mean_counts, hist_s, mse_s = [], None, []
+
+    def split_halves(ha, hb, ng, seed):
+        """-> (emission sums of the guides' ng samples, copies of the halves without them)"""
+        E, _ = s.render_emission(W, H, ng, seed=seed, want_stats=False)
+        sa, sb = ctx.emission_split(E, ng, ha.copy(), hb.copy())
+        return E, sa, sb
     if a.temporal and a.spp < 2:
         ap.error("--temporal needs --spp of at least 2 (two half-frames)")
     render = (lambda **kw: s.render_nee(W, H, bounces=a.bounces, flags=ptx.NEE_FUSED, want_stats=False, **kw)[0]) if a.nee else \
@@ -151,8 +164,15 @@ def main():
             mean_counts.append(float(n.mean()))
             acc_ms.append(st["accumulate_ms"]), filt_ms.append(st["kernel_ms"]), share.append(st["reprojected"] / (W * H))
             mse.append((err((ha + hb) / n, ref), err(single, ref), err(out, ref)))
+            if a.split_emission:
+                E, sa, sb = split_halves(ha, hb, lo, seed)
+                out_s, hist_s, _ = ctx.denoise_temporal_counts(sa, sb, A, N, M, lo, prev=hist_s, flags=tflags)
+                single_s, _ = ctx.denoise_counts(sa, sb, A, N, lo)
+                out, single_s = ctx.emission_merge(E, lo, out_s), ctx.emission_merge(E, lo, single_s)
+                mse_s.append((err(single_s, ref), err(out, ref)))
             print(line + f", frame {render_ms[-1]:8.2f} ms; mean count {mean_counts[-1]:6.2f}, accumulate {acc_ms[-1]:.4f} ms, filter {filt_ms[-1]:.4f} ms, "
-                  f"reprojected {share[-1] * 100:5.1f} %; mse unfiltered {mse[-1][0]:.3e}, ptx_denoise_counts {mse[-1][1]:.3e}, temporal-counts {mse[-1][2]:.3e}")
+                  f"reprojected {share[-1] * 100:5.1f} %; mse unfiltered {mse[-1][0]:.3e}, ptx_denoise_counts {mse[-1][1]:.3e}, temporal-counts {mse[-1][2]:.3e}"
+                  + (f"; with the split: ptx_denoise_counts {mse_s[-1][0]:.3e}, temporal-counts {mse_s[-1][1]:.3e}" if a.split_emission else ""))
             acc, acc_spp = out, 1
         elif a.temporal:
             half, seed = a.spp // 2, 0x5EED + f   # every frame its own key: the frames' noise is independent
@@ -166,8 +186,15 @@ def main():
             ref = render(spp=a.ref_spp, seed=77) / np.float32(a.ref_spp)
             acc_ms.append(st["accumulate_ms"]), filt_ms.append(st["kernel_ms"]), share.append(st["reprojected"] / (W * H))
             mse.append((err((ha + hb) / np.float32(a.spp), ref), err(single, ref), err(out, ref)))
+            if a.split_emission:
+                E, sa, sb = split_halves(ha, hb, a.spp, seed)
+                out_s, hist_s, _ = ctx.denoise_temporal(sa, sb, A, N, M, half, a.spp - half, prev=hist_s)
+                single_s, _ = ctx.denoise(sa, sb, A, N, half, a.spp - half)
+                out, single_s = ctx.emission_merge(E, a.spp, out_s), ctx.emission_merge(E, a.spp, single_s)
+                mse_s.append((err(single_s, ref), err(out, ref)))
             print(line + f", frame {render_ms[-1]:8.2f} ms; accumulate {acc_ms[-1]:.4f} ms, filter {filt_ms[-1]:.4f} ms, reprojected {share[-1] * 100:5.1f} %; "
-                  f"mse unfiltered {mse[-1][0]:.3e}, ptx_denoise {mse[-1][1]:.3e}, temporal {mse[-1][2]:.3e}")
+                  f"mse unfiltered {mse[-1][0]:.3e}, ptx_denoise {mse[-1][1]:.3e}, temporal {mse[-1][2]:.3e}"
+                  + (f"; with the split: ptx_denoise {mse_s[-1][0]:.3e}, temporal {mse_s[-1][1]:.3e}" if a.split_emission else ""))
             acc, acc_spp = out, 1
         else:
             acc, _ = (s.render_nee(W, H, a.spp, a.bounces, flags=ptx.NEE_FUSED) if a.nee else s.render(W, H, a.spp, a.bounces))
@@ -186,6 +213,9 @@ def main():
         out.update(temporal=dict(accumulate_ms=round(med(acc_ms[1:] or acc_ms), 4), filter_ms=round(med(filt_ms), 4), reprojected_share=round(med(share[1:] or share), 4),
                                  ref_spp=a.ref_spp, mse_unfiltered=float(np.median(m[:, 0])), mse_denoise=float(np.median(m[:, 1])), mse_temporal=float(np.median(m[:, 2])),
                                  last_frame_denoise_over_temporal=round(mse[-1][1] / mse[-1][2], 3)))
+        if a.split_emission:
+            ms = np.array(mse_s[1:] or mse_s)
+            out["temporal"].update(mse_denoise_split=float(np.median(ms[:, 0])), mse_temporal_split=float(np.median(ms[:, 1])), mse_last_split=[float(v) for v in mse_s[-1]])
         if adaptive:
             out["temporal"].update(adaptive=a.adaptive, flags=tflags, mean_count=round(float(np.mean(mean_counts)), 3), mse_last=[float(v) for v in mse[-1]])
     print(json.dumps(out))
