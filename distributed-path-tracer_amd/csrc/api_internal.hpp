@@ -98,6 +98,7 @@ struct ptx_scene {
 	double lds_area_share = 0;     // share of the surfaces' box area (sum over surfaces) that belongs to LDS-resident surfaces: how much of what a ray can enter is served from LDS
 	double wf_pairs_per_ray = 0;   // queue-based pipeline: pairs (ray, entered surface) per ray seen so far on this scene, 0 = not yet measured
 	bool leaf_ordered = true; // global-memory copy of the triangle records: per leaf reference (true) or per triangle (false)
+	int kd_shapes = 1;        // shape bits of the leaf-ordered resident trees in SurfaceRec::lds_root (PTX_KD_SHAPES; read with lds_leaf_order)
 	int lds_leaf_order = -1;  // LDS-resident copy: leaf-ordered records for the surfaces where they are cheap (1) or all ref-indexed (0); -1 = not decided yet
 	size_t lds_budget = 0;    // what plan_residency may fill (decide_mode)
 	int mode = MODE_GLOBAL;   // where the traversal arrays live: MODE_GLOBAL / MODE_LDS / MODE_HYBRID (kernels.hip)

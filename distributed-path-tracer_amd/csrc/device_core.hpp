@@ -14,7 +14,8 @@ namespace ptx {
 #define DEV __device__ __forceinline__
 
 // PTX_PROF builds (tools/build_variant.sh prof -DPTX_PROF): count wave-level trips and active lanes per code region, to
-// weigh the static instruction counts of the ISA; regions 16-19 are the kinds of shade_vertex's vertices (miss, back face, last, full).
+// weigh the static instruction counts of the ISA; regions 16-19 are the kinds of shade_vertex's vertices (miss, back face, last, full),
+// 20-25 the short walks of small resident trees (leaf-only calls, complete-tree pops and node steps; inline walks, then set-aside lists).
 // Not compiled into the product.
 #ifdef PTX_PROF
 struct Prof { uint32_t t[kProfRegions], l[kProfRegions]; };
@@ -395,16 +396,111 @@ DEV bool mesh_traverse(const Geom& g, uint32_t root, float nr, float fr, V3 o, V
 	}
 }
 
+// ------------------------------------------------------------------------------------ short walks of small resident trees
+// plan_residency marks the shape of a resident, leaf-ordered tree in SurfaceRec::lds_root (flat_scene.hpp): a single leaf, or a complete
+// tree — every branch has both children — of at most kRegStack branch levels. The two walks below are mesh_traverse on such a tree with
+// what the shape makes constant folded in. PROF regions of their own (PTX_PROF builds): call, pop, node step per caller.
+static_assert(kShapeMaxBranchLevels == kRegStack, "a complete tree's pending entries must fit the register stack");
+template <int PB> constexpr int shape_prof_base() { return PB == 4 ? 20 : 23; }   // inline walks / set-aside lists
+// One leaf of leaf-ordered records: mesh_traverse's leaf part as it stands (leaf_trip<true>, the rcp_key test, the leaf_trip<false> re-test),
+// with leaf_trip's layout branch decided: only leaf-ordered surfaces carry a shape bit.
+template <int PB>
+DEV bool shape_leaf(const Geom& g, uint2 nd, const PRay& pr, float max_dist, MeshHit& out PROF_ARG) {
+	const uint32_t first_ref = nd.x, count = nd.y >> 2;
+	float best_t = -1.0f, bb1 = 0, bb2 = 0;
+	uint32_t best_tri = 0;
+	uint32_t key = 0;
+#ifdef PTX_PROF
+	for (uint32_t i = 0; i < count; i++) PROF(PB + 3);
+#endif
+	leaf_records<true, true>(g, first_ref, count, pr, max_dist, best_t, bb1, bb2, best_tri, key);
+	if (key >= kRcpKeyEnd) {
+		best_t = -1.0f; bb1 = 0; bb2 = 0; best_tri = 0;
+		leaf_records<false, true>(g, first_ref, count, pr, max_dist, best_t, bb1, bb2, best_tri, key);
+	}
+	if (!(best_t >= 0)) return false;
+	out.t = best_t; out.b1 = bb1; out.b2 = bb2; out.tri = best_tri;
+	return true;
+}
+// kLdsLeafOnlyBit: the root is a leaf. mesh_traverse loads the root, finds a leaf, tests its records with max_dist = fr, and on a miss pops
+// an empty stack: one leaf trip, no node loop and no stack.
+template <int PB>
+DEV bool mesh_traverse_leaf(const Geom& g, uint32_t root, float fr, V3 o, V3 d, MeshHit& out PROF_ARG) {
+	PROF(shape_prof_base<PB>());
+	const PRay pr = pack_ray(o, d);
+	return shape_leaf<PB>(g, g.nodes[root], pr, fr, out PROF_PASS);
+}
+// kLdsCompleteBit: in mesh_traverse on such a tree has_l = has_r = true at every branch, so ri = li + 1, has_first = has_second = has_next =
+// true, `valid` stays true and no placeholder (kNoNode) is ever pushed; a branch level leaves at most one entry pending and a path has at
+// most kRegStack of them, so sp never reaches kRegStack and neither spill branch is taken. With those constants folded in, what is left
+// is written out below. Exactness rests on nothing else: every remaining expression, operand order and comparison — the node and record
+// loads, split_dist and its IEEE division, `oa < split`, the three-way decision, the register push, the pop with max_dist rebuilt as
+// sp > 0 ? m0 : fr, and the leaf part — is mesh_traverse's own, in its order. (The resident copy has no child-pair fetch: Geom::pair.)
+template <int PB>
+DEV bool mesh_traverse_complete(const Geom& g, uint32_t root, float nr, float fr, V3 o, V3 d, MeshHit& out PROF_ARG) {
+	PROF(PB);
+	const PRay pr = pack_ray(o, d);
+	int sp = 0;
+	uint32_t n0 = 0, n1 = 0, n2 = 0;  // register stack: entry 0 is the top
+	float m0 = 0, m1 = 0, m2 = 0;
+	uint32_t node = root;
+	float min_dist = nr, max_dist = fr;
+	for (;;) {
+		uint2 nd = g.nodes[node];
+		while ((nd.y & 3u) != KD_LEAF) {
+			PROF(shape_prof_base<PB>() + 2);
+			const uint32_t axis = nd.y & 3u;
+			const float split = __uint_as_float(nd.x);
+			const float oa = sel3(o, axis), da = sel3(d, axis);
+			const float split_dist = (split - oa) / da;
+			const uint32_t li = nd.y >> 4, ri = li + 1u;
+			const bool left_first = oa < split;
+			const uint32_t first = left_first ? li : ri, second = left_first ? ri : li;
+			uint32_t next;
+			if (split_dist < 0 || split_dist > max_dist) next = first;
+			else if (split_dist < min_dist) next = second;
+			else {
+				n2 = n1; m2 = m1; n1 = n0; m1 = m0; n0 = second; m0 = split_dist;
+				sp++;
+				next = first;
+				max_dist = split_dist;
+			}
+			node = next;
+			nd = g.nodes[node];
+		}
+		if (shape_leaf<PB>(g, nd, pr, max_dist, out PROF_PASS)) return true;
+		PROF(shape_prof_base<PB>() + 1);
+		if (sp == 0) return false;
+		sp--;
+		node = n0; min_dist = m0;
+		n0 = n1; m0 = m1; n1 = n2; m1 = m2;
+		max_dist = sp > 0 ? m0 : fr;
+	}
+}
+
 // The LDS copy as one resident surface lays it out: SurfaceRec::lds_root carries the layout of the surface's records in bit 31
 // (plan_residency). The surface record is scalar-loaded, so the flag is wave-uniform.
 DEV Geom lds_geom(const Geom& lds, uint32_t lds_root) { return {lds.nodes, lds.refs, lds.tris, (lds_root & kLdsLeafOrderBit) != 0, lds.pair}; }
+// core::mesh::intersect on a resident surface: a scalar branch on the shape bits of lds_root (wave-uniform, like the layout bit) in front of
+// the short walks and the general one. -DPTX_NO_SHAPE_COMPLETE / -DPTX_NO_SHAPE_LEAF: measurement builds without one of them.
+template <int PB>
+DEV bool mesh_traverse_lds(const Geom& lds, uint32_t lds_root, float nr, float fr, V3 o, V3 d, MeshHit& out, const Spill& spill PROF_ARG) {
+	const uint32_t root = lds_root & kLdsRootMask;
+#ifndef PTX_NO_SHAPE_COMPLETE
+	if (lds_root & kLdsCompleteBit) return mesh_traverse_complete<PB>(lds, root, nr, fr, o, d, out PROF_PASS);
+#endif
+#ifndef PTX_NO_SHAPE_LEAF
+	if (lds_root & kLdsLeafOnlyBit) return mesh_traverse_leaf<PB>(lds, root, fr, o, d, out PROF_PASS);
+#endif
+	return mesh_traverse<PB>(lds_geom(lds, lds_root), root, nr, fr, o, d, out, spill PROF_PASS);
+}
 // core::mesh::intersect on whichever copy of the surface's tree the scene's MODE prescribes; (nr, fr) from the box test
 template <int MODE, int PB>
 DEV bool mesh_traverse_m(const Geoms& G, const SurfaceRec& sf, float nr, float fr, V3 o, V3 d, MeshHit& out, const Spill& spill PROF_ARG) {
 	if constexpr (MODE == MODE_GLOBAL) return mesh_traverse<PB>(G.glb, sf.kd_root, nr, fr, o, d, out, spill PROF_PASS);
-	else if constexpr (MODE == MODE_LDS) return mesh_traverse<PB>(lds_geom(G.lds, sf.lds_root), sf.lds_root & ~kLdsLeafOrderBit, nr, fr, o, d, out, spill PROF_PASS);
+	else if constexpr (MODE == MODE_LDS) return mesh_traverse_lds<PB>(G.lds, sf.lds_root, nr, fr, o, d, out, spill PROF_PASS);
 	else {
-		if (sf.lds_root != 0xFFFFFFFFu) return mesh_traverse<PB>(lds_geom(G.lds, sf.lds_root), sf.lds_root & ~kLdsLeafOrderBit, nr, fr, o, d, out, spill PROF_PASS);
+		if (sf.lds_root != 0xFFFFFFFFu) return mesh_traverse_lds<PB>(G.lds, sf.lds_root, nr, fr, o, d, out, spill PROF_PASS);
 		return mesh_traverse<PB>(G.glb, sf.kd_root, nr, fr, o, d, out, spill PROF_PASS);
 	}
 }

@@ -70,14 +70,22 @@ struct SurfaceRec {
 	float bmin[3], bmax[3];  // mesh AABB (mesh.cpp:254-261)
 	uint32_t kd_root;        // index of the root KD node in the full node array
 	uint32_t tri_base;       // global id of the mesh's triangle 0
-	uint32_t lds_root;       // 0xFFFFFFFF when the surface is not resident (tested first); else bits 30:0 = index of the root in the LDS-resident
-	                         // node array, bit 31 (kLdsLeafOrderBit) = its resident records are leaf-ordered (plan_residency)
+	uint32_t lds_root;       // 0xFFFFFFFF when the surface is not resident (tested first); else bits 28:0 (kLdsRootMask) = index of the root in the
+	                         // LDS-resident node array, bit 31 (kLdsLeafOrderBit) = its resident records are leaf-ordered, bits 30 / 29
+	                         // (kLdsLeafOnlyBit / kLdsCompleteBit) = the shape of its tree, set on leaf-ordered surfaces only (plan_residency)
 	uint32_t model;          // the model this surface belongs to
 	float pbmin[3], pbmax[3];  // mesh AABB grown by the reach of the barycentric slack (see ModelRec)
 	float box[6], pbox[6];     // both boxes as (min, max) pairs per axis (see ModelRec)
 };
 static_assert(sizeof(SurfaceRec) == 28 * 4, "SurfaceRec layout");
 constexpr uint32_t kLdsLeafOrderBit = 0x80000000u;
+// The shape of a resident, leaf-ordered tree, read off its node words (kd_tree_shape). The surface record is scalar-loaded, so a kernel
+// branches on these bits wave-uniformly, to a walk with the shape's constants folded in (device_core.hpp: mesh_traverse_m).
+constexpr uint32_t kLdsLeafOnlyBit = 0x40000000u;   // the root is a leaf
+constexpr uint32_t kLdsCompleteBit = 0x20000000u;   // every branch node has both children and no root-to-leaf path holds more than
+                                                    // kShapeMaxBranchLevels branch nodes (never set together with kLdsLeafOnlyBit)
+constexpr uint32_t kLdsRootMask = 0x1FFFFFFFu;
+constexpr int kShapeMaxBranchLevels = 3;            // = kRegStack (device_core.hpp): one pending entry per branch level fits the register stack
 template <class Rec> inline void interleave_boxes(Rec& r) {
 	for (int k = 0; k < 3; k++) { r.box[2 * k] = r.bmin[k]; r.box[2 * k + 1] = r.bmax[k]; r.pbox[2 * k] = r.pbmin[k]; r.pbox[2 * k + 1] = r.pbmax[k]; }
 }
@@ -208,7 +216,10 @@ struct FlatScene {
 // record per reference, and they add nothing to res_refs. Ref-indexed surfaces keep one record per triangle behind res_refs. The two
 // kinds share the three arrays, so the compact arrays differ from the full ones even when every surface is resident.
 constexpr size_t kLdsLeafOrderCap = 4096;   // bytes the leaf-ordered layouts may cost together: 28 hot hit records (144 B) at the most
-void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order = true);
+// With `kd_shapes`, the leaf-ordered surfaces also get the shape bits of their trees (kLdsLeafOnlyBit / kLdsCompleteBit).
+void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order = true, bool kd_shapes = true);
+// kLdsLeafOnlyBit, kLdsCompleteBit or 0 for the tree at `root` of `nodes` (children at w1 >> 4, adjacent; w1 & 4 / & 8: left / right present)
+uint32_t kd_tree_shape(const std::vector<KdNode>& nodes, uint32_t root);
 
 // Builds everything derived (AABBs, KD-trees, records) from the "as loaded" arrays + camera/sun floats.
 // camera13: origin(3) basis(9) fov ; sun13: basis(9) energy(3) angular_radius or nullptr.

@@ -97,7 +97,7 @@ struct RenderParams {
 	                            // of the pixels this pass renders (interleaved tile sharding), and n_pixels is the list's length
 };
 
-constexpr int kProfRegions = 20;   // PTX_PROF builds only: (wave-level trips, active lanes) per code region
+constexpr int kProfRegions = 26;   // PTX_PROF builds only: (wave-level trips, active lanes) per code region
 
 struct PassBuffers {
 	float4* queues;                   // [n_wave_slots][queue_stride]

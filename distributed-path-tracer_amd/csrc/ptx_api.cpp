@@ -40,14 +40,17 @@ constexpr size_t kLeafOrderMaxBytes = (size_t)1 << 40;   // never reached: see d
 void decide_mode(ptx_scene* sc) {
 	FlatScene& h = sc->host;
 	// PTX_LDS_LEAF_ORDER=0/1: the resident copy all ref-indexed / leaf-ordered where it is cheap (the default); PTX_LDS_BUDGET: a smaller
-	// budget for the residency plan, in bytes (measurement and tests; read once, here)
+	// budget for the residency plan, in bytes (measurement and tests; read once, here); PTX_KD_SHAPES=0/1: no shape bits in lds_root, so
+	// that every walk is the general one / the shape bits of the leaf-ordered trees (the default)
 	if (sc->lds_leaf_order < 0) {
 		const char* e = getenv("PTX_LDS_LEAF_ORDER");
 		sc->lds_leaf_order = (e && e[0] == '0') ? 0 : 1;
+		const char* k = getenv("PTX_KD_SHAPES");
+		sc->kd_shapes = (k && k[0] == '0') ? 0 : 1;
 		sc->lds_budget = kLdsBudget;
 		if (const char* b = getenv("PTX_LDS_BUDGET")) sc->lds_budget = std::min<size_t>(kLdsBudget, (size_t)strtoull(b, nullptr, 10));
 	}
-	plan_residency(h, sc->lds_budget, sc->lds_leaf_order != 0);
+	plan_residency(h, sc->lds_budget, sc->lds_leaf_order != 0, sc->kd_shapes != 0);
 	if (getenv("PTX_FORCE_GLOBAL") || h.n_resident == 0) sc->mode = MODE_GLOBAL;
 	else if (h.n_resident == h.surfaces.size()) sc->mode = MODE_LDS;
 	else sc->mode = getenv("PTX_NO_HYBRID") ? MODE_GLOBAL : MODE_HYBRID;
@@ -796,8 +799,12 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 	case PTX_ARR_RES_NODES: src = h.res_nodes.data(); bytes = h.res_nodes.size() * 8; break;
 	case PTX_ARR_RES_REFS: src = h.res_refs.data(); bytes = h.res_refs.size() * 4; break;
 	case PTX_ARR_RES_TRIS: src = h.res_tris.data(); bytes = h.res_tris.size() * sizeof(TriIsect); break;
-	case PTX_ARR_LDS_ROOT:
-		for (auto& s : h.surfaces) { float f; memcpy(&f, &s.lds_root, 4); tmp.push_back(f); }
+	case PTX_ARR_LDS_ROOT:     // the root and the layout bit, as before the shape bits existed; PTX_ARR_LDS_SHAPE: the whole word
+	case PTX_ARR_LDS_SHAPE:
+		for (auto& s : h.surfaces) {
+			const uint32_t w = (which == PTX_ARR_LDS_SHAPE || s.lds_root == 0xFFFFFFFFu) ? s.lds_root : (s.lds_root & (kLdsRootMask | kLdsLeafOrderBit));
+			float f; memcpy(&f, &w, 4); tmp.push_back(f);
+		}
 		src = tmp.data(); bytes = tmp.size() * 4; break;
 	case PTX_ARR_RES_PLAN: {
 		const uint32_t w[4] = {(uint32_t)h.res_bytes, h.n_resident, (uint32_t)sc->lds_bytes, (uint32_t)h.hot_hitrec.size()};

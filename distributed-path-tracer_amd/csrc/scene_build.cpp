@@ -436,7 +436,24 @@ std::vector<float> lens_table(const CameraRec& cam) {
 	return t;
 }
 
-void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order) {
+uint32_t kd_tree_shape(const std::vector<KdNode>& nodes, uint32_t root) {
+	if (root >= nodes.size()) return 0u;
+	if ((nodes[root].w1 & 3u) == KD_LEAF) return kLdsLeafOnlyBit;
+	std::vector<std::pair<uint32_t, int>> todo{{root, 0}};   // (node, branch nodes above it)
+	while (!todo.empty()) {
+		const auto [n, above] = todo.back();
+		todo.pop_back();
+		if (n >= nodes.size()) return 0u;
+		const uint32_t w1 = nodes[n].w1;
+		if ((w1 & 3u) == KD_LEAF) continue;
+		if ((w1 & 12u) != 12u || above + 1 > kShapeMaxBranchLevels) return 0u;   // a missing child, or one branch level too many
+		todo.push_back({w1 >> 4, above + 1});
+		todo.push_back({(w1 >> 4) + 1u, above + 1});
+	}
+	return kLdsCompleteBit;
+}
+
+void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order, bool kd_shapes) {
 	const size_t n_surf = s.surfaces.size();
 	s.res_nodes.clear(); s.res_refs.clear(); s.res_tris.clear();
 	s.n_resident = 0;
@@ -500,8 +517,9 @@ void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order) {
 			for (uint32_t k = 0; k < nt; k++) s.res_tris.push_back(s.tri_isect[t0 + k]);
 		}
 		const uint32_t root = (s.surfaces[si].kd_root - node0) + nb;
-		assert(root < kLdsLeafOrderBit);   // a resident tree fits LDS: a few thousand nodes
-		s.surfaces[si].lds_root = root | (leaf_order[si] ? kLdsLeafOrderBit : 0u);
+		assert(root <= kLdsRootMask);   // a resident tree fits LDS: a few thousand nodes
+		const uint32_t shape = (kd_shapes && leaf_order[si]) ? kd_tree_shape(s.res_nodes, root) : 0u;
+		s.surfaces[si].lds_root = root | (leaf_order[si] ? kLdsLeafOrderBit : 0u) | shape;
 		s.n_resident++;
 	}
 	s.res_bytes = s.res_tris.size() * 48 + shade_bytes + ((s.res_nodes.size() * 8 + 15) & ~(size_t)15) + ((s.res_refs.size() * 4 + 15) & ~(size_t)15);

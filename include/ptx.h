@@ -236,7 +236,9 @@ typedef enum ptx_array {
 	/* the punctual lights of ptx_scene_set_punctual_lights (host-only scenes too; both empty when none are set) */
 	PTX_ARR_PUNCTUAL = 28,    /* float[n][16], as stored */
 	PTX_ARR_PUNCTUAL_CDF = 29,/* float[n]: cumulative share of lum(intensity), the last entry 1 */
-	PTX_ARR_LENS = 30         /* float[blades + 1][2]: the aperture table of ptx_scene_set_camera; empty while lens_radius == 0 */
+	PTX_ARR_LENS = 30,        /* float[blades + 1][2]: the aperture table of ptx_scene_set_camera; empty while lens_radius == 0 */
+	PTX_ARR_LDS_SHAPE = 31    /* uint32[n_surfaces]: the surface records' whole lds_root word: LDS_ROOT's (root in bits 28:0) | leaf-only tree << 30 |
+	                           * complete tree of at most 3 branch levels << 29 (the shape bits: leaf-ordered surfaces only, none with PTX_KD_SHAPES=0) */
 } ptx_array;
 int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, size_t dst_bytes);
 

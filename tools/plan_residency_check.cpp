@@ -34,7 +34,7 @@ static PlanFacts check_plan(FlatScene& s, size_t budget, bool leaf_order, const 
 		CHECK(leaf_order || !lo, "%s: surface %zu leaf-ordered with the layout switched off", what, si);
 		const int32_t* rg = &s.surf_range[8 * si];
 		const uint32_t t0 = (uint32_t)rg[2], nt = (uint32_t)rg[3], node0 = (uint32_t)rg[4], nn = (uint32_t)rg[5], ref0 = (uint32_t)rg[6], nr = (uint32_t)rg[7];
-		const uint32_t nb = (lr & ~kLdsLeafOrderBit) - (s.surfaces[si].kd_root - node0);
+		const uint32_t nb = (lr & kLdsRootMask) - (s.surfaces[si].kd_root - node0);
 		CHECK((size_t)nb + nn <= s.res_nodes.size(), "%s: surface %zu: nodes [%u, +%u) of %zu", what, si, nb, nn, s.res_nodes.size());
 		if ((size_t)nb + nn > s.res_nodes.size()) continue;
 		n_nodes += nn; n_tris += lo ? nr : nt; n_refs += lo ? 0 : nr;
