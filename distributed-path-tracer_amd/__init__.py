@@ -29,12 +29,13 @@ NO_SUN_LIGHT = 0xFFFFFFFF  # core::renderer::no_sun_light, renderer.hpp:19
 (ARR_MODEL_XFORM, ARR_MODEL_AABB, ARR_MODEL_SURF, ARR_SURF_RANGE, ARR_MESH_AABB, ARR_VERTICES, ARR_TRIANGLES,
  ARR_MATERIALS, ARR_KD_NODES, ARR_KD_REFS, ARR_CAMERA, ARR_SUN, ARR_MODEL_NAMES, ARR_TEXTURES, ARR_TEXELS, ARR_SURF_TEX, ARR_TEXELS_F32,
  ARR_LIGHT_TRIS, ARR_LIGHT_CDF, ARR_LIGHT_GEOM, ARR_TRI_ISECT, ARR_RES_NODES, ARR_RES_REFS, ARR_RES_TRIS, ARR_LDS_ROOT,
- ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF, ARR_PUNCTUAL, ARR_PUNCTUAL_CDF, ARR_LENS, ARR_LDS_SHAPE) = range(32)
+ ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF, ARR_PUNCTUAL, ARR_PUNCTUAL_CDF, ARR_LENS, ARR_LDS_SHAPE, ARR_SURF_AUX) = range(33)
 LDS_LEAF_ORDER_BIT = 0x80000000  # ARR_LDS_ROOT: the surface's resident records are leaf-ordered (flat_scene.hpp)
 LDS_LEAF_ONLY_BIT = 0x40000000   # ARR_LDS_SHAPE: the surface's resident tree is a single leaf
 LDS_COMPLETE_BIT = 0x20000000    # ARR_LDS_SHAPE: ... is complete (no missing child) with at most KD_SHAPE_MAX_BRANCH_LEVELS branch levels
 LDS_ROOT_MASK = 0x1FFFFFFF
 KD_SHAPE_MAX_BRANCH_LEVELS = 3   # kShapeMaxBranchLevels = kRegStack
+AUX_CHAIN_BIT = 1    # ARR_SURF_AUX, word 0: the surface's resident, leaf-ordered tree is a chain: every branch has exactly one child (none with PTX_KD_SHAPES=0)
 
 
 class PtxError(RuntimeError):
@@ -582,7 +583,7 @@ _ARR_DTYPE = {ARR_MODEL_XFORM: (np.float32, 12), ARR_MODEL_AABB: (np.float32, 6)
               ARR_TRI_ISECT: (np.uint32, 12), ARR_RES_NODES: (np.uint32, 2), ARR_RES_REFS: (np.uint32, 1), ARR_RES_TRIS: (np.uint32, 12),
               ARR_LDS_ROOT: (np.uint32, 1), ARR_RES_PLAN: (np.uint32, 1), ARR_ENV_ROW_CDF: (np.float32, 1), ARR_ENV_CELL_CDF: (np.float32, 1),
               ARR_PUNCTUAL: (np.float32, 16), ARR_PUNCTUAL_CDF: (np.float32, 1), ARR_LENS: (np.float32, 2),
-              ARR_LDS_SHAPE: (np.uint32, 1)}
+              ARR_LDS_SHAPE: (np.uint32, 1), ARR_SURF_AUX: (np.uint32, 4)}
 
 
 class Scene:

@@ -338,7 +338,8 @@ int render_stats(ptx_ctx* c, const PassFrame& f, bool wavefront, const WfPlan& p
 	static const char* names[kProfRegions] = {"extend_iter", "model_iter", "space_xform", "inline_model", "mesh_call", "mesh_pop", "node_step",
 	                                           "tri_test", "defer_iter", "shade_iter", "defer_mesh_call", "defer_mesh_pop", "defer_node_step", "defer_tri_test",
 	                                           "list_append", "shade_hit", "vertex_miss", "vertex_back_face", "vertex_last", "vertex_full",
-	                                           "leaf_only_call", "complete_pop", "complete_node_step", "defer_leaf_only_call", "defer_complete_pop", "defer_complete_node_step"};
+	                                           "leaf_only_call", "complete_pop", "complete_node_step", "defer_leaf_only_call", "defer_complete_pop", "defer_complete_node_step",
+	                                           "chain_level", "defer_chain_level"};
 	for (int k = 0; k < kProfRegions; k++)
 		fprintf(stderr, "PROF %-16s trips %12llu lanes %14llu  util %.3f  trips/64rays %.3f\n", names[k], prof[2 * k], prof[2 * k + 1],
 		        prof[2 * k] ? (double)prof[2 * k + 1] / (64.0 * prof[2 * k]) : 0.0, (double)prof[2 * k] / ((double)rays / 64.0));

@@ -15,7 +15,8 @@ namespace ptx {
 
 // PTX_PROF builds (tools/build_variant.sh prof -DPTX_PROF): count wave-level trips and active lanes per code region, to
 // weigh the static instruction counts of the ISA; regions 16-19 are the kinds of shade_vertex's vertices (miss, back face, last, full),
-// 20-25 the short walks of small resident trees (leaf-only calls, complete-tree pops and node steps; inline walks, then set-aside lists).
+// 20-25 the short walks of small resident trees (leaf-only / chain calls, complete-tree pops and node steps; inline walks, then set-aside lists),
+// 26-27 the chain walk's levels (inline, lists).
 // Not compiled into the product.
 #ifdef PTX_PROF
 struct Prof { uint32_t t[kProfRegions], l[kProfRegions]; };
@@ -398,8 +399,9 @@ DEV bool mesh_traverse(const Geom& g, uint32_t root, float nr, float fr, V3 o, V
 
 // ------------------------------------------------------------------------------------ short walks of small resident trees
 // plan_residency marks the shape of a resident, leaf-ordered tree in SurfaceRec::lds_root (flat_scene.hpp): a single leaf, or a complete
-// tree — every branch has both children — of at most kRegStack branch levels. The two walks below are mesh_traverse on such a tree with
-// what the shape makes constant folded in. PROF regions of their own (PTX_PROF builds): call, pop, node step per caller.
+// tree — every branch has both children — of at most kRegStack branch levels; and, in the auxiliary surface table (UnitAux::flags), a chain:
+// every branch has exactly one child. The walks below are mesh_traverse on such a tree with what the shape makes constant folded in. PROF
+// regions of their own (PTX_PROF builds): call, pop, node step per caller, and the chain's levels.
 static_assert(kShapeMaxBranchLevels == kRegStack, "a complete tree's pending entries must fit the register stack");
 template <int PB> constexpr int shape_prof_base() { return PB == 4 ? 20 : 23; }   // inline walks / set-aside lists
 // One leaf of leaf-ordered records: mesh_traverse's leaf part as it stands (leaf_trip<true>, the rcp_key test, the leaf_trip<false> re-test),
@@ -424,11 +426,53 @@ DEV bool shape_leaf(const Geom& g, uint2 nd, const PRay& pr, float max_dist, Mes
 }
 // kLdsLeafOnlyBit: the root is a leaf. mesh_traverse loads the root, finds a leaf, tests its records with max_dist = fr, and on a miss pops
 // an empty stack: one leaf trip, no node loop and no stack.
+// (-DPTX_NO_SHAPE_CHAIN builds only: mesh_traverse_chain below walks such a tree as its chain of zero levels.)
 template <int PB>
 DEV bool mesh_traverse_leaf(const Geom& g, uint32_t root, float fr, V3 o, V3 d, MeshHit& out PROF_ARG) {
 	PROF(shape_prof_base<PB>());
 	const PRay pr = pack_ray(o, d);
 	return shape_leaf<PB>(g, g.nodes[root], pr, fr, out PROF_PASS);
+}
+// kAuxChainBit (UnitAux::flags; kd_chain_shape): every node from the root down is a branch with exactly ONE child, and the last one's child is
+// a leaf; zero branches = kLdsLeafOnlyBit's tree. What mesh_traverse does on such a tree, per branch, with `child` the one that exists:
+//   split_dist < 0 || split_dist > max_dist   next = first.  child is first: go on, bounds unchanged. child is second: has_next is false, the
+//                                             walk pops — see below — and finds nothing: return false.
+//   split_dist < min_dist                     next = second. child is second: go on, bounds unchanged. child is first: return false likewise.
+//   else                                      an entry is pushed and next = first with max_dist = split_dist. child is first: the entry is a
+//                                             placeholder (kNoNode); go on with max_dist = split_dist. child is second: the entry is the child
+//                                             itself, has_next is false, and the pop that follows at once takes it back: node = child,
+//                                             min_dist = split_dist, max_dist = the bound in force before this step.
+// That last max_dist holds because of mesh_traverse's invariant max_dist == (sp > 0 ? m0 : fr) at the head of every node step: every step that
+// cuts max_dist pushes an entry whose m is the new bound, and every pop restores it from the entry beneath. So on a chain every entry left
+// pending below the current node is a placeholder: the one real child that is ever pushed is popped in the same trip round the loop, its
+// sibling being absent. A dead end (has_next false with only placeholders pending) and a leaf that yields nothing both pop placeholders until
+// sp == 0 and return false. A chain is at most 25 branches deep (mesh.hpp: max_depth), below kRegStack + kSpillStack = 27, so mesh_traverse
+// never refuses the push. Hence no stack here: per level the split's own expressions in mesh_traverse's order — split_dist and its IEEE
+// division, `oa < split`, the three-way decision — then the leaf part with the max_dist that the walk arrives with.
+template <int PB>
+DEV bool mesh_traverse_chain(const Geom& g, uint32_t root, float nr, float fr, V3 o, V3 d, MeshHit& out PROF_ARG) {
+	PROF(shape_prof_base<PB>());
+	const PRay pr = pack_ray(o, d);
+	float min_dist = nr, max_dist = fr;
+	uint2 nd = g.nodes[root];
+	while ((nd.y & 3u) != KD_LEAF) {
+		PROF(PB == 4 ? 26 : 27);
+		const uint32_t axis = nd.y & 3u;
+		const float split = __uint_as_float(nd.x);
+		const float oa = sel3(o, axis), da = sel3(d, axis);
+		const float split_dist = (split - oa) / da;
+		const bool left_first = oa < split;
+		// the child is the left one iff has_l. The reference's builder only ever keeps the LEFT child of a chain's branch (its cut below a mesh
+		// is the box's own bound and is refused: tests/test_kd_chain.py), and no entry point takes hand-made nodes, so the has_l == 0 side of
+		// this comparison is run by no test on the device; it is mesh_traverse's `has_first = left_first ? has_l : has_r` with has_r == !has_l.
+		const bool child_first = left_first == ((nd.y & 4u) != 0);
+		if (split_dist < 0 || split_dist > max_dist) { if (!child_first) return false; }
+		else if (split_dist < min_dist) { if (child_first) return false; }
+		else if (child_first) max_dist = split_dist;
+		else min_dist = split_dist;
+		nd = g.nodes[nd.y >> 4];
+	}
+	return shape_leaf<PB>(g, nd, pr, max_dist, out PROF_PASS);
 }
 // kLdsCompleteBit: in mesh_traverse on such a tree has_l = has_r = true at every branch, so ri = li + 1, has_first = has_second = has_next =
 // true, `valid` stays true and no placeholder (kNoNode) is ever pushed; a branch level leaves at most one entry pending and a path has at
@@ -482,34 +526,42 @@ DEV bool mesh_traverse_complete(const Geom& g, uint32_t root, float nr, float fr
 // (plan_residency). The surface record is scalar-loaded, so the flag is wave-uniform.
 DEV Geom lds_geom(const Geom& lds, uint32_t lds_root) { return {lds.nodes, lds.refs, lds.tris, (lds_root & kLdsLeafOrderBit) != 0, lds.pair}; }
 // core::mesh::intersect on a resident surface: a scalar branch on the shape bits of lds_root (wave-uniform, like the layout bit) in front of
-// the short walks and the general one. -DPTX_NO_SHAPE_COMPLETE / -DPTX_NO_SHAPE_LEAF: measurement builds without one of them.
+// the short walks and the general one; `aux_flags`: UnitAux::flags of the surface (kAuxChainBit). -DPTX_NO_SHAPE_COMPLETE / -DPTX_NO_SHAPE_LEAF /
+// -DPTX_NO_SHAPE_CHAIN: measurement builds without one of them; without the chain walk a single leaf goes to mesh_traverse_leaf as before.
 template <int PB>
-DEV bool mesh_traverse_lds(const Geom& lds, uint32_t lds_root, float nr, float fr, V3 o, V3 d, MeshHit& out, const Spill& spill PROF_ARG) {
+DEV bool mesh_traverse_lds(const Geom& lds, uint32_t lds_root, uint32_t aux_flags, float nr, float fr, V3 o, V3 d, MeshHit& out, const Spill& spill PROF_ARG) {
 	const uint32_t root = lds_root & kLdsRootMask;
 #ifndef PTX_NO_SHAPE_COMPLETE
 	if (lds_root & kLdsCompleteBit) return mesh_traverse_complete<PB>(lds, root, nr, fr, o, d, out PROF_PASS);
 #endif
+#ifndef PTX_NO_SHAPE_CHAIN
 #ifndef PTX_NO_SHAPE_LEAF
+	if ((lds_root & kLdsLeafOnlyBit) | (aux_flags & kAuxChainBit)) return mesh_traverse_chain<PB>(lds, root, nr, fr, o, d, out PROF_PASS);
+#else   // without the leaf walk: a single leaf (the chain of zero levels, which carries kAuxChainBit too) goes to the general walk
+	if ((aux_flags & kAuxChainBit) && !(lds_root & kLdsLeafOnlyBit)) return mesh_traverse_chain<PB>(lds, root, nr, fr, o, d, out PROF_PASS);
+#endif
+#elif !defined(PTX_NO_SHAPE_LEAF)
 	if (lds_root & kLdsLeafOnlyBit) return mesh_traverse_leaf<PB>(lds, root, fr, o, d, out PROF_PASS);
 #endif
 	return mesh_traverse<PB>(lds_geom(lds, lds_root), root, nr, fr, o, d, out, spill PROF_PASS);
 }
 // core::mesh::intersect on whichever copy of the surface's tree the scene's MODE prescribes; (nr, fr) from the box test
 template <int MODE, int PB>
-DEV bool mesh_traverse_m(const Geoms& G, const SurfaceRec& sf, float nr, float fr, V3 o, V3 d, MeshHit& out, const Spill& spill PROF_ARG) {
+DEV bool mesh_traverse_m(const Geoms& G, const SurfaceRec& sf, const UnitAux& ax, float nr, float fr, V3 o, V3 d, MeshHit& out, const Spill& spill PROF_ARG) {
 	if constexpr (MODE == MODE_GLOBAL) return mesh_traverse<PB>(G.glb, sf.kd_root, nr, fr, o, d, out, spill PROF_PASS);
-	else if constexpr (MODE == MODE_LDS) return mesh_traverse_lds<PB>(G.lds, sf.lds_root, nr, fr, o, d, out, spill PROF_PASS);
+	else if constexpr (MODE == MODE_LDS) return mesh_traverse_lds<PB>(G.lds, sf.lds_root, ax.flags, nr, fr, o, d, out, spill PROF_PASS);
 	else {
-		if (sf.lds_root != 0xFFFFFFFFu) return mesh_traverse_lds<PB>(G.lds, sf.lds_root, nr, fr, o, d, out, spill PROF_PASS);
+		if (sf.lds_root != 0xFFFFFFFFu) return mesh_traverse_lds<PB>(G.lds, sf.lds_root, ax.flags, nr, fr, o, d, out, spill PROF_PASS);
 		return mesh_traverse<PB>(G.glb, sf.kd_root, nr, fr, o, d, out, spill PROF_PASS);
 	}
 }
+
 // ... including the box test (mesh.cpp:308-315)
 template <int MODE, int PB>
-DEV bool mesh_intersect_m(const Geoms& G, const SurfaceRec& sf, V3 o, V3 d, V3 inv, MeshHit& out, const Spill& spill PROF_ARG) {
+DEV bool mesh_intersect_m(const Geoms& G, const SurfaceRec& sf, const UnitAux& ax, V3 o, V3 d, V3 inv, MeshHit& out, const Spill& spill PROF_ARG) {
 	float nr, fr;
 	if (!aabb_test_inv(sf.bmin, sf.bmax, o, inv, nr, fr)) return false;
-	return mesh_traverse_m<MODE, PB>(G, sf, nr, fr, o, d, out, spill PROF_PASS);
+	return mesh_traverse_m<MODE, PB>(G, sf, ax, nr, fr, o, d, out, spill PROF_PASS);
 }
 
 // Closest hit record: what the shading phase needs to rebuild everything else.
@@ -545,7 +597,7 @@ DEV bool scene_traverse(const DevScene& S, const Geoms& g, V3 o, V3 d, SceneHit&
 		int hit_surface = -1;
 		for (int s = 0; s < M.n_surfaces; s++) {
 			MeshHit h;
-			if (!mesh_intersect_m<MODE, 4>(g, S.surfaces[M.first_surface + s], lo, ld, inv, h, spill PROF_PASS)) continue;
+			if (!mesh_intersect_m<MODE, 4>(g, S.surfaces[M.first_surface + s], S.surf_aux[M.first_surface + s], lo, ld, inv, h, spill PROF_PASS)) continue;
 			if (h.t < nearest.t || !(nearest.t >= 0)) { nearest = h; hit_surface = M.first_surface + s; }
 		}
 		if (!(nearest.t >= 0)) continue;
@@ -590,7 +642,7 @@ DEV bool scene_occluded(const DevScene& S, const Geoms& g, V3 o, V3 d, const Spi
 		if (!aabb_test_inv(M.bmin, M.bmax, lo, inv, nr, fr)) continue;
 		for (int s = 0; s < M.n_surfaces; s++) {
 			MeshHit h;
-			if (!mesh_intersect_m<MODE, 4>(g, S.surfaces[M.first_surface + s], lo, ld, inv, h, spill PROF_PASS)) continue;
+			if (!mesh_intersect_m<MODE, 4>(g, S.surfaces[M.first_surface + s], S.surf_aux[M.first_surface + s], lo, ld, inv, h, spill PROF_PASS)) continue;
 			if (length(mulmv(M.basis, ld * h.t)) >= 0) return true;   // model.cpp:62-63: a hit whose world distance is not NaN
 		}
 	}
@@ -620,7 +672,7 @@ DEV bool model_traverse(const DevScene& S, const Geoms& g, const ModelRec& M, V3
 	int hit_surface = -1;
 	for (int k = 0; k < M.n_surfaces; k++) {
 		MeshHit h;
-		if (!mesh_intersect_m<MODE, PB>(g, S.surfaces[M.first_surface + k], lo, ld, inv, h, spill PROF_PASS)) continue;
+		if (!mesh_intersect_m<MODE, PB>(g, S.surfaces[M.first_surface + k], S.surf_aux[M.first_surface + k], lo, ld, inv, h, spill PROF_PASS)) continue;
 		if (h.t < nearest.t || !(nearest.t >= 0)) { nearest = h; hit_surface = M.first_surface + k; }
 	}
 	if (!(nearest.t >= 0)) return false;

@@ -86,6 +86,16 @@ constexpr uint32_t kLdsCompleteBit = 0x20000000u;   // every branch node has bot
                                                     // kShapeMaxBranchLevels branch nodes (never set together with kLdsLeafOnlyBit)
 constexpr uint32_t kLdsRootMask = 0x1FFFFFFFu;
 constexpr int kShapeMaxBranchLevels = 3;            // = kRegStack (device_core.hpp): one pending entry per branch level fits the register stack
+
+// ---- auxiliary record per surface: flags that do not fit SurfaceRec, whose layout and lds_root word tests pin. A table of its own
+// (FlatScene::surf_aux), passed to the fused kernels as a separate argument and scalar-loaded like the others.
+struct UnitAux {
+	uint32_t flags;    // kAuxChainBit
+	uint32_t pad[3];
+};
+static_assert(sizeof(UnitAux) == 16, "UnitAux layout");
+constexpr uint32_t kAuxChainBit = 1u;   // the resident, leaf-ordered tree is a chain (kd_chain_shape >= 0), walked by mesh_traverse_chain
+
 template <class Rec> inline void interleave_boxes(Rec& r) {
 	for (int k = 0; k < 3; k++) { r.box[2 * k] = r.bmin[k]; r.box[2 * k + 1] = r.bmax[k]; r.pbox[2 * k] = r.pbmin[k]; r.pbox[2 * k + 1] = r.pbmax[k]; }
 }
@@ -187,6 +197,7 @@ struct FlatScene {
 	std::vector<ShadeRec> shade;         // per surface
 	std::vector<SpaceRec> spaces;        // distinct world->local transforms
 	std::vector<uint32_t> model_space;   // per model
+	std::vector<UnitAux> surf_aux;       // per surface: chain flag (plan_residency)
 	std::vector<KdNode> kd_nodes;
 	std::vector<uint32_t> kd_refs;       // global triangle ids
 	std::vector<TriRec> tris;            // corners + vertex ids (host side: counts, inspection)
@@ -216,10 +227,14 @@ struct FlatScene {
 // record per reference, and they add nothing to res_refs. Ref-indexed surfaces keep one record per triangle behind res_refs. The two
 // kinds share the three arrays, so the compact arrays differ from the full ones even when every surface is resident.
 constexpr size_t kLdsLeafOrderCap = 4096;   // bytes the leaf-ordered layouts may cost together: 28 hot hit records (144 B) at the most
-// With `kd_shapes`, the leaf-ordered surfaces also get the shape bits of their trees (kLdsLeafOnlyBit / kLdsCompleteBit).
+// With `kd_shapes`, the leaf-ordered surfaces also get the shape bits of their trees (kLdsLeafOnlyBit / kLdsCompleteBit), and kAuxChainBit
+// in surf_aux (sized and zeroed here) where the tree is a chain.
 void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order = true, bool kd_shapes = true);
 // kLdsLeafOnlyBit, kLdsCompleteBit or 0 for the tree at `root` of `nodes` (children at w1 >> 4, adjacent; w1 & 4 / & 8: left / right present)
 uint32_t kd_tree_shape(const std::vector<KdNode>& nodes, uint32_t root);
+// A chain: every node from `root` down is a branch with exactly one child, ending in a leaf. Returns its number of branch levels (0: the root
+// is a leaf), or -1 when the tree is no chain or an index leaves the array.
+int kd_chain_shape(const std::vector<KdNode>& nodes, uint32_t root);
 
 // Builds everything derived (AABBs, KD-trees, records) from the "as loaded" arrays + camera/sun floats.
 // camera13: origin(3) basis(9) fov ; sun13: basis(9) energy(3) angular_radius or nullptr.

@@ -45,9 +45,9 @@ namespace ptx {
 // parameter and not a test of the flag: at the 128-register cap the test moved the spills and scratch of most variants, so the
 // default kernels are compiled exactly as before and the mode runs ONE variant per (MODE, SURF) with everything compiled in.
 template <int MODE, bool SUN, bool ALPHA, bool TEX, bool WORKER, bool SURF, bool TRANSP>
-__global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParams P, PassBuffers B, const ModelRec* __restrict__ t_models, const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space) {
+__global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParams P, PassBuffers B, const ModelRec* __restrict__ t_models, const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space, const UnitAux* __restrict__ t_surf_aux) {
 	DevScene S = S0;
-	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;  // see struct Tables
+	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space; S.surf_aux = t_surf_aux;  // see struct Tables
 	const Staged st = stage_geometry<MODE>(S, g_smem);
 	S.hot_lds = st.hot;
 	const Geoms g = st.g;
@@ -182,7 +182,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 								if (ent) {
 									PROF(3);
 									MeshHit mh;
-									if (mesh_traverse_m<MODE, 4>(g, sf, nr, fr, lo, ld, mh, spill PROF_PASS)) best_offer(bh, M, m, ld, u, mh);
+									if (mesh_traverse_m<MODE, 4>(g, sf, S.surf_aux[u], nr, fr, lo, ld, mh, spill PROF_PASS)) best_offer(bh, M, m, ld, u, mh);
 								}
 							} else {
 								const uint32_t len = __builtin_amdgcn_readlane(list_len, u);
@@ -271,7 +271,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 								const V3 lo = mk(e0.x, e0.y, e0.z), ld = mk(e1.x, e1.y, e1.z);
 								const V3 inv = mk(1.0f / ld.x, 1.0f / ld.y, 1.0f / ld.z);
 								MeshHit mh;
-								if (!cannot_win(sf.pbmin, M.basis, lo, ld, inv, hd.x) && mesh_intersect_m<MODE, 10>(g, sf, lo, ld, inv, mh, spill PROF_PASS)) {
+								if (!cannot_win(sf.pbmin, M.basis, lo, ld, inv, hd.x) && mesh_intersect_m<MODE, 10>(g, sf, S.surf_aux[u], lo, ld, inv, mh, spill PROF_PASS)) {
 									Best b;
 									b.surf = __float_as_int(hr.x); b.tri = __float_as_uint(hr.y); b.b1 = hr.z; b.b2 = hr.w; b.wd = hd.x; b.tl = hd.y;
 									b.model = b.surf >= 0 ? (int)S.surfaces[b.surf].model : -1;   // per-lane table read, only on a hit
@@ -457,7 +457,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 								if (cnt >= kInlineMin) {
 									if (ent) {
 										MeshHit mh;
-										if (mesh_traverse_m<MODE, 4>(g, sf, nr, fr, lo, ld, mh, spill PROF_PASS) && length(mulmv(M.basis, ld * mh.t)) >= 0) occ = true;
+										if (mesh_traverse_m<MODE, 4>(g, sf, S.surf_aux[u], nr, fr, lo, ld, mh, spill PROF_PASS) && length(mulmv(M.basis, ld * mh.t)) >= 0) occ = true;
 									}
 								} else {
 									const uint32_t len = __builtin_amdgcn_readlane(list_len, u);
@@ -490,7 +490,7 @@ __global__ void __launch_bounds__(kBlock) k_render_pass(DevScene S0, RenderParam
 									const V3 lo = mk(e0.x, e0.y, e0.z), ld = mk(e1.x, e1.y, e1.z);
 									const V3 inv = mk(1.0f / ld.x, 1.0f / ld.y, 1.0f / ld.z);
 									MeshHit mh;
-									if (mesh_intersect_m<MODE, 10>(g, sf, lo, ld, inv, mh, spill PROF_PASS) && length(mulmv(M.basis, ld * mh.t)) >= 0) *kw = *kw | kOccluded;
+									if (mesh_intersect_m<MODE, 10>(g, sf, S.surf_aux[u], lo, ld, inv, mh, spill PROF_PASS) && length(mulmv(M.basis, ld * mh.t)) >= 0) *kw = *kw | kOccluded;
 								}
 							}
 						}
@@ -645,9 +645,9 @@ __global__ void k_resolve_claim(const float4* __restrict__ sample_rad, float4* _
 
 // ------------------------------------------------------------------------------------ batch intersect
 template <int MODE>
-__global__ void __launch_bounds__(kBlock) k_intersect_batch(DevScene S0, IntersectArgs A, const ModelRec* __restrict__ t_models, const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space) {
+__global__ void __launch_bounds__(kBlock) k_intersect_batch(DevScene S0, IntersectArgs A, const ModelRec* __restrict__ t_models, const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space, const UnitAux* __restrict__ t_surf_aux) {
 	DevScene S = S0;
-	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;  // see struct Tables
+	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space; S.surf_aux = t_surf_aux;  // see struct Tables
 	const Staged st = stage_geometry<MODE>(S, g_smem);
 	S.hot_lds = st.hot;
 	const Geoms g = st.g;
@@ -837,7 +837,7 @@ static hipError_t launch_pass_variant(const DevScene& S, const RenderParams& P, 
 		hipError_t e = set_lds(reinterpret_cast<const void*>(&k_render_pass<MODE, SUN, ALPHA, TEX, WORKER, SURF, TRANSP>), lds_bytes);
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL((k_render_pass<MODE, SUN, ALPHA, TEX, WORKER, SURF, TRANSP>), dim3(grid), dim3(kBlock), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, B, S.models, S.surfaces, S.spaces, S.model_space);
+	hipLaunchKernelGGL((k_render_pass<MODE, SUN, ALPHA, TEX, WORKER, SURF, TRANSP>), dim3(grid), dim3(kBlock), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, P, B, S.models, S.surfaces, S.spaces, S.model_space, S.surf_aux);
 	return hipGetLastError();
 }
 
@@ -888,7 +888,7 @@ static hipError_t launch_intersect_mode(const DevScene& S, const IntersectArgs& 
 		hipError_t e = set_lds(reinterpret_cast<const void*>(&k_intersect_batch<MODE>), lds_bytes);
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL(k_intersect_batch<MODE>, dim3(grid), dim3(kBlock), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, A, S.models, S.surfaces, S.spaces, S.model_space);
+	hipLaunchKernelGGL(k_intersect_batch<MODE>, dim3(grid), dim3(kBlock), MODE != MODE_GLOBAL ? lds_bytes : 0, stream, S, A, S.models, S.surfaces, S.spaces, S.model_space, S.surf_aux);
 	return hipGetLastError();
 }
 hipError_t launch_intersect(const DevScene& S, const IntersectArgs& A, int mode, size_t lds_bytes, int grid, hipStream_t stream) {

@@ -70,6 +70,7 @@ struct DevScene {
 	uint32_t any_texture;
 	int32_t env_tex;         // environment map (renderer::environment): texture index or -1
 	const uint32_t* model_space; // per model
+	const UnitAux* surf_aux;     // per surface: chain flag (flat_scene.hpp)
 	const uint32_t* wf_order;    // [n_surfaces] queue-based pipeline: the surfaces in the order the traverse kernel starts their queues (upload_scene)
 	int32_t n_models;
 	uint32_t n_surfaces, n_nodes, n_refs, n_tris;
@@ -97,7 +98,7 @@ struct RenderParams {
 	                            // of the pixels this pass renders (interleaved tile sharding), and n_pixels is the list's length
 };
 
-constexpr int kProfRegions = 26;   // PTX_PROF builds only: (wave-level trips, active lanes) per code region
+constexpr int kProfRegions = 28;   // PTX_PROF builds only: (wave-level trips, active lanes) per code region
 
 struct PassBuffers {
 	float4* queues;                   // [n_wave_slots][queue_stride]

@@ -54,7 +54,10 @@ void decide_mode(ptx_scene* sc) {
 	if (getenv("PTX_FORCE_GLOBAL") || h.n_resident == 0) sc->mode = MODE_GLOBAL;
 	else if (h.n_resident == h.surfaces.size()) sc->mode = MODE_LDS;
 	else sc->mode = getenv("PTX_NO_HYBRID") ? MODE_GLOBAL : MODE_HYBRID;
-	if (sc->mode == MODE_GLOBAL) for (auto& sr : h.surfaces) sr.lds_root = 0xFFFFFFFFu;
+	if (sc->mode == MODE_GLOBAL) {
+		for (auto& sr : h.surfaces) sr.lds_root = 0xFFFFFFFFu;
+		for (auto& a : h.surf_aux) a.flags &= ~kAuxChainBit;   // a flag of resident trees only
+	}
 	sc->lds_bytes = sc->mode == MODE_GLOBAL ? 0 : h.res_bytes;
 	{
 		double all = 0, res = 0;
@@ -139,6 +142,7 @@ int upload_scene(ptx_scene* sc) {
 		sc->dev.n_hot = (uint32_t)h.hot_hitrec.size();
 	}
 	HIP_TRY(up(sc->d_surfaces, h.surfaces.data(), h.surfaces.size() * sizeof(SurfaceRec), h.surfaces.size() * sizeof(SurfaceRec)));
+	HIP_TRY(up(sc->d_surf_aux, h.surf_aux.data(), h.surf_aux.size() * sizeof(UnitAux), h.surf_aux.size() * sizeof(UnitAux)));
 	// KD nodes and the global-memory triangle records share ONE allocation: the queue-based traverse kernel addresses both as
 	// `base + 32-bit offset` (wavefront.hip). + 16: the child-pair fetch of the last branch may read one node past the end.
 	const size_t nodes_bytes = (pad16(h.kd_nodes.size() * 8) + 16 + 255) & ~(size_t)255;
@@ -212,6 +216,7 @@ int upload_scene(ptx_scene* sc) {
 	DevScene& d = sc->dev;
 	d.models = (const ModelRec*)sc->d_models.p;
 	d.surfaces = (const SurfaceRec*)sc->d_surfaces.p;
+	d.surf_aux = (const UnitAux*)sc->d_surf_aux.p;
 	d.materials = (const MaterialRec*)sc->d_materials.p;
 	d.nodes = (const uint2*)sc->d_nodes.p;
 	d.refs = (const uint32_t*)sc->d_refs.p;
@@ -252,7 +257,7 @@ int upload_scene(ptx_scene* sc) {
 
 void release_scene_buffers(ptx_scene* sc) {
 	for (DevBuf* b : {&sc->d_models, &sc->d_surfaces, &sc->d_materials, &sc->d_nodes, &sc->d_refs, &sc->d_tris, &sc->d_shade, &sc->d_tex,
-	                  &sc->d_texels, &sc->d_texels_f, &sc->d_lut, &sc->d_spaces, &sc->d_model_space, &sc->d_wf_order, &sc->d_res_nodes, &sc->d_res_refs, &sc->d_res_tris, &sc->d_hot,
+	                  &sc->d_texels, &sc->d_texels_f, &sc->d_lut, &sc->d_spaces, &sc->d_model_space, &sc->d_surf_aux, &sc->d_wf_order, &sc->d_res_nodes, &sc->d_res_refs, &sc->d_res_tris, &sc->d_hot,
 	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell, &sc->d_punctual, &sc->d_punctual_cdf, &sc->d_lens})
 		b->release();
 	sc->lights.on_device = false;
@@ -806,6 +811,7 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 			float f; memcpy(&f, &w, 4); tmp.push_back(f);
 		}
 		src = tmp.data(); bytes = tmp.size() * 4; break;
+	case PTX_ARR_SURF_AUX: src = h.surf_aux.data(); bytes = h.surf_aux.size() * sizeof(UnitAux); break;
 	case PTX_ARR_RES_PLAN: {
 		const uint32_t w[4] = {(uint32_t)h.res_bytes, h.n_resident, (uint32_t)sc->lds_bytes, (uint32_t)h.hot_hitrec.size()};
 		tmp.resize(4); memcpy(tmp.data(), w, 16);

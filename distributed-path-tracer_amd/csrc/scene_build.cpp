@@ -453,8 +453,21 @@ uint32_t kd_tree_shape(const std::vector<KdNode>& nodes, uint32_t root) {
 	return kLdsCompleteBit;
 }
 
+int kd_chain_shape(const std::vector<KdNode>& nodes, uint32_t root) {
+	uint32_t n = root;
+	for (int levels = 0; levels <= 26; levels++) {   // the reference's trees are at most 26 levels deep; the bound also ends a cycle in bad input
+		if (n >= nodes.size()) return -1;
+		const uint32_t w1 = nodes[n].w1;
+		if ((w1 & 3u) == KD_LEAF) return levels;
+		if ((w1 & 12u) != 4u && (w1 & 12u) != 8u) return -1;   // both children, or none
+		n = w1 >> 4;
+	}
+	return -1;
+}
+
 void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order, bool kd_shapes) {
 	const size_t n_surf = s.surfaces.size();
+	s.surf_aux.assign(n_surf, UnitAux{});
 	s.res_nodes.clear(); s.res_refs.clear(); s.res_tris.clear();
 	s.n_resident = 0;
 	for (auto& sr : s.surfaces) sr.lds_root = 0xFFFFFFFFu;
@@ -520,6 +533,7 @@ void plan_residency(FlatScene& s, size_t lds_budget, bool lds_leaf_order, bool k
 		assert(root <= kLdsRootMask);   // a resident tree fits LDS: a few thousand nodes
 		const uint32_t shape = (kd_shapes && leaf_order[si]) ? kd_tree_shape(s.res_nodes, root) : 0u;
 		s.surfaces[si].lds_root = root | (leaf_order[si] ? kLdsLeafOrderBit : 0u) | shape;
+		if (kd_shapes && leaf_order[si] && kd_chain_shape(s.res_nodes, root) >= 0) s.surf_aux[si].flags |= kAuxChainBit;
 		s.n_resident++;
 	}
 	s.res_bytes = s.res_tris.size() * 48 + shade_bytes + ((s.res_nodes.size() * 8 + 15) & ~(size_t)15) + ((s.res_refs.size() * 4 + 15) & ~(size_t)15);

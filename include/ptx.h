@@ -237,8 +237,10 @@ typedef enum ptx_array {
 	PTX_ARR_PUNCTUAL = 28,    /* float[n][16], as stored */
 	PTX_ARR_PUNCTUAL_CDF = 29,/* float[n]: cumulative share of lum(intensity), the last entry 1 */
 	PTX_ARR_LENS = 30,        /* float[blades + 1][2]: the aperture table of ptx_scene_set_camera; empty while lens_radius == 0 */
-	PTX_ARR_LDS_SHAPE = 31    /* uint32[n_surfaces]: the surface records' whole lds_root word: LDS_ROOT's (root in bits 28:0) | leaf-only tree << 30 |
+	PTX_ARR_LDS_SHAPE = 31,   /* uint32[n_surfaces]: the surface records' whole lds_root word: LDS_ROOT's (root in bits 28:0) | leaf-only tree << 30 |
 	                           * complete tree of at most 3 branch levels << 29 (the shape bits: leaf-ordered surfaces only, none with PTX_KD_SHAPES=0) */
+	PTX_ARR_SURF_AUX = 32     /* uint32[n_surfaces][4]: the auxiliary surface records: word 0 = flags, bit 0 = the resident, leaf-ordered tree is a
+	                           * chain: every branch has exactly one child, down to a leaf (none with PTX_KD_SHAPES=0); words 1-3 are padding */
 } ptx_array;
 int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, size_t dst_bytes);
 
