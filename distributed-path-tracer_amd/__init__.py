@@ -29,7 +29,8 @@ NO_SUN_LIGHT = 0xFFFFFFFF  # core::renderer::no_sun_light, renderer.hpp:19
 (ARR_MODEL_XFORM, ARR_MODEL_AABB, ARR_MODEL_SURF, ARR_SURF_RANGE, ARR_MESH_AABB, ARR_VERTICES, ARR_TRIANGLES,
  ARR_MATERIALS, ARR_KD_NODES, ARR_KD_REFS, ARR_CAMERA, ARR_SUN, ARR_MODEL_NAMES, ARR_TEXTURES, ARR_TEXELS, ARR_SURF_TEX, ARR_TEXELS_F32,
  ARR_LIGHT_TRIS, ARR_LIGHT_CDF, ARR_LIGHT_GEOM, ARR_TRI_ISECT, ARR_RES_NODES, ARR_RES_REFS, ARR_RES_TRIS, ARR_LDS_ROOT,
- ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF, ARR_PUNCTUAL, ARR_PUNCTUAL_CDF, ARR_LENS, ARR_LDS_SHAPE, ARR_SURF_AUX) = range(33)
+ ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF, ARR_PUNCTUAL, ARR_PUNCTUAL_CDF, ARR_LENS, ARR_LDS_SHAPE, ARR_SURF_AUX,
+ ARR_MOTION_XFORM, ARR_MOTION_MOVED, ARR_MOTION_CAMERA) = range(36)
 LDS_LEAF_ORDER_BIT = 0x80000000  # ARR_LDS_ROOT: the surface's resident records are leaf-ordered (flat_scene.hpp)
 LDS_LEAF_ONLY_BIT = 0x40000000   # ARR_LDS_SHAPE: the surface's resident tree is a single leaf
 LDS_COMPLETE_BIT = 0x20000000    # ARR_LDS_SHAPE: ... is complete (no missing child) with at most KD_SHAPE_MAX_BRANCH_LEVELS branch levels
@@ -71,6 +72,11 @@ class Camera(C.Structure):
 
 class MotionPrev(C.Structure):
     _fields_ = [("camera", C.POINTER(Camera)), ("model_xform", C.c_void_p), ("n_models", C.c_uint32)]
+
+
+class Motion(C.Structure):
+    _fields_ = [("begin_camera", C.POINTER(Camera)), ("begin_model_xform", C.c_void_p), ("n_models", C.c_uint32),
+                ("shutter_open", C.c_float), ("shutter_close", C.c_float)]
 
 
 class SceneInfo(C.Structure):
@@ -253,6 +259,9 @@ def lib():
         L.ptx_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
         L.ptx_scene_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
         L.ptx_scene_set_model_xforms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ptx_scene_set_motion.argtypes = [C.c_void_p, C.POINTER(Motion)]
+        L.ptx_scene_motion_state.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        L.ptx_intersect_batch_motion.argtypes = [C.c_void_p, C.POINTER(Rays), C.c_void_p, C.c_size_t, C.POINTER(Hits)]
         L.ptx_camera_lens_rays_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_gltf_read_punctual_lights.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
         L.ptx_gltf_read_punctual_lights.restype = C.c_int64
@@ -583,7 +592,8 @@ _ARR_DTYPE = {ARR_MODEL_XFORM: (np.float32, 12), ARR_MODEL_AABB: (np.float32, 6)
               ARR_TRI_ISECT: (np.uint32, 12), ARR_RES_NODES: (np.uint32, 2), ARR_RES_REFS: (np.uint32, 1), ARR_RES_TRIS: (np.uint32, 12),
               ARR_LDS_ROOT: (np.uint32, 1), ARR_RES_PLAN: (np.uint32, 1), ARR_ENV_ROW_CDF: (np.float32, 1), ARR_ENV_CELL_CDF: (np.float32, 1),
               ARR_PUNCTUAL: (np.float32, 16), ARR_PUNCTUAL_CDF: (np.float32, 1), ARR_LENS: (np.float32, 2),
-              ARR_LDS_SHAPE: (np.uint32, 1), ARR_SURF_AUX: (np.uint32, 4)}
+              ARR_LDS_SHAPE: (np.uint32, 1), ARR_SURF_AUX: (np.uint32, 4),
+              ARR_MOTION_XFORM: (np.float32, 12), ARR_MOTION_MOVED: (np.uint32, 1), ARR_MOTION_CAMERA: (np.float32, 1)}
 
 
 class Scene:
@@ -867,6 +877,74 @@ class Scene:
         if a.size % 12:
             raise PtxError(ERR_INVALID, "set_model_xforms: the array is not [n, 12]")
         _check(lib().ptx_scene_set_model_xforms(self.h, a.ctypes.data, a.size // 12))
+
+    def set_motion(self, begin_model_xform=None, begin_camera=None, shutter=(0.0, 1.0)):
+        """ptx_scene_set_motion: the scene as it stands is the state at u = 1; begin_model_xform ([n_models, 12] float32, ARR_MODEL_XFORM's
+        layout) and begin_camera (a dict as camera() returns, or (origin [3], basis [9], yfov)) give the state at u = 0. None: that part does
+        not move. shutter = (open, close) within [0, 1]. set_model_xforms and set_camera clear the motion: call them first, this last."""
+        m = Motion()
+        keep = []
+        if begin_model_xform is not None:
+            a = np.ascontiguousarray(begin_model_xform, np.float32)
+            if a.size % 12:
+                raise PtxError(ERR_INVALID, "set_motion: begin_model_xform is not [n, 12]")
+            keep.append(a)
+            m.begin_model_xform, m.n_models = a.ctypes.data, a.size // 12
+        if begin_camera is not None:
+            if isinstance(begin_camera, dict):
+                o, b, yfov = begin_camera["origin"], begin_camera["basis"], begin_camera["yfov"]
+            else:
+                o, b, yfov = begin_camera
+            o, b = np.asarray(o, np.float32).reshape(-1), np.asarray(b, np.float32).reshape(-1)
+            if len(o) != 3 or len(b) != 9:
+                raise PtxError(ERR_INVALID, "set_motion: the begin camera's origin is [3], its basis is [9]")
+            cam = Camera((C.c_float * 3)(*o), (C.c_float * 9)(*b), float(yfov), 0.0, 0.0, 0, 0.0)
+            keep.append(cam)
+            m.begin_camera = C.pointer(cam)
+        m.shutter_open, m.shutter_close = float(shutter[0]), float(shutter[1])
+        _check(lib().ptx_scene_set_motion(self.h, C.byref(m)))
+
+    def clear_motion(self):
+        """ptx_scene_set_motion(scene, NULL): the scene renders as one never given motion."""
+        _check(lib().ptx_scene_set_motion(self.h, None))
+
+    def motion_state(self, u):
+        """ptx_scene_motion_state -> (model_xform [n_models, 12], camera [12]: origin, basis) at time u, by the function the kernels use.
+        Static models and a static camera come back as they are stored."""
+        n = self.info()["n_models"]
+        x, cam = np.zeros((n, 12), np.float32), np.zeros(12, np.float32)
+        _check(lib().ptx_scene_motion_state(self.h, float(u), x.ctypes.data, cam.ctypes.data))
+        return x, cam
+
+    def intersect_motion(self, origins, dirs, time, attributes=True):
+        """ptx_intersect_batch_motion: intersect() with a time per ray ([n] float32). origins/dirs [n,3] and time are numpy arrays, or torch
+        tensors on the scene's GPU (then the outputs are torch tensors there). Without a moving model `time` is ignored."""
+        if isinstance(origins, np.ndarray) or not hasattr(origins, "data_ptr"):
+            o = np.ascontiguousarray(np.asarray(origins, np.float32).T)
+            d = np.ascontiguousarray(np.asarray(dirs, np.float32).T)
+            t = np.ascontiguousarray(np.asarray(time, np.float32).reshape(-1))
+            n = o.shape[1]
+            new = lambda dt: np.zeros(n, dt)
+            f32, i32 = np.float32, np.int32
+        else:
+            torch = _torch()
+            o, d = origins.float().t().contiguous(), dirs.float().t().contiguous()
+            t = time.float().reshape(-1).contiguous()
+            n = o.shape[1]
+            new = lambda dt: torch.zeros(n, dtype=dt, device=o.device)
+            f32, i32 = torch.float32, torch.int32
+        if len(t) != n:
+            raise PtxError(ERR_INVALID, "intersect_motion: time is not [n]")
+        out = {k: new(f32) for k in ("distance", "b0", "b1", "b2")}
+        out["surface"], out["triangle"] = new(i32), new(i32)
+        if attributes:
+            out.update({k: new(f32) for k in ("px", "py", "pz", "nx", "ny", "nz", "u", "v")})
+        r = Rays(*[_ptr(o[k]) for k in range(3)], *[_ptr(d[k]) for k in range(3)])
+        hh = Hits(*[_ptr(out[k]) if k in out else None for k, _ in Hits._fields_])
+        _check(lib().ptx_intersect_batch_motion(self.h, C.byref(r), _ptr(t), n, C.byref(hh)))
+        if not isinstance(o, np.ndarray):
+            self.ctx.synchronize()   # device buffers: the call returns with the work queued on the context's stream
+        return out
 
     def lens_rays(self, in5):
         """ptx_camera_lens_rays_batch: [n,5] float32 (ndc.x, ndc.y, aspect ratio, u, v) -> [n,6] float32 (origin, direction): the lens ray the

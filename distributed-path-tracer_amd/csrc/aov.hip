@@ -29,11 +29,13 @@ DEV void aov_sample_of(const RenderParams& P, uint32_t id, uint32_t& px, uint32_
 }
 
 // camera samples 0 .. n-1 of the pass -> stream entries 0 .. n-1 (scene::camera::get_ray; renderer.cpp:359-370)
-__global__ void __launch_bounds__(kAovBlock) k_aov_generate(DevScene S, RenderParams P, AovStream out, uint32_t n) {
+__global__ void __launch_bounds__(kAovBlock) k_aov_generate(DevScene S0, RenderParams P, AovStream out, uint32_t n, RenderMotion Rm) {
 	const uint32_t i = blockIdx.x * kAovBlock + threadIdx.x;
 	if (i >= n) return;
 	uint32_t px, py, sample;
 	aov_sample_of(P, i, px, py, sample);
+	DevScene S = S0;
+	if (Rm.camera_moved) camera_at(S, Rm, sample_time(P, Rm, py * P.W + px, sample));   // the camera of the sample's own time (wave-uniform test)
 	V3 o, d;
 	camera_ray(S, P, px, py, sample, o, d);
 	out.ox[i] = o.x; out.oy[i] = o.y; out.oz[i] = o.z;
@@ -80,7 +82,7 @@ enum : int { AOV_GUIDES = 0, AOV_MOTION = 1, AOV_EMISSION = 2 };
 // One vertex of every live sample. TEX / ALPHA compile the texture lookups / the pass-through in, as the render variants do.
 template <bool TEX, bool ALPHA, int KIND>
 DEV void aov_shade_sample(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* __restrict__ n_out,
-                          float4* __restrict__ rec, size_t rec_stride, const AovMotion* Mo) {
+                          float4* __restrict__ rec, size_t rec_stride, const AovMotion* Mo, const RenderMotion* Rm = nullptr) {
 	const uint32_t i = blockIdx.x * kAovBlock + threadIdx.x;
 	bool through = false;
 	V3 o = {0, 0, 0}, d = {0, 0, 1};
@@ -93,7 +95,23 @@ DEV void aov_shade_sample(const DevScene& S, const RenderParams& P, const AovStr
 		if (surf >= 0) {
 			const ShadeRec& R = S.shade[surf];
 			Surf sf;
-			hit_attributes(S, R, (uint32_t)H.triangle[i] + S.surfaces[surf].tri_base, H.b1[i], H.b2[i], sf);
+			// active motion (the guide kernels alone; a wave-uniform test of a kernel argument): the sample's time, and the records of a moving
+			// model's surface at that time
+			float u = 0;
+			bool moved = false;
+			XformRecs Xm;
+			if (Rm && Rm->active) {
+				uint32_t tx, ty, tsample;
+				aov_sample_of(P, id, tx, ty, tsample);
+				u = sample_time(P, *Rm, ty * P.W + tx, tsample);
+				if (Rm->models_moved) {
+					const uint32_t m = S.surfaces[surf].model;
+					moved = Rm->models.moved[m] != 0u;
+					if (moved) model_records_at(Rm->models, m, u, Xm);
+				}
+			}
+			if (moved) hit_attributes_at(S, Xm.basis, Xm.origin, Xm.nmat, (uint32_t)H.triangle[i] + S.surfaces[surf].tri_base, H.b1[i], H.b2[i], sf);
+			else hit_attributes(S, R, (uint32_t)H.triangle[i] + S.surfaces[surf].tri_base, H.b1[i], H.b2[i], sf);
 			const MatEval me = material_eval<TEX>(S, R.mat, sf.u, sf.v);   // renderer.cpp:458-463
 			bool transparent = false;
 			if constexpr (ALPHA) {
@@ -122,7 +140,12 @@ DEV void aov_shade_sample(const DevScene& S, const RenderParams& P, const AovStr
 					const V3 nrm = shading_normal(sf, me.normal_ts);   // intersect_result::get_normal()
 					uint32_t cx, cy, csample;
 					aov_sample_of(P, id, cx, cy, csample);
-					const V3 co = camera_ray_origin(S, P, cx, cy, csample);   // origin of THIS sample's camera ray: with a lens, its lens point
+					V3 co;   // origin of THIS sample's camera ray: with a lens, its lens point; under motion, of the camera at the sample's time
+					if (Rm && Rm->camera_moved) {
+						DevScene Sc = S;
+						camera_at(Sc, *Rm, u);
+						co = camera_ray_origin(Sc, P, cx, cy, csample);
+					} else co = camera_ray_origin(S, P, cx, cy, csample);
 					ra = make_float4(me.albedo.x, me.albedo.y, me.albedo.z, 1.0f);
 					rn = make_float4(nrm.x, nrm.y, nrm.z, length(sf.pos - co));
 				}
@@ -152,8 +175,8 @@ DEV void aov_shade_sample(const DevScene& S, const RenderParams& P, const AovStr
 
 template <bool TEX, bool ALPHA>
 __global__ void __launch_bounds__(kAovBlock) k_aov_shade(DevScene S, RenderParams P, AovStream in, AovHits H, uint32_t n, AovStream out, uint32_t* __restrict__ n_out,
-                                                         float4* __restrict__ rec, size_t rec_stride) {
-	aov_shade_sample<TEX, ALPHA, AOV_GUIDES>(S, P, in, H, n, out, n_out, rec, rec_stride, nullptr);
+                                                         float4* __restrict__ rec, size_t rec_stride, RenderMotion Rm) {
+	aov_shade_sample<TEX, ALPHA, AOV_GUIDES>(S, P, in, H, n, out, n_out, rec, rec_stride, nullptr, &Rm);
 }
 
 template <bool TEX, bool ALPHA>
@@ -193,20 +216,20 @@ __global__ void k_aov_resolve(const float4* __restrict__ rec, size_t rec_stride,
 }
 
 // ------------------------------------------------------------------------------------ launchers
-hipError_t launch_aov_generate(const DevScene& S, const RenderParams& P, const AovStream& out, uint32_t n, hipStream_t stream) {
-	hipLaunchKernelGGL(k_aov_generate, dim3((n + kAovBlock - 1) / kAovBlock), dim3(kAovBlock), 0, stream, S, P, out, n);
+hipError_t launch_aov_generate(const DevScene& S, const RenderParams& P, const AovStream& out, uint32_t n, const RenderMotion& Rm, hipStream_t stream) {
+	hipLaunchKernelGGL(k_aov_generate, dim3((n + kAovBlock - 1) / kAovBlock), dim3(kAovBlock), 0, stream, S, P, out, n, Rm);
 	return hipGetLastError();
 }
 
 hipError_t launch_aov_shade(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* n_out, float4* rec,
-                            size_t rec_stride, hipStream_t stream) {
+                            size_t rec_stride, const RenderMotion& Rm, hipStream_t stream) {
 	const dim3 grid((n + kAovBlock - 1) / kAovBlock), block(kAovBlock);
 	if (S.any_texture) {
-		if (S.any_alpha) hipLaunchKernelGGL((k_aov_shade<true, true>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, rec_stride);
-		else hipLaunchKernelGGL((k_aov_shade<true, false>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, rec_stride);
+		if (S.any_alpha) hipLaunchKernelGGL((k_aov_shade<true, true>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, rec_stride, Rm);
+		else hipLaunchKernelGGL((k_aov_shade<true, false>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, rec_stride, Rm);
 	} else {
-		if (S.any_alpha) hipLaunchKernelGGL((k_aov_shade<false, true>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, rec_stride);
-		else hipLaunchKernelGGL((k_aov_shade<false, false>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, rec_stride);
+		if (S.any_alpha) hipLaunchKernelGGL((k_aov_shade<false, true>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, rec_stride, Rm);
+		else hipLaunchKernelGGL((k_aov_shade<false, false>), grid, block, 0, stream, S, P, in, H, n, out, n_out, rec, rec_stride, Rm);
 	}
 	return hipGetLastError();
 }

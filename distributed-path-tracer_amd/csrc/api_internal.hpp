@@ -130,10 +130,18 @@ struct ptx_scene {
 		std::vector<float> recs, cdf;   // [n][16], [n]
 	} punctual;
 	DevBuf d_punctual, d_punctual_cdf;
+	// The motion table (ptx_scene_set_motion): begin transforms, current transforms, moved flags, in one buffer; dev_motion points into it
+	// while the scene's motion moves a model, and is all nullptr otherwise. The begin camera travels in kernel arguments.
+	DevBuf d_motion;
+	DevMotion dev_motion{};
 	DevBuf d_lens;   // the aperture table (kLensMaxBlades + 1 corners), allocated by upload_scene, refreshed in stream order by ptx_scene_set_camera
 };
 
 const ptx_scene::LightList* build_lights(ptx_scene* sc);   // ptx_api.cpp
+// Whether a time-dependent state is in force (ptx_scene_set_motion with a model or the camera moving). The caller holds the context's mutex.
+inline bool motion_active(const ptx_scene* sc) { return sc->host.motion.active(); }
+// What the entry points that know no time answer while motion is active: PTX_ERR_UNSUPPORTED, before any device work
+int refuse_motion(const char* who);   // ptx_api.cpp
 const ptx_scene::EnvTable* build_env_table(ptx_scene* sc);   // ptx_api.cpp
 void srgb_thresholds(float thr[256]);                      // ptx_api.cpp
 // api_batch.cpp: one decision on device buffers (adaptive.hip), its count read back: the stream is synchronised. The caller holds the

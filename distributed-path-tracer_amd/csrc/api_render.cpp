@@ -450,6 +450,7 @@ int PassFrame::plan(ptx_ctx* c, const ptx_scene* sc, const char* who, const Pixe
 
 int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_render_stats* stats) {
 	if (!sc || !cfg || !accum) return set_err(PTX_ERR_INVALID, "ptx_render: NULL argument");
+	if (motion_active(sc)) return refuse_motion("ptx_render");
 	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render: scene was created without a GPU context (no CPU path exists)");
 	return render_frame(sc, cfg, "ptx_render", accum, nullptr, stats);
 }
@@ -457,6 +458,7 @@ int ptx_render(ptx_scene* sc, const ptx_render_cfg* cfg, float* accum, ptx_rende
 int ptx_render_transparent(ptx_scene* sc, const ptx_render_cfg* cfg, float* pixel_rgba, uint8_t* claimed, ptx_render_stats* stats) {
 	// every refusal below is decided before any device work
 	if (!sc || !cfg || !pixel_rgba || !claimed) return set_err(PTX_ERR_INVALID, "ptx_render_transparent: NULL argument");
+	if (motion_active(sc)) return refuse_motion("ptx_render_transparent");
 	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
 		return set_err(PTX_ERR_UNSUPPORTED, "ptx_render_transparent: PTX_INTEGRATOR_WORKER has no transparent-background mode here (the worker takes the alpha of the "
 		                                    "path's last vertex and jitters sample 0 in this mode, and nothing pins that); use PTX_INTEGRATOR_LIB");
@@ -467,9 +469,25 @@ int ptx_render_transparent(ptx_scene* sc, const ptx_render_cfg* cfg, float* pixe
 
 namespace {
 
+// The scene's motion as the unfused integrators' kernels take it; all zero (active == 0) without active motion. The caller holds the
+// context's mutex.
+RenderMotion render_motion(const ptx_scene* sc) {
+	RenderMotion R{};
+	const FlatScene::Motion& mo = sc->host.motion;
+	if (!mo.active()) return R;
+	R.active = 1u;
+	R.camera_moved = mo.camera_moved ? 1u : 0u;
+	R.models_moved = mo.any_model() ? 1u : 0u;
+	if (R.models_moved) R.models = sc->dev_motion;
+	memcpy(R.cam_begin, mo.begin_camera, sizeof R.cam_begin);
+	R.shutter_open = mo.shutter_open;
+	R.shutter_close = mo.shutter_close;
+	return R;
+}
+
 // Closest hits of the A.n rays of `A` (device memory) on the scene's own route — the routing body of ptx_intersect_batch, shared with
 // ptx_render_aov: the queue-based pipeline in slices with its overflow / retry handling, or the fused kernel's traversal. The caller holds
-// the context's mutex and has set the device.
+// the context's mutex and has set the device. With A.time set (and A.motion with it) every ray has a time: the motion kernels of either route.
 int intersect_device(ptx_ctx* c, ptx_scene* sc, IntersectArgs& A) {
 	if (use_wavefront(sc)) {
 		// queue-based pipeline, a slice of the batch at a time: as many rays as the pool serves at the pairs per ray this scene was seen
@@ -523,38 +541,52 @@ int intersect_device(ptx_ctx* c, ptx_scene* sc, IntersectArgs& A) {
 		const int grid = (int)std::min<size_t>((size_t)c->n_cu, (A.n + kBlock - 1) / kBlock);
 		HIP_TRY(c->spill.ensure((size_t)c->n_cu * (kBlock / 64) * (size_t)kSpillWords * sizeof(uint2)));
 		A.spill = (uint2*)c->spill.p;
-		HIP_TRY(launch_intersect(sc->dev, A, sc->mode, sc->lds_bytes, grid, c->stream));
+		if (A.time) HIP_TRY(launch_intersect_motion(sc->dev, A, sc->mode, sc->lds_bytes, grid, c->stream));
+		else HIP_TRY(launch_intersect(sc->dev, A, sc->mode, sc->lds_bytes, grid, c->stream));
 	}
 	return PTX_OK;
 }
 
 }  // namespace
 
-int ptx_intersect_batch(ptx_scene* sc, const ptx_rays* r, size_t n, const ptx_hits* hh) {
-	if (!sc || !r || !hh) return set_err(PTX_ERR_INVALID, "ptx_intersect_batch: NULL argument");
-	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_intersect_batch: scene was created without a GPU context (no CPU path exists)");
+namespace {
+
+// ptx_intersect_batch (time == nullptr) and ptx_intersect_batch_motion: the same refusals and staging. A time array is used only while
+// the scene's motion is active; without it the call is ptx_intersect_batch, launch for launch.
+int intersect_batch(const char* who_c, ptx_scene* sc, const ptx_rays* r, const float* time, size_t n, const ptx_hits* hh) {
+	const std::string who = who_c;
+	if (!sc || !r || !hh) return set_err(PTX_ERR_INVALID, who + ": NULL argument");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, who + ": scene was created without a GPU context (no CPU path exists)");
 	if (n == 0) return PTX_OK;
 	if (!r->ox || !r->oy || !r->oz || !r->dx || !r->dy || !r->dz || !hh->distance || !hh->surface || !hh->triangle || !hh->b0 || !hh->b1 || !hh->b2)
-		return set_err(PTX_ERR_INVALID, "ptx_intersect_batch: required array is NULL");
+		return set_err(PTX_ERR_INVALID, who + ": required array is NULL");
 	auto group_ok = [](const void* a, const void* b, const void* c) { return (!a && !b && !c) || (a && b && c); };
 	if (!group_ok(hh->px, hh->py, hh->pz) || !group_ok(hh->nx, hh->ny, hh->nz) || ((hh->u != nullptr) != (hh->v != nullptr)))
-		return set_err(PTX_ERR_INVALID, "ptx_intersect_batch: optional outputs must be given as whole groups");
+		return set_err(PTX_ERR_INVALID, who + ": optional outputs must be given as whole groups");
 	ptx_ctx* c = sc->ctx;
 	std::lock_guard<std::mutex> lk(c->mu);
 	HIP_TRY(hipSetDevice(c->device));
 	const bool dev = is_device_ptr(r->ox);
+	// the time of a ray matters only where a model moves: a moving camera alone leaves every ray's scene the scene at u = 1
+	const bool timed = time && sc->host.motion.set && sc->host.motion.any_model();
+	if (timed && is_device_ptr(time) != dev) return set_err(PTX_ERR_INVALID, who + ": time must be device or host memory as the rays are");
 	IntersectArgs A{};
 	A.n = n;
 	const int n_out = 6 + (hh->px ? 3 : 0) + (hh->nx ? 3 : 0) + (hh->u ? 2 : 0);
-	// host arrays are staged one by one: the rays in stage_a, the outputs that were asked for in stage_b, each group `n` entries apart
+	// host arrays are staged one by one: the rays (and their times) in stage_a, the outputs that were asked for in stage_b, each group `n` entries apart
 	if (!dev) {
-		HIP_TRY(c->stage_a.ensure(6 * n * 4));
+		HIP_TRY(c->stage_a.ensure((timed ? 7 : 6) * n * 4));
 		HIP_TRY(c->stage_b.ensure((size_t)n_out * n * 4));
 	}
 	const float* const src[6] = {r->ox, r->oy, r->oz, r->dx, r->dy, r->dz};
 	void* const dst[14] = {hh->distance, hh->surface, hh->triangle, hh->b0, hh->b1, hh->b2, hh->px, hh->py, hh->pz, hh->nx, hh->ny, hh->nz, hh->u, hh->v};
-	Staged in[6], o[14];
+	Staged in[6], o[14], s_time;
 	for (int k = 0; k < 6; k++) HIP_TRY(in[k].bind(c, dev, src[k], n * 4, c->stage_a, k * n * 4));
+	if (timed) {
+		HIP_TRY(s_time.bind(c, dev, time, n * 4, c->stage_a, 6 * n * 4));
+		A.time = s_time.as<float>();
+		A.motion = sc->dev_motion;
+	}
 	for (size_t k = 0, slot = 0; k < 14; k++)
 		if (dst[k]) HIP_TRY(o[k].bind(c, dev, dst[k], n * 4, c->stage_b, slot++ * n * 4, kOutputOnly));
 	A.ox = in[0].as<float>(); A.oy = in[1].as<float>(); A.oz = in[2].as<float>(); A.dx = in[3].as<float>(); A.dy = in[4].as<float>(); A.dz = in[5].as<float>();
@@ -568,6 +600,15 @@ int ptx_intersect_batch(ptx_scene* sc, const ptx_rays* r, size_t n, const ptx_hi
 	return PTX_OK;
 }
 
+}  // namespace
+
+int ptx_intersect_batch(ptx_scene* sc, const ptx_rays* r, size_t n, const ptx_hits* hh) { return intersect_batch("ptx_intersect_batch", sc, r, nullptr, n, hh); }
+
+int ptx_intersect_batch_motion(ptx_scene* sc, const ptx_rays* r, const float* time, size_t n, const ptx_hits* hh) {
+	if (!time && n) return set_err(PTX_ERR_INVALID, "ptx_intersect_batch_motion: time is NULL");
+	return intersect_batch("ptx_intersect_batch_motion", sc, r, time, n, hh);
+}
+
 namespace {
 
 // ptx_render_aov, ptx_render_motion and ptx_render_emission: the same refusals about the cfg and the scene, the same passes and rounds.
@@ -578,6 +619,7 @@ int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float
               ptx_render_stats* stats) {
 	const bool motion = kind == AovKind::motion;
 	const std::string who = who_c;
+	if (kind != AovKind::guides && motion_active(sc)) return refuse_motion(who_c);   // the guide buffers know the shutter; motion vectors and emission do not
 	if (cfg->integrator == PTX_INTEGRATOR_WORKER)
 		return set_err(PTX_ERR_UNSUPPORTED, who + ": PTX_INTEGRATOR_WORKER has no first-hit buffers here (the worker's opacity handling and its un-jittered "
 		                                    "sample 0 are not pinned); use PTX_INTEGRATOR_LIB");
@@ -623,10 +665,12 @@ int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float
 		}
 	}
 	const size_t n_models = prev_xform ? moved.size() : 0;
+	const RenderMotion Rm = render_motion(sc);   // active only for the guides (the other kinds were refused above)
 	uint32_t* live_count = nullptr;
 	AovStream st[2];
 	float* hits = nullptr;
 	float4* rec = nullptr;
+	float* times = nullptr;   // under motion of a model: the time of each ray of the round, in stream order
 	float* d_xform = nullptr;
 	uint32_t* d_moved = nullptr;
 	auto carve = [&](void* base) {
@@ -641,6 +685,7 @@ int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float
 		rec = k.take<float4>((kind == AovKind::guides ? 2 : 1) * cap);
 		d_xform = k.take<float>(12 * n_models);
 		d_moved = k.take<uint32_t>(n_models);
+		times = k.take<float>(Rm.models_moved ? cap : 0);
 		return k.off;
 	};
 	HIP_TRY(c->round_ws.ensure(carve(nullptr)));
@@ -665,7 +710,7 @@ int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float
 		RenderParams P = f.params(p, false);
 		P.integrator = PTX_INTEGRATOR_LIB;
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
-		HIP_TRY(launch_aov_generate(sc->dev, P, st[0], (uint32_t)P.n_paths, c->stream));
+		HIP_TRY(launch_aov_generate(sc->dev, P, st[0], (uint32_t)P.n_paths, Rm, c->stream));
 		uint32_t live = (uint32_t)P.n_paths;
 		for (uint32_t round = 0; live != 0; round++) {
 			AovStream in = st[round & 1u];
@@ -674,6 +719,11 @@ int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float
 			A.n = live;
 			ray_args(A, in.ox, cap);
 			hit_args(A, hits, cap);
+			if (Rm.models_moved) {   // a time per ray: the sample's, whichever round its ray is in
+				HIP_TRY(launch_motion_times(P, Rm, in.id, live, times, c->stream));
+				A.time = times;
+				A.motion = Rm.models;
+			}
 			if (const int rc = intersect_device(c, sc, A); rc != PTX_OK) return rc;
 			rays += live;
 			const AovHits H{A.surface, A.triangle, A.b1, A.b2};
@@ -681,7 +731,7 @@ int aov_frame(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who_c, float
 			if (follow) HIP_TRY(hipMemsetAsync(n_out, 0, 4, c->stream));
 			if (motion) HIP_TRY(launch_aov_motion_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, Mo, c->stream));
 			else if (kind == AovKind::emission) HIP_TRY(launch_aov_emission_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, c->stream));
-			else HIP_TRY(launch_aov_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, cap, c->stream));
+			else HIP_TRY(launch_aov_shade(sc->dev, P, in, H, live, st[(round + 1u) & 1u], n_out, rec, cap, Rm, c->stream));
 			if (!follow) break;
 			HIP_TRY(hipMemcpyAsync(&live, n_out, 4, hipMemcpyDeviceToHost, c->stream));
 			HIP_TRY(hipStreamSynchronize(c->stream));
@@ -766,7 +816,8 @@ int nee_setup_locked(ptx_scene* sc, uint32_t flags, NeeSetup& S) {
 	const uint32_t n_lights = (uint32_t)ll.cdf.size();
 	S.n_lights = n_lights; S.light_area = ll.area;
 	// PTX_NEE_FUSED: one launch per pass wherever ptx_render would run the fused kernel; a scene of the queue route renders as without the flag
-	S.fused = (flags & PTX_NEE_FUSED) != 0 && !use_wavefront(sc);
+	// ... and under active motion, where the unfused form alone carries a time per sample: ignored, not refused
+	S.fused = (flags & PTX_NEE_FUSED) != 0 && !use_wavefront(sc) && !motion_active(sc);
 	if (n_lights && !(flags & PTX_NEE_NO_LIGHT_SAMPLES)) {
 		if (!sc->lights.on_device) {
 			HIP_TRY(sc->d_light_tris.ensure(ll.tris.size() * 4));
@@ -886,6 +937,8 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 	NeeStream st[2];
 	float *hits = nullptr, *shits = nullptr;
 	NeeShadow W{};
+	const RenderMotion Rm = render_motion(sc);
+	float* times = nullptr;   // under motion of a model: the time of each path ray of the round, in stream order; the shadow rays' are W.tm
 	auto carve = [&](void* base) {
 		Carver k(base);
 		cnt = k.take<uint32_t>(64);
@@ -903,6 +956,8 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 		W.sx = k.take<float>(cap); W.sy = k.take<float>(cap); W.sz = k.take<float>(cap);
 		W.lx = k.take<float>(cap); W.ly = k.take<float>(cap); W.lz = k.take<float>(cap);
 		W.sun_pos = k.take<uint32_t>(cap); W.light_pos = k.take<uint32_t>(cap); W.exp_surf = k.take<uint32_t>(cap); W.exp_tri = k.take<uint32_t>(cap);
+		times = k.take<float>(Rm.models_moved ? cap : 0);
+		W.tm = k.take<float>(Rm.active ? 2 * cap : 0);
 		return k.off;
 	};
 	HIP_TRY(c->round_ws.ensure(carve(nullptr)));
@@ -918,7 +973,7 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 		RenderParams P = f.params(p, true);
 		P.integrator = PTX_INTEGRATOR_LIB;
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
-		HIP_TRY(launch_nee_generate(sc->dev, P, st[0], Lrec, (uint32_t)P.n_paths, c->stream));
+		HIP_TRY(launch_nee_generate(sc->dev, P, st[0], Lrec, (uint32_t)P.n_paths, Rm, c->stream));
 		uint32_t live = P.bounces > 0 ? (uint32_t)P.n_paths : 0u;
 		for (uint32_t round = 0; live != 0; round++) {
 			const NeeStream& in = st[round & 1u];
@@ -927,11 +982,16 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 			A.n = live;
 			ray_args(A, in.ox, cap);
 			hit_args(A, hits, cap);
+			if (Rm.models_moved) {   // a time per ray: the sample's, whichever round its path is in
+				HIP_TRY(launch_motion_times(P, Rm, in.id, live, times, c->stream));
+				A.time = times;
+				A.motion = Rm.models;
+			}
 			if (const int rc = intersect_device(c, sc, A); rc != PTX_OK) return rc;
 			rays += live;
 			const NeeHits H{A.distance, A.surface, A.triangle, A.b1, A.b2};
 			HIP_TRY(hipMemsetAsync(cnt, 0, 8, c->stream));
-			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, Ev, S.Pn, S.sampler_pdf, S.candidates, in, H, live, out, W, cnt, Lrec, c->stream));
+			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, Ev, S.Pn, S.sampler_pdf, S.candidates, in, H, live, out, W, cnt, Lrec, Rm, c->stream));
 			uint32_t got[2] = {0, 0};   // continuations, shadow rays
 			HIP_TRY(hipMemcpyAsync(got, cnt, 8, hipMemcpyDeviceToHost, c->stream));
 			HIP_TRY(hipStreamSynchronize(c->stream));
@@ -941,6 +1001,7 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 				B.n = got[1];
 				ray_args(B, W.ox, 2 * cap);
 				hit_args(B, shits, 2 * cap);
+				if (Rm.models_moved) { B.time = W.tm; B.motion = Rm.models; }   // k_nee_shade wrote each shadow ray's time beside it
 				if (const int rc = intersect_device(c, sc, B); rc != PTX_OK) return rc;
 				rays += got[1];
 				const NeeHits SH{B.distance, B.surface, B.triangle, B.b1, B.b2};
@@ -1103,6 +1164,7 @@ int ptx_render_adaptive(ptx_scene* sc, const ptx_render_cfg* cfg, const ptx_adap
 	// every refusal below is decided before any device work
 	uint32_t x0, y0, w, h, step;
 	if (const int rc = adaptive_args("ptx_render_adaptive", sc, cfg, acfg, accum_a, accum_b, x0, y0, w, h, step); rc != PTX_OK) return rc;
+	if (motion_active(sc)) return refuse_motion("ptx_render_adaptive");
 	if (cfg->shard_count > 1 && !sc->ctx) return set_err(PTX_ERR_UNSUPPORTED, no_exchange("ptx_render_adaptive"));
 	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_render_adaptive: scene was created without a GPU context (no CPU path exists)");
 	const bool dev = is_device_ptr(accum_a);

@@ -611,6 +611,75 @@ DEV bool scene_traverse(const DevScene& S, const Geoms& g, V3 o, V3 d, SceneHit&
 	return best.surface >= 0;
 }
 
+// ------------------------------------------------------------------------------------ a time per ray
+// The local ray of a lane's own time u in the ray space of model `m` (include/ptx.h: MOTION). A static model: scene_traverse's arithmetic
+// on the scalar-loaded SpaceRec, nothing interpolated. A moving one: the lane blends the model's two keys, derives the records with the
+// function apply_model_xforms uses (flat_scene.hpp: derive_xform) and keeps basis(u) for the local -> world distance. The models of a
+// space share both keys (assign_ray_spaces), so whichever model a lane meets the space with gives the same ray. Mo.moved[m] is
+// wave-uniform: so is the branch.
+struct LaneSpace {
+	V3 lo, ld, inv;
+	bool moved;
+	float basis[9];   // basis(u) of a moving space; not written for a static one
+};
+DEV void lane_space(const DevScene& S, const DevMotion& Mo, int m, uint32_t spc, V3 o, V3 d, float u, LaneSpace& L) {
+	L.moved = Mo.moved[m] != 0u;
+	if (L.moved) {
+		float x[12];
+		motion_xform(Mo.begin_xform + 12 * (size_t)m, Mo.end_xform + 12 * (size_t)m, u, x);
+		XformRecs r;
+		derive_xform(x, r);
+		L.lo = mulmv(r.inv_basis, o) + mk(r.inv_origin[0], r.inv_origin[1], r.inv_origin[2]);
+		L.ld = normalize(mulmv(r.inv_basis, d));
+		L.basis[0] = r.basis[0]; L.basis[1] = r.basis[1]; L.basis[2] = r.basis[2]; L.basis[3] = r.basis[3]; L.basis[4] = r.basis[4];
+		L.basis[5] = r.basis[5]; L.basis[6] = r.basis[6]; L.basis[7] = r.basis[7]; L.basis[8] = r.basis[8];
+	} else {
+		const SpaceRec& SP = S.spaces[spc];
+		L.lo = mulmv(SP.inv_basis, o) + mk(SP.inv_origin[0], SP.inv_origin[1], SP.inv_origin[2]);
+		L.ld = normalize(mulmv(SP.inv_basis, d));
+	}
+	L.inv = mk(1.0f / L.ld.x, 1.0f / L.ld.y, 1.0f / L.ld.z);
+}
+// local -> world distance (model.cpp:62-63) with the basis of the lane's time
+DEV float lane_world_distance(const ModelRec& M, const LaneSpace& L, float t) {
+	return L.moved ? length(mulmv(L.basis, L.ld * t)) : length(mulmv(M.basis, L.ld * t));
+}
+
+// scene_traverse with a time per lane: the same model loop, the same walks on the same mesh-local trees
+template <int MODE>
+DEV bool scene_traverse_motion(const DevScene& S, const DevMotion& Mo, const Geoms& g, V3 o, V3 d, float u, SceneHit& best, const Spill& spill) {
+#ifdef PTX_PROF
+	Prof prof{};
+#endif
+	best.dist = -1.0f;
+	best.surface = -1;
+	uint32_t cur_space = 0xFFFFFFFFu;
+	LaneSpace L;
+	L.lo = o; L.ld = d; L.inv = d; L.moved = false;
+	for (int m = 0; m < S.n_models; m++) {
+		const ModelRec& M = S.models[m];
+		const uint32_t spc = S.model_space[m];   // wave-uniform
+		if (spc != cur_space) { lane_space(S, Mo, m, spc, o, d, u, L); cur_space = spc; }
+		float nr, fr;
+		if (!aabb_test_inv(M.bmin, M.bmax, L.lo, L.inv, nr, fr)) continue;
+		MeshHit nearest;
+		nearest.t = -1.0f;
+		int hit_surface = -1;
+		for (int s = 0; s < M.n_surfaces; s++) {
+			MeshHit h;
+			if (!mesh_intersect_m<MODE, 4>(g, S.surfaces[M.first_surface + s], S.surf_aux[M.first_surface + s], L.lo, L.ld, L.inv, h, spill PROF_PASS)) continue;
+			if (h.t < nearest.t || !(nearest.t >= 0)) { nearest = h; hit_surface = M.first_surface + s; }
+		}
+		if (!(nearest.t >= 0)) continue;
+		const float wd = lane_world_distance(M, L, nearest.t);
+		if (!(wd >= 0)) continue;
+		if (wd < best.dist || !(best.dist >= 0)) {
+			best.dist = wd; best.surface = hit_surface; best.tri = nearest.tri; best.b1 = nearest.b1; best.b2 = nearest.b2;
+		}
+	}
+	return best.surface >= 0;
+}
+
 // ------------------------------------------------------------------------------------ deferred models
 // scene_traverse makes the whole wave wait for every model that ANY of its 64 rays enters: on Cornell 9 % / 4 % / 3 % /
 // 1.5 % of the rays enter the two boxes, the light and the sphere, so their triangle loops run with a handful of
@@ -703,7 +772,9 @@ struct Surf { V3 pos, nrm, tan; float u, v; };
 
 // attribute interpolation of renderer::intersect — core/renderer.cpp:688-715. One round of nine 16-byte fetches from the triangle's
 // hit record (flat_scene.hpp: HitRec); the sums are the reference's, term by term.
-DEV void hit_attributes(const DevScene& S, const ShadeRec& R, uint32_t tri_word, float b1, float b2, Surf& out) {
+// (basis, origin, nmat): the local -> world transform and normal matrix of the surface's model: its shade record's, or under motion those of
+// the lane's own time (hit_attributes_at's other callers)
+DEV void hit_attributes_at(const DevScene& S, const float* basis, const float* origin, const float* nmat, uint32_t tri_word, float b1, float b2, Surf& out) {
 	const float b0 = 1 - b1 - b2;
 	// the record: from LDS when the triangle is one of the hot ones (DevScene::hot_lds: nine LDS reads instead of a round of nine global
 	// gathers — on Cornell the 170 largest triangles take nearly all hits), else from global memory
@@ -721,11 +792,14 @@ DEV void hit_attributes(const DevScene& S, const ShadeRec& R, uint32_t tri_word,
 		A = H[0]; B = H[1]; C = H[2]; a0 = H[3]; e0 = H[4]; c0 = H[5]; a1 = H[6]; e1 = H[7]; c1 = H[8];
 	}
 	V3 lp = mk(A.x, A.y, A.z) * b0 + mk(B.x, B.y, B.z) * b1 + mk(C.x, C.y, C.z) * b2;
-	out.pos = mulmv(R.basis, lp) + mk(R.origin[0], R.origin[1], R.origin[2]);
+	out.pos = mulmv(basis, lp) + mk(origin[0], origin[1], origin[2]);
 	out.u = A.w * b0 + B.w * b1 + C.w * b2;
 	out.v = a0.w * b0 + e0.w * b1 + c0.w * b2;
-	out.nrm = normalize(mulmv(R.nmat, mk(a0.x, a0.y, a0.z) * b0 + mk(e0.x, e0.y, e0.z) * b1 + mk(c0.x, c0.y, c0.z) * b2));
-	out.tan = normalize(mulmv(R.nmat, mk(a1.x, a1.y, a1.z) * b0 + mk(e1.x, e1.y, e1.z) * b1 + mk(c1.x, c1.y, c1.z) * b2));
+	out.nrm = normalize(mulmv(nmat, mk(a0.x, a0.y, a0.z) * b0 + mk(e0.x, e0.y, e0.z) * b1 + mk(c0.x, c0.y, c0.z) * b2));
+	out.tan = normalize(mulmv(nmat, mk(a1.x, a1.y, a1.z) * b0 + mk(e1.x, e1.y, e1.z) * b1 + mk(c1.x, c1.y, c1.z) * b2));
+}
+DEV void hit_attributes(const DevScene& S, const ShadeRec& R, uint32_t tri_word, float b1, float b2, Surf& out) {
+	hit_attributes_at(S, R.basis, R.origin, R.nmat, tri_word, b1, b2, out);
 }
 
 // intersect_result::get_normal (renderer.cpp:430-435): TBN * material::get_normal(uv); nts = (0,0,1) without a normal map
@@ -907,6 +981,31 @@ DEV V3 camera_ray_origin(const DevScene& S, const RenderParams& P, uint32_t x, u
 		lp = lens_point(S, j.z, j.w);
 	}
 	return mulmv(S.cam.basis, lp) + mk(S.cam.origin[0], S.cam.origin[1], S.cam.origin[2]);
+}
+
+// ------------------------------------------------------------------------------------ the shutter (include/ptx.h: MOTION)
+enum { BLOCK_TIME = 0x300 };   // the Philox block of a sample's time: blocks 0 .. 34, 0x100 .. and 0x200 .. are taken
+// u of (pixel, sample): a function of the seed, the pixel and the sample alone, so every kernel that meets the sample's path computes the same
+DEV float sample_time(const RenderParams& P, const RenderMotion& Mo, uint32_t pixel, uint32_t sample) {
+	const float r = draws(P, pixel, sample, 0, 0, BLOCK_TIME).x;
+	return Mo.shutter_open + (Mo.shutter_close - Mo.shutter_open) * r;
+}
+// the scene with its camera at time u: origin and basis blended between the two keys, everything else (yfov, the lens) the current camera's
+DEV void camera_at(DevScene& S, const RenderMotion& Mo, float u) {
+	float cur[12], x[12];
+	cur[0] = S.cam.origin[0]; cur[1] = S.cam.origin[1]; cur[2] = S.cam.origin[2];
+	cur[3] = S.cam.basis[0]; cur[4] = S.cam.basis[1]; cur[5] = S.cam.basis[2]; cur[6] = S.cam.basis[3]; cur[7] = S.cam.basis[4];
+	cur[8] = S.cam.basis[5]; cur[9] = S.cam.basis[6]; cur[10] = S.cam.basis[7]; cur[11] = S.cam.basis[8];
+	motion_xform(Mo.cam_begin, cur, u, x);
+	S.cam.origin[0] = x[0]; S.cam.origin[1] = x[1]; S.cam.origin[2] = x[2];
+	S.cam.basis[0] = x[3]; S.cam.basis[1] = x[4]; S.cam.basis[2] = x[5]; S.cam.basis[3] = x[6]; S.cam.basis[4] = x[7];
+	S.cam.basis[5] = x[8]; S.cam.basis[6] = x[9]; S.cam.basis[7] = x[10]; S.cam.basis[8] = x[11];
+}
+// the records of model `m` at time u (the model moves: the caller has looked at Mo.moved[m])
+DEV void model_records_at(const DevMotion& Mo, uint32_t m, float u, XformRecs& r) {
+	float x[12];
+	motion_xform(Mo.begin_xform + 12 * (size_t)m, Mo.end_xform + 12 * (size_t)m, u, x);
+	derive_xform(x, r);
 }
 
 // ------------------------------------------------------------------------------------ textures
@@ -1263,6 +1362,43 @@ DEV void write_hit_outputs(const DevScene& S, const ShadeRec* shade, const Inter
 		V3 sn = {0, 0, 0};
 		if (hit) {
 			const ShadeRec& R = shade[h.surface];
+			hit_attributes(S, R, h.tri, h.b1, h.b2, sf);
+			sn = shading_normal(sf, material_eval<true>(S, R.mat, sf.u, sf.v).normal_ts);
+		}
+		if (A.px) { A.px[i] = sf.pos.x; A.py[i] = sf.pos.y; A.pz[i] = sf.pos.z; }
+		if (A.nx) { A.nx[i] = sn.x; A.ny[i] = sn.y; A.nz[i] = sn.z; }
+		if (A.u) { A.u[i] = sf.u; A.v[i] = sf.v; }
+	}
+}
+// The shade record of surface `surface` at the lane's time u: the scene's own for a static model, read without arithmetic; for a moving
+// one basis(u), origin(u) and nmat(u) from the shared derivation in the record's place (the material does not move)
+DEV ShadeRec shade_record_at(const DevScene& S, const ShadeRec* shade, const DevMotion& Mo, int surface, float u) {
+	ShadeRec R = shade[surface];
+	const uint32_t m = S.surfaces[surface].model;
+	if (Mo.moved[m] != 0u) {
+		float x[12];
+		motion_xform(Mo.begin_xform + 12 * (size_t)m, Mo.end_xform + 12 * (size_t)m, u, x);
+		XformRecs r;
+		derive_xform(x, r);
+		R.origin[0] = r.origin[0]; R.origin[1] = r.origin[1]; R.origin[2] = r.origin[2];
+		R.basis[0] = r.basis[0]; R.basis[1] = r.basis[1]; R.basis[2] = r.basis[2]; R.basis[3] = r.basis[3]; R.basis[4] = r.basis[4];
+		R.basis[5] = r.basis[5]; R.basis[6] = r.basis[6]; R.basis[7] = r.basis[7]; R.basis[8] = r.basis[8];
+		R.nmat[0] = r.nmat[0]; R.nmat[1] = r.nmat[1]; R.nmat[2] = r.nmat[2]; R.nmat[3] = r.nmat[3]; R.nmat[4] = r.nmat[4];
+		R.nmat[5] = r.nmat[5]; R.nmat[6] = r.nmat[6]; R.nmat[7] = r.nmat[7]; R.nmat[8] = r.nmat[8];
+	}
+	return R;
+}
+// write_hit_outputs for a ray of time u (A.time): position and normals of a moving model's surface are those of its transform at u
+DEV void write_hit_outputs_motion(const DevScene& S, const ShadeRec* shade, const IntersectArgs& A, size_t i, bool hit, const SceneHit& h, float u) {
+	A.distance[i] = hit ? h.dist : -1.0f;
+	A.surface[i] = hit ? h.surface : -1;
+	A.triangle[i] = hit ? (int32_t)((h.tri & S.tri_id_mask) - S.surfaces[h.surface].tri_base) : -1;
+	A.b0[i] = hit ? 1 - h.b1 - h.b2 : 0.f; A.b1[i] = hit ? h.b1 : 0.f; A.b2[i] = hit ? h.b2 : 0.f;
+	if (A.px || A.nx || A.u) {
+		Surf sf = {};
+		V3 sn = {0, 0, 0};
+		if (hit) {
+			const ShadeRec R = shade_record_at(S, shade, A.motion, h.surface, u);
 			hit_attributes(S, R, h.tri, h.b1, h.b2, sf);
 			sn = shading_normal(sf, material_eval<true>(S, R.mat, sf.u, sf.v).normal_ts);
 		}

@@ -128,6 +128,51 @@ PTX_HD inline float fresnel_f0sq(float ior) {
 	return f0;
 }
 
+// ---- what a model's transform determines: the five groups of floats of ModelRec / SpaceRec / ShadeRec. One definition for both sides,
+// as rough_consts is: apply_model_xforms calls it per model, and under motion (include/ptx.h: MOTION) a lane calls it on the transform
+// of its own time. IEEE binary32, one rounding per operation, in the reference's order (transform::inverse, transform.cpp:33-36; mat3
+// inverse, mat3.inl:245-263; rows dotted with v, mat3.inl:219-224), so both sides hold the same bits. Written without loops or indexed
+// temporaries: on the device every value stays in a register.
+struct XformRecs {
+	float basis[9], origin[3];       // the transform itself: columns of the basis, origin
+	float inv_basis[9], inv_origin[3];
+	float nmat[9];                   // transpose(inverse(basis)), columns
+};
+PTX_HD inline void mat_inverse_hd(const float* m, float* out) {
+	const float xx = m[0], xy = m[1], xz = m[2], yx = m[3], yy = m[4], yz = m[5], zx = m[6], zy = m[7], zz = m[8];
+	const float det1 = +(yy * zz - zy * yz);
+	const float det2 = -(xy * zz - zy * xz);
+	const float det3 = +(xy * yz - yy * xz);
+	const float det = xx * det1 + yx * det2 + zx * det3;
+	const float s = 1 / det;
+	out[0] = det1 * s; out[1] = det2 * s; out[2] = det3 * s;
+	out[3] = (-(yx * zz - zx * yz)) * s; out[4] = (+(xx * zz - zx * xz)) * s; out[5] = (-(xx * yz - yx * xz)) * s;
+	out[6] = (+(yx * zy - zx * yy)) * s; out[7] = (-(xx * zy - zx * xy)) * s; out[8] = (+(xx * yy - yx * xy)) * s;
+}
+// x: [12] origin, basis columns (PTX_ARR_MODEL_XFORM's layout)
+PTX_HD inline void derive_xform(const float* x, XformRecs& r) {
+	r.origin[0] = x[0]; r.origin[1] = x[1]; r.origin[2] = x[2];
+	r.basis[0] = x[3]; r.basis[1] = x[4]; r.basis[2] = x[5]; r.basis[3] = x[6]; r.basis[4] = x[7]; r.basis[5] = x[8];
+	r.basis[6] = x[9]; r.basis[7] = x[10]; r.basis[8] = x[11];
+	mat_inverse_hd(r.basis, r.inv_basis);
+	const float n0 = -x[0], n1 = -x[1], n2 = -x[2];
+	const float* m = r.inv_basis;
+	r.inv_origin[0] = m[0] * n0 + m[3] * n1 + m[6] * n2;
+	r.inv_origin[1] = m[1] * n0 + m[4] * n1 + m[7] * n2;
+	r.inv_origin[2] = m[2] * n0 + m[5] * n1 + m[8] * n2;
+	// column k of the transpose is row k of the inverse
+	r.nmat[0] = m[0]; r.nmat[1] = m[3]; r.nmat[2] = m[6];
+	r.nmat[3] = m[1]; r.nmat[4] = m[4]; r.nmat[5] = m[7];
+	r.nmat[6] = m[2]; r.nmat[7] = m[5]; r.nmat[8] = m[8];
+}
+// The state of a moving transform (or camera) at time u: x(u)[k] = a[k] + (b[k] - a[k]) * u, a the begin and b the current value
+PTX_HD inline float motion_mix(float a, float b, float u) { return a + (b - a) * u; }
+PTX_HD inline void motion_xform(const float* a, const float* b, float u, float* x) {
+	x[0] = motion_mix(a[0], b[0], u); x[1] = motion_mix(a[1], b[1], u); x[2] = motion_mix(a[2], b[2], u); x[3] = motion_mix(a[3], b[3], u);
+	x[4] = motion_mix(a[4], b[4], u); x[5] = motion_mix(a[5], b[5], u); x[6] = motion_mix(a[6], b[6], u); x[7] = motion_mix(a[7], b[7], u);
+	x[8] = motion_mix(a[8], b[8], u); x[9] = motion_mix(a[9], b[9], u); x[10] = motion_mix(a[10], b[10], u); x[11] = motion_mix(a[11], b[11], u);
+}
+
 // ---- material factors (core/material.hpp:11-17) and texture slots ----
 struct MaterialRec {
 	float albedo[3]; float opacity;
@@ -206,6 +251,17 @@ struct FlatScene {
 	std::vector<HitRec> hot_hitrec;      // the hit records kept in LDS beside the resident geometry (largest triangles first; upload_scene)
 	CameraRec camera{};
 	SunRec sun{};
+	// ptx_scene_set_motion (include/ptx.h: MOTION): the state at u = 0; the scene's own camera and transforms are the state at u = 1.
+	// `set`: a call is in force (the inspection arrays are non-empty); active(): some model or the camera moves.
+	struct Motion {
+		bool set = false, camera_moved = false;
+		std::vector<float> begin_xform;    // [n][12]; a static model's entry is a bitwise copy of its current transform
+		std::vector<uint32_t> moved;       // [n] 1: the begin transform differs bitwise from the current one
+		float begin_camera[12] = {};       // origin, basis; the current camera's when it does not move
+		float shutter_open = 0, shutter_close = 1;
+		bool any_model() const { for (uint32_t m : moved) if (m) return true; return false; }
+		bool active() const { return set && (camera_moved || any_model()); }
+	} motion;
 	uint32_t kd_max_depth = 0;
 	bool any_texture = false;
 	bool any_alpha = false;              // some material can take the opacity / shadow-catcher pass-through branch
@@ -242,6 +298,10 @@ void finalize_scene(FlatScene& s, const float* camera13, const float* sun13);
 // The transform-dependent tail of finalize_scene, from s.model_xform: model records (inverse and normal matrices, boxes), the distinct ray
 // spaces, and the shade records. Builds no tree; ptx_scene_set_model_xforms reruns it on a finished scene.
 void apply_model_xforms(FlatScene& s);
+// The distinct ray spaces (s.spaces, s.model_space) from the model records. Models share one when their inverse transforms are bitwise
+// equal and neither moves (s.motion); two moving models only when their begin and their current transforms are bitwise equal as well; a
+// moving model never shares one with a static model. Without motion: the spaces apply_model_xforms has always made.
+void assign_ray_spaces(FlatScene& s);
 // The aperture table of a camera with a lens (include/ptx.h: THE APERTURE TABLE): blades + 1 corners (x, y), float64 arithmetic, stored as
 // float32, the last entry a bitwise copy of the first. Empty when lens_radius == 0.
 std::vector<float> lens_table(const CameraRec& cam);

@@ -110,6 +110,26 @@ struct PassBuffers {
 	unsigned long long* ray_counter;  // accumulates
 };
 
+// The motion table of a scene (ptx_scene_set_motion; one buffer the scene owns): the two keys of every model and which models move. A
+// kernel argument of its own for the kernels that know time; DevScene does not carry it.
+struct DevMotion {
+	const float* begin_xform;   // [n_models][12] the state at u = 0 (origin, basis columns: PTX_ARR_MODEL_XFORM's layout)
+	const float* end_xform;     // [n_models][12] the state at u = 1: the scene's current transforms
+	const uint32_t* moved;      // [n_models] non-zero: the keys differ bitwise; the records of a model with 0 are the scene's own
+};
+
+// What the unfused integrators' kernels take about the scene's motion (k_nee_generate, k_nee_shade, k_aov_generate, k_aov_shade): a kernel
+// argument of its own, as NeePunctual and AovMotion are. active == 0: no statement of motion runs (a wave-uniform test of this argument).
+struct RenderMotion {
+	DevMotion models;                     // read only where models_moved != 0
+	float cam_begin[12];                  // the begin camera's origin and basis; read only where camera_moved != 0
+	uint32_t active, camera_moved, models_moved;
+	float shutter_open, shutter_close;
+};
+// time[i] = the time of the sample with id id[i] (id == nullptr: entry i is sample i): the times of a round's path stream, in stream order,
+// as intersect_device's timed batch takes them (motion.hip)
+hipError_t launch_motion_times(const RenderParams& P, const RenderMotion& Mo, const uint32_t* id, uint32_t n, float* time, hipStream_t stream);
+
 struct IntersectArgs {
 	const float *ox, *oy, *oz, *dx, *dy, *dz;
 	size_t n;
@@ -117,6 +137,8 @@ struct IntersectArgs {
 	float *b0, *b1, *b2;
 	float *px, *py, *pz, *nx, *ny, *nz, *u, *v;  // optional groups (nullptr = skip)
 	uint2* spill;                                // [grid * waves per block][kSpillWords]
+	const float* time;                           // nullptr: the scene at u = 1, the kernels that know no time; else [n] each ray's u (the motion kernels)
+	DevMotion motion;                            // read only where time != nullptr
 };
 
 // Workspace of the queue-based pipeline (wavefront.hip). A PAIR is (ray, surface whose box it enters). Pair space is a POOL sized from
@@ -176,6 +198,8 @@ hipError_t launch_resolve_halves(const float4* sample_rad, float4* accum_a, floa
 hipError_t launch_resolve_claim(const float4* sample_rad, float4* pixel_rgba, uint8_t* claimed, const uint32_t* pixels, uint32_t n_pixels, uint32_t pass_spp,
                                 uint32_t sample0 /* global index of the pass's first sample */, hipStream_t stream);
 hipError_t launch_intersect(const DevScene& S, const IntersectArgs& A, int mode, size_t lds_bytes, int grid, hipStream_t stream);
+// the same batch with a time per ray (A.time and A.motion set; motion.hip): k_intersect_batch_motion
+hipError_t launch_intersect_motion(const DevScene& S, const IntersectArgs& A, int mode, size_t lds_bytes, int grid, hipStream_t stream);
 hipError_t launch_pbr_eval(const float* in, float* out, size_t n, hipStream_t stream);
 constexpr uint32_t kLeafBatchMaxTris = 256;   // k_leaf_intersect: triangles of its one leaf at most (48 bytes each in LDS)
 // `spill`: [grid * 4 waves][kSpillWords]; grid workgroups of 256 threads
@@ -201,12 +225,13 @@ struct AovHits {   // what the intersect launch wrote for the round's rays
 	const int32_t *surface, *triangle;   // -1 = miss; triangle index within the surface's mesh
 	const float *b1, *b2;
 };
-hipError_t launch_aov_generate(const DevScene& S, const RenderParams& P, const AovStream& out, uint32_t n, hipStream_t stream);
+hipError_t launch_aov_generate(const DevScene& S, const RenderParams& P, const AovStream& out, uint32_t n, const RenderMotion& Rm, hipStream_t stream);
 // rec: [2][rec_stride] per-sample records of the pass, indexed by sample id: (albedo, 1) and (shading normal, depth); zeros for a sample that
 // ends on a miss. *n_out (device, zeroed before the launch) receives the number of entries appended to `out`; untouched when the scene has
 // no pass-through material (DevScene::any_alpha == 0)
+// Rm: the scene's motion (active == 0: none); the guide kernels alone take it: ptx_render_motion and ptx_render_emission refuse active motion
 hipError_t launch_aov_shade(const DevScene& S, const RenderParams& P, const AovStream& in, const AovHits& H, uint32_t n, const AovStream& out, uint32_t* n_out,
-                            float4* rec, size_t rec_stride, hipStream_t stream);
+                            float4* rec, size_t rec_stride, const RenderMotion& Rm, hipStream_t stream);
 // ptx_render_motion: the previous frame as k_aov_motion_shade takes it. The camera travels in the kernel argument; the transforms live in
 // context workspace.
 struct AovMotion {
@@ -247,6 +272,7 @@ struct NeeShadow {
 	float *lx, *ly, *lz;                  // [cap] by path: radiance the light sample adds when visible
 	uint32_t *sun_pos, *light_pos;        // [cap] by path: the ray's position in the shadow stream (< 2^31), or kNeeNone
 	uint32_t *exp_surf, *exp_tri;         // [cap] by path: the sampled triangle (surface, local triangle)
+	float* tm;                            // [2 cap] the time of each shadow ray, beside it; written and read under active motion only (else nullptr)
 };
 struct NeeLights {   // the scene's light list (ptx_api.cpp: build_lights); n == 0: no light samples, every emission weight is 1
 	const uint2* tris;           // [n] (surface, local triangle), ordered by surface, then triangle
@@ -272,12 +298,12 @@ struct NeePunctual {
 };
 constexpr uint32_t kNeePunctualRay = 0xFFFFFFFEu;   // exp_surf of a punctual sample's shadow ray: exp_tri holds the bits of dist, and the sample is visible iff the ray hits nothing nearer than dist
 // cnt (device, 8 words): [0] entries appended to `out`, [1] shadow rays of the round, [2..3] light samples (64-bit), [4..5] visible ones
-hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, hipStream_t stream);
+hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, const RenderMotion& Mo, hipStream_t stream);
 // sampler_pdf: the variants of PTX_NEE_SAMPLER_PDF (nee_core.hpp: sampler_pdf in pe's place in the weights)
 // candidates: M of PTX_NEE_CANDIDATES, 1 .. 16; above 1 the RIS variants run (nee_core.hpp: the candidate loop of nee_vertex)
 // Pn.n != 0: the PUN variants run (part 1 of nee.hip), and launch_nee_settle is told so: its punctual form knows kNeePunctualRay
 hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
-                            const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
+                            const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, hipStream_t stream);
 hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, bool punctual, hipStream_t stream);
 
 // The same estimator in one launch per pass (nee_fused.hip, PTX_NEE_FUSED): persistent workgroups as launch_render_pass sizes them, a lane per path,

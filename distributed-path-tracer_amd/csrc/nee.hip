@@ -28,11 +28,13 @@ constexpr uint32_t kNeeShadePartShift = 6, kNeeShadePartMask = (1u << kNeeShadeP
 static_assert(NEE_PUN == 1u << kNeeShadePartShift, "the two parts are split by PUN");
 
 #if PTX_NEE_PART == 0
-__global__ void __launch_bounds__(kNeeBlock) k_nee_generate(DevScene S, RenderParams P, NeeStream out, float4* __restrict__ L, uint32_t n) {
+__global__ void __launch_bounds__(kNeeBlock) k_nee_generate(DevScene S0, RenderParams P, NeeStream out, float4* __restrict__ L, uint32_t n, RenderMotion Mo) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
 	if (i >= n) return;
 	uint32_t px, py, sample;
 	nee_sample_of(P, i, px, py, sample);
+	DevScene S = S0;
+	if (Mo.camera_moved) camera_at(S, Mo, sample_time(P, Mo, py * P.W + px, sample));   // the camera of the sample's own time (wave-uniform test)
 	V3 o, d;
 	camera_ray(S, P, px, py, sample, o, d);
 	out.ox[i] = o.x; out.oy[i] = o.y; out.oz[i] = o.z;
@@ -62,9 +64,10 @@ DEV void nee_append2(bool first, bool second, uint32_t* counter, uint32_t& pos_f
 // V: the variant (nee_core.hpp has the bits). Ev is read by the ENV variants alone, ris_m by the RIS variants, Pn by the PUN variants.
 template <uint32_t V>
 __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParams P, NeeLights Lt, NeeStream in, NeeHits H, uint32_t n, NeeStream out, NeeShadow W,
-                                                         uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeeEnv Ev, uint32_t ris_m, NeePunctual Pn) {
+                                                         uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeeEnv Ev, uint32_t ris_m, NeePunctual Pn, RenderMotion Mo) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
 	NeeVertex v;
+	float u = 0;   // the path's time; computed under active motion alone
 	V3 o = {0, 0, 0}, d = {0, 0, 1}, T = {1, 1, 1};
 	float p_prev = 0;
 	uint32_t id = 0, depth = 0, pass = 0;
@@ -80,7 +83,18 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 		const uint32_t pixel = py * P.W + px;
 		const float4 l4 = Lrec[id];
 		V3 L = mk(l4.x, l4.y, l4.z);
-		if (nee_vertex<V>(S, P, Lt, Ev, ris_m, pixel, sample, H.surface[i], (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v, Pn))
+		const int32_t surf = H.surface[i];
+		bool moved = false;
+		XformRecs Xm;
+		if (Mo.active) {   // wave-uniform: a kernel argument
+			u = sample_time(P, Mo, pixel, sample);
+			if (Mo.models_moved && surf >= 0) {
+				const uint32_t m = S.surfaces[surf].model;
+				moved = Mo.models.moved[m] != 0u;
+				if (moved) model_records_at(Mo.models, m, u, Xm);   // the hit surface's records at the path's time
+			}
+		}
+		if (nee_vertex<V>(S, P, Lt, Ev, ris_m, pixel, sample, surf, (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v, Pn, moved, Xm))
 			Lrec[id] = make_float4(L.x, L.y, L.z, l4.w);
 	}
 	// shadow rays of the round: at most two per path, so every position is below twice the round's paths
@@ -90,12 +104,14 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 		W.ox[sp] = v.sun_o.x; W.oy[sp] = v.sun_o.y; W.oz[sp] = v.sun_o.z;
 		W.dx[sp] = v.sun_d.x; W.dy[sp] = v.sun_d.y; W.dz[sp] = v.sun_d.z;
 		W.sx[i] = v.sun_x.x; W.sy[i] = v.sun_x.y; W.sz[i] = v.sun_x.z;
+		if (Mo.active) W.tm[sp] = u;   // every ray of the sample's path carries its time
 	}
 	if (v.want_light) {
 		W.ox[lp] = v.lo.x; W.oy[lp] = v.lo.y; W.oz[lp] = v.lo.z;
 		W.dx[lp] = v.ld.x; W.dy[lp] = v.ld.y; W.dz[lp] = v.ld.z;
 		W.lx[i] = v.lx.x; W.ly[i] = v.lx.y; W.lz[i] = v.lx.z;
 		W.exp_surf[i] = v.exp_surf; W.exp_tri[i] = v.exp_tri;
+		if (Mo.active) W.tm[lp] = u;
 	}
 	if (i < n) {
 		W.sun_pos[i] = v.want_sun ? (sp | (v.catcher_req ? kNeeCatcher : 0u)) : kNeeNone;
@@ -159,8 +175,8 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_settle(NeeStream in, uint32_t
 
 // ------------------------------------------------------------------------------------ launchers
 #if PTX_NEE_PART == 0
-hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, hipStream_t stream) {
-	hipLaunchKernelGGL(k_nee_generate, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, S, P, out, L, n);
+hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, const RenderMotion& Mo, hipStream_t stream) {
+	hipLaunchKernelGGL(k_nee_generate, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, S, P, out, L, n, Mo);
 	return hipGetLastError();
 }
 #endif
@@ -183,26 +199,26 @@ static NeeShadeTable nee_shade_table(std::index_sequence<I...>) {
 // (nee_fused.hip has the reason): the linker puts the two together.
 template <uint32_t PART>
 hipError_t launch_nee_shade_part(uint32_t V, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeStream& in, const NeeHits& H,
-                                 uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream);
+                                 uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, hipStream_t stream);
 template <>
 hipError_t launch_nee_shade_part<PTX_NEE_PART>(uint32_t V, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeStream& in,
-                                               const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
+                                               const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, hipStream_t stream) {
 	static const NeeShadeTable table = nee_shade_table(std::make_index_sequence<kNeeVariantCount>{});
 	const NeeShadeKernel kernel = table.fn[V & kNeeShadePartMask];
 	if (!kernel) return hipErrorInvalidValue;
-	hipLaunchKernelGGL(kernel, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m, Pn);
+	hipLaunchKernelGGL(kernel, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m, Pn, Mo);
 	return hipGetLastError();
 }
 
 #if PTX_NEE_PART == 0
 // the variant: nee_select_variant (nee_core.hpp), as for launch_nee_fused
 hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
-                            const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, hipStream_t stream) {
+                            const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, hipStream_t stream) {
 	uint32_t V, ris_m;
 	const hipError_t e = nee_select_variant(S, Ev, Pn, sampler_pdf, candidates, V, ris_m);
 	if (e != hipSuccess) return e;
 	const auto part = (V >> kNeeShadePartShift) ? launch_nee_shade_part<1> : launch_nee_shade_part<0>;
-	return part(V, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L, stream);
+	return part(V, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L, Mo, stream);
 }
 
 hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, bool punctual, hipStream_t stream) {

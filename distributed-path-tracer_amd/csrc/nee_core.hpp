@@ -285,7 +285,8 @@ DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights
 // weight. Without PUN, Pn is not read and no statement changes.
 template <uint32_t V>
 DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, uint32_t pixel, uint32_t sample, int32_t surf, uint32_t tri, float b1, float b2,
-                    float hit_dist, V3& o, V3& d, V3& T, V3& L, float& p_prev, uint32_t& depth, uint32_t& pass, NeeVertex& out, const NeePunctual& Pn = NeePunctual{}) {
+                    float hit_dist, V3& o, V3& d, V3& T, V3& L, float& p_prev, uint32_t& depth, uint32_t& pass, NeeVertex& out, const NeePunctual& Pn = NeePunctual{},
+                    bool moved = false, const XformRecs& Xm = XformRecs{}) {
 	constexpr bool TEX = (V & NEE_TEX) != 0, ALPHA = (V & NEE_ALPHA) != 0, SUN = (V & NEE_SUN) != 0, ENV = (V & NEE_ENV) != 0;
 	constexpr bool SPDF = (V & NEE_SPDF) != 0, RIS = (V & NEE_RIS) != 0, PUN = (V & NEE_PUN) != 0;
 	bool& alive = out.alive;
@@ -320,7 +321,9 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 		}
 		const ShadeRec& R = S.shade[surf];
 		Surf sf;
-		hit_attributes(S, R, tri + S.surfaces[surf].tri_base, b1, b2, sf);
+		// moved (the unfused kernels under active motion alone): the hit surface's model moves, and Xm holds its records at the path's time
+		if (moved) hit_attributes_at(S, Xm.basis, Xm.origin, Xm.nmat, tri + S.surfaces[surf].tri_base, b1, b2, sf);
+		else hit_attributes(S, R, tri + S.surfaces[surf].tri_base, b1, b2, sf);
 		const MaterialRec& mt = R.mat;
 		const MatEval me = material_eval<TEX>(S, mt, sf.u, sf.v);
 		float roughness = me.roughness;

@@ -258,7 +258,7 @@ int upload_scene(ptx_scene* sc) {
 void release_scene_buffers(ptx_scene* sc) {
 	for (DevBuf* b : {&sc->d_models, &sc->d_surfaces, &sc->d_materials, &sc->d_nodes, &sc->d_refs, &sc->d_tris, &sc->d_shade, &sc->d_tex,
 	                  &sc->d_texels, &sc->d_texels_f, &sc->d_lut, &sc->d_spaces, &sc->d_model_space, &sc->d_surf_aux, &sc->d_wf_order, &sc->d_res_nodes, &sc->d_res_refs, &sc->d_res_tris, &sc->d_hot,
-	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell, &sc->d_punctual, &sc->d_punctual_cdf, &sc->d_lens})
+	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell, &sc->d_punctual, &sc->d_punctual_cdf, &sc->d_lens, &sc->d_motion})
 		b->release();
 	sc->lights.on_device = false;
 	sc->env_table.on_device = false;
@@ -279,7 +279,61 @@ int finish_scene(ptx_ctx* ctx, ptx_scene* sc, ptx_scene** out) {
 	return PTX_OK;
 }
 
+// The ray spaces and the motion table of the scene's motion state, in stream order into buffers the scene owns: what ptx_scene_set_motion
+// and the calls that end a motion change on the device. No tree, no triangle, no shade record goes up.
+int upload_motion(ptx_scene* sc) {
+	ptx_ctx* c = sc->ctx;
+	HIP_TRY(hipSetDevice(c->device));
+	const FlatScene& h = sc->host;
+	HIP_TRY(hipStreamSynchronize(c->stream));   // a buffer that grows is freed: nothing queued may still read it
+	auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
+		hipError_t e = b.ensure(std::max<size_t>(bytes, 16));
+		if (e != hipSuccess) return e;
+		return bytes ? hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+	};
+	HIP_TRY(up(sc->d_spaces, h.spaces.data(), h.spaces.size() * sizeof(SpaceRec)));
+	HIP_TRY(up(sc->d_model_space, h.model_space.data(), h.model_space.size() * 4));
+	sc->dev_motion = DevMotion{};
+	std::vector<float> table;
+	if (h.motion.set && h.motion.any_model()) {
+		const size_t n = h.models.size();
+		table.resize(25 * n);
+		memcpy(table.data(), h.motion.begin_xform.data(), 48 * n);
+		memcpy(table.data() + 12 * n, h.model_xform.data(), 48 * n);
+		memcpy(table.data() + 24 * n, h.motion.moved.data(), 4 * n);
+		HIP_TRY(up(sc->d_motion, table.data(), table.size() * 4));
+		const float* base = (const float*)sc->d_motion.p;
+		sc->dev_motion = DevMotion{base, base + 12 * n, (const uint32_t*)(base + 24 * n)};
+	}
+	HIP_TRY(hipStreamSynchronize(c->stream));   // `table` is a local
+	sc->dev.spaces = (const SpaceRec*)sc->d_spaces.p;
+	sc->dev.model_space = (const uint32_t*)sc->d_model_space.p;
+	sc->dev.n_spaces = (uint32_t)h.spaces.size();
+	return PTX_OK;
+}
+
+// Ends the scene's motion: the inspection arrays are empty again, the ray spaces are the static scene's, and the light list (which left
+// out the moving models) is dropped. The caller holds the context's mutex on a scene with one. -> whether ray spaces changed.
+bool drop_motion(ptx_scene* sc) {
+	FlatScene& h = sc->host;
+	if (!h.motion.set) return false;
+	const bool had_models = h.motion.any_model();
+	h.motion = FlatScene::Motion{};
+	sc->dev_motion = DevMotion{};
+	if (!had_models) return false;
+	assign_ray_spaces(h);
+	std::lock_guard<std::mutex> tl(sc->lights_mu);
+	sc->lights = ptx_scene::LightList{};
+	return true;
+}
+
 }  // namespace
+
+int refuse_motion(const char* who) {
+	return set_err(PTX_ERR_UNSUPPORTED, std::string(who) + ": the scene's motion is active (ptx_scene_set_motion) and this call knows no time per sample: it would render the "
+	                                    "scene at u = 1 only. Render the blurred frame with ptx_render_nee (PTX_NEE_NO_LIGHT_SAMPLES gives this estimator) and its guides "
+	                                    "with ptx_render_aov, or clear the motion (ptx_scene_set_motion(scene, NULL)) to render the scene as it stands");
+}
 
 // The emissive triangles ptx_render_nee samples (include/ptx.h: the listing rules). World corners, areas and normals in float64 in the
 // written order, stored as float32.
@@ -296,6 +350,7 @@ const ptx_scene::LightList* build_lights(ptx_scene* sc) {
 		const MaterialRec& m = h.materials[s];
 		if (!(m.emissive[0] > 0 || m.emissive[1] > 0 || m.emissive[2] > 0)) continue;
 		if (m.tex[2] >= 0 || !(m.opacity == 1.0f || std::fabs(m.opacity - 1.0f) < 0.0001f) || m.shadow_catcher) continue;   // can pass a sample through
+		if (h.motion.set && h.motion.moved[h.surfaces[s].model]) continue;   // a moving model's emitter: unlisted, emission weight 1, no light samples
 		const float* X = h.model_xform.data() + 12 * (size_t)h.surfaces[s].model;
 		const int32_t* rg = h.surf_range.data() + 8 * s;
 		for (int32_t t = 0; t < rg[3]; t++) {
@@ -627,6 +682,7 @@ int ptx_scene_set_camera(ptx_scene* sc, const ptx_camera* cam) {
 	}
 	sc->host.camera = next;
 	if (sc->ctx) sc->dev.cam = next;   // a kernel argument: the next launch takes it
+	if (drop_motion(sc) && sc->ctx) return upload_motion(sc);   // the camera's begin key no longer belongs to it: the motion ends (MOTION)
 	return PTX_OK;
 }
 
@@ -655,12 +711,92 @@ int ptx_scene_set_model_xforms(ptx_scene* sc, const float* model_xform, uint32_t
 	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);
 	FlatScene& h = sc->host;
 	h.model_xform.assign(model_xform, model_xform + (size_t)n_models * 12);
+	h.motion = FlatScene::Motion{};   // the begin keys no longer belong to these transforms: the motion ends (MOTION)
+	sc->dev_motion = DevMotion{};
 	apply_model_xforms(h);   // model, space and shade records; no tree is built
 	{   // world normals and areas of the emissive triangles moved with the models: the list is rebuilt at the next request
 		std::lock_guard<std::mutex> tl(sc->lights_mu);
 		sc->lights = ptx_scene::LightList{};
 	}
 	if (sc->ctx) return upload_scene(sc);   // every record goes up again, in stream order, into the buffers the scene already owns
+	return PTX_OK;
+}
+
+int ptx_scene_set_motion(ptx_scene* sc, const ptx_motion* m) {
+	// every refusal is decided before the scene is touched
+	auto bad = [](const char* msg) { return set_err(PTX_ERR_INVALID, std::string("ptx_scene_set_motion: ") + msg); };
+	if (!sc) return bad("NULL scene");
+	const size_t n = sc->host.model_xform.size() / 12;
+	if (m) {
+		if (m->begin_model_xform && (size_t)m->n_models != n) return bad("n_models differs from the scene's");
+		if (m->begin_model_xform)
+			for (size_t k = 0; k < 12 * n; k++)
+				if (!std::isfinite(m->begin_model_xform[k])) return bad("a begin transform value is not finite");
+		if (const ptx_camera* cam = m->begin_camera) {   // what ptx_scene_set_camera refuses of origin, basis and yfov; the lens fields are ignored
+			for (int k = 0; k < 3; k++) if (!std::isfinite(cam->origin[k])) return bad("begin camera: origin is not finite");
+			for (int k = 0; k < 9; k++) if (!std::isfinite(cam->basis[k])) return bad("begin camera: basis is not finite");
+			if (!std::isfinite(cam->yfov) || !(cam->yfov > 0) || !((double)cam->yfov < 3.14159265358979323846)) return bad("begin camera: yfov must lie in (0, pi)");
+		}
+		if (!(m->shutter_open >= 0.0f) || !(m->shutter_open <= m->shutter_close) || !(m->shutter_close <= 1.0f))
+			return bad("the shutter must satisfy 0 <= open <= close <= 1");
+	}
+	std::unique_lock<std::mutex> lk;
+	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);   // no render of this scene is being queued
+	FlatScene& h = sc->host;
+	const bool had_models = h.motion.set && h.motion.any_model();
+	FlatScene::Motion next;
+	if (m) {
+		next.set = true;
+		next.begin_xform = h.model_xform;   // a static model's begin key is its current transform, bit for bit
+		next.moved.assign(n, 0u);
+		if (m->begin_model_xform)
+			for (size_t k = 0; k < n; k++)
+				if (memcmp(m->begin_model_xform + 12 * k, h.model_xform.data() + 12 * k, 48)) {
+					next.moved[k] = 1u;
+					memcpy(next.begin_xform.data() + 12 * k, m->begin_model_xform + 12 * k, 48);
+				}
+		memcpy(next.begin_camera, h.camera.origin, 12);
+		memcpy(next.begin_camera + 3, h.camera.basis, 36);
+		if (m->begin_camera && (memcmp(m->begin_camera->origin, h.camera.origin, 12) || memcmp(m->begin_camera->basis, h.camera.basis, 36))) {
+			next.camera_moved = true;
+			memcpy(next.begin_camera, m->begin_camera->origin, 12);
+			memcpy(next.begin_camera + 3, m->begin_camera->basis, 36);
+		}
+		next.shutter_open = m->shutter_open;
+		next.shutter_close = m->shutter_close;
+	}
+	h.motion = std::move(next);
+	if (had_models || h.motion.any_model()) {   // which models may share a ray space, and which emitters are listed, depend on who moves
+		assign_ray_spaces(h);
+		{
+			std::lock_guard<std::mutex> tl(sc->lights_mu);
+			sc->lights = ptx_scene::LightList{};
+		}
+		if (sc->ctx) return upload_motion(sc);
+	}
+	return PTX_OK;
+}
+
+int ptx_scene_motion_state(const ptx_scene* sc, float u, float* model_xform, float* camera) {
+	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_scene_motion_state: NULL scene");
+	if (!std::isfinite(u)) return set_err(PTX_ERR_INVALID, "ptx_scene_motion_state: u is not finite");
+	std::unique_lock<std::mutex> lk;
+	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);
+	const FlatScene& h = sc->host;
+	const FlatScene::Motion& mo = h.motion;
+	const size_t n = h.model_xform.size() / 12;
+	if (model_xform)
+		for (size_t k = 0; k < n; k++) {
+			if (mo.set && mo.moved[k]) motion_xform(mo.begin_xform.data() + 12 * k, h.model_xform.data() + 12 * k, u, model_xform + 12 * k);
+			else memcpy(model_xform + 12 * k, h.model_xform.data() + 12 * k, 48);   // static: read without arithmetic
+		}
+	if (camera) {
+		float cur[12];
+		memcpy(cur, h.camera.origin, 12);
+		memcpy(cur + 3, h.camera.basis, 36);
+		if (mo.set && mo.camera_moved) motion_xform(mo.begin_camera, cur, u, camera);
+		else memcpy(camera, cur, 48);
+	}
 	return PTX_OK;
 }
 
@@ -811,6 +947,15 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 			float f; memcpy(&f, &w, 4); tmp.push_back(f);
 		}
 		src = tmp.data(); bytes = tmp.size() * 4; break;
+	case PTX_ARR_MOTION_XFORM: if (h.motion.set) { src = h.motion.begin_xform.data(); bytes = h.motion.begin_xform.size() * 4; } break;
+	case PTX_ARR_MOTION_MOVED: if (h.motion.set) { src = h.motion.moved.data(); bytes = h.motion.moved.size() * 4; } break;
+	case PTX_ARR_MOTION_CAMERA:
+		if (h.motion.set) {
+			tmp.assign(h.motion.begin_camera, h.motion.begin_camera + 12);
+			tmp.push_back(h.motion.camera_moved ? 1.0f : 0.0f); tmp.push_back(h.motion.shutter_open); tmp.push_back(h.motion.shutter_close);
+			src = tmp.data(); bytes = tmp.size() * 4;
+		}
+		break;
 	case PTX_ARR_SURF_AUX: src = h.surf_aux.data(); bytes = h.surf_aux.size() * sizeof(UnitAux); break;
 	case PTX_ARR_RES_PLAN: {
 		const uint32_t w[4] = {(uint32_t)h.res_bytes, h.n_resident, (uint32_t)sc->lds_bytes, (uint32_t)h.hot_hitrec.size()};

@@ -48,22 +48,7 @@ inline float box_area(const Box& b) {
 	return (wx * wy + wy * wz + wx * wz) * 2;
 }
 
-// ---- 3x3 helpers on column-major float[9] = {x.x,x.y,x.z, y.x,...} ----
-inline void mat_inverse(const float* m, float* out) {
-	const float xx = m[0], xy = m[1], xz = m[2], yx = m[3], yy = m[4], yz = m[5], zx = m[6], zy = m[7], zz = m[8];
-	float det1 = +(yy * zz - zy * yz);
-	float det2 = -(xy * zz - zy * xz);
-	float det3 = +(xy * yz - yy * xz);
-	float det = xx * det1 + yx * det2 + zx * det3;
-	float s = 1 / det;
-	float r[9] = {det1, det2, det3,
-	              -(yx * zz - zx * yz), +(xx * zz - zx * xz), -(xx * yz - yx * xz),
-	              +(yx * zy - zx * yy), -(xx * zy - zx * xy), +(xx * yy - yx * xy)};
-	for (int k = 0; k < 9; k++) out[k] = r[k] * s;
-}
-inline void mat_mul_vec(const float* m, const float* v, float* out) {  // rows dotted with v (mat3.inl:219-224)
-	for (int r = 0; r < 3; r++) out[r] = m[r] * v[0] + m[3 + r] * v[1] + m[6 + r] * v[2];
-}
+// (the 3x3 inverse and the matrix-vector product of the model records live in flat_scene.hpp: derive_xform, shared with the kernels)
 
 // ---- SAH builder -------------------------------------------------------------------------------
 struct BuildNode {
@@ -365,20 +350,43 @@ void finalize_scene(FlatScene& s, const float* cam, const float* sun) {
 	}
 }
 
+void assign_ray_spaces(FlatScene& s) {
+	const size_t n_models = s.models.size();
+	const FlatScene::Motion& mo = s.motion;
+	auto moved = [&](size_t mi) { return mo.set && mi < mo.moved.size() && mo.moved[mi] != 0; };
+	s.spaces.clear();
+	s.model_space.assign(n_models, 0);
+	std::vector<size_t> owner;   // the first model of each space
+	for (size_t mi = 0; mi < n_models; mi++) {
+		SpaceRec sp;
+		memcpy(sp.inv_basis, s.models[mi].inv_basis, 36);
+		memcpy(sp.inv_origin, s.models[mi].inv_origin, 12);
+		size_t k = 0;
+		for (; k < s.spaces.size(); k++) {
+			if (memcmp(&s.spaces[k], &sp, sizeof sp)) continue;
+			const size_t o = owner[k];
+			if (!moved(mi) && !moved(o)) break;
+			// a lane derives a moving space's local ray from the two keys of the model it meets the space with: both keys must be shared
+			if (moved(mi) && moved(o) && !memcmp(&s.model_xform[12 * mi], &s.model_xform[12 * o], 48) && !memcmp(&mo.begin_xform[12 * mi], &mo.begin_xform[12 * o], 48)) break;
+		}
+		if (k == s.spaces.size()) { s.spaces.push_back(sp); owner.push_back(mi); }
+		s.model_space[mi] = (uint32_t)k;
+	}
+}
+
 void apply_model_xforms(FlatScene& s) {
 	const size_t n_models = s.model_surf.size() / 2;
 	const size_t n_surf = s.surf_range.size() / 8;
 	for (size_t mi = 0; mi < n_models; mi++) {
 		ModelRec& mr = s.models[mi];
 		const float* x = &s.model_xform[12 * mi];
-		memcpy(mr.origin, x, 12);
-		memcpy(mr.basis, x + 3, 36);
-		mat_inverse(mr.basis, mr.inv_basis);
-		const float neg[3] = {-x[0], -x[1], -x[2]};
-		mat_mul_vec(mr.inv_basis, neg, mr.inv_origin);
-		// normal matrix = transpose(inverse(basis)): column k of the transpose is row k of the inverse
-		for (int c = 0; c < 3; c++)
-			for (int r = 0; r < 3; r++) mr.nmat[3 * c + r] = mr.inv_basis[3 * r + c];
+		XformRecs xr;   // inverse, inv_origin = inv_basis * (-origin), normal matrix = transpose(inverse(basis)): the shared derivation
+		derive_xform(x, xr);
+		memcpy(mr.origin, xr.origin, 12);
+		memcpy(mr.basis, xr.basis, 36);
+		memcpy(mr.inv_basis, xr.inv_basis, 36);
+		memcpy(mr.inv_origin, xr.inv_origin, 12);
+		memcpy(mr.nmat, xr.nmat, 36);
 		mr.first_surface = s.model_surf[2 * mi];
 		mr.n_surfaces = s.model_surf[2 * mi + 1];
 		for (int32_t k = 0; k < mr.n_surfaces; k++) s.surfaces[mr.first_surface + k].model = (uint32_t)mi;
@@ -399,18 +407,7 @@ void apply_model_xforms(FlatScene& s) {
 		memcpy(mr.pbmin, pbx.lo, 12);
 		memcpy(mr.pbmax, pbx.hi, 12);
 	}
-	// distinct ray spaces (bitwise-equal inverse transforms)
-	s.spaces.clear();
-	s.model_space.assign(n_models, 0);
-	for (size_t mi = 0; mi < n_models; mi++) {
-		SpaceRec sp;
-		memcpy(sp.inv_basis, s.models[mi].inv_basis, 36);
-		memcpy(sp.inv_origin, s.models[mi].inv_origin, 12);
-		size_t k = 0;
-		for (; k < s.spaces.size(); k++) if (!memcmp(&s.spaces[k], &sp, sizeof sp)) break;
-		if (k == s.spaces.size()) s.spaces.push_back(sp);
-		s.model_space[mi] = (uint32_t)k;
-	}
+	assign_ray_spaces(s);
 	s.shade.assign(n_surf, ShadeRec{});
 	for (size_t mi = 0; mi < n_models; mi++)
 		for (int32_t k = 0; k < s.models[mi].n_surfaces; k++) {

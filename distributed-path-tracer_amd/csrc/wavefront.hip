@@ -68,6 +68,23 @@ struct SoaRays {
 	DEV uint32_t count(uint32_t m) const { return m; }
 	DEV bool valid(uint32_t, uint32_t) const { return true; }
 	DEV void load(uint32_t i, uint32_t, V3& o, V3& d) const { o = mk(ox[i], oy[i], oz[i]); d = mk(dx[i], dy[i], dz[i]); }
+	DEV float time(uint32_t) const { return 0.f; }   // no time: the scene as it stands
+	DEV void space(const DevScene& S, int, uint32_t spc, V3 o, V3 d, float, V3& lo, V3& ld, V3& inv) const { to_space(S.spaces[spc], o, d, lo, ld, inv); }
+};
+// the rays of a timed batch (IntersectArgs::time): ray i has time u[i], and its local ray in a moving space is the lane's own
+// (device_core.hpp: lane_space, what scene_traverse_motion computes)
+struct TimedSoaRays {
+	const float *ox, *oy, *oz, *dx, *dy, *dz, *u;
+	DevMotion motion;
+	DEV uint32_t count(uint32_t m) const { return m; }
+	DEV bool valid(uint32_t, uint32_t) const { return true; }
+	DEV void load(uint32_t i, uint32_t, V3& o, V3& d) const { o = mk(ox[i], oy[i], oz[i]); d = mk(dx[i], dy[i], dz[i]); }
+	DEV float time(uint32_t i) const { return u[i]; }
+	DEV void space(const DevScene& S, int m, uint32_t spc, V3 o, V3 d, float t, V3& lo, V3& ld, V3& inv) const {
+		LaneSpace L;
+		lane_space(S, motion, m, spc, o, d, t, L);
+		lo = L.lo; ld = L.ld; inv = L.inv;
+	}
 };
 
 // One tile = 1024 consecutive rays, one ray per lane: local ray per model space, model box, surface boxes (scene::model::intersect,
@@ -94,6 +111,7 @@ __global__ void __launch_bounds__(kWfClassifyBlock) k_wf_classify(DevScene S0, S
 		const bool active = i < n && src.valid(i, m_in);
 		V3 o = {0, 0, 0}, d = {0, 0, 1};
 		if (active) src.load(i, m_in, o, d);
+		const float ray_time = active ? src.time(i) : 0.f;
 
 		// pass 1: the surfaces this ray enters (bit u of `mine`), and per surface the number of rays of this wave that enter it (lane u of `cnt`)
 		unsigned long long mine = 0;
@@ -104,7 +122,7 @@ __global__ void __launch_bounds__(kWfClassifyBlock) k_wf_classify(DevScene S0, S
 			for (int m = 0; m < S.n_models; m++) {
 				const ModelRec& M = S.models[m];
 				const uint32_t spc = S.model_space[m];
-				if (spc != cur_space) { to_space(S.spaces[spc], o, d, lo, ld, inv); cur_space = spc; }
+				if (spc != cur_space) { src.space(S, m, spc, o, d, ray_time, lo, ld, inv); cur_space = spc; }
 				float nr, fr;
 				const bool enters = active && aabb_test_box(M.box, lo, inv, nr, fr);   // model box first (model.cpp:38-40)
 				if (__ballot(enters) == 0) continue;
@@ -183,7 +201,7 @@ __global__ void __launch_bounds__(kWfClassifyBlock) k_wf_classify(DevScene S0, S
 				const unsigned long long range = (M.n_surfaces >= 64 ? ~0ull : ((1ull << M.n_surfaces) - 1ull)) << M.first_surface;
 				if (__ballot((mine & range) != 0) == 0) continue;
 				const uint32_t spc = S.model_space[m];
-				if (spc != cur_space) { to_space(S.spaces[spc], o, d, lo, ld, inv); cur_space = spc; }
+				if (spc != cur_space) { src.space(S, m, spc, o, d, ray_time, lo, ld, inv); cur_space = spc; }
 				for (int k = 0; k < M.n_surfaces; k++) {
 					const int u = M.first_surface + k;
 					const bool bit = (mine >> u) & 1ull;
@@ -532,6 +550,60 @@ __global__ void __launch_bounds__(kWfBlock) k_wf_merge_batch(DevScene S0, Inters
 	write_hit_outputs(S, S.shade, A, gi, hit, h);
 }
 
+// wf_closest for a ray of time u: the local direction and the local -> world distance of a moving model are the lane's own (lane_space)
+DEV bool wf_closest_motion(const DevScene& S, const DevMotion& Mo, const WfBuffers& W, const PairPre& q, V3 o, V3 d, float u, SceneHit& best) {
+	best.dist = -1.0f;
+	best.surface = -1;
+	best.tri = 0; best.b1 = 0; best.b2 = 0;
+	const unsigned long long mine = q.mask;
+	uint32_t p = 0;
+	uint32_t cur_space = 0xFFFFFFFFu;
+	LaneSpace L;
+	L.lo = o; L.ld = d; L.inv = d; L.moved = false;
+	for (int m = 0; m < S.n_models; m++) {
+		const ModelRec& M = S.models[m];
+		const unsigned long long range = (M.n_surfaces >= 64 ? ~0ull : ((1ull << M.n_surfaces) - 1ull)) << M.first_surface;
+		unsigned long long bits = mine & range;
+		if (__ballot(bits != 0) == 0) continue;
+		const uint32_t spc = S.model_space[m];
+		if (spc != cur_space) { lane_space(S, Mo, m, spc, o, d, u, L); cur_space = spc; }
+		MeshHit nearest;
+		nearest.t = -1.0f; nearest.b1 = 0; nearest.b2 = 0; nearest.tri = 0;
+		int hit_surface = -1;
+		while (bits) {
+			const int s = __builtin_ctzll(bits);
+			bits &= bits - 1ull;
+			const float4 h = wf_pre_get(W, q, p++);
+			if (!(h.x >= 0)) continue;   // this surface reported no hit
+			if (h.x < nearest.t || !(nearest.t >= 0)) { nearest.t = h.x; nearest.tri = __float_as_uint(h.y); nearest.b1 = h.z; nearest.b2 = h.w; hit_surface = s; }
+		}
+		if (!(nearest.t >= 0)) continue;
+		const float wd = lane_world_distance(M, L, nearest.t);
+		if (!(wd >= 0)) continue;
+		if (wd < best.dist || !(best.dist >= 0)) { best.dist = wd; best.surface = hit_surface; best.tri = nearest.tri; best.b1 = nearest.b1; best.b2 = nearest.b2; }
+	}
+	return best.surface >= 0;
+}
+
+// k_wf_merge_batch for a timed batch (A.time, A.motion)
+__global__ void __launch_bounds__(kWfBlock) k_wf_merge_batch_motion(DevScene S0, IntersectArgs A, size_t first_ray, uint32_t n, WfBuffers W, const ModelRec* __restrict__ t_models,
+                                                                   const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces,
+                                                                   const uint32_t* __restrict__ t_model_space) {
+	DevScene S = S0;
+	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;
+	if (W.ctl[1]) return;   // the slice overflowed the pool and is repeated smaller (k_wf_merge_batch)
+	const uint32_t i = blockIdx.x * kWfBlock + threadIdx.x;
+	if (i >= n) return;
+	const size_t gi = first_ray + i;
+	const V3 o = mk(A.ox[gi], A.oy[gi], A.oz[gi]), d = mk(A.dx[gi], A.dy[gi], A.dz[gi]);
+	const float u = A.time[gi];
+	PairPre q;
+	wf_pre_head(W, i, q);
+	wf_pre_results(W, q);
+	SceneHit h;
+	const bool hit = wf_closest_motion(S, A.motion, W, q, o, d, u, h);
+	write_hit_outputs_motion(S, S.shade, A, gi, hit, h, u);
+}
 
 // ------------------------------------------------------------------------------------ integrator on queues
 // The path stream of a render slab: SoA of float4, the fused kernel's stream entry plus flags in the id word, and the entry's shadow
@@ -556,6 +628,8 @@ struct StreamRays {
 		if (t < n_in) { const float4 a = q[t], b = q[cap + t]; o = mk(a.x, a.y, a.z); d = mk(b.x, b.y, b.z); }
 		else { const uint32_t i = t - n_in; const float4 a = r[i], b = r[cap + i]; o = mk(a.x, a.y, a.z); d = mk(b.x, b.y, b.z); }
 	}
+	DEV float time(uint32_t) const { return 0.f; }
+	DEV void space(const DevScene& S, int, uint32_t spc, V3 o, V3 d, float, V3& lo, V3& ld, V3& inv) const { to_space(S.spaces[spc], o, d, lo, ld, inv); }
 };
 
 // camera paths [first, first + n) of the pass -> stream entries 0 .. n-1 (scene::camera::get_ray; renderer.cpp:359-370)
@@ -705,6 +779,16 @@ static void launch_traverse(const DevScene& S, const WfBuffers& W, int n_cu, hip
 
 // One slice of a batch: W.ctl must be zeroed, W.n_in == nullptr (the slice's ray count is known to the host)
 hipError_t launch_wf_intersect(const DevScene& S, const IntersectArgs& A, size_t first_ray, uint32_t n, const WfBuffers& W, int n_cu, hipStream_t stream) {
+	if (A.time) {   // a timed batch: the timed ray source and the motion merge; k_wf_traverse2 works on local rays and is the same
+		if (!A.motion.begin_xform || !A.motion.end_xform || !A.motion.moved) return hipErrorInvalidValue;
+		const TimedSoaRays tsrc{A.ox + first_ray, A.oy + first_ray, A.oz + first_ray, A.dx + first_ray, A.dy + first_ray, A.dz + first_ray, A.time + first_ray, A.motion};
+		const int t_tiles = (int)((n + kWfTile - 1) / kWfTile);
+		hipLaunchKernelGGL(k_wf_classify<TimedSoaRays>, dim3(t_tiles < wf_classify_grid(n_cu) ? t_tiles : wf_classify_grid(n_cu)), dim3(kWfClassifyBlock), 0, stream, S, tsrc, n, W, S.models,
+		                   S.surfaces, S.spaces, S.model_space);
+		launch_traverse(S, W, n_cu, stream);
+		hipLaunchKernelGGL(k_wf_merge_batch_motion, dim3((n + kWfBlock - 1) / kWfBlock), dim3(kWfBlock), 0, stream, S, A, first_ray, n, W, S.models, S.surfaces, S.spaces, S.model_space);
+		return hipGetLastError();
+	}
 	const SoaRays src{A.ox + first_ray, A.oy + first_ray, A.oz + first_ray, A.dx + first_ray, A.dy + first_ray, A.dz + first_ray};
 	const int tiles = (int)((n + kWfTile - 1) / kWfTile);
 	hipLaunchKernelGGL(k_wf_classify<SoaRays>, dim3(tiles < wf_classify_grid(n_cu) ? tiles : wf_classify_grid(n_cu)), dim3(kWfClassifyBlock), 0, stream, S, src, n, W, S.models, S.surfaces, S.spaces, S.model_space);

@@ -596,3 +596,102 @@ def corner_cluster_rays(n: int, ratio: float, size: float, scale: float, count: 
     d = (tgt - org).astype(np.float32)
     d /= np.linalg.norm(d, axis=1, keepdims=True).astype(np.float32)
     return np.concatenate([org, d], 1).astype(np.float32)
+
+
+def _box(half):
+    """Axis-aligned box of half-extents `half` ([3] or a scalar) around the origin: 24 vertices (flat normals), 12 triangles, outward."""
+    h = np.broadcast_to(np.asarray(half, np.float64), (3,))
+    v, t = [], []
+    for axis in range(3):
+        for sign in (-1.0, 1.0):
+            a, b = (axis + 1) % 3, (axis + 2) % 3
+            n = np.zeros(3); n[axis] = sign
+            ta = np.zeros(3); ta[a] = 1.0
+            base = len(v)
+            for k, (sa, sb) in enumerate(((-1, -1), (1, -1), (1, 1), (-1, 1))):
+                p = np.zeros(3)
+                p[axis], p[a], p[b] = sign * h[axis], sa * h[a], sb * h[b]
+                v.append(np.concatenate([p, [(sa + 1) / 2, (sb + 1) / 2], n, ta]))
+            t += [[base, base + 1, base + 2], [base, base + 2, base + 3]] if sign > 0 else [[base, base + 2, base + 1], [base, base + 3, base + 2]]
+    return np.array(v, np.float32), np.array(t, np.uint32)
+
+
+def _xform(origin, rot_y_deg=0.0, scale=1.0):
+    """[12] float32: origin, basis columns of scale * R_y(angle)."""
+    a = np.deg2rad(rot_y_deg)
+    c, s = np.cos(a), np.sin(a)
+    basis = scale * np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]], np.float64)   # rows; columns are the images of x, y, z
+    return np.concatenate([np.asarray(origin, np.float64), basis.T.ravel()]).astype(np.float32)
+
+
+def movers_scene(emissive_mover: bool = False, sun: bool = False, alpha: bool = False):
+    """The motion-blur test scene: few surfaces and a few hundred triangles, so that every intersect route takes it. Static floor and static
+    emissive quad; a translating box; an icosphere(2) that rotates 20 degrees about y and scales 1 -> 1.2; a two-surface model that moves;
+    two boxes whose current transforms are bitwise equal and whose begin transforms differ; two boxes equal in both keys; with
+    `emissive_mover` one emissive box that moves. `sun` adds a directional light, `alpha` makes the second surface of the two-surface model
+    half-transparent. -> the arrays of plaza_scene plus begin_model_xform [n,12] (the state at u = 0; model_xform is the state at u = 1) and
+    begin_camera [13] (camera is the state at u = 1): keys a few degrees and a few centimetres apart."""
+    ident = _xform([0, 0, 0])
+    meshes, models = [], []   # (vertices, triangles, material) ; (first surface, count, begin xform, current xform)
+
+    def add(parts, begin, cur):
+        models.append((len(meshes), len(parts), np.asarray(begin, np.float32), np.asarray(cur, np.float32)))
+        meshes.extend(parts)
+
+    def mat(albedo, rough=0.6, metal=0.0, emissive=(0, 0, 0), opacity=1.0):
+        return np.array(list(albedo) + [opacity, rough, metal] + list(emissive) + [1.33, 0.0], np.float32)
+
+    fv, ft = _quad(0.0, 4.0)
+    add([(fv, ft, mat((0.7, 0.7, 0.7)))], ident, ident)                                            # 0 static floor
+    lv, lt = _quad(0.0, 0.6)
+    lamp = np.array([0.2, 2.6, 0.1, 1, 0, 0, 0, -1, 0, 0, 0, -1], np.float32)                      # half-turn about x: the quad faces down (-0.0 entries stay)
+    lamp[[4, 5, 6, 8, 9, 10]] = [0.0, 0.0, -0.0, -0.0, 0.0, -0.0]
+    add([(lv, lt, mat((0.8, 0.8, 0.8), emissive=(1.7, 1.5, 1.2)))], lamp, lamp)                    # 1 static emissive quad
+    bv, bt = _box(0.4)
+    add([(bv, bt, mat((0.8, 0.3, 0.25)))], _xform([-1.5, 0.4, 0.0]), _xform([-1.1, 0.4, 0.3]))     # 2 translating box
+    sv, st = icosphere(2)
+    s11 = np.zeros((len(sv), 11), np.float32)
+    s11[:, 0:3] = sv
+    s11[:, 3] = np.arctan2(sv[:, 2], sv[:, 0]) / (2 * np.pi) + 0.5
+    s11[:, 4] = np.arcsin(np.clip(sv[:, 1], -1, 1)) / np.pi + 0.5
+    s11[:, 5:8] = sv
+    tan = np.cross(np.where(np.abs(sv[:, 1:2]) < 0.99, [[0.0, 1.0, 0.0]], [[1.0, 0.0, 0.0]]), sv)
+    s11[:, 8:11] = tan / np.linalg.norm(tan, axis=1, keepdims=True)
+    add([(s11, st.astype(np.uint32), mat((0.3, 0.5, 0.85), rough=0.3, metal=0.6))],
+        _xform([0.2, 0.6, -0.5], 0.0, 0.5), _xform([0.2, 0.6, -0.5], 20.0, 0.6))                   # 3 rotating, growing sphere
+    tv, tt = _box([0.3, 0.2, 0.3])
+    qv, qt = _quad(0.45, 0.35)
+    add([(tv, tt, mat((0.35, 0.75, 0.4))), (qv, qt, mat((0.9, 0.85, 0.3), opacity=0.5 if alpha else 1.0))],
+        _xform([1.2, 0.2, -0.9], -6.0), _xform([1.35, 0.25, -0.8], 4.0))                           # 4 two-surface model that moves
+    av, at = _box(0.3)
+    cv, ct = _box([0.2, 0.45, 0.2])
+    meet = _xform([1.3, 0.45, 0.8], 10.0)
+    add([(av, at, mat((0.75, 0.6, 0.3)))], _xform([1.0, 0.45, 0.6], 0.0), meet)                     # 5, 6 meet at u = 1 from different begin states
+    add([(cv, ct, mat((0.3, 0.6, 0.75)))], _xform([1.5, 0.6, 1.1], 25.0), meet)
+    dv, dt = _box([0.25, 0.25, 0.25])
+    ev, et = _box([0.15, 0.4, 0.15])
+    pair_a, pair_b = _xform([-0.9, 0.4, 1.2], -8.0), _xform([-0.7, 0.4, 1.35], 5.0)
+    add([(dv, dt, mat((0.6, 0.3, 0.7)))], pair_a, pair_b)                                           # 7, 8 equal in both keys: one moving ray space
+    add([(ev, et, mat((0.7, 0.7, 0.3)))], pair_a, pair_b)
+    if emissive_mover:
+        gv, gt = _box(0.2)
+        add([(gv, gt, mat((0.8, 0.8, 0.8), emissive=(0.9, 1.1, 1.4)))], _xform([-0.3, 1.5, 0.9]), _xform([0.0, 1.6, 0.8], 12.0))   # 9 moving emitter
+    verts, tris, sr, mats = [], [], [], []
+    nv = nt = 0
+    for v, t, m in meshes:
+        sr.append([nv, len(v), nt, len(t)])
+        verts.append(v); tris.append(t); mats.append(m)
+        nv += len(v); nt += len(t)
+    cam_end = np.concatenate([_look_at([0.3, 2.1, 5.2], [0.1, 0.6, 0.0]), [np.float32(0.75)]]).astype(np.float32)
+    cam_begin = np.concatenate([_look_at([0.22, 2.13, 5.25], [0.0, 0.62, 0.0]), [np.float32(0.75)]]).astype(np.float32)
+    sun13 = None
+    if sun:
+        d = np.array([0.4, 0.75, 0.5])
+        d /= np.linalg.norm(d)
+        x = np.cross([0, 1, 0], d)
+        x /= np.linalg.norm(x)
+        sun13 = np.concatenate([x, np.cross(d, x), d, [2.5, 2.3, 2.0], [0.004732]]).astype(np.float32)
+    return dict(model_xform=np.stack([m[3] for m in models]), begin_model_xform=np.stack([m[2] for m in models]),
+                model_surf=np.array([[m[0], m[1]] for m in models], np.int32), surf_range=np.array(sr, np.int32),
+                vertices=np.concatenate(verts).astype(np.float32), triangles=np.concatenate(tris).astype(np.uint32),
+                materials=np.stack(mats), camera=cam_end, begin_camera=cam_begin, sun=sun13)

@@ -160,6 +160,70 @@ int ptx_scene_get_camera(const ptx_scene* scene, ptx_camera* camera);
  * NULL argument, n_models different from the scene's, and a non-finite value; decided before the scene is touched. */
 int ptx_scene_set_model_xforms(ptx_scene* scene, const float* model_xform /* [n_models][12], host */, uint32_t n_models);
 
+/* MOTION: a shutter over moving models and a moving camera. The scene as it stands (its current camera and current transforms) is the
+ * state at u = 1; `m` gives the state at u = 0, in the shape of ptx_motion_prev on purpose: a frame loop hands the same previous-frame
+ * arrays to both calls. m == NULL clears the motion.
+ *
+ * WHICH MODELS MOVE. A model whose 12 begin floats are bitwise equal to its current ones is static, and so is a camera whose begin origin
+ * and basis are bitwise equal to the current ones (the begin camera's yfov and lens fields are ignored; the current camera's hold).
+ * Nothing is ever interpolated for a static model or camera. If no model and no camera moves the motion is INACTIVE: every call runs
+ * exactly as on a scene never given motion, kernels and PTX_NEE_FUSED included.
+ *
+ * LIFETIME. ptx_scene_set_model_xforms and ptx_scene_set_camera clear the motion, so the order within a frame is: the two setters first,
+ * ptx_scene_set_motion last. The call works on host-only scenes. On a scene with a context it uploads one small table (begin and current
+ * transforms, moved flags) and the ray spaces into buffers the scene owns; it drops the light list and builds no tree.
+ *
+ * REFUSALS, all PTX_ERR_INVALID and decided before the scene is touched (a refused call leaves the motion as it was): a NULL scene;
+ * n_models different from the scene's when transforms are given; a non-finite value; a begin camera that ptx_scene_set_camera would refuse
+ * on its origin, basis or yfov; a shutter value that is NaN or outside 0 <= open <= close <= 1.
+ *
+ * THE SPECIFICATION. IEEE binary32, each operation rounded on its own, in the order written.
+ *   Time of a sample:  r = draws(pixel, sample, 0, 0, BLOCK_TIME = 0x300).x;  u = shutter_open + (shutter_close - shutter_open) * r.
+ *     u is a function of (seed, pixel, sample) alone; the camera ray and every ray of the sample's path carry it: continuation,
+ *     pass-through, sun, light and punctual shadow rays.
+ *   State at u:  for a moving model x(u)[k] = a[k] + (b[k] - a[k]) * u for the 12 floats, a the begin and b the current value; the camera's
+ *     origin and basis follow the same formula. The derived records are those of ptx_scene_set_model_xforms, operation for operation:
+ *     inv_basis = inverse(basis) (mat3 inverse: cofactors times 1 / det), inv_origin = inv_basis * (-origin), nmat = the transposed
+ *     inverse. One function computes them on the host and in the kernels. A static model's records are the scene's own, read without
+ *     arithmetic. (x(1) is what the formula gives; it need not be b bit for bit.)
+ *   Consequence, which the tests hold on to: a ray of time u sees, bit for bit, the scene set with ptx_scene_set_model_xforms(x(u)) and no
+ *     motion; and with shutter_open == shutter_close == u every sample has time exactly u.
+ *   A linear blend of two rotations shrinks in between and can be singular (a half-turn at u = 0.5 is). Nothing special is done: the
+ *     frame is what the static scene with that matrix renders. Subdivide large rotations into several frames' keys.
+ *   The light list: a surface of a moving model is not listed. An emitter on a moving model keeps emission weight 1 and receives no light
+ *     samples (the rule for unlisted emitters: nothing is lost or counted twice). Clearing the motion lists it again.
+ *   Ray spaces: two models share a local ray when their current inverse transforms are bitwise equal and neither moves; two moving models
+ *     only when their begin and current transforms are both bitwise equal. Models that meet at u = 1 from different begin states do not.
+ *
+ * INSPECTION. PTX_ARR_MOTION_XFORM, PTX_ARR_MOTION_MOVED, PTX_ARR_MOTION_CAMERA (below); all three are empty when no motion is set.
+ * ptx_scene_motion_state evaluates the state at u with the one function the kernels use: model_xform [n_models][12] and camera [12]
+ * (origin, basis); either may be NULL; works on host-only scenes; PTX_ERR_INVALID for a NULL scene or a non-finite u.
+ *
+ * WHAT RUNS UNDER ACTIVE MOTION.
+ *   ptx_render_nee and ptx_render_adaptive_nee run their unfused form: k_nee_generate computes u, the camera at u and the camera ray;
+ *     every closest-hit and shadow batch of a round carries the times; k_nee_shade takes the hit surface's records at u. PTX_NEE_FUSED is
+ *     ignored exactly as on the queue route (fused_launches == 0), not refused. Tiles, sample ranges, spp_per_pass, shards and the adaptive
+ *     loop compose bit for bit as without motion. With PTX_NEE_NO_LIGHT_SAMPLES this is ptx_render's estimator under the shutter.
+ *   ptx_render_aov: the same camera sample and time, with depth measured from the lens point of the camera at u: the guides of the
+ *     blurred frame, which is what ptx_denoise needs for it.
+ *   ptx_intersect_batch_motion (below ptx_intersect_batch) takes a time per ray on every route.
+ *   Refused with PTX_ERR_UNSUPPORTED before any device work, the message naming ptx_render_nee: ptx_render, ptx_render_transparent,
+ *     ptx_render_adaptive, ptx_render_motion, ptx_render_emission, and every call with PTX_INTEGRATOR_WORKER. The project refuses rather
+ *     than render a frame with an instantaneous shutter where a blurred one was asked for. With inactive or cleared motion all of them run
+ *     as before.
+ *
+ * OUT OF SCOPE: more than two keys and curved paths; vertex animation; motion in the fused kernels (ptx_render, PTX_NEE_FUSED) and in the
+ * worker estimator; light samples towards moving emitters; ptx_render_motion and ptx_render_emission under a shutter, and with them the
+ * temporal filters on blurred frames; stratified time samples; a moving sun, environment or punctual lights. */
+typedef struct ptx_motion {
+	const ptx_camera* begin_camera;    /* NULL: the camera does not move */
+	const float* begin_model_xform;    /* NULL: no model moves; else [n_models][12], host, layout of PTX_ARR_MODEL_XFORM */
+	uint32_t n_models;
+	float shutter_open, shutter_close; /* 0 <= open <= close <= 1 */
+} ptx_motion;
+int ptx_scene_set_motion(ptx_scene* scene, const ptx_motion* m /* NULL clears */);
+int ptx_scene_motion_state(const ptx_scene* scene, float u, float* model_xform /* [n_models][12] or NULL */, float* camera /* [12] or NULL */);
+
 /* Point and spot lights (glTF KHR_lights_punctual; no counterpart in the reference, which reads only the `directional` sun). They are
  * scene state that ptx_render_nee and ptx_render_adaptive_nee sample as a third light-sampling strategy (PUNCTUAL LIGHTS below
  * ptx_render_nee's flags has the estimator); ptx_render, ptx_render_transparent, ptx_render_aov and the PTX_INTEGRATOR_WORKER estimator
@@ -239,8 +303,12 @@ typedef enum ptx_array {
 	PTX_ARR_LENS = 30,        /* float[blades + 1][2]: the aperture table of ptx_scene_set_camera; empty while lens_radius == 0 */
 	PTX_ARR_LDS_SHAPE = 31,   /* uint32[n_surfaces]: the surface records' whole lds_root word: LDS_ROOT's (root in bits 28:0) | leaf-only tree << 30 |
 	                           * complete tree of at most 3 branch levels << 29 (the shape bits: leaf-ordered surfaces only, none with PTX_KD_SHAPES=0) */
-	PTX_ARR_SURF_AUX = 32     /* uint32[n_surfaces][4]: the auxiliary surface records: word 0 = flags, bit 0 = the resident, leaf-ordered tree is a
+	PTX_ARR_SURF_AUX = 32,    /* uint32[n_surfaces][4]: the auxiliary surface records: word 0 = flags, bit 0 = the resident, leaf-ordered tree is a
 	                           * chain: every branch has exactly one child, down to a leaf (none with PTX_KD_SHAPES=0); words 1-3 are padding */
+	/* the motion of ptx_scene_set_motion (host-only scenes too); all three empty when no motion is set */
+	PTX_ARR_MOTION_XFORM = 33, /* float[n_models][12]: the begin transforms; a static model's entry is its current transform */
+	PTX_ARR_MOTION_MOVED = 34, /* uint32[n_models]: 1 = the model moves */
+	PTX_ARR_MOTION_CAMERA = 35 /* float[15]: begin origin, begin basis (the current camera's when it does not move), camera-moved flag, open, close */
 } ptx_array;
 int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, size_t dst_bytes);
 
@@ -927,6 +995,12 @@ typedef struct ptx_hits {
 	float *u, *v;                   /* interpolated tex_coord (may be NULL) */
 } ptx_hits;
 int ptx_intersect_batch(ptx_scene* scene, const ptx_rays* rays, size_t n, const ptx_hits* hits);
+/* The same batch with a time per ray (MOTION above: ptx_scene_set_motion): ray i meets every moving model at its transform x(time[i]), on
+ * the scene's own route (LDS, hybrid, global, queues), and distance, position and normals of a hit on a moving model are those of that
+ * transform. Every output equals, bit for bit, ptx_intersect_batch on the scene set to x(time[i]) with no motion. `time` is host or device
+ * memory as the rays are; values are used as given (the states outside [0, 1] are the formula's). On a scene without a moving model `time`
+ * is ignored and the call is bitwise ptx_intersect_batch. ptx_intersect_batch itself stays the scene at u = 1: the current transforms. */
+int ptx_intersect_batch_motion(ptx_scene* scene, const ptx_rays* rays, const float* time /* [n] */, size_t n, const ptx_hits* hits);
 
 /* Batch form of scene::camera::get_ray(ndc, ratio) (LIB/scene/camera.cpp:10-21): what the integrator kernels compute for every camera
  * sample after the pixel jitter (renderer.cpp:359-370), evaluated by the same device function.

@@ -39,6 +39,13 @@
                                         synchronised calls after a warm-up. Per row: the time, light rays traced per sample, and the mean squared
                                         error of the written bytes against a ref_spp (1024) frame of the SAME call (unfused, M = 1) of another seed:
                                         ptx_render cannot see the lamps. The lines are the first part of profiles/nee_punctual_bench.txt.
+  tools/bench_nee.py --motion [reps] [spp]
+                                        Motion blur (Scene.set_motion): the unfused ptx_render_nee with the motion active against the same call
+                                        without motion, on Cornell with one box moving and on procedural.movers_scene (its camera moving too),
+                                        at 1920 x 1080, 8 bounces, 16 spp, shutter (0, 1): the two calls alternate in one process, `reps` (5)
+                                        synchronised calls each after a warm-up, kept with their smallest and largest; the time ratio, and the
+                                        rays traced. Also the unflagged static call alone, as the control that is compared between commits.
+                                        Also writes the lines to profiles/motion_blur_bench.txt.
 Prints one JSON line per measurement. A scene without listed emitters (atrium) shows the cost of the wavefront form alone.
 """
 import importlib
@@ -336,7 +343,57 @@ def main_punctual(ref_spp, reps, spp):
         s.close()
 
 
+def main_motion(reps, spp):
+    ctx = ptx.Context(0)
+    lines = []
+    movers = proc.movers_scene()
+
+    def cornell():
+        s = ptx.Scene.load_gltf(ctx, CORNELL)
+        begin = s.array(ptx.ARR_MODEL_XFORM).copy()
+        k = 1                                  # Cube.001, one of the two boxes (single surface, not the light)
+        assert s.array(ptx.ARR_MODEL_SURF)[k, 1] == 1 and not s.array(ptx.ARR_MATERIALS)[s.array(ptx.ARR_MODEL_SURF)[k, 0], 6:9].any()
+        begin[k, 0] += 0.3
+        begin[k, 2] -= 0.2
+        return s, begin, None
+
+    def moving():
+        s = ptx.Scene.from_arrays(ctx, *[movers[k] for k in KEYS])
+        return s, movers["begin_model_xform"], (movers["begin_camera"][:3], movers["begin_camera"][3:12], movers["begin_camera"][12])
+    for name, make in (("cornell_one_box", cornell), ("movers", moving)):
+        s, begin, cam = make()
+        times = {"static": [], "motion": []}
+        st = {}
+        for rep in range(reps + 1):
+            for k in ("static", "motion"):     # the two calls alternate; the motion is set and cleared outside the timed region
+                if k == "motion":
+                    s.set_motion(begin, cam, (0.0, 1.0))
+                a = zeros()
+                t0 = time.perf_counter()
+                _, st[k] = s.render_nee(W, H, spp, BOUNCES, accum=a, seed=SEED)
+                ctx.synchronize()
+                dt = time.perf_counter() - t0
+                if k == "motion":
+                    s.clear_motion()
+                if rep:
+                    times[k].append(dt)
+        lines.append(json.dumps(dict(scene=name, W=W, H=H, bounces=BOUNCES, spp=spp, reps=reps, pipeline=ctx.timing()["pipeline"],
+                                     static_s_min=round(min(times["static"]), 4), static_s_max=round(max(times["static"]), 4),
+                                     motion_s_min=round(min(times["motion"]), 4), motion_s_max=round(max(times["motion"]), 4),
+                                     motion_over_static=round(min(times["motion"]) / min(times["static"]), 4),
+                                     static_msamples_s=round(W * H * spp / min(times["static"]) / 1e6, 1), motion_msamples_s=round(W * H * spp / min(times["motion"]) / 1e6, 1),
+                                     static_rays=st["static"]["rays"], motion_rays=st["motion"]["rays"], static_n_lights=st["static"]["n_lights"],
+                                     motion_n_lights=st["motion"]["n_lights"])))
+        print(lines[-1], flush=True)
+        s.close()
+    with open(os.path.join(ROOT, "profiles", "motion_blur_bench.txt"), "w") as f:
+        f.write("tools/bench_nee.py --motion: the unfused ptx_render_nee under active motion against the same call without motion, alternated, MI355X\n" + "\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--motion":
+        main_motion(int(sys.argv[2]) if len(sys.argv) > 2 else 5, int(sys.argv[3]) if len(sys.argv) > 3 else 16)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--punctual":
         main_punctual(int(sys.argv[2]) if len(sys.argv) > 2 else 1024, int(sys.argv[3]) if len(sys.argv) > 3 else 3, int(sys.argv[4]) if len(sys.argv) > 4 else 16)
         sys.exit(0)

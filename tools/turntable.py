@@ -4,9 +4,12 @@ about the vertical axis through its origin (Scene.set_model_xforms). The scene i
 the time of creating the scene, which is what a second view cost before the setters existed.
 
   tools/turntable.py [--scene cornell|jack|atrium|PATH.gltf] [--frames N] [--size WxH] [--spp S] [--bounces B] [--spin MODEL] [--lens R:F[:BLADES[:ROT]]]
-                     [--nee] [--out PREFIX] [--arc DEG] [--temporal [--ref-spp N] [--adaptive MIN:CAP:THRESHOLD [--search] [--unit-normals]] [--split-emission]]
+                     [--nee] [--motion-blur OPEN:CLOSE] [--out PREFIX] [--arc DEG] [--temporal [--ref-spp N] [--adaptive MIN:CAP:THRESHOLD [--search] [--unit-normals]] [--split-emission]]
 --out PREFIX writes PREFIX_000.png ...; without it the frames are rendered and dropped. The last line is one JSON record.
 --arc DEG: the angle the camera covers over the frames (default: the full circle).
+--motion-blur OPEN:CLOSE: every frame after the first is rendered under a shutter (Scene.set_motion after the two setters) with the previous
+frame's camera and transforms as the begin state, by ptx_render_nee's unfused form (the one that carries a time per sample); the time of
+set_motion is printed with the setters'. Not with --temporal: the temporal filters do not take blurred frames.
 --temporal: every frame goes through ptx_denoise_temporal — its two half-frames, its guides, its motion against the previous frame's camera
 and transforms (Scene.render_motion), the history of the frame before. Per frame: the accumulation kernel's and the filter's time, the share
 of pixels that took history, and the mean squared error (after x / (1 + x)) of the unfiltered frame, the ptx_denoise frame and the temporal
@@ -71,6 +74,7 @@ def main():
     ap.add_argument("--spin", type=int, default=-1, metavar="MODEL", help="index of a model to spin (default: none)")
     ap.add_argument("--lens", default=None, metavar="R:F[:BLADES[:ROT]]")
     ap.add_argument("--nee", action="store_true", help="render with ptx_render_nee (fused form)")
+    ap.add_argument("--motion-blur", default=None, metavar="OPEN:CLOSE", help="a shutter over the motion between consecutive frames (ptx_render_nee)")
     ap.add_argument("--out", default=None, metavar="PREFIX")
     ap.add_argument("--arc", type=float, default=360.0, metavar="DEG")
     ap.add_argument("--temporal", action="store_true", help="accumulate over the frames with ptx_denoise_temporal and compare with ptx_denoise")
@@ -119,7 +123,16 @@ def main():
     tflags = (ptx.TEMPORAL_SEARCH_3X3 if a.search else 0) | (ptx.TEMPORAL_UNIT_NORMALS if a.unit_normals else 0)
     if a.split_emission and not a.temporal:
         ap.error("--split-emission goes with --temporal")
-    mean_counts, hist_s, mse_s = [], None, []
+    shutter = None
+    if a.motion_blur:
+        if a.temporal:
+            ap.error("--motion-blur does not go with --temporal")
+        try:
+            shutter = tuple(float(v) for v in a.motion_blur.split(":"))
+            assert len(shutter) == 2
+        except (ValueError, AssertionError):
+            ap.error("--motion-blur OPEN:CLOSE")
+    mean_counts, hist_s, mse_s, motion_ms = [], None, [], []
 
     def split_halves(ha, hb, ng, seed):
         """-> (emission sums of the guides' ng samples, copies of the halves without them)"""
@@ -196,6 +209,18 @@ def main():
                   f"mse unfiltered {mse[-1][0]:.3e}, ptx_denoise {mse[-1][1]:.3e}, temporal {mse[-1][2]:.3e}"
                   + (f"; with the split: ptx_denoise {mse_s[-1][0]:.3e}, temporal {mse_s[-1][1]:.3e}" if a.split_emission else ""))
             acc, acc_spp = out, 1
+        elif shutter:
+            if prev_cam is not None:   # the order within a frame: the two setters first, set_motion last
+                t = time.perf_counter()
+                s.set_motion(prev_xf, prev_cam, shutter)
+                motion_ms.append((time.perf_counter() - t) * 1e3)
+                line += f", set_motion {motion_ms[-1]:7.3f} ms"
+            t = time.perf_counter()
+            acc, _ = s.render_nee(W, H, a.spp, a.bounces)
+            render_ms.append((time.perf_counter() - t) * 1e3)
+            prev_cam, prev_xf = s.camera(), s.array(ptx.ARR_MODEL_XFORM)
+            print(line + f", render {render_ms[-1]:8.2f} ms")
+            acc_spp = a.spp
         else:
             acc, _ = (s.render_nee(W, H, a.spp, a.bounces, flags=ptx.NEE_FUSED) if a.nee else s.render(W, H, a.spp, a.bounces))
             render_ms.append((time.perf_counter() - t) * 1e3)
@@ -208,6 +233,8 @@ def main():
     out = dict(scene=a.scene, frames=a.frames, W=W, H=H, spp=a.spp, create_ms=round(create_ms, 3), set_camera_ms=round(med(cam_ms), 4),
                set_model_xforms_ms=round(med(xf_ms), 3) if xf_ms else None, render_ms=round(med(render_ms), 3),
                set_model_xforms_share_of_create=round(med(xf_ms) / create_ms, 5) if xf_ms else None)
+    if shutter:
+        out.update(motion_blur=dict(shutter=list(shutter), set_motion_ms=round(med(motion_ms), 4) if motion_ms else None))
     if a.temporal:   # medians over the frames that have a history
         m = np.array(mse[1:] or mse)
         out.update(temporal=dict(accumulate_ms=round(med(acc_ms[1:] or acc_ms), 4), filter_ms=round(med(filt_ms), 4), reprojected_share=round(med(share[1:] or share), 4),
