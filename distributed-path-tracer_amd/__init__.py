@@ -165,6 +165,7 @@ NEE_NO_LIGHT_SAMPLES = 1   # ptx_nee_cfg.flags
 NEE_FUSED = 4              # one kernel launch per pass where render() runs the fused kernel; ignored on the queue route
 NEE_ENV_SAMPLES = 16       # the light sample may go towards the environment map; ignored without a map or with a black one
 NEE_SAMPLER_PDF = 64       # MIS weights on the density of LIB's BSDF sampler instead of LIB's pdf value: the frame's expectation is LIB's
+NEE_FUSED_MOTION = 8192    # beside NEE_FUSED: the fused kernel with a time per lane under active motion (set_motion); alone, or without active motion: nothing
 
 
 def NEE_CANDIDATES(m):
@@ -805,6 +806,8 @@ class Scene:
         sampled by luminance and MIS-weighted against the map's radiance on a miss (ignored without a map or with a black one);
         NEE_SAMPLER_PDF builds the MIS weights on the density of LIB's BSDF sampler instead of LIB's pdf value, which removes the shift of
         the expectation at glossy vertices that see a light (bitwise the unflagged frame when no light sample is possible).
+        NEE_FUSED | NEE_FUSED_MOTION keeps the one launch per pass under active motion (set_motion), where NEE_FUSED alone is ignored:
+        bitwise the unflagged frame under the same motion.
         candidates = m ors NEE_CANDIDATES(m) into flags: the light sample picked among m candidates, still one shadow ray per vertex.
         Returns (accum, stats dict or None)."""
         x0, y0, w, h = tile if tile else (0, 0, W, H)

@@ -790,7 +790,7 @@ struct NeeSetup {
 	NeePunctual Pn{};        // the scene's punctual lights; n != 0: the PUN variants run
 	uint32_t n_lights = 0;   // listed triangles, whatever the flags
 	float light_area = 0;
-	bool fused = false;      // PTX_NEE_FUSED on a scene of the fused route
+	bool fused = false;      // PTX_NEE_FUSED on a scene of the fused route; under active motion only with PTX_NEE_FUSED_MOTION beside it
 	bool sampler_pdf = false;   // PTX_NEE_SAMPLER_PDF where a light sample is possible
 	uint32_t candidates = 1;    // M of PTX_NEE_CANDIDATES where a light sample is possible; above 1 the RIS variants run
 };
@@ -816,8 +816,9 @@ int nee_setup_locked(ptx_scene* sc, uint32_t flags, NeeSetup& S) {
 	const uint32_t n_lights = (uint32_t)ll.cdf.size();
 	S.n_lights = n_lights; S.light_area = ll.area;
 	// PTX_NEE_FUSED: one launch per pass wherever ptx_render would run the fused kernel; a scene of the queue route renders as without the flag
-	// ... and under active motion, where the unfused form alone carries a time per sample: ignored, not refused
-	S.fused = (flags & PTX_NEE_FUSED) != 0 && !use_wavefront(sc) && !motion_active(sc);
+	// ... and under active motion it is ignored, not refused, unless PTX_NEE_FUSED_MOTION stands beside it: then the fused kernel that carries a
+	// time per lane runs (nee_fused_motion.hip). PTX_NEE_FUSED_MOTION without PTX_NEE_FUSED, or without active motion, changes nothing.
+	S.fused = (flags & PTX_NEE_FUSED) != 0 && !use_wavefront(sc) && (!motion_active(sc) || (flags & PTX_NEE_FUSED_MOTION) != 0);
 	if (n_lights && !(flags & PTX_NEE_NO_LIGHT_SAMPLES)) {
 		if (!sc->lights.on_device) {
 			HIP_TRY(sc->d_light_tris.ensure(ll.tris.size() * 4));
@@ -875,7 +876,8 @@ int nee_setup_locked(ptx_scene* sc, uint32_t flags, NeeSetup& S) {
 	return PTX_OK;
 }
 
-// ptx_render_nee with PTX_NEE_FUSED on a scene of the fused route: one launch of k_nee_fused per pass, then the resolve. No round trips to the
+// ptx_render_nee with PTX_NEE_FUSED on a scene of the fused route: one launch of k_nee_fused per pass (under active motion, which only
+// PTX_NEE_FUSED_MOTION lets come here: of k_nee_fused_motion), then the resolve. No round trips to the
 // host and no streams: the workspace is ptx_render's radiance records, overflow stacks and counters. The caller holds the context's mutex, has
 // set the device, planned the passes and made the setup. With stats the stream is synchronised.
 int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeSetup& S, const NeeTargets& T, ptx_nee_stats* stats) {
@@ -885,6 +887,7 @@ int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeSetu
 	HIP_TRY(c->spill.ensure((size_t)grid * (kBlock / 64) * (size_t)kSpillWords * sizeof(uint2)));
 	HIP_TRY(hipMemsetAsync(c->counters.p, 0, 1024, c->stream));
 	const NeeFusedBuffers B{(float4*)c->sample_rad.p, (uint2*)c->spill.p, (unsigned long long*)c->counters.p, (unsigned long long*)((char*)c->counters.p + 16)};
+	const RenderMotion Rm = render_motion(sc);   // what the unfused form's kernels take
 	if (stats)
 		if (const int rc = PassFrame::ensure_events(c, f.n_pass); rc != PTX_OK) return rc;
 	for (uint32_t p = 0; p < f.n_pass; p++) {
@@ -892,7 +895,8 @@ int nee_fused_frame(ptx_ctx* c, ptx_scene* sc, const PassFrame& f, const NeeSetu
 		P.integrator = PTX_INTEGRATOR_LIB;
 		HIP_TRY(hipMemsetAsync(B.chunk_counter, 0, 8, c->stream));
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p], c->stream));
-		HIP_TRY(launch_nee_fused(sc->dev, P, S.Lt, S.Ev, S.Pn, S.sampler_pdf, S.candidates, B, sc->mode, sc->lds_bytes, grid, c->stream));
+		if (Rm.active) HIP_TRY(launch_nee_fused_motion(sc->dev, P, S.Lt, S.Ev, S.Pn, S.sampler_pdf, S.candidates, Rm, B, sc->mode, sc->lds_bytes, grid, c->stream));
+		else HIP_TRY(launch_nee_fused(sc->dev, P, S.Lt, S.Ev, S.Pn, S.sampler_pdf, S.candidates, B, sc->mode, sc->lds_bytes, grid, c->stream));
 		if (stats) HIP_TRY(hipEventRecord(c->events[2 * p + 1], c->stream));
 		HIP_TRY(nee_resolve(B.sample_rad, T, f, P, p, c->stream));
 	}
@@ -1027,7 +1031,7 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 	return PTX_OK;
 }
 
-constexpr uint32_t kNeeFlags = PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED | PTX_NEE_ENV_SAMPLES | PTX_NEE_SAMPLER_PDF | PTX_NEE_CANDIDATES(16);   // bits 8..11: the candidate count
+constexpr uint32_t kNeeFlags = PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED | PTX_NEE_ENV_SAMPLES | PTX_NEE_SAMPLER_PDF | PTX_NEE_CANDIDATES(16) | PTX_NEE_FUSED_MOTION;   // bits 8..11: the candidate count
 
 }  // namespace
 

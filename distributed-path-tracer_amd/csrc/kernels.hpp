@@ -316,6 +316,10 @@ struct NeeFusedBuffers {
 };
 hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates,
                             const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream);
+// The fused kernel with a time per lane (nee_fused_motion.hip, PTX_NEE_FUSED | PTX_NEE_FUSED_MOTION under active motion): Mo as launch_nee_shade
+// takes it. Mo.active == 0, or models_moved without the motion table, is hipErrorInvalidValue: never a static launch.
+hipError_t launch_nee_fused_motion(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates,
+                                   const RenderMotion& Mo, const NeeFusedBuffers& B, int mode, size_t lds_bytes, int grid, hipStream_t stream);
 
 // Variance-guided a-trous filter (denoise.hip, ptx_denoise). All buffers [n_pixels] float4 on the device.
 // prepare: the two radiance sums and the guide sums -> col_var (demodulated colour, v0), guide (mean normal, mean depth), remod (albedo, alpha)

@@ -204,6 +204,11 @@ int ptx_scene_set_model_xforms(ptx_scene* scene, const float* model_xform /* [n_
  *     every closest-hit and shadow batch of a round carries the times; k_nee_shade takes the hit surface's records at u. PTX_NEE_FUSED is
  *     ignored exactly as on the queue route (fused_launches == 0), not refused. Tiles, sample ranges, spp_per_pass, shards and the adaptive
  *     loop compose bit for bit as without motion. With PTX_NEE_NO_LIGHT_SAMPLES this is ptx_render's estimator under the shutter.
+ *   With PTX_NEE_FUSED | PTX_NEE_FUSED_MOTION on a scene of the fused route they run ONE launch per pass of a fused kernel that carries a
+ *     time per lane (k_nee_fused_motion): a lane that starts a sample computes u, blends the camera for itself, traces every ray of the
+ *     path at u and takes a moving hit surface's records at u. accum and the stats are bit for bit the unfused form's under the same
+ *     motion (PTX_NEE_FUSED_MOTION below). PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED | PTX_NEE_FUSED_MOTION is ptx_render's estimator
+ *     under a shutter in one launch per pass.
  *   ptx_render_aov: the same camera sample and time, with depth measured from the lens point of the camera at u: the guides of the
  *     blurred frame, which is what ptx_denoise needs for it.
  *   ptx_intersect_batch_motion (below ptx_intersect_batch) takes a time per ray on every route.
@@ -212,8 +217,8 @@ int ptx_scene_set_model_xforms(ptx_scene* scene, const float* model_xform /* [n_
  *     than render a frame with an instantaneous shutter where a blurred one was asked for. With inactive or cleared motion all of them run
  *     as before.
  *
- * OUT OF SCOPE: more than two keys and curved paths; vertex animation; motion in the fused kernels (ptx_render, PTX_NEE_FUSED) and in the
- * worker estimator; light samples towards moving emitters; ptx_render_motion and ptx_render_emission under a shutter, and with them the
+ * OUT OF SCOPE: more than two keys and curved paths; vertex animation; motion in ptx_render's fused kernel (k_render_pass: ptx_render keeps
+ * refusing; PTX_NEE_FUSED alone stays ignored under active motion and needs PTX_NEE_FUSED_MOTION beside it) and in the worker estimator; light samples towards moving emitters; ptx_render_motion and ptx_render_emission under a shutter, and with them the
  * temporal filters on blurred frames; stratified time samples; a moving sun, environment or punctual lights. */
 typedef struct ptx_motion {
 	const ptx_camera* begin_camera;    /* NULL: the camera does not move */
@@ -873,8 +878,8 @@ int ptx_ctx_get_mask_exchange_stats(ptx_ctx* ctx, uint64_t* calls /* NULL ok */,
 #define PTX_NEE_SAMPLER_PDF 64u
 /* PTX_NEE_CANDIDATES(m), m = 1 .. 16: the light sample of a vertex is picked among M = m candidates in proportion to their unshadowed
  * contributions (resampled importance sampling), and ONE shadow ray is traced for it. The count travels in bits 8..11 of flags:
- * M = ((flags >> 8) & 15) + 1, so PTX_NEE_CANDIDATES(1) is 0, the call without it. Bits at 4096 and above, and the values 2, 8, 32 and 128,
- * stay unassigned and refused as unknown. The estimator for M > 1 is the text of ptx_render_nee above with the LIGHT SAMPLE paragraph
+ * M = ((flags >> 8) & 15) + 1, so PTX_NEE_CANDIDATES(1) is 0, the call without it. 8192 is PTX_NEE_FUSED_MOTION (below); 4096, the bits at
+ * 16384 and above, and the values 2, 8, 32 and 128 stay unassigned and refused as unknown. The estimator for M > 1 is the text of ptx_render_nee above with the LIGHT SAMPLE paragraph
  * replaced by the following; IEEE binary32, each operation rounded on its own, in the order written.
  *   CANDIDATES. Candidate j = 0 .. M - 1 is the light sample of the call without these bits, taken verbatim (with PTX_NEE_ENV_SAMPLES its
  *     SELECTION and ENVIRONMENT SAMPLE, with PTX_NEE_SAMPLER_PDF its ps), with Philox block 3 + 2 j in the place of block 3 and block
@@ -898,6 +903,21 @@ int ptx_ctx_get_mask_exchange_stats(ptx_ctx* ctx, uint64_t* calls /* NULL ok */,
  * unfused call's with the same bits (on the queue route PTX_NEE_FUSED is ignored as above). With no light sample possible (empty list and
  * no environment table) no candidate is drawn, and the call is bit for bit the one without the bits, and ptx_render. */
 #define PTX_NEE_CANDIDATES(m) ((((uint32_t)(m)) - 1u) << 8)   /* m = 1 .. 16; m = 1 is 0: today's call */
+/* PTX_NEE_FUSED_MOTION: lets PTX_NEE_FUSED hold under active motion (ptx_scene_set_motion: MOTION above). With both bits, on a scene of the
+ * fused route (pipeline 0) whose motion is active, the call runs ONE launch per pass of the fused kernel that carries a time per lane.
+ * accum is bit for bit what the unflagged call leaves under the same motion, and rays, samples, n_lights, light_area, light_samples and
+ * light_visible are equal; render.passes = the launches, with ptx_render's pass size and id limit as for PTX_NEE_FUSED, and
+ * ptx_ctx_get_timing reports pipeline 0, fused_launches == passes and fused_ms == kernel_ms. Instead of the 68 (under motion up to 71)
+ * words of stream workspace per sample and one host synchronisation per round, the call needs the 16-byte radiance record per sample.
+ *   Without PTX_NEE_FUSED the bit is accepted and does nothing. With PTX_NEE_FUSED but no active motion (never set, all keys equal, or
+ *   cleared) the call is the PTX_NEE_FUSED call: the same kernels, bits and fused_launches. On the queue route it is ignored as
+ *   PTX_NEE_FUSED is (fused_launches == 0). PTX_NEE_FUSED alone under active motion stays ignored: a caller opts in to the motion kernel.
+ * Combines with every other flag and with PTX_NEE_CANDIDATES(m); ptx_render_adaptive_nee passes it through, and its rounds then run fused
+ * launches. The light-list rule (a surface of a moving model is not listed) and every refusal under active motion are unchanged.
+ * PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED | PTX_NEE_FUSED_MOTION is ptx_render's estimator under a shutter in one launch per pass.
+ * The kernel holds more state per lane than its static twin (the time, the blended basis of a moving ray space, a moving surface's
+ * records), and some variants run at a smaller workgroup for it: DESIGN.md 5.12 has the register table and the measurement. */
+#define PTX_NEE_FUSED_MOTION 8192u
 /* PUNCTUAL LIGHTS. With punctual lights on the scene (ptx_scene_set_punctual_lights) ptx_render_nee and ptx_render_adaptive_nee take them into
  * the LIGHT SAMPLE of a vertex as a third strategy. No flag exists for it: a scene on which none were set (or on which they were cleared) runs
  * the kernels without the branch and renders every bit as before. ptx_render, ptx_render_transparent, ptx_render_aov and the WORKER estimator

@@ -45,7 +45,11 @@
                                         at 1920 x 1080, 8 bounces, 16 spp, shutter (0, 1): the two calls alternate in one process, `reps` (5)
                                         synchronised calls each after a warm-up, kept with their smallest and largest; the time ratio, and the
                                         rays traced. Also the unflagged static call alone, as the control that is compared between commits.
-                                        Also writes the lines to profiles/motion_blur_bench.txt.
+                                        Alternated with them on the same scene: the call with PTX_NEE_FUSED | PTX_NEE_FUSED_MOTION under the
+                                        motion (fused_motion_*: the fused kernel with a time per lane, one launch per pass) and the
+                                        PTX_NEE_FUSED call without motion (fused_static_*); the fused motion frame is checked bitwise
+                                        against the unfused one. Also writes the lines to profiles/nee_fused_motion_bench.txt
+                                        (profiles/motion_blur_bench.txt holds the two unfused columns as measured before the kernel existed).
 Prints one JSON line per measurement. A scene without listed emitters (atrium) shows the cost of the wavefront form alone.
 """
 import importlib
@@ -362,32 +366,46 @@ def main_motion(reps, spp):
         return s, movers["begin_model_xform"], (movers["begin_camera"][:3], movers["begin_camera"][3:12], movers["begin_camera"][12])
     for name, make in (("cornell_one_box", cornell), ("movers", moving)):
         s, begin, cam = make()
-        times = {"static": [], "motion": []}
-        st = {}
+        FM = ptx.NEE_FUSED | ptx.NEE_FUSED_MOTION
+        calls = {"static": (False, 0), "motion": (True, 0), "fused_static": (False, ptx.NEE_FUSED), "fused_motion": (True, FM)}
+        times = {k: [] for k in calls}
+        st, launches, frames = {}, {}, {}
         for rep in range(reps + 1):
-            for k in ("static", "motion"):     # the two calls alternate; the motion is set and cleared outside the timed region
-                if k == "motion":
+            for k, (moving_now, flags) in calls.items():     # the four calls alternate; the motion is set and cleared outside the timed region
+                if moving_now:
                     s.set_motion(begin, cam, (0.0, 1.0))
                 a = zeros()
                 t0 = time.perf_counter()
-                _, st[k] = s.render_nee(W, H, spp, BOUNCES, accum=a, seed=SEED)
+                _, st[k] = s.render_nee(W, H, spp, BOUNCES, accum=a, seed=SEED, flags=flags)
                 ctx.synchronize()
                 dt = time.perf_counter() - t0
-                if k == "motion":
+                launches[k] = ctx.timing()["fused_launches"]
+                if moving_now:
                     s.clear_motion()
                 if rep:
                     times[k].append(dt)
+                else:
+                    frames[k] = a.cpu().numpy() if hasattr(a, "cpu") else np.array(a)
+        bitwise = bool((frames["fused_motion"].view(np.uint32) == frames["motion"].view(np.uint32)).all())
         lines.append(json.dumps(dict(scene=name, W=W, H=H, bounces=BOUNCES, spp=spp, reps=reps, pipeline=ctx.timing()["pipeline"],
                                      static_s_min=round(min(times["static"]), 4), static_s_max=round(max(times["static"]), 4),
                                      motion_s_min=round(min(times["motion"]), 4), motion_s_max=round(max(times["motion"]), 4),
                                      motion_over_static=round(min(times["motion"]) / min(times["static"]), 4),
                                      static_msamples_s=round(W * H * spp / min(times["static"]) / 1e6, 1), motion_msamples_s=round(W * H * spp / min(times["motion"]) / 1e6, 1),
                                      static_rays=st["static"]["rays"], motion_rays=st["motion"]["rays"], static_n_lights=st["static"]["n_lights"],
-                                     motion_n_lights=st["motion"]["n_lights"])))
+                                     motion_n_lights=st["motion"]["n_lights"],
+                                     fused_motion_s_min=round(min(times["fused_motion"]), 4), fused_motion_s_max=round(max(times["fused_motion"]), 4),
+                                     fused_static_s_min=round(min(times["fused_static"]), 4), fused_static_s_max=round(max(times["fused_static"]), 4),
+                                     fused_motion_launches=launches["fused_motion"], fused_static_launches=launches["fused_static"], motion_launches=launches["motion"],
+                                     unfused_motion_over_fused_motion=round(min(times["motion"]) / min(times["fused_motion"]), 4),
+                                     fused_motion_over_fused_static=round(min(times["fused_motion"]) / min(times["fused_static"]), 4),
+                                     fused_motion_msamples_s=round(W * H * spp / min(times["fused_motion"]) / 1e6, 1), fused_motion_rays=st["fused_motion"]["rays"],
+                                     fused_motion_frame_is_unfused_motion_frame=bitwise)))
         print(lines[-1], flush=True)
         s.close()
-    with open(os.path.join(ROOT, "profiles", "motion_blur_bench.txt"), "w") as f:
-        f.write("tools/bench_nee.py --motion: the unfused ptx_render_nee under active motion against the same call without motion, alternated, MI355X\n" + "\n".join(lines) + "\n")
+    with open(os.path.join(ROOT, "profiles", "nee_fused_motion_bench.txt"), "w") as f:
+        f.write("tools/bench_nee.py --motion: ptx_render_nee under active motion, unfused and with PTX_NEE_FUSED | PTX_NEE_FUSED_MOTION, against the same calls "
+                "without motion (unflagged and PTX_NEE_FUSED), the four alternated, MI355X\n" + "\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":

@@ -141,7 +141,7 @@ def main():
         return E, sa, sb
     if a.temporal and a.spp < 2:
         ap.error("--temporal needs --spp of at least 2 (two half-frames)")
-    render = (lambda **kw: s.render_nee(W, H, bounces=a.bounces, flags=ptx.NEE_FUSED, want_stats=False, **kw)[0]) if a.nee else \
+    render = (lambda **kw: s.render_nee(W, H, bounces=a.bounces, flags=ptx.NEE_FUSED | ptx.NEE_FUSED_MOTION, want_stats=False, **kw)[0]) if a.nee else \
              (lambda **kw: s.render(W, H, bounces=a.bounces, want_stats=False, **kw)[0])
     hist, prev_cam, prev_xf, acc_ms, filt_ms, share, mse = None, None, None, [], [], [], []
 
