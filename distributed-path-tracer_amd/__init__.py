@@ -30,7 +30,8 @@ NO_SUN_LIGHT = 0xFFFFFFFF  # core::renderer::no_sun_light, renderer.hpp:19
  ARR_MATERIALS, ARR_KD_NODES, ARR_KD_REFS, ARR_CAMERA, ARR_SUN, ARR_MODEL_NAMES, ARR_TEXTURES, ARR_TEXELS, ARR_SURF_TEX, ARR_TEXELS_F32,
  ARR_LIGHT_TRIS, ARR_LIGHT_CDF, ARR_LIGHT_GEOM, ARR_TRI_ISECT, ARR_RES_NODES, ARR_RES_REFS, ARR_RES_TRIS, ARR_LDS_ROOT,
  ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF, ARR_PUNCTUAL, ARR_PUNCTUAL_CDF, ARR_LENS, ARR_LDS_SHAPE, ARR_SURF_AUX,
- ARR_MOTION_XFORM, ARR_MOTION_MOVED, ARR_MOTION_CAMERA) = range(36)
+ ARR_MOTION_XFORM, ARR_MOTION_MOVED, ARR_MOTION_CAMERA, ARR_PUNCTUAL_TREE) = range(37)
+PUNCTUAL_PICK_CDF, PUNCTUAL_PICK_TREE = 0, 1   # ptx_punctual_pick: how a punctual sample picks its light (Scene.set_punctual_pick)
 LDS_LEAF_ORDER_BIT = 0x80000000  # ARR_LDS_ROOT: the surface's resident records are leaf-ordered (flat_scene.hpp)
 LDS_LEAF_ONLY_BIT = 0x40000000   # ARR_LDS_SHAPE: the surface's resident tree is a single leaf
 LDS_COMPLETE_BIT = 0x20000000    # ARR_LDS_SHAPE: ... is complete (no missing child) with at most KD_SHAPE_MAX_BRANCH_LEVELS branch levels
@@ -257,6 +258,9 @@ def lib():
         L.ptx_scene_destroy.argtypes = [C.c_void_p]
         L.ptx_scene_set_environment.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.ptx_scene_set_punctual_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ptx_scene_set_punctual_pick.argtypes = [C.c_void_p, C.c_uint32]
+        L.ptx_scene_get_punctual_pick.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.ptx_punctual_pick_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.ptx_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
         L.ptx_scene_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
         L.ptx_scene_set_model_xforms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
@@ -594,7 +598,8 @@ _ARR_DTYPE = {ARR_MODEL_XFORM: (np.float32, 12), ARR_MODEL_AABB: (np.float32, 6)
               ARR_LDS_ROOT: (np.uint32, 1), ARR_RES_PLAN: (np.uint32, 1), ARR_ENV_ROW_CDF: (np.float32, 1), ARR_ENV_CELL_CDF: (np.float32, 1),
               ARR_PUNCTUAL: (np.float32, 16), ARR_PUNCTUAL_CDF: (np.float32, 1), ARR_LENS: (np.float32, 2),
               ARR_LDS_SHAPE: (np.uint32, 1), ARR_SURF_AUX: (np.uint32, 4),
-              ARR_MOTION_XFORM: (np.float32, 12), ARR_MOTION_MOVED: (np.uint32, 1), ARR_MOTION_CAMERA: (np.float32, 1)}
+              ARR_MOTION_XFORM: (np.float32, 12), ARR_MOTION_MOVED: (np.uint32, 1), ARR_MOTION_CAMERA: (np.float32, 1),
+              ARR_PUNCTUAL_TREE: (np.uint32, 8)}
 
 
 class Scene:
@@ -856,6 +861,26 @@ class Scene:
         a = a.reshape(-1, 16)
         _check(lib().ptx_scene_set_punctual_lights(self.h, a.ctypes.data if len(a) else None, len(a)))
 
+    def set_punctual_pick(self, pick):
+        """ptx_scene_set_punctual_pick: PUNCTUAL_PICK_CDF (the default: by lum(intensity) alone) or PUNCTUAL_PICK_TREE (a light tree descended
+        from the shading point with importance power / distance^2). The mode survives set_punctual_lights; array(ARR_PUNCTUAL_TREE) is the tree."""
+        _check(lib().ptx_scene_set_punctual_pick(self.h, int(pick)))
+
+    @property
+    def punctual_pick(self):
+        """ptx_scene_get_punctual_pick"""
+        v = C.c_uint32()
+        _check(lib().ptx_scene_get_punctual_pick(self.h, C.byref(v)))
+        return v.value
+
+    def punctual_pick_batch(self, pos_u):
+        """ptx_punctual_pick_batch: [n,4] float32 (position, u) -> (light [n] int32, pmf [n] float32): the light a punctual candidate at the
+        position with draw u samples and its probability, by the device function the integrators inline, in the scene's mode."""
+        a = np.ascontiguousarray(pos_u, np.float32).reshape(-1, 4)
+        light, pmf = np.zeros(len(a), np.int32), np.zeros(len(a), np.float32)
+        _check(lib().ptx_punctual_pick_batch(self.h, a.ctypes.data, len(a), light.ctypes.data, pmf.ctypes.data))
+        return light, pmf
+
     def set_camera(self, origin, basis, yfov, lens_radius=0.0, focus_distance=0.0, blades=0, blade_rotation=0.0):
         """ptx_scene_set_camera: origin [3], basis [9] (columns x, y, z) and yfov as from_arrays' camera [13]; lens_radius > 0 gives a thin
         lens with a polygonal aperture of `blades` corners (0 = 16) focused at focus_distance. No tree is built and nothing is re-uploaded."""
@@ -1076,6 +1101,12 @@ class Renderer:
         if self._scene is None:
             raise PtxError(ERR_INVALID, "set_punctual_lights() before load_gltf()")
         self._scene.set_punctual_lights(lights)
+
+    def set_punctual_pick(self, pick):
+        """Scene.set_punctual_pick on the loaded scene: PUNCTUAL_PICK_CDF or PUNCTUAL_PICK_TREE; the mode survives set_punctual_lights."""
+        if self._scene is None:
+            raise PtxError(ERR_INVALID, "set_punctual_pick() before load_gltf()")
+        self._scene.set_punctual_pick(pick)
 
     def render_accum(self):
         """Radiance SUMS [H,W,4] of the frame; with transparent_background set, the reference's blended MEANS (colour, alpha) instead

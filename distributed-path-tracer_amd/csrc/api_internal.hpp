@@ -128,8 +128,10 @@ struct ptx_scene {
 	struct Punctual {
 		bool on_device = false;
 		std::vector<float> recs, cdf;   // [n][16], [n]
+		std::vector<uint32_t> tree;     // [n_nodes][8] the light tree (build_punctual_tree); empty in CDF mode and without lights
 	} punctual;
-	DevBuf d_punctual, d_punctual_cdf;
+	uint32_t punctual_pick = PTX_PUNCTUAL_PICK_CDF;   // ptx_scene_set_punctual_pick; outlives the lights, guarded as they are
+	DevBuf d_punctual, d_punctual_cdf, d_punctual_tree;
 	// The motion table (ptx_scene_set_motion): begin transforms, current transforms, moved flags, in one buffer; dev_motion points into it
 	// while the scene's motion moves a model, and is all nullptr otherwise. The begin camera travels in kernel arguments.
 	DevBuf d_motion;
@@ -143,6 +145,9 @@ inline bool motion_active(const ptx_scene* sc) { return sc->host.motion.active()
 // What the entry points that know no time answer while motion is active: PTX_ERR_UNSUPPORTED, before any device work
 int refuse_motion(const char* who);   // ptx_api.cpp
 const ptx_scene::EnvTable* build_env_table(ptx_scene* sc);   // ptx_api.cpp
+// api_render.cpp: the scene's punctual lights as the kernels take them (records, CDF and, in tree mode, the tree), uploaded at the first
+// call after a change; Pn stays empty without lights. The caller holds the context's mutex and has set the device.
+int punctual_on_device_locked(ptx_scene* sc, NeePunctual& Pn);
 void srgb_thresholds(float thr[256]);                      // ptx_api.cpp
 // api_batch.cpp: one decision on device buffers (adaptive.hip), its count read back: the stream is synchronised. The caller holds the
 // context's mutex. select_ms: nullptr, or where the HIP-event time of the decision kernels is added.

@@ -780,6 +780,28 @@ int ptx_render_emission(ptx_scene* sc, const ptx_render_cfg* cfg, float* emissio
 	return aov_frame(sc, cfg, "ptx_render_emission", emission, nullptr, AovKind::emission, nullptr, stats);
 }
 
+int punctual_on_device_locked(ptx_scene* sc, NeePunctual& Pn) {
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> tl(sc->lights_mu);
+	ptx_scene::Punctual& pl = sc->punctual;
+	if (pl.cdf.empty()) return PTX_OK;
+	if (!pl.on_device) {
+		HIP_TRY(sc->d_punctual.ensure(pl.recs.size() * 4));
+		HIP_TRY(sc->d_punctual_cdf.ensure(pl.cdf.size() * 4));
+		HIP_TRY(hipMemcpyAsync(sc->d_punctual.p, pl.recs.data(), pl.recs.size() * 4, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync(sc->d_punctual_cdf.p, pl.cdf.data(), pl.cdf.size() * 4, hipMemcpyHostToDevice, c->stream));
+		if (!pl.tree.empty()) {
+			HIP_TRY(sc->d_punctual_tree.ensure(pl.tree.size() * 4));
+			HIP_TRY(hipMemcpyAsync(sc->d_punctual_tree.p, pl.tree.data(), pl.tree.size() * 4, hipMemcpyHostToDevice, c->stream));
+		}
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		pl.on_device = true;
+	}
+	Pn.recs = (const float4*)sc->d_punctual.p; Pn.cdf = (const float*)sc->d_punctual_cdf.p; Pn.n = (uint32_t)pl.cdf.size();
+	if (!pl.tree.empty()) { Pn.nodes = (const float4*)sc->d_punctual_tree.p; Pn.n_nodes = (uint32_t)(pl.tree.size() / 8); }   // tree mode
+	return PTX_OK;
+}
+
 namespace {
 
 // What ptx_render_nee's passes read besides the scene: the light list and the environment table on the device, and which form renders.
@@ -853,21 +875,7 @@ int nee_setup_locked(ptx_scene* sc, uint32_t flags, NeeSetup& S) {
 		}
 	}
 	// punctual lights on the scene: a third kind of candidate, whatever the flags. The copy goes up at the first call after a set.
-	{
-		std::lock_guard<std::mutex> tl(sc->lights_mu);
-		ptx_scene::Punctual& pl = sc->punctual;
-		if (!pl.cdf.empty()) {
-			if (!pl.on_device) {
-				HIP_TRY(sc->d_punctual.ensure(pl.recs.size() * 4));
-				HIP_TRY(sc->d_punctual_cdf.ensure(pl.cdf.size() * 4));
-				HIP_TRY(hipMemcpyAsync(sc->d_punctual.p, pl.recs.data(), pl.recs.size() * 4, hipMemcpyHostToDevice, c->stream));
-				HIP_TRY(hipMemcpyAsync(sc->d_punctual_cdf.p, pl.cdf.data(), pl.cdf.size() * 4, hipMemcpyHostToDevice, c->stream));
-				HIP_TRY(hipStreamSynchronize(c->stream));
-				pl.on_device = true;
-			}
-			S.Pn.recs = (const float4*)sc->d_punctual.p; S.Pn.cdf = (const float*)sc->d_punctual_cdf.p; S.Pn.n = (uint32_t)pl.cdf.size();
-		}
-	}
+	if (const int rc = punctual_on_device_locked(sc, S.Pn); rc != PTX_OK) return rc;
 	// PTX_NEE_SAMPLER_PDF changes weights only: with no light sample that has a weight possible every weight is 1, and the unflagged variants
 	// run (a punctual sample has none: alone it leaves every weight 1)
 	S.sampler_pdf = (flags & PTX_NEE_SAMPLER_PDF) != 0 && (S.Lt.n != 0 || S.Ev.row_cdf != nullptr);

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "device_core.hpp"
+#include "nee_core.hpp"   // punctual_pick, for k_punctual_pick
 
 namespace ptx {
 
@@ -792,6 +793,18 @@ __global__ void k_material_eval(DevScene S, const int32_t* __restrict__ surface,
 	q[9] = e.emissive10.x; q[10] = e.emissive10.y; q[11] = e.emissive10.z;
 }
 
+// ------------------------------------------------------------------------------------ batch punctual picks
+// Which light a punctual candidate at position x with draw u samples, and its pmf: punctual_pick exactly as nee_candidate inlines it, one
+// (x, u) per lane (ptx_punctual_pick_batch). In CDF mode (Pn.nodes == nullptr) the position is not read.
+__global__ void k_punctual_pick(NeePunctual Pn, const float* __restrict__ pos_u, size_t n, int32_t* __restrict__ light, float* __restrict__ pmf) {
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float* q = pos_u + 4 * i;
+	float p;
+	light[i] = (int32_t)punctual_pick(Pn, mk(q[0], q[1], q[2]), q[3], p);
+	pmf[i] = p;
+}
+
 // ------------------------------------------------------------------------------------ tonemap + encode
 // core::tonemap_approx_aces (core/utils.hpp:29-36) + image::image::write (image/image.cpp:143-154)
 DEV float aces1(float x) {
@@ -927,6 +940,10 @@ hipError_t launch_camera_rays(const DevScene& S, const float* in, float* out, si
 }
 hipError_t launch_material_eval(const DevScene& S, const int32_t* surface, const float* uv, size_t n, float* out, hipStream_t stream) {
 	hipLaunchKernelGGL(k_material_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, S, surface, uv, n, out);
+	return hipGetLastError();
+}
+hipError_t launch_punctual_pick(const NeePunctual& Pn, const float* pos_u, size_t n, int32_t* light, float* pmf, hipStream_t stream) {
+	hipLaunchKernelGGL(k_punctual_pick, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, Pn, pos_u, n, light, pmf);
 	return hipGetLastError();
 }
 hipError_t launch_tonemap(const float4* accum, uint32_t n_pixels, float spp, const float* thresholds, uchar4* out, hipStream_t stream) {

@@ -295,7 +295,13 @@ struct NeePunctual {
 	const float4* recs;   // [n][4] the 16-float records as stored: (position, range) (direction, kind) (intensity, cos_inner) (cos_outer, 0, 0, 0)
 	const float* cdf;     // [n] cumulative share of lum(intensity), the last entry 1
 	uint32_t n;
+	// The light tree of PTX_PUNCTUAL_PICK_TREE (ptx_api.cpp: build_punctual_tree). nodes == nullptr: the pick is the CDF's. A node is two float4:
+	// (lo.xyz, power) (hi.xyz, word 7), word 7 = 0x80000000 | light for a leaf, else the left child's index; the right child is the next node.
+	const float4* nodes;
+	uint32_t n_nodes;
 };
+// the pick alone, one (position, u) per lane (ptx_punctual_pick_batch): the device function nee_candidate inlines
+hipError_t launch_punctual_pick(const NeePunctual& Pn, const float* pos_u /* [n][4] */, size_t n, int32_t* light, float* pmf, hipStream_t stream);
 constexpr uint32_t kNeePunctualRay = 0xFFFFFFFEu;   // exp_surf of a punctual sample's shadow ray: exp_tri holds the bits of dist, and the sample is visible iff the ray hits nothing nearer than dist
 // cnt (device, 8 words): [0] entries appended to `out`, [1] shadow rays of the round, [2..3] light samples (64-bit), [4..5] visible ones
 hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const NeeStream& out, float4* L, uint32_t n, const RenderMotion& Mo, hipStream_t stream);

@@ -131,6 +131,78 @@ DEV float sampler_pdf(V3 normal, V3 outcoming, V3 w, float roughness, float spec
 	return lerpf(pdf_diffuse(normal, w), ps_spec, spec_prob);
 }
 
+// ---- punctual lights (include/ptx.h: PUNCTUAL LIGHTS, PUNCTUAL PICK)
+// Light k seen from x, the expressions of PUNCTUAL SAMPLE: v, dist2, dist, w, att and the range test. One function for the sample and for a
+// leaf's importance, so that the importance is 0 exactly where the sample's own geometric conditions fail. false: dist2 is not > 0, and
+// nothing but dist2 is written.
+DEV bool punctual_geom(const NeePunctual& Pn, uint32_t k, V3 x, V3& w, float& dist2, float& dist, float& att, bool& in_range) {
+	const float4 r0 = Pn.recs[4 * (size_t)k], r1 = Pn.recs[4 * (size_t)k + 1];
+	const V3 v = mk(r0.x, r0.y, r0.z) - x;
+	dist2 = dot(v, v);
+	if (!(dist2 > 0)) return false;
+	dist = sqrt_exact(dist2);
+	w = v / dist;
+	att = 1.0f;
+	if (r1.w != 0.0f) {   // a spot: the cone's smooth edge
+		const float4 r2 = Pn.recs[4 * (size_t)k + 2], r3 = Pn.recs[4 * (size_t)k + 3];
+		const float cd = dot(mk(r1.x, r1.y, r1.z), -w);
+		const float sm = clampf((cd - r3.x) / pmax(r2.w - r3.x, 1e-6F), 0, 1);
+		att = sm * sm;
+	}
+	in_range = r0.w == 0.0f || dist <= r0.w;
+	return true;
+}
+constexpr uint32_t kPunctualLeaf = 0x80000000u;   // word 7 of a tree node: a leaf, the light's index in the low bits
+// importance of the node (n0, n1) seen from x: power / max(squared distance to the box's centre, squared half diagonal) for a branch, the
+// light's own power * att / dist2 for a leaf
+DEV float punctual_importance(const NeePunctual& Pn, float4 n0, float4 n1, V3 x) {
+	const uint32_t w7 = __float_as_uint(n1.w);
+	if (w7 & kPunctualLeaf) {
+		V3 w;
+		float dist2, dist, att;
+		bool in_range;
+		if (!punctual_geom(Pn, w7 & ~kPunctualLeaf, x, w, dist2, dist, att, in_range) || !in_range) return 0.0f;
+		return (n0.w * att) / dist2;
+	}
+	const V3 lo = mk(n0.x, n0.y, n0.z), hi = mk(n1.x, n1.y, n1.z);
+	const V3 c = (lo + hi) * 0.5F, d = x - c, h = (hi - lo) * 0.5F;
+	return n0.w / pmax(dot(d, d), dot(h, h));
+}
+// The stochastic descent from the root: at a branch the two children (adjacent nodes: one 64-byte read) are weighed from x, u picks one and
+// is stretched back to [0, 1). -> the leaf's light; pmf: the product of the branch probabilities as the descent realised them. The tree is
+// balanced by count, so the trip counts of a wave's lanes differ by one at most.
+DEV uint32_t punctual_pick_tree(const NeePunctual& Pn, V3 x, float u, float& pmf) {
+	pmf = 1.0f;
+	uint32_t w7 = __float_as_uint(Pn.nodes[1].w);
+	while (!(w7 & kPunctualLeaf)) {
+		const float4* __restrict__ ch = Pn.nodes + 2 * (size_t)w7;
+		const float4 l0 = ch[0], l1 = ch[1], r0 = ch[2], r1 = ch[3];
+		const float il = punctual_importance(Pn, l0, l1, x), ir = punctual_importance(Pn, r0, r1, x);
+		const float s = il + ir;
+		const float p = (s > 0 && s < __builtin_inff()) ? il / s : 0.5F;
+		if (u < p) {
+			pmf = pmf * p;
+			u = u / p;
+			w7 = __float_as_uint(l1.w);
+		} else {
+			const float q1 = 1 - p;
+			pmf = pmf * q1;
+			u = (u - p) / q1;
+			w7 = __float_as_uint(r1.w);
+		}
+		u = pmin(u, 0x1.fffffep-1F);
+	}
+	return w7 & ~kPunctualLeaf;
+}
+// Which light a punctual candidate samples and the probability pmf_k that divides it: the tree's descent from x when the scene has one
+// (a wave-uniform test of a kernel argument), else the first entry of the CDF with u below it and the difference of the STORED entries
+DEV uint32_t punctual_pick(const NeePunctual& Pn, V3 x, float u, float& pmf) {
+	if (Pn.nodes) return punctual_pick_tree(Pn, x, u, pmf);
+	const uint32_t k = env_pick(Pn.cdf, Pn.n, u);
+	pmf = Pn.cdf[k] - (k ? Pn.cdf[k - 1] : 0.0f);   // from the stored values: what the pick realises
+	return k;
+}
+
 // What a vertex leaves besides the path state: whether the path goes on, and its up-to-two shadow requests
 struct NeeVertex {
 	bool alive = false;         // the path continues with (o, d, T, p_prev, depth, pass) as the vertex left them
@@ -148,6 +220,7 @@ struct NeeVertex {
 // statements are then the former ones, and the unflagged kernels keep their registers. The RIS vertex takes M of them.
 // PUN (punctual lights on the scene, Pn; include/ptx.h: PUNCTUAL LIGHTS): the candidate is a punctual sample with probability c_p, drawn from
 // block_pun, and the other strategies' densities carry (1 - c_p). Without PUN, Pn, c_p and block_pun are not read and no statement changes.
+// Its light and pmf come from punctual_pick: the CDF's, or with a light tree on the scene (Pn.nodes) the descent from the vertex's position.
 template <uint32_t V>
 DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, float c_env, uint32_t pixel, uint32_t sample, uint32_t depth, uint32_t pass,
                        uint32_t block_light, uint32_t block_env, const Surf& sf, V3 normal, V3 outcoming, V3 T, const MatEval& me, float roughness, float spec_prob, V3& lx, V3& lo, V3& ld,
@@ -156,22 +229,15 @@ DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights
 	if constexpr (PUN) {
 		const float4 q = draws(P, pixel, sample, depth, pass, block_pun);
 		if (c_p == 1.0F || q.x < 0.5F) {
-			const uint32_t k = env_pick(Pn.cdf, Pn.n, q.y);
-			const float pmf = Pn.cdf[k] - (k ? Pn.cdf[k - 1] : 0.0f);   // from the stored values: what the pick realises
-			const float4 r0 = Pn.recs[4 * (size_t)k], r1 = Pn.recs[4 * (size_t)k + 1], r2 = Pn.recs[4 * (size_t)k + 2], r3 = Pn.recs[4 * (size_t)k + 3];
-			const V3 v = mk(r0.x, r0.y, r0.z) - sf.pos;
-			const float dist2 = dot(v, v);
-			if (dist2 > 0) {
-				const float dist = sqrt_exact(dist2);
-				const V3 w = v / dist;
-				float att = 1.0f;
-				if (r1.w != 0.0f) {   // a spot: the cone's smooth edge
-					const float cd = dot(mk(r1.x, r1.y, r1.z), -w);
-					const float sm = clampf((cd - r3.x) / pmax(r2.w - r3.x, 1e-6F), 0, 1);
-					att = sm * sm;
-				}
+			float pmf;
+			const uint32_t k = punctual_pick(Pn, sf.pos, q.y, pmf);
+			V3 w;
+			float dist2, dist, att;
+			bool in_range;
+			if (punctual_geom(Pn, k, sf.pos, w, dist2, dist, att, in_range)) {
+				const float4 r2 = Pn.recs[4 * (size_t)k + 2];
 				const V3 E = (mk(r2.x, r2.y, r2.z) * att) / dist2;
-				if (dot(normal, w) > 0 && pmf > 0 && (r0.w == 0.0f || dist <= r0.w) && att > 0 && pmax(E.x, pmax(E.y, E.z)) > 0) {
+				if (dot(normal, w) > 0 && pmf > 0 && in_range && att > 0 && pmax(E.x, pmax(E.y, E.z)) > 0) {
 					float pdf;
 					const V3 brdf = eval_brdf(normal, outcoming, w, me.albedo, roughness, me.metallic, spec_prob, pdf);
 					const float pe = pmax(pdf, kEps);

@@ -2,7 +2,9 @@
 // This file: contexts and scenes; api_render.cpp: the render entry points; api_batch.cpp: the batch calls; api_internal.hpp: what they share.
 // All arithmetic of the hot path lives in kernels.hip; there is no CPU fallback — GPU entry points fail with PTX_ERR_NO_DEVICE when no HIP
 // device exists.
+#include <algorithm>
 #include <cmath>
+#include <deque>
 
 #include "api_internal.hpp"
 
@@ -258,7 +260,7 @@ int upload_scene(ptx_scene* sc) {
 void release_scene_buffers(ptx_scene* sc) {
 	for (DevBuf* b : {&sc->d_models, &sc->d_surfaces, &sc->d_materials, &sc->d_nodes, &sc->d_refs, &sc->d_tris, &sc->d_shade, &sc->d_tex,
 	                  &sc->d_texels, &sc->d_texels_f, &sc->d_lut, &sc->d_spaces, &sc->d_model_space, &sc->d_surf_aux, &sc->d_wf_order, &sc->d_res_nodes, &sc->d_res_refs, &sc->d_res_tris, &sc->d_hot,
-	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell, &sc->d_punctual, &sc->d_punctual_cdf, &sc->d_lens, &sc->d_motion})
+	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell, &sc->d_punctual, &sc->d_punctual_cdf, &sc->d_punctual_tree, &sc->d_lens, &sc->d_motion})
 		b->release();
 	sc->lights.on_device = false;
 	sc->env_table.on_device = false;
@@ -608,6 +610,83 @@ int ptx_scene_set_environment(ptx_scene* sc, const char* png_path, int srgb) {
 	return PTX_OK;
 }
 
+// The light tree of PTX_PUNCTUAL_PICK_TREE over the stored records (include/ptx.h: PUNCTUAL PICK, THE TREE): [n_nodes][8] words. Nodes are
+// split in FIFO order, by count along the widest axis; a black light is in no leaf. Empty without lights.
+static std::vector<uint32_t> build_punctual_tree(const std::vector<float>& recs) {
+	const uint32_t n = (uint32_t)(recs.size() / 16);
+	std::vector<double> lum(n);
+	std::vector<uint32_t> root;
+	for (uint32_t k = 0; k < n; k++) {
+		const float* r = recs.data() + 16 * (size_t)k;
+		lum[k] = (0.2126 * (double)r[8] + 0.7152 * (double)r[9]) + 0.0722 * (double)r[10];
+		if (lum[k] > 0) root.push_back(k);
+	}
+	std::vector<uint32_t> nodes;
+	if (root.empty()) return nodes;
+	auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+	std::deque<std::pair<uint32_t, std::vector<uint32_t>>> queue;   // (node, its lights in order)
+	nodes.resize(8);
+	queue.emplace_back(0u, std::move(root));
+	while (!queue.empty()) {
+		const uint32_t node = queue.front().first;
+		std::vector<uint32_t> idx = std::move(queue.front().second);
+		queue.pop_front();
+		float lo[3], hi[3];
+		double power = 0;
+		for (size_t i = 0; i < idx.size(); i++) {
+			const float* p = recs.data() + 16 * (size_t)idx[i];
+			for (int a = 0; a < 3; a++) {
+				if (i == 0 || p[a] < lo[a]) lo[a] = p[a];
+				if (i == 0 || p[a] > hi[a]) hi[a] = p[a];
+			}
+			power += lum[idx[i]];
+		}
+		uint32_t w7;
+		if (idx.size() == 1) {
+			w7 = 0x80000000u | idx[0];
+		} else {
+			int ax = 0;
+			for (int a = 1; a < 3; a++)
+				if ((double)hi[a] - (double)lo[a] > (double)hi[ax] - (double)lo[ax]) ax = a;
+			std::sort(idx.begin(), idx.end(), [&](uint32_t i, uint32_t j) {
+				const float pi = recs[16 * (size_t)i + ax], pj = recs[16 * (size_t)j + ax];
+				return pi < pj || (pi == pj && i < j);
+			});
+			const size_t half = idx.size() / 2;
+			w7 = (uint32_t)(nodes.size() / 8);
+			nodes.resize(nodes.size() + 16);
+			queue.emplace_back(w7, std::vector<uint32_t>(idx.begin(), idx.begin() + half));
+			queue.emplace_back(w7 + 1, std::vector<uint32_t>(idx.begin() + half, idx.end()));
+		}
+		uint32_t* q = nodes.data() + 8 * (size_t)node;
+		for (int a = 0; a < 3; a++) { q[a] = bits(lo[a]); q[4 + a] = bits(hi[a]); }
+		q[3] = bits((float)power);
+		q[7] = w7;
+	}
+	return nodes;
+}
+
+int ptx_scene_set_punctual_pick(ptx_scene* sc, uint32_t pick) {
+	// no device work: ptx_render_nee uploads the tree when it next runs
+	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_scene_set_punctual_pick: scene is NULL");
+	if (pick != PTX_PUNCTUAL_PICK_CDF && pick != PTX_PUNCTUAL_PICK_TREE) return set_err(PTX_ERR_INVALID, "ptx_scene_set_punctual_pick: unknown mode");
+	std::unique_lock<std::mutex> lk;
+	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);   // no render of this scene is in flight
+	std::lock_guard<std::mutex> tl(sc->lights_mu);
+	if (pick == sc->punctual_pick) return PTX_OK;
+	sc->punctual_pick = pick;
+	sc->punctual.tree = pick == PTX_PUNCTUAL_PICK_TREE ? build_punctual_tree(sc->punctual.recs) : std::vector<uint32_t>();
+	sc->punctual.on_device = false;
+	return PTX_OK;
+}
+
+int ptx_scene_get_punctual_pick(const ptx_scene* sc, uint32_t* pick) {
+	if (!sc || !pick) return set_err(PTX_ERR_INVALID, "ptx_scene_get_punctual_pick: NULL argument");
+	std::lock_guard<std::mutex> tl(const_cast<ptx_scene*>(sc)->lights_mu);
+	*pick = sc->punctual_pick;
+	return PTX_OK;
+}
+
 int ptx_scene_set_punctual_lights(ptx_scene* sc, const float* lights, uint32_t n) {
 	// every refusal is decided before any device work; the call itself does none (ptx_render_nee uploads the lights when it next runs)
 	auto bad = [](const std::string& m) { return set_err(PTX_ERR_INVALID, "ptx_scene_set_punctual_lights: " + m); };
@@ -642,6 +721,7 @@ int ptx_scene_set_punctual_lights(ptx_scene* sc, const float* lights, uint32_t n
 	std::unique_lock<std::mutex> lk;
 	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);   // no render of this scene is in flight
 	std::lock_guard<std::mutex> tl(sc->lights_mu);
+	if (sc->punctual_pick == PTX_PUNCTUAL_PICK_TREE) next.tree = build_punctual_tree(next.recs);   // the mode outlives the lights
 	sc->punctual = std::move(next);
 	return PTX_OK;
 }
@@ -898,6 +978,7 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 	const void* src = nullptr;
 	size_t bytes = 0, elem = 4;
 	std::vector<float> tmp;
+	std::vector<uint32_t> tmp_words;
 	std::string names;
 	switch (which) {
 	case PTX_ARR_MODEL_XFORM: src = h.model_xform.data(); bytes = h.model_xform.size() * 4; break;
@@ -935,6 +1016,7 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 	case PTX_ARR_ENV_CELL_CDF: { const auto& et = *build_env_table(const_cast<ptx_scene*>(sc)); src = et.cell_cdf.data(); bytes = et.cell_cdf.size() * 4; break; }
 	case PTX_ARR_PUNCTUAL: { std::lock_guard<std::mutex> tl(const_cast<ptx_scene*>(sc)->lights_mu); tmp = sc->punctual.recs; src = tmp.data(); bytes = tmp.size() * 4; break; }
 	case PTX_ARR_PUNCTUAL_CDF: { std::lock_guard<std::mutex> tl(const_cast<ptx_scene*>(sc)->lights_mu); tmp = sc->punctual.cdf; src = tmp.data(); bytes = tmp.size() * 4; break; }
+	case PTX_ARR_PUNCTUAL_TREE: { std::lock_guard<std::mutex> tl(const_cast<ptx_scene*>(sc)->lights_mu); tmp_words = sc->punctual.tree; src = tmp_words.data(); bytes = tmp_words.size() * 4; break; }
 	case PTX_ARR_LENS: tmp = lens_table(h.camera); src = tmp.data(); bytes = tmp.size() * 4; break;
 	case PTX_ARR_TRI_ISECT: src = h.tri_isect.data(); bytes = h.tri_isect.size() * sizeof(TriIsect); break;
 	case PTX_ARR_RES_NODES: src = h.res_nodes.data(); bytes = h.res_nodes.size() * 8; break;

@@ -88,6 +88,27 @@ public:
 		if (records.size() % 16) throw std::runtime_error("set_punctual_lights: the records are 16 floats each");
 		check(ptx_scene_set_punctual_lights(scene_, records.empty() ? nullptr : records.data(), (uint32_t)(records.size() / 16)));
 	}
+	// How a punctual sample picks its light (ptx_scene_set_punctual_pick): PTX_PUNCTUAL_PICK_CDF, the default, or PTX_PUNCTUAL_PICK_TREE, a
+	// light tree descended from the shading point. The mode survives set_punctual_lights.
+	void set_punctual_pick(uint32_t pick) {
+		if (!scene_) throw std::runtime_error("set_punctual_pick() before load_gltf()");
+		check(ptx_scene_set_punctual_pick(scene_, pick));
+	}
+	uint32_t punctual_pick() const {
+		if (!scene_) throw std::runtime_error("punctual_pick() before load_gltf()");
+		uint32_t pick = 0;
+		check(ptx_scene_get_punctual_pick(scene_, &pick));
+		return pick;
+	}
+	// The pick alone for n (position, u) records of 4 floats, host memory (ptx_punctual_pick_batch) -> the lights; pmf receives their probabilities
+	std::vector<int32_t> punctual_pick_batch(const std::vector<float>& pos_u, std::vector<float>& pmf) const {
+		if (!scene_) throw std::runtime_error("punctual_pick_batch() before load_gltf()");
+		if (pos_u.size() % 4) throw std::runtime_error("punctual_pick_batch: the records are 4 floats each");
+		std::vector<int32_t> light(pos_u.size() / 4);
+		pmf.assign(light.size(), 0.0f);
+		check(ptx_punctual_pick_batch(scene_, pos_u.data(), light.size(), light.data(), pmf.data()));
+		return light;
+	}
 
 	// radiance sums [H][W][4]; with transparent_background set: the blended means (colour, alpha) of ptx_render_transparent. stats optional
 	std::vector<float> render_accum(ptx_render_stats* stats = nullptr) const {

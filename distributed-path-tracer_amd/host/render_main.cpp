@@ -1,6 +1,6 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--denoise] [--split-emission] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--split-emission] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--nee-punctual-tree] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
 //       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
 //       --split-emission: with --denoise, alone or with --adaptive (with or without --nee*): the first-hit emission of the guides' samples is
@@ -18,6 +18,8 @@
 //                      samples (8), then rounds of STEP (MIN) go to the pixels whose half-frames still disagree by more than THR
 //       --nee-punctual: with --nee (or a switch that implies it): the `point` and `spot` lights of the glTF being rendered (KHR_lights_punctual)
 //                      are read and set on the scene, and the light sample takes them as a third strategy; without --nee it is an error
+//       --nee-punctual-tree: --nee-punctual with the light of a punctual sample picked from a light tree by its distance from the shading point
+//                      (renderer::set_punctual_pick, PTX_PUNCTUAL_PICK_TREE) instead of by intensity alone; implies --nee-punctual
 //       combinations:  --adaptive with --nee / --nee-fused / --nee-env / --nee-sampler-pdf / --nee-candidates renders the adaptive loop on the light-sampling estimator
 //                      (renderer::render_adaptive_nee); --adaptive --denoise, with or without --nee*, filters the adaptive frame
 //                      (ptx_denoise_counts on the guides of the first MIN samples); --nee* --denoise filters two light-sampled half-frames
@@ -54,7 +56,7 @@ static void write_png(const std::string& path, const std::vector<uint8_t>& rgba,
 
 int main(int argc, char** argv) {
 	bool split_emission = false;
-	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false, nee_sampler_pdf = false, nee_punctual = false;
+	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false, nee_sampler_pdf = false, nee_punctual = false, nee_punctual_tree = false;
 	float ad_thr = 0.1f;
 	unsigned ad_min = 8, ad_step = 0, nee_candidates = 1;
 	std::string aov_prefix, nee_env;
@@ -68,6 +70,7 @@ int main(int argc, char** argv) {
 		else if (argc > 1 && std::string(argv[1]) == "--nee-fused") { nee = nee_fused = true; argv[1] = argv[0]; argv++; argc--; }   // ... one launch per pass
 		else if (argc > 1 && std::string(argv[1]) == "--nee-sampler-pdf") { nee = nee_sampler_pdf = true; argv[1] = argv[0]; argv++; argc--; }   // ... weights on the sampler's density
 		else if (argc > 1 && std::string(argv[1]) == "--nee-punctual") { nee_punctual = true; argv[1] = argv[0]; argv++; argc--; }   // ... the file's point and spot lights too; does not imply --nee
+		else if (argc > 1 && std::string(argv[1]) == "--nee-punctual-tree") { nee_punctual = nee_punctual_tree = true; argv[1] = argv[0]; argv++; argc--; }   // ... picked from the light tree
 		else if (argc > 2 && std::string(argv[1]) == "--nee-env") { nee = true; nee_env = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }   // ... the map as a light
 		else if (argc > 2 && std::string(argv[1]) == "--nee-candidates") {   // ... picked among M candidates
 			if (std::sscanf(argv[2], "%u", &nee_candidates) < 1 || nee_candidates < 1 || nee_candidates > 16) { std::fprintf(stderr, "error: --nee-candidates M, M = 1 .. 16\n"); return 1; }
@@ -90,7 +93,7 @@ int main(int argc, char** argv) {
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--split-emission] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--split-emission] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--nee-punctual-tree] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (nee_punctual && !nee) {
@@ -144,6 +147,7 @@ int main(int argc, char** argv) {
 		if (nee_punctual) {
 			const std::vector<float> lamps = core::renderer::read_punctual_lights(argv[1]);
 			r.set_punctual_lights(lamps);
+			if (nee_punctual_tree) r.set_punctual_pick(PTX_PUNCTUAL_PICK_TREE);
 			n_punctual = lamps.size() / 16;
 		}
 		auto t0 = std::chrono::steady_clock::now();
@@ -197,6 +201,7 @@ int main(int argc, char** argv) {
 			std::printf(", \"nee_lights\": %u, \"nee_light_samples\": %llu, \"nee_light_visible\": %llu, \"nee_kernel_ms\": %.3f", nst.n_lights,
 			            (unsigned long long)nst.light_samples, (unsigned long long)nst.light_visible, nst.render.kernel_ms);
 		if (nee_punctual) std::printf(", \"nee_punctual_lights\": %zu", n_punctual);
+		if (nee_punctual_tree) std::printf(", \"nee_punctual_pick\": \"tree\"");
 		std::printf("}\n");
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "error: %s\n", e.what());

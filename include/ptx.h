@@ -250,6 +250,17 @@ int ptx_scene_set_punctual_lights(ptx_scene* scene, const float* lights /* [n][1
  * where it is (ptx_load_opts::sun_light_index). Returns the number of records; dst == NULL only counts. Returns -(ptx_status) on a file or
  * parse error and when dst_floats < 16 x the count. ptx_scene_load_gltf does not pick the lights up: the caller reads and sets them. */
 int64_t ptx_gltf_read_punctual_lights(const char* gltf_path, float* dst /* NULL = count only */, size_t dst_floats);
+/* How a punctual sample picks its light (PUNCTUAL PICK below ptx_render_nee's flags has the tree, the importance and the descent):
+ * PTX_PUNCTUAL_PICK_CDF, the default, from the CDF over lum(intensity), whatever the shading point; PTX_PUNCTUAL_PICK_TREE by a stochastic
+ * descent of a binary tree over the lights with importance power / distance^2 seen from the shading point. Opt-in scene state: a scene on
+ * which the setter was never called, or was last called with CDF, renders every bit as before. Works on host-only scenes and does no device
+ * work; the tree (PTX_ARR_PUNCTUAL_TREE) is built by the call from the stored lights, rebuilt by every later ptx_scene_set_punctual_lights
+ * (the mode survives a new light set and a clear) and uploaded at the first render after a change, as the records and the CDF are.
+ * ptx_scene_set_model_xforms, ptx_scene_set_camera and ptx_scene_set_motion leave mode and tree alone: lights are world-space state.
+ * PTX_ERR_INVALID for a NULL scene (or a NULL `pick` of the getter) and for an unknown mode; a refused call leaves the mode as it was. */
+typedef enum ptx_punctual_pick { PTX_PUNCTUAL_PICK_CDF = 0, PTX_PUNCTUAL_PICK_TREE = 1 } ptx_punctual_pick;
+int ptx_scene_set_punctual_pick(ptx_scene* scene, uint32_t pick);
+int ptx_scene_get_punctual_pick(const ptx_scene* scene, uint32_t* pick);
 
 typedef struct ptx_scene_info {
 	uint32_t n_models, n_surfaces, n_vertices, n_triangles;
@@ -313,7 +324,9 @@ typedef enum ptx_array {
 	/* the motion of ptx_scene_set_motion (host-only scenes too); all three empty when no motion is set */
 	PTX_ARR_MOTION_XFORM = 33, /* float[n_models][12]: the begin transforms; a static model's entry is its current transform */
 	PTX_ARR_MOTION_MOVED = 34, /* uint32[n_models]: 1 = the model moves */
-	PTX_ARR_MOTION_CAMERA = 35 /* float[15]: begin origin, begin basis (the current camera's when it does not move), camera-moved flag, open, close */
+	PTX_ARR_MOTION_CAMERA = 35,/* float[15]: begin origin, begin basis (the current camera's when it does not move), camera-moved flag, open, close */
+	/* the light tree of ptx_scene_set_punctual_pick (host-only scenes too) */
+	PTX_ARR_PUNCTUAL_TREE = 36 /* uint32[n_nodes][8], bit patterns: lo.xyz, power, hi.xyz, word 7; empty in CDF mode and without lights */
 } ptx_array;
 int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, size_t dst_bytes);
 
@@ -942,7 +955,36 @@ int ptx_ctx_get_mask_exchange_stats(ptx_ctx* ctx, uint64_t* calls /* NULL ok */,
  *     one shadow ray for the pick, with the punctual visibility rule when the pick is punctual. PTX_NEE_NO_LIGHT_SAMPLES empties the triangle
  *     list only. light_samples and light_visible count punctual rays like the others; the order of the additions of a sample is unchanged.
  *   EXPECTATION. A punctual candidate has selection probability c_p * pmf_k and returns brdf'(w_k) E_k V_k over it: unbiased for the sum over
- *     the lights. The other strategies' light-side and BSDF-side weights still add to one over the directions they share. */
+ *     the lights. The other strategies' light-side and BSDF-side weights still add to one over the directions they share.
+ * PUNCTUAL PICK (ptx_scene_set_punctual_pick, PTX_PUNCTUAL_PICK_TREE). The CDF above picks a lamp across the room as often as the lamp
+ * overhead. In tree mode two things change in the text above and nothing else: which light k a punctual candidate samples, and the pmf that
+ * stands wherever the text has pmf_k. A delta light has no MIS partner, so no other weight knows the pick: c_p, the (1 - c_p) convention,
+ * the reservoir, the visibility rule, the counters and the order of the additions are as written, and so is the condition pmf_k > 0. No NEE
+ * flag exists for it and no variant: the PUN kernels test one kernel argument, uniform over the launch.
+ *   THE TREE (PTX_ARR_PUNCTUAL_TREE), built on the host, deterministic. Leaves are the stored lights with lum_k > 0, lum_k =
+ *     (0.2126 r + 0.7152 g) + 0.0722 b of the float32 intensity in float64; a black light is in no leaf. A node is 8 words: lo.xyz (0-2) and
+ *     hi.xyz (4-6), the float32 bounds of the positions below it; power (3), the float64 sum of the lum_k below it in the node's light order,
+ *     stored as float32; word 7 = 0x80000000 | light index for a leaf, for a branch the index of its left child, whose right sibling is the
+ *     next node. The root is node 0 over the lights in index order. Nodes are split in FIFO order. A node over one light is a leaf. Otherwise
+ *     the axis is the largest extent hi - lo, taken in float64 from the float32 values, the lowest axis winning a tie; the lights are sorted
+ *     by (position[axis], index); the first count / 2 (integer division) go left, in that order, the others right; the two children take
+ *     the next two free slots, left first. m leaves give 2 m - 1 nodes and a depth of at most ceil(log2 m) + 1; the trip counts of two
+ *     descents differ by one at most.
+ *   THE IMPORTANCE of child N seen from x. IEEE binary32, each operation rounded on its own, in the order written; dot is the device's,
+ *     (a.x b.x + a.y b.y) + a.z b.z. Branch: c = (lo + hi) * 0.5F, d = x - c, h = (hi - lo) * 0.5F, I = power / max(dot(d, d), dot(h, h)):
+ *     inside the box's sphere the distance says nothing, and the node counts with its half diagonal. Leaf of light k: v, dist2, dist, w, att
+ *     and the range test are the expressions of PUNCTUAL SAMPLE (one device function shared with the sample); I = (power * att) / dist2
+ *     when dist2 > 0 and the light is in range, else 0. So a leaf's importance is exactly 0 precisely where the sample's own geometric
+ *     conditions fail, and the cone of a spot steers the last step of the descent.
+ *   THE PICK, with u = q.y of the candidate's block 0x200 + j, node = 0, pmf = 1. While node is a branch with children l and l + 1:
+ *     s = I_l + I_r; p = I_l / s, or 0.5F if s is not a positive finite number. If u < p: pmf = pmf * p, u = u / p, go left. Otherwise
+ *     q1 = 1 - p, pmf = pmf * q1, u = (u - p) / q1, go right. Then u = min(u, 0x1.fffffep-1F). The leaf's light is k and pmf is pmf_k. A
+ *     light whose realised pmf rounds to 0 from some point is not sampled from there, as under the CDF. With one light the root is its leaf:
+ *     (0, 1.0F), and the frame is the CDF mode's bit for bit.
+ *   EXPECTATION. The pmf is a function of x alone and positive wherever E_k(x) > 0 (a leaf with I > 0 has p > 0 at every branch above it),
+ *     so the punctual term stays unbiased for the sum over the lights. What falls is the variance; DESIGN.md 5.13 has the measurement.
+ *   Out of scope: emissive triangles in the tree (their MIS weights need the pick's density from the previous vertex), orientation and cone
+ *     bounds in the branches, the receiver's cosine, a tree for the environment map, lights that move under a shutter. */
 typedef struct ptx_nee_cfg { uint32_t flags; } ptx_nee_cfg;
 typedef struct ptx_nee_stats {
 	ptx_render_stats render;   /* rays = closest-hit + shadow queries */
@@ -1031,6 +1073,12 @@ int ptx_camera_rays_batch(ptx_scene* scene, const float* ndc_ratio, size_t n, fl
  * inline; on a scene without a lens the pinhole rays. in [n][5]: ndc.x, ndc.y, aspect ratio, u, v;  out [n][6]. Pointers and refusals as
  * in ptx_camera_rays_batch. */
 int ptx_camera_lens_rays_batch(ptx_scene* scene, const float* in, size_t n, float* rays);
+/* The light a punctual candidate at position x with draw u samples, and its pmf_k (PUNCTUAL LIGHTS, PUNCTUAL PICK): the pick alone,
+ * evaluated by the same device function the integrators inline, in the scene's mode. In CDF mode the position is ignored: the first
+ * entry of the stored CDF with u below it, and the difference of the stored entries. pos_u [n][4]: x(3), u;  light [n], pmf [n]. Pointers
+ * device or host, all of one kind. The lights (and the tree) are uploaded if a change is pending. PTX_ERR_NO_DEVICE on a host-only scene;
+ * PTX_ERR_INVALID for a NULL scene, NULL pointers with n > 0, mixed kinds and a scene without stored lights. */
+int ptx_punctual_pick_batch(ptx_scene* scene, const float* pos_u /* [n][4]: position, u */, size_t n, int32_t* light /* [n] */, float* pmf /* [n] */);
 
 /* Batch form of core::material::get_normal / get_albedo / get_opacity / get_roughness / get_metallic / get_emissive (LIB/core/material.cpp:6-53,
  * bilinear image_texture::sample lookups): what the shading kernels compute at a hit, evaluated by the same device function.

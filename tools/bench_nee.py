@@ -34,11 +34,14 @@
                                         lines to profiles/nee_ris_bench.txt.
   tools/bench_nee.py --punctual [ref_spp] [reps] [spp]
                                         Point and spot lights (Scene.set_punctual_lights) on procedural.lamp_scene with an emitter, with 1 lamp and
-                                        with 64 (half of them spots), at 1920 x 1080, 8 bounces, 16 spp, M = 1 and M = 4, with and without
-                                        PTX_NEE_FUSED: the four calls of a scene alternate in one process, each kept at the smallest of `reps`
+                                        with 64 (half of them spots), at 1920 x 1080, 8 bounces, 16 spp, with and without PTX_NEE_FUSED: the light
+                                        of a punctual sample picked from the light tree (Scene.set_punctual_pick) at M = 1, and from the CDF at
+                                        M = 1 and M = 4. The six calls of a scene alternate in one process, each kept at the smallest of `reps`
                                         synchronised calls after a warm-up. Per row: the time, light rays traced per sample, and the mean squared
-                                        error of the written bytes against a ref_spp (1024) frame of the SAME call (unfused, M = 1) of another seed:
-                                        ptx_render cannot see the lamps. The lines are the first part of profiles/nee_punctual_bench.txt.
+                                        error of the written bytes against a ref_spp (1024) frame of the SAME call (unfused, CDF, M = 1) of another
+                                        seed: ptx_render cannot see the lamps; a tree row also has the error of the CDF call (M = 1, same form) at
+                                        the spp that takes the tree call's time. The lines are the first part of
+                                        profiles/nee_punctual_tree_bench.txt (profiles/nee_punctual_bench.txt: the CDF rows before the tree existed).
   tools/bench_nee.py --motion [reps] [spp]
                                         Motion blur (Scene.set_motion): the unfused ptx_render_nee with the motion active against the same call
                                         without motion, on Cornell with one box moving and on procedural.movers_scene (its camera moving too),
@@ -325,26 +328,46 @@ def main_punctual(ref_spp, reps, spp):
         ctx.synchronize()
         ref = ctx.tonemap_encode(ref_acc, W, H, ref_spp)[..., :3].astype(np.float64) / 255
         del ref_acc
-        forms = {(form, m): base | ptx.NEE_CANDIDATES(m) for form, base in (("fused", ptx.NEE_FUSED), ("unfused", 0)) for m in (1, 4)}
-        best, acc, st, launches = {k: 1e30 for k in forms}, {}, {}, {}
-        for r in range(reps + 1):
-            for k, flags in forms.items():
-                a = zeros()
-                t0 = time.perf_counter()
-                _, st[k] = s.render_nee(W, H, spp, BOUNCES, accum=a, seed=SEED, flags=flags)
-                ctx.synchronize()
-                dt = time.perf_counter() - t0
-                if r:
-                    best[k] = min(best[k], dt)
-                acc[k], launches[k] = a, ctx.timing()["fused_launches"]
-        for (form, m), sec in best.items():
-            k = (form, m)
-            mse = float(np.mean((ctx.tonemap_encode(acc[k], W, H, spp)[..., :3].astype(np.float64) / 255 - ref) ** 2))
-            print(json.dumps(dict(scene="lamp_scene", lamps=n_lamps, form=form, M=m, W=W, H=H, bounces=BOUNCES, spp=spp, n_lights=st[k]["n_lights"],
-                                  fused_launches=launches[k], s=round(sec, 4), msamples_s=round(W * H * spp / sec / 1e6, 1), rays=st[k]["rays"],
-                                  light_samples_per_sample=round(st[k]["light_samples"] / st[k]["samples"], 4),
-                                  light_visible_per_sample=round(st[k]["light_visible"] / st[k]["samples"], 4), mse=mse, ref_spp=ref_spp)), flush=True)
+        # the same scene with the light of a punctual sample picked from the light tree (Scene.set_punctual_pick): a scene of its own, so that
+        # no call of the alternation uploads anything
+        tree = ptx.Scene.from_arrays(ctx, *[d[k] for k in KEYS])
+        tree.set_punctual_lights(lamps)
+        tree.set_punctual_pick(ptx.PUNCTUAL_PICK_TREE)
+        scene_of = {"cdf": s, "tree": tree}
+        forms = {(form, pick, m): base | ptx.NEE_CANDIDATES(m) for form, base in (("fused", ptx.NEE_FUSED), ("unfused", 0))
+                 for pick, m in (("tree", 1), ("cdf", 1), ("cdf", 4))}
+
+        def mse_of(a, n):
+            return float(np.mean((ctx.tonemap_encode(a, W, H, n)[..., :3].astype(np.float64) / 255 - ref) ** 2))
+
+        def timed(forms, n):
+            best, acc, st, launches = {k: 1e30 for k in forms}, {}, {}, {}
+            for r in range(reps + 1):
+                for k, flags in forms.items():
+                    a = zeros()
+                    t0 = time.perf_counter()
+                    _, st[k] = scene_of[k[1]].render_nee(W, H, n, BOUNCES, accum=a, seed=SEED, flags=flags)
+                    ctx.synchronize()
+                    dt = time.perf_counter() - t0
+                    if r:
+                        best[k] = min(best[k], dt)
+                    acc[k], launches[k] = a, ctx.timing()["fused_launches"]
+            return best, acc, st, launches
+        best, acc, st, launches = timed(forms, spp)
+        for k, sec in best.items():
+            form, pick, m = k
+            row = dict(scene="lamp_scene", lamps=n_lamps, form=form, pick=pick, M=m, W=W, H=H, bounces=BOUNCES, spp=spp, n_lights=st[k]["n_lights"],
+                       fused_launches=launches[k], s=round(sec, 4), msamples_s=round(W * H * spp / sec / 1e6, 1), rays=st[k]["rays"],
+                       light_samples_per_sample=round(st[k]["light_samples"] / st[k]["samples"], 4),
+                       light_visible_per_sample=round(st[k]["light_visible"] / st[k]["samples"], 4), mse=mse_of(acc[k], spp), ref_spp=ref_spp)
+            if pick == "tree":   # what the CDF call (M = 1, same form) reaches in the tree call's time
+                spp_eq = max(1, int(round(spp * sec / best[(form, "cdf", 1)])))
+                eq_key = (form, "cdf", 1)
+                eq_best, eq_acc, _, _ = timed({eq_key: forms[eq_key]}, spp_eq)
+                row.update(cdf_equal_time_spp=spp_eq, cdf_equal_time_s=round(eq_best[eq_key], 4), cdf_equal_time_mse=mse_of(eq_acc[eq_key], spp_eq))
+            print(json.dumps(row), flush=True)
         s.close()
+        tree.close()
 
 
 def main_motion(reps, spp):
