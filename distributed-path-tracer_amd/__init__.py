@@ -30,7 +30,9 @@ NO_SUN_LIGHT = 0xFFFFFFFF  # core::renderer::no_sun_light, renderer.hpp:19
  ARR_MATERIALS, ARR_KD_NODES, ARR_KD_REFS, ARR_CAMERA, ARR_SUN, ARR_MODEL_NAMES, ARR_TEXTURES, ARR_TEXELS, ARR_SURF_TEX, ARR_TEXELS_F32,
  ARR_LIGHT_TRIS, ARR_LIGHT_CDF, ARR_LIGHT_GEOM, ARR_TRI_ISECT, ARR_RES_NODES, ARR_RES_REFS, ARR_RES_TRIS, ARR_LDS_ROOT,
  ARR_RES_PLAN, ARR_ENV_ROW_CDF, ARR_ENV_CELL_CDF, ARR_PUNCTUAL, ARR_PUNCTUAL_CDF, ARR_LENS, ARR_LDS_SHAPE, ARR_SURF_AUX,
- ARR_MOTION_XFORM, ARR_MOTION_MOVED, ARR_MOTION_CAMERA, ARR_PUNCTUAL_TREE) = range(37)
+ ARR_MOTION_XFORM, ARR_MOTION_MOVED, ARR_MOTION_CAMERA, ARR_PUNCTUAL_TREE, ARR_LIGHT_TREE, ARR_LIGHT_PATH) = range(39)
+LIGHT_PICK_CDF, LIGHT_PICK_TREE = 0, 1   # ptx_light_pick: how a light sample picks its emissive triangle (Scene.set_light_pick)
+_LIGHT_PICK_NAMES = {"cdf": LIGHT_PICK_CDF, "tree": LIGHT_PICK_TREE}
 PUNCTUAL_PICK_CDF, PUNCTUAL_PICK_TREE = 0, 1   # ptx_punctual_pick: how a punctual sample picks its light (Scene.set_punctual_pick)
 LDS_LEAF_ORDER_BIT = 0x80000000  # ARR_LDS_ROOT: the surface's resident records are leaf-ordered (flat_scene.hpp)
 LDS_LEAF_ONLY_BIT = 0x40000000   # ARR_LDS_SHAPE: the surface's resident tree is a single leaf
@@ -261,6 +263,10 @@ def lib():
         L.ptx_scene_set_punctual_pick.argtypes = [C.c_void_p, C.c_uint32]
         L.ptx_scene_get_punctual_pick.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.ptx_punctual_pick_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.ptx_scene_set_light_pick.argtypes = [C.c_void_p, C.c_uint32]
+        L.ptx_scene_get_light_pick.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.ptx_light_pick_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.ptx_light_pmf_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ptx_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
         L.ptx_scene_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
         L.ptx_scene_set_model_xforms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
@@ -599,7 +605,7 @@ _ARR_DTYPE = {ARR_MODEL_XFORM: (np.float32, 12), ARR_MODEL_AABB: (np.float32, 6)
               ARR_PUNCTUAL: (np.float32, 16), ARR_PUNCTUAL_CDF: (np.float32, 1), ARR_LENS: (np.float32, 2),
               ARR_LDS_SHAPE: (np.uint32, 1), ARR_SURF_AUX: (np.uint32, 4),
               ARR_MOTION_XFORM: (np.float32, 12), ARR_MOTION_MOVED: (np.uint32, 1), ARR_MOTION_CAMERA: (np.float32, 1),
-              ARR_PUNCTUAL_TREE: (np.uint32, 8)}
+              ARR_PUNCTUAL_TREE: (np.uint32, 8), ARR_LIGHT_TREE: (np.uint32, 8), ARR_LIGHT_PATH: (np.uint32, 1)}
 
 
 class Scene:
@@ -881,6 +887,41 @@ class Scene:
         _check(lib().ptx_punctual_pick_batch(self.h, a.ctypes.data, len(a), light.ctypes.data, pmf.ctypes.data))
         return light, pmf
 
+    def set_light_pick(self, pick):
+        """ptx_scene_set_light_pick: "cdf" / LIGHT_PICK_CDF (the default: by area alone) or "tree" / LIGHT_PICK_TREE (a light tree over the
+        light list descended from the shading point with importance power / distance^2). The mode outlives the list;
+        array(ARR_LIGHT_TREE) and array(ARR_LIGHT_PATH) are the tree and the path words."""
+        if isinstance(pick, str):
+            if pick not in _LIGHT_PICK_NAMES:
+                raise PtxError(ERR_INVALID, f"set_light_pick: unknown mode {pick!r}")
+            pick = _LIGHT_PICK_NAMES[pick]
+        _check(lib().ptx_scene_set_light_pick(self.h, int(pick)))
+
+    def get_light_pick(self):
+        """ptx_scene_get_light_pick -> "cdf" or "tree"""
+        v = C.c_uint32()
+        _check(lib().ptx_scene_get_light_pick(self.h, C.byref(v)))
+        return "tree" if v.value == LIGHT_PICK_TREE else "cdf"
+
+    def light_pick_batch(self, pos_u):
+        """ptx_light_pick_batch: [n,4] float32 (position, u) -> (light [n] int32, pmf [n] float32): the entry of the light list a triangle
+        sample at the position with draw u picks and its probability, by the device function the integrator inlines, in the scene's mode."""
+        a = np.ascontiguousarray(pos_u, np.float32).reshape(-1, 4)
+        light, pmf = np.zeros(len(a), np.int32), np.zeros(len(a), np.float32)
+        _check(lib().ptx_light_pick_batch(self.h, a.ctypes.data, len(a), light.ctypes.data, pmf.ctypes.data))
+        return light, pmf
+
+    def light_pmf_batch(self, pos, light):
+        """ptx_light_pmf_batch: positions [n,3] float32 and list entries [n] int32 -> pmf [n] float32: the probability with which the pick
+        returns the entry from the position, by the device function the emission weight inlines."""
+        a = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        k = np.ascontiguousarray(light, np.int32).reshape(-1)
+        if len(k) != len(a):
+            raise PtxError(ERR_INVALID, "light_pmf_batch: one entry per position")
+        pmf = np.zeros(len(a), np.float32)
+        _check(lib().ptx_light_pmf_batch(self.h, a.ctypes.data, k.ctypes.data, len(a), pmf.ctypes.data))
+        return pmf
+
     def set_camera(self, origin, basis, yfov, lens_radius=0.0, focus_distance=0.0, blades=0, blade_rotation=0.0):
         """ptx_scene_set_camera: origin [3], basis [9] (columns x, y, z) and yfov as from_arrays' camera [13]; lens_radius > 0 gives a thin
         lens with a polygonal aperture of `blades` corners (0 = 16) focused at focus_distance. No tree is built and nothing is re-uploaded."""
@@ -1107,6 +1148,12 @@ class Renderer:
         if self._scene is None:
             raise PtxError(ERR_INVALID, "set_punctual_pick() before load_gltf()")
         self._scene.set_punctual_pick(pick)
+
+    def set_light_pick(self, pick):
+        """Scene.set_light_pick on the loaded scene: "cdf" or "tree"; the mode outlives the light list."""
+        if self._scene is None:
+            raise PtxError(ERR_INVALID, "set_light_pick() before load_gltf()")
+        self._scene.set_light_pick(pick)
 
     def render_accum(self):
         """Radiance SUMS [H,W,4] of the frame; with transparent_background set, the reference's blended MEANS (colour, alpha) instead

@@ -634,6 +634,62 @@ int ptx_punctual_pick_batch(ptx_scene* sc, const float* pos_u, size_t n, int32_t
 	return PTX_OK;
 }
 
+int ptx_light_pick_batch(ptx_scene* sc, const float* pos_u, size_t n, int32_t* light, float* pmf) {
+	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_light_pick_batch: scene is NULL");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_light_pick_batch: scene was created without a GPU context (no CPU path exists)");
+	if (n && (!pos_u || !light || !pmf)) return set_err(PTX_ERR_INVALID, "ptx_light_pick_batch: NULL argument");
+	if (n > (size_t)0x7FFFFFFF) return set_err(PTX_ERR_INVALID, "ptx_light_pick_batch: batch too large");
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	NeeLights Lt{};
+	if (const int rc = lights_on_device_locked(sc, Lt); rc != PTX_OK) return rc;
+	if (Lt.n == 0) return set_err(PTX_ERR_INVALID, "ptx_light_pick_batch: the scene's light list is empty");
+	if (n == 0) return PTX_OK;
+	const bool dev = is_device_ptr(pos_u);
+	if (dev != is_device_ptr(light) || dev != is_device_ptr(pmf))
+		return set_err(PTX_ERR_INVALID, "ptx_light_pick_batch: pos_u, light and pmf must all be device or all be host memory");
+	Staged s_in, s_light, s_pmf;   // light and pmf share stage_b
+	if (!dev) HIP_TRY(c->stage_b.ensure(n * 8));
+	HIP_TRY(s_in.bind(c, dev, pos_u, n * 16, c->stage_a));
+	HIP_TRY(s_light.bind(c, dev, light, n * 4, c->stage_b, 0, kOutputOnly));
+	HIP_TRY(s_pmf.bind(c, dev, pmf, n * 4, c->stage_b, n * 4, kOutputOnly));
+	HIP_TRY(launch_light_pick(Lt, s_in.as<float>(), n, s_light.as<int32_t>(), s_pmf.as<float>(), c->stream));
+	HIP_TRY(s_light.copy_back(c));
+	HIP_TRY(s_pmf.copy_back(c));
+	if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
+	return PTX_OK;
+}
+
+int ptx_light_pmf_batch(ptx_scene* sc, const float* pos, const int32_t* light, size_t n, float* pmf) {
+	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_light_pmf_batch: scene is NULL");
+	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_light_pmf_batch: scene was created without a GPU context (no CPU path exists)");
+	if (n && (!pos || !light || !pmf)) return set_err(PTX_ERR_INVALID, "ptx_light_pmf_batch: NULL argument");
+	if (n > (size_t)0x7FFFFFFF) return set_err(PTX_ERR_INVALID, "ptx_light_pmf_batch: batch too large");
+	ptx_ctx* c = sc->ctx;
+	std::lock_guard<std::mutex> lk(c->mu);
+	HIP_TRY(hipSetDevice(c->device));
+	NeeLights Lt{};
+	if (const int rc = lights_on_device_locked(sc, Lt); rc != PTX_OK) return rc;
+	if (Lt.n == 0) return set_err(PTX_ERR_INVALID, "ptx_light_pmf_batch: the scene's light list is empty");
+	if (n == 0) return PTX_OK;
+	const bool dev = is_device_ptr(pos);
+	if (dev != is_device_ptr(light) || dev != is_device_ptr(pmf))
+		return set_err(PTX_ERR_INVALID, "ptx_light_pmf_batch: pos, light and pmf must all be device or all be host memory");
+	if (!dev)
+		for (size_t i = 0; i < n; i++)
+			if (light[i] < 0 || (uint32_t)light[i] >= Lt.n) return set_err(PTX_ERR_INVALID, "ptx_light_pmf_batch: light " + std::to_string(i) + " is outside the light list");
+	Staged s_pos, s_light, s_pmf;   // pos and light share stage_a
+	if (!dev) HIP_TRY(c->stage_a.ensure(n * 16));
+	HIP_TRY(s_pos.bind(c, dev, pos, n * 12, c->stage_a));
+	HIP_TRY(s_light.bind(c, dev, light, n * 4, c->stage_a, n * 12));
+	HIP_TRY(s_pmf.bind(c, dev, pmf, n * 4, c->stage_b, 0, kOutputOnly));
+	HIP_TRY(launch_light_pmf(Lt, s_pos.as<float>(), s_light.as<int32_t>(), n, s_pmf.as<float>(), c->stream));
+	HIP_TRY(s_pmf.copy_back(c));
+	if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
+	return PTX_OK;
+}
+
 int ptx_material_eval_batch(ptx_scene* sc, const int32_t* surface, const float* uv, size_t n, float* out) {
 	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_material_eval_batch: scene is NULL");
 	if (!sc->ctx) return set_err(PTX_ERR_NO_DEVICE, "ptx_material_eval_batch: scene was created without a GPU context (no CPU path exists)");

@@ -111,9 +111,11 @@ struct ptx_scene {
 		std::vector<float> cdf, geom;      // [n], [n][4] geometric normal + area
 		std::vector<int32_t> surf_first;   // [n_surfaces] first entry or -1
 		float area = 0;                    // A_total
+		std::vector<uint32_t> tree, path;  // [n_nodes][8], [n] the light tree and each entry's path word (build_light_tree); empty in CDF mode and with an empty list
 	} lights;
+	uint32_t light_pick = PTX_LIGHT_PICK_CDF;   // ptx_scene_set_light_pick; outlives the list, guarded by lights_mu
 	std::mutex lights_mu;   // host-only scenes have no context whose mutex could guard the build
-	DevBuf d_light_tris, d_light_cdf, d_light_geom, d_light_first;
+	DevBuf d_light_tris, d_light_cdf, d_light_geom, d_light_first, d_light_tree, d_light_path;
 	// The sampling table of the environment map (build_env_table, PTX_NEE_ENV_SAMPLES): built at the first request under lights_mu, dropped
 	// by ptx_scene_set_environment. Empty vectors: no map, or a black one. The device copies are made by the first flagged ptx_render_nee.
 	struct EnvTable {
@@ -148,6 +150,9 @@ const ptx_scene::EnvTable* build_env_table(ptx_scene* sc);   // ptx_api.cpp
 // api_render.cpp: the scene's punctual lights as the kernels take them (records, CDF and, in tree mode, the tree), uploaded at the first
 // call after a change; Pn stays empty without lights. The caller holds the context's mutex and has set the device.
 int punctual_on_device_locked(ptx_scene* sc, NeePunctual& Pn);
+// api_render.cpp: the light list as the kernels take it (and, in tree mode, the tree and the path words), built at the first request and
+// uploaded at the first call after a change; Lt stays empty with an empty list. The caller holds the context's mutex and has set the device.
+int lights_on_device_locked(ptx_scene* sc, NeeLights& Lt);
 void srgb_thresholds(float thr[256]);                      // ptx_api.cpp
 // api_batch.cpp: one decision on device buffers (adaptive.hip), its count read back: the stream is synchronised. The caller holds the
 // context's mutex. select_ms: nullptr, or where the HIP-event time of the decision kernels is added.

@@ -802,6 +802,37 @@ int punctual_on_device_locked(ptx_scene* sc, NeePunctual& Pn) {
 	return PTX_OK;
 }
 
+int lights_on_device_locked(ptx_scene* sc, NeeLights& Lt) {
+	ptx_ctx* c = sc->ctx;
+	const ptx_scene::LightList& ll = *build_lights(sc);
+	const uint32_t n_lights = (uint32_t)ll.cdf.size();
+	if (!n_lights) return PTX_OK;
+	if (!ll.tree.empty() && ll.cdf.size() > ((size_t)1 << 30))
+		return set_err(PTX_ERR_UNSUPPORTED, "the light tree (PTX_LIGHT_PICK_TREE) holds at most 2^30 listed triangles: a path word has 32 bits");
+	if (!sc->lights.on_device) {
+		HIP_TRY(sc->d_light_tris.ensure(ll.tris.size() * 4));
+		HIP_TRY(sc->d_light_cdf.ensure(ll.cdf.size() * 4));
+		HIP_TRY(sc->d_light_geom.ensure(ll.geom.size() * 4));
+		HIP_TRY(sc->d_light_first.ensure(ll.surf_first.size() * 4));
+		HIP_TRY(hipMemcpyAsync(sc->d_light_tris.p, ll.tris.data(), ll.tris.size() * 4, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync(sc->d_light_cdf.p, ll.cdf.data(), ll.cdf.size() * 4, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync(sc->d_light_geom.p, ll.geom.data(), ll.geom.size() * 4, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync(sc->d_light_first.p, ll.surf_first.data(), ll.surf_first.size() * 4, hipMemcpyHostToDevice, c->stream));
+		if (!ll.tree.empty()) {   // tree mode: the tree and the path words travel with the list
+			HIP_TRY(sc->d_light_tree.ensure(ll.tree.size() * 4));
+			HIP_TRY(sc->d_light_path.ensure(ll.path.size() * 4));
+			HIP_TRY(hipMemcpyAsync(sc->d_light_tree.p, ll.tree.data(), ll.tree.size() * 4, hipMemcpyHostToDevice, c->stream));
+			HIP_TRY(hipMemcpyAsync(sc->d_light_path.p, ll.path.data(), ll.path.size() * 4, hipMemcpyHostToDevice, c->stream));
+		}
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		sc->lights.on_device = true;
+	}
+	Lt.tris = (const uint2*)sc->d_light_tris.p; Lt.cdf = (const float*)sc->d_light_cdf.p; Lt.geom = (const float4*)sc->d_light_geom.p;
+	Lt.surf_first = (const int32_t*)sc->d_light_first.p; Lt.n = n_lights; Lt.area = ll.area;
+	if (!ll.tree.empty()) { Lt.nodes = (const float4*)sc->d_light_tree.p; Lt.path = (const uint32_t*)sc->d_light_path.p; Lt.n_nodes = (uint32_t)(ll.tree.size() / 8); }
+	return PTX_OK;
+}
+
 namespace {
 
 // What ptx_render_nee's passes read besides the scene: the light list and the environment table on the device, and which form renders.
@@ -842,21 +873,10 @@ int nee_setup_locked(ptx_scene* sc, uint32_t flags, NeeSetup& S) {
 	// time per lane runs (nee_fused_motion.hip). PTX_NEE_FUSED_MOTION without PTX_NEE_FUSED, or without active motion, changes nothing.
 	S.fused = (flags & PTX_NEE_FUSED) != 0 && !use_wavefront(sc) && (!motion_active(sc) || (flags & PTX_NEE_FUSED_MOTION) != 0);
 	if (n_lights && !(flags & PTX_NEE_NO_LIGHT_SAMPLES)) {
-		if (!sc->lights.on_device) {
-			HIP_TRY(sc->d_light_tris.ensure(ll.tris.size() * 4));
-			HIP_TRY(sc->d_light_cdf.ensure(ll.cdf.size() * 4));
-			HIP_TRY(sc->d_light_geom.ensure(ll.geom.size() * 4));
-			HIP_TRY(sc->d_light_first.ensure(ll.surf_first.size() * 4));
-			HIP_TRY(hipMemcpyAsync(sc->d_light_tris.p, ll.tris.data(), ll.tris.size() * 4, hipMemcpyHostToDevice, c->stream));
-			HIP_TRY(hipMemcpyAsync(sc->d_light_cdf.p, ll.cdf.data(), ll.cdf.size() * 4, hipMemcpyHostToDevice, c->stream));
-			HIP_TRY(hipMemcpyAsync(sc->d_light_geom.p, ll.geom.data(), ll.geom.size() * 4, hipMemcpyHostToDevice, c->stream));
-			HIP_TRY(hipMemcpyAsync(sc->d_light_first.p, ll.surf_first.data(), ll.surf_first.size() * 4, hipMemcpyHostToDevice, c->stream));
-			HIP_TRY(hipStreamSynchronize(c->stream));
-			sc->lights.on_device = true;
-		}
-		NeeLights& Lt = S.Lt;
-		Lt.tris = (const uint2*)sc->d_light_tris.p; Lt.cdf = (const float*)sc->d_light_cdf.p; Lt.geom = (const float4*)sc->d_light_geom.p;
-		Lt.surf_first = (const int32_t*)sc->d_light_first.p; Lt.n = n_lights; Lt.area = ll.area;
+		if (const int rc = lights_on_device_locked(sc, S.Lt); rc != PTX_OK) return rc;
+		// Tree mode with a non-empty list under active motion (include/ptx.h: LIGHT PICK, FORMS): k_nee_fused_motion has no tree variants,
+		// so PTX_NEE_FUSED | PTX_NEE_FUSED_MOTION is ignored as PTX_NEE_FUSED alone is, and the unfused form renders the tree
+		if (S.Lt.nodes && motion_active(sc)) S.fused = false;
 	}
 	// PTX_NEE_ENV_SAMPLES: the ENV variants wherever the map has a table; no map or a black one: the call runs exactly as without the flag
 	if (flags & PTX_NEE_ENV_SAMPLES) {
@@ -934,7 +954,7 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 		*stats = ptx_nee_stats{}; c->timing = ptx_kernel_timing{}; c->timing.pipeline = use_wavefront(sc) ? 1u : 0u;
 		stats->n_lights = S.n_lights; stats->light_area = S.light_area;
 	}
-	// The wavefront form's workspace takes 68 words per sample, so by default a pass has 16 Mi samples (8 spp of a 1080p frame, 4.6 GB); at most
+	// The wavefront form's workspace takes 68 words per sample (74 in tree mode: x_prev beside both streams), so by default a pass has 16 Mi samples (8 spp of a 1080p frame, 4.6 GB); at most
 	// 2^30, so that the positions of a round's shadow rays (two per path at most) stay below 2^31. The fused form keeps only the 16-byte
 	// radiance record per sample: ptx_render's pass size and id limit.
 	if (const int rc = f.plan(c, sc, who, subset, S.fused ? 128ull << 20 : 16ull << 20, S.fused ? 0xFFFFFFFFull : 0x3FFFFFFFull); rc != PTX_OK || !f.n_pass) return rc;
@@ -947,9 +967,11 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 	uint32_t* cnt = nullptr;
 	float4* Lrec = nullptr;
 	NeeStream st[2];
+	NeePrev prev[2] = {};
 	float *hits = nullptr, *shits = nullptr;
 	NeeShadow W{};
 	const RenderMotion Rm = render_motion(sc);
+	const bool tree = Lt.n != 0 && Lt.nodes != nullptr;   // the LTREE variants run: the streams carry x_prev
 	float* times = nullptr;   // under motion of a model: the time of each path ray of the round, in stream order; the shadow rays' are W.tm
 	auto carve = [&](void* base) {
 		Carver k(base);
@@ -961,6 +983,8 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 			s.tx = k.take<float>(cap); s.ty = k.take<float>(cap); s.tz = k.take<float>(cap); s.pp = k.take<float>(cap);
 			s.id = k.take<uint32_t>(cap); s.dp = k.take<uint32_t>(cap);
 		}
+		for (NeePrev& x : prev)   // x_prev beside each stream: tree mode alone
+			if (tree) { x.px = k.take<float>(cap); x.py = k.take<float>(cap); x.pz = k.take<float>(cap); }
 		hits = k.take<float>(6 * cap);
 		W.ox = k.take<float>(2 * cap); W.oy = k.take<float>(2 * cap); W.oz = k.take<float>(2 * cap);
 		W.dx = k.take<float>(2 * cap); W.dy = k.take<float>(2 * cap); W.dz = k.take<float>(2 * cap);
@@ -1003,7 +1027,7 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 			rays += live;
 			const NeeHits H{A.distance, A.surface, A.triangle, A.b1, A.b2};
 			HIP_TRY(hipMemsetAsync(cnt, 0, 8, c->stream));
-			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, Ev, S.Pn, S.sampler_pdf, S.candidates, in, H, live, out, W, cnt, Lrec, Rm, c->stream));
+			HIP_TRY(launch_nee_shade(sc->dev, P, Lt, Ev, S.Pn, S.sampler_pdf, S.candidates, in, H, live, out, W, cnt, Lrec, Rm, prev[round & 1u], prev[(round + 1u) & 1u], c->stream));
 			uint32_t got[2] = {0, 0};   // continuations, shadow rays
 			HIP_TRY(hipMemcpyAsync(got, cnt, 8, hipMemcpyDeviceToHost, c->stream));
 			HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1017,7 +1041,7 @@ int nee_frame_locked(ptx_scene* sc, const ptx_render_cfg* cfg, const char* who, 
 				if (const int rc = intersect_device(c, sc, B); rc != PTX_OK) return rc;
 				rays += got[1];
 				const NeeHits SH{B.distance, B.surface, B.triangle, B.b1, B.b2};
-				HIP_TRY(launch_nee_settle(in, live, W, SH, out, cnt, Lrec, S.Pn.n != 0, c->stream));
+				HIP_TRY(launch_nee_settle(in, live, W, SH, out, cnt, Lrec, S.Pn.n != 0, prev[round & 1u], prev[(round + 1u) & 1u], c->stream));
 				if (catchers) {
 					HIP_TRY(hipMemcpyAsync(got, cnt, 4, hipMemcpyDeviceToHost, c->stream));
 					HIP_TRY(hipStreamSynchronize(c->stream));

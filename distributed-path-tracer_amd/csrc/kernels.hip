@@ -19,7 +19,7 @@
 #include <type_traits>
 
 #include "device_core.hpp"
-#include "nee_core.hpp"   // punctual_pick, for k_punctual_pick
+#include "nee_core.hpp"   // punctual_pick, for k_punctual_pick; light_pick and light_pmf, for k_light_pick and k_light_pmf
 
 namespace ptx {
 
@@ -805,6 +805,27 @@ __global__ void k_punctual_pick(NeePunctual Pn, const float* __restrict__ pos_u,
 	pmf[i] = p;
 }
 
+// ------------------------------------------------------------------------------------ batch light picks
+// Which entry of the light list a triangle sample at position x with draw u picks, and its pmf: light_pick exactly as nee_candidate inlines
+// it in the scene's mode, one (x, u) per lane (ptx_light_pick_batch). In CDF mode (Lt.nodes == nullptr) the position is not read.
+__global__ void k_light_pick(NeeLights Lt, const float* __restrict__ pos_u, size_t n, int32_t* __restrict__ light, float* __restrict__ pmf) {
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float* q = pos_u + 4 * i;
+	float p;
+	light[i] = (int32_t)light_pick(Lt, mk(q[0], q[1], q[2]), q[3], p);
+	pmf[i] = p;
+}
+// pmf_k(x) of a given entry: light_pmf exactly as the emission weight inlines it, one (x, k) per lane (ptx_light_pmf_batch). An entry
+// outside the list reads nothing and gives 0.
+__global__ void k_light_pmf(NeeLights Lt, const float* __restrict__ pos, const int32_t* __restrict__ light, size_t n, float* __restrict__ pmf) {
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const int32_t k = light[i];
+	const float* q = pos + 3 * i;
+	pmf[i] = (k >= 0 && (uint32_t)k < Lt.n) ? light_pmf(Lt, (uint32_t)k, mk(q[0], q[1], q[2])) : 0.0f;
+}
+
 // ------------------------------------------------------------------------------------ tonemap + encode
 // core::tonemap_approx_aces (core/utils.hpp:29-36) + image::image::write (image/image.cpp:143-154)
 DEV float aces1(float x) {
@@ -944,6 +965,14 @@ hipError_t launch_material_eval(const DevScene& S, const int32_t* surface, const
 }
 hipError_t launch_punctual_pick(const NeePunctual& Pn, const float* pos_u, size_t n, int32_t* light, float* pmf, hipStream_t stream) {
 	hipLaunchKernelGGL(k_punctual_pick, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, Pn, pos_u, n, light, pmf);
+	return hipGetLastError();
+}
+hipError_t launch_light_pick(const NeeLights& Lt, const float* pos_u, size_t n, int32_t* light, float* pmf, hipStream_t stream) {
+	hipLaunchKernelGGL(k_light_pick, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, Lt, pos_u, n, light, pmf);
+	return hipGetLastError();
+}
+hipError_t launch_light_pmf(const NeeLights& Lt, const float* pos, const int32_t* light, size_t n, float* pmf, hipStream_t stream) {
+	hipLaunchKernelGGL(k_light_pmf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, Lt, pos, light, n, pmf);
 	return hipGetLastError();
 }
 hipError_t launch_tonemap(const float4* accum, uint32_t n_pixels, float spp, const float* thresholds, uchar4* out, hipStream_t stream) {

@@ -260,6 +260,12 @@ struct NeeStream {   // path state, SoA, `cap` entries per array; the six ray ar
 	uint32_t* id;          // the sample's id within the pass (sample-major, pixel-minor)
 	uint32_t* dp;          // depth << 16 | pass
 };
+// x_prev of a stream's entries, the position of the vertex that drew the BSDF sample: three arrays beside a NeeStream's, allocated, written
+// and read in tree mode only (PTX_LIGHT_PICK_TREE; else all nullptr). A struct of its own, the kernels' last argument, so that the
+// arguments of the kernels that never read it stay where they were.
+struct NeePrev {
+	float *px, *py, *pz;
+};
 struct NeeHits {   // what an intersect launch wrote
 	const float* distance;
 	const int32_t *surface, *triangle;   // -1 = miss; triangle index within the surface's mesh
@@ -281,7 +287,16 @@ struct NeeLights {   // the scene's light list (ptx_api.cpp: build_lights); n ==
 	const int32_t* surf_first;   // [n_surfaces] first entry of the surface, or -1
 	uint32_t n;
 	float area;                  // A_total
+	// The light tree of PTX_LIGHT_PICK_TREE (ptx_api.cpp: build_light_tree). nodes == nullptr: CDF mode. A node is two float4:
+	// (lo.xyz, power) (hi.xyz, word 7), word 7 = 0x80000000 | entry for a leaf, else the left child's index; the right child is the next node.
+	const float4* nodes;
+	const uint32_t* path;        // [n] bit i = step i of the descent to the entry's leaf goes right
+	uint32_t n_nodes;
 };
+// the stochastic pick alone, one (position, u) per lane (ptx_light_pick_batch), and the directed pmf of a given entry, one (position, entry)
+// per lane (ptx_light_pmf_batch): the device functions nee_candidate and nee_vertex inline
+hipError_t launch_light_pick(const NeeLights& Lt, const float* pos_u /* [n][4] */, size_t n, int32_t* light, float* pmf, hipStream_t stream);
+hipError_t launch_light_pmf(const NeeLights& Lt, const float* pos /* [n][3] */, const int32_t* light, size_t n, float* pmf, hipStream_t stream);
 // The environment map's sampling table (ptx_api.cpp: build_env_table), PTX_NEE_ENV_SAMPLES. row_cdf == nullptr: no table, the unflagged estimator
 struct NeeEnv {
 	const float* row_cdf;    // [h] cumulative share of the rows' mass, top row first, the last entry 1
@@ -309,8 +324,9 @@ hipError_t launch_nee_generate(const DevScene& S, const RenderParams& P, const N
 // candidates: M of PTX_NEE_CANDIDATES, 1 .. 16; above 1 the RIS variants run (nee_core.hpp: the candidate loop of nee_vertex)
 // Pn.n != 0: the PUN variants run (part 1 of nee.hip), and launch_nee_settle is told so: its punctual form knows kNeePunctualRay
 hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
-                            const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, hipStream_t stream);
-hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, bool punctual, hipStream_t stream);
+                            const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, const NeePrev& in_prev, const NeePrev& out_prev,
+                            hipStream_t stream);
+hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, bool punctual, const NeePrev& in_prev, const NeePrev& out_prev, hipStream_t stream);   // in_prev.px != nullptr: tree mode
 
 // The same estimator in one launch per pass (nee_fused.hip, PTX_NEE_FUSED): persistent workgroups as launch_render_pass sizes them, a lane per path,
 // no streams. The only per-sample memory is sample_rad.

@@ -17,15 +17,15 @@ namespace ptx {
 
 constexpr int kNeeBlock = 256;
 
-// This file is compiled twice, with -DPTX_NEE_PART=0 and 1, so that the two halves of k_nee_shade's variants build side by side. Here a part
-// is the PUN bit of the mask alone (nee_core.hpp), 48 kernels each: part 0 is everything but the PUN variants, part 1 the PUN variants and
-// launch_nee_shade_part<1> alone.
+// This file is compiled four times, with -DPTX_NEE_PART=0 .. 3, so that the quarters of k_nee_shade's variants build side by side. Here a part
+// is the PUN and LTREE bits of the mask (nee_core.hpp), 48 kernels each: part 0 is everything without either, part 1 the PUN variants, parts
+// 2 and 3 the tree variants (kNeeTreeVariants) without and with PUN; parts 1 to 3 hold launch_nee_shade_part<part> alone.
 #ifndef PTX_NEE_PART
-#error "nee.hip is compiled once per half of the variants: -DPTX_NEE_PART=<0..1> (the Makefile's NEE_SHADE_PARTS)"
+#error "nee.hip is compiled once per quarter of the variants: -DPTX_NEE_PART=<0..3> (the Makefile's NEE_SHADE_PARTS)"
 #endif
-static_assert(PTX_NEE_PART == 0 || PTX_NEE_PART == 1, "a part of this file is the PUN bit of a variant");
+static_assert(PTX_NEE_PART >= 0 && PTX_NEE_PART <= 3, "a part of this file is the PUN and LTREE bits of a variant");
 constexpr uint32_t kNeeShadePartShift = 6, kNeeShadePartMask = (1u << kNeeShadePartShift) - 1;
-static_assert(NEE_PUN == 1u << kNeeShadePartShift, "the two parts are split by PUN");
+static_assert(NEE_PUN == 1u << kNeeShadePartShift && NEE_LTREE == 2u << kNeeShadePartShift, "the four parts are split by PUN and LTREE");
 
 #if PTX_NEE_PART == 0
 __global__ void __launch_bounds__(kNeeBlock) k_nee_generate(DevScene S0, RenderParams P, NeeStream out, float4* __restrict__ L, uint32_t n, RenderMotion Mo) {
@@ -61,16 +61,19 @@ DEV void nee_append2(bool first, bool second, uint32_t* counter, uint32_t& pos_f
 }
 
 // One vertex of every live path: loads the hit and the path state of entry i, runs nee_vertex (nee_core.hpp) and stores what it returns.
-// V: the variant (nee_core.hpp has the bits). Ev is read by the ENV variants alone, ris_m by the RIS variants, Pn by the PUN variants.
+// V: the variant (nee_core.hpp has the bits). Ev is read by the ENV variants alone, ris_m by the RIS variants, Pn by the PUN variants; the
+// LTREE variants alone read and write the streams' x_prev arrays (Xi beside `in`, Xo beside `out`).
 template <uint32_t V>
 __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParams P, NeeLights Lt, NeeStream in, NeeHits H, uint32_t n, NeeStream out, NeeShadow W,
-                                                         uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeeEnv Ev, uint32_t ris_m, NeePunctual Pn, RenderMotion Mo) {
+                                                         uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeeEnv Ev, uint32_t ris_m, NeePunctual Pn, RenderMotion Mo, NeePrev Xi, NeePrev Xo) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
 	NeeVertex v;
 	float u = 0;   // the path's time; computed under active motion alone
 	V3 o = {0, 0, 0}, d = {0, 0, 1}, T = {1, 1, 1};
 	float p_prev = 0;
 	uint32_t id = 0, depth = 0, pass = 0;
+	constexpr bool LTREE = (V & NEE_LTREE) != 0;
+	V3 x_prev = {0, 0, 0};
 	if (i < n) {
 		id = in.id[i];
 		const uint32_t dp = in.dp[i];
@@ -78,6 +81,8 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 		d = mk(in.dx[i], in.dy[i], in.dz[i]);
 		T = mk(in.tx[i], in.ty[i], in.tz[i]);
 		p_prev = in.pp[i];
+		if constexpr (LTREE)
+			if (depth != 0) x_prev = mk(Xi.px[i], Xi.py[i], Xi.pz[i]);   // set by the vertex that drew the BSDF sample; none has at depth 0
 		uint32_t px, py, sample;
 		nee_sample_of(P, id, px, py, sample);
 		const uint32_t pixel = py * P.W + px;
@@ -94,7 +99,7 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 				if (moved) model_records_at(Mo.models, m, u, Xm);   // the hit surface's records at the path's time
 			}
 		}
-		if (nee_vertex<V>(S, P, Lt, Ev, ris_m, pixel, sample, surf, (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v, Pn, moved, Xm))
+		if (nee_vertex<V>(S, P, Lt, Ev, ris_m, pixel, sample, surf, (uint32_t)H.triangle[i], H.b1[i], H.b2[i], H.distance[i], o, d, T, L, p_prev, depth, pass, v, Pn, moved, Xm, LTREE ? &x_prev : nullptr))
 			Lrec[id] = make_float4(L.x, L.y, L.z, l4.w);
 	}
 	// shadow rays of the round: at most two per path, so every position is below twice the round's paths
@@ -127,14 +132,16 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_shade(DevScene S, RenderParam
 		out.dx[pos] = d.x; out.dy[pos] = d.y; out.dz[pos] = d.z;
 		out.tx[pos] = T.x; out.ty[pos] = T.y; out.tz[pos] = T.z; out.pp[pos] = p_prev;
 		out.id[pos] = id; out.dp[pos] = (depth << 16) | pass;
+		if constexpr (LTREE) { Xo.px[pos] = x_prev.x; Xo.py[pos] = x_prev.y; Xo.pz[pos] = x_prev.z; }
 	}
 }
 
 #if PTX_NEE_PART == 0
 // The answers of the round's shadow rays (SH: their closest hits). One lane per path of the round, sun before light.
 // PUN: the round may hold punctual samples' rays (kNeePunctualRay): visible iff nothing is hit nearer than the light.
-template <bool PUN>
-__global__ void __launch_bounds__(kNeeBlock) k_nee_settle(NeeStream in, uint32_t n, NeeShadow W, NeeHits SH, NeeStream out, uint32_t* __restrict__ cnt, float4* __restrict__ Lrec) {
+// LTREE: the streams carry x_prev (Xi, Xo), and a lit catcher's pass-through writes its entry of Xo.
+template <bool PUN, bool LTREE>
+__global__ void __launch_bounds__(kNeeBlock) k_nee_settle(NeeStream in, uint32_t n, NeeShadow W, NeeHits SH, NeeStream out, uint32_t* __restrict__ cnt, float4* __restrict__ Lrec, NeePrev Xi, NeePrev Xo) {
 	const uint32_t i = blockIdx.x * kNeeBlock + threadIdx.x;
 	bool through = false, visible = false;
 	if (i < n) {
@@ -168,6 +175,8 @@ __global__ void __launch_bounds__(kNeeBlock) k_nee_settle(NeeStream in, uint32_t
 		out.dx[pos] = dn.x; out.dy[pos] = dn.y; out.dz[pos] = dn.z;
 		out.tx[pos] = in.tx[i]; out.ty[pos] = in.ty[i]; out.tz[pos] = in.tz[i]; out.pp[pos] = in.pp[i];
 		out.id[pos] = in.id[i]; out.dp[pos] = in.dp[i] + 1u;
+		// a catcher is a depth-0 vertex, where no vertex has set x_prev yet and k_nee_shade does not read it: the entry's x_prev is 0
+		if constexpr (LTREE) { Xo.px[pos] = 0.0f; Xo.py[pos] = 0.0f; Xo.pz[pos] = 0.0f; }
 	}
 }
 
@@ -189,7 +198,7 @@ template <size_t... I>
 static NeeShadeTable nee_shade_table(std::index_sequence<I...>) {
 	NeeShadeTable t{};
 	([&] {
-		constexpr uint32_t V = kNeeVariants.v[I];
+		constexpr uint32_t V = (PTX_NEE_PART >= 2 ? kNeeTreeVariants : kNeeVariants).v[I];
 		if constexpr ((V >> kNeeShadePartShift) == PTX_NEE_PART) t.fn[V & kNeeShadePartMask] = &k_nee_shade<V>;
 	}(), ...);
 	return t;
@@ -199,31 +208,38 @@ static NeeShadeTable nee_shade_table(std::index_sequence<I...>) {
 // (nee_fused.hip has the reason): the linker puts the two together.
 template <uint32_t PART>
 hipError_t launch_nee_shade_part(uint32_t V, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeStream& in, const NeeHits& H,
-                                 uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, hipStream_t stream);
+                                 uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, const NeePrev& Xi, const NeePrev& Xo, hipStream_t stream);
 template <>
 hipError_t launch_nee_shade_part<PTX_NEE_PART>(uint32_t V, const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, uint32_t ris_m, const NeeStream& in,
-                                               const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, hipStream_t stream) {
+                                               const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, const NeePrev& Xi, const NeePrev& Xo,
+                                               hipStream_t stream) {
 	static const NeeShadeTable table = nee_shade_table(std::make_index_sequence<kNeeVariantCount>{});
 	const NeeShadeKernel kernel = table.fn[V & kNeeShadePartMask];
 	if (!kernel) return hipErrorInvalidValue;
-	hipLaunchKernelGGL(kernel, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m, Pn, Mo);
+	hipLaunchKernelGGL(kernel, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, S, P, Lt, in, H, n, out, W, cnt, L, Ev, ris_m, Pn, Mo, Xi, Xo);
 	return hipGetLastError();
 }
 
 #if PTX_NEE_PART == 0
 // the variant: nee_select_variant (nee_core.hpp), as for launch_nee_fused
 hipError_t launch_nee_shade(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeStream& in,
-                            const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, hipStream_t stream) {
+                            const NeeHits& H, uint32_t n, const NeeStream& out, const NeeShadow& W, uint32_t* cnt, float4* L, const RenderMotion& Mo, const NeePrev& Xi, const NeePrev& Xo,
+                            hipStream_t stream) {
 	uint32_t V, ris_m;
-	const hipError_t e = nee_select_variant(S, Ev, Pn, sampler_pdf, candidates, V, ris_m);
+	const hipError_t e = nee_select_variant(S, Lt, Ev, Pn, sampler_pdf, candidates, V, ris_m);
 	if (e != hipSuccess) return e;
-	const auto part = (V >> kNeeShadePartShift) ? launch_nee_shade_part<1> : launch_nee_shade_part<0>;
-	return part(V, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L, Mo, stream);
+	static constexpr decltype(&launch_nee_shade_part<0>) parts[] = {&launch_nee_shade_part<0>, &launch_nee_shade_part<1>, &launch_nee_shade_part<2>, &launch_nee_shade_part<3>};
+	const auto part = parts[V >> kNeeShadePartShift];
+	return part(V, S, P, Lt, Ev, Pn, ris_m, in, H, n, out, W, cnt, L, Mo, Xi, Xo, stream);
 }
 
-hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, bool punctual, hipStream_t stream) {
-	if (punctual) hipLaunchKernelGGL(k_nee_settle<true>, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, in, n, W, SH, out, cnt, L);
-	else hipLaunchKernelGGL(k_nee_settle<false>, dim3((n + kNeeBlock - 1) / kNeeBlock), dim3(kNeeBlock), 0, stream, in, n, W, SH, out, cnt, L);
+hipError_t launch_nee_settle(const NeeStream& in, uint32_t n, const NeeShadow& W, const NeeHits& SH, const NeeStream& out, uint32_t* cnt, float4* L, bool punctual, const NeePrev& Xi, const NeePrev& Xo, hipStream_t stream) {
+	const dim3 grid((n + kNeeBlock - 1) / kNeeBlock), block(kNeeBlock);
+	const bool tree = Xi.px != nullptr;
+	if (tree && punctual) hipLaunchKernelGGL((k_nee_settle<true, true>), grid, block, 0, stream, in, n, W, SH, out, cnt, L, Xi, Xo);
+	else if (tree) hipLaunchKernelGGL((k_nee_settle<false, true>), grid, block, 0, stream, in, n, W, SH, out, cnt, L, Xi, Xo);
+	else if (punctual) hipLaunchKernelGGL((k_nee_settle<true, false>), grid, block, 0, stream, in, n, W, SH, out, cnt, L, Xi, Xo);
+	else hipLaunchKernelGGL((k_nee_settle<false, false>), grid, block, 0, stream, in, n, W, SH, out, cnt, L, Xi, Xo);
 	return hipGetLastError();
 }
 #endif

@@ -13,7 +13,10 @@ namespace ptx {
 // render variants do; ENV the environment sample (PTX_NEE_ENV_SAMPLES with a table; TEX only: a map implies the TEX variants).
 // High three bits, the PART (V >> kNeePartShift): SPDF the weights of PTX_NEE_SAMPLER_PDF, RIS the light sample chosen among ris_m candidates
 // (PTX_NEE_CANDIDATES), PUN punctual lights on the scene. nee_fused.hip is compiled once per part.
-enum : uint32_t { NEE_TEX = 1u, NEE_ALPHA = 2u, NEE_SUN = 4u, NEE_ENV = 8u, NEE_SPDF = 16u, NEE_RIS = 32u, NEE_PUN = 64u };
+// One more PART bit, LTREE: a non-empty light list in tree mode (PTX_LIGHT_PICK_TREE): the triangle of a light sample comes from the light
+// tree, and the path carries x_prev. k_nee_shade (nee.hip) and k_nee_fused (nee_fused.hip) have such variants, k_nee_fused_motion has
+// none; they stand in a second list, kNeeTreeVariants.
+enum : uint32_t { NEE_TEX = 1u, NEE_ALPHA = 2u, NEE_SUN = 4u, NEE_ENV = 8u, NEE_SPDF = 16u, NEE_RIS = 32u, NEE_PUN = 64u, NEE_LTREE = 128u };
 constexpr uint32_t kNeePartShift = 4, kNeeSceneMask = (1u << kNeePartShift) - 1, kNeeParts = 8;
 
 // The variants that exist, as data: every mask but those with ENV and without TEX, ascending, so 12 per part. The launchers' tables are built
@@ -40,12 +43,20 @@ constexpr bool nee_all_variants(Pred pred) {
 constexpr bool nee_env_has_tex(uint32_t v) { return !(v & NEE_ENV) || (v & NEE_TEX); }
 static_assert(kNeeVariants.n == kNeeVariantCount, "96 variants: 12 scene masks in each of the 8 parts");
 static_assert(nee_all_variants(nee_env_has_tex), "ENV reads the map through the TEX code");
+// The tree variants, a second list beside the first: every entry of kNeeVariants with LTREE set, in its order
+constexpr NeeVariantList nee_tree_variant_list() {
+	NeeVariantList l = nee_variant_list();
+	for (uint32_t i = 0; i < kNeeVariantCount; i++) l.v[i] |= NEE_LTREE;
+	return l;
+}
+constexpr NeeVariantList kNeeTreeVariants = nee_tree_variant_list();
 
 // The one rule from a scene and a call to a variant, for both forms. A table (Ev) means a map, and a map means the ENV variants, which are TEX
 // variants: a scene without textures or without an environment texture cannot have one. sampler_pdf: SPDF. candidates > 1: RIS with
 // M = candidates; ris_m is what the kernel receives. Pn.n != 0: PUN.
-inline hipError_t nee_select_variant(const DevScene& S, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, uint32_t& V, uint32_t& ris_m) {
-	V = (S.any_texture ? NEE_TEX : 0u) | (S.any_alpha ? NEE_ALPHA : 0u) | (S.sun.present != 0 ? NEE_SUN : 0u) | (sampler_pdf ? NEE_SPDF : 0u) | (candidates > 1 ? NEE_RIS : 0u) | (Pn.n != 0 ? NEE_PUN : 0u);
+// Lt.n != 0 with a tree (Lt.nodes): LTREE (launch_nee_fused_motion has no kernel for it and refuses the mask).
+inline hipError_t nee_select_variant(const DevScene& S, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, uint32_t& V, uint32_t& ris_m) {
+	V = ((Lt.n != 0 && Lt.nodes != nullptr) ? NEE_LTREE : 0u) | (S.any_texture ? NEE_TEX : 0u) | (S.any_alpha ? NEE_ALPHA : 0u) | (S.sun.present != 0 ? NEE_SUN : 0u) | (sampler_pdf ? NEE_SPDF : 0u) | (candidates > 1 ? NEE_RIS : 0u) | (Pn.n != 0 ? NEE_PUN : 0u);
 	ris_m = candidates > 1 ? candidates : 1u;
 	if (Ev.row_cdf) {
 		if (!S.any_texture || S.env_tex < 0) return hipErrorInvalidValue;
@@ -203,6 +214,90 @@ DEV uint32_t punctual_pick(const NeePunctual& Pn, V3 x, float u, float& pmf) {
 	return k;
 }
 
+// ---- the light tree over the light list (include/ptx.h: LIGHT PICK)
+constexpr uint32_t kLightLeaf = 0x80000000u;   // word 7 of a tree node: a leaf, the list entry in the low bits
+// importance of the node (n0, n1) seen from x, one formula for leaves and branches: power / max(squared distance to the box's centre,
+// squared half diagonal)
+DEV float light_importance(float4 n0, float4 n1, V3 x) {
+	const V3 lo = mk(n0.x, n0.y, n0.z), hi = mk(n1.x, n1.y, n1.z);
+	const V3 c = (lo + hi) * 0.5F, d = x - c, h = (hi - lo) * 0.5F;
+	return n0.w / pmax(dot(d, d), dot(h, h));
+}
+// The probability p of going left at the branch whose left child is node `left`, seen from x; wl, wr: word 7 of the two children (adjacent
+// nodes: one 64-byte read). Shared by the stochastic pick and the directed pmf, so that the two multiply the same numbers.
+DEV float light_branch_p(const NeeLights& Lt, uint32_t left, V3 x, uint32_t& wl, uint32_t& wr) {
+	const float4* __restrict__ ch = Lt.nodes + 2 * (size_t)left;
+	const float4 l0 = ch[0], l1 = ch[1], r0 = ch[2], r1 = ch[3];
+	const float il = light_importance(l0, l1, x), ir = light_importance(r0, r1, x);
+	const float s = il + ir;
+	wl = __float_as_uint(l1.w); wr = __float_as_uint(r1.w);
+	return (s > 0 && s < __builtin_inff()) ? il / s : 0.5F;
+}
+// The stochastic descent from the root (punctual_pick_tree's loop): -> the leaf's list entry; pmf: the product of the branch probabilities
+// as the descent realised them. The tree is balanced by count, so the trip counts of a wave's lanes differ by one at most.
+DEV uint32_t light_pick_tree(const NeeLights& Lt, V3 x, float u, float& pmf) {
+	pmf = 1.0f;
+	uint32_t w7 = __float_as_uint(Lt.nodes[1].w);
+	while (!(w7 & kLightLeaf)) {
+		uint32_t wl, wr;
+		const float p = light_branch_p(Lt, w7, x, wl, wr);
+		if (u < p) {
+			pmf = pmf * p;
+			u = u / p;
+			w7 = wl;
+		} else {
+			const float q1 = 1 - p;
+			pmf = pmf * q1;
+			u = (u - p) / q1;
+			w7 = wr;
+		}
+		u = pmin(u, 0x1.fffffep-1F);
+	}
+	return w7 & ~kLightLeaf;
+}
+// pmf_k(x): the same loop from the root, taking at step i the side bit i of path[k] names and multiplying the same p or 1 - p in the same
+// order: bit for bit the pmf light_pick_tree returns whenever it returns k
+DEV float light_pmf_tree(const NeeLights& Lt, uint32_t k, V3 x) {
+	float pmf = 1.0f;
+	uint32_t word = Lt.path[k];
+	uint32_t w7 = __float_as_uint(Lt.nodes[1].w);
+	while (!(w7 & kLightLeaf)) {
+		uint32_t wl, wr;
+		const float p = light_branch_p(Lt, w7, x, wl, wr);
+		if (!(word & 1u)) {
+			pmf = pmf * p;
+			w7 = wl;
+		} else {
+			const float q1 = 1 - p;
+			pmf = pmf * q1;
+			w7 = wr;
+		}
+		word >>= 1;
+	}
+	return pmf;
+}
+// first entry of the list's CDF with u below it, clamped to the last: the CDF mode's pick
+DEV uint32_t light_pick_cdf(const NeeLights& Lt, float u) {
+	uint32_t a = 0, b = Lt.n;
+	while (a < b) {
+		const uint32_t mid = a + (b - a) / 2;
+		if (u < Lt.cdf[mid]) b = mid; else a = mid + 1;
+	}
+	return a < Lt.n - 1 ? a : Lt.n - 1;
+}
+// The pick and the directed pmf in the scene's mode (the batch calls): the tree's when the scene has one, else the CDF's with the
+// difference of the STORED entries
+DEV uint32_t light_pick(const NeeLights& Lt, V3 x, float u, float& pmf) {
+	if (Lt.nodes) return light_pick_tree(Lt, x, u, pmf);
+	const uint32_t k = light_pick_cdf(Lt, u);
+	pmf = Lt.cdf[k] - (k ? Lt.cdf[k - 1] : 0.0f);
+	return k;
+}
+DEV float light_pmf(const NeeLights& Lt, uint32_t k, V3 x) {
+	if (Lt.nodes) return light_pmf_tree(Lt, k, x);
+	return Lt.cdf[k] - (k ? Lt.cdf[k - 1] : 0.0f);
+}
+
 // What a vertex leaves besides the path state: whether the path goes on, and its up-to-two shadow requests
 struct NeeVertex {
 	bool alive = false;         // the path continues with (o, d, T, p_prev, depth, pass) as the vertex left them
@@ -221,11 +316,13 @@ struct NeeVertex {
 // PUN (punctual lights on the scene, Pn; include/ptx.h: PUNCTUAL LIGHTS): the candidate is a punctual sample with probability c_p, drawn from
 // block_pun, and the other strategies' densities carry (1 - c_p). Without PUN, Pn, c_p and block_pun are not read and no statement changes.
 // Its light and pmf come from punctual_pick: the CDF's, or with a light tree on the scene (Pn.nodes) the descent from the vertex's position.
+// LTREE (a non-empty list in tree mode; include/ptx.h: LIGHT PICK): the triangle and pmf_i come from light_pick_tree at the vertex's position,
+// and p_l is (pmf_i * dist2) / (cg * A_i). Without LTREE the tree is not read and no statement changes.
 template <uint32_t V>
 DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, float c_env, uint32_t pixel, uint32_t sample, uint32_t depth, uint32_t pass,
                        uint32_t block_light, uint32_t block_env, const Surf& sf, V3 normal, V3 outcoming, V3 T, const MatEval& me, float roughness, float spec_prob, V3& lx, V3& lo, V3& ld,
                        uint32_t& exp_surf, uint32_t& exp_tri, bool& want, const NeePunctual& Pn = NeePunctual{}, float c_p = 0.0f, uint32_t block_pun = 0u) {
-	constexpr bool TEX = (V & NEE_TEX) != 0, ENV = (V & NEE_ENV) != 0, SPDF = (V & NEE_SPDF) != 0, PUN = (V & NEE_PUN) != 0;   // ALPHA, SUN and RIS are not read here
+	constexpr bool TEX = (V & NEE_TEX) != 0, ENV = (V & NEE_ENV) != 0, SPDF = (V & NEE_SPDF) != 0, PUN = (V & NEE_PUN) != 0, LTREE = (V & NEE_LTREE) != 0;   // ALPHA, SUN and RIS are not read here
 	if constexpr (PUN) {
 		const float4 q = draws(P, pixel, sample, depth, pass, block_pun);
 		if (c_p == 1.0F || q.x < 0.5F) {
@@ -296,12 +393,18 @@ DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights
 	}
 	if (Lt.n != 0 && !to_env) {
 		const float4 r = draws(P, pixel, sample, depth, pass, block_light);
-		uint32_t a = 0, b = Lt.n;   // first entry with r.x < cdf
-		while (a < b) {
-			const uint32_t mid = a + (b - a) / 2;
-			if (r.x < Lt.cdf[mid]) b = mid; else a = mid + 1;
+		uint32_t k;
+		float pmf_i = 1.0f;
+		if constexpr (LTREE) {
+			k = light_pick_tree(Lt, sf.pos, r.x, pmf_i);
+		} else {
+			uint32_t a = 0, b = Lt.n;   // first entry with r.x < cdf
+			while (a < b) {
+				const uint32_t mid = a + (b - a) / 2;
+				if (r.x < Lt.cdf[mid]) b = mid; else a = mid + 1;
+			}
+			k = a < Lt.n - 1 ? a : Lt.n - 1;
 		}
-		const uint32_t k = a < Lt.n - 1 ? a : Lt.n - 1;
 		const float su = sqrt_exact(r.y), beta = su * (1 - r.z), gamma = su * r.z;
 		const uint2 lt = Lt.tris[k];
 		const ShadeRec& Ry = S.shade[lt.x];
@@ -315,13 +418,15 @@ DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights
 			const V3 w = v / sqrt_exact(dist2);
 			const float4 g = Lt.geom[k];
 			const float cg = fabsf(dot(mk(g.x, g.y, g.z), w));
-			if (dot(normal, w) > 0 && dot(n_y, -w) > 0 && cg > 0 && pmax(Le.x, pmax(Le.y, Le.z)) > 0) {
+			if (dot(normal, w) > 0 && dot(n_y, -w) > 0 && cg > 0 && pmax(Le.x, pmax(Le.y, Le.z)) > 0 && (!LTREE || pmf_i > 0)) {
 				float pdf;
 				const V3 brdf = eval_brdf(normal, outcoming, w, me.albedo, roughness, me.metallic, spec_prob, pdf);
 				const float pe = pmax(pdf, kEps);
 				const V3 q = brdf / pe;
 				const V3 qc = mk(clampf(q.x, 0, 1), clampf(q.y, 0, 1), clampf(q.z, 0, 1));
-				float p_l = dist2 / (cg * Lt.area);
+				float p_l;
+				if constexpr (LTREE) p_l = (pmf_i * dist2) / (cg * g.w);
+				else p_l = dist2 / (cg * Lt.area);
 				if constexpr (ENV) p_l = (1 - c_env) * p_l;
 				if constexpr (PUN) p_l = (1 - c_p) * p_l;
 				float pw = pe;
@@ -349,12 +454,14 @@ DEV void nee_candidate(const DevScene& S, const RenderParams& P, const NeeLights
 // RIS (PTX_NEE_CANDIDATES(m), m > 1): the light sample is chosen among ris_m candidates. Without RIS ris_m is not read and no statement changes.
 // PUN (punctual lights on the scene, Pn): a candidate may be a punctual sample, and the other strategies' densities carry (1 - c_p) in every
 // weight. Without PUN, Pn is not read and no statement changes.
+// LTREE (a non-empty list in tree mode): the emission weight's density is the directed pmf of the hit triangle seen from *x_prev, the position
+// of the vertex that drew the BSDF sample, and x_prev is set where p_prev is set. Without LTREE x_prev is not touched (nullptr).
 template <uint32_t V>
 DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, uint32_t ris_m, uint32_t pixel, uint32_t sample, int32_t surf, uint32_t tri, float b1, float b2,
                     float hit_dist, V3& o, V3& d, V3& T, V3& L, float& p_prev, uint32_t& depth, uint32_t& pass, NeeVertex& out, const NeePunctual& Pn = NeePunctual{},
-                    bool moved = false, const XformRecs& Xm = XformRecs{}) {
+                    bool moved = false, const XformRecs& Xm = XformRecs{}, V3* x_prev = nullptr) {
 	constexpr bool TEX = (V & NEE_TEX) != 0, ALPHA = (V & NEE_ALPHA) != 0, SUN = (V & NEE_SUN) != 0, ENV = (V & NEE_ENV) != 0;
-	constexpr bool SPDF = (V & NEE_SPDF) != 0, RIS = (V & NEE_RIS) != 0, PUN = (V & NEE_PUN) != 0;
+	constexpr bool SPDF = (V & NEE_SPDF) != 0, RIS = (V & NEE_RIS) != 0, PUN = (V & NEE_PUN) != 0, LTREE = (V & NEE_LTREE) != 0;
 	bool& alive = out.alive;
 	bool& want_sun = out.want_sun;
 	bool& want_light = out.want_light;
@@ -451,7 +558,9 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 				const float4 g = Lt.geom[k];
 				const float cg = fabsf(dot(mk(g.x, g.y, g.z), d));
 				const float dist = hit_dist;
-				float p_l = (dist * dist) / (cg * Lt.area);
+				float p_l;
+				if constexpr (LTREE) p_l = (light_pmf_tree(Lt, (uint32_t)k, *x_prev) * (dist * dist)) / (cg * g.w);
+				else p_l = (dist * dist) / (cg * Lt.area);
 				if constexpr (ENV) p_l = (1 - c_env) * p_l;
 				if constexpr (PUN) p_l = (1 - c_p) * p_l;
 				em = em * (p_prev / (p_prev + p_l));
@@ -506,6 +615,7 @@ DEV bool nee_vertex(const DevScene& S, const RenderParams& P, const NeeLights& L
 			const float ps = sampler_pdf(normal, outcoming, inc, roughness, spec_prob);
 			if (ps > 0 && ps < __builtin_inff()) p_prev = ps;
 		}
+		if constexpr (LTREE) *x_prev = sf.pos;
 		o = sf.pos + inc * kEps;
 		d = normalize(inc);
 		depth++;

@@ -23,17 +23,26 @@ namespace ptx {
 // The PUN variants (punctual lights on the scene) carry the punctual branch of the candidate besides the others and get 512 threads: 166-231
 // VGPRs without RIS, 184-256 with. One is too full for that: with ENV, SUN, RIS and SPDF together the global-memory variant with ALPHA spills
 // 3 VGPRs at 512, so the variants of that combination get 256 (up to 260 VGPRs). All 144 were compiled; none uses scratch.
+// The LTREE variants (a light tree over the light list) carry x_prev and the descent: 2 to 10 VGPRs over their twins, at their twins' sizes
+// but for ENV, SUN, RIS and PUN together without SPDF, whose LDS and hybrid variants spill 1 VGPR at 512 and get 256 as well.
 // -DPTX_NEE_FUSED_BLOCK=n: one size for all (measurement).
 constexpr int nee_fused_block(uint32_t V) {
 #ifdef PTX_NEE_FUSED_BLOCK
 	return PTX_NEE_FUSED_BLOCK;
 #else
 	constexpr uint32_t kFullest = NEE_PUN | NEE_RIS | NEE_SPDF | NEE_ENV | NEE_SUN;
-	return (V & kFullest) == kFullest ? 256 : (V & (NEE_TEX | NEE_SUN | NEE_ENV | NEE_RIS | NEE_PUN)) ? 512 : 768;
+	constexpr uint32_t kFullestTree = NEE_LTREE | NEE_PUN | NEE_RIS | NEE_ENV | NEE_SUN;   // the descent and x_prev fill that combination without SPDF too
+	return ((V & kFullest) == kFullest || (V & kFullestTree) == kFullestTree) ? 256 : (V & (NEE_TEX | NEE_SUN | NEE_ENV | NEE_RIS | NEE_PUN)) ? 512 : 768;
 #endif
 }
 constexpr bool nee_fused_block_fits(uint32_t V) { return nee_fused_block(V) % 64 == 0 && nee_fused_block(V) <= kBlock; }
 static_assert(nee_all_variants(nee_fused_block_fits), "whole waves, and the spill area is sized for kBlock / 64 waves per workgroup");
+constexpr bool nee_fused_tree_blocks_fit() {
+	for (uint32_t i = 0; i < kNeeVariantCount; i++)
+		if (!nee_fused_block_fits(kNeeTreeVariants.v[i])) return false;
+	return true;
+}
+static_assert(nee_fused_tree_blocks_fit(), "the tree variants too");
 
 DEV uint32_t wave_sum(uint32_t v) {
 	for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
@@ -46,11 +55,13 @@ DEV uint32_t wave_sum(uint32_t v) {
 // twin's workgroup size, so nee_fused_block holds for them too (DESIGN.md 5.7 has their rows).
 // RIS: the variants of PTX_NEE_CANDIDATES, the light sample chosen among ris_m candidates; the other variants do not read ris_m.
 // PUN: the variants for scenes with punctual lights (Pn), a third kind of candidate; the other variants do not read Pn.
+// LTREE: the variants for a non-empty light list in tree mode (kNeeTreeVariants): the lane carries x_prev, three more registers, and the
+// vertex descends the light tree; the other variants have neither.
 template <int MODE, uint32_t V>
 __global__ void __launch_bounds__(nee_fused_block(V)) k_nee_fused(DevScene S0, RenderParams P, NeeLights Lt, NeeFusedBuffers B, const ModelRec* __restrict__ t_models,
                                                               const SurfaceRec* __restrict__ t_surfaces, const SpaceRec* __restrict__ t_spaces, const uint32_t* __restrict__ t_model_space,
                                                               NeeEnv Ev, uint32_t ris_m, NeePunctual Pn) {
-	constexpr bool SUN = (V & NEE_SUN) != 0, ENV = (V & NEE_ENV) != 0, PUN = (V & NEE_PUN) != 0;
+	constexpr bool SUN = (V & NEE_SUN) != 0, ENV = (V & NEE_ENV) != 0, PUN = (V & NEE_PUN) != 0, LTREE = (V & NEE_LTREE) != 0;
 	constexpr int kThreads = nee_fused_block(V);
 	DevScene S = S0;
 	S.models = t_models; S.surfaces = t_surfaces; S.spaces = t_spaces; S.model_space = t_model_space;  // see struct Tables
@@ -70,6 +81,7 @@ __global__ void __launch_bounds__(nee_fused_block(V)) k_nee_fused(DevScene S0, R
 	uint32_t id = 0, pixel = 0, sample = 0, depth = 0, pass = 0;
 	V3 o = {0, 0, 0}, d = {0, 0, 1}, T = {1, 1, 1}, L = {0, 0, 0};
 	float p_prev = 0;
+	V3 x_prev = {0, 0, 0};   // LTREE alone: the position of the vertex that drew the BSDF sample; read at depth != 0 only, after that vertex set it
 
 	for (;;) {
 		// ---------------- idle lanes take the next unstarted ids
@@ -127,7 +139,8 @@ __global__ void __launch_bounds__(nee_fused_block(V)) k_nee_fused(DevScene S0, R
 			const int32_t surf = hit ? h.surface : -1;
 			const uint32_t tri = hit ? (h.tri & S.tri_id_mask) - S.surfaces[h.surface].tri_base : 0u;
 			NeeVertex v;
-			nee_vertex<V>(S, P, Lt, Ev, ris_m, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v, Pn);
+			nee_vertex<V>(S, P, Lt, Ev, ris_m, pixel, sample, surf, tri, hit ? h.b1 : 0.f, hit ? h.b2 : 0.f, hit ? h.dist : -1.0f, o, d, T, L, p_prev, depth, pass, v, Pn, false, XformRecs{},
+			              LTREE ? &x_prev : nullptr);
 			bool alive = v.alive;
 			// ---------------- the sun ray: occluded = any hit
 			if constexpr (SUN) {
@@ -184,13 +197,16 @@ static hipError_t set_lds(const void* fn, size_t bytes) {
 	return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-// This file is compiled once per part (nee_core.hpp: the SPDF, RIS and PUN bits of the mask), with -DPTX_NEE_PART=<part>, so that the eight
-// parts of the variants build side by side. Each compilation holds the 36 kernels of its part and defines launch_nee_fused_part<its part>;
-// part 0 holds launch_nee_fused as well, which picks the part by the mask's high bits.
+// This file is compiled once per part (nee_core.hpp: the SPDF, RIS, PUN and LTREE bits of the mask), with -DPTX_NEE_PART=<part>, so that the
+// sixteen parts of the variants build side by side: parts 0 to 7 hold kNeeVariants, parts 8 to 15 the tree variants (kNeeTreeVariants). Each
+// compilation holds the 36 kernels of its part and defines launch_nee_fused_part<its part>; part 0 holds launch_nee_fused as well, which
+// picks the part by the mask's high bits.
 #ifndef PTX_NEE_PART
-#error "nee_fused.hip is compiled once per part of the variants: -DPTX_NEE_PART=<0..7> (the Makefile's NEE_FUSED_PARTS)"
+#error "nee_fused.hip is compiled once per part of the variants: -DPTX_NEE_PART=<0..15> (the Makefile's NEE_FUSED_PARTS)"
 #endif
-static_assert(PTX_NEE_PART >= 0 && PTX_NEE_PART < (int)kNeeParts, "a part is the SPDF, RIS and PUN bits of a variant");
+constexpr uint32_t kNeeFusedParts = 2 * kNeeParts;
+static_assert(PTX_NEE_PART >= 0 && PTX_NEE_PART < (int)kNeeFusedParts, "a part is the SPDF, RIS, PUN and LTREE bits of a variant");
+static_assert(NEE_LTREE >> kNeePartShift == kNeeParts, "the tree variants are the upper half of the parts");
 
 using NeeFusedKernel = decltype(&k_nee_fused<MODE_GLOBAL, 0u>);
 struct NeeFusedTable { NeeFusedKernel fn[kNeeSceneMask + 1]; };   // by the low four bits; nullptr: no such variant
@@ -200,7 +216,7 @@ template <int MODE, size_t... I>
 static NeeFusedTable nee_fused_table(std::index_sequence<I...>) {
 	NeeFusedTable t{};
 	([&] {
-		constexpr uint32_t V = kNeeVariants.v[I];
+		constexpr uint32_t V = (PTX_NEE_PART >= (int)kNeeParts ? kNeeTreeVariants : kNeeVariants).v[I];
 		if constexpr ((V >> kNeePartShift) == PTX_NEE_PART) t.fn[V & kNeeSceneMask] = &k_nee_fused<MODE, V>;
 	}(), ...);
 	return t;
@@ -245,9 +261,9 @@ static hipError_t launch_nee_fused_in_part(std::index_sequence<PART...>, uint32_
 hipError_t launch_nee_fused(const DevScene& S, const RenderParams& P, const NeeLights& Lt, const NeeEnv& Ev, const NeePunctual& Pn, bool sampler_pdf, uint32_t candidates, const NeeFusedBuffers& B,
                             int mode, size_t lds_bytes, int grid, hipStream_t stream) {
 	uint32_t V, ris_m;
-	const hipError_t e = nee_select_variant(S, Ev, Pn, sampler_pdf, candidates, V, ris_m);
+	const hipError_t e = nee_select_variant(S, Lt, Ev, Pn, sampler_pdf, candidates, V, ris_m);
 	if (e != hipSuccess) return e;
-	return launch_nee_fused_in_part(std::make_index_sequence<kNeeParts>{}, V, S, P, Lt, Ev, Pn, ris_m, B, mode, lds_bytes, grid, stream);
+	return launch_nee_fused_in_part(std::make_index_sequence<kNeeFusedParts>{}, V, S, P, Lt, Ev, Pn, ris_m, B, mode, lds_bytes, grid, stream);
 }
 #endif
 

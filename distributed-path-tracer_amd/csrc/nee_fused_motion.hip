@@ -263,7 +263,8 @@ hipError_t launch_nee_fused_motion(const DevScene& S, const RenderParams& P, con
 	if (!Mo.active) return hipErrorInvalidValue;
 	if (Mo.models_moved && (!Mo.models.begin_xform || !Mo.models.end_xform || !Mo.models.moved)) return hipErrorInvalidValue;
 	uint32_t V, ris_m;
-	const hipError_t e = nee_select_variant(S, Ev, Pn, sampler_pdf, candidates, V, ris_m);
+	const hipError_t e = nee_select_variant(S, Lt, Ev, Pn, sampler_pdf, candidates, V, ris_m);
+	if (e == hipSuccess && (V & NEE_LTREE)) return hipErrorInvalidValue;   // no tree variants of this kernel: the host runs the unfused form in tree mode
 	if (e != hipSuccess) return e;
 	return launch_nee_fused_motion_in_part(std::make_index_sequence<kNeeParts>{}, V, S, P, Lt, Ev, Pn, ris_m, Mo, B, mode, lds_bytes, grid, stream);
 }

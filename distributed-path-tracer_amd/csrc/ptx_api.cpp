@@ -260,7 +260,7 @@ int upload_scene(ptx_scene* sc) {
 void release_scene_buffers(ptx_scene* sc) {
 	for (DevBuf* b : {&sc->d_models, &sc->d_surfaces, &sc->d_materials, &sc->d_nodes, &sc->d_refs, &sc->d_tris, &sc->d_shade, &sc->d_tex,
 	                  &sc->d_texels, &sc->d_texels_f, &sc->d_lut, &sc->d_spaces, &sc->d_model_space, &sc->d_surf_aux, &sc->d_wf_order, &sc->d_res_nodes, &sc->d_res_refs, &sc->d_res_tris, &sc->d_hot,
-	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_env_row, &sc->d_env_cell, &sc->d_punctual, &sc->d_punctual_cdf, &sc->d_punctual_tree, &sc->d_lens, &sc->d_motion})
+	                  &sc->d_light_tris, &sc->d_light_cdf, &sc->d_light_geom, &sc->d_light_first, &sc->d_light_tree, &sc->d_light_path, &sc->d_env_row, &sc->d_env_cell, &sc->d_punctual, &sc->d_punctual_cdf, &sc->d_punctual_tree, &sc->d_lens, &sc->d_motion})
 		b->release();
 	sc->lights.on_device = false;
 	sc->env_table.on_device = false;
@@ -337,8 +337,72 @@ int refuse_motion(const char* who) {
 	                                    "with ptx_render_aov, or clear the motion (ptx_scene_set_motion(scene, NULL)) to render the scene as it stands");
 }
 
+namespace {
+// One listed triangle as the light tree sees it (include/ptx.h: LIGHT PICK, THE TREE): the float64 centroid, the float32 box of the corners
+// and the float64 power
+struct LightLeaf {
+	double centroid[3];
+	float lo[3], hi[3];
+	double power;
+};
+// The light tree of PTX_LIGHT_PICK_TREE over the list's entries, and each entry's path word. build_punctual_tree's rule with the centroid in
+// the place of the position: FIFO splits by count along the widest axis of the centroids' bounds. A node's box holds the CORNERS below it.
+void build_light_tree(const std::vector<LightLeaf>& leaves, std::vector<uint32_t>& nodes, std::vector<uint32_t>& path) {
+	nodes.clear();
+	path.assign(leaves.size(), 0u);
+	if (leaves.empty()) return;
+	auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+	struct Pending { uint32_t node, depth, word; std::vector<uint32_t> idx; };   // word: the steps from the root so far, bit i = step i went right
+	std::deque<Pending> queue;
+	std::vector<uint32_t> root(leaves.size());
+	for (uint32_t k = 0; k < (uint32_t)leaves.size(); k++) root[k] = k;
+	nodes.resize(8);
+	queue.push_back(Pending{0u, 0u, 0u, std::move(root)});
+	while (!queue.empty()) {
+		Pending pd = std::move(queue.front());
+		queue.pop_front();
+		std::vector<uint32_t>& idx = pd.idx;
+		float lo[3], hi[3];
+		double clo[3], chi[3], power = 0;
+		for (size_t i = 0; i < idx.size(); i++) {
+			const LightLeaf& lf = leaves[idx[i]];
+			for (int a = 0; a < 3; a++) {
+				if (i == 0 || lf.lo[a] < lo[a]) lo[a] = lf.lo[a];
+				if (i == 0 || lf.hi[a] > hi[a]) hi[a] = lf.hi[a];
+				if (i == 0 || lf.centroid[a] < clo[a]) clo[a] = lf.centroid[a];
+				if (i == 0 || lf.centroid[a] > chi[a]) chi[a] = lf.centroid[a];
+			}
+			power += lf.power;
+		}
+		uint32_t w7;
+		if (idx.size() == 1) {
+			w7 = 0x80000000u | idx[0];
+			path[idx[0]] = pd.word;
+		} else {
+			int ax = 0;
+			for (int a = 1; a < 3; a++)
+				if (chi[a] - clo[a] > chi[ax] - clo[ax]) ax = a;
+			std::sort(idx.begin(), idx.end(), [&](uint32_t i, uint32_t j) {
+				const double ci = leaves[i].centroid[ax], cj = leaves[j].centroid[ax];
+				return ci < cj || (ci == cj && i < j);
+			});
+			const size_t half = idx.size() / 2;
+			w7 = (uint32_t)(nodes.size() / 8);
+			nodes.resize(nodes.size() + 16);
+			const uint32_t bit = pd.depth < 32 ? 1u << pd.depth : 0u;   // a list the render accepts (<= 2^30 entries) is at most 31 steps deep
+			queue.push_back(Pending{w7, pd.depth + 1, pd.word, std::vector<uint32_t>(idx.begin(), idx.begin() + half)});
+			queue.push_back(Pending{w7 + 1, pd.depth + 1, pd.word | bit, std::vector<uint32_t>(idx.begin() + half, idx.end())});
+		}
+		uint32_t* q = nodes.data() + 8 * (size_t)pd.node;
+		for (int a = 0; a < 3; a++) { q[a] = bits(lo[a]); q[4 + a] = bits(hi[a]); }
+		q[3] = bits((float)power);
+		q[7] = w7;
+	}
+}
+}  // namespace
+
 // The emissive triangles ptx_render_nee samples (include/ptx.h: the listing rules). World corners, areas and normals in float64 in the
-// written order, stored as float32.
+// written order, stored as float32. In tree mode (ptx_scene_set_light_pick) the light tree and the path words are built with the list.
 const ptx_scene::LightList* build_lights(ptx_scene* sc) {
 	std::lock_guard<std::mutex> lk(sc->lights_mu);
 	ptx_scene::LightList& ll = sc->lights;
@@ -348,6 +412,8 @@ const ptx_scene::LightList* build_lights(ptx_scene* sc) {
 	ll.surf_first.assign(n_surf, -1);
 	std::vector<double> cum;
 	double total = 0;
+	const bool tree_mode = sc->light_pick == PTX_LIGHT_PICK_TREE;
+	std::vector<LightLeaf> leaves;
 	for (size_t s = 0; s < n_surf; s++) {
 		const MaterialRec& m = h.materials[s];
 		if (!(m.emissive[0] > 0 || m.emissive[1] > 0 || m.emissive[2] > 0)) continue;
@@ -372,11 +438,22 @@ const ptx_scene::LightList* build_lights(ptx_scene* sc) {
 			ll.geom.push_back((float)area);
 			total += area;
 			cum.push_back(total);
+			if (tree_mode) {
+				LightLeaf lf;
+				for (int a = 0; a < 3; a++) {
+					lf.centroid[a] = ((c[0][a] + c[1][a]) + c[2][a]) / 3.0;
+					lf.lo[a] = (float)std::min(c[0][a], std::min(c[1][a], c[2][a]));
+					lf.hi[a] = (float)std::max(c[0][a], std::max(c[1][a], c[2][a]));
+				}
+				lf.power = area * ((0.2126 * (double)m.emissive[0] + 0.7152 * (double)m.emissive[1]) + 0.0722 * (double)m.emissive[2]);
+				leaves.push_back(lf);
+			}
 		}
 	}
 	for (double v : cum) ll.cdf.push_back((float)(v / total));
 	if (!ll.cdf.empty()) ll.cdf.back() = 1.0f;
 	ll.area = (float)total;
+	if (tree_mode) build_light_tree(leaves, ll.tree, ll.path);
 	ll.built = true;
 	return &ll;
 }
@@ -684,6 +761,26 @@ int ptx_scene_get_punctual_pick(const ptx_scene* sc, uint32_t* pick) {
 	if (!sc || !pick) return set_err(PTX_ERR_INVALID, "ptx_scene_get_punctual_pick: NULL argument");
 	std::lock_guard<std::mutex> tl(const_cast<ptx_scene*>(sc)->lights_mu);
 	*pick = sc->punctual_pick;
+	return PTX_OK;
+}
+
+int ptx_scene_set_light_pick(ptx_scene* sc, uint32_t pick) {
+	// no device work: the list and the tree are rebuilt at the next request and uploaded by the next ptx_render_nee
+	if (!sc) return set_err(PTX_ERR_INVALID, "ptx_scene_set_light_pick: scene is NULL");
+	if (pick != PTX_LIGHT_PICK_CDF && pick != PTX_LIGHT_PICK_TREE) return set_err(PTX_ERR_INVALID, "ptx_scene_set_light_pick: unknown mode");
+	std::unique_lock<std::mutex> lk;
+	if (sc->ctx) lk = std::unique_lock<std::mutex>(sc->ctx->mu);   // no render of this scene is in flight
+	std::lock_guard<std::mutex> tl(sc->lights_mu);
+	if (pick == sc->light_pick) return PTX_OK;
+	sc->light_pick = pick;
+	sc->lights = ptx_scene::LightList{};   // the tree lives and dies with the list: both are built anew, the list bit for bit as before
+	return PTX_OK;
+}
+
+int ptx_scene_get_light_pick(const ptx_scene* sc, uint32_t* pick) {
+	if (!sc || !pick) return set_err(PTX_ERR_INVALID, "ptx_scene_get_light_pick: NULL argument");
+	std::lock_guard<std::mutex> tl(const_cast<ptx_scene*>(sc)->lights_mu);
+	*pick = sc->light_pick;
 	return PTX_OK;
 }
 
@@ -1011,6 +1108,8 @@ int64_t ptx_scene_get_array(const ptx_scene* sc, ptx_array which, void* dst, siz
 	case PTX_ARR_TEXELS_F32: src = h.texels_f.data(); bytes = h.texels_f.size() * 4; break;
 	case PTX_ARR_LIGHT_TRIS: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.tris.data(); bytes = ll.tris.size() * 4; break; }
 	case PTX_ARR_LIGHT_CDF: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.cdf.data(); bytes = ll.cdf.size() * 4; break; }
+	case PTX_ARR_LIGHT_TREE: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.tree.data(); bytes = ll.tree.size() * 4; break; }
+	case PTX_ARR_LIGHT_PATH: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.path.data(); bytes = ll.path.size() * 4; break; }
 	case PTX_ARR_LIGHT_GEOM: { const auto& ll = *build_lights(const_cast<ptx_scene*>(sc)); src = ll.geom.data(); bytes = ll.geom.size() * 4; break; }
 	case PTX_ARR_ENV_ROW_CDF: { const auto& et = *build_env_table(const_cast<ptx_scene*>(sc)); src = et.row_cdf.data(); bytes = et.row_cdf.size() * 4; break; }
 	case PTX_ARR_ENV_CELL_CDF: { const auto& et = *build_env_table(const_cast<ptx_scene*>(sc)); src = et.cell_cdf.data(); bytes = et.cell_cdf.size() * 4; break; }

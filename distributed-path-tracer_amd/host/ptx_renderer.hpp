@@ -100,6 +100,36 @@ public:
 		check(ptx_scene_get_punctual_pick(scene_, &pick));
 		return pick;
 	}
+	// How a light sample picks its emissive triangle (ptx_scene_set_light_pick): PTX_LIGHT_PICK_CDF, the default, or PTX_LIGHT_PICK_TREE, a
+	// light tree over the light list descended from the shading point. The mode outlives the light list.
+	void set_light_pick(uint32_t pick) {
+		if (!scene_) throw std::runtime_error("set_light_pick() before load_gltf()");
+		check(ptx_scene_set_light_pick(scene_, pick));
+	}
+	uint32_t light_pick() const {
+		if (!scene_) throw std::runtime_error("light_pick() before load_gltf()");
+		uint32_t pick = 0;
+		check(ptx_scene_get_light_pick(scene_, &pick));
+		return pick;
+	}
+	// The stochastic pick alone for n (position, u) records of 4 floats, host memory (ptx_light_pick_batch) -> the list entries; pmf receives
+	// their probabilities
+	std::vector<int32_t> light_pick_batch(const std::vector<float>& pos_u, std::vector<float>& pmf) const {
+		if (!scene_) throw std::runtime_error("light_pick_batch() before load_gltf()");
+		if (pos_u.size() % 4) throw std::runtime_error("light_pick_batch: the records are 4 floats each");
+		std::vector<int32_t> light(pos_u.size() / 4);
+		pmf.assign(light.size(), 0.0f);
+		check(ptx_light_pick_batch(scene_, pos_u.data(), light.size(), light.data(), pmf.data()));
+		return light;
+	}
+	// pmf_k(x) for n positions of 3 floats and n list entries, host memory (ptx_light_pmf_batch)
+	std::vector<float> light_pmf_batch(const std::vector<float>& pos, const std::vector<int32_t>& light) const {
+		if (!scene_) throw std::runtime_error("light_pmf_batch() before load_gltf()");
+		if (pos.size() != 3 * light.size()) throw std::runtime_error("light_pmf_batch: three floats per entry");
+		std::vector<float> pmf(light.size(), 0.0f);
+		check(ptx_light_pmf_batch(scene_, pos.data(), light.data(), light.size(), pmf.data()));
+		return pmf;
+	}
 	// The pick alone for n (position, u) records of 4 floats, host memory (ptx_punctual_pick_batch) -> the lights; pmf receives their probabilities
 	std::vector<int32_t> punctual_pick_batch(const std::vector<float>& pos_u, std::vector<float>& pmf) const {
 		if (!scene_) throw std::runtime_error("punctual_pick_batch() before load_gltf()");

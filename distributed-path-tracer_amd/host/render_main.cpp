@@ -1,6 +1,6 @@
 // Minimal C++ host over the mirror class: what path-tracer-core/src/main.cpp + worker.cpp reduce to once the
 // Lambda / S3 plumbing (out of scope) is taken away:
-//   ptx_render_cli [--transparent] [--denoise] [--split-emission] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--nee-punctual-tree] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
+//   ptx_render_cli [--transparent] [--denoise] [--split-emission] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--nee-punctual-tree] [--nee-light-tree] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]
 //       --transparent: renderer::transparent_background
 //       --denoise:     writes the frame through the variance-guided a-trous filter (renderer::render_denoised) in place of the plain one
 //       --split-emission: with --denoise, alone or with --adaptive (with or without --nee*): the first-hit emission of the guides' samples is
@@ -20,6 +20,9 @@
 //                      are read and set on the scene, and the light sample takes them as a third strategy; without --nee it is an error
 //       --nee-punctual-tree: --nee-punctual with the light of a punctual sample picked from a light tree by its distance from the shading point
 //                      (renderer::set_punctual_pick, PTX_PUNCTUAL_PICK_TREE) instead of by intensity alone; implies --nee-punctual
+//       --nee-light-tree: implies --nee: the emissive triangle of a light sample is picked from a light tree over the light list by its power and
+//                      distance from the shading point (renderer::set_light_pick, PTX_LIGHT_PICK_TREE) instead of by area alone. Combines
+//                      with every other --nee switch; with --nee-fused the fused kernel's tree variants render
 //       combinations:  --adaptive with --nee / --nee-fused / --nee-env / --nee-sampler-pdf / --nee-candidates renders the adaptive loop on the light-sampling estimator
 //                      (renderer::render_adaptive_nee); --adaptive --denoise, with or without --nee*, filters the adaptive frame
 //                      (ptx_denoise_counts on the guides of the first MIN samples); --nee* --denoise filters two light-sampled half-frames
@@ -56,7 +59,7 @@ static void write_png(const std::string& path, const std::vector<uint8_t>& rgba,
 
 int main(int argc, char** argv) {
 	bool split_emission = false;
-	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false, nee_sampler_pdf = false, nee_punctual = false, nee_punctual_tree = false;
+	bool transparent = false, denoise = false, adaptive = false, nee = false, nee_fused = false, nee_sampler_pdf = false, nee_punctual = false, nee_punctual_tree = false, nee_light_tree = false;
 	float ad_thr = 0.1f;
 	unsigned ad_min = 8, ad_step = 0, nee_candidates = 1;
 	std::string aov_prefix, nee_env;
@@ -70,6 +73,7 @@ int main(int argc, char** argv) {
 		else if (argc > 1 && std::string(argv[1]) == "--nee-fused") { nee = nee_fused = true; argv[1] = argv[0]; argv++; argc--; }   // ... one launch per pass
 		else if (argc > 1 && std::string(argv[1]) == "--nee-sampler-pdf") { nee = nee_sampler_pdf = true; argv[1] = argv[0]; argv++; argc--; }   // ... weights on the sampler's density
 		else if (argc > 1 && std::string(argv[1]) == "--nee-punctual") { nee_punctual = true; argv[1] = argv[0]; argv++; argc--; }   // ... the file's point and spot lights too; does not imply --nee
+		else if (argc > 1 && std::string(argv[1]) == "--nee-light-tree") { nee = nee_light_tree = true; argv[1] = argv[0]; argv++; argc--; }   // ... the triangle picked from the light tree
 		else if (argc > 1 && std::string(argv[1]) == "--nee-punctual-tree") { nee_punctual = nee_punctual_tree = true; argv[1] = argv[0]; argv++; argc--; }   // ... picked from the light tree
 		else if (argc > 2 && std::string(argv[1]) == "--nee-env") { nee = true; nee_env = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }   // ... the map as a light
 		else if (argc > 2 && std::string(argv[1]) == "--nee-candidates") {   // ... picked among M candidates
@@ -93,7 +97,7 @@ int main(int argc, char** argv) {
 		else break;
 	}
 	if (argc < 3) {
-		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--split-emission] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--nee-punctual-tree] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--transparent] [--denoise] [--split-emission] [--nee] [--nee-fused] [--nee-env MAP] [--nee-sampler-pdf] [--nee-candidates M] [--nee-punctual] [--nee-punctual-tree] [--nee-light-tree] [--adaptive THR[:MIN[:STEP]]] [--lens R:F[:BLADES[:ROT]]] [--aov PREFIX] <scene.gltf> <out.png> [W H spp bounces]\n", argv[0]);
 		return 1;
 	}
 	if (nee_punctual && !nee) {
@@ -143,6 +147,7 @@ int main(int argc, char** argv) {
 		r.nee_candidates = nee_candidates;
 		r.split_emission = split_emission;
 		r.lens_radius = lens_r; r.focus_distance = lens_f; r.blades = lens_blades; r.blade_rotation = lens_rot;
+		if (nee_light_tree) r.set_light_pick(PTX_LIGHT_PICK_TREE);
 		size_t n_punctual = 0;
 		if (nee_punctual) {
 			const std::vector<float> lamps = core::renderer::read_punctual_lights(argv[1]);
@@ -202,6 +207,7 @@ int main(int argc, char** argv) {
 			            (unsigned long long)nst.light_samples, (unsigned long long)nst.light_visible, nst.render.kernel_ms);
 		if (nee_punctual) std::printf(", \"nee_punctual_lights\": %zu", n_punctual);
 		if (nee_punctual_tree) std::printf(", \"nee_punctual_pick\": \"tree\"");
+		if (nee_light_tree) std::printf(", \"nee_light_pick\": \"tree\"");
 		std::printf("}\n");
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "error: %s\n", e.what());

@@ -695,3 +695,59 @@ def movers_scene(emissive_mover: bool = False, sun: bool = False, alpha: bool = 
                 model_surf=np.array([[m[0], m[1]] for m in models], np.int32), surf_range=np.array(sr, np.int32),
                 vertices=np.concatenate(verts).astype(np.float32), triangles=np.concatenate(tris).astype(np.uint32),
                 materials=np.stack(mats), camera=cam_end, begin_camera=cam_begin, sun=sun13)
+
+
+# ---------------------------------------------------------------------------- the emitter field (many small emissive quads)
+def emitter_field_scene(n: int = 16, seed: int = 7):
+    """A diffuse floor (8 x 8 on y = 0) seen from above at an angle, lit by `n` small emissive quads facing down, for the light tree of
+    ptx_render_nee (Scene.set_light_pick): the list has 2 n triangles whose distances from a shading point differ by an order of magnitude.
+      emitters: on a jittered ceil(sqrt(n))^2 grid over |x|, |z| < 3.4, at heights 0.35 .. 1.6, half sizes 0.04 .. 0.12; emitter k belongs
+                to surface 4 + k % min(n, 8), and each of those surfaces has its own emissive factor (log-uniform over a decade), so powers
+                vary through both the area and the factor.
+      blockers: three opaque quads at y = 0.25, 0.2 and 0.3 (surfaces 1 .. 3).
+      No sun, no alpha, no textures. One model; small n keeps the scene on the LDS route.
+    -> dict of arrays as plaza_scene, plus `emitters` [n, 5]: centre x, y, z, half size, surface."""
+    rng = np.random.default_rng(seed)
+    n_es = min(n, 8)
+    surf_v = [[] for _ in range(4 + n_es)]   # per surface: its quads' vertex blocks
+    mats = [None] * (4 + n_es)
+
+    def add(s, x0, x1, z0, z1, y, up):
+        v = np.zeros((4, 11), np.float32)
+        v[:, 0:3] = [[x0, y, z0], [x1, y, z0], [x1, y, z1], [x0, y, z1]]
+        v[:, 3:5] = [[0, 0], [1, 0], [1, 1], [0, 1]]
+        v[:, 5:8] = [0, 1 if up else -1, 0]
+        v[:, 8:11] = [1, 0, 0]
+        surf_v[s].append((v, up))
+    add(0, -4, 4, -4, 4, 0.0, True)
+    mats[0] = [0.7, 0.7, 0.7, 1.0, 0.6, 0.0, 0, 0, 0, 1.33, 0]
+    for s, (x0, x1, z0, z1, y) in enumerate([(-2.6, -1.2, -0.4, 0.9, 0.25), (0.6, 2.2, -2.4, -1.3, 0.2), (0.9, 2.0, 1.2, 2.6, 0.3)], 1):
+        add(s, x0, x1, z0, z1, y, True)
+        mats[s] = [0.4, 0.5, 0.6, 1.0, 0.5, 0.0, 0, 0, 0, 1.33, 0]
+    for j in range(n_es):
+        colour = rng.uniform(0.5, 1.0, 3)
+        mats[4 + j] = [0.8, 0.8, 0.8, 1.0, 0.5, 0.0] + list(colour * 4.0 * 10.0 ** rng.uniform(-0.5, 0.5)) + [1.33, 0]
+    side = int(np.ceil(np.sqrt(n)))
+    cell = 6.8 / side
+    emitters = np.zeros((n, 5), np.float32)
+    for k in range(n):
+        cx = -3.4 + (k % side + rng.uniform(0.25, 0.75)) * cell
+        cz = -3.4 + (k // side + rng.uniform(0.25, 0.75)) * cell
+        y, hs = rng.uniform(0.35, 1.6), rng.uniform(0.04, 0.12)
+        add(4 + k % n_es, cx - hs, cx + hs, cz - hs, cz + hs, y, False)
+        emitters[k] = [cx, y, cz, hs, 4 + k % n_es]
+    verts, tris, ranges = [], [], []
+    nv = nt = 0
+    for quads in surf_v:
+        ranges.append([nv, 4 * len(quads), nt, 2 * len(quads)])
+        for q, (v, up) in enumerate(quads):
+            verts.append(v)
+            local = np.array([[0, 2, 1], [0, 3, 2]] if up else [[0, 1, 2], [0, 2, 3]], np.uint32) + np.uint32(4 * q)
+            tris.append(local)
+        nv += 4 * len(quads)
+        nt += 2 * len(quads)
+    ident = [1, 0, 0, 0, 1, 0, 0, 0, 1]
+    cam = np.concatenate([_look_at([0.0, 5.0, 4.5], [0.0, 0.0, 0.0]), [np.float32(0.8)]]).astype(np.float32)
+    return dict(model_xform=np.array([[0, 0, 0] + ident], np.float32), model_surf=np.array([[0, len(surf_v)]], np.int32),
+                surf_range=np.array(ranges, np.int32), vertices=np.concatenate(verts), triangles=np.concatenate(tris),
+                materials=np.array(mats, np.float32), camera=cam, sun=None, emitters=emitters)

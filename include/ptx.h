@@ -261,6 +261,17 @@ int64_t ptx_gltf_read_punctual_lights(const char* gltf_path, float* dst /* NULL 
 typedef enum ptx_punctual_pick { PTX_PUNCTUAL_PICK_CDF = 0, PTX_PUNCTUAL_PICK_TREE = 1 } ptx_punctual_pick;
 int ptx_scene_set_punctual_pick(ptx_scene* scene, uint32_t pick);
 int ptx_scene_get_punctual_pick(const ptx_scene* scene, uint32_t* pick);
+/* How a light sample picks its emissive triangle (LIGHT PICK below ptx_render_nee's flags has the tree, the importance, the descent and what
+ * changes in the estimator): PTX_LIGHT_PICK_CDF, the default, from the CDF over area, whatever the shading point; PTX_LIGHT_PICK_TREE by a
+ * stochastic descent of a binary tree over the light list with importance power / distance^2 seen from the shading point. Opt-in scene
+ * state, independent of the punctual mode: a scene on which the setter was never called, or was last called with CDF, runs the same kernels
+ * and renders every bit as before. Works on host-only scenes and does no device work. The mode outlives the light list: the tree
+ * (PTX_ARR_LIGHT_TREE, PTX_ARR_LIGHT_PATH) is built together with the list at the first request, dropped with it by whatever drops the list
+ * (ptx_scene_set_model_xforms, ptx_scene_set_motion both ways, and a change of this mode), rebuilt with it and uploaded with it.
+ * PTX_ERR_INVALID for a NULL scene (or a NULL `pick` of the getter) and for an unknown mode; a refused call leaves the mode as it was. */
+typedef enum ptx_light_pick { PTX_LIGHT_PICK_CDF = 0, PTX_LIGHT_PICK_TREE = 1 } ptx_light_pick;
+int ptx_scene_set_light_pick(ptx_scene* scene, uint32_t pick);
+int ptx_scene_get_light_pick(const ptx_scene* scene, uint32_t* pick);
 
 typedef struct ptx_scene_info {
 	uint32_t n_models, n_surfaces, n_vertices, n_triangles;
@@ -326,7 +337,11 @@ typedef enum ptx_array {
 	PTX_ARR_MOTION_MOVED = 34, /* uint32[n_models]: 1 = the model moves */
 	PTX_ARR_MOTION_CAMERA = 35,/* float[15]: begin origin, begin basis (the current camera's when it does not move), camera-moved flag, open, close */
 	/* the light tree of ptx_scene_set_punctual_pick (host-only scenes too) */
-	PTX_ARR_PUNCTUAL_TREE = 36 /* uint32[n_nodes][8], bit patterns: lo.xyz, power, hi.xyz, word 7; empty in CDF mode and without lights */
+	PTX_ARR_PUNCTUAL_TREE = 36,/* uint32[n_nodes][8], bit patterns: lo.xyz, power, hi.xyz, word 7; empty in CDF mode and without lights */
+	/* the light tree over the light list of ptx_scene_set_light_pick (built with the list, on host-only scenes too; both empty in CDF mode
+	 * and with an empty list) */
+	PTX_ARR_LIGHT_TREE = 37,   /* uint32[n_nodes][8], bit patterns: lo.xyz, power, hi.xyz, word 7 (LIGHT PICK below ptx_render_nee's flags) */
+	PTX_ARR_LIGHT_PATH = 38    /* uint32[n_lights]: the path word of each listed triangle: bit i = step i of the descent to its leaf goes right */
 } ptx_array;
 int64_t ptx_scene_get_array(const ptx_scene* scene, ptx_array which, void* dst, size_t dst_bytes);
 
@@ -925,6 +940,8 @@ int ptx_ctx_get_mask_exchange_stats(ptx_ctx* ctx, uint64_t* calls /* NULL ok */,
  *   Without PTX_NEE_FUSED the bit is accepted and does nothing. With PTX_NEE_FUSED but no active motion (never set, all keys equal, or
  *   cleared) the call is the PTX_NEE_FUSED call: the same kernels, bits and fused_launches. On the queue route it is ignored as
  *   PTX_NEE_FUSED is (fused_launches == 0). PTX_NEE_FUSED alone under active motion stays ignored: a caller opts in to the motion kernel.
+ *   With a non-empty light list in tree mode (ptx_scene_set_light_pick, LIGHT PICK below) under active motion both bits together are
+ *   ignored in the same way (fused_launches == 0): the motion kernel has no tree variants, and the unfused form runs the tree.
  * Combines with every other flag and with PTX_NEE_CANDIDATES(m); ptx_render_adaptive_nee passes it through, and its rounds then run fused
  * launches. The light-list rule (a surface of a moving model is not listed) and every refusal under active motion are unchanged.
  * PTX_NEE_NO_LIGHT_SAMPLES | PTX_NEE_FUSED | PTX_NEE_FUSED_MOTION is ptx_render's estimator under a shutter in one launch per pass.
@@ -984,7 +1001,56 @@ int ptx_ctx_get_mask_exchange_stats(ptx_ctx* ctx, uint64_t* calls /* NULL ok */,
  *   EXPECTATION. The pmf is a function of x alone and positive wherever E_k(x) > 0 (a leaf with I > 0 has p > 0 at every branch above it),
  *     so the punctual term stays unbiased for the sum over the lights. What falls is the variance; DESIGN.md 5.13 has the measurement.
  *   Out of scope: emissive triangles in the tree (their MIS weights need the pick's density from the previous vertex), orientation and cone
- *     bounds in the branches, the receiver's cosine, a tree for the environment map, lights that move under a shutter. */
+ *     bounds in the branches, the receiver's cosine, a tree for the environment map, lights that move under a shutter.
+ * LIGHT PICK (ptx_scene_set_light_pick, PTX_LIGHT_PICK_TREE). The CDF over area picks a small emitter across the scene as often as an equal
+ * one a hand's breadth away. In tree mode with a non-empty list exactly three things change in the text of ptx_render_nee: the LIGHT
+ * SAMPLE's triangle and density, the EMISSION WEIGHT's density, and the path state, which gains x_prev. ENV, SPDF, RIS, PUN, the draws, the
+ * blocks, the visibility rule, the counters and the order of the additions stay as they are. With an empty list (or
+ * PTX_NEE_NO_LIGHT_SAMPLES) the mode is ignored bit for bit. IEEE binary32, each operation rounded on its own, in the order written.
+ *   THE TREE (PTX_ARR_LIGHT_TREE, PTX_ARR_LIGHT_PATH), built on the host with the light list, deterministic. The leaves are the entries
+ *     of the list, in list order. Per entry, in float64 from the float64 world corners c0, c1, c2 of THE LIGHT LIST: centroid =
+ *     ((c0 + c1) + c2) / 3; the box of the three corners; power_k = area_k * lum, lum = (0.2126 r + 0.7152 g) + 0.0722 b of the float32
+ *     emissive factor. Every listed surface has a positive component, so every leaf's power is positive. The emissive TEXTURE is not
+ *     consulted. A node is 8 words: lo.xyz (0-2) and hi.xyz (4-6), the float32 bounds of the CORNERS below it (each corner coordinate
+ *     rounded to float32, then the minimum and maximum); power (3), the float64 sum in the node's entry order, stored as float32; word 7 =
+ *     0x80000000 | list entry for a leaf, for a branch the index of its left child, whose right sibling is the next node. The root is node
+ *     0 over the entries in list order. Nodes are split in FIFO order. A node over one entry is a leaf. Otherwise the axis is the largest
+ *     extent of the bounds of the float64 centroids below it, the lowest axis winning a tie; the entries are sorted by (centroid[axis],
+ *     index); the first count / 2 (integer division) go left, in that order, the others right; the two children take the next two free
+ *     slots, left first. m entries give 2 m - 1 nodes and a depth of at most ceil(log2 m) + 1. Bit i of path[k] is 1 iff step i of the
+ *     descent from the root to leaf k goes right. A list of more than 2^30 entries is refused in tree mode at the render
+ *     (PTX_ERR_UNSUPPORTED).
+ *   THE IMPORTANCE of node N seen from x, ONE formula for leaves and branches: c = (lo + hi) * 0.5F, d = x - c, h = (hi - lo) * 0.5F,
+ *     I = power / max(dot(d, d), dot(h, h)), dot the device's (a.x b.x + a.y b.y) + a.z b.z. I is positive everywhere, so every listed
+ *     triangle has a positive pmf wherever the product is finite and does not underflow. There is no orientation term: the sample's own
+ *     conditions (dot(n_y, -w) > 0, cg > 0) may reject a picked triangle, which costs variance, not expectation.
+ *   THE PICK from x with draw u is PUNCTUAL PICK's loop, word for word: node = 0, pmf = 1; while node is a branch with children l and
+ *     l + 1: s = I_l + I_r; p = I_l / s, or 0.5F if s is not a positive finite number. If u < p: pmf = pmf * p, u = u / p, go left.
+ *     Otherwise q1 = 1 - p, pmf = pmf * q1, u = (u - p) / q1, go right. Then u = min(u, 0x1.fffffep-1F). The leaf's entry is i.
+ *   THE DIRECTED PMF pmf_k(x) is the same loop from the root, taking at step j the side that bit j of path[k] names and multiplying the
+ *     same p or q1 = 1 - p in the same order (one device function gives p to both): bit for bit the pmf THE PICK returns whenever it
+ *     returns k.
+ *   LIGHT SAMPLE. Triangle i and pmf_i come from THE PICK at pos_x with u = r.x of the candidate's light block, instead of the CDF. No
+ *     contribution unless additionally pmf_i > 0. p_l = (pmf_i * dist2) / (cg * A_i), A_i the stored float32 area geom[i].w; this replaces
+ *     dist2 / (cg * A_total). The (1 - c_env) and (1 - c_p) factors then apply from the left, as the conventions say.
+ *   EMISSION WEIGHT. For a listed hit triangle k at depth != 0 && pass == 0: p_l = (pmf_k(x_prev) * (dist * dist)) / (cg * A_k), then the
+ *     same factors. x_prev is the pos_x of the vertex that drew the BSDF sample. If p_l == 0, w is 1 as the formula gives it: the light
+ *     side never samples the triangle from there.
+ *   PATH STATE. x_prev joins the path state and is set where p_prev is set (a pass-through vertex leaves both alone).
+ *   CANDIDATES. Under PTX_NEE_CANDIDATES every candidate descends with its own r.x. The BSDF-side p_l stays a single candidate's density.
+ *   ONE TRIANGLE. The root is a leaf and pmf = 1.0F; 1 * dist2 and A_0 == A_total are exact, so the frame is bitwise the CDF mode's.
+ *   FORMS. Both forms run the tree, in variants of their own (a fourth part bit of the variant mask, NEE_LTREE): the unfused form carries
+ *     x_prev in three more stream words per path, allocated and touched in tree mode only; the fused form in three registers per lane, in
+ *     the tree variants only. With PTX_NEE_FUSED the frame and the stats equal the unfused call's, as in CDF mode. No kernel of the CDF
+ *     mode changes (DESIGN.md 5.14 has the register table of the tree variants). Under ACTIVE MOTION the fused motion kernel is not
+ *     extended: with a non-empty list in tree mode PTX_NEE_FUSED | PTX_NEE_FUSED_MOTION is ignored as PTX_NEE_FUSED alone is
+ *     (fused_launches == 0), and the unfused form runs the tree. With an empty list, PTX_NEE_NO_LIGHT_SAMPLES or CDF mode the flags act
+ *     as before.
+ *   EXPECTATION. pmf_i(x) is a function of x alone, positive for every listed triangle; the light-side density p_l is the true density of
+ *     the direction, and the BSDF-side weight evaluates the same function at the same x: the two weights add to one over the shared
+ *     directions, and the estimator's expectation is the CDF mode's.
+ *   Out of scope: orientation or normal cones in the nodes; the receiver's cosine in the importance; textured emission in the power; the
+ *     tree inside k_nee_fused_motion; emitters on moving models (unlisted, as before); a tree over the environment map. */
 typedef struct ptx_nee_cfg { uint32_t flags; } ptx_nee_cfg;
 typedef struct ptx_nee_stats {
 	ptx_render_stats render;   /* rays = closest-hit + shadow queries */
@@ -1079,6 +1145,18 @@ int ptx_camera_lens_rays_batch(ptx_scene* scene, const float* in, size_t n, floa
  * device or host, all of one kind. The lights (and the tree) are uploaded if a change is pending. PTX_ERR_NO_DEVICE on a host-only scene;
  * PTX_ERR_INVALID for a NULL scene, NULL pointers with n > 0, mixed kinds and a scene without stored lights. */
 int ptx_punctual_pick_batch(ptx_scene* scene, const float* pos_u /* [n][4]: position, u */, size_t n, int32_t* light /* [n] */, float* pmf /* [n] */);
+/* The entry of the light list a triangle sample at position x with draw u picks, and its pmf (LIGHT PICK): the stochastic pick alone,
+ * evaluated by the same device function the integrator inlines, in the scene's mode. In CDF mode the position is ignored: the first entry
+ * of the stored CDF with u below it (clamped to the last), and the difference of the stored entries. pos_u [n][4]: x(3), u; light [n],
+ * pmf [n]. Pointer kinds, the upload of pending state and the refusals are those of ptx_punctual_pick_batch: PTX_ERR_NO_DEVICE on a
+ * host-only scene; PTX_ERR_INVALID for a NULL scene, NULL pointers with n > 0, mixed pointer kinds and an empty light list. */
+int ptx_light_pick_batch(ptx_scene* scene, const float* pos_u /* [n][4]: position, u */, size_t n, int32_t* light /* [n] */, float* pmf /* [n] */);
+/* pmf_k(x), the probability with which the pick above returns list entry k = light[i] from position x = pos[i]: the directed evaluation the
+ * emission weight inlines. In tree mode it walks the path word of k from the root and multiplies the same branch probabilities in the same
+ * order, so it is bit for bit the pmf that ptx_light_pick_batch returns whenever it returns k. In CDF mode the difference of the stored
+ * entries. Refusals as above, and PTX_ERR_INVALID for a host `light` entry outside the list (device entries are the caller's to keep
+ * inside; an entry outside the list gives pmf 0 and reads nothing). */
+int ptx_light_pmf_batch(ptx_scene* scene, const float* pos /* [n][3] */, const int32_t* light /* [n] */, size_t n, float* pmf /* [n] */);
 
 /* Batch form of core::material::get_normal / get_albedo / get_opacity / get_roughness / get_metallic / get_emissive (LIB/core/material.cpp:6-53,
  * bilinear image_texture::sample lookups): what the shading kernels compute at a hit, evaluated by the same device function.

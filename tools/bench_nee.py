@@ -42,6 +42,16 @@
                                         seed: ptx_render cannot see the lamps; a tree row also has the error of the CDF call (M = 1, same form) at
                                         the spp that takes the tree call's time. The lines are the first part of
                                         profiles/nee_punctual_tree_bench.txt (profiles/nee_punctual_bench.txt: the CDF rows before the tree existed).
+  tools/bench_nee.py --light-tree [ref_spp] [reps] [spp] [W H]
+                                        The emissive triangle of a light sample picked from the light tree over the light list
+                                        (Scene.set_light_pick("tree")) against the CDF over area, on procedural.emitter_field_scene with 16 and
+                                        with 256 emitters and on procedural.emitter_cloud_scene (271 listed triangles), at 1920 x 1080 (or W H),
+                                        8 bounces, 16 spp, with and without PTX_NEE_FUSED, at M = 1 and M = 4. The eight calls of a scene alternate
+                                        in one process, each kept at the smallest of `reps` synchronised calls after a warm-up. Per row: the time,
+                                        light rays traced per sample, and the mean squared error of the written bytes against a ref_spp (1024)
+                                        frame of the SAME call (unfused, CDF, M = 1) of another seed; a tree row also has the error of the CDF call
+                                        (same form, same M) at the spp that takes the tree call's time. Also writes the lines to
+                                        profiles/nee_light_tree_bench.txt.
   tools/bench_nee.py --motion [reps] [spp]
                                         Motion blur (Scene.set_motion): the unfused ptx_render_nee with the motion active against the same call
                                         without motion, on Cornell with one box moving and on procedural.movers_scene (its camera moving too),
@@ -370,6 +380,65 @@ def main_punctual(ref_spp, reps, spp):
         tree.close()
 
 
+def main_light_tree(ref_spp, reps, spp, w, h):
+    import torch
+    ctx = ptx.Context(0)
+    lines = []
+
+    def buf():
+        t = torch.zeros((h, w, 4), device="cuda:0")
+        torch.cuda.synchronize()   # the fill runs on torch's stream, the library on its own
+        return t
+    for name, d in (("emitter_field_16", proc.emitter_field_scene(16)), ("emitter_field_256", proc.emitter_field_scene(256)),
+                    ("emitter_cloud", proc.emitter_cloud_scene())):
+        # one scene per mode, so that no call of the alternation builds or uploads anything
+        scene_of = {"cdf": ptx.Scene.from_arrays(ctx, *[d[k] for k in KEYS]), "tree": ptx.Scene.from_arrays(ctx, *[d[k] for k in KEYS])}
+        scene_of["tree"].set_light_pick("tree")
+        ref_acc = buf()
+        scene_of["cdf"].render_nee(w, h, ref_spp, BOUNCES, accum=ref_acc, seed=REF_SEED, want_stats=False)
+        ctx.synchronize()
+        ref = ctx.tonemap_encode(ref_acc, w, h, ref_spp)[..., :3].astype(np.float64) / 255
+        del ref_acc
+        forms = {(form, pick, m): base | ptx.NEE_CANDIDATES(m) for form, base in (("fused", ptx.NEE_FUSED), ("unfused", 0))
+                 for pick in ("tree", "cdf") for m in (1, 4)}
+
+        def mse_of(a, n):
+            return float(np.mean((ctx.tonemap_encode(a, w, h, n)[..., :3].astype(np.float64) / 255 - ref) ** 2))
+
+        def timed(forms, n):
+            best, acc, st, launches = {k: 1e30 for k in forms}, {}, {}, {}
+            for r in range(reps + 1):
+                for k, flags in forms.items():
+                    a = buf()
+                    t0 = time.perf_counter()
+                    _, st[k] = scene_of[k[1]].render_nee(w, h, n, BOUNCES, accum=a, seed=SEED, flags=flags)
+                    ctx.synchronize()
+                    dt = time.perf_counter() - t0
+                    if r:
+                        best[k] = min(best[k], dt)
+                    acc[k], launches[k] = a, ctx.timing()["fused_launches"]
+            return best, acc, st, launches
+        best, acc, st, launches = timed(forms, spp)
+        for k, sec in best.items():
+            form, pick, m = k
+            row = dict(scene=name, form=form, pick=pick, M=m, W=w, H=h, bounces=BOUNCES, spp=spp, n_lights=st[k]["n_lights"], fused_launches=launches[k],
+                       s=round(sec, 4), msamples_s=round(w * h * spp / sec / 1e6, 1), rays=st[k]["rays"],
+                       light_samples_per_sample=round(st[k]["light_samples"] / st[k]["samples"], 4),
+                       light_visible_per_sample=round(st[k]["light_visible"] / st[k]["samples"], 4), mse=mse_of(acc[k], spp), ref_spp=ref_spp)
+            if pick == "tree":   # what the CDF call (same form, same M) reaches in the tree call's time
+                eq_key = (form, "cdf", m)
+                spp_eq = max(1, int(round(spp * sec / best[eq_key])))
+                eq_best, eq_acc, _, _ = timed({eq_key: forms[eq_key]}, spp_eq)
+                row.update(time_ratio_to_cdf=round(sec / best[eq_key], 4), cdf_equal_time_spp=spp_eq, cdf_equal_time_s=round(eq_best[eq_key], 4),
+                           cdf_equal_time_mse=mse_of(eq_acc[eq_key], spp_eq))
+            lines.append(json.dumps(row))
+            print(lines[-1], flush=True)
+        for sc in scene_of.values():
+            sc.close()
+    with open(os.path.join(ROOT, "profiles", "nee_light_tree_bench.txt"), "w") as f:
+        f.write("tools/bench_nee.py --light-tree: the light tree over the light list against the CDF over area, fused and unfused, MI355X\n" + "\n".join(lines) + "\n")
+
+
 def main_motion(reps, spp):
     ctx = ptx.Context(0)
     lines = []
@@ -434,6 +503,10 @@ def main_motion(reps, spp):
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--motion":
         main_motion(int(sys.argv[2]) if len(sys.argv) > 2 else 5, int(sys.argv[3]) if len(sys.argv) > 3 else 16)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "--light-tree":
+        av = [int(x) for x in sys.argv[2:]]
+        main_light_tree(av[0] if len(av) > 0 else 1024, av[1] if len(av) > 1 else 3, av[2] if len(av) > 2 else 16, av[3] if len(av) > 4 else W, av[4] if len(av) > 4 else H)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--punctual":
         main_punctual(int(sys.argv[2]) if len(sys.argv) > 2 else 1024, int(sys.argv[3]) if len(sys.argv) > 3 else 3, int(sys.argv[4]) if len(sys.argv) > 4 else 16)
